@@ -3,6 +3,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR      # + the last timed step's SR frames as DIR/<name>.npy (float32)
 
 Workload = BASELINE.json configs[1]: PFNL 4xSR, 7 LR frames 128x128 -> one 512x512 HR frame per clip,
 batch 4 clips per GPU, fp32, synthetic U[0,1) clips and seeded Xavier weights (no checkpoint/dataset
@@ -237,6 +238,29 @@ def blocks_sampled(nb):
     """PF blocks that carry events in sampled profiling (pfnl_amd/csrc/capi.hip, prof_sampled): blocks 3, 13, ... from ten blocks
     up, every 4th below."""
     return len([i for i in range(nb) if (i % 10 == 3 if nb >= 10 else i % 4 == 0)]) or 1
+
+
+DUMP_LIMIT_BYTES = 64 << 20                                        # --dump-outputs: all ranks' files together
+
+
+def dump_output(out, dump_dir, name, budget):
+    """Writes the forward's output [B,1,sH,sW,3] (float32) as dump_dir/<name>.npy.  An output larger than `budget` bytes is cut
+    to a fixed, seeded choice of whole clips (in clip order); the record says which clips were kept."""
+    import numpy as np
+    a = out.detach().float().cpu().numpy()
+    per_clip = a[0].nbytes if a.shape[0] else 1
+    keep = list(range(a.shape[0]))
+    if a.nbytes > budget:
+        n = max(1, int(budget // per_clip))
+        keep = sorted(np.random.default_rng(0).choice(a.shape[0], size=n, replace=False).tolist())
+        a = a[keep]
+        if a.nbytes > budget:                                          # one clip alone is over the budget: a seeded sample of its values
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, size=int(budget // 4), replace=False))
+            a = flat[idx]
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"file": name + ".npy", "shape": list(a.shape), "dtype": "float32", "full_shape": list(out.shape), "clips": keep}
 
 
 def timed_steps(step, fence, steps):
@@ -511,7 +535,12 @@ def main():
                     help="HIP events around every launch of the timed steps (default: the launches of one of the twenty progressive-fusion "
                          "blocks; the whole-forward breakdown from an untimed pass)")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events (no roofline object)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the SR frames a caller of the forward receives) "
+                         "as DIR/output.npy (DIR/output_rank<r>.npy with N > 1), float32, at most 64 MB over all ranks")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     wl = WORKLOADS[args.workload]
     H, W, T_WL = wl["H"], wl["W"], wl["T"]
 
@@ -675,6 +704,9 @@ def main():
     eng.profile(prof_mode)
     elapsed = timed_steps(step, fence, args.steps)
     eng.profile(False)
+    dumped = None
+    if args.dump_outputs:                                              # the last timed step's result, before anything else writes `out`
+        dumped = dump_output(out, args.dump_outputs, "output" if world == 1 else "output_rank%d" % rank, DUMP_LIMIT_BYTES // world)
     prof = eng.profile_read()
     prof_all, n_all = None, 0
     if prof_mode == 3 or (small_shape and not args.no_profile and not args.full_profile):
@@ -741,6 +773,8 @@ def main():
                           "tflops_direct_shared_base": round(f_exec / (ms_per_step * 1e-3) / 1e12, 2),
                           "kernel_ms_per_step": breakdown},
     }
+    if dumped is not None:
+        res["dump_outputs"] = dict(dumped, dir=os.path.abspath(args.dump_outputs))
 
     if not args.no_secondary:
         # ---- sustained: >= 2 s of back-to-back steps, no events (clock droop shows up as ms/step above the headline's)

@@ -147,37 +147,60 @@ def test_bench_self_spawn():
     assert rec["n_gpus"] == 2 and rec["config"]["global_batch"] == 8 and rec["value"] > 0
 
 
-def _cfg2_worker(rank, world, port, q):
+def _cfg2_shard(weights, shard, q):
+    sys.path.insert(0, ROOT)
+    from pfnl_amd.engine import PFNLEngine
+    eng = PFNLEngine(PFNLGeometry(), device=0)
+    eng.load_weights(weights)
+    q.put(eng.forward(shard))
+    eng.close()
+
+
+def _cfg2_worker(rank, world, port, gpu_slots, q):
+    """One of eight gloo ranks.  The rank itself never opens the GPU: its engine runs in a child process of its own that exits
+    once the shard is computed, and a rank starts that child only while one of the `gpu_slots` is free - eight ranks plus the
+    test's own process would otherwise hold the one device at the same time."""
+    import torch.multiprocessing as mp
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     sys.path.insert(0, ROOT)
     import torch.distributed as dist
-    from pfnl_amd.engine import PFNLEngine
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         g = PFNLGeometry()                                             # the full 20-block model
         w = pd.broadcast_weights(g, synth.synthetic_weights(g, seed=0) if rank == 0 else None, src=0)
-        eng = PFNLEngine(g, device=0)
-        eng.load_weights(w)
+        ctx = mp.get_context("spawn")
+
+        def forward(shard):                                            # the rank's engine, loaded with the broadcast replica
+            with gpu_slots:
+                cq = ctx.Queue()
+                p = ctx.Process(target=_cfg2_shard, args=(w, shard, cq))
+                p.start()
+                y = cq.get(timeout=600)
+                p.join(timeout=120)
+                assert p.exitcode == 0, p.exitcode
+            return y
+
         clips = synth.uniform_clips(32, 7, 128, 128, seed=32)          # every rank holds the batch; its shard is 4 clips
         lo, hi = pd.shard_range(32, rank, world)
-        out = pd.sharded_forward(eng.forward, clips, gather_to=0)
+        out = pd.sharded_forward(forward, clips, gather_to=0)
         q.put((rank, (lo, hi), None if out is None else out))
-        eng.close()
     finally:
         dist.destroy_process_group()
 
 
 def test_configs2_eight_ranks_batch32():
     """BASELINE.json configs[2], functionally: B = 32 clips of 7x128x128 sharded over 8 ranks (4 clips each; all eight on the
-    one visible GPU, gloo transport - the sharding, weight replica and gather are the code an 8-GPU node runs).  The gathered
-    result is bit-equal to the unsharded forward of the same engine, and a sample of it is checked against the oracle."""
+    one visible GPU, gloo transport - the sharding, weight replica and gather are the code an 8-GPU node runs; at most three
+    ranks' engines hold the GPU at a time).  The gathered result is bit-equal to the unsharded forward of the same engine, and a
+    sample of it is checked against the oracle."""
     import torch.multiprocessing as mp
     from oracle import pfnl_fast
     from pfnl_amd.engine import PFNLEngine
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_cfg2_worker, args=(r, 8, port, q)) for r in range(8)]
+    gpu_slots = ctx.Semaphore(3)
+    procs = [ctx.Process(target=_cfg2_worker, args=(r, 8, port, gpu_slots, q)) for r in range(8)]
     for p in procs:
         p.start()
     res = sorted([q.get(timeout=900) for _ in procs], key=lambda t: t[0])
@@ -217,6 +240,31 @@ def test_bench_rccl_path_with_one_rank():
     assert d["n_gpus"] == 1 and d["config"]["backend"] == "nccl"
     assert d["config"]["comm"] == "pfnl_comm (RCCL)", (d["config"], r.stderr[-800:])
     assert d["value"] > 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: after the K timed steps the last step's SR frames land in DIR/output.npy (float32), equal bit
+    for bit to the engine's forward of the bench's own seeded input, and the line times exactly K steps.  Two runs dump the same."""
+    from pfnl_amd.engine import PFNLEngine
+    outs = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg0", "--steps", "3", "--warmup", "1",
+                            "--no-cpu-baseline", "--no-secondary", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert abs(rec["value"] - 3 / (rec["ms_per_step"] * 1e-3 * 3)) < 1e-2 * rec["value"]
+        assert sorted(p.name for p in d.iterdir()) == ["output.npy"] and rec["dump_outputs"]["file"] == "output.npy"
+        outs.append(np.load(d / "output.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (1, 1, 128, 128, 3)
+    assert np.array_equal(outs[0], outs[1])
+    g = PFNLGeometry()
+    eng = PFNLEngine(g, device=0)
+    eng.load_weights(synth.synthetic_weights(g, seed=0))
+    ref = eng.forward(synth.uniform_clips(1, 7, 32, 32, seed=1234))
+    eng.close()
+    assert np.array_equal(outs[0], ref)
 
 
 def test_weight_replica_without_host_tensors():

@@ -475,3 +475,24 @@ def test_harness_numerics_match_the_reference_functions():
         for b in range(13):
             want += gd["blur"][a, b] * xp[:, a:a + 21:4, b:b + 29:4]
     assert np.abs(synth.blur_decimate(hr, 4) - want).max() < 1e-7              # (blur_decimate returns float32)
+
+
+def test_bench_dump_output_budget(tmp_path):
+    """bench.py --dump-outputs writes float32 [B,1,sH,sW,3]; past the byte budget it keeps a fixed, seeded choice of whole clips
+    (and, should one clip alone be over it, a seeded sample of that clip's values) - the same files from run to run."""
+    import sys
+    torch = pytest.importorskip("torch")
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    out = torch.arange(6 * 1 * 8 * 8 * 3, dtype=torch.float32).reshape(6, 1, 8, 8, 3)
+    rec = bench.dump_output(out, str(tmp_path / "a"), "output", 1 << 20)
+    got = np.load(tmp_path / "a" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, out.numpy()) and rec["clips"] == list(range(6))
+    clip = out[0].numpy().nbytes
+    rec = bench.dump_output(out, str(tmp_path / "b"), "output", 2 * clip + 7)
+    got = np.load(tmp_path / "b" / "output.npy")
+    assert len(rec["clips"]) == 2 and rec["clips"] == sorted(rec["clips"]) and np.array_equal(got, out.numpy()[rec["clips"]])
+    assert bench.dump_output(out, str(tmp_path / "c"), "output", 2 * clip + 7) == rec
+    rec = bench.dump_output(out, str(tmp_path / "d"), "output", 100)
+    got = np.load(tmp_path / "d" / "output.npy")
+    assert got.shape == (25,) and got.nbytes <= 100 and np.all(np.isin(got, out.numpy()[rec["clips"]]))
