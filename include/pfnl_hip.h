@@ -58,7 +58,7 @@ typedef struct pfnl_config {
 } pfnl_config;
 
 const char* pfnl_last_error(void);
-int pfnl_version(void);                        /* ABI version, currently 3 (round 6: + pfnl_plan, pfnl_get_option, the _sf0 op hooks; - pfnl_op_conv3x3_wsplit) */
+int pfnl_version(void);                        /* ABI version, currently 4 (+ the _ex op hooks: MFMA shape and split chains chosen by the caller) */
 int pfnl_device_count(int* count);
 
 /* ---- model lifetime ---------------------------------------------------------------------- */
@@ -345,6 +345,33 @@ int pfnl_op_conv1_conv10_split16_sf0(const float* in, const float* k1_host, cons
  * (device) = per pixel [channel half][hi 32 | lo' 32], hi = f16(out), lo' = f16((out - hi) 2^11). */
 int pfnl_op_conv2_chain_sf0(const float* in, const float* kernel_host, const float* bias_host, const float* base, int add_div, const float* resid,
                             float* out, uint16_t* out_sf, int items, int H, int W, int act, void* stream);
+/* C-ABI v4: the chained launches of the trunk with the MFMA shape and the split-chain geometry chosen by the caller instead of the
+ * forward's plan, so that every form the plan can pick is compared with the spec op by op.  Arguments and results as the hooks named below.
+ *   mfma = 16: the v_mfma_*_16x16x32 form on its own weight pack; mfma = 32: the 32x32x16 form.
+ *   split chains (split_s > 0): the first n_full (clip, 8x32 tile) chains - a multiple of the launch grid (the CU count rounded down to whole
+ *   XCDs, at least 8) below the chain count - run whole; each chain behind them is cut by frames into split_s <= 7 parts of <= split_q
+ *   frames, every part non-empty, the parts together the chain's frames, at most one part per workgroup of the grid.  split_s = 0: no cut
+ *   (n_full and split_q ignored).  A geometry outside that rule returns PFNL_ERR_INVALID before any allocation or launch; `out` is untouched.
+ * pfnl_op_conv2_chain_ex: the whole of conv2_i as pfnl_op_conv3x3_split16_sf(which = 2) (conv3x3_sf_chain_kernel / conv3x3_sf_chain16_kernel);
+ *   mfma = 16 with split_s > 0 is refused (split chains exist on the 32x32x16 kernel only). */
+int pfnl_op_conv2_chain_ex(const float* in, const float* kernel_host, const float* bias_host, const float* base, int add_div, const float* resid,
+                           float* out, int items, int H, int W, int act, int mfma, int n_full, int split_s, int split_q, void* stream);
+/* pfnl_op_conv1_conv10_split16 with split chains: the cut chains' parts leave raw conv10_i sums that c10_finalize_kernel adds into base. */
+int pfnl_op_conv1_conv10_split16_ex(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
+                                    const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
+                                    int n_full, int split_s, int split_q, void* stream);
+/* pfnl_op_conv3x3_accum_split16 (convmerge1) with split chains: the parts' raw sums meet in c10_finalize_kernel (+ bias, act) into out. */
+int pfnl_op_conv3x3_accum_split16_ex(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
+                                     int frames_per_clip, int H, int W, int cout, int act, int n_full, int split_s, int split_q, void* stream);
+/* pfnl_op_conv3x3_bf16 in its fused mode (addend and resid required) and pfnl_op_conv1_conv10_bf16, both on the third-generation bf16
+ * kernel called directly (conv_bf16_v3.hip; PFNL_BF16_V3 does not apply); mfma = 16 runs its M16 form.  Split chains of the conv1_conv10
+ * form: the parts' raw conv10_i sums meet in c10_finalize_bf16_kernel (+ b10, leaky-relu, bf16) into base. */
+int pfnl_op_conv3x3_bf16_ex(const uint16_t* in, const float* kernel_host, const float* bias_host, const uint16_t* addend, int add_div,
+                            const uint16_t* resid, uint16_t* out, int items, int H, int W, int act, int mfma, int n_full, int split_s,
+                            int split_q, void* stream);
+int pfnl_op_conv1_conv10_bf16_ex(const uint16_t* in, const float* k1_host, const float* b1_host, const float* k10_host, const float* b10_host,
+                                 uint16_t* out1, uint16_t* base, int clips, int frames_per_clip, int H, int W, int mfma, int n_full, int split_s,
+                                 int split_q, void* stream);
 /* The split-format variants of the split-f16 kernels (pfnl_amd/csrc/conv_split16.h "SF": an activation tensor that only feeds MFMA
  * operands - conv1_i's and conv10_i's outputs, model/pfnl.py:66-68 - is kept as (hi, lo') binary16 pairs, built once by its
  * producer).  fp32 at the hook's interface: conversions bracket the kernel under test.

@@ -1029,7 +1029,7 @@ int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull
 extern "C" {
 
 const char* pfnl_last_error(void) { return g_err.c_str(); }
-int pfnl_version(void) { return 3; }
+int pfnl_version(void) { return 4; }
 
 int pfnl_device_count(int* count) {
     if (!count) return fail(PFNL_ERR_INVALID, "count is NULL");
@@ -2224,11 +2224,21 @@ int pfnl_op_conv3x3_accum(const float* in, const float* kernel_host, const float
     return 0;
 }
 
-int pfnl_op_conv3x3_accum_split16(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
-                                  int frames_per_clip, int H, int W, int cout, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (clips < 1 || frames_per_clip < 1 || H < 1 || W < 1 || cout < 1 || cout > 64) return fail(PFNL_ERR_INVALID, "accumulating conv needs cout <= 64");
-    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
+// ---- the C-ABI v4 hooks' split-chain arguments: split_s = 0 is no cut (n_full, split_q ignored); otherwise the geometry every split launch
+// checks (split_geometry_ok) on the grid of the current device, tested before any allocation or launch
+static bool split_args_ok(int H, int W, int items, int T, int n_full, int split_s, int split_q) {
+    if (split_s == 0) return true;
+    return split_s <= 7 && pfnl::split_geometry_ok(H, W, items, T, n_full, split_s, split_q, pfnl::conv_split16_grid());
+}
+// floats of the parts' raw sums: one [8][32][64] tile per part of every cut chain
+static size_t split_partial_floats(int H, int W, int items, int T, int n_full, int split_s) {
+    const size_t nchains = (size_t)((W + 31) / 32) * ((H + 7) / 8) * (items / T);
+    return (nchains - (size_t)n_full) * split_s * 8 * 32 * 64;
+}
+
+static int op_conv3x3_accum_split16(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
+                                    int frames_per_clip, int H, int W, int cout, int act, void* stream, int n_full = 0, int split_s = 0,
+                                    int split_q = 0) {
     hipStream_t s = (hipStream_t)stream;
     const int T = frames_per_clip;
     const size_t nh = pfnl::conv3x3_split16_pack_halfs();
@@ -2236,14 +2246,45 @@ int pfnl_op_conv3x3_accum_split16(const float* in, const float* kernel_host, con
     for (int f = 0; f < T; ++f) pfnl::conv3x3_split16_pack_weights(kernel_host, 64 * T, 64 * f, pack.data() + (size_t)f * nh, cout);
     if (bias_host) std::memcpy(&pack[(size_t)T * nh], bias_host, cout * sizeof(float));
     uint16_t* dw = nullptr;
+    float* part = nullptr;
     HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
     hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    pfnl::ConvSplitParams q{in, dw, reinterpret_cast<const float*>(dw + (size_t)T * nh), nullptr, nullptr, out, H, W, clips * T, T, act, 1};
+    if (e == hipSuccess && split_s) e = hipMalloc(&part, split_partial_floats(H, W, clips * T, T, n_full, split_s) * sizeof(float));
+    const float* const db = reinterpret_cast<const float*>(dw + (size_t)T * nh);
+    pfnl::ConvSplitParams q{in, dw, db, nullptr, nullptr, out, H, W, clips * T, T, act, 1};
+    q.n_full = n_full;
+    q.split_s = split_s;
+    q.split_q = split_q;
+    q.partial = part;
     if (e == hipSuccess) e = pfnl::launch_conv3x3_split16(q, s);
+    if (e == hipSuccess && split_s) {                                   // the cut chains: the parts' raw sums + bias, act -> out
+        pfnl::ConvSplitParams f{};
+        f.H = H;
+        f.W = W;
+        f.items = clips * T;
+        f.add_div = T;
+        f.act = act;
+        f.n_full = n_full;
+        f.split_s = split_s;
+        f.split_q = split_q;
+        f.partial = part;
+        f.bias = db;
+        f.out = out;
+        e = pfnl::launch_c10_finalize(f, s);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(dw);
+    if (part) (void)hipFree(part);
     if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("accumulating conv (split16) op: ") + hipGetErrorString(e));
     return 0;
+}
+
+int pfnl_op_conv3x3_accum_split16(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
+                                  int frames_per_clip, int H, int W, int cout, int act, void* stream) {
+    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (clips < 1 || frames_per_clip < 1 || H < 1 || W < 1 || cout < 1 || cout > 64) return fail(PFNL_ERR_INVALID, "accumulating conv needs cout <= 64");
+    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
+    return op_conv3x3_accum_split16(in, kernel_host, bias_host, out, clips, frames_per_clip, H, W, cout, act, stream);
 }
 
 int pfnl_op_conv3x3_bf16(const uint16_t* in, const float* kernel_host, const float* bias_host, const uint16_t* addend,
@@ -2452,37 +2493,46 @@ int pfnl_op_conv_small_pf_block(const float* x, const float* k1_host, const floa
 //   which = 0: conv3x3_sf_kernel (input SF by LDS-DMA, epilogue from registers; plain or fused with addend + resid)
 //   which = 1: conv3x3_split16_kernel<0, OSF> (conv1_i: fp32 in, SF out)
 static int op_conv2_chain(const float* in, const float* kernel_host, const float* bias_host, const float* addend, int add_div, const float* resid,
-                          float* out, uint16_t* out_sf, int items, int H, int W, int act, void* stream) {
-    {
-        {
-        hipStream_t s2 = (hipStream_t)stream;
-        const size_t nh2 = pfnl::conv3x3_split16_pack_halfs();
-        std::vector<uint16_t> pk(2 * nh2 + 128, 0);
-        pfnl::conv3x3_split16_pack_weights(kernel_host, 128, 0, pk.data(), 64, true);
-        pfnl::conv3x3_split16_pack_weights(kernel_host, 128, 64, pk.data() + nh2, 64, true);
-        if (bias_host) std::memcpy(&pk[2 * nh2], bias_host, 64 * sizeof(float));
-        const size_t npf = (size_t)items * H * W, npb = (size_t)(items / add_div) * H * W;
-        uint16_t *dw2 = nullptr, *tf = nullptr, *tb = nullptr;
-        HIPCHK(hipMalloc(&dw2, pk.size() * sizeof(uint16_t)));
-        hipError_t e2 = hipMalloc(&tf, npf * 256);
-        if (e2 == hipSuccess) e2 = hipMalloc(&tb, npb * 256);
-        if (e2 == hipSuccess) e2 = hipMemcpy(dw2, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-        if (e2 == hipSuccess) e2 = pfnl::launch_sf_from_f32(in, tf, npf, s2);
-        if (e2 == hipSuccess) e2 = pfnl::launch_sf_from_f32(addend, tb, npb, s2);
-        if (e2 == hipSuccess && out != resid) e2 = hipMemcpyAsync(out, resid, npf * 256, hipMemcpyDeviceToDevice, s2);   // the kernel works in place
-        pfnl::ConvSplitParams q{reinterpret_cast<const float*>(tf), dw2 + nh2, reinterpret_cast<const float*>(dw2 + 2 * nh2), nullptr, out, out, H, W, items, add_div, act};
-        q.in2 = reinterpret_cast<const float*>(tb);
-        q.wpack2 = dw2;
-        q.out2 = reinterpret_cast<float*>(out_sf);                      // (null: no split-format copy)
-        if (e2 == hipSuccess) e2 = pfnl::launch_conv3x3_sf_chain(q, s2);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(s2);
-        (void)hipFree(dw2);
-        (void)hipFree(tf);
-        (void)hipFree(tb);
-        if (e2 != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv2 chain op: ") + hipGetErrorString(e2));
-        return 0;
-        }
+                          float* out, uint16_t* out_sf, int items, int H, int W, int act, void* stream,
+                          int mfma = 32, int n_full = 0, int split_s = 0, int split_q = 0) {
+    hipStream_t s2 = (hipStream_t)stream;
+    const size_t nh2 = pfnl::conv3x3_split16_pack_halfs();
+    const bool m16 = mfma == 16;
+    std::vector<uint16_t> pk((m16 ? 4 : 2) * nh2 + 128, 0);
+    pfnl::conv3x3_split16_pack_weights(kernel_host, 128, 0, pk.data(), 64, true);
+    pfnl::conv3x3_split16_pack_weights(kernel_host, 128, 64, pk.data() + nh2, 64, true);
+    if (bias_host) std::memcpy(&pk[2 * nh2], bias_host, 64 * sizeof(float));
+    if (m16) {                                                          // conv3x3_sf_chain16_kernel's packs behind the bias, halves as the forward's
+        pfnl::conv3x3_split16_pack_weights16(kernel_host, 128, 0, pk.data() + 2 * nh2 + 128);
+        pfnl::conv3x3_split16_pack_weights16(kernel_host, 128, 64, pk.data() + 3 * nh2 + 128);
     }
+    const size_t npf = (size_t)items * H * W, npb = (size_t)(items / add_div) * H * W;
+    uint16_t *dw2 = nullptr, *tf = nullptr, *tb = nullptr;
+    HIPCHK(hipMalloc(&dw2, pk.size() * sizeof(uint16_t)));
+    hipError_t e2 = hipMalloc(&tf, npf * 256);
+    if (e2 == hipSuccess) e2 = hipMalloc(&tb, npb * 256);
+    if (e2 == hipSuccess) e2 = hipMemcpy(dw2, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e2 == hipSuccess) e2 = pfnl::launch_sf_from_f32(in, tf, npf, s2);
+    if (e2 == hipSuccess) e2 = pfnl::launch_sf_from_f32(addend, tb, npb, s2);
+    if (e2 == hipSuccess && out != resid) e2 = hipMemcpyAsync(out, resid, npf * 256, hipMemcpyDeviceToDevice, s2);   // the kernel works in place
+    pfnl::ConvSplitParams q{reinterpret_cast<const float*>(tf), dw2 + nh2, reinterpret_cast<const float*>(dw2 + 2 * nh2), nullptr, out, out, H, W, items, add_div, act};
+    q.in2 = reinterpret_cast<const float*>(tb);
+    q.wpack2 = dw2;
+    q.out2 = reinterpret_cast<float*>(out_sf);                          // (null: no split-format copy)
+    q.n_full = n_full;
+    q.split_s = split_s;
+    q.split_q = split_q;
+    if (m16) {
+        q.wpack_m16 = dw2 + 3 * nh2 + 128;
+        q.wpack2_m16 = dw2 + 2 * nh2 + 128;
+    }
+    if (e2 == hipSuccess) e2 = pfnl::launch_conv3x3_sf_chain(q, s2);
+    if (e2 == hipSuccess) e2 = hipStreamSynchronize(s2);
+    (void)hipFree(dw2);
+    (void)hipFree(tf);
+    (void)hipFree(tb);
+    if (e2 != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv2 chain op: ") + hipGetErrorString(e2));
+    return 0;
 }
 // the whole of conv2_i in one launch WITH the split-format copy of its output (conv3x3_sf_chain_kernel<true>, option split16_sf0):
 // out as pfnl_op_conv3x3_split16_sf(which = 2); out_sf [items][H][W][128] binary16 bit patterns (device) = the split format of `out`
@@ -2533,7 +2583,7 @@ int pfnl_op_conv3x3_split16_sf(int which, const float* in, const float* kernel_h
 // the kernel writes both in the split format, the hook hands them back as fp32 (hi + lo' 2^-11: what the consumers' MFMAs see)
 static int op_conv1_conv10_split16(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
                                    const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
-                                   void* stream, bool in_sf) {
+                                   void* stream, bool in_sf, int n_full = 0, int split_s = 0, int split_q = 0) {
     if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
     const int T = frames_per_clip;
     if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
@@ -2546,10 +2596,12 @@ static int op_conv1_conv10_split16(const float* in, const float* k1_host, const 
     if (b10_host) std::memcpy(&pack[n3 + n1 + 128], b10_host, 64 * sizeof(float));
     const size_t np1 = (size_t)clips * T * H * W, npb = (size_t)clips * H * W;
     uint16_t *dw = nullptr, *t1 = nullptr, *tb = nullptr, *ti = nullptr;
+    float* part = nullptr;
     HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
     hipError_t e = hipMalloc(&t1, np1 * 256);
     if (e == hipSuccess) e = hipMalloc(&tb, npb * 256);
     if (e == hipSuccess && in_sf) e = hipMalloc(&ti, np1 * 256);
+    if (e == hipSuccess && split_s) e = hipMalloc(&part, split_partial_floats(H, W, clips * T, T, n_full, split_s) * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && in_sf) e = pfnl::launch_sf_from_f32(in, ti, np1, s);   // (the same split the chain kernel's epilogue applies: sf_split4)
     pfnl::ConvSplitParams q{in_sf ? reinterpret_cast<const float*>(ti) : in, dw, reinterpret_cast<const float*>(dw + n3 + n1), nullptr, nullptr, reinterpret_cast<float*>(t1), H, W, clips * T, T, 1};
@@ -2557,7 +2609,25 @@ static int op_conv1_conv10_split16(const float* in, const float* k1_host, const 
     q.wpack2 = dw + n3;
     q.bias2 = reinterpret_cast<const float*>(dw + n3 + n1 + 128);
     q.out2 = reinterpret_cast<float*>(tb);
+    q.n_full = n_full;
+    q.split_s = split_s;
+    q.split_q = split_q;
+    q.partial = part;
     if (e == hipSuccess) e = pfnl::launch_conv3x3_c1c10(q, s);
+    if (e == hipSuccess && split_s) {                                   // the cut chains' base from the parts' raw conv10_i sums
+        pfnl::ConvSplitParams f{};
+        f.H = H;
+        f.W = W;
+        f.items = clips * T;
+        f.add_div = T;
+        f.act = 1;
+        f.n_full = n_full;
+        f.split_s = split_s;
+        f.split_q = split_q;
+        f.partial = part;
+        f.out2 = reinterpret_cast<float*>(tb);
+        e = pfnl::launch_c10_finalize(f, s);
+    }
     if (e == hipSuccess) e = pfnl::launch_sf_to_f32(t1, out1, np1, s);
     if (e == hipSuccess) e = pfnl::launch_sf_to_f32(tb, base, npb, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -2565,6 +2635,7 @@ static int op_conv1_conv10_split16(const float* in, const float* k1_host, const 
     (void)hipFree(t1);
     (void)hipFree(tb);
     if (ti) (void)hipFree(ti);
+    if (part) (void)hipFree(part);
     if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv1+conv10 split16 op: ") + hipGetErrorString(e));
     return 0;
 }
@@ -2579,6 +2650,104 @@ int pfnl_op_conv1_conv10_split16_sf0(const float* in, const float* k1_host, cons
                                      const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
                                      void* stream) {
     return op_conv1_conv10_split16(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, frames_per_clip, H, W, stream, true);
+}
+
+// ---- C-ABI v4: the chained launches with the MFMA shape and the split-chain geometry chosen by the caller instead of trunk_plan, so that the
+// 16x16x32 forms and every cut of a chain can be compared with the spec op by op (include/pfnl_hip.h)
+int pfnl_op_conv2_chain_ex(const float* in, const float* kernel_host, const float* bias_host, const float* base, int add_div, const float* resid,
+                           float* out, int items, int H, int W, int act, int mfma, int n_full, int split_s, int split_q, void* stream) {
+    if (!in || !kernel_host || !out || !base || !resid) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (items < 1 || H < 1 || W < 1 || add_div < 1 || items % add_div) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
+    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
+    if (mfma != 16 && mfma != 32) return fail(PFNL_ERR_INVALID, "mfma must be 16 or 32");
+    if (mfma == 16 && split_s) return fail(PFNL_ERR_INVALID, "split chains run on the 32x32x16 kernel only");
+    if (!split_args_ok(H, W, items, add_div, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
+    return op_conv2_chain(in, kernel_host, bias_host, base, add_div, resid, out, nullptr, items, H, W, act, stream, mfma, n_full, split_s, split_q);
+}
+
+int pfnl_op_conv1_conv10_split16_ex(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
+                                    const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
+                                    int n_full, int split_s, int split_q, void* stream) {
+    if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
+    const int T = frames_per_clip;
+    if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
+    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
+    if (!split_args_ok(H, W, clips * T, T, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
+    return op_conv1_conv10_split16(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, T, H, W, stream, false, n_full, split_s, split_q);
+}
+
+int pfnl_op_conv3x3_accum_split16_ex(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
+                                     int frames_per_clip, int H, int W, int cout, int act, int n_full, int split_s, int split_q, void* stream) {
+    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (clips < 1 || frames_per_clip < 1 || H < 1 || W < 1 || cout < 1 || cout > 64) return fail(PFNL_ERR_INVALID, "accumulating conv needs cout <= 64");
+    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
+    if (!split_args_ok(H, W, clips * frames_per_clip, frames_per_clip, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
+    return op_conv3x3_accum_split16(in, kernel_host, bias_host, out, clips, frames_per_clip, H, W, cout, act, stream, n_full, split_s, split_q);
+}
+
+// the bf16 chained modes on the third-generation kernel, called directly (PFNL_BF16_V3 does not apply); mfma = 16 adds the M16 pack
+static int op_bf16_v3(int mode, const uint16_t* in, const float* k_host, const float* b_host, const uint16_t* addend, int add_div,
+                      const uint16_t* resid, uint16_t* out, const float* k10_host, const float* b10_host, uint16_t* base, int items, int H,
+                      int W, int act, int mfma, int n_full, int split_s, int split_q, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int T = add_div;
+    const size_t n3 = pfnl::conv3x3_bf16_pack_halfs(), n1 = mode == 2 ? pfnl::conv1x1_bf16_pack_halfs(T) : 0;
+    // [3x3 pack | M16 pack | conv10_i pack | bias | conv10_i bias]
+    std::vector<uint16_t> pack(2 * n3 + n1 + 256, 0);
+    pfnl::conv3x3_bf16_pack_weights(k_host, 64, 0, pack.data());
+    pfnl::conv3x3_bf16_pack_weights16(k_host, 64, 0, pack.data() + n3);
+    if (mode == 2) pfnl::conv1x1_bf16_pack_weights(k10_host, T, pack.data() + 2 * n3);
+    if (b_host) std::memcpy(&pack[2 * n3 + n1], b_host, 64 * sizeof(float));
+    if (b10_host) std::memcpy(&pack[2 * n3 + n1 + 128], b10_host, 64 * sizeof(float));
+    uint16_t* dw = nullptr;
+    float* part = nullptr;
+    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
+    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && mode == 2 && split_s) e = hipMalloc(&part, split_partial_floats(H, W, items, T, n_full, split_s) * sizeof(float));
+    const float* const db = reinterpret_cast<const float*>(dw + 2 * n3 + n1);
+    pfnl::ConvBf16Params q{in, dw, db, addend, resid, out, H, W, items, T, act};
+    if (mode == 2) {
+        q.x_w = dw + 2 * n3;
+        q.x_bias = db + 64;
+        q.x_out = base;
+    }
+    q.n_full = n_full;
+    q.split_s = split_s;
+    q.split_q = split_q;
+    q.partial = part;
+    if (mfma == 16) q.wpack16 = dw + n3;
+    if (e == hipSuccess) e = pfnl::launch_conv3x3_bf16_v3(q, mode, s);
+    if (e == hipSuccess && mode == 2 && split_s) e = pfnl::launch_c10_finalize_bf16(q, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(dw);
+    if (part) (void)hipFree(part);
+    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("bf16 v3 op: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int pfnl_op_conv3x3_bf16_ex(const uint16_t* in, const float* kernel_host, const float* bias_host, const uint16_t* addend, int add_div,
+                            const uint16_t* resid, uint16_t* out, int items, int H, int W, int act, int mfma, int n_full, int split_s,
+                            int split_q, void* stream) {
+    if (!in || !kernel_host || !addend || !resid || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (items < 1 || H < 1 || W < 1 || add_div < 1 || items % add_div) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
+    if ((long long)H * W * 128 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
+    if (mfma != 16 && mfma != 32) return fail(PFNL_ERR_INVALID, "mfma must be 16 or 32");
+    if (!split_args_ok(H, W, items, add_div, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
+    return op_bf16_v3(1, in, kernel_host, bias_host, addend, add_div, resid, out, nullptr, nullptr, nullptr, items, H, W, act, mfma, n_full,
+                      split_s, split_q, stream);
+}
+
+int pfnl_op_conv1_conv10_bf16_ex(const uint16_t* in, const float* k1_host, const float* b1_host, const float* k10_host, const float* b10_host,
+                                 uint16_t* out1, uint16_t* base, int clips, int frames_per_clip, int H, int W, int mfma, int n_full, int split_s,
+                                 int split_q, void* stream) {
+    if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
+    const int T = frames_per_clip;
+    if (clips < 1 || (T != 3 && T != 5 && T != 7) || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
+    if ((long long)H * W * 128 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
+    if (mfma != 16 && mfma != 32) return fail(PFNL_ERR_INVALID, "mfma must be 16 or 32");
+    if (!split_args_ok(H, W, clips * T, T, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
+    return op_bf16_v3(2, in, k1_host, b1_host, nullptr, T, nullptr, out1, k10_host, b10_host, base, clips * T, H, W, 1, mfma, n_full, split_s,
+                      split_q, stream);
 }
 
 // conv10_i with its input and / or output in the split format (fp32 at the hook's interface, see above)

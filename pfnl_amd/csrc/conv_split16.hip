@@ -211,9 +211,12 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
 
     // weights of half 0 + bias: requested here, written to LDS in the prologue below - after the first halo has been requested
     // too, so that the two latencies of a launch's start overlap (a launch is only 20-100 us long)
+    // (SPLIT: a workgroup without whole chains starts with its part, at frame sp_f0 - ACCUM's pack index 2 f + half)
+    const int f_first = (SPLIT && nfull_tiles == 0) ? sp_f0 : 0;
+    const u32x4* const w0src = reinterpret_cast<const u32x4*>(p.wpack) + (size_t)(2 * f_first) * (CS_W_BYTES / 16);
     u32x4 w0reg[CS_W_BYTES / 16 / CS_THREADS];
 #pragma unroll
-    for (int k = 0; k < CS_W_BYTES / 16 / CS_THREADS; ++k) w0reg[k] = reinterpret_cast<const u32x4*>(p.wpack)[k * CS_THREADS + tid];
+    for (int k = 0; k < CS_W_BYTES / 16 / CS_THREADS; ++k) w0reg[k] = w0src[k * CS_THREADS + tid];
     const float bias_r = tid < 64 ? p.bias[tid] : 0.f;
 
     // staging map: piece id = k*512 + tid -> halo pixel id >> 3, 4-channel piece id & 7 (8 threads read one pixel's 128 B)
@@ -449,7 +452,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
         if (tid < 64) bl[tid] = bias_r;
 #pragma unroll
         for (int k = 0; k < CS_ITERS; ++k) CS_COMMIT1(k, 0);
-        if constexpr (ACCUM) w_request(0, 2);                       // (every ACCUM unit writes "its" slot 2 in group 1: identical data here)
+        if constexpr (ACCUM) w_request(2 * f_first, 2);             // (every ACCUM unit writes "its" slot 2 in group 1: identical data here)
     }
     __syncthreads();
 
@@ -466,7 +469,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
     n_item = c_item;
     n_y0 = c_y0;
     n_x0 = c_x0;
-    [[maybe_unused]] int fch = 0;                                   // ACCUM: frame of the chain the current tile is
+    [[maybe_unused]] int fch = f_first;                             // ACCUM: frame of the chain the current tile is
     for (int kt = 0; kt < nt; ++kt) {
         const int half_a = kt & 1;                                  // channel half of unit A; unit B: the other one
         auto unit = [&](auto par) __attribute__((always_inline)) {
@@ -1395,13 +1398,15 @@ int conv_split16_grid() {
 }
 
 // the geometry of a split-chain launch must be the one the kernels assume: whole rounds of the grid in front, one part per workgroup behind
+bool split_geometry_ok(int H, int W, int items, int T, int n_full, int split_s, int split_q, int grid) {
+    if (T < 1 || grid < 1) return false;
+    const long long nchains = (long long)((W + CS_TW - 1) / CS_TW) * ((H + CS_TH - 1) / CS_TH) * (items / T);
+    if (split_s < 2 || split_q < 1 || n_full < 0 || n_full % grid || n_full >= nchains) return false;
+    if ((long long)split_s * split_q < T || (long long)(split_s - 1) * split_q >= T) return false;   // every part non-empty, together the T frames
+    return (nchains - n_full) * split_s <= grid;
+}
 static bool split_params_ok(const ConvSplitParams& p, int grid) {
-    if (p.split_s == 0) return true;
-    const int T = p.add_div;
-    const long long nchains = (long long)((p.W + CS_TW - 1) / CS_TW) * ((p.H + CS_TH - 1) / CS_TH) * (p.items / T);
-    if (p.split_s < 2 || p.split_q < 1 || p.n_full < 0 || p.n_full % grid || p.n_full >= nchains) return false;
-    if ((long long)p.split_s * p.split_q < T || (long long)(p.split_s - 1) * p.split_q >= T) return false;   // every part non-empty, together the T frames
-    return (nchains - p.n_full) * p.split_s <= grid;
+    return p.split_s == 0 || split_geometry_ok(p.H, p.W, p.items, p.add_div, p.n_full, p.split_s, p.split_q, grid);
 }
 
 // ---- split chains: the parts' raw conv10_i sums -> `base` in the split format (see conv3x3_c1c10_kernel).  One workgroup per split chain;

@@ -432,3 +432,99 @@ def quantise_u8(sr):
     out = torch.empty(sr.shape, dtype=torch.uint8, device=sr.device)
     _capi.check(lib.pfnl_op_quantise_u8(C.c_void_p(sr.data_ptr()), C.c_void_p(out.data_ptr()), sr.numel(), _stream(sr)))
     return out
+
+
+def conv2_chain_ex(x, kernel, bias, base, resid, add_div: int, act: bool = True, mfma: int = 32, split=(0, 0, 0), out=None):
+    """The whole of conv2_i in one launch (reference model/pfnl.py:69-71) with the MFMA shape and the split-chain geometry given explicitly
+    (pfnl_op_conv2_chain_ex): x = inp1 [F,H,W,64], base [F/add_div,H,W,64], resid [F,H,W,64] (cuda fp32), kernel HWIO [3,3,128,64] ->
+    lrelu(conv3x3(concat([base, x])) + bias) + resid.  split = (n_full, split_s, split_q); split_s = 0: no cut.  `out` (optional) is
+    written in place."""
+    import torch
+    lib = _capi.load_library()
+    F, H, W, c = x.shape
+    k, b = _host(kernel, "kernel"), _host(bias, "bias")
+    if c != 64 or k.shape != (3, 3, 128, 64) or F % add_div:
+        raise ValueError("conv2_chain_ex: geometry mismatch")
+    if out is None:
+        out = torch.empty((F, H, W, 64), dtype=torch.float32, device=x.device)
+    n_full, s, q = (int(v) for v in split)
+    _capi.check(lib.pfnl_op_conv2_chain_ex(_req(x, "x"), _hp(k), _hp(b), _req(base, "base"), int(add_div), _req(resid, "resid"),
+                                           _req(out, "out"), F, H, W, 1 if act else 0, int(mfma), n_full, s, q, _stream(x)))
+    return out
+
+
+def conv1_conv10_split16_ex(x, k1, b1, k10, b10, frames_per_clip: int, split=(0, 0, 0), out1=None, base=None):
+    """conv1_i + conv10_i in one launch (pfnl_op_conv1_conv10_split16_ex; reference model/pfnl.py:66-68) with the split-chain geometry
+    split = (n_full, split_s, split_q) given explicitly; results as conv1_conv10_split16."""
+    import torch
+    lib = _capi.load_library()
+    F, H, W, c = x.shape
+    T = int(frames_per_clip)
+    k1h, k10h = _host(k1, "k1"), _host(k10, "k10")
+    if c != 64 or F % T or k1h.size != 9 * 64 * 64 or k10h.size != 64 * T * 64:
+        raise ValueError("conv1_conv10_split16_ex: geometry mismatch")
+    if out1 is None:
+        out1 = torch.empty((F, H, W, 64), dtype=torch.float32, device=x.device)
+    if base is None:
+        base = torch.empty((F // T, H, W, 64), dtype=torch.float32, device=x.device)
+    n_full, s, q = (int(v) for v in split)
+    _capi.check(lib.pfnl_op_conv1_conv10_split16_ex(_req(x, "x"), _hp(k1h), _hp(_host(b1, "b1")), _hp(k10h), _hp(_host(b10, "b10")),
+                                                    _req(out1, "out1"), _req(base, "base"), F // T, T, H, W, n_full, s, q, _stream(x)))
+    return out1, base
+
+
+def conv3x3_accum_split16_ex(x, kernel, bias=None, act=True, frames_per_clip=1, split=(0, 0, 0), out=None):
+    """convmerge1 on the split-f16 kernel (pfnl_op_conv3x3_accum_split16_ex; reference model/pfnl.py:52, :73-74) with the split-chain
+    geometry split = (n_full, split_s, split_q) given explicitly.  x [clips*fpc,H,W,64]; kernel HWIO [3,3,64*fpc,cout];
+    returns [clips,H,W,64] (channels >= cout: act(0))."""
+    import torch
+    lib = _capi.load_library()
+    k, b = _host(kernel, "kernel"), _host(bias, "bias")
+    F, H, W, c = x.shape
+    T = int(frames_per_clip)
+    if k.shape[:3] != (3, 3, 64 * T) or c != 64 or F % T or k.shape[3] > 64:
+        raise ValueError("conv3x3_accum_split16_ex: geometry mismatch")
+    if out is None:
+        out = torch.empty((F // T, H, W, 64), dtype=torch.float32, device=x.device)
+    n_full, s, q = (int(v) for v in split)
+    _capi.check(lib.pfnl_op_conv3x3_accum_split16_ex(_req(x, "x"), _hp(k), _hp(b), _req(out, "out"), F // T, T, H, W, int(k.shape[3]),
+                                                     1 if act else 0, n_full, s, q, _stream(x)))
+    return out
+
+
+def conv3x3_bf16_ex(x, kernel, bias, addend, add_div, resid, act=True, mfma: int = 32, split=(0, 0, 0), out=None):
+    """The fused mode of the bf16 3x3 kernel (out = act(conv + bias + addend[item / add_div]) + resid; reference model/pfnl.py:69-71) on the
+    third-generation kernel with the MFMA shape and the split-chain geometry given explicitly (pfnl_op_conv3x3_bf16_ex)."""
+    import torch
+    lib = _capi.load_library()
+    k, b = _host(kernel, "kernel"), _host(bias, "bias")
+    F, H, W, c = x.shape
+    if k.shape != (3, 3, 64, 64) or c != 64 or F % add_div:
+        raise ValueError("conv3x3_bf16_ex: geometry mismatch")
+    if out is None:
+        out = torch.empty_like(x)
+    n_full, s, q = (int(v) for v in split)
+    _capi.check(lib.pfnl_op_conv3x3_bf16_ex(_req16(x, "x"), _hp(k), _hp(b), _req16(addend, "addend"), int(add_div), _req16(resid, "resid"),
+                                            _req16(out, "out"), F, H, W, 1 if act else 0, int(mfma), n_full, s, q, _stream(x)))
+    return out
+
+
+def conv1_conv10_bf16_ex(x, k1, b1, k10, b10, frames_per_clip, mfma: int = 32, split=(0, 0, 0), out1=None, base=None):
+    """conv1_i + conv10_i in one launch of the bf16 kernel (reference model/pfnl.py:66-68) on the third-generation kernel with the MFMA
+    shape and the split-chain geometry given explicitly (pfnl_op_conv1_conv10_bf16_ex); results as conv1_conv10_bf16."""
+    import torch
+    lib = _capi.load_library()
+    k1h, b1h, k10h, b10h = _host(k1, "k1"), _host(b1, "b1"), _host(k10, "k10"), _host(b10, "b10")
+    F, H, W, c = x.shape
+    T = int(frames_per_clip)
+    if k1h.shape != (3, 3, 64, 64) or k10h.shape != (1, 1, 64 * T, 64) or c != 64 or F % T:
+        raise ValueError("conv1_conv10_bf16_ex: geometry mismatch")
+    if out1 is None:
+        out1 = torch.empty_like(x)
+    if base is None:
+        base = torch.empty((F // T, H, W, 64), dtype=torch.bfloat16, device=x.device)
+    n_full, s, q = (int(v) for v in split)
+    _capi.check(lib.pfnl_op_conv1_conv10_bf16_ex(_req16(x, "x"), _hp(k1h), _hp(b1h), _hp(k10h), _hp(b10h), _req16(out1, "out1"),
+                                                 _req16(base, "base"), F // T, T, H, W, int(mfma), n_full, s, q, _stream(x)))
+    return out1, base
+

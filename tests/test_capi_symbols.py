@@ -27,9 +27,19 @@ def test_library_built_and_exports_header_symbols():
     assert set(syms) == set(_capi.SIGNATURES), "ctypes signatures and header disagree"
 
 
-def test_version_and_argument_validation_without_gpu():
+def test_abi_v4_and_argument_validation_without_gpu():
+    """ABI version 4 (the _ex op hooks); arguments that need no device are refused before any HIP call."""
     lib = _capi.load_library()
-    assert lib.pfnl_version() == 3
+    assert lib.pfnl_version() == 4
+    dummy = C.c_void_p(16)                                                     # never dereferenced: the hooks return first
+    chain = lambda mfma, n_full, s, q: lib.pfnl_op_conv2_chain_ex(dummy, dummy, None, dummy, 7, dummy, dummy, 14, 8, 32, 1,  # noqa: E731
+                                                                  mfma, n_full, s, q, None)
+    assert chain(8, 0, 0, 0) == -1 and b"mfma" in lib.pfnl_last_error()
+    assert chain(16, 8, 2, 4) == -1 and b"32x32x16" in lib.pfnl_last_error()
+    assert lib.pfnl_op_conv3x3_bf16_ex(dummy, dummy, None, dummy, 7, dummy, dummy, 14, 8, 32, 1, 64, 0, 0, 0, None) == -1
+    assert b"mfma" in lib.pfnl_last_error()
+    assert lib.pfnl_op_conv3x3_bf16_ex(dummy, dummy, None, None, 7, None, dummy, 14, 8, 32, 1, 16, 0, 0, 0, None) == -1
+    assert b"NULL" in lib.pfnl_last_error()
     h = C.c_void_p()
     bad = _capi.pfnl_config(4, 4, 64, 20, 0, (C.c_int32 * 3)(0, 0, 0))        # even num_frames
     assert lib.pfnl_create(C.byref(bad), C.byref(h)) == -1

@@ -152,8 +152,9 @@ def test_forward_bf16_split_chains(T, scale, nb, H, W, Bs):
     for B in Bs:
         x, _ = synth.moving_field_clips(B, T, H, W, scale, seed=3)
         pl = eng.plan(B, H, W)
-        R = (B * chains_clip) % 256
-        cut = B * chains_clip > 256 and 0 < R <= 128 and min(T, 256 // R) >= 2
+        G = _grid()
+        R = (B * chains_clip) % G
+        cut = B * chains_clip > G and 0 < R <= G // 2 and min(T, G // R) >= 2
         assert pl["structure"] == ("bf16_3_split" if cut else "bf16_3"), (B, pl)
         y = eng.forward(x)
         assert np.array_equal(y, eng.forward(x)), B
@@ -421,3 +422,228 @@ def test_round4_schedules_are_deterministic_and_bit_equal_across_generations():
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "soak_r04.py"), "4"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0 and "soak_r04: ok" in r.stdout, r.stdout[-1500:] + r.stderr[-800:]
 
+
+
+# ---- C-ABI v4 hooks: the third-generation kernel's 16x16x32 form and split chains, op by op.  (Named so that the -k filter of
+# test_bf16_3x3_kernel_generations does not select them: they call conv_bf16_v3.hip directly, PFNL_BF16_V3 changes nothing here.)
+
+def _grid():
+    """The grid of the persistent launches on this device (conv_split16_grid: the CU count rounded down to whole XCDs, at least 8)."""
+    return max(8, torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8)
+
+
+def _within_one_ulp(a, b):
+    """|a - b| <= one bf16 ulp of the larger magnitude, element-wise - above close_bf16's absolute floor of 1e-5: near zero the two fp32
+    summation orders differ by more than a bf16 ulp of the (cancelled) result (observed up to 6e-7)."""
+    a, b = a.float().cpu(), b.float().cpu()
+    m = torch.maximum(a.abs(), b.abs()).clamp_min(2.0 ** -126)
+    ulp = torch.exp2(torch.floor(torch.log2(m)) - 7)
+    d = (a - b).abs()
+    assert bool((d <= ulp + 1e-5).all()), float((d - ulp).max())
+
+
+def _mode1_case(clips, T, H, W, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = r16(torch.randn(clips * T, H, W, 64, generator=g))
+    addend = r16(torch.randn(clips, H, W, 64, generator=g))
+    resid = r16(torch.randn(clips * T, H, W, 64, generator=g))
+    k = (torch.randn(3, 3, 64, 64, generator=g) * 0.05).numpy()
+    b = (torch.randn(64, generator=g) * 0.1).numpy()
+    return x, addend, resid, k, b
+
+
+def _mode2_case(clips, T, H, W, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = r16(torch.randn(clips * T, H, W, 64, generator=g))
+    k1 = (torch.randn(3, 3, 64, 64, generator=g) * 0.05).numpy()
+    b1 = (torch.randn(64, generator=g) * 0.1).numpy()
+    k10 = (torch.randn(1, 1, 64 * T, 64, generator=g) * 0.05).numpy()
+    b10 = (torch.randn(64, generator=g) * 0.1).numpy()
+    return x, k1, b1, k10, b10
+
+
+def _base_ref(out1, k10, b10, T):
+    o = out1.float().cpu()
+    n, H, W = o.shape[0] // T, o.shape[1], o.shape[2]
+    cat = o.reshape(n, T, H, W, 64).permute(0, 2, 3, 1, 4).reshape(n, H, W, T * 64)
+    return F.leaky_relu(cat @ r16(torch.from_numpy(k10[0, 0])) + torch.from_numpy(b10), 0.2)
+
+
+def _bf16_mode1_both_shapes(clips, T, H, W, seed):
+    x, addend, resid, k, b = _mode1_case(clips, T, H, W, seed)
+    xd, ad, rd = (t.to(torch.bfloat16).cuda() for t in (x, addend, resid))
+    ref = ref_conv3(x, k, b, True, addend, T, resid)
+    got = {}
+    for mfma in (16, 32):
+        got[mfma] = ops.conv3x3_bf16_ex(xd, k, b, ad, T, rd, mfma=mfma)
+        assert torch.equal(got[mfma], ops.conv3x3_bf16_ex(xd, k, b, ad, T, rd, mfma=mfma)), mfma
+        close_bf16(got[mfma], ref)
+    _within_one_ulp(got[16], got[32])
+
+
+def _bf16_mode2_both_shapes(clips, T, H, W, seed):
+    x, k1, b1, k10, b10 = _mode2_case(clips, T, H, W, seed)
+    xd = x.to(torch.bfloat16).cuda()
+    ref1 = ref_conv3(x, k1, b1, True)
+    got = {}
+    for mfma in (16, 32):
+        out1, base = ops.conv1_conv10_bf16_ex(xd, k1, b1, k10, b10, T, mfma=mfma)
+        rep1, repb = ops.conv1_conv10_bf16_ex(xd, k1, b1, k10, b10, T, mfma=mfma)
+        assert torch.equal(out1, rep1) and torch.equal(base, repb), mfma
+        close_bf16(out1, ref1)
+        close_bf16(base, _base_ref(out1, k10, b10, T))
+        got[mfma] = out1
+    _within_one_ulp(got[16], got[32])       # (base: each form against the 1x1 of its own, already rounded out1)
+
+
+@pytest.mark.parametrize("clips,T,H,W", [(2, 7, 20, 36), (1, 5, 32, 64), (3, 3, 17, 33)])
+def test_bf16_v3_mode1_mfma16_op(clips, T, H, W):
+    """The fused mode of the third-generation bf16 kernel (per-frame half of conv2_i: act(conv + bias + addend) + resid; reference
+    model/pfnl.py:69-71) in its 16x16x32 form (conv3x3_bf16_pack_weights16) and its 32x32x16 form: each against the torch reference with the
+    same rounding points, each repeatable bit for bit, the two within one bf16 ulp of each other element-wise."""
+    _bf16_mode1_both_shapes(clips, T, H, W, seed=clips * 100 + T)
+
+
+@pytest.mark.parametrize("clips,T,H,W", [(2, 7, 20, 36), (1, 5, 32, 64), (3, 3, 17, 33), (1, 7, 8, 32), (2, 7, 70, 100)])
+def test_bf16_v3_mode2_mfma16_op(clips, T, H, W):
+    """conv1_i + conv10_i in one launch of the third-generation bf16 kernel (reference model/pfnl.py:66-68), 16x16x32 and 32x32x16 forms:
+    out1 and base each against the torch reference (base from the form's own rounded out1), repeatable, out1 within one bf16 ulp across
+    the two forms.  (Bit equality with the plain launch does not carry over: that one is a 32x32x16 kernel.)"""
+    _bf16_mode2_both_shapes(clips, T, H, W, seed=clips * 100 + T + H)
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("case", ["grid-1", "grid", "grid+1", "1.8grid"])
+def test_bf16_v3_mfma16_chain_counts(case, mode):
+    """Both chained modes at chain counts around the launch grid (from the device): clips of 8x32 pixels (one chain each), T = 3."""
+    G = _grid()
+    clips = {"grid-1": G - 1, "grid": G, "grid+1": G + 1, "1.8grid": (9 * G) // 5}[case]
+    (_bf16_mode1_both_shapes if mode == 1 else _bf16_mode2_both_shapes)(clips, 3, 8, 32, seed=clips + mode)
+
+
+def _exact_taps():
+    """One one-hot tap per output channel (ky, kx, ci): every 16-channel output tile sees the 9 taps; ci(co) = (37 co + 5) mod 64 is a
+    permutation of the input channels."""
+    return [(((co * 5 + co // 9) % 9) // 3, ((co * 5 + co // 9) % 9) % 3, (37 * co + 5) % 64) for co in range(64)]
+
+
+def _shifted(x, taps, wval):
+    n, H, W, _ = x.shape
+    pad = torch.zeros(n, H + 2, W + 2, 64)
+    pad[:, 1:H + 1, 1:W + 1] = x
+    out = torch.zeros(n, H, W, 64)
+    for co, (ky, kx, ci) in enumerate(taps):
+        out[..., co] = pad[:, ky:ky + H, kx:kx + W, ci] * float(wval[co])
+    return out
+
+
+@pytest.mark.parametrize("mfma", [16, 32])
+@pytest.mark.parametrize("T,clips,H,W", [(3, 2, 11, 45), (7, 1, 9, 70), (5, 1, 1, 1)])
+def test_bf16_v3_pack_orders_exact(T, clips, H, W, mfma):
+    """Exact answers that pin every entry of conv3x3_bf16_pack_weights16 / conv3x3_bf16_pack_weights (and conv10_i's pack): one one-hot tap
+    of weight +-2^k per output channel, bf16 inputs, so each output is the zero-padded shifted input times a power of two BIT FOR BIT.
+    Mode 1 with act off and zero bias / addend / resid (signed inputs); mode 2 with positive inputs and weights (the leaky-relu is then the
+    identity) and a one-hot conv10_i (frame f(co), channel c(co)), so base is exact as well."""
+    g = torch.Generator().manual_seed(T * 10 + H)
+    taps = _exact_taps()
+    pw = torch.randint(-3, 3, (64,), generator=g).float()
+    sign = torch.where(torch.rand(64, generator=g) < 0.5, -1.0, 1.0)
+    wval = (sign * torch.exp2(pw)).numpy()
+    k = np.zeros((3, 3, 64, 64), np.float32)
+    for co, (ky, kx, ci) in enumerate(taps):
+        k[ky, kx, ci, co] = wval[co]
+    Fr = clips * T
+    x = r16(torch.randn(Fr, H, W, 64, generator=g))
+    zero_a = torch.zeros(clips, H, W, 64, dtype=torch.bfloat16, device="cuda")
+    zero_r = torch.zeros(Fr, H, W, 64, dtype=torch.bfloat16, device="cuda")
+    out = ops.conv3x3_bf16_ex(x.to(torch.bfloat16).cuda(), k, np.zeros(64, np.float32), zero_a, T, zero_r, act=False, mfma=mfma)
+    want = (_shifted(x, taps, wval) + 0.0).to(torch.bfloat16)
+    assert torch.equal(out.cpu().view(torch.int16), want.view(torch.int16)), int((out.cpu() != want).sum())
+    # mode 2: positive inputs and weights
+    xp = x.abs()
+    kp = np.abs(k)
+    k10 = np.zeros((1, 1, 64 * T, 64), np.float32)
+    w10 = np.exp2(torch.randint(-2, 2, (64,), generator=g).float().numpy()).astype(np.float32)
+    for co in range(64):
+        k10[0, 0, (co % T) * 64 + (29 * co + 3) % 64, co] = w10[co]
+    out1, base = ops.conv1_conv10_bf16_ex(xp.to(torch.bfloat16).cuda(), kp, np.zeros(64, np.float32), k10, np.zeros(64, np.float32), T, mfma=mfma)
+    want1 = (_shifted(xp, taps, np.abs(wval)) + 0.0).to(torch.bfloat16)
+    assert torch.equal(out1.cpu().view(torch.int16), want1.view(torch.int16)), int((out1.cpu() != want1).sum())
+    w1 = want1.float().reshape(clips, T, H, W, 64)
+    wantb = torch.stack([w1[:, co % T, :, :, (29 * co + 3) % 64] * float(w10[co]) for co in range(64)], dim=-1).to(torch.bfloat16)
+    assert torch.equal(base.cpu().view(torch.int16), wantb.view(torch.int16)), int((base.cpu() != wantb).sum())
+
+
+# split-chain geometries as in test_gpu_ops.py: (T, clips, H, W, (n_full, split_s, split_q)) with n_full in rounds of the grid
+def _split_case(name, G):
+    if name == "plan-5x128":
+        clips = -(-5 * G // 256)
+        nch = clips * 64
+        R = nch % G
+        q = -(-7 // min(7, G // R))
+        return 7, clips, 128, 128, (nch - R, -(-7 // q), q)
+    return {"T3-q1": (3, G + 5, 8, 32, (G, 3, 1)), "T5-q1": (5, G + 3, 8, 32, (G, 5, 1)), "T7-s2-uneven": (7, 3, 13, 40, (0, 2, 4)),
+            "fills-grid": (7, G // 4, 8, 32, (0, 4, 2)), "ragged-T5": (5, G // 9 + 2, 20, 70, (G, 3, 2)),
+            "nfull0-ragged": (7, 2, 11, 45, (0, 3, 3))}[name]
+
+
+def _split_sel(clips, T, H, W, split):
+    if clips * T * H * W <= 120000:
+        return list(range(clips))
+    return sorted({clips - 1, split[0] // (((W + 31) // 32) * ((H + 7) // 8))})
+
+
+def _clips_of(t, T, sel):
+    return torch.cat([t[c * T:(c + 1) * T] for c in sel])
+
+
+@pytest.mark.parametrize("mfma", [16, 32])
+@pytest.mark.parametrize("name", ["plan-5x128", "T3-q1", "T5-q1", "T7-s2-uneven", "fills-grid", "ragged-T5", "nfull0-ragged"])
+def test_bf16_v3_split_chains_op(name, mfma):
+    """conv_bf16_v3.hip's SPLIT forms (modes 1 and 2; mode 2 + c10_finalize_bf16_kernel) at explicit split geometries, both MFMA shapes:
+    against the torch reference with the same rounding points (on a subset of clips for the large cases), against the same hook uncut
+    (bf16 rounding of another summation order) and repeatable bit for bit."""
+    G = _grid()
+    T, clips, H, W, split = _split_case(name, G)
+    sel = _split_sel(clips, T, H, W, split)
+    x, addend, resid, k, b = _mode1_case(clips, T, H, W, seed=len(name) + mfma)
+    xd, ad, rd = (t.to(torch.bfloat16).cuda() for t in (x, addend, resid))
+    got = ops.conv3x3_bf16_ex(xd, k, b, ad, T, rd, mfma=mfma, split=split)
+    assert torch.equal(got, ops.conv3x3_bf16_ex(xd, k, b, ad, T, rd, mfma=mfma, split=split))
+    close_bf16(got, ops.conv3x3_bf16_ex(xd, k, b, ad, T, rd, mfma=mfma).float().cpu())
+    close_bf16(_clips_of(got, T, sel), ref_conv3(_clips_of(x, T, sel), k, b, True, addend[sel], T, _clips_of(resid, T, sel)))
+    del xd, ad, rd, got
+    x, k1, b1, k10, b10 = _mode2_case(clips, T, H, W, seed=len(name) * 3 + mfma)
+    xd = x.to(torch.bfloat16).cuda()
+    out1, base = ops.conv1_conv10_bf16_ex(xd, k1, b1, k10, b10, T, mfma=mfma, split=split)
+    rep1, repb = ops.conv1_conv10_bf16_ex(xd, k1, b1, k10, b10, T, mfma=mfma, split=split)
+    assert torch.equal(out1, rep1) and torch.equal(base, repb)
+    un1, unb = ops.conv1_conv10_bf16_ex(xd, k1, b1, k10, b10, T, mfma=mfma)
+    close_bf16(out1, un1.float().cpu())
+    close_bf16(base, unb.float().cpu())
+    o1 = _clips_of(out1.cpu(), T, sel)
+    close_bf16(o1, ref_conv3(_clips_of(x, T, sel), k1, b1, True))
+    close_bf16(base.cpu()[sel], _base_ref(o1, k10, b10, T))
+
+
+def test_bf16_v3_split_hooks_refuse_bad_geometries():
+    """The bf16 v4 hooks refuse split geometries outside the rule of b3_split_ok on the host, before any launch, and leave out untouched."""
+    from pfnl_amd import _capi
+    G = _grid()
+    T, H, W = 7, 8, 32
+    g = torch.Generator().manual_seed(9)
+    k = (torch.randn(3, 3, 64, 64, generator=g) * 0.05).numpy()
+    k10 = (torch.randn(1, 1, 64 * T, 64, generator=g) * 0.05).numpy()
+    b = np.zeros(64, np.float32)
+    for clips, split in ((G + 2, (G - 1, 4, 2)), (G + 2, (G, 3, 2)), (G + 2, (G, 4, 3)), (G + G // 2, (G, 4, 2)), (G, (G, 2, 4))):
+        x = torch.randn(clips * T, H, W, 64, generator=g).to(torch.bfloat16).cuda()
+        a = torch.zeros(clips, H, W, 64, dtype=torch.bfloat16, device="cuda")
+        out = torch.full((clips * T, H, W, 64), float("nan"), dtype=torch.bfloat16, device="cuda")
+        with pytest.raises(_capi.PFNLHipError, match="split-chain geometry"):
+            ops.conv3x3_bf16_ex(x, k, b, a, T, x, mfma=16, split=split, out=out)
+        out1 = torch.full_like(out, float("nan"))
+        base = torch.full((clips, H, W, 64), float("nan"), dtype=torch.bfloat16, device="cuda")
+        with pytest.raises(_capi.PFNLHipError, match="split-chain geometry"):
+            ops.conv1_conv10_bf16_ex(x, k, b, k10, b, T, mfma=32, split=split, out1=out1, base=base)
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(out.float()).all() and torch.isnan(out1.float()).all() and torch.isnan(base.float()).all()), (clips, split)

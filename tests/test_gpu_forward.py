@@ -19,6 +19,17 @@ from pfnl_amd.spec import PFNLGeometry  # noqa: E402
 PSNR_TOL_DB = 0.01          # BASELINE.json: |dPSNR| <= 0.01 dB (fp32)
 ABS_TOL = 5e-5              # direct element-wise bound on [0,1]-scale outputs (observed ~1e-5)
 
+
+def _split_grid():
+    """The grid of the persistent launches on this device (conv_split16_grid: the CU count rounded down to whole XCDs, at least 8)."""
+    return max(8, torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8)
+
+
+def _plan_cuts(chains, T, G):
+    """trunk_plan's split-chain rule: a last, partial round of R chains is cut when at least two parts of a chain fit the idle workgroups."""
+    R = chains % G
+    return chains > G and 0 < R <= G // 2 and min(T, G // R) >= 2
+
 _engines = {}
 
 
@@ -618,10 +629,13 @@ def test_chain_launch_mfma_shapes():
     w = synth.synthetic_weights(geom, seed=3)
     eng = _engine_with(geom, w)
     fo = pfnl_fast.FastOracle(w, 7, 4, 3)
-    for B, H, W, want in ((4, 128, 128, 16), (2, 180, 318, 16), (1, 180, 318, 32), (5, 128, 128, 32), (1, 64, 64, 32)):
+    G = _split_grid()
+    for B, H, W in ((4, 128, 128), (2, 180, 318), (1, 180, 318), (5, 128, 128), (1, 64, 64)):
         x = synth.uniform_clips(B, 7, H, W, seed=B + W)
         assert eng.get_option("split16_mfma") == "16"
         pl = eng.plan(B, H, W)
+        chains = B * ((W + 31) // 32) * ((H + 7) // 8)
+        want = 16 if chains >= G and not _plan_cuts(chains, 7, G) else 32      # (256 CUs: 16, 16, 32, 32, 32)
         assert pl["mfma"] == want, (B, H, W, pl)
         y16 = eng.forward(x)
         assert np.array_equal(y16, eng.forward(x))
@@ -683,15 +697,16 @@ def test_forward_split_chains(T, scale, nb, H, W, Bs):
     assert eng.get_option("split16_splitchains") == "auto"
     fo = pfnl_fast.FastOracle(w, T, scale, nb) if nb <= 3 else None
     chains_clip = ((W + 31) // 32) * ((H + 7) // 8)
+    G = _split_grid()
     for B in Bs:
         x = synth.uniform_clips(B, T, H, W, seed=100 + H)         # (the first clips of every batch are the same clips)
         pl = eng.plan(B, H, W)
-        R = (B * chains_clip) % 256
-        cut = B * chains_clip > 256 and 0 < R <= 128 and min(T, 256 // R) >= 2
+        R = (B * chains_clip) % G
+        cut = _plan_cuts(B * chains_clip, T, G)
         assert pl["structure"] == ("chain2_split" if cut else "chain2"), (B, pl)
         if cut:
             assert pl["whole_chains"] == B * chains_clip - R and pl["split_parts"] * pl["part_frames"] >= T > (pl["split_parts"] - 1) * pl["part_frames"]
-            assert (B * chains_clip - pl["whole_chains"]) * pl["split_parts"] <= 256 and pl["launches_per_block"] == 3 and pl["c1x1"] == 1
+            assert (B * chains_clip - pl["whole_chains"]) * pl["split_parts"] <= G and pl["launches_per_block"] == 3 and pl["c1x1"] == 1
             eng.profile(1)
             eng.profile_reset()
             eng.forward(x)

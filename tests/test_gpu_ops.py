@@ -780,3 +780,301 @@ def test_round4_kernels_random_geometries_short():
     spec.loader.exec_module(mod)
     n, worst = mod.run(seed=11, seconds=6.0)
     assert n >= 20 and worst < 3e-5, (n, worst)
+
+
+# ---- C-ABI v4 hooks: the 16x16x32 chain kernel and split chains, op by op ------------------------------------------------------------------
+
+def _grid():
+    """The grid of the persistent split-f16 launches on this device (conv_split16_grid: the CU count rounded down to whole XCDs, at least 8)."""
+    return max(8, torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8)
+
+
+def _chains(clips, H, W):
+    return clips * ((W + 31) // 32) * ((H + 7) // 8)
+
+
+def _chain_ref(x, base, res, k2, b, T, clips_sel, act=True):
+    """fp64 spec of conv2_i (reference model/pfnl.py:69-71) on the selected clips: [len(sel)*T, H, W, 64]."""
+    xs = np.concatenate([x[c * T:(c + 1) * T] for c in clips_sel]).astype(np.float64)
+    bs = np.repeat(base[clips_sel].astype(np.float64), T, axis=0)
+    y = pfnl_spec.conv2d_same(np.concatenate([bs, xs], axis=-1), k2.astype(np.float64), b.astype(np.float64))
+    if act:
+        y = pfnl_spec.lrelu(y)
+    return y + np.concatenate([res[c * T:(c + 1) * T] for c in clips_sel])
+
+
+def _frames_of(a, T, clips_sel):
+    return np.concatenate([a[c * T:(c + 1) * T] for c in clips_sel])
+
+
+def _clip_subset(clips, grid, per_clip):
+    """The clips the fp64 spec runs on for large cases: the first, the last, and those holding the chains at round boundaries."""
+    sel = {0, clips - 1}
+    for r in range(1, clips * per_clip // grid + 1):
+        for ch in (r * grid - 1, r * grid):
+            if ch < clips * per_clip:
+                sel.add(ch // per_clip)
+    return sorted(sel)
+
+
+def _conv2_chain_mfma_case(T, clips, H, W, seed):
+    rng = np.random.default_rng(seed)
+    F = clips * T
+    x = rng.normal(size=(F, H, W, 64)).astype(np.float32)
+    base = rng.normal(size=(clips, H, W, 64)).astype(np.float32)
+    res = rng.normal(size=(F, H, W, 64)).astype(np.float32)
+    k2 = (rng.normal(size=(3, 3, 128, 64)) / 34.0).astype(np.float32)
+    b = (rng.normal(size=64) * 0.1).astype(np.float32)
+    xd, bd, rd = dev(x), dev(base), dev(res)
+    got = {}
+    for mfma in (32, 16):
+        got[mfma] = ops.conv2_chain_ex(xd, k2, b, bd, rd, T, mfma=mfma).cpu().numpy()
+        again = ops.conv2_chain_ex(xd, k2, b, bd, rd, T, mfma=mfma).cpu().numpy()
+        assert np.array_equal(got[mfma].view(np.uint32), again.view(np.uint32)), mfma
+    per_clip = _chains(1, H, W)
+    sel = list(range(clips)) if F * H * W <= 200000 else _clip_subset(clips, _grid(), per_clip)
+    ref = _chain_ref(x, base, res, k2, b, T, sel)
+    scale = max(1.0, np.abs(ref).max())
+    for mfma in (32, 16):
+        e = np.abs(_frames_of(got[mfma], T, sel) - ref).max()
+        assert e < 4e-6 * scale, (mfma, e)
+    d = np.abs(got[16] - got[32]).max()
+    assert d < 2e-6 * max(1.0, np.abs(got[32]).max()), d
+    return got
+
+
+@pytest.mark.parametrize("T,clips,H,W", [(7, 1, 8, 32), (7, 2, 10, 38), (5, 1, 33, 70), (3, 3, 16, 24), (7, 4, 128, 128), (7, 1, 1, 1), (7, 3, 9, 130)])
+def test_conv2_chain_mfma16_against_spec(T, clips, H, W):
+    """conv3x3_sf_chain16_kernel (the 16x16x32 form of the conv2_i chain launch, on conv3x3_split16_pack_weights16's packs; reference
+    model/pfnl.py:69-71) and the 32x32x16 form through pfnl_op_conv2_chain_ex: each against the fp64 spec of the concat form, against each
+    other (summation order only), and repeatable bit for bit - on test_conv2_chain_sf's geometries (T = 7 / 5 / 3, ragged, 1x1)."""
+    _conv2_chain_mfma_case(T, clips, H, W, seed=T * 1000 + H * 10 + W)
+
+
+@pytest.mark.parametrize("case", ["grid-1", "grid", "grid+1", "1.8grid", "ragged-T5"])
+def test_conv2_chain_mfma16_chain_counts(case):
+    """The 16x16x32 chain kernel at chain counts around the launch grid (taken from the device): one chain short of a round, a whole round,
+    one chain over it, a partial last round of ~0.8 (trunk_plan sends such batches to it), and a ragged T = 5 case of 20x70 clips over
+    ~1.5 rounds.  Clips of 8x32 pixels are one chain each; the fp64 spec runs on the first and last clips and those at round boundaries."""
+    G = _grid()
+    if case == "ragged-T5":
+        T, H, W = 5, 20, 70
+        clips = -(-3 * G // (2 * _chains(1, H, W)))
+    else:
+        T, H, W = 3, 8, 32
+        clips = {"grid-1": G - 1, "grid": G, "grid+1": G + 1, "1.8grid": (9 * G) // 5}[case]
+    _conv2_chain_mfma_case(T, clips, H, W, seed=clips * 10 + T)
+
+
+def _exact_taps(ncin):
+    """One one-hot tap per output channel: co -> (ky, kx, ci(co)); the 64 channels cover the 9 taps in every 16-channel output tile and,
+    for ncin = 128, both input halves (base and frame) - ci(co) = (37 co + 5) mod ncin is injective."""
+    taps = []
+    for co in range(64):
+        t = (co * 5 + co // 9) % 9
+        taps.append((t // 3, t % 3, (37 * co + 5) % ncin))
+    return taps
+
+
+def _shift_ref(inp, taps, wval):
+    """out[..., co] = w(co) * inp[y + ky - 1, x + kx - 1, ci(co)] with zero padding, in fp32 (exact by construction), + 0."""
+    n, H, W, _ = inp.shape
+    pad = np.zeros((n, H + 2, W + 2, inp.shape[-1]), np.float32)
+    pad[:, 1:H + 1, 1:W + 1] = inp
+    out = np.zeros((n, H, W, 64), np.float32)
+    for co, (ky, kx, ci) in enumerate(taps):
+        out[..., co] = pad[:, ky:ky + H, kx:kx + W, ci] * wval[co]
+    return out + np.float32(0.0)
+
+
+def _bits22(rng, shape):
+    """Values with 22 significant bits (hi and lo' of the split both exact)."""
+    m = rng.integers(2 ** 21, 2 ** 22, size=shape).astype(np.float64) * rng.choice([-1.0, 1.0], size=shape)
+    return (m * 2.0 ** (rng.integers(-2, 3, size=shape) - 21)).astype(np.float32)
+
+
+def _bits2(rng, shape):
+    """Values with at most 2 significant bits (lo' = 0)."""
+    m = rng.choice([2.0, 3.0], size=shape) * rng.choice([-1.0, 1.0], size=shape)
+    return (m * 2.0 ** rng.integers(-3, 2, size=shape)).astype(np.float32)
+
+
+@pytest.mark.parametrize("variant", ["x22_wpow2", "x2_w22"])
+@pytest.mark.parametrize("T,clips,H,W", [(3, 2, 11, 45), (5, 1, 9, 70), (7, 1, 1, 1)])
+def test_conv2_chain_pack_orders_exact(variant, T, clips, H, W):
+    """Exact answers that pin every entry of conv3x3_split16_pack_weights16 (and of the 32x32x16 packs): each output channel gets one one-hot
+    tap, act off, zero bias and resid, per-clip-distinct base, so the output is the zero-padded shifted input times the weight BIT FOR BIT.
+    x22_wpow2: inputs of 22 significant bits, weights +-2^k (the x_lo' * w_hi products); x2_w22: inputs of 2 significant bits, weights of
+    22 bits (the x_hi * w_lo' products).  A swapped 16-channel tile or a dropped lo' term cannot pass."""
+    rng = np.random.default_rng(T * 100 + H + W)
+    F = clips * T
+    mk_x, mk_w = (_bits22, lambda r, s: (r.choice([-1.0, 1.0], size=s) * 2.0 ** r.integers(-3, 3, size=s)).astype(np.float32)) \
+        if variant == "x22_wpow2" else (_bits2, lambda r, s: np.abs(_bits22(r, s)) * np.float32(0.25))
+    x, base = mk_x(rng, (F, H, W, 64)), mk_x(rng, (clips, H, W, 64))
+    taps = _exact_taps(128)
+    wval = mk_w(rng, (64,))
+    k2 = np.zeros((3, 3, 128, 64), np.float32)
+    for co, (ky, kx, ci) in enumerate(taps):
+        k2[ky, kx, ci, co] = wval[co]
+    inp = np.concatenate([np.repeat(base, T, axis=0), x], axis=-1)
+    want = _shift_ref(inp, taps, wval)
+    zero = np.zeros((F, H, W, 64), np.float32)
+    for mfma in (32, 16):
+        got = ops.conv2_chain_ex(dev(x), k2, np.zeros(64, np.float32), dev(base), dev(zero), T, act=False, mfma=mfma).cpu().numpy()
+        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+        assert bad.size == 0, (mfma, len(bad), bad[:4], got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+# split-chain geometries (n_full in rounds of the grid, clips of H x W): the plan's own cut, T = 3 / 5 with one frame per part, two uneven parts,
+# parts that fill the grid exactly, cut chains with ragged tiles (the cut starting inside a clip), and workgroups with no whole chain holding
+# parts r > 0 (n_full = 0)
+def _split_case(name, G):
+    if name == "plan-5x128":
+        T, H, W = 7, 128, 128
+        clips = -(-5 * G // (4 * 64))                               # 1.25 rounds: 5 clips on 256 workgroups
+        nch = _chains(clips, H, W)
+        R = nch % G
+        s0 = min(T, G // R)
+        q = -(-T // s0)
+        return T, clips, H, W, (nch - R, -(-T // q), q)
+    if name == "T3-q1":
+        return 3, G + 5, 8, 32, (G, 3, 1)
+    if name == "T5-q1":
+        return 5, G + 3, 8, 32, (G, 5, 1)
+    if name == "T7-s2-uneven":
+        return 7, 3, 13, 40, (0, 2, 4)
+    if name == "fills-grid":
+        return 7, G // 4, 8, 32, (0, 4, 2)
+    if name == "ragged-T5":
+        return 5, G // 9 + 2, 20, 70, (G, 3, 2)
+    if name == "nfull0-ragged":
+        return 7, 2, 11, 45, (0, 3, 3)
+    raise KeyError(name)
+
+
+SPLIT_CASES = ["plan-5x128", "T3-q1", "T5-q1", "T7-s2-uneven", "fills-grid", "ragged-T5", "nfull0-ragged"]
+
+
+def _split_subset(name, T, clips, H, W, split, G):
+    """Clips the fp64 spec runs on: all of them for small cases; else the first clip holding a cut chain and the last one."""
+    if clips * T * H * W <= 120000:
+        return list(range(clips))
+    return sorted({clips - 1, split[0] // _chains(1, H, W)})
+
+
+@pytest.mark.parametrize("name", SPLIT_CASES)
+def test_conv1_conv10_split_chains_op(name):
+    """conv3x3_c1c10_kernel<., SPLIT> + c10_finalize_kernel (reference model/pfnl.py:66-68) at explicit split geometries: inp1 and base
+    against the fp64 spec, against the uncut launch (summation order of conv10_i's parts only) and repeatable bit for bit."""
+    G = _grid()
+    T, clips, H, W, split = _split_case(name, G)
+    rng = np.random.default_rng(len(name) * 7 + T)
+    F = clips * T
+    x = rng.normal(size=(F, H, W, 64)).astype(np.float32)
+    k1 = (rng.normal(size=(3, 3, 64, 64)) / 24.0).astype(np.float32)
+    b1 = (rng.normal(size=64) * 0.1).astype(np.float32)
+    k10 = (rng.normal(size=(1, 1, 64 * T, 64)) / np.sqrt(64 * T)).astype(np.float32)
+    b10 = (rng.normal(size=64) * 0.1).astype(np.float32)
+    xd = dev(x)
+    got1, gotb = (t.cpu().numpy() for t in ops.conv1_conv10_split16_ex(xd, k1, b1, k10, b10, T, split=split))
+    rep1, repb = (t.cpu().numpy() for t in ops.conv1_conv10_split16_ex(xd, k1, b1, k10, b10, T, split=split))
+    assert np.array_equal(got1.view(np.uint32), rep1.view(np.uint32)) and np.array_equal(gotb.view(np.uint32), repb.view(np.uint32))
+    un1, unb = (t.cpu().numpy() for t in ops.conv1_conv10_split16_ex(xd, k1, b1, k10, b10, T))
+    sel = _split_subset(name, T, clips, H, W, split, G)
+    ref1 = pfnl_spec.lrelu(pfnl_spec.conv2d_same(_frames_of(x, T, sel).astype(np.float64), k1.astype(np.float64), b1.astype(np.float64)))
+    cat = ref1.reshape(len(sel), T, H, W, 64).transpose(0, 2, 3, 1, 4).reshape(len(sel), H, W, T * 64)
+    refb = pfnl_spec.lrelu(pfnl_spec.conv2d_same(cat, k10.astype(np.float64), b10.astype(np.float64)))
+    s1, sb = max(1.0, np.abs(ref1).max()), max(1.0, np.abs(refb).max())
+    e1, eb = np.abs(_frames_of(got1, T, sel) - ref1).max(), np.abs(gotb[sel] - refb).max()
+    assert e1 < 4e-6 * s1 and eb < 4e-6 * sb, (e1, eb)
+    d1, db = np.abs(got1 - un1).max(), np.abs(gotb - unb).max()
+    assert d1 <= 2.0 ** -20 * s1 and db < 2e-6 * sb, (d1, db)
+
+
+@pytest.mark.parametrize("name", SPLIT_CASES)
+def test_conv2_chain_split_chains_op(name):
+    """conv3x3_sf_chain_kernel<false, true> (the 32x32x16 chain launch cut by frames; reference model/pfnl.py:69-71) at explicit split
+    geometries: against the fp64 spec, the uncut launch and itself (bit for bit)."""
+    G = _grid()
+    T, clips, H, W, split = _split_case(name, G)
+    rng = np.random.default_rng(len(name) * 11 + T)
+    F = clips * T
+    x = rng.normal(size=(F, H, W, 64)).astype(np.float32)
+    base = rng.normal(size=(clips, H, W, 64)).astype(np.float32)
+    res = rng.normal(size=(F, H, W, 64)).astype(np.float32)
+    k2 = (rng.normal(size=(3, 3, 128, 64)) / 34.0).astype(np.float32)
+    b = (rng.normal(size=64) * 0.1).astype(np.float32)
+    xd, bd, rd = dev(x), dev(base), dev(res)
+    got = ops.conv2_chain_ex(xd, k2, b, bd, rd, T, split=split).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), ops.conv2_chain_ex(xd, k2, b, bd, rd, T, split=split).cpu().numpy().view(np.uint32))
+    uncut = ops.conv2_chain_ex(xd, k2, b, bd, rd, T).cpu().numpy()
+    sel = _split_subset(name, T, clips, H, W, split, G)
+    ref = _chain_ref(x, base, res, k2, b, T, sel)
+    scale = max(1.0, np.abs(ref).max())
+    e, d = np.abs(_frames_of(got, T, sel) - ref).max(), np.abs(got - uncut).max()
+    assert e < 4e-6 * scale and d < 2e-6 * scale, (e, d)
+
+
+@pytest.mark.parametrize("name", SPLIT_CASES)
+def test_conv3x3_accum_split_chains_op(name):
+    """convmerge1's split launch (conv3x3_split16_kernel<2, false, true> + c10_finalize_kernel with out; reference model/pfnl.py:52, 73-74) at
+    explicit split geometries, cout = 48 as the model's: against the fp64 spec, the uncut launch and itself.  The n_full = 0 cases hold
+    workgroups whose part starts at frame sp_f0 > 0 without a whole chain in front: their first weights must be that frame's."""
+    G = _grid()
+    T, clips, H, W, split = _split_case(name, G)
+    rng = np.random.default_rng(len(name) * 13 + T)
+    F, cout = clips * T, 48
+    x = rng.normal(size=(F, H, W, 64)).astype(np.float32)
+    k = (rng.normal(size=(3, 3, 64 * T, cout)) / np.sqrt(576 * T)).astype(np.float32)
+    b = (rng.normal(size=cout) * 0.1).astype(np.float32)
+    xd = dev(x)
+    got = ops.conv3x3_accum_split16_ex(xd, k, b, act=True, frames_per_clip=T, split=split).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), ops.conv3x3_accum_split16_ex(xd, k, b, act=True, frames_per_clip=T, split=split).cpu().numpy().view(np.uint32))
+    uncut = ops.conv3x3_accum_split16_ex(xd, k, b, act=True, frames_per_clip=T).cpu().numpy()
+    sel = _split_subset(name, T, clips, H, W, split, G)
+    xc = _frames_of(x, T, sel).reshape(len(sel), T, H, W, 64).transpose(0, 2, 3, 1, 4).reshape(len(sel), H, W, 64 * T)
+    ref = pfnl_spec.lrelu(pfnl_spec.conv2d_same(xc.astype(np.float64), k.astype(np.float64), b.astype(np.float64)))
+    scale = max(1.0, np.abs(ref).max())
+    e, d = np.abs(got[sel][..., :cout] - ref).max(), np.abs(got - uncut).max()
+    assert e < 4e-6 * scale and d < 2e-6 * scale, (e, d)
+    assert not got[..., cout:].any()
+
+
+def test_split_chain_hooks_refuse_bad_geometries():
+    """The v4 hooks check the split geometry on the host before any launch (the rule of split_params_ok): a refused call raises and leaves
+    `out` as it was (NaN sentinel).  n_full not a multiple of the grid, parts that do not cover the T frames, an empty last part, more parts
+    than workgroups, and the 16x16x32 chain kernel with a cut (it has no split form)."""
+    from pfnl_amd import _capi
+    G = _grid()
+    T, H, W = 7, 8, 32
+    rng = np.random.default_rng(5)
+    bad = {"n_full % grid": (G + 2, G - 1, 4, 2), "s*q < T": (G + 2, G, 3, 2), "(s-1)q >= T": (G + 2, G, 4, 3),
+           "parts > grid": (G + G // 2, G, 4, 2), "n_full >= chains": (G, G, 2, 4)}
+    k2 = (rng.normal(size=(3, 3, 128, 64)) / 34.0).astype(np.float32)
+    k1 = (rng.normal(size=(3, 3, 64, 64)) / 24.0).astype(np.float32)
+    k10 = (rng.normal(size=(1, 1, 64 * T, 64)) / 24.0).astype(np.float32)
+    km = (rng.normal(size=(3, 3, 64 * T, 48)) / 24.0).astype(np.float32)
+    b = np.zeros(64, np.float32)
+    for label, (clips, n_full, s, q) in bad.items():
+        split = (n_full, s, q)
+        x = dev(rng.normal(size=(clips * T, H, W, 64)))
+        base = dev(rng.normal(size=(clips, H, W, 64)))
+        nan = lambda shape: torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")  # noqa: E731
+        calls = [("chain", lambda o: ops.conv2_chain_ex(x, k2, b, base, x, T, split=split, out=o[0]), [(clips * T, H, W, 64)]),
+                 ("c1c10", lambda o: ops.conv1_conv10_split16_ex(x, k1, b, k10, b, T, split=split, out1=o[0], base=o[1]),
+                  [(clips * T, H, W, 64), (clips, H, W, 64)]),
+                 ("merge1", lambda o: ops.conv3x3_accum_split16_ex(x, km, b[:48], frames_per_clip=T, split=split, out=o[0]), [(clips, H, W, 64)])]
+        for name, call, shapes in calls:
+            outs = [nan(sh) for sh in shapes]
+            with pytest.raises(_capi.PFNLHipError, match="split-chain geometry"):
+                call(outs)
+            torch.cuda.synchronize()
+            assert all(bool(torch.isnan(o).all()) for o in outs), (label, name)
+    clips = G + 2
+    x = dev(rng.normal(size=(clips * 3, H, W, 64)))
+    base = dev(rng.normal(size=(clips, H, W, 64)))
+    out = torch.full((clips * 3, H, W, 64), float("nan"), dtype=torch.float32, device="cuda")
+    with pytest.raises(_capi.PFNLHipError, match="32x32x16"):
+        ops.conv2_chain_ex(x, k2, b, base, x, 3, mfma=16, split=(G, 3, 1), out=out)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all())
