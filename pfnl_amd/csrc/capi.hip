@@ -37,13 +37,6 @@ int pfnl_internal_fail(int code, const std::string& msg) { return fail(code, msg
 
 namespace {
 
-#define HIPCHK(expr)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess)                                                                \
-            return fail(PFNL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));    \
-    } while (0)
-
 static unsigned long long g_alloc_gen = 0;   // bumped whenever a device buffer moves: captured graphs hold raw pointers
 
 struct DevBuf {
@@ -1024,7 +1017,103 @@ int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull
     return 0;
 }
 
+// ---- the options of pfnl_set_option / pfnl_get_option: each key sets one int or bool field of the handle (a bool takes 0 / 1) to the value
+// of one of its names; the first name of a value is the one pfnl_get_option returns.  nl_sub_sample (an integer) and bf16_nonlocal (f16
+// only) are the two keys outside the table.
+struct OptionField {
+    int pfnl_handle::*i = nullptr;
+    bool pfnl_handle::*b = nullptr;
+    constexpr OptionField(int pfnl_handle::*f) : i(f) {}
+    constexpr OptionField(bool pfnl_handle::*f) : b(f) {}
+    int get(const pfnl_handle* h) const { return i ? h->*i : (int)(h->*b); }
+    void set(pfnl_handle* h, int v) const {
+        if (i) h->*i = v;
+        else h->*b = v != 0;
+    }
+};
+
+struct OptionName {
+    const char* name;   // (null: past the last name)
+    int value;
+};
+
+struct OptionSpec {
+    const char* key;
+    OptionField field;
+    OptionName names[8];
+    const char* refusal;
+};
+
+const OptionSpec kOptions[] = {
+    {"graph", &pfnl_handle::graph_mode, {{"auto", 1}, {"on", 2}, {"off", 0}}, "graph must be auto, on or off"},
+    {"conv3x3", &pfnl_handle::conv_algo, {{"winograd", 3}, {"winograd_ws", 3}, {"winograd_tile", 1}, {"direct", 0}, {"split16", 4}, {"auto", 5}},
+     "conv3x3 must be auto, split16, winograd, winograd_tile or direct"},
+    {"strict_fp32", &pfnl_handle::strict, {{"on", 1}, {"off", 0}}, "strict_fp32 must be on or off"},
+    {"small", &pfnl_handle::small_mode, {{"auto", 0}, {"on", 1}, {"off", 2}}, "small must be auto, on or off"},
+    {"split16_chain", &pfnl_handle::sf_chain, {{"on", 1}, {"off", 0}}, "split16_chain must be on or off"},
+    {"split16_c10", &pfnl_handle::sf_c10, {{"on", 1}, {"off", 0}}, "split16_c10 must be on or off"},
+    {"split16_mid", &pfnl_handle::sf_mid, {{"auto", 1}, {"off", 0}}, "split16_mid must be auto or off"},
+    {"split16_sf0", &pfnl_handle::sf0, {{"on", 1}, {"off", 0}}, "split16_sf0 must be on or off"},
+    {"split16_splitchains", &pfnl_handle::split_chains, {{"auto", 1}, {"off", 0}}, "split16_splitchains must be auto or off"},
+    {"split16_sf", &pfnl_handle::sf_path, {{"on", 1}, {"off", 0}}, "split16_sf must be on or off"},
+    {"conv2", &pfnl_handle::conv2_grouped, {{"grouped", 1}, {"split", 0}}, "conv2 must be grouped or split"},
+    {"split16_mfma", &pfnl_handle::s16_m16, {{"16", 1}, {"32", 0}}, "split16_mfma must be 16 or 32"},
+    {"bf16_mfma", &pfnl_handle::bf16_m16, {{"16", 1}, {"32", 0}}, "bf16_mfma must be 16 or 32"},
+    {"bf16_conv10", &pfnl_handle::bf16_fuse10, {{"fused", 1}, {"separate", 0}}, "bf16_conv10 must be fused or separate"},
+    {"precision", &pfnl_handle::bf16, {{"bf16", 1}, {"fp32", 0}}, "precision must be fp32 or bf16"},
+    {"merge1", &pfnl_handle::m1_algo, {{"auto", 0}, {"split16", 1}, {"winograd", 2}}, "merge1 must be auto, split16 or winograd"},
+    {"nl_type", &pfnl_handle::nl_type,
+     {{"auto", -1}, {"0", 0}, {"embedded_gaussian", 0}, {"1", 1}, {"gaussian", 1}, {"2", 2}, {"dot_product", 2}},
+     "nl_type: auto | 0 | 1 | 2 (nltype 3, 'concat', builds no graph in the reference either: utils.py:23)"},
+    {"small_c10", &pfnl_handle::small_c10, {{"on", 1}, {"off", 0}}, "small_c10 must be on or off"},
+    {"nonlocal", &pfnl_handle::nl_algo, {{"f32", 0}, {"split16", 1}, {"auto", 2}}, "nonlocal must be auto, f32 or split16"},
+    {"conv1x1", &pfnl_handle::conv1x1_algo, {{"stream", 1}, {"tiled", 0}, {"split16", 2}}, "conv1x1 must be split16, stream or tiled"},
+};
+
+const OptionSpec* find_option(const std::string& key) {
+    for (const OptionSpec& o : kOptions)
+        if (key == o.key) return &o;
+    return nullptr;
+}
+
 }  // namespace
+
+void pfnl_nl_fold_gw(const float* wg, const float* bg, const float* ww, const float* bw, int C, int CP, float* Wf, float* bf) {
+    for (int ci = 0; ci < C; ++ci)
+        for (int co = 0; co < C; ++co) {
+            double acc = 0.0;
+            for (int cm = 0; cm < C; ++cm) acc += (double)wg[(size_t)ci * C + cm] * (double)ww[(size_t)cm * C + co];
+            Wf[(size_t)ci * CP + co] = (float)acc;
+        }
+    for (int co = 0; co < C; ++co) {
+        double acc = bw[co];
+        for (int cm = 0; cm < C; ++cm) acc += (double)bg[cm] * (double)ww[(size_t)cm * C + co];
+        bf[co] = (float)acc;
+    }
+}
+
+void pfnl_nl_fold_theta_phi(const float* wt, const float* bt, const float* wp, const float* bp, int C, int CP, float* Mf, float* cf) {
+    for (int ci = 0; ci < C; ++ci)
+        for (int cj = 0; cj < C; ++cj) {
+            double acc = 0.0;
+            for (int cm = 0; cm < C; ++cm) acc += (double)wt[(size_t)ci * C + cm] * (double)wp[(size_t)cj * C + cm];
+            Mf[(size_t)ci * CP + cj] = (float)acc;
+        }
+    for (int cj = 0; cj < C; ++cj) {
+        double acc = 0.0;
+        for (int cm = 0; cm < C; ++cm) acc += (double)bt[cm] * (double)wp[(size_t)cj * C + cm];
+        cf[cj] = (float)acc;
+    }
+    if (!bp) return;
+    double d0 = 0.0;
+    for (int cm = 0; cm < C; ++cm) d0 += (double)bt[cm] * (double)bp[cm];
+    cf[C] = (float)d0;
+    for (int ci = 0; ci < C; ++ci) {
+        double acc = 0.0;
+        for (int cm = 0; cm < C; ++cm) acc += (double)wt[(size_t)ci * C + cm] * (double)bp[cm];
+        Mf[(size_t)ci * CP + C] = (float)acc;
+    }
+}
 
 extern "C" {
 
@@ -1155,148 +1244,24 @@ int pfnl_set_option(pfnl_handle* h, const char* key, const char* value) {
     if (!h || !key || !value) return fail(PFNL_ERR_INVALID, "NULL argument");
     const std::string k(key), v(value);
     ++h->cfg_gen;
-    if (k == "graph") {
-        if (v == "auto") h->graph_mode = 1;
-        else if (v == "on") h->graph_mode = 2;
-        else if (v == "off") h->graph_mode = 0;
-        else return fail(PFNL_ERR_INVALID, "graph must be auto, on or off");
-        return 0;
-    }
-    if (k == "conv3x3") {
-        if (v == "winograd" || v == "winograd_ws") h->conv_algo = 3;
-        else if (v == "winograd_tile") h->conv_algo = 1;
-        else if (v == "direct") h->conv_algo = 0;
-        else if (v == "split16") h->conv_algo = 4;
-        else if (v == "auto") h->conv_algo = 5;
-        else return fail(PFNL_ERR_INVALID, "conv3x3 must be auto, split16, winograd, winograd_tile or direct");
-        return 0;
-    }
-    if (k == "strict_fp32") {
-        if (v == "on") h->strict = true;
-        else if (v == "off") h->strict = false;
-        else return fail(PFNL_ERR_INVALID, "strict_fp32 must be on or off");
-        return 0;
-    }
-    if (k == "small") {
-        if (v == "auto") h->small_mode = 0;
-        else if (v == "on") h->small_mode = 1;
-        else if (v == "off") h->small_mode = 2;
-        else return fail(PFNL_ERR_INVALID, "small must be auto, on or off");
-        return 0;
-    }
-    if (k == "split16_chain") {
-        if (v == "on") h->sf_chain = true;
-        else if (v == "off") h->sf_chain = false;
-        else return fail(PFNL_ERR_INVALID, "split16_chain must be on or off");
-        return 0;
-    }
-    if (k == "split16_c10") {
-        if (v == "on") h->sf_c10 = true;
-        else if (v == "off") h->sf_c10 = false;
-        else return fail(PFNL_ERR_INVALID, "split16_c10 must be on or off");
-        return 0;
-    }
-    if (k == "split16_mid") {
-        if (v == "auto") h->sf_mid = true;
-        else if (v == "off") h->sf_mid = false;
-        else return fail(PFNL_ERR_INVALID, "split16_mid must be auto or off");
-        return 0;
-    }
-    if (k == "split16_sf0") {
-        if (v == "on") h->sf0 = true;
-        else if (v == "off") h->sf0 = false;
-        else return fail(PFNL_ERR_INVALID, "split16_sf0 must be on or off");
-        return 0;
-    }
-    if (k == "split16_splitchains") {
-        if (v == "auto") h->split_chains = true;
-        else if (v == "off") h->split_chains = false;
-        else return fail(PFNL_ERR_INVALID, "split16_splitchains must be auto or off");
-        return 0;
-    }
-    if (k == "split16_sf") {
-        if (v == "on") h->sf_path = true;
-        else if (v == "off") h->sf_path = false;
-        else return fail(PFNL_ERR_INVALID, "split16_sf must be on or off");
-        return 0;
-    }
-    if (k == "conv2") {
-        if (v == "grouped") h->conv2_grouped = true;
-        else if (v == "split") h->conv2_grouped = false;
-        else return fail(PFNL_ERR_INVALID, "conv2 must be grouped or split");
-        return 0;
-    }
-    if (k == "split16_mfma") {
-        if (v == "16") h->s16_m16 = true;
-        else if (v == "32") h->s16_m16 = false;
-        else return fail(PFNL_ERR_INVALID, "split16_mfma must be 16 or 32");
-        return 0;
-    }
-    if (k == "bf16_mfma") {
-        if (v == "16") h->bf16_m16 = true;
-        else if (v == "32") h->bf16_m16 = false;
-        else return fail(PFNL_ERR_INVALID, "bf16_mfma must be 16 or 32");
-        return 0;
-    }
-    if (k == "bf16_conv10") {
-        if (v == "fused") h->bf16_fuse10 = true;
-        else if (v == "separate") h->bf16_fuse10 = false;
-        else return fail(PFNL_ERR_INVALID, "bf16_conv10 must be fused or separate");
-        return 0;
-    }
-    if (k == "precision") {
-        if (v == "bf16") h->bf16 = true;
-        else if (v == "fp32") h->bf16 = false;
-        else return fail(PFNL_ERR_INVALID, "precision must be fp32 or bf16");
-        return 0;
-    }
-    if (k == "merge1") {
-        if (v == "auto") h->m1_algo = 0;
-        else if (v == "split16") h->m1_algo = 1;
-        else if (v == "winograd") h->m1_algo = 2;
-        else return fail(PFNL_ERR_INVALID, "merge1 must be auto, split16 or winograd");
-        ++h->cfg_gen;
-        return 0;
-    }
-    if (k == "nl_type") {
-        if (v == "auto") h->nl_type = -1;
-        else if (v == "0" || v == "embedded_gaussian") h->nl_type = 0;
-        else if (v == "1" || v == "gaussian") h->nl_type = 1;
-        else if (v == "2" || v == "dot_product") h->nl_type = 2;
-        else return fail(PFNL_ERR_INVALID, "nl_type: auto | 0 | 1 | 2 (nltype 3, 'concat', builds no graph in the reference either: utils.py:23)");
-        return 0;
-    }
     if (k == "nl_sub_sample") {
         const int n = atoi(v.c_str());
         if (n < 1 || n > 64) return fail(PFNL_ERR_INVALID, "nl_sub_sample: an integer >= 1");
         h->nl_sub = n;
         return 0;
     }
-    if (k == "small_c10") {
-        if (v == "on") h->small_c10 = true;
-        else if (v == "off") h->small_c10 = false;
-        else return fail(PFNL_ERR_INVALID, "small_c10 must be on or off");
-        return 0;
-    }
     if (k == "bf16_nonlocal") {   // (the split-bf16 kernel of round 1 left the library in round 4: tools/experiments/nonlocal_bf16.hip)
         if (v != "f16") return fail(PFNL_ERR_INVALID, "bf16_nonlocal must be f16");
         return 0;
     }
-    if (k == "nonlocal") {
-        if (v == "f32") h->nl_algo = 0;
-        else if (v == "split16") h->nl_algo = 1;
-        else if (v == "auto") h->nl_algo = 2;
-        else return fail(PFNL_ERR_INVALID, "nonlocal must be auto, f32 or split16");
-        return 0;
-    }
-    if (k == "conv1x1") {
-        if (v == "stream") h->conv1x1_algo = 1;
-        else if (v == "tiled") h->conv1x1_algo = 0;
-        else if (v == "split16") h->conv1x1_algo = 2;
-        else return fail(PFNL_ERR_INVALID, "conv1x1 must be split16, stream or tiled");
-        return 0;
-    }
-    return fail(PFNL_ERR_INVALID, "unknown option " + k);
+    const OptionSpec* o = find_option(k);
+    if (!o) return fail(PFNL_ERR_INVALID, "unknown option " + k);
+    for (const OptionName& n : o->names)
+        if (n.name && v == n.name) {
+            o->field.set(h, n.value);
+            return 0;
+        }
+    return fail(PFNL_ERR_INVALID, o->refusal);
 }
 
 // the CURRENT value of an option as pfnl_set_option would take it back - whatever set it (pfnl_set_option, an environment variable read by
@@ -1305,30 +1270,16 @@ int pfnl_get_option(pfnl_handle* h, const char* key, char* buf, size_t buflen) {
     if (!h || !key || !buf || buflen < 1) return fail(PFNL_ERR_INVALID, "NULL argument");
     const std::string k(key);
     std::string v;
-    auto onoff = [](bool b) { return std::string(b ? "on" : "off"); };
-    if (k == "graph") v = h->graph_mode == 1 ? "auto" : (h->graph_mode == 2 ? "on" : "off");
-    else if (k == "conv3x3") v = h->conv_algo == 3 ? "winograd" : h->conv_algo == 1 ? "winograd_tile" : h->conv_algo == 0 ? "direct" : h->conv_algo == 4 ? "split16" : "auto";
-    else if (k == "strict_fp32") v = onoff(h->strict);
-    else if (k == "small") v = h->small_mode == 1 ? "on" : (h->small_mode == 2 ? "off" : "auto");
-    else if (k == "split16_chain") v = onoff(h->sf_chain);
-    else if (k == "split16_c10") v = onoff(h->sf_c10);
-    else if (k == "split16_mid") v = h->sf_mid ? "auto" : "off";
-    else if (k == "split16_sf0") v = onoff(h->sf0);
-    else if (k == "split16_sf") v = onoff(h->sf_path);
-    else if (k == "split16_splitchains") v = h->split_chains ? "auto" : "off";
-    else if (k == "conv2") v = h->conv2_grouped ? "grouped" : "split";
-    else if (k == "bf16_conv10") v = h->bf16_fuse10 ? "fused" : "separate";
-    else if (k == "bf16_mfma") v = h->bf16_m16 ? "16" : "32";
-    else if (k == "split16_mfma") v = h->s16_m16 ? "16" : "32";
-    else if (k == "precision") v = h->bf16 ? "bf16" : "fp32";
-    else if (k == "merge1") v = h->m1_algo == 1 ? "split16" : (h->m1_algo == 2 ? "winograd" : "auto");
-    else if (k == "nl_type") v = h->nl_type < 0 ? "auto" : std::to_string(h->nl_type);
-    else if (k == "nl_sub_sample") v = std::to_string(h->nl_sub);
-    else if (k == "small_c10") v = onoff(h->small_c10);
+    if (k == "nl_sub_sample") v = std::to_string(h->nl_sub);
     else if (k == "bf16_nonlocal") v = "f16";
-    else if (k == "nonlocal") v = h->nl_algo == 0 ? "f32" : (h->nl_algo == 1 ? "split16" : "auto");
-    else if (k == "conv1x1") v = h->conv1x1_algo == 1 ? "stream" : (h->conv1x1_algo == 0 ? "tiled" : "split16");
-    else return fail(PFNL_ERR_INVALID, "unknown option " + k);
+    else if (const OptionSpec* o = find_option(k)) {
+        const int cur = o->field.get(h);
+        for (const OptionName& n : o->names)
+            if (n.name && n.value == cur) {
+                v = n.name;
+                break;
+            }
+    } else return fail(PFNL_ERR_INVALID, "unknown option " + k);
     if (v.size() + 1 > buflen) return fail(PFNL_ERR_INVALID, "buffer too small");
     std::memcpy(buf, v.c_str(), v.size() + 1);
     return 0;
@@ -1418,58 +1369,22 @@ int pfnl_finalize_weights(pfnl_handle* h) {
         h->off_m2_b = put_bias(Bv("convmerge2"));
     }
     {   // fold the two 1x1 projections of the non-local block: W' = Wg Ww, b' = bg Ww + bw
-        const auto& wg = W("nlblock_0/g/g");   // [C][C] (ci, cm)
-        const auto& ww = W("nlblock_0/w/w");   // [C][C] (cm, co)
-        const auto& bg = Bv("nlblock_0/g/g");
-        const auto& bw = Bv("nlblock_0/w/w");
         h->off_nl_w = reserve((size_t)CP * CP);
         h->off_nl_b = reserve(CP);
-        for (int ci = 0; ci < C; ++ci)
-            for (int co = 0; co < C; ++co) {
-                double acc = 0.0;
-                for (int cm = 0; cm < C; ++cm) acc += (double)wg[(size_t)ci * C + cm] * (double)ww[(size_t)cm * C + co];
-                blob[h->off_nl_w + (size_t)ci * CP + co] = (float)acc;
-            }
-        for (int co = 0; co < C; ++co) {
-            double acc = bw[co];
-            for (int cm = 0; cm < C; ++cm) acc += (double)bg[cm] * (double)ww[(size_t)cm * C + co];
-            blob[h->off_nl_b + co] = (float)acc;
-        }
+        pfnl_nl_fold_gw(W("nlblock_0/g/g").data(), Bv("nlblock_0/g/g").data(), W("nlblock_0/w/w").data(), Bv("nlblock_0/w/w").data(), C, CP,
+                        &blob[h->off_nl_w], &blob[h->off_nl_b]);
     }
-    {   // optional embedded-Gaussian projections: M = Wt Wp^T, c = bt Wp^T (see nl_qproj_kernel)
+    {   // optional embedded-Gaussian projections: M = Wt Wp^T, c = bt Wp^T and column C (see nl_qproj_kernel)
         int have = 0;
         for (auto& kv : h->optional) have += (int)h->host.count(kv.first);
         if (have != 0 && have != (int)h->optional.size())
             return fail(PFNL_ERR_STATE, "nlblock_0 theta/phi: all four tensors (two kernels, two biases) or none");
         h->nl_theta = have != 0;
         if (h->nl_theta) {
-            const auto& wt = W("nlblock_0/theta/theta");   // [C][C] (ci, cm)
-            const auto& wp = W("nlblock_0/phi/phi");
-            const auto& bt = Bv("nlblock_0/theta/theta");
             h->off_nl_m = reserve((size_t)CP * CP);
             h->off_nl_c = reserve(CP);
-            for (int ci = 0; ci < C; ++ci)
-                for (int cj = 0; cj < C; ++cj) {
-                    double acc = 0.0;
-                    for (int cm = 0; cm < C; ++cm) acc += (double)wt[(size_t)ci * C + cm] * (double)wp[(size_t)cj * C + cm];
-                    blob[h->off_nl_m + (size_t)ci * CP + cj] = (float)acc;
-                }
-            for (int cj = 0; cj < C; ++cj) {
-                double acc = 0.0;
-                for (int cm = 0; cm < C; ++cm) acc += (double)bt[cm] * (double)wp[(size_t)cj * C + cm];
-                blob[h->off_nl_c + cj] = (float)acc;
-            }
-            // column C (a pad column: C < CP): theta_i . b_phi = X_i (Wt b_phi) + bt . b_phi - the per-query constant of the logits
-            // that cancels in the softmax of nltype 0 and does not under the relu of nltype 2 (nl_attn_kernel<., DOT>)
-            const auto& bph = Bv("nlblock_0/phi/phi");
-            double d0 = 0.0;
-            for (int cm = 0; cm < C; ++cm) d0 += (double)bt[cm] * (double)bph[cm];
-            blob[h->off_nl_c + C] = (float)d0;
-            for (int ci = 0; ci < C; ++ci) {
-                double acc = 0.0;
-                for (int cm = 0; cm < C; ++cm) acc += (double)wt[(size_t)ci * C + cm] * (double)bph[cm];
-                blob[h->off_nl_m + (size_t)ci * CP + C] = (float)acc;
-            }
+            pfnl_nl_fold_theta_phi(W("nlblock_0/theta/theta").data(), Bv("nlblock_0/theta/theta").data(), W("nlblock_0/phi/phi").data(),
+                                   Bv("nlblock_0/phi/phi").data(), C, CP, &blob[h->off_nl_m], &blob[h->off_nl_c]);
         }
     }
     {   // bf16 packs of the trunk (precision=bf16)
@@ -2100,852 +2015,6 @@ int pfnl_debug_tap(pfnl_handle* h, const char* name, float* host_dst, size_t cou
     }
     if (count != need) return fail(PFNL_ERR_INVALID, "tap size mismatch");
     HIPCHK(hipMemcpy(host_dst, src, need * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// ---- single ops -------------------------------------------------------------------------------
-
-int pfnl_op_conv2d(const float* in, const float* kernel_host, const float* bias_host, const float* addend,
-                   int add_div, const float* resid, float* out, int items, int frames_per_item, int H, int W,
-                   int ksize, int cout, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if ((ksize != 1 && ksize != 3) || cout < 1 || cout > 64 || items < 1 || frames_per_item < 1 || H < 1 || W < 1)
-        return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    if ((addend != nullptr) != (resid != nullptr))
-        return fail(PFNL_ERR_INVALID, "addend and resid must be given together (fused conv2 epilogue) or not at all");
-    if (addend && add_div < 1) return fail(PFNL_ERR_INVALID, "add_div must be >= 1");
-    if (addend && cout != 64) return fail(PFNL_ERR_INVALID, "fused epilogue needs cout == 64");
-    hipStream_t s = (hipStream_t)stream;
-    const int cin = 64 * frames_per_item;
-    std::vector<float> pack(pfnl::conv_pack_floats(ksize, cin) + 64, 0.f);
-    pfnl::conv_pack_weights(kernel_host, ksize, cin, 0, cin, cout, pack.data());
-    const size_t boff = pack.size() - 64;
-    if (bias_host) std::memcpy(&pack[boff], bias_host, cout * sizeof(float));
-    float* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        pfnl::ConvParams p{};
-        p.in = in;
-        p.wpack = dw;
-        p.bias = dw + boff;   // zeros when bias_host is NULL
-        p.addend = addend;
-        p.resid = resid;
-        p.out = out;
-        p.H = H;
-        p.W = W;
-        p.in_cstride = 64;
-        p.out_cstride = cout;
-        p.cout = cout;
-        p.chunks_per_frame = 64 / pfnl::CONV_CK;
-        p.frames_per_item = frames_per_item;
-        p.nchunks = frames_per_item * p.chunks_per_frame;
-        p.add_div = addend ? add_div : 1;
-        p.act = act;
-        e = pfnl::launch_conv_mfma(p, ksize, items, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv2_grouped(const float* in, const float* base, const float* kernel_host, const float* bias_host,
-                          const float* resid, float* out, int clips, int frames_per_clip, int H, int W, int act,
-                          void* stream) {
-    if (!in || !base || !kernel_host || !resid || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (clips < 1 || frames_per_clip < 1 || H < 2 || W < 2 || (H & 1) || (W & 1))
-        return fail(PFNL_ERR_INVALID, "grouped conv2 needs even H, W");
-    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the grouped kernel");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t pf = pfnl::wino_pack_floats();
-    std::vector<float> pack(2 * pf + 64, 0.f);
-    pfnl::wino_pack_weights(kernel_host, 128, 0, pack.data());            // rows 0..63 multiply `base`
-    pfnl::wino_pack_weights(kernel_host, 128, 64, pack.data() + pf);      // rows 64..127 multiply the frame
-    if (bias_host) std::memcpy(&pack[2 * pf], bias_host, 64 * sizeof(float));
-    float* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        pfnl::WinoParams wp{};
-        wp.in = in;
-        wp.in2 = base;
-        wp.upack = dw + pf;
-        wp.upack2 = dw;
-        wp.bias = dw + 2 * pf;
-        wp.resid = resid;
-        wp.out = out;
-        wp.H = H;
-        wp.W = W;
-        wp.add_div = frames_per_clip;
-        wp.act = act;
-        wp.items = clips * frames_per_clip;
-        e = pfnl::launch_conv_wino_ws(wp, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("grouped conv2 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv3x3_accum(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
-                          int frames_per_clip, int H, int W, int cout, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (clips < 1 || frames_per_clip < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || cout < 1 || cout > 64)
-        return fail(PFNL_ERR_INVALID, "accumulating conv needs even H, W and cout <= 64");
-    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
-    hipStream_t s = (hipStream_t)stream;
-    const int T = frames_per_clip;
-    const size_t pf = pfnl::wino_pack_floats();
-    std::vector<float> pack(T * pf + 64, 0.f);
-    for (int f = 0; f < T; ++f) pfnl::wino_pack_weights(kernel_host, 64 * T, 64 * f, pack.data() + f * pf, cout);
-    if (bias_host) std::memcpy(&pack[T * pf], bias_host, cout * sizeof(float));
-    float* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        pfnl::WinoParams wp{};
-        wp.in = in;
-        wp.upack = dw;
-        wp.upack_stride = (long long)pf;
-        wp.accum = 1;
-        wp.bias = dw + T * pf;
-        wp.out = out;
-        wp.H = H;
-        wp.W = W;
-        wp.add_div = T;
-        wp.act = act;
-        wp.items = clips * T;
-        e = pfnl::launch_conv_wino_ws(wp, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("accumulating conv op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// ---- the C-ABI v4 hooks' split-chain arguments: split_s = 0 is no cut (n_full, split_q ignored); otherwise the geometry every split launch
-// checks (split_geometry_ok) on the grid of the current device, tested before any allocation or launch
-static bool split_args_ok(int H, int W, int items, int T, int n_full, int split_s, int split_q) {
-    if (split_s == 0) return true;
-    return split_s <= 7 && pfnl::split_geometry_ok(H, W, items, T, n_full, split_s, split_q, pfnl::conv_split16_grid());
-}
-// floats of the parts' raw sums: one [8][32][64] tile per part of every cut chain
-static size_t split_partial_floats(int H, int W, int items, int T, int n_full, int split_s) {
-    const size_t nchains = (size_t)((W + 31) / 32) * ((H + 7) / 8) * (items / T);
-    return (nchains - (size_t)n_full) * split_s * 8 * 32 * 64;
-}
-
-static int op_conv3x3_accum_split16(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
-                                    int frames_per_clip, int H, int W, int cout, int act, void* stream, int n_full = 0, int split_s = 0,
-                                    int split_q = 0) {
-    hipStream_t s = (hipStream_t)stream;
-    const int T = frames_per_clip;
-    const size_t nh = pfnl::conv3x3_split16_pack_halfs();
-    std::vector<uint16_t> pack((size_t)T * nh + 128, 0);
-    for (int f = 0; f < T; ++f) pfnl::conv3x3_split16_pack_weights(kernel_host, 64 * T, 64 * f, pack.data() + (size_t)f * nh, cout);
-    if (bias_host) std::memcpy(&pack[(size_t)T * nh], bias_host, cout * sizeof(float));
-    uint16_t* dw = nullptr;
-    float* part = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && split_s) e = hipMalloc(&part, split_partial_floats(H, W, clips * T, T, n_full, split_s) * sizeof(float));
-    const float* const db = reinterpret_cast<const float*>(dw + (size_t)T * nh);
-    pfnl::ConvSplitParams q{in, dw, db, nullptr, nullptr, out, H, W, clips * T, T, act, 1};
-    q.n_full = n_full;
-    q.split_s = split_s;
-    q.split_q = split_q;
-    q.partial = part;
-    if (e == hipSuccess) e = pfnl::launch_conv3x3_split16(q, s);
-    if (e == hipSuccess && split_s) {                                   // the cut chains: the parts' raw sums + bias, act -> out
-        pfnl::ConvSplitParams f{};
-        f.H = H;
-        f.W = W;
-        f.items = clips * T;
-        f.add_div = T;
-        f.act = act;
-        f.n_full = n_full;
-        f.split_s = split_s;
-        f.split_q = split_q;
-        f.partial = part;
-        f.bias = db;
-        f.out = out;
-        e = pfnl::launch_c10_finalize(f, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (part) (void)hipFree(part);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("accumulating conv (split16) op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv3x3_accum_split16(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
-                                  int frames_per_clip, int H, int W, int cout, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (clips < 1 || frames_per_clip < 1 || H < 1 || W < 1 || cout < 1 || cout > 64) return fail(PFNL_ERR_INVALID, "accumulating conv needs cout <= 64");
-    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
-    return op_conv3x3_accum_split16(in, kernel_host, bias_host, out, clips, frames_per_clip, H, W, cout, act, stream);
-}
-
-int pfnl_op_conv3x3_bf16(const uint16_t* in, const float* kernel_host, const float* bias_host, const uint16_t* addend,
-                         int add_div, const uint16_t* resid, uint16_t* out, int items, int H, int W, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || H < 1 || W < 1 || (addend == nullptr) != (resid == nullptr)) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nh = pfnl::conv3x3_bf16_pack_halfs();
-    std::vector<uint16_t> pack(nh + 128, 0);
-    pfnl::conv3x3_bf16_pack_weights(kernel_host, 64, 0, pack.data());
-    if (bias_host) std::memcpy(&pack[nh], bias_host, 64 * sizeof(float));
-    uint16_t* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    pfnl::ConvBf16Params q{in, dw, reinterpret_cast<const float*>(dw + nh), addend, resid, out, H, W, items, add_div < 1 ? 1 : add_div, act};
-    if (e == hipSuccess) e = pfnl::launch_conv3x3_bf16(q, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv3x3 bf16 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv3x3_split16(const float* in, const float* kernel_host, const float* bias_host, const float* addend, int add_div,
-                            const float* resid, float* out, int items, int H, int W, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || H < 1 || W < 1 || (addend == nullptr) != (resid == nullptr)) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    if (addend && (add_div < 1 || items % add_div)) return fail(PFNL_ERR_INVALID, "items must be a multiple of add_div");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nh = pfnl::conv3x3_split16_pack_halfs();
-    std::vector<uint16_t> pack(nh + 128, 0);
-    pfnl::conv3x3_split16_pack_weights(kernel_host, 64, 0, pack.data());
-    if (bias_host) std::memcpy(&pack[nh], bias_host, 64 * sizeof(float));
-    uint16_t* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    pfnl::ConvSplitParams q{in, dw, reinterpret_cast<const float*>(dw + nh), addend, resid, out, H, W, items, add_div < 1 ? 1 : add_div, act};
-    if (e == hipSuccess) e = pfnl::launch_conv3x3_split16(q, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv3x3 split16 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv1_conv10_bf16(const uint16_t* in, const float* k1_host, const float* b1_host, const float* k10_host,
-                              const float* b10_host, uint16_t* out1, uint16_t* base, int clips, int frames_per_clip, int H, int W,
-                              void* stream) {
-    if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const int T = frames_per_clip;
-    if (clips < 1 || (T != 3 && T != 5 && T != 7) || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n3 = pfnl::conv3x3_bf16_pack_halfs(), n1 = pfnl::conv1x1_bf16_pack_halfs(T);
-    std::vector<uint16_t> pack(n3 + n1 + 256, 0);
-    pfnl::conv3x3_bf16_pack_weights(k1_host, 64, 0, pack.data());
-    pfnl::conv1x1_bf16_pack_weights(k10_host, T, pack.data() + n3);
-    if (b1_host) std::memcpy(&pack[n3 + n1], b1_host, 64 * sizeof(float));
-    if (b10_host) std::memcpy(&pack[n3 + n1 + 128], b10_host, 64 * sizeof(float));
-    uint16_t* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    pfnl::ConvBf16Params q{in, dw, reinterpret_cast<const float*>(dw + n3 + n1), nullptr, nullptr, out1, H, W, clips * T, T, 1,
-                           dw + n3, reinterpret_cast<const float*>(dw + n3 + n1 + 128), base};
-    if (e == hipSuccess) e = pfnl::launch_conv3x3_bf16(q, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv1+conv10 bf16 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv3x3_accum_bf16(const uint16_t* in, const float* kernel_host, const float* bias_host, float* out, int clips,
-                               int frames_per_clip, int H, int W, int cout, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const int T = frames_per_clip;
-    if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1 || cout < 1 || cout > 64) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nh = pfnl::conv3x3_bf16_pack_halfs();
-    std::vector<uint16_t> pack((size_t)T * nh + 128, 0);
-    for (int f = 0; f < T; ++f) pfnl::conv3x3_bf16_pack_weights(kernel_host, 64 * T, 64 * f, &pack[(size_t)f * nh], cout);
-    if (bias_host) std::memcpy(&pack[(size_t)T * nh], bias_host, cout * sizeof(float));
-    uint16_t* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    pfnl::ConvBf16Params q{in, dw, reinterpret_cast<const float*>(dw + (size_t)T * nh), nullptr, nullptr, nullptr, H, W, clips * T, T, act};
-    q.out_f32 = out;
-    if (e == hipSuccess) e = pfnl::launch_conv3x3_bf16(q, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv3x3 accum bf16 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv1x1_bf16(const uint16_t* in, const float* kernel_host, const float* bias_host, uint16_t* out, int items,
-                         int frames_per_item, int HW, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const int T = frames_per_item;
-    if (items < 1 || (T != 3 && T != 5 && T != 7) || HW < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nh = pfnl::conv1x1_bf16_pack_halfs(T);
-    std::vector<uint16_t> pack(nh + 128, 0);
-    pfnl::conv1x1_bf16_pack_weights(kernel_host, T, pack.data());
-    if (bias_host) std::memcpy(&pack[nh], bias_host, 64 * sizeof(float));
-    uint16_t* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = pfnl::launch_conv1x1_bf16(in, dw, reinterpret_cast<const float*>(dw + nh), out, items, T, HW, act, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv1x1 bf16 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv1x1_split16(const float* in, const float* kernel_host, const float* bias_host, float* out, int items,
-                            int frames_per_item, int HW, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || frames_per_item < 1 || HW < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const int T = frames_per_item;
-    const size_t nh = pfnl::conv1x1_split16_pack_halfs(T);
-    std::vector<uint16_t> pack(nh + 128, 0);
-    pfnl::conv1x1_split16_pack_weights(kernel_host, T, pack.data());
-    if (bias_host) std::memcpy(&pack[nh], bias_host, 64 * sizeof(float));
-    uint16_t* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = pfnl::launch_conv1x1_split16(in, dw, reinterpret_cast<const float*>(dw + nh), out, items, T, HW, act, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv1x1 split16 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// The small-shape trunk kernel (conv_small.hip; ConvSmallParams in conv_small.h says which tensor each source comes from):
-// out[i] = act(sum_s conv_ks(src(i, s); kernel rows [64 s, 64 s + 64)) + bias) (+ resid[i]); kernel HWIO [ks, ks, 64 nsrc, cout]
-int pfnl_op_conv_small(const float* a, const float* b, int nA, int a_div, int b_mul, int nsrc, const float* kernel_host,
-                       const float* bias_host, const float* resid, float* out, int items, int H, int W, int ks, int cout, int act,
-                       void* stream) {
-    if (!b || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || H < 1 || W < 1 || nsrc < 1 || nsrc > 16 || (ks != 1 && ks != 3) || cout < 1 || cout > 64 || nA < 0 || nA > nsrc || (nA && !a))
-        return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nh = pfnl::conv_small_pack_halfs(ks, nsrc);
-    std::vector<uint16_t> pack(nh + 128, 0);
-    pfnl::conv_small_pack_weights(kernel_host, ks, nsrc, cout, pack.data());
-    if (bias_host) std::memcpy(&pack[nh], bias_host, cout * sizeof(float));
-    uint16_t* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    pfnl::ConvSmallParams q{a, b, nA, a_div < 1 ? 1 : a_div, b_mul < 1 ? 1 : b_mul, nsrc, dw, reinterpret_cast<const float*>(dw + nh), resid, out, H, W, items, act, ks};
-    if (e == hipSuccess) e = pfnl::launch_conv_small(q, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv_small op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// One progressive-fusion block on the small-shape kernels as the forward launches it since round 4 (two launches, conv_small.h):
-// inp1 = lrelu(conv3x3(x; k1) + b1) together with the per-frame partials of conv10_i; out = x + lrelu(conv3x3(concat([base, inp1_t]); k2)
-// + b2) with base = lrelu(sum_t partial_t + b10) built in the second launch's prologue (reference model/pfnl.py:66-71).
-int pfnl_op_conv_small_pf_block(const float* x, const float* k1_host, const float* b1_host, const float* k10_host, const float* b10_host,
-                                const float* k2_host, const float* b2_host, float* inp1, float* out, int clips, int T, int H, int W,
-                                void* stream) {
-    if (!x || !k1_host || !k10_host || !k2_host || !inp1 || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n1 = pfnl::conv_small_pack_halfs(3, 1), n10 = pfnl::conv_small_pack_halfs(1, T), n2 = pfnl::conv_small_pack_halfs(3, 2);
-    std::vector<uint16_t> pack(n1 + n10 + n2 + 3 * 128, 0);
-    pfnl::conv_small_pack_weights(k1_host, 3, 1, 64, pack.data());
-    pfnl::conv_small_pack_weights(k10_host, 1, T, 64, pack.data() + n1);
-    pfnl::conv_small_pack_weights(k2_host, 3, 2, 64, pack.data() + n1 + n10);
-    uint16_t* const bh = pack.data() + n1 + n10 + n2;
-    if (b1_host) std::memcpy(bh, b1_host, 64 * sizeof(float));
-    if (b10_host) std::memcpy(bh + 128, b10_host, 64 * sizeof(float));
-    if (b2_host) std::memcpy(bh + 256, b2_host, 64 * sizeof(float));
-    const size_t F = (size_t)clips * T, tensor = F * H * W * 64;
-    uint16_t* dw = nullptr;
-    float* part = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    if (hipMalloc(&part, tensor * sizeof(float)) != hipSuccess) {
-        (void)hipFree(dw);
-        return fail(PFNL_ERR_NOMEM, "allocation failed");
-    }
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    const float* const db = reinterpret_cast<const float*>(dw + n1 + n10 + n2);
-    if (e == hipSuccess) {
-        pfnl::ConvSmallParams q{nullptr, x, 0, 1, 1, 1, dw, db, nullptr, inp1, H, W, (int)F, 1, 3};
-        q.x_wpack = dw + n1;
-        q.x_out = part;
-        q.x_T = T;
-        e = pfnl::launch_conv_small(q, s);
-    }
-    if (e == hipSuccess) {
-        pfnl::ConvSmallParams q{part, inp1, 1, T, 1, 2, dw + n1 + n10, db + 128, x, out, H, W, (int)F, 1, 3};
-        q.a_nsum = T;
-        q.a_bias = db + 64;
-        e = pfnl::launch_conv_small(q, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    (void)hipFree(part);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv_small block op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// ---- the split-format ("SF", conv_split16.h) variants of the split-f16 kernels, op by op.  The hooks take and return fp32
-// tensors: fp32 -> SF and SF -> fp32 (hi + lo' 2^-11) conversions bracket the kernel under test, so that each of them is checked
-// against the fp64 spec at its own scale and not only inside the forward.
-//   which = 0: conv3x3_sf_kernel (input SF by LDS-DMA, epilogue from registers; plain or fused with addend + resid)
-//   which = 1: conv3x3_split16_kernel<0, OSF> (conv1_i: fp32 in, SF out)
-static int op_conv2_chain(const float* in, const float* kernel_host, const float* bias_host, const float* addend, int add_div, const float* resid,
-                          float* out, uint16_t* out_sf, int items, int H, int W, int act, void* stream,
-                          int mfma = 32, int n_full = 0, int split_s = 0, int split_q = 0) {
-    hipStream_t s2 = (hipStream_t)stream;
-    const size_t nh2 = pfnl::conv3x3_split16_pack_halfs();
-    const bool m16 = mfma == 16;
-    std::vector<uint16_t> pk((m16 ? 4 : 2) * nh2 + 128, 0);
-    pfnl::conv3x3_split16_pack_weights(kernel_host, 128, 0, pk.data(), 64, true);
-    pfnl::conv3x3_split16_pack_weights(kernel_host, 128, 64, pk.data() + nh2, 64, true);
-    if (bias_host) std::memcpy(&pk[2 * nh2], bias_host, 64 * sizeof(float));
-    if (m16) {                                                          // conv3x3_sf_chain16_kernel's packs behind the bias, halves as the forward's
-        pfnl::conv3x3_split16_pack_weights16(kernel_host, 128, 0, pk.data() + 2 * nh2 + 128);
-        pfnl::conv3x3_split16_pack_weights16(kernel_host, 128, 64, pk.data() + 3 * nh2 + 128);
-    }
-    const size_t npf = (size_t)items * H * W, npb = (size_t)(items / add_div) * H * W;
-    uint16_t *dw2 = nullptr, *tf = nullptr, *tb = nullptr;
-    HIPCHK(hipMalloc(&dw2, pk.size() * sizeof(uint16_t)));
-    hipError_t e2 = hipMalloc(&tf, npf * 256);
-    if (e2 == hipSuccess) e2 = hipMalloc(&tb, npb * 256);
-    if (e2 == hipSuccess) e2 = hipMemcpy(dw2, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e2 == hipSuccess) e2 = pfnl::launch_sf_from_f32(in, tf, npf, s2);
-    if (e2 == hipSuccess) e2 = pfnl::launch_sf_from_f32(addend, tb, npb, s2);
-    if (e2 == hipSuccess && out != resid) e2 = hipMemcpyAsync(out, resid, npf * 256, hipMemcpyDeviceToDevice, s2);   // the kernel works in place
-    pfnl::ConvSplitParams q{reinterpret_cast<const float*>(tf), dw2 + nh2, reinterpret_cast<const float*>(dw2 + 2 * nh2), nullptr, out, out, H, W, items, add_div, act};
-    q.in2 = reinterpret_cast<const float*>(tb);
-    q.wpack2 = dw2;
-    q.out2 = reinterpret_cast<float*>(out_sf);                          // (null: no split-format copy)
-    q.n_full = n_full;
-    q.split_s = split_s;
-    q.split_q = split_q;
-    if (m16) {
-        q.wpack_m16 = dw2 + 3 * nh2 + 128;
-        q.wpack2_m16 = dw2 + 2 * nh2 + 128;
-    }
-    if (e2 == hipSuccess) e2 = pfnl::launch_conv3x3_sf_chain(q, s2);
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(s2);
-    (void)hipFree(dw2);
-    (void)hipFree(tf);
-    (void)hipFree(tb);
-    if (e2 != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv2 chain op: ") + hipGetErrorString(e2));
-    return 0;
-}
-// the whole of conv2_i in one launch WITH the split-format copy of its output (conv3x3_sf_chain_kernel<true>, option split16_sf0):
-// out as pfnl_op_conv3x3_split16_sf(which = 2); out_sf [items][H][W][128] binary16 bit patterns (device) = the split format of `out`
-int pfnl_op_conv2_chain_sf0(const float* in, const float* kernel_host, const float* bias_host, const float* base, int add_div, const float* resid,
-                            float* out, uint16_t* out_sf, int items, int H, int W, int act, void* stream) {
-    if (!in || !kernel_host || !out || !out_sf || !base || !resid) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || H < 1 || W < 1 || add_div < 1 || items % add_div) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    return op_conv2_chain(in, kernel_host, bias_host, base, add_div, resid, out, out_sf, items, H, W, act, stream);
-}
-
-int pfnl_op_conv3x3_split16_sf(int which, const float* in, const float* kernel_host, const float* bias_host, const float* addend,
-                               int add_div, const float* resid, float* out, int items, int H, int W, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (which < 0 || which > 2 || items < 1 || H < 1 || W < 1 || (addend == nullptr) != (resid == nullptr)) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    if (addend && ((which != 0 && which != 2) || add_div < 1 || items % add_div)) return fail(PFNL_ERR_INVALID, "fused mode: which = 0 or 2, items a multiple of add_div");
-    if (which == 2) {   // the whole of conv2_i (conv3x3_sf_chain_kernel): kernel_host = HWIO [3,3,128,64], `addend` = base [items/add_div][H][W][64] fp32
-        if (!addend) return fail(PFNL_ERR_INVALID, "which = 2 needs base (addend argument) and resid");
-        return op_conv2_chain(in, kernel_host, bias_host, addend, add_div, resid, out, nullptr, items, H, W, act, stream);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nh = pfnl::conv3x3_split16_pack_halfs();
-    std::vector<uint16_t> pack(nh + 128, 0);
-    pfnl::conv3x3_split16_pack_weights(kernel_host, 64, 0, pack.data(), 64, which == 0);
-    if (bias_host) std::memcpy(&pack[nh], bias_host, 64 * sizeof(float));
-    const size_t npix = (size_t)items * H * W;
-    uint16_t *dw = nullptr, *tmp = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMalloc(&tmp, npix * 256);
-    if (e == hipSuccess) e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (which == 0) {
-        if (e == hipSuccess) e = pfnl::launch_sf_from_f32(in, tmp, npix, s);
-        pfnl::ConvSplitParams q{reinterpret_cast<const float*>(tmp), dw, reinterpret_cast<const float*>(dw + nh), addend, resid, out, H, W, items, add_div < 1 ? 1 : add_div, act};
-        if (e == hipSuccess) e = pfnl::launch_conv3x3_sf(q, s);
-    } else {
-        pfnl::ConvSplitParams q{in, dw, reinterpret_cast<const float*>(dw + nh), nullptr, nullptr, reinterpret_cast<float*>(tmp), H, W, items, 1, act};
-        q.out_sf = 1;
-        if (e == hipSuccess) e = pfnl::launch_conv3x3_split16(q, s);
-        if (e == hipSuccess) e = pfnl::launch_sf_to_f32(tmp, out, npix, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv3x3 split16 SF op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-// conv1_i + conv10_i as ONE launch (conv3x3_c1c10_kernel): in fp32 [clips*T][H][W][64] -> out1 = inp1 [clips*T][H][W][64], base [clips][H][W][64];
-// the kernel writes both in the split format, the hook hands them back as fp32 (hi + lo' 2^-11: what the consumers' MFMAs see)
-static int op_conv1_conv10_split16(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
-                                   const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
-                                   void* stream, bool in_sf, int n_full = 0, int split_s = 0, int split_q = 0) {
-    if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const int T = frames_per_clip;
-    if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n3 = pfnl::conv3x3_split16_pack_halfs(), n1 = pfnl::conv1x1_c10_pack_halfs(T);
-    std::vector<uint16_t> pack(n3 + n1 + 256, 0);
-    pfnl::conv3x3_split16_pack_weights(k1_host, 64, 0, pack.data());
-    pfnl::conv1x1_c10_pack_weights(k10_host, T, pack.data() + n3);
-    if (b1_host) std::memcpy(&pack[n3 + n1], b1_host, 64 * sizeof(float));
-    if (b10_host) std::memcpy(&pack[n3 + n1 + 128], b10_host, 64 * sizeof(float));
-    const size_t np1 = (size_t)clips * T * H * W, npb = (size_t)clips * H * W;
-    uint16_t *dw = nullptr, *t1 = nullptr, *tb = nullptr, *ti = nullptr;
-    float* part = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMalloc(&t1, np1 * 256);
-    if (e == hipSuccess) e = hipMalloc(&tb, npb * 256);
-    if (e == hipSuccess && in_sf) e = hipMalloc(&ti, np1 * 256);
-    if (e == hipSuccess && split_s) e = hipMalloc(&part, split_partial_floats(H, W, clips * T, T, n_full, split_s) * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && in_sf) e = pfnl::launch_sf_from_f32(in, ti, np1, s);   // (the same split the chain kernel's epilogue applies: sf_split4)
-    pfnl::ConvSplitParams q{in_sf ? reinterpret_cast<const float*>(ti) : in, dw, reinterpret_cast<const float*>(dw + n3 + n1), nullptr, nullptr, reinterpret_cast<float*>(t1), H, W, clips * T, T, 1};
-    q.in_sf = in_sf ? 1 : 0;
-    q.wpack2 = dw + n3;
-    q.bias2 = reinterpret_cast<const float*>(dw + n3 + n1 + 128);
-    q.out2 = reinterpret_cast<float*>(tb);
-    q.n_full = n_full;
-    q.split_s = split_s;
-    q.split_q = split_q;
-    q.partial = part;
-    if (e == hipSuccess) e = pfnl::launch_conv3x3_c1c10(q, s);
-    if (e == hipSuccess && split_s) {                                   // the cut chains' base from the parts' raw conv10_i sums
-        pfnl::ConvSplitParams f{};
-        f.H = H;
-        f.W = W;
-        f.items = clips * T;
-        f.add_div = T;
-        f.act = 1;
-        f.n_full = n_full;
-        f.split_s = split_s;
-        f.split_q = split_q;
-        f.partial = part;
-        f.out2 = reinterpret_cast<float*>(tb);
-        e = pfnl::launch_c10_finalize(f, s);
-    }
-    if (e == hipSuccess) e = pfnl::launch_sf_to_f32(t1, out1, np1, s);
-    if (e == hipSuccess) e = pfnl::launch_sf_to_f32(tb, base, npb, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    (void)hipFree(t1);
-    (void)hipFree(tb);
-    if (ti) (void)hipFree(ti);
-    if (part) (void)hipFree(part);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv1+conv10 split16 op: ") + hipGetErrorString(e));
-    return 0;
-}
-int pfnl_op_conv1_conv10_split16(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
-                                 const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
-                                 void* stream) {
-    return op_conv1_conv10_split16(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, frames_per_clip, H, W, stream, false);
-}
-// ... with the input converted to the split format first and the halo taken from there by LDS-DMA (conv3x3_c1c10_kernel<true>, option
-// split16_sf0): the same operands in the same order - bit-identical to pfnl_op_conv1_conv10_split16
-int pfnl_op_conv1_conv10_split16_sf0(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
-                                     const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
-                                     void* stream) {
-    return op_conv1_conv10_split16(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, frames_per_clip, H, W, stream, true);
-}
-
-// ---- C-ABI v4: the chained launches with the MFMA shape and the split-chain geometry chosen by the caller instead of trunk_plan, so that the
-// 16x16x32 forms and every cut of a chain can be compared with the spec op by op (include/pfnl_hip.h)
-int pfnl_op_conv2_chain_ex(const float* in, const float* kernel_host, const float* bias_host, const float* base, int add_div, const float* resid,
-                           float* out, int items, int H, int W, int act, int mfma, int n_full, int split_s, int split_q, void* stream) {
-    if (!in || !kernel_host || !out || !base || !resid) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || H < 1 || W < 1 || add_div < 1 || items % add_div) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
-    if (mfma != 16 && mfma != 32) return fail(PFNL_ERR_INVALID, "mfma must be 16 or 32");
-    if (mfma == 16 && split_s) return fail(PFNL_ERR_INVALID, "split chains run on the 32x32x16 kernel only");
-    if (!split_args_ok(H, W, items, add_div, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
-    return op_conv2_chain(in, kernel_host, bias_host, base, add_div, resid, out, nullptr, items, H, W, act, stream, mfma, n_full, split_s, split_q);
-}
-
-int pfnl_op_conv1_conv10_split16_ex(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
-                                    const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
-                                    int n_full, int split_s, int split_q, void* stream) {
-    if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const int T = frames_per_clip;
-    if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
-    if (!split_args_ok(H, W, clips * T, T, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
-    return op_conv1_conv10_split16(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, T, H, W, stream, false, n_full, split_s, split_q);
-}
-
-int pfnl_op_conv3x3_accum_split16_ex(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
-                                     int frames_per_clip, int H, int W, int cout, int act, int n_full, int split_s, int split_q, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (clips < 1 || frames_per_clip < 1 || H < 1 || W < 1 || cout < 1 || cout > 64) return fail(PFNL_ERR_INVALID, "accumulating conv needs cout <= 64");
-    if ((long long)H * W * 256 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
-    if (!split_args_ok(H, W, clips * frames_per_clip, frames_per_clip, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
-    return op_conv3x3_accum_split16(in, kernel_host, bias_host, out, clips, frames_per_clip, H, W, cout, act, stream, n_full, split_s, split_q);
-}
-
-// the bf16 chained modes on the third-generation kernel, called directly (PFNL_BF16_V3 does not apply); mfma = 16 adds the M16 pack
-static int op_bf16_v3(int mode, const uint16_t* in, const float* k_host, const float* b_host, const uint16_t* addend, int add_div,
-                      const uint16_t* resid, uint16_t* out, const float* k10_host, const float* b10_host, uint16_t* base, int items, int H,
-                      int W, int act, int mfma, int n_full, int split_s, int split_q, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const int T = add_div;
-    const size_t n3 = pfnl::conv3x3_bf16_pack_halfs(), n1 = mode == 2 ? pfnl::conv1x1_bf16_pack_halfs(T) : 0;
-    // [3x3 pack | M16 pack | conv10_i pack | bias | conv10_i bias]
-    std::vector<uint16_t> pack(2 * n3 + n1 + 256, 0);
-    pfnl::conv3x3_bf16_pack_weights(k_host, 64, 0, pack.data());
-    pfnl::conv3x3_bf16_pack_weights16(k_host, 64, 0, pack.data() + n3);
-    if (mode == 2) pfnl::conv1x1_bf16_pack_weights(k10_host, T, pack.data() + 2 * n3);
-    if (b_host) std::memcpy(&pack[2 * n3 + n1], b_host, 64 * sizeof(float));
-    if (b10_host) std::memcpy(&pack[2 * n3 + n1 + 128], b10_host, 64 * sizeof(float));
-    uint16_t* dw = nullptr;
-    float* part = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && mode == 2 && split_s) e = hipMalloc(&part, split_partial_floats(H, W, items, T, n_full, split_s) * sizeof(float));
-    const float* const db = reinterpret_cast<const float*>(dw + 2 * n3 + n1);
-    pfnl::ConvBf16Params q{in, dw, db, addend, resid, out, H, W, items, T, act};
-    if (mode == 2) {
-        q.x_w = dw + 2 * n3;
-        q.x_bias = db + 64;
-        q.x_out = base;
-    }
-    q.n_full = n_full;
-    q.split_s = split_s;
-    q.split_q = split_q;
-    q.partial = part;
-    if (mfma == 16) q.wpack16 = dw + n3;
-    if (e == hipSuccess) e = pfnl::launch_conv3x3_bf16_v3(q, mode, s);
-    if (e == hipSuccess && mode == 2 && split_s) e = pfnl::launch_c10_finalize_bf16(q, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (part) (void)hipFree(part);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("bf16 v3 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv3x3_bf16_ex(const uint16_t* in, const float* kernel_host, const float* bias_host, const uint16_t* addend, int add_div,
-                            const uint16_t* resid, uint16_t* out, int items, int H, int W, int act, int mfma, int n_full, int split_s,
-                            int split_q, void* stream) {
-    if (!in || !kernel_host || !addend || !resid || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || H < 1 || W < 1 || add_div < 1 || items % add_div) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    if ((long long)H * W * 128 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
-    if (mfma != 16 && mfma != 32) return fail(PFNL_ERR_INVALID, "mfma must be 16 or 32");
-    if (!split_args_ok(H, W, items, add_div, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
-    return op_bf16_v3(1, in, kernel_host, bias_host, addend, add_div, resid, out, nullptr, nullptr, nullptr, items, H, W, act, mfma, n_full,
-                      split_s, split_q, stream);
-}
-
-int pfnl_op_conv1_conv10_bf16_ex(const uint16_t* in, const float* k1_host, const float* b1_host, const float* k10_host, const float* b10_host,
-                                 uint16_t* out1, uint16_t* base, int clips, int frames_per_clip, int H, int W, int mfma, int n_full, int split_s,
-                                 int split_q, void* stream) {
-    if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const int T = frames_per_clip;
-    if (clips < 1 || (T != 3 && T != 5 && T != 7) || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    if ((long long)H * W * 128 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the persistent kernel");
-    if (mfma != 16 && mfma != 32) return fail(PFNL_ERR_INVALID, "mfma must be 16 or 32");
-    if (!split_args_ok(H, W, clips * T, T, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
-    return op_bf16_v3(2, in, k1_host, b1_host, nullptr, T, nullptr, out1, k10_host, b10_host, base, clips * T, H, W, 1, mfma, n_full, split_s,
-                      split_q, stream);
-}
-
-// conv10_i with its input and / or output in the split format (fp32 at the hook's interface, see above)
-int pfnl_op_conv1x1_split16_sf(const float* in, const float* kernel_host, const float* bias_host, float* out, int items,
-                               int frames_per_item, int HW, int act, int in_sf, int out_sf, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || frames_per_item < 1 || HW < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const int T = frames_per_item;
-    const size_t nh = pfnl::conv1x1_split16_pack_halfs(T);
-    std::vector<uint16_t> pack(nh + 128, 0);
-    pfnl::conv1x1_split16_pack_weights(kernel_host, T, pack.data());
-    if (bias_host) std::memcpy(&pack[nh], bias_host, 64 * sizeof(float));
-    const size_t npin = (size_t)items * T * HW, npout = (size_t)items * HW;
-    uint16_t *dw = nullptr, *tin = nullptr, *tout = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(uint16_t)));
-    hipError_t e = hipMalloc(&tin, npin * 256);
-    if (e == hipSuccess) e = hipMalloc(&tout, npout * 256);
-    if (e == hipSuccess) e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && in_sf) e = pfnl::launch_sf_from_f32(in, tin, npin, s);
-    if (e == hipSuccess)
-        e = pfnl::launch_conv1x1_split16(in_sf ? reinterpret_cast<const float*>(tin) : in, dw, reinterpret_cast<const float*>(dw + nh),
-                                         out_sf ? reinterpret_cast<float*>(tout) : out, items, T, HW, act, s, in_sf != 0, out_sf != 0);
-    if (e == hipSuccess && out_sf) e = pfnl::launch_sf_to_f32(tout, out, npout, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    (void)hipFree(tin);
-    (void)hipFree(tout);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv1x1 split16 SF op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv1x1_stream(const float* in, const float* kernel_host, const float* bias_host, float* out, int items,
-                           int frames_per_item, int HW, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || frames_per_item < 1 || HW < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const int T = frames_per_item;
-    std::vector<float> pack(pfnl::conv1x1_pack_floats(T) + 64, 0.f);
-    pfnl::conv1x1_pack_weights(kernel_host, T, pack.data());
-    const size_t boff = pack.size() - 64;
-    if (bias_host) std::memcpy(&pack[boff], bias_host, 64 * sizeof(float));
-    float* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = pfnl::launch_conv1x1_stream(in, dw, dw + boff, out, items, T, HW, act, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("conv1x1 op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-static int op_conv3x3_wino(bool ws, const float* in, const float* kernel_host, const float* bias_host,
-                           const float* addend, int add_div, const float* resid, float* out, int items, int H,
-                           int W, int act, void* stream) {
-    if (!in || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (items < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "winograd conv needs even H, W");
-    if ((addend != nullptr) != (resid != nullptr))
-        return fail(PFNL_ERR_INVALID, "addend and resid must be given together or not at all");
-    if (addend && add_div < 1) return fail(PFNL_ERR_INVALID, "add_div must be >= 1");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<float> pack(pfnl::wino_pack_floats() + 64, 0.f);
-    pfnl::wino_pack_weights(kernel_host, 64, 0, pack.data());
-    const size_t boff = pack.size() - 64;
-    if (bias_host) std::memcpy(&pack[boff], bias_host, 64 * sizeof(float));
-    float* dw = nullptr;
-    HIPCHK(hipMalloc(&dw, pack.size() * sizeof(float)));
-    hipError_t e = hipMemcpy(dw, pack.data(), pack.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        pfnl::WinoParams wp{in, dw, dw + boff, addend, resid, out, H, W, addend ? add_div : 1, act, items, nullptr};
-#ifdef PFNL_WINO_TIMING
-        long long* dbg = nullptr;
-        const size_t dbg_n = 4096 * 64;
-        if (hipMalloc(&dbg, dbg_n * sizeof(long long)) == hipSuccess) {
-            (void)hipMemset(dbg, 0, dbg_n * sizeof(long long));
-            wp.dbg = dbg;
-        }
-#endif
-        e = ws ? pfnl::launch_conv_wino_ws(wp, s) : pfnl::launch_conv_wino(wp, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-#ifdef PFNL_WINO_TIMING
-        if (dbg) {
-            std::vector<long long> hst(dbg_n);
-            (void)hipMemcpy(hst.data(), dbg, dbg_n * sizeof(long long), hipMemcpyDeviceToHost);
-            if (ws) {
-                for (int b : {0, 8, 101, 200, 255})
-                    for (int role = 0; role < 2; ++role) {
-                        const long long* t = &hst[(size_t)b * 128 + role * 64];
-                        std::fprintf(stderr, "WS_TIMING wg %d %s:", b, role ? "helper" : "matrix");
-                        for (int i = 1; i < 64 && t[i]; ++i) std::fprintf(stderr, " %lld", t[i] - t[i - 1]);
-                        std::fprintf(stderr, " | t0-t0[wg0] %lld\n", t[0] - hst[0]);
-                    }
-            } else
-            for (int b : {0, 8, 16, 1024, 2048, 4096, 7000}) {
-                std::fprintf(stderr, "WINO_TIMING wg %d:", b);
-                for (int i = 1; i < 16 && hst[(size_t)b * 16 + i]; ++i)
-                    std::fprintf(stderr, " %lld", hst[(size_t)b * 16 + i] - hst[(size_t)b * 16]);
-                std::fprintf(stderr, " | t0-t0[wg0] %lld\n", hst[(size_t)b * 16] - hst[0]);
-            }
-            (void)hipFree(dbg);
-        }
-#endif
-    }
-    (void)hipFree(dw);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("winograd conv op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_conv3x3_winograd(const float* in, const float* kernel_host, const float* bias_host,
-                             const float* addend, int add_div, const float* resid, float* out, int items, int H,
-                             int W, int act, void* stream) {
-    return op_conv3x3_wino(false, in, kernel_host, bias_host, addend, add_div, resid, out, items, H, W, act, stream);
-}
-
-int pfnl_op_conv3x3_winograd_ws(const float* in, const float* kernel_host, const float* bias_host,
-                                const float* addend, int add_div, const float* resid, float* out, int items, int H,
-                                int W, int act, void* stream) {
-    return op_conv3x3_wino(true, in, kernel_host, bias_host, addend, add_div, resid, out, items, H, W, act, stream);
-}
-
-
-static int op_nonlocal(int bf16 /* 0 f32, 2 f16 split, 3 f16 (hi parts only) */, const float* x, const float* wg, const float* bg, const float* ww, const float* bw,
-                       float* out, int B, int T, int H, int W, void* stream) {
-    if (!x || !wg || !bg || !ww || !bw || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if ((T != 3 && T != 5 && T != 7) || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1))
-        return fail(PFNL_ERR_INVALID, "unsupported non-local geometry");
-    hipStream_t s = (hipStream_t)stream;
-    const int C = 12 * T, CP = pfnl::nl_padded_ch(C), N = (H / 2) * (W / 2);
-    std::vector<float> blob((size_t)CP * CP + CP, 0.f);
-    for (int ci = 0; ci < C; ++ci)
-        for (int co = 0; co < C; ++co) {
-            double acc = 0.0;
-            for (int cm = 0; cm < C; ++cm) acc += (double)wg[(size_t)ci * C + cm] * (double)ww[(size_t)cm * C + co];
-            blob[(size_t)ci * CP + co] = (float)acc;
-        }
-    for (int co = 0; co < C; ++co) {
-        double acc = bw[co];
-        for (int cm = 0; cm < C; ++cm) acc += (double)bg[cm] * (double)ww[(size_t)cm * C + co];
-        blob[(size_t)CP * CP + co] = (float)acc;
-    }
-    float* d = nullptr;
-    const size_t nX = (size_t)B * N * CP;
-    const size_t nP = pfnl::nl_partial_floats(B, N, C);
-    const size_t n16 = bf16 ? (pfnl::nl_f16_scratch_halfs(B, N) + 1) / 2 : 0;   // in floats
-    HIPCHK(hipMalloc(&d, (blob.size() + 2 * nX + nP + n16 + 64) * sizeof(float)));
-    float* dX = d + blob.size();
-    float* dXo = dX + nX;
-    float* dP = nP ? dXo + nX : nullptr;
-    uint16_t* d16 = reinterpret_cast<uint16_t*>(d + (blob.size() + 2 * nX + nP + 63) / 64 * 64);
-    hipError_t e = hipMemcpy(d, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = pfnl::launch_nl_pack(x, dX, B, T, H, W, s);
-    if (e == hipSuccess)
-        e = bf16 >= 2 ? pfnl::launch_nl_attn_f16(dX, dXo, d, d + (size_t)CP * CP, dP, d16, B, N, C, s, 0, -1, bf16 == 2)
-                    : pfnl::launch_nl_attn(dX, dXo, d, d + (size_t)CP * CP, dP, B, N, C, s);
-    if (e == hipSuccess) e = pfnl::launch_nl_unpack(dXo, out, B, T, H, W, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(d);
-    if (e != hipSuccess) return fail(PFNL_ERR_HIP, std::string("nonlocal op: ") + hipGetErrorString(e));
-    return 0;
-}
-
-int pfnl_op_nonlocal(const float* x, const float* wg, const float* bg, const float* ww, const float* bw,
-                     float* out, int B, int T, int H, int W, void* stream) {
-    return op_nonlocal(0, x, wg, bg, ww, bw, out, B, T, H, W, stream);
-}
-
-int pfnl_op_nonlocal_split16(const float* x, const float* wg, const float* bg, const float* ww, const float* bw,
-                             float* out, int B, int T, int H, int W, void* stream) {
-    return op_nonlocal(2, x, wg, bg, ww, bw, out, B, T, H, W, stream);
-}
-
-int pfnl_op_nonlocal_f16(const float* x, const float* wg, const float* bg, const float* ww, const float* bw,
-                         float* out, int B, int T, int H, int W, void* stream) {
-    return op_nonlocal(3, x, wg, bg, ww, bw, out, B, T, H, W, stream);
-}
-
-int pfnl_op_bicubic(const float* x, float* out, int B, int H, int W, int scale, void* stream) {
-    if (!x || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (B < 1 || H < 1 || W < 1 || (scale != 2 && scale != 4)) return fail(PFNL_ERR_INVALID, "bad bicubic geometry");
-    HIPCHK(pfnl::launch_bicubic(x, out, B, H, W, scale, (hipStream_t)stream));
-    return 0;
-}
-
-int pfnl_op_blur_decimate(const float* hr, float* lr, int F, int H, int W, int scale, void* stream) {
-    if (!hr || !lr) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (F < 1 || H < 7 || W < 7 || (scale != 2 && scale != 4))
-        return fail(PFNL_ERR_INVALID, "blur_decimate needs H, W >= 7 (reflect pad 6) and scale 2 or 4");
-    HIPCHK(pfnl::launch_blur_decimate(hr, lr, F, H, W, scale, (hipStream_t)stream));
-    return 0;
-}
-
-int pfnl_selftest_mfma(int device_id) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PFNL_ERR_NODEVICE, "no HIP device visible");
-    HIPCHK(hipSetDevice(device_id));
-    int bad = -1;
-    HIPCHK(pfnl::run_mfma_selftest(&bad));
-    if (bad != 0) return fail(PFNL_ERR_STATE, "MFMA fragment layout mismatch: " + std::to_string(bad) + " elements");
     return 0;
 }
 

@@ -87,11 +87,6 @@ struct pfnl_comm {
 };
 
 #define COMM_FAIL(code, msg) return pfnl_internal_fail(code, msg)
-#define HIPCHK(expr)                                                                                      \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) COMM_FAIL(PFNL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 #define NCHK(expr)                                                                                             \
     do {                                                                                                       \
         ncclResult_t _r = (expr);                                                                              \

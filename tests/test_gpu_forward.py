@@ -1157,3 +1157,54 @@ def test_split16_domain_weight_range_selects_f32_kernels():
     y = eng.forward(x)
     assert eng.range_reruns() == 0 and np.isfinite(y).all() and _rel_err(y, ref) < 5e-5
     eng.close()
+
+
+# every option key: each accepted value -> the name pfnl_get_option reads back for it (include/pfnl_hip.h)
+_OPTION_VALUES = {
+    "graph": {"auto": "auto", "on": "on", "off": "off"},
+    "conv3x3": {"winograd": "winograd", "winograd_ws": "winograd", "winograd_tile": "winograd_tile", "direct": "direct",
+                "split16": "split16", "auto": "auto"},
+    "strict_fp32": {"on": "on", "off": "off"},
+    "small": {"auto": "auto", "on": "on", "off": "off"},
+    "split16_chain": {"on": "on", "off": "off"},
+    "split16_c10": {"on": "on", "off": "off"},
+    "split16_mid": {"auto": "auto", "off": "off"},
+    "split16_sf0": {"on": "on", "off": "off"},
+    "split16_splitchains": {"auto": "auto", "off": "off"},
+    "split16_sf": {"on": "on", "off": "off"},
+    "conv2": {"grouped": "grouped", "split": "split"},
+    "split16_mfma": {"16": "16", "32": "32"},
+    "bf16_mfma": {"16": "16", "32": "32"},
+    "bf16_conv10": {"fused": "fused", "separate": "separate"},
+    "precision": {"bf16": "bf16", "fp32": "fp32"},
+    "merge1": {"auto": "auto", "split16": "split16", "winograd": "winograd"},
+    "nl_type": {"auto": "auto", "0": "0", "embedded_gaussian": "0", "1": "1", "gaussian": "1", "2": "2", "dot_product": "2"},
+    "nl_sub_sample": {"1": "1", "2": "2", "64": "64"},
+    "small_c10": {"on": "on", "off": "off"},
+    "bf16_nonlocal": {"f16": "f16"},
+    "nonlocal": {"f32": "f32", "split16": "split16", "auto": "auto"},
+    "conv1x1": {"stream": "stream", "tiled": "tiled", "split16": "split16"},
+}
+
+
+def test_every_option_value_round_trips():
+    """pfnl_set_option / pfnl_get_option over the whole option table: every accepted name of every key is taken, reads back as its
+    canonical name, and that name is taken back; a bad value is refused (naming the key) and leaves the value as it was; an unknown key
+    is refused by both calls."""
+    from pfnl_amd._capi import PFNLHipError
+    eng = PFNLEngine(PFNLGeometry(num_block=1), device=0)
+    for key, values in _OPTION_VALUES.items():
+        for value, canonical in values.items():
+            eng.set_option(key, value)
+            assert eng.get_option(key) == canonical, (key, value)
+            eng.set_option(key, eng.get_option(key))
+            assert eng.get_option(key) == canonical, (key, value)
+        for bad in ("", "bogus", "65" if key == "nl_sub_sample" else "ON"):
+            with pytest.raises(PFNLHipError, match=key):
+                eng.set_option(key, bad)
+            assert eng.get_option(key) == canonical, (key, bad)
+    with pytest.raises(PFNLHipError, match="unknown option no_such_option"):
+        eng.set_option("no_such_option", "on")
+    with pytest.raises(PFNLHipError, match="unknown option no_such_option"):
+        eng.get_option("no_such_option")
+    eng.close()
