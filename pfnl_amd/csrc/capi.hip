@@ -441,19 +441,10 @@ TrunkPlan trunk_plan(const pfnl_handle* h, int B, int H, int W) {
         pl.fuse10 = h->bf16_fuse10 && !pl.bmid;
         pl.launches_per_block = pl.fuse10 ? 3 : 4;
         pl.c1x1_launches = pl.fuse10 ? 0 : 1;
-        if (pl.fuse10 && h->split_chains && T <= 7 && fits32) {        // SPLIT CHAINS of the two chained launches (the rule of the fp32 trunk below)
-            const int grid = conv_split16_grid();
-            const int R = pl.chains % grid;
-            if (pl.chains > grid && R > 0 && grid / R >= 2) {
-                const int s0 = std::min(T, grid / R), q = (T + s0 - 1) / s0, s = (T + q - 1) / q;
-                if (s >= 2) {
-                    pl.n_full = pl.chains - R;
-                    pl.split_s = s;
-                    pl.split_q = q;
-                    pl.launches_per_block += 1;                         // c10_finalize_bf16_kernel
-                    pl.c1x1_launches = 1;
-                }
-            }
+        // SPLIT CHAINS of the two chained launches (chain_order.h, split_rule)
+        if (pl.fuse10 && h->split_chains && fits32 && split_rule(pl.chains, T, persistent_grid(device_cu_count()), pl.n_full, pl.split_s, pl.split_q)) {
+            pl.launches_per_block += 1;                                 // c10_finalize_bf16_kernel
+            pl.c1x1_launches = 1;
         }
         pl.name = pl.bmid ? "bf16_mid4" : (pl.fuse10 ? (pl.split_s ? "bf16_3_split" : "bf16_3") : "bf16_4");
         pl.mfma = h->bf16_m16 ? 16 : 32;
@@ -483,26 +474,14 @@ TrunkPlan trunk_plan(const pfnl_handle* h, int B, int H, int W) {
     pl.conv2_grouped = pl.algo == 3 && h->conv2_grouped && wino_groups >= 224 && fits32;
     pl.launches_per_block = (pl.c10_fused ? 1 : 2) + ((pl.chain || pl.conv2_grouped) ? 1 : 2);
     pl.c1x1_launches = pl.c10_fused ? 0 : 1;
-    if (pl.c10_fused && pl.chain && h->split_chains && T <= 7) {
-        // SPLIT CHAINS: with R = chains mod grid chains in a last, partial round, a workgroup with one chain more than the others sets the time of
-        // both launches (5 clips of 128x128 = 1.25 rounds: 7.2 ms against 4.5 for 4).  When at least two parts of a chain fit the idle
-        // workgroups (R <= grid / 2), those R chains are cut by frames: s = grid / R parts of q = ceil(T / s) frames.
-        const int grid = conv_split16_grid();
-        const int R = pl.chains % grid;
-        if (pl.chains > grid && R > 0 && grid / R >= 2) {
-            const int s0 = std::min(T, grid / R), q = (T + s0 - 1) / s0, s = (T + q - 1) / q;
-            if (s >= 2) {
-                pl.n_full = pl.chains - R;
-                pl.split_s = s;
-                pl.split_q = q;
-                pl.launches_per_block += 1;                             // c10_finalize_kernel
-                pl.c1x1_launches = 1;
-            }
-        }
+    // SPLIT CHAINS of conv1_i + conv10_i and conv2_i (chain_order.h, split_rule)
+    if (pl.c10_fused && pl.chain && h->split_chains && split_rule(pl.chains, T, persistent_grid(device_cu_count()), pl.n_full, pl.split_s, pl.split_q)) {
+        pl.launches_per_block += 1;                                     // c10_finalize_kernel
+        pl.c1x1_launches = 1;
     }
     // the chain launch on 16x16x32: where every CU has a chain the launch sits on the power cap and the shape's energy counts; below that (UDM10: 230
     // chains) its extra cycles do (+0.9 %); split chains and the split-format copy stay on the 32x32x16 kernel
-    pl.mfma = (h->s16_m16 && pl.c10_fused && pl.chain && !pl.sf0 && !pl.split_s && pl.chains >= conv_split16_grid()) ? 16 : 32;
+    pl.mfma = (h->s16_m16 && pl.c10_fused && pl.chain && !pl.sf0 && !pl.split_s && pl.chains >= persistent_grid(device_cu_count())) ? 16 : 32;
     pl.name = pl.mid ? "mid4" : (pl.c10_fused && pl.chain) ? (pl.sf0 ? "chain2_sf0" : (pl.split_s ? "chain2_split" : "chain2"))
             : pl.algo == 4 ? (pl.launches_per_block == 3 ? "split16_3" : "split16_4")
             : pl.algo == 3 ? (pl.conv2_grouped ? "winograd_ws3" : "winograd_ws4")

@@ -80,7 +80,7 @@ bool paired(const void* addend, const void* resid) { return (addend == nullptr) 
 // checks (split_geometry_ok) on the grid of the current device, tested before any allocation or launch
 static bool split_args_ok(int H, int W, int items, int T, int n_full, int split_s, int split_q) {
     if (split_s == 0) return true;
-    return split_s <= 7 && pfnl::split_geometry_ok(H, W, items, T, n_full, split_s, split_q, pfnl::conv_split16_grid());
+    return pfnl::split_geometry_ok(H, W, items, T, n_full, split_s, split_q, pfnl::persistent_grid(pfnl::device_cu_count()));
 }
 // floats of the parts' raw sums: one [8][32][64] tile per part of every cut chain
 static size_t split_partial_floats(int H, int W, int items, int T, int n_full, int split_s) {

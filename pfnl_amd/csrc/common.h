@@ -56,6 +56,9 @@ inline int device_cu_count() {                                      // CUs of th
     return n;
 }
 
+// the grid of the persistent launches: whole XCDs (workgroup b runs on XCD b & 7), at least 8 - what split chains' n_full is a multiple of
+inline int persistent_grid(int ncu) { return ncu >= 8 ? ncu / 8 * 8 : 8; }
+
 __device__ __forceinline__ float lrelu(float v) { return fmaxf(v, 0.2f * v); }  // tf.nn.leaky_relu
 
 // ---- MFMA implicit-GEMM convolution (conv_mfma.hip) ------------------------------------------

@@ -572,7 +572,7 @@ hipError_t launch_conv3x3_bf16(const ConvBf16Params& p, hipStream_t s) {
     if ((long long)p.H * p.W * 128 >= 0x7fffffffLL) return hipErrorInvalidValue;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;                    // whole XCDs; surplus workgroups exit at once
+    const int grid = persistent_grid(ncu);                          // surplus workgroups exit at once
     const bool accum = p.out_f32 != nullptr;
     if (accum && (p.addend || p.x_out || p.add_div < 1 || p.items % p.add_div)) return hipErrorInvalidValue;
     const bool with10 = p.x_out != nullptr;

@@ -436,7 +436,7 @@ hipError_t launch_conv3x3_bf16_v2(const ConvBf16Params& p, int mode, hipStream_t
     if (mode < 0 || mode > 2) return hipErrorInvalidValue;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;                    // whole XCDs; surplus workgroups exit at once
+    const int grid = persistent_grid(ncu);                          // surplus workgroups exit at once
     static std::atomic<int> attr_dev[64][3];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;

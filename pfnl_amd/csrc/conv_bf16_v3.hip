@@ -25,6 +25,7 @@
 // group A's two trailing ones): no flags, no spinning.
 #include <type_traits>
 
+#include "chain_order.h"
 #include "common.h"
 #include "conv_bf16.h"
 
@@ -40,7 +41,7 @@ typedef unsigned b3u4 __attribute__((ext_vector_type(4)));
 typedef unsigned b3u2 __attribute__((ext_vector_type(2)));
 
 constexpr int B3_THREADS = 512, B3_GTHREADS = 256;
-constexpr int B3_TH = 8, B3_TW = 32, B3_IH = 10, B3_IW = 34;
+constexpr int B3_TH = CHAIN_TH, B3_TW = CHAIN_TW, B3_IH = 10, B3_IW = 34;
 constexpr int B3_NDMA = (B3_IH * B3_IW + 7) / 8;                    // 43 DMA instructions of 8 pixels x 128 B
 constexpr int B3_TILE_BYTES = B3_NDMA * 1024;                       // 44 032 (the last instruction's 4 surplus pixels land in padding)
 constexpr int B3_W_BYTES = 9 * 4 * 2 * 1024;                        // 73 728: conv3x3_bf16_pack_weights
@@ -711,20 +712,11 @@ __global__ __launch_bounds__(256) void c10_finalize_bf16_kernel(ConvBf16Params p
     }
 }
 
-static bool b3_split_ok(const ConvBf16Params& p, int grid) {
-    const int T = p.add_div;
-    const long long nchains = (long long)((p.W + B3_TW - 1) / B3_TW) * ((p.H + B3_TH - 1) / B3_TH) * (p.items / T);
-    if (p.split_s < 2 || p.split_s > 7 || p.split_q < 1 || p.n_full < 0 || p.n_full % grid || p.n_full >= nchains) return false;
-    if ((long long)p.split_s * p.split_q < T || (long long)(p.split_s - 1) * p.split_q >= T) return false;
-    return (nchains - p.n_full) * p.split_s <= grid;
-}
-
 hipError_t launch_c10_finalize_bf16(const ConvBf16Params& p, hipStream_t s) {
     if (!p.partial || !p.x_out || !p.x_bias || p.items < 1 || p.add_div < 1 || p.items % p.add_div) return hipErrorInvalidValue;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;
-    if (!b3_split_ok(p, grid)) return hipErrorInvalidValue;
+    if (!split_geometry_ok(p.H, p.W, p.items, p.add_div, p.n_full, p.split_s, p.split_q, persistent_grid(ncu))) return hipErrorInvalidValue;
     const long long nchains = (long long)((p.W + B3_TW - 1) / B3_TW) * ((p.H + B3_TH - 1) / B3_TH) * (p.items / p.add_div);
     hipLaunchKernelGGL(c10_finalize_bf16_kernel, dim3((unsigned)(nchains - p.n_full) * 8), dim3(256), 0, s, p);
     return hipGetLastError();
@@ -735,7 +727,7 @@ hipError_t launch_conv3x3_bf16_v3(const ConvBf16Params& p, int mode, hipStream_t
     if (mode < 0 || mode > 2) return hipErrorInvalidValue;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;                    // whole XCDs; surplus workgroups exit at once
+    const int grid = persistent_grid(ncu);                          // surplus workgroups exit at once
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     // p.wpack16 (conv3x3_bf16_pack_weights16): the M16 form of the kernel on that pack
@@ -743,7 +735,7 @@ hipError_t launch_conv3x3_bf16_v3(const ConvBf16Params& p, int mode, hipStream_t
     const bool m16 = p.wpack16 != nullptr;
     if (m16) q.wpack = p.wpack16;
     if (p.split_s) {                                                // split chains: the chained modes only, geometry as the kernels assume it
-        if (mode == 0 || p.flat || !b3_split_ok(p, grid) || (mode == 2 && !p.partial)) return hipErrorInvalidValue;
+        if (mode == 0 || p.flat || !split_geometry_ok(p.H, p.W, p.items, p.add_div, p.n_full, p.split_s, p.split_q, grid) || (mode == 2 && !p.partial)) return hipErrorInvalidValue;
         if (m16) return mode == 1 ? b3_launch<1, true, true>(q, grid, dev, s) : b3_launch<2, true, true>(q, grid, dev, s);
         return mode == 1 ? b3_launch<1, true>(p, grid, dev, s) : b3_launch<2, true>(p, grid, dev, s);
     }

@@ -40,7 +40,7 @@ typedef _Float16 sfh8 __attribute__((ext_vector_type(8)));
 typedef unsigned sfu4 __attribute__((ext_vector_type(4)));
 
 constexpr int SF_THREADS = 512;
-constexpr int SF_TH = 8, SF_TW = 32;
+constexpr int SF_TH = CHAIN_TH, SF_TW = CHAIN_TW;
 constexpr int SF_IH = SF_TH + 2, SF_IW = SF_TW + 2;
 constexpr int SF_NPIX = SF_IH * SF_IW;                              // 340
 constexpr int SF_NDMA = (SF_NPIX + 7) / 8;                          // 43 DMA instructions of 8 pixels x 128 B
@@ -488,40 +488,19 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
     const int wbytes = W * 256;
     const int T = p.add_div, gT = T + 1;                            // tiles of a chain: the shared half, then the T frames
     const int nchains = per_item * (p.items / T);
-    const int xcd = blockIdx.x & 7, xj = blockIdx.x >> 3, cpx = gridDim.x >> 3;
-    // SPLIT CHAINS (round 6; p.split_s > 0; conv_split16.h): whole chains for the first p.n_full, one PART per workgroup of each chain behind
-    // them - the shared half (recomputed per part: one tile in 1 + frames) and the part's frames [sp_f0, sp_f1)
-    const int n_full = SPLIT ? p.n_full : nchains;
-    const int per_xcd = (n_full + 7) >> 3;
-    const int cbeg = xcd * per_xcd;
-    const int ccnt = min(per_xcd, n_full - cbeg);
-    if (!SPLIT && xj >= ccnt) return;
-    const int nfull_tiles = ((!SPLIT || xj < ccnt) ? (ccnt - xj + cpx - 1) / cpx : 0) * gT;
-    [[maybe_unused]] const int slot = xcd * cpx + xj;
-    const bool has_part = SPLIT && slot < (nchains - n_full) * p.split_s;
-    const int sp_chain = has_part ? n_full + slot / p.split_s : 0;
-    const int sp_f0 = has_part ? (slot % p.split_s) * p.split_q : 0, sp_f1 = has_part ? min(T, sp_f0 + p.split_q) : 0;
-    const int nt_tiles = nfull_tiles + (has_part ? 1 + sp_f1 - sp_f0 : 0);
+    // SPLIT CHAINS (round 6; p.split_s > 0; chain_order.h): whole chains first, then one PART per workgroup of a cut chain - the shared half
+    // (recomputed per part: one tile in 1 + frames) and the part's frames [sp_f0, sp_f1)
+    ChainShare<SPLIT, 1> cs(blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3, nchains, p.n_full);
+    if (cs.idle()) return;
+    cs.deal(gT, p.split_s, p.split_q);
+    const int nt_tiles = cs.nt;
     if (SPLIT && nt_tiles <= 0) return;
     // tile k -> (f = position in the chain: 0 = shared half, 1 .. T = frame f - 1; clip, y0, x0)
-#define SFC_TILE(k_, f_, clip_, y0_, x0_)                                                        \
-    do {                                                                                         \
-        int ch_;                                                                                 \
-        if (!SPLIT || (k_) < nfull_tiles) {                                                      \
-            const int ci_ = (k_) / gT;                                                           \
-            f_ = (k_) - ci_ * gT;                                                                \
-            ch_ = cbeg + xj + ci_ * cpx;                                                         \
-        } else {                                                                                 \
-            const int kk_ = (k_) - nfull_tiles;                                                  \
-            f_ = kk_ == 0 ? 0 : sp_f0 + kk_;                                                     \
-            ch_ = sp_chain;                                                                      \
-        }                                                                                        \
-        clip_ = ch_ / per_item;                                                                  \
-        const int sp_ = ch_ - clip_ * per_item;                                                  \
-        const int ty_ = sp_ / tiles_x;                                                           \
-        y0_ = ty_ * SF_TH;                                                                       \
-        x0_ = (sp_ - ty_ * tiles_x) * SF_TW;                                                     \
-    } while (0)
+    auto decode = [&](int k, int& f, int& clip, int& y0, int& x0) __attribute__((always_inline)) {
+        int ch;
+        cs.tile(k, gT, ch, f);
+        chain_tile(ch, per_item, tiles_x, 1, 0, clip, y0, x0);
+    };
 #define SFC_HALF(u_) ((((u_) >> 1) ^ (u_)) & 1)
 
     const float bias_r = tid < 64 ? p.bias[tid] : 0.f;
@@ -666,7 +645,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
 
     // ---- prologue: halo of unit 0 (the first chain's shared half: `base`) and its weights (pack 0 = shared half, channel half 0)
     int c_f, c_clip, c_y0, c_x0, n_f, n_clip, n_y0, n_x0;
-    SFC_TILE(0, c_f, c_clip, c_y0, c_x0);
+    decode(0, c_f, c_clip, c_y0, c_x0);
     n_f = c_f;
     n_clip = c_clip;
     n_y0 = c_y0;
@@ -770,7 +749,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
 #endif
                         if constexpr (PAR == 0) {                   // decode the next tile (past the end: this one again - a harmless re-read)
                             const int kn = min(kt + 1, nt_tiles - 1);
-                            SFC_TILE(kn, n_f, n_clip, n_y0, n_x0);
+                            decode(kn, n_f, n_clip, n_y0, n_x0);
                         }
                     }
                     if constexpr (g == 4) {
@@ -883,7 +862,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
                 // (+ bias) as the initial C of the frames that follow, and is cleared behind the chain's last frame (the next
                 // tile is a shared half again: initial C = 0).  Branch-free (selects on wave-uniform conditions): arms that
                 // define 32-register vectors cost the allocator live copies of both.
-                const bool head = c_f == 0, last = c_f == ((SPLIT && kt >= nfull_tiles) ? sp_f1 : T);   // (the last frame of a whole chain / of this workgroup's part)
+                const bool head = c_f == 0, last = c_f == ((SPLIT && kt >= cs.nfull_tiles) ? cs.sp_f1 : T);   // (the last frame of a whole chain / of this workgroup's part)
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
                     const f32x16 fold = accm[n] + accc[n] * SF_ISCALE;
@@ -925,7 +904,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
 #undef SFC_DMA_HALO
 #undef SFC_DMA_W
 #undef SFC_HALF
-#undef SFC_TILE
 #undef SFC_BARRIER
 }
 
@@ -986,40 +964,19 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
     const int wbytes = W * 256;
     const int T = p.add_div, gT = T + 1;                            // tiles of a chain: the shared half, then the T frames
     const int nchains = per_item * (p.items / T);
-    const int xcd = blockIdx.x & 7, xj = blockIdx.x >> 3, cpx = gridDim.x >> 3;
-    // SPLIT CHAINS (round 6; p.split_s > 0; conv_split16.h): whole chains for the first p.n_full, one PART per workgroup of each chain behind
-    // them - the shared half (recomputed per part: one tile in 1 + frames) and the part's frames [sp_f0, sp_f1)
-    const int n_full = SPLIT ? p.n_full : nchains;
-    const int per_xcd = (n_full + 7) >> 3;
-    const int cbeg = xcd * per_xcd;
-    const int ccnt = min(per_xcd, n_full - cbeg);
-    if (!SPLIT && xj >= ccnt) return;
-    const int nfull_tiles = ((!SPLIT || xj < ccnt) ? (ccnt - xj + cpx - 1) / cpx : 0) * gT;
-    [[maybe_unused]] const int slot = xcd * cpx + xj;
-    const bool has_part = SPLIT && slot < (nchains - n_full) * p.split_s;
-    const int sp_chain = has_part ? n_full + slot / p.split_s : 0;
-    const int sp_f0 = has_part ? (slot % p.split_s) * p.split_q : 0, sp_f1 = has_part ? min(T, sp_f0 + p.split_q) : 0;
-    const int nt_tiles = nfull_tiles + (has_part ? 1 + sp_f1 - sp_f0 : 0);
+    // SPLIT CHAINS (round 6; p.split_s > 0; chain_order.h): whole chains first, then one PART per workgroup of a cut chain - the shared half
+    // (recomputed per part: one tile in 1 + frames) and the part's frames [sp_f0, sp_f1)
+    ChainShare<SPLIT, 1> cs(blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3, nchains, p.n_full);
+    if (cs.idle()) return;
+    cs.deal(gT, p.split_s, p.split_q);
+    const int nt_tiles = cs.nt;
     if (SPLIT && nt_tiles <= 0) return;
     // tile k -> (f = position in the chain: 0 = shared half, 1 .. T = frame f - 1; clip, y0, x0)
-#define SFC_TILE(k_, f_, clip_, y0_, x0_)                                                        \
-    do {                                                                                         \
-        int ch_;                                                                                 \
-        if (!SPLIT || (k_) < nfull_tiles) {                                                      \
-            const int ci_ = (k_) / gT;                                                           \
-            f_ = (k_) - ci_ * gT;                                                                \
-            ch_ = cbeg + xj + ci_ * cpx;                                                         \
-        } else {                                                                                 \
-            const int kk_ = (k_) - nfull_tiles;                                                  \
-            f_ = kk_ == 0 ? 0 : sp_f0 + kk_;                                                     \
-            ch_ = sp_chain;                                                                      \
-        }                                                                                        \
-        clip_ = ch_ / per_item;                                                                  \
-        const int sp_ = ch_ - clip_ * per_item;                                                  \
-        const int ty_ = sp_ / tiles_x;                                                           \
-        y0_ = ty_ * SF_TH;                                                                       \
-        x0_ = (sp_ - ty_ * tiles_x) * SF_TW;                                                     \
-    } while (0)
+    auto decode = [&](int k, int& f, int& clip, int& y0, int& x0) __attribute__((always_inline)) {
+        int ch;
+        cs.tile(k, gT, ch, f);
+        chain_tile(ch, per_item, tiles_x, 1, 0, clip, y0, x0);
+    };
 #define SFC_HALF(u_) ((((u_) >> 1) ^ (u_)) & 1)
 
     const float bias_r = tid < 64 ? p.bias[tid] : 0.f;
@@ -1116,7 +1073,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
 
     // ---- prologue: halo of unit 0 (the first chain's shared half: `base`) and its weights (pack 0 = shared half, channel half 0)
     int c_f, c_clip, c_y0, c_x0, n_f, n_clip, n_y0, n_x0;
-    SFC_TILE(0, c_f, c_clip, c_y0, c_x0);
+    decode(0, c_f, c_clip, c_y0, c_x0);
     n_f = c_f;
     n_clip = c_clip;
     n_y0 = c_y0;
@@ -1213,7 +1170,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
                         if (w_replace) SFC_DMA_WX(nx_pk, nx_half, 0);
                         if constexpr (PAR == 0) {                   // decode the next tile (past the end: this one again - a harmless re-read)
                             const int kn = min(kt + 1, nt_tiles - 1);
-                            SFC_TILE(kn, n_f, n_clip, n_y0, n_x0);
+                            decode(kn, n_f, n_clip, n_y0, n_x0);
                         }
                     }
                     if constexpr (kx == 2) {
@@ -1274,7 +1231,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
                 // (+ bias) as the initial C of the frames that follow, and is cleared behind the chain's last frame (the next
                 // tile is a shared half again: initial C = 0).  Branch-free (selects on wave-uniform conditions): arms that
                 // define 32-register vectors cost the allocator live copies of both.
-                const bool head = c_f == 0, last = c_f == ((SPLIT && kt >= nfull_tiles) ? sp_f1 : T);   // (the last frame of a whole chain / of this workgroup's part)
+                const bool head = c_f == 0, last = c_f == ((SPLIT && kt >= cs.nfull_tiles) ? cs.sp_f1 : T);   // (the last frame of a whole chain / of this workgroup's part)
                 // (the lane's two bias values: read from LDS HERE, once per tile and in front of the loop - as 32 reads inside it, each with its own wait, they
                 // cost the kernel ~1 500 cycles per unit)
                 const float bias_q[2] = {bl[ech], bl[ech + 16]};
@@ -1322,7 +1279,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
 #undef SFC_DMA_HALO
 #undef SFC_DMA_W
 #undef SFC_HALF
-#undef SFC_TILE
 #undef SFC_BARRIER
 }
 
@@ -1335,13 +1291,8 @@ hipError_t launch_conv3x3_sf_chain(const ConvSplitParams& p, hipStream_t s) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;
-    if (p.split_s) {                                                       // (the geometry conv3x3_c1c10_kernel was launched with: conv_split16.hip checks it in full)
-        const long long nch = (long long)((p.W + SF_TW - 1) / SF_TW) * ((p.H + SF_TH - 1) / SF_TH) * (p.items / p.add_div);
-        if (p.split_s < 2 || p.split_q < 1 || p.n_full % grid || p.n_full >= nch || (nch - p.n_full) * p.split_s > grid ||
-            (long long)(p.split_s - 1) * p.split_q >= p.add_div || (long long)p.split_s * p.split_q < p.add_div)
-            return hipErrorInvalidValue;
-    }
+    const int grid = persistent_grid(ncu);
+    if (p.split_s && !split_geometry_ok(p.H, p.W, p.items, p.add_div, p.n_full, p.split_s, p.split_q, grid)) return hipErrorInvalidValue;
     if ((p.wpack_m16 == nullptr) != (p.wpack2_m16 == nullptr) || (p.wpack_m16 && p.out2)) return hipErrorInvalidValue;
     if (p.wpack_m16 && !p.split_s) {                                       // the 16x16x32 form, on its own packs (split chains: the 32x32x16 kernel - its bookkeeping does not fit the registers)
         ConvSplitParams q = p;
@@ -1382,7 +1333,7 @@ hipError_t launch_conv3x3_sf(const ConvSplitParams& p, hipStream_t s) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;          // whole XCDs; surplus workgroups exit at once
+    const int grid = persistent_grid(ncu);                // surplus workgroups exit at once
     static std::atomic<int> attr_dev[64][2];                               // the attribute is per device
     const int mode = p.addend ? 1 : 0;
     const void* fn = mode ? reinterpret_cast<const void*>(conv3x3_sf_kernel<1>) : reinterpret_cast<const void*>(conv3x3_sf_kernel<0>);

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "chain_order.h"
+
 // schedule switches of the two launches of a progressive-fusion block (conv3x3_c1c10_kernel, conv3x3_sf_chain_kernel)
 #ifndef PFNL_S16_SPREAD
 #define PFNL_S16_SPREAD 1    // 1: the next sub-step's operand reads between the MFMAs of the current one instead of in front of them
@@ -60,11 +62,6 @@ hipError_t launch_conv3x3_c1c10(const ConvSplitParams& p, hipStream_t s);
 // split chains: base[clip][tile of chain n_full + j] = split format of act(sum over the parts r of partial[j * split_s + r]), j < nchains - n_full
 // (p: H, W, items = clips * T, add_div = T, act, n_full, split_s, partial, out2 = base)
 hipError_t launch_c10_finalize(const ConvSplitParams& p, hipStream_t s);
-// the grid the persistent split-f16 launches use on the current device (whole XCDs): what n_full must be a multiple of
-int conv_split16_grid();
-// the split-chain geometry every split launch checks (8 x 32 tiles, T = add_div frames per chain; split_s >= 2): n_full a multiple of
-// `grid` below the chain count, split_s parts of <= split_q frames that are all non-empty and together the T frames, one part per workgroup
-bool split_geometry_ok(int H, int W, int items, int T, int n_full, int split_s, int split_q, int grid);
 size_t conv1x1_c10_pack_halfs(int T);
 void conv1x1_c10_pack_weights(const float* hwio, int T, uint16_t* dst);
 

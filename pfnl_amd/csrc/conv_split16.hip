@@ -58,7 +58,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CS_THREADS = 512;
-constexpr int CS_TH = 8, CS_TW = 32;
+constexpr int CS_TH = CHAIN_TH, CS_TW = CHAIN_TW;
 constexpr int CS_IH = CS_TH + 2, CS_IW = CS_TW + 2;
 constexpr int CS_TILE_BYTES = CS_IH * CS_IW * 128;                  // 43 520 per buffer
 constexpr int CS_W_BYTES = 3 * 2 * 3 * 2 * 2 * 1024;                // 73 728: [kx][ks][ky][m][hi/lo][lane] x 16 B, one half
@@ -169,50 +169,28 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
     const int tiles_x = (W + CS_TW - 1) / CS_TW, tiles_y = (H + CS_TH - 1) / CS_TH;
     const int per_item = tiles_x * tiles_y;
     const int item_bytes = H * W * 256;
-    // Work order (as conv_bf16.hip): chains of the gT frames of a clip at one spatial tile (the addend tile is then an L2
-    // hit for all but the first), dealt out XCD by XCD so that neighbouring tiles share their halo rows in one L2.
+    // Work order (chain_order.h): chains of the gT frames of a clip at one spatial tile (the addend tile is then an L2 hit for all but the
+    // first), dealt out XCD by XCD.  SPLIT: the workgroup's part of a cut chain follows its whole chains
     const int gT = (FUSE || ACCUM) ? p.add_div : 1;
     const int nchains = per_item * (p.items / gT);
-    const int xcd = blockIdx.x & 7, xj = blockIdx.x >> 3, cpx = gridDim.x >> 3;
-    const int n_full = SPLIT ? p.n_full : nchains;
-    const int per_xcd = (n_full + 7) >> 3;
-    const int cbeg = xcd * per_xcd;
-    const int ccnt = min(per_xcd, n_full - cbeg);
-    if (!SPLIT && xj >= ccnt) return;
-    const int nfull_tiles = ((!SPLIT || xj < ccnt) ? (ccnt - xj + cpx - 1) / cpx : 0) * gT;   // tiles of this workgroup's whole chains
-    [[maybe_unused]] const int slot = xcd * cpx + xj;
-    const bool has_part = SPLIT && slot < (nchains - n_full) * p.split_s;
-    const int sp_chain = has_part ? n_full + slot / p.split_s : 0;
-    const int sp_f0 = has_part ? (slot % p.split_s) * p.split_q : 0, sp_f1 = has_part ? min(gT, sp_f0 + p.split_q) : 0;
-    const int nt = SPLIT ? nfull_tiles + (sp_f1 - sp_f0) : nfull_tiles;   // tiles of this workgroup
+    ChainShare<SPLIT> cs(blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3, nchains, p.n_full);
+    if (cs.idle()) return;
+    cs.deal(gT, p.split_s, p.split_q);
+    const int nt = cs.nt;                                           // tiles of this workgroup
     if (SPLIT && nt <= 0) return;
     [[maybe_unused]] const int nu = 2 * nt;                         // units: (tile, channel half); nu >= 2
     // tile k -> (item, y0, x0)
-#define CS_TILE(k_, item_, y0_, x0_)                                                             \
-    do {                                                                                         \
-        int ci_, f_, ch_;                                                                        \
-        if (!SPLIT || (k_) < nfull_tiles) {                                                      \
-            ci_ = (k_) / gT;                                                                     \
-            f_ = (k_) - ci_ * gT;                                                                \
-            ch_ = cbeg + xj + ci_ * cpx;                                                         \
-        } else {                                                                                 \
-            f_ = sp_f0 + ((k_) - nfull_tiles);                                                   \
-            ch_ = sp_chain;                                                                      \
-        }                                                                                        \
-        const int cl_ = ch_ / per_item;                                                          \
-        const int sp_ = ch_ - cl_ * per_item;                                                    \
-        item_ = cl_ * gT + f_;                                                                   \
-        const int ty_ = sp_ / tiles_x;                                                           \
-        y0_ = ty_ * CS_TH;                                                                       \
-        x0_ = (sp_ - ty_ * tiles_x) * CS_TW;                                                     \
-    } while (0)
-    // unit u: tile u >> 1; the channel half walks 0,1 | 1,0 | 0,1 ... so that consecutive units of different tiles share it
+    auto decode = [&](int k, int& item, int& y0, int& x0) __attribute__((always_inline)) {
+        int ch, f;
+        cs.tile(k, gT, ch, f);
+        chain_tile(ch, per_item, tiles_x, gT, f, item, y0, x0);
+    };
 #define CS_HALF(u_) ((((u_) >> 1) ^ (u_)) & 1)
 
     // weights of half 0 + bias: requested here, written to LDS in the prologue below - after the first halo has been requested
     // too, so that the two latencies of a launch's start overlap (a launch is only 20-100 us long)
     // (SPLIT: a workgroup without whole chains starts with its part, at frame sp_f0 - ACCUM's pack index 2 f + half)
-    const int f_first = (SPLIT && nfull_tiles == 0) ? sp_f0 : 0;
+    const int f_first = (SPLIT && cs.nfull_tiles == 0) ? cs.sp_f0 : 0;
     const u32x4* const w0src = reinterpret_cast<const u32x4*>(p.wpack) + (size_t)(2 * f_first) * (CS_W_BYTES / 16);
     u32x4 w0reg[CS_W_BYTES / 16 / CS_THREADS];
 #pragma unroll
@@ -251,7 +229,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
     // descriptor of unit u_'s halo: resource of its item, byte offset of the halo origin (+ the channel half), interior flag
 #define CS_REQ_SETUP(u_, rs_, org_, interior_, y0_, x0_)                                         \
     int item_q_, y0_, x0_;                                                                       \
-    CS_TILE((u_) >> 1, item_q_, y0_, x0_);                                                       \
+    decode((u_) >> 1, item_q_, y0_, x0_);                                                        \
     const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(                        \
         const_cast<float*>(p.in) + (size_t)item_q_ * H * W * 64, 0, item_bytes, 0x00020000);     \
     const int org_ = ((y0_ - 1) * W + x0_ - 1) * 256 + CS_HALF(u_) * 128;                        \
@@ -465,7 +443,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
     // coordinates of the current tile and of the next one: ONE decode (three scalar divisions) per tile, done in unit A for the
     // tile after this one, where its latency is nobody's critical path
     int c_item, c_y0, c_x0, n_item, n_y0, n_x0;
-    CS_TILE(0, c_item, c_y0, c_x0);
+    decode(0, c_item, c_y0, c_x0);
     n_item = c_item;
     n_y0 = c_y0;
     n_x0 = c_x0;
@@ -502,8 +480,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
             [[maybe_unused]] int w_next = 0;
             if constexpr (ACCUM) {
                 // (SPLIT: behind this workgroup's last whole chain comes its part, which starts at frame sp_f0)
-                const int f_end = (SPLIT && kt >= nfull_tiles) ? sp_f1 : gT;
-                const int fn = fch + 1 == f_end ? ((SPLIT && kt + 1 == nfull_tiles) ? sp_f0 : 0) : fch + 1;
+                const int fn = fch + 1 == ((SPLIT && kt >= cs.nfull_tiles) ? cs.sp_f1 : gT) ? ((SPLIT && kt + 1 == cs.nfull_tiles) ? cs.sp_f0 : 0) : fch + 1;
                 w_next = PAR == 0 ? 2 * fch + (half_a ^ 1) : 2 * fn + (half_a ^ 1);   // unit B's half is also the next tile's first half
             }
             if constexpr (PAR == 0 && !ACCUM) w_request(half_a ^ 1, 0);
@@ -575,7 +552,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                         }
                         if constexpr (PAR == 0) {                   // decode the next tile (past the end: this one again - a harmless re-read)
                             const int kn = min(kt + 1, nt - 1);
-                            CS_TILE(kn, n_item, n_y0, n_x0);
+                            decode(kn, n_item, n_y0, n_x0);
                         }
                     }
                     if constexpr (g == 4) {
@@ -686,7 +663,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
 #undef CS_PX
 #undef CS_WT
             if constexpr (PAR == 1 && ACCUM) {                      // a tile is one frame of the chain: only the last one ends a sum
-                const bool last = fch + 1 == ((SPLIT && kt >= nfull_tiles) ? sp_f1 : gT);   // (wave-uniform; arithmetic only inside the branch)
+                const bool last = fch + 1 == ((SPLIT && kt >= cs.nfull_tiles) ? cs.sp_f1 : gT); // (wave-uniform; arithmetic only inside the branch)
                 if (last) {
 #pragma unroll
                     for (int n = 0; n < 2; ++n) {
@@ -702,7 +679,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                     eitemp = c_item / gT;                           // output item = the clip
                 }
                 pending = last;
-                fch = last ? ((SPLIT && kt + 1 == nfull_tiles) ? sp_f0 : 0) : fch + 1;
+                fch = last ? ((SPLIT && kt + 1 == cs.nfull_tiles) ? cs.sp_f0 : 0) : fch + 1;
                 c_item = n_item;
                 c_y0 = n_y0;
                 c_x0 = n_x0;
@@ -730,8 +707,8 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
 
     // ---- the last tile: both passes, any buffer is free now ------------------------------------------
     if constexpr (SPLIT) {
-        if (has_part) {                                             // (wave-uniform) the part's sum: raw, a dense [row][column][64] fp32 tile in its slot
-            float* const pt = p.partial + (size_t)slot * (CS_TH * CS_TW * 64);
+        if (cs.has_part) {                                          // (wave-uniform) the part's sum: raw, a dense [row][column][64] fp32 tile in its slot
+            float* const pt = p.partial + (size_t)cs.slot * (CS_TH * CS_TW * 64);
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
                 unsigned char* const scratch = cs_smem + n * CS_TILE_BYTES;
@@ -767,7 +744,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
 #undef CS_REQ_SETUP
 #undef CS_REQUEST_ALL
 #undef CS_HALF
-#undef CS_TILE
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -845,43 +821,18 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
     const int item_bytes = H * W * 256;
     const int gT = p.add_div;                                       // frames per clip = tiles per chain
     const int nchains = per_item * (p.items / gT);
-    const int xcd = blockIdx.x & 7, xj = blockIdx.x >> 3, cpx = gridDim.x >> 3;
-    // SPLIT CHAINS (round 6; p.split_s > 0): the first p.n_full chains - a whole number of rounds of the grid - are dealt out as whole
-    // chains, as ever; every chain behind them is cut by FRAMES into p.split_s parts of <= p.split_q frames, one part per workgroup (slot
-    // = xcd * cpx + xj -> chain n_full + slot / s, part slot % s).  A launch of 1.25 rounds of chains then takes 1 chain + 2 tiles
-    // instead of 2 chains.  A part cannot finish conv10_i - it only sees its own frames: it leaves its partial sum (part 0 starts from
-    // the bias, the others from 0) as raw fp32 in p.partial[slot], and c10_finalize_kernel adds the parts up in fixed order.
-    const int n_full = SPLIT ? p.n_full : nchains;
-    const int per_xcd = (n_full + 7) >> 3;
-    const int cbeg = xcd * per_xcd;
-    const int ccnt = min(per_xcd, n_full - cbeg);
-    if (!SPLIT && xj >= ccnt) return;
-    const int nfull_tiles = ((!SPLIT || xj < ccnt) ? (ccnt - xj + cpx - 1) / cpx : 0) * gT;   // tiles of this workgroup's whole chains
-    [[maybe_unused]] const int slot = xcd * cpx + xj;
-    const bool has_part = SPLIT && slot < (nchains - n_full) * p.split_s;
-    const int sp_chain = has_part ? n_full + slot / p.split_s : 0;
-    const int sp_r = has_part ? slot % p.split_s : 0;
-    const int sp_f0 = has_part ? sp_r * p.split_q : 0, sp_f1 = has_part ? min(gT, sp_f0 + p.split_q) : 0;   // frames [sp_f0, sp_f1) of chain sp_chain
-    const int nt = SPLIT ? nfull_tiles + (sp_f1 - sp_f0) : nfull_tiles;   // tiles of this workgroup
+    // SPLIT CHAINS (round 6; p.split_s > 0; chain_order.h): a part cannot finish conv10_i - it only sees its own frames: it leaves its partial
+    // sum (part 0 starts from the bias, the others from 0) as raw fp32 in p.partial[slot], and c10_finalize_kernel adds the parts up in fixed order.
+    ChainShare<SPLIT> cs(blockIdx.x & 7, blockIdx.x >> 3, gridDim.x >> 3, nchains, p.n_full);
+    if (cs.idle()) return;
+    cs.deal(gT, p.split_s, p.split_q);
+    const int nt = cs.nt;                                           // tiles of this workgroup
     if (SPLIT && nt <= 0) return;
-#define K1_TILE(k_, item_, y0_, x0_, fr_)                                                        \
-    do {                                                                                         \
-        int ch_;                                                                                 \
-        if (!SPLIT || (k_) < nfull_tiles) {                                                      \
-            const int ci_ = (k_) / gT;                                                           \
-            fr_ = (k_) - ci_ * gT;                                                               \
-            ch_ = cbeg + xj + ci_ * cpx;                                                         \
-        } else {                                                                                 \
-            fr_ = sp_f0 + ((k_) - nfull_tiles);                                                  \
-            ch_ = sp_chain;                                                                      \
-        }                                                                                        \
-        const int cl_ = ch_ / per_item;                                                          \
-        const int sp_ = ch_ - cl_ * per_item;                                                    \
-        item_ = cl_ * gT + fr_;                                                                  \
-        const int ty_ = sp_ / tiles_x;                                                           \
-        y0_ = ty_ * CS_TH;                                                                       \
-        x0_ = (sp_ - ty_ * tiles_x) * CS_TW;                                                     \
-    } while (0)
+    auto decode = [&](int k, int& item, int& y0, int& x0, int& fr) __attribute__((always_inline)) {
+        int ch;
+        cs.tile(k, gT, ch, fr);
+        chain_tile(ch, per_item, tiles_x, gT, fr, item, y0, x0);
+    };
 
     u32x4 w0reg[CS_W_BYTES / 16 / CS_THREADS];
 #pragma unroll
@@ -1086,7 +1037,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
 
     // ---- prologue: halo of unit 0 -> buffer 0; weights of half 0, both biases -> LDS ----------------------------------------
     int c_item, c_y0, c_x0, n_item, n_y0, n_x0, fch, n_f;           // fch / n_f: frame of its chain the current / the next tile is
-    K1_TILE(0, c_item, c_y0, c_x0, fch);
+    decode(0, c_item, c_y0, c_x0, fch);
     n_item = c_item;
     n_y0 = c_y0;
     n_x0 = c_x0;
@@ -1114,7 +1065,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         }
     }
     __syncthreads();
-    base_init(SPLIT && nfull_tiles == 0 && sp_r > 0);
+    base_init(cs.head_pos(0) > 0);
 
     for (int kt = 0; kt < nt; ++kt) {
         const int half_a = kt & 1;
@@ -1188,7 +1139,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                     }
                     if constexpr (g == 3 && PAR == 0) {
                         const int kn = min(kt + 1, nt - 1);         // decode the next tile (past the end: this one again - a harmless re-read)
-                        K1_TILE(kn, n_item, n_y0, n_x0, n_f);
+                        decode(kn, n_item, n_y0, n_x0, n_f);
                     }
                     if constexpr (g == 4) {
                         K1_BARRIER();                               // b1: column tap 1 consumed
@@ -1331,12 +1282,12 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                 hy0 = c_y0;
                 hitem = c_item;
                 hpend = true;
-                const bool is_part = SPLIT && kt >= nfull_tiles;    // (wave-uniform) a tile of this workgroup's part of a split chain
-                const bool last = fch + 1 == (is_part ? sp_f1 : gT);
+                const bool is_part = cs.in_part(kt);                // (wave-uniform) a tile of this workgroup's part of a split chain
+                const bool last = fch + 1 == cs.end_pos(kt, gT);
                 if (last && is_part) {                              // a PART's sum leaves as raw fp32 (no activation: c10_finalize_kernel adds the parts up)
 #pragma unroll
                     for (int j = 0; j < 8; ++j) held_store(j, p.out);
-                    float* const pt = p.partial + (size_t)slot * (CS_TH * CS_TW * 64) + (size_t)(2 * rp * CS_TW + (lane & 31)) * 64 + ech;
+                    float* const pt = p.partial + (size_t)cs.slot * (CS_TH * CS_TW * 64) + (size_t)(2 * rp * CS_TW + (lane & 31)) * 64 + ech;
 #pragma unroll
                     for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -1366,7 +1317,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
 #pragma unroll
                     for (int j = 0; j < 8; ++j) held_store(j, p.out2);
                     hpend = false;
-                    base_init(SPLIT && kt + 1 == nfull_tiles && sp_r > 0);   // (the next item is a part > 0 of a split chain: it starts from 0)
+                    base_init(cs.head_pos(kt + 1) > 0);             // (the next item is a part > 0 of a split chain: it starts from 0)
                 }
                 if constexpr (SPLIT) fch = n_f;
                 else fch = last ? 0 : fch + 1;
@@ -1384,7 +1335,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) held_store(j, p.out);               // the last tile's lines (nothing held: dropped)
-#undef K1_TILE
 #undef K1_DMA_HALO
 #undef K1_REQUEST_ALL
 #undef K1_COMMIT1
@@ -1392,19 +1342,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
 #undef K1_DMA_W
 }
 
-int conv_split16_grid() {
-    const int ncu = device_cu_count();
-    return ncu >= 8 ? ncu / 8 * 8 : 8;                              // whole XCDs; surplus workgroups exit at once
-}
-
-// the geometry of a split-chain launch must be the one the kernels assume: whole rounds of the grid in front, one part per workgroup behind
-bool split_geometry_ok(int H, int W, int items, int T, int n_full, int split_s, int split_q, int grid) {
-    if (T < 1 || grid < 1) return false;
-    const long long nchains = (long long)((W + CS_TW - 1) / CS_TW) * ((H + CS_TH - 1) / CS_TH) * (items / T);
-    if (split_s < 2 || split_q < 1 || n_full < 0 || n_full % grid || n_full >= nchains) return false;
-    if ((long long)split_s * split_q < T || (long long)(split_s - 1) * split_q >= T) return false;   // every part non-empty, together the T frames
-    return (nchains - n_full) * split_s <= grid;
-}
 static bool split_params_ok(const ConvSplitParams& p, int grid) {
     return p.split_s == 0 || split_geometry_ok(p.H, p.W, p.items, p.add_div, p.n_full, p.split_s, p.split_q, grid);
 }
@@ -1416,8 +1353,8 @@ __global__ __launch_bounds__(256) void c10_finalize_kernel(ConvSplitParams p) {
     const int tiles_x = (W + CS_TW - 1) / CS_TW, tiles_y = (H + CS_TH - 1) / CS_TH;
     const int per_item = tiles_x * tiles_y;
     const int j = blockIdx.x >> 3, ch = p.n_full + j;                // 8 workgroups per split chain: one tile row (32 pixels x 16 groups = 512 ids) each
-    const int clip = ch / per_item, sp = ch - clip * per_item;
-    const int ty = sp / tiles_x, y0 = ty * CS_TH, x0 = (sp - ty * tiles_x) * CS_TW;
+    int clip, y0, x0;
+    chain_tile(ch, per_item, tiles_x, 1, 0, clip, y0, x0);
     const float slope = p.act ? 0.2f : 1.0f;
     const int S = p.split_s;                                        // 2 .. 7
 #pragma unroll
@@ -1453,10 +1390,8 @@ __global__ __launch_bounds__(256) void c10_finalize_kernel(ConvSplitParams p) {
 
 hipError_t launch_c10_finalize(const ConvSplitParams& p, hipStream_t s) {
     if (!p.partial || (!p.out2 == !p.out) || (p.out && !p.bias) || p.items < 1 || p.H < 1 || p.W < 1 || p.add_div < 1 || p.items % p.add_div) return hipErrorInvalidValue;
-    const int grid = conv_split16_grid();
-    if (p.split_s < 2 || !split_params_ok(p, grid)) return hipErrorInvalidValue;
+    if (!split_geometry_ok(p.H, p.W, p.items, p.add_div, p.n_full, p.split_s, p.split_q, persistent_grid(device_cu_count()))) return hipErrorInvalidValue;
     const long long nchains = (long long)((p.W + CS_TW - 1) / CS_TW) * ((p.H + CS_TH - 1) / CS_TH) * (p.items / p.add_div);
-    if (p.split_s > 7) return hipErrorInvalidValue;
     hipLaunchKernelGGL(c10_finalize_kernel, dim3((unsigned)(nchains - p.n_full) * 8), dim3(256), 0, s, p);
     return hipGetLastError();
 }
@@ -1469,7 +1404,7 @@ hipError_t launch_conv3x3_c1c10(const ConvSplitParams& p, hipStream_t s) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;
+    const int grid = persistent_grid(ncu);
     if (!split_params_ok(p, grid) || (p.split_s && !p.partial)) return hipErrorInvalidValue;
     static std::atomic<int> attr_dev[64][4];
     const int isf = p.in_sf ? 1 : 0;                                // `in` is the split-format copy of inp0 (conv3x3_sf_chain_kernel<true, .>)
@@ -1498,7 +1433,7 @@ hipError_t launch_conv3x3_split16(const ConvSplitParams& p, hipStream_t s) {
     if ((long long)p.H * p.W * 256 >= 0x7fffffffLL) return hipErrorInvalidValue;
     const int ncu = device_cu_count();
     if (!ncu) return hipErrorUnknown;
-    const int grid = ncu >= 8 ? ncu / 8 * 8 : 8;                    // whole XCDs; surplus workgroups exit at once
+    const int grid = persistent_grid(ncu);
     static std::atomic<int> attr_dev[64][4];                               // the attribute is per device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;

@@ -428,7 +428,7 @@ def test_round4_schedules_are_deterministic_and_bit_equal_across_generations():
 # test_bf16_3x3_kernel_generations does not select them: they call conv_bf16_v3.hip directly, PFNL_BF16_V3 changes nothing here.)
 
 def _grid():
-    """The grid of the persistent launches on this device (conv_split16_grid: the CU count rounded down to whole XCDs, at least 8)."""
+    """The grid of the persistent launches on this device (persistent_grid: the CU count rounded down to whole XCDs, at least 8)."""
     return max(8, torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8)
 
 
@@ -627,7 +627,7 @@ def test_bf16_v3_split_chains_op(name, mfma):
 
 
 def test_bf16_v3_split_hooks_refuse_bad_geometries():
-    """The bf16 v4 hooks refuse split geometries outside the rule of b3_split_ok on the host, before any launch, and leave out untouched."""
+    """The bf16 v4 hooks refuse split geometries outside the rule of split_geometry_ok on the host, before any launch, and leave out untouched."""
     from pfnl_amd import _capi
     G = _grid()
     T, H, W = 7, 8, 32

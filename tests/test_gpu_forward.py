@@ -21,7 +21,7 @@ ABS_TOL = 5e-5              # direct element-wise bound on [0,1]-scale outputs (
 
 
 def _split_grid():
-    """The grid of the persistent launches on this device (conv_split16_grid: the CU count rounded down to whole XCDs, at least 8)."""
+    """The grid of the persistent launches on this device (persistent_grid: the CU count rounded down to whole XCDs, at least 8)."""
     return max(8, torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8)
 
 

@@ -785,7 +785,7 @@ def test_round4_kernels_random_geometries_short():
 # ---- C-ABI v4 hooks: the 16x16x32 chain kernel and split chains, op by op ------------------------------------------------------------------
 
 def _grid():
-    """The grid of the persistent split-f16 launches on this device (conv_split16_grid: the CU count rounded down to whole XCDs, at least 8)."""
+    """The grid of the persistent split-f16 launches on this device (persistent_grid: the CU count rounded down to whole XCDs, at least 8)."""
     return max(8, torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8)
 
 
