@@ -191,7 +191,7 @@ int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes);
 /* THE LAUNCH PLAN of the progressive-fusion trunk (reference model/pfnl.py:65-71) for a [B,T,H,W,3] forward under the handle's current
  * options, as text: "<structure> launches_per_block=<n> c1x1=<launches of class conv1x1 among them> precision=<..> conv3x3=<..> conv1x1=<..>
  * c10_fused=<0|1> chain=<0|1> sf0=<0|1> strict=<0|1> tiles=<8x32-pixel tiles per per-frame launch> chains=<(clip, tile) chains>
- * whole_chains=<n> split_parts=<s> part_frames=<q> nl=<split16 | f16 | f32 | general_f32: the non-local block's kernel family> nl_pack_fused=<0|1> mfma=<16|32: the MFMA shape of the chained 3x3 launches - 16 = v_mfma_f32_16x16x32_*: the bf16 trunk's, and the fp32 chain launch of conv2_i when every CU has a chain>".  Structures: "small2" / "small3" (conv_small.hip,
+ * whole_chains=<n> split_parts=<s> part_frames=<q> nl=<split16 | f16 | f32 | general_f32: the non-local block's kernel family> nl_pack_fused=<0|1> mfma=<16|32: the MFMA shape of the chained 3x3 launches - 16 = v_mfma_f32_16x16x32_*: the bf16 trunk's, and the fp32 chain launch of conv2_i when every CU has a chain> merge1=<small | bf16 | split16 | split16_cut | winograd | direct: convmerge1's launch; split16_cut adds c10_finalize_kernel>".  Structures: "small2" / "small3" (conv_small.hip,
  * below ~0.78 tiles per CU: 200 on a 256-CU device), "mid4" (four per-tile launches, below ~0.53 chains per CU: 136), "chain2" (conv1_i +
  * conv10_i, then the whole of conv2_i), "chain2_split" (the same with the chains of a last, partial round cut by frames: option
  * split16_splitchains) and "chain2_sf0" (the same with a split-format copy of every block's output so that the next block's

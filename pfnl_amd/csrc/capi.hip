@@ -157,16 +157,30 @@ struct HostPool {
 // here on the split-f16 kernels' per-tile launches are faster (tools/precision_ladder.py: 210 - 224 tiles 1.99 - 2.14 -> 1.85 - 1.90 ms;
 // 168 tiles 1.08 against 1.88).  256 (a tile per CU) until round 5.
 // Both work-order thresholds were measured on the 256-CU part and are a fraction of the CUs a launch can occupy: they scale with
-// device_cu_count() (a CPX partition or a smaller device keeps the same tiles-per-CU crossover).
+// the CU count of the handle's device (a CPX partition or a smaller device keeps the same tiles-per-CU crossover).
 static constexpr int kSmallTiles256 = 200;                  // tiles of 8x32 pixels per 3x3 launch below which the small-shape trunk runs (0.78 per CU)
 static constexpr int kMidChains256 = 136;                   // (clip, tile) chains below which a block runs as four per-tile launches (0.53 per CU)
-static int scaled_by_cus(int v256) {
-    const int ncu = pfnl::device_cu_count();
+static int scaled_by_cus(int v256, int ncu) {
     return ncu > 0 && ncu != 256 ? std::max(1, (int)((long long)v256 * ncu / 256)) : v256;
 }
 
+// the weight packs of one PF block: offsets into the three device blobs, filled by pfnl_finalize_weights
+struct BlockPacks {
+    // fp32 blob `wdev` (floats): the direct kernel's packs, biases, conv1x1_pack_weights (c10_s), the Winograd packs (_u)
+    size_t c1_w = 0, c1_b = 0, c10_w = 0, c10_b = 0, c10_s = 0, c2a_w = 0, c2b_w = 0, c2_b = 0;
+    size_t c1_u = 0, c2a_u = 0, c2b_u = 0;
+    // bf16 blob `wdev16` (16-bit elements): conv3x3_bf16_pack_weights, conv1x1_bf16_pack_weights; _m16: conv3x3_bf16_pack_weights16
+    size_t bf_c1 = 0, bf_c10 = 0, bf_c2a = 0, bf_c2b = 0, bf_c1_m16 = 0, bf_c2b_m16 = 0;
+    // split-f16 blob `wdev16s` (16-bit elements): the 3x3 / 1x1 split-f16 packs; c10f: conv10_i as conv3x3_c1c10_kernel takes it; _sf: with the
+    // identity row map conv3x3_sf_kernel takes (conv_sf.hip); _m16: the order of the v_mfma_f32_16x16x32_f16 chain kernel (conv3x3_split16_pack_weights16)
+    size_t s_c1 = 0, s_c2a = 0, s_c2b = 0, s_c10 = 0, s_c10f = 0, s_c2a_sf = 0, s_c2b_sf = 0, s_c2a_m16 = 0, s_c2b_m16 = 0;
+    // ... and the small-shape packs (conv_small.hip) in the same blob
+    size_t sm_c1 = 0, sm_c10 = 0, sm_c2 = 0;
+};
+
 struct pfnl_handle {
     pfnl_config cfg;
+    int ncu = 0;                                              // CUs of the device (cfg.device_id): the launch plan's thresholds and grid
     hipStream_t stream = nullptr;
     std::map<std::string, std::vector<int64_t>> expected;   // tf name -> shape
     std::map<std::string, HostTensor> host;                  // tensors received so far
@@ -192,22 +206,16 @@ struct pfnl_handle {
     int conv1x1_algo = 2;                                     // conv10: 2 streaming kernel on the f16 pipe, split operands (default), 1 streaming f32-MFMA kernel (conv1x1.hip), 0 LDS-tiled implicit GEMM
     bool bf16_fuse10 = true;                                  // bf16 trunk: conv10_i inside the conv1_i launch (option bf16_conv10=fused|separate)
     bool bf16_m16 = true;                                     // bf16 trunk: the two chained 3x3 launches on v_mfma_f32_16x16x32_bf16 (option bf16_mfma=16|32)
-    std::vector<size_t> off16_c1_m16, off16_c2b_m16;          // conv3x3_bf16_pack_weights16 of conv1_i / conv2_i's per-frame half
     bool bf16 = false;                                        // option precision=bf16: progressive-fusion trunk in bf16 (conv_bf16.hip); NL, conv0 maths, merge, tail stay fp32
     DevBuf wdev16;                                            // bf16 packs (offsets in 16-bit elements)
-    std::vector<size_t> off16_c1, off16_c10, off16_c2a, off16_c2b;
     size_t off16_m1 = 0;                                      // convmerge1: T consecutive packs (cout 48 zero-padded to 64)
     size_t off16s_m1 = 0;                                     // convmerge1, split-f16 packs: T consecutive (frame, both halves) packs
     int m1_algo = 0;                                          // convmerge1 with conv3x3=split16: 0 auto (= 1), 1 the split-f16 kernel's accumulating mode, 2 Winograd
     int conv_algo = 5;                                        // conv3x3: 5 auto (4 for large shapes, 3 for small), 0 direct, 1 winograd (4 waves / tile), 3 winograd_ws (persistent, wave-specialised), 4 split16 (f16 MFMA, split fp32 operands)
     int nl_algo = 2;                                          // non-local block of the fp32 path: 0 f32 MFMA (nonlocal.hip), 1 split-f16 (nonlocal_f16.hip), 2 auto (1 from N = 1024 keys)
     DevBuf wdev16s;                                           // split-f16 packs of the 3x3 kernels (offsets in 16-bit elements)
-    std::vector<size_t> off16s_c1, off16s_c2a, off16s_c2b, off16s_c10, off16s_c10f;   // (c10f: conv10_i as conv3x3_c1c10_kernel takes it)
-    std::vector<size_t> off16s_c2a_sf, off16s_c2b_sf;         // ... with the identity row map conv3x3_sf_kernel takes (conv_sf.hip)
-    std::vector<size_t> off16s_c2a_m16, off16s_c2b_m16;       // ... in the order of the v_mfma_f32_16x16x32_f16 chain kernel (conv3x3_split16_pack_weights16)
     bool s16_m16 = true;                                      // option split16_mfma=16|32: the chain launch of conv2_i on v_mfma_f32_16x16x32_f16
-    std::vector<size_t> off16m_c1, off16m_c10, off16m_c2;     // small-shape packs (conv_small.hip), in the same blob
-    size_t off16m_m1 = 0;
+    size_t off16m_m1 = 0;                                     // convmerge1's small-shape pack (conv_small.hip), in the same blob
     // The f16-pipe kernels of the fp32 path have a DOMAIN (operands inside binary16's range; the non-local kernel: inputs x 2^7).
     // Beyond it an operand becomes inf and the result non-finite - the tail kernel, which every output value passes through, ORs
     // that into `rflag` (sticky device word).  Host-pointer calls read it before they return and, when it is set, redo the call on
@@ -245,8 +253,7 @@ struct pfnl_handle {
     // device weights (offsets in floats into `wdev`)
     DevBuf wdev;
     size_t off_conv0_w = 0, off_conv0_b = 0;
-    std::vector<size_t> off_c1_w, off_c1_b, off_c10_w, off_c10_b, off_c10_s, off_c2a_w, off_c2b_w, off_c2_b;
-    std::vector<size_t> off_c1_u, off_c2a_u, off_c2b_u;       // Winograd-packed variants
+    std::vector<BlockPacks> blocks;                           // per PF block, offsets into all three blobs
     std::vector<size_t> off_m1_u;                             // convmerge1 per frame, Winograd pack (cout 48 padded to 64)
     size_t off_m1_w = 0, off_m1_b = 0, off_m2_w = 0, off_m2_b = 0, off_nl_w = 0, off_nl_b = 0, off_zero = 0;
 
@@ -402,10 +409,26 @@ size_t numel(const std::vector<int64_t>& s) {
     return n;
 }
 
-// THE LAUNCH PLAN of the progressive-fusion trunk for a shape under the handle's current options: the one place the dispatch rule lives.
+// convmerge1 (model/pfnl.py:73-74): which launch computes it
+enum Merge1Kind {
+    M1_SMALL,         // conv_small.hip: T sources, cout 48 zero-padded to 64
+    M1_BF16,          // the accumulating mode of the bf16 3x3 kernel
+    M1_SPLIT16,       // the accumulating mode of conv3x3_split16_kernel
+    M1_SPLIT16_CUT,   // ... with the trunk's split chains, + c10_finalize_kernel
+    M1_WINOGRAD,      // the accumulating mode of the persistent Winograd kernel
+    M1_DIRECT,        // conv_mfma: 3x3 over the concat of T frames, cout 48
+};
+const char* const kMerge1Names[] = {"small", "bf16", "split16", "split16_cut", "winograd", "direct"};
+
+// THE LAUNCH PLAN of a forward for a shape under the handle's current options: the one place the dispatch rule lives.
 // forward_device runs it, pfnl_workspace_bytes sizes from it, pfnl_plan reports it (bench.py's byte model and the tests read it there).
 struct TrunkPlan {
-    bool bf16 = false, strict = false;
+    bool bf16 = false;
+    bool strict = false;                   // fp32: f32-MFMA kernels only (strict_fp32, a range rerun, weights beyond binary16): trunk, non-local block, conv0
+    int nltype = 1;                        // utils.NonLocalBlock nltype, resolved (option nl_type -1 = auto)
+    int nl_family = 0;                     // the non-local block's kernels: 0 the general form (nltype 0 / 2 or sub-sampling: f32 MFMA), 1 the f16 pipe with
+                                           // exactly split operands (fp32 precision, from 1024 keys), 2 the f16 pipe on the hi parts (precision bf16), 3 f32 MFMA
+    bool nl_fused_pack = false;            // families 1 / 2: one pack launch writes X fp32 + the binary16 K / V^T operands (round 6)
     // bf16 trunk
     bool bmid = false, fuse10 = false;
     // fp32 trunk
@@ -423,35 +446,34 @@ struct TrunkPlan {
     int tiles8x32 = 0, chains = 0;
     int mfma = 32;                         // MFMA shape of the chained 3x3 launches: 16 = v_mfma_f32_16x16x32_* (bf16: conv_bf16_v3.hip M16; fp32: the chain launch
                                            // of conv2_i, conv3x3_sf_chain16_kernel - whole rounds of at least a chain per CU only), 32 = 32x32x16
+    int merge1 = M1_DIRECT;                // convmerge1's launch (Merge1Kind)
+    int merge_stride = 48;                 // floats per pixel of `merge` as convmerge1 writes it
+    // the trunk's buffers that depend on the plan (floats): the small-shape trunk's conv10_i partials [B*T][H][W][64]; the split-format copy of
+    // inp0 [B*T][H][W] x 256 B; split chains' partial sums [slot][8][32][64] (conv10_i's, then convmerge1's)
+    size_t p10_floats = 0, inp0sf_floats = 0, c10part_floats = 0;
     const char* name = "";
 };
 
-TrunkPlan trunk_plan(const pfnl_handle* h, int B, int H, int W) {
-    TrunkPlan pl;
-    const int T = h->cfg.num_frames;
-    pl.bf16 = h->bf16;
-    pl.tiles8x32 = B * T * ((W + 31) / 32) * ((H + 7) / 8);
-    pl.chains = pl.tiles8x32 / T;
-    const int mid_chains = h->sf_mid_chains > 0 ? h->sf_mid_chains : scaled_by_cus(kMidChains256);
-    const int small_tiles = scaled_by_cus(kSmallTiles256);
-    const bool fits32 = (long long)H * W * 256 < 0x7fffffffLL;
-    if (h->bf16) {
-        // MID shapes (as in the fp32 trunk): with fewer (clip, tile) chains than mid_chains the chained launches leave most CUs idle
-        pl.bmid = h->sf_mid && h->bf16_fuse10 && pl.chains < mid_chains;
-        pl.fuse10 = h->bf16_fuse10 && !pl.bmid;
-        pl.launches_per_block = pl.fuse10 ? 3 : 4;
-        pl.c1x1_launches = pl.fuse10 ? 0 : 1;
-        // SPLIT CHAINS of the two chained launches (chain_order.h, split_rule)
-        if (pl.fuse10 && h->split_chains && fits32 && split_rule(pl.chains, T, persistent_grid(device_cu_count()), pl.n_full, pl.split_s, pl.split_q)) {
-            pl.launches_per_block += 1;                                 // c10_finalize_bf16_kernel
-            pl.c1x1_launches = 1;
-        }
-        pl.name = pl.bmid ? "bf16_mid4" : (pl.fuse10 ? (pl.split_s ? "bf16_3_split" : "bf16_3") : "bf16_4");
-        pl.mfma = h->bf16_m16 ? 16 : 32;
-        return pl;
+void plan_bf16_trunk(const pfnl_handle* h, TrunkPlan& pl, int T, int grid, int mid_chains, bool fits32) {
+    // MID shapes (as in the fp32 trunk): with fewer (clip, tile) chains than mid_chains the chained launches leave most CUs idle
+    pl.bmid = h->sf_mid && h->bf16_fuse10 && pl.chains < mid_chains;
+    pl.fuse10 = h->bf16_fuse10 && !pl.bmid;
+    pl.launches_per_block = pl.fuse10 ? 3 : 4;
+    pl.c1x1_launches = pl.fuse10 ? 0 : 1;
+    // SPLIT CHAINS of the two chained launches (chain_order.h, split_rule)
+    if (pl.fuse10 && h->split_chains && fits32 && split_rule(pl.chains, T, grid, pl.n_full, pl.split_s, pl.split_q)) {
+        pl.launches_per_block += 1;                                     // c10_finalize_bf16_kernel
+        pl.c1x1_launches = 1;
     }
-    pl.strict = h->strict || h->strict_once || !h->weights_f16_ok;   // f32-MFMA kernels only
+    pl.name = pl.bmid ? "bf16_mid4" : (pl.fuse10 ? (pl.split_s ? "bf16_3_split" : "bf16_3") : "bf16_4");
+    pl.mfma = h->bf16_m16 ? 16 : 32;
+    pl.merge1 = M1_BF16;
+    pl.merge_stride = 64;
+}
+
+void plan_fp32_trunk(const pfnl_handle* h, TrunkPlan& pl, int B, int H, int W, int T, int grid, int mid_chains, bool fits32) {
     // conv3x3 = auto (default): the split-f16 kernels when a launch has at least ~0.78 tiles per CU, the Winograd f32 kernel below
+    const int small_tiles = scaled_by_cus(kSmallTiles256, h->ncu);
     const int algo0 = h->conv_algo == 5 ? ((pl.tiles8x32 >= small_tiles && fits32) ? 4 : 3) : h->conv_algo;
     pl.algo = (pl.strict && algo0 == 4) ? 3 : algo0;
     pl.conv1x1_algo = (pl.strict && h->conv1x1_algo == 2) ? 1 : h->conv1x1_algo;
@@ -464,40 +486,440 @@ TrunkPlan trunk_plan(const pfnl_handle* h, int B, int H, int W) {
         pl.launches_per_block = pl.small_c10 ? 2 : 3;
         pl.c1x1_launches = pl.small_c10 ? 0 : 1;
         pl.name = pl.small_c10 ? "small2" : "small3";
-        return pl;
+        pl.merge1 = M1_SMALL;
+        pl.merge_stride = 64;
+        return;
     }
     pl.mid = pl.sf && h->sf_mid && h->conv_algo == 5 && h->sf_c10 && h->sf_chain && pl.chains < mid_chains;   // (only under the default choices, like `small`)
     pl.c10_fused = pl.sf && h->sf_c10 && !pl.mid;
     pl.chain = pl.sf && h->sf_chain && !pl.mid;
     pl.sf0 = pl.c10_fused && pl.chain && h->sf0;
+    // grouped / accumulating Winograd modes chain T(+1) units inside one workgroup: only worth it when there are enough (clip, 4x32-pixel tile)
+    // groups to occupy the chip (below ~220 the split launches finish sooner)
     const int wino_groups = B * ((W + 31) / 32) * ((H + 3) / 4);
     pl.conv2_grouped = pl.algo == 3 && h->conv2_grouped && wino_groups >= 224 && fits32;
     pl.launches_per_block = (pl.c10_fused ? 1 : 2) + ((pl.chain || pl.conv2_grouped) ? 1 : 2);
     pl.c1x1_launches = pl.c10_fused ? 0 : 1;
     // SPLIT CHAINS of conv1_i + conv10_i and conv2_i (chain_order.h, split_rule)
-    if (pl.c10_fused && pl.chain && h->split_chains && split_rule(pl.chains, T, persistent_grid(device_cu_count()), pl.n_full, pl.split_s, pl.split_q)) {
+    if (pl.c10_fused && pl.chain && h->split_chains && split_rule(pl.chains, T, grid, pl.n_full, pl.split_s, pl.split_q)) {
         pl.launches_per_block += 1;                                     // c10_finalize_kernel
         pl.c1x1_launches = 1;
     }
     // the chain launch on 16x16x32: where every CU has a chain the launch sits on the power cap and the shape's energy counts; below that (UDM10: 230
     // chains) its extra cycles do (+0.9 %); split chains and the split-format copy stay on the 32x32x16 kernel
-    pl.mfma = (h->s16_m16 && pl.c10_fused && pl.chain && !pl.sf0 && !pl.split_s && pl.chains >= persistent_grid(device_cu_count())) ? 16 : 32;
+    pl.mfma = (h->s16_m16 && pl.c10_fused && pl.chain && !pl.sf0 && !pl.split_s && pl.chains >= grid) ? 16 : 32;
     pl.name = pl.mid ? "mid4" : (pl.c10_fused && pl.chain) ? (pl.sf0 ? "chain2_sf0" : (pl.split_s ? "chain2_split" : "chain2"))
             : pl.algo == 4 ? (pl.launches_per_block == 3 ? "split16_3" : "split16_4")
             : pl.algo == 3 ? (pl.conv2_grouped ? "winograd_ws3" : "winograd_ws4")
             : pl.algo == 1 ? "winograd_tile4" : "direct4";
+    // convmerge1: on the f16 pipe with the split-f16 trunk (convmerge1's chains are the trunk's: a cut last round is cut here too), else the
+    // persistent Winograd kernel where there are enough groups, else the direct kernel
+    if (pl.algo == 4 && h->m1_algo != 2 && fits32) pl.merge1 = pl.split_s ? M1_SPLIT16_CUT : M1_SPLIT16;
+    else if ((pl.algo == 3 || pl.algo == 4) && wino_groups >= 224 && fits32) pl.merge1 = M1_WINOGRAD;
+    pl.merge_stride = pl.merge1 == M1_DIRECT ? 48 : 64;
+}
+
+// H: the rows the trunk buffers hold (a strip's with its halo); Hfull: the frame's (the non-local block's keys are global)
+TrunkPlan trunk_plan(const pfnl_handle* h, int B, int H, int W, int Hfull) {
+    TrunkPlan pl;
+    const int T = h->cfg.num_frames;
+    pl.bf16 = h->bf16;
+    pl.strict = !h->bf16 && (h->strict || h->strict_once || !h->weights_f16_ok);
+    pl.tiles8x32 = B * T * ((W + 31) / 32) * ((H + 7) / 8);
+    pl.chains = pl.tiles8x32 / T;
+    const int grid = persistent_grid(h->ncu);
+    const int mid_chains = h->sf_mid_chains > 0 ? h->sf_mid_chains : scaled_by_cus(kMidChains256, h->ncu);
+    const bool fits32 = (long long)H * W * 256 < 0x7fffffffLL;
+    if (h->bf16) plan_bf16_trunk(h, pl, T, grid, mid_chains, fits32);
+    else plan_fp32_trunk(h, pl, B, H, W, T, grid, mid_chains, fits32);
+
+    const int N = (Hfull / 2) * (W / 2);
+    pl.nltype = h->nl_type < 0 ? (h->nl_theta ? 0 : 1) : h->nl_type;
+    pl.nl_family = (pl.nltype != 1 || h->nl_sub > 1) ? 0
+                 : h->bf16 ? 2
+                 : (!pl.strict && (h->nl_algo == 1 || (h->nl_algo == 2 && N >= 1024))) ? 1 : 3;
+    pl.nl_fused_pack = (pl.nl_family == 1 || pl.nl_family == 2) && nl_f16_fits_one_launch(B, N);
+
+    const size_t frame_floats = (size_t)B * T * H * W * 64;
+    pl.p10_floats = pl.small_c10 ? frame_floats : 0;
+    pl.inp0sf_floats = pl.sf0 ? frame_floats : 0;
+    pl.c10part_floats = pl.split_s ? (size_t)(pl.chains - pl.n_full) * pl.split_s * 8 * 32 * 64 : 0;
     return pl;
 }
 
-// which kernel family the non-local block takes (the same one statement for forward_device and pfnl_plan): 0 the general form (nltype 0 / 2 or
-// sub-sampling: f32 MFMA), 1 the f16 pipe with exactly split operands (fp32 precision, from 1024 keys), 2 the f16 pipe on the hi parts (precision
-// bf16), 3 f32 MFMA (small key counts, strict_fp32)
-int nl_family(const pfnl_handle* h, int N) {
-    const int nlt = h->nl_type < 0 ? (h->nl_theta ? 0 : 1) : h->nl_type;
-    if (nlt != 1 || h->nl_sub > 1) return 0;
-    if (h->bf16) return 2;
-    const bool nl_strict = h->strict || h->strict_once || !h->weights_f16_ok;
-    return (!nl_strict && (h->nl_algo == 1 || (h->nl_algo == 2 && N >= 1024))) ? 1 : 3;
+// what every stage of one forward reads
+struct Fwd {
+    pfnl_handle* h;
+    const TrunkPlan& pl;
+    hipStream_t s;
+    int B, T, F, H, W;         // F = B * T frames; H: the rows the trunk buffers hold
+    const float* wd;           // the fp32 blob
+    const uint16_t* w16;       // the bf16 packs
+    const uint16_t* w16s;      // the split-f16 and small-shape packs
+};
+
+// the split-chain geometry of a chained launch; `partial`: where its parts leave their sums (null: the launch leaves none)
+template <class P>
+void set_split_chains(P& q, const TrunkPlan& pl, float* partial) {
+    q.n_full = pl.n_full;
+    q.split_s = pl.split_s;
+    q.split_q = pl.split_q;
+    q.partial = pl.split_s ? partial : nullptr;
+}
+
+// launch_c10_finalize(_bf16): the parts' raw sums in c10part -> the chains that were cut (the caller sets the output, bias and act)
+template <class P>
+P split_finalize_params(const Fwd& f) {
+    P q{};
+    q.H = f.H;
+    q.W = f.W;
+    q.items = f.F;
+    q.add_div = f.T;
+    set_split_chains(q, f.pl, f.h->c10part.p);
+    return q;
+}
+
+// a launch of the direct kernel (conv_mfma.hip) over 64-channel frames, `frames` of them per item (1: per frame, T: over their concat)
+ConvParams direct_params(const Fwd& f, const float* in, const float* wpack, const float* bias, float* out, int cout, int frames, int act) {
+    ConvParams p{};
+    p.in = in;
+    p.wpack = wpack;
+    p.bias = bias;
+    p.out = out;
+    p.H = f.H;
+    p.W = f.W;
+    p.in_cstride = 64;
+    p.out_cstride = cout;
+    p.cout = cout;
+    p.chunks_per_frame = 64 / CONV_CK;
+    p.frames_per_item = frames;
+    p.nchunks = frames * p.chunks_per_frame;
+    p.add_div = 1;
+    p.act = act;
+    return p;
+}
+
+int ensure_workspace(pfnl_handle* h, const TrunkPlan& pl, int B, int H, int W, int N) {
+    const int T = h->cfg.num_frames, C = 12 * T, CP = nl_padded_ch(C);
+    const size_t P = (size_t)H * W;
+    if (h->X.ensure((size_t)B * N * CP) || h->Xo.ensure((size_t)B * N * CP) ||     // (N: the FULL frame - keys are global)
+        h->nlp.ensure(nl_partial_floats(B, N, C)) ||
+        h->inp0.ensure((size_t)B * T * P * 64) || h->inp1.ensure((size_t)B * T * P * 64) ||
+        h->base.ensure((size_t)B * P * 64) || h->pb.ensure((size_t)B * P * 64) ||
+        h->merge.ensure((size_t)B * P * 64))
+        return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
+    h->lastB = B;
+    h->lastH = H;
+    h->lastW = W;
+    if (h->p10.ensure(h->cfg.num_block > 0 ? pl.p10_floats : 0) || h->inp0sf.ensure(pl.inp0sf_floats) || h->c10part.ensure(pl.c10part_floats))
+        return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
+    return 0;
+}
+
+// model/pfnl.py:55-60 (+ utils.py:18-71): x -> Xo; queries [q0, q1) against all keys
+int nonlocal_block(const Fwd& f, const float* in, int Hfull, int q0, int q1) {
+    pfnl_handle* const h = f.h;
+    const TrunkPlan& pl = f.pl;
+    const int B = f.B, T = f.T, W = f.W, N = (Hfull / 2) * (W / 2), C = 12 * T, CP = nl_padded_ch(C), nlt = pl.nltype;
+    const float* const wd = f.wd;
+    const hipStream_t s = f.s;
+    if ((pl.nl_family == 1 || pl.nl_family == 2) && h->nl16.ensure((nl_f16_scratch_halfs(B, N) + 1) / 2))
+        return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
+    {
+        ProfScope ps(h, s, PFNL_K_NL_PACK);
+        if (pl.nl_fused_pack) HIPCHK(launch_nl_pack_fused(in, h->X.p, reinterpret_cast<uint16_t*>(h->nl16.p), B, T, Hfull, W, s));
+        else HIPCHK(launch_nl_pack(in, h->X.p, B, T, Hfull, W, s));
+    }
+    ProfScope ps(h, s, PFNL_K_NL_ATTN);
+    if ((nlt == 0 || nlt == 2) && !h->nl_theta)
+        return fail(PFNL_ERR_STATE, "nl_type 0 / 2 need the nlblock_0 theta / phi variables (reference utils.py:31-42)");
+    if (pl.nl_family == 0) {
+        // the general form of utils.NonLocalBlock (nltype 0 / 2: queries X M + c; sub_sample: keys = values = avg-pooled X) on
+        // the f32-MFMA kernel in both precisions; PFNL's own call (nltype 1, sub_sample 1) takes the branches below
+        const float* Kx = h->X.p;
+        int Nk = N;
+        if (h->nl_sub > 1) {
+            const int h2 = Hfull / 2, w2 = W / 2;
+            if (h2 / h->nl_sub < 1 || w2 / h->nl_sub < 1) return fail(PFNL_ERR_INVALID, "nl_sub_sample larger than the space_to_depth grid");
+            Nk = (h2 / h->nl_sub) * (w2 / h->nl_sub);
+            if (h->Xs.ensure((size_t)B * Nk * CP)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
+            HIPCHK(launch_nl_pool(h->X.p, h->Xs.p, B, h2, w2, h->nl_sub, C, s));
+            Kx = h->Xs.p;
+        }
+        const float* Qp = nullptr;
+        if (nlt != 1) {
+            if (h->Q.ensure((size_t)B * N * CP)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
+            HIPCHK(launch_nl_qproj(h->X.p, wd + h->off_nl_m, wd + h->off_nl_c, h->Q.p, B, N, C, s, nlt == 2));
+            Qp = h->Q.p;
+        }
+        HIPCHK(launch_nl_attn_general(h->X.p, Kx, Nk, h->Xo.p, wd + h->off_nl_w, wd + h->off_nl_b, h->nlp.p, B, N, C, s, Qp, q0, q1, nlt == 2));
+    } else if (pl.nl_family == 1 || pl.nl_family == 2) {
+        // the f16 pipe: fp32 precision with exactly split operands (1), 16-bit operands throughout - the hi parts only (2)
+        HIPCHK(launch_nl_attn_f16(h->X.p, h->Xo.p, wd + h->off_nl_w, wd + h->off_nl_b, h->nlp.p, reinterpret_cast<uint16_t*>(h->nl16.p), B, N, C, s,
+                                  q0, q1, pl.nl_family == 1, pl.nl_fused_pack));
+    } else {
+        HIPCHK(launch_nl_attn(h->X.p, h->Xo.p, wd + h->off_nl_w, wd + h->off_nl_b, h->nlp.p, B, N, C, s, nullptr, q0, q1));
+    }
+    return 0;
+}
+
+// ---- the PF blocks (model/pfnl.py:65-71), one function per trunk family
+
+// bf16 trunk (conv_bf16.hip): activations bf16 in the same workspace buffers, fp32 accumulation and biases.  MID shapes (bmid): the chained
+// launches - conv1_i + conv10_i, the per-frame half of conv2_i - would leave most CUs idle for T tile times; conv10_i then runs as its own
+// launch and the per-frame half deals out single tiles (bit-identical: this kernel has one summation order)
+int block_bf16(const Fwd& f, const BlockPacks& k) {
+    pfnl_handle* const h = f.h;
+    const TrunkPlan& pl = f.pl;
+    const hipStream_t s = f.s;
+    const float* const wd = f.wd;
+    uint16_t* const a0 = reinterpret_cast<uint16_t*>(h->inp0.p);
+    uint16_t* const a1 = reinterpret_cast<uint16_t*>(h->inp1.p);
+    uint16_t* const ab = reinterpret_cast<uint16_t*>(h->base.p);
+    uint16_t* const ap = reinterpret_cast<uint16_t*>(h->pb.p);
+    {   // conv1_i (+ conv10_i from the LDS scratch its tiles pass through: conv_bf16.hip MODE 2)
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        ConvBf16Params q{a0, f.w16 + k.bf_c1, wd + k.c1_b, nullptr, nullptr, a1, f.H, f.W, f.F, 1, 1};
+        if (pl.fuse10) {
+            q.add_div = f.T;
+            q.x_w = f.w16 + k.bf_c10;
+            q.x_bias = wd + k.c10_b;
+            q.x_out = ab;
+            set_split_chains(q, pl, h->c10part.p);
+        }
+        if (pl.mfma == 16) q.wpack16 = f.w16 + k.bf_c1_m16;   // (used where the launch goes to the third-generation kernel)
+        HIPCHK(launch_conv3x3_bf16(q, s));
+    }
+    if (pl.fuse10 && pl.split_s) {   // split chains: the parts' raw conv10_i sums -> base (+ bias, leaky-relu, bf16) for the chains that were cut
+        ProfScope ps(h, s, PFNL_K_CONV1X1);
+        ConvBf16Params q = split_finalize_params<ConvBf16Params>(f);
+        q.x_bias = wd + k.c10_b;
+        q.x_out = ab;
+        HIPCHK(launch_c10_finalize_bf16(q, s));
+    }
+    if (!pl.fuse10) {   // conv10_i as a launch of its own
+        ProfScope ps(h, s, PFNL_K_CONV1X1);
+        HIPCHK(launch_conv1x1_bf16(a1, f.w16 + k.bf_c10, wd + k.c10_b, ab, f.B, f.T, f.H * f.W, 1, s));
+    }
+    {   // conv2_i, shared half (raw, once per clip)
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        ConvBf16Params q{ab, f.w16 + k.bf_c2a, wd + h->off_zero, nullptr, nullptr, ap, f.H, f.W, f.B, 1, 0};
+        HIPCHK(launch_conv3x3_bf16(q, s));
+    }
+    {   // conv2_i, per-frame half + shared half + bias, lrelu, residual
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        ConvBf16Params q{a1, f.w16 + k.bf_c2b, wd + k.c2_b, ap, a0, a0, f.H, f.W, f.F, f.T, 1};
+        q.flat = pl.bmid ? 1 : 0;
+        set_split_chains(q, pl, nullptr);
+        if (pl.mfma == 16) q.wpack16 = f.w16 + k.bf_c2b_m16;
+        HIPCHK(launch_conv3x3_bf16(q, s));
+    }
+    return 0;
+}
+
+// small shapes (BASELINE.json configs[0], configs[4]): the trunk through conv_small.hip - conv2_i as the reference writes it (3x3 over
+// concat([base, f])).  small_c10: two launches per block, conv10_i rides in the conv1_i launch as per-frame partials (W10_t^T . inp1_t), which
+// conv2_i's prologue adds up (+ bias, leaky-relu) into its `base` source - no 1x1 launch, no inter-workgroup traffic inside a launch
+int block_small(const Fwd& f, const BlockPacks& k) {
+    pfnl_handle* const h = f.h;
+    const hipStream_t s = f.s;
+    const float* const wd = f.wd;
+    const int H = f.H, W = f.W, F = f.F, T = f.T;
+    {   // conv1_i (:66) (+ this frame's part of conv10_i, :67-68)
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        ConvSmallParams q{nullptr, h->inp0.p, 0, 1, 1, 1, f.w16s + k.sm_c1, wd + k.c1_b, nullptr, h->inp1.p, H, W, F, 1, 3};
+        if (f.pl.small_c10) {
+            q.x_wpack = f.w16s + k.sm_c10;
+            q.x_out = h->p10.p;
+            q.x_T = T;
+        }
+        HIPCHK(launch_conv_small(q, s));
+    }
+    if (!f.pl.small_c10) {   // conv10_i (:67-68)
+        ProfScope ps(h, s, PFNL_K_CONV1X1);
+        ConvSmallParams q{nullptr, h->inp1.p, 0, 1, T, T, f.w16s + k.sm_c10, wd + k.c10_b, nullptr, h->base.p, H, W, f.B, 1, 1};
+        HIPCHK(launch_conv_small(q, s));
+    }
+    {   // conv2_i over concat([base, inp1_t]) + lrelu + residual (:69-71); small_c10: base = lrelu(sum of the T partials + bias)
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        ConvSmallParams q{f.pl.small_c10 ? h->p10.p : h->base.p, h->inp1.p, 1, T, 1, 2, f.w16s + k.sm_c2, wd + k.c2_b, h->inp0.p, h->inp0.p, H, W, F, 1, 3};
+        if (f.pl.small_c10) {
+            q.a_nsum = T;
+            q.a_bias = wd + k.c10_b;
+        }
+        HIPCHK(launch_conv_small(q, s));
+    }
+    return 0;
+}
+
+// the fp32 trunk (every structure but small): inp0 -> inp1 (conv1_i), base (conv10_i), inp0 += conv2_i; `last`: the forward's last block
+int block_fp32(const Fwd& f, const BlockPacks& k, bool first, bool last) {
+    pfnl_handle* const h = f.h;
+    const TrunkPlan& pl = f.pl;
+    const hipStream_t s = f.s;
+    const float* const wd = f.wd;
+    const int H = f.H, W = f.W, F = f.F, T = f.T, B = f.B, algo = pl.algo;
+    const bool sf = pl.sf;                                          // inp1 and base in the split format (conv_split16.h)
+    // chain2_sf0 (round 6): blocks 1 .. nb-1 read the split-format copy of inp0 the previous block's chain kernel wrote (halo by
+    // LDS-DMA); block 0 reads conv0's fp32 output, the last block writes no copy (convmerge1 reads fp32).  Bit-identical to chain2.
+    const bool in_sf0 = pl.sf0 && !first, out_sf0 = pl.sf0 && !last;
+    if (pl.c10_fused) {
+        // conv1_i AND conv10_i in one launch (conv_split16.hip, conv3x3_c1c10_kernel): per (clip, tile) the T frame tiles of conv1_i
+        // leave as split-format lines through LDS, where conv10_i picks them up as MFMA operands; inp1 is written, never read back
+        {
+            ProfScope ps(h, s, PFNL_K_CONV3X3);
+            ConvSplitParams q{in_sf0 ? h->inp0sf.p : h->inp0.p, f.w16s + k.s_c1, wd + k.c1_b, nullptr, nullptr, h->inp1.p, H, W, F, T, 1};
+            q.in_sf = in_sf0 ? 1 : 0;
+            q.wpack2 = f.w16s + k.s_c10f;
+            q.bias2 = wd + k.c10_b;
+            q.out2 = h->base.p;
+            set_split_chains(q, pl, h->c10part.p);
+            HIPCHK(launch_conv3x3_c1c10(q, s));
+        }
+        if (pl.split_s) {   // split chains: the parts' raw conv10_i sums -> base (+ leaky-relu, split format) for the chains that were cut
+            ProfScope ps(h, s, PFNL_K_CONV1X1);
+            ConvSplitParams q = split_finalize_params<ConvSplitParams>(f);
+            q.act = 1;
+            q.out2 = h->base.p;
+            HIPCHK(launch_c10_finalize(q, s));
+        }
+    } else {
+        {   // conv1_i: per frame 3x3 64->64 + lrelu                       (:66)
+            ProfScope ps(h, s, PFNL_K_CONV3X3);
+            if (algo == 4) {
+                ConvSplitParams q{h->inp0.p, f.w16s + k.s_c1, wd + k.c1_b, nullptr, nullptr, h->inp1.p, H, W, F, 1, 1};
+                q.out_sf = sf ? 1 : 0;                              // inp1 in the split format: it only feeds conv10_i and conv2_i's MFMA operands
+                HIPCHK(launch_conv3x3_split16(q, s));
+            } else if (algo == 1 || algo == 3) {
+                WinoParams wp{h->inp0.p, wd + k.c1_u, wd + k.c1_b, nullptr, nullptr, h->inp1.p, H, W, 1, 1, F, nullptr};
+                HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
+            } else {
+                HIPCHK(launch_conv_mfma(direct_params(f, h->inp0.p, wd + k.c1_w, wd + k.c1_b, h->inp1.p, 64, 1, 1), 3, F, s));
+            }
+        }
+        {   // conv10_i: 1x1 over the concat of T frames -> base + lrelu    (:67-68)
+            ProfScope ps(h, s, PFNL_K_CONV1X1);
+            if (pl.conv1x1_algo == 2)
+                HIPCHK(launch_conv1x1_split16(h->inp1.p, f.w16s + k.s_c10, wd + k.c10_b, h->base.p, B, T, H * W, 1, s, sf, sf));
+            else if (pl.conv1x1_algo == 1)
+                HIPCHK(launch_conv1x1_stream(h->inp1.p, wd + k.c10_s, wd + k.c10_b, h->base.p, B, T, H * W, 1, s));
+            else
+                HIPCHK(launch_conv_mfma(direct_params(f, h->inp1.p, wd + k.c10_w, wd + k.c10_b, h->base.p, 64, T, 1), 1, B, s));
+        }
+    }
+    if (pl.conv2_grouped) {
+        // the whole of conv2_i in one launch: per (clip, tile) the shared half stays in LDS (conv_wino_ws MODE 2)
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        WinoParams wp{h->inp1.p, wd + k.c2b_u, wd + k.c2_b, nullptr, h->inp0.p, h->inp0.p, H, W, T, 1, F, nullptr};
+        wp.in2 = h->base.p;
+        wp.upack2 = wd + k.c2a_u;
+        HIPCHK(launch_conv_wino_ws(wp, s));
+        return 0;
+    }
+    if (pl.chain) {
+        // the whole of conv2_i in one launch (conv_sf.hip, conv3x3_sf_chain_kernel): per (clip, tile) the shared half stays in
+        // registers as the initial C of the T frame tiles; in place on inp0 (residual)
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        ConvSplitParams q{h->inp1.p, f.w16s + k.s_c2b_sf, wd + k.c2_b, nullptr, h->inp0.p, h->inp0.p, H, W, F, T, 1};
+        q.in2 = h->base.p;
+        q.wpack2 = f.w16s + k.s_c2a_sf;
+        q.out2 = out_sf0 ? h->inp0sf.p : nullptr;
+        set_split_chains(q, pl, nullptr);
+        if (pl.mfma == 16) {                                        // (trunk_plan: whole rounds with a chain per CU)
+            q.wpack_m16 = f.w16s + k.s_c2b_m16;
+            q.wpack2_m16 = f.w16s + k.s_c2a_m16;
+        }
+        HIPCHK(launch_conv3x3_sf_chain(q, s));
+        return 0;
+    }
+    {   // conv2_i, shared half: 3x3 over `base` (kernel rows 0..63), once per clip, raw
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        if (algo == 4) {
+            ConvSplitParams q{h->base.p, f.w16s + (sf ? k.s_c2a_sf : k.s_c2a), wd + h->off_zero, nullptr, nullptr, h->pb.p, H, W, B, 1, 0};
+            HIPCHK(sf ? launch_conv3x3_sf(q, s) : launch_conv3x3_split16(q, s));
+        } else if (algo == 1 || algo == 3) {
+            WinoParams wp{h->base.p, wd + k.c2a_u, wd + h->off_zero, nullptr, nullptr, h->pb.p, H, W, 1, 0, B, nullptr};
+            HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
+        } else {
+            HIPCHK(launch_conv_mfma(direct_params(f, h->base.p, wd + k.c2a_w, wd + h->off_zero, h->pb.p, 64, 1, 0), 3, B, s));
+        }
+    }
+    {   // conv2_i, per-frame half (kernel rows 64..127) + shared half + bias, lrelu, residual (:69-71)
+        // MID shapes (mid): the block deals out single tiles here - a launch with fewer (clip, tile) chains than CUs would leave most of the chip
+        // idle for T + 2 tile times (1 clip of 128x128: 64 chains - 3.06 ms for a quarter of configs[1]'s work)
+        ProfScope ps(h, s, PFNL_K_CONV3X3);
+        if (algo == 4) {
+            ConvSplitParams q{h->inp1.p, f.w16s + (sf ? k.s_c2b_sf : k.s_c2b), wd + k.c2_b, h->pb.p, h->inp0.p, h->inp0.p, H, W, F, T, 1};
+            q.flat = pl.mid ? 1 : 0;
+            HIPCHK(sf ? launch_conv3x3_sf(q, s) : launch_conv3x3_split16(q, s));
+        } else if (algo == 1 || algo == 3) {
+            WinoParams wp{h->inp1.p, wd + k.c2b_u, wd + k.c2_b, h->pb.p, h->inp0.p, h->inp0.p, H, W, T, 1, F, nullptr};
+            HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
+        } else {
+            ConvParams p = direct_params(f, h->inp1.p, wd + k.c2b_w, wd + k.c2_b, h->inp0.p, 64, 1, 1);
+            p.addend = h->pb.p;
+            p.add_div = T;
+            p.resid = h->inp0.p;
+            HIPCHK(launch_conv_mfma(p, 3, F, s));
+        }
+    }
+    return 0;
+}
+
+// convmerge1 (model/pfnl.py:73-74): the trunk [B*T][H][W] -> merge [B][H][W][merge_stride], lrelu
+int convmerge1(const Fwd& f) {
+    pfnl_handle* const h = f.h;
+    const TrunkPlan& pl = f.pl;
+    const hipStream_t s = f.s;
+    const float* const wd = f.wd;
+    const int H = f.H, W = f.W, F = f.F, T = f.T;
+    h->merge_cstride = pl.merge_stride;
+    if (pl.merge1 == M1_SPLIT16 || pl.merge1 == M1_SPLIT16_CUT) {
+        // on the f16 pipe: the accumulating mode of conv3x3_split16_kernel (the T frame tiles of a clip run through the same accumulators, every
+        // unit with its own weights; cout zero-padded to 64; one epilogue per clip tile).  Cut: convmerge1's chains are the trunk's - the same
+        // last, partial round is cut by frames, the parts' raw sums meet in c10_finalize_kernel (+ bias, leaky-relu); c10part is free behind the last block
+        {
+            ProfScope ps(h, s, PFNL_K_MERGE1);
+            ConvSplitParams q{h->inp0.p, f.w16s + h->off16s_m1, wd + h->off_m1_b, nullptr, nullptr, h->merge.p, H, W, F, T, 1, 1};
+            set_split_chains(q, pl, h->c10part.p);
+            HIPCHK(launch_conv3x3_split16(q, s));
+        }
+        if (pl.merge1 == M1_SPLIT16_CUT) {
+            ProfScope ps(h, s, PFNL_K_MERGE1);
+            ConvSplitParams q = split_finalize_params<ConvSplitParams>(f);
+            q.act = 1;
+            q.bias = wd + h->off_m1_b;
+            q.out = h->merge.p;
+            HIPCHK(launch_c10_finalize(q, s));
+        }
+        return 0;
+    }
+    ProfScope ps(h, s, PFNL_K_MERGE1);
+    switch (pl.merge1) {
+    case M1_SMALL: {   // T sources, cout 48 zero-padded to 64
+        ConvSmallParams q{nullptr, h->inp0.p, 0, 1, T, T, f.w16s + h->off16m_m1, wd + h->off_m1_b, nullptr, h->merge.p, H, W, f.B, 1, 3};
+        HIPCHK(launch_conv_small(q, s));
+        return 0;
+    }
+    case M1_BF16: {    // the accumulating mode of the bf16 3x3 kernel, fp32 out for the tail
+        ConvBf16Params q{reinterpret_cast<const uint16_t*>(h->inp0.p), f.w16 + h->off16_m1, wd + h->off_m1_b, nullptr, nullptr, nullptr, H, W, F, T, 1};
+        q.out_f32 = h->merge.p;
+        HIPCHK(launch_conv3x3_bf16(q, s));
+        return 0;
+    }
+    case M1_WINOGRAD: {
+        // one launch of the persistent Winograd kernel in its accumulating mode (cout zero-padded to 64; the T frame tiles of a clip add into
+        // the same accumulators, one epilogue per clip tile)
+        WinoParams wp{h->inp0.p, wd + h->off_m1_u[0], wd + h->off_m1_b, nullptr, nullptr, h->merge.p, H, W, T, 1, F, nullptr};
+        wp.upack_stride = T > 1 ? (long long)(h->off_m1_u[1] - h->off_m1_u[0]) : 0;
+        wp.accum = 1;
+        HIPCHK(launch_conv_wino_ws(wp, s));
+        return 0;
+    }
+    default:           // 3x3 over the concat of T frames -> 48
+        HIPCHK(launch_conv_mfma(direct_params(f, h->inp0.p, wd + h->off_m1_w, wd + h->off_m1_b, h->merge.p, 48, T, 1), 3, f.B, s));
+        return 0;
+    }
 }
 
 // forward over device buffers
@@ -506,194 +928,23 @@ int nl_family(const pfnl_handle* h, int N) {
 int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull, int W, hipStream_t s,
                    const StripGeom* strip = nullptr, int q0 = 0, int q1 = -1, int flag_slot = 1 /* 0: synchronous call, 1: asynchronous */) {
     const pfnl_config& c = h->cfg;
-    const int T = c.num_frames, F = B * T;
+    const int T = c.num_frames;
     const int H = strip ? strip->Hs : Hfull;                       // rows the trunk buffers hold
-    const size_t P = (size_t)H * W;
-    const int N = (Hfull / 2) * (W / 2);
-    const int C = 12 * T, CP = nl_padded_ch(C);
-    const float* wd = h->wdev.p;
-    const TrunkPlan pl = trunk_plan(h, B, H, W);
+    const TrunkPlan pl = trunk_plan(h, B, H, W, Hfull);
+    if (pl.bf16 && (long long)T * H * W * 128 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the bf16 trunk");
+    if (int e = ensure_workspace(h, pl, B, H, W, (Hfull / 2) * (W / 2))) return e;
+    const Fwd f{h, pl, s, B, T, B * T, H, W, h->wdev.p, reinterpret_cast<const uint16_t*>(h->wdev16.p), reinterpret_cast<const uint16_t*>(h->wdev16s.p)};
+    const float* const wd = h->wdev.p;
 
-    if (h->X.ensure((size_t)B * N * CP) || h->Xo.ensure((size_t)B * N * CP) ||     // (N: the FULL frame - keys are global)
-        h->nlp.ensure(nl_partial_floats(B, N, C)) ||
-        h->inp0.ensure((size_t)F * P * 64) || h->inp1.ensure((size_t)F * P * 64) ||
-        h->base.ensure((size_t)B * P * 64) || h->pb.ensure((size_t)B * P * 64) ||
-        h->merge.ensure((size_t)B * P * 64))
-        return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-    h->lastB = B;
-    h->lastH = H;
-    h->lastW = W;
-
-    const bool nl_strict = !h->bf16 && (h->strict || h->strict_once || !h->weights_f16_ok);
-    // The range fence is armed only when a kernel with a binary16 DOMAIN runs (fp32 precision off the strict path: split-f16 trunk,
-    // non-local block and conv0; bf16 precision: its non-local block and conv0) and a non-finite value cannot be the reference's
-    // own result (nltype 2 divides 0 by 0 for a query without a positive affinity, utils.py:59-62).
-    const int nlt_fence = h->nl_type < 0 ? (h->nl_theta ? 0 : 1) : h->nl_type;
-    unsigned* const rflag = (nl_strict || nlt_fence == 2) ? nullptr : h->rflag_dev + flag_slot;
-    // the non-local block on the f16 matrix pipe (PFNL's own call: nltype 1, no sub-sampling; fp32 precision from 1024 keys, bf16 always)
-    const int nl_fam = nl_family(h, N);
-    const bool nl_fused_pack = (nl_fam == 1 || nl_fam == 2) && nl_f16_fits_one_launch(B, N);   // one pack launch: x -> X fp32 + the binary16 K / V^T operands (round 6)
-    {   // model/pfnl.py:55-60 (+ utils.py:18-71)
-        ProfScope ps(h, s, PFNL_K_NL_PACK);
-        if (nl_fused_pack) {
-            if (h->nl16.ensure((nl_f16_scratch_halfs(B, N) + 1) / 2)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-            HIPCHK(launch_nl_pack_fused(in, h->X.p, reinterpret_cast<uint16_t*>(h->nl16.p), B, T, Hfull, W, s));
-        } else {
-            HIPCHK(launch_nl_pack(in, h->X.p, B, T, Hfull, W, s));
-        }
-    }
-    {
-        ProfScope ps(h, s, PFNL_K_NL_ATTN);
-        const int nlt = h->nl_type < 0 ? (h->nl_theta ? 0 : 1) : h->nl_type;
-        if ((nlt == 0 || nlt == 2) && !h->nl_theta)
-            return fail(PFNL_ERR_STATE, "nl_type 0 / 2 need the nlblock_0 theta / phi variables (reference utils.py:31-42)");
-        if (nlt != 1 || h->nl_sub > 1) {
-            // the general form of utils.NonLocalBlock (nltype 0 / 2: queries X M + c; sub_sample: keys = values = avg-pooled X) on
-            // the f32-MFMA kernel in both precisions; PFNL's own call (nltype 1, sub_sample 1) takes the branches below
-            const float* Kx = h->X.p;
-            int Nk = N;
-            if (h->nl_sub > 1) {
-                const int h2 = Hfull / 2, w2 = W / 2;
-                if (h2 / h->nl_sub < 1 || w2 / h->nl_sub < 1) return fail(PFNL_ERR_INVALID, "nl_sub_sample larger than the space_to_depth grid");
-                Nk = (h2 / h->nl_sub) * (w2 / h->nl_sub);
-                if (h->Xs.ensure((size_t)B * Nk * CP)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-                HIPCHK(launch_nl_pool(h->X.p, h->Xs.p, B, h2, w2, h->nl_sub, C, s));
-                Kx = h->Xs.p;
-            }
-            const float* Qp = nullptr;
-            if (nlt != 1) {
-                if (h->Q.ensure((size_t)B * N * CP)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-                HIPCHK(launch_nl_qproj(h->X.p, wd + h->off_nl_m, wd + h->off_nl_c, h->Q.p, B, N, C, s, nlt == 2));
-                Qp = h->Q.p;
-            }
-            HIPCHK(launch_nl_attn_general(h->X.p, Kx, Nk, h->Xo.p, wd + h->off_nl_w, wd + h->off_nl_b, h->nlp.p, B, N, C, s, Qp, q0, q1, nlt == 2));
-        } else if (nl_fam == 1) {   // fp32 path on the f16 pipe, exactly split operands
-            if (h->nl16.ensure((nl_f16_scratch_halfs(B, N) + 1) / 2)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-            HIPCHK(launch_nl_attn_f16(h->X.p, h->Xo.p, wd + h->off_nl_w, wd + h->off_nl_b, h->nlp.p,
-                                      reinterpret_cast<uint16_t*>(h->nl16.p), B, N, C, s, q0, q1, true, nl_fused_pack));
-        } else if (nl_fam == 2) {   // 16-bit operands throughout: the f16 kernel on the hi parts only
-            if (h->nl16.ensure((nl_f16_scratch_halfs(B, N) + 1) / 2)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-            HIPCHK(launch_nl_attn_f16(h->X.p, h->Xo.p, wd + h->off_nl_w, wd + h->off_nl_b, h->nlp.p,
-                                      reinterpret_cast<uint16_t*>(h->nl16.p), B, N, C, s, q0, q1, false, nl_fused_pack));
-        } else {
-            HIPCHK(launch_nl_attn(h->X.p, h->Xo.p, wd + h->off_nl_w, wd + h->off_nl_b, h->nlp.p, B, N, C, s, nullptr, q0, q1));
-        }
-    }
+    if (int e = nonlocal_block(f, in, Hfull, q0, q1)) return e;
     {   // model/pfnl.py:61-62
         ProfScope ps(h, s, PFNL_K_CONV0);
-        if (h->bf16)
+        if (pl.bf16)
             HIPCHK(launch_conv0_bf16(h->Xo.p, wd + h->off_conv0_w, wd + h->off_conv0_b, reinterpret_cast<uint16_t*>(h->inp0.p), B, T, Hfull, W, s, strip));
         else
-            HIPCHK(launch_conv0(h->Xo.p, wd + h->off_conv0_w, wd + h->off_conv0_b, h->inp0.p, B, T, Hfull, W, s, strip, nl_strict));
+            HIPCHK(launch_conv0(h->Xo.p, wd + h->off_conv0_w, wd + h->off_conv0_b, h->inp0.p, B, T, Hfull, W, s, strip, pl.strict));
     }
-    const float* merge_in = h->inp0.p;
-    if (h->bf16) {
-        // bf16 trunk (conv_bf16.hip): activations bf16 in the same workspace buffers, fp32 accumulation and biases
-        if ((long long)T * H * W * 128 >= 0x7fffffffLL) return fail(PFNL_ERR_INVALID, "frame too large for the bf16 trunk");
-        uint16_t* const a0 = reinterpret_cast<uint16_t*>(h->inp0.p);
-        uint16_t* const a1 = reinterpret_cast<uint16_t*>(h->inp1.p);
-        uint16_t* const ab = reinterpret_cast<uint16_t*>(h->base.p);
-        uint16_t* const ap = reinterpret_cast<uint16_t*>(h->pb.p);
-        const uint16_t* const w16 = reinterpret_cast<const uint16_t*>(h->wdev16.p);
-        // MID shapes (trunk_plan): the chained launches - conv1_i + conv10_i, the per-frame half of conv2_i - leave most CUs idle for T
-        // tile times; conv10_i then runs as its own launch and the per-frame half deals out single tiles (bit-identical: this kernel
-        // has one summation order)
-        const bool bmid = pl.bmid, fuse10 = pl.fuse10;
-        if (pl.split_s && h->c10part.ensure((size_t)(pl.chains - pl.n_full) * pl.split_s * 8 * 32 * 64)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-        for (int i = 0; i < c.num_block; ++i) {   // model/pfnl.py:65-71
-            if (h->prof_mode == 2) {
-                h->prof_gate = prof_sampled(c.num_block, i);
-                h->chain_open = false;
-            } else if (h->prof_mode == 3) {
-                h->prof_gate = i == c.num_block / 2;
-                h->chain_open = false;
-            }
-            {   // conv1_i (+ conv10_i from the LDS scratch its tiles pass through: conv_bf16.hip MODE 2)
-                ProfScope ps(h, s, PFNL_K_CONV3X3);
-                ConvBf16Params q{a0, w16 + h->off16_c1[i], wd + h->off_c1_b[i], nullptr, nullptr, a1, H, W, F, 1, 1};
-                if (fuse10) {
-                    q.add_div = T;
-                    q.x_w = w16 + h->off16_c10[i];
-                    q.x_bias = wd + h->off_c10_b[i];
-                    q.x_out = ab;
-                    q.n_full = pl.n_full;
-                    q.split_s = pl.split_s;
-                    q.split_q = pl.split_q;
-                    q.partial = pl.split_s ? h->c10part.p : nullptr;
-                }
-                if (pl.mfma == 16) q.wpack16 = w16 + h->off16_c1_m16[i];   // (used where the launch goes to the third-generation kernel)
-                HIPCHK(launch_conv3x3_bf16(q, s));
-            }
-            if (fuse10 && pl.split_s) {   // split chains: the parts' raw conv10_i sums -> base (+ bias, leaky-relu, bf16) for the chains that were cut
-                ProfScope ps(h, s, PFNL_K_CONV1X1);
-                ConvBf16Params q{};
-                q.H = H;
-                q.W = W;
-                q.items = F;
-                q.add_div = T;
-                q.n_full = pl.n_full;
-                q.split_s = pl.split_s;
-                q.split_q = pl.split_q;
-                q.partial = h->c10part.p;
-                q.x_bias = wd + h->off_c10_b[i];
-                q.x_out = ab;
-                HIPCHK(launch_c10_finalize_bf16(q, s));
-            }
-            if (!fuse10) {   // conv10_i as a launch of its own
-                ProfScope ps(h, s, PFNL_K_CONV1X1);
-                HIPCHK(launch_conv1x1_bf16(a1, w16 + h->off16_c10[i], wd + h->off_c10_b[i], ab, B, T, H * W, 1, s));
-            }
-            {   // conv2_i, shared half (raw, once per clip)
-                ProfScope ps(h, s, PFNL_K_CONV3X3);
-                ConvBf16Params q{ab, w16 + h->off16_c2a[i], wd + h->off_zero, nullptr, nullptr, ap, H, W, B, 1, 0};
-                HIPCHK(launch_conv3x3_bf16(q, s));
-            }
-            {   // conv2_i, per-frame half + shared half + bias, lrelu, residual
-                ProfScope ps(h, s, PFNL_K_CONV3X3);
-                ConvBf16Params q{a1, w16 + h->off16_c2b[i], wd + h->off_c2_b[i], ap, a0, a0, H, W, F, T, 1};
-                q.flat = bmid ? 1 : 0;
-                q.n_full = pl.n_full;
-                q.split_s = pl.split_s;
-                q.split_q = pl.split_q;
-                if (pl.mfma == 16) q.wpack16 = w16 + h->off16_c2b_m16[i];
-                HIPCHK(launch_conv3x3_bf16(q, s));
-            }
-        }
-        h->prof_gate = h->prof_mode != 3;
-        if (h->prof_mode == 2 || h->prof_mode == 3) h->chain_open = false;
-        {   // convmerge1 (:73-74): the accumulating mode of the bf16 3x3 kernel, fp32 out for the tail
-            ProfScope ps(h, s, PFNL_K_MERGE1);
-            ConvBf16Params q{a0, w16 + h->off16_m1, wd + h->off_m1_b, nullptr, nullptr, nullptr, H, W, F, T, 1};
-            q.out_f32 = h->merge.p;
-            HIPCHK(launch_conv3x3_bf16(q, s));
-        }
-        h->merge_cstride = 64;
-        {   // model/pfnl.py:63,76-80
-            ProfScope ps(h, s, PFNL_K_TAIL);
-            HIPCHK(launch_tail(h->merge.p, in, wd + h->off_m2_w, wd + h->off_m2_b, out, B, T, Hfull, W, c.scale, 64, s, strip, rflag));
-        }
-        prof_flush_run(h, s);
-        h->chain_open = false;
-        return 0;
-    }
-
-    ConvParams p{};
-    p.H = H;
-    p.W = W;
-    p.in_cstride = 64;
-    p.chunks_per_frame = 64 / CONV_CK;
-    const int wino_groups = B * ((W + 31) / 32) * ((H + 3) / 4);   // (clip, 4x32-pixel tile) groups of conv_wino_ws
-    // the launch structure of a block: trunk_plan (conv3x3 = auto: the split-f16 kernels - persistent, 72 KB of weights per workgroup in
-    // their prologue - when a launch has enough tiles, the small-shape trunk / the Winograd f32 kernel below that)
-    const int algo = pl.algo, conv1x1_algo = pl.conv1x1_algo;
-    const bool sf = pl.sf;                                          // inp1 and base in the split format (conv_split16.h)
-    // small shapes (BASELINE.json configs[0], configs[4]): the trunk through conv_small.hip - conv2_i as the reference writes it
-    // (3x3 over concat([base, f]))
-    const bool small = pl.small;
-    if (pl.sf0 && h->inp0sf.ensure((size_t)F * P * 64)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-    if (pl.split_s && h->c10part.ensure((size_t)(pl.chains - pl.n_full) * pl.split_s * 8 * 32 * 64)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-    const uint16_t* const w16m = reinterpret_cast<const uint16_t*>(h->wdev16s.p);
-    for (int i = 0; i < (h->bf16 ? 0 : c.num_block); ++i) {   // model/pfnl.py:65-71
+    for (int i = 0; i < c.num_block; ++i) {   // model/pfnl.py:65-71
         if (h->prof_mode == 2) {          // sampled profiling: see prof_sampled; each sampled block with a fresh event chain
             h->prof_gate = prof_sampled(c.num_block, i);
             h->chain_open = false;
@@ -701,295 +952,20 @@ int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull
             h->prof_gate = i == c.num_block / 2;
             h->chain_open = false;
         }
-        if (pl.small_c10) {
-            // two launches per block: conv10_i rides in the conv1_i launch as per-frame partials (W10_t^T . inp1_t), which conv2_i's
-            // prologue adds up (+ bias, leaky-relu) into its `base` source - no 1x1 launch, no inter-workgroup traffic inside a launch
-            if (h->p10.ensure((size_t)F * P * 64)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-            {   // conv1_i (:66) + this frame's part of conv10_i (:67-68)
-                ProfScope ps(h, s, PFNL_K_CONV3X3);
-                ConvSmallParams q{nullptr, h->inp0.p, 0, 1, 1, 1, w16m + h->off16m_c1[i], wd + h->off_c1_b[i], nullptr, h->inp1.p, H, W, F, 1, 3};
-                q.x_wpack = w16m + h->off16m_c10[i];
-                q.x_out = h->p10.p;
-                q.x_T = T;
-                HIPCHK(launch_conv_small(q, s));
-            }
-            {   // conv2_i over concat([base, inp1_t]) + lrelu + residual (:69-71), base = lrelu(sum of the T partials + bias)
-                ProfScope ps(h, s, PFNL_K_CONV3X3);
-                ConvSmallParams q{h->p10.p, h->inp1.p, 1, T, 1, 2, w16m + h->off16m_c2[i], wd + h->off_c2_b[i], h->inp0.p, h->inp0.p, H, W, F, 1, 3};
-                q.a_nsum = T;
-                q.a_bias = wd + h->off_c10_b[i];
-                HIPCHK(launch_conv_small(q, s));
-            }
-            continue;
-        }
-        if (small) {
-            {   // conv1_i (:66)
-                ProfScope ps(h, s, PFNL_K_CONV3X3);
-                ConvSmallParams q{nullptr, h->inp0.p, 0, 1, 1, 1, w16m + h->off16m_c1[i], wd + h->off_c1_b[i], nullptr, h->inp1.p, H, W, F, 1, 3};
-                HIPCHK(launch_conv_small(q, s));
-            }
-            {   // conv10_i (:67-68)
-                ProfScope ps(h, s, PFNL_K_CONV1X1);
-                ConvSmallParams q{nullptr, h->inp1.p, 0, 1, T, T, w16m + h->off16m_c10[i], wd + h->off_c10_b[i], nullptr, h->base.p, H, W, B, 1, 1};
-                HIPCHK(launch_conv_small(q, s));
-            }
-            {   // conv2_i over concat([base, inp1_t]) + lrelu + residual (:69-71)
-                ProfScope ps(h, s, PFNL_K_CONV3X3);
-                ConvSmallParams q{h->base.p, h->inp1.p, 1, T, 1, 2, w16m + h->off16m_c2[i], wd + h->off_c2_b[i], h->inp0.p, h->inp0.p, H, W, F, 1, 3};
-                HIPCHK(launch_conv_small(q, s));
-            }
-            continue;
-        }
-        // MID shapes: the two-launch block deals out CHAINS (a workgroup takes the T frames of a (clip, tile), + the shared half), so a
-        // launch with fewer chains than CUs leaves most of the chip idle for T + 2 tile times (1 clip of 128x128: 64 chains - 3.06 ms
-        // for a quarter of configs[1]'s work).  Below ~0.53 chains per CU (trunk_plan) the block runs as four launches that deal out
-        // single tiles: conv1_i, conv10_i (1x1), the shared half of conv2_i, the per-frame half in flat order.
-        const bool mid = pl.mid, c10_fused = pl.c10_fused;
-        // chain2_sf0 (round 6): blocks 1 .. nb-1 read the split-format copy of inp0 the previous block's chain kernel wrote (halo by
-        // LDS-DMA); block 0 reads conv0's fp32 output, the last block writes no copy (convmerge1 reads fp32).  Bit-identical to chain2.
-        const bool in_sf0 = pl.sf0 && i > 0, out_sf0 = pl.sf0 && i + 1 < c.num_block;
-        if (c10_fused) {
-            // conv1_i AND conv10_i in one launch (conv_split16.hip, conv3x3_c1c10_kernel): per (clip, tile) the T frame tiles of conv1_i
-            // leave as split-format lines through LDS, where conv10_i picks them up as MFMA operands; inp1 is written, never read back
-            ProfScope ps(h, s, PFNL_K_CONV3X3);
-            const uint16_t* const w16s = reinterpret_cast<const uint16_t*>(h->wdev16s.p);
-            ConvSplitParams q{in_sf0 ? h->inp0sf.p : h->inp0.p, w16s + h->off16s_c1[i], wd + h->off_c1_b[i], nullptr, nullptr, h->inp1.p, H, W, F, T, 1};
-            q.in_sf = in_sf0 ? 1 : 0;
-            q.wpack2 = w16s + h->off16s_c10f[i];
-            q.bias2 = wd + h->off_c10_b[i];
-            q.out2 = h->base.p;
-            q.n_full = pl.n_full;
-            q.split_s = pl.split_s;
-            q.split_q = pl.split_q;
-            q.partial = pl.split_s ? h->c10part.p : nullptr;
-            HIPCHK(launch_conv3x3_c1c10(q, s));
-        }
-        if (c10_fused && pl.split_s) {   // split chains: the parts' raw conv10_i sums -> base (+ leaky-relu, split format) for the chains that were cut
-            ProfScope ps(h, s, PFNL_K_CONV1X1);
-            ConvSplitParams q{};
-            q.H = H;
-            q.W = W;
-            q.items = F;
-            q.add_div = T;
-            q.act = 1;
-            q.n_full = pl.n_full;
-            q.split_s = pl.split_s;
-            q.split_q = pl.split_q;
-            q.partial = h->c10part.p;
-            q.out2 = h->base.p;
-            HIPCHK(launch_c10_finalize(q, s));
-        }
-        if (!c10_fused) {   // conv1_i: per frame 3x3 64->64 + lrelu                       (:66)
-            ProfScope ps(h, s, PFNL_K_CONV3X3);
-            p.in = h->inp0.p;
-            p.wpack = wd + h->off_c1_w[i];
-            p.bias = wd + h->off_c1_b[i];
-            p.addend = nullptr;
-            p.resid = nullptr;
-            p.out = h->inp1.p;
-            p.out_cstride = 64;
-            p.cout = 64;
-            p.frames_per_item = 1;
-            p.nchunks = p.chunks_per_frame;
-            p.add_div = 1;
-            p.act = 1;
-            if (algo == 4) {
-                ConvSplitParams q{p.in, reinterpret_cast<const uint16_t*>(h->wdev16s.p) + h->off16s_c1[i], p.bias, nullptr, nullptr, p.out, H, W, F, 1, 1};
-                q.out_sf = sf ? 1 : 0;                              // inp1 in the split format: it only feeds conv10_i and conv2_i's MFMA operands
-                HIPCHK(launch_conv3x3_split16(q, s));
-            } else if (algo == 1 || algo == 3) {
-                WinoParams wp{p.in, wd + h->off_c1_u[i], p.bias, nullptr, nullptr, p.out, H, W, 1, 1, F, nullptr};
-                HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
-            } else {
-                HIPCHK(launch_conv_mfma(p, 3, F, s));
-            }
-        }
-        if (!c10_fused) {   // conv10_i: 1x1 over the concat of T frames -> base + lrelu    (:67-68)
-            ProfScope ps(h, s, PFNL_K_CONV1X1);
-            p.in = h->inp1.p;
-            p.wpack = wd + h->off_c10_w[i];
-            p.bias = wd + h->off_c10_b[i];
-            p.out = h->base.p;
-            p.frames_per_item = T;
-            p.nchunks = T * p.chunks_per_frame;
-            if (conv1x1_algo == 2)
-                HIPCHK(launch_conv1x1_split16(p.in, reinterpret_cast<const uint16_t*>(h->wdev16s.p) + h->off16s_c10[i], p.bias, p.out, B, T, H * W, 1, s, sf, sf));
-            else if (conv1x1_algo == 1)
-                HIPCHK(launch_conv1x1_stream(p.in, wd + h->off_c10_s[i], p.bias, p.out, B, T, H * W, 1, s));
-            else
-                HIPCHK(launch_conv_mfma(p, 1, B, s));
-        }
-        // grouped / accumulating modes chain T(+1) units inside one workgroup: only worth it when there are enough
-        // (clip, tile) groups to occupy the chip (below ~220 the split launches finish sooner)
-        if (pl.conv2_grouped) {
-            // the whole of conv2_i in one launch: per (clip, tile) the shared half stays in LDS (conv_wino_ws MODE 2)
-            ProfScope ps(h, s, PFNL_K_CONV3X3);
-            WinoParams wp{};
-            wp.in = h->inp1.p;
-            wp.in2 = h->base.p;
-            wp.upack = wd + h->off_c2b_u[i];
-            wp.upack2 = wd + h->off_c2a_u[i];
-            wp.bias = wd + h->off_c2_b[i];
-            wp.resid = h->inp0.p;
-            wp.out = h->inp0.p;
-            wp.H = H;
-            wp.W = W;
-            wp.add_div = T;
-            wp.act = 1;
-            wp.items = F;
-            HIPCHK(launch_conv_wino_ws(wp, s));
-            continue;
-        }
-        if (pl.chain) {
-            // the whole of conv2_i in one launch (conv_sf.hip, conv3x3_sf_chain_kernel): per (clip, tile) the shared half stays in
-            // registers as the initial C of the T frame tiles; in place on inp0 (residual)
-            ProfScope ps(h, s, PFNL_K_CONV3X3);
-            const uint16_t* const w16s = reinterpret_cast<const uint16_t*>(h->wdev16s.p);
-            ConvSplitParams q{h->inp1.p, w16s + h->off16s_c2b_sf[i], wd + h->off_c2_b[i], nullptr, h->inp0.p, h->inp0.p, H, W, F, T, 1};
-            q.in2 = h->base.p;
-            q.wpack2 = w16s + h->off16s_c2a_sf[i];
-            q.out2 = out_sf0 ? h->inp0sf.p : nullptr;
-            q.n_full = pl.n_full;
-            q.split_s = pl.split_s;
-            q.split_q = pl.split_q;
-            if (pl.mfma == 16) {                                    // (trunk_plan: whole rounds with a chain per CU)
-                q.wpack_m16 = w16s + h->off16s_c2b_m16[i];
-                q.wpack2_m16 = w16s + h->off16s_c2a_m16[i];
-            }
-            HIPCHK(launch_conv3x3_sf_chain(q, s));
-            continue;
-        }
-        {   // conv2_i, shared half: 3x3 over `base` (kernel rows 0..63), once per clip, raw
-            ProfScope ps(h, s, PFNL_K_CONV3X3);
-            p.in = h->base.p;
-            p.wpack = wd + h->off_c2a_w[i];
-            p.bias = wd + h->off_zero;
-            p.out = h->pb.p;
-            p.frames_per_item = 1;
-            p.nchunks = p.chunks_per_frame;
-            p.act = 0;
-            if (algo == 4) {
-                ConvSplitParams q{p.in, reinterpret_cast<const uint16_t*>(h->wdev16s.p) + (sf ? h->off16s_c2a_sf[i] : h->off16s_c2a[i]), p.bias, nullptr, nullptr, p.out, H, W, B, 1, 0};
-                HIPCHK(sf ? launch_conv3x3_sf(q, s) : launch_conv3x3_split16(q, s));
-            } else if (algo == 1 || algo == 3) {
-                WinoParams wp{p.in, wd + h->off_c2a_u[i], p.bias, nullptr, nullptr, p.out, H, W, 1, 0, B, nullptr};
-                HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
-            } else {
-                HIPCHK(launch_conv_mfma(p, 3, B, s));
-            }
-        }
-        {   // conv2_i, per-frame half (kernel rows 64..127) + shared half + bias, lrelu, residual (:69-71)
-            ProfScope ps(h, s, PFNL_K_CONV3X3);
-            p.in = h->inp1.p;
-            p.wpack = wd + h->off_c2b_w[i];
-            p.bias = wd + h->off_c2_b[i];
-            p.addend = h->pb.p;
-            p.add_div = T;
-            p.resid = h->inp0.p;
-            p.out = h->inp0.p;
-            p.act = 1;
-            if (algo == 4) {
-                ConvSplitParams q{p.in, reinterpret_cast<const uint16_t*>(h->wdev16s.p) + (sf ? h->off16s_c2b_sf[i] : h->off16s_c2b[i]), p.bias, p.addend, p.resid, p.out, H, W, F, T, 1};
-                q.flat = mid ? 1 : 0;
-                HIPCHK(sf ? launch_conv3x3_sf(q, s) : launch_conv3x3_split16(q, s));
-            } else if (algo == 1 || algo == 3) {
-                WinoParams wp{p.in, wd + h->off_c2b_u[i], p.bias, p.addend, p.resid, p.out, H, W, T, 1, F, nullptr};
-                HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
-            } else {
-                HIPCHK(launch_conv_mfma(p, 3, F, s));
-            }
-        }
+        const BlockPacks& k = h->blocks[i];
+        const int e = pl.bf16 ? block_bf16(f, k) : pl.small ? block_small(f, k) : block_fp32(f, k, i == 0, i + 1 == c.num_block);
+        if (e) return e;
     }
     h->prof_gate = h->prof_mode != 3;
     if (h->prof_mode == 2 || h->prof_mode == 3) h->chain_open = false;
-    if (small && !h->bf16) {   // convmerge1 (:73-74): T sources, cout 48 zero-padded to 64
-        {
-            ProfScope ps(h, s, PFNL_K_MERGE1);
-            ConvSmallParams q{nullptr, merge_in, 0, 1, T, T, w16m + h->off16m_m1, wd + h->off_m1_b, nullptr, h->merge.p, H, W, B, 1, 3};
-            HIPCHK(launch_conv_small(q, s));
-        }
-        h->merge_cstride = 64;
-        {   // model/pfnl.py:63,76-80
-            ProfScope ps(h, s, PFNL_K_TAIL);
-            HIPCHK(launch_tail(h->merge.p, in, wd + h->off_m2_w, wd + h->off_m2_b, out, B, T, Hfull, W, c.scale, 64, s, strip, rflag));
-        }
-        prof_flush_run(h, s);
-        h->chain_open = false;
-        h->prof_gate = h->prof_mode != 3;
-        return 0;
-    }
-    const bool m1_s16 = algo == 4 && h->m1_algo != 2 && (long long)H * W * 256 < 0x7fffffffLL;
-    const bool m1_wino = !m1_s16 && (algo == 3 || algo == 4) && wino_groups >= 224 && (long long)H * W * 256 < 0x7fffffffLL;
-    const int mstride = (m1_wino || m1_s16) ? 64 : 48;
-    h->merge_cstride = mstride;
-    if (m1_s16) {
-        // convmerge1 (:73-74) on the f16 pipe: the accumulating mode of conv3x3_split16_kernel (the T frame tiles of a clip run
-        // through the same accumulators, every unit with its own weights; cout zero-padded to 64; one epilogue per clip tile)
-        {
-            ProfScope ps(h, s, PFNL_K_MERGE1);
-            ConvSplitParams q{merge_in, reinterpret_cast<const uint16_t*>(h->wdev16s.p) + h->off16s_m1, wd + h->off_m1_b, nullptr, nullptr,
-                              h->merge.p, H, W, F, T, 1, 1};
-            // split chains (trunk_plan): convmerge1's chains are the trunk's - the same last, partial round is cut by frames, the parts' raw sums
-            // meet in c10_finalize_kernel (+ bias, leaky-relu); c10part is free behind the last block
-            q.n_full = pl.n_full;
-            q.split_s = pl.split_s;
-            q.split_q = pl.split_q;
-            q.partial = pl.split_s ? h->c10part.p : nullptr;
-            HIPCHK(launch_conv3x3_split16(q, s));
-        }
-        if (pl.split_s) {
-            ProfScope ps(h, s, PFNL_K_MERGE1);
-            ConvSplitParams f{};
-            f.H = H;
-            f.W = W;
-            f.items = F;
-            f.add_div = T;
-            f.act = 1;
-            f.n_full = pl.n_full;
-            f.split_s = pl.split_s;
-            f.split_q = pl.split_q;
-            f.partial = h->c10part.p;
-            f.bias = wd + h->off_m1_b;
-            f.out = h->merge.p;
-            HIPCHK(launch_c10_finalize(f, s));
-        }
-    } else if (m1_wino) {
-        // convmerge1 (:73-74) = sum over the T frames of a 3x3 64->48 convolution: one launch of the persistent
-        // Winograd kernel in its accumulating mode (cout zero-padded to 64; the T frame tiles of a clip add into
-        // the same accumulators, one epilogue per clip tile)
-        ProfScope ps(h, s, PFNL_K_MERGE1);
-        WinoParams wp{};
-        wp.in = merge_in;
-        wp.upack = wd + h->off_m1_u[0];
-        wp.upack_stride = T > 1 ? (long long)(h->off_m1_u[1] - h->off_m1_u[0]) : 0;
-        wp.accum = 1;
-        wp.bias = wd + h->off_m1_b;
-        wp.out = h->merge.p;
-        wp.H = H;
-        wp.W = W;
-        wp.items = F;
-        wp.add_div = T;
-        wp.act = 1;
-        HIPCHK(launch_conv_wino_ws(wp, s));
-    } else {   // convmerge1: 3x3 over the concat of T frames -> 48 + lrelu        (:73-74)
-        ProfScope ps(h, s, PFNL_K_MERGE1);
-        p.in = merge_in;
-        p.wpack = wd + h->off_m1_w;
-        p.bias = wd + h->off_m1_b;
-        p.addend = nullptr;
-        p.resid = nullptr;
-        p.out = h->merge.p;
-        p.out_cstride = 48;
-        p.cout = 48;
-        p.frames_per_item = T;
-        p.nchunks = T * p.chunks_per_frame;
-        p.add_div = 1;
-        p.act = 1;
-        HIPCHK(launch_conv_mfma(p, 3, B, s));
-    }
+    if (int e = convmerge1(f)) return e;
     {   // model/pfnl.py:63,76-80
+        // The range fence is armed only when a kernel with a binary16 DOMAIN runs (fp32 precision off the strict path: split-f16 trunk,
+        // non-local block and conv0; bf16 precision: its non-local block and conv0) and a non-finite value cannot be the reference's
+        // own result (nltype 2 divides 0 by 0 for a query without a positive affinity, utils.py:59-62).
+        unsigned* const rflag = (pl.strict || pl.nltype == 2) ? nullptr : h->rflag_dev + flag_slot;
         ProfScope ps(h, s, PFNL_K_TAIL);
-        HIPCHK(launch_tail(h->merge.p, in, wd + h->off_m2_w, wd + h->off_m2_b, out, B, T, Hfull, W, c.scale, mstride, s, strip, rflag));
+        HIPCHK(launch_tail(h->merge.p, in, wd + h->off_m2_w, wd + h->off_m2_b, out, B, T, Hfull, W, c.scale, pl.merge_stride, s, strip, rflag));
     }
     prof_flush_run(h, s);
     h->chain_open = false;
@@ -1117,6 +1093,7 @@ int pfnl_create(const pfnl_config* cfg, pfnl_handle** out) {
     HIPCHK(hipSetDevice(cfg->device_id));
     pfnl_handle* h = new pfnl_handle();
     h->cfg = *cfg;
+    h->ncu = pfnl::device_cu_count();
     if (const char* e = std::getenv("PFNL_SMALL")) h->small_mode = std::string(e) == "on" ? 1 : (std::string(e) == "off" ? 2 : 0);   // (A/B runs)
     if (const char* e = std::getenv("PFNL_SMALL_C10")) h->small_c10 = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
     if (const char* e = std::getenv("PFNL_SF_CHAIN")) h->sf_chain = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
@@ -1307,32 +1284,23 @@ int pfnl_finalize_weights(pfnl_handle* h) {
     h->off_conv0_w = reserve(75 * 64);
     std::memcpy(&blob[h->off_conv0_w], W("conv0").data(), 75 * 64 * sizeof(float));
     h->off_conv0_b = put_bias(Bv("conv0"));
-    h->off_c1_w.assign(nb, 0);
-    h->off_c1_b.assign(nb, 0);
-    h->off_c10_w.assign(nb, 0);
-    h->off_c10_b.assign(nb, 0);
-    h->off_c10_s.assign(nb, 0);
-    h->off_c2a_w.assign(nb, 0);
-    h->off_c2b_w.assign(nb, 0);
-    h->off_c2_b.assign(nb, 0);
-    h->off_c1_u.assign(nb, 0);
-    h->off_c2a_u.assign(nb, 0);
-    h->off_c2b_u.assign(nb, 0);
+    h->blocks.assign(nb, BlockPacks{});
     for (int i = 0; i < nb; ++i) {
         const std::string s = std::to_string(i);
-        h->off_c1_w[i] = put_pack(W("conv1_" + s), 3, 64, 0, 64, 64);
-        h->off_c1_b[i] = put_bias(Bv("conv1_" + s));
-        h->off_c10_w[i] = put_pack(W("conv10_" + s), 1, 64 * T, 0, 64 * T, 64);
-        h->off_c10_b[i] = put_bias(Bv("conv10_" + s));
-        h->off_c10_s[i] = reserve(pfnl::conv1x1_pack_floats(T));
-        pfnl::conv1x1_pack_weights(W("conv10_" + s).data(), T, &blob[h->off_c10_s[i]]);
+        BlockPacks& k = h->blocks[i];
+        k.c1_w = put_pack(W("conv1_" + s), 3, 64, 0, 64, 64);
+        k.c1_b = put_bias(Bv("conv1_" + s));
+        k.c10_w = put_pack(W("conv10_" + s), 1, 64 * T, 0, 64 * T, 64);
+        k.c10_b = put_bias(Bv("conv10_" + s));
+        k.c10_s = reserve(pfnl::conv1x1_pack_floats(T));
+        pfnl::conv1x1_pack_weights(W("conv10_" + s).data(), T, &blob[k.c10_s]);
         // conv2_i input = concat([base, inp1_t]) (model/pfnl.py:69): rows 0..63 see `base`.
-        h->off_c2a_w[i] = put_pack(W("conv2_" + s), 3, 128, 0, 64, 64);
-        h->off_c2b_w[i] = put_pack(W("conv2_" + s), 3, 128, 64, 64, 64);
-        h->off_c2_b[i] = put_bias(Bv("conv2_" + s));
-        h->off_c1_u[i] = put_wino(W("conv1_" + s), 64, 0);
-        h->off_c2a_u[i] = put_wino(W("conv2_" + s), 128, 0);
-        h->off_c2b_u[i] = put_wino(W("conv2_" + s), 128, 64);
+        k.c2a_w = put_pack(W("conv2_" + s), 3, 128, 0, 64, 64);
+        k.c2b_w = put_pack(W("conv2_" + s), 3, 128, 64, 64, 64);
+        k.c2_b = put_bias(Bv("conv2_" + s));
+        k.c1_u = put_wino(W("conv1_" + s), 64, 0);
+        k.c2a_u = put_wino(W("conv2_" + s), 128, 0);
+        k.c2b_u = put_wino(W("conv2_" + s), 128, 64);
     }
     h->off_m1_w = put_pack(W("convmerge1"), 3, 64 * T, 0, 64 * T, 48);
     h->off_m1_b = put_bias(Bv("convmerge1"));
@@ -1373,26 +1341,21 @@ int pfnl_finalize_weights(pfnl_handle* h) {
             b16.resize(off + n, 0);
             return off;
         };
-        h->off16_c1.assign(nb, 0);
-        h->off16_c10.assign(nb, 0);
-        h->off16_c2a.assign(nb, 0);
-        h->off16_c2b.assign(nb, 0);
-        h->off16_c1_m16.assign(nb, 0);
-        h->off16_c2b_m16.assign(nb, 0);
         for (int i = 0; i < nb; ++i) {
             const std::string s = std::to_string(i);
-            h->off16_c1[i] = reserve16(pfnl::conv3x3_bf16_pack_halfs());
-            pfnl::conv3x3_bf16_pack_weights(W("conv1_" + s).data(), 64, 0, &b16[h->off16_c1[i]]);
-            h->off16_c10[i] = reserve16(pfnl::conv1x1_bf16_pack_halfs(T));
-            pfnl::conv1x1_bf16_pack_weights(W("conv10_" + s).data(), T, &b16[h->off16_c10[i]]);
-            h->off16_c2a[i] = reserve16(pfnl::conv3x3_bf16_pack_halfs());
-            pfnl::conv3x3_bf16_pack_weights(W("conv2_" + s).data(), 128, 0, &b16[h->off16_c2a[i]]);
-            h->off16_c2b[i] = reserve16(pfnl::conv3x3_bf16_pack_halfs());
-            pfnl::conv3x3_bf16_pack_weights(W("conv2_" + s).data(), 128, 64, &b16[h->off16_c2b[i]]);
-            h->off16_c1_m16[i] = reserve16(pfnl::conv3x3_bf16_pack_halfs());
-            pfnl::conv3x3_bf16_pack_weights16(W("conv1_" + s).data(), 64, 0, &b16[h->off16_c1_m16[i]]);
-            h->off16_c2b_m16[i] = reserve16(pfnl::conv3x3_bf16_pack_halfs());
-            pfnl::conv3x3_bf16_pack_weights16(W("conv2_" + s).data(), 128, 64, &b16[h->off16_c2b_m16[i]]);
+            BlockPacks& k = h->blocks[i];
+            k.bf_c1 = reserve16(pfnl::conv3x3_bf16_pack_halfs());
+            pfnl::conv3x3_bf16_pack_weights(W("conv1_" + s).data(), 64, 0, &b16[k.bf_c1]);
+            k.bf_c10 = reserve16(pfnl::conv1x1_bf16_pack_halfs(T));
+            pfnl::conv1x1_bf16_pack_weights(W("conv10_" + s).data(), T, &b16[k.bf_c10]);
+            k.bf_c2a = reserve16(pfnl::conv3x3_bf16_pack_halfs());
+            pfnl::conv3x3_bf16_pack_weights(W("conv2_" + s).data(), 128, 0, &b16[k.bf_c2a]);
+            k.bf_c2b = reserve16(pfnl::conv3x3_bf16_pack_halfs());
+            pfnl::conv3x3_bf16_pack_weights(W("conv2_" + s).data(), 128, 64, &b16[k.bf_c2b]);
+            k.bf_c1_m16 = reserve16(pfnl::conv3x3_bf16_pack_halfs());
+            pfnl::conv3x3_bf16_pack_weights16(W("conv1_" + s).data(), 64, 0, &b16[k.bf_c1_m16]);
+            k.bf_c2b_m16 = reserve16(pfnl::conv3x3_bf16_pack_halfs());
+            pfnl::conv3x3_bf16_pack_weights16(W("conv2_" + s).data(), 128, 64, &b16[k.bf_c2b_m16]);
         }
         h->off16_m1 = reserve16((size_t)T * pfnl::conv3x3_bf16_pack_halfs());
         for (int f = 0; f < T; ++f)
@@ -1405,22 +1368,10 @@ int pfnl_finalize_weights(pfnl_handle* h) {
     {   // split-f16 packs of the 3x3 64->64 kernels (conv3x3=split16)
         std::vector<uint16_t> b16;
         const size_t n3 = pfnl::conv3x3_split16_pack_halfs(), n1 = pfnl::conv1x1_split16_pack_halfs(T);
-        h->off16s_c1.assign(nb, 0);
-        h->off16s_c2a.assign(nb, 0);
-        h->off16s_c2b.assign(nb, 0);
-        h->off16s_c10.assign(nb, 0);
-        h->off16s_c2a_sf.assign(nb, 0);
-        h->off16s_c2b_sf.assign(nb, 0);
-        h->off16s_c2a_m16.assign(nb, 0);
-        h->off16s_c2b_m16.assign(nb, 0);
         const size_t blk = 7 * n3 + n1 + pfnl::conv1x1_c10_pack_halfs(T);   // (5 packs of the 32x32x16 kernels + 2 of the 16x16x32 chain kernel)
-        h->off16s_c10f.assign(nb, 0);
         h->off16s_m1 = (size_t)nb * blk;
         const size_t m3 = pfnl::conv_small_pack_halfs(3, 1), m10 = pfnl::conv_small_pack_halfs(1, T);
         const size_t small_base = (size_t)nb * blk + (size_t)T * n3;
-        h->off16m_c1.assign(nb, 0);
-        h->off16m_c10.assign(nb, 0);
-        h->off16m_c2.assign(nb, 0);
         h->off16m_m1 = small_base + (size_t)nb * (3 * m3 + m10);
         b16.resize(h->off16m_m1 + (size_t)T * m3 + 2, 0);
         pfnl::conv_small_pack_weights(W("convmerge1").data(), 3, T, 48, &b16[h->off16m_m1]);
@@ -1428,30 +1379,31 @@ int pfnl_finalize_weights(pfnl_handle* h) {
             pfnl::conv3x3_split16_pack_weights(W("convmerge1").data(), 64 * T, 64 * f, &b16[h->off16s_m1 + (size_t)f * n3], 48);
         for (int i = 0; i < nb; ++i) {
             const std::string s = std::to_string(i);
-            h->off16s_c1[i] = (size_t)i * blk;
-            h->off16s_c2a[i] = h->off16s_c1[i] + n3;
-            h->off16s_c2b[i] = h->off16s_c1[i] + 2 * n3;
-            h->off16s_c10[i] = h->off16s_c1[i] + 3 * n3;
-            h->off16s_c2a_sf[i] = h->off16s_c10[i] + n1;
-            h->off16s_c2b_sf[i] = h->off16s_c2a_sf[i] + n3;
-            h->off16s_c10f[i] = h->off16s_c2b_sf[i] + n3;
-            h->off16s_c2a_m16[i] = h->off16s_c10f[i] + pfnl::conv1x1_c10_pack_halfs(T);
-            h->off16s_c2b_m16[i] = h->off16s_c2a_m16[i] + n3;
-            pfnl::conv3x3_split16_pack_weights16(W("conv2_" + s).data(), 128, 0, &b16[h->off16s_c2a_m16[i]]);
-            pfnl::conv3x3_split16_pack_weights16(W("conv2_" + s).data(), 128, 64, &b16[h->off16s_c2b_m16[i]]);
-            pfnl::conv1x1_c10_pack_weights(W("conv10_" + s).data(), T, &b16[h->off16s_c10f[i]]);
-            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 0, &b16[h->off16s_c2a_sf[i]], 64, true);
-            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 64, &b16[h->off16s_c2b_sf[i]], 64, true);
-            h->off16m_c1[i] = small_base + (size_t)i * (3 * m3 + m10);
-            h->off16m_c2[i] = h->off16m_c1[i] + m3;
-            h->off16m_c10[i] = h->off16m_c1[i] + 3 * m3;
-            pfnl::conv_small_pack_weights(W("conv1_" + s).data(), 3, 1, 64, &b16[h->off16m_c1[i]]);
-            pfnl::conv_small_pack_weights(W("conv2_" + s).data(), 3, 2, 64, &b16[h->off16m_c2[i]]);
-            pfnl::conv_small_pack_weights(W("conv10_" + s).data(), 1, T, 64, &b16[h->off16m_c10[i]]);
-            pfnl::conv1x1_split16_pack_weights(W("conv10_" + s).data(), T, &b16[h->off16s_c10[i]]);
-            pfnl::conv3x3_split16_pack_weights(W("conv1_" + s).data(), 64, 0, &b16[h->off16s_c1[i]]);
-            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 0, &b16[h->off16s_c2a[i]]);
-            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 64, &b16[h->off16s_c2b[i]]);
+            BlockPacks& k = h->blocks[i];
+            k.s_c1 = (size_t)i * blk;
+            k.s_c2a = k.s_c1 + n3;
+            k.s_c2b = k.s_c1 + 2 * n3;
+            k.s_c10 = k.s_c1 + 3 * n3;
+            k.s_c2a_sf = k.s_c10 + n1;
+            k.s_c2b_sf = k.s_c2a_sf + n3;
+            k.s_c10f = k.s_c2b_sf + n3;
+            k.s_c2a_m16 = k.s_c10f + pfnl::conv1x1_c10_pack_halfs(T);
+            k.s_c2b_m16 = k.s_c2a_m16 + n3;
+            pfnl::conv3x3_split16_pack_weights16(W("conv2_" + s).data(), 128, 0, &b16[k.s_c2a_m16]);
+            pfnl::conv3x3_split16_pack_weights16(W("conv2_" + s).data(), 128, 64, &b16[k.s_c2b_m16]);
+            pfnl::conv1x1_c10_pack_weights(W("conv10_" + s).data(), T, &b16[k.s_c10f]);
+            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 0, &b16[k.s_c2a_sf], 64, true);
+            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 64, &b16[k.s_c2b_sf], 64, true);
+            k.sm_c1 = small_base + (size_t)i * (3 * m3 + m10);
+            k.sm_c2 = k.sm_c1 + m3;
+            k.sm_c10 = k.sm_c1 + 3 * m3;
+            pfnl::conv_small_pack_weights(W("conv1_" + s).data(), 3, 1, 64, &b16[k.sm_c1]);
+            pfnl::conv_small_pack_weights(W("conv2_" + s).data(), 3, 2, 64, &b16[k.sm_c2]);
+            pfnl::conv_small_pack_weights(W("conv10_" + s).data(), 1, T, 64, &b16[k.sm_c10]);
+            pfnl::conv1x1_split16_pack_weights(W("conv10_" + s).data(), T, &b16[k.s_c10]);
+            pfnl::conv3x3_split16_pack_weights(W("conv1_" + s).data(), 64, 0, &b16[k.s_c1]);
+            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 0, &b16[k.s_c2a]);
+            pfnl::conv3x3_split16_pack_weights(W("conv2_" + s).data(), 128, 64, &b16[k.s_c2b]);
         }
         h->wdev16s_used = b16.size() / 2;
         if (h->wdev16s.ensure(b16.size() / 2)) return fail(PFNL_ERR_NOMEM, "weight allocation failed");
@@ -1487,12 +1439,8 @@ int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes) {
     if (h->bf16 || h->nl_algo != 0) f += (pfnl::nl_f16_scratch_halfs(B, (int)N) + 1) / 2;   // split K / V^T operands (bf16 or f16)
     if (h->nl_theta) f += (size_t)B * N * CP;                   // projected queries (nltype 0 / 2)
     if (h->nl_sub > 1) f += (size_t)B * ((H / 2) / h->nl_sub) * ((W / 2) / h->nl_sub) * CP;   // pooled keys
-    {   // buffers that depend on the launch plan: the small-shape trunk's conv10_i partials; the split-format copy of inp0
-        const TrunkPlan pl = trunk_plan(h, B, H, W);
-        if (pl.small_c10) f += B * T * P * 64;
-        if (pl.sf0) f += B * T * P * 64;
-        if (pl.split_s) f += (size_t)(pl.chains - pl.n_full) * pl.split_s * 8 * 32 * 64;
-    }
+    const TrunkPlan pl = trunk_plan(h, B, H, W, H);
+    f += pl.p10_floats + pl.inp0sf_floats + pl.c10part_floats;   // the buffers that depend on the launch plan
     *bytes = f * sizeof(float);
     return 0;
 }
@@ -1500,22 +1448,22 @@ int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes) {
 int pfnl_plan(pfnl_handle* h, int B, int H, int W, char* buf, size_t buflen) {
     if (!h || !buf || buflen < 1) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "bad shape");
-    const TrunkPlan pl = trunk_plan(h, B, H, W);
-    const int N = (H / 2) * (W / 2), nlf = nl_family(h, N);
+    const TrunkPlan pl = trunk_plan(h, B, H, W, H);
     static const char* const nln[] = {"general_f32", "split16", "f16", "f32"};
-    const int nl_fused = (nlf == 1 || nlf == 2) && pfnl::nl_f16_fits_one_launch(B, N);
     static const char* const a3[] = {"direct", "winograd_tile", "?", "winograd", "split16"};
     static const char* const a1[] = {"tiled", "stream", "split16"};
     char tmp[384];
     if (pl.bf16)
-        std::snprintf(tmp, sizeof tmp, "%s launches_per_block=%d c1x1=%d precision=bf16 tiles=%d chains=%d whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d",
-                      pl.name, pl.launches_per_block, pl.c1x1_launches, pl.tiles8x32, pl.chains, pl.split_s ? pl.n_full : pl.chains, pl.split_s, pl.split_q, nln[nlf], nl_fused, pl.mfma);
+        std::snprintf(tmp, sizeof tmp, "%s launches_per_block=%d c1x1=%d precision=bf16 tiles=%d chains=%d whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d merge1=%s",
+                      pl.name, pl.launches_per_block, pl.c1x1_launches, pl.tiles8x32, pl.chains, pl.split_s ? pl.n_full : pl.chains, pl.split_s, pl.split_q,
+                      nln[pl.nl_family], pl.nl_fused_pack ? 1 : 0, pl.mfma, kMerge1Names[pl.merge1]);
     else
         std::snprintf(tmp, sizeof tmp, "%s launches_per_block=%d c1x1=%d precision=fp32 conv3x3=%s conv1x1=%s c10_fused=%d chain=%d sf0=%d strict=%d tiles=%d chains=%d "
-                      "whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d",
+                      "whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d merge1=%s",
                       pl.name, pl.launches_per_block, pl.c1x1_launches, pl.small ? "small" : a3[pl.algo < 0 || pl.algo > 4 ? 2 : pl.algo],
                       a1[pl.conv1x1_algo < 0 || pl.conv1x1_algo > 2 ? 0 : pl.conv1x1_algo], pl.c10_fused ? 1 : 0, pl.chain ? 1 : 0, pl.sf0 ? 1 : 0,
-                      pl.strict ? 1 : 0, pl.tiles8x32, pl.chains, pl.split_s ? pl.n_full : pl.chains, pl.split_s, pl.split_q, nln[nlf], nl_fused, pl.mfma);
+                      pl.strict ? 1 : 0, pl.tiles8x32, pl.chains, pl.split_s ? pl.n_full : pl.chains, pl.split_s, pl.split_q, nln[pl.nl_family],
+                      pl.nl_fused_pack ? 1 : 0, pl.mfma, kMerge1Names[pl.merge1]);
     if (std::strlen(tmp) + 1 > buflen) return fail(PFNL_ERR_INVALID, "buffer too small");
     std::strcpy(buf, tmp);
     return 0;

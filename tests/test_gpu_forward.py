@@ -771,25 +771,29 @@ def test_split_chains_random_geometries():
 
 def test_plan_is_what_runs():
     """pfnl_plan is the ONE statement of the trunk's dispatch rule (capi.hip trunk_plan; reference model/pfnl.py:65-71): for every structure
-    the launches the profiler counts per block equal the plan's, in both precisions and under the options that change it; the thresholds
-    it prints (tiles, chains) are the shape's; pfnl_get_option reads back what set_option / the defaults put there."""
+    the launches the profiler counts per block equal the plan's, in both precisions and under the options that change it, and so do convmerge1's
+    algorithm (merge1) and its launches; the thresholds it prints (tiles, chains) are the shape's; pfnl_get_option reads back what set_option / the defaults put there."""
     geom = PFNLGeometry(num_block=2)
     w = synth.synthetic_weights(geom, seed=0)
     eng = _engine_with(geom, w)
-    cases = [((1, 32, 32), {}, "small2"), ((1, 32, 32), {"small_c10": "off"}, "small3"), ((1, 128, 128), {}, "mid4"),
-             ((1, 128, 128), {"split16_mid": "off"}, "chain2"), ((3, 128, 128), {}, "chain2"), ((3, 128, 128), {"split16_sf0": "on"}, "chain2_sf0"),
-             ((3, 128, 128), {"split16_c10": "off"}, "split16_3"), ((3, 128, 128), {"split16_chain": "off"}, "split16_3"),
-             ((3, 128, 128), {"split16_sf": "off"}, "split16_4"), ((3, 128, 128), {"strict_fp32": "on"}, "winograd_ws3"),
-             ((1, 64, 64), {"conv3x3": "direct", "conv1x1": "tiled", "small": "off"}, "direct4"),
-             ((3, 128, 128), {"precision": "bf16"}, "bf16_3"), ((1, 128, 128), {"precision": "bf16"}, "bf16_mid4"),
-             ((3, 128, 128), {"precision": "bf16", "bf16_conv10": "separate"}, "bf16_4")]
-    for (B, H, W), opts, want in cases:
+    cases = [((1, 32, 32), {}, "small2", "small"), ((1, 32, 32), {"small_c10": "off"}, "small3", "small"), ((1, 128, 128), {}, "mid4", "split16"),
+             ((1, 128, 128), {"split16_mid": "off"}, "chain2", "split16"), ((3, 128, 128), {}, "chain2", "split16"),
+             ((5, 128, 128), {}, "chain2_split", "split16_cut"), ((3, 128, 128), {"merge1": "winograd"}, "chain2", "winograd"),
+             ((3, 128, 128), {"split16_sf0": "on"}, "chain2_sf0", "split16"), ((3, 128, 128), {"split16_c10": "off"}, "split16_3", "split16"),
+             ((3, 128, 128), {"split16_chain": "off"}, "split16_3", "split16"), ((3, 128, 128), {"split16_sf": "off"}, "split16_4", "split16"),
+             ((3, 128, 128), {"strict_fp32": "on"}, "winograd_ws3", "winograd"),
+             ((1, 64, 64), {"conv3x3": "direct", "conv1x1": "tiled", "small": "off"}, "direct4", "direct"),
+             ((1, 64, 64), {"conv3x3": "winograd", "small": "off"}, "winograd_ws4", "direct"),
+             ((3, 128, 128), {"precision": "bf16"}, "bf16_3", "bf16"), ((5, 128, 128), {"precision": "bf16"}, "bf16_3_split", "bf16"),
+             ((1, 128, 128), {"precision": "bf16"}, "bf16_mid4", "bf16"), ((3, 128, 128), {"precision": "bf16", "bf16_conv10": "separate"}, "bf16_4", "bf16")]
+    for (B, H, W), opts, want, merge1 in cases:
         before = {k: eng.get_option(k) for k in opts}
         for k, v in opts.items():
             eng.set_option(k, v)
             assert eng.get_option(k) == v
         pl = eng.plan(B, H, W)
         assert pl["structure"] == want, (B, H, W, opts, pl)
+        assert pl["merge1"] == merge1, (B, H, W, opts, pl)
         assert pl["tiles"] == B * 7 * ((W + 31) // 32) * ((H + 7) // 8) and pl["chains"] == pl["tiles"] // 7
         x = synth.uniform_clips(B, 7, H, W, seed=3)
         eng.profile(1)
@@ -798,6 +802,7 @@ def test_plan_is_what_runs():
         p = eng.profile_read()
         eng.profile(0)
         assert p["conv3x3"]["launches"] + p["conv1x1"]["launches"] == pl["launches_per_block"] * 2, (want, p, pl)
+        assert p["merge1"]["launches"] == (2 if merge1 == "split16_cut" else 1), (want, p, pl)   # (a cut convmerge1: + its finalize)
         for k, v in before.items():
             eng.set_option(k, v)
     with pytest.raises(Exception):
