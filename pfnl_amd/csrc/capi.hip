@@ -233,7 +233,7 @@ struct pfnl_handle {
     bool strict = false, strict_once = false, weights_f16_ok = true;
     long long range_reruns = 0;
     int small_mode = 0;                                       // option small=auto|on|off: the small-shape trunk kernels (auto: when a launch has < 256 tiles of 8x32 pixels)
-    bool small_c10 = true;                                    // ... with conv10_i inside the conv1_i launch (per-frame partials, summed in conv2_i's prologue): option small_c10=on|off
+    bool small_c10 = true;                                    // ... with conv10_i inside the conv1_i launch (per-frame partials, summed in conv2_i's prologue); false: three launches (small3)
     DevBuf p10;                                               // ... those partials [B*T][H][W][64] fp32
     bool sf_chain = true;                                     // ... and conv2_i is ONE launch (option split16_chain=on|off)
     bool sf_c10 = true;                                       // ... and conv1_i + conv10_i are ONE launch (option split16_c10=on|off)
@@ -791,7 +791,7 @@ int block_fp32(const Fwd& f, const BlockPacks& k, bool first, bool last) {
                 q.out_sf = sf ? 1 : 0;                              // inp1 in the split format: it only feeds conv10_i and conv2_i's MFMA operands
                 HIPCHK(launch_conv3x3_split16(q, s));
             } else if (algo == 1 || algo == 3) {
-                WinoParams wp{h->inp0.p, wd + k.c1_u, wd + k.c1_b, nullptr, nullptr, h->inp1.p, H, W, 1, 1, F, nullptr};
+                WinoParams wp{h->inp0.p, wd + k.c1_u, wd + k.c1_b, nullptr, nullptr, h->inp1.p, H, W, 1, 1, F};
                 HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
             } else {
                 HIPCHK(launch_conv_mfma(direct_params(f, h->inp0.p, wd + k.c1_w, wd + k.c1_b, h->inp1.p, 64, 1, 1), 3, F, s));
@@ -810,7 +810,7 @@ int block_fp32(const Fwd& f, const BlockPacks& k, bool first, bool last) {
     if (pl.conv2_grouped) {
         // the whole of conv2_i in one launch: per (clip, tile) the shared half stays in LDS (conv_wino_ws MODE 2)
         ProfScope ps(h, s, PFNL_K_CONV3X3);
-        WinoParams wp{h->inp1.p, wd + k.c2b_u, wd + k.c2_b, nullptr, h->inp0.p, h->inp0.p, H, W, T, 1, F, nullptr};
+        WinoParams wp{h->inp1.p, wd + k.c2b_u, wd + k.c2_b, nullptr, h->inp0.p, h->inp0.p, H, W, T, 1, F};
         wp.in2 = h->base.p;
         wp.upack2 = wd + k.c2a_u;
         HIPCHK(launch_conv_wino_ws(wp, s));
@@ -838,7 +838,7 @@ int block_fp32(const Fwd& f, const BlockPacks& k, bool first, bool last) {
             ConvSplitParams q{h->base.p, f.w16s + (sf ? k.s_c2a_sf : k.s_c2a), wd + h->off_zero, nullptr, nullptr, h->pb.p, H, W, B, 1, 0};
             HIPCHK(sf ? launch_conv3x3_sf(q, s) : launch_conv3x3_split16(q, s));
         } else if (algo == 1 || algo == 3) {
-            WinoParams wp{h->base.p, wd + k.c2a_u, wd + h->off_zero, nullptr, nullptr, h->pb.p, H, W, 1, 0, B, nullptr};
+            WinoParams wp{h->base.p, wd + k.c2a_u, wd + h->off_zero, nullptr, nullptr, h->pb.p, H, W, 1, 0, B};
             HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
         } else {
             HIPCHK(launch_conv_mfma(direct_params(f, h->base.p, wd + k.c2a_w, wd + h->off_zero, h->pb.p, 64, 1, 0), 3, B, s));
@@ -853,7 +853,7 @@ int block_fp32(const Fwd& f, const BlockPacks& k, bool first, bool last) {
             q.flat = pl.mid ? 1 : 0;
             HIPCHK(sf ? launch_conv3x3_sf(q, s) : launch_conv3x3_split16(q, s));
         } else if (algo == 1 || algo == 3) {
-            WinoParams wp{h->inp1.p, wd + k.c2b_u, wd + k.c2_b, h->pb.p, h->inp0.p, h->inp0.p, H, W, T, 1, F, nullptr};
+            WinoParams wp{h->inp1.p, wd + k.c2b_u, wd + k.c2_b, h->pb.p, h->inp0.p, h->inp0.p, H, W, T, 1, F};
             HIPCHK(algo == 3 ? launch_conv_wino_ws(wp, s) : launch_conv_wino(wp, s));
         } else {
             ConvParams p = direct_params(f, h->inp1.p, wd + k.c2b_w, wd + k.c2_b, h->inp0.p, 64, 1, 1);
@@ -910,7 +910,7 @@ int convmerge1(const Fwd& f) {
     case M1_WINOGRAD: {
         // one launch of the persistent Winograd kernel in its accumulating mode (cout zero-padded to 64; the T frame tiles of a clip add into
         // the same accumulators, one epilogue per clip tile)
-        WinoParams wp{h->inp0.p, wd + h->off_m1_u[0], wd + h->off_m1_b, nullptr, nullptr, h->merge.p, H, W, T, 1, F, nullptr};
+        WinoParams wp{h->inp0.p, wd + h->off_m1_u[0], wd + h->off_m1_b, nullptr, nullptr, h->merge.p, H, W, T, 1, F};
         wp.upack_stride = T > 1 ? (long long)(h->off_m1_u[1] - h->off_m1_u[0]) : 0;
         wp.accum = 1;
         HIPCHK(launch_conv_wino_ws(wp, s));
@@ -1094,15 +1094,7 @@ int pfnl_create(const pfnl_config* cfg, pfnl_handle** out) {
     pfnl_handle* h = new pfnl_handle();
     h->cfg = *cfg;
     h->ncu = pfnl::device_cu_count();
-    if (const char* e = std::getenv("PFNL_SMALL")) h->small_mode = std::string(e) == "on" ? 1 : (std::string(e) == "off" ? 2 : 0);   // (A/B runs)
-    if (const char* e = std::getenv("PFNL_SMALL_C10")) h->small_c10 = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
-    if (const char* e = std::getenv("PFNL_SF_CHAIN")) h->sf_chain = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
-    if (const char* e = std::getenv("PFNL_SF_C10")) h->sf_c10 = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
-    if (const char* e = std::getenv("PFNL_SF_MID")) h->sf_mid = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
     if (const char* e = std::getenv("PFNL_SF_MID_CHAINS")) h->sf_mid_chains = std::atoi(e);   // (threshold sweeps)
-    if (const char* e = std::getenv("PFNL_SPLIT_CHAINS")) h->split_chains = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
-    if (const char* e = std::getenv("PFNL_SF0")) h->sf0 = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
-    if (const char* e = std::getenv("PFNL_SPLIT16_SF")) h->sf_path = std::string(e) != "0" && std::string(e) != "off";   // (A/B runs)
     if (const char* e = std::getenv("PFNL_CONV3X3")) {
         const std::string v(e);
         h->conv_algo = v == "direct" ? 0 : (v == "winograd_tile" ? 1 : (v == "split16" ? 4 : (v == "winograd" ? 3 : 5)));

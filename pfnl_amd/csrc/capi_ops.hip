@@ -1,6 +1,5 @@
 // Single-op hooks of the C-ABI (include/pfnl_hip.h): one kernel form each, with the weights packed on the host as the forward packs them,
 // for the per-op parity tests (pfnl_amd/ops.py).  None of them is on the forward's path.
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -269,40 +268,9 @@ static int op_conv3x3_wino(bool ws, const float* in, const float* kernel_host, c
     if (bias_host) std::memcpy(&pack[boff], bias_host, 64 * sizeof(float));
     float* dw = st.upload(pack);
     if (!st.ok()) return st.finish("winograd conv op: ");
-    pfnl::WinoParams wp{in, dw, dw + boff, addend, resid, out, H, W, addend ? add_div : 1, act, items, nullptr};
-#ifdef PFNL_WINO_TIMING
-    long long* dbg = nullptr;
-    const size_t dbg_n = 4096 * 64;
-    if (hipMalloc(&dbg, dbg_n * sizeof(long long)) == hipSuccess) {
-        (void)hipMemset(dbg, 0, dbg_n * sizeof(long long));
-        wp.dbg = dbg;
-    }
-#endif
+    pfnl::WinoParams wp{in, dw, dw + boff, addend, resid, out, H, W, addend ? add_div : 1, act, items};
     st.run([&] { return ws ? pfnl::launch_conv_wino_ws(wp, st.s) : pfnl::launch_conv_wino(wp, st.s); });
-    const int r = st.finish("winograd conv op: ");
-#ifdef PFNL_WINO_TIMING
-    if (dbg) {
-        std::vector<long long> hst(dbg_n);
-        (void)hipMemcpy(hst.data(), dbg, dbg_n * sizeof(long long), hipMemcpyDeviceToHost);
-        if (ws) {
-            for (int b : {0, 8, 101, 200, 255})
-                for (int role = 0; role < 2; ++role) {
-                    const long long* t = &hst[(size_t)b * 128 + role * 64];
-                    std::fprintf(stderr, "WS_TIMING wg %d %s:", b, role ? "helper" : "matrix");
-                    for (int i = 1; i < 64 && t[i]; ++i) std::fprintf(stderr, " %lld", t[i] - t[i - 1]);
-                    std::fprintf(stderr, " | t0-t0[wg0] %lld\n", t[0] - hst[0]);
-                }
-        } else
-        for (int b : {0, 8, 16, 1024, 2048, 4096, 7000}) {
-            std::fprintf(stderr, "WINO_TIMING wg %d:", b);
-            for (int i = 1; i < 16 && hst[(size_t)b * 16 + i]; ++i)
-                std::fprintf(stderr, " %lld", hst[(size_t)b * 16 + i] - hst[(size_t)b * 16]);
-            std::fprintf(stderr, " | t0-t0[wg0] %lld\n", hst[(size_t)b * 16] - hst[0]);
-        }
-        (void)hipFree(dbg);
-    }
-#endif
-    return r;
+    return st.finish("winograd conv op: ");
 }
 
 static int op_nonlocal(int bf16 /* 0 f32, 2 f16 split, 3 f16 (hi parts only) */, const float* x, const float* wg, const float* bg, const float* ww, const float* bw,

@@ -6,13 +6,6 @@
 
 #include <atomic>
 
-#ifndef PFNL_WINO_WPS
-#define PFNL_WINO_WPS 3      // waves per SIMD the Winograd kernel is compiled for (= workgroups per CU)
-#endif
-#ifndef PFNL_WINO_UDEPTH
-#define PFNL_WINO_UDEPTH 2
-#endif
-
 namespace pfnl {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -116,7 +109,6 @@ struct WinoParams {
     int add_div;
     int act;
     int items;
-    long long* dbg;        // PFNL_WINO_TIMING builds only: 64 clock64() stamps per workgroup (else null)
     long long in_item_stride;   // floats between consecutive input items; 0 = H*W*64 (conv_wino_ws only)
     const float* in2;      // conv_wino_ws MODE 2 (whole conv2_i): base [items/add_div][H][W][64]; else null
     const float* upack2;   // ... and the packed U of the kernel rows that multiply it

@@ -51,14 +51,10 @@ __global__ __launch_bounds__(C1_THREADS, 2) void conv1x1_stream_kernel(const flo
     // A: this lane's pixel (clamped; masked at the store), 16-byte pieces at channel 16*kh + 4*t of half M
     const f32x4* ap = reinterpret_cast<const f32x4*>(in) + (((size_t)item * T * HW + min(p0 + xl, HW - 1)) * 16 + kh * 4);
     const size_t aframe = (size_t)HW * 16;                          // f32x4 per frame
-#ifdef PFNL_C1_NO_A   /* timing experiment only: wrong results */
-#define C1_LOAD_A(dst, ap_) do { (void)(ap_); } while (0)
-#else
 #define C1_LOAD_A(dst, ap_)                                                                            \
     do {                                                                                               \
         _Pragma("unroll") for (int q_ = 0; q_ < 8; ++q_) dst[q_] = (ap_)[(q_ >> 2) * 8 + (q_ & 3)];     \
     } while (0)
-#endif
     f32x4 a0[8] = {}, a1[8] = {}, a2[8] = {};                                    // rotating sets: [M*4 + t] of one frame
     C1_LOAD_A(a0, ap);
     C1_LOAD_A(a1, ap + (size_t)min(1, T - 1) * aframe);

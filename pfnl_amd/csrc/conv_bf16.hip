@@ -32,8 +32,7 @@
 // also runs conv10_i inside the conv1_i launch (mode 2) and convmerge1 (mode 3, accumulating over the frames of a clip
 // with the weight pack replaced in LDS between frames): see the mode list above the kernel.
 // Measured (1x7x270x480, rocprofv3): conv1_i 72 us, conv2_i per-frame half 87 us, shared half 16 us, conv10_i 29 us
-// per block; 3.2-4.3 TB/s of HBM traffic; matrix pipe 38 % busy.  -DCB_X_NOMFMA / NOSTORE / NOLOAD are timing
-// experiments (wrong results on purpose) used to find what bounds the kernel; -DPFNL_BF16_TIMING adds phase stamps.
+// per block; 3.2-4.3 TB/s of HBM traffic; matrix pipe 38 % busy.
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -42,11 +41,9 @@
 #include "common.h"
 #include "conv_bf16.h"
 
-#ifndef CB_STORE_AUX
-#define CB_STORE_AUX 0      // cache-policy bits of the output stores (sc0 sc1 = 17 is worth 2 % in conv_split16.hip; here it measured +0.5 %)
-#endif
-
 namespace pfnl {
+
+constexpr int CB_OUT_AUX = 0;    // cache-policy bits of the output stores (sc0 sc1 = 17 is worth 2 % in conv_split16.hip; here it measured +0.5 %)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -63,10 +60,6 @@ constexpr int CB_CHUNKS = CB_IH * CB_IW * 8;                        // 16-byte p
 constexpr int CB_ITERS = (CB_CHUNKS + CB_THREADS - 1) / CB_THREADS; // 6
 
 __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
-#ifdef CB_X_NOMFMA
-    c[0] += (float)a[0] * (float)b[0];
-    return c;
-#endif
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
@@ -89,13 +82,6 @@ __device__ __forceinline__ u32x2 f32x4_to_bf16(f32x4 v) {         // round to ne
     return __builtin_bit_cast(u32x2, b);
 }
 
-#ifdef PFNL_BF16_TIMING   /* phase timeline of the kernel (tools/bf16_timing.py); not part of the product build */
-__device__ long long cb_dbg[256 * 8 * 256];
-#define CB_STAMP() do { if (lane == 0 && dbg_n < 256) cb_dbg[(blockIdx.x * 8 + wave) * 256 + dbg_n++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define CB_STAMP() do {} while (0)
-#endif
-
 // MODE 0: out = act(conv + bias).  MODE 1 (conv2_i per-frame half): out = act(conv + bias + addend[item / add_div]) + resid.
 // MODE 2 (conv1_i + conv10_i): MODE 0, and per chain of add_div frames x_out = act(sum_t W10_t out_t + x_bias), the 1x1
 // contraction running from the LDS scratch each finished tile passes through anyway (conv10_i costs no launch and
@@ -114,9 +100,6 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef PFNL_BF16_TIMING
-    int dbg_n = 0;
-#endif
     const int rp = wave >> 1;                                       // rows 2rp, 2rp+1 of the tile
     const int mt = wave & 1;                                        // output channels 32mt .. 32mt+31
     const int H = p.H, W = p.W;
@@ -238,7 +221,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
     // column (tid >> 3) & 31), 8 lanes per 128-byte line - into the scratch slot its output will take, and each epilogue unit
     // reads its 16 bytes from there (a quarter of the cache-line requests of reading them in accumulator layout, a lane = a
     // pixel: 32 lines per instruction).  Measured: the launch takes the same 89 us either way, and 67 us with the residual
-    // not read at all (-DCB_X_NOFUSELOAD) - it is the 116 MB, not the access pattern: the per-frame launch runs at the
+    // not read at all (a removal build) - it is the 116 MB, not the access pattern: the per-frame launch runs at the
     // ~4.2 TB/s this chip gives a kernel that reads and writes at once.
     u32x4 rq[4];
     int rbase = 0x7fffffff;                                         // byte offset of this thread's piece 0 in the tile's item (out of range: nothing)
@@ -270,7 +253,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
                 const int r0 = 8 * h + 4 * q;
                 f32x4 v = f32x4{accp[n][r0], accp[n][r0 + 1], accp[n][r0 + 2], accp[n][r0 + 3]} + *reinterpret_cast<const f32x4*>(bl + ech + r0);
                 v = lrelu4(v, eslope);
-                buffer_store_b128_guarded<CB_STORE_AUX>(__builtin_bit_cast(u32x4, v), rsF, off, 16 * q);
+                buffer_store_b128_guarded<CB_OUT_AUX>(__builtin_bit_cast(u32x4, v), rsF, off, 16 * q);
             }
             return;
         }
@@ -298,25 +281,16 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
         const int pp = id >> 3, c = id & 7;
         const int sx = ex0p + (pp & 31), sy = ey0p + (pp >> 5);
         const u32x4 o = *reinterpret_cast<const u32x4*>(scratch + pp * 128 + ((c ^ ((pp >> 1) & 7)) << 4));
-#ifdef CB_X_NOSTORE   /* timing experiments only */
-        if (o.x == 0x12345678u)
-#endif
-        buffer_store_b128_guarded<CB_STORE_AUX>(o, rsO, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
+        buffer_store_b128_guarded<CB_OUT_AUX>(o, rsO, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
     };
     auto fuse_request = [&](bool with_addend, int n, int h) __attribute__((always_inline)) {   // addend / residual piece (n, h) of the tile described by eoff / eitem
         // (base pointers of the tile's items: computed once per tile, not per request - a 64-bit product and a division each)
         const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ptrA), 0, item_bytes, 0x00020000);
-#ifdef CB_X_NOFUSELOAD   /* timing experiments only (wrong results on purpose) */
-        if (eoff[n] == 0x12345)
-#endif
         if (with_addend)                                            // (same pixels for every frame of the chain)
             radd[n][h] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, eoff[n], (ech + 8 * h) * 2, 0));
     };
     auto resid_request = [&](int k) __attribute__((always_inline)) {   // rows 2k, 2k+1 of the current tile (rows past the image: past the resource)
         const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(ptrR), 0, item_bytes, 0x00020000);
-#ifdef CB_X_NOFUSELOAD
-        if (rbase == 0x12345)
-#endif
         rq[k] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, rbase, k * 2 * wbytes, 0));
     };
     auto resid_stage = [&](unsigned char* scratch) __attribute__((always_inline)) {
@@ -365,7 +339,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
                     v[q] = lrelu4(v[q], 0.2f);
                 }
                 const u32x2 lo = f32x4_to_bf16(v[0]), hi = f32x4_to_bf16(v[1]);
-                buffer_store_b128_guarded<CB_STORE_AUX>(u32x4{lo.x, lo.y, hi.x, hi.y}, rsX, off, 16 * h);
+                buffer_store_b128_guarded<CB_OUT_AUX>(u32x4{lo.x, lo.y, hi.x, hi.y}, rsX, off, 16 * h);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) bacc[n][r] = 0.f;
@@ -443,9 +417,6 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
         auto group = [&](auto gc) {
             constexpr int g = decltype(gc)::value;
             constexpr int cur = g & 1;
-#ifdef PFNL_BF16_TIMING
-            CB_STAMP();                                             // group start (16 stamps per tile: 12 groups + commit pair + barrier pair)
-#endif
             // FUSE: everything one group later - group 0 puts the residual lines of the pending tile into the scratch, group 1
             // starts with the barrier that makes them visible
             constexpr int SH = FUSE ? 1 : 0;
@@ -470,16 +441,12 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
             if constexpr (g == SH + 8) {
                 __syncthreads();                                       // the scratch has been read
                 if (WITH10 && pending && eitemp % gT == gT - 1) x_epilogue();   // the pending tile closed its chain
-                CB_STAMP();
 #pragma unroll
                 for (int k = 0; k < CB_ITERS; ++k) asm volatile("" : "+v"(spk[k]));   // opaque: nothing derived from it is hoisted into registers
                 CB_COMMIT(cb ^ 1);
-                CB_STAMP();
             }
             if constexpr (g == 10) {
-#ifndef CB_X_NOLOAD   /* timing experiments only */
                 CB_REQUEST(min(u + 2, nu - 1));
-#endif
                 if constexpr (ACCUM) {                              // weights of the next unit's frame (units are whole chains: frame + 1 mod T)
                     const size_t wo = (size_t)((item % gT + 1) % gT) * (CB_W_BYTES / 16);
 #pragma unroll
@@ -533,9 +500,7 @@ __global__ __launch_bounds__(CB_THREADS, 1) void conv3x3_bf16_kernel(ConvBf16Par
         } else {
             pending = false;
         }
-        CB_STAMP();
         __syncthreads();                                               // this tile's buffer is free, the next tile's is complete
-        CB_STAMP();
         if constexpr (ACCUM) {                                      // every wave is past its last MFMA with the old weights
             if (gT > 1) {
 #pragma unroll
@@ -675,7 +640,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bf16_kernel(const uint16_t* __
                     }
                 }
                 const u32x2 lo = f32x4_to_bf16(v[0]), hi = f32x4_to_bf16(v[1]);
-                buffer_store_b128_guarded<CB_STORE_AUX>(u32x4{lo.x, lo.y, hi.x, hi.y}, rsO, ooff, (32 * m + 8 * h) * 2);
+                buffer_store_b128_guarded<CB_OUT_AUX>(u32x4{lo.x, lo.y, hi.x, hi.y}, rsO, ooff, (32 * m + 8 * h) * 2);
             }
     }
 }
@@ -790,9 +755,3 @@ void conv1x1_bf16_pack_weights(const float* hwio, int T, uint16_t* dst) {
 }
 
 }  // namespace pfnl
-
-#ifdef PFNL_BF16_TIMING
-extern "C" int pfnl_debug_read_bf16_stamps(long long* host, size_t n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pfnl::cb_dbg), n * sizeof(long long)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -21,11 +21,9 @@
 #include "common.h"
 #include "conv_bf16.h"
 
-#ifndef B2_STORE_AUX
-#define B2_STORE_AUX 0
-#endif
-
 namespace pfnl {
+
+constexpr int B2_OUT_AUX = 0;                                       // cache-policy bits of the output stores
 
 typedef __bf16 b2h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b2h4 __attribute__((ext_vector_type(4)));
@@ -64,15 +62,6 @@ __device__ __forceinline__ b2u2 b2_to_bf16(f32x4 v) {             // round to ne
     return __builtin_bit_cast(b2u2, b);
 }
 #define B2_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#ifdef PFNL_B2_TIMING   /* phase timeline (tools/b2_timing.py); not part of the product build */
-__device__ long long b2_dbg[256 * 2 * 128];
-#ifndef PFNL_B2_TIMING_MODE
-#define PFNL_B2_TIMING_MODE 1
-#endif
-#define B2_STAMP() do { if (MODE == PFNL_B2_TIMING_MODE && lane == 0 && (wave == 0 || wave == 5) && dbg_n < 128) b2_dbg[(blockIdx.x * 2 + (wave != 0)) * 128 + dbg_n++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define B2_STAMP() do {} while (0)
-#endif
 
 // MODE 0: out = act(conv + bias).  MODE 1 (conv2_i per-frame half): out = act(conv + bias + addend[item / add_div]) + resid.
 // MODE 2 (conv1_i + conv10_i): MODE 0, and per chain of add_div frames x_out = lrelu(sum_t W10_t out_t + x_bias).
@@ -86,9 +75,6 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef PFNL_B2_TIMING
-    int dbg_n = 0;
-#endif
     const int rp = wave >> 1;                                       // rows 2rp, 2rp+1 of the tile
     const int mt = wave & 1;                                        // output channels 32mt .. 32mt+31
     const int H = p.H, W = p.W;
@@ -117,7 +103,6 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
         x0_ = (sp_ - ty_ * tiles_x) * B2_TW;                                                     \
     } while (0)
 
-    B2_STAMP();                                                 // (timing build) kernel entry, past the work-order arithmetic
     // weights + bias -> LDS (once per workgroup)
 #pragma unroll
     for (int k = 0; k < B2_W_BYTES / 16 / B2_THREADS; ++k)
@@ -196,12 +181,8 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
     }
     __syncthreads();
 
-#ifdef B2_PRIO   /* experiment: static priority for the younger half of the workgroup (MI355X_MICROARCH.md, "two waves per SIMD", item 4) */
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
     for (int u = 0; u < nu; ++u) {
         const int cb = u & 1;
-        B2_STAMP();                                                 // 0: tile start
         unsigned char* const tile = b2_smem + cb * B2_TILE_BYTES;   // this tile's halo, then its scratch
         const int item = c_item, y0 = c_y0, x0 = c_x0;
         // ---- the next tile's halo -> the other buffer (free since the previous tile's closing barrier); past the end: nothing
@@ -245,7 +226,6 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
 
         // ---- 12 groups (column tap kx, k-step ks): the 4 halo rows 2rp..2rp+3 serve the 3 row taps of both output rows - 4 pixel reads
         // + 3 weight reads feed 6 MFMAs; the operands of group g + 1 are requested before the MFMAs of g.  Nothing else in here.
-        B2_STAMP();                                                 // 1: requests issued
         b2h8 px[2][4], wv[2][3];
 #define B2_PX(g_, r_) (*reinterpret_cast<const b2h8*>(tile + paddr[(g_) >> 2][(g_) & 3] + (r_) * (B2_IW * 128)))
 #define B2_WT(g_, ky_) (*reinterpret_cast<const b2h8*>(wlane + ((((ky_) * 3 + ((g_) >> 2)) * 4 + ((g_) & 3)) << 11)))
@@ -261,16 +241,12 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
                 const int id = g * B2_THREADS + tid;
                 const int pp = id >> 3, c = id & 7;
                 const int sx = h_x0 + (pp & 31), sy = h_y0 + (pp >> 5);
-                buffer_store_b128_guarded<B2_STORE_AUX>(held[g], rsH, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
+                buffer_store_b128_guarded<B2_OUT_AUX>(held[g], rsH, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
                 if constexpr (FUSE) {
                     // the residual pieces in ACCUMULATOR layout (a lane = a pixel, 16 bytes of its line): 64 lines per instruction instead of
                     // 8, but no staging through the scratch and no fourth barrier - measured 4.17 -> 4.13 ms per 1080p forward against
-                    // whole-line loads + a stage + a barrier (-DB2_RESID_LINES)
-#ifdef B2_RESID_LINES
-                    rq[g] = __builtin_bit_cast(b2u4, __builtin_amdgcn_raw_buffer_load_b128(rsR, rbase, g * 2 * wbytes, 0));
-#else
+                    // whole-line loads + a stage + a barrier
                     rq[g] = __builtin_bit_cast(b2u4, __builtin_amdgcn_raw_buffer_load_b128(rsR, eoff[g >> 1], (ech + 8 * (g & 1)) * 2, 0));
-#endif
                     if (chain_head)
                         radd[g >> 1][g & 1] = __builtin_bit_cast(b2u4, __builtin_amdgcn_raw_buffer_load_b128(rsA, eoff[g >> 1], (ech + 8 * (g & 1)) * 2, 0));
                 }
@@ -317,23 +293,10 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
         group(std::integral_constant<int, 11>{});
 #undef B2_PX
 #undef B2_WT
-        B2_STAMP();                                                 // 2: MFMA groups issued
-        B2_STAMP();                                                 // 3: (the fence wait moved to the closing barrier)
-        B2_BARRIER();
-        B2_STAMP();                                                 // 4: barrier passed                                               // every wave is past its last operand read of this buffer: it is the scratch now
+        B2_BARRIER();                                               // every wave is past its last operand read of this buffer: it is the scratch now
 
         // ---- serial phase.  Scratch = pixel-major lines, 16-byte pieces XOR-swizzled by (pixel >> 1) & 7 (conflict-free for the piece
         // writes, the line read-back and the 1x1 operand reads)
-#ifdef B2_RESID_LINES
-        if constexpr (FUSE) {                                       // the residual lines go where the output lines will be
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int pp = k * 64 + (tid >> 3), c = tid & 7;
-                *reinterpret_cast<b2u4*>(tile + pp * 128 + ((c ^ ((pp >> 1) & 7)) << 4)) = rq[k];
-            }
-            B2_BARRIER();
-        }
-#endif
 #pragma unroll
         for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -342,11 +305,7 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
                 const int c = 4 * mt + 2 * (lane >> 5) + h;         // piece of the pixel's line
                 b2u4* const slot = reinterpret_cast<b2u4*>(tile + ((2 * rp + n) * 32 + j) * 128 + ((c ^ ((j >> 1) & 7)) << 4));
                 [[maybe_unused]] b2u4 rr = {0, 0, 0, 0};
-#ifdef B2_RESID_LINES
-                if constexpr (FUSE) rr = *slot;
-#else
                 if constexpr (FUSE) rr = rq[2 * n + h];
-#endif
                 f32x4 v[2];
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
@@ -359,9 +318,7 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
                 const b2u2 lo = b2_to_bf16(v[0]), hi = b2_to_bf16(v[1]);
                 *slot = b2u4{lo.x, lo.y, hi.x, hi.y};
             }
-        B2_STAMP();                                                 // 5: epilogue pieces written
         B2_BARRIER();                                               // the 256 lines are complete
-        B2_STAMP();                                                 // 6: barrier passed
         {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                           // 2048 pieces, 4 per thread: whole 128-byte lines, 8 pixels per wave instruction
@@ -402,7 +359,7 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
                             v[q] = b2_lrelu4(v[q], 0.2f);
                         }
                         const b2u2 lo = b2_to_bf16(v[0]), hi = b2_to_bf16(v[1]);
-                        buffer_store_b128_guarded<B2_STORE_AUX>(b2u4{lo.x, lo.y, hi.x, hi.y}, rsX, off, 16 * h);
+                        buffer_store_b128_guarded<B2_OUT_AUX>(b2u4{lo.x, lo.y, hi.x, hi.y}, rsX, off, 16 * h);
                     }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) bacc[n][r] = 0.f;
@@ -412,7 +369,6 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
         c_item = n_item;
         c_y0 = n_y0;
         c_x0 = n_x0;
-        B2_STAMP();                                                 // 7: lines picked up
         asm volatile("" ::"v"(fence));                              // the next tile's halo has landed (fence load: conv_sf.hip)
         B2_BARRIER();                                               // the scratch has been read: the buffer is free for the halo after next
     }
@@ -423,7 +379,7 @@ __global__ __launch_bounds__(B2_THREADS, 1) void conv3x3_bf16_v2_kernel(ConvBf16
             const int id = k * B2_THREADS + tid;
             const int pp = id >> 3, c = id & 7;
             const int sx = h_x0 + (pp & 31), sy = h_y0 + (pp >> 5);
-            buffer_store_b128_guarded<B2_STORE_AUX>(held[k], rsH, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
+            buffer_store_b128_guarded<B2_OUT_AUX>(held[k], rsH, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
         }
     }
 #undef B2_DMA_HALO
@@ -454,9 +410,3 @@ hipError_t launch_conv3x3_bf16_v2(const ConvBf16Params& p, int mode, hipStream_t
 }
 
 }  // namespace pfnl
-
-#ifdef PFNL_B2_TIMING
-extern "C" int pfnl_debug_read_b2_stamps(long long* host, size_t n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pfnl::b2_dbg), n * sizeof(long long)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -4,7 +4,7 @@
 // phase in the tile's own halo buffer); what changes is that the two HALVES of the workgroup run half a tile period apart.
 //
 // Why.  In the second generation both waves of a SIMD reach the serial phase together, so the matrix pipe idles for its whole length
-// (tools/b2_timing.py: 2.3 - 3 k of a tile's 8.9 - 9.9 k cycles).  Here waves 0-3 (group A = tile rows 0-3) and waves 4-7 (group B =
+// (measured phase stamps: 2.3 - 3 k of a tile's 8.9 - 9.9 k cycles).  Here waves 0-3 (group A = tile rows 0-3) and waves 4-7 (group B =
 // rows 4-7) process the SAME tile sequence, group B two workgroup barriers behind group A.  A tile is four intervals -
 //     I0  MFMA groups 0-5        I1  MFMA groups 6-11        I2  epilogue dump (+ halo requests)        I3  lines out (+ conv10_i)
 // - so one half's I2 | I3 always faces the other half's I0 | I1: on every SIMD one wave feeds the matrix pipe while its partner does
@@ -29,11 +29,9 @@
 #include "common.h"
 #include "conv_bf16.h"
 
-#ifndef B3_STORE_AUX
-#define B3_STORE_AUX 0
-#endif
-
 namespace pfnl {
+
+constexpr int B3_OUT_AUX = 0;                                       // cache-policy bits of the output stores
 
 typedef __bf16 b3h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b3h4 __attribute__((ext_vector_type(4)));
@@ -64,17 +62,6 @@ __device__ __forceinline__ void b3_dma4(__amdgpu_buffer_rsrc_t rs, unsigned lds_
                  : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(rs) : "memory");
 }
 __device__ __forceinline__ f32x16 b3_mfma(b3h8 a, b3h8 b, f32x16 c) {
-#ifdef PFNL_X_MFMA16   /* timing experiment only (wrong results on purpose): the same FLOPs as two v_mfma_f32_16x16x32_bf16 on the same operand registers */
-    {
-        typedef float f32x4_ __attribute__((ext_vector_type(4)));
-        f32x4_ lo = {c[0], c[1], c[2], c[3]}, hi = {c[4], c[5], c[6], c[7]};
-        lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, lo, 0, 0, 0);
-        hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, hi, 0, 0, 0);
-        c[0] = lo[0]; c[1] = lo[1]; c[2] = lo[2]; c[3] = lo[3];
-        c[4] = hi[0]; c[5] = hi[1]; c[6] = hi[2]; c[7] = hi[3];
-        return c;
-    }
-#endif
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x4 b3_to_f32(b3u2 v) {
@@ -94,22 +81,6 @@ __device__ __forceinline__ b3u2 b3_to_bf16(f32x4 v) {             // round to ne
     return __builtin_bit_cast(b3u2, b);
 }
 #define B3_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#ifdef PFNL_B3_TIMING   /* phase timeline (tools/b3_timing.py); not part of the product build */
-__device__ long long b3_dbg[256 * 2 * 128];
-#ifndef PFNL_B3_TIMING_MODE
-#define PFNL_B3_TIMING_MODE 2
-#endif
-#define B3_STAMP() do { if (MODE == PFNL_B3_TIMING_MODE && lane == 0 && (wave == 0 || wave == 5) && dbg_n < 128) b3_dbg[(blockIdx.x * 2 + (wave != 0)) * 128 + dbg_n++] = __builtin_readcyclecounter(); } while (0)
-#ifdef PFNL_B3_PSTAMPS
-#define B3_PSTAMP() B3_STAMP()
-#else
-#define B3_PSTAMP() do {} while (0)
-#endif
-#else
-#define B3_STAMP() do {} while (0)
-#define B3_PSTAMP() do {} while (0)
-#endif
-
 // (M16) the K = 32 shape: 16 x 16 outputs, 4 accumulator registers - 14 % less energy per FLOP than 32x32x16 under the package power cap
 typedef float b3f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ b3f4 b3_mfma16(b3h8 a, b3h8 b, b3f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
@@ -136,9 +107,6 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef PFNL_B3_TIMING
-    int dbg_n = 0;
-#endif
     const int rp = wave >> 1;                                       // rows 2rp, 2rp+1 of the tile
     const int mt = wave & 1;                                        // output channels 32mt .. 32mt+31
     const int grp = wave >> 2;                                      // half of the workgroup: 0 = A (early), 1 = B (two intervals behind)
@@ -184,7 +152,6 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
         return unit_head(c.ci + 1);
     };
 
-    B3_STAMP();                                                 // (timing build) kernel entry, past the work-order arithmetic
     // DMA map: piece i covers halo pixels 8 i .. 8 i + 7 (linear, 34 per row); lane L -> pixel 8 i + (L >> 3), LDS slot L & 7, which
     // holds chunk (L & 7) ^ ((px >> 1) & 7) of that pixel: `drel` = byte offset of the lane's SOURCE chunk relative to the halo origin,
     // `dpk` = py | px << 8 (border test).  This wave's pieces: group B i = wq + 4k (< 25), group A i = 25 + wq + 4k (< 43).
@@ -199,7 +166,6 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
         dpk[k] = py | (px << 8);
     }
     const unsigned lds0 = (unsigned)(uintptr_t)b3_smem;
-    B3_PSTAMP();                                                // (timing build) P1: DMA tables
     // this wave's share of the halo of unit `un` -> buffer `buf`; `live` false: nothing (an empty resource)
     auto dma_share = [&](const Unit& un, bool live, int buf) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.in) + (size_t)un.item * H * W * 64, 0, live ? item_bytes : 0, 0x00020000);
@@ -298,10 +264,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
     // ---- prologue: halo of tile 0 -> buffer 0 (both halves' shares = all of it); group B's share of tile 1 -> buffer 1 while it waits
     Unit cu = unit_head(0);
     Unit nx = nu > 1 ? unit_next(cu) : cu;
-    B3_PSTAMP();                                                // P2: operand addresses, first units
     dma_share(cu, true, 0);
     request_inputs(cu, true);
-    B3_PSTAMP();                                                // P3: halo + input requests issued
     // bias (and conv10_i's) by LDS-DMA, IN FRONT of the weight pieces (the wait below counts the late ones): one dword per lane
     if (wave == 0) b3_dma4(__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, 256, 0x00020000), lds0 + 2 * B3_TILE_BYTES + B3_W_BYTES, lane * 4);
     if constexpr (WITH10) {
@@ -325,10 +289,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
                 if (early == (part == 0)) b3_dma16(rsW, lds0 + 2 * B3_TILE_BYTES + (wave + 8 * j) * 1024, (wave + 8 * j) * 1024 + lane * 16);
             }
     }
-    B3_PSTAMP();                                                // P4: weights requested
     if (M16 || wave < 6) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // all but the late weight pieces (waves 0-5: three of nine, waves 6-7: six; M16: three for every wave)
     else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    B3_PSTAMP();                                                // P5: halo and the early weights landed
     __syncthreads();
     [[maybe_unused]] b3f4 bias4[2];                                 // M16: output tile ct, rows 4 g + r = channels ech16 + 4 ct + r
     if constexpr (M16) {
@@ -356,13 +318,9 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         B3_BARRIER();
     }
-#ifdef B3_PRIO_B
-    if (grp) __builtin_amdgcn_s_setprio(1);
-#endif
 
     for (int u = 0; u < nu; ++u) {
         const int cb = u & 1;
-        B3_STAMP();                                                 // 0: tile start
         unsigned char* const tile = b3_smem + cb * B3_TILE_BYTES;   // this tile's halo
         unsigned char* const scr = tile + (grp ? B3_SCR_B : 0);     // then this half's 128 lines
         const int item = cu.item, y0 = cu.y0, x0 = cu.x0;
@@ -417,10 +375,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
             group16(std::integral_constant<int, 0>{});
             group16(std::integral_constant<int, 1>{});
             group16(std::integral_constant<int, 2>{});
-            B3_STAMP();                                             // 1: groups 0-2 issued
             if (u == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the late weight pieces of the prologue (column tap 2)
             B3_BARRIER();                                           // interval boundary (the other half's dump | lines)
-            B3_STAMP();                                             // 2
             group16(std::integral_constant<int, 3>{});
             group16(std::integral_constant<int, 4>{});
             group16(std::integral_constant<int, 5>{});
@@ -483,10 +439,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
             group16(std::integral_constant<int, 0>{});
             group16(std::integral_constant<int, 1>{});
             group16(std::integral_constant<int, 2>{});
-            B3_STAMP();                                             // 1: groups 0-2 issued
             if (u == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the late weight pieces of the prologue (column tap 2)
             B3_BARRIER();                                           // interval boundary (the other half's dump | lines)
-            B3_STAMP();                                             // 2
             group16(std::integral_constant<int, 3>{});
             group16(std::integral_constant<int, 4>{});
             group16(std::integral_constant<int, 5>{});
@@ -541,10 +495,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
         group(std::integral_constant<int, 3>{});
         group(std::integral_constant<int, 4>{});
         group(std::integral_constant<int, 5>{});
-        B3_STAMP();                                                 // 1: groups 0-5 issued
         if (u == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the late weight pieces of the prologue (groups 6-11 read them)
         B3_BARRIER();                                               // interval boundary (the other half's dump | lines)
-        B3_STAMP();                                                 // 2
         group(std::integral_constant<int, 6>{});
         group(std::integral_constant<int, 7>{});
         group(std::integral_constant<int, 8>{});
@@ -554,10 +506,8 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
 #undef B3_PX
 #undef B3_WT
         }
-        B3_STAMP();                                                 // 3: groups 6-11 issued
         if (grp) B3_PIECES_LANDED();                                // group B's share of the next halo has landed (group A reads it after this barrier)
         B3_BARRIER();                                               // this half is past its last operand read of its rows: they are its scratch now
-        B3_STAMP();                                                 // 4
 
         // ---- I2: the halo requests this half owes, then the epilogue dump
         const bool more = u + 1 < nu, more2 = u + 2 < nu;           // (wave-uniform)
@@ -593,9 +543,7 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
                 const b3u2 lo = b3_to_bf16(v[0]), hi = b3_to_bf16(v[1]);
                 *slot = b3u4{lo.x, lo.y, hi.x, hi.y};
             }
-        B3_STAMP();                                                 // 5: epilogue pieces written
         B3_BARRIER();                                               // this half's 128 lines are complete
-        B3_STAMP();                                                 // 6
 
         // ---- I3: whole 128-byte lines to HBM (8 pixels per wave instruction), conv10_i on the same lines, the next tile's epilogue inputs
         {
@@ -612,7 +560,7 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
                 const int id = k * B3_GTHREADS + tidl;
                 const int pp = id >> 3, c = id & 7;
                 const int sx = x0 + (pp & 31), sy = y0 + 4 * grp + (pp >> 5);
-                buffer_store_b128_guarded<B3_STORE_AUX>(line[k], rsO, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
+                buffer_store_b128_guarded<B3_OUT_AUX>(line[k], rsO, (sx < W && sy < H) ? (sy * W + sx) * 128 + c * 16 : 0x7fffffff, 0);
             }
         }
         if constexpr (WITH10) {                                     // conv10_i: 4 k-steps x 2 rows, B = the lines of this frame's tile, A = W10 of the frame
@@ -651,7 +599,7 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
                             v[q] = b3_lrelu4(v[q], 0.2f);
                         }
                         const b3u2 lo = b3_to_bf16(v[0]), hi = b3_to_bf16(v[1]);
-                        buffer_store_b128_guarded<B3_STORE_AUX>(b3u4{lo.x, lo.y, hi.x, hi.y}, rsX, off, 16 * h);
+                        buffer_store_b128_guarded<B3_OUT_AUX>(b3u4{lo.x, lo.y, hi.x, hi.y}, rsX, off, 16 * h);
                     }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) bacc[n][r] = 0.f;
@@ -661,7 +609,6 @@ __global__ __launch_bounds__(B3_THREADS, 1) void conv3x3_bf16_v3_kernel(ConvBf16
         request_inputs(nx, more);                                   // (after the 1x1's MFMAs have read xw)
         cu = nx;
         nx = n2;
-        B3_STAMP();                                                 // 7: lines out
         if (!grp) B3_PIECES_LANDED();                               // group A's share of the next halo has landed
         B3_BARRIER();                                               // this half's scratch has been read: its bytes are free for the halo after next
     }
@@ -746,9 +693,3 @@ hipError_t launch_conv3x3_bf16_v3(const ConvBf16Params& p, int mode, hipStream_t
 }
 
 }  // namespace pfnl
-
-#ifdef PFNL_B3_TIMING
-extern "C" int pfnl_debug_read_b3_stamps(long long* host, size_t n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pfnl::b3_dbg), n * sizeof(long long)) == hipSuccess ? 0 : -1;
-}
-#endif

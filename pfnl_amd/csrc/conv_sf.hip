@@ -30,11 +30,9 @@
 #include "common.h"
 #include "conv_split16.h"
 
-#ifndef SF_STORE_AUX
-#define SF_STORE_AUX 17     // output stores written through (sc0 sc1), as conv_split16.hip measured
-#endif
-
 namespace pfnl {
+
+constexpr int SF_OUT_AUX = 17;      // output stores written through (sc0 sc1), as conv_split16.hip measured
 
 typedef _Float16 sfh8 __attribute__((ext_vector_type(8)));
 typedef unsigned sfu4 __attribute__((ext_vector_type(4)));
@@ -90,28 +88,8 @@ __device__ __forceinline__ void sf_split4(f32x4 v, sfu2& hi, sfu2& lo, float nsc
 }
 
 __device__ __forceinline__ f32x16 sf_mfma(sfh8 a, sfh8 b, f32x16 c) {
-#ifdef SF_X_NOMFMA   /* timing experiments only (wrong results on purpose; tools/sf_variants.sh) */
-    c[0] += (float)a[0] * (float)b[0];
-    return c;
-#endif
-#ifdef PFNL_X_MFMA16   /* timing experiment only (wrong results on purpose): the same FLOPs as two v_mfma_f32_16x16x32_f16 on the same operand registers */
-    {
-        typedef float f32x4_ __attribute__((ext_vector_type(4)));
-        f32x4_ lo = {c[0], c[1], c[2], c[3]}, hi = {c[4], c[5], c[6], c[7]};
-        lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, lo, 0, 0, 0);
-        hi = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, hi, 0, 0, 0);
-        c[0] = lo[0]; c[1] = lo[1]; c[2] = lo[2]; c[3] = lo[3];
-        c[4] = hi[0]; c[5] = hi[1]; c[6] = hi[2]; c[7] = hi[3];
-        return c;
-    }
-#endif
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
-#ifdef SF_X_NODMA
-#define SF_DMA16(rs_, dst_, voff_) do { if ((voff_) == 0x12345) sf_dma16(rs_, dst_, voff_); } while (0)
-#else
-#define SF_DMA16(rs_, dst_, voff_) sf_dma16(rs_, dst_, voff_)
-#endif
 
 // MODE 0: out = act(conv + bias).   MODE 1 (conv2_i per-frame half): out = act(conv + bias + addend[item / add_div]) + resid.
 template <int MODE>
@@ -180,7 +158,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_kernel(ConvSplitPara
             if (k_ < SF_DMA_ITERS - 1 || i_ < SF_NDMA) {                                         \
                 const int gy_ = (y0_) + (dpk[k_] & 0xff) - 1, gx_ = (x0_) + (dpk[k_] >> 8) - 1;  \
                 const bool in_ = (interior_) || ((unsigned)gy_ < (unsigned)H && (unsigned)gx_ < (unsigned)W && (dpk[k_] & 0xff) < SF_IH); \
-                SF_DMA16(rs_, lds0 + (buf_) * SF_TILE_BYTES + i_ * 1024, in_ ? (org_) + dgrel[k_] : 0x7fffffff); \
+                sf_dma16(rs_, lds0 + (buf_) * SF_TILE_BYTES + i_ * 1024, in_ ? (org_) + dgrel[k_] : 0x7fffffff); \
             }                                                                                    \
         }                                                                                        \
     } while (0)
@@ -233,16 +211,8 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_kernel(ConvSplitPara
         if constexpr (FUSE) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-#ifdef SF_X_NOADDEND
-                radd[4 * q + j] = 0.25f;
-#else
                 radd[4 * q + j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsA, evoff + j * 256, q * 2048, 0));
-#endif
-#ifdef SF_X_NORESID
-                rres[4 * q + j] = 0.125f;
-#else
                 rres[4 * q + j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsR, evoff + j * 256, q * 2048, 0));
-#endif
             }
         }
     };
@@ -254,10 +224,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_kernel(ConvSplitPara
             const float sv = v * slope;
             asm("v_max_f32 %0, %1, %2" : "=v"(v) : "v"(v), "v"(sv)); // leaky_relu(0.2) or identity (slope 1), branch-free
             if constexpr (FUSE) v += rres[4 * q + j];
-#ifdef SF_X_NOSTORE
-            if (v == 1.2345e30f)
-#endif
-            sf_store_b32<SF_STORE_AUX>(v, rsO, evoff + j * 256, q * 2048);
+            sf_store_b32<SF_OUT_AUX>(v, rsO, evoff + j * 256, q * 2048);
         }
     };
 
@@ -456,9 +423,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_kernel(ConvSplitPara
 // Against conv3x3_sf_kernel<0> + <1>: the weight slices travel by LDS-DMA as well (L2 -> LDS, no registers: a chain switches
 // packs twice, and every unit may now bring the next unit's weights - the same three slices following the column taps consumed -
 // skipped when the next unit uses what is already there), each slice covered by its own fence load.
-#ifdef PFNL_SFC_TIMING
-__device__ long long sfc_dbg[256 * 2 * 160];
-#endif
 // SFCOPY (round 6): the block's output - the next block's inp0 - is ALSO written in the split format (p.out2, [items][H][W] x 256 B), so
 // that conv3x3_c1c10_kernel can take its halo by LDS-DMA in operand form instead of splitting fp32 on the VALU at every commit.  A lane
 // owns one channel (D[pixel][cout]) where an SF chunk is 8 channels of one pixel: neighbouring lanes swap one binary16 pair per pixel
@@ -467,18 +431,13 @@ __device__ long long sfc_dbg[256 * 2 * 160];
 // SPLIT: split chains (below) - a template parameter so that the whole-round launches keep their instruction stream (conv_split16.hip).
 template <bool SFCOPY, bool SPLIT>
 __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSplitParams p) {
-#ifdef PFNL_SFC_TIMING
-    int dbg_n = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char sf_smem[];
     unsigned char* const wl = sf_smem + 2 * SF_TILE_BYTES;
     float* const bl = reinterpret_cast<float*>(sf_smem + 2 * SF_TILE_BYTES + SF_W_BYTES);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if PFNL_S16_PRIO
-    if (wave >= 4) __builtin_amdgcn_s_setprio(PFNL_S16_PRIO);
-#endif
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);                   // the younger wave of every SIMD above the older one
     const int rp = wave >> 1;
     const int nt = wave & 1;
     const int H = p.H, W = p.W;
@@ -526,17 +485,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
             }                                                                                    \
         }                                                                                        \
     } while (0)
-#define SFC_DMA_HALO_PIECE(k_, rs_, org_, interior_, y0_, x0_, buf_)                             \
-    do {                                                                                         \
-        const int i_ = wave + 8 * (k_);                                                          \
-        if ((k_) < SF_DMA_ITERS - 1 || i_ < SF_NDMA) {                                           \
-            const int py_ = dpk[k_] & 0xff, px_ = dpk[k_] >> 8;                                  \
-            const int gy_ = (y0_) + py_ - 1, gx_ = (x0_) + px_ - 1;                              \
-            const bool in_ = (interior_) || ((unsigned)gy_ < (unsigned)H && (unsigned)gx_ < (unsigned)W && py_ < SF_IH); \
-            const int rel_ = py_ * wbytes + px_ * 256 + (((lane & 7) ^ ((px_ >> 1) & 7)) << 4);   \
-            sf_dma16(rs_, lds0 + (buf_) * SF_TILE_BYTES + i_ * 1024, in_ ? (org_) + rel_ : 0x7fffffff); \
-        }                                                                                        \
-    } while (0)
     // one 24 KB weight slice (column tap `slot` of pack `pk_`, channel half `half_`): 24 DMA instructions, 3 per wave
     const int wvoff = wave * 1024 + lane * 16;
 #define SFC_DMA_W(pk_, half_, slot_)                                                             \
@@ -546,12 +494,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
         _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_)                                         \
             sf_dma16(rw_, ldsw + (slot_) * SF_SLOT_BYTES + (wave + 8 * k_) * 1024, (half_) * SF_W_BYTES + (slot_) * SF_SLOT_BYTES + wvoff + k_ * 8192); \
     } while (0)
-
-#ifdef PFNL_X_NOWSTREAM   /* timing experiment only (wrong results on purpose), as in conv_split16.hip */
-#define SFC_DMA_WX(pk_, half_, slot_) do {} while (0)
-#else
-#define SFC_DMA_WX(pk_, half_, slot_) SFC_DMA_W(pk_, half_, slot_)
-#endif
 
     int paddr[3];
 #pragma unroll
@@ -604,10 +546,10 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
             const unsigned r1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s1, 0xB1, 0xf, 0xf, false);
             const unsigned a0 = odd ? r0 : hi.x, a1 = odd ? r1 : hi.y;             // channel c (even) / c - 1 (odd): the low halfword
             const unsigned b0 = odd ? lo.x : r0, b1 = odd ? lo.y : r1;             // channel c + 1 (even) / c (odd): the high halfword
-            sf_store_u32<SF_STORE_AUX>(__builtin_amdgcn_perm(b0, a0, 0x05040100u), rsS, evoff_sf, q * 2048);
-            sf_store_u32<SF_STORE_AUX>(__builtin_amdgcn_perm(b0, a0, 0x07060302u), rsS, evoff_sf + 256, q * 2048);
-            sf_store_u32<SF_STORE_AUX>(__builtin_amdgcn_perm(b1, a1, 0x05040100u), rsS, evoff_sf + 512, q * 2048);
-            sf_store_u32<SF_STORE_AUX>(__builtin_amdgcn_perm(b1, a1, 0x07060302u), rsS, evoff_sf + 768, q * 2048);
+            sf_store_u32<SF_OUT_AUX>(__builtin_amdgcn_perm(b0, a0, 0x05040100u), rsS, evoff_sf, q * 2048);
+            sf_store_u32<SF_OUT_AUX>(__builtin_amdgcn_perm(b0, a0, 0x07060302u), rsS, evoff_sf + 256, q * 2048);
+            sf_store_u32<SF_OUT_AUX>(__builtin_amdgcn_perm(b1, a1, 0x05040100u), rsS, evoff_sf + 512, q * 2048);
+            sf_store_u32<SF_OUT_AUX>(__builtin_amdgcn_perm(b1, a1, 0x07060302u), rsS, evoff_sf + 768, q * 2048);
         }
     };
     auto quarter_request = [&](int q) __attribute__((always_inline)) {
@@ -623,7 +565,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
             asm("v_max_f32 %0, %1, %2" : "=v"(v) : "v"(v), "v"(sv));
             v += rv[j];
             vv[j] = v;
-            sf_store_b32<SF_STORE_AUX>(v, rsO, evoff + j * 256, q * 2048);
+            sf_store_b32<SF_OUT_AUX>(v, rsO, evoff + j * 256, q * 2048);
         }
         sf_copy_quarter(vv, q);
     };
@@ -634,14 +576,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
         quarter_finish_with(n, q, rv);
     };
 #define SFC_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#ifndef SFC_SPREAD_HALO
-#define SFC_SPREAD_HALO 0
-#endif
-#ifdef PFNL_SFC_TIMING   /* phase timeline of the chain kernel (tools/sfc_timing.py); not part of the product build */
-#define SFC_STAMP() do { if (lane == 0 && (wave == 0 || wave == 5) && dbg_n < 160) sfc_dbg[(blockIdx.x * 2 + (wave != 0)) * 160 + dbg_n++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define SFC_STAMP() do {} while (0)
-#endif
 
     // ---- prologue: halo of unit 0 (the first chain's shared half: `base`) and its weights (pack 0 = shared half, channel half 0)
     int c_f, c_clip, c_y0, c_x0, n_f, n_clip, n_y0, n_x0;
@@ -679,7 +613,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
             const int nx_pk = PAR == 0 ? w_pk : (n_f != 0);
             const int nx_half = half_a ^ 1;
             const bool w_replace = PAR == 0 || nx_pk != w_pk;       // (wave-uniform; unit B -> next A only at the two ends of a chain)
-            SFC_STAMP();                                            // 0: unit start
             sfh8 X[4][2], Wv[2][2];
 #define SF_PX(g_, r_, part_) (*reinterpret_cast<const sfh8*>(tile + (paddr[(g_) >> 1] ^ (((part_) ? lo_xor : 0) | (((g_) & 1) << 5))) + (r_) * (SF_IW * 128)))
 #define SF_WT(g_, ky_, part_) (*reinterpret_cast<const sfh8*>(wlane + (((g_) * 3 + (ky_)) << 12) + ((part_) << 10)))
@@ -692,20 +625,14 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
             __builtin_amdgcn_sched_barrier(0);
             // slice 2 of THIS unit's weights (its slot was free only after the previous unit's closing barrier), then the next
             // unit's halo; one fence load covers both (slice 2 is first read after b0, the halo after this unit's closing barrier)
-            if (w_slice2_owed) SFC_DMA_WX(w_pk, half_u, 2);
+            if (w_slice2_owed) SFC_DMA_W(w_pk, half_u, 2);
             const int q_f = PAR == 0 ? c_f : n_f, q_clip = PAR == 0 ? c_clip : n_clip, y0q = PAR == 0 ? c_y0 : n_y0, x0q = PAR == 0 ? c_x0 : n_x0;
             const float* const qsrc = q_f == 0 ? p.in2 + (size_t)q_clip * H * W * 64 : p.in + ((size_t)q_clip * T + (q_f - 1)) * H * W * 64;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(qsrc), 0, item_bytes, 0x00020000);
             const int org = ((y0q - 1) * W + x0q - 1) * 256 + nx_half * 128;
             const bool interior = y0q > 0 && y0q + SF_IH - 1 <= H && x0q > 0 && x0q + SF_IW - 1 <= W;
-#if SFC_SPREAD_HALO
-            // the halo pieces go one per sub-step BEHIND b0 (sub-steps 6 .. 11) instead of in a burst at the unit's start, where both waves
-            // of a SIMD issue their DMAs at the same time and nobody computes; slice 2 of this unit's weights keeps a fence of its own
-            unsigned fence = __builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0);   // (covers slice 2; re-issued behind the last halo piece)
-#else
             SFC_DMA_HALO(rs, org, interior, y0q, x0q, cb ^ 1);
             const unsigned fence = __builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0);
-#endif
             unsigned fence_w = 0;
             row_setup(PAR);
 
@@ -732,36 +659,23 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
                 }
                 if constexpr (S == 14) quarter_finish(PAR, 2);
                 if constexpr (S == 15) quarter_finish(PAR, 3);
-#if SFC_SPREAD_HALO
-                if constexpr (S >= 7 && S < 6 + SF_DMA_ITERS) SFC_DMA_HALO_PIECE(S - 6, rs, org, interior, y0q, x0q, cb ^ 1);
-                if constexpr (S == 6 + SF_DMA_ITERS) fence = __builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0);   // behind the last piece
-#endif
                 if constexpr (ky == 0) {
                     if constexpr (g == 2) {
-                        SFC_STAMP();                                // 1: groups 0-1 done
                         asm volatile("" ::"v"(fence));              // slice 2 of this unit's weights has landed (and the halo, as it happens)
-                        SFC_STAMP();                                // 2: fence passed
                         SFC_BARRIER();                              // b0: column tap 0 consumed; slice 2 complete
-                        SFC_STAMP();                                // 3: past b0
-                        if (w_replace) SFC_DMA_WX(nx_pk, nx_half, 0);
-#if SFC_SPREAD_HALO
-                        SFC_DMA_HALO_PIECE(0, rs, org, interior, y0q, x0q, cb ^ 1);
-#endif
+                        if (w_replace) SFC_DMA_W(nx_pk, nx_half, 0);
                         if constexpr (PAR == 0) {                   // decode the next tile (past the end: this one again - a harmless re-read)
                             const int kn = min(kt + 1, nt_tiles - 1);
                             decode(kn, n_f, n_clip, n_y0, n_x0);
                         }
                     }
                     if constexpr (g == 4) {
-                        SFC_STAMP();                                // 4: groups 2-3 done
                         SFC_BARRIER();                              // b1: column tap 1 consumed
-                        SFC_STAMP();                                // 5: past b1
-                        if (w_replace) SFC_DMA_WX(nx_pk, nx_half, 1);
+                        if (w_replace) SFC_DMA_W(nx_pk, nx_half, 1);
                         fence_w = __builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0);   // covers slices 0 and 1 of the next unit's weights
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#if PFNL_S16_SPREAD
                 // the next sub-step's operand reads between this sub-step's MFMAs (conv_split16.hip, conv3x3_c1c10_kernel)
                 {
                     constexpr int S1 = S + 1, g1 = S1 / 3, ky1 = S1 % 3;
@@ -801,40 +715,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
                     accc[0] = sf_mfma(X[ky][1], wh, accc[0]);
                     accc[1] = sf_mfma(X[ky + 1][1], wh, accc[1]);
                 }
-#else
-                if constexpr (S < 17) {
-                    constexpr int S1 = S + 1, g1 = S1 / 3, ky1 = S1 % 3;
-                    Wv[S1 & 1][0] = SF_WT(g1, ky1, 0);
-                    Wv[S1 & 1][1] = SF_WT(g1, ky1, 1);
-                    if constexpr (ky1 == 0) {
-                        X[0][0] = SF_PX(g1, 0, 0);
-                        X[0][1] = SF_PX(g1, 0, 1);
-                        X[1][0] = SF_PX(g1, 1, 0);
-                        X[1][1] = SF_PX(g1, 1, 1);
-                    } else {
-                        X[ky1 + 1][0] = SF_PX(g1, ky1 + 1, 0);
-                        X[ky1 + 1][1] = SF_PX(g1, ky1 + 1, 1);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const sfh8 wh = Wv[S & 1][0], wo = Wv[S & 1][1];
-                if constexpr (PAR == 0 && S == 0) {                 // a tile's first products: C = the chain's shared half + bias (or 0 for that half itself)
-                    f32x16 zero;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) zero[r] = 0.f;
-                    accm[0] = sf_mfma(X[ky][0], wh, pbv[0]);
-                    accm[1] = sf_mfma(X[ky + 1][0], wh, pbv[1]);
-                    accc[0] = sf_mfma(X[ky][0], wo, zero);
-                    accc[1] = sf_mfma(X[ky + 1][0], wo, zero);
-                } else {
-                    accm[0] = sf_mfma(X[ky][0], wh, accm[0]);
-                    accm[1] = sf_mfma(X[ky + 1][0], wh, accm[1]);
-                    accc[0] = sf_mfma(X[ky][0], wo, accc[0]);
-                    accc[1] = sf_mfma(X[ky + 1][0], wo, accc[1]);
-                }
-                accc[0] = sf_mfma(X[ky][1], wh, accc[0]);
-                accc[1] = sf_mfma(X[ky + 1][1], wh, accc[1]);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             };
             substep(std::integral_constant<int, 0>{});
@@ -881,9 +761,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
             }
             w_slice2_owed = w_replace;                              // slice 2 of the next unit's weights goes once this unit's is consumed: at its start
             w_pk = nx_pk;
-            SFC_STAMP();                                            // 6: groups 4-5 done
             asm volatile("" ::"v"(fence), "v"(fence_w));            // the next unit's halo and weight slices 0, 1 have landed
-            SFC_STAMP();                                            // 7: fences passed
             SFC_BARRIER();                                          // b2
         };
         unit(std::integral_constant<int, 0>{});
@@ -928,10 +806,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
 // Summation order differs from the 32x32x16 form (K = 32 per instruction): equal to it within rounding, not bit for bit.
 typedef float sff4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ sff4 sf_mfma16(sfh8 a, sfh8 b, sff4 c) {
-#ifdef SF_X_NOMFMA   /* timing experiments only (wrong results on purpose) */
-    c[0] += (float)a[0] * (float)b[0];
-    return c;
-#endif
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
@@ -943,18 +817,13 @@ __device__ __forceinline__ sff4 sf_mfma16(sfh8 a, sfh8 b, sff4 c) {
 #define SF_SWZ16(px_) ((((px_) >> 1) & 3) << 1)
 template <bool SPLIT>
 __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvSplitParams p) {
-#ifdef PFNL_SFC_TIMING
-    int dbg_n = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char sf_smem[];
     unsigned char* const wl = sf_smem + 2 * SF_TILE_BYTES;
     float* const bl = reinterpret_cast<float*>(sf_smem + 2 * SF_TILE_BYTES + SF_W_BYTES);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if PFNL_S16_PRIO
-    if (wave >= 4) __builtin_amdgcn_s_setprio(PFNL_S16_PRIO);
-#endif
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);                   // the younger wave of every SIMD above the older one
     const int rp = wave >> 1;
     const int nt = wave & 1;
     const int H = p.H, W = p.W;
@@ -1008,12 +877,6 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
             sf_dma16(rw_, ldsw + (slot_) * SF_SLOT_BYTES + (wave + 8 * k_) * 1024, (half_) * SF_W_BYTES + (slot_) * SF_SLOT_BYTES + wvoff + k_ * 8192); \
     } while (0)
 
-#ifdef PFNL_X_NOWSTREAM   /* timing experiment only (wrong results on purpose), as in conv_split16.hip */
-#define SFC_DMA_WX(pk_, half_, slot_) do {} while (0)
-#else
-#define SFC_DMA_WX(pk_, half_, slot_) SFC_DMA_W(pk_, half_, slot_)
-#endif
-
     int paddr[3];                                                   // [column tap]: pixel half 0; half 1 is 16 pixels = 2 048 bytes further (SF_SWZ16(px + 16) = SF_SWZ16(px)): an immediate
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
@@ -1057,19 +920,11 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
             float v = accp[n][q][j];                                // (shared half + bias are already in: initial C of the tile)
             const float sv = v * slope;
             asm("v_max_f32 %0, %1, %2" : "=v"(v) : "v"(v), "v"(sv));
-            sf_store_b32<SF_STORE_AUX>(v + rv[j], rsO, evoff + j * 256, (q >> 1) * 4096 + (q & 1) * 64);
+            sf_store_b32<SF_OUT_AUX>(v + rv[j], rsO, evoff + j * 256, (q >> 1) * 4096 + (q & 1) * 64);
         }
     };
     auto quarter_finish = [&](int n, int q) __attribute__((always_inline)) { quarter_finish_with(n, q, rres[q & 1]); };
 #define SFC_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#ifndef SFC_SPREAD_HALO
-#define SFC_SPREAD_HALO 0
-#endif
-#ifdef PFNL_SFC_TIMING   /* phase timeline of the chain kernel (tools/sfc_timing.py); not part of the product build */
-#define SFC_STAMP() do { if (lane == 0 && (wave == 0 || wave == 5) && dbg_n < 160) sfc_dbg[(blockIdx.x * 2 + (wave != 0)) * 160 + dbg_n++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define SFC_STAMP() do {} while (0)
-#endif
 
     // ---- prologue: halo of unit 0 (the first chain's shared half: `base`) and its weights (pack 0 = shared half, channel half 0)
     int c_f, c_clip, c_y0, c_x0, n_f, n_clip, n_y0, n_x0;
@@ -1110,15 +965,10 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
             const int nx_pk = PAR == 0 ? w_pk : (n_f != 0);
             const int nx_half = half_a ^ 1;
             const bool w_replace = PAR == 0 || nx_pk != w_pk;       // (wave-uniform; unit B -> next A only at the two ends of a chain)
-            SFC_STAMP();                                            // 0: unit start
             // operands: X[halo row of the column tap][pixel half][hi / lo'], Wv[row tap][output tile][hi / lo'] - never more than ~16 of the 28 live: every
             // register set is refilled for the next sub-step behind the MFMAs that read it last
             sfh8 X[4][2][2], Wv[3][2][2];
-#ifdef SF_X_PXLIN   /* experiment: linear (conflict-free) pixel operand reads - wrong results on purpose: where do the bank conflicts come from? */
-#define SF_PX16(kx_, ph_, r_, part_) (*reinterpret_cast<const sfh8*>(tile + lane * 16 + ((kx_) * 16 + (ph_) * 8 + (r_) * 2 + (part_)) * 1024))
-#else
 #define SF_PX16(kx_, ph_, r_, part_) (*reinterpret_cast<const sfh8*>(tile + (paddr[kx_] ^ ((part_) ? lo_xor : 0)) + (r_) * (SF_IW * 128) + (ph_) * 2048))
-#endif
 #define SF_WT16(kx_, ky_, ct_, part_) (*reinterpret_cast<const sfh8*>(wlane + (((kx_) * 3 + (ky_)) << 13) + (((ct_) * 2 + (part_)) << 10)))
             // (in the order the first sub-step uses them: LDS returns are in order, so its first MFMA waits for two reads, not for twelve)
             Wv[0][0][0] = SF_WT16(0, 0, 0, 0);
@@ -1136,7 +986,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
             __builtin_amdgcn_sched_barrier(0);
             // slice 2 of THIS unit's weights (its slot was free only after the previous unit's closing barrier), then the next
             // unit's halo; one fence load covers both (slice 2 is first read after b0, the halo after this unit's closing barrier)
-            if (w_slice2_owed) SFC_DMA_WX(w_pk, half_u, 2);
+            if (w_slice2_owed) SFC_DMA_W(w_pk, half_u, 2);
             const int q_f = PAR == 0 ? c_f : n_f, q_clip = PAR == 0 ? c_clip : n_clip, y0q = PAR == 0 ? c_y0 : n_y0, x0q = PAR == 0 ? c_x0 : n_x0;
             const float* const qsrc = q_f == 0 ? p.in2 + (size_t)q_clip * H * W * 64 : p.in + ((size_t)q_clip * T + (q_f - 1)) * H * W * 64;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(qsrc), 0, item_bytes, 0x00020000);
@@ -1162,22 +1012,17 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
                 if constexpr (S == 7) quarter_finish(PAR, 3);
                 if constexpr (ky == 0) {
                     if constexpr (kx == 1) {
-                        SFC_STAMP();                                // 1: column tap 0 done
                         asm volatile("" ::"v"(fence));              // slice 2 of this unit's weights has landed (and the halo, as it happens)
-                        SFC_STAMP();                                // 2: fence passed
                         SFC_BARRIER();                              // b0: column tap 0 consumed; slice 2 complete
-                        SFC_STAMP();                                // 3: past b0
-                        if (w_replace) SFC_DMA_WX(nx_pk, nx_half, 0);
+                        if (w_replace) SFC_DMA_W(nx_pk, nx_half, 0);
                         if constexpr (PAR == 0) {                   // decode the next tile (past the end: this one again - a harmless re-read)
                             const int kn = min(kt + 1, nt_tiles - 1);
                             decode(kn, n_f, n_clip, n_y0, n_x0);
                         }
                     }
                     if constexpr (kx == 2) {
-                        SFC_STAMP();                                // 4: column tap 1 done
                         SFC_BARRIER();                              // b1: column tap 1 consumed
-                        SFC_STAMP();                                // 5: past b1
-                        if (w_replace) SFC_DMA_WX(nx_pk, nx_half, 1);
+                        if (w_replace) SFC_DMA_W(nx_pk, nx_half, 1);
                         fence_w = __builtin_amdgcn_raw_buffer_load_b32(rs, 0, 0, 0);   // covers slices 0 and 1 of the next unit's weights
                     }
                 }
@@ -1258,9 +1103,7 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
             row_setup(PAR ^ 1);                                     // the NEXT unit's epilogue row (unit A: row 0 of the tile that has just been folded; unit B: row 1)
             quarter_request(0);
             quarter_request(1);
-            SFC_STAMP();                                            // 6: groups 4-5 done
             asm volatile("" ::"v"(fence), "v"(fence_w));            // the next unit's halo and weight slices 0, 1 have landed
-            SFC_STAMP();                                            // 7: fences passed
             SFC_BARRIER();                                          // b2
         };
         unit(std::integral_constant<int, 0>{});
@@ -1384,9 +1227,3 @@ hipError_t launch_sf_to_f32(const uint16_t* in, float* out, size_t npix, hipStre
 }
 
 }  // namespace pfnl
-
-#ifdef PFNL_SFC_TIMING
-extern "C" int pfnl_debug_read_sfc_stamps(long long* host, size_t n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pfnl::sfc_dbg), n * sizeof(long long)) == hipSuccess ? 0 : -1;
-}
-#endif

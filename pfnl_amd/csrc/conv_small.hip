@@ -38,13 +38,6 @@ constexpr int CM_NQ = CM_NW / 2;                                    // K parts t
 constexpr int CM_CGW = 8 / CM_NW;                                   // 16-channel groups of a source per wave (1)
 constexpr int CM_ASUM_MAX = 7;                                      // partial tensors a summed source can have (T <= 7)
 
-#ifdef PFNL_CM_TIMING   /* phase timeline of a workgroup (tools/cm_timing.py); not part of the product build */
-__device__ long long cm_dbg[4096 * 16];
-#define CM_STAMP(i_) do { if (tid == 0 && blockIdx.x < 4096) cm_dbg[blockIdx.x * 16 + (i_)] = wall_clock64(); } while (0)
-#else
-#define CM_STAMP(i_) do {} while (0)
-#endif
-
 template <int KS, int R>
 struct CmGeom {
     static constexpr int IH = R + KS - 1, IW = 32 + KS - 1;
@@ -187,9 +180,7 @@ __global__ __launch_bounds__(CM_THREADS, 1) void conv_small_kernel(ConvSmallPara
         const int col = (lane & 31) + kx;
         paddr[kx] = col * 256 + ((((kq >> 1) * 8 + (kq & 1) * 2 + (lane >> 5)) ^ (col & 15)) << 4);
     }
-    CM_STAMP(0);
     request(0, std::true_type{});                                   // (ahead of the weight ring: the summed source is register-hungry)
-    CM_STAMP(1);
     // weights: this wave's steps are contiguous: [kq][nt][source][tap][part][lane] x 16 B
     const cmu4* const wsrc = reinterpret_cast<const cmu4*>(p.wpack) + ((size_t)(kq * 2 + nt) * ntot) * 128 + lane;
     cmu4 wring[G::RING][2];
@@ -216,9 +207,7 @@ __global__ __launch_bounds__(CM_THREADS, 1) void conv_small_kernel(ConvSmallPara
 
 
     commit(0);
-    CM_STAMP(2);
     __syncthreads();
-    CM_STAMP(3);
     for (int c = 0; c < nsrc; ++c) {
         const unsigned char* const tile = cm_smem + (c & 1) * G::BUF_BYTES;
         const bool more = c + 1 < nsrc;                             // (wave-uniform)
@@ -268,11 +257,9 @@ __global__ __launch_bounds__(CM_THREADS, 1) void conv_small_kernel(ConvSmallPara
             step(std::integral_constant<int, 7>{});
             step(std::integral_constant<int, 8>{});
         }
-        if (c == 0) CM_STAMP(4);
         if (more) commit((c & 1) ^ 1);
         __syncthreads();                                            // the next source is complete; this one's buffer is free
     }
-    CM_STAMP(5);
 
     // ---- the two K halves meet in LDS (the halo buffers are free now): [kh][row][pixel] x 256 B
     constexpr int EP = (R * 32 * 16) / CM_THREADS;
@@ -293,7 +280,6 @@ __global__ __launch_bounds__(CM_THREADS, 1) void conv_small_kernel(ConvSmallPara
             for (int i = 0; i < 16; ++i) red[(r * 32 + drow(i, lane)) * 64] = accm[r][i] + accc[r][i] * (1.0f / 2048.0f);
     }
     __syncthreads();
-    CM_STAMP(6);
     const float slope = p.act ? 0.2f : 1.0f;
     const f32x4 bias4 = *reinterpret_cast<const f32x4*>(p.bias + (tid & 15) * 4);
 #pragma unroll
@@ -322,7 +308,6 @@ __global__ __launch_bounds__(CM_THREADS, 1) void conv_small_kernel(ConvSmallPara
             *reinterpret_cast<f32x4*>(p.out + o) = v;
         }
     }
-    CM_STAMP(7);
     if constexpr (XS) {
         // ---- X stage: conv10_i's partial of this frame, W10_t^T . tile (K = 64: one k-step per wave, three MFMAs per row); the four
         // K parts meet in the same LDS area the 3x3 used; the sum leaves as fp32 NHWC - the NEXT launch (conv2_i) adds the T partials
@@ -528,9 +513,3 @@ void conv_small_pack_weights(const float* hwio, int ks, int nsrc, int cout, uint
 }
 
 }  // namespace pfnl
-
-#ifdef PFNL_CM_TIMING
-extern "C" int pfnl_debug_read_cm_stamps(long long* host, size_t n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pfnl::cm_dbg), n * sizeof(long long)) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -33,24 +33,16 @@
 #include "common.h"
 #include "conv_split16.h"
 
-#ifndef CS_STORE_AUX
-#define CS_STORE_AUX 17     // cache-policy bits of the output stores: sc0 sc1 = written through, not kept in L2.  Measured on
-                            // configs[1] (tools/s16_variants.sh, same box, ms per step): 0 (default policy) 5.43, nt 5.43, sc1 5.33,
-                            // sc0 sc1 5.30, sc1 nt 5.49 - the 117 MB an output tensor has are not read back through this L2
-                            // before they are evicted anyway; kept out, they leave it to the halo rows, weights and addend tiles.
-                            // (residual loads with sc1 or nt: no further gain; halo loads with nt: worse)
-#endif
-#ifndef CS_RESID_AUX
-#define CS_RESID_AUX 0      // ... of the residual loads
-#endif
-#ifndef CS_LATE_FINISH
-#define CS_LATE_FINISH 1    // per-frame variant: store pieces 2, 3 finished 4-5 sub-steps after their addend / residual requests
-#endif
-#ifndef CS_HALO_AUX
-#define CS_HALO_AUX 0       // ... of the halo loads
-#endif
-
 namespace pfnl {
+
+constexpr int CS_OUT_AUX = 17;        // cache-policy bits of the output stores: sc0 sc1 = written through, not kept in L2.  Measured on
+                                      // configs[1] (same box, ms per step): 0 (default policy) 5.43, nt 5.43, sc1 5.33, sc0 sc1 5.30,
+                                      // sc1 nt 5.49 - the 117 MB an output tensor has are not read back through this L2 before they
+                                      // are evicted anyway; kept out, they leave it to the halo rows, weights and addend tiles.
+                                      // (residual loads with sc1 or nt: no further gain; halo loads with nt: worse)
+constexpr int CS_RESID_AUX = 0;       // ... of the residual loads
+constexpr int CS_HALO_AUX = 0;        // ... of the halo loads
+constexpr bool CS_LATE_FINISH = true; // per-frame variant: store pieces 2, 3 finished 4-5 sub-steps after their addend / residual requests
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -70,29 +62,7 @@ constexpr int CS_WITERS = CS_SLOT_BYTES / 16 / CS_THREADS;          // 3 pieces 
 constexpr float CS_SCALE = 2048.0f, CS_ISCALE = 1.0f / 2048.0f;
 static_assert(CS_SLOT_BYTES % (16 * CS_THREADS) == 0, "slot copy must divide evenly");
 
-#ifdef PFNL_S16_TIMING   /* phase timeline of the kernel (tools/s16_timing.py); not part of the product build */
-__device__ long long cs_dbg[256 * 2 * 128];
-#define CS_STAMP() do { if (lane == 0 && (wave == 0 || wave == 5) && dbg_n < 128) cs_dbg[(blockIdx.x * 2 + (wave != 0)) * 128 + dbg_n++] = __builtin_readcyclecounter(); } while (0)
-#else
-#define CS_STAMP() do {} while (0)
-#endif
-
 __device__ __forceinline__ f32x16 mfma_f16(h8 a, h8 b, f32x16 c) {
-#ifdef CS_X_NOMFMA   /* timing experiments only (wrong results on purpose) */
-    c[0] += (float)a[0] * (float)b[0];
-    return c;
-#endif
-#ifdef PFNL_X_MFMA16   /* timing experiment only (wrong results on purpose): the same FLOPs as two v_mfma_f32_16x16x32_f16 on the same operand registers */
-    {
-        typedef float f32x4_ __attribute__((ext_vector_type(4)));
-        f32x4_ lo = {c[0], c[1], c[2], c[3]}, hi = {c[4], c[5], c[6], c[7]};
-        lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, lo, 0, 0, 0);
-        hi = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, hi, 0, 0, 0);
-        c[0] = lo[0]; c[1] = lo[1]; c[2] = lo[2]; c[3] = lo[3];
-        c[4] = hi[0]; c[5] = hi[1]; c[6] = hi[2]; c[7] = hi[3];
-        return c;
-    }
-#endif
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
@@ -106,26 +76,15 @@ __device__ __forceinline__ f32x16 mfma_f16(h8 a, h8 b, f32x16 c) {
 // consumer of MFMA results gets none of the XDL -> VALU wait states the compiler pads its own instructions with (round 5: a fold written
 // this way read the cross-term accumulator one MFMA after it was issued - repeatable at -O3, caught as run-to-run noise of 1e-7 by the -O1
 // ASAN build); the folds of accumulators therefore stay compiler-generated.
-#ifndef CS_SCALAR_F32
-#define CS_SCALAR_F32 1
-#endif
 __device__ __forceinline__ f32x4 mul4s(f32x4 v, float s) {
-#if CS_SCALAR_F32
     f32x4 r;
     asm("v_mul_f32 %0, %4, %5\n\tv_mul_f32 %1, %4, %6\n\tv_mul_f32 %2, %4, %7\n\tv_mul_f32 %3, %4, %8"
         : "=&v"(r.x), "=&v"(r.y), "=&v"(r.z), "=&v"(r.w) : "s"(s), "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
     return r;
-#else
-    return v * s;
-#endif
 }
 __device__ __forceinline__ void split4(f32x4 v, u32x2& hi, u32x2& lo, float nscale) {
     const h4 h = __builtin_convertvector(v, h4);                    // 2 x v_cvt_pk_f16_f32
     hi = __builtin_bit_cast(u32x2, h);
-#ifdef CS_X_PLAINSPLIT
-    const f32x4 r = (v - __builtin_convertvector(h, f32x4)) * CS_SCALE;
-    lo = __builtin_bit_cast(u32x2, __builtin_convertvector(r, h4));
-#else
     const f32x4 t = mul4s(v, CS_SCALE);                             // exact
     unsigned l0, l1;
     asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(hi.x), "s"(nscale), "v"(t.x));
@@ -133,7 +92,6 @@ __device__ __forceinline__ void split4(f32x4 v, u32x2& hi, u32x2& lo, float nsca
     asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(hi.y), "s"(nscale), "v"(t.z));
     asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l1) : "v"(hi.y), "s"(nscale), "v"(t.w));
     lo = u32x2{l0, l1};
-#endif
 }
 
 // MODE 0: out = act(conv + bias).   MODE 1 (FUSE; conv2_i per-frame half): out = act(conv + bias + addend[item / add_div]) + resid.
@@ -157,12 +115,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef PFNL_S16_TIMING
-    int dbg_n = 0;
-#endif
-#ifdef CS_PRIO_LATE   /* experiment: waves 4-7 (the younger wave of every SIMD) above waves 0-3 */
-    if (wave >= 4) __builtin_amdgcn_s_setprio(CS_PRIO_LATE);
-#endif
     const int rp = wave >> 1;                                       // rows 2rp, 2rp+1 of the tile
     const int mt = wave & 1;                                        // output channels 32mt .. 32mt+31
     const int H = p.H, W = p.W;
@@ -208,7 +160,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
         int pix = id >> 3;
         const int c = id & 7;
         // the two pixels of a 16-lane ds_write_b64 group are 8 apart, not neighbours: their hi halves (and then their lo' halves) fall on
-        // different banks (see conv3x3_c1c10_kernel, K1_COMMIT_PAIR8: SQ_LDS_BANK_CONFLICT 1.3e6 -> 9e4 per launch)
+        // different banks (see conv3x3_c1c10_kernel, halo commit: SQ_LDS_BANK_CONFLICT 1.3e6 -> 9e4 per launch)
         if (pix < (CS_IH * CS_IW & ~15)) pix = (pix & ~15) | ((pix & 1) << 3) | ((pix & 15) >> 1);
         const int py = pix / CS_IW, px = pix - py * CS_IW;
         grel[k] = py * wbytes + px * 256 + c * 16;
@@ -234,9 +186,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
         const_cast<float*>(p.in) + (size_t)item_q_ * H * W * 64, 0, item_bytes, 0x00020000);     \
     const int org_ = ((y0_ - 1) * W + x0_ - 1) * 256 + CS_HALF(u_) * 128;                        \
     const bool interior_ = y0_ > 0 && y0_ + CS_IH - 1 <= H && x0_ > 0 && x0_ + CS_IW - 1 <= W
-#ifdef CS_X_NOCOMMIT   /* timing experiments only */
-#define CS_COMMIT1(k_, buf_) do { if (stg[k_].x == 1.2345e30f) *reinterpret_cast<f32x4*>(cs_smem) = stg[k_]; } while (0)
-#else
 #define CS_COMMIT1(k_, buf_)                                                                     \
     do {                                                                                         \
         u32x2 hi_, lo2_;                                                                         \
@@ -245,7 +194,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
         *reinterpret_cast<u32x2*>(cs_smem + (buf_) * CS_TILE_BYTES + lo_) = hi_;                 \
         *reinterpret_cast<u32x2*>(cs_smem + (buf_) * CS_TILE_BYTES + (lo_ ^ 64)) = lo2_;   /* lo' chunk = hi chunk ^ 4 */ \
     } while (0)
-#endif
 
     // operand addresses: pixel operand of (column tap kx, k-step ks, part) = chunk 4*part + 2*ks + (lane >> 5) of halo pixel
     // (row 2*rp + ..., column (lane & 31) + kx); weights: 16 bytes per lane
@@ -314,16 +262,8 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                 const_cast<float*>(p.resid) + (size_t)eitemp * H * W * 64, 0, item_bytes, 0x00020000);
             const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float*>(p.addend) + (size_t)(eitemp / p.add_div) * H * W * 64, 0, item_bytes, 0x00020000);
-#ifdef CS_X_NOADDEND   /* timing experiments only (wrong results on purpose): the load is issued, always to the same cached line */
-            radd[k & 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (tid & 15) * 16, 0, 0));
-#else
             radd[k & 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, soff0, k * wbytes2, 0));
-#endif
-#ifdef CS_X_NORESID
-            rres[k & 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, (tid & 15) * 16, 0, 0));
-#else
             rres[k & 1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsR, soff0, k * wbytes2, CS_RESID_AUX));
-#endif
         }
     };
     // A store piece is taken in two steps one sub-step apart - the scratch read, then arithmetic + store - so that the LDS
@@ -351,13 +291,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
         f32x4 v = src;
         if constexpr (FUSE) v += radd[k & 1];
         if constexpr (ACCUM) v += bias4;
-#ifdef CS_X_PKSLOPE
-        const f32x4 sv = mul4s(v, slope);
-        v.x = fmaxf(v.x, sv.x);
-        v.y = fmaxf(v.y, sv.y);
-        v.z = fmaxf(v.z, sv.z);
-        v.w = fmaxf(v.w, sv.w);
-#else
         {                                                           // leaky_relu(0.2) or identity (slope 1), branch-free
             const f32x4 sv = mul4s(v, slope);
             asm("v_max_f32 %0, %1, %2" : "=v"(v.x) : "v"(v.x), "v"(sv.x));   // (fmaxf adds a canonicalising v_max x,x,x per element)
@@ -365,11 +298,8 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
             asm("v_max_f32 %0, %1, %2" : "=v"(v.z) : "v"(v.z), "v"(sv.z));
             asm("v_max_f32 %0, %1, %2" : "=v"(v.w) : "v"(v.w), "v"(sv.w));
         }
-#endif
         if constexpr (FUSE) v += rres[k & 1];
-#ifndef CS_REQ_AFTER_STORE
         if (next >= 0) fuse_request(next);
-#endif
         if constexpr (OSF) {
             if ((k & 1) == 0) {
                 osf_hold = v;                                       // channels 8cg .. 8cg+3: wait for the other half of the group
@@ -377,21 +307,15 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                 u32x2 h0, l0, h1, l1;
                 split4(osf_hold, h0, l0, nscale);
                 split4(v, h1, l1, nscale);
-                buffer_store_b128_guarded<CS_STORE_AUX>(u32x4{h0.x, h0.y, h1.x, h1.y}, rsO, soff0, (k >> 1) * 2 * wbytes2);
-                buffer_store_b128_guarded<CS_STORE_AUX>(u32x4{l0.x, l0.y, l1.x, l1.y}, rsO, (int)((unsigned)soff0 + 64u), (k >> 1) * 2 * wbytes2);
+                buffer_store_b128_guarded<CS_OUT_AUX>(u32x4{h0.x, h0.y, h1.x, h1.y}, rsO, soff0, (k >> 1) * 2 * wbytes2);
+                buffer_store_b128_guarded<CS_OUT_AUX>(u32x4{l0.x, l0.y, l1.x, l1.y}, rsO, (int)((unsigned)soff0 + 64u), (k >> 1) * 2 * wbytes2);
             }
         } else {
-#ifdef CS_X_NOSTORE   /* timing experiments only */
-            if (v.x == 1.2345e30f)
-#endif
-            buffer_store_b128_guarded<CS_STORE_AUX>(__builtin_bit_cast(u32x4, v), rsO, soff0, k * wbytes2);   // (common.h: store-data hazard)
+            buffer_store_b128_guarded<CS_OUT_AUX>(__builtin_bit_cast(u32x4, v), rsO, soff0, k * wbytes2);   // (common.h: store-data hazard)
         }
     };
     auto piece_finish = [&](int k, int next = -1) __attribute__((always_inline)) {
         piece_finish_from(pv, k, next);
-#ifdef CS_REQ_AFTER_STORE   /* the order before this was measured */
-        if (next >= 0) fuse_request(next);
-#endif
     };
     auto store_piece = [&](const unsigned char* scratch, int k) __attribute__((always_inline)) {
         piece_read(scratch, k);
@@ -403,18 +327,14 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
     // into vmcnt(0) - the halo commit would then wait for the stores issued a moment earlier: measured.)
     [[maybe_unused]] u32x4 wnx[CS_WITERS];
     auto w_request = [&](int half, int slot) __attribute__((always_inline)) {
-#ifndef CS_X_NOSWAP   /* timing experiments only */
         const u32x4* src = reinterpret_cast<const u32x4*>(p.wpack) + (size_t)half * (CS_W_BYTES / 16) + slot * (CS_SLOT_BYTES / 16);
 #pragma unroll
         for (int k = 0; k < CS_WITERS; ++k) wnx[k] = src[k * CS_THREADS + tid];
-#endif
     };
     auto w_write = [&](int slot) __attribute__((always_inline)) {
-#ifndef CS_X_NOSWAP
         u32x4* dst = reinterpret_cast<u32x4*>(wl + slot * CS_SLOT_BYTES);
 #pragma unroll
         for (int k = 0; k < CS_WITERS; ++k) dst[k * CS_THREADS + tid] = wnx[k];
-#endif
     };
     // Workgroup barrier of the main loop: this wave's ds_writes complete (lgkmcnt), then s_barrier - without the memory-model
     // fences of __syncthreads() (nothing here communicates through global memory); the "memory" clobber keeps the compiler
@@ -456,7 +376,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
             const unsigned char* const tile = cs_smem + cb * CS_TILE_BYTES;
             unsigned char* const other = cs_smem + (cb ^ 1) * CS_TILE_BYTES;
             [[maybe_unused]] const int u = 2 * kt + PAR;
-            CS_STAMP();                                             // 0: unit start
             // weights of unit B (the other channel half) follow the column taps unit A has consumed.  A slice must be in LDS
             // before the barrier that precedes its first operand prefetch (issued one sub-step before its group):
             //   tap 0: requested here, written in group 3 of unit A (free since b0; read from unit B's start, after b2)
@@ -493,9 +412,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                 const_cast<float*>(p.in) + (size_t)q_item * H * W * 64, 0, item_bytes, 0x00020000);
             const int org = ((y0q - 1) * W + x0q - 1) * 256 + q_half * 128;
             const bool interior = y0q > 0 && y0q + CS_IH - 1 <= H && x0q > 0 && x0q + CS_IW - 1 <= W;
-#if !defined(CS_X_NOLOAD) && !defined(CS_SPREAD_REQ)
             CS_REQUEST_ALL(rs, org, interior, y0q, x0q);
-#endif
             piece_setup(PAR);                                       // epilogue pass PAR of the previous tile (nothing pending: out of range)
 
             [[maybe_unused]] f32x16 bias16;                         // register r of a lane = channel ech + r
@@ -530,10 +447,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                         }
                     }
                     if constexpr (g == 2) {
-                        CS_STAMP();                                 // 1: groups 0-1 done
                         CS_BARRIER();                              // b0: scratch complete; column tap 0 of the weights consumed
-                        CS_STAMP();                                 // 2: past b0
-                        CS_STAMP();                                 // 3
                         piece_read(other, 0);
                     }
                     if constexpr (g == 3) {
@@ -556,15 +470,11 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                         }
                     }
                     if constexpr (g == 4) {
-                        CS_STAMP();                                 // 4: groups 2-3 done
                         CS_BARRIER();                              // b1: scratch read; column tap 1 consumed
-                        CS_STAMP();                                 // 5: past b1
-                        CS_STAMP();                                 // 6
 #pragma unroll
                         for (int k = 0; k < CS_ITERS; ++k) asm volatile("" : "+v"(lpk[k]));   // opaque: addresses derived from it are not hoisted into registers
 #pragma unroll
                         for (int k = 0; k < CS_ITERS / 2; ++k) CS_COMMIT1(k, cb ^ 1);
-                        CS_STAMP();                                 // 7: first half of the halo committed
                     }
                     if constexpr (g == 5) {
 #pragma unroll
@@ -578,13 +488,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                         }
                     }
                 }
-#if defined(CS_SPREAD_REQ) && !defined(CS_X_NOLOAD)   /* experiment: one halo request per sub-step instead of six at the unit's start */
-                if constexpr (S < CS_ITERS) {
-                    const int gy_ = y0q + ((lpk[S] >> 16) & 0xff) - 1, gx_ = x0q + ((unsigned)lpk[S] >> 24) - 1;
-                    const bool in_ = interior || ((unsigned)gy_ < (unsigned)H && (unsigned)gx_ < (unsigned)W);
-                    stg[S] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, in_ ? org + grel[S] : 0x7fffffff, 0, CS_HALO_AUX));
-                }
-#endif
                 if constexpr (S == 7) {
                     piece_finish(0, 2);
                     piece_read(other, 1);
@@ -605,11 +508,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // --- operands of the next sub-step
-#ifdef CS_X_NOREAD   /* timing experiments only */
-                if constexpr (false) {
-#else
                 if constexpr (S < 17) {
-#endif
                     constexpr int S1 = S + 1, g1 = S1 / 3, ky1 = S1 % 3;
                     Wv[S1 & 1][0] = CS_WT(g1, ky1, 0);
                     Wv[S1 & 1][1] = CS_WT(g1, ky1, 1);
@@ -694,11 +593,8 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
                 c_item = n_item;                                    // on to the next tile
                 c_y0 = n_y0;
                 c_x0 = n_x0;
-#ifndef CS_X_NOEPI   /* timing experiments only */
                 pending = true;
-#endif
             }
-            CS_STAMP();                                             // 8: groups 4-5 done
             CS_BARRIER();                                          // b2: this unit's buffer is free, the next unit's is complete
         };
         unit(std::integral_constant<int, 0>{});
@@ -762,7 +658,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_split16_kernel(ConvSpli
 //   * behind the chain's last frame `base_m` (+ bias: its initial value) takes the same road - leaky-relu, split, lines - to `out2`.
 // conv10_i as a launch of its own read inp1 (117 MB at configs[1]) back for 11 % of conv1_i's MFMAs; here it reads nothing.
 // The weight slices travel by LDS-DMA (no staging registers) and the halo pieces' source offsets are recomputed: 254 VGPRs.
-// The serial phase is ~4.5 - 5.5 k shader cycles per tile of ~26 k (tools/k1_timing.py: barrier waits 1.5 k, two dumps 1.1 k, the
+// The serial phase is ~4.5 - 5.5 k shader cycles per tile of ~26 k (measured phase stamps: barrier waits 1.5 k, two dumps 1.1 k, the
 // two passes of operand / line reads + 12 MFMAs 2 - 2.7 k); rearranging it moves the launch time by nothing - the launch runs at the
 // pace the power cap gives its MFMAs; what the fusion saves is the 117 MB and a launch.
 
@@ -774,15 +670,7 @@ __device__ __forceinline__ void k1_dma16(__amdgpu_buffer_rsrc_t rs, unsigned lds
                  : "=&s"(keep) : "v"(voff), "s"(lds_dst), "s"(rs), "s"(soff) : "memory");
 }
 
-#ifndef K1_W10_AT
-#define K1_W10_AT 16          // sub-step of a tile's second unit at which conv10_i's operands are requested
-#endif
-#ifndef K1_STORE_AUX
-#define K1_STORE_AUX CS_STORE_AUX
-#endif
-#ifndef K1_COMMIT_PAIR8
-#define K1_COMMIT_PAIR8 1     // halo commit: the two pixels of a 16-lane ds_write_b64 group are 8 apart (bank-conflict-free), not neighbours
-#endif
+constexpr int K1_W10_AT = 16;                                      // sub-step of a tile's second unit at which conv10_i's operands are requested
 constexpr int K1_LDS_BYTES = CS_LDS_BYTES + 64 * 4;                 // + conv10_i's bias
 // ISF (round 6): `in` is the SPLIT-FORMAT copy of inp0 that conv3x3_sf_chain_kernel<true> writes next to the fp32 one (conv_sf.hip): the
 // halo of a unit travels HBM -> LDS by LDS-DMA in operand form (43 wave instructions of 1 KB, the XOR swizzle applied to the source
@@ -807,12 +695,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef PFNL_S16_TIMING
-    int dbg_n = 0;
-#endif
-#if PFNL_S16_PRIO
-    if (wave >= 4) __builtin_amdgcn_s_setprio(PFNL_S16_PRIO);      // the younger wave of every SIMD above the older one (tools/ubench/conv_core V3)
-#endif
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);                  // the younger wave of every SIMD above the older one (tools/ubench/conv_core V3)
     const int rp = wave >> 1;                                       // rows 2rp, 2rp+1 of the tile
     const int mt = wave & 1;                                        // output channels 32mt .. 32mt+31 (of conv1_i and of conv10_i)
     const int H = p.H, W = p.W;
@@ -871,13 +754,11 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         const int id = k * CS_THREADS + tid < CS_PIECES ? k * CS_THREADS + tid : CS_PIECES - 8 + (tid & 7);
         int pix = id >> 3;
         const int c = id & 7;
-#if K1_COMMIT_PAIR8
         // a ds_write_b64 is served 16 lanes (two pixels of 8 pieces) at a time over 32 banks = one 128-byte pixel slot: with pixels p, p + 1
         // both hi halves (and then both lo' halves) fall on the same 16 banks - 2-way conflicts on every commit (SQ_LDS_BANK_CONFLICT 1.3e6
         // per launch, profiles/r04_pmc.md).  Paired as (p, p + 8) the swizzle term (px >> 1) & 7 differs in bit 2: one pixel's hi half
         // occupies the banks of the other's lo' half.  (the last 4 pixels of the 340 keep their order)
         if (pix < (CS_IH * CS_IW & ~15)) pix = (pix & ~15) | ((pix & 1) << 3) | ((pix & 15) >> 1);
-#endif
         const int py = pix / CS_IW, px = pix - py * CS_IW;
         lpk[k] = ((py * CS_IW + px) * 128 + 8 * (c & 1) + (((c >> 1) ^ ((px >> 1) & 7)) << 4)) | (py << 16) | (px << 24);
     }
@@ -894,14 +775,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
             K1_HALO_LOAD(stg[k_], rs_, in_ ? off_ : 0x7fffffff);                                  \
         }                                                                                        \
     } while (0)
-#ifdef K1_X_NOLOAD    /* timing experiments only (wrong results on purpose; tools/variant_run_r4.sh) */
-#define K1_HALO_LOAD(dst_, rs_, off_) do { dst_ = f32x4{(float)(off_), 0.25f, -0.5f, 1.5f}; } while (0)
-#else
 #define K1_HALO_LOAD(dst_, rs_, off_) do { dst_ = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_, off_, 0, CS_HALO_AUX)); } while (0)
-#endif
-#ifdef K1_X_NOCOMMIT  /* timing experiments only: no split arithmetic, no ds_write of the halo (the MFMAs run on stale LDS) */
-#define K1_COMMIT1(k_, buf_) do { if (stg[k_].x == 1.2345e30f) *reinterpret_cast<f32x4*>(cs_smem) = stg[k_]; } while (0)
-#else
 #define K1_COMMIT1(k_, buf_)                                                                     \
     do {                                                                                         \
         u32x2 hi_, lo2_;                                                                         \
@@ -910,7 +784,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         *reinterpret_cast<u32x2*>(cs_smem + (buf_) * TILE_BYTES + lo_) = hi_;                    \
         *reinterpret_cast<u32x2*>(cs_smem + (buf_) * TILE_BYTES + (lo_ ^ 64)) = lo2_;            \
     } while (0)
-#endif
 
     int paddr[3];
 #pragma unroll
@@ -948,11 +821,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         _Pragma("unroll") for (int k_ = 0; k_ < 3; ++k_)                                         \
             k1_dma16(rw_, ldsw + (slot_) * CS_SLOT_BYTES + (wave + 8 * k_) * 1024, wvoff, (half_) * CS_W_BYTES + (slot_) * CS_SLOT_BYTES + k_ * 8192); \
     } while (0)
-#ifdef PFNL_X_NOWSTREAM   /* timing experiment only (wrong results on purpose): no weight replacement - what does the 73 KB per tile from L2 cost? */
-#define K1_DMA_WX(half_, slot_) do {} while (0)
-#else
-#define K1_DMA_WX(half_, slot_) K1_DMA_W(half_, slot_)
-#endif
 #define K1_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
     // ---- a finished row (n) of the workgroup's tile: leaky-relu, split, 128 pixel lines in `scratch`; optionally conv10_i's
@@ -1026,7 +894,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         const int id = (j & 3) * CS_THREADS + tid, ppx = id >> 4, c = id & 15;
         const int gy = hy0 + 2 * (ppx >> 5) + (j >> 2), gx = hx0 + (ppx & 31);   // rows past the image: past the end of the resource
         const int off = (gy * W + gx) * 256 + c * 16;
-        buffer_store_b128_guarded<K1_STORE_AUX>(held[j], rsO, (hpend & (gx < W)) ? off : 0x7fffffff, 0);
+        buffer_store_b128_guarded<CS_OUT_AUX>(held[j], rsO, (hpend & (gx < W)) ? off : 0x7fffffff, 0);
     };
     auto base_init = [&](bool zero) __attribute__((always_inline)) {   // conv10_i's bias: the initial value of a chain's sum (parts > 0 of a split chain: 0)
 #pragma unroll
@@ -1074,7 +942,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
             constexpr int cb = PAR;
             const unsigned char* const tile = cs_smem + cb * TILE_BYTES;
             h8 X[4][2], Wv[2][2];
-            CS_STAMP();                                             // 0 / 1: unit A / B start
 #define CS_PX(g_, r_, part_) (*reinterpret_cast<const h8*>(tile + (paddr[(g_) >> 1] ^ (((part_) ? lo_xor : 0) | (((g_) & 1) << 5))) + (r_) * (CS_IW * 128)))
 #define CS_WT(g_, ky_, part_) (*reinterpret_cast<const h8*>(wlane + (((g_) * 3 + (ky_)) << 12) + ((part_) << 10)))
             X[0][0] = CS_PX(0, 0, 0);
@@ -1088,7 +955,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
             [[maybe_unused]] unsigned fence_w = 0;
             const __amdgpu_buffer_rsrc_t rsf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), 0, 256, 0x00020000);
             if constexpr (PAR == 1) {
-                K1_DMA_WX(half_a ^ 1, 2);
+                K1_DMA_W(half_a ^ 1, 2);
                 fence_w = __builtin_amdgcn_raw_buffer_load_b32(rsf, 0, 0, 0);
             }
             // the NEXT unit's halo: unit A asks for the other half of ITS tile, unit B for the first half of the next tile
@@ -1129,7 +996,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                     if constexpr (g == 2) {
                         if constexpr (PAR == 1) asm volatile("" ::"v"(fence_w));   // tap 2 of this unit's weights has landed
                         K1_BARRIER();                               // b0: column tap 0 of the weights consumed (unit B: tap 2 complete)
-                        if constexpr (PAR == 0) K1_DMA_WX(half_a ^ 1, 0);
+                        if constexpr (PAR == 0) K1_DMA_W(half_a ^ 1, 0);
                         if constexpr (ISF) {
                             // the next unit's halo by DMA, behind b0: unit A's target is the SCRATCH of the previous tile's serial phase, whose
                             // last line reads (row_pass(1)) no barrier followed - every wave has passed them here.  12 sub-steps to land.
@@ -1144,7 +1011,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                     if constexpr (g == 4) {
                         K1_BARRIER();                               // b1: column tap 1 consumed
                         if constexpr (PAR == 0) {
-                            K1_DMA_WX(half_a ^ 1, 1);
+                            K1_DMA_W(half_a ^ 1, 1);
                             fence_w = __builtin_amdgcn_raw_buffer_load_b32(rsf, 0, 0, 0);   // covers taps 0 and 1 of the next unit's weights
                         }
                         if constexpr (!ISF) {
@@ -1160,7 +1027,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#if PFNL_S16_SPREAD
                 // the next sub-step's operand reads ride BETWEEN this sub-step's MFMAs (M w w M x x M x x M M M, every position pinned):
                 // as a clump in front of the six MFMAs they are ~100 cycles in which this wave's share of the matrix pipe idles
                 // (tools/ubench/conv_core: 5.66 -> 5.02 us per unit for the bare core)
@@ -1200,38 +1066,6 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                     accc[0] = mfma_f16(wh, X[ky][1], accc[0]);
                     accc[1] = mfma_f16(wh, X[ky + 1][1], accc[1]);
                 }
-#else
-                if constexpr (S < 17) {
-                    constexpr int S1 = S + 1, g1 = S1 / 3, ky1 = S1 % 3;
-                    Wv[S1 & 1][0] = CS_WT(g1, ky1, 0);
-                    Wv[S1 & 1][1] = CS_WT(g1, ky1, 1);
-                    if constexpr (ky1 == 0) {
-                        X[0][0] = CS_PX(g1, 0, 0);
-                        X[0][1] = CS_PX(g1, 0, 1);
-                        X[1][0] = CS_PX(g1, 1, 0);
-                        X[1][1] = CS_PX(g1, 1, 1);
-                    } else {
-                        X[ky1 + 1][0] = CS_PX(g1, ky1 + 1, 0);
-                        X[ky1 + 1][1] = CS_PX(g1, ky1 + 1, 1);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const h8 wh = Wv[S & 1][0], wo = Wv[S & 1][1];
-                if constexpr (PAR == 0 && S == 0) {
-                    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    accm[0] = mfma_f16(wh, X[ky][0], bias16);
-                    accm[1] = mfma_f16(wh, X[ky + 1][0], bias16);
-                    accc[0] = mfma_f16(wo, X[ky][0], zero);
-                    accc[1] = mfma_f16(wo, X[ky + 1][0], zero);
-                } else {
-                    accm[0] = mfma_f16(wh, X[ky][0], accm[0]);
-                    accm[1] = mfma_f16(wh, X[ky + 1][0], accm[1]);
-                    accc[0] = mfma_f16(wo, X[ky][0], accc[0]);
-                    accc[1] = mfma_f16(wo, X[ky + 1][0], accc[1]);
-                }
-                accc[0] = mfma_f16(wh, X[ky][1], accc[0]);
-                accc[1] = mfma_f16(wh, X[ky + 1][1], accc[1]);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             };
             substep(std::integral_constant<int, 0>{});
@@ -1261,23 +1095,15 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                 RowHalves h0, h1;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) quarter_prep(h0, accm[0], accc[0], q, true);
-                CS_STAMP();                                         // 2: sub-steps done, row 0 prepared
                 if constexpr (ISF) asm volatile("" ::"v"(fence_w)); // the next tile's first halo has landed
                 K1_BARRIER();                                       // b2: this unit's buffer (the scratch) is free, the next unit's is complete
-                CS_STAMP();                                         // 3: past b2
                 row_dump(h0);
-                CS_STAMP();                                         // 4: row 0 dumped
                 K1_BARRIER();                                       // the 128 lines of row 0 are complete
-                CS_STAMP();                                         // 5
                 row_pass(0, std::true_type{}, w10, &held[0], [&](int q) __attribute__((always_inline)) { quarter_prep(h1, accm[1], accc[1], q, true); });
-                CS_STAMP();                                         // 6: row 0's lines picked up, its products issued, row 1 prepared
                 K1_BARRIER();                                       // ... and read
-                CS_STAMP();                                         // 7
                 row_dump(h1);
                 K1_BARRIER();
-                CS_STAMP();                                         // 8
                 row_pass(1, std::true_type{}, w10, &held[4], [&](int) __attribute__((always_inline)) {});
-                CS_STAMP();                                         // 9
                 hx0 = c_x0;
                 hy0 = c_y0;
                 hitem = c_item;
@@ -1545,9 +1371,3 @@ void conv1x1_c10_pack_weights(const float* hwio, int T, uint16_t* dst) {
 }
 
 }  // namespace pfnl
-
-#ifdef PFNL_S16_TIMING
-extern "C" int pfnl_debug_read_s16_stamps(long long* host, size_t n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pfnl::cs_dbg), n * sizeof(long long)) == hipSuccess ? 0 : -1;
-}
-#endif

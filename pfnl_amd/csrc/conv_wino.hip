@@ -13,7 +13,7 @@
 // same XCD so the second halo read hits L2).  Wave w owns Winograd row xi = w: its 4 positions
 // (nu = 0..3) = 4 accumulators (64 VGPRs) persist across all input-channel chunks.  <=128 VGPRs and
 // 36.9 KB LDS allow FOUR independent workgroups per CU (4 waves/SIMD): measured phase timelines
-// (tools/wino_timing.py) showed that what starves the matrix pipe is not the K-loop but the
+//  showed that what starves the matrix pipe is not the K-loop but the
 // prologue / epilogue / barrier bubbles of a workgroup coinciding with its neighbour's, so the design
 // maximises the number of independent, dynamically scheduled streams rather than their size.
 //
@@ -35,8 +35,8 @@
 
 namespace pfnl {
 
-template <bool FUSE>
-__global__ __launch_bounds__(WN_THREADS, PFNL_WINO_WPS) void conv_wino_kernel(WinoParams p) {
+template <bool FUSE>                                            // compiled for 3 waves per SIMD (= workgroups per CU)
+__global__ __launch_bounds__(WN_THREADS, 3) void conv_wino_kernel(WinoParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -63,15 +63,6 @@ __global__ __launch_bounds__(WN_THREADS, PFNL_WINO_WPS) void conv_wino_kernel(Wi
     const int by = rem / tiles_x;
     const int y0 = by * (2 * WN_TY);
     const int x0 = (rem - by * tiles_x) * (2 * WN_TX);
-
-#ifdef PFNL_WINO_TIMING
-    long long* dbg = p.dbg ? p.dbg + (size_t)blockIdx.x * 16 : nullptr;
-    int dbg_n = 0;
-#define WN_STAMP() do { if (dbg && tid == 0 && dbg_n < 16) dbg[dbg_n++] = clock64(); } while (0)
-#else
-#define WN_STAMP() do {} while (0)
-#endif
-    WN_STAMP();                                                 // 0: entry
 
     // U ring first: its latency overlaps the halo-tile staging below.
     constexpr int KS_F4 = 64;                                   // float4 per (chunk, xi, N-tile, kk)
@@ -148,7 +139,6 @@ __global__ __launch_bounds__(WN_THREADS, PFNL_WINO_WPS) void conv_wino_kernel(Wi
     WN_LOAD_RAW(1, rinB);
     WN_STORE_RAW(smem, rinA);
     __syncthreads();
-    WN_STAMP();                                                 // 1: first halo tile in LDS
 
     // V of the first K-step of a chunk (plain code; every later K-step's V comes out of the asm step before it)
 #define WN_VFIRST(q_, v_)                                                                        \
@@ -190,7 +180,6 @@ __global__ __launch_bounds__(WN_THREADS, PFNL_WINO_WPS) void conv_wino_kernel(Wi
         WN_KSTEP(q_, 4, va, vb); WN_KSTEP(q_, 5, vb, va); WN_KSTEP(q_, 6, va, vb); WN_KSTEP(q_, 7, vb, va); \
         if ((q_) + 1 < WN_NCHUNK) WN_STORE_RAW(smem + (((q_) + 1) & 1) * WN_BUF, rnext_);        \
         __syncthreads();                                                                         \
-        WN_STAMP();                                             /* 2..5: chunk done */           \
     } while (0)
     static_assert(WN_CK == 16 && WN_NCHUNK == 4, "WN_CHUNK is written out for 8 K-steps x 4 chunks");
     WN_CHUNK(0, rinB, rinA);
@@ -234,7 +223,6 @@ __global__ __launch_bounds__(WN_THREADS, PFNL_WINO_WPS) void conv_wino_kernel(Wi
         slab[(1 * 32 + etile) * WN_ES + xl] = m1 - m2 - m3;
     }
     __syncthreads();
-    WN_STAMP();                                                 // 6: slab exchanged
     const f32x4 bias4 = *reinterpret_cast<const f32x4*>(p.bias + cbase);
     const float slope = p.act ? 0.2f : 1.0f;
 #pragma unroll
@@ -266,7 +254,6 @@ __global__ __launch_bounds__(WN_THREADS, PFNL_WINO_WPS) void conv_wino_kernel(Wi
                 *reinterpret_cast<f32x4*>(p.out + (((size_t)item * H + y) * W + ox) * 64 + cbase) = o;
         }
     }
-    WN_STAMP();                                                 // 7: stores issued
 }
 
 template <bool FUSE>

@@ -110,19 +110,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void conv_wino_ws_kernel(WinoParams 
         x0_ = (sp_ - by_ * tiles_x) * (2 * WN_TX);                    \
     } while (0)
 
-#ifdef PFNL_WINO_TIMING
-    long long* dbg = p.dbg ? p.dbg + (size_t)blockIdx.x * 128 + (wave < 4 ? 0 : 64) : nullptr;
-    int dbg_n = 0;
-    const bool dbg_on = dbg && (lane == 0) && (wave == 0 || wave == 4);
-#define WS_STAMP() do { if (dbg_on && dbg_n < 64) dbg[dbg_n++] = clock64(); } while (0)
-#else
-#define WS_STAMP() do {} while (0)
-#endif
     if (wave < 4) {
         // =================================== matrix waves ===========================================
-#ifdef PFNL_WS_MPRIO
-        __builtin_amdgcn_s_setprio(PFNL_WS_MPRIO);
-#endif
         const int xi = wave;
         const int tx = lane & 15;
         const int ty = (lane >> 4) & 1;
@@ -288,36 +277,27 @@ __global__ __launch_bounds__(WS_THREADS, 1) void conv_wino_ws_kernel(WinoParams 
             WS_STEP2(2);
             WS_STEP2(4);
             WS_STEP(6, vA, vB, vC, vD);
-            WS_STAMP();
             __syncthreads();                                        // chunk 1 ready / chunk 0's buffer free
-            WS_STAMP();
             WS_STEP(7, vC, vD, vA, vB);
             WS_STEP2(8);
             WS_STEP2(10);
             WS_STEP2(12);
             WS_STEP(14, vA, vB, vC, vD);
-            WS_STAMP();
             __syncthreads();
-            WS_STAMP();
             WS_STEP(15, vC, vD, vA, vB);
             WS_STEP2(16);
             WS_STEP2(18);
             WS_STEP2(20);
             WS_STEP(22, vA, vB, vC, vD);
-            WS_STAMP();
             __syncthreads();
-            WS_STAMP();
             WS_STEP(23, vC, vD, vA, vB);
             WS_STEP2(24);
             WS_STEP2(26);
             WS_STEP2(28);
             WS_STEP(30, vA, vB, vC, vD);
-            WS_STAMP();
             __syncthreads();                                        // next tile's chunk 0 ready
-            WS_STAMP();
             if (ACCUM) {
                 WS_STEP(31, vC, vD, vA, vB);
-                WS_STAMP();
                 // MODE 3: only a clip's last frame leaves the accumulators; both N-tiles after the last MFMA
                 asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // MFMA results of the asm blocks -> VALU reads
                 if (mu == gT - 1) {
@@ -328,9 +308,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void conv_wino_ws_kernel(WinoParams 
                 }
             } else {
                 WS_STEP31_D0(vC, vD, vA, vB);                       // N-tile 0 leaves here, N-tile 1 in the next tile's K-step 0
-                WS_STAMP();
             }
-            WS_STAMP();
             if (GROUPED) {                                          // weight pack of the next unit / the one after
                 mu = mu == gT ? 0 : mu + 1;
                 uoff_cur = uoff_nxt;
@@ -361,10 +339,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void conv_wino_ws_kernel(WinoParams 
     // ====================================== helper waves =============================================
     // Few instructions, but every one is on the barrier-critical path and only gets an issue slot when the
     // matrix wave of its SIMD leaves one: highest priority.
-#ifndef PFNL_WS_HPRIO
-#define PFNL_WS_HPRIO 3
-#endif
-    __builtin_amdgcn_s_setprio(PFNL_WS_HPRIO);
+    __builtin_amdgcn_s_setprio(3);
     const int ht = tid - 4 * 64;                                    // 0..255
     // unit-independent part of the staging descriptors
     int loff[WN_IN_ITERS], pyx[WN_IN_ITERS];
@@ -557,9 +532,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void conv_wino_ws_kernel(WinoParams 
         WS_DESC(min(i + 2, nu - 1));
         WS_EPI_UNIT(i);
         WS_EPI_OFFS();
-        WS_STAMP();
         __syncthreads();                                            // the matrix waves have filled the slab (tile i-1)
-        WS_STAMP();
         // phase 1: chunk 2 -> buffer 0; half of the previous tile's epilogue
         WS_STORE(2);
         WS_LOAD(2);
@@ -567,16 +540,12 @@ __global__ __launch_bounds__(WS_THREADS, 1) void conv_wino_ws_kernel(WinoParams 
             WS_EPI(0);
             WS_EPI(1);
         }
-        WS_STAMP();
         __syncthreads();
-        WS_STAMP();
         // phase 2: chunk 3 -> buffer 1
         WS_STORE(3);
         WS_LOAD(3);
         if (i > 0 && e_fin) WS_EPI(2);
-        WS_STAMP();
         __syncthreads();
-        WS_STAMP();
         // phase 3: next tile's chunk 0 -> buffer 0; request chunk 0 of the tile after; last quarter of the
         // epilogue, then the addend / residual of THIS tile (first half)
         WS_STORE(0);
@@ -586,9 +555,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void conv_wino_ws_kernel(WinoParams 
         WS_EPI_COMMIT();
         WS_EPI_LOAD(0);
         WS_EPI_LOAD(1);
-        WS_STAMP();
         __syncthreads();
-        WS_STAMP();
     }
     WS_EPI_LOAD(2);
     WS_EPI_LOAD(3);

@@ -21,7 +21,7 @@ constexpr size_t WN_LDS_BYTES = size_t(WN_LDS_FLOATS) * sizeof(float);   // 36 8
 constexpr int WN_THREADS = 256;
 constexpr int WN_IN_ITEMS = WN_IH * WN_IW * (WN_CK / 4);                 // 816 float4 pieces
 constexpr int WN_IN_ITERS = (WN_IN_ITEMS + WN_THREADS - 1) / WN_THREADS; // 4
-constexpr int WN_UDEPTH = PFNL_WINO_UDEPTH;       // K-steps of U kept in flight
+constexpr int WN_UDEPTH = 2;                      // K-steps of U kept in flight
 constexpr int WN_NSTEP = WN_NCHUNK * (WN_CK / 2); // 32 K-steps
 constexpr int wino_pack_floats_c = 16 * 64 * 64;
 

@@ -1,4 +1,4 @@
-"""Same-box A/B of library builds (PFNL_HIP_LIB=pfnl_amd/lib/var_<name>.so): one JSON line per run with the sustained ms per step,
+"""Same-box A/B of library builds (PFNL_HIP_LIB=the build under test): one JSON line per run with the sustained ms per step,
 the package power and shader clock rocm-smi reported DURING the run (the split-f16 launches sit on the power cap: a variant is only
 understood with W and MHz next to its microseconds), the per-class kernel times (HIP events, sampled blocks) and a sha256 of the
 output (variants that only reorder instructions must be bit-identical).  Usage: python tools/ab_r05.py [cfg2|cfg4|cfg4bf16|cfg0|cfg5] [seconds]"""

@@ -1,4 +1,4 @@
-"""A few forwards of the default engine (for rocprofv3 runs: tools/sf_variants.sh).  usage: run_fwd.py B H W [precision]"""
+"""A few forwards of the default engine (for rocprofv3 runs).  usage: run_fwd.py B H W [precision]"""
 import os
 import sys
 
