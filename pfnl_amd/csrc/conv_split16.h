@@ -42,6 +42,9 @@ struct ConvSplitParams {
 // hi = f16(x), lo' = f16((x - hi) 2^11) - exactly the two operands conv_split16.hip builds from an fp32 tensor when it commits a
 // halo tile, built once by the producer instead.  Same bytes per value as fp32.  16-byte chunk c of a (pixel, half) = channels
 // 32 M + 8 (c & 3) .. + 7 of part c >> 2: the unit the 3x3 kernels' LDS tiles and the 1x1 kernel's operands are made of.
+// hi + lo' 2^-11 keeps 22 significant bits of x for |x| >= 2^-12 (an fp32-FMA-chain error per product).  Below that lo' can be a binary16
+// subnormal: its step 2^-24 makes an absolute floor of 2^-36 per operand (hi is subnormal too under 2^-14, 0 under 2^-25).  The hardware
+// keeps binary16 subnormals in v_cvt_pk_f16_f32, v_fma_mix*_f16 and the f16 MFMA operands; tests/test_gpu_numerics.py pins both.
 hipError_t launch_conv3x3_split16(const ConvSplitParams& p, hipStream_t s);
 size_t conv3x3_split16_pack_halfs();                                  // 16-bit elements per packed 3x3 64->64 kernel
 void conv3x3_split16_pack_weights16(const float* hwio, int cin_total, int cin_begin, uint16_t* dst);   // the order of the 16x16x32 kernels: [half][kx][ky][16-channel output tile][hi / lo'][lane] (64 output channels)

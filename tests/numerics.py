@@ -1,0 +1,172 @@
+"""Host model of the exact fp32 split the f16-pipe kernels run on, and the error bound the split-f16 op tests hold them to.
+
+THE SPLIT (conv_split16.h): an fp32 value x becomes two binary16 operands, hi = f16(x) and lo' = f16((x - hi) 2^11), both rounded to
+nearest even; x - hi and the scaling are exact in fp32.  The kernels multiply hi.hi on one accumulator and the cross products
+hi.lo' + lo'.hi on a second one that is scaled by 2^-11 at the end (the lo'.lo' product is dropped).  The operand they work on is
+therefore emulate(x) = hi + lo' 2^-11:
+
+  - |x - hi| <= 2^-11 |x| and lo' keeps 11 bits of it: |x - emulate(x)| <= 2^-22 |x| while lo' is a normal binary16 number;
+  - lo' is a binary16 subnormal when |x - hi| < 2^-25, its step is then 2^-24: |x - emulate(x)| <= 2^-25 2^-11 = 2^-36 absolute.
+    Below 2^-14 hi itself is subnormal and below 2^-25 it is 0, but x - hi then lies under 2^-25 and only lo' carries the value:
+    the same 2^-36 floor.  So a split operand keeps all its 22 bits only above roughly 2^-14 (where lo' leaves the subnormal range
+    for most values); at 2^-24 it keeps about 12 bits, at 2^-36 none.  This is the lower edge of the kernels' "fp32-FMA-chain
+    accuracy": by design, not by a flush.
+  - above 65504 hi rounds to 65504 up to 65520 and to infinity from there (the range flag of the forward, include/pfnl_hip.h).
+
+THE BOUND, element-wise against the fp64 spec, for an output that sums K products a_i b_i (plus bias / addend / resid c_j):
+
+    |got - ref| <= alpha(K) S + beta A,   S = sum |a_i b_i| + sum |c_j|,   A = sum (|a_i| [|b_i| < 2^-12] + |b_i| [|a_i| < 2^-12])
+
+  - the operand error is |x - emulate(x)| <= max(2^-22 |x|, 2^-36), and the floor 2^-36 is reached only for |x| < 2^-12: above it
+    x - hi is a multiple of ulp32(x) >= 2^-35, so lo' is a multiple of 2^-24 and exact even when it is subnormal.  A therefore
+    counts an operand |a_i| only when its partner b_i is under 2^-12 (and vice versa): sum (|a_i| + |b_i|) restricted to the
+    products a floor can touch.  Without the restriction one large activation would hide the floor of every small one.
+  - beta = 2^-35: a product of two split operands is off by at most |e_a| |b| + |a| |e_b| + |e_a e_b|; the floor part of the e's is
+    2^-36 each, so beta A is twice what the floor can contribute.  An MFMA that flushed binary16 subnormal inputs would lose a whole
+    hi (up to 2^-14) or lo' (up to 2^-25 after the 2^-11 scale): 2^10 ... 2^21 times beta.
+  - alpha(K): the accumulation is an fp32 FMA chain (fp32 A/B MFMA) or an fp32 accumulator fed exact f16 x f16 products (f16 MFMA).
+    An fp32 FMA chain (v_mfma_f32_32x32x2_f32 is one, bit for bit) measures 0.75 - 1.5e-7 S for K <= 1024 on data of one scale,
+    where the partial sums stay ~sqrt(K) below S.  On data spread over many binades a few terms carry S and every later rounding
+    is a step of up to 2^-24 |partial| ~ 2^-24 S: K such steps, uniform and independent, have the standard deviation
+    2^-24 sqrt(K / 3) S (8.3e-7 S at K = 576); the chain term is sqrt(3) of that, 2^-24 sqrt(K) S, as the worst of thousands of
+    outputs sits near 2 standard deviations.  The split adds, per product, the normal-range part of the operand errors plus the
+    dropped lo'.lo': 2^-22 S with independent signs.  So alpha(K) = 2^-24 sqrt(K) + 2^-22.  A sequential fp32 chain emulated on
+    the edge data reaches 0.45 - 0.6 of it at K = 448 - 576 and ~0.2 at K = 4032; on the MI355X the f32-MFMA kernels reach up to
+    0.65 and the split-f16 kernels up to 0.53 (test_gpu_numerics.py prints the ratios).  The f32-MFMA kernels must meet
+    alpha(K) S on the same data (they have no beta term).
+"""
+import numpy as np
+
+SPLIT_SHIFT = 11                    # lo' = f16((x - hi) 2^11)
+F16_MAX = 65504.0
+BETA = 2.0 ** -35
+FLOOR_BELOW = 2.0 ** -12            # operands that can reach the 2^-36 floor
+
+
+def split_parts(x):
+    """(hi, lo') of every element of an fp32 array, as binary16 arrays: hi = f16(x), lo' = f16((x - hi) 2^11), nearest even."""
+    x = np.asarray(x, dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        hi = x.astype(np.float16)
+        lo = ((x - hi.astype(np.float32)) * np.float32(2.0 ** SPLIT_SHIFT)).astype(np.float16)
+    return hi, lo
+
+
+def split_host(v):
+    """The split format of an fp32 array [..., 64] as the kernels build it (conv_split16.h): per pixel [channel half][hi 32 | lo' 32]
+    binary16, hi = f16(x) (nearest even), lo' = f16((x - hi) 2^11) - x - hi and the scaling are exact in fp32, one rounding each."""
+    hi, lo = split_parts(v)
+    hi, lo = hi.reshape(v.shape[:-1] + (2, 32)), lo.reshape(v.shape[:-1] + (2, 32))
+    return np.concatenate([hi, lo], axis=-1).reshape(v.shape[:-1] + (128,)).view(np.int16)
+
+
+def emulate(x):
+    """The operand the kernels multiply: hi + lo' 2^-11, in fp64."""
+    hi, lo = split_parts(x)
+    return hi.astype(np.float64) + lo.astype(np.float64) * 2.0 ** -SPLIT_SHIFT
+
+
+def alpha(K):
+    """Error per unit of S of a K-product sum: the fp32 chain's 2^-24 sqrt(K) plus the split's 2^-22 (module docstring)."""
+    return 2.0 ** -24 * np.sqrt(K) + 2.0 ** -22
+
+
+def conv_terms(x, k, extra=()):
+    """S and A of the bound for conv2d_same(x, k) (fp64, [B, H, W, cout]); `extra`: arrays added to S (bias, addend, resid:
+    anything that broadcasts to the output)."""
+    from oracle import pfnl_spec
+    ax, ak = np.abs(np.asarray(x, np.float64)), np.abs(np.asarray(k, np.float64))
+    S = pfnl_spec.conv2d_same(ax, ak, None)
+    fx, fk = (ax < FLOOR_BELOW).astype(np.float64), (ak < FLOOR_BELOW).astype(np.float64)
+    A = pfnl_spec.conv2d_same(ax, fk, None) + pfnl_spec.conv2d_same(fx, ak, None)
+    for e in extra:
+        if e is not None:
+            S = S + np.abs(np.asarray(e, np.float64))
+    return S, A
+
+
+def conv_bound(x, k, extra=(), xerr=None, beta=BETA):
+    """Element-wise bound alpha(K) S + beta A for conv2d_same(x, k) [+ extra]; xerr: an element-wise bound on an error the input
+    already carries (a fused producer's output), propagated as conv2d_same(xerr, |k|)."""
+    from oracle import pfnl_spec
+    K = k.shape[0] * k.shape[1] * k.shape[2]
+    S, A = conv_terms(x, k, extra)
+    b = alpha(K) * S + beta * A
+    if xerr is not None:
+        b = b + pfnl_spec.conv2d_same(np.asarray(xerr, np.float64), np.abs(np.asarray(k, np.float64)), None)
+    return b
+
+
+def worst_ratio(got, ref, bound):
+    """max |got - ref| / bound over the elements (an element with bound 0 must be exact: ratio inf otherwise)."""
+    err = np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, 0.0, err / bound)
+    return float(r.max()) if r.size else 0.0
+
+
+def equivariant_scales(x, ks=range(-40, 41)):
+    """The k of `ks` for which the split commutes with the scale 2^k bit for bit on every element of x:
+    hi(2^k x) = 2^k hi(x) and lo'(2^k x) = 2^k lo'(x) (both exactly, 2^k x itself exact in fp32)."""
+    x = np.asarray(x, np.float32)
+    h0, l0 = (p.astype(np.float64) for p in split_parts(x))
+    out = []
+    for k in ks:
+        xs = (x.astype(np.float64) * 2.0 ** k)
+        if not np.array_equal(xs.astype(np.float32).astype(np.float64), xs):
+            continue
+        h, l = (p.astype(np.float64) for p in split_parts(xs.astype(np.float32)))
+        if np.array_equal(h, h0 * 2.0 ** k) and np.array_equal(l, l0 * 2.0 ** k):
+            out.append(int(k))
+    return out
+
+
+# ---- data families of the split-f16 op tests -------------------------------------------------------------------------------------
+
+def binades(rng, shape, lo=-30, hi=14, spread=True):
+    """+-2^u (1 + v), u uniform over [lo, hi], v uniform [0, 1); channel c (last axis) scaled by 2^((c % 9) - 4) when `spread`;
+    |x| < 2^15 (inside binary16's 65504)."""
+    u = rng.integers(lo, hi + 1, size=shape).astype(np.float64)
+    x = np.ldexp(1.0 + rng.random(shape), u.astype(np.int64)) * rng.choice([-1.0, 1.0], size=shape)
+    if spread:
+        x = x * 2.0 ** ((np.arange(shape[-1]) % 9) - 4)
+    x = np.clip(x, -(2.0 ** 15) * (1 - 2.0 ** -20), 2.0 ** 15 * (1 - 2.0 ** -20))
+    return x.astype(np.float32)
+
+
+def edge_values():
+    """fp32 values at the split's edges: +-0, binary16 ties, just below powers of two (hi rounds up a binade, lo' < 0), subnormal hi,
+    hi = 0, the top of the 65504 domain."""
+    f = np.float32
+    v = [0.0, -0.0, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, -(1.0 + 2.0 ** -11), 2.0 ** -3 * (1 + 2.0 ** -11),
+         np.nextafter(f(1.0), f(0)), np.nextafter(f(2.0 ** -14), f(0)), np.nextafter(f(2.0 ** 10), f(0)), -np.nextafter(f(0.5), f(0)),
+         2.0 ** -14, 2.0 ** -15 * 1.3, 2.0 ** -20 * 1.7, 2.0 ** -24, 2.0 ** -24 * 1.5, 2.0 ** -25 * 0.99, 2.0 ** -30, 2.0 ** -36,
+         np.nextafter(f(2.0 ** -24), f(1)), 2.0 ** -24 * 2.5, 6.5e4, -6.5e4, 65000.123, 4097.0 + 2.0 ** -11]
+    return np.array(v, dtype=np.float32)
+
+
+def edges(rng, shape):
+    """Data made of edge_values() (random positions and signs) mixed with binades: every edge meets every tap position."""
+    x = binades(rng, shape, spread=False)
+    e = edge_values()
+    pick = rng.random(shape) < 0.5
+    x[pick] = e[rng.integers(0, e.size, size=int(pick.sum()))] * rng.choice([-1.0, 1.0], size=int(pick.sum())).astype(np.float32)
+    return x
+
+
+def edge_weights(rng, shape, big=6.0e4):
+    """Weights from 1e-7 to ~1 (log-uniform, random sign), output channel 0 all zero, one weight near 6e4 (under 65504)."""
+    w = (10.0 ** rng.uniform(-7, 0, size=shape)) * rng.choice([-1.0, 1.0], size=shape)
+    w[..., 0] = 0.0
+    w.reshape(-1, shape[-1])[0, 1] = big
+    return w.astype(np.float32)
+
+
+def dark(rng, shape, scale):
+    """N(0, 1) data scaled by `scale` (2^-16, 2^-20: where the split's operand floor shows)."""
+    return (rng.normal(size=shape) * scale).astype(np.float32)
+
+
+def unit_binades(rng, shape):
+    """|x| in [1/4, 4): the data of the bit-exact scale-equivariance checks (equivariant_scales: k in [-10, 13])."""
+    return (np.ldexp(1.0 + rng.random(shape), rng.integers(-2, 2, size=shape)) * rng.choice([-1.0, 1.0], size=shape)).astype(np.float32)

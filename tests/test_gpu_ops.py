@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 torch = pytest.importorskip("torch")
 
+from numerics import split_host  # noqa: E402
 from oracle import pfnl_spec  # noqa: E402
 from pfnl_amd import ops  # noqa: E402
 
@@ -623,15 +624,6 @@ def test_conv1_conv10_fused_split16_sf0_is_bit_identical(T, clips, H, W):
         assert np.array_equal(gotb.view(np.uint32), refb.view(np.uint32)), (rep, np.abs(gotb - refb).max())
 
 
-def _sf_split_host(v):
-    """The split format of an fp32 array [..., 64] as the kernels build it (conv_split16.h): per pixel [channel half][hi 32 | lo' 32]
-    binary16, hi = f16(x) (nearest even), lo' = f16((x - hi) 2^11) - x - hi and the scaling are exact in fp32, one rounding each."""
-    hi = v.astype(np.float16)
-    lo = ((v - hi.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
-    hi, lo = hi.reshape(v.shape[:-1] + (2, 32)), lo.reshape(v.shape[:-1] + (2, 32))
-    return np.concatenate([hi, lo], axis=-1).reshape(v.shape[:-1] + (128,)).view(np.int16)
-
-
 @pytest.mark.parametrize("T,clips,H,W", [(7, 1, 8, 32), (7, 2, 10, 38), (5, 1, 33, 70), (3, 3, 16, 24), (7, 4, 128, 128), (7, 1, 1, 1), (7, 3, 9, 130), (7, 40, 8, 32)])
 def test_conv2_chain_sf0_writes_the_split_format_copy(T, clips, H, W):
     """Round 6 (option split16_sf0; reference model/pfnl.py:69-71): conv3x3_sf_chain_kernel<true> writes its output - the next block's
@@ -649,7 +641,7 @@ def test_conv2_chain_sf0_writes_the_split_format_copy(T, clips, H, W):
     out, out_sf = ops.conv2_chain_sf0(dev(x), k2, b, dev(base), dev(res), T)
     out, out_sf = out.cpu().numpy(), out_sf.cpu().numpy()
     assert np.array_equal(out.view(np.uint32), plain.view(np.uint32))
-    want = _sf_split_host(out)
+    want = split_host(out)
     bad = np.argwhere(out_sf != want)
     assert bad.size == 0, (len(bad), bad[:4], out_sf[tuple(bad[0])], want[tuple(bad[0])])
 
@@ -725,9 +717,11 @@ def test_conv_small_pf_block_two_launches(T, clips, H, W):
 
 
 def test_conv3x3_split16_scaling_and_data_movement():
-    """Accuracy does not depend on the magnitude of the activations inside binary16's range (lo' is kept scaled by 2^11, so
-    small values do not lean on binary16 subnormals); a delta kernel moves data bit-exactly (hi + lo' 2^-11 reconstructs x
-    when x has <= 22 significant bits)."""
+    """Accuracy does not depend on the magnitude of the activations from 2^-12 to binary16's top (lo' is kept scaled by 2^11, so
+    such values do not lean on binary16 subnormals).  Below that it does, by design: lo' becomes subnormal, its step 2^-24 is an
+    absolute floor of 2^-36 per operand, and under 2^-14 hi is subnormal too (tests/numerics.py; test_gpu_numerics.py holds every
+    split-f16 kernel to that bound down to 2^-30).  A delta kernel moves data bit-exactly (hi + lo' 2^-11 reconstructs x when x
+    has <= 22 significant bits)."""
     rng = np.random.default_rng(3)
     x = rng.normal(size=(2, 16, 32, 64)).astype(np.float32)
     k = (rng.normal(size=(3, 3, 64, 64)) / 24.0).astype(np.float32)
