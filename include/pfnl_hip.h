@@ -154,7 +154,8 @@ int pfnl_finalize_weights(pfnl_handle* h);
  *   less energy per FLOP on a package that sits on its power cap; 1080p 3.77 -> 3.58 ms) | "32" (the 32x32x16 form: same rounding points, another summation order).
  * key "split16_mfma" = "16" (default since round 6: the chain launch of conv2_i - fp32 path, whole rounds of at least one (clip, tile) chain per CU - issues
  *   v_mfma_f32_16x16x32_f16, conv3x3_sf_chain16_kernel; split chains, split16_sf0 and launches with fewer chains stay on the 32x32x16 kernel) | "32".
- *   pfnl_plan's mfma field says which ran.  Same operands, another summation order: results agree within rounding (observed 2e-7), not bit for bit.
+ *   Under the same rule conv1_i's 3x3 stage of the block's other launch runs on that shape too (conv3x3_c1c10_kernel's M16 form; conv10_i's stage stays on
+ *   32x32x16); "32" restores the 32x32x16 kernels for both launches.  pfnl_plan's mfma field says which ran (c1_mfma: the conv1_i + conv10_i launch).  Same operands, another summation order: results agree within rounding (observed 2e-7), not bit for bit.
  * key "bf16_nonlocal" = "f16" (the only value since round 4: the non-local block of precision=bf16 on the f16 matrix pipe with
  *                 binary16 operands, fp32 accumulation and softmax state - nonlocal_f16.hip, hi parts only; within 1e-3 of the
  *                 fp64 block on [0,1]-scale outputs, measured 1e-4 ... 5e-4.  Round 1's split-operand bf16 kernel - 2.5x the
@@ -360,6 +361,11 @@ int pfnl_op_conv2_chain_ex(const float* in, const float* kernel_host, const floa
 int pfnl_op_conv1_conv10_split16_ex(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
                                     const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
                                     int n_full, int split_s, int split_q, void* stream);
+/* ... with the MFMA shape of conv1_i's 3x3 stage given: mfma = 16 runs conv3x3_c1c10_kernel's 16x16x32 form (what trunk_plan picks where pfnl_plan
+ * says c1_mfma=16; whole rounds only: split_s must be 0), 32 is pfnl_op_conv1_conv10_split16_ex.  conv10_i's stage is on 32x32x16 in both. */
+int pfnl_op_conv1_conv10_split16_mfma(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
+                                      const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
+                                      int mfma, int n_full, int split_s, int split_q, void* stream);
 /* pfnl_op_conv3x3_accum_split16 (convmerge1) with split chains: the parts' raw sums meet in c10_finalize_kernel (+ bias, act) into out. */
 int pfnl_op_conv3x3_accum_split16_ex(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,
                                      int frames_per_clip, int H, int W, int cout, int act, int n_full, int split_s, int split_q, void* stream);

@@ -173,7 +173,7 @@ struct BlockPacks {
     size_t bf_c1 = 0, bf_c10 = 0, bf_c2a = 0, bf_c2b = 0, bf_c1_m16 = 0, bf_c2b_m16 = 0;
     // split-f16 blob `wdev16s` (16-bit elements): the 3x3 / 1x1 split-f16 packs; c10f: conv10_i as conv3x3_c1c10_kernel takes it; _sf: with the
     // identity row map conv3x3_sf_kernel takes (conv_sf.hip); _m16: the order of the v_mfma_f32_16x16x32_f16 chain kernel (conv3x3_split16_pack_weights16)
-    size_t s_c1 = 0, s_c2a = 0, s_c2b = 0, s_c10 = 0, s_c10f = 0, s_c2a_sf = 0, s_c2b_sf = 0, s_c2a_m16 = 0, s_c2b_m16 = 0;
+    size_t s_c1 = 0, s_c2a = 0, s_c2b = 0, s_c10 = 0, s_c10f = 0, s_c2a_sf = 0, s_c2b_sf = 0, s_c2a_m16 = 0, s_c2b_m16 = 0, s_c1_m16 = 0;   // (s_c1_m16: conv1_i for conv3x3_c1c10_kernel's 16x16x32 form - rows permuted)
     // ... and the small-shape packs (conv_small.hip) in the same blob
     size_t sm_c1 = 0, sm_c10 = 0, sm_c2 = 0;
 };
@@ -446,6 +446,7 @@ struct TrunkPlan {
     int tiles8x32 = 0, chains = 0;
     int mfma = 32;                         // MFMA shape of the chained 3x3 launches: 16 = v_mfma_f32_16x16x32_* (bf16: conv_bf16_v3.hip M16; fp32: the chain launch
                                            // of conv2_i, conv3x3_sf_chain16_kernel - whole rounds of at least a chain per CU only), 32 = 32x32x16
+    int c1_mfma = 32;                      // fp32: MFMA shape of conv1_i's 3x3 stage in the fused conv1_i + conv10_i launch (conv3x3_c1c10_kernel; 16 exactly where mfma is)
     int merge1 = M1_DIRECT;                // convmerge1's launch (Merge1Kind)
     int merge_stride = 48;                 // floats per pixel of `merge` as convmerge1 writes it
     // the trunk's buffers that depend on the plan (floats): the small-shape trunk's conv10_i partials [B*T][H][W][64]; the split-format copy of
@@ -508,6 +509,7 @@ void plan_fp32_trunk(const pfnl_handle* h, TrunkPlan& pl, int B, int H, int W, i
     // the chain launch on 16x16x32: where every CU has a chain the launch sits on the power cap and the shape's energy counts; below that (UDM10: 230
     // chains) its extra cycles do (+0.9 %); split chains and the split-format copy stay on the 32x32x16 kernel
     pl.mfma = (h->s16_m16 && pl.c10_fused && pl.chain && !pl.sf0 && !pl.split_s && pl.chains >= grid) ? 16 : 32;
+    pl.c1_mfma = pl.mfma;                                               // conv1_i's stage of the other launch of the block: the same rule
     pl.name = pl.mid ? "mid4" : (pl.c10_fused && pl.chain) ? (pl.sf0 ? "chain2_sf0" : (pl.split_s ? "chain2_split" : "chain2"))
             : pl.algo == 4 ? (pl.launches_per_block == 3 ? "split16_3" : "split16_4")
             : pl.algo == 3 ? (pl.conv2_grouped ? "winograd_ws3" : "winograd_ws4")
@@ -774,6 +776,7 @@ int block_fp32(const Fwd& f, const BlockPacks& k, bool first, bool last) {
             q.bias2 = wd + k.c10_b;
             q.out2 = h->base.p;
             set_split_chains(q, pl, h->c10part.p);
+            if (pl.c1_mfma == 16) q.wpack_m16 = f.w16s + k.s_c1_m16;  // (trunk_plan: whole rounds with a chain per CU, fp32 input)
             HIPCHK(launch_conv3x3_c1c10(q, s));
         }
         if (pl.split_s) {   // split chains: the parts' raw conv10_i sums -> base (+ leaky-relu, split format) for the chains that were cut
@@ -1360,7 +1363,7 @@ int pfnl_finalize_weights(pfnl_handle* h) {
     {   // split-f16 packs of the 3x3 64->64 kernels (conv3x3=split16)
         std::vector<uint16_t> b16;
         const size_t n3 = pfnl::conv3x3_split16_pack_halfs(), n1 = pfnl::conv1x1_split16_pack_halfs(T);
-        const size_t blk = 7 * n3 + n1 + pfnl::conv1x1_c10_pack_halfs(T);   // (5 packs of the 32x32x16 kernels + 2 of the 16x16x32 chain kernel)
+        const size_t blk = 8 * n3 + n1 + pfnl::conv1x1_c10_pack_halfs(T);   // (5 packs of the 32x32x16 kernels + 2 of the 16x16x32 chain kernel + conv1_i's for the 16x16x32 c1c10 form)
         h->off16s_m1 = (size_t)nb * blk;
         const size_t m3 = pfnl::conv_small_pack_halfs(3, 1), m10 = pfnl::conv_small_pack_halfs(1, T);
         const size_t small_base = (size_t)nb * blk + (size_t)T * n3;
@@ -1381,6 +1384,8 @@ int pfnl_finalize_weights(pfnl_handle* h) {
             k.s_c10f = k.s_c2b_sf + n3;
             k.s_c2a_m16 = k.s_c10f + pfnl::conv1x1_c10_pack_halfs(T);
             k.s_c2b_m16 = k.s_c2a_m16 + n3;
+            k.s_c1_m16 = k.s_c2b_m16 + n3;
+            pfnl::conv3x3_split16_pack_weights16(W("conv1_" + s).data(), 64, 0, &b16[k.s_c1_m16], true);
             pfnl::conv3x3_split16_pack_weights16(W("conv2_" + s).data(), 128, 0, &b16[k.s_c2a_m16]);
             pfnl::conv3x3_split16_pack_weights16(W("conv2_" + s).data(), 128, 64, &b16[k.s_c2b_m16]);
             pfnl::conv1x1_c10_pack_weights(W("conv10_" + s).data(), T, &b16[k.s_c10f]);
@@ -1451,11 +1456,11 @@ int pfnl_plan(pfnl_handle* h, int B, int H, int W, char* buf, size_t buflen) {
                       nln[pl.nl_family], pl.nl_fused_pack ? 1 : 0, pl.mfma, kMerge1Names[pl.merge1]);
     else
         std::snprintf(tmp, sizeof tmp, "%s launches_per_block=%d c1x1=%d precision=fp32 conv3x3=%s conv1x1=%s c10_fused=%d chain=%d sf0=%d strict=%d tiles=%d chains=%d "
-                      "whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d merge1=%s",
+                      "whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d c1_mfma=%d merge1=%s",
                       pl.name, pl.launches_per_block, pl.c1x1_launches, pl.small ? "small" : a3[pl.algo < 0 || pl.algo > 4 ? 2 : pl.algo],
                       a1[pl.conv1x1_algo < 0 || pl.conv1x1_algo > 2 ? 0 : pl.conv1x1_algo], pl.c10_fused ? 1 : 0, pl.chain ? 1 : 0, pl.sf0 ? 1 : 0,
                       pl.strict ? 1 : 0, pl.tiles8x32, pl.chains, pl.split_s ? pl.n_full : pl.chains, pl.split_s, pl.split_q, nln[pl.nl_family],
-                      pl.nl_fused_pack ? 1 : 0, pl.mfma, kMerge1Names[pl.merge1]);
+                      pl.nl_fused_pack ? 1 : 0, pl.mfma, pl.c1_mfma, kMerge1Names[pl.merge1]);
     if (std::strlen(tmp) + 1 > buflen) return fail(PFNL_ERR_INVALID, "buffer too small");
     std::strcpy(buf, tmp);
     return 0;

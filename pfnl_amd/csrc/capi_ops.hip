@@ -171,14 +171,16 @@ static int op_conv2_chain(const float* in, const float* kernel_host, const float
 // the kernel writes both in the split format, the hook hands them back as fp32 (hi + lo' 2^-11: what the consumers' MFMAs see)
 static int op_conv1_conv10_split16(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
                                    const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
-                                   void* stream, bool in_sf, int n_full = 0, int split_s = 0, int split_q = 0) {
+                                   void* stream, bool in_sf, int n_full = 0, int split_s = 0, int split_q = 0, bool m16 = false) {
     if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
     const int T = frames_per_clip;
     if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
     OpStage st(stream);
     const size_t n3 = pfnl::conv3x3_split16_pack_halfs(), n1 = pfnl::conv1x1_c10_pack_halfs(T);
-    std::vector<uint16_t> pack(n3 + n1 + 256, 0);
+    // [3x3 pack | conv10_i pack | bias | conv10_i bias | m16: the 3x3 pack of the 16x16x32 form]
+    std::vector<uint16_t> pack(n3 + n1 + 256 + (m16 ? n3 : 0), 0);
     pfnl::conv3x3_split16_pack_weights(k1_host, 64, 0, pack.data());
+    if (m16) pfnl::conv3x3_split16_pack_weights16(k1_host, 64, 0, pack.data() + n3 + n1 + 256, true);
     pfnl::conv1x1_c10_pack_weights(k10_host, T, pack.data() + n3);
     if (b1_host) std::memcpy(&pack[n3 + n1], b1_host, 64 * sizeof(float));
     if (b10_host) std::memcpy(&pack[n3 + n1 + 128], b10_host, 64 * sizeof(float));
@@ -199,6 +201,7 @@ static int op_conv1_conv10_split16(const float* in, const float* k1_host, const 
         q.split_s = split_s;
         q.split_q = split_q;
         q.partial = part;
+        if (m16) q.wpack_m16 = dw + n3 + n1 + 256;
         return pfnl::launch_conv3x3_c1c10(q, st.s);
     });
     if (split_s) st.run([&] {                                           // the cut chains' base from the parts' raw conv10_i sums
@@ -704,6 +707,21 @@ int pfnl_op_conv1_conv10_split16_ex(const float* in, const float* k1_host, const
     if (int r = frame_too_large(H, W, 256)) return r;
     if (!split_args_ok(H, W, clips * T, T, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
     return op_conv1_conv10_split16(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, T, H, W, stream, false, n_full, split_s, split_q);
+}
+
+// ... with the MFMA shape of conv1_i's 3x3 stage chosen by the caller: 16 = conv3x3_c1c10_kernel's 16x16x32 form (whole rounds only), 32 = the hook above
+int pfnl_op_conv1_conv10_split16_mfma(const float* in, const float* k1_host, const float* b1_host, const float* k10_host,
+                                      const float* b10_host, float* out1, float* base, int clips, int frames_per_clip, int H, int W,
+                                      int mfma, int n_full, int split_s, int split_q, void* stream) {
+    if (mfma != 16 && mfma != 32) return fail(PFNL_ERR_INVALID, "mfma must be 16 or 32");
+    if (mfma == 16 && split_s) return fail(PFNL_ERR_INVALID, "split chains run on the 32x32x16 kernel only");
+    if (mfma == 32) return pfnl_op_conv1_conv10_split16_ex(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, frames_per_clip, H, W, n_full, split_s, split_q, stream);
+    if (!in || !k1_host || !k10_host || !out1 || !base) return fail(PFNL_ERR_INVALID, "NULL argument");
+    const int T = frames_per_clip;
+    if (clips < 1 || T < 1 || T > 7 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "unsupported conv geometry");
+    if (int r = frame_too_large(H, W, 256)) return r;
+    if (!split_args_ok(H, W, clips * T, T, n_full, split_s, split_q)) return fail(PFNL_ERR_INVALID, "invalid split-chain geometry");
+    return op_conv1_conv10_split16(in, k1_host, b1_host, k10_host, b10_host, out1, base, clips, T, H, W, stream, false, n_full, 0, split_q, true);
 }
 
 int pfnl_op_conv3x3_accum_split16_ex(const float* in, const float* kernel_host, const float* bias_host, float* out, int clips,

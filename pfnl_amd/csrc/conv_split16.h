@@ -33,8 +33,9 @@ struct ConvSplitParams {
                              // of a (clip, tile) - for launches with fewer chains than workgroups (capi.hip, "MID shapes").  The two input-channel
                              // halves of a tile are summed in the order its position in the workgroup's sequence gives (boustrophedon:
                              // the weights in LDS serve two units in a row), so the work order moves the last bit of some results
-    const uint16_t* wpack_m16;   // launch_conv3x3_sf_chain only, both or neither: conv3x3_split16_pack_weights16 of wpack / wpack2 - the launch then runs on
+    const uint16_t* wpack_m16;   // launch_conv3x3_sf_chain, both or neither: conv3x3_split16_pack_weights16 of wpack / wpack2 - the launch then runs on
     const uint16_t* wpack2_m16;  // v_mfma_f32_16x16x32_f16 (conv3x3_sf_chain16_kernel).  Not with out2
+                                 // launch_conv3x3_c1c10: wpack_m16 = conv3x3_split16_pack_weights16(perm_rows) of conv1_i - its 3x3 stage on 16x16x32 (not with split_s / in_sf)
 };
 
 // THE SPLIT FORMAT ("SF") of an activation tensor that only ever feeds MFMA operands (conv1_i's output, conv10_i's output):
@@ -47,7 +48,8 @@ struct ConvSplitParams {
 // keeps binary16 subnormals in v_cvt_pk_f16_f32, v_fma_mix*_f16 and the f16 MFMA operands; tests/test_gpu_numerics.py pins both.
 hipError_t launch_conv3x3_split16(const ConvSplitParams& p, hipStream_t s);
 size_t conv3x3_split16_pack_halfs();                                  // 16-bit elements per packed 3x3 64->64 kernel
-void conv3x3_split16_pack_weights16(const float* hwio, int cin_total, int cin_begin, uint16_t* dst);   // the order of the 16x16x32 kernels: [half][kx][ky][16-channel output tile][hi / lo'][lane] (64 output channels)
+void conv3x3_split16_pack_weights16(const float* hwio, int cin_total, int cin_begin, uint16_t* dst,     // the order of the 16x16x32 kernels: [half][kx][ky][16-channel output tile][hi / lo'][lane] (64 output channels)
+                                    bool perm_rows = false);          // true: the pack conv3x3_c1c10_kernel's 16x16x32 form takes (output rows permuted across a wave's two tiles)
 void conv3x3_split16_pack_weights(const float* hwio, int cin_total, int cin_begin, uint16_t* dst, int cout = 64,   // cout < 64: zero-padded
                                   bool identity_rows = false);        // true: the pack conv3x3_sf_kernel takes
 

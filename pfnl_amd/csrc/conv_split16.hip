@@ -685,8 +685,27 @@ static_assert(K1_SF_LDS_BYTES <= 160 * 1024, "LDS budget");
 
 // SPLIT: the launch cuts the chains of its last, partial round by frames (p.split_s > 0; below).  A template parameter, not a run-time
 // test: with the part bookkeeping compiled in, the whole-round launches (configs[1]) ran 1.3 us per launch slower on the same box.
-template <bool ISF, bool SPLIT>
+//
+// M16 (whole rounds, fp32 input only): conv1_i's 3x3 stage on v_mfma_f32_16x16x32_f16 (the K = 32 shape costs ~14 % less energy per FLOP under
+// the package power cap).  A = weights (16 output channels x 32 input channels = a unit's channel half in ONE k-step), B = pixels: lane (n = l & 15, g = l >> 4)
+// reads chunk g (hi) / 4 + g (lo') of halo pixel 16 ph + n + kx and, with the output rows permuted across a wave's two 16-channel tiles by the pack
+// (conv3x3_split16_pack_weights16, perm_rows: row 4 g + r of tile t = channel 8 g + 4 t + r), owns channels 32 mt + 8 g .. + 7 of ONE pixel per (output row,
+// pixel half ph) - a whole 16-byte chunk of a split-format line.  9 sub-steps (column tap, row tap) of 24 MFMAs per unit instead of 18 of 6, the two cross-term
+// MFMAs of an accumulator back to back; operand registers as conv3x3_sf_chain16_kernel keeps them (12 sets live, each refilled for the next sub-step behind its
+// last reader).  The halo image takes that kernel's swizzle (K1_SWZ16) - the (px >> 1) & 7 of the 32x32x16 form collides under ds_read_b128's lane groups for a
+// 16-pixel operand - and the commit pairs pixels (p, p + 4) instead of (p, p + 8): the swizzle's bit 2 is now bit 2 of px, so one pixel's hi half again falls on
+// the banks of the other's lo' half.  What pays for the 16 registers the wider operand set takes: the halo is requested and committed in two groups of three
+// pieces (12 staging registers instead of 24), the first group of a tile's first unit only once half of the previous tile's `held` lines have left, and those
+// leave two per sub-step.  Everything behind the 3x3 stage (the serial phase, conv10_i on 32x32x16, `held`, the output formats) is the 32x32x16 form's; the
+// summation order differs from it (K = 32 per instruction): equal within rounding, not bit for bit.
+#define K1_SWZ16(px_) ((((px_) >> 1) & 3) << 1)
+typedef float k1f4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ k1f4 k1_mfma16(h8 a, h8 b, k1f4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+template <bool ISF, bool SPLIT, bool M16 = false>
 __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitParams p) {
+    static_assert(!M16 || (!ISF && !SPLIT), "16x16x32 form: whole rounds, fp32 input");
     constexpr int TILE_BYTES = ISF ? K1_SF_TILE_BYTES : CS_TILE_BYTES;
     extern __shared__ __attribute__((aligned(16))) unsigned char cs_smem[];
     unsigned char* const wl = cs_smem + 2 * TILE_BYTES;
@@ -758,16 +777,18 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         // both hi halves (and then both lo' halves) fall on the same 16 banks - 2-way conflicts on every commit (SQ_LDS_BANK_CONFLICT 1.3e6
         // per launch, profiles/r04_pmc.md).  Paired as (p, p + 8) the swizzle term (px >> 1) & 7 differs in bit 2: one pixel's hi half
         // occupies the banks of the other's lo' half.  (the last 4 pixels of the 340 keep their order)
-        if (pix < (CS_IH * CS_IW & ~15)) pix = (pix & ~15) | ((pix & 1) << 3) | ((pix & 15) >> 1);
+        // (M16: pairs (p, p + 4) under K1_SWZ16 - see the header)
+        if (pix < (CS_IH * CS_IW & ~15)) pix = M16 ? ((pix & ~7) | ((pix & 1) << 2) | ((pix & 7) >> 1)) : ((pix & ~15) | ((pix & 1) << 3) | ((pix & 15) >> 1));
         const int py = pix / CS_IW, px = pix - py * CS_IW;
-        lpk[k] = ((py * CS_IW + px) * 128 + 8 * (c & 1) + (((c >> 1) ^ ((px >> 1) & 7)) << 4)) | (py << 16) | (px << 24);
+        lpk[k] = ((py * CS_IW + px) * 128 + 8 * (c & 1) + (((c >> 1) ^ (M16 ? K1_SWZ16(px) : ((px >> 1) & 7))) << 4)) | (py << 16) | (px << 24);
     }
     const int c16 = (tid & 7) * 16;                                 // (piece id = k * 512 + tid: its 4-channel piece of the pixel is tid & 7 for every k)
     const float nscale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, -CS_SCALE)));
     [[maybe_unused]] f32x4 stg[CS_ITERS];
-#define K1_REQUEST_ALL(rs_, org_, interior_, y0_, x0_)                                           \
+#define K1_REQUEST_ALL(rs_, org_, interior_, y0_, x0_) K1_REQUEST(0, CS_ITERS, rs_, org_, interior_, y0_, x0_)
+#define K1_REQUEST(k0_, k1_, rs_, org_, interior_, y0_, x0_)                                     \
     do {                                                                                         \
-        _Pragma("unroll") for (int k_ = 0; k_ < CS_ITERS; ++k_) {                                \
+        _Pragma("unroll") for (int k_ = (k0_); k_ < (k1_); ++k_) {                               \
             const int py_ = (lpk[k_] >> 16) & 0xff, px_ = (unsigned)lpk[k_] >> 24;               \
             const int gy_ = (y0_) + py_ - 1, gx_ = (x0_) + px_ - 1;                              \
             const bool in_ = (interior_) | (((unsigned)gy_ < (unsigned)H) & ((unsigned)gx_ < (unsigned)W));   /* (no short circuit: no branches) */ \
@@ -785,17 +806,28 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         *reinterpret_cast<u32x2*>(cs_smem + (buf_) * TILE_BYTES + (lo_ ^ 64)) = lo2_;            \
     } while (0)
 
-    int paddr[3];
+    int paddr[3];                                                   // (M16: pixel half 0; half 1 is 2 048 bytes further - K1_SWZ16(px + 16) = K1_SWZ16(px))
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
-        const int col = (lane & 31) + kx;
-        paddr[kx] = ((2 * rp) * CS_IW + col) * 128 + ((((lane >> 5)) ^ ((col >> 1) & 7)) << 4);
+        const int col = (lane & (M16 ? 15 : 31)) + kx;
+        paddr[kx] = M16 ? ((2 * rp) * CS_IW + col) * 128 + (((lane >> 4) ^ K1_SWZ16(col)) << 4)
+                        : ((2 * rp) * CS_IW + col) * 128 + ((((lane >> 5)) ^ ((col >> 1) & 7)) << 4);
     }
     const int lo_xor = 4 << 4;
-    const unsigned char* const wlane = wl + mt * 2048 + lane * 16;
+    const unsigned char* const wlane = wl + mt * (M16 ? 4096 : 2048) + lane * 16;   // M16: [kx][ky][output tile 2 mt + t][hi / lo'][lane] x 16 B
     const int kh = lane >> 5;
-    const int ech = 32 * mt + 16 * kh;                              // register r of a lane = channel ech + r (both convolutions)
+    const int ech = 32 * mt + 16 * kh;                              // register r of a lane = channel ech + r (both convolutions; M16: conv10_i only)
     f32x16 accm[2], accc[2], base_m[2];                             // [output row]: hi.hi / cross products (x 2^11) of conv1_i; conv10_i of the chain
+    [[maybe_unused]] k1f4 am16[2][4], ac16[2][4];                   // M16: [output row][2 ph + t], register r = channel 32 mt + 8 (lane >> 4) + 4 t + r of pixel 16 ph + (lane & 15)
+    if constexpr (M16) {
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                am16[n][q] = k1f4{0.f, 0.f, 0.f, 0.f};
+                ac16[n][q] = k1f4{0.f, 0.f, 0.f, 0.f};
+            }
+    }
     // the finished tile's 256 pixel lines as this thread's 8 pieces of 16 bytes (row n: piece id = i * 512 + tid -> pixel id >> 4 of
     // the row's 128, chunk id & 15): picked up from the scratch in the serial phase, stored one by one under the NEXT tile's MFMAs -
     // a CU moves store data at ~16 B per clock (measured: 2 k cycles for the 32 KB of a row), far too slow to wait for
@@ -842,6 +874,15 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         asm("v_max_f32 %0, %1, %2" : "=v"(t.w) : "v"(t.w), "v"(st.w));
         split4(t, h.hi[q], h.lo[q], nscale);
     };
+    [[maybe_unused]] auto quarter_prep4 = [&](RowHalves& h, const k1f4& m, const k1f4& c, int q) __attribute__((always_inline)) {   // M16: quarter q = 2 ph + t
+        f32x4 t = f32x4{m[0], m[1], m[2], m[3]} + f32x4{c[0], c[1], c[2], c[3]} * CS_ISCALE;   // (compiler-generated: reads MFMA results)
+        const f32x4 st = mul4s(t, slope);
+        asm("v_max_f32 %0, %1, %2" : "=v"(t.x) : "v"(t.x), "v"(st.x));
+        asm("v_max_f32 %0, %1, %2" : "=v"(t.y) : "v"(t.y), "v"(st.y));
+        asm("v_max_f32 %0, %1, %2" : "=v"(t.z) : "v"(t.z), "v"(st.z));
+        asm("v_max_f32 %0, %1, %2" : "=v"(t.w) : "v"(t.w), "v"(st.w));
+        split4(t, h.hi[q], h.lo[q], nscale);
+    };
     const int pp = rp * 32 + (lane & 31);
     const int sw = pp & 15;
     unsigned char* const pl = scratch + pp * 256;
@@ -851,6 +892,16 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
         *reinterpret_cast<u32x4*>(pl + (((c0 + 1) ^ sw) << 4)) = u32x4{h.hi[2].x, h.hi[2].y, h.hi[3].x, h.hi[3].y};
         *reinterpret_cast<u32x4*>(pl + (((c0 + 4) ^ sw) << 4)) = u32x4{h.lo[0].x, h.lo[0].y, h.lo[1].x, h.lo[1].y};
         *reinterpret_cast<u32x4*>(pl + (((c0 + 5) ^ sw) << 4)) = u32x4{h.lo[2].x, h.lo[2].y, h.lo[3].x, h.lo[3].y};
+    };
+    // M16: the lane's 8 channels of pixel 16 ph + (lane & 15) are chunk 8 mt + (lane >> 4) (hi) / + 4 (lo') of that pixel's line; slot swizzle pp & 15 = lane & 15
+    [[maybe_unused]] auto row_dump16 = [&](const RowHalves& h) __attribute__((always_inline)) {
+        const int n16 = lane & 15, c0 = 8 * mt + (lane >> 4);
+#pragma unroll
+        for (int ph = 0; ph < 2; ++ph) {
+            unsigned char* const plx = scratch + (rp * 32 + 16 * ph + n16) * 256;
+            *reinterpret_cast<u32x4*>(plx + ((c0 ^ n16) << 4)) = u32x4{h.hi[2 * ph].x, h.hi[2 * ph].y, h.hi[2 * ph + 1].x, h.hi[2 * ph + 1].y};
+            *reinterpret_cast<u32x4*>(plx + (((c0 + 4) ^ n16) << 4)) = u32x4{h.lo[2 * ph].x, h.lo[2 * ph].y, h.lo[2 * ph + 1].x, h.lo[2 * ph + 1].y};
+        }
     };
     // One pass over the 128 lines in the scratch: (a) this thread's 4 pieces of them -> `pc` (stored later); (b) conv10_i, frame f:
     // base_m[n][cout][pixel] += W10_f[cout][k] X[k][pixel], k-step q = (M, h): channels 32 M + 16 kh + 8 h + e - 3 MFMAs per k-step,
@@ -944,12 +995,32 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
             h8 X[4][2], Wv[2][2];
 #define CS_PX(g_, r_, part_) (*reinterpret_cast<const h8*>(tile + (paddr[(g_) >> 1] ^ (((part_) ? lo_xor : 0) | (((g_) & 1) << 5))) + (r_) * (CS_IW * 128)))
 #define CS_WT(g_, ky_, part_) (*reinterpret_cast<const h8*>(wlane + (((g_) * 3 + (ky_)) << 12) + ((part_) << 10)))
-            X[0][0] = CS_PX(0, 0, 0);
-            X[0][1] = CS_PX(0, 0, 1);
-            X[1][0] = CS_PX(0, 1, 0);
-            X[1][1] = CS_PX(0, 1, 1);
-            Wv[0][0] = CS_WT(0, 0, 0);
-            Wv[0][1] = CS_WT(0, 0, 1);
+            if constexpr (!M16) {
+                X[0][0] = CS_PX(0, 0, 0);
+                X[0][1] = CS_PX(0, 0, 1);
+                X[1][0] = CS_PX(0, 1, 0);
+                X[1][1] = CS_PX(0, 1, 1);
+                Wv[0][0] = CS_WT(0, 0, 0);
+                Wv[0][1] = CS_WT(0, 0, 1);
+            }
+            // M16 operands: X6[halo row of the column tap][pixel half][hi / lo'], W6[row tap][output tile][hi / lo'] - 12 of the 28 sets live
+            [[maybe_unused]] h8 X6[4][2][2], W6[3][2][2];
+#define K1_PX16(kx_, ph_, r_, part_) (*reinterpret_cast<const h8*>(tile + (paddr[kx_] ^ ((part_) ? lo_xor : 0)) + (r_) * (CS_IW * 128) + (ph_) * 2048))
+#define K1_WT16(kx_, ky_, t_, part_) (*reinterpret_cast<const h8*>(wlane + (((kx_) * 3 + (ky_)) << 13) + (((t_) * 2 + (part_)) << 10)))
+            if constexpr (M16) {                                    // (in the order the first sub-step uses them: LDS returns are in order)
+                W6[0][0][0] = K1_WT16(0, 0, 0, 0);
+                X6[0][0][0] = K1_PX16(0, 0, 0, 0);
+                W6[0][1][0] = K1_WT16(0, 0, 1, 0);
+                W6[0][0][1] = K1_WT16(0, 0, 0, 1);
+                X6[0][0][1] = K1_PX16(0, 0, 0, 1);
+                W6[0][1][1] = K1_WT16(0, 0, 1, 1);
+                X6[0][1][0] = K1_PX16(0, 1, 0, 0);
+                X6[0][1][1] = K1_PX16(0, 1, 0, 1);
+                X6[1][0][0] = K1_PX16(0, 0, 1, 0);
+                X6[1][1][0] = K1_PX16(0, 1, 1, 0);
+                X6[1][0][1] = K1_PX16(0, 0, 1, 1);
+                X6[1][1][1] = K1_PX16(0, 1, 1, 1);
+            }
             __builtin_amdgcn_sched_barrier(0);
             // unit B: column tap 2 of ITS half (the slot was in use until unit A's closing barrier); read from group 4 on, behind b0
             [[maybe_unused]] unsigned fence_w = 0;
@@ -965,9 +1036,15 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                 const_cast<float*>(p.in) + (size_t)q_item * H * W * 64, 0, item_bytes, 0x00020000);
             const int org = ((y0q - 1) * W + x0q - 1) * 256 + q_half * 128;
             const bool interior = y0q > 0 && y0q + CS_IH - 1 <= H && x0q > 0 && x0q + CS_IW - 1 <= W;
-            if constexpr (!ISF) K1_REQUEST_ALL(rs, org, interior, y0q, x0q);
+            if constexpr (!ISF && !M16) K1_REQUEST_ALL(rs, org, interior, y0q, x0q);
+            if constexpr (M16 && PAR == 1) K1_REQUEST(0, CS_ITERS / 2, rs, org, interior, y0q, x0q);   // (unit A: at sub-step 1, when half of `held` has left)
             [[maybe_unused]] f32x16 bias16;
-            if constexpr (PAR == 0) {
+            [[maybe_unused]] k1f4 bias4[2];                         // M16: the lane's 8 bias values (output tile t: channels 32 mt + 8 (lane >> 4) + 4 t ..)
+            if constexpr (M16 && PAR == 0) {
+                bias4[0] = *reinterpret_cast<const k1f4*>(bl + 32 * mt + 8 * (lane >> 4));
+                bias4[1] = *reinterpret_cast<const k1f4*>(bl + 32 * mt + 8 * (lane >> 4) + 4);
+            }
+            if constexpr (PAR == 0 && !M16) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const f32x4 b4 = *reinterpret_cast<const f32x4*>(bl + ech + 4 * q);
@@ -1068,24 +1145,120 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                 }
                 __builtin_amdgcn_sched_barrier(0);
             };
-            substep(std::integral_constant<int, 0>{});
-            substep(std::integral_constant<int, 1>{});
-            substep(std::integral_constant<int, 2>{});
-            substep(std::integral_constant<int, 3>{});
-            substep(std::integral_constant<int, 4>{});
-            substep(std::integral_constant<int, 5>{});
-            substep(std::integral_constant<int, 6>{});
-            substep(std::integral_constant<int, 7>{});
-            substep(std::integral_constant<int, 8>{});
-            substep(std::integral_constant<int, 9>{});
-            substep(std::integral_constant<int, 10>{});
-            substep(std::integral_constant<int, 11>{});
-            substep(std::integral_constant<int, 12>{});
-            substep(std::integral_constant<int, 13>{});
-            substep(std::integral_constant<int, 14>{});
-            substep(std::integral_constant<int, 15>{});
-            substep(std::integral_constant<int, 16>{});
-            substep(std::integral_constant<int, 17>{});
+            // M16: sub-step S = 3 kx + ky, 24 MFMAs.  What rides on it: `held` two pieces per sub-step (S <= 3 of unit A); the next unit's halo in two groups of
+            // three pieces - group 0 requested at the unit's start (unit A: at S = 1) and committed at S = 4, group 1 requested there and committed at S = 7;
+            // b0 / b1 and the weight slices as in the 32x32x16 form; conv10_i's operands requested at the last sub-step of unit B (no refills there: registers)
+            auto substep16 = [&](auto sc) __attribute__((always_inline)) {
+                constexpr int S = decltype(sc)::value;
+                constexpr int ky = S % 3;
+                if constexpr (PAR == 1 && S == 8) {
+                    const u32x4* src = reinterpret_cast<const u32x4*>(p.wpack2) + ((size_t)fch * 16 + 2 * mt) * 64 + lane;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        w10[2 * q] = src[(4 * q) * 64];
+                        w10[2 * q + 1] = src[(4 * q + 1) * 64];
+                    }
+                }
+                if constexpr (PAR == 0 && S <= 3) {
+                    held_store(2 * S, p.out);
+                    held_store(2 * S + 1, p.out);
+                }
+                if constexpr (PAR == 0 && S == 1) K1_REQUEST(0, CS_ITERS / 2, rs, org, interior, y0q, x0q);
+                if constexpr (S == 3) {
+                    if constexpr (PAR == 1) asm volatile("" ::"v"(fence_w));   // tap 2 of this unit's weights has landed
+                    K1_BARRIER();                                   // b0: column tap 0 of the weights consumed (unit B: tap 2 complete)
+                    if constexpr (PAR == 0) K1_DMA_W(half_a ^ 1, 0);
+                }
+                if constexpr (S == 4) {
+                    if constexpr (PAR == 0) {
+                        const int kn = min(kt + 1, nt - 1);         // decode the next tile (past the end: this one again - a harmless re-read)
+                        decode(kn, n_item, n_y0, n_x0, n_f);
+                    }
+#pragma unroll
+                    for (int k = 0; k < CS_ITERS / 2; ++k) asm volatile("" : "+v"(lpk[k]));
+#pragma unroll
+                    for (int k = 0; k < CS_ITERS / 2; ++k) K1_COMMIT1(k, cb ^ 1);
+                    K1_REQUEST(CS_ITERS / 2, CS_ITERS, rs, org, interior, y0q, x0q);
+                }
+                if constexpr (S == 6) {
+                    K1_BARRIER();                                   // b1: column tap 1 consumed
+                    if constexpr (PAR == 0) {
+                        K1_DMA_W(half_a ^ 1, 1);
+                        fence_w = __builtin_amdgcn_raw_buffer_load_b32(rsf, 0, 0, 0);   // covers taps 0 and 1 of the next unit's weights
+                    }
+                }
+                if constexpr (S == 7) {
+#pragma unroll
+                    for (int k = CS_ITERS / 2; k < CS_ITERS; ++k) asm volatile("" : "+v"(lpk[k]));
+#pragma unroll
+                    for (int k = CS_ITERS / 2; k < CS_ITERS; ++k) K1_COMMIT1(k, cb ^ 1);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                constexpr bool FIRST = PAR == 0 && S == 0;          // a tile's first products: C = bias / 0
+                constexpr bool NX = S < 8;
+                constexpr int kx1 = (S + 1) / 3, ky1 = (S + 1) % 3;
+                const k1f4 zero4 = k1f4{0.f, 0.f, 0.f, 0.f};
+                // the three products of output row n_, output tile t_, pixel half ph_: main += Wh Xh; cross += Wl Xh; cross += Wh Xl
+#define K1_MM(n_, t_, ph_) do { am16[n_][2 * (ph_) + (t_)] = k1_mfma16(W6[ky][t_][0], X6[ky + (n_)][ph_][0], FIRST ? bias4[t_] : am16[n_][2 * (ph_) + (t_)]); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define K1_CA(n_, t_, ph_) do { ac16[n_][2 * (ph_) + (t_)] = k1_mfma16(W6[ky][t_][1], X6[ky + (n_)][ph_][0], FIRST ? zero4 : ac16[n_][2 * (ph_) + (t_)]); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define K1_CB(n_, t_, ph_) do { ac16[n_][2 * (ph_) + (t_)] = k1_mfma16(W6[ky][t_][0], X6[ky + (n_)][ph_][1], ac16[n_][2 * (ph_) + (t_)]); __builtin_amdgcn_sched_barrier(0); } while (0)
+                // refills for the next sub-step (one LDS read each, pinned between two MFMAs)
+#define K1_LW(t_, part_) do { if constexpr (NX) W6[ky1][t_][part_] = K1_WT16(kx1, ky1, t_, part_); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define K1_LX(r_, ph_, part_) do { if constexpr (NX) X6[r_][ph_][part_] = K1_PX16(kx1, ph_, r_, part_); __builtin_amdgcn_sched_barrier(0); } while (0)
+                // output row 0 (halo row ky) pixel half by pixel half, output row 1 (halo row ky + 1) output tile by output tile; the two cross-term MFMAs of an
+                // accumulator back to back.  A register set is refilled two or three MFMAs behind its last reader: the next sub-step's weights go where halo
+                // row ky was, the next halo row (or rows 0 / 1 of the next column tap) where this sub-step's weights were
+                K1_MM(0, 0, 0); K1_MM(0, 1, 0); K1_CA(0, 0, 0); K1_CB(0, 0, 0); K1_CA(0, 1, 0); K1_CB(0, 1, 0);
+                K1_MM(0, 0, 1); K1_LW(0, 0);
+                K1_MM(0, 1, 1); K1_LW(0, 1);
+                K1_CA(0, 0, 1); K1_CB(0, 0, 1); K1_CA(0, 1, 1); K1_CB(0, 1, 1);
+                K1_MM(1, 0, 0); K1_LW(1, 0);
+                K1_MM(1, 0, 1); K1_CA(1, 0, 0); K1_LW(1, 1);
+                K1_CB(1, 0, 0); K1_CA(1, 0, 1); K1_CB(1, 0, 1);
+                K1_MM(1, 1, 0); K1_LX(ky1 != 0 ? ky + 2 : 0, 0, 0);
+                K1_MM(1, 1, 1); K1_CA(1, 1, 0); K1_LX(ky1 != 0 ? ky + 2 : 0, 0, 1);
+                K1_CB(1, 1, 0); K1_CA(1, 1, 1); K1_CB(1, 1, 1);
+                K1_LX(ky1 != 0 ? ky + 2 : 0, 1, 0); K1_LX(ky1 != 0 ? ky + 2 : 0, 1, 1);
+                if constexpr (ky1 == 0) { K1_LX(1, 0, 0); K1_LX(1, 0, 1); K1_LX(1, 1, 0); K1_LX(1, 1, 1); }
+#undef K1_MM
+#undef K1_CA
+#undef K1_CB
+#undef K1_LW
+#undef K1_LX
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            if constexpr (M16) {
+                substep16(std::integral_constant<int, 0>{});
+                substep16(std::integral_constant<int, 1>{});
+                substep16(std::integral_constant<int, 2>{});
+                substep16(std::integral_constant<int, 3>{});
+                substep16(std::integral_constant<int, 4>{});
+                substep16(std::integral_constant<int, 5>{});
+                substep16(std::integral_constant<int, 6>{});
+                substep16(std::integral_constant<int, 7>{});
+                substep16(std::integral_constant<int, 8>{});
+            } else {
+                substep(std::integral_constant<int, 0>{});
+                substep(std::integral_constant<int, 1>{});
+                substep(std::integral_constant<int, 2>{});
+                substep(std::integral_constant<int, 3>{});
+                substep(std::integral_constant<int, 4>{});
+                substep(std::integral_constant<int, 5>{});
+                substep(std::integral_constant<int, 6>{});
+                substep(std::integral_constant<int, 7>{});
+                substep(std::integral_constant<int, 8>{});
+                substep(std::integral_constant<int, 9>{});
+                substep(std::integral_constant<int, 10>{});
+                substep(std::integral_constant<int, 11>{});
+                substep(std::integral_constant<int, 12>{});
+                substep(std::integral_constant<int, 13>{});
+                substep(std::integral_constant<int, 14>{});
+                substep(std::integral_constant<int, 15>{});
+                substep(std::integral_constant<int, 16>{});
+                substep(std::integral_constant<int, 17>{});
+            }
+#undef K1_PX16
+#undef K1_WT16
 #undef CS_PX
 #undef CS_WT
             if constexpr (PAR == 1) {
@@ -1094,14 +1267,22 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
                 // row 0's conv10 MFMAs.
                 RowHalves h0, h1;
 #pragma unroll
-                for (int q = 0; q < 4; ++q) quarter_prep(h0, accm[0], accc[0], q, true);
+                for (int q = 0; q < 4; ++q) {
+                    if constexpr (M16) quarter_prep4(h0, am16[0][q], ac16[0][q], q);
+                    else quarter_prep(h0, accm[0], accc[0], q, true);
+                }
                 if constexpr (ISF) asm volatile("" ::"v"(fence_w)); // the next tile's first halo has landed
                 K1_BARRIER();                                       // b2: this unit's buffer (the scratch) is free, the next unit's is complete
-                row_dump(h0);
+                if constexpr (M16) row_dump16(h0);
+                else row_dump(h0);
                 K1_BARRIER();                                       // the 128 lines of row 0 are complete
-                row_pass(0, std::true_type{}, w10, &held[0], [&](int q) __attribute__((always_inline)) { quarter_prep(h1, accm[1], accc[1], q, true); });
+                row_pass(0, std::true_type{}, w10, &held[0], [&](int q) __attribute__((always_inline)) {
+                    if constexpr (M16) quarter_prep4(h1, am16[1][q], ac16[1][q], q);
+                    else quarter_prep(h1, accm[1], accc[1], q, true);
+                });
                 K1_BARRIER();                                       // ... and read
-                row_dump(h1);
+                if constexpr (M16) row_dump16(h1);
+                else row_dump(h1);
                 K1_BARRIER();
                 row_pass(1, std::true_type{}, w10, &held[4], [&](int) __attribute__((always_inline)) {});
                 hx0 = c_x0;
@@ -1163,6 +1344,7 @@ __global__ __launch_bounds__(CS_THREADS, 1) void conv3x3_c1c10_kernel(ConvSplitP
     for (int j = 0; j < 8; ++j) held_store(j, p.out);               // the last tile's lines (nothing held: dropped)
 #undef K1_DMA_HALO
 #undef K1_REQUEST_ALL
+#undef K1_REQUEST
 #undef K1_COMMIT1
 #undef K1_BARRIER
 #undef K1_DMA_W
@@ -1232,11 +1414,15 @@ hipError_t launch_conv3x3_c1c10(const ConvSplitParams& p, hipStream_t s) {
     if (!ncu) return hipErrorUnknown;
     const int grid = persistent_grid(ncu);
     if (!split_params_ok(p, grid) || (p.split_s && !p.partial)) return hipErrorInvalidValue;
-    static std::atomic<int> attr_dev[64][4];
+    static std::atomic<int> attr_dev[64][5];
     const int isf = p.in_sf ? 1 : 0;                                // `in` is the split-format copy of inp0 (conv3x3_sf_chain_kernel<true, .>)
-    const int var = isf + (p.split_s ? 2 : 0);
-    const void* const fns[4] = {reinterpret_cast<const void*>(conv3x3_c1c10_kernel<false, false>), reinterpret_cast<const void*>(conv3x3_c1c10_kernel<true, false>),
-                                reinterpret_cast<const void*>(conv3x3_c1c10_kernel<false, true>), reinterpret_cast<const void*>(conv3x3_c1c10_kernel<true, true>)};
+    // p.wpack_m16 (conv3x3_split16_pack_weights16, perm_rows): conv1_i's stage on 16x16x32 MFMAs - whole rounds and fp32 input only, like the chain launch
+    // (split chains / a split-format input: the 32x32x16 kernels on p.wpack)
+    const bool m16 = p.wpack_m16 && !p.split_s && !isf;
+    const int var = m16 ? 4 : isf + (p.split_s ? 2 : 0);
+    const void* const fns[5] = {reinterpret_cast<const void*>(conv3x3_c1c10_kernel<false, false>), reinterpret_cast<const void*>(conv3x3_c1c10_kernel<true, false>),
+                                reinterpret_cast<const void*>(conv3x3_c1c10_kernel<false, true>), reinterpret_cast<const void*>(conv3x3_c1c10_kernel<true, true>),
+                                reinterpret_cast<const void*>(conv3x3_c1c10_kernel<false, false, true>)};
     const int lds = isf ? K1_SF_LDS_BYTES : K1_LDS_BYTES;
     if (!attr_dev[dev][var]) {
         hipError_t e = hipFuncSetAttribute(fns[var], hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1247,6 +1433,12 @@ hipError_t launch_conv3x3_c1c10(const ConvSplitParams& p, hipStream_t s) {
         case 0: hipLaunchKernelGGL((conv3x3_c1c10_kernel<false, false>), dim3(grid), dim3(CS_THREADS), lds, s, p); break;
         case 1: hipLaunchKernelGGL((conv3x3_c1c10_kernel<true, false>), dim3(grid), dim3(CS_THREADS), lds, s, p); break;
         case 2: hipLaunchKernelGGL((conv3x3_c1c10_kernel<false, true>), dim3(grid), dim3(CS_THREADS), lds, s, p); break;
+        case 4: {
+            ConvSplitParams q = p;
+            q.wpack = p.wpack_m16;
+            hipLaunchKernelGGL((conv3x3_c1c10_kernel<false, false, true>), dim3(grid), dim3(CS_THREADS), lds, s, q);
+            break;
+        }
         default: hipLaunchKernelGGL((conv3x3_c1c10_kernel<true, true>), dim3(grid), dim3(CS_THREADS), lds, s, p); break;
     }
     return hipGetLastError();
@@ -1329,8 +1521,9 @@ void conv3x3_split16_pack_weights(const float* hwio, int cin_total, int cin_begi
 
 // The same kernel in the order of the v_mfma_f32_16x16x32_f16 kernels (conv_sf.hip, conv3x3_sf_chain16_kernel: A = weights, 16 output channels x 32 input
 // channels per operand): [half][kx][ky][output tile c4][part][lane][e] = W[ky][kx][cin_begin + 32 half + 8 (lane >> 4) + e][16 c4 + (lane & 15)] - the 24 KB per
-// column tap kx are again one LDS-DMA slice
-void conv3x3_split16_pack_weights16(const float* hwio, int cin_total, int cin_begin, uint16_t* dst) {
+// column tap kx are again one LDS-DMA slice.  perm_rows (conv3x3_c1c10_kernel<., ., M16>: the weights are the A operand of a wave that owns output tiles
+// 2 mt, 2 mt + 1): row r of tile c4 = channel 32 (c4 >> 1) + 8 (r >> 2) + 4 (c4 & 1) + (r & 3) - a lane of the result then holds 8 consecutive channels
+void conv3x3_split16_pack_weights16(const float* hwio, int cin_total, int cin_begin, uint16_t* dst, bool perm_rows) {
     for (int half = 0; half < 2; ++half)
         for (int kx = 0; kx < 3; ++kx)
             for (int ky = 0; ky < 3; ++ky)
@@ -1338,7 +1531,8 @@ void conv3x3_split16_pack_weights16(const float* hwio, int cin_total, int cin_be
                     for (int lane = 0; lane < 64; ++lane)
                         for (int e = 0; e < 8; ++e) {
                             const int ci = cin_begin + 32 * half + 8 * (lane >> 4) + e;
-                            const int co = 16 * c4 + (lane & 15);
+                            const int r = lane & 15;
+                            const int co = perm_rows ? 32 * (c4 >> 1) + 8 * (r >> 2) + 4 * (c4 & 1) + (r & 3) : 16 * c4 + r;
                             const float w = hwio[((size_t)(ky * 3 + kx) * cin_total + ci) * 64 + co];
                             const _Float16 hi = (_Float16)w;
                             const float lo = (w - (float)hi) * CS_SCALE;

@@ -473,6 +473,27 @@ def conv1_conv10_split16_ex(x, k1, b1, k10, b10, frames_per_clip: int, split=(0,
     return out1, base
 
 
+def conv1_conv10_split16_mfma(x, k1, b1, k10, b10, frames_per_clip: int, mfma: int = 16, split=(0, 0, 0), out1=None, base=None):
+    """conv1_conv10_split16_ex with the MFMA shape of conv1_i's 3x3 stage given (pfnl_op_conv1_conv10_split16_mfma): mfma = 16 runs the
+    16x16x32 form of conv3x3_c1c10_kernel (whole rounds only: split must be (0, 0, 0)), 32 the 32x32x16 kernel."""
+    import torch
+    lib = _capi.load_library()
+    F, H, W, c = x.shape
+    T = int(frames_per_clip)
+    k1h, k10h = _host(k1, "k1"), _host(k10, "k10")
+    if c != 64 or F % T or k1h.size != 9 * 64 * 64 or k10h.size != 64 * T * 64:
+        raise ValueError("conv1_conv10_split16_mfma: geometry mismatch")
+    if out1 is None:
+        out1 = torch.empty((F, H, W, 64), dtype=torch.float32, device=x.device)
+    if base is None:
+        base = torch.empty((F // T, H, W, 64), dtype=torch.float32, device=x.device)
+    n_full, s, q = (int(v) for v in split)
+    _capi.check(lib.pfnl_op_conv1_conv10_split16_mfma(_req(x, "x"), _hp(k1h), _hp(_host(b1, "b1")), _hp(k10h), _hp(_host(b10, "b10")),
+                                                      _req(out1, "out1"), _req(base, "base"), F // T, T, H, W, int(mfma), n_full, s, q,
+                                                      _stream(x)))
+    return out1, base
+
+
 def conv3x3_accum_split16_ex(x, kernel, bias=None, act=True, frames_per_clip=1, split=(0, 0, 0), out=None):
     """convmerge1 on the split-f16 kernel (pfnl_op_conv3x3_accum_split16_ex; reference model/pfnl.py:52, :73-74) with the split-chain
     geometry split = (n_full, split_s, split_q) given explicitly.  x [clips*fpc,H,W,64]; kernel HWIO [3,3,64*fpc,cout];

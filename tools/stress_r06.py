@@ -2,7 +2,7 @@
 of rounds of the grid (option split16_splitchains: the chains of the partial round cut by frames, conv10_i's partial sums through
 c10_finalize_kernel) and the opt-in split16_sf0 (split-format copy of inp0, halo by LDS-DMA).  Every forward is repeated bit for bit; the cut
 launch is compared with the uncut one (summation-order noise only) and with strict_fp32 (the f32-MFMA kernels: an independent implementation
-of every layer); split16_sf0 must equal the default BIT FOR BIT (same operands, same order).  usage: python tools/stress_r06.py [seed] [seconds]"""
+of every layer); split16_sf0 must equal the default BIT FOR BIT (same operands, same order).  usage: python tools/stress_r06.py [seed] [seconds] [op geometries]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -12,6 +12,29 @@ from pfnl_amd import synth
 
 
 worst16 = 0.0
+worst_op16 = 0.0
+n_op16 = 0
+
+
+def c1c10_op_sweep(rng, count):
+    """`count` random geometries of the conv1_i + conv10_i op on its two MFMA shapes (pfnl_op_conv1_conv10_split16_mfma: 16 = conv3x3_c1c10_kernel's
+    16x16x32 form): repeated bit for bit, max |16x16x32 - 32x32x16| over inp1 and base (summation order only)."""
+    import torch
+    from pfnl_amd import ops
+    global worst_op16, n_op16
+    for _ in range(count):
+        T = int(rng.choice([1, 3, 5, 7])); H = int(rng.integers(1, 41)); W = int(rng.integers(1, 81)); clips = int(rng.integers(1, 4))
+        x = torch.from_numpy(rng.normal(size=(clips * T, H, W, 64)).astype(np.float32)).cuda()
+        k1 = (rng.normal(size=(3, 3, 64, 64)) / 24.0).astype(np.float32); b1 = (rng.normal(size=64) * 0.1).astype(np.float32)
+        k10 = (rng.normal(size=(1, 1, 64 * T, 64)) / np.sqrt(64 * T)).astype(np.float32); b10 = (rng.normal(size=64) * 0.1).astype(np.float32)
+        a1, ab = ops.conv1_conv10_split16_mfma(x, k1, b1, k10, b10, T, mfma=16)
+        r1, rb = ops.conv1_conv10_split16_mfma(x, k1, b1, k10, b10, T, mfma=16)
+        assert torch.equal(a1, r1) and torch.equal(ab, rb), ("c1c10 16x16x32 not repeatable", T, clips, H, W)
+        o1, ob = ops.conv1_conv10_split16_mfma(x, k1, b1, k10, b10, T, mfma=32)
+        d = max(float((a1 - o1).abs().max()), float((ab - ob).abs().max()))
+        assert d < 1e-5, ("c1c10 16x16x32 vs 32x32x16", T, clips, H, W, d)
+        worst_op16 = max(worst_op16, d)
+        n_op16 += 1
 
 
 def run(seed=0, seconds=60.0):
@@ -78,5 +101,8 @@ def run(seed=0, seconds=60.0):
 
 if __name__ == "__main__":
     n, ncut, worst, ws, parts = run(int(sys.argv[1]) if len(sys.argv) > 1 else 0, float(sys.argv[2]) if len(sys.argv) > 2 else 60.0)
+    if len(sys.argv) > 3:                                           # [op geometries]: the conv1_i + conv10_i op on both MFMA shapes
+        c1c10_op_sweep(np.random.default_rng(int(sys.argv[1]) + 1), int(sys.argv[3]))
+        print("stress_r06: conv1_i + conv10_i op, %d geometries (all repeated bit for bit): max |16x16x32 - 32x32x16| %.3g" % (n_op16, worst_op16))
     print("stress_r06: %d geometries on the two-launch block (all repeated bit for bit, split16_sf0 bit-equal), %d with split chains "
           "(parts x frames: %s): max |cut - uncut| %.3g, max |cut - strict_fp32| %.3g, max |16x16x32 - 32x32x16 chain kernel| %.3g" % (n, ncut, sorted(parts.items()), worst, ws, worst16))
