@@ -470,6 +470,19 @@ int pfnl_op_tail(const float* merge, const float* x, const float* kernel_host, c
  * quantise: uint8(np.round(np.clip(sr * 255, 0, 255))) (round half to even), n % 4 == 0. */
 int pfnl_op_gather_windows(const float* frames, float* win, int F, int first, int count, int T, int H, int W, void* stream);
 int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream);
+/* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
+ * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
+ *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),
+ *   out[f][0] = sum of (Y_truth - Y_pred)^2 over the frame                              (matlab/compute_psnr.m:1-18, boundarypixels = 0),
+ *   out[f][1] = the same over [sp_border : H - sp_border, sp_border : W - sp_border]    (utils.py:213-246, AVG_PSNR: 8),
+ *   out[f][2] = sum of the SSIM map of modules/SSIM_Index.py:23-89 (11x11 Gaussian sigma 1.5, K = (0.01, 0.03), L = 255, 'reflect'),
+ *   out[f][3] = its sum over [5 : H - 5, 5 : W - 5], what matlab/SSIM.m's filter2(..., 'valid') averages.
+ * fp64 throughout; out [F,4] double (device); two calls on the same frames return identical bits.  11 <= H, W <= 65536, 1 <= F <= 65535,
+ * 0 <= 2 * sp_border < H, W.  Asynchronous on stream, allocates nothing: scratch is pfnl_op_score_scratch_bytes(F, H, W) bytes of
+ * device memory (8-byte aligned).  pfnl_amd/metrics.py sequence_scores turns the sums into PSNR_Y / SSIM / AVG_PSNR. */
+int pfnl_op_score_scratch_bytes(int F, int H, int W, size_t* bytes);
+int pfnl_op_score_y(const uint8_t* pred, const uint8_t* truth, int F, int H, int W, int sp_border, double* out, void* scratch,
+                    void* stream);
 /* tf.image.resize_images(method=2) of TF1.12 (model/pfnl.py:63): x [B,H,W,3] -> [B,sH,sW,3]. */
 int pfnl_op_bicubic(const float* x, float* out, int B, int H, int W, int scale, void* stream);
 /* The step before the path in test_video_truth / eval (reference utils.py:95-105,169-192:

@@ -95,6 +95,8 @@ SIGNATURES = {
     "pfnl_op_tail": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pfnl_op_quantise_u8": (_i, [_vp, _vp, C.c_size_t, _vp]),
+    "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
+    "pfnl_op_score_y": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pfnl_comm_get_unique_id": (_i, [_vp]),
     "pfnl_comm_init_rank": (_i, [_i, _i, _vp, _i, C.POINTER(_vp)]),
     "pfnl_comm_init_all": (_i, [_i, C.POINTER(_i), C.POINTER(_vp)]),

@@ -882,6 +882,31 @@ int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream) {
     return 0;
 }
 
+// every refusal comes before any HIP call: the argument checks work without a device
+static int score_geometry_refused(int F, int H, int W) {
+    if (F < 1 || F > 65535) return fail(PFNL_ERR_INVALID, "score: F must be in 1 .. 65535");
+    if (H < 11 || W < 11) return fail(PFNL_ERR_INVALID, "score: H and W must be at least 11 (the 11x11 SSIM window)");
+    if (H > 65536 || W > 65536) return fail(PFNL_ERR_INVALID, "score: H and W must be at most 65536");
+    return 0;
+}
+
+int pfnl_op_score_scratch_bytes(int F, int H, int W, size_t* bytes) {
+    if (!bytes) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (int r = score_geometry_refused(F, H, W)) return r;
+    *bytes = pfnl::score_scratch_bytes(F, H, W);
+    return 0;
+}
+
+int pfnl_op_score_y(const uint8_t* pred, const uint8_t* truth, int F, int H, int W, int sp_border, double* out, void* scratch,
+                    void* stream) {
+    if (!pred || !truth || !out || !scratch) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (int r = score_geometry_refused(F, H, W)) return r;
+    if (sp_border < 0 || 2 * (long long)sp_border >= H || 2 * (long long)sp_border >= W)
+        return fail(PFNL_ERR_INVALID, "score: sp_border must leave a crop (0 <= 2 * sp_border < H, W)");
+    HIPCHK(pfnl::launch_score_y(pred, truth, F, H, W, sp_border, out, static_cast<double*>(scratch), (hipStream_t)stream));
+    return 0;
+}
+
 int pfnl_op_bicubic(const float* x, float* out, int B, int H, int W, int scale, void* stream) {
     if (!x || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (B < 1 || H < 1 || W < 1 || (scale != 2 && scale != 4)) return fail(PFNL_ERR_INVALID, "bad bicubic geometry");

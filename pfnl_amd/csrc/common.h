@@ -156,4 +156,11 @@ hipError_t launch_gather_windows(const float* frames, float* win, int F, int fir
                                  hipStream_t s);
 hipError_t launch_quantise_u8(const float* sr, uint8_t* out, size_t n, hipStream_t s);
 
+// ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
+// pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;
+// partial: score_scratch_bytes(F, H, W) of device memory (one slot per workgroup: the sums are repeatable bit for bit)
+size_t score_scratch_bytes(int F, int H, int W);
+hipError_t launch_score_y(const uint8_t* pred, const uint8_t* truth, int F, int H, int W, int sp_border, double* out, double* partial,
+                          hipStream_t s);
+
 }  // namespace pfnl

@@ -9,6 +9,10 @@ numpy, not on the hot path.
                       spatial border 8, mean of per-frame PSNR.
 * ``ssim``          : `modules/SSIM_Index.py:23-89`: 11x11 Gaussian window sigma 1.5, K = (0.01, 0.03),
                       L = 255, reflect-mode correlation (scipy.ndimage convolve default), mean SSIM map.
+* ``ssim_valid``    : the same map averaged over its interior [5:-5, 5:-5] - what `matlab/SSIM.m`'s
+                      filter2(..., 'valid') averages (the interior never sees the boundary rule).
+* ``sequence_scores``: per-frame and per-sequence PSNR_Y / SSIM / AVG_PSNR from the four sums per frame that
+                      ``ops.score_y`` (pfnl_op_score_y) forms on the device.
 """
 from __future__ import annotations
 
@@ -66,8 +70,7 @@ def _gauss_2d(n=11, sigma=1.5) -> np.ndarray:
     return h / h.sum()
 
 
-def ssim(im1, im2, L: float = 255.0) -> float:
-    """Single-channel images; modules/SSIM_Index.py:23-89."""
+def _ssim_map(im1, im2, L: float = 255.0) -> np.ndarray:
     import scipy.ndimage
     c1, c2 = (0.01 * L) ** 2, (0.03 * L) ** 2
     w = _gauss_2d()
@@ -77,5 +80,37 @@ def ssim(im1, im2, L: float = 255.0) -> float:
     s1 = conv(a * a) - mu1 * mu1
     s2 = conv(b * b) - mu2 * mu2
     s12 = conv(a * b) - mu1 * mu2
-    m = ((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s1 + s2 + c2))
-    return float(np.mean(m))
+    return ((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s1 + s2 + c2))
+
+
+def ssim(im1, im2, L: float = 255.0) -> float:
+    """Single-channel images; modules/SSIM_Index.py:23-89."""
+    return float(np.mean(_ssim_map(im1, im2, L)))
+
+
+def ssim_valid(im1, im2, L: float = 255.0) -> float:
+    """Single-channel images of at least 11 x 11: the mean of ``ssim``'s map over [5:-5, 5:-5] (matlab/SSIM.m, 'valid')."""
+    m = _ssim_map(im1, im2, L)
+    if m.ndim != 2 or m.shape[0] < 11 or m.shape[1] < 11:
+        raise ValueError("ssim_valid needs a single-channel image of at least 11 x 11")
+    return float(np.mean(m[5:-5, 5:-5]))
+
+
+def sequence_scores(sums, H: int, W: int, sp_border: int = 8, t_border: int = 2) -> dict:
+    """sums [F,4] = per frame sum_d2_full, sum_d2_crop (over [sp_border:H-sp_border, sp_border:W-sp_border]), ssim_sum_full,
+    ssim_sum_valid (over [5:H-5, 5:W-5]) of the Y channels of uint8 frames, as ``ops.score_y`` returns them -> the per-frame
+    ``psnr_y`` (matlab/compute_psnr.m), ``ssim`` and ``ssim_valid``, their means, and ``avg_psnr`` = AVG_PSNR (utils.py:213-246):
+    the mean over frames t_border .. F - t_border of the cropped PSNR (nan when no frame is left).  Identical frames give inf."""
+    s = np.asarray(sums, np.float64).reshape(-1, 4)
+    F = s.shape[0]
+
+    def psnr(sum_d2, n):
+        with np.errstate(divide="ignore"):
+            return 20.0 * np.log10(255.0 / np.sqrt(sum_d2 / n))
+
+    p = psnr(s[:, 0], H * W)
+    crop = psnr(s[t_border:F - t_border, 1], (H - 2 * sp_border) * (W - 2 * sp_border))
+    sm, sv = s[:, 2] / (H * W), s[:, 3] / ((H - 10) * (W - 10))
+    mean = lambda v: float(np.mean(v)) if len(v) else float("nan")                     # noqa: E731
+    return {"psnr_y": p.tolist(), "ssim": sm.tolist(), "ssim_valid": sv.tolist(),
+            "psnr_y_mean": mean(p), "ssim_mean": mean(sm), "ssim_valid_mean": mean(sv), "avg_psnr": mean(crop)}

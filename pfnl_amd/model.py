@@ -263,25 +263,30 @@ class PFNL(VSR):
     # ---- inference harness ------------------------------------------------------------------------
     encode_threads = min(16, os.cpu_count() or 1)   # PNG encoders / decoders running while the GPU works on the next batch
 
-    def _run_sequence(self, lrs, save_path: str, part: int):
-        """Device-scoped wrapper: the harness helpers (pfnl_op_gather_windows / quantise_u8) launch on the tensor's stream without
-        a hipSetDevice of their own, so the whole body runs with this model's device current (self.device != 0)."""
+    def _run_sequence(self, lrs, save_path: str, part: int, truth_u8=None):
+        """Device-scoped wrapper: the harness helpers (pfnl_op_gather_windows / quantise_u8 / score_y) launch on the tensor's stream
+        without a hipSetDevice of their own, so the whole body runs with this model's device current (self.device != 0)."""
         import torch
         with torch.cuda.device(self.device):
-            return self._run_sequence_on_device(lrs, save_path, part)
+            return self._run_sequence_on_device(lrs, save_path, part, truth_u8)
 
-    def _run_sequence_on_device(self, lrs, save_path: str, part: int):
+    def _run_sequence_on_device(self, lrs, save_path: str, part: int, truth_u8=None):
         """Shared tail of test_video_truth / test_video_lr (model/pfnl.py:236-262, 293-320).  ``lrs`` [F,H,W,3] float32:
         numpy (uploaded ONCE) or already a cuda tensor.  Per batch, all on the device: gather of the clamped T-frame
         windows (pfnl_op_gather_windows), pfnl_forward, uint8 quantisation (pfnl_op_quantise_u8); the uint8 frames
         come back over PCIe (a quarter of the float bytes, pinned double-buffered, asynchronous) and are PNG-encoded on
         worker threads while the NEXT batch runs on the GPU.  The time reported per batch is the device time from the
         window gather to the frames' arrival on the host (HIP events) - what the reference times around sess.run
-        (:249-253) -, first batch excluded from the average."""
+        (:249-253) -, first batch excluded from the average.
+        ``truth_u8`` [F,Hc,Wc,3] uint8 on the device (score_video_truth): every batch's uint8 frames - their top-left
+        Hc x Wc where the SR frame is larger - are scored against it on the batch's stream right behind the quantisation
+        (pfnl_op_score_y), the 32 bytes per frame travel with the frames, and the [F,4] float64 sums are returned
+        (metrics.sequence_scores).  A batch recomputed on the strict kernels is scored again from the recomputed frames.
+        Without it nothing more is launched or copied, and None is returned."""
         max_frame = int(lrs.shape[0])
         if max_frame == 0:
             print('Save at {}'.format(save_path))
-            return
+            return None if truth_u8 is None else np.zeros((0, 4), np.float64)
         import torch
         from concurrent.futures import ThreadPoolExecutor
         from . import ops
@@ -299,7 +304,18 @@ class PFNL(VSR):
         jobs = []
         stream = torch.cuda.current_stream(frames.device)
         host = []                                                    # pinned uint8 landing buffers: a ring of lanes + 1 (one being drained, `lanes` in flight)
-        inflight = []                                                # FIFO of (done event, start event, host buffer, first, count, ran strict, lane)
+        host_sums = []                                               # ... and, when scoring, the pinned [num_once,4] float64 buffers beside them
+        sums = None if truth_u8 is None else np.zeros((max_frame, 4), np.float64)
+        inflight = []                                                # FIFO of (done event, start event, host buffer, sums buffer, first, count, ran strict, lane)
+
+        def score_into(sbuf, u8_, first_, count_):                   # on the current stream, behind quantise_u8
+            if truth_u8 is None:
+                return
+            hc, wc = int(truth_u8.shape[1]), int(truth_u8.shape[2])
+            pred = u8_[:, 0]
+            if tuple(pred.shape[1:3]) != (hc, wc):
+                pred = pred[:, :hc, :wc].contiguous()
+            sbuf[:count_].copy_(ops.score_y(pred, truth_u8[first_:first_ + count_], 8), non_blocking=True)
 
         # TWO FORWARDS IN FLIGHT (round 6, opt-in: PFNL_HARNESS_INFLIGHT=2).  The reference calls this with part = 50 / 1000 (model/pfnl.py:264,
         # 332), i.e. ONE window per sess.run for every Vid4 / UDM10 sequence (:211-216) - and one clip of that size is the launch structure
@@ -356,18 +372,19 @@ class PFNL(VSR):
                 e.set_option("strict_fp32", "on")
             state["strict"] = True
 
-        def recompute_strict(buf, first_, count_, lane_):
+        def recompute_strict(buf, sbuf, first_, count_, lane_):
             with torch.cuda.stream(streams[lane_]):
                 win_ = ops.gather_windows(frames, first_, count_, self.num_frames)
                 u8_ = ops.quantise_u8(engines[lane_].forward(win_))
                 buf[:count_].copy_(u8_, non_blocking=True)
+                score_into(sbuf, u8_, first_, count_)                # the scores are those of the frames that are written
             streams[lane_].synchronize()
             engines[lane_].range_flagged()                           # (strict path: the fence is not armed; clears a stale flag)
 
         last_done = [None]
 
         def drain(item, pool):
-            done, started, buf, first_, count_, was_strict, lane_ = item
+            done, started, buf, sbuf, first_, count_, was_strict, lane_ = item
             done.synchronize()                                       # this batch's frames are on the host
             # device time of the batch: gather + forward + quantise + D2H.  Two in flight: the time from the previous batch's arrival to
             # this one's (the batches overlap: their own spans would count the shared time twice)
@@ -382,8 +399,10 @@ class PFNL(VSR):
             if not was_strict and (engines[lane_].range_flagged() or state["strict"]):
                 if not state["strict"]:
                     go_strict()
-                recompute_strict(buf, first_, count_, lane_)
+                recompute_strict(buf, sbuf, first_, count_, lane_)
             frames_u8 = buf[:count_].numpy().copy()                  # (the pinned buffer is reused two batches later)
+            if sums is not None:
+                sums[first_:first_ + count_] = sbuf[:count_].numpy()
             for j in range(count_):
                 jobs.append(pool.submit(imsave_rgb, join(save_path, '{:0>4}.png'.format(first_ + j)), frames_u8[j][0]))
 
@@ -405,9 +424,11 @@ class PFNL(VSR):
                         k = i % (lanes + 1)
                         if len(host) <= k:
                             host.append(torch.empty((num_once,) + tuple(u8.shape[1:]), dtype=torch.uint8).pin_memory())
+                            host_sums.append(None if sums is None else torch.empty((num_once, 4), dtype=torch.float64).pin_memory())
                         host[k][:count].copy_(u8, non_blocking=True)
+                        score_into(host_sums[k], u8, first, count)
                         done.record(streams[lane])
-                    inflight.append((done, started, host[k], first, count, was_strict, lane))
+                    inflight.append((done, started, host[k], host_sums[k], first, count, was_strict, lane))
                     if len(inflight) > lanes:                        # while the GPU runs the `lanes` newest batches: the oldest goes to the PNG encoders
                         drain(inflight.pop(0), pool)
                 while inflight:
@@ -426,6 +447,7 @@ class PFNL(VSR):
         all_time = np.array(all_time)
         avg = np.mean(all_time[1:]) if len(all_time) > 1 else float('nan')
         print('spent {} s in total and {} s in average'.format(np.sum(all_time), avg))
+        return sums
 
     def _ensure_loaded(self, reuse):
         """model/pfnl.py:229-232: restore the checkpoint unless the session is being reused.  load() returning False
@@ -439,20 +461,53 @@ class PFNL(VSR):
 
     def test_video_truth(self, path, name='result', reuse=False, part=50):
         """HR pngs in <path>/truth -> blur + decimate (utils.py:169-192) -> SR pngs in <path>/<name>."""
+        self._video_truth(path, name, reuse, part, score=False)
+
+    def score_video_truth(self, path, name='result', reuse=False, part=50):
+        """test_video_truth that also scores the SR frames against the HR frames on the device as they are produced
+        (pfnl_op_score_y: Y-channel PSNR of matlab/compute_psnr.m, AVG_PSNR of utils.py:213-246, SSIM of
+        modules/SSIM_Index.py:23-89): writes the same PNGs, prints one line with the sequence's means and returns the dict of
+        metrics.sequence_scores.  (A method of its own: the signatures of the reference's methods stay the reference's.)"""
+        return self._video_truth(path, name, reuse, part, score=True)
+
+    def _video_truth(self, path, name, reuse, part, score):
         save_path = join(path, name)
         automkdir(save_path)
         imgs = sorted(glob.glob(join(path, 'truth', '*.png')))
-        hr = imread_many(imgs, self.encode_threads) / 255.
+        truth = imread_many(imgs, self.encode_threads)
+        hr = truth / 255.
+        if score and hr.shape[0] and (hr.shape[1] < 11 or hr.shape[2] < 11):
+            raise ValueError("scoring needs HR frames of at least 11 x 11 (the SSIM window): {} x {}".format(*hr.shape[1:3]))
         self._ensure_loaded(reuse)
         if hr.shape[0] == 0:
-            return self._run_sequence(np.zeros((0, 0, 0, 3), np.float32), save_path, part)
+            self._run_sequence(np.zeros((0, 0, 0, 3), np.float32), save_path, part)
+            return self._report_scores(path, np.zeros((0, 4)), 0, 0) if score else None
         # unquantised float LR, as model/pfnl.py:224,234 - on the GPU (pfnl_op_blur_decimate)
         import torch
         from . import ops
         self._get_engine()                       # fails loudly without a device
         dev = "cuda:%d" % self.device
         lrs = ops.blur_decimate(torch.from_numpy(np.ascontiguousarray(hr, np.float32)).to(dev), self.scale)   # stays on the device
-        self._run_sequence(lrs, save_path, part)
+        if not score:
+            self._run_sequence(lrs, save_path, part)
+            return None
+        # the truth stays on the device as uint8.  The LR frame has ceil(H / scale) rows, so where H or W is no multiple of `scale` the
+        # SR frame and the HR frame differ in size: both are scored over their common top-left region (LR pixel i sits on HR pixel scale * i)
+        H, W = truth.shape[1:3]
+        hc, wc = min(H, int(lrs.shape[1]) * self.scale), min(W, int(lrs.shape[2]) * self.scale)
+        if (hc, wc) != (H, W) or (hc, wc) != (int(lrs.shape[1]) * self.scale, int(lrs.shape[2]) * self.scale):
+            print('score: HR {} x {} and SR {} x {} are compared over their common top-left {} x {}'.format(
+                H, W, int(lrs.shape[1]) * self.scale, int(lrs.shape[2]) * self.scale, hc, wc))
+        truth_u8 = torch.from_numpy(np.ascontiguousarray(truth[:, :hc, :wc])).to(dev)
+        return self._report_scores(path, self._run_sequence(lrs, save_path, part, truth_u8), hc, wc)
+
+    @staticmethod
+    def _report_scores(path, sums, H, W):
+        from . import metrics
+        sc = metrics.sequence_scores(sums, H, W)
+        print('{}: PSNR_Y {:.4f} dB, AVG_PSNR {:.4f} dB, SSIM {:.6f}'.format(
+            os.path.basename(os.path.normpath(path)), sc["psnr_y_mean"], sc["avg_psnr"], sc["ssim_mean"]))
+        return sc
 
     def test_video_lr(self, path, name='result', reuse=False, part=50):
         """LR pngs in <path>/blur{scale} -> SR pngs in <path>/<name>."""
@@ -468,11 +523,22 @@ class PFNL(VSR):
     testvideo = test_video_lr      # the README's wording (reference README.md:31)
 
     def testvideos(self, path='/dev/f/data/video/test2/udm10', start=0, name='pfnl'):
+        self._videos(path, start, name, score=False)
+
+    def score_videos(self, path='/dev/f/data/video/test2/udm10', start=0, name='pfnl'):
+        """testvideos with every sequence scored (score_video_truth): returns {sequence directory name: scores}."""
+        return self._videos(path, start, name, score=True)
+
+    def _videos(self, path, start, name, score):
         kind = sorted(glob.glob(join(path, '*')))
         kind = [k for k in kind if os.path.isdir(k)]
         reuse = False
+        scores = {}
         for idx, k in enumerate(kind):
             if idx >= start:
                 if idx > start:
                     reuse = True
-                self.test_video_truth(k, name=name, reuse=reuse, part=1000)
+                sc = (self.score_video_truth if score else self.test_video_truth)(k, name=name, reuse=reuse, part=1000)
+                if score:
+                    scores[os.path.basename(os.path.normpath(k))] = sc
+        return scores if score else None

@@ -434,6 +434,28 @@ def quantise_u8(sr):
     return out
 
 
+def score_y(pred_u8, truth_u8, sp_border: int = 8):
+    """Y-channel quality sums of uint8 RGB frame pairs on the device (pfnl_op_score_y): pred_u8, truth_u8 [F,H,W,3] uint8 (cuda)
+    -> [F,4] float64 (cuda): sum_d2_full, sum_d2_crop (spatial border sp_border), ssim_sum_full, ssim_sum_valid.
+    metrics.sequence_scores turns them into PSNR_Y / SSIM / AVG_PSNR (matlab/compute_psnr.m, modules/SSIM_Index.py:23-89,
+    utils.py:213-246).  Asynchronous on the current stream; the partials scratch comes from torch's allocator."""
+    import torch
+    lib = _capi.load_library()
+    for t, name in ((pred_u8, "pred_u8"), (truth_u8, "truth_u8")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise TypeError(f"{name} must be a contiguous uint8 tensor on the GPU")
+    if pred_u8.dim() != 4 or pred_u8.shape[3] != 3 or truth_u8.shape != pred_u8.shape or truth_u8.device != pred_u8.device:
+        raise ValueError("score_y expects two [F,H,W,3] tensors of one shape on one device")
+    F, H, W, _ = pred_u8.shape
+    nbytes = C.c_size_t(0)
+    _capi.check(lib.pfnl_op_score_scratch_bytes(F, H, W, C.byref(nbytes)))
+    scratch = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=pred_u8.device)
+    out = torch.empty((F, 4), dtype=torch.float64, device=pred_u8.device)
+    _capi.check(lib.pfnl_op_score_y(C.c_void_p(pred_u8.data_ptr()), C.c_void_p(truth_u8.data_ptr()), F, H, W, int(sp_border),
+                                    C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), _stream(pred_u8)))
+    return out
+
+
 def conv2_chain_ex(x, kernel, bias, base, resid, add_div: int, act: bool = True, mfma: int = 32, split=(0, 0, 0), out=None):
     """The whole of conv2_i in one launch (reference model/pfnl.py:69-71) with the MFMA shape and the split-chain geometry given explicitly
     (pfnl_op_conv2_chain_ex): x = inp1 [F,H,W,64], base [F/add_div,H,W,64], resid [F,H,W,64] (cuda fp32), kernel HWIO [3,3,128,64] ->
