@@ -216,6 +216,39 @@ int pfnl_range_reruns(pfnl_handle* h, long long* count);
  * re-runs a batch on it should treat the batches already enqueued behind it as suspect too: pfnl_amd/model.py does). */
 int pfnl_range_flag(pfnl_handle* h, int* flagged);
 
+/* ---- streaming session: uint8 LR frames in, uint8 SR frames out ------------------------------ */
+/* The loop the reference runs around sess.run (model/pfnl.py:236-262, 293-320: clamped T-frame windows, the forward, clip / round to uint8)
+ * for frames that arrive one at a time and a sequence whose length is not known: push LR frames [H,W,3] uint8 RGB (values / 255. as the
+ * harness feeds them), pop SR frames [sH,sW,3] uint8 in index order.  One open session per handle; `hip_stream` NULL = the handle's own.
+ * BATCHES: frame i is super-resolved in the batch [k*batch, min((k+1)*batch, F)) that holds it, whatever the timing of the calls -
+ *   pfnl_stream_next_batch is the rule, and the session runs it: first = launched; before pfnl_stream_end a batch launches when its last
+ *   window's newest frame is there (pushed >= launched + batch + T/2), after it the remainder does (count = min(batch, pushed - launched)).
+ *   The launch plan, and with it the last bits, depend on the batch size (pfnl_plan): these are the batches - and the bytes - of
+ *   test_video_lr with num_once == batch.
+ * push copies the frame into a device ring (host pointer: the buffer is free on return) and, when a batch is due, enqueues window gather,
+ *   pfnl_forward and quantisation on the session's stream without waiting for them.  pop delivers the next frame (*got = 1, *index) or
+ *   nothing (*got = 0: not an error); it waits only for the batch that holds that frame.  With device pointers both are asynchronous on
+ *   the session's stream.  pfnl_stream_ready: the frames pop would deliver without another push.
+ * BOUNDED: at most 2 * batch undelivered SR frames; a push that would launch a batch beyond that returns PFNL_ERR_STATE ("pop first") and
+ *   changes nothing.  All device buffers are allocated by pfnl_stream_open (ring of 3 batch + T - 2 LR frames, one window stack, two
+ *   batches of SR frames).
+ * RANGE: before the first frame of a batch leaves, the session reads pfnl_range_flag; a flagged batch and every batch already enqueued
+ *   behind it are computed again with strict_fp32=on (under precision=bf16: precision=fp32 as well), and so is the rest of the sequence.
+ *   The flag belongs to the handle, not to a batch: with two batches in flight, one raised by the second may be read at the first's check,
+ *   and then the batch IN FRONT of the one that left the range is recomputed too (its strict result is as valid; the harness does the same).
+ *   The pop that delivers the last frame after pfnl_stream_end, pfnl_stream_reset and pfnl_stream_close put back what pfnl_get_option
+ *   returned before (only the keys that were changed).  pfnl_stream_reset drops what was not popped and starts the next sequence.
+ * Plain pfnl_forward calls on the handle remain possible between pushes: on the session's stream, or after synchronising it. */
+typedef struct pfnl_stream pfnl_stream;
+int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, pfnl_stream** out);
+int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame /*[H,W,3]*/, int is_device);
+int pfnl_stream_end(pfnl_stream* s);
+int pfnl_stream_ready(pfnl_stream* s, int* frames);
+int pfnl_stream_pop(pfnl_stream* s, uint8_t* out /*[sH,sW,3]*/, int is_device, long long* index, int* got);
+int pfnl_stream_reset(pfnl_stream* s);
+int pfnl_stream_close(pfnl_stream* s);
+int pfnl_stream_next_batch(int T, int batch, long long pushed, int ended, long long launched, long long* first, int* count);
+
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
  * no staging copy through the handle's strips.  Process-wide, not tied to a handle; pfnl_amd/engine.py keeps a small, size-capped pool of
@@ -470,6 +503,12 @@ int pfnl_op_tail(const float* merge, const float* x, const float* kernel_host, c
  * quantise: uint8(np.round(np.clip(sr * 255, 0, 255))) (round half to even), n % 4 == 0. */
 int pfnl_op_gather_windows(const float* frames, float* win, int F, int first, int count, int T, int H, int W, void* stream);
 int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream);
+/* The session's input side (stream_gather_u8_kernel): ring [cap,H,W,3] uint8 with frame f in slot f % cap -> win [count,T,H,W,3] float32,
+ * window w slot t = frame clip(first + w + t - T/2, 0, last), every value the harness's (u8 / 255.).astype(np.float32) bit for bit
+ * (reference model/pfnl.py:287; a 256-entry table).  The frames the windows name must fit the ring; first + count - 1 <= last; ring
+ * 4-byte aligned (16-byte for the 16-byte reads), win 16-byte aligned - else PFNL_ERR_INVALID. */
+int pfnl_op_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T, int H, int W,
+                              void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

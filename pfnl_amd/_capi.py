@@ -95,6 +95,15 @@ SIGNATURES = {
     "pfnl_op_tail": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pfnl_op_quantise_u8": (_i, [_vp, _vp, C.c_size_t, _vp]),
+    "pfnl_op_gather_windows_u8": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
+    "pfnl_stream_open": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
+    "pfnl_stream_push": (_i, [_vp, _vp, _i]),
+    "pfnl_stream_end": (_i, [_vp]),
+    "pfnl_stream_ready": (_i, [_vp, C.POINTER(_i)]),
+    "pfnl_stream_pop": (_i, [_vp, _vp, _i, C.POINTER(C.c_longlong), C.POINTER(_i)]),
+    "pfnl_stream_reset": (_i, [_vp]),
+    "pfnl_stream_close": (_i, [_vp]),
+    "pfnl_stream_next_batch": (_i, [_i, _i, C.c_longlong, _i, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_i)]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
     "pfnl_op_score_y": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pfnl_comm_get_unique_id": (_i, [_vp]),

@@ -286,7 +286,13 @@ struct pfnl_handle {
     size_t evs_used = 0;
     double prof_ms[PFNL_K_COUNT] = {0};
     int64_t prof_n[PFNL_K_COUNT] = {0};
+
+    pfnl_stream* session = nullptr;   // the one open streaming session (capi_stream.hip): the handle is not re-entrant
 };
+
+pfnl_handle_view pfnl_internal_view(pfnl_handle* h) {
+    return {h->cfg.num_frames, h->cfg.scale, h->cfg.device_id, h->finalized, h->stream, &h->session};
+}
 
 namespace {
 
@@ -1140,6 +1146,7 @@ int pfnl_create(const pfnl_config* cfg, pfnl_handle** out) {
 
 int pfnl_destroy(pfnl_handle* h) {
     if (!h) return 0;
+    if (h->session) pfnl_stream_close(h->session);               // (its buffers and events; the options die with the handle)
     hipSetDevice(h->cfg.device_id);
     if (h->stream) {
         hipStreamSynchronize(h->stream);

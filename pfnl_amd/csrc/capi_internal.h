@@ -1,5 +1,7 @@
 // Internal to libpfnl_hip: shared by the translation units of the C-ABI.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <string>
 
 int pfnl_internal_fail(int code, const std::string& msg);   // records msg for pfnl_last_error(); returns code
@@ -10,6 +12,18 @@ int pfnl_internal_fail(int code, const std::string& msg);   // records msg for p
         hipError_t _e = (expr);                                                                                     \
         if (_e != hipSuccess) return pfnl_internal_fail(PFNL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
+
+// What the streaming session (capi_stream.hip) needs of a handle, whose layout stays private to capi.hip: its geometry and state, its own
+// stream, and the slot that holds the handle's one open session (NULL: none).
+struct pfnl_handle;
+struct pfnl_stream;
+struct pfnl_handle_view {
+    int num_frames, scale, device_id;
+    bool finalized;
+    hipStream_t stream;
+    pfnl_stream** session;
+};
+pfnl_handle_view pfnl_internal_view(pfnl_handle* h);
 
 // The 1x1 convolutions of the non-local block folded on the host in fp64 (reference utils.py:18-71), as pfnl_finalize_weights and the op
 // hooks use them.  Inputs are [C][C] row-major (in, out); the folded matrices are written with row stride CP (>= C + 1).

@@ -875,6 +875,21 @@ int pfnl_op_gather_windows(const float* frames, float* win, int F, int first, in
     return 0;
 }
 
+int pfnl_op_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T, int H, int W,
+                              void* stream) {
+    if (!ring || !win) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (cap < 1 || last < 0 || first < 0 || count < 1 || T < 1 || !(T & 1) || H < 1 || W < 1 || ((size_t)H * W * 3) % 4)
+        return fail(PFNL_ERR_INVALID, "bad window geometry (H*W*3 must be a multiple of 4, T odd, cap >= 1, first, last >= 0)");
+    if (first + count - 1 > last) return fail(PFNL_ERR_INVALID, "a window's centre frame lies beyond `last`");
+    if (reinterpret_cast<uintptr_t>(ring) % 4 || reinterpret_cast<uintptr_t>(win) % 16)
+        return fail(PFNL_ERR_INVALID, "ring must be 4-byte aligned and win 16-byte aligned");
+    // the frames the windows name, after the clamps, must all be in the ring at once
+    const long long lo = first - T / 2 < 0 ? 0 : first - T / 2, hi = first + count - 1 + T / 2 > last ? last : first + count - 1 + T / 2;
+    if (hi - lo + 1 > cap) return fail(PFNL_ERR_INVALID, "the windows span more frames than the ring holds");
+    HIPCHK(pfnl::launch_gather_windows_u8(ring, win, cap, last, first, count, T, (size_t)H * W * 3, (hipStream_t)stream));
+    return 0;
+}
+
 int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream) {
     if (!sr || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (!n || n % 4) return fail(PFNL_ERR_INVALID, "element count must be a positive multiple of 4");

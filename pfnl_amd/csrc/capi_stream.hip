@@ -1,0 +1,304 @@
+// The streaming session of the C-ABI (include/pfnl_hip.h, pfnl_stream_*): uint8 LR frames are pushed one at a time, uint8 SR frames are
+// popped in order.  What the harness's loop does around the forward (reference model/pfnl.py:236-262; pfnl_amd/model.py
+// _run_sequence_on_device) - clamped windows, batching, quantisation, the range flag and the recomputation on the strict kernels - lives
+// here, behind pfnl_forward's own interface: the session calls pfnl_forward / pfnl_get_option / pfnl_set_option / pfnl_range_flag like
+// any other caller and knows nothing of the handle's layout (capi_internal.h, pfnl_handle_view).
+#include <deque>
+#include <string>
+
+#include "../../include/pfnl_hip.h"
+#include "capi_internal.h"
+#include "common.h"
+
+namespace {
+
+int fail(int code, const std::string& msg) { return pfnl_internal_fail(code, msg); }
+
+struct Batch {
+    long long first, last;   // its first frame; the newest frame its windows may name (the clamp)
+    int count, slot;
+    bool was_strict;         // launched after the session went strict: the range fence was not armed, nothing to check
+    bool checked;            // its event has been waited for and its range flag read (and the batch recomputed if need be)
+};
+
+}  // namespace
+
+struct pfnl_stream {
+    pfnl_handle* h = nullptr;
+    int H = 0, W = 0, batch = 0, T = 0, scale = 0, device = 0, cap = 0;
+    size_t lr_bytes = 0, sr_bytes = 0;                // one LR / SR frame, uint8
+    hipStream_t s = nullptr;                          // everything the session computes runs here
+    hipStream_t cs = nullptr;                         // host-pointer frames in and out: copies that never wait for a later batch
+    uint8_t* ring = nullptr;                          // [cap][H][W][3], frame f in slot f % cap
+    float* win = nullptr;                             // [batch][T][H][W][3]
+    float* sr = nullptr;                              // [batch][sH][sW][3]
+    uint8_t* out[2] = {nullptr, nullptr};             // [batch][sH][sW][3] each: the undelivered frames of at most two batches
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool slot_busy[2] = {false, false};
+    long long pushed = 0, launched = 0, delivered = 0;
+    bool ended = false;
+    std::deque<Batch> q;                              // launched, not yet fully delivered: at most two
+    bool strict = false;                              // a batch was flagged: the rest of the sequence runs on the strict kernels
+    std::string prior_strict, prior_precision;        // what the library held before go_strict changed it ("" = unchanged)
+};
+
+namespace {
+
+int get_option(pfnl_stream* s, const char* key, std::string* v) {
+    char buf[64];
+    if (int e = pfnl_get_option(s->h, key, buf, sizeof buf)) return e;
+    *v = buf;
+    return 0;
+}
+
+// gather -> forward -> quantise into the batch's slot, then its event; asynchronous on the session's stream
+int enqueue(pfnl_stream* s, const Batch& b) {
+    HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
+    if (int e = pfnl_forward(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->s)) return e;
+    HIPCHK(pfnl::launch_quantise_u8(s->sr, s->out[b.slot], (size_t)b.count * s->sr_bytes, s->s));
+    HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
+    return 0;
+}
+
+// launches every batch the rule yields for which an output slot is free
+int pump(pfnl_stream* s) {
+    for (;;) {
+        long long first = 0;
+        int count = 0;
+        if (int e = pfnl_stream_next_batch(s->T, s->batch, s->pushed, s->ended, s->launched, &first, &count)) return e;
+        if (!count) return 0;
+        const int slot = !s->slot_busy[0] ? 0 : (!s->slot_busy[1] ? 1 : -1);
+        if (slot < 0) return 0;
+        const Batch b{first, s->pushed - 1, count, slot, s->strict, false};
+        if (int e = enqueue(s, b)) return e;
+        s->slot_busy[slot] = true;
+        s->launched += count;
+        s->q.push_back(b);
+    }
+}
+
+// The rest of the sequence on the kernels without a binary16 domain (pfnl_hip.h "strict_fp32"); under precision=bf16 that means
+// precision=fp32 as well, as strict_fp32 changes nothing about that precision's non-local block and conv0.
+int go_strict(pfnl_stream* s) {
+    HIPCHK(hipStreamSynchronize(s->s));               // no forward of the old configuration is in flight when it changes
+    std::string v;
+    if (int e = get_option(s, "precision", &v)) return e;
+    if (v == "bf16") {
+        if (int e = pfnl_set_option(s->h, "precision", "fp32")) return e;
+        s->prior_precision = v;
+    }
+    if (int e = get_option(s, "strict_fp32", &v)) return e;
+    if (v != "on") {
+        if (int e = pfnl_set_option(s->h, "strict_fp32", "on")) return e;
+        s->prior_strict = v;
+    }
+    s->strict = true;
+    return 0;
+}
+
+// back to what the library held before go_strict; only the keys it changed.  The caller has made sure nothing is in flight.
+int restore_options(pfnl_stream* s) {
+    int r = 0;
+    if (!s->prior_strict.empty()) {
+        if (int e = pfnl_set_option(s->h, "strict_fp32", s->prior_strict.c_str())) r = e;
+        s->prior_strict.clear();
+    }
+    if (!s->prior_precision.empty()) {
+        if (int e = pfnl_set_option(s->h, "precision", s->prior_precision.c_str())) r = e;
+        s->prior_precision.clear();
+    }
+    s->strict = false;
+    return r;
+}
+
+// The range fence, once per batch, before any of its frames leaves: wait for the batch, read the flag; a flagged batch - and every batch
+// that was enqueued behind it before the flag was seen - is computed again on the strict kernels from the frames the ring still holds.
+int check_batch(pfnl_stream* s, Batch& b) {
+    HIPCHK(hipEventSynchronize(s->ev[b.slot]));
+    if (!b.was_strict) {
+        int flagged = 0;
+        if (int e = pfnl_range_flag(s->h, &flagged)) return e;
+        if (flagged || s->strict) {
+            if (!s->strict)
+                if (int e = go_strict(s)) return e;
+            if (int e = enqueue(s, b)) return e;
+            HIPCHK(hipEventSynchronize(s->ev[b.slot]));
+            (void)pfnl_range_flag(s->h, &flagged);    // (strict path: the fence is not armed; clears a stale flag)
+        }
+    }
+    b.checked = true;
+    return 0;
+}
+
+// forgets the sequence: nothing in flight afterwards, options as before the session changed them
+int drop_sequence(pfnl_stream* s) {
+    int r = 0;
+    if (hipStreamSynchronize(s->s) != hipSuccess || hipStreamSynchronize(s->cs) != hipSuccess)
+        r = fail(PFNL_ERR_HIP, "stream synchronisation failed");
+    bool unchecked = false;
+    for (const Batch& b : s->q) unchecked = unchecked || !b.checked;
+    if (unchecked) {                                  // a flag raised by a batch that is dropped must not fall on the next sequence
+        int flagged = 0;
+        (void)pfnl_range_flag(s->h, &flagged);
+    }
+    s->q.clear();
+    s->slot_busy[0] = s->slot_busy[1] = false;
+    s->pushed = s->launched = s->delivered = 0;
+    s->ended = false;
+    if (int e = restore_options(s)) r = e;
+    return r;
+}
+
+void release(pfnl_stream* s) {
+    for (int i = 0; i < 2; ++i) {
+        if (s->out[i]) (void)hipFree(s->out[i]);
+        if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
+    }
+    if (s->ring) (void)hipFree(s->ring);
+    if (s->win) (void)hipFree(s->win);
+    if (s->sr) (void)hipFree(s->sr);
+    if (s->cs) (void)hipStreamDestroy(s->cs);
+    delete s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfnl_stream_next_batch(int T, int batch, long long pushed, int ended, long long launched, long long* first, int* count) {
+    if (!first || !count) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (T < 1 || !(T & 1) || batch < 1 || launched < 0 || pushed < launched)
+        return fail(PFNL_ERR_INVALID, "next_batch: T odd, batch >= 1, 0 <= launched <= pushed");
+    *first = launched;
+    if (ended)
+        *count = (int)(pushed - launched < batch ? pushed - launched : batch);
+    else
+        *count = pushed >= launched + batch + T / 2 ? batch : 0;   // the last window's newest frame, index + T/2, is present
+    return 0;
+}
+
+int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, pfnl_stream** out) {
+    if (!h || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (batch < 1) return fail(PFNL_ERR_INVALID, "batch must be at least 1");
+    if (H <= 0 || W <= 0 || (H & 1) || (W & 1))
+        return fail(PFNL_ERR_INVALID, "H and W must be positive and even (space_to_depth(2), reference model/pfnl.py:57)");
+    const pfnl_handle_view v = pfnl_internal_view(h);
+    if (!v.finalized) return fail(PFNL_ERR_STATE, "pfnl_finalize_weights has not been called");
+    if (*v.session) return fail(PFNL_ERR_STATE, "the handle already has an open session (a handle is not re-entrant): close it first");
+    if ((long long)batch * v.num_frames > (1 << 30)) return fail(PFNL_ERR_INVALID, "batch too large");
+    HIPCHK(hipSetDevice(v.device_id));
+    pfnl_stream* s = new pfnl_stream();
+    s->h = h;
+    s->H = H;
+    s->W = W;
+    s->batch = batch;
+    s->T = v.num_frames;
+    s->scale = v.scale;
+    s->device = v.device_id;
+    s->s = hip_stream ? (hipStream_t)hip_stream : v.stream;
+    s->lr_bytes = (size_t)H * W * 3;
+    s->sr_bytes = s->lr_bytes * v.scale * v.scale;
+    // The ring keeps a batch's frames until the batch has been checked (it may have to be computed again): with two batches undelivered,
+    // the oldest needed frame is launched - 2 batch - T/2, and pushes go on up to launched + batch + T/2 - 2 before the one that would
+    // launch a third batch is refused: 3 batch + T - 2 frames.
+    s->cap = 3 * batch + s->T - 2;
+    bool ok = hipStreamCreateWithFlags(&s->cs, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&s->ring), (size_t)s->cap * s->lr_bytes) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&s->win), (size_t)batch * s->T * s->lr_bytes * sizeof(float)) == hipSuccess;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&s->sr), (size_t)batch * s->sr_bytes * sizeof(float)) == hipSuccess;
+    for (int i = 0; i < 2; ++i) {
+        ok = ok && hipMalloc(reinterpret_cast<void**>(&s->out[i]), (size_t)batch * s->sr_bytes) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&s->ev[i], hipEventDisableTiming) == hipSuccess;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        release(s);
+        return fail(PFNL_ERR_NOMEM, "session allocation failed");
+    }
+    *v.session = s;
+    *out = s;
+    return 0;
+}
+
+int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
+    if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (s->ended) return fail(PFNL_ERR_STATE, "push after pfnl_stream_end (pfnl_stream_reset starts the next sequence)");
+    long long first = 0;
+    int count = 0;
+    if (int e = pfnl_stream_next_batch(s->T, s->batch, s->pushed + 1, 0, s->launched, &first, &count)) return e;
+    const long long oldest = s->q.empty() ? s->launched : s->q.front().first;
+    const long long lo = oldest - s->T / 2 < 0 ? 0 : oldest - s->T / 2;
+    if ((count && s->launched - s->delivered + count > 2LL * s->batch) || s->pushed - lo + 1 > s->cap)
+        return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
+    HIPCHK(hipSetDevice(s->device));
+    uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->lr_bytes;
+    if (is_device) {
+        HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
+    } else {
+        // the slot's previous frame belongs to batches that have been delivered, so nothing on the session's stream reads it; the copy
+        // runs beside the batches in flight and the caller's buffer is free on return
+        HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
+        HIPCHK(hipStreamSynchronize(s->cs));
+    }
+    ++s->pushed;
+    return pump(s);
+}
+
+int pfnl_stream_end(pfnl_stream* s) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    HIPCHK(hipSetDevice(s->device));
+    s->ended = true;
+    if (int e = pump(s)) return e;
+    if (s->delivered == s->pushed) return restore_options(s);   // (nothing left to pop: nothing in flight either)
+    return 0;
+}
+
+int pfnl_stream_ready(pfnl_stream* s, int* frames) {
+    if (!s || !frames) return fail(PFNL_ERR_INVALID, "NULL argument");
+    *frames = (int)((s->ended ? s->pushed : s->launched) - s->delivered);
+    return 0;
+}
+
+int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* index, int* got) {
+    if (!s || !out || !index || !got) return fail(PFNL_ERR_INVALID, "NULL argument");
+    *got = 0;
+    HIPCHK(hipSetDevice(s->device));
+    if (int e = pump(s)) return e;
+    if (s->q.empty()) return 0;
+    Batch& b = s->q.front();
+    if (!b.checked)
+        if (int e = check_batch(s, b)) return e;
+    const uint8_t* const src = s->out[b.slot] + (size_t)(s->delivered - b.first) * s->sr_bytes;
+    if (is_device) {
+        HIPCHK(hipMemcpyAsync(out, src, s->sr_bytes, hipMemcpyDeviceToDevice, s->s));   // ordered like the caller's own work on that stream
+    } else {
+        HIPCHK(hipMemcpyAsync(out, src, s->sr_bytes, hipMemcpyDeviceToHost, s->cs));    // the batch has completed: no wait for a later one
+        HIPCHK(hipStreamSynchronize(s->cs));
+    }
+    *index = s->delivered++;
+    *got = 1;
+    if (s->delivered == b.first + b.count) {
+        s->slot_busy[b.slot] = false;                 // (a device-pointer copy out of it is ahead of the next batch on the same stream)
+        s->q.pop_front();
+        if (int e = pump(s)) return e;
+        if (s->ended && s->delivered == s->pushed) return restore_options(s);   // (every forward has completed: its batch was checked)
+    }
+    return 0;
+}
+
+int pfnl_stream_reset(pfnl_stream* s) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    HIPCHK(hipSetDevice(s->device));
+    return drop_sequence(s);
+}
+
+int pfnl_stream_close(pfnl_stream* s) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    (void)hipSetDevice(s->device);
+    const int r = drop_sequence(s);
+    *pfnl_internal_view(s->h).session = nullptr;
+    release(s);
+    return r;
+}
+
+}  // extern "C"

@@ -155,6 +155,10 @@ hipError_t run_mfma_selftest(int* mismatches);
 hipError_t launch_gather_windows(const float* frames, float* win, int F, int first, int count, int T, size_t frame_floats,
                                  hipStream_t s);
 hipError_t launch_quantise_u8(const float* sr, uint8_t* out, size_t n, hipStream_t s);
+// ring [cap][frame_bytes] uint8 (frame f in slot f % cap) -> win [count][T][frame_bytes] fp32 = u8 / 255. as the harness computes it,
+// window w slot t = frame clamp(first + w + t - T/2, 0, last); frame_bytes % 4 == 0 (stream.hip)
+hipError_t launch_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T,
+                                    size_t frame_bytes, hipStream_t s);
 
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;

@@ -424,6 +424,23 @@ def gather_windows(frames, first: int, count: int, num_frames: int):
     return out
 
 
+def gather_windows_u8(ring, last: int, first: int, count: int, num_frames: int):
+    """ring [cap,H,W,3] uint8 (cuda), frame f in slot f % cap -> [count,T,H,W,3] float32: the clamped sliding windows of frames
+    first..first+count-1 of a sequence whose newest frame is ``last``, dequantised as the harness does, (u8 / 255.).astype(np.float32)
+    (pfnl_op_gather_windows_u8: the streaming session's input side; reference model/pfnl.py:238-242, :287)."""
+    import torch
+    lib = _capi.load_library()
+    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dtype == torch.uint8 and ring.is_contiguous()):
+        raise TypeError("ring must be a contiguous uint8 tensor on the GPU")
+    cap, H, W, c = ring.shape
+    if c != 3:
+        raise ValueError("gather_windows_u8 expects [cap,H,W,3]")
+    out = torch.empty((count, num_frames, H, W, 3), dtype=torch.float32, device=ring.device)
+    _capi.check(lib.pfnl_op_gather_windows_u8(C.c_void_p(ring.data_ptr()), _req(out, "out"), cap, int(last), int(first), count, num_frames,
+                                              H, W, _stream(ring)))
+    return out
+
+
 def quantise_u8(sr):
     """uint8(np.round(np.clip(sr * 255, 0, 255))) on the device (reference model/pfnl.py:254-257)."""
     import torch

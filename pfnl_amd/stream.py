@@ -1,0 +1,145 @@
+"""VideoStream - the Python face of the C-ABI's streaming session (include/pfnl_hip.h, pfnl_stream_*).
+
+uint8 LR frames go in one at a time, uint8 SR frames come out in order; the clamped windows, the batching, the quantisation and the
+range-flag recovery of the harness (pfnl_amd/model.py _run_sequence_on_device; reference model/pfnl.py:236-262) happen inside the
+library.  Nothing here computes::
+
+    with model.open_stream(H, W, batch=4) as vs:
+        for frame in decoder:                      # [H,W,3] uint8
+            for index, sr in vs.push(frame):       # [] until a batch of 4 has its look-ahead of T/2 frames
+                sink(index, sr)                    # [sH,sW,3] uint8
+        for index, sr in vs.end():
+            sink(index, sr)
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Tuple
+
+import numpy as np
+
+from . import _capi
+
+
+def next_batch(num_frames: int, batch: int, pushed: int, ended: bool, launched: int) -> Tuple[int, int]:
+    """(first, count) of the batch that may launch now, count = 0 for none (pfnl_stream_next_batch: the session's own rule; needs no
+    device).  A sequence of F frames always runs as the batches [k*batch, min((k+1)*batch, F))."""
+    first, count = C.c_longlong(0), C.c_int(0)
+    _capi.check(_capi.load_library().pfnl_stream_next_batch(int(num_frames), int(batch), int(pushed), 1 if ended else 0, int(launched),
+                                                            C.byref(first), C.byref(count)))
+    return first.value, count.value
+
+
+class VideoStream:
+    """One open session on an engine (``PFNLEngine.open_stream`` / ``PFNL.open_stream``); an engine has one at a time.
+
+    ``push(frame)`` takes a [H,W,3] uint8 numpy array or a uint8 torch tensor on the engine's device and returns the SR frames that
+    have become deliverable as a list of ``(index, frame)`` - numpy in, numpy out; device tensor in, device tensors out.  Device
+    tensors are read and written on the stream that was torch's current stream when the session was opened."""
+
+    def __init__(self, engine, H: int, W: int, batch: int = 1):
+        import torch
+        if not engine._ready:
+            raise RuntimeError("weights have not been loaded")
+        self._engine = engine                       # (keeps the handle alive)
+        self._lib = engine._lib
+        self.H, self.W, self.batch = int(H), int(W), int(batch)
+        self.scale = engine.geom.scale
+        self.device = torch.device("cuda", engine.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        s = C.c_void_p()
+        _capi.check(self._lib.pfnl_stream_open(engine._h, self.H, self.W, self.batch, C.c_void_p(stream) if stream else None, C.byref(s)))
+        self._s = s
+        self._device_frames = False                 # the container of the last pushed frame decides that of the popped ones
+
+    # ---- lifetime --------------------------------------------------------------------------
+    def close(self) -> None:
+        """Drops what was not popped, restores the options a range recovery changed, frees the session's buffers."""
+        if getattr(self, "_s", None):
+            s, self._s = self._s, None
+            if getattr(self._engine, "_h", None):   # (a closed engine has closed its session with it)
+                _capi.check(self._lib.pfnl_stream_close(s))
+
+    def __enter__(self) -> "VideoStream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _handle(self):
+        if not getattr(self, "_s", None):
+            raise RuntimeError("the stream is closed")
+        if not getattr(self._engine, "_h", None):   # the engine destroyed its handle, and the session with it
+            self._s = None
+            raise RuntimeError("the stream's engine has been closed")
+        return self._s
+
+    # ---- frames ----------------------------------------------------------------------------
+    def push(self, frame) -> List[tuple]:
+        """Hands one LR frame over and returns the SR frames of the batches launched BEFORE this push (possibly none).  A batch this
+        push launches is left running - its frames come with the next push or with ``end()`` - so the GPU works on it while the caller
+        fetches the next frame (``pop`` is there for a caller that wants them at once)."""
+        s = self._handle()
+        due = self.ready()
+        shape = (self.H, self.W, 3)
+        if type(frame).__module__.startswith("torch"):
+            import torch
+            if frame.dtype != torch.uint8 or tuple(frame.shape) != shape:
+                raise ValueError(f"expected a uint8 frame of shape {shape}, got {frame.dtype} {tuple(frame.shape)}")
+            if not frame.is_cuda or frame.device.index != self.device.index:
+                raise ValueError(f"tensor on {frame.device}, stream on {self.device} (host frames: numpy arrays)")
+            frame = frame.contiguous()
+            self._device_frames = True
+            _capi.check(self._lib.pfnl_stream_push(s, C.c_void_p(frame.data_ptr()), 1))
+        else:
+            frame = np.asarray(frame)
+            if frame.dtype != np.uint8 or frame.shape != shape:
+                raise ValueError(f"expected a uint8 frame of shape {shape}, got {frame.dtype} {frame.shape}")
+            frame = np.ascontiguousarray(frame)
+            self._device_frames = False
+            _capi.check(self._lib.pfnl_stream_push(s, frame.ctypes.data_as(C.c_void_p), 0))
+        return self.pop_ready(due)
+
+    def end(self) -> List[tuple]:
+        """No more frames: the remaining windows clamp at the last one.  Returns the remaining SR frames."""
+        _capi.check(self._lib.pfnl_stream_end(self._handle()))
+        return self.pop_ready()
+
+    def reset(self) -> None:
+        """The next sequence, same geometry; what was not popped is dropped."""
+        _capi.check(self._lib.pfnl_stream_reset(self._handle()))
+
+    def ready(self) -> int:
+        """SR frames that ``pop`` would deliver without another push."""
+        n = C.c_int(0)
+        _capi.check(self._lib.pfnl_stream_ready(self._handle(), C.byref(n)))
+        return n.value
+
+    def pop(self):
+        """The next SR frame as ``(index, frame)``, or None when none is deliverable; waits only for the batch that holds it."""
+        s = self._handle()
+        shape = (self.scale * self.H, self.scale * self.W, 3)
+        index, got = C.c_longlong(0), C.c_int(0)
+        if self._device_frames:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            _capi.check(self._lib.pfnl_stream_pop(s, C.c_void_p(out.data_ptr()), 1, C.byref(index), C.byref(got)))
+        else:
+            out = np.empty(shape, np.uint8)
+            _capi.check(self._lib.pfnl_stream_pop(s, out.ctypes.data_as(C.c_void_p), 0, C.byref(index), C.byref(got)))
+        return (index.value, out) if got.value else None
+
+    def pop_ready(self, limit=None) -> List[tuple]:
+        frames = []
+        for _ in range(self.ready() if limit is None else limit):
+            item = self.pop()
+            if item is None:
+                break
+            frames.append(item)
+        return frames
