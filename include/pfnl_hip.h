@@ -248,6 +248,23 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out /*[sH,sW,3]*/, int is_device, l
 int pfnl_stream_reset(pfnl_stream* s);
 int pfnl_stream_close(pfnl_stream* s);
 int pfnl_stream_next_batch(int T, int batch, long long pushed, int ended, long long launched, long long* first, int* count);
+/* SCENES (off by default; off, the session delivers what it always did).  A video has cuts, and a T-frame window across one mixes two
+ * unrelated scenes in the non-local block and in conv10_i.  With scenes on, each scene is a sequence of its own: window c, slot t = frame
+ * clamp(c + t - T/2, a, b), a = the first frame of c's scene, b = its last frame among those pushed - the rule of model/pfnl.py:238-242 with
+ * the scene's ends in the place of 0 and `last` (stated once, on the host: pfnl_amd/scene.py).  Batches, the ring and the bound do not change.
+ *   pfnl_stream_scenes: mode 0 off | 1 cuts marked by the caller | 2 marks and the detector: frame f >= 1 starts a scene when
+ *     min(sad[f], |sad[f] - sad[f-1]|) >= ceil(threshold * H * W), sad[f] = the sum over the pixels of |Y(f) - Y(f-1)|,
+ *     Y = (66 R + 129 G + 25 B + 128) >> 8, sad[0] = 0; threshold = a mean luma difference in (0, 255].  The second term keeps fast motion,
+ *     flicker and the frame behind a cut from firing.  Accepted only while no frame of the current sequence has been pushed (else
+ *     PFNL_ERR_STATE); the setting survives pfnl_stream_reset.  Modes 1 and 2 compute sad for every frame, on the device, in the ring,
+ *     without a host round trip: on the session's stream for device-pointer pushes, on the copy's for host-pointer ones.
+ *   pfnl_stream_mark_cut: the next pushed frame starts a scene.  PFNL_ERR_STATE in mode 0; before the first frame of a sequence it does
+ *     nothing (frame 0 starts scene 0 anyway); pfnl_stream_reset clears it.
+ *   pfnl_stream_pop_info: the first frame of the scene of the frame the last successful pop delivered, and that frame's sad (0, 0 in
+ *     mode 0); PFNL_ERR_STATE before any pop of the sequence.  Both travel with the batch, so this call waits for nothing. */
+int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold);
+int pfnl_stream_mark_cut(pfnl_stream* s);
+int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long long* sad);
 
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
@@ -509,6 +526,13 @@ int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream);
  * 4-byte aligned (16-byte for the 16-byte reads), win 16-byte aligned - else PFNL_ERR_INVALID. */
 int pfnl_op_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T, int H, int W,
                               void* stream);
+/* The session's scene kernels (pfnl_stream_scenes).  sad: a, b [H,W,3] uint8 (device) -> *out_dev (device) = sum |Y(a) - Y(b)|, exact; any
+ * H, W >= 1 and any alignment (16-byte reads where H*W*3 is a multiple of 16 and both pointers are aligned, else 4-byte or single-byte
+ * ones).  Synchronises `stream` (it owns a scratch word).  gather: pfnl_op_gather_windows_u8 with scene_first_dev [cap] int64 (device),
+ * slot f % cap = the first frame of frame f's scene; one scene gives pfnl_op_gather_windows_u8's windows. */
+int pfnl_op_scene_sad_u8(const uint8_t* a, const uint8_t* b, int H, int W, unsigned long long* out_dev, void* stream);
+int pfnl_op_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene_first_dev, float* win, int cap, long long last, long long first,
+                                     int count, int T, int H, int W, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

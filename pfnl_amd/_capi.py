@@ -104,6 +104,11 @@ SIGNATURES = {
     "pfnl_stream_reset": (_i, [_vp]),
     "pfnl_stream_close": (_i, [_vp]),
     "pfnl_stream_next_batch": (_i, [_i, _i, C.c_longlong, _i, C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(_i)]),
+    "pfnl_stream_scenes": (_i, [_vp, _i, C.c_double]),
+    "pfnl_stream_mark_cut": (_i, [_vp]),
+    "pfnl_stream_pop_info": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong)]),
+    "pfnl_op_scene_sad_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "pfnl_op_gather_windows_u8_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
     "pfnl_op_score_y": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pfnl_comm_get_unique_id": (_i, [_vp]),

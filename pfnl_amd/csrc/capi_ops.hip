@@ -890,6 +890,32 @@ int pfnl_op_gather_windows_u8(const uint8_t* ring, float* win, int cap, long lon
     return 0;
 }
 
+int pfnl_op_scene_sad_u8(const uint8_t* a, const uint8_t* b, int H, int W, unsigned long long* out_dev, void* stream) {
+    if (!a || !b || !out_dev) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "H and W must be positive");
+    if (reinterpret_cast<uintptr_t>(out_dev) % 8) return fail(PFNL_ERR_INVALID, "out_dev must be 8-byte aligned");
+    OpStage st(stream);
+    unsigned long long* scratch = st.alloc<unsigned long long>(2);
+    st.run([&] { return hipMemsetAsync(scratch, 0, 2 * sizeof(unsigned long long), st.s); });
+    st.run([&] { return pfnl::launch_scene_sad_u8(a, b, (size_t)H * W, scratch, pfnl::SceneDecision{out_dev, nullptr, 0, 0, 0, 0, 0, 0}, st.s); });
+    return st.finish("scene sad op: ");
+}
+
+int pfnl_op_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene_first_dev, float* win, int cap, long long last, long long first,
+                                     int count, int T, int H, int W, void* stream) {
+    if (!ring || !scene_first_dev || !win) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (cap < 1 || last < 0 || first < 0 || count < 1 || T < 1 || !(T & 1) || H < 1 || W < 1 || ((size_t)H * W * 3) % 4)
+        return fail(PFNL_ERR_INVALID, "bad window geometry (H*W*3 must be a multiple of 4, T odd, cap >= 1, first, last >= 0)");
+    if (first + count - 1 > last) return fail(PFNL_ERR_INVALID, "a window's centre frame lies beyond `last`");
+    if (reinterpret_cast<uintptr_t>(ring) % 4 || reinterpret_cast<uintptr_t>(win) % 16 || reinterpret_cast<uintptr_t>(scene_first_dev) % 8)
+        return fail(PFNL_ERR_INVALID, "ring must be 4-byte aligned, scene_first 8-byte and win 16-byte aligned");
+    // every frame the windows can name lies between the plain clamps, whatever the scenes: those must all be in the ring at once
+    const long long lo = first - T / 2 < 0 ? 0 : first - T / 2, hi = first + count - 1 + T / 2 > last ? last : first + count - 1 + T / 2;
+    if (hi - lo + 1 > cap) return fail(PFNL_ERR_INVALID, "the windows span more frames than the ring holds");
+    HIPCHK(pfnl::launch_gather_windows_u8_scenes(ring, scene_first_dev, win, cap, last, first, count, T, (size_t)H * W * 3, (hipStream_t)stream));
+    return 0;
+}
+
 int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream) {
     if (!sr || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (!n || n % 4) return fail(PFNL_ERR_INVALID, "element count must be a positive multiple of 4");

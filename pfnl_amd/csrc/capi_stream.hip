@@ -3,6 +3,7 @@
 // _run_sequence_on_device) - clamped windows, batching, quantisation, the range flag and the recomputation on the strict kernels - lives
 // here, behind pfnl_forward's own interface: the session calls pfnl_forward / pfnl_get_option / pfnl_set_option / pfnl_range_flag like
 // any other caller and knows nothing of the handle's layout (capi_internal.h, pfnl_handle_view).
+#include <cmath>
 #include <deque>
 #include <string>
 
@@ -40,6 +41,18 @@ struct pfnl_stream {
     std::deque<Batch> q;                              // launched, not yet fully delivered: at most two
     bool strict = false;                              // a batch was flagged: the rest of the sequence runs on the strict kernels
     std::string prior_strict, prior_precision;        // what the library held before go_strict changed it ("" = unchanged)
+    // scenes (pfnl_stream_scenes): allocated by the first call that turns them on; they have the ring's lifetime and its slots
+    int scene_mode = 0;                               // 0 off | 1 marks | 2 marks + detector
+    unsigned long long thr_sum = 0;                   // ceil(threshold H W): the detector compares sums
+    bool mark = false;                                // pfnl_stream_mark_cut: the next pushed frame starts a scene
+    long long* scene_first = nullptr;                 // [cap] the first frame of the scene of the frame in the slot | sad [cap] | scratch [2]
+    unsigned long long* sad = nullptr;                // (= scene_first + cap)
+    long long* info[2] = {nullptr, nullptr};          // pinned host copies of scene_first | sad, one per output slot: they travel with the batch
+    hipEvent_t scene_ev = nullptr;                    // the newest decision on the session's stream (device-pointer pushes)
+    bool decided_on_s = false;                        // ... that a decision on the copy stream has not yet been ordered behind
+    bool has_info = false;                            // what pfnl_stream_pop_info returns
+    long long info_first = 0;
+    unsigned long long info_sad = 0;
 };
 
 namespace {
@@ -53,7 +66,14 @@ int get_option(pfnl_stream* s, const char* key, std::string* v) {
 
 // gather -> forward -> quantise into the batch's slot, then its event; asynchronous on the session's stream
 int enqueue(pfnl_stream* s, const Batch& b) {
-    HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
+    if (s->scene_mode) {
+        // every frame up to b.last has been decided: on this stream, or on the copy stream before its push returned.  A replay
+        // (check_batch) reads the same entries: the push bound keeps a batch's slots until it has been delivered.
+        HIPCHK(pfnl::launch_gather_windows_u8_scenes(s->ring, s->scene_first, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
+        HIPCHK(hipMemcpyAsync(s->info[b.slot], s->scene_first, 2 * (size_t)s->cap * sizeof(long long), hipMemcpyDeviceToHost, s->s));
+    } else {
+        HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
+    }
     if (int e = pfnl_forward(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->s)) return e;
     HIPCHK(pfnl::launch_quantise_u8(s->sr, s->out[b.slot], (size_t)b.count * s->sr_bytes, s->s));
     HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
@@ -130,6 +150,21 @@ int check_batch(pfnl_stream* s, Batch& b) {
     return 0;
 }
 
+// frame s->pushed has been copied into its slot on `on`: its sum against the frame before it and its scene, behind the copy
+int decide_scene(pfnl_stream* s, hipStream_t on) {
+    const long long f = s->pushed;
+    const int slot = (int)(f % s->cap);
+    if (f == 0) {
+        HIPCHK(pfnl::launch_scene_first_frame(s->sad, s->scene_first, slot, on));
+        return 0;
+    }
+    const int prev = (int)((f - 1) % s->cap);
+    const pfnl::SceneDecision d{s->sad, s->scene_first, slot, prev, f, s->mark ? 1 : 0, s->scene_mode == 2 ? 1 : 0, s->thr_sum};
+    HIPCHK(pfnl::launch_scene_sad_u8(s->ring + (size_t)slot * s->lr_bytes, s->ring + (size_t)prev * s->lr_bytes, (size_t)s->H * s->W,
+                                     s->sad + s->cap, d, on));
+    return 0;
+}
+
 // forgets the sequence: nothing in flight afterwards, options as before the session changed them
 int drop_sequence(pfnl_stream* s) {
     int r = 0;
@@ -145,6 +180,7 @@ int drop_sequence(pfnl_stream* s) {
     s->slot_busy[0] = s->slot_busy[1] = false;
     s->pushed = s->launched = s->delivered = 0;
     s->ended = false;
+    s->mark = s->decided_on_s = s->has_info = false;
     if (int e = restore_options(s)) r = e;
     return r;
 }
@@ -154,6 +190,10 @@ void release(pfnl_stream* s) {
         if (s->out[i]) (void)hipFree(s->out[i]);
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
     }
+    for (int i = 0; i < 2; ++i)
+        if (s->info[i]) (void)hipHostFree(s->info[i]);
+    if (s->scene_first) (void)hipFree(s->scene_first);
+    if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
     if (s->ring) (void)hipFree(s->ring);
     if (s->win) (void)hipFree(s->win);
     if (s->sr) (void)hipFree(s->sr);
@@ -234,12 +274,28 @@ int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
     uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->lr_bytes;
     if (is_device) {
         HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
+        if (s->scene_mode) {                          // behind the copy, ahead of any gather that can name the frame
+            if (int e = decide_scene(s, s->s)) return e;
+            HIPCHK(hipEventRecord(s->scene_ev, s->s));
+            s->decided_on_s = true;
+        }
     } else {
         // the slot's previous frame belongs to batches that have been delivered, so nothing on the session's stream reads it; the copy
         // runs beside the batches in flight and the caller's buffer is free on return
+        // With scenes on, the frame's sum and decision go on the copy stream as well, so that they are complete when push returns: on
+        // the session's stream they could still be queued behind a long forward when the copy of frame f + cap - 1 overwrites the slot
+        // they have yet to read.  They read the frame before and its decision, and share the sum's scratch: where those came through
+        // device-pointer pushes they are on the session's stream, and the copy stream falls in behind them first.
+        if (s->scene_mode && s->decided_on_s) {
+            HIPCHK(hipStreamWaitEvent(s->cs, s->scene_ev, 0));
+            s->decided_on_s = false;
+        }
         HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
+        if (s->scene_mode)
+            if (int e = decide_scene(s, s->cs)) return e;
         HIPCHK(hipStreamSynchronize(s->cs));
     }
+    s->mark = false;
     ++s->pushed;
     return pump(s);
 }
@@ -275,6 +331,15 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
         HIPCHK(hipMemcpyAsync(out, src, s->sr_bytes, hipMemcpyDeviceToHost, s->cs));    // the batch has completed: no wait for a later one
         HIPCHK(hipStreamSynchronize(s->cs));
     }
+    if (s->scene_mode) {                              // (the copy is ahead of the batch's event, which check_batch has waited for)
+        const int slot = (int)(s->delivered % s->cap);
+        s->info_first = s->info[b.slot][slot];
+        s->info_sad = (unsigned long long)s->info[b.slot][s->cap + slot];
+    } else {
+        s->info_first = 0;
+        s->info_sad = 0;
+    }
+    s->has_info = true;
     *index = s->delivered++;
     *got = 1;
     if (s->delivered == b.first + b.count) {
@@ -283,6 +348,55 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
         if (int e = pump(s)) return e;
         if (s->ended && s->delivered == s->pushed) return restore_options(s);   // (every forward has completed: its batch was checked)
     }
+    return 0;
+}
+
+int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (mode < 0 || mode > 2) return fail(PFNL_ERR_INVALID, "scenes: mode 0 (off), 1 (marks) or 2 (marks and the detector)");
+    if (mode == 2 && !(threshold > 0.0 && threshold <= 255.0))
+        return fail(PFNL_ERR_INVALID, "scenes: the threshold is a mean luma difference in (0, 255]");
+    if (s->pushed) return fail(PFNL_ERR_STATE, "scenes are set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (mode && !s->scene_first) {
+        HIPCHK(hipSetDevice(s->device));
+        const size_t words = 2 * (size_t)s->cap + 2;  // scene_first | sad | the sum's scratch (zero between launches)
+        bool ok = hipMalloc(reinterpret_cast<void**>(&s->scene_first), words * sizeof(long long)) == hipSuccess;
+        ok = ok && hipMemset(s->scene_first, 0, words * sizeof(long long)) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&s->scene_ev, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; i < 2; ++i)
+            ok = ok && hipHostMalloc(reinterpret_cast<void**>(&s->info[i]), 2 * (size_t)s->cap * sizeof(long long), hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (int i = 0; i < 2; ++i) {
+                if (s->info[i]) (void)hipHostFree(s->info[i]);
+                s->info[i] = nullptr;
+            }
+            if (s->scene_first) (void)hipFree(s->scene_first);
+            if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
+            s->scene_first = nullptr;
+            s->scene_ev = nullptr;
+            return fail(PFNL_ERR_NOMEM, "scene table allocation failed");
+        }
+        s->sad = reinterpret_cast<unsigned long long*>(s->scene_first) + s->cap;
+    }
+    s->scene_mode = mode;
+    s->thr_sum = mode == 2 ? (unsigned long long)std::ceil(threshold * s->H * s->W) : 0;
+    s->mark = false;
+    return 0;
+}
+
+int pfnl_stream_mark_cut(pfnl_stream* s) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!s->scene_mode) return fail(PFNL_ERR_STATE, "mark_cut: scenes are off (pfnl_stream_scenes)");
+    if (s->pushed) s->mark = true;                    // (frame 0 starts scene 0 and is no cut)
+    return 0;
+}
+
+int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long long* sad) {
+    if (!s || !scene_first || !sad) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!s->has_info) return fail(PFNL_ERR_STATE, "pop_info: no frame of this sequence has been popped");
+    *scene_first = s->info_first;
+    *sad = s->info_sad;
     return 0;
 }
 

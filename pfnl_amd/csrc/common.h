@@ -159,6 +159,22 @@ hipError_t launch_quantise_u8(const float* sr, uint8_t* out, size_t n, hipStream
 // window w slot t = frame clamp(first + w + t - T/2, 0, last); frame_bytes % 4 == 0 (stream.hip)
 hipError_t launch_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T,
                                     size_t frame_bytes, hipStream_t s);
+// ---- scenes of the streaming session (stream.hip; the rule: pfnl_amd/scene.py) ----
+// What the block that completes a frame's sum of absolute luma differences does with it: sad[slot] = the sum and, where scene_first is
+// given, scene_first[slot] = (force || (detect && min(sum, |sum - sad[prev]|) >= thr_sum)) ? frame : scene_first[prev].
+struct SceneDecision {
+    unsigned long long* sad;       // [cap]
+    long long* scene_first;        // [cap], or null: the sum alone
+    int slot, prev;                // frame % cap, (frame - 1) % cap
+    long long frame;
+    int force, detect;
+    unsigned long long thr_sum;
+};
+hipError_t launch_scene_sad_u8(const uint8_t* a, const uint8_t* b, size_t npix, unsigned long long* scratch, const SceneDecision& d,
+                               hipStream_t s);
+hipError_t launch_scene_first_frame(unsigned long long* sad, long long* scene_first, int slot, hipStream_t s);
+hipError_t launch_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene_first, float* win, int cap, long long last,
+                                           long long first, int count, int T, size_t frame_bytes, hipStream_t s);
 
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;

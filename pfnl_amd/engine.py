@@ -229,11 +229,12 @@ class PFNLEngine:
         _capi.check(self._lib.pfnl_forward_strip(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), B, H, W,
                                                  int(row0), int(nrows), C.c_void_p(stream) if stream else None))
 
-    def open_stream(self, H: int, W: int, batch: int = 1):
+    def open_stream(self, H: int, W: int, batch: int = 1, scene_cut=None):
         """A streaming session on this engine (pfnl_stream_open; pfnl_amd/stream.py VideoStream): uint8 LR frames [H,W,3] pushed one at
-        a time, uint8 SR frames popped in order, ``batch`` windows per forward.  One open session per engine."""
+        a time, uint8 SR frames popped in order, ``batch`` windows per forward.  One open session per engine.  ``scene_cut``: None,
+        "manual" or a detector threshold - windows that stay inside a scene (VideoStream)."""
         from .stream import VideoStream
-        return VideoStream(self, H, W, batch)
+        return VideoStream(self, H, W, batch, scene_cut)
 
     def sync(self) -> None:
         """Synchronise the engine's streams; raises if a device-pointer forward left the f16-pipe kernels' range

@@ -441,6 +441,41 @@ def gather_windows_u8(ring, last: int, first: int, count: int, num_frames: int):
     return out
 
 
+def gather_windows_u8_scenes(ring, scene_first, last: int, first: int, count: int, num_frames: int):
+    """gather_windows_u8 with the windows kept inside the centre's scene: scene_first [cap] int64 (cuda), slot f % cap = the first frame
+    of frame f's scene (pfnl_op_gather_windows_u8_scenes; the rule: pfnl_amd/scene.py scene_windows_index)."""
+    import torch
+    lib = _capi.load_library()
+    if not (isinstance(ring, torch.Tensor) and ring.is_cuda and ring.dtype == torch.uint8 and ring.is_contiguous()):
+        raise TypeError("ring must be a contiguous uint8 tensor on the GPU")
+    cap, H, W, c = ring.shape
+    if c != 3:
+        raise ValueError("gather_windows_u8_scenes expects [cap,H,W,3]")
+    if not (isinstance(scene_first, torch.Tensor) and scene_first.device == ring.device and scene_first.dtype == torch.int64
+            and scene_first.is_contiguous() and tuple(scene_first.shape) == (cap,)):
+        raise TypeError("scene_first must be a contiguous int64 tensor [cap] on the ring's device")
+    out = torch.empty((count, num_frames, H, W, 3), dtype=torch.float32, device=ring.device)
+    _capi.check(lib.pfnl_op_gather_windows_u8_scenes(C.c_void_p(ring.data_ptr()), C.c_void_p(scene_first.data_ptr()), _req(out, "out"), cap,
+                                                     int(last), int(first), count, num_frames, H, W, _stream(ring)))
+    return out
+
+
+def scene_sad_u8(a, b) -> int:
+    """sum |Y(a) - Y(b)| of two [H,W,3] uint8 frames (cuda), Y = (66 R + 129 G + 25 B + 128) >> 8, as a Python int: the streaming session's
+    scene score (pfnl_op_scene_sad_u8; exact: pfnl_amd/scene.py frame_sad).  Synchronises."""
+    import torch
+    lib = _capi.load_library()
+    for t, name in ((a, "a"), (b, "b")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise TypeError(f"{name} must be a contiguous uint8 tensor on the GPU")
+    if a.dim() != 3 or a.shape[2] != 3 or b.shape != a.shape or b.device != a.device:
+        raise ValueError("scene_sad_u8 expects two [H,W,3] frames on one device")
+    out = torch.zeros((1,), dtype=torch.int64, device=a.device)
+    _capi.check(lib.pfnl_op_scene_sad_u8(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), a.shape[0], a.shape[1],
+                                         C.c_void_p(out.data_ptr()), _stream(a)))
+    return int(out.item())
+
+
 def quantise_u8(sr):
     """uint8(np.round(np.clip(sr * 255, 0, 255))) on the device (reference model/pfnl.py:254-257)."""
     import torch

@@ -10,6 +10,10 @@ library.  Nothing here computes::
                 sink(index, sr)                    # [sH,sW,3] uint8
         for index, sr in vs.end():
             sink(index, sr)
+
+Scenes (off by default): ``open_stream(H, W, batch, scene_cut=10.0)`` runs the cut detector of pfnl_amd/scene.py on the device ring, and
+``scene_cut="manual"`` takes the cuts from the caller (``vs.mark_cut()`` before the push of a scene's first frame); the windows of a frame
+then stay inside its scene, and ``vs.cuts`` lists the delivered frames that started one.
 """
 from __future__ import annotations
 
@@ -35,9 +39,12 @@ class VideoStream:
 
     ``push(frame)`` takes a [H,W,3] uint8 numpy array or a uint8 torch tensor on the engine's device and returns the SR frames that
     have become deliverable as a list of ``(index, frame)`` - numpy in, numpy out; device tensor in, device tensors out.  Device
-    tensors are read and written on the stream that was torch's current stream when the session was opened."""
+    tensors are read and written on the stream that was torch's current stream when the session was opened.
 
-    def __init__(self, engine, H: int, W: int, batch: int = 1):
+    ``scene_cut``: None - one scene, the reference's windows; ``"manual"`` - scenes begin where ``mark_cut()`` says; a float - a mean
+    luma difference in (0, 255] for the detector (pfnl_amd/scene.py cut_rule), marks included."""
+
+    def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None):
         import torch
         if not engine._ready:
             raise RuntimeError("weights have not been loaded")
@@ -51,6 +58,20 @@ class VideoStream:
         _capi.check(self._lib.pfnl_stream_open(engine._h, self.H, self.W, self.batch, C.c_void_p(stream) if stream else None, C.byref(s)))
         self._s = s
         self._device_frames = False                 # the container of the last pushed frame decides that of the popped ones
+        self.scene_cut = scene_cut
+        self.cuts: List[int] = []                   # delivered frames > 0 that start a scene
+        self.last_info = None                       # (scene_first, sad) of the frame the last pop delivered
+        if scene_cut is not None:
+            try:
+                if isinstance(scene_cut, str):
+                    if scene_cut != "manual":
+                        raise ValueError(f'scene_cut: None, "manual" or a threshold in (0, 255], got {scene_cut!r}')
+                    _capi.check(self._lib.pfnl_stream_scenes(s, 1, 0.0))
+                else:
+                    _capi.check(self._lib.pfnl_stream_scenes(s, 2, float(scene_cut)))
+            except Exception:
+                self.close()
+                raise
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -112,8 +133,14 @@ class VideoStream:
         return self.pop_ready()
 
     def reset(self) -> None:
-        """The next sequence, same geometry; what was not popped is dropped."""
+        """The next sequence, same geometry and scene setting; what was not popped is dropped, and so are a pending mark and ``cuts``."""
         _capi.check(self._lib.pfnl_stream_reset(self._handle()))
+        self.cuts = []
+        self.last_info = None
+
+    def mark_cut(self) -> None:
+        """The next pushed frame starts a scene (needs ``scene_cut``; before the first frame of a sequence it changes nothing)."""
+        _capi.check(self._lib.pfnl_stream_mark_cut(self._handle()))
 
     def ready(self) -> int:
         """SR frames that ``pop`` would deliver without another push."""
@@ -133,7 +160,17 @@ class VideoStream:
         else:
             out = np.empty(shape, np.uint8)
             _capi.check(self._lib.pfnl_stream_pop(s, out.ctypes.data_as(C.c_void_p), 0, C.byref(index), C.byref(got)))
-        return (index.value, out) if got.value else None
+        if not got.value:
+            return None
+        if self.scene_cut is not None:
+            first, sad = C.c_longlong(0), C.c_ulonglong(0)
+            _capi.check(self._lib.pfnl_stream_pop_info(s, C.byref(first), C.byref(sad)))
+            self.last_info = (first.value, sad.value)
+            if index.value > 0 and first.value == index.value:
+                self.cuts.append(index.value)
+        else:
+            self.last_info = (0, 0)
+        return index.value, out
 
     def pop_ready(self, limit=None) -> List[tuple]:
         frames = []
