@@ -265,6 +265,24 @@ int pfnl_stream_next_batch(int T, int batch, long long pushed, int ended, long l
 int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold);
 int pfnl_stream_mark_cut(pfnl_stream* s);
 int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long long* sad);
+/* YUV 4:2:0 (RGB24 by default; then the session is what it always was).  Decoders deliver NV12 or I420 and encoders take them back; with a
+ * format set the session converts at its two edges, on the device, and everything between them - the ring, the scene sums, the windows, a
+ * replay behind the range fence - goes on seeing RGB bytes.  The arithmetic is integer and stated once on the host, pfnl_amd/yuv.py:
+ *   frames are tightly packed, H * W * 3 / 2 bytes: NV12 = Y [H][W], CbCr [H/2][W/2][2]; I420 = Y [H][W], Cb [H/2][W/2], Cr [H/2][W/2];
+ *   coefficients of BT.601 or BT.709, limited (16..235 / 16..240) or full range, with 14 fractional bits, each rounded once
+ *     (pfnl_yuv_coefficients: y0, then yr yg yb cbr cbg cbb crr crg crb, then dy drv dgu dgv dbu);
+ *   chroma sited left (H.264 / HEVC type 0): in: 3 : 1 between the near and the far chroma row, 1 : 1 between two samples on odd columns,
+ *     indices clamped; out: 1-2-1 over the two luma rows of the unrounded numerators, columns clamped, one rounding.
+ *   pfnl_stream_format: in_fmt for push (H*W*3/2 bytes, converted into the frame's ring slot: a device pointer on the session's stream, a
+ *     host pointer through a staging buffer on the copy's, before push returns), out_fmt for pop (sH*sW*3/2 bytes = the conversion of the
+ *     RGB frame it would have delivered, made per batch behind the quantisation, recomputed batches included).  The two are independent;
+ *     (RGB24, RGB24) is the default again.  Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE);
+ *     the setting survives pfnl_stream_reset.  Allocates its staging on first use (PFNL_ERR_NOMEM); pfnl_stream_close frees it.
+ * Out of scope: pitched or padded planes, 10-bit formats (P010), 4:2:2 and 4:4:4, other sitings, transfer functions, BT.2020. */
+enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2 };
+enum { PFNL_MATRIX_BT601 = 0, PFNL_MATRIX_BT709 = 1 };
+int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range);
+int pfnl_yuv_coefficients(int matrix, int full_range, int32_t out[15]);    /* y0, 9 encode, 5 decode; no device needed */
 
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
@@ -533,6 +551,12 @@ int pfnl_op_gather_windows_u8(const uint8_t* ring, float* win, int cap, long lon
 int pfnl_op_scene_sad_u8(const uint8_t* a, const uint8_t* b, int H, int W, unsigned long long* out_dev, void* stream);
 int pfnl_op_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene_first_dev, float* win, int cap, long long last, long long first,
                                      int count, int T, int H, int W, void* stream);
+/* The session's format kernels (pfnl_stream_format; the rule: pfnl_amd/yuv.py).  yuv [n][H*W*3/2] uint8 in fmt PFNL_PIX_NV12 or
+ * PFNL_PIX_I420 <-> rgb [n][H][W][3] uint8, device pointers, asynchronous on stream.  H and W even; any alignment (16-byte words where
+ * W is a multiple of 16 and both pointers are aligned, 4-byte words for multiples of 4, else single bytes).  NULL, odd or non-positive
+ * H / W, n < 1, an unknown fmt / matrix / full_range and fmt = PFNL_PIX_RGB24: PFNL_ERR_INVALID before any HIP call. */
+int pfnl_op_yuv420_to_rgb_u8(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, void* stream);
+int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

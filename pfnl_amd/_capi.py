@@ -107,6 +107,10 @@ SIGNATURES = {
     "pfnl_stream_scenes": (_i, [_vp, _i, C.c_double]),
     "pfnl_stream_mark_cut": (_i, [_vp]),
     "pfnl_stream_pop_info": (_i, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong)]),
+    "pfnl_stream_format": (_i, [_vp, _i, _i, _i, _i]),
+    "pfnl_yuv_coefficients": (_i, [_i, _i, C.POINTER(C.c_int32)]),
+    "pfnl_op_yuv420_to_rgb_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_op_rgb_to_yuv420_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_op_scene_sad_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pfnl_op_gather_windows_u8_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
@@ -123,6 +127,8 @@ SIGNATURES = {
     "pfnl_comm_barrier": (_i, [_vp]),
     "pfnl_comm_allgather": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
 }
+PIXEL_FORMATS = {"rgb24": 0, "nv12": 1, "i420": 2}        # PFNL_PIX_*
+YUV_MATRICES = {"bt601": 0, "bt709": 1}                    # PFNL_MATRIX_*
 COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX = 0, 1
 

@@ -923,6 +923,38 @@ int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream) {
     return 0;
 }
 
+int pfnl_yuv_coefficients(int matrix, int full_range, int32_t out[15]) {
+    if (!out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    pfnl::YuvCoef c;
+    if (!pfnl::yuv_coefficients(matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    const int v[15] = {c.y0, c.yr, c.yg, c.yb, c.cbr, c.cbg, c.cbb, c.crr, c.crg, c.crb, c.dy, c.drv, c.dgu, c.dgv, c.dbu};
+    for (int k = 0; k < 15; ++k) out[k] = v[k];
+    return 0;
+}
+
+// as below: refused before any HIP call; *c = the table of (matrix, full_range)
+static int yuv_op_refused(const void* a, const void* b, int fmt, int matrix, int full_range, int n, int H, int W, pfnl::YuvCoef* c) {
+    if (!a || !b) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (fmt != PFNL_PIX_NV12 && fmt != PFNL_PIX_I420) return fail(PFNL_ERR_INVALID, "yuv: fmt must be PFNL_PIX_NV12 or PFNL_PIX_I420");
+    if (!pfnl::yuv_coefficients(matrix, full_range, c)) return fail(PFNL_ERR_INVALID, "yuv: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (n < 1 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "yuv: n >= 1, H and W positive and even (4:2:0)");
+    return 0;
+}
+
+int pfnl_op_yuv420_to_rgb_u8(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = yuv_op_refused(yuv, rgb, fmt, matrix, full_range, n, H, W, &c)) return r;
+    HIPCHK(pfnl::launch_yuv420_to_rgb_u8(yuv, rgb, fmt == PFNL_PIX_NV12, c, n, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = yuv_op_refused(rgb, yuv, fmt, matrix, full_range, n, H, W, &c)) return r;
+    HIPCHK(pfnl::launch_rgb_to_yuv420_u8(rgb, yuv, fmt == PFNL_PIX_NV12, c, n, H, W, (hipStream_t)stream));
+    return 0;
+}
+
 // every refusal comes before any HIP call: the argument checks work without a device
 static int score_geometry_refused(int F, int H, int W) {
     if (F < 1 || F > 65535) return fail(PFNL_ERR_INVALID, "score: F must be in 1 .. 65535");

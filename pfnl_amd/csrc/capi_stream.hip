@@ -53,6 +53,12 @@ struct pfnl_stream {
     bool has_info = false;                            // what pfnl_stream_pop_info returns
     long long info_first = 0;
     unsigned long long info_sad = 0;
+    // formats (pfnl_stream_format): the ring and out[] stay RGB; a YUV frame is converted on its way into its ring slot, a batch's SR
+    // frames behind their quantisation into yout[] - allocated by the first call that needs them, freed with the session
+    int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
+    pfnl::YuvCoef coef{};
+    uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel
+    uint8_t* yout[2] = {nullptr, nullptr};            // [batch][sH*sW*3/2] each, beside out[]
 };
 
 namespace {
@@ -76,6 +82,9 @@ int enqueue(pfnl_stream* s, const Batch& b) {
     }
     if (int e = pfnl_forward(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->s)) return e;
     HIPCHK(pfnl::launch_quantise_u8(s->sr, s->out[b.slot], (size_t)b.count * s->sr_bytes, s->s));
+    if (s->out_fmt != PFNL_PIX_RGB24)                 // (a replay takes the same route: pop stays a copy)
+        HIPCHK(pfnl::launch_rgb_to_yuv420_u8(s->out[b.slot], s->yout[b.slot], s->out_fmt == PFNL_PIX_NV12, s->coef, b.count, s->scale * s->H,
+                                             s->scale * s->W, s->s));
     HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
     return 0;
 }
@@ -188,12 +197,14 @@ int drop_sequence(pfnl_stream* s) {
 void release(pfnl_stream* s) {
     for (int i = 0; i < 2; ++i) {
         if (s->out[i]) (void)hipFree(s->out[i]);
+        if (s->yout[i]) (void)hipFree(s->yout[i]);
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
     }
     for (int i = 0; i < 2; ++i)
         if (s->info[i]) (void)hipHostFree(s->info[i]);
     if (s->scene_first) (void)hipFree(s->scene_first);
     if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
+    if (s->yin) (void)hipFree(s->yin);
     if (s->ring) (void)hipFree(s->ring);
     if (s->win) (void)hipFree(s->win);
     if (s->sr) (void)hipFree(s->sr);
@@ -272,8 +283,12 @@ int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
         return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
     HIPCHK(hipSetDevice(s->device));
     uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->lr_bytes;
+    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24;  // the frame is H*W*3/2 bytes and reaches its slot through the kernel, as RGB
     if (is_device) {
-        HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
+        if (yuv_in)
+            HIPCHK(pfnl::launch_yuv420_to_rgb_u8(frame, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->s));
+        else
+            HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
         if (s->scene_mode) {                          // behind the copy, ahead of any gather that can name the frame
             if (int e = decide_scene(s, s->s)) return e;
             HIPCHK(hipEventRecord(s->scene_ev, s->s));
@@ -290,7 +305,12 @@ int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
             HIPCHK(hipStreamWaitEvent(s->cs, s->scene_ev, 0));
             s->decided_on_s = false;
         }
-        HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
+        if (yuv_in) {                                 // (the staging frame is free again: every push ends with the copy stream idle)
+            HIPCHK(hipMemcpyAsync(s->yin, frame, s->lr_bytes / 2, hipMemcpyHostToDevice, s->cs));
+            HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->cs));
+        } else {
+            HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
+        }
         if (s->scene_mode)
             if (int e = decide_scene(s, s->cs)) return e;
         HIPCHK(hipStreamSynchronize(s->cs));
@@ -324,11 +344,13 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
     Batch& b = s->q.front();
     if (!b.checked)
         if (int e = check_batch(s, b)) return e;
-    const uint8_t* const src = s->out[b.slot] + (size_t)(s->delivered - b.first) * s->sr_bytes;
+    const bool yuv_out = s->out_fmt != PFNL_PIX_RGB24;
+    const size_t bytes = yuv_out ? s->sr_bytes / 2 : s->sr_bytes;
+    const uint8_t* const src = (yuv_out ? s->yout[b.slot] : s->out[b.slot]) + (size_t)(s->delivered - b.first) * bytes;
     if (is_device) {
-        HIPCHK(hipMemcpyAsync(out, src, s->sr_bytes, hipMemcpyDeviceToDevice, s->s));   // ordered like the caller's own work on that stream
+        HIPCHK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, s->s));   // ordered like the caller's own work on that stream
     } else {
-        HIPCHK(hipMemcpyAsync(out, src, s->sr_bytes, hipMemcpyDeviceToHost, s->cs));    // the batch has completed: no wait for a later one
+        HIPCHK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, s->cs));    // the batch has completed: no wait for a later one
         HIPCHK(hipStreamSynchronize(s->cs));
     }
     if (s->scene_mode) {                              // (the copy is ahead of the batch's event, which check_batch has waited for)
@@ -382,6 +404,38 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
     s->scene_mode = mode;
     s->thr_sum = mode == 2 ? (unsigned long long)std::ceil(threshold * s->H * s->W) : 0;
     s->mark = false;
+    return 0;
+}
+
+int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || out_fmt < PFNL_PIX_RGB24 || out_fmt > PFNL_PIX_I420)
+        return fail(PFNL_ERR_INVALID, "format: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420");
+    pfnl::YuvCoef coef;
+    if (!pfnl::yuv_coefficients(matrix, full_range, &coef))
+        return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    const bool need_in = in_fmt != PFNL_PIX_RGB24 && !s->yin, need_out = out_fmt != PFNL_PIX_RGB24 && !s->yout[0];
+    if (need_in || need_out) {
+        HIPCHK(hipSetDevice(s->device));
+        bool ok = true;
+        if (need_in) ok = hipMalloc(reinterpret_cast<void**>(&s->yin), s->lr_bytes / 2) == hipSuccess;
+        if (need_out)
+            for (int i = 0; i < 2; ++i)
+                ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout[i]), (size_t)s->batch * (s->sr_bytes / 2)) == hipSuccess;
+        if (!ok) {                                    // nothing half allocated stays behind, and the setting is unchanged
+            (void)hipGetLastError();
+            if (need_in && s->yin) (void)hipFree(s->yin), s->yin = nullptr;
+            for (int i = 0; need_out && i < 2; ++i) {
+                if (s->yout[i]) (void)hipFree(s->yout[i]);
+                s->yout[i] = nullptr;
+            }
+            return fail(PFNL_ERR_NOMEM, "format staging allocation failed");
+        }
+    }
+    s->in_fmt = in_fmt;
+    s->out_fmt = out_fmt;
+    s->coef = coef;
     return 0;
 }
 

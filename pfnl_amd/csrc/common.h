@@ -176,6 +176,18 @@ hipError_t launch_scene_first_frame(unsigned long long* sad, long long* scene_fi
 hipError_t launch_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene_first, float* win, int cap, long long last,
                                            long long first, int count, int T, size_t frame_bytes, hipStream_t s);
 
+// ---- YUV 4:2:0 <-> RGB, 8 bits (yuv.hip; the rule: pfnl_amd/yuv.py) ----
+// The fifteen integers of yuv.py coefficients(), 14 fractional bits: the one table, computed on the host and passed to the kernels by value.
+struct YuvCoef {
+    int y0;
+    int yr, yg, yb, cbr, cbg, cbb, crr, crg, crb;   // RGB -> YUV
+    int dy, drv, dgu, dgv, dbu;                     // YUV -> RGB
+};
+bool yuv_coefficients(int matrix, int full_range, YuvCoef* c);   // matrix 0 BT.601 | 1 BT.709; false: unknown matrix or range (no device needed)
+// yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow)
+hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;
 // partial: score_scratch_bytes(F, H, W) of device memory (one slot per workgroup: the sums are repeatable bit for bit)

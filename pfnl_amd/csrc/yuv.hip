@@ -1,0 +1,296 @@
+// YUV 4:2:0 (NV12, I420) <-> packed RGB, 8 bits: the two edges of the streaming session (include/pfnl_hip.h, pfnl_stream_format).  The
+// arithmetic is integer and stated once on the host, pfnl_amd/yuv.py: 14 fractional bits, coefficients rounded once, chroma sited left
+// (on the even luma columns, midway between two luma rows); the kernels give its bytes.
+// Both kernels move bytes - 1.5 per pixel on one side, 3 on the other.  A lane owns a strip of two luma rows by P pixels, so that the chroma
+// samples it reads (or forms) serve both rows; P = 16 reads and writes 16-byte words (8-byte ones for I420's half-width planes), P = 4
+// 4-byte words (2-byte ones), P = 2 single bytes: any even H, W and any pointer.  Edges are index clamps inside the one kernel.
+#include <cmath>
+
+#include "common.h"
+
+namespace pfnl {
+
+bool yuv_coefficients(int matrix, int full_range, YuvCoef* c) {
+    if (!c || matrix < 0 || matrix > 1 || full_range < 0 || full_range > 1) return false;
+    const double kr = matrix == 0 ? 0.299 : 0.2126, kb = matrix == 0 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
+    const double ys = full_range ? 1.0 : 219.0 / 255.0, cs = full_range ? 1.0 : 224.0 / 255.0;
+    const auto rnd = [](double x) { return (int)std::floor(x * 16384.0 + 0.5); };
+    c->y0 = full_range ? 0 : 16;
+    c->yr = rnd(ys * kr);
+    c->yb = rnd(ys * kb);
+    c->yg = rnd(ys) - c->yr - c->yb;
+    c->cbr = rnd(-cs * kr / (2.0 * (1.0 - kb)));
+    c->cbb = rnd(cs / 2.0);
+    c->cbg = -c->cbr - c->cbb;
+    c->crr = rnd(cs / 2.0);
+    c->crb = rnd(-cs * kb / (2.0 * (1.0 - kr)));
+    c->crg = -c->crr - c->crb;
+    c->dy = rnd(1.0 / ys);
+    c->drv = rnd(2.0 * (1.0 - kr) / cs);
+    c->dbu = rnd(2.0 * (1.0 - kb) / cs);
+    c->dgu = rnd(-2.0 * kb * (1.0 - kb) / (kg * cs));
+    c->dgv = rnd(-2.0 * kr * (1.0 - kr) / (kg * cs));
+    return true;
+}
+
+namespace {
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// the widest word that divides N bytes: the strips are laid out so that a run of N bytes is aligned to it in the forms that use words
+template <int N>
+constexpr int word_of() {
+    return N % 16 == 0 ? 16 : (N % 8 == 0 ? 8 : (N % 4 == 0 ? 4 : (N % 2 == 0 ? 2 : 1)));
+}
+
+// N bytes at p -> v[0 .. N), in words (WORDS) or byte by byte
+template <int N, bool WORDS>
+__device__ __forceinline__ void load_bytes(const uint8_t* __restrict__ p, int* v) {
+    constexpr int WB = WORDS ? word_of<N>() : 1;
+    if constexpr (WB == 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = p[k];
+    } else if constexpr (WB == 2) {
+#pragma unroll
+        for (int k = 0; k < N; k += 2) {
+            const unsigned w = *reinterpret_cast<const uint16_t*>(p + k);
+            v[k] = (int)(w & 255u), v[k + 1] = (int)(w >> 8);
+        }
+    } else {
+        unsigned w[N / 4];
+#pragma unroll
+        for (int k = 0; k < N; k += WB) {
+            if constexpr (WB == 16) {
+                const u32x4 q = *reinterpret_cast<const u32x4*>(p + k);
+                w[k / 4] = q.x, w[k / 4 + 1] = q.y, w[k / 4 + 2] = q.z, w[k / 4 + 3] = q.w;
+            } else if constexpr (WB == 8) {
+                const u32x2 q = *reinterpret_cast<const u32x2*>(p + k);
+                w[k / 4] = q.x, w[k / 4 + 1] = q.y;
+            } else {
+                w[k / 4] = *reinterpret_cast<const unsigned*>(p + k);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
+    }
+}
+
+// v[0 .. N), each in [0, 255] -> N bytes at p
+template <int N, bool WORDS>
+__device__ __forceinline__ void store_bytes(uint8_t* __restrict__ p, const int* v) {
+    constexpr int WB = WORDS ? word_of<N>() : 1;
+    if constexpr (WB == 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) p[k] = (uint8_t)v[k];
+    } else if constexpr (WB == 2) {
+#pragma unroll
+        for (int k = 0; k < N; k += 2) *reinterpret_cast<uint16_t*>(p + k) = (uint16_t)(v[k] | (v[k + 1] << 8));
+    } else {
+        unsigned w[N / 4];
+#pragma unroll
+        for (int k = 0; k < N / 4; ++k)
+            w[k] = (unsigned)v[4 * k] | ((unsigned)v[4 * k + 1] << 8) | ((unsigned)v[4 * k + 2] << 16) | ((unsigned)v[4 * k + 3] << 24);
+#pragma unroll
+        for (int k = 0; k < N; k += WB) {
+            if constexpr (WB == 16)
+                *reinterpret_cast<u32x4*>(p + k) = u32x4{w[k / 4], w[k / 4 + 1], w[k / 4 + 2], w[k / 4 + 3]};
+            else if constexpr (WB == 8)
+                *reinterpret_cast<u32x2*>(p + k) = u32x2{w[k / 4], w[k / 4 + 1]};
+            else
+                *reinterpret_cast<unsigned*>(p + k) = w[k / 4];
+        }
+    }
+}
+
+// clip(v >> S, 0, 255) with the clamp AHEAD of the shift (the same value: both are monotonic).  Written as shift-then-clamp, two results
+// that are packed into neighbouring bytes become one v_ashr_pk_u8_i32 (new on gfx950), which the compiler ORs with bytes 2 and 3 as if
+// the instruction left the upper half of its result zero.  With that code the 4-pixel NV12 decode delivered wrong bytes 2 of its packed
+// words on the device (values no input can produce) and right ones in a host build of the same source: tools/GFX950_NOTES.md.
+template <int S>
+__device__ __forceinline__ int shift_clip_u8(int v) {
+    v = v < 0 ? 0 : v;
+    v = v > (256 << S) - 1 ? (256 << S) - 1 : v;
+    return v >> S;
+}
+
+}  // namespace
+
+// yuv [n][H*W*3/2] -> rgb [n][H][W][3].  Strip k of 0 .. H/2 is the luma rows 2k - 1 and 2k: exactly the two rows that lie between the
+// chroma rows k - 1 and k, each three quarters its near row and one quarter the other (yuv.py upsample); row -1 and row H do not exist,
+// and there the missing chroma row clamps onto the present one.  Per row and plane a lane reads P/2 samples and the one to their right.
+template <int P, bool NV12>
+__global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __restrict__ yuv, uint8_t* __restrict__ rgb, int n, int H,
+                                                               int W, YuvCoef c) {
+    constexpr bool WORDS = P > 2;
+    constexpr int HP = P / 2;
+    const int gw = W / P, strips = H / 2 + 1, hh = H >> 1, hw = W >> 1;
+    const size_t plane = (size_t)H * W, total = (size_t)n * strips * gw;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const int g = (int)(t % gw);
+        const size_t fk = t / gw;
+        const int k = (int)(fk % strips);
+        const size_t f = fk / strips;
+        const uint8_t* const fr = yuv + f * (plane + plane / 2);
+        const int x0 = g * P, i0 = x0 >> 1;
+        const int ie = i0 + HP < hw ? i0 + HP : hw - 1;
+        const int jrow[2] = {k > 0 ? k - 1 : 0, k < hh ? k : hh - 1};
+        int cb[2][HP + 1], cr[2][HP + 1];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            if constexpr (NV12) {
+                const uint8_t* const p = fr + plane + (size_t)jrow[a] * W;
+                int pair[P], e[2];
+                load_bytes<P, WORDS>(p + x0, pair);
+                load_bytes<2, WORDS>(p + 2 * ie, e);
+#pragma unroll
+                for (int q = 0; q < HP; ++q) cb[a][q] = pair[2 * q], cr[a][q] = pair[2 * q + 1];
+                cb[a][HP] = e[0], cr[a][HP] = e[1];
+            } else {
+                const uint8_t* const pb = fr + plane + (size_t)jrow[a] * hw;
+                const uint8_t* const pr = pb + (size_t)hh * hw;
+                load_bytes<HP, WORDS>(pb + i0, cb[a]);
+                load_bytes<HP, WORDS>(pr + i0, cr[a]);
+                cb[a][HP] = pb[ie], cr[a][HP] = pr[ie];
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {                                  // a = 0: row 2k - 1, near chroma row k - 1; a = 1: row 2k, near row k
+            const int y = 2 * k - 1 + a;
+            if (y < 0 || y >= H) continue;
+            int luma[P], out[3 * P];
+            load_bytes<P, WORDS>(fr + (size_t)y * W + x0, luma);
+#pragma unroll
+            for (int px = 0; px < P; ++px) {
+                const int q = px >> 1;
+                int u, v;
+                if (px & 1) {
+                    u = (3 * cb[a][q] + cb[1 - a][q] + 3 * cb[a][q + 1] + cb[1 - a][q + 1] + 4) >> 3;
+                    v = (3 * cr[a][q] + cr[1 - a][q] + 3 * cr[a][q + 1] + cr[1 - a][q + 1] + 4) >> 3;
+                } else {
+                    u = (6 * cb[a][q] + 2 * cb[1 - a][q] + 4) >> 3;
+                    v = (6 * cr[a][q] + 2 * cr[1 - a][q] + 4) >> 3;
+                }
+                u -= 128, v -= 128;
+                const int yy = c.dy * (luma[px] - c.y0) + (1 << 13);
+                out[3 * px] = shift_clip_u8<14>(yy + c.drv * v);
+                out[3 * px + 1] = shift_clip_u8<14>(yy + c.dgu * u + c.dgv * v);
+                out[3 * px + 2] = shift_clip_u8<14>(yy + c.dbu * u);
+            }
+            store_bytes<3 * P, WORDS>(rgb + ((f * H + y) * W + x0) * 3, out);
+        }
+    }
+}
+
+// rgb [n][H][W][3] -> yuv [n][H*W*3/2].  A lane takes the luma rows 2j, 2j + 1 by P pixels: 2 P luma bytes and P/2 samples of each chroma
+// plane - the unrounded numerators of both rows added per column, then 1-2-1 across columns 2i - 1, 2i, 2i + 1 (yuv.py downsample).  Only
+// the column left of the strip is not its own (2i + 1 <= W - 1 always); at x = 0 it clamps onto column 0.
+template <int P, bool NV12>
+__global__ __launch_bounds__(256) void rgb_to_yuv420_u8_kernel(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ yuv, int n, int H,
+                                                               int W, YuvCoef c) {
+    constexpr bool WORDS = P > 2;
+    constexpr int HP = P / 2;
+    const int gw = W / P, hh = H >> 1, hw = W >> 1;
+    const size_t plane = (size_t)H * W, total = (size_t)n * hh * gw;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const int g = (int)(t % gw);
+        const size_t fj = t / gw;
+        const int j = (int)(fj % hh);
+        const size_t f = fj / hh;
+        uint8_t* const fr = yuv + f * (plane + plane / 2);
+        const int x0 = g * P, xl = x0 > 0 ? x0 - 1 : 0;
+        int nb[P + 1], nr[P + 1];                                      // per column, both rows: [0] the column left of the strip
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int y = 2 * j + a;
+            const uint8_t* const row = rgb + (f * H + y) * (size_t)W * 3;
+            int px[3 * P + 3], luma[P];
+            px[0] = row[3 * (size_t)xl], px[1] = row[3 * (size_t)xl + 1], px[2] = row[3 * (size_t)xl + 2];
+            load_bytes<3 * P, WORDS>(row + (size_t)x0 * 3, px + 3);
+#pragma unroll
+            for (int p = 0; p <= P; ++p) {
+                const int r = px[3 * p], gg = px[3 * p + 1], b = px[3 * p + 2];
+                const int vb = c.cbr * r + c.cbg * gg + c.cbb * b, vr = c.crr * r + c.crg * gg + c.crb * b;
+                nb[p] = a ? nb[p] + vb : vb;
+                nr[p] = a ? nr[p] + vr : vr;
+                if (p) luma[p - 1] = shift_clip_u8<14>(c.yr * r + c.yg * gg + c.yb * b + (c.y0 << 14) + (1 << 13));
+            }
+            store_bytes<P, WORDS>(fr + (size_t)y * W + x0, luma);
+        }
+        int ob[HP], orr[HP];
+#pragma unroll
+        for (int q = 0; q < HP; ++q) {
+            ob[q] = shift_clip_u8<17>(nb[2 * q] + 2 * nb[2 * q + 1] + nb[2 * q + 2] + (1 << 16) + (128 << 17));   // 128 + (S' >> 17)
+            orr[q] = shift_clip_u8<17>(nr[2 * q] + 2 * nr[2 * q + 1] + nr[2 * q + 2] + (1 << 16) + (128 << 17));
+        }
+        if constexpr (NV12) {
+            int pair[P];
+#pragma unroll
+            for (int q = 0; q < HP; ++q) pair[2 * q] = ob[q], pair[2 * q + 1] = orr[q];
+            store_bytes<P, WORDS>(fr + plane + (size_t)j * W + x0, pair);
+        } else {
+            uint8_t* const pb = fr + plane + (size_t)j * hw + (x0 >> 1);
+            store_bytes<HP, WORDS>(pb, ob);
+            store_bytes<HP, WORDS>(pb + (size_t)hh * hw, orr);
+        }
+    }
+}
+
+namespace {
+
+// the strip width both kernels run with: 16-byte words, 4-byte words, bytes
+int strip_width(const void* a, const void* b, int W) {
+    const uintptr_t align = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
+    return W % 16 == 0 && align % 16 == 0 ? 16 : (W % 4 == 0 && align % 4 == 0 ? 4 : 2);
+}
+
+int strip_blocks(size_t items) {
+    const size_t blocks = (items + 255) / 256;
+    return (int)(blocks < 8192 ? blocks : 8192);
+}
+
+bool yuv_geometry_ok(const void* a, const void* b, int n, int H, int W) { return a && b && n >= 1 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1); }
+
+}  // namespace
+
+hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+    if (!yuv_geometry_ok(yuv, rgb, n, H, W)) return hipErrorInvalidValue;
+    const int P = strip_width(yuv, rgb, W);
+    const dim3 grid(strip_blocks((size_t)n * (H / 2 + 1) * (W / P))), block(256);
+#define PFNL_YUV_LAUNCH(P_)                                                                                        \
+    if (nv12)                                                                                                      \
+        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, true>), grid, block, 0, s, yuv, rgb, n, H, W, c);          \
+    else                                                                                                           \
+        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, false>), grid, block, 0, s, yuv, rgb, n, H, W, c)
+    if (P == 16) {
+        PFNL_YUV_LAUNCH(16);
+    } else if (P == 4) {
+        PFNL_YUV_LAUNCH(4);
+    } else {
+        PFNL_YUV_LAUNCH(2);
+    }
+#undef PFNL_YUV_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+    if (!yuv_geometry_ok(rgb, yuv, n, H, W)) return hipErrorInvalidValue;
+    const int P = strip_width(rgb, yuv, W);
+    const dim3 grid(strip_blocks((size_t)n * (H / 2) * (W / P))), block(256);
+#define PFNL_YUV_LAUNCH(P_)                                                                                        \
+    if (nv12)                                                                                                      \
+        hipLaunchKernelGGL((rgb_to_yuv420_u8_kernel<P_, true>), grid, block, 0, s, rgb, yuv, n, H, W, c);          \
+    else                                                                                                           \
+        hipLaunchKernelGGL((rgb_to_yuv420_u8_kernel<P_, false>), grid, block, 0, s, rgb, yuv, n, H, W, c)
+    if (P == 16) {
+        PFNL_YUV_LAUNCH(16);
+    } else if (P == 4) {
+        PFNL_YUV_LAUNCH(4);
+    } else {
+        PFNL_YUV_LAUNCH(2);
+    }
+#undef PFNL_YUV_LAUNCH
+    return hipGetLastError();
+}
+
+}  // namespace pfnl

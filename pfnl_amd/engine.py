@@ -229,12 +229,14 @@ class PFNLEngine:
         _capi.check(self._lib.pfnl_forward_strip(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), B, H, W,
                                                  int(row0), int(nrows), C.c_void_p(stream) if stream else None))
 
-    def open_stream(self, H: int, W: int, batch: int = 1, scene_cut=None):
+    def open_stream(self, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
+                    full_range=False):
         """A streaming session on this engine (pfnl_stream_open; pfnl_amd/stream.py VideoStream): uint8 LR frames [H,W,3] pushed one at
         a time, uint8 SR frames popped in order, ``batch`` windows per forward.  One open session per engine.  ``scene_cut``: None,
-        "manual" or a detector threshold - windows that stay inside a scene (VideoStream)."""
+        "manual" or a detector threshold - windows that stay inside a scene (VideoStream).  ``pixel_format`` / ``out_format`` "nv12" or "i420":
+        YUV 4:2:0 frames in / out, converted on the device with ``matrix`` and ``full_range`` (pfnl_amd/yuv.py)."""
         from .stream import VideoStream
-        return VideoStream(self, H, W, batch, scene_cut)
+        return VideoStream(self, H, W, batch, scene_cut, pixel_format, out_format, matrix, full_range)
 
     def sync(self) -> None:
         """Synchronise the engine's streams; raises if a device-pointer forward left the f16-pipe kernels' range

@@ -476,6 +476,64 @@ def scene_sad_u8(a, b) -> int:
     return int(out.item())
 
 
+def _req_u8(t, name):
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+        raise TypeError(f"{name} must be a contiguous uint8 tensor on the GPU")
+    return C.c_void_p(t.data_ptr())
+
+
+def _yuv_ids(fmt, matrix, full_range):
+    if fmt not in ("nv12", "i420"):
+        raise ValueError(f'fmt: "nv12" or "i420", got {fmt!r}')
+    if matrix not in _capi.YUV_MATRICES:
+        raise ValueError(f"matrix: one of {sorted(_capi.YUV_MATRICES)}, got {matrix!r}")
+    return _capi.PIXEL_FORMATS[fmt], _capi.YUV_MATRICES[matrix], int(bool(full_range))
+
+
+def yuv420_to_rgb(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None):
+    """n tightly packed NV12 / I420 frames, a uint8 tensor (cuda) of n * H*W*3/2 elements in any shape -> [n,H,W,3] uint8, byte for byte
+    pfnl_amd/yuv.py to_rgb (pfnl_op_yuv420_to_rgb_u8: the streaming session's input edge).  Any alignment; ``out``: write there."""
+    import torch
+    lib = _capi.load_library()
+    ids = _yuv_ids(fmt, matrix, full_range)
+    src = _req_u8(frames, "frames")
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"H and W must be even and at least 2, got {H} x {W}")
+    fb = H * W * 3 // 2
+    n = frames.numel() // fb
+    if n < 1 or n * fb != frames.numel():
+        raise ValueError(f"frames must hold a whole number of {fb}-byte frames, got {frames.numel()} bytes")
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device)
+    elif out.numel() != n * H * W * 3 or out.device != frames.device:
+        raise ValueError("out must hold n * H * W * 3 bytes on the frames' device")
+    _capi.check(lib.pfnl_op_yuv420_to_rgb_u8(src, ids[0], ids[1], ids[2], n, H, W, _req_u8(out, "out"), _stream(frames)))
+    return out.view(n, H, W, 3)
+
+
+def rgb_to_yuv420(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None):
+    """[n,H,W,3] (or [H,W,3]) uint8 (cuda) -> [n, H*3/2, W] uint8: tightly packed NV12 / I420 frames, byte for byte pfnl_amd/yuv.py from_rgb
+    (pfnl_op_rgb_to_yuv420_u8: the streaming session's output edge).  H, W even; any alignment; ``out``: write there."""
+    import torch
+    lib = _capi.load_library()
+    ids = _yuv_ids(fmt, matrix, full_range)
+    src = _req_u8(frames, "frames")
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError("rgb_to_yuv420 expects [n,H,W,3]")
+    n, H, W, _ = frames.shape
+    if n < 1 or H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"n >= 1, H and W even and at least 2, got {n} x {H} x {W}")
+    if out is None:
+        out = torch.empty((n, H * 3 // 2, W), dtype=torch.uint8, device=frames.device)
+    elif out.numel() != n * H * W * 3 // 2 or out.device != frames.device:
+        raise ValueError("out must hold n * H * W * 3 / 2 bytes on the frames' device")
+    _capi.check(lib.pfnl_op_rgb_to_yuv420_u8(src, ids[0], ids[1], ids[2], n, H, W, _req_u8(out, "out"), _stream(frames)))
+    return out.view(n, H * 3 // 2, W)
+
+
 def quantise_u8(sr):
     """uint8(np.round(np.clip(sr * 255, 0, 255))) on the device (reference model/pfnl.py:254-257)."""
     import torch

@@ -14,6 +14,11 @@ library.  Nothing here computes::
 Scenes (off by default): ``open_stream(H, W, batch, scene_cut=10.0)`` runs the cut detector of pfnl_amd/scene.py on the device ring, and
 ``scene_cut="manual"`` takes the cuts from the caller (``vs.mark_cut()`` before the push of a scene's first frame); the windows of a frame
 then stay inside its scene, and ``vs.cuts`` lists the delivered frames that started one.
+
+YUV 4:2:0 (off by default): ``open_stream(H, W, batch, pixel_format="nv12")`` takes frames as a decoder delivers them - ``(H*3//2, W)``
+uint8, or flat - and returns SR frames ``(sH*3//2, sW)`` for an encoder; ``"i420"`` likewise; ``out_format`` sets the two sides apart
+(``"rgb24"`` among them).  The conversion runs on the device at the two edges of the session, by the integer rule of pfnl_amd/yuv.py
+(``matrix`` "bt601" | "bt709", ``full_range``; chroma sited left); the ring, the scenes and the windows go on seeing RGB.
 """
 from __future__ import annotations
 
@@ -34,6 +39,28 @@ def next_batch(num_frames: int, batch: int, pushed: int, ended: bool, launched: 
     return first.value, count.value
 
 
+def format_arguments(pixel_format="rgb24", out_format=None, matrix="bt709", full_range=False) -> Tuple[int, int, int, int]:
+    """The four arguments of pfnl_stream_format for open_stream's keywords (``out_format`` None = ``pixel_format``); ValueError for
+    anything the library would refuse.  Needs no device."""
+    if out_format is None:
+        out_format = pixel_format
+    for name, value in (("pixel_format", pixel_format), ("out_format", out_format)):
+        if value not in _capi.PIXEL_FORMATS:
+            raise ValueError(f"{name}: one of {sorted(_capi.PIXEL_FORMATS)}, got {value!r}")
+    if matrix not in _capi.YUV_MATRICES:
+        raise ValueError(f"matrix: one of {sorted(_capi.YUV_MATRICES)}, got {matrix!r}")
+    if full_range not in (False, True, 0, 1):
+        raise ValueError(f"full_range: False or True, got {full_range!r}")
+    return _capi.PIXEL_FORMATS[pixel_format], _capi.PIXEL_FORMATS[out_format], _capi.YUV_MATRICES[matrix], int(bool(full_range))
+
+
+def frame_shapes(pixel_format: str, H: int, W: int) -> Tuple[tuple, ...]:
+    """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24; ``(H*3//2, W)`` or flat for the 4:2:0 formats."""
+    if pixel_format == "rgb24":
+        return ((H, W, 3),)
+    return ((H * 3 // 2, W), (H * W * 3 // 2,))
+
+
 class VideoStream:
     """One open session on an engine (``PFNLEngine.open_stream`` / ``PFNL.open_stream``); an engine has one at a time.
 
@@ -42,10 +69,18 @@ class VideoStream:
     tensors are read and written on the stream that was torch's current stream when the session was opened.
 
     ``scene_cut``: None - one scene, the reference's windows; ``"manual"`` - scenes begin where ``mark_cut()`` says; a float - a mean
-    luma difference in (0, 255] for the detector (pfnl_amd/scene.py cut_rule), marks included."""
+    luma difference in (0, 255] for the detector (pfnl_amd/scene.py cut_rule), marks included.
 
-    def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None):
+    ``pixel_format`` / ``out_format`` ("rgb24" | "nv12" | "i420"; ``out_format`` None = the same): what ``push`` takes and ``pop`` returns.
+    The 4:2:0 frames are tightly packed, ``(H*3//2, W)`` or flat in, ``(sH*3//2, sW)`` out (pfnl_amd/yuv.py), converted with ``matrix``
+    ("bt601" | "bt709") at limited or ``full_range``."""
+
+    def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
+                 full_range=False):
         import torch
+        fmt = format_arguments(pixel_format, out_format, matrix, full_range)
+        self.pixel_format, self.out_format = pixel_format, pixel_format if out_format is None else out_format
+        self.matrix, self.full_range = matrix, bool(full_range)
         if not engine._ready:
             raise RuntimeError("weights have not been loaded")
         self._engine = engine                       # (keeps the handle alive)
@@ -69,6 +104,12 @@ class VideoStream:
                     _capi.check(self._lib.pfnl_stream_scenes(s, 1, 0.0))
                 else:
                     _capi.check(self._lib.pfnl_stream_scenes(s, 2, float(scene_cut)))
+            except Exception:
+                self.close()
+                raise
+        if fmt[0] or fmt[1]:                        # (all defaults: the session as it always was, and no call)
+            try:
+                _capi.check(self._lib.pfnl_stream_format(s, *fmt))
             except Exception:
                 self.close()
                 raise
@@ -108,10 +149,11 @@ class VideoStream:
         fetches the next frame (``pop`` is there for a caller that wants them at once)."""
         s = self._handle()
         due = self.ready()
-        shape = (self.H, self.W, 3)
+        shapes = frame_shapes(self.pixel_format, self.H, self.W)
+        shape = " or ".join(map(str, shapes))
         if type(frame).__module__.startswith("torch"):
             import torch
-            if frame.dtype != torch.uint8 or tuple(frame.shape) != shape:
+            if frame.dtype != torch.uint8 or tuple(frame.shape) not in shapes:
                 raise ValueError(f"expected a uint8 frame of shape {shape}, got {frame.dtype} {tuple(frame.shape)}")
             if not frame.is_cuda or frame.device.index != self.device.index:
                 raise ValueError(f"tensor on {frame.device}, stream on {self.device} (host frames: numpy arrays)")
@@ -120,7 +162,7 @@ class VideoStream:
             _capi.check(self._lib.pfnl_stream_push(s, C.c_void_p(frame.data_ptr()), 1))
         else:
             frame = np.asarray(frame)
-            if frame.dtype != np.uint8 or frame.shape != shape:
+            if frame.dtype != np.uint8 or frame.shape not in shapes:
                 raise ValueError(f"expected a uint8 frame of shape {shape}, got {frame.dtype} {frame.shape}")
             frame = np.ascontiguousarray(frame)
             self._device_frames = False
@@ -151,7 +193,7 @@ class VideoStream:
     def pop(self):
         """The next SR frame as ``(index, frame)``, or None when none is deliverable; waits only for the batch that holds it."""
         s = self._handle()
-        shape = (self.scale * self.H, self.scale * self.W, 3)
+        shape = frame_shapes(self.out_format, self.scale * self.H, self.scale * self.W)[0]
         index, got = C.c_longlong(0), C.c_int(0)
         if self._device_frames:
             import torch

@@ -1,0 +1,140 @@
+"""YUV 4:2:0 <-> RGB, 8 bits, stated once in integers (numpy only; no device).
+
+The streaming session takes and delivers NV12 / I420 frames (include/pfnl_hip.h, pfnl_stream_format; pfnl_amd/csrc/yuv.hip); this module is
+the rule its kernels are tested against, byte for byte.  Everything after the coefficients is integer arithmetic:
+
+* F = 14 fractional bits, ONE = 1 << 14, rnd(x) = floor(x * ONE + 0.5); every coefficient is computed in double precision and rounded once,
+  the third of each encode row is derived from the other two - greys have zero chroma and white is y0 + round(255 ys) exactly;
+* frames are tightly packed, H * W * 3 / 2 bytes, H and W even: ``nv12`` = Y [H][W], CbCr [H/2][W/2][2]; ``i420`` = Y, Cb [H/2][W/2], Cr;
+* chroma is sited left (H.264 / HEVC type 0): on the even luma columns, midway between the two luma rows.  YUV -> RGB interpolates it
+  with the weights 3 : 1 vertically (near row : far row) and 1 : 1 between two samples on odd columns, indices clamped to the plane; RGB ->
+  YUV filters the unrounded chroma numerators with 1-2-1 over the two luma rows, columns clamped, and rounds once.
+
+Out of scope: pitched planes, 10-bit formats, 4:2:2 / 4:4:4, other sitings, transfer functions, BT.2020.
+"""
+from __future__ import annotations
+
+import math
+from typing import Tuple
+
+import numpy as np
+
+F = 14
+ONE = 1 << F
+HALF = ONE >> 1
+FORMATS = ("nv12", "i420")
+MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # Kr, Kb
+
+
+def _rnd(x: float) -> int:
+    return int(math.floor(x * ONE + 0.5))
+
+
+def coefficients(matrix: str, full_range) -> Tuple[int, Tuple[int, ...], Tuple[int, ...]]:
+    """(y0, encode, decode): encode = (yr, yg, yb, cbr, cbg, cbb, crr, crg, crb), decode = (dy, drv, dgu, dgv, dbu) - the fifteen
+    integers of pfnl_yuv_coefficients, in its order."""
+    if matrix not in MATRICES:
+        raise ValueError(f"matrix: one of {sorted(MATRICES)}, got {matrix!r}")
+    kr, kb = MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    if full_range:
+        y0, ys, cs = 0, 1.0, 1.0
+    else:
+        y0, ys, cs = 16, 219.0 / 255.0, 224.0 / 255.0
+    yr, yb = _rnd(ys * kr), _rnd(ys * kb)
+    yg = _rnd(ys) - yr - yb
+    cbr, cbb = _rnd(-cs * kr / (2.0 * (1.0 - kb))), _rnd(cs / 2.0)
+    cbg = -cbr - cbb
+    crr, crb = _rnd(cs / 2.0), _rnd(-cs * kb / (2.0 * (1.0 - kr)))
+    crg = -crr - crb
+    dy = _rnd(1.0 / ys)
+    drv, dbu = _rnd(2.0 * (1.0 - kr) / cs), _rnd(2.0 * (1.0 - kb) / cs)
+    dgu, dgv = _rnd(-2.0 * kb * (1.0 - kb) / (kg * cs)), _rnd(-2.0 * kr * (1.0 - kr) / (kg * cs))
+    return y0, (yr, yg, yb, cbr, cbg, cbb, crr, crg, crb), (dy, drv, dgu, dgv, dbu)
+
+
+def _geometry(fmt: str, H: int, W: int) -> None:
+    if fmt not in FORMATS:
+        raise ValueError(f"fmt: one of {FORMATS}, got {fmt!r}")
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"H and W must be even and at least 2, got {H} x {W}")
+
+
+def frame_bytes(H: int, W: int) -> int:
+    return H * W * 3 // 2
+
+
+def planes(frame, fmt: str, H: int, W: int):
+    """(Y [H,W], Cb [H/2,W/2], Cr [H/2,W/2]) uint8 of one packed frame (any shape with H*W*3/2 elements)."""
+    _geometry(fmt, H, W)
+    flat = np.asarray(frame).reshape(-1)
+    if flat.dtype != np.uint8 or flat.size != frame_bytes(H, W):
+        raise ValueError(f"expected {frame_bytes(H, W)} uint8 elements, got {flat.dtype} x {flat.size}")
+    y = flat[:H * W].reshape(H, W)
+    c = flat[H * W:]
+    if fmt == "nv12":
+        c = c.reshape(H // 2, W // 2, 2)
+        return y, c[..., 0], c[..., 1]
+    c = c.reshape(2, H // 2, W // 2)
+    return y, c[0], c[1]
+
+
+def pack(Y, Cb, Cr, fmt: str):
+    """[H*3/2, W] uint8: the planes as one packed frame."""
+    Y, Cb, Cr = (np.asarray(p, np.uint8) for p in (Y, Cb, Cr))
+    H, W = Y.shape
+    _geometry(fmt, H, W)
+    if Cb.shape != (H // 2, W // 2) or Cr.shape != Cb.shape:
+        raise ValueError("Cb and Cr must be [H/2, W/2]")
+    c = np.stack([Cb, Cr], axis=-1) if fmt == "nv12" else np.stack([Cb, Cr], axis=0)
+    return np.concatenate([Y.reshape(-1), c.reshape(-1)]).reshape(H * 3 // 2, W)
+
+
+def upsample(C, H: int, W: int):
+    """One chroma plane [H/2, W/2] at every luma pixel, [H,W] int32 in [0, 255]."""
+    C = np.asarray(C).astype(np.int32)
+    y, x = np.arange(H), np.arange(W)
+    j, i = y >> 1, x >> 1
+    jn = np.clip(np.where(y & 1, j + 1, j - 1), 0, H // 2 - 1)
+    ir = np.clip(i + 1, 0, W // 2 - 1)
+    near, far = C[j], C[jn]                                             # [H, W/2]
+    even = (6 * near[:, i] + 2 * far[:, i] + 4) >> 3
+    odd = (3 * near[:, i] + far[:, i] + 3 * near[:, ir] + far[:, ir] + 4) >> 3
+    return np.where((x & 1)[None, :], odd, even)
+
+
+def to_rgb(frame, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False):
+    """One packed frame -> [H,W,3] uint8."""
+    y0, _, (dy, drv, dgu, dgv, dbu) = coefficients(matrix, full_range)
+    Y, Cb, Cr = planes(frame, fmt, H, W)
+    yy = dy * (Y.astype(np.int32) - y0)
+    u, v = upsample(Cb, H, W) - 128, upsample(Cr, H, W) - 128
+    r = (yy + drv * v + HALF) >> F
+    g = (yy + dgu * u + dgv * v + HALF) >> F
+    b = (yy + dbu * u + HALF) >> F
+    return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+
+
+def downsample(N):
+    """Chroma numerators [H,W] int32 (14 fractional bits, unrounded) -> the plane [H/2, W/2] uint8: 1-2-1 over two rows, one rounding."""
+    N = np.asarray(N, np.int32)
+    H, W = N.shape
+    v = N[0::2] + N[1::2]                                               # [H/2, W]
+    c = np.arange(0, W, 2)
+    s = v[:, np.clip(c - 1, 0, W - 1)] + 2 * v[:, c] + v[:, np.clip(c + 1, 0, W - 1)]
+    return np.clip(128 + ((s + (1 << (F + 2))) >> (F + 3)), 0, 255).astype(np.uint8)
+
+
+def from_rgb(rgb, fmt: str, matrix: str = "bt709", full_range=False):
+    """[H,W,3] uint8 -> one packed frame [H*3/2, W] uint8."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"expected [H,W,3] uint8, got {rgb.dtype} {rgb.shape}")
+    H, W = rgb.shape[:2]
+    _geometry(fmt, H, W)
+    y0, (yr, yg, yb, cbr, cbg, cbb, crr, crg, crb), _ = coefficients(matrix, full_range)
+    r, g, b = (rgb[..., k].astype(np.int32) for k in range(3))
+    Y = np.clip((yr * r + yg * g + yb * b + (y0 << F) + HALF) >> F, 0, 255)
+    Cb = downsample(cbr * r + cbg * g + cbb * b)
+    Cr = downsample(crr * r + crg * g + crb * b)
+    return pack(Y, Cb, Cr, fmt)
