@@ -197,7 +197,8 @@ int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes);
  * conv10_i, then the whole of conv2_i), "chain2_split" (the same with the chains of a last, partial round cut by frames: option
  * split16_splitchains) and "chain2_sf0" (the same with a split-format copy of every block's output so that the next block's
  * conv1_i takes its halo by LDS-DMA: option split16_sf0=on), "split16_3" / "split16_4", "winograd_ws3" / "winograd_ws4", "winograd_tile4",
- * "direct4"; bf16: "bf16_3", "bf16_3_split", "bf16_4", "bf16_mid4".  The ONE statement of the dispatch rule: pfnl_forward runs it, pfnl_workspace_bytes sizes
+ * "direct4"; bf16: "bf16_3", "bf16_3_split", "bf16_4", "bf16_mid4".  The ONE statement of the dispatch rule (pfnl_amd/csrc/launch_plan.h: trunk_plan, a pure
+ * function of the options, the shape and the CU count, testable on the host): pfnl_forward runs it, pfnl_workspace_bytes sizes
  * from it, bench.py's byte model and the tests read it here.  The structure changes the summation order, hence the last bits: the same clip
  * gives bit-different (oracle-equal) results in a batch that takes "chain2" and alone ("mid4" / "small2"). */
 int pfnl_plan(pfnl_handle* h, int B, int H, int W, char* buf, size_t buflen);

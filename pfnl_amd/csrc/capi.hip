@@ -22,6 +22,7 @@
 #include "conv_bf16.h"
 #include "conv_split16.h"
 #include "conv_small.h"
+#include "launch_plan.h"
 
 namespace {
 
@@ -153,17 +154,6 @@ struct HostPool {
 
 }  // namespace
 
-// a 3x3 launch with fewer tiles of 8x32 pixels than this takes the small-shape trunk (conv_small.hip) under the default choices; from
-// here on the split-f16 kernels' per-tile launches are faster (tools/precision_ladder.py: 210 - 224 tiles 1.99 - 2.14 -> 1.85 - 1.90 ms;
-// 168 tiles 1.08 against 1.88).  256 (a tile per CU) until round 5.
-// Both work-order thresholds were measured on the 256-CU part and are a fraction of the CUs a launch can occupy: they scale with
-// the CU count of the handle's device (a CPX partition or a smaller device keeps the same tiles-per-CU crossover).
-static constexpr int kSmallTiles256 = 200;                  // tiles of 8x32 pixels per 3x3 launch below which the small-shape trunk runs (0.78 per CU)
-static constexpr int kMidChains256 = 136;                   // (clip, tile) chains below which a block runs as four per-tile launches (0.53 per CU)
-static int scaled_by_cus(int v256, int ncu) {
-    return ncu > 0 && ncu != 256 ? std::max(1, (int)((long long)v256 * ncu / 256)) : v256;
-}
-
 // the weight packs of one PF block: offsets into the three device blobs, filled by pfnl_finalize_weights
 struct BlockPacks {
     // fp32 blob `wdev` (floats): the direct kernel's packs, biases, conv1x1_pack_weights (c10_s), the Winograd packs (_u)
@@ -200,21 +190,12 @@ struct pfnl_handle {
     std::vector<GraphEntry> graphs;
     unsigned long long cfg_gen = 0;                           // bumped by finalize_weights / set_option
     hipEvent_t gev = nullptr;                                  // ordering with the legacy default stream around a replay
-    int graph_mode = 0;                                       // 0 off (default: measured slower), 1 auto (frames*H*W <= 65536 pixels), 2 on
-    bool conv2_grouped = true;                                // winograd: conv2_i as one grouped launch (option conv2=grouped|split)
+    pfnl::Options opt;                                        // what pfnl_set_option and the environment reads of pfnl_create set (launch_plan.h)
     int merge_cstride = 48;                                   // floats per pixel of `merge` as written by the last forward
-    int conv1x1_algo = 2;                                     // conv10: 2 streaming kernel on the f16 pipe, split operands (default), 1 streaming f32-MFMA kernel (conv1x1.hip), 0 LDS-tiled implicit GEMM
-    bool bf16_fuse10 = true;                                  // bf16 trunk: conv10_i inside the conv1_i launch (option bf16_conv10=fused|separate)
-    bool bf16_m16 = true;                                     // bf16 trunk: the two chained 3x3 launches on v_mfma_f32_16x16x32_bf16 (option bf16_mfma=16|32)
-    bool bf16 = false;                                        // option precision=bf16: progressive-fusion trunk in bf16 (conv_bf16.hip); NL, conv0 maths, merge, tail stay fp32
     DevBuf wdev16;                                            // bf16 packs (offsets in 16-bit elements)
     size_t off16_m1 = 0;                                      // convmerge1: T consecutive packs (cout 48 zero-padded to 64)
     size_t off16s_m1 = 0;                                     // convmerge1, split-f16 packs: T consecutive (frame, both halves) packs
-    int m1_algo = 0;                                          // convmerge1 with conv3x3=split16: 0 auto (= 1), 1 the split-f16 kernel's accumulating mode, 2 Winograd
-    int conv_algo = 5;                                        // conv3x3: 5 auto (4 for large shapes, 3 for small), 0 direct, 1 winograd (4 waves / tile), 3 winograd_ws (persistent, wave-specialised), 4 split16 (f16 MFMA, split fp32 operands)
-    int nl_algo = 2;                                          // non-local block of the fp32 path: 0 f32 MFMA (nonlocal.hip), 1 split-f16 (nonlocal_f16.hip), 2 auto (1 from N = 1024 keys)
     DevBuf wdev16s;                                           // split-f16 packs of the 3x3 kernels (offsets in 16-bit elements)
-    bool s16_m16 = true;                                      // option split16_mfma=16|32: the chain launch of conv2_i on v_mfma_f32_16x16x32_f16
     size_t off16m_m1 = 0;                                     // convmerge1's small-shape pack (conv_small.hip), in the same blob
     // The f16-pipe kernels of the fp32 path have a DOMAIN (operands inside binary16's range; the non-local kernel: inputs x 2^7).
     // Beyond it an operand becomes inf and the result non-finite - the tail kernel, which every output value passes through, ORs
@@ -230,25 +211,11 @@ struct pfnl_handle {
     PinBuf pin_in, pin_out;
     HostPool pool;
     std::vector<hipEvent_t> d2h_ev;
-    bool strict = false, strict_once = false, weights_f16_ok = true;
+    bool strict_once = false, weights_f16_ok = true;
     long long range_reruns = 0;
-    int small_mode = 0;                                       // option small=auto|on|off: the small-shape trunk kernels (auto: when a launch has < 256 tiles of 8x32 pixels)
-    bool small_c10 = true;                                    // ... with conv10_i inside the conv1_i launch (per-frame partials, summed in conv2_i's prologue); false: three launches (small3)
-    DevBuf p10;                                               // ... those partials [B*T][H][W][64] fp32
-    bool sf_chain = true;                                     // ... and conv2_i is ONE launch (option split16_chain=on|off)
-    bool sf_c10 = true;                                       // ... and conv1_i + conv10_i are ONE launch (option split16_c10=on|off)
-    bool sf_mid = true;                                       // option split16_mid=auto|off: launches with fewer (clip, tile) chains than sf_mid_chains run the block as four per-tile launches
-    int sf_mid_chains = 0;                                    // 0: kMidChains256 scaled by the device's CUs (measured crossover, tools/precision_ladder.py; env PFNL_SF_MID_CHAINS for sweeps)
-    bool sf0 = false;                                         // option split16_sf0=off|on: in the two-launch block the chain kernel ALSO writes the block's output in the split
-                                                              // format (`inp0sf`), and the next block's conv1_i + conv10_i launch takes its halo from there by LDS-DMA (round 6).
-                                                              // Bit-identical; MEASURED SLOWER (configs[1], same box: 4.86 vs 4.45 ms - the chain kernel pays 22 us for the copy,
-                                                              // conv1_i + conv10_i gains 0.6: DESIGN.md R6.1), hence off
-    DevBuf inp0sf;                                            // ... that copy [B*T][H][W] x 256 B
-    bool split_chains = true;                                 // option split16_splitchains=auto|off: in the two-launch block, a batch that is not a whole number of rounds of
-                                                              // (clip, tile) chains runs its last, partial round as PARTS of chains cut by frames (conv_split16.h "SPLIT CHAINS")
-    DevBuf c10part;                                           // ... conv10_i's partial sums of those parts: [slot][8][32][64] fp32
-    bool sf_path = true;                                      // option split16_sf=on|off: with conv3x3 = conv1x1 = split16, conv1_i and conv10_i write the
-                                                              // split format (conv_split16.h) and both halves of conv2_i read it by LDS-DMA (conv_sf.hip)
+    DevBuf p10;                                               // the small-shape trunk's conv10_i partials (small_c10) [B*T][H][W][64] fp32
+    DevBuf inp0sf;                                            // the split-format copy of the block output (sf0) [B*T][H][W] x 256 B
+    DevBuf c10part;                                           // split chains: conv10_i's partial sums of the parts: [slot][8][32][64] fp32
 
     // device weights (offsets in floats into `wdev`)
     DevBuf wdev;
@@ -263,8 +230,6 @@ struct pfnl_handle {
     size_t off_nl_m = 0, off_nl_c = 0;                        // M = Wt Wp^T [CP][CP], c = bt Wp^T [CP]
     DevBuf Q;                                                 // projected queries [B][N][CP]
     DevBuf Xs;                                                // average-pooled keys / values [B][Nk][CP] (nl_sub_sample > 1)
-    int nl_type = -1;                                         // utils.NonLocalBlock nltype: -1 auto (0 with theta / phi variables, else 1 = PFNL's call), 0, 1, 2
-    int nl_sub = 1;                                           // ... sub_sample (utils.py:27-28,35-36); PFNL's call: 1
 
     // workspace
     DevBuf nl16;                                              // bf16 non-local: split K / V^T operands
@@ -415,144 +380,10 @@ size_t numel(const std::vector<int64_t>& s) {
     return n;
 }
 
-// convmerge1 (model/pfnl.py:73-74): which launch computes it
-enum Merge1Kind {
-    M1_SMALL,         // conv_small.hip: T sources, cout 48 zero-padded to 64
-    M1_BF16,          // the accumulating mode of the bf16 3x3 kernel
-    M1_SPLIT16,       // the accumulating mode of conv3x3_split16_kernel
-    M1_SPLIT16_CUT,   // ... with the trunk's split chains, + c10_finalize_kernel
-    M1_WINOGRAD,      // the accumulating mode of the persistent Winograd kernel
-    M1_DIRECT,        // conv_mfma: 3x3 over the concat of T frames, cout 48
-};
-const char* const kMerge1Names[] = {"small", "bf16", "split16", "split16_cut", "winograd", "direct"};
-
-// THE LAUNCH PLAN of a forward for a shape under the handle's current options: the one place the dispatch rule lives.
-// forward_device runs it, pfnl_workspace_bytes sizes from it, pfnl_plan reports it (bench.py's byte model and the tests read it there).
-struct TrunkPlan {
-    bool bf16 = false;
-    bool strict = false;                   // fp32: f32-MFMA kernels only (strict_fp32, a range rerun, weights beyond binary16): trunk, non-local block, conv0
-    int nltype = 1;                        // utils.NonLocalBlock nltype, resolved (option nl_type -1 = auto)
-    int nl_family = 0;                     // the non-local block's kernels: 0 the general form (nltype 0 / 2 or sub-sampling: f32 MFMA), 1 the f16 pipe with
-                                           // exactly split operands (fp32 precision, from 1024 keys), 2 the f16 pipe on the hi parts (precision bf16), 3 f32 MFMA
-    bool nl_fused_pack = false;            // families 1 / 2: one pack launch writes X fp32 + the binary16 K / V^T operands (round 6)
-    // bf16 trunk
-    bool bmid = false, fuse10 = false;
-    // fp32 trunk
-    int algo = 0, conv1x1_algo = 0;        // resolved 3x3 / 1x1 algorithm (conv_algo 5 = auto is resolved here)
-    bool sf = false;                       // inp1 and base in the split format
-    bool small = false, small_c10 = false; // conv_small.hip: 3 (2 with small_c10) launches per block
-    bool mid = false;                      // four per-tile launches per block
-    bool c10_fused = false;                // conv1_i + conv10_i in one launch (conv3x3_c1c10_kernel)
-    bool chain = false;                    // conv2_i in one launch (conv3x3_sf_chain_kernel)
-    bool sf0 = false;                      // chain2 only: split-format copy of the block output, conv1_i's halo by LDS-DMA
-    bool conv2_grouped = false;            // Winograd: conv2_i as one grouped launch
-    int n_full = 0, split_s = 0, split_q = 0;   // chain2 only: SPLIT CHAINS (conv_split16.h) - the chains behind the first n_full are cut into split_s parts of <= split_q frames
-    int c1x1_launches = 0;                 // launches per block of class conv1x1 (conv10_i on its own / c10_finalize_kernel)
-    int launches_per_block = 0;
-    int tiles8x32 = 0, chains = 0;
-    int mfma = 32;                         // MFMA shape of the chained 3x3 launches: 16 = v_mfma_f32_16x16x32_* (bf16: conv_bf16_v3.hip M16; fp32: the chain launch
-                                           // of conv2_i, conv3x3_sf_chain16_kernel - whole rounds of at least a chain per CU only), 32 = 32x32x16
-    int c1_mfma = 32;                      // fp32: MFMA shape of conv1_i's 3x3 stage in the fused conv1_i + conv10_i launch (conv3x3_c1c10_kernel; 16 exactly where mfma is)
-    int merge1 = M1_DIRECT;                // convmerge1's launch (Merge1Kind)
-    int merge_stride = 48;                 // floats per pixel of `merge` as convmerge1 writes it
-    // the trunk's buffers that depend on the plan (floats): the small-shape trunk's conv10_i partials [B*T][H][W][64]; the split-format copy of
-    // inp0 [B*T][H][W] x 256 B; split chains' partial sums [slot][8][32][64] (conv10_i's, then convmerge1's)
-    size_t p10_floats = 0, inp0sf_floats = 0, c10part_floats = 0;
-    const char* name = "";
-};
-
-void plan_bf16_trunk(const pfnl_handle* h, TrunkPlan& pl, int T, int grid, int mid_chains, bool fits32) {
-    // MID shapes (as in the fp32 trunk): with fewer (clip, tile) chains than mid_chains the chained launches leave most CUs idle
-    pl.bmid = h->sf_mid && h->bf16_fuse10 && pl.chains < mid_chains;
-    pl.fuse10 = h->bf16_fuse10 && !pl.bmid;
-    pl.launches_per_block = pl.fuse10 ? 3 : 4;
-    pl.c1x1_launches = pl.fuse10 ? 0 : 1;
-    // SPLIT CHAINS of the two chained launches (chain_order.h, split_rule)
-    if (pl.fuse10 && h->split_chains && fits32 && split_rule(pl.chains, T, grid, pl.n_full, pl.split_s, pl.split_q)) {
-        pl.launches_per_block += 1;                                     // c10_finalize_bf16_kernel
-        pl.c1x1_launches = 1;
-    }
-    pl.name = pl.bmid ? "bf16_mid4" : (pl.fuse10 ? (pl.split_s ? "bf16_3_split" : "bf16_3") : "bf16_4");
-    pl.mfma = h->bf16_m16 ? 16 : 32;
-    pl.merge1 = M1_BF16;
-    pl.merge_stride = 64;
-}
-
-void plan_fp32_trunk(const pfnl_handle* h, TrunkPlan& pl, int B, int H, int W, int T, int grid, int mid_chains, bool fits32) {
-    // conv3x3 = auto (default): the split-f16 kernels when a launch has at least ~0.78 tiles per CU, the Winograd f32 kernel below
-    const int small_tiles = scaled_by_cus(kSmallTiles256, h->ncu);
-    const int algo0 = h->conv_algo == 5 ? ((pl.tiles8x32 >= small_tiles && fits32) ? 4 : 3) : h->conv_algo;
-    pl.algo = (pl.strict && algo0 == 4) ? 3 : algo0;
-    pl.conv1x1_algo = (pl.strict && h->conv1x1_algo == 2) ? 1 : h->conv1x1_algo;
-    pl.sf = pl.algo == 4 && pl.conv1x1_algo == 2 && h->sf_path;
-    // small shapes (BASELINE.json configs[0], configs[4]): the trunk through conv_small.hip; only under the default algorithm choices
-    pl.small = !pl.strict && fits32 &&
-               (h->small_mode == 1 || (h->small_mode == 0 && h->conv_algo == 5 && h->conv1x1_algo == 2 && pl.tiles8x32 < small_tiles));
-    pl.small_c10 = pl.small && h->small_c10;
-    if (pl.small) {
-        pl.launches_per_block = pl.small_c10 ? 2 : 3;
-        pl.c1x1_launches = pl.small_c10 ? 0 : 1;
-        pl.name = pl.small_c10 ? "small2" : "small3";
-        pl.merge1 = M1_SMALL;
-        pl.merge_stride = 64;
-        return;
-    }
-    pl.mid = pl.sf && h->sf_mid && h->conv_algo == 5 && h->sf_c10 && h->sf_chain && pl.chains < mid_chains;   // (only under the default choices, like `small`)
-    pl.c10_fused = pl.sf && h->sf_c10 && !pl.mid;
-    pl.chain = pl.sf && h->sf_chain && !pl.mid;
-    pl.sf0 = pl.c10_fused && pl.chain && h->sf0;
-    // grouped / accumulating Winograd modes chain T(+1) units inside one workgroup: only worth it when there are enough (clip, 4x32-pixel tile)
-    // groups to occupy the chip (below ~220 the split launches finish sooner)
-    const int wino_groups = B * ((W + 31) / 32) * ((H + 3) / 4);
-    pl.conv2_grouped = pl.algo == 3 && h->conv2_grouped && wino_groups >= 224 && fits32;
-    pl.launches_per_block = (pl.c10_fused ? 1 : 2) + ((pl.chain || pl.conv2_grouped) ? 1 : 2);
-    pl.c1x1_launches = pl.c10_fused ? 0 : 1;
-    // SPLIT CHAINS of conv1_i + conv10_i and conv2_i (chain_order.h, split_rule)
-    if (pl.c10_fused && pl.chain && h->split_chains && split_rule(pl.chains, T, grid, pl.n_full, pl.split_s, pl.split_q)) {
-        pl.launches_per_block += 1;                                     // c10_finalize_kernel
-        pl.c1x1_launches = 1;
-    }
-    // the chain launch on 16x16x32: where every CU has a chain the launch sits on the power cap and the shape's energy counts; below that (UDM10: 230
-    // chains) its extra cycles do (+0.9 %); split chains and the split-format copy stay on the 32x32x16 kernel
-    pl.mfma = (h->s16_m16 && pl.c10_fused && pl.chain && !pl.sf0 && !pl.split_s && pl.chains >= grid) ? 16 : 32;
-    pl.c1_mfma = pl.mfma;                                               // conv1_i's stage of the other launch of the block: the same rule
-    pl.name = pl.mid ? "mid4" : (pl.c10_fused && pl.chain) ? (pl.sf0 ? "chain2_sf0" : (pl.split_s ? "chain2_split" : "chain2"))
-            : pl.algo == 4 ? (pl.launches_per_block == 3 ? "split16_3" : "split16_4")
-            : pl.algo == 3 ? (pl.conv2_grouped ? "winograd_ws3" : "winograd_ws4")
-            : pl.algo == 1 ? "winograd_tile4" : "direct4";
-    // convmerge1: on the f16 pipe with the split-f16 trunk (convmerge1's chains are the trunk's: a cut last round is cut here too), else the
-    // persistent Winograd kernel where there are enough groups, else the direct kernel
-    if (pl.algo == 4 && h->m1_algo != 2 && fits32) pl.merge1 = pl.split_s ? M1_SPLIT16_CUT : M1_SPLIT16;
-    else if ((pl.algo == 3 || pl.algo == 4) && wino_groups >= 224 && fits32) pl.merge1 = M1_WINOGRAD;
-    pl.merge_stride = pl.merge1 == M1_DIRECT ? 48 : 64;
-}
-
-// H: the rows the trunk buffers hold (a strip's with its halo); Hfull: the frame's (the non-local block's keys are global)
+// the launch plan of a forward (launch_plan.h) for a shape under the handle's current options and weights
 TrunkPlan trunk_plan(const pfnl_handle* h, int B, int H, int W, int Hfull) {
-    TrunkPlan pl;
-    const int T = h->cfg.num_frames;
-    pl.bf16 = h->bf16;
-    pl.strict = !h->bf16 && (h->strict || h->strict_once || !h->weights_f16_ok);
-    pl.tiles8x32 = B * T * ((W + 31) / 32) * ((H + 7) / 8);
-    pl.chains = pl.tiles8x32 / T;
-    const int grid = persistent_grid(h->ncu);
-    const int mid_chains = h->sf_mid_chains > 0 ? h->sf_mid_chains : scaled_by_cus(kMidChains256, h->ncu);
-    const bool fits32 = (long long)H * W * 256 < 0x7fffffffLL;
-    if (h->bf16) plan_bf16_trunk(h, pl, T, grid, mid_chains, fits32);
-    else plan_fp32_trunk(h, pl, B, H, W, T, grid, mid_chains, fits32);
-
-    const int N = (Hfull / 2) * (W / 2);
-    pl.nltype = h->nl_type < 0 ? (h->nl_theta ? 0 : 1) : h->nl_type;
-    pl.nl_family = (pl.nltype != 1 || h->nl_sub > 1) ? 0
-                 : h->bf16 ? 2
-                 : (!pl.strict && (h->nl_algo == 1 || (h->nl_algo == 2 && N >= 1024))) ? 1 : 3;
-    pl.nl_fused_pack = (pl.nl_family == 1 || pl.nl_family == 2) && nl_f16_fits_one_launch(B, N);
-
-    const size_t frame_floats = (size_t)B * T * H * W * 64;
-    pl.p10_floats = pl.small_c10 ? frame_floats : 0;
-    pl.inp0sf_floats = pl.sf0 ? frame_floats : 0;
-    pl.c10part_floats = pl.split_s ? (size_t)(pl.chains - pl.n_full) * pl.split_s * 8 * 32 * 64 : 0;
-    return pl;
+    const PlanFacts facts{h->cfg.num_frames, h->ncu, h->nl_theta, h->strict_once, h->weights_f16_ok};
+    return trunk_plan(h->opt, facts, B, H, W, Hfull, nl_f16_fits_one_launch(B, (Hfull / 2) * (W / 2)));
 }
 
 // what every stage of one forward reads
@@ -646,12 +477,12 @@ int nonlocal_block(const Fwd& f, const float* in, int Hfull, int q0, int q1) {
         // the f32-MFMA kernel in both precisions; PFNL's own call (nltype 1, sub_sample 1) takes the branches below
         const float* Kx = h->X.p;
         int Nk = N;
-        if (h->nl_sub > 1) {
+        if (h->opt.nl_sub > 1) {
             const int h2 = Hfull / 2, w2 = W / 2;
-            if (h2 / h->nl_sub < 1 || w2 / h->nl_sub < 1) return fail(PFNL_ERR_INVALID, "nl_sub_sample larger than the space_to_depth grid");
-            Nk = (h2 / h->nl_sub) * (w2 / h->nl_sub);
+            if (h2 / h->opt.nl_sub < 1 || w2 / h->opt.nl_sub < 1) return fail(PFNL_ERR_INVALID, "nl_sub_sample larger than the space_to_depth grid");
+            Nk = (h2 / h->opt.nl_sub) * (w2 / h->opt.nl_sub);
             if (h->Xs.ensure((size_t)B * Nk * CP)) return fail(PFNL_ERR_NOMEM, "workspace allocation failed");
-            HIPCHK(launch_nl_pool(h->X.p, h->Xs.p, B, h2, w2, h->nl_sub, C, s));
+            HIPCHK(launch_nl_pool(h->X.p, h->Xs.p, B, h2, w2, h->opt.nl_sub, C, s));
             Kx = h->Xs.p;
         }
         const float* Qp = nullptr;
@@ -981,65 +812,6 @@ int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull
     return 0;
 }
 
-// ---- the options of pfnl_set_option / pfnl_get_option: each key sets one int or bool field of the handle (a bool takes 0 / 1) to the value
-// of one of its names; the first name of a value is the one pfnl_get_option returns.  nl_sub_sample (an integer) and bf16_nonlocal (f16
-// only) are the two keys outside the table.
-struct OptionField {
-    int pfnl_handle::*i = nullptr;
-    bool pfnl_handle::*b = nullptr;
-    constexpr OptionField(int pfnl_handle::*f) : i(f) {}
-    constexpr OptionField(bool pfnl_handle::*f) : b(f) {}
-    int get(const pfnl_handle* h) const { return i ? h->*i : (int)(h->*b); }
-    void set(pfnl_handle* h, int v) const {
-        if (i) h->*i = v;
-        else h->*b = v != 0;
-    }
-};
-
-struct OptionName {
-    const char* name;   // (null: past the last name)
-    int value;
-};
-
-struct OptionSpec {
-    const char* key;
-    OptionField field;
-    OptionName names[8];
-    const char* refusal;
-};
-
-const OptionSpec kOptions[] = {
-    {"graph", &pfnl_handle::graph_mode, {{"auto", 1}, {"on", 2}, {"off", 0}}, "graph must be auto, on or off"},
-    {"conv3x3", &pfnl_handle::conv_algo, {{"winograd", 3}, {"winograd_ws", 3}, {"winograd_tile", 1}, {"direct", 0}, {"split16", 4}, {"auto", 5}},
-     "conv3x3 must be auto, split16, winograd, winograd_tile or direct"},
-    {"strict_fp32", &pfnl_handle::strict, {{"on", 1}, {"off", 0}}, "strict_fp32 must be on or off"},
-    {"small", &pfnl_handle::small_mode, {{"auto", 0}, {"on", 1}, {"off", 2}}, "small must be auto, on or off"},
-    {"split16_chain", &pfnl_handle::sf_chain, {{"on", 1}, {"off", 0}}, "split16_chain must be on or off"},
-    {"split16_c10", &pfnl_handle::sf_c10, {{"on", 1}, {"off", 0}}, "split16_c10 must be on or off"},
-    {"split16_mid", &pfnl_handle::sf_mid, {{"auto", 1}, {"off", 0}}, "split16_mid must be auto or off"},
-    {"split16_sf0", &pfnl_handle::sf0, {{"on", 1}, {"off", 0}}, "split16_sf0 must be on or off"},
-    {"split16_splitchains", &pfnl_handle::split_chains, {{"auto", 1}, {"off", 0}}, "split16_splitchains must be auto or off"},
-    {"split16_sf", &pfnl_handle::sf_path, {{"on", 1}, {"off", 0}}, "split16_sf must be on or off"},
-    {"conv2", &pfnl_handle::conv2_grouped, {{"grouped", 1}, {"split", 0}}, "conv2 must be grouped or split"},
-    {"split16_mfma", &pfnl_handle::s16_m16, {{"16", 1}, {"32", 0}}, "split16_mfma must be 16 or 32"},
-    {"bf16_mfma", &pfnl_handle::bf16_m16, {{"16", 1}, {"32", 0}}, "bf16_mfma must be 16 or 32"},
-    {"bf16_conv10", &pfnl_handle::bf16_fuse10, {{"fused", 1}, {"separate", 0}}, "bf16_conv10 must be fused or separate"},
-    {"precision", &pfnl_handle::bf16, {{"bf16", 1}, {"fp32", 0}}, "precision must be fp32 or bf16"},
-    {"merge1", &pfnl_handle::m1_algo, {{"auto", 0}, {"split16", 1}, {"winograd", 2}}, "merge1 must be auto, split16 or winograd"},
-    {"nl_type", &pfnl_handle::nl_type,
-     {{"auto", -1}, {"0", 0}, {"embedded_gaussian", 0}, {"1", 1}, {"gaussian", 1}, {"2", 2}, {"dot_product", 2}},
-     "nl_type: auto | 0 | 1 | 2 (nltype 3, 'concat', builds no graph in the reference either: utils.py:23)"},
-    {"small_c10", &pfnl_handle::small_c10, {{"on", 1}, {"off", 0}}, "small_c10 must be on or off"},
-    {"nonlocal", &pfnl_handle::nl_algo, {{"f32", 0}, {"split16", 1}, {"auto", 2}}, "nonlocal must be auto, f32 or split16"},
-    {"conv1x1", &pfnl_handle::conv1x1_algo, {{"stream", 1}, {"tiled", 0}, {"split16", 2}}, "conv1x1 must be split16, stream or tiled"},
-};
-
-const OptionSpec* find_option(const std::string& key) {
-    for (const OptionSpec& o : kOptions)
-        if (key == o.key) return &o;
-    return nullptr;
-}
-
 }  // namespace
 
 void pfnl_nl_fold_gw(const float* wg, const float* bg, const float* ww, const float* bw, int C, int CP, float* Wf, float* bf) {
@@ -1103,10 +875,10 @@ int pfnl_create(const pfnl_config* cfg, pfnl_handle** out) {
     pfnl_handle* h = new pfnl_handle();
     h->cfg = *cfg;
     h->ncu = pfnl::device_cu_count();
-    if (const char* e = std::getenv("PFNL_SF_MID_CHAINS")) h->sf_mid_chains = std::atoi(e);   // (threshold sweeps)
+    if (const char* e = std::getenv("PFNL_SF_MID_CHAINS")) h->opt.sf_mid_chains = std::atoi(e);   // (threshold sweeps)
     if (const char* e = std::getenv("PFNL_CONV3X3")) {
         const std::string v(e);
-        h->conv_algo = v == "direct" ? 0 : (v == "winograd_tile" ? 1 : (v == "split16" ? 4 : (v == "winograd" ? 3 : 5)));
+        h->opt.conv_algo = v == "direct" ? 0 : (v == "winograd_tile" ? 1 : (v == "split16" ? 4 : (v == "winograd" ? 3 : 5)));
     }
     // A BLOCKING stream: it is implicitly ordered with the legacy null stream (= torch's default stream) in both
     // directions, so host-pointer calls and graph replays on it are ordered with the caller's default-stream work.
@@ -1122,7 +894,7 @@ int pfnl_create(const pfnl_config* cfg, pfnl_handle** out) {
         return fail(PFNL_ERR_NOMEM, "allocation failed");
     }
     std::memset(h->rflag_host, 0, 64);
-    if (const char* e = std::getenv("PFNL_STRICT_FP32")) h->strict = std::string(e) != "0" && std::string(e) != "off";
+    if (const char* e = std::getenv("PFNL_STRICT_FP32")) h->opt.strict = std::string(e) != "0" && std::string(e) != "off";
     const int T = cfg->num_frames, C = 12 * T;
     add_expected(h, "conv0", 5, 3, 64);
     for (int i = 0; i < cfg->num_block; ++i) {
@@ -1205,7 +977,7 @@ int pfnl_set_option(pfnl_handle* h, const char* key, const char* value) {
     if (k == "nl_sub_sample") {
         const int n = atoi(v.c_str());
         if (n < 1 || n > 64) return fail(PFNL_ERR_INVALID, "nl_sub_sample: an integer >= 1");
-        h->nl_sub = n;
+        h->opt.nl_sub = n;
         return 0;
     }
     if (k == "bf16_nonlocal") {   // (the split-bf16 kernel of round 1 left the library in round 4: tools/experiments/nonlocal_bf16.hip)
@@ -1214,12 +986,7 @@ int pfnl_set_option(pfnl_handle* h, const char* key, const char* value) {
     }
     const OptionSpec* o = find_option(k);
     if (!o) return fail(PFNL_ERR_INVALID, "unknown option " + k);
-    for (const OptionName& n : o->names)
-        if (n.name && v == n.name) {
-            o->field.set(h, n.value);
-            return 0;
-        }
-    return fail(PFNL_ERR_INVALID, o->refusal);
+    return o->set_named(h->opt, v) ? 0 : fail(PFNL_ERR_INVALID, o->refusal);
 }
 
 // the CURRENT value of an option as pfnl_set_option would take it back - whatever set it (pfnl_set_option, an environment variable read by
@@ -1228,16 +995,10 @@ int pfnl_get_option(pfnl_handle* h, const char* key, char* buf, size_t buflen) {
     if (!h || !key || !buf || buflen < 1) return fail(PFNL_ERR_INVALID, "NULL argument");
     const std::string k(key);
     std::string v;
-    if (k == "nl_sub_sample") v = std::to_string(h->nl_sub);
+    if (k == "nl_sub_sample") v = std::to_string(h->opt.nl_sub);
     else if (k == "bf16_nonlocal") v = "f16";
-    else if (const OptionSpec* o = find_option(k)) {
-        const int cur = o->field.get(h);
-        for (const OptionName& n : o->names)
-            if (n.name && n.value == cur) {
-                v = n.name;
-                break;
-            }
-    } else return fail(PFNL_ERR_INVALID, "unknown option " + k);
+    else if (const OptionSpec* o = find_option(k)) v = o->name_in(h->opt);
+    else return fail(PFNL_ERR_INVALID, "unknown option " + k);
     if (v.size() + 1 > buflen) return fail(PFNL_ERR_INVALID, "buffer too small");
     std::memcpy(buf, v.c_str(), v.size() + 1);
     return 0;
@@ -1440,9 +1201,9 @@ int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes) {
              + 2 * B * T * P * 64                               // inp0, inp1
              + 3 * B * P * 64                                   // base, pb, merge (64 floats per pixel)
              + (size_t)B * T * P * 3 + (size_t)B * P * sc * sc * 3;   // stage_in, stage_out
-    if (h->bf16 || h->nl_algo != 0) f += (pfnl::nl_f16_scratch_halfs(B, (int)N) + 1) / 2;   // split K / V^T operands (bf16 or f16)
+    if (h->opt.bf16 || h->opt.nl_algo != 0) f += (pfnl::nl_f16_scratch_halfs(B, (int)N) + 1) / 2;   // split K / V^T operands (bf16 or f16)
     if (h->nl_theta) f += (size_t)B * N * CP;                   // projected queries (nltype 0 / 2)
-    if (h->nl_sub > 1) f += (size_t)B * ((H / 2) / h->nl_sub) * ((W / 2) / h->nl_sub) * CP;   // pooled keys
+    if (h->opt.nl_sub > 1) f += (size_t)B * ((H / 2) / h->opt.nl_sub) * ((W / 2) / h->opt.nl_sub) * CP;   // pooled keys
     const TrunkPlan pl = trunk_plan(h, B, H, W, H);
     f += pl.p10_floats + pl.inp0sf_floats + pl.c10part_floats;   // the buffers that depend on the launch plan
     *bytes = f * sizeof(float);
@@ -1452,24 +1213,9 @@ int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes) {
 int pfnl_plan(pfnl_handle* h, int B, int H, int W, char* buf, size_t buflen) {
     if (!h || !buf || buflen < 1) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "bad shape");
-    const TrunkPlan pl = trunk_plan(h, B, H, W, H);
-    static const char* const nln[] = {"general_f32", "split16", "f16", "f32"};
-    static const char* const a3[] = {"direct", "winograd_tile", "?", "winograd", "split16"};
-    static const char* const a1[] = {"tiled", "stream", "split16"};
-    char tmp[384];
-    if (pl.bf16)
-        std::snprintf(tmp, sizeof tmp, "%s launches_per_block=%d c1x1=%d precision=bf16 tiles=%d chains=%d whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d merge1=%s",
-                      pl.name, pl.launches_per_block, pl.c1x1_launches, pl.tiles8x32, pl.chains, pl.split_s ? pl.n_full : pl.chains, pl.split_s, pl.split_q,
-                      nln[pl.nl_family], pl.nl_fused_pack ? 1 : 0, pl.mfma, kMerge1Names[pl.merge1]);
-    else
-        std::snprintf(tmp, sizeof tmp, "%s launches_per_block=%d c1x1=%d precision=fp32 conv3x3=%s conv1x1=%s c10_fused=%d chain=%d sf0=%d strict=%d tiles=%d chains=%d "
-                      "whole_chains=%d split_parts=%d part_frames=%d nl=%s nl_pack_fused=%d mfma=%d c1_mfma=%d merge1=%s",
-                      pl.name, pl.launches_per_block, pl.c1x1_launches, pl.small ? "small" : a3[pl.algo < 0 || pl.algo > 4 ? 2 : pl.algo],
-                      a1[pl.conv1x1_algo < 0 || pl.conv1x1_algo > 2 ? 0 : pl.conv1x1_algo], pl.c10_fused ? 1 : 0, pl.chain ? 1 : 0, pl.sf0 ? 1 : 0,
-                      pl.strict ? 1 : 0, pl.tiles8x32, pl.chains, pl.split_s ? pl.n_full : pl.chains, pl.split_s, pl.split_q, nln[pl.nl_family],
-                      pl.nl_fused_pack ? 1 : 0, pl.mfma, pl.c1_mfma, kMerge1Names[pl.merge1]);
-    if (std::strlen(tmp) + 1 > buflen) return fail(PFNL_ERR_INVALID, "buffer too small");
-    std::strcpy(buf, tmp);
+    const std::string text = pfnl::plan_text(trunk_plan(h, B, H, W, H));
+    if (text.size() + 1 > buflen) return fail(PFNL_ERR_INVALID, "buffer too small");
+    std::memcpy(buf, text.c_str(), text.size() + 1);
     return 0;
 }
 
@@ -1620,8 +1366,8 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
     float* dout = (float*)out;
     const bool sync_call = !in_is_device || !out_is_device;     // a host pointer: the call returns with `out` filled
     const int slot = sync_call ? 0 : 1;                         // whose range flag the tail kernel of this call writes
-    const bool can_rerun = !h->bf16 && !(h->strict || !h->weights_f16_ok);
-    const bool want_graph = !h->prof && (h->graph_mode == 2 || (h->graph_mode == 1 && (size_t)B * T * H * W <= 65536));
+    const bool can_rerun = !h->opt.bf16 && !(h->opt.strict || !h->weights_f16_ok);
+    const bool want_graph = !h->prof && (h->opt.graph_mode == 2 || (h->opt.graph_mode == 1 && (size_t)B * T * H * W <= 65536));
     // stream == NULL: device-pointer calls are launched on the LEGACY NULL STREAM itself (what a caller that passes
     // torch.cuda.current_stream().cuda_stream == 0 means: same-stream ordering with everything it has enqueued and will
     // enqueue); host-pointer calls and graph replays (a capture cannot run on the null stream) use the handle's stream.
@@ -1704,7 +1450,7 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
                     } else if (int e2 = stage_d2h(h, out, h->stage_out.p, n_out * sizeof(float), s)) {
                         return e2;
                     }
-                } else if (flagged && h->bf16) {
+                } else if (flagged && h->opt.bf16) {
                     return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
                 }
             } else if (!stream) {
@@ -1749,7 +1495,7 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
             } else {
                 HIPCHK(hipStreamSynchronize(s));
             }
-        } else if (flagged && h->bf16) {
+        } else if (flagged && h->opt.bf16) {
             return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
         }
     }
@@ -1786,7 +1532,7 @@ int pfnl_sync(pfnl_handle* h) {
     // (a device-pointer call on a stream of the caller's: the caller synchronises that stream before pfnl_sync)
     int flagged = 0;
     if (int e = range_flag_take(h, 1, &flagged)) return e;
-    if (flagged) return fail(PFNL_ERR_RANGE, h->bf16 ? RANGE_MSG_BF16 : RANGE_MSG_FP32);
+    if (flagged) return fail(PFNL_ERR_RANGE, h->opt.bf16 ? RANGE_MSG_BF16 : RANGE_MSG_FP32);
     return 0;
 }
 
@@ -1929,7 +1675,7 @@ int pfnl_debug_tap(pfnl_handle* h, const char* name, float* host_dst, size_t cou
     } else if (n == "trunk") {
         need = (size_t)B * T * H * W * 64;
         src = h->inp0.p;
-        if (h->bf16) {                                              // bf16 trunk: cast on demand
+        if (h->opt.bf16) {                                              // bf16 trunk: cast on demand
             if (h->scratch.ensure(need)) return fail(PFNL_ERR_NOMEM, "scratch allocation failed");
             HIPCHK(pfnl::launch_cast_bf16_f32(reinterpret_cast<const uint16_t*>(h->inp0.p), h->scratch.p, need, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));

@@ -12,6 +12,9 @@ namespace pfnl {
 
 constexpr int CHAIN_TH = 8, CHAIN_TW = 32;                          // the spatial tile of a chain
 
+// the grid of the persistent launches: whole XCDs (workgroup b runs on XCD b & 7), at least 8 - what split chains' n_full is a multiple of
+inline int persistent_grid(int ncu) { return ncu >= 8 ? ncu / 8 * 8 : 8; }
+
 // chain `ch` -> item = clip * T + f (f: a frame of the clip; T = 1, f = 0: the clip) and the origin of its tile (per_item = tiles_x * tiles_y
 // chains per clip)
 __host__ __device__ __forceinline__ void chain_tile(int ch, int per_item, int tiles_x, int T, int f, int& item, int& y0, int& x0) {
@@ -78,7 +81,7 @@ struct ChainShare {
     __host__ __device__ __forceinline__ int end_pos(int k, int L) const { return in_part(k) ? sp_f1 + LEAD : L; }
 };
 
-// The geometry every split launch checks: n_full a multiple of `grid` (persistent_grid, common.h) below the chain count, 2 <= split_s <= 7 parts
+// The geometry every split launch checks: n_full a multiple of `grid` (persistent_grid) below the chain count, 2 <= split_s <= 7 parts
 // (7: what the finalize kernels add up) of <= split_q frames that are all non-empty and together the T frames, one part per workgroup.
 inline bool split_geometry_ok(int H, int W, int items, int T, int n_full, int split_s, int split_q, int grid) {
     if (T < 1 || grid < 1) return false;

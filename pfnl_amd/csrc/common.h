@@ -6,6 +6,8 @@
 
 #include <atomic>
 
+#include "chain_order.h"   // persistent_grid: the grid of the persistent launches
+
 namespace pfnl {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -48,9 +50,6 @@ inline int device_cu_count() {                                      // CUs of th
     }
     return n;
 }
-
-// the grid of the persistent launches: whole XCDs (workgroup b runs on XCD b & 7), at least 8 - what split chains' n_full is a multiple of
-inline int persistent_grid(int ncu) { return ncu >= 8 ? ncu / 8 * 8 : 8; }
 
 __device__ __forceinline__ float lrelu(float v) { return fmaxf(v, 0.2f * v); }  // tf.nn.leaky_relu
 

@@ -264,14 +264,18 @@ class PFNLEngine:
     def plan(self, B: int, H: int, W: int) -> Dict[str, object]:
         """The launch plan of the progressive-fusion trunk for this shape under the current options (pfnl_plan: the one statement of the
         dispatch rule).  {"structure": "chain2_sf0", "launches_per_block": 2, "conv3x3": "split16", "sf0": 1, ...}."""
-        buf = C.create_string_buffer(512)
-        _capi.check(self._lib.pfnl_plan(self._h, B, H, W, buf, 512))
-        toks = buf.value.decode().split()
+        toks = self.plan_text(B, H, W).split()
         d: Dict[str, object] = {"structure": toks[0]}
         for t in toks[1:]:
             k, v = t.split("=", 1)
             d[k] = int(v) if v.lstrip("-").isdigit() else v
         return d
+
+    def plan_text(self, B: int, H: int, W: int) -> str:
+        """The string pfnl_plan returns, as it is."""
+        buf = C.create_string_buffer(512)
+        _capi.check(self._lib.pfnl_plan(self._h, B, H, W, buf, 512))
+        return buf.value.decode()
 
     def get_option(self, key: str) -> str:
         """The CURRENT value of an option (pfnl_get_option): whatever set it - set_option, the environment at pfnl_create, the default."""

@@ -770,7 +770,7 @@ def test_split_chains_random_geometries():
 
 
 def test_plan_is_what_runs():
-    """pfnl_plan is the ONE statement of the trunk's dispatch rule (capi.hip trunk_plan; reference model/pfnl.py:65-71): for every structure
+    """pfnl_plan is the ONE statement of the trunk's dispatch rule (launch_plan.h trunk_plan; reference model/pfnl.py:65-71): for every structure
     the launches the profiler counts per block equal the plan's, in both precisions and under the options that change it, and so do convmerge1's
     algorithm (merge1) and its launches; the thresholds it prints (tiles, chains) are the shape's; pfnl_get_option reads back what set_option / the defaults put there."""
     geom = PFNLGeometry(num_block=2)
@@ -808,6 +808,26 @@ def test_plan_is_what_runs():
     with pytest.raises(Exception):
         eng.get_option("no_such_option")
     eng.close()
+
+
+def test_plan_matches_host_rule(tmp_path):
+    """The library's pfnl_plan is launch_plan.h's rule at THIS device's CU count, whatever that is: the host driver of tests/test_plan_host.py
+    (where the rule is pinned at 256 CUs and its invariants at every count) gives the same text - small, mid, whole, cut and ragged shapes
+    (reference model/pfnl.py:65-71), the defaults, strict_fp32 and bf16.  Handles only, no forward."""
+    import plan_driver
+    run = plan_driver.build(tmp_path)
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    shapes = [(1, 32, 32), (1, 128, 128), (4, 128, 128), (5, 128, 128), (6, 90, 98), (1, 180, 318)]
+    queries, texts = [], []
+    for opts in ((), (("strict_fp32", "on"),), (("precision", "bf16"),)):
+        eng = PFNLEngine(PFNLGeometry(), device=0)
+        for k, v in opts:
+            eng.set_option(k, v)
+        for B, H, W in shapes:
+            texts.append(eng.plan_text(B, H, W))
+            queries.append(" ".join([str(ncu), "7", str(B), str(H), str(W), str(H), str(plan_driver.nl_fits_of(texts[-1]))] + [f"{k}={v}" for k, v in opts]))
+        eng.close()
+    assert [p for p, _ in run(queries)] == texts
 
 
 @pytest.mark.parametrize("T,scale,nb,B,H,W", [(7, 4, 3, 1, 32, 32), (5, 2, 2, 1, 64, 64), (7, 4, 2, 2, 18, 40)])
