@@ -4,6 +4,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py ... --dump-outputs DIR      # + the last timed step's SR frames as DIR/<name>.npy (float32)
+    python bench.py ... --full                  # + everything below that takes runs of its own
 
 Workload = BASELINE.json configs[1]: PFNL 4xSR, 7 LR frames 128x128 -> one 512x512 HR frame per clip,
 batch 4 clips per GPU, fp32, synthetic U[0,1) clips and seeded Xavier weights (no checkpoint/dataset
@@ -11,18 +12,20 @@ can be fetched).  A "step" = one pfnl_forward over the rank's batch with the inp
 HBM.  Clips are independent, so ranks share nothing on the data path (weak scaling: 4 clips per GPU);
 RCCL carries the weight replica (pfnl_comm_bcast_weights), the barriers and the max-over-ranks time only.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE JSON line (rank 0) with the contract fields plus
+`roofline` (it rides in the timed steps).  `--full` adds what costs runs of its own: the per-class breakdown pass (`roofline_nl`,
+`roofline_hbm_classes`, the whole of `kernel_ms_per_step`; the small shapes' `roofline`), `sustained`, `secondary` and `cpu_baseline`.
   roofline      dominant kernel class (the 3x3 64->64 convolutions), timed live with HIP events on the launch stream INSIDE the timed
                 steps (the launches of one of the 20 identical progressive-fusion blocks: 3 events per forward; the per-class
-                breakdown of the whole forward comes from a separate untimed pass);
+                breakdown of the whole forward comes from a separate untimed pass: --full);
                 frac = ALGORITHMIC work (bytes or FLOPs the reference graph needs, shared-base split) / time / the binding peak;
                 what the kernel executes on the matrix pipe (3 f16 MFMAs per product block) is in mfma_executed_*, next to the
                 ceiling the chip sustains on that instruction stream under its power cap (tools/ubench/conv_core)
-  sustained     >= 2 s of back-to-back steps (no events): ms/step, so clock droop is visible
-  secondary     measured in the same process after the headline: configs[3] (1080p bf16), one Vid4 window, configs[0], configs[4]
+  sustained     (--full) >= 2 s of back-to-back steps (no events): ms/step, so clock droop is visible
+  secondary     (--full) measured in the same process after the headline: configs[3] (1080p bf16), one Vid4 window, configs[0], configs[4]
                 (2x, T=5, 64x64) and the HOST-pointer configs[1] path (H2D + D2H inside, what the reference's
                 sess.run timing covers, model/pfnl.py:249-253)
-  cpu_baseline  (N=1) the torch-CPU fp32 oracle = the stand-in for the reference's TF1 CPU path, on a bounded sample.
+  cpu_baseline  (--full, N=1) the torch-CPU fp32 oracle = the stand-in for the reference's TF1 CPU path, on a bounded sample.
 """
 import argparse
 import hashlib
@@ -508,8 +511,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads and the sustained run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed per-class breakdown pass (roofline_nl, "
+                         "roofline_hbm_classes, the whole kernel_ms_per_step; the small shapes' roofline), the sustained run with the "
+                         "power sampler, the secondary workloads and the CPU baseline.  Off by default: a plain run warms up, times "
+                         "the steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads and the sustained run")
     ap.add_argument("--conv3x3", choices=["auto", "split16", "winograd", "winograd_tile", "direct"], default=None,
                     help="override the 3x3 conv algorithm (default auto: split16 for launches of >= 200 tiles, the small-shape kernels below)")
     ap.add_argument("--conv1x1", choices=["split16", "stream", "tiled"], default=None, help="override the conv10_i algorithm")
@@ -709,7 +717,7 @@ def main():
         dumped = dump_output(out, args.dump_outputs, "output" if world == 1 else "output_rank%d" % rank, DUMP_LIMIT_BYTES // world)
     prof = eng.profile_read()
     prof_all, n_all = None, 0
-    if prof_mode == 3 or (small_shape and not args.no_profile and not args.full_profile):
+    if args.full and (prof_mode == 3 or (small_shape and not args.no_profile and not args.full_profile)):
         n_all = max(3, args.steps // 2)
         eng.profile_reset()
         eng.profile(4 if small_shape else 2)
@@ -739,7 +747,10 @@ def main():
     # sampled mode: the two classes inside the PF blocks were timed in ceil(nb/4) of the nb blocks
     nb = geom.num_block
     scale_blk = nb / float(blocks_sampled(nb)) if prof_mode == 2 and nb else 1.0
-    if prof_all is None:
+    if prof_all is None and prof_mode == 3:
+        # a plain run: the one block of the timed steps (x nb) is all that carried events - the other classes are --full's
+        breakdown = {n: round(v["ms"] / args.steps * nb, 4) for n, v in prof.items() if v["launches"]}
+    elif prof_all is None:
         breakdown = {n: round(v["ms"] / args.steps * (scale_blk if n in ("conv3x3", "conv1x1") else 1.0), 4)
                      for n, v in prof.items()}
     else:
@@ -757,7 +768,7 @@ def main():
     res = {
         "metric": "HR frames/sec at %dxSR, %d-frame %dx%d->%dx%d" % (wl["scale"], T_WL, H, W, wl["scale"] * H, wl["scale"] * W),
         "value": round(value, 3), "unit": "HR frames/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_s": PREWARM_S, "ms_per_step": round(ms_per_step, 4),
+        "n_gpus": world, "full": bool(args.full), "steps": args.steps, "warmup": args.warmup, "prewarm_s": PREWARM_S, "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "bf16" if bf16 else "f32",
         "data": "synthetic",
         "config": {"workload": wl["label"] % (B_PER_GPU, "bf16 trunk" if bf16 else "fp32",
@@ -768,7 +779,7 @@ def main():
                    "weights": "synthetic Xavier (seed 0)", "input": "resident in HBM", "conv3x3": algo, "plan": plan["structure"], "mfma": plan.get("mfma")},
         "roofline": roof,
         "roofline_nl": nonlocal_roofline(geom, breakdown, B_PER_GPU, H, W, bf16, plan),
-        "roofline_hbm_classes": hbm_class_rooflines(geom, breakdown, B_PER_GPU, H, W, plan=plan),
+        "roofline_hbm_classes": hbm_class_rooflines(geom, breakdown, B_PER_GPU, H, W, plan=plan) if (args.full or prof_mode == 1) else None,
         "whole_forward": {"tflops_ref_graph": round(f_ref / (ms_per_step * 1e-3) / 1e12, 2),
                           "tflops_direct_shared_base": round(f_exec / (ms_per_step * 1e-3) / 1e12, 2),
                           "kernel_ms_per_step": breakdown},
@@ -776,7 +787,7 @@ def main():
     if dumped is not None:
         res["dump_outputs"] = dict(dumped, dir=os.path.abspath(args.dump_outputs))
 
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # ---- sustained: >= 2 s of back-to-back steps, no events (clock droop shows up as ms/step above the headline's)
         n_sus = max(args.steps, int(2.2e3 / max(ms_per_step, 1e-3)) + 1)
         sampler = PowerSampler(local_dev) if rank == 0 else None       # package power / shader clock while the sustained run is under way
@@ -803,9 +814,9 @@ def main():
             # energy per HR frame = package power x time per step / clips per step, both from the sustained run: the split-f16 launches sit on
             # the package power cap, so a kernel change is a change of THIS number or it is nothing
             res["joules_per_frame"] = round(res["power"]["package_w"] * (el / n_sus) / B_PER_GPU, 4)
-    if rank == 0 and world == 1 and not args.no_secondary and args.workload == "cfg2" and not bf16 and not args.strong and not args.clips_per_gpu:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and args.workload == "cfg2" and not bf16 and not args.strong and not args.clips_per_gpu:
         res["secondary"] = secondary_workloads(eng, geom, weights, local_dev, dev, x, out)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("cfg2", "cfg0"):   # (the 1080p oracle needs minutes per pass; configs[4] is build-defined)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.workload in ("cfg2", "cfg0"):   # (the 1080p oracle needs minutes per pass; configs[4] is build-defined)
         sample = synth.uniform_clips(B_PER_GPU, T, H, W, seed=1234)     # the GPU line's batch (same seed: the same clips)
         res["cpu_baseline"] = cpu_baseline(weights, sample, H, W)
         res["gpu_over_cpu"] = round(value / res["cpu_baseline"]["value"], 1)

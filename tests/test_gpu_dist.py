@@ -107,7 +107,7 @@ def _bench_two_gloo_ranks(*extra):
 def test_bench_two_ranks_cfg0_weak():
     """north_star's second size (7x32x32 -> 128x128, BASELINE.json configs[0]) on N ranks: one clip per rank, its own roofline object
     and the road the exchanges took named in the line (VERDICT r3 next #3)."""
-    rec = _bench_two_gloo_ranks("--workload", "cfg0")
+    rec = _bench_two_gloo_ranks("--workload", "cfg0", "--full")          # (a small shape's roofline comes from the breakdown pass: --full)
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and rec["config"]["clips_per_gpu"] == 1 and rec["config"]["global_batch"] == 2
     assert "32x32->128x128" in rec["metric"] and "configs[0]" in rec["config"]["workload"]
     assert rec["roofline"] and rec["roofline"]["frac"] > 0 and rec["config"]["conv3x3"] == "small"
@@ -131,6 +131,23 @@ def test_bench_two_ranks_strong_scaling():
     assert one.returncode == 0, one.stderr[-2000:]
     r1 = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][0])
     assert r1["scaling"] == "strong" and r1["n_gpus"] == 1 and r1["config"]["global_batch"] == 6 and r1["config"]["clips_per_gpu"] == 6
+
+
+def test_bench_plain_run_is_lean():
+    """A plain `bench.py` run does what its headline needs and no more: the line carries the contract fields and says `full: false`;
+    the sustained run, the secondary workloads, the CPU baseline and the figures of the breakdown pass are `--full`'s."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfg0", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["full"] is False and rec["steps"] == 3 and rec["warmup"] == 1
+    assert rec["value"] > 0 and rec["unit"] == "HR frames/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert abs(rec["value"] - 1 / (rec["ms_per_step"] * 1e-3)) < 1e-2 * rec["value"]
+    for k in ("sustained", "power", "joules_per_frame", "secondary", "cpu_baseline", "gpu_over_cpu"):
+        assert k not in rec, k
+    assert rec["roofline_nl"] is None and rec["roofline_hbm_classes"] is None
 
 
 def test_bench_self_spawn():

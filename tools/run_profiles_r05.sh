@@ -49,5 +49,5 @@ rm -rf $o/prof_cfg0 $o/prof_cfg5 $o/prof_bf16 $o/prof_ws $o/raw/pmc_1 $o/raw/pmc
 du -sh $o/raw
 tools/ubench/mfma_agpr_src > $o/${tag}_ubench_mfma_agpr_src.txt 2>&1
 cp $o/${tag}_traffic_split16.json $o/${tag}_traffic_bf16.json $o/${tag}_pmc_nl.json profiles/    # (on the GPU box: the bench line below reports them)
-python bench.py --steps 20 --warmup 5 > $o/${tag}_bench.json 2> $o/bench.err
+python bench.py --full --steps 20 --warmup 5 > $o/${tag}_bench.json 2> $o/bench.err
 head -8 $o/${tag}_kernel_stats.md | cut -c1-160; cat $o/${tag}_pmc_nl.json | head -12; tail -c 300 $o/bench.err

@@ -1,8 +1,10 @@
-# rocprofv3 kernel trace + stats of the default bench command; DB under gpurun_out/prof_<tag>/
+# rocprofv3 kernel trace + stats of a plain bench run (warm-up + timed steps of the headline workload only); DB under $PROFILE_OUT/prof_<tag>/
 export TMPDIR=/tmp
 tag=${1:-x}
-rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${tag} -o p -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline $BENCH_ARGS > gpurun_out/prof_${tag}_bench.log 2>&1
-db=$(find gpurun_out/prof_${tag} -name "*.db" | head -1)
-python tools/rocprof_summary.py $db gpurun_out/prof_${tag}_summary.md
-tail -1 gpurun_out/prof_${tag}_bench.log > gpurun_out/prof_${tag}_bench.json
-head -20 gpurun_out/prof_${tag}_summary.md
+o=${PROFILE_OUT:-profile_out}
+mkdir -p $o
+rocprofv3 --kernel-trace --stats -d $o/prof_${tag} -o p -- python bench.py --steps 5 --warmup 2 $BENCH_ARGS > $o/prof_${tag}_bench.log 2>&1
+db=$(find $o/prof_${tag} -name "*.db" | head -1)
+python tools/rocprof_summary.py $db $o/prof_${tag}_summary.md
+tail -1 $o/prof_${tag}_bench.log > $o/prof_${tag}_bench.json
+head -20 $o/prof_${tag}_summary.md
