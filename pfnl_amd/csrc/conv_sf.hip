@@ -767,16 +767,31 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain_kernel(ConvSpl
         unit(std::integral_constant<int, 0>{});
         unit(std::integral_constant<int, 1>{});
     }
-    // ---- the last tile (a frame tile): both rows
+    // ---- the last tile (a frame tile): both rows.  No next tile carries this epilogue: all 2 x 4 quarters are requested before the first store (the operand
+    // and accumulator registers are dead here), so the launch ends one residual round trip after the last MFMA instead of four, each of which also waited for
+    // the stores in front of it (stores count in vmcnt).  A lane reads exactly the addresses it writes (out == resid); the stores - the split-format copy's
+    // among them - leave in the order they always did.  (nothing pending: the resources are empty - zeros read, stores dropped)
+    {
+        __amdgpu_buffer_rsrc_t rsT[2];
+        [[maybe_unused]] __amdgpu_buffer_rsrc_t rsST[2];
+        float rt[2][4][4];
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        row_setup(n);
+        for (int n = 0; n < 2; ++n) {
+            row_setup(n);
+            rsT[n] = rsO;
+            if constexpr (SFCOPY) rsST[n] = rsS;
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            quarter_request(2 * h2);
-            quarter_request(2 * h2 + 1);
-            quarter_finish(n, 2 * h2);
-            quarter_finish(n, 2 * h2 + 1);
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    rt[n][q][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsT[n], evoff + j * 256, q * 2048, 0));
+        }
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            rsO = rsT[n];
+            if constexpr (SFCOPY) rsS = rsST[n];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) quarter_finish_with(n, q, rt[n][q]);
         }
     }
 #undef SFC_DMA_HALO
@@ -1109,14 +1124,29 @@ __global__ __launch_bounds__(SF_THREADS, 1) void conv3x3_sf_chain16_kernel(ConvS
         unit(std::integral_constant<int, 0>{});
         unit(std::integral_constant<int, 1>{});
     }
-    // ---- the last tile (a frame tile): both rows
+    // ---- the last tile (a frame tile): both rows.  No next tile carries this epilogue, and every workgroup gets here at about the same time: the launch ends
+    // one residual round trip after the last MFMA, not eight.  All 2 x 4 quarters are requested before the first store (the operand and accumulator registers are
+    // dead here: 32 values fit) - request + finish per quarter made every quarter wait for its own loads AND for the previous quarter's write-through stores
+    // (stores count in vmcnt).  A lane reads exactly the addresses it writes, so loads in front of other quarters' stores are safe with out == resid; the
+    // stores leave in the order they always did.  (nothing pending: both resources are empty - zeros read, stores dropped)
+    {
+        __amdgpu_buffer_rsrc_t rsT[2];
+        sff4 rt[2][4];
 #pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        row_setup(n);
+        for (int n = 0; n < 2; ++n) {
+            row_setup(n);
+            rsT[n] = rsO;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            quarter_request(q);
-            quarter_finish(n, q);
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    rt[n][q][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsT[n], evoff + j * 256, (q >> 1) * 4096 + (q & 1) * 64, 0));
+        }
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            rsO = rsT[n];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) quarter_finish_with(n, q, rt[n][q]);
         }
     }
 #undef SFC_DMA_HALO
