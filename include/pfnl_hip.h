@@ -284,6 +284,25 @@ enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2 };
 enum { PFNL_MATRIX_BT601 = 0, PFNL_MATRIX_BT709 = 1 };
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range);
 int pfnl_yuv_coefficients(int matrix, int full_range, int32_t out[15]);    /* y0, 9 encode, 5 decode; no device needed */
+/* OUTPUT SIZE (off by default; then the session is what it always was).  The network's factor is fixed and display and encode rasters are
+ * not (480p -> 1080p is 2.25 x, 720p -> 2160p is 3 x): with a size set the session resamples each batch's uint8 RGB frames on the device,
+ * behind the quantisation and ahead of the YUV conversion, so a delivered frame is a pure function of the bytes the plain session
+ * delivers.  The arithmetic is integer and stated once on the host, pfnl_amd/resize.py: a separable Keys cubic (a = -1/2) whose support
+ * widens by in / out when the raster shrinks; per axis and output index a run of taps with 14 fractional bits that sums to 2^14 exactly,
+ * indices clamped to the frame; horizontal pass first, h = (sum c p + 2^7) >> 8, unclipped; then clip((sum c h + 2^19) >> 20, 0, 255).
+ *   pfnl_stream_resize: pop delivers out_H x out_W pixels (out_H*out_W*3 bytes, or *3/2 in a YUV output format: then both must be even -
+ *     whichever of pfnl_stream_resize and pfnl_stream_format comes second checks against the other's setting, PFNL_ERR_INVALID); 0, 0 is off.
+ *     Per axis ceil(n_in / 4) <= n_out <= 2 n_in with n_in = scale * H or scale * W, and n_in, n_out <= 16384, else PFNL_ERR_INVALID.
+ *     Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); the setting survives pfnl_stream_reset.
+ *     Builds and uploads the tap tables and allocates the resized batches (PFNL_ERR_NOMEM: nothing half-made stays and the setting is
+ *     unchanged); recomputed batches take the same route; pfnl_stream_close frees everything.
+ *   pfnl_resize_max_taps / pfnl_resize_taps: one axis of the table, in exact integers, no device needed: output o =
+ *     sum over k < count[o] of coef[o * ntaps + k] * in[first[o] + k] / 2^14; coef is [n_out][ntaps], zero behind count[o], with ntaps the
+ *     longest run, as pfnl_resize_max_taps reports it.  Sizes outside the limits above and NULL: PFNL_ERR_INVALID.
+ * Out of scope: other filters, cropping, letterboxing and aspect handling, resampling ahead of the quantisation, the input side. */
+int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W);
+int pfnl_resize_max_taps(int n_in, int n_out, int* ntaps);
+int pfnl_resize_taps(int n_in, int n_out, int32_t* first /*[n_out]*/, int32_t* count /*[n_out]*/, int16_t* coef /*[n_out][ntaps]*/);
 
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
@@ -558,6 +577,11 @@ int pfnl_op_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene
  * H / W, n < 1, an unknown fmt / matrix / full_range and fmt = PFNL_PIX_RGB24: PFNL_ERR_INVALID before any HIP call. */
 int pfnl_op_yuv420_to_rgb_u8(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, void* stream);
 int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, void* stream);
+/* The session's resampler (pfnl_stream_resize; the rule: pfnl_amd/resize.py).  in [n][H][W][3] uint8 -> out [n][oH][oW][3] uint8, device
+ * pointers, asynchronous on stream up to the hook's own synchronisation (it uploads the tap tables and frees them on return).  One launch
+ * does both passes through an int16 LDS tile; any alignment (16-byte stores where oW is a multiple of 16 and out is aligned, single bytes
+ * otherwise).  NULL, n < 1 and sizes outside pfnl_resize_taps' limits: PFNL_ERR_INVALID before any HIP call. */
+int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, uint8_t* out, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

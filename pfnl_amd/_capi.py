@@ -111,6 +111,10 @@ SIGNATURES = {
     "pfnl_yuv_coefficients": (_i, [_i, _i, C.POINTER(C.c_int32)]),
     "pfnl_op_yuv420_to_rgb_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_op_rgb_to_yuv420_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_stream_resize": (_i, [_vp, _i, _i]),
+    "pfnl_resize_max_taps": (_i, [_i, _i, C.POINTER(_i)]),
+    "pfnl_resize_taps": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]),
+    "pfnl_op_resize_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_op_scene_sad_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pfnl_op_gather_windows_u8_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),

@@ -955,6 +955,38 @@ int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_r
     return 0;
 }
 
+int pfnl_resize_max_taps(int n_in, int n_out, int* ntaps) {
+    if (!ntaps) return fail(PFNL_ERR_INVALID, "NULL argument");
+    pfnl::ResizeAxis t;
+    std::string why;
+    if (!pfnl::resize_axis(n_in, n_out, &t, &why)) return fail(PFNL_ERR_INVALID, why);
+    *ntaps = t.ntaps;
+    return 0;
+}
+
+int pfnl_resize_taps(int n_in, int n_out, int32_t* first, int32_t* count, int16_t* coef) {
+    if (!first || !count || !coef) return fail(PFNL_ERR_INVALID, "NULL argument");
+    pfnl::ResizeAxis t;
+    std::string why;
+    if (!pfnl::resize_axis(n_in, n_out, &t, &why)) return fail(PFNL_ERR_INVALID, why);
+    std::memcpy(first, t.first.data(), t.first.size() * sizeof(int32_t));
+    std::memcpy(count, t.count.data(), t.count.size() * sizeof(int32_t));
+    std::memcpy(coef, t.coef.data(), t.coef.size() * sizeof(int16_t));
+    return 0;
+}
+
+int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, uint8_t* out, void* stream) {
+    if (!in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(PFNL_ERR_INVALID, "resize: n >= 1");
+    pfnl::ResizePlan plan;
+    std::string why;
+    if (!pfnl::resize_plan(H, W, oH, oW, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
+    OpStage st(stream);
+    const int32_t* blob = st.upload(plan.blob);
+    st.run([&] { return pfnl::launch_resize_u8(in, out, plan, blob, n, st.s); });
+    return st.finish("resize op: ");
+}
+
 // every refusal comes before any HIP call: the argument checks work without a device
 static int score_geometry_refused(int F, int H, int W) {
     if (F < 1 || F > 65535) return fail(PFNL_ERR_INVALID, "score: F must be in 1 .. 65535");

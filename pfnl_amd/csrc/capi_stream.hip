@@ -58,7 +58,15 @@ struct pfnl_stream {
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
     pfnl::YuvCoef coef{};
     uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel
-    uint8_t* yout[2] = {nullptr, nullptr};            // [batch][sH*sW*3/2] each, beside out[]
+    uint8_t* yout[2] = {nullptr, nullptr};            // [batch][oH*oW*3/2] each, beside out[]: where present, sized for the current output
+    // output size (pfnl_stream_resize): out[] stays the network's raster; a batch is resampled behind its quantisation into rout[], and
+    // that is what the YUV conversion reads and pop copies - allocated by the call that sets a size, freed with the session
+    pfnl::ResizePlan rplan;                           // rplan.oH = 0: off
+    int32_t* rtab = nullptr;                          // rplan.blob on the device
+    uint8_t* rout[2] = {nullptr, nullptr};            // [batch][oH][oW][3] each
+    int out_h() const { return rplan.oH ? rplan.oH : scale * H; }
+    int out_w() const { return rplan.oW ? rplan.oW : scale * W; }
+    size_t out_bytes() const { return (size_t)out_h() * out_w() * 3; }   // one delivered frame as RGB
 };
 
 namespace {
@@ -82,9 +90,11 @@ int enqueue(pfnl_stream* s, const Batch& b) {
     }
     if (int e = pfnl_forward(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->s)) return e;
     HIPCHK(pfnl::launch_quantise_u8(s->sr, s->out[b.slot], (size_t)b.count * s->sr_bytes, s->s));
-    if (s->out_fmt != PFNL_PIX_RGB24)                 // (a replay takes the same route: pop stays a copy)
-        HIPCHK(pfnl::launch_rgb_to_yuv420_u8(s->out[b.slot], s->yout[b.slot], s->out_fmt == PFNL_PIX_NV12, s->coef, b.count, s->scale * s->H,
-                                             s->scale * s->W, s->s));
+    if (s->rplan.oH)                                  // (a replay takes the same route: pop stays a copy)
+        HIPCHK(pfnl::launch_resize_u8(s->out[b.slot], s->rout[b.slot], s->rplan, s->rtab, b.count, s->s));
+    if (s->out_fmt != PFNL_PIX_RGB24)
+        HIPCHK(pfnl::launch_rgb_to_yuv420_u8(s->rplan.oH ? s->rout[b.slot] : s->out[b.slot], s->yout[b.slot], s->out_fmt == PFNL_PIX_NV12,
+                                             s->coef, b.count, s->out_h(), s->out_w(), s->s));
     HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
     return 0;
 }
@@ -198,6 +208,7 @@ void release(pfnl_stream* s) {
     for (int i = 0; i < 2; ++i) {
         if (s->out[i]) (void)hipFree(s->out[i]);
         if (s->yout[i]) (void)hipFree(s->yout[i]);
+        if (s->rout[i]) (void)hipFree(s->rout[i]);
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
     }
     for (int i = 0; i < 2; ++i)
@@ -205,6 +216,7 @@ void release(pfnl_stream* s) {
     if (s->scene_first) (void)hipFree(s->scene_first);
     if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
     if (s->yin) (void)hipFree(s->yin);
+    if (s->rtab) (void)hipFree(s->rtab);
     if (s->ring) (void)hipFree(s->ring);
     if (s->win) (void)hipFree(s->win);
     if (s->sr) (void)hipFree(s->sr);
@@ -345,8 +357,8 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
     if (!b.checked)
         if (int e = check_batch(s, b)) return e;
     const bool yuv_out = s->out_fmt != PFNL_PIX_RGB24;
-    const size_t bytes = yuv_out ? s->sr_bytes / 2 : s->sr_bytes;
-    const uint8_t* const src = (yuv_out ? s->yout[b.slot] : s->out[b.slot]) + (size_t)(s->delivered - b.first) * bytes;
+    const size_t bytes = yuv_out ? s->out_bytes() / 2 : s->out_bytes();
+    const uint8_t* const src = (yuv_out ? s->yout[b.slot] : (s->rplan.oH ? s->rout[b.slot] : s->out[b.slot])) + (size_t)(s->delivered - b.first) * bytes;
     if (is_device) {
         HIPCHK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, s->s));   // ordered like the caller's own work on that stream
     } else {
@@ -414,6 +426,8 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
     pfnl::YuvCoef coef;
     if (!pfnl::yuv_coefficients(matrix, full_range, &coef))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (out_fmt != PFNL_PIX_RGB24 && ((s->out_h() | s->out_w()) & 1))
+        return fail(PFNL_ERR_INVALID, "format: a YUV output needs an even output size (pfnl_stream_resize)");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     const bool need_in = in_fmt != PFNL_PIX_RGB24 && !s->yin, need_out = out_fmt != PFNL_PIX_RGB24 && !s->yout[0];
     if (need_in || need_out) {
@@ -422,7 +436,7 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
         if (need_in) ok = hipMalloc(reinterpret_cast<void**>(&s->yin), s->lr_bytes / 2) == hipSuccess;
         if (need_out)
             for (int i = 0; i < 2; ++i)
-                ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout[i]), (size_t)s->batch * (s->sr_bytes / 2)) == hipSuccess;
+                ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout[i]), (size_t)s->batch * (s->out_bytes() / 2)) == hipSuccess;
         if (!ok) {                                    // nothing half allocated stays behind, and the setting is unchanged
             (void)hipGetLastError();
             if (need_in && s->yin) (void)hipFree(s->yin), s->yin = nullptr;
@@ -436,6 +450,55 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
     s->in_fmt = in_fmt;
     s->out_fmt = out_fmt;
     s->coef = coef;
+    return 0;
+}
+
+int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    const bool on = out_H != 0 || out_W != 0;
+    pfnl::ResizePlan plan;                            // (off: oH = oW = 0, no table)
+    if (on) {
+        std::string why;
+        if (!pfnl::resize_plan(s->scale * s->H, s->scale * s->W, out_H, out_W, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
+        if (s->out_fmt != PFNL_PIX_RGB24 && ((out_H | out_W) & 1))
+            return fail(PFNL_ERR_INVALID, "resize: a YUV output format needs an even output size (pfnl_stream_format)");
+    }
+    if (s->pushed) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (!on && !s->rplan.oH) return 0;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->s));               // (a dropped sequence's device-pointer pops may still read what is freed below)
+    // everything new first: nothing half-made stays behind and the setting is unchanged where one of them fails
+    const size_t px = on ? (size_t)out_H * out_W : (size_t)s->scale * s->H * s->scale * s->W;
+    int32_t* tab = nullptr;
+    uint8_t *ro[2] = {nullptr, nullptr}, *yo[2] = {nullptr, nullptr};
+    bool ok = true;
+    if (on) {
+        ok = hipMalloc(reinterpret_cast<void**>(&tab), plan.blob.size() * sizeof(int32_t)) == hipSuccess;
+        ok = ok && hipMemcpy(tab, plan.blob.data(), plan.blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+        for (int i = 0; i < 2; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&ro[i]), (size_t)s->batch * px * 3) == hipSuccess;
+    }
+    const bool had_yout = s->yout[0] != nullptr;      // it follows the output size, whatever the format is at the moment
+    for (int i = 0; had_yout && i < 2; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&yo[i]), (size_t)s->batch * ((px * 3 + 1) / 2)) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (tab) (void)hipFree(tab);
+        for (int i = 0; i < 2; ++i) {
+            if (ro[i]) (void)hipFree(ro[i]);
+            if (yo[i]) (void)hipFree(yo[i]);
+        }
+        return fail(PFNL_ERR_NOMEM, "resize allocation failed");
+    }
+    if (s->rtab) (void)hipFree(s->rtab);
+    s->rtab = tab;
+    for (int i = 0; i < 2; ++i) {
+        if (s->rout[i]) (void)hipFree(s->rout[i]);
+        s->rout[i] = ro[i];
+        if (had_yout) {
+            (void)hipFree(s->yout[i]);
+            s->yout[i] = yo[i];
+        }
+    }
+    s->rplan = std::move(plan);
     return 0;
 }
 

@@ -5,6 +5,8 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <string>
+#include <vector>
 
 #include "chain_order.h"   // persistent_grid: the grid of the persistent launches
 
@@ -186,6 +188,27 @@ bool yuv_coefficients(int matrix, int full_range, YuvCoef* c);   // matrix 0 BT.
 // yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow)
 hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
 hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+
+// ---- uint8 RGB frames at a chosen raster (resize.hip; the rule: pfnl_amd/resize.py) ----
+constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in
+constexpr int RESIZE_TW = 64;            // output pixels of one workgroup: across,
+constexpr int RESIZE_TH = 16;            // and down
+// One axis: output o = sum_k coef[o * ntaps + k] * in[first[o] + k] / 2^14 over k < count[o] (zero behind count); ntaps = max count.
+struct ResizeAxis {
+    std::vector<int32_t> first, count;
+    std::vector<int16_t> coef;
+    int ntaps = 0;
+};
+bool resize_axis(int n_in, int n_out, ResizeAxis* t, std::string* why);   // false + *why: outside the limits (no device needed)
+// Both axes of H x W -> oH x oW as the one block of device memory the kernel reads, and the rows of its largest tile.
+struct ResizePlan {
+    int H = 0, W = 0, oH = 0, oW = 0, ht = 0, vt = 0, max_rows = 0;
+    std::vector<int32_t> blob;
+};
+bool resize_plan(int H, int W, int oH, int oW, ResizePlan* p, std::string* why);
+// in [n][H][W][3] -> out [n][oH][oW][3], both passes in one launch; blob_dev: p.blob on the device; any alignment (16-byte stores where
+// oW is a multiple of 16 and out is aligned, single bytes otherwise)
+hipError_t launch_resize_u8(const uint8_t* in, uint8_t* out, const ResizePlan& p, const int32_t* blob_dev, int n, hipStream_t s);
 
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;

@@ -534,6 +534,30 @@ def rgb_to_yuv420(frames, fmt: str, matrix: str = "bt709", full_range=False, out
     return out.view(n, H * 3 // 2, W)
 
 
+def resize_u8(frames, out_size, out=None):
+    """[n,H,W,3] (or [H,W,3]) uint8 (cuda) -> [n,oH,oW,3] uint8, ``out_size`` = (oH, oW): byte for byte pfnl_amd/resize.py resize
+    (pfnl_op_resize_u8: the streaming session's resampler).  Each axis between a quarter and twice its input; any alignment; ``out``:
+    write there."""
+    import torch
+    from . import resize as _resize
+    lib = _capi.load_library()
+    src = _req_u8(frames, "frames")
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("resize_u8 expects [n,H,W,3]")
+    n, H, W, _ = frames.shape
+    oH, oW = (int(v) for v in out_size)
+    _resize.check_limits(H, oH)
+    _resize.check_limits(W, oW)
+    if out is None:
+        out = torch.empty((n, oH, oW, 3), dtype=torch.uint8, device=frames.device)
+    elif out.numel() != n * oH * oW * 3 or out.device != frames.device:
+        raise ValueError("out must hold n * oH * oW * 3 bytes on the frames' device")
+    _capi.check(lib.pfnl_op_resize_u8(src, n, H, W, oH, oW, _req_u8(out, "out"), _stream(frames)))
+    return out.view(n, oH, oW, 3)
+
+
 def quantise_u8(sr):
     """uint8(np.round(np.clip(sr * 255, 0, 255))) on the device (reference model/pfnl.py:254-257)."""
     import torch

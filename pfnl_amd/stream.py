@@ -19,6 +19,11 @@ YUV 4:2:0 (off by default): ``open_stream(H, W, batch, pixel_format="nv12")`` ta
 uint8, or flat - and returns SR frames ``(sH*3//2, sW)`` for an encoder; ``"i420"`` likewise; ``out_format`` sets the two sides apart
 (``"rgb24"`` among them).  The conversion runs on the device at the two edges of the session, by the integer rule of pfnl_amd/yuv.py
 (``matrix`` "bt601" | "bt709", ``full_range``; chroma sited left); the ring, the scenes and the windows go on seeing RGB.
+
+Output size (off by default): ``open_stream(H, W, batch, out_size=(1080, 1920))`` delivers every frame at that raster - ``(oH, oW, 3)``, or
+``(oH*3//2, oW)`` in a 4:2:0 output format (then both even) - resampled on the device behind the quantisation and ahead of the YUV conversion by
+the integer rule of pfnl_amd/resize.py (a Keys cubic that widens when the raster shrinks): each axis between a quarter and twice the
+network's own size.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from . import _capi
+from . import _capi, resize as _resize
 
 
 def next_batch(num_frames: int, batch: int, pushed: int, ended: bool, launched: int) -> Tuple[int, int]:
@@ -54,6 +59,22 @@ def format_arguments(pixel_format="rgb24", out_format=None, matrix="bt709", full
     return _capi.PIXEL_FORMATS[pixel_format], _capi.PIXEL_FORMATS[out_format], _capi.YUV_MATRICES[matrix], int(bool(full_range))
 
 
+def resize_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24") -> Tuple[int, int]:
+    """The two arguments of pfnl_stream_resize for open_stream's ``out_size`` (None = off = (0, 0)) behind a network output of sH x sW;
+    ValueError for anything the library would refuse.  Needs no device."""
+    if out_size is None:
+        return 0, 0
+    try:
+        oH, oW = (int(v) for v in out_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"out_size: None or (oH, oW), got {out_size!r}") from None
+    _resize.check_limits(sH, oH)
+    _resize.check_limits(sW, oW)
+    if out_format != "rgb24" and (oH % 2 or oW % 2):
+        raise ValueError(f"out_size: a {out_format} output needs even sizes, got {oH} x {oW}")
+    return oH, oW
+
+
 def frame_shapes(pixel_format: str, H: int, W: int) -> Tuple[tuple, ...]:
     """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24; ``(H*3//2, W)`` or flat for the 4:2:0 formats."""
     if pixel_format == "rgb24":
@@ -73,13 +94,18 @@ class VideoStream:
 
     ``pixel_format`` / ``out_format`` ("rgb24" | "nv12" | "i420"; ``out_format`` None = the same): what ``push`` takes and ``pop`` returns.
     The 4:2:0 frames are tightly packed, ``(H*3//2, W)`` or flat in, ``(sH*3//2, sW)`` out (pfnl_amd/yuv.py), converted with ``matrix``
-    ("bt601" | "bt709") at limited or ``full_range``."""
+    ("bt601" | "bt709") at limited or ``full_range``.
+
+    ``out_size`` (None | ``(oH, oW)``): the raster ``pop`` delivers, ``(oH, oW, 3)`` or ``(oH*3//2, oW)``, by the rule of pfnl_amd/resize.py;
+    each axis between a quarter and twice the network's output, even in a 4:2:0 output format."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
-                 full_range=False):
+                 full_range=False, out_size=None):
         import torch
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
         self.pixel_format, self.out_format = pixel_format, pixel_format if out_format is None else out_format
+        size = resize_arguments(out_size, engine.geom.scale * int(H), engine.geom.scale * int(W), self.out_format)
+        self.out_size = size if out_size is not None else None
         self.matrix, self.full_range = matrix, bool(full_range)
         if not engine._ready:
             raise RuntimeError("weights have not been loaded")
@@ -110,6 +136,12 @@ class VideoStream:
         if fmt[0] or fmt[1]:                        # (all defaults: the session as it always was, and no call)
             try:
                 _capi.check(self._lib.pfnl_stream_format(s, *fmt))
+            except Exception:
+                self.close()
+                raise
+        if self.out_size is not None:               # (behind the format: the size is checked against it)
+            try:
+                _capi.check(self._lib.pfnl_stream_resize(s, *self.out_size))
             except Exception:
                 self.close()
                 raise
@@ -175,7 +207,8 @@ class VideoStream:
         return self.pop_ready()
 
     def reset(self) -> None:
-        """The next sequence, same geometry and scene setting; what was not popped is dropped, and so are a pending mark and ``cuts``."""
+        """The next sequence, same geometry, scene setting, formats and output size; what was not popped is dropped, and so are a pending
+        mark and ``cuts``."""
         _capi.check(self._lib.pfnl_stream_reset(self._handle()))
         self.cuts = []
         self.last_info = None
@@ -193,7 +226,8 @@ class VideoStream:
     def pop(self):
         """The next SR frame as ``(index, frame)``, or None when none is deliverable; waits only for the batch that holds it."""
         s = self._handle()
-        shape = frame_shapes(self.out_format, self.scale * self.H, self.scale * self.W)[0]
+        oH, oW = self.out_size if self.out_size is not None else (self.scale * self.H, self.scale * self.W)
+        shape = frame_shapes(self.out_format, oH, oW)[0]
         index, got = C.c_longlong(0), C.c_int(0)
         if self._device_frames:
             import torch
