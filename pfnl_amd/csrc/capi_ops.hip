@@ -837,8 +837,8 @@ int pfnl_op_nonlocal_block(const float* x, const float* wg, const float* bg, con
     return op_nonlocal_block(x, wg, bg, ww, bw, wt, bt, wp, bp, nltype, sub_sample, out, B, T, H, W, stream);
 }
 
-int pfnl_op_conv0(const float* x, const float* kernel_host, const float* bias_host, float* out, int B, int T, int H, int W,
-                  void* stream) {
+int pfnl_op_conv0_ex(const float* x, const float* kernel_host, const float* bias_host, float* out, int B, int T, int H, int W,
+                     int f32, void* stream) {
     if (!x || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if ((T != 3 && T != 5 && T != 7) || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "unsupported conv0 geometry");
     OpStage st(stream);
@@ -849,8 +849,13 @@ int pfnl_op_conv0(const float* x, const float* kernel_host, const float* bias_ho
     float* d = st.upload(wb, (size_t)B * N * CP);
     // conv0 reads the frame stack in the packed space_to_depth layout the non-local block leaves it in
     st.run([&] { return pfnl::launch_nl_pack(x, d + wb.size(), B, T, H, W, st.s); });
-    st.run([&] { return pfnl::launch_conv0(d + wb.size(), d, d + 75 * 64, out, B, T, H, W, st.s); });
+    st.run([&] { return pfnl::launch_conv0(d + wb.size(), d, d + 75 * 64, out, B, T, H, W, st.s, nullptr, f32 != 0); });
     return st.finish("conv0 op: ");
+}
+
+int pfnl_op_conv0(const float* x, const float* kernel_host, const float* bias_host, float* out, int B, int T, int H, int W,
+                  void* stream) {
+    return pfnl_op_conv0_ex(x, kernel_host, bias_host, out, B, T, H, W, 0, stream);
 }
 
 int pfnl_op_tail(const float* merge, const float* x, const float* kernel_host, const float* bias_host, float* out, int B,

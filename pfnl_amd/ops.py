@@ -385,8 +385,9 @@ def nonlocal_block(x, wg, bg, ww, bw, theta=None, phi=None, nltype: int = 1, sub
     return out
 
 
-def conv0(x, kernel, bias=None):
-    """conv0 (reference model/pfnl.py:48,61-62): x [B,T,H,W,3] (cuda) -> lrelu(conv5x5(frame) + b) [B*T,H,W,64]."""
+def conv0(x, kernel, bias=None, f32=False):
+    """conv0 (reference model/pfnl.py:48,61-62): x [B,T,H,W,3] (cuda) -> lrelu(conv5x5(frame) + b) [B*T,H,W,64].
+    f32: the fp32 VALU kernel of strict_fp32=on instead of the default split-f16 MFMA kernel."""
     import torch
     lib = _capi.load_library()
     B, T, H, W, c = x.shape
@@ -394,7 +395,7 @@ def conv0(x, kernel, bias=None):
     if k.shape != (5, 5, 3, 64) or c != 3:
         raise ValueError("conv0: geometry mismatch")
     out = torch.empty((B * T, H, W, 64), dtype=torch.float32, device=x.device)
-    _capi.check(lib.pfnl_op_conv0(_req(x, "x"), _hp(k), _hp(b), _req(out, "out"), B, T, H, W, _stream(x)))
+    _capi.check(lib.pfnl_op_conv0_ex(_req(x, "x"), _hp(k), _hp(b), _req(out, "out"), B, T, H, W, 1 if f32 else 0, _stream(x)))
     return out
 
 

@@ -34,6 +34,43 @@ THE BOUND, element-wise against the fp64 spec, for an output that sums K product
     the edge data reaches 0.45 - 0.6 of it at K = 448 - 576 and ~0.2 at K = 4032; on the MI355X the f32-MFMA kernels reach up to
     0.65 and the split-f16 kernels up to 0.53 (test_gpu_numerics.py prints the ratios).  The f32-MFMA kernels must meet
     alpha(K) S on the same data (they have no beta term).
+
+THE WINOGRAD MODEL (conv_wino.hip, conv_wino_ws.hip: F(2x2,3x3), the strict-fp32 3x3 kernels).  A 2x2 output tile at an even origin
+comes from the 4x4 input tile d around it (zero padding, even H and W) and the filter g:
+
+    Y = A^T [ U .* (B^T d B) ] A  summed over the input channels,   U = fp32(G g G^T)  (fp64 on the host, rounded once)
+
+    B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]    G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]    A^T = [1 1 1 0; 0 1 -1 -1]
+
+An output's error does not scale with its own nine taps: every rounding acts on a quantity made of the whole 4x4 tile and the
+transformed filter, and the cancellation that turns those into the nine-tap sum happens afterwards.  The magnitude that bounds every
+intermediate of output (p, q) is therefore
+
+    S_w = |A^T| [ |U| .* (|B^T| |d| |B|) ] |A|   summed over the input channels  (+ |bias|, |addend|, |resid| as in S)
+
+and the bound is |got - ref| <= alpha_wino(K) S_w, alpha_wino(K) = 2^-24 (sqrt(K) + 7 + e), one 2^-24 S_w per rounding that every
+output passes through, the roundings of the fixed stages added linearly (worst case), the chain's statistically as in alpha:
+
+  - input transform, 2: t = d_a +- d_b (one fma with +-1: |error| <= 2^-24 (|d_a| + |d_b|)), then v = t_a +- t_b; both stages
+    together are off by at most 2 2^-24 (|B^T| |d| |B|), which the rest of the formula carries to 2 2^-24 S_w;
+  - U's one rounding, 1: 2^-24 |U| per element;
+  - the chain over the K input channels of one accumulator (fp32 FMAs, each product exact): every step rounds a partial sum that
+    is at most sum |U| |V| of its position, at most S_w after |A^T| . |A|: 2^-24 sqrt(K) S_w, the convention of alpha;
+  - output transform, 4: two stages (over nu, then over xi) of two additions each, every partial result at most S_w;
+  - the epilogue, e: one per addition (bias; the addend or mode 2's LDS partial; the residual) and one for the activation's
+    multiplication by fp32(0.2) (which is off 0.2 by 2^-26 relative and scales everything before it by 0.2: under one 2^-24 S_w).
+    Mode 0 (act(conv + bias)) and mode 3 (convmerge1): e = 2, alpha_wino = 2^-24 (sqrt(K) + 9).  Mode 1 (+ addend, + resid) and
+    mode 2 (conv2_i: + the base half's partial from LDS, + bias, act, + resid): e = 4.
+  - K: 64 in modes 0 and 1.  Mode 2 runs two chains of 64 (the base half's finished partial goes through its own output transform,
+    is rounded into LDS as an fp32 value and added in the frame half's epilogue): sqrt(64) on each half's share of S_w, and
+    the base half's own 2 + 1 + 4 roundings act on its share only, so 2^-24 (sqrt(128) + 7 + 4) (S_w over all 128 channels)
+    covers it.  Mode 3 keeps one accumulator over all T frames: K = 64 T.
+The kernels differ from the textbook form in two places that change no magnitude: Winograd row 2 is computed as d1 - d2 with -U, and
+the persistent kernel's second output of each stage is m1 - (m2 + m3) where the per-tile kernel's is (m1 - m2) - m3.
+wino_emulate_f32 restates the algorithm in numpy fp32 with the kernels' order of operations; on the families below it stays under
+0.35 alpha_wino S_w (tests/test_wino_numerics_host.py prints the ratios; on the MI355X the kernels reach up to 0.46 with the rms of
+err / S_w equal to the emulation's: test_gpu_strict_numerics.py), while against alpha(576) S it is off by a factor of
+thousands on the edge data - the direct kernels' bound cannot be reused.
 """
 import numpy as np
 
@@ -155,7 +192,8 @@ def edges(rng, shape):
 
 
 def edge_weights(rng, shape, big=6.0e4):
-    """Weights from 1e-7 to ~1 (log-uniform, random sign), output channel 0 all zero, one weight near 6e4 (under 65504)."""
+    """Weights from 1e-7 to ~1 (log-uniform, random sign), output channel 0 all zero, one weight near 6e4 (under 65504).
+    big=1e6 is the strict-fp32 variant: a weight beyond binary16, which sends the forward to the f32 kernels."""
     w = (10.0 ** rng.uniform(-7, 0, size=shape)) * rng.choice([-1.0, 1.0], size=shape)
     w[..., 0] = 0.0
     w.reshape(-1, shape[-1])[0, 1] = big
@@ -170,3 +208,125 @@ def dark(rng, shape, scale):
 def unit_binades(rng, shape):
     """|x| in [1/4, 4): the data of the bit-exact scale-equivariance checks (equivariant_scales: k in [-10, 13])."""
     return (np.ldexp(1.0 + rng.random(shape), rng.integers(-2, 2, size=shape)) * rng.choice([-1.0, 1.0], size=shape)).astype(np.float32)
+
+
+def bright(rng, shape, lo=10, hi=40):
+    """+-2^u (1 + v), u uniform over [lo, hi] = [10, 40]: nearly every element beyond 65504, where only the strict-fp32 kernels run."""
+    u = rng.integers(lo, hi + 1, size=shape)
+    return (np.ldexp(1.0 + rng.random(shape), u) * rng.choice([-1.0, 1.0], size=shape)).astype(np.float32)
+
+
+# ---- the Winograd F(2x2,3x3) model of the strict-fp32 3x3 kernels (module docstring) ------------------------------------------
+
+WINO_BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64)
+WINO_G = np.array([[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]], np.float64)
+WINO_AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float64)
+
+
+def alpha_wino(K, epilogue=2):
+    """Error per unit of S_w: 2^-24 (sqrt(K) + 2 [input transform] + 1 [U] + 4 [output transform] + epilogue roundings)."""
+    return 2.0 ** -24 * (np.sqrt(K) + 7 + epilogue)
+
+
+def wino_tiles(x, zero_halo=True):
+    """The 4x4 input tiles of x [B, H, W, C] (even H, W; zero padding): d[i, j, b, ty, tx, c] = x_padded[b, 2 ty + i, 2 tx + j, c].
+    zero_halo=False is a fault for the host test's mutant: the halo column right of the image holds the image's last column."""
+    B, H, W, C = x.shape
+    assert H % 2 == 0 and W % 2 == 0, "F(2x2,3x3) tiles need even H and W"
+    xp = np.pad(x, ((0, 0), (1, 1), (1, 1), (0, 0)))
+    if not zero_halo:
+        xp[:, :, W + 1] = xp[:, :, W]
+    return np.stack([np.stack([xp[:, i:i + H:2, j:j + W:2] for j in range(4)]) for i in range(4)])
+
+
+def wino_u(k):
+    """U = G g G^T of HWIO k [3, 3, C, cout] in fp64: [4, 4, C, cout]."""
+    return np.einsum("xa,nb,abco->xnco", WINO_G, WINO_G, np.asarray(k, np.float64))
+
+
+def _untile(y):
+    """[2, 2, B, th, tw, cout] -> [B, 2 th, 2 tw, cout]."""
+    _, _, B, th, tw, co = y.shape
+    return y.transpose(2, 3, 0, 4, 1, 5).reshape(B, 2 * th, 2 * tw, co)
+
+
+def wino_conv_f64(x, k):
+    """The algorithm carried out in fp64 (nothing rounded, U included): equals pfnl_spec.conv2d_same(x, k, None)."""
+    d = wino_tiles(np.asarray(x, np.float64))
+    V = np.einsum("xi,nj,ijbtuc->xnbtuc", WINO_BT, WINO_BT, d)
+    M = np.einsum("xnbtuc,xnco->xnbtuo", V, wino_u(k))
+    return _untile(np.einsum("px,qn,xnbtuo->pqbtuo", WINO_AT, WINO_AT, M))
+
+
+def wino_terms(x, k, extra=()):
+    """S_w of the Winograd bound for conv2d_same(x, k) (fp64, [B, H, W, cout]); `extra`: arrays added by magnitude (bias, addend, resid)."""
+    d = np.abs(wino_tiles(np.asarray(x, np.float64)))
+    U = np.abs(wino_u(k).astype(np.float32).astype(np.float64))
+    aB, aA = np.abs(WINO_BT), np.abs(WINO_AT)
+    V = np.einsum("xi,nj,ijbtuc->xnbtuc", aB, aB, d)
+    M = np.einsum("xnbtuc,xnco->xnbtuo", V, U)
+    S = _untile(np.einsum("px,qn,xnbtuo->pqbtuo", aA, aA, M))
+    for e in extra:
+        if e is not None:
+            S = S + np.abs(np.asarray(e, np.float64))
+    return S
+
+
+def _lrelu_f32(o):
+    return np.maximum(o, o * np.float32(0.2))
+
+
+def wino_emulate_f32(x, k, bias=None, addend=None, resid=None, act=True, base=None, base_div=1, per_tile=False, fault=None):
+    """numpy fp32 emulation of the Winograd kernels, their order of operations (test infrastructure; the product never imports it).
+
+    x [B, H, W, C] and k [3, 3, C, cout]: C = 64 (modes 0 and 1) or 64 T, the concat of a clip's frames (mode 3: one accumulator over
+    all of them).  base [B / base_div, H, W, 64] (one per clip of base_div frames) selects mode 2: k is [3, 3, 128, cout], rows 0..63 the base
+    half, whose raw result is finished, kept as an fp32 value and added in the epilogue of each of the clip's frames.  addend / resid broadcast to the output.
+      - input transform in fp32: over the rows first (d0 - d2, d1 + d2, d1 - d2 [with -U], d1 - d3), then over the columns;
+      - U = fp32(G g G^T) from fp64;
+      - one sequential fp32 chain over the channels per (xi, nu), every product formed exactly (an FMA: the sum is formed in fp64
+        and rounded once - a double rounding only where the fp64 sum is inexact and lands on an fp32 tie);
+      - output transform over nu, then over xi: (m0 + m1) + m2 and m1 - (m2 + m3), or (m1 - m2) - m3 with per_tile (conv_wino.hip);
+      - epilogue: + bias, + addend (or + the base partial), max(o, 0.2f o), + resid.
+    fault (the host test's mutants): "halo" - the halo column right of the image is not zero; "resid_first" - the residual is added
+    before the activation."""
+    f = np.float32
+    x = np.asarray(x, f)
+    if base is not None:
+        kb, k = k[:, :, :64], k[:, :, 64:]
+        part = np.repeat(_wino_raw_f32(base, kb, per_tile, fault), base_div, axis=0)
+    y = _wino_raw_f32(x, k, per_tile, fault)
+    o = y + (np.zeros(y.shape[-1], f) if bias is None else np.asarray(bias, f))
+    if base is not None:
+        o = o + part
+    elif addend is not None:
+        o = o + np.asarray(addend, f)
+    if fault == "resid_first" and resid is not None:
+        o = o + np.asarray(resid, f)
+    if act:
+        o = _lrelu_f32(o)
+    if fault != "resid_first" and resid is not None:
+        o = o + np.asarray(resid, f)
+    return o
+
+
+def _wino_raw_f32(x, k, per_tile, fault):
+    """The transformed convolution itself (no epilogue), fp32 [B, H, W, cout]."""
+    f = np.float32
+    d = wino_tiles(np.asarray(x, f), zero_halo=fault != "halo")
+    t = np.stack([d[0] - d[2], d[1] + d[2], d[1] - d[2], d[1] - d[3]])                       # rows: [xi, j, ...]
+    V = np.stack([t[:, 0] - t[:, 2], t[:, 1] + t[:, 2], t[:, 2] - t[:, 1], t[:, 1] - t[:, 3]], axis=1)   # [xi, nu, b, ty, tx, c]
+    U = wino_u(k).astype(f)
+    U[2] = -U[2]                                                                              # row 2 is d1 - d2
+    C = x.shape[-1]
+    V64, U64 = V.astype(np.float64), U.astype(np.float64)
+    acc = np.zeros(V.shape[:-1] + (U.shape[-1],), f)
+    for c in range(C):
+        acc = (acc.astype(np.float64) + V64[..., c, None] * U64[:, :, None, None, None, c, :]).astype(f)
+    if per_tile:
+        s = np.stack([(acc[:, 0] + acc[:, 1]) + acc[:, 2], (acc[:, 1] - acc[:, 2]) - acc[:, 3]])      # [q, xi, ...]
+        y = np.stack([(s[:, 0] + s[:, 1]) + s[:, 2], (s[:, 1] - s[:, 2]) - s[:, 3]])                  # [p, q, ...]
+    else:
+        s = np.stack([(acc[:, 0] + acc[:, 1]) + acc[:, 2], acc[:, 1] - (acc[:, 2] + acc[:, 3])])
+        y = np.stack([(s[:, 0] + s[:, 1]) + s[:, 2], s[:, 1] - (s[:, 2] + s[:, 3])])
+    return _untile(y)

@@ -40,6 +40,9 @@ def test_abi_v4_and_argument_validation_without_gpu():
     assert b"mfma" in lib.pfnl_last_error()
     assert lib.pfnl_op_conv3x3_bf16_ex(dummy, dummy, None, None, 7, None, dummy, 14, 8, 32, 1, 16, 0, 0, 0, None) == -1
     assert b"NULL" in lib.pfnl_last_error()
+    for f32 in (0, 1):                                                         # pfnl_op_conv0_ex: an addition to v4, same checks as pfnl_op_conv0
+        assert lib.pfnl_op_conv0_ex(None, dummy, None, dummy, 1, 7, 8, 8, f32, None) == -1 and b"NULL" in lib.pfnl_last_error()
+        assert lib.pfnl_op_conv0_ex(dummy, dummy, None, dummy, 1, 4, 8, 8, f32, None) == -1 and b"geometry" in lib.pfnl_last_error()
     h = C.c_void_p()
     bad = _capi.pfnl_config(4, 4, 64, 20, 0, (C.c_int32 * 3)(0, 0, 0))        # even num_frames
     assert lib.pfnl_create(C.byref(bad), C.byref(h)) == -1

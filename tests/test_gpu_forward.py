@@ -916,7 +916,9 @@ def _rel_err(y, ref):
 
 def test_split16_domain_undamped_weights():
     """Un-damped Xavier weights (no x0.1 on conv2_i: the trunk's activations grow block by block instead of staying O(1)) over 20
-    blocks: the default path against the fp64 spec, relative to the size of the result."""
+    blocks: the default path against the fp64 spec, relative to the size of the result; then strict_fp32=on under the same bound (the
+    only forward that takes the strict kernels - Winograd, direct f32 MFMA, 1x1 stream, VALU conv0 - through 20 blocks of growing
+    activations)."""
     geom = PFNLGeometry(num_block=20)
     w = synth.synthetic_weights(geom, seed=4)
     for k in w:
@@ -931,6 +933,13 @@ def test_split16_domain_undamped_weights():
     print("undamped: |trunk| max %.3g, |y| max %.3g, rel err %.3g, reruns %d" % (np.abs(trunk).max(), np.abs(ref).max(), _rel_err(y, ref), eng.range_reruns()))
     assert np.isfinite(y).all() and eng.range_reruns() == 0
     assert _rel_err(y, ref) < 2e-5
+    eng.close()
+    eng = _engine_with(geom, w)
+    eng.set_option("strict_fp32", "on")
+    ys = eng.forward(x)
+    print("undamped strict_fp32=on: rel err %.3g, reruns %d" % (_rel_err(ys, ref), eng.range_reruns()))
+    assert np.isfinite(ys).all() and eng.range_reruns() == 0
+    assert _rel_err(ys, ref) < 2e-5
     eng.close()
 
 

@@ -490,7 +490,7 @@ def test_bf16_kernels_equivariant():
 
 
 def test_f32_kernels_equivariant():
-    """The f32-MFMA kernels (direct, Winograd, persistent Winograd, 1x1 stream): bit-equivariant under 2^+-40."""
+    """The f32-MFMA kernels (direct, Winograd, persistent Winograd in its four modes, 1x1 stream): bit-equivariant under 2^+-40."""
     rng = np.random.default_rng(32)
     T, items, H, W = 7, 2, 10, 38
     x = rng.normal(size=(items * T, H, W, 64)).astype(np.float32)
@@ -506,6 +506,13 @@ def test_f32_kernels_equivariant():
                                                                                            resid=dev(r), variant=v)), [x, add, res], ks, split_inputs=False)
     _assert_equivariant("conv1x1 stream", lambda a: _np(ops.conv1x1_stream(dev(a), k10, zb, act=True, frames_per_item=T)), [x], ks,
                         split_inputs=False)
+    k2 = (rng.normal(size=(3, 3, 128, 64)) / 34).astype(np.float32)
+    _assert_equivariant("conv2_grouped (ws mode 2)", lambda a, ad, r: _np(ops.conv2_grouped(dev(a), dev(ad), k2, zb, dev(r), T)), [x, add, res], ks,
+                        split_inputs=False)
+    for cout in (48, 64):
+        km = (rng.normal(size=(3, 3, 64 * T, cout)) / np.sqrt(576 * T)).astype(np.float32)
+        _assert_equivariant(f"conv3x3_accum winograd (ws mode 3) cout {cout}", lambda a: _np(ops.conv3x3_accum(
+            dev(a), km, zb[:cout], act=True, frames_per_clip=T, variant="winograd")), [x], ks, split_inputs=False)
 
 
 # ---- one forward on dark clips -------------------------------------------------------------------------------------------------------
