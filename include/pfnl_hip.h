@@ -279,18 +279,30 @@ int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long l
  *     RGB frame it would have delivered, made per batch behind the quantisation, recomputed batches included).  The two are independent;
  *     (RGB24, RGB24) is the default again.  Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE);
  *     the setting survives pfnl_stream_reset.  Allocates its staging on first use (PFNL_ERR_NOMEM); pfnl_stream_close frees it.
- * Out of scope: pitched or padded planes, 10-bit formats (P010), 4:2:2 and 4:4:4, other sitings, transfer functions, BT.2020. */
-enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2 };
+ * 10 BITS OUT (off by default; a session that sets none of these runs the launches it always ran).  The network's result is fp32 and a 4 x
+ * upscale turns one-level steps of the LR frames into ramps that 8 bits do not resolve; HEVC Main10 and AV1 encoders take P010.  With
+ * out_fmt = PFNL_PIX_RGB10, PFNL_PIX_P010 or PFNL_PIX_I010 the session quantises each batch to round(clip(sr * 1023, 0, 1023)) (the float32
+ * product, half to even) and runs the resampler and the 4:2:0 conversion on those values: samples are little-endian uint16, pop copies
+ * twice the bytes and takes the same uint8_t* (2-byte aligned).  The arithmetic is stated once on the host, pfnl_amd/depth10.py:
+ *   RGB10 = [H][W][3], values 0 .. 1023; P010 = Y [H][W], CbCr [H/2][W/2][2], every sample value << 6; I010 (yuv420p10le) = Y, Cb, Cr,
+ *     every sample the value itself; limited range is 64 .. 940 / 64 .. 960 (pfnl_yuv10_coefficients: y0, then the nine encode integers);
+ *   the output size uses pfnl_resize_taps' tables with h = (sum c p + 2^9) >> 10 and clip((sum c h + 2^17) >> 18, 0, 1023);
+ *   the input side (RGB24, NV12, I420), scenes, the push bound, reset and the replay behind the range fence are what they are at 8 bits.
+ *   As in_fmt the three are PFNL_ERR_INVALID (10-bit input is not built: it needs a 16-bit ring), and so is RGB10 out of a YUV in_fmt.
+ *   The 16-bit output slots are allocated by the call that sets the format (PFNL_ERR_NOMEM) and freed by pfnl_stream_close.
+ * Out of scope: pitched or padded planes, 10-bit input, 12 and 16 bits, 4:2:2 and 4:4:4, other sitings, transfer functions, BT.2020. */
+enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2, PFNL_PIX_RGB10 = 3, PFNL_PIX_P010 = 4, PFNL_PIX_I010 = 5 };
 enum { PFNL_MATRIX_BT601 = 0, PFNL_MATRIX_BT709 = 1 };
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range);
 int pfnl_yuv_coefficients(int matrix, int full_range, int32_t out[15]);    /* y0, 9 encode, 5 decode; no device needed */
+int pfnl_yuv10_coefficients(int matrix, int full_range, int32_t out[10]);  /* y0, 9 encode, for 10-bit samples; no device needed */
 /* OUTPUT SIZE (off by default; then the session is what it always was).  The network's factor is fixed and display and encode rasters are
  * not (480p -> 1080p is 2.25 x, 720p -> 2160p is 3 x): with a size set the session resamples each batch's uint8 RGB frames on the device,
  * behind the quantisation and ahead of the YUV conversion, so a delivered frame is a pure function of the bytes the plain session
  * delivers.  The arithmetic is integer and stated once on the host, pfnl_amd/resize.py: a separable Keys cubic (a = -1/2) whose support
  * widens by in / out when the raster shrinks; per axis and output index a run of taps with 14 fractional bits that sums to 2^14 exactly,
  * indices clamped to the frame; horizontal pass first, h = (sum c p + 2^7) >> 8, unclipped; then clip((sum c h + 2^19) >> 20, 0, 255).
- *   pfnl_stream_resize: pop delivers out_H x out_W pixels (out_H*out_W*3 bytes, or *3/2 in a YUV output format: then both must be even -
+ *   pfnl_stream_resize: pop delivers out_H x out_W pixels (out_H*out_W*3 samples, or *3/2 in a 4:2:0 output format: then both must be even -
  *     whichever of pfnl_stream_resize and pfnl_stream_format comes second checks against the other's setting, PFNL_ERR_INVALID); 0, 0 is off.
  *     Per axis ceil(n_in / 4) <= n_out <= 2 n_in with n_in = scale * H or scale * W, and n_in, n_out <= 16384, else PFNL_ERR_INVALID.
  *     Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); the setting survives pfnl_stream_reset.
@@ -586,6 +598,16 @@ int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_r
  * does both passes through an int16 LDS tile; any alignment (16-byte stores where oW is a multiple of 16 and out is aligned, single bytes
  * otherwise).  NULL, n < 1 and sizes outside pfnl_resize_taps' limits: PFNL_ERR_INVALID before any HIP call. */
 int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, uint8_t* out, void* stream);
+/* The session's 10-bit output kernels (pfnl_stream_format with a 10-bit out_fmt; the rule: pfnl_amd/depth10.py), uint16 samples, device
+ * pointers, asynchronous on stream.  quantise: sr [n] float32 (16-byte aligned) -> uint16(round(clip(sr * 1023, 0, 1023))) (8-byte
+ * aligned), n a positive multiple of 4; NaN gives 0.  rgb_to_yuv420: rgb [n][H][W][3] with values 0 .. 1023 -> [n][H*W*3/2] in fmt
+ * PFNL_PIX_P010 or PFNL_PIX_I010; H and W even; any alignment (16-byte words where W is a multiple of 8 and both pointers are aligned, else
+ * single samples).  resize: pfnl_op_resize_u8 on values 0 .. 1023 (16-byte stores where oW is a multiple of 8 and out is aligned); it
+ * synchronises as that hook does.  NULL, odd or non-positive sizes, n < 1, an unknown fmt / matrix / full_range (fmt: the 8-bit formats
+ * and PFNL_PIX_RGB10 among them) and sizes outside pfnl_resize_taps' limits: PFNL_ERR_INVALID before any HIP call. */
+int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream);
+int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, void* stream);
+int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

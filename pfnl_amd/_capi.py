@@ -96,6 +96,7 @@ SIGNATURES = {
     "pfnl_op_tail": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pfnl_op_quantise_u8": (_i, [_vp, _vp, C.c_size_t, _vp]),
+    "pfnl_op_quantise_u10": (_i, [_vp, _vp, C.c_size_t, _vp]),
     "pfnl_op_gather_windows_u8": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_stream_open": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "pfnl_stream_push": (_i, [_vp, _vp, _i]),
@@ -112,10 +113,13 @@ SIGNATURES = {
     "pfnl_yuv_coefficients": (_i, [_i, _i, C.POINTER(C.c_int32)]),
     "pfnl_op_yuv420_to_rgb_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_op_rgb_to_yuv420_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_yuv10_coefficients": (_i, [_i, _i, C.POINTER(C.c_int32)]),
+    "pfnl_op_rgb_to_yuv420_u10": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_stream_resize": (_i, [_vp, _i, _i]),
     "pfnl_resize_max_taps": (_i, [_i, _i, C.POINTER(_i)]),
     "pfnl_resize_taps": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]),
     "pfnl_op_resize_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_op_resize_u10": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_op_scene_sad_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pfnl_op_gather_windows_u8_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
@@ -132,7 +136,9 @@ SIGNATURES = {
     "pfnl_comm_barrier": (_i, [_vp]),
     "pfnl_comm_allgather": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
 }
-PIXEL_FORMATS = {"rgb24": 0, "nv12": 1, "i420": 2}        # PFNL_PIX_*
+PIXEL_FORMATS = {"rgb24": 0, "nv12": 1, "i420": 2, "rgb10": 3, "p010": 4, "i010": 5}   # PFNL_PIX_*
+TEN_BIT_FORMATS = ("rgb10", "p010", "i010")                # uint16 samples; out_format only
+FORMATS_420 = ("nv12", "i420", "p010", "i010")             # H * W * 3 / 2 samples, even sizes
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                    # PFNL_MATRIX_*
 COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX = 0, 1

@@ -960,6 +960,48 @@ int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_r
     return 0;
 }
 
+int pfnl_yuv10_coefficients(int matrix, int full_range, int32_t out[10]) {
+    if (!out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    pfnl::YuvCoef c;
+    if (!pfnl::yuv10_coefficients(matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    const int v[10] = {c.y0, c.yr, c.yg, c.yb, c.cbr, c.cbg, c.cbb, c.crr, c.crg, c.crb};
+    for (int k = 0; k < 10; ++k) out[k] = v[k];
+    return 0;
+}
+
+int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream) {
+    if (!sr || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!n || n % 4) return fail(PFNL_ERR_INVALID, "element count must be a positive multiple of 4");
+    if (reinterpret_cast<uintptr_t>(sr) % 16 || reinterpret_cast<uintptr_t>(out) % 8)
+        return fail(PFNL_ERR_INVALID, "quantise_u10: sr must be 16-byte aligned and out 8-byte aligned");
+    HIPCHK(pfnl::launch_quantise_u10(sr, out, n, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, void* stream) {
+    if (!rgb || !yuv) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (fmt != PFNL_PIX_P010 && fmt != PFNL_PIX_I010) return fail(PFNL_ERR_INVALID, "yuv10: fmt must be PFNL_PIX_P010 or PFNL_PIX_I010");
+    pfnl::YuvCoef c;
+    if (!pfnl::yuv10_coefficients(matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (n < 1 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "yuv10: n >= 1, H and W positive and even (4:2:0)");
+    if ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(yuv)) % 2) return fail(PFNL_ERR_INVALID, "yuv10: uint16 samples are 2-byte aligned");
+    HIPCHK(pfnl::launch_rgb_to_yuv420_u10(rgb, yuv, fmt == PFNL_PIX_P010, c, n, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream) {
+    if (!in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(PFNL_ERR_INVALID, "resize: n >= 1");
+    pfnl::ResizePlan plan;
+    std::string why;
+    if (!pfnl::resize_plan(H, W, oH, oW, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 2) return fail(PFNL_ERR_INVALID, "resize: uint16 samples are 2-byte aligned");
+    OpStage st(stream);
+    const int32_t* blob = st.upload(plan.blob);
+    st.run([&] { return pfnl::launch_resize_u10(in, out, plan, blob, n, st.s); });
+    return st.finish("resize10 op: ");
+}
+
 int pfnl_resize_max_taps(int n_in, int n_out, int* ntaps) {
     if (!ntaps) return fail(PFNL_ERR_INVALID, "NULL argument");
     pfnl::ResizeAxis t;

@@ -56,7 +56,8 @@ struct pfnl_stream {
     // formats (pfnl_stream_format): the ring and out[] stay RGB; a YUV frame is converted on its way into its ring slot, a batch's SR
     // frames behind their quantisation into yout[] - allocated by the first call that needs them, freed with the session
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
-    pfnl::YuvCoef coef{};
+    pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
+    pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010
     uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel
     uint8_t* yout[2] = {nullptr, nullptr};            // [batch][oH*oW*3/2] each, beside out[]: where present, sized for the current output
     // output size (pfnl_stream_resize): out[] stays the network's raster; a batch is resampled behind its quantisation into rout[], and
@@ -64,12 +65,21 @@ struct pfnl_stream {
     pfnl::ResizePlan rplan;                           // rplan.oH = 0: off
     int32_t* rtab = nullptr;                          // rplan.blob on the device
     uint8_t* rout[2] = {nullptr, nullptr};            // [batch][oH][oW][3] each
+    // 10 bits out (pfnl_stream_format with PFNL_PIX_RGB10 / P010 / I010): the same three steps on uint16 samples in slots of their own,
+    // beside the 8-bit ones, which such a batch does not touch - allocated by the call that sets the format (the resized and the 4:2:0
+    // ones follow the output size from then on), freed with the session
+    uint16_t* out10[2] = {nullptr, nullptr};          // [batch][sH][sW][3] each
+    uint16_t* rout10[2] = {nullptr, nullptr};         // [batch][oH][oW][3] each: present where out10 is and a size is set
+    uint16_t* yout10[2] = {nullptr, nullptr};         // [batch][oH*oW*3/2] each
     int out_h() const { return rplan.oH ? rplan.oH : scale * H; }
     int out_w() const { return rplan.oW ? rplan.oW : scale * W; }
-    size_t out_bytes() const { return (size_t)out_h() * out_w() * 3; }   // one delivered frame as RGB
+    size_t out_bytes() const { return (size_t)out_h() * out_w() * 3; }   // one delivered frame as RGB24 (the samples of one as RGB10)
 };
 
 namespace {
+
+bool is_10bit(int fmt) { return fmt == PFNL_PIX_RGB10 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
+bool is_420(int fmt) { return fmt == PFNL_PIX_NV12 || fmt == PFNL_PIX_I420 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
 
 int get_option(pfnl_stream* s, const char* key, std::string* v) {
     char buf[64];
@@ -78,7 +88,7 @@ int get_option(pfnl_stream* s, const char* key, std::string* v) {
     return 0;
 }
 
-// gather -> forward -> quantise into the batch's slot, then its event; asynchronous on the session's stream
+// gather -> forward -> quantise (-> resize -> 4:2:0) into the batch's slots, then its event; asynchronous on the session's stream
 int enqueue(pfnl_stream* s, const Batch& b) {
     if (s->scene_mode) {
         // every frame up to b.last has been decided: on this stream, or on the copy stream before its push returned.  A replay
@@ -89,6 +99,15 @@ int enqueue(pfnl_stream* s, const Batch& b) {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
     if (int e = pfnl_forward(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->s)) return e;
+    if (is_10bit(s->out_fmt)) {                       // the same route on uint16 samples (depth10.hip)
+        HIPCHK(pfnl::launch_quantise_u10(s->sr, s->out10[b.slot], (size_t)b.count * s->sr_bytes, s->s));
+        if (s->rplan.oH) HIPCHK(pfnl::launch_resize_u10(s->out10[b.slot], s->rout10[b.slot], s->rplan, s->rtab, b.count, s->s));
+        if (s->out_fmt != PFNL_PIX_RGB10)
+            HIPCHK(pfnl::launch_rgb_to_yuv420_u10(s->rplan.oH ? s->rout10[b.slot] : s->out10[b.slot], s->yout10[b.slot],
+                                                  s->out_fmt == PFNL_PIX_P010, s->coef10, b.count, s->out_h(), s->out_w(), s->s));
+        HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
+        return 0;
+    }
     HIPCHK(pfnl::launch_quantise_u8(s->sr, s->out[b.slot], (size_t)b.count * s->sr_bytes, s->s));
     if (s->rplan.oH)                                  // (a replay takes the same route: pop stays a copy)
         HIPCHK(pfnl::launch_resize_u8(s->out[b.slot], s->rout[b.slot], s->rplan, s->rtab, b.count, s->s));
@@ -207,6 +226,9 @@ int drop_sequence(pfnl_stream* s) {
 void release(pfnl_stream* s) {
     for (int i = 0; i < 2; ++i) {
         if (s->out[i]) (void)hipFree(s->out[i]);
+        if (s->out10[i]) (void)hipFree(s->out10[i]);
+        if (s->rout10[i]) (void)hipFree(s->rout10[i]);
+        if (s->yout10[i]) (void)hipFree(s->yout10[i]);
         if (s->yout[i]) (void)hipFree(s->yout[i]);
         if (s->rout[i]) (void)hipFree(s->rout[i]);
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
@@ -356,9 +378,11 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
     Batch& b = s->q.front();
     if (!b.checked)
         if (int e = check_batch(s, b)) return e;
-    const bool yuv_out = s->out_fmt != PFNL_PIX_RGB24;
-    const size_t bytes = yuv_out ? s->out_bytes() / 2 : s->out_bytes();
-    const uint8_t* const src = (yuv_out ? s->yout[b.slot] : (s->rplan.oH ? s->rout[b.slot] : s->out[b.slot])) + (size_t)(s->delivered - b.first) * bytes;
+    const bool yuv_out = is_420(s->out_fmt), ten = is_10bit(s->out_fmt);
+    const size_t bytes = (yuv_out ? s->out_bytes() / 2 : s->out_bytes()) * (ten ? 2 : 1);
+    const uint8_t* const slot = ten ? reinterpret_cast<const uint8_t*>(yuv_out ? s->yout10[b.slot] : (s->rplan.oH ? s->rout10[b.slot] : s->out10[b.slot]))
+                                    : (yuv_out ? s->yout[b.slot] : (s->rplan.oH ? s->rout[b.slot] : s->out[b.slot]));
+    const uint8_t* const src = slot + (size_t)(s->delivered - b.first) * bytes;
     if (is_device) {
         HIPCHK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, s->s));   // ordered like the caller's own work on that stream
     } else {
@@ -421,35 +445,50 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
 
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || out_fmt < PFNL_PIX_RGB24 || out_fmt > PFNL_PIX_I420)
-        return fail(PFNL_ERR_INVALID, "format: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420");
-    pfnl::YuvCoef coef;
-    if (!pfnl::yuv_coefficients(matrix, full_range, &coef))
+    if (is_10bit(in_fmt)) return fail(PFNL_ERR_INVALID, "format: 10-bit input is not built (in_fmt: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420)");
+    if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || out_fmt < PFNL_PIX_RGB24 || out_fmt > PFNL_PIX_I010)
+        return fail(PFNL_ERR_INVALID, "format: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420, and as out_fmt PFNL_PIX_RGB10, PFNL_PIX_P010 or PFNL_PIX_I010");
+    if (in_fmt != PFNL_PIX_RGB24 && out_fmt == PFNL_PIX_RGB10)
+        return fail(PFNL_ERR_INVALID, "format: PFNL_PIX_RGB10 is delivered for RGB24 input only (a YUV in_fmt pairs with a YUV out_fmt or RGB24)");
+    pfnl::YuvCoef coef, coef10;
+    if (!pfnl::yuv_coefficients(matrix, full_range, &coef) || !pfnl::yuv10_coefficients(matrix, full_range, &coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
-    if (out_fmt != PFNL_PIX_RGB24 && ((s->out_h() | s->out_w()) & 1))
+    if (is_420(out_fmt) && ((s->out_h() | s->out_w()) & 1))
         return fail(PFNL_ERR_INVALID, "format: a YUV output needs an even output size (pfnl_stream_resize)");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    const bool need_in = in_fmt != PFNL_PIX_RGB24 && !s->yin, need_out = out_fmt != PFNL_PIX_RGB24 && !s->yout[0];
-    if (need_in || need_out) {
+    const bool ten = is_10bit(out_fmt), yuv_out = is_420(out_fmt);
+    const bool need_in = in_fmt != PFNL_PIX_RGB24 && !s->yin, need_out = yuv_out && !ten && !s->yout[0];
+    const bool need_q10 = ten && !s->out10[0], need_r10 = ten && s->rplan.oH && !s->rout10[0], need_y10 = ten && yuv_out && !s->yout10[0];
+    if (need_in || need_out || need_q10 || need_r10 || need_y10) {
         HIPCHK(hipSetDevice(s->device));
         bool ok = true;
         if (need_in) ok = hipMalloc(reinterpret_cast<void**>(&s->yin), s->lr_bytes / 2) == hipSuccess;
-        if (need_out)
-            for (int i = 0; i < 2; ++i)
-                ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout[i]), (size_t)s->batch * (s->out_bytes() / 2)) == hipSuccess;
+        for (int i = 0; i < 2; ++i) {
+            if (need_out) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout[i]), (size_t)s->batch * (s->out_bytes() / 2)) == hipSuccess;
+            if (need_q10) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->out10[i]), (size_t)s->batch * s->sr_bytes * sizeof(uint16_t)) == hipSuccess;
+            if (need_r10) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->rout10[i]), (size_t)s->batch * s->out_bytes() * sizeof(uint16_t)) == hipSuccess;
+            if (need_y10) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout10[i]), (size_t)s->batch * (s->out_bytes() / 2) * sizeof(uint16_t)) == hipSuccess;
+        }
         if (!ok) {                                    // nothing half allocated stays behind, and the setting is unchanged
             (void)hipGetLastError();
             if (need_in && s->yin) (void)hipFree(s->yin), s->yin = nullptr;
-            for (int i = 0; need_out && i < 2; ++i) {
-                if (s->yout[i]) (void)hipFree(s->yout[i]);
-                s->yout[i] = nullptr;
-            }
+            const auto drop = [](auto** slots) {
+                for (int i = 0; i < 2; ++i) {
+                    if (slots[i]) (void)hipFree(slots[i]);
+                    slots[i] = nullptr;
+                }
+            };
+            if (need_out) drop(s->yout);
+            if (need_q10) drop(s->out10);
+            if (need_r10) drop(s->rout10);
+            if (need_y10) drop(s->yout10);
             return fail(PFNL_ERR_NOMEM, "format staging allocation failed");
         }
     }
     s->in_fmt = in_fmt;
     s->out_fmt = out_fmt;
     s->coef = coef;
+    s->coef10 = coef10;
     return 0;
 }
 
@@ -460,7 +499,7 @@ int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) {
     if (on) {
         std::string why;
         if (!pfnl::resize_plan(s->scale * s->H, s->scale * s->W, out_H, out_W, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
-        if (s->out_fmt != PFNL_PIX_RGB24 && ((out_H | out_W) & 1))
+        if (is_420(s->out_fmt) && ((out_H | out_W) & 1))
             return fail(PFNL_ERR_INVALID, "resize: a YUV output format needs an even output size (pfnl_stream_format)");
     }
     if (s->pushed) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
@@ -479,12 +518,21 @@ int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) {
     }
     const bool had_yout = s->yout[0] != nullptr;      // it follows the output size, whatever the format is at the moment
     for (int i = 0; had_yout && i < 2; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&yo[i]), (size_t)s->batch * ((px * 3 + 1) / 2)) == hipSuccess;
+    // the 16-bit slots of a session that has delivered 10 bits follow it likewise
+    const bool had_out10 = s->out10[0] != nullptr, had_yout10 = s->yout10[0] != nullptr;
+    uint16_t *ro10[2] = {nullptr, nullptr}, *yo10[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i) {
+        if (on && had_out10) ok = ok && hipMalloc(reinterpret_cast<void**>(&ro10[i]), (size_t)s->batch * px * 3 * sizeof(uint16_t)) == hipSuccess;
+        if (had_yout10) ok = ok && hipMalloc(reinterpret_cast<void**>(&yo10[i]), (size_t)s->batch * ((px * 3 + 1) / 2) * sizeof(uint16_t)) == hipSuccess;
+    }
     if (!ok) {
         (void)hipGetLastError();
         if (tab) (void)hipFree(tab);
         for (int i = 0; i < 2; ++i) {
             if (ro[i]) (void)hipFree(ro[i]);
             if (yo[i]) (void)hipFree(yo[i]);
+            if (ro10[i]) (void)hipFree(ro10[i]);
+            if (yo10[i]) (void)hipFree(yo10[i]);
         }
         return fail(PFNL_ERR_NOMEM, "resize allocation failed");
     }
@@ -496,6 +544,12 @@ int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) {
         if (had_yout) {
             (void)hipFree(s->yout[i]);
             s->yout[i] = yo[i];
+        }
+        if (s->rout10[i]) (void)hipFree(s->rout10[i]);
+        s->rout10[i] = ro10[i];
+        if (had_yout10) {
+            (void)hipFree(s->yout10[i]);
+            s->yout10[i] = yo10[i];
         }
     }
     s->rplan = std::move(plan);

@@ -156,6 +156,7 @@ hipError_t run_mfma_selftest(int* mismatches);
 hipError_t launch_gather_windows(const float* frames, float* win, int F, int first, int count, int T, size_t frame_floats,
                                  hipStream_t s);
 hipError_t launch_quantise_u8(const float* sr, uint8_t* out, size_t n, hipStream_t s);
+hipError_t launch_quantise_u10(const float* sr, uint16_t* out, size_t n, hipStream_t s);   // 0 .. 1023 (depth10.hip); sr 16-byte, out 8-byte aligned
 // ring [cap][frame_bytes] uint8 (frame f in slot f % cap) -> win [count][T][frame_bytes] fp32 = u8 / 255. as the harness computes it,
 // window w slot t = frame clamp(first + w + t - T/2, 0, last); frame_bytes % 4 == 0 (stream.hip)
 hipError_t launch_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T,
@@ -188,6 +189,10 @@ bool yuv_coefficients(int matrix, int full_range, YuvCoef* c);   // matrix 0 BT.
 // yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow)
 hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
 hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+// 10 bits, uint16 samples (depth10.hip; the rule: pfnl_amd/depth10.py): y0 and the encode side of the table for 64 .. 940 / 64 .. 960 or
+// full range (the decode side stays zero); rgb [n][H][W][3] with values 0 .. 1023 -> P010 (samples << 6) or I010; H, W even; any alignment
+bool yuv10_coefficients(int matrix, int full_range, YuvCoef* c);
+hipError_t launch_rgb_to_yuv420_u10(const uint16_t* rgb, uint16_t* yuv, bool p010, const YuvCoef& c, int n, int H, int W, hipStream_t s);
 
 // ---- uint8 RGB frames at a chosen raster (resize.hip; the rule: pfnl_amd/resize.py) ----
 constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in
@@ -209,6 +214,8 @@ bool resize_plan(int H, int W, int oH, int oW, ResizePlan* p, std::string* why);
 // in [n][H][W][3] -> out [n][oH][oW][3], both passes in one launch; blob_dev: p.blob on the device; any alignment (16-byte stores where
 // oW is a multiple of 16 and out is aligned, single bytes otherwise)
 hipError_t launch_resize_u8(const uint8_t* in, uint8_t* out, const ResizePlan& p, const int32_t* blob_dev, int n, hipStream_t s);
+// the same plan and blob on uint16 samples 0 .. 1023 (depth10.hip): 16-byte stores where oW is a multiple of 8 and out is aligned
+hipError_t launch_resize_u10(const uint16_t* in, uint16_t* out, const ResizePlan& p, const int32_t* blob_dev, int n, hipStream_t s);
 
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;

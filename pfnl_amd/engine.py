@@ -235,7 +235,8 @@ class PFNLEngine:
         a time, uint8 SR frames popped in order, ``batch`` windows per forward.  One open session per engine.  ``scene_cut``: None,
         "manual" or a detector threshold - windows that stay inside a scene (VideoStream).  ``pixel_format`` / ``out_format`` "nv12" or "i420":
         YUV 4:2:0 frames in / out, converted on the device with ``matrix`` and ``full_range`` (pfnl_amd/yuv.py).  ``out_size`` (oH, oW): the raster of the
-        delivered frames, resampled on the device (pfnl_amd/resize.py)."""
+        delivered frames, resampled on the device (pfnl_amd/resize.py).  ``out_format`` "rgb10", "p010" or "i010": uint16 frames with 10-bit
+        values, quantised, resampled and converted at that depth (pfnl_amd/depth10.py)."""
         from .stream import VideoStream
         return VideoStream(self, H, W, batch, scene_cut, pixel_format, out_format, matrix, full_range, out_size)
 

@@ -466,7 +466,7 @@ class PFNL(VSR):
         per forward (the batches of test_video_lr with num_once == batch, hence its bytes).  Restores the checkpoint as the harness
         methods do.  ``scene_cut`` (None | "manual" | a threshold): windows that stay inside a scene, see VideoStream.  ``pixel_format`` / ``out_format``
         ("rgb24" | "nv12" | "i420") with ``matrix`` and ``full_range``: YUV 4:2:0 frames in / out, see VideoStream.  ``out_size`` (oH, oW): the raster
-        of the delivered frames, see VideoStream.  (A method of its own: the reference has no counterpart.)"""
+        of the delivered frames, see VideoStream.  ``out_format`` "rgb10" | "p010" | "i010": uint16 SR frames at 10 bits, see VideoStream.  (A method of its own: the reference has no counterpart.)"""
         import torch
         self._ensure_loaded(False)
         with torch.cuda.device(self.device):

@@ -569,6 +569,75 @@ def quantise_u8(sr):
     return out
 
 
+def _req_u16(t, name):
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint16 and t.is_contiguous()):
+        raise TypeError(f"{name} must be a contiguous uint16 tensor on the GPU")
+    return C.c_void_p(t.data_ptr())
+
+
+def quantise_u10(sr):
+    """uint16(np.round(np.clip(sr * 1023, 0, 1023))) on the device, the product in float32 (pfnl_op_quantise_u10; sample for sample
+    pfnl_amd/depth10.py quantise10; NaN gives 0).  sr.numel() a multiple of 4."""
+    import torch
+    lib = _capi.load_library()
+    _req(sr, "sr")
+    out = torch.empty(sr.shape, dtype=torch.uint16, device=sr.device)
+    _capi.check(lib.pfnl_op_quantise_u10(C.c_void_p(sr.data_ptr()), C.c_void_p(out.data_ptr()), sr.numel(), _stream(sr)))
+    return out
+
+
+def rgb_to_yuv420_u10(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None):
+    """[n,H,W,3] (or [H,W,3]) uint16 (cuda) with values 0 .. 1023 -> [n, H*3/2, W] uint16: tightly packed P010 / I010 frames, sample for
+    sample pfnl_amd/depth10.py from_rgb10 (pfnl_op_rgb_to_yuv420_u10: the streaming session's 10-bit output edge).  H, W even; any
+    alignment; ``out``: write there."""
+    import torch
+    lib = _capi.load_library()
+    if fmt not in ("p010", "i010"):
+        raise ValueError(f'fmt: "p010" or "i010", got {fmt!r}')
+    if matrix not in _capi.YUV_MATRICES:
+        raise ValueError(f"matrix: one of {sorted(_capi.YUV_MATRICES)}, got {matrix!r}")
+    src = _req_u16(frames, "frames")
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError("rgb_to_yuv420_u10 expects [n,H,W,3]")
+    n, H, W, _ = frames.shape
+    if n < 1 or H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"n >= 1, H and W even and at least 2, got {n} x {H} x {W}")
+    if out is None:
+        out = torch.empty((n, H * 3 // 2, W), dtype=torch.uint16, device=frames.device)
+    elif out.numel() != n * H * W * 3 // 2 or out.device != frames.device:
+        raise ValueError("out must hold n * H * W * 3 / 2 samples on the frames' device")
+    _capi.check(lib.pfnl_op_rgb_to_yuv420_u10(src, _capi.PIXEL_FORMATS[fmt], _capi.YUV_MATRICES[matrix], int(bool(full_range)), n, H, W,
+                                              _req_u16(out, "out"), _stream(frames)))
+    return out.view(n, H * 3 // 2, W)
+
+
+def resize_u10(frames, out_size, out=None):
+    """[n,H,W,3] (or [H,W,3]) uint16 (cuda) with values 0 .. 1023 -> [n,oH,oW,3] uint16, ``out_size`` = (oH, oW): sample for sample
+    pfnl_amd/depth10.py resize10 (pfnl_op_resize_u10: the streaming session's resampler at 10 bits).  Each axis between a quarter and
+    twice its input; any alignment; ``out``: write there."""
+    import torch
+    from . import resize as _resize
+    lib = _capi.load_library()
+    src = _req_u16(frames, "frames")
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("resize_u10 expects [n,H,W,3]")
+    n, H, W, _ = frames.shape
+    oH, oW = (int(v) for v in out_size)
+    _resize.check_limits(H, oH)
+    _resize.check_limits(W, oW)
+    if out is None:
+        out = torch.empty((n, oH, oW, 3), dtype=torch.uint16, device=frames.device)
+    elif out.numel() != n * oH * oW * 3 or out.device != frames.device:
+        raise ValueError("out must hold n * oH * oW * 3 samples on the frames' device")
+    _capi.check(lib.pfnl_op_resize_u10(src, n, H, W, oH, oW, _req_u16(out, "out"), _stream(frames)))
+    return out.view(n, oH, oW, 3)
+
+
 def score_y(pred_u8, truth_u8, sp_border: int = 8):
     """Y-channel quality sums of uint8 RGB frame pairs on the device (pfnl_op_score_y): pred_u8, truth_u8 [F,H,W,3] uint8 (cuda)
     -> [F,4] float64 (cuda): sum_d2_full, sum_d2_crop (spatial border sp_border), ssim_sum_full, ssim_sum_valid.

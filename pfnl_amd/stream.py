@@ -24,6 +24,11 @@ Output size (off by default): ``open_stream(H, W, batch, out_size=(1080, 1920))`
 ``(oH*3//2, oW)`` in a 4:2:0 output format (then both even) - resampled on the device behind the quantisation and ahead of the YUV conversion by
 the integer rule of pfnl_amd/resize.py (a Keys cubic that widens when the raster shrinks): each axis between a quarter and twice the
 network's own size.
+
+10 bits out (off by default): ``open_stream(H, W, batch, out_format="p010")`` delivers uint16 frames for an HEVC Main10 / AV1 encoder -
+``(oH*3//2, oW)``, every sample value << 6; ``"i010"`` (yuv420p10le) the values themselves, ``"rgb10"`` ``(oH, oW, 3)`` with values 0 .. 1023:
+the fp32 result quantised to 1023 levels instead of 255, then the same resampling and conversion by the rule of pfnl_amd/depth10.py.
+These are output formats only (``pixel_format`` stays "rgb24" | "nv12" | "i420"), and "rgb10" goes with RGB input.
 """
 from __future__ import annotations
 
@@ -52,6 +57,10 @@ def format_arguments(pixel_format="rgb24", out_format=None, matrix="bt709", full
     for name, value in (("pixel_format", pixel_format), ("out_format", out_format)):
         if value not in _capi.PIXEL_FORMATS:
             raise ValueError(f"{name}: one of {sorted(_capi.PIXEL_FORMATS)}, got {value!r}")
+    if pixel_format in _capi.TEN_BIT_FORMATS:
+        raise ValueError(f"pixel_format: 10-bit input is not built ({pixel_format!r} is an out_format), one of 'rgb24', 'nv12', 'i420'")
+    if out_format == "rgb10" and pixel_format != "rgb24":
+        raise ValueError(f"out_format 'rgb10' goes with pixel_format 'rgb24', got {pixel_format!r}")
     if matrix not in _capi.YUV_MATRICES:
         raise ValueError(f"matrix: one of {sorted(_capi.YUV_MATRICES)}, got {matrix!r}")
     if full_range not in (False, True, 0, 1):
@@ -70,16 +79,22 @@ def resize_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24") -> T
         raise ValueError(f"out_size: None or (oH, oW), got {out_size!r}") from None
     _resize.check_limits(sH, oH)
     _resize.check_limits(sW, oW)
-    if out_format != "rgb24" and (oH % 2 or oW % 2):
+    if out_format in _capi.FORMATS_420 and (oH % 2 or oW % 2):
         raise ValueError(f"out_size: a {out_format} output needs even sizes, got {oH} x {oW}")
     return oH, oW
 
 
 def frame_shapes(pixel_format: str, H: int, W: int) -> Tuple[tuple, ...]:
-    """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24; ``(H*3//2, W)`` or flat for the 4:2:0 formats."""
-    if pixel_format == "rgb24":
+    """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24 and rgb10; ``(H*3//2, W)`` or flat for the 4:2:0 formats
+    (in samples: uint8, or uint16 for the 10-bit formats - ``frame_dtype``)."""
+    if pixel_format in ("rgb24", "rgb10"):
         return ((H, W, 3),)
     return ((H * 3 // 2, W), (H * W * 3 // 2,))
+
+
+def frame_dtype(pixel_format: str):
+    """numpy's type of one sample: uint16 for rgb10 / p010 / i010, uint8 otherwise."""
+    return np.uint16 if pixel_format in _capi.TEN_BIT_FORMATS else np.uint8
 
 
 class VideoStream:
@@ -95,6 +110,9 @@ class VideoStream:
     ``pixel_format`` / ``out_format`` ("rgb24" | "nv12" | "i420"; ``out_format`` None = the same): what ``push`` takes and ``pop`` returns.
     The 4:2:0 frames are tightly packed, ``(H*3//2, W)`` or flat in, ``(sH*3//2, sW)`` out (pfnl_amd/yuv.py), converted with ``matrix``
     ("bt601" | "bt709") at limited or ``full_range``.
+
+    ``out_format`` "rgb10" | "p010" | "i010": ``pop`` returns uint16 frames (``torch.uint16`` on the device), 10-bit values by the rule of
+    pfnl_amd/depth10.py - p010 in the upper ten bits of each sample; ``pixel_format`` takes none of them.
 
     ``out_size`` (None | ``(oH, oW)``): the raster ``pop`` delivers, ``(oH, oW, 3)`` or ``(oH*3//2, oW)``, by the rule of pfnl_amd/resize.py;
     each axis between a quarter and twice the network's output, even in a 4:2:0 output format."""
@@ -229,12 +247,13 @@ class VideoStream:
         oH, oW = self.out_size if self.out_size is not None else (self.scale * self.H, self.scale * self.W)
         shape = frame_shapes(self.out_format, oH, oW)[0]
         index, got = C.c_longlong(0), C.c_int(0)
+        ten = self.out_format in _capi.TEN_BIT_FORMATS
         if self._device_frames:
             import torch
-            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            out = torch.empty(shape, dtype=torch.uint16 if ten else torch.uint8, device=self.device)
             _capi.check(self._lib.pfnl_stream_pop(s, C.c_void_p(out.data_ptr()), 1, C.byref(index), C.byref(got)))
         else:
-            out = np.empty(shape, np.uint8)
+            out = np.empty(shape, frame_dtype(self.out_format))
             _capi.check(self._lib.pfnl_stream_pop(s, out.ctypes.data_as(C.c_void_p), 0, C.byref(index), C.byref(got)))
         if not got.value:
             return None

@@ -10,7 +10,7 @@ the rule its kernels are tested against, byte for byte.  Everything after the co
   with the weights 3 : 1 vertically (near row : far row) and 1 : 1 between two samples on odd columns, indices clamped to the plane; RGB ->
   YUV filters the unrounded chroma numerators with 1-2-1 over the two luma rows, columns clamped, and rounds once.
 
-Out of scope: pitched planes, 10-bit formats, 4:2:2 / 4:4:4, other sitings, transfer functions, BT.2020.
+Out of scope: pitched planes, 10-bit input (10-bit output is pfnl_amd/depth10.py), 4:2:2 / 4:4:4, other sitings, transfer functions, BT.2020.
 """
 from __future__ import annotations
 
