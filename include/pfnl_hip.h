@@ -564,7 +564,11 @@ int pfnl_op_conv0(const float* x, const float* kernel_host, const float* bias_ho
  * f32 != 0 the fp32 VALU kernel that strict_fp32=on and the range re-run use (an addition to ABI v4: nothing existing changed). */
 int pfnl_op_conv0_ex(const float* x, const float* kernel_host, const float* bias_host, float* out, int B, int T, int H, int W,
                      int f32, void* stream);
-/* The tail (reference model/pfnl.py:53,63,76-80): depth_to_space(2) -> convmerge2 3x3 (no activation) -> depth_to_space(2)
+/* conv0 as precision=bf16 runs it: the default kernel of pfnl_op_conv0 (same arithmetic, same PFNL_CONV0 choice), its result rounded
+ * once to bf16 at the store.  out [B*T,H,W,64] bf16 (device).  (An addition to ABI v4: nothing existing changed.) */
+int pfnl_op_conv0_bf16(const float* x, const float* kernel_host, const float* bias_host, uint16_t* out, int B, int T, int H, int W,
+                       void* stream);
+/* The tail(reference model/pfnl.py:53,63,76-80): depth_to_space(2) -> convmerge2 3x3 (no activation) -> depth_to_space(2)
  * (scale 4 only) -> + ResizeBicubic(x[:, T/2]) -> [B,1,sH,sW,3].  merge [B,H,W,48] (device, the output of convmerge1),
  * x [B,T,H,W,3] (device), kernel_host HWIO [3,3,12,12] (scale 4) or [3,3,12,3] (scale 2), bias_host or NULL. */
 int pfnl_op_tail(const float* merge, const float* x, const float* kernel_host, const float* bias_host, float* out, int B,

@@ -853,6 +853,21 @@ int pfnl_op_conv0_ex(const float* x, const float* kernel_host, const float* bias
     return st.finish("conv0 op: ");
 }
 
+int pfnl_op_conv0_bf16(const float* x, const float* kernel_host, const float* bias_host, uint16_t* out, int B, int T, int H, int W,
+                       void* stream) {
+    if (!x || !kernel_host || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if ((T != 3 && T != 5 && T != 7) || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "unsupported conv0 geometry");
+    OpStage st(stream);
+    const int CP = pfnl::nl_padded_ch(12 * T), N = (H / 2) * (W / 2);
+    std::vector<float> wb(75 * 64 + 64, 0.f);
+    std::memcpy(wb.data(), kernel_host, 75 * 64 * sizeof(float));
+    if (bias_host) std::memcpy(&wb[75 * 64], bias_host, 64 * sizeof(float));
+    float* d = st.upload(wb, (size_t)B * N * CP);
+    st.run([&] { return pfnl::launch_nl_pack(x, d + wb.size(), B, T, H, W, st.s); });
+    st.run([&] { return pfnl::launch_conv0_bf16(d + wb.size(), d, d + 75 * 64, out, B, T, H, W, st.s); });
+    return st.finish("conv0 bf16 op: ");
+}
+
 int pfnl_op_conv0(const float* x, const float* kernel_host, const float* bias_host, float* out, int B, int T, int H, int W,
                   void* stream) {
     return pfnl_op_conv0_ex(x, kernel_host, bias_host, out, B, T, H, W, 0, stream);

@@ -399,6 +399,20 @@ def conv0(x, kernel, bias=None, f32=False):
     return out
 
 
+def conv0_bf16(x, kernel, bias=None):
+    """conv0 as precision=bf16 runs it (pfnl_op_conv0_bf16): the default kernel of `conv0`, its result rounded once to bf16 at the
+    store.  x [B,T,H,W,3] float32 (cuda) -> [B*T,H,W,64] bfloat16."""
+    import torch
+    lib = _capi.load_library()
+    B, T, H, W, c = x.shape
+    k, b = _host(kernel, "kernel"), _host(bias, "bias")
+    if k.shape != (5, 5, 3, 64) or c != 3:
+        raise ValueError("conv0_bf16: geometry mismatch")
+    out = torch.empty((B * T, H, W, 64), dtype=torch.bfloat16, device=x.device)
+    _capi.check(lib.pfnl_op_conv0_bf16(_req(x, "x"), _hp(k), _hp(b), _req16(out, "out"), B, T, H, W, _stream(x)))
+    return out
+
+
 def tail(merge, x, kernel, bias, scale: int):
     """The tail (reference model/pfnl.py:53,63,76-80): merge [B,H,W,48] (cuda), x [B,T,H,W,3] (cuda) -> [B,1,sH,sW,3]."""
     import torch

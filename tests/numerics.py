@@ -71,6 +71,40 @@ wino_emulate_f32 restates the algorithm in numpy fp32 with the kernels' order of
 0.35 alpha_wino S_w (tests/test_wino_numerics_host.py prints the ratios; on the MI355X the kernels reach up to 0.46 with the rms of
 err / S_w equal to the emulation's: test_gpu_strict_numerics.py), while against alpha(576) S it is off by a factor of
 thousands on the edge data - the direct kernels' bound cannot be reused.
+
+THE BF16 MODEL (conv_bf16.hip, conv_bf16_v2.hip, conv_bf16_v3.hip, conv0_kernel<true> / conv0_mfma_kernel<true>: precision=bf16).  Every
+operand of these kernels is a bf16 number - the activations as they arrive, the weights rounded once by bf16_rne on the host - so every
+product has 16 significant bits and is exact in fp32.  Accumulation and epilogue are fp32, and the result is rounded ONCE, to nearest
+even, at the store.  The stored value is therefore the nearest-even bf16 of a number v within e of the fp64 result r, and since that
+rounding is monotone
+
+    bf16(r - e) <= got <= bf16(r + e)   element-wise,   e = (alpha(K) + n_e 2^-24) S          (bf16_interval, bf16_slack)
+
+  - r: the fp64 spec on the bf16 inputs and the bf16_round-ed weights; S = sum |a_i b_i| + |bias| + |addend| + |resid| on the same
+    operands (conv_terms).  Where the interval [r - e, r + e] holds no rounding boundary, lo == hi: the output is PINNED to one bf16
+    value and the test is bit-exact there (96 % of the outputs on N(0, 1) data and on binades at K = 576); elsewhere two neighbours
+    are admitted - cancellation the fp32 sum cannot resolve, not a tolerance.  S = 0 gives e = 0: the answer is exact.
+  - alpha(K) is the constant above, unchanged: the chain's 2^-24 sqrt(K) plus 2^-22.  The bf16 operands need no 2^-22 (there is no
+    split to be inexact); it stays because alpha is the figure the f32- and f16-MFMA kernels were measured against (at most 0.65),
+    and the MFMA's summation inside a K = 16 / 32 block is not specified beyond "fp32".
+  - n_e: one 2^-24 S per fp32 epilogue operation every output passes through, added linearly as in the Winograd model: the bias
+    addition and the activation's multiplication by fp32(0.2) (plain launch, conv10_i / the 1x1, convmerge1: n_e = 2); the fused
+    launch adds the addend and the residual (4); conv10_i of a cut chain is finished by c10_finalize_bf16_kernel, which adds split_s
+    raw fp32 partial sums before the bias (2 + split_s).  The leaky-relu is a contraction (|lrelu(u) - lrelu(v)| <= |u - v|), so
+    the error in front of it passes through it unamplified.
+  - conv10_i inside the conv1_i + conv10_i launch reads conv1_i's ROUNDED tile from LDS: its spec is the 1x1 over the kernel's own
+    out1 (checked first), not over the fp64 out1.
+  - the fp32-output kernel (convmerge1, conv3x3_accum_bf16) has no store rounding: |got - r| <= e with K = 576 T.
+  - exact cases (bf16_ties): with a one-hot centre tap of weight 1 and a bias of +-2^(E - 8) on inputs of binade E the fp32 value in
+    front of the store is exact and lies exactly between two bf16 numbers (or, where the signs differ at the bottom of the binade,
+    on one); likewise zero weights, addend a > 0 of binade E and resid 2^(E - 8) in the fused launch.  The expectation is then
+    bf16_round(r) bit for bit: this is what tells round-half-even from round-half-away, which no interval can.  With a zero bias
+    the identity returns its input bit for bit - except that -0 comes back as +0, the accumulator starting from the bias +0
+    ((+0) + (-0) = +0 in IEEE arithmetic, and the other 575 products are zeros of either sign).
+bf16_emulate restates the rounding points in numpy fp32 (a sequential chain, exact products, + bias, + addend, max(o, 0.2f o), + resid,
+one RNE store; conv10_i from the rounded out1) and carries the faults of tests/test_bf16_numerics_host.py: a truncating store puts 48 %
+of the outputs outside the interval, a second rounding in front of "+ resid" 25 % on N(0, 1) data and 8 % on binades.  On the MI355X the
+kernels need at most 0.10 of e (3x3, 1x1), 0.26 (convmerge1) and 0.28 (conv0, against the split-f16 slack): test_gpu_bf16_numerics.py prints it.
 """
 import numpy as np
 
@@ -330,3 +364,301 @@ def _wino_raw_f32(x, k, per_tile, fault):
         s = np.stack([(acc[:, 0] + acc[:, 1]) + acc[:, 2], acc[:, 1] - (acc[:, 2] + acc[:, 3])])
         y = np.stack([(s[:, 0] + s[:, 1]) + s[:, 2], s[:, 1] - (s[:, 2] + s[:, 3])])
     return _untile(y)
+
+
+# ---- the bf16 model of the precision=bf16 kernels (module docstring) ----------------------------------------------------------
+
+def bf16_round(x):
+    """fp32 -> the fp32 value of its nearest-even bf16: bf16_rne of conv_bf16.hip bit for bit (NaN stays NaN)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    u = x.view(np.uint32).astype(np.uint64)
+    r = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000
+    r = np.where((u & 0x7fffffff) > 0x7f800000, (u | 0x400000) & 0xffff0000, r)
+    return r.astype(np.uint32).view(np.float32).reshape(x.shape)
+
+
+def bf16_trunc(x):
+    """fp32 -> bf16 by dropping the low 16 bits (a fault of the host test's mutants)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    return (x.view(np.uint32) & np.uint32(0xffff0000)).view(np.float32).reshape(x.shape)
+
+
+def bf16_round_away(x):
+    """fp32 -> bf16, ties away from zero (a fault of the host test's mutants)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    u = x.view(np.uint32).astype(np.uint64)
+    return ((u + 0x8000) & 0xffff0000).astype(np.uint32).view(np.float32).reshape(x.shape)
+
+
+def bf16_round64(r):
+    """fp64 -> the nearest-even bf16 (as fp32) in ONE rounding: 8 significant bits above 2^-126, the step 2^-133 below; a value just
+    off a bf16 tie does not collapse onto the tie in fp32 first.  Beyond bf16's largest finite value: infinity."""
+    r = np.asarray(r, np.float64)
+    _, ex = np.frexp(r)                                             # |r| = m 2^ex, m in [0.5, 1)
+    q = np.maximum(ex.astype(np.int64) - 8, -133)
+    with np.errstate(over="ignore"):
+        return np.ldexp(np.rint(np.ldexp(r, -q)), q).astype(np.float32)
+
+
+def bf16_bits(x):
+    """The 16-bit patterns of an array of bf16-representable fp32 values."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    assert not (x.view(np.uint32) & np.uint32(0xffff)).any(), "not bf16 values"
+    return (x.view(np.uint32) >> np.uint32(16)).astype(np.uint16).reshape(x.shape)
+
+
+def bf16_slack(K, n_e, S):
+    """e = (alpha(K) + n_e 2^-24) S: the distance of the fp32 value in front of the store from the fp64 result (module docstring)."""
+    return (alpha(K) + n_e * 2.0 ** -24) * np.asarray(S, np.float64)
+
+
+def bf16_interval(r, e):
+    """(lo, hi) = (bf16(r - e), bf16(r + e)), one rounding each: a correct kernel's output lies in [lo, hi] element-wise."""
+    r, e = np.asarray(r, np.float64), np.asarray(e, np.float64)
+    return bf16_round64(r - e), bf16_round64(r + e)
+
+
+def bf16_pinned(lo, hi):
+    """The elements whose interval admits one bf16 value only (the test is bit-exact there)."""
+    return lo == hi
+
+
+def bf16_outside(got, lo, hi):
+    """The elements of got outside [lo, hi]."""
+    got = np.asarray(got, np.float32)
+    return ~((lo <= got) & (got <= hi))
+
+
+def _bf16_neighbours(g):
+    """The bf16 numbers just below and just above every element of g (bf16 values as fp32), in fp64."""
+    b = bf16_bits(g).astype(np.int64)
+    k = np.where(b < 0x8000, b, -(b & 0x7fff))                      # ordered integers; +-0 -> 0
+    def val(k):
+        bits = np.where(k >= 0, k, 0x8000 | -k).astype(np.uint32) << np.uint32(16)
+        return bits.view(np.float32).astype(np.float64)
+    return val(k - 1), val(k + 1)
+
+
+def bf16_smallest_factor(got, r, e):
+    """The smallest c for which bf16_interval(r, c e) admits every element of got (bf16 values): per element the distance of r from
+    the rounding cell of got, in units of e (0 where got is the rounding of r itself; inf where e = 0 and it is not)."""
+    g = np.asarray(got, np.float32)
+    r, e = np.asarray(r, np.float64), np.asarray(e, np.float64)
+    below, above = _bf16_neighbours(g)
+    g64 = g.astype(np.float64)
+    d = np.maximum(np.maximum((g64 + below) / 2 - r, r - (g64 + above) / 2), 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = np.where(d == 0, 0.0, d / e)
+    return float(c.max()) if c.size else 0.0
+
+
+def bf16_spec(x, k, bias=None, addend=None, add_div=1, resid=None, act=True, n_e=None):
+    """(r, e) of one bf16 launch: the fp64 spec act(conv2d_same(x, bf16_round(k)) + bias + addend[item / add_div]) + resid on the bf16
+    inputs, and the slack (alpha(K) + n_e 2^-24) S.  x [items, H, W, C] (for the 1x1 and convmerge1: the concat over the frames);
+    n_e: 4 with an addend, else 2, unless given."""
+    from oracle import pfnl_spec
+    f64 = lambda a: None if a is None else np.asarray(a, np.float64)          # noqa: E731
+    kr = bf16_round(k)
+    y = pfnl_spec.conv2d_same(f64(x), f64(kr), f64(bias))
+    add = None if addend is None else np.repeat(f64(addend), add_div, axis=0)
+    if add is not None:
+        y = y + add
+    if act:
+        y = pfnl_spec.lrelu(y)
+    if resid is not None:
+        y = y + f64(resid)
+    S, _ = conv_terms(x, kr, (bias, add, resid))
+    if n_e is None:
+        n_e = 4 if addend is not None else 2
+    return y, bf16_slack(k.shape[0] * k.shape[1] * k.shape[2], n_e, S)
+
+
+def concat_frames(x, T):
+    """[clips T, H, W, 64] -> [clips, H, W, 64 T]: the reference's concat over the frames of a clip."""
+    F, H, W, c = x.shape
+    return x.reshape(F // T, T, H, W, c).transpose(0, 2, 3, 1, 4).reshape(F // T, H, W, T * c)
+
+
+# data families of the bf16 tests: activations are bf16 values; weights are NOT pre-rounded (the hooks round them, the spec with bf16_round)
+
+BF16_FAMILIES = ["normal", "binades", "bright", "dark16", "dark20", "bf16_edges"]
+
+
+def bf16_edges(rng, shape, lo=-120, hi=120):
+    """bf16 values at the format's edges: +-(s 2^-7) 2^u with 8-bit significands s in [128, 256) - half of them drawn from
+    255 (0x..7f: just below a power of two), 128, 129 / 253 (odd), 130 / 254 (even) - and u uniform over [lo, hi), 3 % zeros of either
+    sign, channel 5 (last axis) all zero.  Channel 0 stays below 2^(hi - 30): edge_weights(big=1e6) puts its large weight there and
+    results beyond bf16's largest finite value are not this test's subject."""
+    s = rng.integers(128, 256, size=shape)
+    pick = rng.random(shape) < 0.5
+    s[pick] = np.array([255, 128, 129, 253, 130, 254])[rng.integers(0, 6, size=int(pick.sum()))]
+    u = rng.integers(lo, hi, size=shape)
+    u[..., 0] = np.minimum(u[..., 0], hi - 30)
+    x = np.ldexp(s.astype(np.float64), u - 7) * rng.choice([-1.0, 1.0], size=shape)
+    x[rng.random(shape) < 0.03] = 0.0
+    x = x.astype(np.float32)
+    neg0 = rng.random(shape) < 0.5
+    x[(x == 0) & neg0] = -0.0
+    if shape[-1] > 5:
+        x[..., 5] = 0.0
+    return x
+
+
+def bf16_xdata(rng, fam, shape, hi=120):
+    """Activations of a bf16 family (bf16 values as fp32)."""
+    if fam == "normal":
+        return bf16_round(rng.normal(size=shape).astype(np.float32))
+    if fam == "binades":
+        return bf16_round(binades(rng, shape))
+    if fam == "bright":
+        return bf16_round(bright(rng, shape))
+    if fam == "bf16_edges":
+        return bf16_edges(rng, shape, hi=hi)
+    return bf16_round(dark(rng, shape, 2.0 ** -int(fam[4:])))
+
+
+def bf16_wdata(rng, fam, shape):
+    """Weights of a bf16 family, fp32 and not rounded: N(0, 1 / fan-in); bf16_edges: edge_weights with big=1e6."""
+    if fam == "bf16_edges":
+        return edge_weights(rng, shape, big=1.0e6)
+    return (rng.normal(size=shape) / np.sqrt(np.prod(shape[:-1]))).astype(np.float32)
+
+
+def bf16_bias(rng, fam, n):
+    """A bias at the family's scale, fp32 (the kernels take it unrounded); element 0 is zero.  normal: N(0, 1), as large as the
+    convolution itself - a zero-mean output passes through zero, where the slack spans many bf16 steps and the interval pins nothing;
+    the bias thins those outputs out (pinned share of the plain launch 0.90 with a bias of 0.1, the floor the tests hold the data to)."""
+    scale = {"dark16": 2.0 ** -18, "dark20": 2.0 ** -22, "bright": 2.0 ** 20, "normal": 1.0}.get(fam, 0.1)
+    b = (rng.normal(size=n) * scale).astype(np.float32)
+    b[0] = 0.0
+    return b
+
+
+def identity_kernel():
+    """HWIO [3, 3, 64, 64]: the centre tap is the identity, weight 1."""
+    k = np.zeros((3, 3, 64, 64), np.float32)
+    k[1, 1, np.arange(64), np.arange(64)] = 1.0
+    return k
+
+
+def bf16_ties_plain(rng, shape, elo=-20, ehi=20):
+    """(x, bias, want) of the plain identity launch with the activation off: channel c holds +-(s 2^-7) 2^E_c with random 8-bit
+    significands s, the bias is +-2^(E_c - 8) in fp32, so x + bias is exact in fp32 and lies exactly between two bf16 numbers (on
+    one where the signs differ and s = 128); want = bf16_round(x + bias)."""
+    C = shape[-1]
+    E = rng.integers(elo, ehi + 1, size=C)
+    x = (np.ldexp(rng.integers(128, 256, size=shape).astype(np.float64), E - 7) * rng.choice([-1.0, 1.0], size=shape)).astype(np.float32)
+    bias = (np.ldexp(1.0, E - 8) * rng.choice([-1.0, 1.0], size=C)).astype(np.float32)
+    r = x.astype(np.float64) + bias.astype(np.float64)
+    assert np.array_equal((x + bias).astype(np.float64), r)                  # exact in fp32
+    return x, bias, bf16_round(x + bias)
+
+
+def bf16_ties_fused(rng, clips, T, H, W, elo=-20, ehi=20):
+    """(addend, resid, want) of the fused launch with zero weights and zero bias: the addend a = (s 2^-7) 2^E > 0 with E drawn per
+    element of the clip, resid = 2^(E - 8) for each of its frames; act(0 + 0 + a) + resid = a + resid exactly, a bf16 tie."""
+    E = rng.integers(elo, ehi + 1, size=(clips, H, W, 64))
+    a = np.ldexp(rng.integers(128, 256, size=E.shape).astype(np.float64), E - 7).astype(np.float32)
+    resid = np.repeat(np.ldexp(1.0, E - 8).astype(np.float32), T, axis=0)
+    s = np.repeat(a, T, axis=0) + resid
+    assert np.array_equal(s.astype(np.float64), np.repeat(a, T, axis=0).astype(np.float64) + resid.astype(np.float64))
+    return a, resid, bf16_round(s)
+
+
+def identity_inputs(rng, shape):
+    """bf16 values over 60 binades with zeros of both signs among them, and what the zero-bias identity launch returns for them:
+    the input bit for bit, -0 as +0 (module docstring)."""
+    x = (np.ldexp(rng.integers(128, 256, size=shape).astype(np.float64), rng.integers(-37, 23, size=shape)) *
+         rng.choice([-1.0, 1.0], size=shape)).astype(np.float32)
+    z = rng.random(shape) < 0.05
+    x[z] = np.where(rng.random(int(z.sum())) < 0.5, np.float32(-0.0), np.float32(0.0))
+    return x, x + np.float32(0.0)
+
+
+BF16_FAULTS = ("trunc_store", "half_away", "round_before_resid", "trunc_weights", "c10_unrounded", "addend_mod", "resid_first")
+
+
+def _chain_f32(x, k):
+    """conv2d_same(x, k) as ONE sequential fp32 chain per output over (ky, kx, ci), every product formed exactly (bf16 operands: the
+    sum is formed in fp64 and rounded once to fp32); the accumulator starts from +0."""
+    f = np.float32
+    ks = k.shape[0]
+    p = ks // 2
+    B, H, W, C = x.shape
+    xp = np.pad(np.asarray(x, np.float64), ((0, 0), (p, p), (p, p), (0, 0)))
+    k64 = np.asarray(k, np.float64)
+    acc = np.zeros((B, H, W, k.shape[-1]), f)
+    for ky in range(ks):
+        for kx in range(ks):
+            win = xp[:, ky:ky + H, kx:kx + W]
+            for c in range(C):
+                acc = (acc.astype(np.float64) + win[..., c, None] * k64[ky, kx, c]).astype(f)
+    return acc
+
+
+def bf16_emulate(x, k, bias=None, addend=None, add_div=1, resid=None, act=True, k10=None, b10=None, T=1, out_f32=False, fault=None):
+    """numpy fp32 restatement of the bf16 kernels' rounding points (test infrastructure; the product never imports it).
+
+    x [items, H, W, C] bf16 values (for the 1x1 and convmerge1: the concat over the frames), k fp32 HWIO, rounded here as the hooks
+    round it.  Sequential fp32 chain with exact products; epilogue + bias, + addend[item / add_div], max(o, 0.2f o), + resid; one
+    nearest-even store (none with out_f32: convmerge1).  (The 3x3 kernels start the accumulator from the bias instead of adding it last:
+    another order of the same fp32 additions, inside the same slack.)  k10 / b10 / T: conv1_i + conv10_i, returns (out1, base) with base the
+    same restatement of the 1x1 over the ROUNDED out1.
+    fault (BF16_FAULTS, the host test's mutants): trunc_store - the store truncates; half_away - it rounds ties away from zero;
+    round_before_resid - the activation's result is rounded to bf16, then + resid, then rounded again; trunc_weights - the pack
+    truncates; c10_unrounded - conv10_i reads the fp32 out1; addend_mod - the addend of item % add_div; resid_first - the residual
+    goes in before the activation."""
+    f = np.float32
+    assert fault is None or fault in BF16_FAULTS, fault
+    store = {"trunc_store": bf16_trunc, "half_away": bf16_round_away}.get(fault, bf16_round)
+    wround = bf16_trunc if fault == "trunc_weights" else bf16_round
+    o = _chain_f32(x, wround(k))
+    if bias is not None:
+        o = o + np.asarray(bias, f)
+    if addend is not None:
+        item = np.arange(x.shape[0])
+        o = o + np.asarray(addend, f)[(item % add_div) % len(addend) if fault == "addend_mod" else item // add_div]
+    if fault == "resid_first" and resid is not None:
+        o = o + np.asarray(resid, f)
+    if act:
+        o = _lrelu_f32(o)
+    if resid is not None and fault != "resid_first":
+        if fault == "round_before_resid":
+            o = bf16_round(o)
+        o = o + np.asarray(resid, f)
+    out = o if out_f32 else store(o)
+    if k10 is None:
+        return out
+    b = _chain_f32(concat_frames(o if fault == "c10_unrounded" else out, T), wround(k10))
+    if b10 is not None:
+        b = b + np.asarray(b10, f)
+    return out, store(_lrelu_f32(b))
+
+
+BF16_MODES = ("plain", "fused", "c1c10", "1x1", "merge")
+
+
+def bf16_case(mode, fam, rng, clips, T, H, W, cout=64):
+    """The inputs of one bf16 launch on one family, as keyword arguments of bf16_emulate (x per frame: [clips T, H, W, 64]; the 1x1
+    and convmerge1 take concat_frames(x, T)).  c1c10 on bf16_edges keeps its inputs under 2^100: out1 feeds a second sum."""
+    F = clips * T
+    x = bf16_xdata(rng, fam, (F, H, W, 64), hi=100 if mode == "c1c10" else 120)
+    if mode == "1x1":
+        return dict(x=x, k=bf16_wdata(rng, fam, (1, 1, 64 * T, 64)), bias=bf16_bias(rng, fam, 64))
+    if mode == "merge":
+        return dict(x=x, k=bf16_wdata(rng, fam, (3, 3, 64 * T, cout)), bias=bf16_bias(rng, fam, cout))
+    kw = dict(x=x, k=bf16_wdata(rng, fam, (3, 3, 64, 64)), bias=bf16_bias(rng, fam, 64))
+    if mode == "fused":
+        kw.update(addend=bf16_xdata(rng, fam, (clips, H, W, 64)), add_div=T, resid=bf16_xdata(rng, fam, (F, H, W, 64)))
+    if mode == "c1c10":
+        kw.update(k10=bf16_wdata(rng, fam, (1, 1, 64 * T, 64)), b10=bf16_bias(rng, fam, 64), T=T)
+    return kw
+
+
+def bf16_report(got, r, e):
+    """(share outside [lo, hi], pinned share, pinned elements, pinned elements that match, smallest factor c) of a bf16 output."""
+    lo, hi = bf16_interval(r, e)
+    pin = bf16_pinned(lo, hi)
+    got = np.asarray(got, np.float32)
+    return (float(bf16_outside(got, lo, hi).mean()), float(pin.mean()), int(pin.sum()), int((pin & (got == lo)).sum()),
+            bf16_smallest_factor(got, r, e))

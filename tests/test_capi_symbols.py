@@ -43,6 +43,10 @@ def test_abi_v4_and_argument_validation_without_gpu():
     for f32 in (0, 1):                                                         # pfnl_op_conv0_ex: an addition to v4, same checks as pfnl_op_conv0
         assert lib.pfnl_op_conv0_ex(None, dummy, None, dummy, 1, 7, 8, 8, f32, None) == -1 and b"NULL" in lib.pfnl_last_error()
         assert lib.pfnl_op_conv0_ex(dummy, dummy, None, dummy, 1, 4, 8, 8, f32, None) == -1 and b"geometry" in lib.pfnl_last_error()
+    assert lib.pfnl_op_conv0_bf16(None, dummy, None, dummy, 1, 7, 8, 8, None) == -1 and b"NULL" in lib.pfnl_last_error()   # and its bf16 form
+    assert lib.pfnl_op_conv0_bf16(dummy, dummy, None, None, 1, 7, 8, 8, None) == -1 and b"NULL" in lib.pfnl_last_error()
+    assert lib.pfnl_op_conv0_bf16(dummy, dummy, None, dummy, 1, 4, 8, 8, None) == -1 and b"geometry" in lib.pfnl_last_error()
+    assert lib.pfnl_op_conv0_bf16(dummy, dummy, None, dummy, 1, 7, 7, 8, None) == -1 and b"geometry" in lib.pfnl_last_error()
     h = C.c_void_p()
     bad = _capi.pfnl_config(4, 4, 64, 20, 0, (C.c_int32 * 3)(0, 0, 0))        # even num_frames
     assert lib.pfnl_create(C.byref(bad), C.byref(h)) == -1
