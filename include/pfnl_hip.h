@@ -17,11 +17,28 @@
  * success or a negative pfnl_status; the message of the last failure on the calling thread is
  * available from pfnl_last_error().  A handle is bound to one device and is not re-entrant;
  * distinct handles are independent.  "device pointer" = memory accessible from that device
- * (e.g. a torch-ROCm tensor's data_ptr()); "stream" = a hipStream_t passed as void* (NULL = the
- * handle's own stream).  All tensors are float32 (the *_bf16 single-op hooks alone take bfloat16 bit patterns as
+ * (e.g. a torch-ROCm tensor's data_ptr()); "stream" = a hipStream_t passed as void* (NULL: see
+ * STREAMS below).  All tensors are float32 (the *_bf16 single-op hooks alone take bfloat16 bit patterns as
  * uint16_t), contiguous, NHWC-style as in the reference:
  *   input  [B, T, H, W, 3]      values nominally in [0,1]
  *   output [B, 1, s*H, s*W, 3]  not clipped (the harness clips, reference model/pfnl.py:255-257)
+ *
+ * STREAMS (tested on hipStreamNonBlocking streams: tests/test_gpu_streams.py).  An entry that takes `stream` and
+ * device pointers enqueues ALL its work on that stream and returns: nothing of it runs on, or waits for, another stream.  stream == NULL
+ * with device pointers is the legacy null stream itself (pfnl_forward, pfnl_forward_strip, the op hooks); host-pointer forwards and
+ * graph replays of a NULL-stream call run on the handle's own blocking stream, which the null stream orders implicitly, and a
+ * host-pointer call returns with its output filled.  A captured graph (option "graph") is captured and replayed on the caller's stream,
+ * between staging copies on that stream.  A session has two streams: the one given to pfnl_stream_open (gather, forward, quantisation,
+ * the edge kernels, device-pointer pushes and pops) and a non-blocking copy stream of its own (host-pointer pushes and pops, which
+ * return with the copy complete); pfnl_stream_scenes / _format / _resize are setup calls that allocate and may block.  The calls on one
+ * handle share its workspace: a caller that changes the stream between calls orders them itself (an event, or a synchronise), and plain
+ * forwards between the pushes of a session go on the session's stream.  pfnl_sync waits for the handle's own stream and the null
+ * stream, NOT for a stream of the caller's: synchronise that one first, then pfnl_sync or pfnl_range_flag reads the range flag of the
+ * device-pointer calls behind it.  Op hooks that synchronise `stream` before they return (they upload a weight pack or a table with a
+ * blocking copy, which goes through the null stream): every pfnl_op_* that takes host weights (the conv, non-local, conv0 and tail
+ * hooks), pfnl_op_resize_u8 / _u10 and pfnl_op_scene_sad_u8.  Asynchronous: pfnl_op_gather_windows / _u8 / _u8_scenes,
+ * pfnl_op_quantise_u8 / _u10, pfnl_op_yuv420_to_rgb_u8, pfnl_op_rgb_to_yuv420_u8 / _u10, pfnl_op_bicubic, pfnl_op_blur_decimate (its
+ * first call per device uploads a constant table), pfnl_op_score_y.
  */
 #ifndef PFNL_HIP_H
 #define PFNL_HIP_H

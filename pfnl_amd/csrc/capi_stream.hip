@@ -419,7 +419,11 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
         HIPCHK(hipSetDevice(s->device));
         const size_t words = 2 * (size_t)s->cap + 2;  // scene_first | sad | the sum's scratch (zero between launches)
         bool ok = hipMalloc(reinterpret_cast<void**>(&s->scene_first), words * sizeof(long long)) == hipSuccess;
-        ok = ok && hipMemset(s->scene_first, 0, words * sizeof(long long)) == hipSuccess;
+        // Zeroed on the copy stream and waited for: hipMemset on device memory is queued on the null stream and returns at once, and
+        // neither of the session's streams waits for the null stream when the caller's is non-blocking - behind a busy null stream it
+        // wiped the first frames' sums after the copy stream had written them.  The copy stream is idle here, so this waits for the fill alone.
+        ok = ok && hipMemsetAsync(s->scene_first, 0, words * sizeof(long long), s->cs) == hipSuccess;
+        ok = ok && hipStreamSynchronize(s->cs) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s->scene_ev, hipEventDisableTiming) == hipSuccess;
         for (int i = 0; i < 2; ++i)
             ok = ok && hipHostMalloc(reinterpret_cast<void**>(&s->info[i]), 2 * (size_t)s->cap * sizeof(long long), hipHostMallocDefault) == hipSuccess;
