@@ -37,7 +37,7 @@
  * device-pointer calls behind it.  Op hooks that synchronise `stream` before they return (they upload a weight pack or a table with a
  * blocking copy, which goes through the null stream): every pfnl_op_* that takes host weights (the conv, non-local, conv0 and tail
  * hooks), pfnl_op_resize_u8 / _u10 and pfnl_op_scene_sad_u8.  Asynchronous: pfnl_op_gather_windows / _u8 / _u8_scenes,
- * pfnl_op_quantise_u8 / _u10, pfnl_op_yuv420_to_rgb_u8, pfnl_op_rgb_to_yuv420_u8 / _u10, pfnl_op_bicubic, pfnl_op_blur_decimate (its
+ * pfnl_op_quantise_u8 / _u10, pfnl_op_yuv420_to_rgb_u8 / _u8_surface, pfnl_op_rgb_to_yuv420_u8 / _u10, pfnl_op_bicubic, pfnl_op_blur_decimate (its
  * first call per device uploads a constant table), pfnl_op_score_y.
  */
 #ifndef PFNL_HIP_H
@@ -307,7 +307,7 @@ int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long l
  *   the input side (RGB24, NV12, I420), scenes, the push bound, reset and the replay behind the range fence are what they are at 8 bits.
  *   As in_fmt the three are PFNL_ERR_INVALID (10-bit input is not built: it needs a 16-bit ring), and so is RGB10 out of a YUV in_fmt.
  *   The 16-bit output slots are allocated by the call that sets the format (PFNL_ERR_NOMEM) and freed by pfnl_stream_close.
- * Out of scope: pitched or padded planes, 10-bit input, 12 and 16 bits, 4:2:2 and 4:4:4, other sitings, transfer functions, BT.2020. */
+ * Out of scope: 10-bit input, 12 and 16 bits, 4:2:2 and 4:4:4, other sitings, transfer functions, BT.2020. */
 enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2, PFNL_PIX_RGB10 = 3, PFNL_PIX_P010 = 4, PFNL_PIX_I010 = 5 };
 enum { PFNL_MATRIX_BT601 = 0, PFNL_MATRIX_BT709 = 1 };
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range);
@@ -332,6 +332,35 @@ int pfnl_yuv10_coefficients(int matrix, int full_range, int32_t out[10]);  /* y0
 int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W);
 int pfnl_resize_max_taps(int n_in, int n_out, int* ntaps);
 int pfnl_resize_taps(int n_in, int n_out, int32_t* first /*[n_out]*/, int32_t* count /*[n_out]*/, int16_t* coef /*[n_out][ntaps]*/);
+/* SURFACES (additions to version 4; a session that calls neither function issues the launches and copies it always issued).  A hardware
+ * decoder or encoder hands out no packed frame: a surface is a pointer per plane and a row pitch per plane, rounded up to 64 or 256 bytes,
+ * with a coded height above the displayed one, so that CbCr does not start at Y + H * W.  pfnl_stream_push_surface and
+ * pfnl_stream_pop_surface are pfnl_stream_push and pfnl_stream_pop with the frame described that way, in the session's in_fmt and, for
+ * pop, its out_fmt and output size; a sequence may mix them with the packed calls, and every state rule is theirs (ended, "pop first",
+ * marks, the scene decision, the range check and the replay, pfnl_stream_pop_info, *got = 0).
+ *   planes of a frame of H x W, b = 1 byte per sample, 2 for RGB10 / P010 / I010:
+ *     RGB24 / RGB10: plane[0] = H rows of 3 W b bytes;  NV12 / P010: plane[0] = Y, H rows of W b, plane[1] = CbCr, H/2 rows of W b;
+ *     I420 / I010: plane[0] = Y, H rows of W b, plane[1] = Cb and plane[2] = Cr, H/2 rows of W/2 b each.  Entries past those are ignored.
+ *   the planes a format needs are non-NULL, all host pointers (is_device = 0) or all device pointers; pitch >= the bytes of a row; with
+ *     16-bit samples pointers and pitches are even.  Anything else is PFNL_ERR_INVALID (the message names the plane or the pitch) before
+ *     any HIP call and before any change to the session: pfnl_amd/csrc/surface_geom.h states the check once.
+ *   push, device pointers: NV12 / I420 are read in place by the one conversion kernel, on the session's stream, straight into the ring slot
+ *     (no staging pass; 16-byte words where W, every plane and every pitch are multiples of 16 - 8 for I420's chroma -, 4-byte words for
+ *     multiples of 4 - 2 -, else single bytes); RGB24 is one hipMemcpy2DAsync.  Host pointers: one pitched copy per plane on the copy
+ *     stream, YUV through the packed staging frame and the kernel; the caller's memory is free on return.
+ *   pop: the batch has been converted into its packed slot as ever; delivery is one hipMemcpy2DAsync per plane out of it (device pointers:
+ *     on the session's stream; host pointers: on the copy stream, complete on return).  Only the bytes of each row are written: what lies
+ *     between a row's end and the pitch is never touched.
+ *   a window of a larger surface needs no argument of its own: point plane[] at the first displayed sample (x and y even, so that the
+ *     chroma pointers are whole samples) and keep the surface's pitch - the frame is then that window, and chroma clamps at its edges.
+ * Out of scope: conversion kernels that write into the caller's surface (the conversion runs per batch, before a destination is known),
+ * 10-bit input, crop and letterbox arguments, odd sizes. */
+typedef struct pfnl_surface {
+    void*  plane[3];   /* RGB24 / RGB10: [0].  NV12 / P010: Y, CbCr.  I420 / I010: Y, Cb, Cr.  Unused entries are ignored. */
+    size_t pitch[3];   /* bytes from one row of that plane to the next */
+} pfnl_surface;
+int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_device);
+int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_device, long long* index, int* got);
 
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
@@ -614,6 +643,11 @@ int pfnl_op_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene
  * H / W, n < 1, an unknown fmt / matrix / full_range and fmt = PFNL_PIX_RGB24: PFNL_ERR_INVALID before any HIP call. */
 int pfnl_op_yuv420_to_rgb_u8(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, void* stream);
 int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, void* stream);
+/* The same decode of one frame given as a surface (SURFACES: device planes by pointer and pitch, NV12 or I420) -> rgb [H][W][3], tightly
+ * packed: the kernel a device-pointer pfnl_stream_push_surface runs, and byte for byte pfnl_op_yuv420_to_rgb_u8 of the packed frame.  A
+ * NULL or short surface is refused as there, before any HIP call. */
+int pfnl_op_yuv420_to_rgb_u8_surface(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W,
+                                     uint8_t* rgb /*[H][W][3] packed*/, void* stream);
 /* The session's resampler (pfnl_stream_resize; the rule: pfnl_amd/resize.py).  in [n][H][W][3] uint8 -> out [n][oH][oW][3] uint8, device
  * pointers, asynchronous on stream up to the hook's own synchronisation (it uploads the tap tables and frees them on return).  One launch
  * does both passes through an int16 LDS tile; any alignment (16-byte stores where oW is a multiple of 16 and out is aligned, single bytes

@@ -31,6 +31,11 @@ class pfnl_config(C.Structure):
                 ("num_block", C.c_int32), ("device_id", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class pfnl_surface(C.Structure):
+    """A frame as plane pointers with a row pitch each (include/pfnl_hip.h SURFACES)."""
+    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/pfnl_hip.h declares
 _vp, _i, _fp = C.c_void_p, C.c_int, C.POINTER(C.c_float)
 SIGNATURES = {
@@ -117,6 +122,9 @@ SIGNATURES = {
     "pfnl_yuv10_coefficients": (_i, [_i, _i, C.POINTER(C.c_int32)]),
     "pfnl_op_rgb_to_yuv420_u10": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_stream_resize": (_i, [_vp, _i, _i]),
+    "pfnl_stream_push_surface": (_i, [_vp, C.POINTER(pfnl_surface), _i]),
+    "pfnl_stream_pop_surface": (_i, [_vp, C.POINTER(pfnl_surface), _i, C.POINTER(C.c_longlong), C.POINTER(_i)]),
+    "pfnl_op_yuv420_to_rgb_u8_surface": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_resize_max_taps": (_i, [_i, _i, C.POINTER(_i)]),
     "pfnl_resize_taps": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]),
     "pfnl_op_resize_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -4,6 +4,9 @@
 
 #include <string>
 
+#include "../../include/pfnl_hip.h"
+#include "common.h"
+
 int pfnl_internal_fail(int code, const std::string& msg);   // records msg for pfnl_last_error(); returns code
 
 // return PFNL_ERR_HIP from the enclosing C-ABI function when a HIP call fails
@@ -24,6 +27,12 @@ struct pfnl_handle_view {
     pfnl_stream** session;
 };
 pfnl_handle_view pfnl_internal_view(pfnl_handle* h);
+
+// An NV12 / I420 surface that surface_refused (surface_geom.h) has passed, as the decode kernel's one frame of planes
+inline pfnl::YuvPlanes pfnl_internal_yuv_planes(const pfnl_surface& sf, bool nv12) {
+    return pfnl::YuvPlanes{static_cast<const uint8_t*>(sf.plane[0]), static_cast<const uint8_t*>(sf.plane[1]),
+                           nv12 ? nullptr : static_cast<const uint8_t*>(sf.plane[2]), sf.pitch[0], sf.pitch[1], nv12 ? 0 : sf.pitch[2], 0};
+}
 
 // The 1x1 convolutions of the non-local block folded on the host in fp64 (reference utils.py:18-71), as pfnl_finalize_weights and the op
 // hooks use them.  Inputs are [C][C] row-major (in, out); the folded matrices are written with row stride CP (>= C + 1).

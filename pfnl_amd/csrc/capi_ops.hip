@@ -10,6 +10,7 @@
 #include "conv_bf16.h"
 #include "conv_small.h"
 #include "conv_split16.h"
+#include "surface_geom.h"
 
 namespace {
 
@@ -965,6 +966,15 @@ int pfnl_op_yuv420_to_rgb_u8(const uint8_t* yuv, int fmt, int matrix, int full_r
     pfnl::YuvCoef c;
     if (int r = yuv_op_refused(yuv, rgb, fmt, matrix, full_range, n, H, W, &c)) return r;
     HIPCHK(pfnl::launch_yuv420_to_rgb_u8(yuv, rgb, fmt == PFNL_PIX_NV12, c, n, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_yuv420_to_rgb_u8_surface(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint8_t* rgb, void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = yuv_op_refused(yuv, rgb, fmt, matrix, full_range, 1, H, W, &c)) return r;
+    if (const char* why = pfnl::surface_refused(yuv, fmt, H, W)) return fail(PFNL_ERR_INVALID, why);
+    HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*yuv, fmt == PFNL_PIX_NV12), rgb, fmt == PFNL_PIX_NV12, c, 1, H, W,
+                                                (hipStream_t)stream));
     return 0;
 }
 

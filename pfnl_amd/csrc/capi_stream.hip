@@ -10,6 +10,7 @@
 #include "../../include/pfnl_hip.h"
 #include "capi_internal.h"
 #include "common.h"
+#include "surface_geom.h"
 
 namespace {
 
@@ -223,6 +224,93 @@ int drop_sequence(pfnl_stream* s) {
     return r;
 }
 
+// What every push is, around the step that puts the frame into its ring slot as RGB: the state rules first (nothing has changed where
+// one of them refuses), then on_device(slot) on the session's stream or on_host(slot) on the copy stream, the scene decision behind it,
+// the synchronisation that frees the caller's host memory, and the batches the frame completes.
+template <class OnDevice, class OnHost>
+int push_frame(pfnl_stream* s, int is_device, OnDevice&& on_device, OnHost&& on_host) {
+    if (s->ended) return fail(PFNL_ERR_STATE, "push after pfnl_stream_end (pfnl_stream_reset starts the next sequence)");
+    long long first = 0;
+    int count = 0;
+    if (int e = pfnl_stream_next_batch(s->T, s->batch, s->pushed + 1, 0, s->launched, &first, &count)) return e;
+    const long long oldest = s->q.empty() ? s->launched : s->q.front().first;
+    const long long lo = oldest - s->T / 2 < 0 ? 0 : oldest - s->T / 2;
+    if ((count && s->launched - s->delivered + count > 2LL * s->batch) || s->pushed - lo + 1 > s->cap)
+        return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
+    HIPCHK(hipSetDevice(s->device));
+    uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->lr_bytes;
+    if (is_device) {
+        if (int e = on_device(dst)) return e;
+        if (s->scene_mode) {                          // behind the copy, ahead of any gather that can name the frame
+            if (int e = decide_scene(s, s->s)) return e;
+            HIPCHK(hipEventRecord(s->scene_ev, s->s));
+            s->decided_on_s = true;
+        }
+    } else {
+        // the slot's previous frame belongs to batches that have been delivered, so nothing on the session's stream reads it; the copy
+        // runs beside the batches in flight and the caller's buffer is free on return
+        // With scenes on, the frame's sum and decision go on the copy stream as well, so that they are complete when push returns: on
+        // the session's stream they could still be queued behind a long forward when the copy of frame f + cap - 1 overwrites the slot
+        // they have yet to read.  They read the frame before and its decision, and share the sum's scratch: where those came through
+        // device-pointer pushes they are on the session's stream, and the copy stream falls in behind them first.
+        if (s->scene_mode && s->decided_on_s) {
+            HIPCHK(hipStreamWaitEvent(s->cs, s->scene_ev, 0));
+            s->decided_on_s = false;
+        }
+        if (int e = on_host(dst)) return e;
+        if (s->scene_mode)
+            if (int e = decide_scene(s, s->cs)) return e;
+        HIPCHK(hipStreamSynchronize(s->cs));
+    }
+    s->mark = false;
+    ++s->pushed;
+    return pump(s);
+}
+
+// What every pop is, around the copy that delivers: the batch at the front, checked (and replayed) once; deliver(src, bytes, on) copies
+// the packed frame at src out on the session's stream (device pointers: ordered like the caller's own work there) or the copy stream
+// (host pointers: the batch has completed, no wait for a later one; synchronised here); then the scene info, the index, the slot's
+// release and the options' return.  *got = 0: no frame is deliverable and deliver has not run.
+template <class Deliver>
+int pop_frame(pfnl_stream* s, int is_device, long long* index, int* got, Deliver&& deliver) {
+    *got = 0;
+    HIPCHK(hipSetDevice(s->device));
+    if (int e = pump(s)) return e;
+    if (s->q.empty()) return 0;
+    Batch& b = s->q.front();
+    if (!b.checked)
+        if (int e = check_batch(s, b)) return e;
+    const bool yuv_out = is_420(s->out_fmt), ten = is_10bit(s->out_fmt);
+    const size_t bytes = (yuv_out ? s->out_bytes() / 2 : s->out_bytes()) * (ten ? 2 : 1);
+    const uint8_t* const slot = ten ? reinterpret_cast<const uint8_t*>(yuv_out ? s->yout10[b.slot] : (s->rplan.oH ? s->rout10[b.slot] : s->out10[b.slot]))
+                                    : (yuv_out ? s->yout[b.slot] : (s->rplan.oH ? s->rout[b.slot] : s->out[b.slot]));
+    const uint8_t* const src = slot + (size_t)(s->delivered - b.first) * bytes;
+    if (is_device) {
+        if (int e = deliver(src, bytes, s->s)) return e;
+    } else {
+        if (int e = deliver(src, bytes, s->cs)) return e;
+        HIPCHK(hipStreamSynchronize(s->cs));
+    }
+    if (s->scene_mode) {                              // (the copy is ahead of the batch's event, which check_batch has waited for)
+        const int slot = (int)(s->delivered % s->cap);
+        s->info_first = s->info[b.slot][slot];
+        s->info_sad = (unsigned long long)s->info[b.slot][s->cap + slot];
+    } else {
+        s->info_first = 0;
+        s->info_sad = 0;
+    }
+    s->has_info = true;
+    *index = s->delivered++;
+    *got = 1;
+    if (s->delivered == b.first + b.count) {
+        s->slot_busy[b.slot] = false;                 // (a device-pointer copy out of it is ahead of the next batch on the same stream)
+        s->q.pop_front();
+        if (int e = pump(s)) return e;
+        if (s->ended && s->delivered == s->pushed) return restore_options(s);   // (every forward has completed: its batch was checked)
+    }
+    return 0;
+}
+
 void release(pfnl_stream* s) {
     for (int i = 0; i < 2; ++i) {
         if (s->out[i]) (void)hipFree(s->out[i]);
@@ -307,51 +395,52 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
 
 int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
     if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (s->ended) return fail(PFNL_ERR_STATE, "push after pfnl_stream_end (pfnl_stream_reset starts the next sequence)");
-    long long first = 0;
-    int count = 0;
-    if (int e = pfnl_stream_next_batch(s->T, s->batch, s->pushed + 1, 0, s->launched, &first, &count)) return e;
-    const long long oldest = s->q.empty() ? s->launched : s->q.front().first;
-    const long long lo = oldest - s->T / 2 < 0 ? 0 : oldest - s->T / 2;
-    if ((count && s->launched - s->delivered + count > 2LL * s->batch) || s->pushed - lo + 1 > s->cap)
-        return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
-    HIPCHK(hipSetDevice(s->device));
-    uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->lr_bytes;
     const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24;  // the frame is H*W*3/2 bytes and reaches its slot through the kernel, as RGB
-    if (is_device) {
-        if (yuv_in)
-            HIPCHK(pfnl::launch_yuv420_to_rgb_u8(frame, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->s));
-        else
-            HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
-        if (s->scene_mode) {                          // behind the copy, ahead of any gather that can name the frame
-            if (int e = decide_scene(s, s->s)) return e;
-            HIPCHK(hipEventRecord(s->scene_ev, s->s));
-            s->decided_on_s = true;
-        }
-    } else {
-        // the slot's previous frame belongs to batches that have been delivered, so nothing on the session's stream reads it; the copy
-        // runs beside the batches in flight and the caller's buffer is free on return
-        // With scenes on, the frame's sum and decision go on the copy stream as well, so that they are complete when push returns: on
-        // the session's stream they could still be queued behind a long forward when the copy of frame f + cap - 1 overwrites the slot
-        // they have yet to read.  They read the frame before and its decision, and share the sum's scratch: where those came through
-        // device-pointer pushes they are on the session's stream, and the copy stream falls in behind them first.
-        if (s->scene_mode && s->decided_on_s) {
-            HIPCHK(hipStreamWaitEvent(s->cs, s->scene_ev, 0));
-            s->decided_on_s = false;
-        }
-        if (yuv_in) {                                 // (the staging frame is free again: every push ends with the copy stream idle)
-            HIPCHK(hipMemcpyAsync(s->yin, frame, s->lr_bytes / 2, hipMemcpyHostToDevice, s->cs));
-            HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->cs));
-        } else {
-            HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
-        }
-        if (s->scene_mode)
-            if (int e = decide_scene(s, s->cs)) return e;
-        HIPCHK(hipStreamSynchronize(s->cs));
-    }
-    s->mark = false;
-    ++s->pushed;
-    return pump(s);
+    return push_frame(
+        s, is_device,
+        [&](uint8_t* dst) {
+            if (yuv_in)
+                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(frame, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->s));
+            else
+                HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
+            return 0;
+        },
+        [&](uint8_t* dst) {
+            if (yuv_in) {                             // (the staging frame is free again: every push ends with the copy stream idle)
+                HIPCHK(hipMemcpyAsync(s->yin, frame, s->lr_bytes / 2, hipMemcpyHostToDevice, s->cs));
+                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->cs));
+            } else {
+                HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
+            }
+            return 0;
+        });
+}
+
+int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_device) {
+    if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (const char* why = pfnl::surface_refused(frame, s->in_fmt, s->H, s->W)) return fail(PFNL_ERR_INVALID, why);
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->in_fmt, s->H, s->W);
+    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24, nv12 = s->in_fmt == PFNL_PIX_NV12;
+    return push_frame(
+        s, is_device,
+        [&](uint8_t* dst) {                           // YUV: the kernel reads the surface where it lies
+            if (yuv_in)
+                HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*frame, nv12), dst, nv12, s->coef, 1, s->H, s->W, s->s));
+            else
+                HIPCHK(hipMemcpy2DAsync(dst, g.plane[0].row_bytes, frame->plane[0], frame->pitch[0], g.plane[0].row_bytes, g.plane[0].rows,
+                                        hipMemcpyDeviceToDevice, s->s));
+            return 0;
+        },
+        [&](uint8_t* dst) {                           // YUV: the planes packed into the staging frame, then the packed push's kernel
+            uint8_t* to = yuv_in ? s->yin : dst;
+            for (int k = 0; k < g.planes; ++k) {
+                HIPCHK(hipMemcpy2DAsync(to, g.plane[k].row_bytes, frame->plane[k], frame->pitch[k], g.plane[k].row_bytes, g.plane[k].rows,
+                                        hipMemcpyHostToDevice, s->cs));
+                to += g.plane[k].rows * g.plane[k].row_bytes;
+            }
+            if (yuv_in) HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, nv12, s->coef, 1, s->H, s->W, s->cs));
+            return 0;
+        });
 }
 
 int pfnl_stream_end(pfnl_stream* s) {
@@ -371,42 +460,24 @@ int pfnl_stream_ready(pfnl_stream* s, int* frames) {
 
 int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* index, int* got) {
     if (!s || !out || !index || !got) return fail(PFNL_ERR_INVALID, "NULL argument");
-    *got = 0;
-    HIPCHK(hipSetDevice(s->device));
-    if (int e = pump(s)) return e;
-    if (s->q.empty()) return 0;
-    Batch& b = s->q.front();
-    if (!b.checked)
-        if (int e = check_batch(s, b)) return e;
-    const bool yuv_out = is_420(s->out_fmt), ten = is_10bit(s->out_fmt);
-    const size_t bytes = (yuv_out ? s->out_bytes() / 2 : s->out_bytes()) * (ten ? 2 : 1);
-    const uint8_t* const slot = ten ? reinterpret_cast<const uint8_t*>(yuv_out ? s->yout10[b.slot] : (s->rplan.oH ? s->rout10[b.slot] : s->out10[b.slot]))
-                                    : (yuv_out ? s->yout[b.slot] : (s->rplan.oH ? s->rout[b.slot] : s->out[b.slot]));
-    const uint8_t* const src = slot + (size_t)(s->delivered - b.first) * bytes;
-    if (is_device) {
-        HIPCHK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToDevice, s->s));   // ordered like the caller's own work on that stream
-    } else {
-        HIPCHK(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, s->cs));    // the batch has completed: no wait for a later one
-        HIPCHK(hipStreamSynchronize(s->cs));
-    }
-    if (s->scene_mode) {                              // (the copy is ahead of the batch's event, which check_batch has waited for)
-        const int slot = (int)(s->delivered % s->cap);
-        s->info_first = s->info[b.slot][slot];
-        s->info_sad = (unsigned long long)s->info[b.slot][s->cap + slot];
-    } else {
-        s->info_first = 0;
-        s->info_sad = 0;
-    }
-    s->has_info = true;
-    *index = s->delivered++;
-    *got = 1;
-    if (s->delivered == b.first + b.count) {
-        s->slot_busy[b.slot] = false;                 // (a device-pointer copy out of it is ahead of the next batch on the same stream)
-        s->q.pop_front();
-        if (int e = pump(s)) return e;
-        if (s->ended && s->delivered == s->pushed) return restore_options(s);   // (every forward has completed: its batch was checked)
-    }
-    return 0;
+    return pop_frame(s, is_device, index, got, [&](const uint8_t* src, size_t bytes, hipStream_t on) {
+        HIPCHK(hipMemcpyAsync(out, src, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, on));
+        return 0;
+    });
+}
+
+int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_device, long long* index, int* got) {
+    if (!s || !out || !index || !got) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (const char* why = pfnl::surface_refused(out, s->out_fmt, s->out_h(), s->out_w())) return fail(PFNL_ERR_INVALID, why);
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->out_fmt, s->out_h(), s->out_w());
+    return pop_frame(s, is_device, index, got, [&](const uint8_t* src, size_t, hipStream_t on) {
+        for (int k = 0; k < g.planes; ++k) {          // the packed frame is its planes one behind the other: rows of row_bytes, nothing between
+            HIPCHK(hipMemcpy2DAsync(out->plane[k], out->pitch[k], src, g.plane[k].row_bytes, g.plane[k].row_bytes, g.plane[k].rows,
+                                    is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, on));
+            src += g.plane[k].rows * g.plane[k].row_bytes;
+        }
+        return 0;
+    });
 }
 
 int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {

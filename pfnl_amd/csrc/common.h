@@ -188,6 +188,14 @@ struct YuvCoef {
 bool yuv_coefficients(int matrix, int full_range, YuvCoef* c);   // matrix 0 BT.601 | 1 BT.709; false: unknown matrix or range (no device needed)
 // yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow)
 hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+// The decode's source as planes: H rows of W bytes at y; NV12: H/2 rows of W bytes (Cb, Cr interleaved) at cb, cr unused; I420: H/2 rows of
+// W/2 bytes at cb and at cr.  pitch_*: bytes from one row to the next (>= the row); frame: bytes from one frame's planes to the next's.
+struct YuvPlanes {
+    const uint8_t *y, *cb, *cr;
+    size_t pitch_y, pitch_cb, pitch_cr, frame;
+};
+// the same kernel on planes (the packed launcher calls this with pitch W, W/2): words where W, every plane, every pitch and rgb allow
+hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
 hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
 // 10 bits, uint16 samples (depth10.hip; the rule: pfnl_amd/depth10.py): y0 and the encode side of the table for 64 .. 940 / 64 .. 960 or
 // full range (the decode side stays zero); rgb [n][H][W][3] with values 0 .. 1023 -> P010 (samples << 6) or I010; H, W even; any alignment

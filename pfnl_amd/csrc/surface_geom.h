@@ -1,0 +1,59 @@
+// THE GEOMETRY OF A SURFACE (include/pfnl_hip.h SURFACES): the planes a pixel format has, the rows and the bytes per row of each for a frame
+// of H x W, and the one check every entry that takes a pfnl_surface makes before it touches the device or its session.  No HIP types and
+// no HIP runtime calls: a plain C++ program can include this file and walk the rule (tests/test_surface_host.py does).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/pfnl_hip.h"
+
+namespace pfnl {
+
+struct SurfacePlane {
+    int rows;
+    size_t row_bytes;        // the bytes of a row that hold samples; the pitch is at least this
+};
+
+struct SurfaceGeom {
+    int planes;              // 1 (RGB24 / RGB10), 2 (NV12 / P010) or 3 (I420 / I010); 0: no such format
+    int sample_bytes;        // 1, or 2 for the 10-bit formats
+    SurfacePlane plane[3];
+};
+
+// H and W are the frame's (even for the 4:2:0 formats: the entries check that with their own geometry)
+inline SurfaceGeom surface_geom(int fmt, int H, int W) {
+    SurfaceGeom g{};
+    if (fmt < PFNL_PIX_RGB24 || fmt > PFNL_PIX_I010 || H < 1 || W < 1) return g;
+    const size_t b = fmt >= PFNL_PIX_RGB10 ? 2 : 1, w = (size_t)W;
+    g.sample_bytes = (int)b;
+    if (fmt == PFNL_PIX_RGB24 || fmt == PFNL_PIX_RGB10) {
+        g.planes = 1;
+        g.plane[0] = {H, 3 * w * b};
+    } else if (fmt == PFNL_PIX_NV12 || fmt == PFNL_PIX_P010) {
+        g.planes = 2;
+        g.plane[0] = {H, w * b};
+        g.plane[1] = {H / 2, w * b};                 // Cb and Cr interleaved: W / 2 pairs
+    } else {
+        g.planes = 3;
+        g.plane[0] = {H, w * b};
+        g.plane[1] = g.plane[2] = {H / 2, w / 2 * b};
+    }
+    return g;
+}
+
+// nullptr: `sf` describes a frame of H x W in `fmt`; else what is wrong with it, in words that name the plane or the pitch.  Entries past
+// the format's planes are not looked at.
+inline const char* surface_refused(const pfnl_surface* sf, int fmt, int H, int W) {
+    if (!sf) return "NULL argument";
+    const SurfaceGeom g = surface_geom(fmt, H, W);
+    if (!g.planes) return "surface: no plane layout for this format and size";
+    for (int k = 0; k < g.planes; ++k) {
+        if (!sf->plane[k]) return "surface: a plane the format needs is NULL";
+        if (sf->pitch[k] < g.plane[k].row_bytes) return "surface: a pitch is smaller than the bytes of a row of its plane";
+        if (g.sample_bytes == 2 && ((reinterpret_cast<uintptr_t>(sf->plane[k]) | sf->pitch[k]) & 1))
+            return "surface: 16-bit samples need an even plane pointer and an even pitch";
+    }
+    return nullptr;
+}
+
+}  // namespace pfnl

@@ -4,6 +4,7 @@
 // Both kernels move bytes - 1.5 per pixel on one side, 3 on the other.  A lane owns a strip of two luma rows by P pixels, so that the chroma
 // samples it reads (or forms) serve both rows; P = 16 reads and writes 16-byte words (8-byte ones for I420's half-width planes), P = 4
 // 4-byte words (2-byte ones), P = 2 single bytes: any even H, W and any pointer.  Edges are index clamps inside the one kernel.
+// The decode reads its planes by pointer and row pitch, so a decoder's surface (include/pfnl_hip.h SURFACES) and a packed frame are one kernel.
 #include <cmath>
 
 #include "common.h"
@@ -116,22 +117,24 @@ __device__ __forceinline__ int shift_clip_u8(int v) {
 
 }  // namespace
 
-// yuv [n][H*W*3/2] -> rgb [n][H][W][3].  Strip k of 0 .. H/2 is the luma rows 2k - 1 and 2k: exactly the two rows that lie between the
+// planes of n frames -> rgb [n][H][W][3].  A frame is its planes by pointer and row pitch (common.h YuvPlanes): W, and W / 2 for I420's
+// chroma, in a tightly packed frame, whatever the decoder chose in a surface; frame f lies f * src.frame bytes behind the first.
+// Strip k of 0 .. H/2 is the luma rows 2k - 1 and 2k: exactly the two rows that lie between the
 // chroma rows k - 1 and k, each three quarters its near row and one quarter the other (yuv.py upsample); row -1 and row H do not exist,
 // and there the missing chroma row clamps onto the present one.  Per row and plane a lane reads P/2 samples and the one to their right.
 template <int P, bool NV12>
-__global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __restrict__ yuv, uint8_t* __restrict__ rgb, int n, int H,
-                                                               int W, YuvCoef c) {
+__global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, uint8_t* __restrict__ rgb, int n, int H, int W, YuvCoef c) {
     constexpr bool WORDS = P > 2;
     constexpr int HP = P / 2;
     const int gw = W / P, strips = H / 2 + 1, hh = H >> 1, hw = W >> 1;
-    const size_t plane = (size_t)H * W, total = (size_t)n * strips * gw;
+    const size_t total = (size_t)n * strips * gw;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const int g = (int)(t % gw);
         const size_t fk = t / gw;
         const int k = (int)(fk % strips);
         const size_t f = fk / strips;
-        const uint8_t* const fr = yuv + f * (plane + plane / 2);
+        const uint8_t* __restrict__ const fy = src.y + f * src.frame;
+        const uint8_t* __restrict__ const fb = src.cb + f * src.frame;   // (NV12: Cb and Cr interleaved)
         const int x0 = g * P, i0 = x0 >> 1;
         const int ie = i0 + HP < hw ? i0 + HP : hw - 1;
         const int jrow[2] = {k > 0 ? k - 1 : 0, k < hh ? k : hh - 1};
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             if constexpr (NV12) {
-                const uint8_t* const p = fr + plane + (size_t)jrow[a] * W;
+                const uint8_t* const p = fb + (size_t)jrow[a] * src.pitch_cb;
                 int pair[P], e[2];
                 load_bytes<P, WORDS>(p + x0, pair);
                 load_bytes<2, WORDS>(p + 2 * ie, e);
@@ -147,8 +150,8 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __
                 for (int q = 0; q < HP; ++q) cb[a][q] = pair[2 * q], cr[a][q] = pair[2 * q + 1];
                 cb[a][HP] = e[0], cr[a][HP] = e[1];
             } else {
-                const uint8_t* const pb = fr + plane + (size_t)jrow[a] * hw;
-                const uint8_t* const pr = pb + (size_t)hh * hw;
+                const uint8_t* const pb = fb + (size_t)jrow[a] * src.pitch_cb;
+                const uint8_t* const pr = src.cr + f * src.frame + (size_t)jrow[a] * src.pitch_cr;
                 load_bytes<HP, WORDS>(pb + i0, cb[a]);
                 load_bytes<HP, WORDS>(pr + i0, cr[a]);
                 cb[a][HP] = pb[ie], cr[a][HP] = pr[ie];
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(const uint8_t* __
             const int y = 2 * k - 1 + a;
             if (y < 0 || y >= H) continue;
             int luma[P], out[3 * P];
-            load_bytes<P, WORDS>(fr + (size_t)y * W + x0, luma);
+            load_bytes<P, WORDS>(fy + (size_t)y * src.pitch_y + x0, luma);
 #pragma unroll
             for (int px = 0; px < P; ++px) {
                 const int q = px >> 1;
@@ -253,15 +256,32 @@ bool yuv_geometry_ok(const void* a, const void* b, int n, int H, int W) { return
 
 }  // namespace
 
-hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
-    if (!yuv_geometry_ok(yuv, rgb, n, H, W)) return hipErrorInvalidValue;
-    const int P = strip_width(yuv, rgb, W);
+namespace {
+
+// The strip width the decode runs with.  Every word is read or written at plane + row * pitch (+ f * frame) + a multiple of its size, so
+// the planes, their pitches, the frame stride and rgb (rows of 3 W bytes) all have to be multiples of it: 16 | 4 for the full-width planes
+// and rgb, half of that for I420's chroma planes, whose words are half as wide.  A tightly packed frame gives what strip_width gives.
+int decode_strip_width(const YuvPlanes& p, const void* rgb, bool nv12, int W) {
+    const auto bits = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    const uintptr_t full = bits(p.y) | p.pitch_y | p.frame | bits(rgb) | (nv12 ? bits(p.cb) | p.pitch_cb : 0);
+    const uintptr_t half = nv12 ? 0 : bits(p.cb) | bits(p.cr) | p.pitch_cb | p.pitch_cr;
+    if (W % 16 == 0 && full % 16 == 0 && half % 8 == 0) return 16;
+    if (W % 4 == 0 && full % 4 == 0 && half % 2 == 0) return 4;
+    return 2;
+}
+
+}  // namespace
+
+hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+    if (!yuv_geometry_ok(src.y, rgb, n, H, W) || !src.cb || (!nv12 && !src.cr)) return hipErrorInvalidValue;
+    if (src.pitch_y < (size_t)W || src.pitch_cb < (size_t)(nv12 ? W : W / 2) || (!nv12 && src.pitch_cr < (size_t)(W / 2))) return hipErrorInvalidValue;
+    const int P = decode_strip_width(src, rgb, nv12, W);
     const dim3 grid(strip_blocks((size_t)n * (H / 2 + 1) * (W / P))), block(256);
 #define PFNL_YUV_LAUNCH(P_)                                                                                        \
     if (nv12)                                                                                                      \
-        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, true>), grid, block, 0, s, yuv, rgb, n, H, W, c);          \
+        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, true>), grid, block, 0, s, src, rgb, n, H, W, c);          \
     else                                                                                                           \
-        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, false>), grid, block, 0, s, yuv, rgb, n, H, W, c)
+        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, false>), grid, block, 0, s, src, rgb, n, H, W, c)
     if (P == 16) {
         PFNL_YUV_LAUNCH(16);
     } else if (P == 4) {
@@ -271,6 +291,14 @@ hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, 
     }
 #undef PFNL_YUV_LAUNCH
     return hipGetLastError();
+}
+
+// the packed frames as planes: the same kernel, the same strip width as ever
+hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+    if (!yuv_geometry_ok(yuv, rgb, n, H, W)) return hipErrorInvalidValue;
+    const size_t plane = (size_t)H * W, hw = (size_t)W / 2;
+    const YuvPlanes src{yuv, yuv + plane, nv12 ? nullptr : yuv + plane + plane / 4, (size_t)W, nv12 ? (size_t)W : hw, nv12 ? 0 : hw, plane + plane / 2};
+    return launch_yuv420_planes_to_rgb_u8(src, rgb, nv12, c, n, H, W, s);
 }
 
 hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {

@@ -527,6 +527,30 @@ def yuv420_to_rgb(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_
     return out.view(n, H, W, 3)
 
 
+def yuv420_to_rgb_surface(planes, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None):
+    """One NV12 / I420 frame given as its planes - uint8 tensors (cuda), each a strided view with a row pitch of its own, as
+    pfnl_amd/surface.py describes them: typically ``surface[:H, :W]`` of a decoder's pitched allocation -> [H,W,3] uint8, byte for byte
+    pfnl_amd/yuv.py to_rgb of the packed frame (pfnl_op_yuv420_to_rgb_u8_surface: the kernel a device push_planes runs).  Any pointer and
+    any pitch; ``out``: write there."""
+    import torch
+    from . import surface as _surface
+    lib = _capi.load_library()
+    ids = _yuv_ids(fmt, matrix, full_range)
+    planes = tuple(planes)
+    for k, p in enumerate(planes):
+        if not (isinstance(p, torch.Tensor) and p.is_cuda and p.device == planes[0].device):
+            raise TypeError(f"plane {k} must be a tensor on the GPU, all on one device")
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"H and W must be even and at least 2, got {H} x {W}")
+    sf = _surface.as_struct(planes, fmt, H, W)
+    if out is None:
+        out = torch.empty((H, W, 3), dtype=torch.uint8, device=planes[0].device)
+    elif out.numel() != H * W * 3 or out.device != planes[0].device:
+        raise ValueError("out must hold H * W * 3 bytes on the planes' device")
+    _capi.check(lib.pfnl_op_yuv420_to_rgb_u8_surface(C.byref(sf), ids[0], ids[1], ids[2], H, W, _req_u8(out, "out"), _stream(planes[0])))
+    return out.view(H, W, 3)
+
+
 def rgb_to_yuv420(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None):
     """[n,H,W,3] (or [H,W,3]) uint8 (cuda) -> [n, H*3/2, W] uint8: tightly packed NV12 / I420 frames, byte for byte pfnl_amd/yuv.py from_rgb
     (pfnl_op_rgb_to_yuv420_u8: the streaming session's output edge).  H, W even; any alignment; ``out``: write there."""

@@ -29,6 +29,10 @@ network's own size.
 ``(oH*3//2, oW)``, every sample value << 6; ``"i010"`` (yuv420p10le) the values themselves, ``"rgb10"`` ``(oH, oW, 3)`` with values 0 .. 1023:
 the fp32 result quantised to 1023 levels instead of 255, then the same resampling and conversion by the rule of pfnl_amd/depth10.py.
 These are output formats only (``pixel_format`` stays "rgb24" | "nv12" | "i420"), and "rgb10" goes with RGB input.
+
+Surfaces: ``vs.push_planes(y, cbcr)`` / ``vs.pop_planes(y, cbcr)`` take and fill a frame as a decoder or encoder holds it - one array per
+plane, each with the row pitch its strides say (pfnl_amd/surface.py), e.g. ``surface[:H, :W]`` of a pitched device allocation - in the
+session's formats; a device NV12 / I420 surface is converted where it lies, and only the samples of a destination are written.
 """
 from __future__ import annotations
 
@@ -37,7 +41,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from . import _capi, resize as _resize
+from . import _capi, resize as _resize, surface as _surface
 
 
 def next_batch(num_frames: int, batch: int, pushed: int, ended: bool, launched: int) -> Tuple[int, int]:
@@ -257,15 +261,60 @@ class VideoStream:
             _capi.check(self._lib.pfnl_stream_pop(s, out.ctypes.data_as(C.c_void_p), 0, C.byref(index), C.byref(got)))
         if not got.value:
             return None
+        self._note_info(s, index.value)
+        return index.value, out
+
+    def _note_info(self, s, index: int) -> None:
+        """``last_info`` and ``cuts`` for the frame a pop has just delivered."""
         if self.scene_cut is not None:
             first, sad = C.c_longlong(0), C.c_ulonglong(0)
             _capi.check(self._lib.pfnl_stream_pop_info(s, C.byref(first), C.byref(sad)))
             self.last_info = (first.value, sad.value)
-            if index.value > 0 and first.value == index.value:
-                self.cuts.append(index.value)
+            if index > 0 and first.value == index:
+                self.cuts.append(index)
         else:
             self.last_info = (0, 0)
-        return index.value, out
+
+    # ---- surfaces: planes with a row pitch (pfnl_amd/surface.py) -------------------------------
+    def _planes_struct(self, planes, fmt, H, W):
+        """(pfnl_surface, on the device?) of a tuple of planes, all numpy arrays or all tensors on the stream's device."""
+        on_device = [type(p).__module__.startswith("torch") for p in planes]
+        if any(on_device) != all(on_device):
+            raise ValueError("the planes of a frame are all numpy arrays or all device tensors")
+        if planes and on_device[0]:
+            for p in planes:
+                if not p.is_cuda or p.device.index != self.device.index:
+                    raise ValueError(f"tensor on {p.device}, stream on {self.device} (host planes: numpy arrays)")
+        return _surface.as_struct(planes, fmt, H, W), bool(planes) and on_device[0]
+
+    def push_planes(self, *planes) -> List[tuple]:
+        """``push`` of a frame given as its planes in ``pixel_format`` - (Y, CbCr) for nv12, (Y, Cb, Cr) for i420, one (H, W, 3) or (H, 3 W)
+        plane for rgb24 - each a numpy array or each a device tensor, with whatever row pitch its strides say (pfnl_amd/surface.py):
+        typically views ``surface[:H, :W]`` of a decoder's pitched surface, which is read where it lies.  Returns what ``push`` returns;
+        the two may alternate within a sequence."""
+        s = self._handle()
+        sf, on_device = self._planes_struct(planes, self.pixel_format, self.H, self.W)
+        due = self.ready()
+        _capi.check(self._lib.pfnl_stream_push_surface(s, C.byref(sf), 1 if on_device else 0))
+        self._device_frames = on_device
+        return self.pop_ready(due)
+
+    def pop_planes(self, *planes):
+        """``pop`` into planes the caller owns, in ``out_format`` at the output size - numpy arrays or device tensors with a row pitch of
+        their own, an encoder's surface: only the samples are written, never the bytes between a row's end and the pitch.  Returns the
+        frame's index, or None when no frame is deliverable (then nothing was written)."""
+        s = self._handle()
+        oH, oW = self.out_size if self.out_size is not None else (self.scale * self.H, self.scale * self.W)
+        sf, on_device = self._planes_struct(planes, self.out_format, oH, oW)
+        for p in planes:
+            if not on_device and not p.flags.writeable:
+                raise ValueError("pop_planes writes into its planes: a read-only array")
+        index, got = C.c_longlong(0), C.c_int(0)
+        _capi.check(self._lib.pfnl_stream_pop_surface(s, C.byref(sf), 1 if on_device else 0, C.byref(index), C.byref(got)))
+        if not got.value:
+            return None
+        self._note_info(s, index.value)
+        return index.value
 
     def pop_ready(self, limit=None) -> List[tuple]:
         frames = []
