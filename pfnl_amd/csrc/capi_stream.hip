@@ -3,6 +3,9 @@
 // _run_sequence_on_device) - clamped windows, batching, quantisation, the range flag and the recomputation on the strict kernels - lives
 // here, behind pfnl_forward's own interface: the session calls pfnl_forward / pfnl_get_option / pfnl_set_option / pfnl_range_flag like
 // any other caller and knows nothing of the handle's layout (capi_internal.h, pfnl_handle_view).
+// The output side is one route (stream_route.h: quantise -> resize -> 4:2:0, at 1 or 2 bytes per sample) and one slot per stage: the
+// two setters validate through that header and hand their candidate to apply_setting, the only place that allocates or frees a slot
+// after open; enqueue and pop_frame read the stored route.
 #include <cmath>
 #include <deque>
 #include <string>
@@ -10,7 +13,7 @@
 #include "../../include/pfnl_hip.h"
 #include "capi_internal.h"
 #include "common.h"
-#include "surface_geom.h"
+#include "stream_route.h"
 
 namespace {
 
@@ -21,6 +24,11 @@ struct Batch {
     int count, slot;
     bool was_strict;         // launched after the session went strict: the range fence was not armed, nothing to check
     bool checked;            // its event has been waited for and its range flag read (and the batch recomputed if need be)
+};
+
+struct StageSlot {
+    uint8_t* buf[2] = {nullptr, nullptr};             // [batch][the stage's frame] each: the undelivered frames of at most two batches
+    size_t cap = 0;                                   // bytes of each
 };
 
 }  // namespace
@@ -34,7 +42,6 @@ struct pfnl_stream {
     uint8_t* ring = nullptr;                          // [cap][H][W][3], frame f in slot f % cap
     float* win = nullptr;                             // [batch][T][H][W][3]
     float* sr = nullptr;                              // [batch][sH][sW][3]
-    uint8_t* out[2] = {nullptr, nullptr};             // [batch][sH][sW][3] each: the undelivered frames of at most two batches
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool slot_busy[2] = {false, false};
     long long pushed = 0, launched = 0, delivered = 0;
@@ -54,33 +61,20 @@ struct pfnl_stream {
     bool has_info = false;                            // what pfnl_stream_pop_info returns
     long long info_first = 0;
     unsigned long long info_sad = 0;
-    // formats (pfnl_stream_format): the ring and out[] stay RGB; a YUV frame is converted on its way into its ring slot, a batch's SR
-    // frames behind their quantisation into yout[] - allocated by the first call that needs them, freed with the session
+    // the setting (pfnl_stream_format, pfnl_stream_resize; stored by apply_setting alone).  The ring stays RGB24: a YUV frame is converted
+    // on its way into its ring slot.  Every stage `route` runs has a slot with room for a batch - 8- and 10-bit samples share it, as a
+    // sequence has one route - and no other stage holds memory; stage 0 is allocated at open.
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
     pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
     pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010
-    uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel
-    uint8_t* yout[2] = {nullptr, nullptr};            // [batch][oH*oW*3/2] each, beside out[]: where present, sized for the current output
-    // output size (pfnl_stream_resize): out[] stays the network's raster; a batch is resampled behind its quantisation into rout[], and
-    // that is what the YUV conversion reads and pop copies - allocated by the call that sets a size, freed with the session
+    uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel; from the first YUV in_fmt on
     pfnl::ResizePlan rplan;                           // rplan.oH = 0: off
     int32_t* rtab = nullptr;                          // rplan.blob on the device
-    uint8_t* rout[2] = {nullptr, nullptr};            // [batch][oH][oW][3] each
-    // 10 bits out (pfnl_stream_format with PFNL_PIX_RGB10 / P010 / I010): the same three steps on uint16 samples in slots of their own,
-    // beside the 8-bit ones, which such a batch does not touch - allocated by the call that sets the format (the resized and the 4:2:0
-    // ones follow the output size from then on), freed with the session
-    uint16_t* out10[2] = {nullptr, nullptr};          // [batch][sH][sW][3] each
-    uint16_t* rout10[2] = {nullptr, nullptr};         // [batch][oH][oW][3] each: present where out10 is and a size is set
-    uint16_t* yout10[2] = {nullptr, nullptr};         // [batch][oH*oW*3/2] each
-    int out_h() const { return rplan.oH ? rplan.oH : scale * H; }
-    int out_w() const { return rplan.oW ? rplan.oW : scale * W; }
-    size_t out_bytes() const { return (size_t)out_h() * out_w() * 3; }   // one delivered frame as RGB24 (the samples of one as RGB10)
+    pfnl::OutRoute route{};
+    StageSlot slot[pfnl::ROUTE_STAGES];
 };
 
 namespace {
-
-bool is_10bit(int fmt) { return fmt == PFNL_PIX_RGB10 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
-bool is_420(int fmt) { return fmt == PFNL_PIX_NV12 || fmt == PFNL_PIX_I420 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
 
 int get_option(pfnl_stream* s, const char* key, std::string* v) {
     char buf[64];
@@ -100,21 +94,21 @@ int enqueue(pfnl_stream* s, const Batch& b) {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
     if (int e = pfnl_forward(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->s)) return e;
-    if (is_10bit(s->out_fmt)) {                       // the same route on uint16 samples (depth10.hip)
-        HIPCHK(pfnl::launch_quantise_u10(s->sr, s->out10[b.slot], (size_t)b.count * s->sr_bytes, s->s));
-        if (s->rplan.oH) HIPCHK(pfnl::launch_resize_u10(s->out10[b.slot], s->rout10[b.slot], s->rplan, s->rtab, b.count, s->s));
-        if (s->out_fmt != PFNL_PIX_RGB10)
-            HIPCHK(pfnl::launch_rgb_to_yuv420_u10(s->rplan.oH ? s->rout10[b.slot] : s->out10[b.slot], s->yout10[b.slot],
-                                                  s->out_fmt == PFNL_PIX_P010, s->coef10, b.count, s->out_h(), s->out_w(), s->s));
-        HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
-        return 0;
-    }
-    HIPCHK(pfnl::launch_quantise_u8(s->sr, s->out[b.slot], (size_t)b.count * s->sr_bytes, s->s));
-    if (s->rplan.oH)                                  // (a replay takes the same route: pop stays a copy)
-        HIPCHK(pfnl::launch_resize_u8(s->out[b.slot], s->rout[b.slot], s->rplan, s->rtab, b.count, s->s));
-    if (s->out_fmt != PFNL_PIX_RGB24)
-        HIPCHK(pfnl::launch_rgb_to_yuv420_u8(s->rplan.oH ? s->rout[b.slot] : s->out[b.slot], s->yout[b.slot], s->out_fmt == PFNL_PIX_NV12,
-                                             s->coef, b.count, s->out_h(), s->out_w(), s->s));
+    // the route, each stage out of the slot of the one before it (a replay takes the same route: pop stays a copy); 10 bits: the same
+    // launches on uint16 samples (depth10.hip) - the twins stay apart, tools/GFX950_NOTES.md
+    const pfnl::OutRoute& r = s->route;
+    const bool ten = r.sample_bytes == 2;
+    const auto u16 = [](uint8_t* p) { return reinterpret_cast<uint16_t*>(p); };
+    uint8_t *const q = s->slot[0].buf[b.slot], *const rs = s->slot[1].buf[b.slot], *const y = s->slot[2].buf[b.slot];
+    uint8_t* const rgb = r.runs[1] ? rs : q;          // what the 4:2:0 conversion reads
+    HIPCHK(ten ? pfnl::launch_quantise_u10(s->sr, u16(q), (size_t)b.count * s->sr_bytes, s->s)
+               : pfnl::launch_quantise_u8(s->sr, q, (size_t)b.count * s->sr_bytes, s->s));
+    if (r.runs[1])
+        HIPCHK(ten ? pfnl::launch_resize_u10(u16(q), u16(rs), s->rplan, s->rtab, b.count, s->s)
+                   : pfnl::launch_resize_u8(q, rs, s->rplan, s->rtab, b.count, s->s));
+    if (r.runs[2])
+        HIPCHK(ten ? pfnl::launch_rgb_to_yuv420_u10(u16(rgb), u16(y), s->out_fmt == PFNL_PIX_P010, s->coef10, b.count, r.out_h, r.out_w, s->s)
+                   : pfnl::launch_rgb_to_yuv420_u8(rgb, y, s->out_fmt == PFNL_PIX_NV12, s->coef, b.count, r.out_h, r.out_w, s->s));
     HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
     return 0;
 }
@@ -280,11 +274,8 @@ int pop_frame(pfnl_stream* s, int is_device, long long* index, int* got, Deliver
     Batch& b = s->q.front();
     if (!b.checked)
         if (int e = check_batch(s, b)) return e;
-    const bool yuv_out = is_420(s->out_fmt), ten = is_10bit(s->out_fmt);
-    const size_t bytes = (yuv_out ? s->out_bytes() / 2 : s->out_bytes()) * (ten ? 2 : 1);
-    const uint8_t* const slot = ten ? reinterpret_cast<const uint8_t*>(yuv_out ? s->yout10[b.slot] : (s->rplan.oH ? s->rout10[b.slot] : s->out10[b.slot]))
-                                    : (yuv_out ? s->yout[b.slot] : (s->rplan.oH ? s->rout[b.slot] : s->out[b.slot]));
-    const uint8_t* const src = slot + (size_t)(s->delivered - b.first) * bytes;
+    const size_t bytes = s->route.frame_bytes;
+    const uint8_t* const src = s->slot[s->route.last].buf[b.slot] + (size_t)(s->delivered - b.first) * bytes;
     if (is_device) {
         if (int e = deliver(src, bytes, s->s)) return e;
     } else {
@@ -311,18 +302,18 @@ int pop_frame(pfnl_stream* s, int is_device, long long* index, int* got, Deliver
     return 0;
 }
 
+void drop_slot(StageSlot& t) {
+    for (uint8_t* p : t.buf)
+        if (p) (void)hipFree(p);
+    t = StageSlot();
+}
+
 void release(pfnl_stream* s) {
+    for (StageSlot& t : s->slot) drop_slot(t);
     for (int i = 0; i < 2; ++i) {
-        if (s->out[i]) (void)hipFree(s->out[i]);
-        if (s->out10[i]) (void)hipFree(s->out10[i]);
-        if (s->rout10[i]) (void)hipFree(s->rout10[i]);
-        if (s->yout10[i]) (void)hipFree(s->yout10[i]);
-        if (s->yout[i]) (void)hipFree(s->yout[i]);
-        if (s->rout[i]) (void)hipFree(s->rout[i]);
         if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
-    }
-    for (int i = 0; i < 2; ++i)
         if (s->info[i]) (void)hipHostFree(s->info[i]);
+    }
     if (s->scene_first) (void)hipFree(s->scene_first);
     if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
     if (s->yin) (void)hipFree(s->yin);
@@ -332,6 +323,62 @@ void release(pfnl_stream* s) {
     if (s->sr) (void)hipFree(s->sr);
     if (s->cs) (void)hipStreamDestroy(s->cs);
     delete s;
+}
+
+// The one place where a setting becomes the session's: both setters end here, with a candidate they have validated and no frame pushed
+// (`plan` NULL: the output size stays).  1. the route and a batch's bytes per stage; 2. everything new first - a stage slot whose capacity
+// is below the need, the tap table of a new plan, the staging frame of the first YUV in_fmt - and where one fails, what was just made is
+// freed, the session is what it was and the answer is PFNL_ERR_NOMEM with `nomem`; 3. the new buffers go in, the ones they replace and the
+// slots of stages the route does not run are freed, the setting is stored.  A call that replaces or releases device memory first waits
+// for the session's stream - a dropped sequence's device-pointer pops may still be reading it - and only such a call: pfnl_stream_format
+// waits where a 10-bit format meets 8-bit slots or a 4:2:0 slot is no longer needed, and not where it only adds memory or changes none.
+int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& coef, const pfnl::YuvCoef& coef10, pfnl::ResizePlan* plan,
+                  const char* nomem) {
+    const pfnl::ResizePlan& rp = plan ? *plan : s->rplan;
+    const pfnl::OutRoute route = pfnl::out_route(out_fmt, s->scale * s->H, s->scale * s->W, rp.oH, rp.oW);
+    StageSlot fresh[pfnl::ROUTE_STAGES];              // cap != 0: the stage's slot is too small and this one takes its place
+    bool frees = plan && s->rtab;
+    for (int k = 0; k < pfnl::ROUTE_STAGES; ++k) {
+        const size_t need = (size_t)s->batch * route.stage_bytes[k];   // (0 for a stage that does not run)
+        if (need > s->slot[k].cap) fresh[k].cap = need;
+        frees = frees || (s->slot[k].cap && (fresh[k].cap || !route.runs[k]));
+    }
+    HIPCHK(hipSetDevice(s->device));
+    if (frees) HIPCHK(hipStreamSynchronize(s->s));
+    int32_t* tab = nullptr;
+    uint8_t* yin = nullptr;
+    bool ok = true;
+    if (plan && plan->oH) {
+        ok = hipMalloc(reinterpret_cast<void**>(&tab), plan->blob.size() * sizeof(int32_t)) == hipSuccess;
+        ok = ok && hipMemcpy(tab, plan->blob.data(), plan->blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (in_fmt != PFNL_PIX_RGB24 && !s->yin) ok = ok && hipMalloc(reinterpret_cast<void**>(&yin), s->lr_bytes / 2) == hipSuccess;
+    for (StageSlot& t : fresh)
+        for (int i = 0; i < 2 && t.cap; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&t.buf[i]), t.cap) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        if (tab) (void)hipFree(tab);
+        if (yin) (void)hipFree(yin);
+        for (StageSlot& t : fresh) drop_slot(t);
+        return fail(PFNL_ERR_NOMEM, nomem);
+    }
+    if (plan) {
+        if (s->rtab) (void)hipFree(s->rtab);
+        s->rtab = tab;
+        s->rplan = std::move(*plan);
+    }
+    if (yin) s->yin = yin;
+    for (int k = 0; k < pfnl::ROUTE_STAGES; ++k)
+        if (fresh[k].cap || !route.runs[k]) {
+            drop_slot(s->slot[k]);
+            s->slot[k] = fresh[k];
+        }
+    s->in_fmt = in_fmt;
+    s->out_fmt = out_fmt;
+    s->coef = coef;
+    s->coef10 = coef10;
+    s->route = route;
+    return 0;
 }
 
 }  // namespace
@@ -379,8 +426,10 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
     ok = ok && hipMalloc(reinterpret_cast<void**>(&s->ring), (size_t)s->cap * s->lr_bytes) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&s->win), (size_t)batch * s->T * s->lr_bytes * sizeof(float)) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&s->sr), (size_t)batch * s->sr_bytes * sizeof(float)) == hipSuccess;
+    s->route = pfnl::out_route(s->out_fmt, v.scale * H, v.scale * W, 0, 0);   // RGB24 at the network's raster: stage 0 alone
+    s->slot[0].cap = (size_t)batch * s->route.stage_bytes[0];
     for (int i = 0; i < 2; ++i) {
-        ok = ok && hipMalloc(reinterpret_cast<void**>(&s->out[i]), (size_t)batch * s->sr_bytes) == hipSuccess;
+        ok = ok && hipMalloc(reinterpret_cast<void**>(&s->slot[0].buf[i]), s->slot[0].cap) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&s->ev[i], hipEventDisableTiming) == hipSuccess;
     }
     if (!ok) {
@@ -468,8 +517,8 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
 
 int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_device, long long* index, int* got) {
     if (!s || !out || !index || !got) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (const char* why = pfnl::surface_refused(out, s->out_fmt, s->out_h(), s->out_w())) return fail(PFNL_ERR_INVALID, why);
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->out_fmt, s->out_h(), s->out_w());
+    if (const char* why = pfnl::surface_refused(out, s->out_fmt, s->route.out_h, s->route.out_w)) return fail(PFNL_ERR_INVALID, why);
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->out_fmt, s->route.out_h, s->route.out_w);
     return pop_frame(s, is_device, index, got, [&](const uint8_t* src, size_t, hipStream_t on) {
         for (int k = 0; k < g.planes; ++k) {          // the packed frame is its planes one behind the other: rows of row_bytes, nothing between
             HIPCHK(hipMemcpy2DAsync(out->plane[k], out->pitch[k], src, g.plane[k].row_bytes, g.plane[k].row_bytes, g.plane[k].rows,
@@ -518,117 +567,26 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
     return 0;
 }
 
+// Both setters: bad arguments first (stream_route.h: PFNL_ERR_INVALID at any time), then "before the first frame", then apply_setting.
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (is_10bit(in_fmt)) return fail(PFNL_ERR_INVALID, "format: 10-bit input is not built (in_fmt: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420)");
-    if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || out_fmt < PFNL_PIX_RGB24 || out_fmt > PFNL_PIX_I010)
-        return fail(PFNL_ERR_INVALID, "format: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420, and as out_fmt PFNL_PIX_RGB10, PFNL_PIX_P010 or PFNL_PIX_I010");
-    if (in_fmt != PFNL_PIX_RGB24 && out_fmt == PFNL_PIX_RGB10)
-        return fail(PFNL_ERR_INVALID, "format: PFNL_PIX_RGB10 is delivered for RGB24 input only (a YUV in_fmt pairs with a YUV out_fmt or RGB24)");
+    if (const char* why = pfnl::route_refused(in_fmt, out_fmt, s->route.out_h, s->route.out_w)) return fail(PFNL_ERR_INVALID, why);
     pfnl::YuvCoef coef, coef10;
     if (!pfnl::yuv_coefficients(matrix, full_range, &coef) || !pfnl::yuv10_coefficients(matrix, full_range, &coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
-    if (is_420(out_fmt) && ((s->out_h() | s->out_w()) & 1))
-        return fail(PFNL_ERR_INVALID, "format: a YUV output needs an even output size (pfnl_stream_resize)");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    const bool ten = is_10bit(out_fmt), yuv_out = is_420(out_fmt);
-    const bool need_in = in_fmt != PFNL_PIX_RGB24 && !s->yin, need_out = yuv_out && !ten && !s->yout[0];
-    const bool need_q10 = ten && !s->out10[0], need_r10 = ten && s->rplan.oH && !s->rout10[0], need_y10 = ten && yuv_out && !s->yout10[0];
-    if (need_in || need_out || need_q10 || need_r10 || need_y10) {
-        HIPCHK(hipSetDevice(s->device));
-        bool ok = true;
-        if (need_in) ok = hipMalloc(reinterpret_cast<void**>(&s->yin), s->lr_bytes / 2) == hipSuccess;
-        for (int i = 0; i < 2; ++i) {
-            if (need_out) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout[i]), (size_t)s->batch * (s->out_bytes() / 2)) == hipSuccess;
-            if (need_q10) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->out10[i]), (size_t)s->batch * s->sr_bytes * sizeof(uint16_t)) == hipSuccess;
-            if (need_r10) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->rout10[i]), (size_t)s->batch * s->out_bytes() * sizeof(uint16_t)) == hipSuccess;
-            if (need_y10) ok = ok && hipMalloc(reinterpret_cast<void**>(&s->yout10[i]), (size_t)s->batch * (s->out_bytes() / 2) * sizeof(uint16_t)) == hipSuccess;
-        }
-        if (!ok) {                                    // nothing half allocated stays behind, and the setting is unchanged
-            (void)hipGetLastError();
-            if (need_in && s->yin) (void)hipFree(s->yin), s->yin = nullptr;
-            const auto drop = [](auto** slots) {
-                for (int i = 0; i < 2; ++i) {
-                    if (slots[i]) (void)hipFree(slots[i]);
-                    slots[i] = nullptr;
-                }
-            };
-            if (need_out) drop(s->yout);
-            if (need_q10) drop(s->out10);
-            if (need_r10) drop(s->rout10);
-            if (need_y10) drop(s->yout10);
-            return fail(PFNL_ERR_NOMEM, "format staging allocation failed");
-        }
-    }
-    s->in_fmt = in_fmt;
-    s->out_fmt = out_fmt;
-    s->coef = coef;
-    s->coef10 = coef10;
-    return 0;
+    return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, "format staging allocation failed");
 }
 
 int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const bool on = out_H != 0 || out_W != 0;
-    pfnl::ResizePlan plan;                            // (off: oH = oW = 0, no table)
-    if (on) {
-        std::string why;
-        if (!pfnl::resize_plan(s->scale * s->H, s->scale * s->W, out_H, out_W, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
-        if (is_420(s->out_fmt) && ((out_H | out_W) & 1))
-            return fail(PFNL_ERR_INVALID, "resize: a YUV output format needs an even output size (pfnl_stream_format)");
-    }
+    const int sH = s->scale * s->H, sW = s->scale * s->W;
+    pfnl::ResizePlan plan;                            // (0, 0 is off: oH = oW = 0, no table, the network's raster - which is even)
+    std::string why;
+    if ((out_H || out_W) && !pfnl::resize_plan(sH, sW, out_H, out_W, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
+    if (const char* no = pfnl::route_refused(s->in_fmt, s->out_fmt, plan.oH ? plan.oH : sH, plan.oW ? plan.oW : sW)) return fail(PFNL_ERR_INVALID, no);
     if (s->pushed) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    if (!on && !s->rplan.oH) return 0;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->s));               // (a dropped sequence's device-pointer pops may still read what is freed below)
-    // everything new first: nothing half-made stays behind and the setting is unchanged where one of them fails
-    const size_t px = on ? (size_t)out_H * out_W : (size_t)s->scale * s->H * s->scale * s->W;
-    int32_t* tab = nullptr;
-    uint8_t *ro[2] = {nullptr, nullptr}, *yo[2] = {nullptr, nullptr};
-    bool ok = true;
-    if (on) {
-        ok = hipMalloc(reinterpret_cast<void**>(&tab), plan.blob.size() * sizeof(int32_t)) == hipSuccess;
-        ok = ok && hipMemcpy(tab, plan.blob.data(), plan.blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-        for (int i = 0; i < 2; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&ro[i]), (size_t)s->batch * px * 3) == hipSuccess;
-    }
-    const bool had_yout = s->yout[0] != nullptr;      // it follows the output size, whatever the format is at the moment
-    for (int i = 0; had_yout && i < 2; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&yo[i]), (size_t)s->batch * ((px * 3 + 1) / 2)) == hipSuccess;
-    // the 16-bit slots of a session that has delivered 10 bits follow it likewise
-    const bool had_out10 = s->out10[0] != nullptr, had_yout10 = s->yout10[0] != nullptr;
-    uint16_t *ro10[2] = {nullptr, nullptr}, *yo10[2] = {nullptr, nullptr};
-    for (int i = 0; i < 2; ++i) {
-        if (on && had_out10) ok = ok && hipMalloc(reinterpret_cast<void**>(&ro10[i]), (size_t)s->batch * px * 3 * sizeof(uint16_t)) == hipSuccess;
-        if (had_yout10) ok = ok && hipMalloc(reinterpret_cast<void**>(&yo10[i]), (size_t)s->batch * ((px * 3 + 1) / 2) * sizeof(uint16_t)) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        if (tab) (void)hipFree(tab);
-        for (int i = 0; i < 2; ++i) {
-            if (ro[i]) (void)hipFree(ro[i]);
-            if (yo[i]) (void)hipFree(yo[i]);
-            if (ro10[i]) (void)hipFree(ro10[i]);
-            if (yo10[i]) (void)hipFree(yo10[i]);
-        }
-        return fail(PFNL_ERR_NOMEM, "resize allocation failed");
-    }
-    if (s->rtab) (void)hipFree(s->rtab);
-    s->rtab = tab;
-    for (int i = 0; i < 2; ++i) {
-        if (s->rout[i]) (void)hipFree(s->rout[i]);
-        s->rout[i] = ro[i];
-        if (had_yout) {
-            (void)hipFree(s->yout[i]);
-            s->yout[i] = yo[i];
-        }
-        if (s->rout10[i]) (void)hipFree(s->rout10[i]);
-        s->rout10[i] = ro10[i];
-        if (had_yout10) {
-            (void)hipFree(s->yout10[i]);
-            s->yout10[i] = yo10[i];
-        }
-    }
-    s->rplan = std::move(plan);
-    return 0;
+    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, "resize allocation failed");
 }
 
 int pfnl_stream_mark_cut(pfnl_stream* s) {

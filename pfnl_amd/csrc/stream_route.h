@@ -1,0 +1,61 @@
+// THE OUTPUT ROUTE OF A STREAMING SESSION (include/pfnl_hip.h pfnl_stream_format / pfnl_stream_resize): what a batch goes through between
+// the fp32 result and pop - stage 0 quantise -> stage 1 resize -> stage 2 RGB -> 4:2:0, at 1 or 2 bytes per sample -, the bytes of a frame
+// behind each stage, which stage pop reads, and the one check of a (formats, size) setting that needs no session.  No HIP types and no HIP
+// runtime calls: a plain C++ program can include this file and walk the rule (tests/test_route_host.py does).
+#pragma once
+#include "surface_geom.h"
+
+namespace pfnl {
+
+inline bool is_10bit(int fmt) { return fmt == PFNL_PIX_RGB10 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
+inline bool is_420(int fmt) { return fmt == PFNL_PIX_NV12 || fmt == PFNL_PIX_I420 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
+
+constexpr int ROUTE_STAGES = 3;   // 0 quantise (always) | 1 resize (a size is set) | 2 RGB -> 4:2:0 (a 4:2:0 out_fmt)
+
+struct OutRoute {
+    bool runs[ROUTE_STAGES];
+    int sample_bytes;                  // 1, or 2 for RGB10 / P010 / I010; 0: no such format, and no stage runs
+    size_t stage_bytes[ROUTE_STAGES];  // one frame as the stage writes it; 0 where it does not run
+    int last;                          // the last stage that runs: pop reads its slot
+    int out_h, out_w;                  // the delivered frame,
+    size_t frame_bytes;                // and its bytes = stage_bytes[last]
+};
+
+// the packed frame is its planes one behind the other: rows of row_bytes, nothing between
+inline size_t packed_bytes(const SurfaceGeom& g) {
+    size_t n = 0;
+    for (int k = 0; k < g.planes; ++k) n += g.plane[k].rows * g.plane[k].row_bytes;
+    return n;
+}
+
+// sH x sW: the network's raster; oH = oW = 0: no resampling.  Sizes are what route_refused has let through.
+inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW) {
+    OutRoute r{};
+    r.out_h = oH ? oH : sH;
+    r.out_w = oW ? oW : sW;
+    const SurfaceGeom g = surface_geom(out_fmt, r.out_h, r.out_w);
+    if (!g.planes) return r;
+    const int rgb = is_10bit(out_fmt) ? PFNL_PIX_RGB10 : PFNL_PIX_RGB24;
+    const SurfaceGeom writes[ROUTE_STAGES] = {surface_geom(rgb, sH, sW), surface_geom(rgb, r.out_h, r.out_w), g};
+    r.sample_bytes = g.sample_bytes;
+    r.runs[0] = true, r.runs[1] = oH != 0, r.runs[2] = is_420(out_fmt);
+    for (int k = 0; k < ROUTE_STAGES; ++k)
+        if (r.runs[k]) r.last = k, r.stage_bytes[k] = packed_bytes(writes[k]);
+    r.frame_bytes = r.stage_bytes[r.last];
+    return r;
+}
+
+// nullptr: a session may take in_fmt -> out_fmt and deliver out_h x out_w; else why not.  Both setters ask this before they look at
+// the session's state, each with the other's current setting.
+inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w) {
+    if (is_10bit(in_fmt)) return "format: 10-bit input is not built (in_fmt: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420)";
+    if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || out_fmt < PFNL_PIX_RGB24 || out_fmt > PFNL_PIX_I010)
+        return "format: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420, and as out_fmt PFNL_PIX_RGB10, PFNL_PIX_P010 or PFNL_PIX_I010";
+    if (in_fmt != PFNL_PIX_RGB24 && out_fmt == PFNL_PIX_RGB10)
+        return "format: PFNL_PIX_RGB10 is delivered for RGB24 input only (a YUV in_fmt pairs with a YUV out_fmt or RGB24)";
+    if (is_420(out_fmt) && ((out_h | out_w) & 1))
+        return "a YUV output format needs an even output size (pfnl_stream_format, pfnl_stream_resize)";
+    return nullptr;
+}
+
+}  // namespace pfnl

@@ -382,3 +382,41 @@ def test_state_and_validation():
         odd = np.stack([f for _, f in _stream_all(vs, lr)])
     assert odd.shape == (6, 37, 55, 3) and odd.dtype == np.uint16 and int(odd.max()) <= 1023
     eng.close()
+
+
+ROUTE_WALK = [("rgb24", None), ("p010", (36, 54)), ("nv12", (36, 54)), ("i010", None), ("rgb10", (37, 55)), ("i420", (96, 160)), ("rgb24", None)]
+
+
+def test_one_session_walks_every_route():
+    """One open session through seven settings with a reset between them - each makes the slot table grow, shrink or free another stage
+    (pfnl_amd/csrc/capi_stream.hip apply_setting) - delivers at every step the bytes of a fresh session opened with that setting, through
+    host pointers and through device pointers.  Two batches per sequence, the second partial."""
+    from pfnl_amd import _capi
+    H, W, batch = 16, 24, 2
+    geom = PFNLGeometry(num_block=1)
+    eng = _engine_with(geom, synth.synthetic_weights(geom, seed=0))
+    lib = eng._lib
+    lr = list(np.random.default_rng(71).integers(0, 256, (5, H, W, 3), np.uint8))
+    dtype = lambda fmt: torch.uint16 if fmt in _capi.TEN_BIT_FORMATS else torch.uint8   # noqa: E731
+    fresh = {}
+    for fmt, size in dict.fromkeys(ROUTE_WALK):
+        with eng.open_stream(H, W, batch, out_format=fmt, out_size=size) as vs:
+            fresh[fmt, size] = np.stack([f for _, f in _stream_all(vs, lr, dtype=dtype(fmt))])
+    assert len(fresh) == 6 and len({f.tobytes() for f in fresh.values()}) == 6
+    walked = []
+    with eng.open_stream(H, W, batch) as vs:
+        for fmt, size in ROUTE_WALK:
+            calls = [lambda: lib.pfnl_stream_format(vs._s, 0, _capi.PIXEL_FORMATS[fmt], 1, 0), lambda: lib.pfnl_stream_resize(vs._s, *(size or (0, 0)))]
+            for call in (reversed(calls) if fmt in _capi.FORMATS_420 else calls):   # a 4:2:0 format comes behind its even size, an odd size behind RGB
+                assert call() == 0, (fmt, size, lib.pfnl_last_error())
+            vs.out_format, vs.out_size = fmt, size                                  # (the raw calls went past the Python object)
+            for device in (False, True):
+                got = _stream_all(vs, lr, device, dtype(fmt))
+                assert [i for i, _ in got] == list(range(5))
+                sr = np.stack([f for _, f in got])
+                want = fresh[fmt, size]
+                assert sr.dtype == want.dtype and sr.shape == want.shape and np.array_equal(sr, want), (fmt, size, device)
+                vs.reset()
+            walked.append(sr)
+    assert np.array_equal(walked[6], walked[0])
+    eng.close()
