@@ -30,13 +30,13 @@
  * host-pointer call returns with its output filled.  A captured graph (option "graph") is captured and replayed on the caller's stream,
  * between staging copies on that stream.  A session has two streams: the one given to pfnl_stream_open (gather, forward, quantisation,
  * the edge kernels, device-pointer pushes and pops) and a non-blocking copy stream of its own (host-pointer pushes and pops, which
- * return with the copy complete); pfnl_stream_scenes / _format / _resize are setup calls that allocate and may block.  The calls on one
+ * return with the copy complete); pfnl_stream_scenes / _format / _resize / _place are setup calls that allocate and may block.  The calls on one
  * handle share its workspace: a caller that changes the stream between calls orders them itself (an event, or a synchronise), and plain
  * forwards between the pushes of a session go on the session's stream.  pfnl_sync waits for the handle's own stream and the null
  * stream, NOT for a stream of the caller's: synchronise that one first, then pfnl_sync or pfnl_range_flag reads the range flag of the
  * device-pointer calls behind it.  Op hooks that synchronise `stream` before they return (they upload a weight pack or a table with a
  * blocking copy, which goes through the null stream): every pfnl_op_* that takes host weights (the conv, non-local, conv0 and tail
- * hooks), pfnl_op_resize_u8 / _u10 and pfnl_op_scene_sad_u8.  Asynchronous: pfnl_op_gather_windows / _u8 / _u8_scenes,
+ * hooks), pfnl_op_resize_u8 / _u10, pfnl_op_resize_place_u8 / _u10 and pfnl_op_scene_sad_u8.  Asynchronous: pfnl_op_gather_windows / _u8 / _u8_scenes,
  * pfnl_op_quantise_u8 / _u10, pfnl_op_yuv420_to_rgb_u8 / _u8_surface, pfnl_op_rgb_to_yuv420_u8 / _u10, pfnl_op_bicubic, pfnl_op_blur_decimate (its
  * first call per device uploads a constant table), pfnl_op_score_y.
  */
@@ -328,10 +328,33 @@ int pfnl_yuv10_coefficients(int matrix, int full_range, int32_t out[10]);  /* y0
  *   pfnl_resize_max_taps / pfnl_resize_taps: one axis of the table, in exact integers, no device needed: output o =
  *     sum over k < count[o] of coef[o * ntaps + k] * in[first[o] + k] / 2^14; coef is [n_out][ntaps], zero behind count[o], with ntaps the
  *     longest run, as pfnl_resize_max_taps reports it.  Sizes outside the limits above and NULL: PFNL_ERR_INVALID.
- * Out of scope: other filters, cropping, letterboxing and aspect handling, resampling ahead of the quantisation, the input side. */
+ * Out of scope: other filters, resampling ahead of the quantisation, the input side (crop, letterbox and aspect fit: PLACEMENT below). */
 int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W);
 int pfnl_resize_max_taps(int n_in, int n_out, int* ntaps);
 int pfnl_resize_taps(int n_in, int n_out, int32_t* first /*[n_out]*/, int32_t* count /*[n_out]*/, int16_t* coef /*[n_out][ntaps]*/);
+/* PLACEMENT (additions to version 4; off by default, and a session that does not call pfnl_stream_place issues the launches it always
+ * issued).  pfnl_stream_resize stretches the whole SR raster onto the whole output raster; where the two aspect ratios differ a frame
+ * wants a crop, bars, or both.  With a placement the session resamples the rectangle `src` of the network's raster (scale*H x scale*W)
+ * into the rectangle `dst` of a canvas of out_H x out_W and writes fill_rgb everywhere else, in the one launch that is stage 1 of the
+ * output route, at 8 and at 10 bits: every sample of the canvas is written once - no memset, no cropped copy, no second launch.  The rule
+ * is stated once on the host, pfnl_amd/fit.py place: the canvas = fill, with the resize of pfnl_stream_resize (pfnl_amd/resize.py; at 10
+ * bits pfnl_amd/depth10.py) of the source rectangle ALONE written at dst - taps clamp at the edges of `src`, no pixel outside it reaches
+ * the output.  The tables are pfnl_resize_taps(src.w, dst.w) and (src.h, dst.h).  A rectangle is y, x, h, w in pixels.
+ *   pfnl_stream_place: src NULL = the whole raster, dst NULL = the whole canvas, fill_rgb NULL = black; at 10 bits a fill value v becomes
+ *     (v << 2) | (v >> 6).  A 4:2:0 out_fmt converts the canvas as it converts any frame (an even canvas, as for pfnl_stream_resize; the
+ *     rectangles need not be even; black bars leave as Y 16 / 64, chroma 128 / 512).  out_H = out_W = 0 with all pointers NULL is off; a size
+ *     with src and dst NULL - or covering raster and canvas - is pfnl_stream_resize(s, out_H, out_W), the same launches; each of the two
+ *     calls replaces what the other set.  Rectangles have h, w >= 1 and lie inside their rasters, per axis ceil(src / 4) <= dst <= 2 src,
+ *     raster and canvas <= 16384: else PFNL_ERR_INVALID, the message naming src or dst (pfnl_amd/csrc/stream_route.h place_refused states
+ *     the check once, before any HIP call and any change to the session).  State, reset, PFNL_ERR_NOMEM, recomputed batches, pop,
+ *     pfnl_stream_pop_surface and pfnl_stream_format called later: as for pfnl_stream_resize, with the canvas as the output size.
+ *   Aspect rules ("contain", "cover", a sample aspect ratio) are integer arithmetic on the host: pfnl_amd/fit.py rects; this interface
+ *     takes rectangles only.
+ * Out of scope: rotation and flips, cropping the input side, more than one picture on a canvas. */
+typedef struct pfnl_rect {
+    int32_t y, x, h, w;
+} pfnl_rect;
+int pfnl_stream_place(pfnl_stream* s, int out_H, int out_W, const pfnl_rect* src, const pfnl_rect* dst, const uint8_t fill_rgb[3]);
 /* SURFACES (additions to version 4; a session that calls neither function issues the launches and copies it always issued).  A hardware
  * decoder or encoder hands out no packed frame: a surface is a pointer per plane and a row pitch per plane, rounded up to 64 or 256 bytes,
  * with a coded height above the displayed one, so that CbCr does not start at Y + H * W.  pfnl_stream_push_surface and
@@ -354,7 +377,7 @@ int pfnl_resize_taps(int n_in, int n_out, int32_t* first /*[n_out]*/, int32_t* c
  *   a window of a larger surface needs no argument of its own: point plane[] at the first displayed sample (x and y even, so that the
  *     chroma pointers are whole samples) and keep the surface's pitch - the frame is then that window, and chroma clamps at its edges.
  * Out of scope: conversion kernels that write into the caller's surface (the conversion runs per batch, before a destination is known),
- * 10-bit input, crop and letterbox arguments, odd sizes. */
+ * 10-bit input, odd sizes (crop and letterbox: PLACEMENT above puts the frame on a canvas before it is delivered). */
 typedef struct pfnl_surface {
     void*  plane[3];   /* RGB24 / RGB10: [0].  NV12 / P010: Y, CbCr.  I420 / I010: Y, Cb, Cr.  Unused entries are ignored. */
     size_t pitch[3];   /* bytes from one row of that plane to the next */
@@ -663,6 +686,16 @@ int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, ui
 int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream);
 int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, void* stream);
 int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream);
+/* The session's placement kernels (PLACEMENT, pfnl_stream_place; the rule: pfnl_amd/fit.py place, pfnl_amd/depth10.py place10).  in
+ * [n][H][W][3] -> out [n][oH][oW][3]: fill everywhere, the resize of in[src] at dst; src NULL = the whole frame, dst NULL = the whole canvas,
+ * fill NULL = zeros; at 10 bits fill is in sample values, <= 1023.  Device pointers; they synchronise as pfnl_op_resize_u8 does.  One launch,
+ * every output sample stored once; any alignment (16-byte stores where oW is a multiple of 16 - of 8 at 10 bits - and out is aligned, single
+ * samples otherwise).  NULL in / out, n < 1, a rectangle outside its raster, a src -> dst ratio outside pfnl_resize_taps' limits and a fill
+ * above 1023: PFNL_ERR_INVALID before any HIP call, the message naming src, dst or fill. */
+int pfnl_op_resize_place_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, const pfnl_rect* src, const pfnl_rect* dst,
+                            const uint8_t fill[3], uint8_t* out, void* stream);
+int pfnl_op_resize_place_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, const pfnl_rect* src, const pfnl_rect* dst,
+                             const uint16_t fill[3], uint16_t* out, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

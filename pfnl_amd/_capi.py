@@ -36,6 +36,11 @@ class pfnl_surface(C.Structure):
     _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_size_t * 3)]
 
 
+class pfnl_rect(C.Structure):
+    """A rectangle of a raster in pixels (include/pfnl_hip.h PLACEMENT)."""
+    _fields_ = [("y", C.c_int32), ("x", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/pfnl_hip.h declares
 _vp, _i, _fp = C.c_void_p, C.c_int, C.POINTER(C.c_float)
 SIGNATURES = {
@@ -129,6 +134,9 @@ SIGNATURES = {
     "pfnl_resize_taps": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]),
     "pfnl_op_resize_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pfnl_op_resize_u10": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_stream_place": (_i, [_vp, _i, _i, C.POINTER(pfnl_rect), C.POINTER(pfnl_rect), C.POINTER(C.c_uint8)]),
+    "pfnl_op_resize_place_u8": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(pfnl_rect), C.POINTER(pfnl_rect), C.POINTER(C.c_uint8), _vp, _vp]),
+    "pfnl_op_resize_place_u10": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(pfnl_rect), C.POINTER(pfnl_rect), C.POINTER(C.c_uint16), _vp, _vp]),
     "pfnl_op_scene_sad_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pfnl_op_gather_windows_u8_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
@@ -178,6 +186,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def rect_arg(r):
+    """A (y, x, h, w) tuple as the pointer argument of the placement calls; None stays NULL (the whole raster / canvas)."""
+    return None if r is None else C.byref(pfnl_rect(*(int(v) for v in r)))
 
 
 def check(status: int) -> None:

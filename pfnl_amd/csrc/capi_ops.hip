@@ -1059,6 +1059,40 @@ int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, ui
     return st.finish("resize op: ");
 }
 
+// both placement hooks: everything that needs no device (place_plan asks place_refused of stream_route.h, as the session does)
+static int place_op_refused(const void* in, int n, int H, int W, int oH, int oW, const pfnl_rect* src, const pfnl_rect* dst, const void* out,
+                            pfnl::PlacePlan* plan) {
+    if (!in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(PFNL_ERR_INVALID, "place: n >= 1");
+    std::string why;
+    if (!pfnl::place_plan(H, W, oH, oW, src, dst, plan, &why)) return fail(PFNL_ERR_INVALID, why);
+    return 0;
+}
+
+int pfnl_op_resize_place_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, const pfnl_rect* src, const pfnl_rect* dst,
+                            const uint8_t fill[3], uint8_t* out, void* stream) {
+    pfnl::PlacePlan plan;
+    if (int r = place_op_refused(in, n, H, W, oH, oW, src, dst, out, &plan)) return r;
+    const uint8_t black[3] = {0, 0, 0};
+    OpStage st(stream);
+    const int32_t* blob = st.upload(plan.r.blob);
+    st.run([&] { return pfnl::launch_resize_place_u8(in, out, plan, blob, fill ? fill : black, n, st.s); });
+    return st.finish("place op: ");
+}
+
+int pfnl_op_resize_place_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, const pfnl_rect* src, const pfnl_rect* dst,
+                             const uint16_t fill[3], uint16_t* out, void* stream) {
+    pfnl::PlacePlan plan;
+    if (int r = place_op_refused(in, n, H, W, oH, oW, src, dst, out, &plan)) return r;
+    if (fill && (fill[0] > 1023 || fill[1] > 1023 || fill[2] > 1023)) return fail(PFNL_ERR_INVALID, "place: fill holds 10-bit sample values, 0 .. 1023");
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 2) return fail(PFNL_ERR_INVALID, "place: uint16 samples are 2-byte aligned");
+    const uint16_t black[3] = {0, 0, 0};
+    OpStage st(stream);
+    const int32_t* blob = st.upload(plan.r.blob);
+    st.run([&] { return pfnl::launch_resize_place_u10(in, out, plan, blob, fill ? fill : black, n, st.s); });
+    return st.finish("place10 op: ");
+}
+
 // every refusal comes before any HIP call: the argument checks work without a device
 static int score_geometry_refused(int F, int H, int W) {
     if (F < 1 || F > 65535) return fail(PFNL_ERR_INVALID, "score: F must be in 1 .. 65535");

@@ -3,8 +3,8 @@
 // _run_sequence_on_device) - clamped windows, batching, quantisation, the range flag and the recomputation on the strict kernels - lives
 // here, behind pfnl_forward's own interface: the session calls pfnl_forward / pfnl_get_option / pfnl_set_option / pfnl_range_flag like
 // any other caller and knows nothing of the handle's layout (capi_internal.h, pfnl_handle_view).
-// The output side is one route (stream_route.h: quantise -> resize -> 4:2:0, at 1 or 2 bytes per sample) and one slot per stage: the
-// two setters validate through that header and hand their candidate to apply_setting, the only place that allocates or frees a slot
+// The output side is one route (stream_route.h: quantise -> resize / place -> 4:2:0, at 1 or 2 bytes per sample) and one slot per stage: the
+// setters validate through that header and hand their candidate to apply_setting, the only place that allocates or frees a slot
 // after open; enqueue and pop_frame read the stored route.
 #include <cmath>
 #include <deque>
@@ -61,15 +61,15 @@ struct pfnl_stream {
     bool has_info = false;                            // what pfnl_stream_pop_info returns
     long long info_first = 0;
     unsigned long long info_sad = 0;
-    // the setting (pfnl_stream_format, pfnl_stream_resize; stored by apply_setting alone).  The ring stays RGB24: a YUV frame is converted
+    // the setting (pfnl_stream_format, pfnl_stream_resize, pfnl_stream_place; stored by apply_setting alone).  The ring stays RGB24: a YUV frame is converted
     // on its way into its ring slot.  Every stage `route` runs has a slot with room for a batch - 8- and 10-bit samples share it, as a
     // sequence has one route - and no other stage holds memory; stage 0 is allocated at open.
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
     pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
     pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010
     uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel; from the first YUV in_fmt on
-    pfnl::ResizePlan rplan;                           // rplan.oH = 0: off
-    int32_t* rtab = nullptr;                          // rplan.blob on the device
+    pfnl::PlacePlan rplan;                            // stage 1: a rectangle of the raster on a canvas, the whole onto the whole for a plain size; cH = 0: off
+    int32_t* rtab = nullptr;                          // rplan.r.blob on the device
     pfnl::OutRoute route{};
     StageSlot slot[pfnl::ROUTE_STAGES];
 };
@@ -103,9 +103,15 @@ int enqueue(pfnl_stream* s, const Batch& b) {
     uint8_t* const rgb = r.runs[1] ? rs : q;          // what the 4:2:0 conversion reads
     HIPCHK(ten ? pfnl::launch_quantise_u10(s->sr, u16(q), (size_t)b.count * s->sr_bytes, s->s)
                : pfnl::launch_quantise_u8(s->sr, q, (size_t)b.count * s->sr_bytes, s->s));
-    if (r.runs[1])
-        HIPCHK(ten ? pfnl::launch_resize_u10(u16(q), u16(rs), s->rplan, s->rtab, b.count, s->s)
-                   : pfnl::launch_resize_u8(q, rs, s->rplan, s->rtab, b.count, s->s));
+    if (r.runs[1] && s->rplan.whole) {                // the plain resize launches, as ever
+        HIPCHK(ten ? pfnl::launch_resize_u10(u16(q), u16(rs), s->rplan.r, s->rtab, b.count, s->s)
+                   : pfnl::launch_resize_u8(q, rs, s->rplan.r, s->rtab, b.count, s->s));
+    } else if (r.runs[1]) {                           // a placement: one launch writes the whole canvas, the fill colour included
+        const uint8_t* const f = s->rplan.fill;
+        const uint16_t f10[3] = {pfnl::fill_u10(f[0]), pfnl::fill_u10(f[1]), pfnl::fill_u10(f[2])};
+        HIPCHK(ten ? pfnl::launch_resize_place_u10(u16(q), u16(rs), s->rplan, s->rtab, f10, b.count, s->s)
+                   : pfnl::launch_resize_place_u8(q, rs, s->rplan, s->rtab, f, b.count, s->s));
+    }
     if (r.runs[2])
         HIPCHK(ten ? pfnl::launch_rgb_to_yuv420_u10(u16(rgb), u16(y), s->out_fmt == PFNL_PIX_P010, s->coef10, b.count, r.out_h, r.out_w, s->s)
                    : pfnl::launch_rgb_to_yuv420_u8(rgb, y, s->out_fmt == PFNL_PIX_NV12, s->coef, b.count, r.out_h, r.out_w, s->s));
@@ -325,17 +331,17 @@ void release(pfnl_stream* s) {
     delete s;
 }
 
-// The one place where a setting becomes the session's: both setters end here, with a candidate they have validated and no frame pushed
+// The one place where a setting becomes the session's: every setter ends here, with a candidate they have validated and no frame pushed
 // (`plan` NULL: the output size stays).  1. the route and a batch's bytes per stage; 2. everything new first - a stage slot whose capacity
 // is below the need, the tap table of a new plan, the staging frame of the first YUV in_fmt - and where one fails, what was just made is
 // freed, the session is what it was and the answer is PFNL_ERR_NOMEM with `nomem`; 3. the new buffers go in, the ones they replace and the
 // slots of stages the route does not run are freed, the setting is stored.  A call that replaces or releases device memory first waits
 // for the session's stream - a dropped sequence's device-pointer pops may still be reading it - and only such a call: pfnl_stream_format
 // waits where a 10-bit format meets 8-bit slots or a 4:2:0 slot is no longer needed, and not where it only adds memory or changes none.
-int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& coef, const pfnl::YuvCoef& coef10, pfnl::ResizePlan* plan,
+int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& coef, const pfnl::YuvCoef& coef10, pfnl::PlacePlan* plan,
                   const char* nomem) {
-    const pfnl::ResizePlan& rp = plan ? *plan : s->rplan;
-    const pfnl::OutRoute route = pfnl::out_route(out_fmt, s->scale * s->H, s->scale * s->W, rp.oH, rp.oW);
+    const pfnl::PlacePlan& rp = plan ? *plan : s->rplan;
+    const pfnl::OutRoute route = pfnl::out_route(out_fmt, s->scale * s->H, s->scale * s->W, rp.cH, rp.cW);   // (the delivered frame is the canvas)
     StageSlot fresh[pfnl::ROUTE_STAGES];              // cap != 0: the stage's slot is too small and this one takes its place
     bool frees = plan && s->rtab;
     for (int k = 0; k < pfnl::ROUTE_STAGES; ++k) {
@@ -348,9 +354,10 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
     int32_t* tab = nullptr;
     uint8_t* yin = nullptr;
     bool ok = true;
-    if (plan && plan->oH) {
-        ok = hipMalloc(reinterpret_cast<void**>(&tab), plan->blob.size() * sizeof(int32_t)) == hipSuccess;
-        ok = ok && hipMemcpy(tab, plan->blob.data(), plan->blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    if (plan && plan->cH) {
+        const std::vector<int32_t>& blob = plan->r.blob;
+        ok = hipMalloc(reinterpret_cast<void**>(&tab), blob.size() * sizeof(int32_t)) == hipSuccess;
+        ok = ok && hipMemcpy(tab, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (in_fmt != PFNL_PIX_RGB24 && !s->yin) ok = ok && hipMalloc(reinterpret_cast<void**>(&yin), s->lr_bytes / 2) == hipSuccess;
     for (StageSlot& t : fresh)
@@ -567,7 +574,7 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
     return 0;
 }
 
-// Both setters: bad arguments first (stream_route.h: PFNL_ERR_INVALID at any time), then "before the first frame", then apply_setting.
+// The setters: bad arguments first (stream_route.h: PFNL_ERR_INVALID at any time), then "before the first frame", then apply_setting.
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (const char* why = pfnl::route_refused(in_fmt, out_fmt, s->route.out_h, s->route.out_w)) return fail(PFNL_ERR_INVALID, why);
@@ -578,16 +585,21 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
     return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, "format staging allocation failed");
 }
 
-int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) {
+// pfnl_stream_resize is the placement of the whole raster on the whole canvas: one body, and place_plan keeps resize_plan's words for it
+int pfnl_stream_place(pfnl_stream* s, int out_H, int out_W, const pfnl_rect* src, const pfnl_rect* dst, const uint8_t fill_rgb[3]) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     const int sH = s->scale * s->H, sW = s->scale * s->W;
-    pfnl::ResizePlan plan;                            // (0, 0 is off: oH = oW = 0, no table, the network's raster - which is even)
+    pfnl::PlacePlan plan;                             // (0, 0 is off: cH = cW = 0, no table, the network's raster - which is even)
     std::string why;
-    if ((out_H || out_W) && !pfnl::resize_plan(sH, sW, out_H, out_W, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
-    if (const char* no = pfnl::route_refused(s->in_fmt, s->out_fmt, plan.oH ? plan.oH : sH, plan.oW ? plan.oW : sW)) return fail(PFNL_ERR_INVALID, no);
+    if (!out_H && !out_W && (src || dst || fill_rgb)) return fail(PFNL_ERR_INVALID, "place: src, dst and a fill colour need a canvas size (0, 0 is off)");
+    if ((out_H || out_W) && !pfnl::place_plan(sH, sW, out_H, out_W, src, dst, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
+    if (const char* no = pfnl::route_refused(s->in_fmt, s->out_fmt, plan.cH ? plan.cH : sH, plan.cW ? plan.cW : sW)) return fail(PFNL_ERR_INVALID, no);
     if (s->pushed) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    for (int k = 0; k < 3 && fill_rgb; ++k) plan.fill[k] = fill_rgb[k];
     return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, "resize allocation failed");
 }
+
+int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) { return pfnl_stream_place(s, out_H, out_W, nullptr, nullptr, nullptr); }
 
 int pfnl_stream_mark_cut(pfnl_stream* s) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/pfnl_hip.h"   // pfnl_rect
 #include "chain_order.h"   // persistent_grid: the grid of the persistent launches
 
 namespace pfnl {
@@ -224,6 +225,28 @@ bool resize_plan(int H, int W, int oH, int oW, ResizePlan* p, std::string* why);
 hipError_t launch_resize_u8(const uint8_t* in, uint8_t* out, const ResizePlan& p, const int32_t* blob_dev, int n, hipStream_t s);
 // the same plan and blob on uint16 samples 0 .. 1023 (depth10.hip): 16-byte stores where oW is a multiple of 8 and out is aligned
 hipError_t launch_resize_u10(const uint16_t* in, uint16_t* out, const ResizePlan& p, const int32_t* blob_dev, int n, hipStream_t s);
+
+// ---- a rectangle of the frame on a canvas (place.hip; the rule: pfnl_amd/fit.py place, pfnl_amd/depth10.py place10) ----
+// What a session's stage 1 runs (pfnl_stream_resize, pfnl_stream_place): the rectangle src of the raster sH x sW resampled into the rectangle
+// dst of the canvas cH x cW, the fill colour elsewhere.  `r` is resize_plan(src.h, src.w, dst.h, dst.w) as it always was - tables, blob and
+// the rows of the largest tile, the placed kernel's tiling being anchored at dst -; cH = 0: off; `whole`: src is the raster and dst the
+// canvas, and the launch is launch_resize_u8 / _u10 on `r`.
+struct PlacePlan {
+    ResizePlan r;
+    int sH = 0, sW = 0, cH = 0, cW = 0;
+    pfnl_rect src{}, dst{};
+    bool whole = true;
+    uint8_t fill[3] = {0, 0, 0};   // the session's, as given: 8 bits (a 10-bit route replicates, (v << 2) | (v >> 6)); the launchers take their own
+};
+constexpr uint16_t fill_u10(uint8_t v) { return (uint16_t)((v << 2) | (v >> 6)); }   // 0 -> 0, 255 -> 1023
+// src NULL: the whole raster; dst NULL: the whole canvas.  false + *why: place_refused (stream_route.h) or resize_plan says no (no device needed)
+bool place_plan(int sH, int sW, int cH, int cW, const pfnl_rect* src, const pfnl_rect* dst, PlacePlan* p, std::string* why);
+// in [n][sH][sW][3] -> out [n][cH][cW][3], one launch, every sample of out stored once; blob_dev: p.r.blob on the device; any alignment (16-byte
+// stores where cW is a multiple of 16 - of 8 for uint16 samples - and out is aligned, single samples otherwise); fill: sample values
+hipError_t launch_resize_place_u8(const uint8_t* in, uint8_t* out, const PlacePlan& p, const int32_t* blob_dev, const uint8_t fill[3], int n,
+                                  hipStream_t s);
+hipError_t launch_resize_place_u10(const uint16_t* in, uint16_t* out, const PlacePlan& p, const int32_t* blob_dev, const uint16_t fill[3], int n,
+                                   hipStream_t s);
 
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;

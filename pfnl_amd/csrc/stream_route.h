@@ -1,7 +1,8 @@
 // THE OUTPUT ROUTE OF A STREAMING SESSION (include/pfnl_hip.h pfnl_stream_format / pfnl_stream_resize): what a batch goes through between
-// the fp32 result and pop - stage 0 quantise -> stage 1 resize -> stage 2 RGB -> 4:2:0, at 1 or 2 bytes per sample -, the bytes of a frame
-// behind each stage, which stage pop reads, and the one check of a (formats, size) setting that needs no session.  No HIP types and no HIP
-// runtime calls: a plain C++ program can include this file and walk the rule (tests/test_route_host.py does).
+// the fp32 result and pop - stage 0 quantise -> stage 1 resize (or a placement on a canvas: pfnl_stream_place) -> stage 2 RGB -> 4:2:0, at 1
+// or 2 bytes per sample -, the bytes of a frame behind each stage, which stage pop reads, the one check of a (formats, size) setting that
+// needs no session, and the one check of a placement's rectangles.  No HIP types and no HIP runtime calls: a plain C++ program can include
+// this file and walk the rule (tests/test_route_host.py and tests/test_place_host.py do).
 #pragma once
 #include "surface_geom.h"
 
@@ -55,6 +56,25 @@ inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w) 
         return "format: PFNL_PIX_RGB10 is delivered for RGB24 input only (a YUV in_fmt pairs with a YUV out_fmt or RGB24)";
     if (is_420(out_fmt) && ((out_h | out_w) & 1))
         return "a YUV output format needs an even output size (pfnl_stream_format, pfnl_stream_resize)";
+    return nullptr;
+}
+
+// A PLACEMENT (include/pfnl_hip.h pfnl_stream_place, pfnl_op_resize_place_u8 / _u10; the rule: pfnl_amd/fit.py check_rects): nullptr where
+// `src` is a rectangle of the raster sH x sW, `dst` one of the canvas oH x oW and the resampler takes src -> dst on both axes; else why
+// not, in words that name src or dst.  The session and the op hooks ask this before any HIP call and before any change to a session.
+constexpr int PLACE_MAX_SIZE = 16384;   // a side of raster and canvas (RESIZE_MAX_SIZE: pfnl_resize_taps' limit)
+
+inline const char* place_refused(int sH, int sW, int oH, int oW, const pfnl_rect& src, const pfnl_rect& dst) {
+    if (sH < 1 || sW < 1 || sH > PLACE_MAX_SIZE || sW > PLACE_MAX_SIZE) return "place: the raster src lies in must be 1 .. 16384 a side";
+    if (oH < 1 || oW < 1 || oH > PLACE_MAX_SIZE || oW > PLACE_MAX_SIZE) return "place: the canvas dst lies in must be 1 .. 16384 a side";
+    const auto inside = [](const pfnl_rect& r, int H, int W) {   // (64 bits: y + h of two int32 cannot wrap)
+        return r.h >= 1 && r.w >= 1 && r.y >= 0 && r.x >= 0 && (long long)r.y + r.h <= H && (long long)r.x + r.w <= W;
+    };
+    if (!inside(src, sH, sW)) return "place: src must have h, w >= 1 and lie inside the raster";
+    if (!inside(dst, oH, oW)) return "place: dst must have h, w >= 1 and lie inside the canvas";
+    const auto takes = [](int n_in, int n_out) { return n_out >= (n_in + 3) / 4 && n_out <= 2 * n_in; };
+    if (!takes(src.h, dst.h)) return "place: src.h -> dst.h: the output must lie between a quarter and twice the input";
+    if (!takes(src.w, dst.w)) return "place: src.w -> dst.w: the output must lie between a quarter and twice the input";
     return nullptr;
 }
 

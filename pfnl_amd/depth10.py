@@ -169,3 +169,17 @@ def resize10_unclipped(frame, out_h: int, out_w: int):
 def resize10(frame, out_h: int, out_w: int):
     """[H,W,3] uint16 with values <= 1023 -> [out_h, out_w, 3] uint16."""
     return np.clip(resize10_unclipped(frame, out_h, out_w), 0, MAXV).astype(np.uint16)
+
+
+# ---- placement on a canvas (pfnl_amd/fit.py) -----------------------------------------------------------------------------------------------
+def fill10(fill) -> Tuple[int, int, int]:
+    """An 8-bit fill colour at 10 bits: (v << 2) | (v >> 6) per channel, so 0 -> 0 and 255 -> 1023 (bit replication)."""
+    from . import fit as _fit
+    return tuple((v << 2) | (v >> 6) for v in _fit.as_fill(fill))
+
+
+def place10(frame, out_h: int, out_w: int, src=None, dst=None, fill=(0, 0, 0)):
+    """fit.place on 10-bit samples: [H,W,3] uint16 with values <= 1023 -> [out_h, out_w, 3] uint16, ``fill10(fill)`` everywhere - ``fill``
+    is the 8-bit colour - and resize10(frame[src], dst.h, dst.w) at ``dst``."""
+    from . import fit as _fit
+    return _fit._place(_check_rgb10(frame), out_h, out_w, src, dst, fill10(fill), np.uint16, resize10)

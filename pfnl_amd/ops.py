@@ -676,6 +676,46 @@ def resize_u10(frames, out_size, out=None):
     return out.view(n, oH, oW, 3)
 
 
+def _resize_place(frames, canvas, src, dst, fill, out, name, req, dtype, limit, hook):
+    """Both depths of the placement op: the argument checks of resize_u8 / resize_u10, the rectangles by fit.check_rects."""
+    import torch
+    from . import fit as _fit
+    ptr = req(frames, "frames")
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError(f"{name} expects [n,H,W,3]")
+    n, H, W, _ = frames.shape
+    oH, oW = (int(v) for v in canvas)
+    _fit.check_rects(H, W, oH, oW, _fit.as_rect(src, "src", H, W), _fit.as_rect(dst, "dst", oH, oW))
+    fill = _fit.as_fill(fill, limit)
+    if out is None:
+        out = torch.empty((n, oH, oW, 3), dtype=dtype, device=frames.device)
+    elif out.numel() != n * oH * oW * 3 or out.device != frames.device:
+        raise ValueError("out must hold n * oH * oW * 3 samples on the frames' device")
+    ctype = C.c_uint8 if limit == 255 else C.c_uint16
+    _capi.check(hook(ptr, n, H, W, oH, oW, _capi.rect_arg(src), _capi.rect_arg(dst), (ctype * 3)(*fill), req(out, "out"), _stream(frames)))
+    return out.view(n, oH, oW, 3)
+
+
+def resize_place_u8(frames, canvas, src=None, dst=None, fill=(0, 0, 0), out=None):
+    """[n,H,W,3] (or [H,W,3]) uint8 (cuda) -> [n,oH,oW,3] uint8, ``canvas`` = (oH, oW): ``fill`` everywhere and the resize of the
+    rectangle ``src`` = (y, x, h, w) of each frame (None: the whole frame) at the rectangle ``dst`` of the canvas (None: the whole canvas),
+    byte for byte pfnl_amd/fit.py place (pfnl_op_resize_place_u8: the streaming session's placement, one launch).  Per axis dst between a
+    quarter and twice src; any alignment; ``out``: write there."""
+    import torch
+    return _resize_place(frames, canvas, src, dst, fill, out, "resize_place_u8", _req_u8, torch.uint8, 255,
+                         _capi.load_library().pfnl_op_resize_place_u8)
+
+
+def resize_place_u10(frames, canvas, src=None, dst=None, fill=(0, 0, 0), out=None):
+    """resize_place_u8 on uint16 samples 0 .. 1023: sample for sample pfnl_amd/depth10.py place10 (pfnl_op_resize_place_u10).  ``fill`` holds
+    sample values, 0 .. 1023 (depth10.fill10 of an 8-bit colour)."""
+    import torch
+    return _resize_place(frames, canvas, src, dst, fill, out, "resize_place_u10", _req_u16, torch.uint16, 1023,
+                         _capi.load_library().pfnl_op_resize_place_u10)
+
+
 def score_y(pred_u8, truth_u8, sp_border: int = 8):
     """Y-channel quality sums of uint8 RGB frame pairs on the device (pfnl_op_score_y): pred_u8, truth_u8 [F,H,W,3] uint8 (cuda)
     -> [F,4] float64 (cuda): sum_d2_full, sum_d2_crop (spatial border sp_border), ssim_sum_full, ssim_sum_valid.

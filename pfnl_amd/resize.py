@@ -24,7 +24,8 @@ At the borders this rule clamps - as the bicubic skip and the chroma filters of 
 frame and renormalises; in the interior the two differ by at most one level.  The library builds the same tables with 128-bit integers
 (pfnl_resize_taps) for 1 <= n_in, n_out <= 16384 and ceil(n_in / 4) <= n_out <= 2 n_in; this module states the rule for any pair.
 
-Out of scope: other filters, cropping, letterboxing and aspect handling, resampling ahead of the quantisation.
+Cropping, letterboxing and aspect handling build on this rule in pfnl_amd/fit.py.  Out of scope: other filters, resampling ahead of the
+quantisation.
 """
 from __future__ import annotations
 

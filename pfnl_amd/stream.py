@@ -30,6 +30,12 @@ network's own size.
 the fp32 result quantised to 1023 levels instead of 255, then the same resampling and conversion by the rule of pfnl_amd/depth10.py.
 These are output formats only (``pixel_format`` stays "rgb24" | "nv12" | "i420"), and "rgb10" goes with RGB input.
 
+Placement (off by default): ``open_stream(H, W, batch, out_size=(1080, 1920), fit="contain")`` keeps the picture's aspect ratio - a 4:3
+source lands 1080 x 1440 in the middle of a 16:9 canvas, bars of ``fill`` left and right; ``fit="cover"`` fills the canvas and loses two
+edges; ``sar=(16, 15)`` honours non-square pixels; ``crop=(y, x, h, w)`` (SR-raster pixels) cuts bars off before the picture is scaled;
+``place=(y, x, h, w)`` names the destination outright (``out_size=(1088, 1920), place=(0, 0, 1080, 1920)``: coded height, no resampling).
+One launch on the device writes the canvas, by the integer rule of pfnl_amd/fit.py.
+
 Surfaces: ``vs.push_planes(y, cbcr)`` / ``vs.pop_planes(y, cbcr)`` take and fill a frame as a decoder or encoder holds it - one array per
 plane, each with the row pitch its strides say (pfnl_amd/surface.py), e.g. ``surface[:H, :W]`` of a pitched device allocation - in the
 session's formats; a device NV12 / I420 surface is converted where it lies, and only the samples of a destination are written.
@@ -41,7 +47,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from . import _capi, resize as _resize, surface as _surface
+from . import _capi, fit as _fit, resize as _resize, surface as _surface
 
 
 def next_batch(num_frames: int, batch: int, pushed: int, ended: bool, launched: int) -> Tuple[int, int]:
@@ -88,6 +94,46 @@ def resize_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24") -> T
     return oH, oW
 
 
+def placement_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24", crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0)):
+    """``(oH, oW, src, dst, fill)`` for open_stream's ``out_size``, ``crop``, ``fit``, ``place``, ``sar`` and ``fill`` behind a network output
+    of sH x sW: the arguments of pfnl_stream_place, rectangles as (y, x, h, w).  With ``crop``, ``fit`` and ``place`` at their defaults src and
+    dst are None and (oH, oW) is resize_arguments' answer - pfnl_stream_resize, or no call at all for (0, 0).  The canvas is ``out_size``, else
+    the crop's own size, else the network's raster.  ValueError for anything the library would refuse.  Needs no device."""
+    fill = _fit.as_fill(fill)
+    if fit not in (None, "contain", "cover"):
+        raise ValueError(f'fit: None, "contain" or "cover", got {fit!r}')
+    if fit is not None and place is not None:
+        raise ValueError("fit and place exclude each other: place names the destination that fit would work out")
+    try:
+        sar = tuple(int(v) for v in sar)
+    except (TypeError, ValueError):
+        raise ValueError(f"sar: (num, den), got {sar!r}") from None
+    if len(sar) != 2 or sar[0] < 1 or sar[1] < 1:
+        raise ValueError(f"sar: two positive integers, got {sar!r}")
+    if sar[0] != sar[1] and fit is None:
+        raise ValueError('sar goes with fit="contain" or "cover"')
+    oH, oW = resize_arguments(out_size, sH, sW, out_format) if crop is None and fit is None and place is None else (0, 0)
+    if crop is None and fit is None and place is None:
+        return oH, oW, None, None, fill
+    src = _fit.as_rect(crop, "crop", sH, sW)
+    if out_size is None:
+        oH, oW = (src[2], src[3]) if crop is not None else (sH, sW)
+    else:
+        try:
+            oH, oW = (int(v) for v in out_size)
+        except (TypeError, ValueError):
+            raise ValueError(f"out_size: None or (oH, oW), got {out_size!r}") from None
+    g = 2 if out_format in _capi.FORMATS_420 else 1
+    if g == 2 and (oH % 2 or oW % 2):
+        raise ValueError(f"a {out_format} output needs an even canvas, got {oH} x {oW}")
+    if place is not None:
+        dst = _fit.as_rect(place, "place", oH, oW)
+        _fit.check_rects(sH, sW, oH, oW, src, dst)
+    else:
+        src, dst = _fit.rects(sH, sW, oH, oW, crop, fit, sar, g)
+    return oH, oW, src, dst, fill
+
+
 def frame_shapes(pixel_format: str, H: int, W: int) -> Tuple[tuple, ...]:
     """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24 and rgb10; ``(H*3//2, W)`` or flat for the 4:2:0 formats
     (in samples: uint8, or uint16 for the 10-bit formats - ``frame_dtype``)."""
@@ -119,15 +165,22 @@ class VideoStream:
     pfnl_amd/depth10.py - p010 in the upper ten bits of each sample; ``pixel_format`` takes none of them.
 
     ``out_size`` (None | ``(oH, oW)``): the raster ``pop`` delivers, ``(oH, oW, 3)`` or ``(oH*3//2, oW)``, by the rule of pfnl_amd/resize.py;
-    each axis between a quarter and twice the network's output, even in a 4:2:0 output format."""
+    each axis between a quarter and twice the network's output, even in a 4:2:0 output format.
+
+    ``crop`` / ``fit`` / ``place`` / ``sar`` / ``fill`` (placement_arguments; pfnl_amd/fit.py): the rectangle ``crop`` of the SR raster
+    resampled into a rectangle of the ``out_size`` canvas - the one ``fit`` ("contain" | "cover", with the sample aspect ratio ``sar``) works
+    out, or ``place`` itself - and the 8-bit colour ``fill`` elsewhere.  ``crop`` alone delivers the crop at its own size.  With any of the
+    three set, ``vs.crop`` and ``vs.place`` are the resolved rectangles and ``vs.out_size`` the canvas; else they are None."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
-                 full_range=False, out_size=None):
+                 full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0)):
         import torch
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
         self.pixel_format, self.out_format = pixel_format, pixel_format if out_format is None else out_format
-        size = resize_arguments(out_size, engine.geom.scale * int(H), engine.geom.scale * int(W), self.out_format)
-        self.out_size = size if out_size is not None else None
+        oH, oW, self.crop, self.place, self.fill = placement_arguments(out_size, engine.geom.scale * int(H), engine.geom.scale * int(W),
+                                                                       self.out_format, crop, fit, place, sar, fill)
+        self.out_size = (oH, oW) if oH else None
+        self.fit, self.sar = fit, tuple(sar)
         self.matrix, self.full_range = matrix, bool(full_range)
         if not engine._ready:
             raise RuntimeError("weights have not been loaded")
@@ -163,7 +216,11 @@ class VideoStream:
                 raise
         if self.out_size is not None:               # (behind the format: the size is checked against it)
             try:
-                _capi.check(self._lib.pfnl_stream_resize(s, *self.out_size))
+                if self.place is None:
+                    _capi.check(self._lib.pfnl_stream_resize(s, *self.out_size))
+                else:
+                    _capi.check(self._lib.pfnl_stream_place(s, *self.out_size, _capi.rect_arg(self.crop), _capi.rect_arg(self.place),
+                                                            (C.c_uint8 * 3)(*self.fill)))
             except Exception:
                 self.close()
                 raise
