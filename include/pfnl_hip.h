@@ -205,6 +205,33 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
  * 4 + 2*num_block LR rows per side that is recomputed instead of exchanged - ranks share nothing on the data path and the
  * union of the strips equals pfnl_forward's output up to summation order (tile alignment differs). */
 int pfnl_forward_strip(pfnl_handle* h, const void* in, void* out, int B, int H, int W, int row0, int nrows, void* stream);
+/* SELF-ENSEMBLE (additions to version 4; with n = 1, the default everywhere, every path issues the calls it always issued).  The "+" row
+ * of a super-resolution table: the network runs on the flips and transposes of its input, each result is transformed back, and the
+ * results are averaged.  The reference has no such switch; the loop sits around its sess.run(SR_test, ...) (model/pfnl.py:252, 309), i.e.
+ * around pfnl_forward.  The rule is stated once on the host, pfnl_amd/ensemble.py.  Members k = 0 .. 7 act on the axes H, W of
+ * [..., H, W, 3]: bit 0 mirrors W, bit 1 mirrors H, bit 2 transposes H and W and is applied last; g_k^-1 undoes the steps in reverse
+ * order.  An ensemble of n in {1, 2, 4, 8} uses members 0 .. n-1 (2: the horizontal mirror; 4: both mirrors; 8: adds the transposes, which
+ * run the network at W x H) and is
+ *     acc = f(x);  for k = 1 .. n-1: acc = fl32(acc + g_k^-1(f(g_k(x))));  out = acc * (1 / n)
+ * with f the plain forward of this handle at the same B, fp32 accumulation in increasing k by the one thread that owns each output element,
+ * and an exact scale (a power of two).  n = 1 IS pfnl_forward; n > 1 equals the composition of pfnl_forward calls byte for byte.
+ *   pfnl_forward_ensemble: arguments, checks, stream rule and host-pointer staging of pfnl_forward; n outside {1, 2, 4, 8} is
+ *     PFNL_ERR_INVALID before any device call.  Member 0 writes `out` directly; every other member goes g_k(in) -> a handle buffer, the
+ *     forward -> a second handle buffer, and is added into `out` at g_k^-1's positions (pfnl_amd/csrc/dihedral.hip: two bandwidth-bound
+ *     kernels, the transposing members through an LDS tile).  Both buffers and the workspace of BOTH geometries (the plan-dependent
+ *     buffers differ between H x W and W x H) are sized before the first member is enqueued: nothing moves while members are in flight.
+ *   Range: every member's tail kernel writes the call's flag.  A host-pointer call reads it once, behind the last member, and redoes the
+ *     WHOLE ensemble on the f32-MFMA kernels (one count in pfnl_range_reruns; PFNL_ERR_RANGE under precision=bf16, as pfnl_forward);
+ *     device-pointer calls stay asynchronous and leave the flag to pfnl_sync / pfnl_range_flag.
+ *   The option "graph" does not apply for n > 1: members always run eagerly.  The kernels of dihedral.hip run under no profile class.
+ *   pfnl_stream_ensemble (below): a session's batches go through this call.
+ * Out of scope: pfnl_forward_strip and the multi-GPU paths stay without an ensemble; other groups (rotations by other angles, temporal
+ * reversal); weighting the members. */
+int pfnl_forward_ensemble(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device,
+                          int B, int H, int W, int n, void* stream);
+/* Every buffer a pfnl_forward with these arguments can touch.  pfnl_forward_ensemble with n > 1 adds two grow-only buffers that are not
+ * counted here: the transformed input, B*T*H*W*3 floats, and one member's output, B*sH*sW*3 floats; with n = 8 also whatever the plan of
+ * (B, W, H) needs beyond that of (B, H, W) (pfnl_workspace_bytes(h, B, W, H) states it). */
 int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes);
 /* THE LAUNCH PLAN of the progressive-fusion trunk (reference model/pfnl.py:65-71) for a [B,T,H,W,3] forward under the handle's current
  * options, as text: "<structure> launches_per_block=<n> c1x1=<launches of class conv1x1 among them> precision=<..> conv3x3=<..> conv1x1=<..>
@@ -384,6 +411,12 @@ typedef struct pfnl_surface {
 } pfnl_surface;
 int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_device);
 int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_device, long long* index, int* got);
+/* SELF-ENSEMBLE in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With
+ * n in {2, 4, 8} the one forward of every batch is pfnl_forward_ensemble(..., n, ...) (SELF-ENSEMBLE above); gather, quantisation, the
+ * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  n = 1 is
+ * off; any other n is PFNL_ERR_INVALID.  Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); the
+ * setting survives pfnl_stream_reset. */
+int pfnl_stream_ensemble(pfnl_stream* s, int n);
 
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
@@ -715,6 +748,15 @@ int pfnl_op_bicubic(const float* x, float* out, int B, int H, int W, int scale, 
  * DownSample_4D with BLUR): reflect-pad 6, 13x13 Gaussian sigma 1.6, stride `scale`, VALID.
  * hr [F,H,W,3] -> lr [F,ceil(H/scale),ceil(W/scale),3], device pointers, async on stream. */
 int pfnl_op_blur_decimate(const float* hr, float* lr, int F, int H, int W, int scale, void* stream);
+/* The two launches of the self-ensemble (SELF-ENSEMBLE above; pfnl_amd/csrc/dihedral.hip; the rule: pfnl_amd/ensemble.py), device
+ * pointers, asynchronous on `stream`; NULL, k outside 0 .. 7, n_img < 1 and non-positive H or W are PFNL_ERR_INVALID before any HIP call.
+ *   pfnl_op_dihedral: out = g_k(in) * scale.  in [n_img,H,W,3] -> out [n_img,H,W,3], or [n_img,W,H,3] for k >= 4; scale = 1 copies bits.
+ *   pfnl_op_dihedral_accum: acc = fl32(acc + g_k^-1(y)) * scale.  acc [n_img,H,W,3]; y [n_img,H,W,3], or [n_img,W,H,3] for k >= 4
+ *     (H, W are acc's); scale = 1 is the plain sum.  Every element of acc is read and written once, by one thread; no atomics.
+ * in / y must not overlap out / acc.  16-byte accesses where W % 4 == 0 (the row length of both sides for k < 4) and both pointers are
+ * 16-byte aligned; any alignment of whole floats otherwise. */
+int pfnl_op_dihedral(const float* in, float* out, int n_img, int H, int W, int k, float scale, void* stream);
+int pfnl_op_dihedral_accum(float* acc, const float* y, int n_img, int H, int W, int k, float scale, void* stream);
 /* MFMA operand/accumulator layout self-test (asymmetric operands); returns 0 if the f32
  * 32x32x2 fragment maps this library assumes hold on the device. */
 int pfnl_selftest_mfma(int device_id);

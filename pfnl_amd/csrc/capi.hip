@@ -234,6 +234,7 @@ struct pfnl_handle {
     // workspace
     DevBuf nl16;                                              // bf16 non-local: split K / V^T operands
     DevBuf X, Xo, nlp, inp0, inp1, base, pb, merge, stage_in, stage_out, scratch;
+    DevBuf ens_in, ens_y;                                     // pfnl_forward_ensemble: g_k(in) [B][T][H][W][3] and one member's output [B][sH][sW][3]
     int lastB = 0, lastH = 0, lastW = 0;
 
     // profiling: boundary events.  One event after every kernel launch (plus one at the start of a
@@ -936,7 +937,7 @@ int pfnl_destroy(pfnl_handle* h) {
     h->pin_out.release();
     if (h->rflag_host) hipHostFree(h->rflag_host);
     for (DevBuf* b : {&h->p10, &h->Xs, &h->Q, &h->wdev16s, &h->wdev, &h->wdev16, &h->nl16, &h->X, &h->Xo, &h->nlp, &h->inp0, &h->inp0sf, &h->c10part, &h->inp1, &h->base, &h->pb, &h->merge,
-                      &h->stage_in, &h->stage_out, &h->scratch})
+                      &h->stage_in, &h->stage_out, &h->scratch, &h->ens_in, &h->ens_y})
         b->release();
     delete h;
     return 0;
@@ -1488,6 +1489,89 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
             h->strict_once = true;
             const int e = forward_device(h, din, dout, B, H, W, s, nullptr, 0, -1, 0);   // (strict: the fence is not armed; still
             h->strict_once = false;                                                    //  non-finite = so is the reference's result)
+            if (e) return e;
+            ++h->range_reruns;
+            if (!out_is_device) {
+                if (int e2 = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e2;
+            } else {
+                HIPCHK(hipStreamSynchronize(s));
+            }
+        } else if (flagged && h->opt.bf16) {
+            return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
+        }
+    }
+    return 0;
+}
+
+// ---- self-ensemble (include/pfnl_hip.h SELF-ENSEMBLE; the rule: pfnl_amd/ensemble.py): the loop around forward_device
+
+// Everything the members of one ensemble touch, sized before the first of them is enqueued: the two ensemble buffers and the workspace of
+// both geometries (ensure_workspace only grows; the plan-dependent buffers differ between H x W and W x H, the others - and what
+// nonlocal_block sizes by B and the key count - do not)
+static int ensemble_presize(pfnl_handle* h, int B, int H, int W, int n) {
+    const int T = h->cfg.num_frames, sc = h->cfg.scale;
+    if (h->ens_in.ensure((size_t)B * T * H * W * 3) || h->ens_y.ensure((size_t)B * H * W * sc * sc * 3))
+        return fail(PFNL_ERR_NOMEM, "ensemble buffer allocation failed");
+    if (n > 4)
+        if (int e = ensure_workspace(h, trunk_plan(h, B, W, H, W), B, W, H, (W / 2) * (H / 2))) return e;
+    return ensure_workspace(h, trunk_plan(h, B, H, W, H), B, H, W, (H / 2) * (W / 2));
+}
+
+// members 0 .. n-1 on `s`: din [B][T][H][W][3] -> dout [B][sH][sW][3] (device pointers); under the handle's current strict_once
+static int ensemble_device(pfnl_handle* h, const float* din, float* dout, int B, int H, int W, int n, hipStream_t s, int slot) {
+    const int T = h->cfg.num_frames, sc = h->cfg.scale;
+    if (int e = ensemble_presize(h, B, H, W, n)) return e;
+    if (int e = forward_device(h, din, dout, B, H, W, s, nullptr, 0, -1, slot)) return e;   // member 0 writes acc
+    for (int k = 1; k < n; ++k) {
+        const bool t = (k & 4) != 0;
+        HIPCHK(launch_dihedral(din, h->ens_in.p, B * T, H, W, k, 1.0f, s));
+        if (int e = forward_device(h, h->ens_in.p, h->ens_y.p, B, t ? W : H, t ? H : W, s, nullptr, 0, -1, slot)) return e;
+        HIPCHK(launch_dihedral_accum(dout, h->ens_y.p, B, sc * H, sc * W, k, k == n - 1 ? 1.0f / (float)n : 1.0f, s));
+    }
+    return 0;
+}
+
+int pfnl_forward_ensemble(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device, int B, int H, int W, int n,
+                          void* stream) {
+    if (n != 1 && n != 2 && n != 4 && n != 8) return fail(PFNL_ERR_INVALID, "ensemble: n must be 1, 2, 4 or 8");
+    if (n == 1) return pfnl_forward(h, in, in_is_device, out, out_is_device, B, H, W, stream);
+    if (!h || !in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!h->finalized) return fail(PFNL_ERR_STATE, "pfnl_finalize_weights has not been called");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(PFNL_ERR_INVALID, "B, H, W must be positive");
+    if ((H & 1) || (W & 1))
+        return fail(PFNL_ERR_INVALID, "H and W must be even (space_to_depth(2), reference model/pfnl.py:57)");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    const int T = h->cfg.num_frames, sc = h->cfg.scale;
+    const size_t n_in = (size_t)B * T * H * W * 3, n_out = (size_t)B * H * W * sc * sc * 3;
+    const float* din = (const float*)in;
+    float* dout = (float*)out;
+    const bool sync_call = !in_is_device || !out_is_device;     // as pfnl_forward: whose range flag, which stream
+    const int slot = sync_call ? 0 : 1;
+    const bool can_rerun = !h->opt.bf16 && !(h->opt.strict || !h->weights_f16_ok);
+    hipStream_t s = stream ? (hipStream_t)stream : ((in_is_device && out_is_device) ? (hipStream_t) nullptr : h->stream);
+    if (!in_is_device) {
+        if (h->stage_in.ensure(n_in)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
+        if (int e = stage_h2d(h, h->stage_in.p, in, n_in * sizeof(float), s)) return e;
+        din = h->stage_in.p;
+    }
+    if (!out_is_device) {
+        if (h->stage_out.ensure(n_out)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
+        dout = h->stage_out.p;
+    }
+    if (int e = ensemble_device(h, din, dout, B, H, W, n, s, slot)) return e;
+    if (!out_is_device) {
+        if (int e = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e;
+    } else if (!in_is_device) {
+        HIPCHK(hipStreamSynchronize(s));   // the caller may reuse its host buffer on return
+    }
+    if (sync_call) {
+        // the flag of all n members, read once behind the last of them; set: the whole ensemble once more on the f32-MFMA kernels
+        int flagged = 0;
+        if (int e = range_flag_take(h, 0, &flagged)) return e;
+        if (flagged && can_rerun) {
+            h->strict_once = true;
+            const int e = ensemble_device(h, din, dout, B, H, W, n, s, 0);
+            h->strict_once = false;
             if (e) return e;
             ++h->range_reruns;
             if (!out_is_device) {

@@ -1118,6 +1118,26 @@ int pfnl_op_score_y(const uint8_t* pred, const uint8_t* truth, int F, int H, int
     return 0;
 }
 
+// as below: refused before any HIP call
+static int dihedral_op_refused(const void* a, const void* b, int n_img, int H, int W, int k) {
+    if (!a || !b) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (k < 0 || k > 7) return fail(PFNL_ERR_INVALID, "dihedral: member k must lie in 0 .. 7");
+    if (n_img < 1 || H <= 0 || W <= 0) return fail(PFNL_ERR_INVALID, "dihedral: n_img, H and W must be positive");
+    return 0;
+}
+
+int pfnl_op_dihedral(const float* in, float* out, int n_img, int H, int W, int k, float scale, void* stream) {
+    if (int r = dihedral_op_refused(in, out, n_img, H, W, k)) return r;
+    HIPCHK(pfnl::launch_dihedral(in, out, n_img, H, W, k, scale, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_dihedral_accum(float* acc, const float* y, int n_img, int H, int W, int k, float scale, void* stream) {
+    if (int r = dihedral_op_refused(acc, y, n_img, H, W, k)) return r;
+    HIPCHK(pfnl::launch_dihedral_accum(acc, y, n_img, H, W, k, scale, (hipStream_t)stream));
+    return 0;
+}
+
 int pfnl_op_bicubic(const float* x, float* out, int B, int H, int W, int scale, void* stream) {
     if (!x || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (B < 1 || H < 1 || W < 1 || (scale != 2 && scale != 4)) return fail(PFNL_ERR_INVALID, "bad bicubic geometry");

@@ -49,6 +49,7 @@ struct pfnl_stream {
     std::deque<Batch> q;                              // launched, not yet fully delivered: at most two
     bool strict = false;                              // a batch was flagged: the rest of the sequence runs on the strict kernels
     std::string prior_strict, prior_precision;        // what the library held before go_strict changed it ("" = unchanged)
+    int ensemble = 1;                                 // pfnl_stream_ensemble: the members of every batch's forward (1: the plain forward)
     // scenes (pfnl_stream_scenes): allocated by the first call that turns them on; they have the ring's lifetime and its slots
     int scene_mode = 0;                               // 0 off | 1 marks | 2 marks + detector
     unsigned long long thr_sum = 0;                   // ceil(threshold H W): the detector compares sums
@@ -93,7 +94,7 @@ int enqueue(pfnl_stream* s, const Batch& b) {
     } else {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
-    if (int e = pfnl_forward(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->s)) return e;
+    if (int e = pfnl_forward_ensemble(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->ensemble, s->s)) return e;   // (1: pfnl_forward itself)
     // the route, each stage out of the slot of the one before it (a replay takes the same route: pop stays a copy); 10 bits: the same
     // launches on uint16 samples (depth10.hip) - the twins stay apart, tools/GFX950_NOTES.md
     const pfnl::OutRoute& r = s->route;
@@ -534,6 +535,14 @@ int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_devi
         }
         return 0;
     });
+}
+
+int pfnl_stream_ensemble(pfnl_stream* s, int n) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (n != 1 && n != 2 && n != 4 && n != 8) return fail(PFNL_ERR_INVALID, "ensemble: n must be 1, 2, 4 or 8");
+    if (s->pushed) return fail(PFNL_ERR_STATE, "the ensemble is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    s->ensemble = n;
+    return 0;
 }
 
 int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {

@@ -248,6 +248,13 @@ hipError_t launch_resize_place_u8(const uint8_t* in, uint8_t* out, const PlacePl
 hipError_t launch_resize_place_u10(const uint16_t* in, uint16_t* out, const PlacePlan& p, const int32_t* blob_dev, const uint16_t fill[3], int n,
                                    hipStream_t s);
 
+// ---- the flips and transposes of the self-ensemble (dihedral.hip; the rule: pfnl_amd/ensemble.py) ----
+// member k: bit 0 mirrors W, bit 1 mirrors H, bit 2 transposes H and W (applied last).  scale == 1 leaves the bits as they are.
+// out = g_k(in) * scale: in [n][H][W][3] -> out [n][H][W][3], or [n][W][H][3] for k >= 4
+hipError_t launch_dihedral(const float* in, float* out, int n, int H, int W, int k, float scale, hipStream_t s);
+// acc = (acc + g_k^-1(y)) * scale: acc [n][H][W][3]; y [n][H][W][3], or [n][W][H][3] for k >= 4; one thread per element of acc, no atomics
+hipError_t launch_dihedral_accum(float* acc, const float* y, int n, int H, int W, int k, float scale, hipStream_t s);
+
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;
 // partial: score_scratch_bytes(F, H, W) of device memory (one slot per workgroup: the sums are repeatable bit for bit)

@@ -13,6 +13,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import _capi
+from .ensemble import members as _members
 from .spec import PFNLGeometry, check_weights
 
 
@@ -74,6 +75,12 @@ class _PinnedPool:
 _pinned_pool = _PinnedPool()
 
 
+def ensemble_members(n) -> int:
+    """``n`` as the C-ABI takes it; ValueError for anything but 1, 2, 4, 8 (the host rule's own check: pfnl_amd/ensemble.py members)."""
+    _members(n)
+    return int(n)
+
+
 class PFNLEngine:
     def __init__(self, geom: PFNLGeometry = PFNLGeometry(), device: int = 0):
         self.geom = geom
@@ -86,6 +93,7 @@ class PFNLEngine:
         self._h = h
         self._ready = False
         self._options: Dict[str, str] = {}       # what set_option was called with (the library's own view: get_option)
+        self.ensemble = 1                        # members of forward()'s self-ensemble when the call names none (pfnl_amd/ensemble.py)
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -127,6 +135,7 @@ class PFNLEngine:
         for k in self.OPTION_KEYS:
             other.set_option(k, self.get_option(k))
         other.copy_weights_from(self)
+        other.ensemble = self.ensemble
         return other
 
     def set_option(self, key: str, value: str) -> None:
@@ -164,11 +173,13 @@ class PFNLEngine:
         s = self.geom.scale
         return (B, 1, s * H, s * W, 3)
 
-    def forward(self, x):
+    def forward(self, x, ensemble=None):
         """x: [B,T,H,W,3] float32 (numpy array, torch CPU tensor or torch tensor on this engine's
         GPU) -> [B,1,sH,sW,3] float32 in the same kind of container (reference model/pfnl.py:39-80).
         Host containers: synchronous (H2D + kernels + D2H inside pfnl_forward).  Device tensors:
-        enqueued on torch's current stream."""
+        enqueued on torch's current stream.  ``ensemble``: 1, 2, 4 or 8 members of the geometric self-ensemble
+        (pfnl_forward_ensemble; the rule: pfnl_amd/ensemble.py); None: ``self.ensemble``, 1 unless set - the plain forward."""
+        n = ensemble_members(self.ensemble if ensemble is None else ensemble)
         if _is_torch(x):
             import torch
             if x.is_cuda:
@@ -178,18 +189,21 @@ class PFNLEngine:
                 x = x.contiguous()
                 out = torch.empty(self.out_shape(B, H, W), dtype=torch.float32, device=x.device)
                 stream = torch.cuda.current_stream(x.device).cuda_stream
-                _capi.check(self._lib.pfnl_forward(self._h, C.c_void_p(x.data_ptr()), 1,
-                                                   C.c_void_p(out.data_ptr()), 1, B, H, W,
-                                                   C.c_void_p(stream)))
+                _capi.check(self._forward(n, C.c_void_p(x.data_ptr()), 1, C.c_void_p(out.data_ptr()), 1, B, H, W, C.c_void_p(stream)))
                 return out
-            return torch.from_numpy(self.forward(x.detach().numpy()))
+            return torch.from_numpy(self.forward(x.detach().numpy(), ensemble=n))
         x = np.asarray(x)
         B, T, H, W = self._check_input(x.shape, x.dtype == np.float32)
         x = np.ascontiguousarray(x)
         out = self._host_output(self.out_shape(B, H, W))
-        _capi.check(self._lib.pfnl_forward(self._h, x.ctypes.data_as(C.c_void_p), 0,
-                                           out.ctypes.data_as(C.c_void_p), 0, B, H, W, None))
+        _capi.check(self._forward(n, x.ctypes.data_as(C.c_void_p), 0, out.ctypes.data_as(C.c_void_p), 0, B, H, W, None))
         return out
+
+    def _forward(self, n: int, inp, in_is_device: int, out, out_is_device: int, B: int, H: int, W: int, stream) -> int:
+        """pfnl_forward on this handle, or pfnl_forward_ensemble with n > 1 members; the status."""
+        if n == 1:
+            return self._lib.pfnl_forward(self._h, inp, in_is_device, out, out_is_device, B, H, W, stream)
+        return self._lib.pfnl_forward_ensemble(self._h, inp, in_is_device, out, out_is_device, B, H, W, n, stream)
 
     @staticmethod
     def _host_output(shape) -> np.ndarray:
@@ -210,12 +224,13 @@ class PFNLEngine:
         """"pinned" (pool of pfnl_host_alloc blocks) or "pageable": what bench.py records next to its host-pointer line."""
         return "pageable" if os.environ.get("PFNL_HOST_OUTPUT", "pinned") == "pageable" else "pinned (pfnl_host_alloc pool)"
 
-    def forward_device(self, in_ptr: int, out_ptr: int, B: int, H: int, W: int, stream: int = 0) -> None:
+    def forward_device(self, in_ptr: int, out_ptr: int, B: int, H: int, W: int, stream: int = 0, ensemble: int = 1) -> None:
         """Raw device-pointer form (asynchronous on ``stream``; 0 = the legacy null stream, i.e. torch's default stream).
-        Asynchronous calls cannot re-run on the f32 kernels when the f16-pipe range flag fires: check ``sync()``."""
+        Asynchronous calls cannot re-run on the f32 kernels when the f16-pipe range flag fires: check ``sync()``.
+        ``ensemble``: as for ``forward``; the default is the plain forward whatever ``self.ensemble`` holds."""
         self._check_input((B, self.geom.num_frames, H, W, 3), True)
-        _capi.check(self._lib.pfnl_forward(self._h, C.c_void_p(in_ptr), 1, C.c_void_p(out_ptr), 1, B, H, W,
-                                           C.c_void_p(stream) if stream else None))
+        _capi.check(self._forward(ensemble_members(ensemble), C.c_void_p(in_ptr), 1, C.c_void_p(out_ptr), 1, B, H, W,
+                                  C.c_void_p(stream) if stream else None))
 
     def forward_strip(self, x, out, row0: int, nrows: int) -> None:
         """Single-clip sharding: x [B,T,H,W,3] float32 cuda tensor (the whole clip), out [B,1,sH,sW,3] float32 cuda tensor
@@ -230,16 +245,18 @@ class PFNLEngine:
                                                  int(row0), int(nrows), C.c_void_p(stream) if stream else None))
 
     def open_stream(self, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
-                    full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0)):
+                    full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0), ensemble=1):
         """A streaming session on this engine (pfnl_stream_open; pfnl_amd/stream.py VideoStream): uint8 LR frames [H,W,3] pushed one at
         a time, uint8 SR frames popped in order, ``batch`` windows per forward.  One open session per engine.  ``scene_cut``: None,
         "manual" or a detector threshold - windows that stay inside a scene (VideoStream).  ``pixel_format`` / ``out_format`` "nv12" or "i420":
         YUV 4:2:0 frames in / out, converted on the device with ``matrix`` and ``full_range`` (pfnl_amd/yuv.py).  ``out_size`` (oH, oW): the raster of the
         delivered frames, resampled on the device (pfnl_amd/resize.py).  ``out_format`` "rgb10", "p010" or "i010": uint16 frames with 10-bit
         values, quantised, resampled and converted at that depth (pfnl_amd/depth10.py).  ``crop`` / ``fit`` / ``place`` / ``sar`` / ``fill``: a
-        rectangle of the SR raster on the ``out_size`` canvas - crop, letterbox, aspect fit - in one launch (pfnl_amd/fit.py; VideoStream)."""
+        rectangle of the SR raster on the ``out_size`` canvas - crop, letterbox, aspect fit - in one launch (pfnl_amd/fit.py; VideoStream).
+        ``ensemble``: 1, 2, 4 or 8 - every batch's forward as a self-ensemble of that many members (pfnl_amd/ensemble.py); 1: off."""
         from .stream import VideoStream
-        return VideoStream(self, H, W, batch, scene_cut, pixel_format, out_format, matrix, full_range, out_size, crop, fit, place, sar, fill)
+        return VideoStream(self, H, W, batch, scene_cut, pixel_format, out_format, matrix, full_range, out_size, crop, fit, place, sar, fill,
+                           ensemble)
 
     def sync(self) -> None:
         """Synchronise the engine's streams; raises if a device-pointer forward left the f16-pipe kernels' range

@@ -288,6 +288,42 @@ def bicubic(x, scale: int):
     return out
 
 
+def _dihedral_shape(x, k, name):
+    if not (isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 0 <= int(k) <= 7):
+        raise ValueError(f"member k must lie in 0 .. 7, got {k!r}")
+    if x.dim() < 3 or x.shape[-1] != 3 or x.numel() == 0:
+        raise ValueError(f"{name}: expected [..., H, W, 3], got {tuple(x.shape)}")
+    H, W = int(x.shape[-3]), int(x.shape[-2])
+    return int(k), x.numel() // (H * W * 3), H, W
+
+
+def dihedral(x, k: int, out=None, scale: float = 1.0):
+    """Member k of the self-ensemble's group (pfnl_amd/ensemble.py transform): x [..., H, W, 3] (cuda) -> [..., H, W, 3], or
+    [..., W, H, 3] for k >= 4, times ``scale`` (1: the bits as they are).  ``out``: a contiguous tensor of that shape to fill."""
+    import torch
+    lib = _capi.load_library()
+    k, n, H, W = _dihedral_shape(x, k, "x")
+    shape = tuple(x.shape[:-3]) + ((W, H, 3) if k & 4 else (H, W, 3))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out must have shape {shape}, got {tuple(out.shape)}")
+    _capi.check(lib.pfnl_op_dihedral(_req(x, "x"), _req(out, "out"), n, H, W, k, float(scale), _stream(x)))
+    return out
+
+
+def dihedral_accum(acc, y, k: int, scale: float = 1.0):
+    """acc = (acc + inverse(y, k)) * scale in place, float32, one thread per element (pfnl_amd/ensemble.py inverse; the step of
+    ``combine``): acc [..., H, W, 3] (cuda), y of the same shape, or [..., W, H, 3] for k >= 4.  Returns acc."""
+    lib = _capi.load_library()
+    k, n, H, W = _dihedral_shape(acc, k, "acc")
+    want = tuple(acc.shape[:-3]) + ((W, H, 3) if k & 4 else (H, W, 3))
+    if tuple(y.shape) != want:
+        raise ValueError(f"y must have shape {want}, got {tuple(y.shape)}")
+    _capi.check(lib.pfnl_op_dihedral_accum(_req(acc, "acc"), _req(y, "y"), n, H, W, k, float(scale), _stream(acc)))
+    return acc
+
+
 def blur_decimate(hr, scale: int = 4):
     """reference utils.py:169-192 (DownSample_4D with BLUR): hr [F,H,W,3] (cuda) -> [F,ceil(H/s),ceil(W/s),3]."""
     import torch

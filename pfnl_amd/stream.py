@@ -47,7 +47,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from . import _capi, fit as _fit, resize as _resize, surface as _surface
+from . import _capi, ensemble as _ensemble, fit as _fit, resize as _resize, surface as _surface
 
 
 def next_batch(num_frames: int, batch: int, pushed: int, ended: bool, launched: int) -> Tuple[int, int]:
@@ -134,6 +134,13 @@ def placement_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24", c
     return oH, oW, src, dst, fill
 
 
+def ensemble_argument(ensemble=1) -> int:
+    """The argument of pfnl_stream_ensemble for open_stream's ``ensemble``: 1 (off: no call), 2, 4 or 8 members of pfnl_amd/ensemble.py;
+    ValueError for anything the library would refuse.  Needs no device."""
+    _ensemble.members(ensemble)
+    return int(ensemble)
+
+
 def frame_shapes(pixel_format: str, H: int, W: int) -> Tuple[tuple, ...]:
     """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24 and rgb10; ``(H*3//2, W)`` or flat for the 4:2:0 formats
     (in samples: uint8, or uint16 for the 10-bit formats - ``frame_dtype``)."""
@@ -170,12 +177,15 @@ class VideoStream:
     ``crop`` / ``fit`` / ``place`` / ``sar`` / ``fill`` (placement_arguments; pfnl_amd/fit.py): the rectangle ``crop`` of the SR raster
     resampled into a rectangle of the ``out_size`` canvas - the one ``fit`` ("contain" | "cover", with the sample aspect ratio ``sar``) works
     out, or ``place`` itself - and the 8-bit colour ``fill`` elsewhere.  ``crop`` alone delivers the crop at its own size.  With any of the
-    three set, ``vs.crop`` and ``vs.place`` are the resolved rectangles and ``vs.out_size`` the canvas; else they are None."""
+    three set, ``vs.crop`` and ``vs.place`` are the resolved rectangles and ``vs.out_size`` the canvas; else they are None.
+
+    ``ensemble`` (1 | 2 | 4 | 8): every batch's forward as a geometric self-ensemble of that many members (pfnl_amd/ensemble.py); 1 is off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
-                 full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0)):
+                 full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0), ensemble=1):
         import torch
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
+        self.ensemble = ensemble_argument(ensemble)
         self.pixel_format, self.out_format = pixel_format, pixel_format if out_format is None else out_format
         oH, oW, self.crop, self.place, self.fill = placement_arguments(out_size, engine.geom.scale * int(H), engine.geom.scale * int(W),
                                                                        self.out_format, crop, fit, place, sar, fill)
@@ -221,6 +231,12 @@ class VideoStream:
                 else:
                     _capi.check(self._lib.pfnl_stream_place(s, *self.out_size, _capi.rect_arg(self.crop), _capi.rect_arg(self.place),
                                                             (C.c_uint8 * 3)(*self.fill)))
+            except Exception:
+                self.close()
+                raise
+        if self.ensemble != 1:                      # (1: the session as it always was, and no call)
+            try:
+                _capi.check(self._lib.pfnl_stream_ensemble(s, self.ensemble))
             except Exception:
                 self.close()
                 raise
