@@ -940,14 +940,14 @@ int pfnl_op_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene
 int pfnl_op_quantise_u8(const float* sr, uint8_t* out, size_t n, void* stream) {
     if (!sr || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (!n || n % 4) return fail(PFNL_ERR_INVALID, "element count must be a positive multiple of 4");
-    HIPCHK(pfnl::launch_quantise_u8(sr, out, n, (hipStream_t)stream));
+    HIPCHK(pfnl::launch_quantise(sr, out, n, (hipStream_t)stream));
     return 0;
 }
 
 int pfnl_yuv_coefficients(int matrix, int full_range, int32_t out[15]) {
     if (!out) return fail(PFNL_ERR_INVALID, "NULL argument");
     pfnl::YuvCoef c;
-    if (!pfnl::yuv_coefficients(matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (!pfnl::yuv_coefficients(8, matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     const int v[15] = {c.y0, c.yr, c.yg, c.yb, c.cbr, c.cbg, c.cbb, c.crr, c.crg, c.crb, c.dy, c.drv, c.dgu, c.dgv, c.dbu};
     for (int k = 0; k < 15; ++k) out[k] = v[k];
     return 0;
@@ -957,7 +957,7 @@ int pfnl_yuv_coefficients(int matrix, int full_range, int32_t out[15]) {
 static int yuv_op_refused(const void* a, const void* b, int fmt, int matrix, int full_range, int n, int H, int W, pfnl::YuvCoef* c) {
     if (!a || !b) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (fmt != PFNL_PIX_NV12 && fmt != PFNL_PIX_I420) return fail(PFNL_ERR_INVALID, "yuv: fmt must be PFNL_PIX_NV12 or PFNL_PIX_I420");
-    if (!pfnl::yuv_coefficients(matrix, full_range, c)) return fail(PFNL_ERR_INVALID, "yuv: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (!pfnl::yuv_coefficients(8, matrix, full_range, c)) return fail(PFNL_ERR_INVALID, "yuv: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (n < 1 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "yuv: n >= 1, H and W positive and even (4:2:0)");
     return 0;
 }
@@ -981,14 +981,14 @@ int pfnl_op_yuv420_to_rgb_u8_surface(const pfnl_surface* yuv, int fmt, int matri
 int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, void* stream) {
     pfnl::YuvCoef c;
     if (int r = yuv_op_refused(rgb, yuv, fmt, matrix, full_range, n, H, W, &c)) return r;
-    HIPCHK(pfnl::launch_rgb_to_yuv420_u8(rgb, yuv, fmt == PFNL_PIX_NV12, c, n, H, W, (hipStream_t)stream));
+    HIPCHK(pfnl::launch_rgb_to_yuv420(rgb, yuv, fmt == PFNL_PIX_NV12, c, n, H, W, (hipStream_t)stream));
     return 0;
 }
 
 int pfnl_yuv10_coefficients(int matrix, int full_range, int32_t out[10]) {
     if (!out) return fail(PFNL_ERR_INVALID, "NULL argument");
     pfnl::YuvCoef c;
-    if (!pfnl::yuv10_coefficients(matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (!pfnl::yuv_coefficients(10, matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     const int v[10] = {c.y0, c.yr, c.yg, c.yb, c.cbr, c.cbg, c.cbb, c.crr, c.crg, c.crb};
     for (int k = 0; k < 10; ++k) out[k] = v[k];
     return 0;
@@ -999,7 +999,7 @@ int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream)
     if (!n || n % 4) return fail(PFNL_ERR_INVALID, "element count must be a positive multiple of 4");
     if (reinterpret_cast<uintptr_t>(sr) % 16 || reinterpret_cast<uintptr_t>(out) % 8)
         return fail(PFNL_ERR_INVALID, "quantise_u10: sr must be 16-byte aligned and out 8-byte aligned");
-    HIPCHK(pfnl::launch_quantise_u10(sr, out, n, (hipStream_t)stream));
+    HIPCHK(pfnl::launch_quantise(sr, out, n, (hipStream_t)stream));
     return 0;
 }
 
@@ -1007,23 +1007,24 @@ int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full
     if (!rgb || !yuv) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (fmt != PFNL_PIX_P010 && fmt != PFNL_PIX_I010) return fail(PFNL_ERR_INVALID, "yuv10: fmt must be PFNL_PIX_P010 or PFNL_PIX_I010");
     pfnl::YuvCoef c;
-    if (!pfnl::yuv10_coefficients(matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (!pfnl::yuv_coefficients(10, matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (n < 1 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "yuv10: n >= 1, H and W positive and even (4:2:0)");
     if ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(yuv)) % 2) return fail(PFNL_ERR_INVALID, "yuv10: uint16 samples are 2-byte aligned");
-    HIPCHK(pfnl::launch_rgb_to_yuv420_u10(rgb, yuv, fmt == PFNL_PIX_P010, c, n, H, W, (hipStream_t)stream));
+    HIPCHK(pfnl::launch_rgb_to_yuv420(rgb, yuv, fmt == PFNL_PIX_P010, c, n, H, W, (hipStream_t)stream));
     return 0;
 }
 
 int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream) {
     if (!in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (n < 1) return fail(PFNL_ERR_INVALID, "resize: n >= 1");
-    pfnl::ResizePlan plan;
+    pfnl::PlacePlan plan;                             // the whole raster on the whole canvas
     std::string why;
-    if (!pfnl::resize_plan(H, W, oH, oW, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
+    if (!pfnl::place_plan(H, W, oH, oW, nullptr, nullptr, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
     if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) % 2) return fail(PFNL_ERR_INVALID, "resize: uint16 samples are 2-byte aligned");
+    const uint16_t black[3] = {0, 0, 0};
     OpStage st(stream);
-    const int32_t* blob = st.upload(plan.blob);
-    st.run([&] { return pfnl::launch_resize_u10(in, out, plan, blob, n, st.s); });
+    const int32_t* blob = st.upload(plan.r.blob);
+    st.run([&] { return pfnl::launch_resize_place(in, out, plan, blob, black, n, st.s); });
     return st.finish("resize10 op: ");
 }
 
@@ -1050,12 +1051,12 @@ int pfnl_resize_taps(int n_in, int n_out, int32_t* first, int32_t* count, int16_
 int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, uint8_t* out, void* stream) {
     if (!in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (n < 1) return fail(PFNL_ERR_INVALID, "resize: n >= 1");
-    pfnl::ResizePlan plan;
+    pfnl::PlacePlan plan;                             // the whole raster on the whole canvas
     std::string why;
-    if (!pfnl::resize_plan(H, W, oH, oW, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
+    if (!pfnl::place_plan(H, W, oH, oW, nullptr, nullptr, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
     OpStage st(stream);
-    const int32_t* blob = st.upload(plan.blob);
-    st.run([&] { return pfnl::launch_resize_u8(in, out, plan, blob, n, st.s); });
+    const int32_t* blob = st.upload(plan.r.blob);
+    st.run([&] { return pfnl::launch_resize_place(in, out, plan, blob, plan.fill, n, st.s); });
     return st.finish("resize op: ");
 }
 
@@ -1076,7 +1077,7 @@ int pfnl_op_resize_place_u8(const uint8_t* in, int n, int H, int W, int oH, int 
     const uint8_t black[3] = {0, 0, 0};
     OpStage st(stream);
     const int32_t* blob = st.upload(plan.r.blob);
-    st.run([&] { return pfnl::launch_resize_place_u8(in, out, plan, blob, fill ? fill : black, n, st.s); });
+    st.run([&] { return pfnl::launch_resize_place(in, out, plan, blob, fill ? fill : black, n, st.s); });
     return st.finish("place op: ");
 }
 
@@ -1089,7 +1090,7 @@ int pfnl_op_resize_place_u10(const uint16_t* in, int n, int H, int W, int oH, in
     const uint16_t black[3] = {0, 0, 0};
     OpStage st(stream);
     const int32_t* blob = st.upload(plan.r.blob);
-    st.run([&] { return pfnl::launch_resize_place_u10(in, out, plan, blob, fill ? fill : black, n, st.s); });
+    st.run([&] { return pfnl::launch_resize_place(in, out, plan, blob, fill ? fill : black, n, st.s); });
     return st.finish("place10 op: ");
 }
 

@@ -84,6 +84,25 @@ int get_option(pfnl_stream* s, const char* key, std::string* v) {
     return 0;
 }
 
+// The route on samples of T (uint8_t, or uint16_t for the 10-bit formats), each stage out of the slot of the one before it; a replay takes
+// the same route, so pop stays a copy.  The launchers are overloaded on the sample type: one kernel body per stage (sample_depth.h).
+template <typename T>
+int run_route(pfnl_stream* s, const Batch& b) {
+    constexpr bool ten = sizeof(T) == 2;
+    const pfnl::OutRoute& r = s->route;
+    const auto slot = [&](int k) { return reinterpret_cast<T*>(s->slot[k].buf[b.slot]); };
+    HIPCHK(pfnl::launch_quantise(s->sr, slot(0), (size_t)b.count * s->sr_bytes, s->s));
+    if (r.runs[1]) {                                  // one launch writes the whole canvas, the fill colour included (a plain size has none)
+        const auto sample = [](uint8_t v) { return (T)(ten ? pfnl::fill_u10(v) : v); };
+        const T fill[3] = {sample(s->rplan.fill[0]), sample(s->rplan.fill[1]), sample(s->rplan.fill[2])};
+        HIPCHK(pfnl::launch_resize_place(slot(0), slot(1), s->rplan, s->rtab, fill, b.count, s->s));
+    }
+    if (r.runs[2])                                    // reads the resampled frames where stage 1 runs
+        HIPCHK(pfnl::launch_rgb_to_yuv420(slot(r.runs[1] ? 1 : 0), slot(2), s->out_fmt == PFNL_PIX_NV12 || s->out_fmt == PFNL_PIX_P010,
+                                          ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w, s->s));
+    return 0;
+}
+
 // gather -> forward -> quantise (-> resize -> 4:2:0) into the batch's slots, then its event; asynchronous on the session's stream
 int enqueue(pfnl_stream* s, const Batch& b) {
     if (s->scene_mode) {
@@ -95,27 +114,7 @@ int enqueue(pfnl_stream* s, const Batch& b) {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
     if (int e = pfnl_forward_ensemble(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->ensemble, s->s)) return e;   // (1: pfnl_forward itself)
-    // the route, each stage out of the slot of the one before it (a replay takes the same route: pop stays a copy); 10 bits: the same
-    // launches on uint16 samples (depth10.hip) - the twins stay apart, tools/GFX950_NOTES.md
-    const pfnl::OutRoute& r = s->route;
-    const bool ten = r.sample_bytes == 2;
-    const auto u16 = [](uint8_t* p) { return reinterpret_cast<uint16_t*>(p); };
-    uint8_t *const q = s->slot[0].buf[b.slot], *const rs = s->slot[1].buf[b.slot], *const y = s->slot[2].buf[b.slot];
-    uint8_t* const rgb = r.runs[1] ? rs : q;          // what the 4:2:0 conversion reads
-    HIPCHK(ten ? pfnl::launch_quantise_u10(s->sr, u16(q), (size_t)b.count * s->sr_bytes, s->s)
-               : pfnl::launch_quantise_u8(s->sr, q, (size_t)b.count * s->sr_bytes, s->s));
-    if (r.runs[1] && s->rplan.whole) {                // the plain resize launches, as ever
-        HIPCHK(ten ? pfnl::launch_resize_u10(u16(q), u16(rs), s->rplan.r, s->rtab, b.count, s->s)
-                   : pfnl::launch_resize_u8(q, rs, s->rplan.r, s->rtab, b.count, s->s));
-    } else if (r.runs[1]) {                           // a placement: one launch writes the whole canvas, the fill colour included
-        const uint8_t* const f = s->rplan.fill;
-        const uint16_t f10[3] = {pfnl::fill_u10(f[0]), pfnl::fill_u10(f[1]), pfnl::fill_u10(f[2])};
-        HIPCHK(ten ? pfnl::launch_resize_place_u10(u16(q), u16(rs), s->rplan, s->rtab, f10, b.count, s->s)
-                   : pfnl::launch_resize_place_u8(q, rs, s->rplan, s->rtab, f, b.count, s->s));
-    }
-    if (r.runs[2])
-        HIPCHK(ten ? pfnl::launch_rgb_to_yuv420_u10(u16(rgb), u16(y), s->out_fmt == PFNL_PIX_P010, s->coef10, b.count, r.out_h, r.out_w, s->s)
-                   : pfnl::launch_rgb_to_yuv420_u8(rgb, y, s->out_fmt == PFNL_PIX_NV12, s->coef, b.count, r.out_h, r.out_w, s->s));
+    if (int e = s->route.sample_bytes == 2 ? run_route<uint16_t>(s, b) : run_route<uint8_t>(s, b)) return e;
     HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
     return 0;
 }
@@ -588,7 +587,7 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (const char* why = pfnl::route_refused(in_fmt, out_fmt, s->route.out_h, s->route.out_w)) return fail(PFNL_ERR_INVALID, why);
     pfnl::YuvCoef coef, coef10;
-    if (!pfnl::yuv_coefficients(matrix, full_range, &coef) || !pfnl::yuv10_coefficients(matrix, full_range, &coef10))
+    if (!pfnl::yuv_coefficients(8, matrix, full_range, &coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, "format staging allocation failed");

@@ -156,8 +156,9 @@ hipError_t launch_bicubic(const float* x, float* out, int B, int H, int W, int s
 hipError_t run_mfma_selftest(int* mismatches);
 hipError_t launch_gather_windows(const float* frames, float* win, int F, int first, int count, int T, size_t frame_floats,
                                  hipStream_t s);
-hipError_t launch_quantise_u8(const float* sr, uint8_t* out, size_t n, hipStream_t s);
-hipError_t launch_quantise_u10(const float* sr, uint16_t* out, size_t n, hipStream_t s);   // 0 .. 1023 (depth10.hip); sr 16-byte, out 8-byte aligned
+// the output edge's stage 0, one kernel over the sample type (sample_depth.h): fp32 -> uint8 0 .. 255 | uint16 0 .. 1023; n % 4 == 0
+hipError_t launch_quantise(const float* sr, uint8_t* out, size_t n, hipStream_t s);
+hipError_t launch_quantise(const float* sr, uint16_t* out, size_t n, hipStream_t s);   // sr 16-byte, out 8-byte aligned
 // ring [cap][frame_bytes] uint8 (frame f in slot f % cap) -> win [count][T][frame_bytes] fp32 = u8 / 255. as the harness computes it,
 // window w slot t = frame clamp(first + w + t - T/2, 0, last); frame_bytes % 4 == 0 (stream.hip)
 hipError_t launch_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T,
@@ -179,14 +180,16 @@ hipError_t launch_scene_first_frame(unsigned long long* sad, long long* scene_fi
 hipError_t launch_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene_first, float* win, int cap, long long last,
                                            long long first, int count, int T, size_t frame_bytes, hipStream_t s);
 
-// ---- YUV 4:2:0 <-> RGB, 8 bits (yuv.hip; the rule: pfnl_amd/yuv.py) ----
+// ---- YUV 4:2:0 <-> RGB (yuv.hip; the rule: pfnl_amd/yuv.py, 10 bits: pfnl_amd/depth10.py) ----
 // The fifteen integers of yuv.py coefficients(), 14 fractional bits: the one table, computed on the host and passed to the kernels by value.
 struct YuvCoef {
     int y0;
     int yr, yg, yb, cbr, cbg, cbb, crr, crg, crb;   // RGB -> YUV
     int dy, drv, dgu, dgv, dbu;                     // YUV -> RGB
 };
-bool yuv_coefficients(int matrix, int full_range, YuvCoef* c);   // matrix 0 BT.601 | 1 BT.709; false: unknown matrix or range (no device needed)
+// bits 8: samples 0 .. 255, limited range 16 .. 235 / 16 .. 240; bits 10: samples 0 .. 1023, 64 .. 940 / 64 .. 960, y0 and the encode
+// side alone (the decode side stays zero); matrix 0 BT.601 | 1 BT.709; false: unknown depth, matrix or range (no device needed)
+bool yuv_coefficients(int bits, int matrix, int full_range, YuvCoef* c);
 // yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow)
 hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
 // The decode's source as planes: H rows of W bytes at y; NV12: H/2 rows of W bytes (Cb, Cr interleaved) at cb, cr unused; I420: H/2 rows of
@@ -197,13 +200,12 @@ struct YuvPlanes {
 };
 // the same kernel on planes (the packed launcher calls this with pitch W, W/2): words where W, every plane, every pitch and rgb allow
 hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
-hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
-// 10 bits, uint16 samples (depth10.hip; the rule: pfnl_amd/depth10.py): y0 and the encode side of the table for 64 .. 940 / 64 .. 960 or
-// full range (the decode side stays zero); rgb [n][H][W][3] with values 0 .. 1023 -> P010 (samples << 6) or I010; H, W even; any alignment
-bool yuv10_coefficients(int matrix, int full_range, YuvCoef* c);
-hipError_t launch_rgb_to_yuv420_u10(const uint16_t* rgb, uint16_t* yuv, bool p010, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+// the encode, one kernel over the sample type: uint8 -> NV12 (semiplanar) or I420 with the 8-bit table; uint16 with values 0 .. 1023 ->
+// P010 (semiplanar, samples << 6) or I010 with the 10-bit table; H, W even; any alignment a sample can have
+hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+hipError_t launch_rgb_to_yuv420(const uint16_t* rgb, uint16_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, hipStream_t s);
 
-// ---- uint8 RGB frames at a chosen raster (resize.hip; the rule: pfnl_amd/resize.py) ----
+// ---- RGB frames at a chosen raster: the tap tables (resize.hip; the rule: pfnl_amd/resize.py) ----
 constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in
 constexpr int RESIZE_TW = 64;            // output pixels of one workgroup: across,
 constexpr int RESIZE_TH = 16;            // and down
@@ -220,17 +222,12 @@ struct ResizePlan {
     std::vector<int32_t> blob;
 };
 bool resize_plan(int H, int W, int oH, int oW, ResizePlan* p, std::string* why);
-// in [n][H][W][3] -> out [n][oH][oW][3], both passes in one launch; blob_dev: p.blob on the device; any alignment (16-byte stores where
-// oW is a multiple of 16 and out is aligned, single bytes otherwise)
-hipError_t launch_resize_u8(const uint8_t* in, uint8_t* out, const ResizePlan& p, const int32_t* blob_dev, int n, hipStream_t s);
-// the same plan and blob on uint16 samples 0 .. 1023 (depth10.hip): 16-byte stores where oW is a multiple of 8 and out is aligned
-hipError_t launch_resize_u10(const uint16_t* in, uint16_t* out, const ResizePlan& p, const int32_t* blob_dev, int n, hipStream_t s);
 
 // ---- a rectangle of the frame on a canvas (place.hip; the rule: pfnl_amd/fit.py place, pfnl_amd/depth10.py place10) ----
 // What a session's stage 1 runs (pfnl_stream_resize, pfnl_stream_place): the rectangle src of the raster sH x sW resampled into the rectangle
 // dst of the canvas cH x cW, the fill colour elsewhere.  `r` is resize_plan(src.h, src.w, dst.h, dst.w) as it always was - tables, blob and
-// the rows of the largest tile, the placed kernel's tiling being anchored at dst -; cH = 0: off; `whole`: src is the raster and dst the
-// canvas, and the launch is launch_resize_u8 / _u10 on `r`.
+// the rows of the largest tile, the kernel's tiling being anchored at dst -; cH = 0: off; `whole`: src is the raster and dst the canvas, a
+// plain resize, and the launch is the kernel's instantiation without rectangles.
 struct PlacePlan {
     ResizePlan r;
     int sH = 0, sW = 0, cH = 0, cW = 0;
@@ -241,12 +238,13 @@ struct PlacePlan {
 constexpr uint16_t fill_u10(uint8_t v) { return (uint16_t)((v << 2) | (v >> 6)); }   // 0 -> 0, 255 -> 1023
 // src NULL: the whole raster; dst NULL: the whole canvas.  false + *why: place_refused (stream_route.h) or resize_plan says no (no device needed)
 bool place_plan(int sH, int sW, int cH, int cW, const pfnl_rect* src, const pfnl_rect* dst, PlacePlan* p, std::string* why);
-// in [n][sH][sW][3] -> out [n][cH][cW][3], one launch, every sample of out stored once; blob_dev: p.r.blob on the device; any alignment (16-byte
-// stores where cW is a multiple of 16 - of 8 for uint16 samples - and out is aligned, single samples otherwise); fill: sample values
-hipError_t launch_resize_place_u8(const uint8_t* in, uint8_t* out, const PlacePlan& p, const int32_t* blob_dev, const uint8_t fill[3], int n,
-                                  hipStream_t s);
-hipError_t launch_resize_place_u10(const uint16_t* in, uint16_t* out, const PlacePlan& p, const int32_t* blob_dev, const uint16_t fill[3], int n,
-                                   hipStream_t s);
+// in [n][sH][sW][3] -> out [n][cH][cW][3], both passes in one launch, every sample of out stored once; blob_dev: p.r.blob on the device; any
+// alignment a sample can have (16-byte stores where cW is a multiple of 16 - of 8 for uint16 samples - and out is aligned, single samples
+// otherwise); fill: sample values (uint16: 0 .. 1023), unused by a whole plan.  One kernel over the sample type (sample_depth.h).
+hipError_t launch_resize_place(const uint8_t* in, uint8_t* out, const PlacePlan& p, const int32_t* blob_dev, const uint8_t fill[3], int n,
+                               hipStream_t s);
+hipError_t launch_resize_place(const uint16_t* in, uint16_t* out, const PlacePlan& p, const int32_t* blob_dev, const uint16_t fill[3], int n,
+                               hipStream_t s);
 
 // ---- the flips and transposes of the self-ensemble (dihedral.hip; the rule: pfnl_amd/ensemble.py) ----
 // member k: bit 0 mirrors W, bit 1 mirrors H, bit 2 transposes H and W (applied last).  scale == 1 leaves the bits as they are.

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "conv_bf16.h"
+#include "sample_depth.h"
 
 namespace pfnl {
 
@@ -635,25 +636,39 @@ hipError_t launch_gather_windows(const float* frames, float* win, int F, int fir
     return hipGetLastError();
 }
 
-// uint8(np.round(np.clip(sr * 255, 0, 255))): rintf = round half to even, like np.round
-__global__ __launch_bounds__(256) void quantise_u8_kernel(const f32x4* __restrict__ sr, uint32_t* __restrict__ out, size_t n4) {
+// T(np.round(np.clip(sr * top, 0, top))), top = 255 or 1023: the float32 product; rintf = round half to even, like np.round; NaN -> 0
+// (fmaxf).  Four results are one 32-bit word of uint8 samples or two of uint16 (sample_depth.h store_samples).
+template <typename T>
+__global__ __launch_bounds__(256) void quantise_kernel(const f32x4* __restrict__ sr, T* __restrict__ out, size_t n4) {
+    constexpr float TOP = (float)(Depth<T>::LEVELS - 1);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         const f32x4 v = sr[i];
-        const uint32_t a = (uint32_t)rintf(fminf(fmaxf(v.x * 255.0f, 0.f), 255.f));
-        const uint32_t b = (uint32_t)rintf(fminf(fmaxf(v.y * 255.0f, 0.f), 255.f));
-        const uint32_t c = (uint32_t)rintf(fminf(fmaxf(v.z * 255.0f, 0.f), 255.f));
-        const uint32_t d = (uint32_t)rintf(fminf(fmaxf(v.w * 255.0f, 0.f), 255.f));
-        out[i] = a | (b << 8) | (c << 16) | (d << 24);
+        const auto level = [](float x) { return (int)(uint32_t)rintf(fminf(fmaxf(x * TOP, 0.f), TOP)); };
+        const int q[4] = {level(v.x), level(v.y), level(v.z), level(v.w)};
+        store_samples<T, 4, true>(out + 4 * i, q);
     }
 }
 
-hipError_t launch_quantise_u8(const float* sr, uint8_t* out, size_t n, hipStream_t s) {
-    if (n % 4) return hipErrorInvalidValue;
+namespace {
+
+template <typename T>
+hipError_t launch_quantise_as(const float* sr, T* out, size_t n, hipStream_t s) {
     const size_t n4 = n / 4;
     const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-    hipLaunchKernelGGL(quantise_u8_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, reinterpret_cast<const f32x4*>(sr),
-                       reinterpret_cast<uint32_t*>(out), n4);
+    hipLaunchKernelGGL(quantise_kernel<T>, dim3(blocks ? blocks : 1), dim3(256), 0, s, reinterpret_cast<const f32x4*>(sr), out, n4);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_quantise(const float* sr, uint8_t* out, size_t n, hipStream_t s) {
+    if (n % 4) return hipErrorInvalidValue;
+    return launch_quantise_as(sr, out, n, s);
+}
+
+hipError_t launch_quantise(const float* sr, uint16_t* out, size_t n, hipStream_t s) {
+    if (!sr || !out || !n || n % 4 || reinterpret_cast<uintptr_t>(sr) % 16 || reinterpret_cast<uintptr_t>(out) % 8) return hipErrorInvalidValue;
+    return launch_quantise_as(sr, out, n, s);
 }
 
 }  // namespace pfnl

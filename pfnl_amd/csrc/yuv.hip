@@ -1,22 +1,27 @@
-// YUV 4:2:0 (NV12, I420) <-> packed RGB, 8 bits: the two edges of the streaming session (include/pfnl_hip.h, pfnl_stream_format).  The
-// arithmetic is integer and stated once on the host, pfnl_amd/yuv.py: 14 fractional bits, coefficients rounded once, chroma sited left
-// (on the even luma columns, midway between two luma rows); the kernels give its bytes.
-// Both kernels move bytes - 1.5 per pixel on one side, 3 on the other.  A lane owns a strip of two luma rows by P pixels, so that the chroma
-// samples it reads (or forms) serve both rows; P = 16 reads and writes 16-byte words (8-byte ones for I420's half-width planes), P = 4
-// 4-byte words (2-byte ones), P = 2 single bytes: any even H, W and any pointer.  Edges are index clamps inside the one kernel.
+// YUV 4:2:0 <-> packed RGB: the two edges of the streaming session (include/pfnl_hip.h, pfnl_stream_format) - the decode of NV12 / I420
+// input, and the encode to NV12 / I420 or, with uint16 samples 0 .. 1023, to P010 / I010.  The arithmetic is integer and stated once on the
+// host, pfnl_amd/yuv.py (10 bits: pfnl_amd/depth10.py): 14 fractional bits, coefficients rounded once, chroma sited left (on the even luma
+// columns, midway between two luma rows); the kernels give its samples.
+// Both kernels move bytes - 1.5 samples per pixel on one side, 3 on the other.  A lane owns a strip of two luma rows by P pixels, so that the
+// chroma samples it reads (or forms) serve both rows.  8 bits: P = 16 reads and writes 16-byte words (8-byte ones for I420's half-width
+// planes), P = 4 4-byte words (2-byte ones), P = 2 single bytes; 10 bits: P = 8 reads three 16-byte words per row and writes one per luma
+// row and one of interleaved chroma (I010's half-width planes take 8 bytes each), P = 2 single samples.  So any even H, W and any pointer
+// a sample can sit at.  Edges are index clamps inside the one kernel.  The encode is one body over the sample type (sample_depth.h).
 // The decode reads its planes by pointer and row pitch, so a decoder's surface (include/pfnl_hip.h SURFACES) and a packed frame are one kernel.
 #include <cmath>
 
-#include "common.h"
+#include "sample_depth.h"
 
 namespace pfnl {
 
-bool yuv_coefficients(int matrix, int full_range, YuvCoef* c) {
-    if (!c || matrix < 0 || matrix > 1 || full_range < 0 || full_range > 1) return false;
+bool yuv_coefficients(int bits, int matrix, int full_range, YuvCoef* c) {
+    if (!c || (bits != 8 && bits != 10) || matrix < 0 || matrix > 1 || full_range < 0 || full_range > 1) return false;
     const double kr = matrix == 0 ? 0.299 : 0.2126, kb = matrix == 0 ? 0.114 : 0.0722, kg = 1.0 - kr - kb;
-    const double ys = full_range ? 1.0 : 219.0 / 255.0, cs = full_range ? 1.0 : 224.0 / 255.0;
+    const double top = (double)((1 << bits) - 1);                      // 219 / 255, 224 / 255 | 876 / 1023, 896 / 1023
+    const double ys = full_range ? 1.0 : (219 << (bits - 8)) / top, cs = full_range ? 1.0 : (224 << (bits - 8)) / top;
     const auto rnd = [](double x) { return (int)std::floor(x * 16384.0 + 0.5); };
-    c->y0 = full_range ? 0 : 16;
+    *c = YuvCoef{};
+    c->y0 = full_range ? 0 : 16 << (bits - 8);
     c->yr = rnd(ys * kr);
     c->yb = rnd(ys * kb);
     c->yg = rnd(ys) - c->yr - c->yb;
@@ -26,6 +31,7 @@ bool yuv_coefficients(int matrix, int full_range, YuvCoef* c) {
     c->crr = rnd(cs / 2.0);
     c->crb = rnd(-cs * kb / (2.0 * (1.0 - kr)));
     c->crg = -c->crr - c->crb;
+    if (bits != 8) return true;                                        // (no decode side: 10-bit input is not built)
     c->dy = rnd(1.0 / ys);
     c->drv = rnd(2.0 * (1.0 - kr) / cs);
     c->dbu = rnd(2.0 * (1.0 - kb) / cs);
@@ -33,89 +39,6 @@ bool yuv_coefficients(int matrix, int full_range, YuvCoef* c) {
     c->dgv = rnd(-2.0 * kr * (1.0 - kr) / (kg * cs));
     return true;
 }
-
-namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// the widest word that divides N bytes: the strips are laid out so that a run of N bytes is aligned to it in the forms that use words
-template <int N>
-constexpr int word_of() {
-    return N % 16 == 0 ? 16 : (N % 8 == 0 ? 8 : (N % 4 == 0 ? 4 : (N % 2 == 0 ? 2 : 1)));
-}
-
-// N bytes at p -> v[0 .. N), in words (WORDS) or byte by byte
-template <int N, bool WORDS>
-__device__ __forceinline__ void load_bytes(const uint8_t* __restrict__ p, int* v) {
-    constexpr int WB = WORDS ? word_of<N>() : 1;
-    if constexpr (WB == 1) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = p[k];
-    } else if constexpr (WB == 2) {
-#pragma unroll
-        for (int k = 0; k < N; k += 2) {
-            const unsigned w = *reinterpret_cast<const uint16_t*>(p + k);
-            v[k] = (int)(w & 255u), v[k + 1] = (int)(w >> 8);
-        }
-    } else {
-        unsigned w[N / 4];
-#pragma unroll
-        for (int k = 0; k < N; k += WB) {
-            if constexpr (WB == 16) {
-                const u32x4 q = *reinterpret_cast<const u32x4*>(p + k);
-                w[k / 4] = q.x, w[k / 4 + 1] = q.y, w[k / 4 + 2] = q.z, w[k / 4 + 3] = q.w;
-            } else if constexpr (WB == 8) {
-                const u32x2 q = *reinterpret_cast<const u32x2*>(p + k);
-                w[k / 4] = q.x, w[k / 4 + 1] = q.y;
-            } else {
-                w[k / 4] = *reinterpret_cast<const unsigned*>(p + k);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
-    }
-}
-
-// v[0 .. N), each in [0, 255] -> N bytes at p
-template <int N, bool WORDS>
-__device__ __forceinline__ void store_bytes(uint8_t* __restrict__ p, const int* v) {
-    constexpr int WB = WORDS ? word_of<N>() : 1;
-    if constexpr (WB == 1) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) p[k] = (uint8_t)v[k];
-    } else if constexpr (WB == 2) {
-#pragma unroll
-        for (int k = 0; k < N; k += 2) *reinterpret_cast<uint16_t*>(p + k) = (uint16_t)(v[k] | (v[k + 1] << 8));
-    } else {
-        unsigned w[N / 4];
-#pragma unroll
-        for (int k = 0; k < N / 4; ++k)
-            w[k] = (unsigned)v[4 * k] | ((unsigned)v[4 * k + 1] << 8) | ((unsigned)v[4 * k + 2] << 16) | ((unsigned)v[4 * k + 3] << 24);
-#pragma unroll
-        for (int k = 0; k < N; k += WB) {
-            if constexpr (WB == 16)
-                *reinterpret_cast<u32x4*>(p + k) = u32x4{w[k / 4], w[k / 4 + 1], w[k / 4 + 2], w[k / 4 + 3]};
-            else if constexpr (WB == 8)
-                *reinterpret_cast<u32x2*>(p + k) = u32x2{w[k / 4], w[k / 4 + 1]};
-            else
-                *reinterpret_cast<unsigned*>(p + k) = w[k / 4];
-        }
-    }
-}
-
-// clip(v >> S, 0, 255) with the clamp AHEAD of the shift (the same value: both are monotonic).  Written as shift-then-clamp, two results
-// that are packed into neighbouring bytes become one v_ashr_pk_u8_i32 (new on gfx950), which the compiler ORs with bytes 2 and 3 as if
-// the instruction left the upper half of its result zero.  With that code the 4-pixel NV12 decode delivered wrong bytes 2 of its packed
-// words on the device (values no input can produce) and right ones in a host build of the same source: tools/GFX950_NOTES.md.
-template <int S>
-__device__ __forceinline__ int shift_clip_u8(int v) {
-    v = v < 0 ? 0 : v;
-    v = v > (256 << S) - 1 ? (256 << S) - 1 : v;
-    return v >> S;
-}
-
-}  // namespace
 
 // planes of n frames -> rgb [n][H][W][3].  A frame is its planes by pointer and row pitch (common.h YuvPlanes): W, and W / 2 for I420's
 // chroma, in a tightly packed frame, whatever the decoder chose in a surface; frame f lies f * src.frame bytes behind the first.
@@ -144,16 +67,16 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
             if constexpr (NV12) {
                 const uint8_t* const p = fb + (size_t)jrow[a] * src.pitch_cb;
                 int pair[P], e[2];
-                load_bytes<P, WORDS>(p + x0, pair);
-                load_bytes<2, WORDS>(p + 2 * ie, e);
+                load_samples<uint8_t, P, WORDS>(p + x0, pair);
+                load_samples<uint8_t, 2, WORDS>(p + 2 * ie, e);
 #pragma unroll
                 for (int q = 0; q < HP; ++q) cb[a][q] = pair[2 * q], cr[a][q] = pair[2 * q + 1];
                 cb[a][HP] = e[0], cr[a][HP] = e[1];
             } else {
                 const uint8_t* const pb = fb + (size_t)jrow[a] * src.pitch_cb;
                 const uint8_t* const pr = src.cr + f * src.frame + (size_t)jrow[a] * src.pitch_cr;
-                load_bytes<HP, WORDS>(pb + i0, cb[a]);
-                load_bytes<HP, WORDS>(pr + i0, cr[a]);
+                load_samples<uint8_t, HP, WORDS>(pb + i0, cb[a]);
+                load_samples<uint8_t, HP, WORDS>(pr + i0, cr[a]);
                 cb[a][HP] = pb[ie], cr[a][HP] = pr[ie];
             }
         }
@@ -162,7 +85,7 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
             const int y = 2 * k - 1 + a;
             if (y < 0 || y >= H) continue;
             int luma[P], out[3 * P];
-            load_bytes<P, WORDS>(fy + (size_t)y * src.pitch_y + x0, luma);
+            load_samples<uint8_t, P, WORDS>(fy + (size_t)y * src.pitch_y + x0, luma);
 #pragma unroll
             for (int px = 0; px < P; ++px) {
                 const int q = px >> 1;
@@ -176,23 +99,23 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
                 }
                 u -= 128, v -= 128;
                 const int yy = c.dy * (luma[px] - c.y0) + (1 << 13);
-                out[3 * px] = shift_clip_u8<14>(yy + c.drv * v);
-                out[3 * px + 1] = shift_clip_u8<14>(yy + c.dgu * u + c.dgv * v);
-                out[3 * px + 2] = shift_clip_u8<14>(yy + c.dbu * u);
+                out[3 * px] = shift_clip<14, 256>(yy + c.drv * v);
+                out[3 * px + 1] = shift_clip<14, 256>(yy + c.dgu * u + c.dgv * v);
+                out[3 * px + 2] = shift_clip<14, 256>(yy + c.dbu * u);
             }
-            store_bytes<3 * P, WORDS>(rgb + ((f * H + y) * W + x0) * 3, out);
+            store_samples<uint8_t, 3 * P, WORDS>(rgb + ((f * H + y) * W + x0) * 3, out);
         }
     }
 }
 
-// rgb [n][H][W][3] -> yuv [n][H*W*3/2].  A lane takes the luma rows 2j, 2j + 1 by P pixels: 2 P luma bytes and P/2 samples of each chroma
-// plane - the unrounded numerators of both rows added per column, then 1-2-1 across columns 2i - 1, 2i, 2i + 1 (yuv.py downsample).  Only
-// the column left of the strip is not its own (2i + 1 <= W - 1 always); at x = 0 it clamps onto column 0.
-template <int P, bool NV12>
-__global__ __launch_bounds__(256) void rgb_to_yuv420_u8_kernel(const uint8_t* __restrict__ rgb, uint8_t* __restrict__ yuv, int n, int H,
-                                                               int W, YuvCoef c) {
+// rgb [n][H][W][3] -> yuv [n][H*W*3/2] samples of T: NV12 / P010 (SEMIPLANAR; P010's samples << 6) or I420 / I010.  A lane takes the luma
+// rows 2j, 2j + 1 by P pixels: 2 P luma samples and P/2 samples of each chroma plane - the unrounded numerators of both rows added per
+// column, then 1-2-1 across columns 2i - 1, 2i, 2i + 1 (yuv.py downsample, depth10.py downsample10).  Only the column left of the strip is
+// not its own (2i + 1 <= W - 1 always); at x = 0 it clamps onto column 0.
+template <typename T, int P, bool SEMIPLANAR>
+__global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const T* __restrict__ rgb, T* __restrict__ yuv, int n, int H, int W, YuvCoef c) {
     constexpr bool WORDS = P > 2;
-    constexpr int HP = P / 2;
+    constexpr int HP = P / 2, LEVELS = Depth<T>::LEVELS, SH = sizeof(T) == 2 && SEMIPLANAR ? 6 : 0;
     const int gw = W / P, hh = H >> 1, hw = W >> 1;
     const size_t plane = (size_t)H * W, total = (size_t)n * hh * gw;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
@@ -200,51 +123,55 @@ __global__ __launch_bounds__(256) void rgb_to_yuv420_u8_kernel(const uint8_t* __
         const size_t fj = t / gw;
         const int j = (int)(fj % hh);
         const size_t f = fj / hh;
-        uint8_t* const fr = yuv + f * (plane + plane / 2);
+        T* const fr = yuv + f * (plane + plane / 2);
         const int x0 = g * P, xl = x0 > 0 ? x0 - 1 : 0;
         int nb[P + 1], nr[P + 1];                                      // per column, both rows: [0] the column left of the strip
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             const int y = 2 * j + a;
-            const uint8_t* const row = rgb + (f * H + y) * (size_t)W * 3;
+            const T* const row = rgb + (f * H + y) * (size_t)W * 3;
             int px[3 * P + 3], luma[P];
             px[0] = row[3 * (size_t)xl], px[1] = row[3 * (size_t)xl + 1], px[2] = row[3 * (size_t)xl + 2];
-            load_bytes<3 * P, WORDS>(row + (size_t)x0 * 3, px + 3);
+            load_samples<T, 3 * P, WORDS>(row + (size_t)x0 * 3, px + 3);
 #pragma unroll
             for (int p = 0; p <= P; ++p) {
                 const int r = px[3 * p], gg = px[3 * p + 1], b = px[3 * p + 2];
                 const int vb = c.cbr * r + c.cbg * gg + c.cbb * b, vr = c.crr * r + c.crg * gg + c.crb * b;
                 nb[p] = a ? nb[p] + vb : vb;
                 nr[p] = a ? nr[p] + vr : vr;
-                if (p) luma[p - 1] = shift_clip_u8<14>(c.yr * r + c.yg * gg + c.yb * b + (c.y0 << 14) + (1 << 13));
+                if (p) luma[p - 1] = shift_clip<14, LEVELS>(c.yr * r + c.yg * gg + c.yb * b + (c.y0 << 14) + (1 << 13));
             }
-            store_bytes<P, WORDS>(fr + (size_t)y * W + x0, luma);
+            store_samples<T, P, WORDS, SH>(fr + (size_t)y * W + x0, luma);
         }
         int ob[HP], orr[HP];
 #pragma unroll
-        for (int q = 0; q < HP; ++q) {
-            ob[q] = shift_clip_u8<17>(nb[2 * q] + 2 * nb[2 * q + 1] + nb[2 * q + 2] + (1 << 16) + (128 << 17));   // 128 + (S' >> 17)
-            orr[q] = shift_clip_u8<17>(nr[2 * q] + 2 * nr[2 * q + 1] + nr[2 * q + 2] + (1 << 16) + (128 << 17));
+        for (int q = 0; q < HP; ++q) {                                 // the chroma offset + (S' >> 17)
+            ob[q] = shift_clip<17, LEVELS>(nb[2 * q] + 2 * nb[2 * q + 1] + nb[2 * q + 2] + (1 << 16) + (Depth<T>::CHROMA << 17));
+            orr[q] = shift_clip<17, LEVELS>(nr[2 * q] + 2 * nr[2 * q + 1] + nr[2 * q + 2] + (1 << 16) + (Depth<T>::CHROMA << 17));
         }
-        if constexpr (NV12) {
+        if constexpr (SEMIPLANAR) {
             int pair[P];
 #pragma unroll
             for (int q = 0; q < HP; ++q) pair[2 * q] = ob[q], pair[2 * q + 1] = orr[q];
-            store_bytes<P, WORDS>(fr + plane + (size_t)j * W + x0, pair);
+            store_samples<T, P, WORDS, SH>(fr + plane + (size_t)j * W + x0, pair);
         } else {
-            uint8_t* const pb = fr + plane + (size_t)j * hw + (x0 >> 1);
-            store_bytes<HP, WORDS>(pb, ob);
-            store_bytes<HP, WORDS>(pb + (size_t)hh * hw, orr);
+            T* const pb = fr + plane + (size_t)j * hw + (x0 >> 1);
+            store_samples<T, HP, WORDS, SH>(pb, ob);
+            store_samples<T, HP, WORDS, SH>(pb + (size_t)hh * hw, orr);
         }
     }
 }
 
 namespace {
 
-// the strip width both kernels run with: 16-byte words, 4-byte words, bytes
-int strip_width(const void* a, const void* b, int W) {
-    const uintptr_t align = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
-    return W % 16 == 0 && align % 16 == 0 ? 16 : (W % 4 == 0 && align % 4 == 0 ? 4 : 2);
+// The strip width the encode runs with.  8 bits: 16-byte words, 4-byte words, bytes.  10 bits: W % 8 == 0 puts every row of every plane,
+// every strip of 8 pixels in it and every frame on a 16-byte boundary (I010's chroma: 8); single samples otherwise.
+template <typename T>
+int strip_width(uintptr_t align, int W) {
+    if constexpr (sizeof(T) == 1)
+        return W % 16 == 0 && align % 16 == 0 ? 16 : (W % 4 == 0 && align % 4 == 0 ? 4 : 2);
+    else
+        return W % 8 == 0 && align % 16 == 0 ? 8 : 2;
 }
 
 int strip_blocks(size_t items) {
@@ -253,10 +180,6 @@ int strip_blocks(size_t items) {
 }
 
 bool yuv_geometry_ok(const void* a, const void* b, int n, int H, int W) { return a && b && n >= 1 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1); }
-
-}  // namespace
-
-namespace {
 
 // The strip width the decode runs with.  Every word is read or written at plane + row * pitch (+ f * frame) + a multiple of its size, so
 // the planes, their pitches, the frame stride and rgb (rows of 3 W bytes) all have to be multiples of it: 16 | 4 for the full-width planes
@@ -301,24 +224,46 @@ hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, 
     return launch_yuv420_planes_to_rgb_u8(src, rgb, nv12, c, n, H, W, s);
 }
 
-hipError_t launch_rgb_to_yuv420_u8(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
-    if (!yuv_geometry_ok(rgb, yuv, n, H, W)) return hipErrorInvalidValue;
-    const int P = strip_width(rgb, yuv, W);
+namespace {
+
+template <typename T>
+hipError_t launch_encode(const T* rgb, T* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+    const uintptr_t align = reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(yuv);
+    if (!yuv_geometry_ok(rgb, yuv, n, H, W) || align % sizeof(T)) return hipErrorInvalidValue;
+    const int P = strip_width<T>(align, W);
     const dim3 grid(strip_blocks((size_t)n * (H / 2) * (W / P))), block(256);
 #define PFNL_YUV_LAUNCH(P_)                                                                                        \
-    if (nv12)                                                                                                      \
-        hipLaunchKernelGGL((rgb_to_yuv420_u8_kernel<P_, true>), grid, block, 0, s, rgb, yuv, n, H, W, c);          \
+    if (semiplanar)                                                                                                \
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<T, P_, true>), grid, block, 0, s, rgb, yuv, n, H, W, c);          \
     else                                                                                                           \
-        hipLaunchKernelGGL((rgb_to_yuv420_u8_kernel<P_, false>), grid, block, 0, s, rgb, yuv, n, H, W, c)
-    if (P == 16) {
-        PFNL_YUV_LAUNCH(16);
-    } else if (P == 4) {
-        PFNL_YUV_LAUNCH(4);
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<T, P_, false>), grid, block, 0, s, rgb, yuv, n, H, W, c)
+    if constexpr (sizeof(T) == 1) {
+        if (P == 16) {
+            PFNL_YUV_LAUNCH(16);
+        } else if (P == 4) {
+            PFNL_YUV_LAUNCH(4);
+        } else {
+            PFNL_YUV_LAUNCH(2);
+        }
     } else {
-        PFNL_YUV_LAUNCH(2);
+        if (P == 8) {
+            PFNL_YUV_LAUNCH(8);
+        } else {
+            PFNL_YUV_LAUNCH(2);
+        }
     }
 #undef PFNL_YUV_LAUNCH
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+    return launch_encode<uint8_t>(rgb, yuv, nv12, c, n, H, W, s);
+}
+
+hipError_t launch_rgb_to_yuv420(const uint16_t* rgb, uint16_t* yuv, bool p010, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+    return launch_encode<uint16_t>(rgb, yuv, p010, c, n, H, W, s);
 }
 
 }  // namespace pfnl

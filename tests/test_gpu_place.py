@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from pfnl_amd import _capi, depth10, fit, ops, surface, synth, yuv  # noqa: E402
+from pfnl_amd import _capi, depth10, fit, ops, resize, surface, synth, yuv  # noqa: E402
 from pfnl_amd.engine import PFNLEngine  # noqa: E402
 from pfnl_amd.spec import PFNLGeometry  # noqa: E402
 
@@ -97,9 +97,10 @@ def test_place_equals_the_host_rule(case, depth):
 def test_whole_rectangles_are_the_resize(depth):
     frames = _frames(2, 64, 96, depth, seed=3)
     dev = _dev(frames)
-    op, plain = (ops.resize_place_u8, ops.resize_u8) if depth == 8 else (ops.resize_place_u10, ops.resize_u10)
+    op, plain, rule = (ops.resize_place_u8, ops.resize_u8, resize.resize) if depth == 8 else (ops.resize_place_u10, ops.resize_u10, depth10.resize10)
     for size in [(36, 54), (128, 192), (64, 96)]:
         want = _host(plain(dev, size))
+        assert np.array_equal(want, np.stack([rule(f, *size) for f in frames]))   # both hooks launch one kernel: the host rule is the reference
         assert np.array_equal(_host(op(dev, size)), want)
         assert np.array_equal(_host(op(dev, size, (0, 0, 64, 96), (0, 0, *size), (1, 2, 3))), want)
 
