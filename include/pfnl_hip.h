@@ -229,9 +229,46 @@ int pfnl_forward_strip(pfnl_handle* h, const void* in, void* out, int B, int H, 
  * reversal); weighting the members. */
 int pfnl_forward_ensemble(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device,
                           int B, int H, int W, int n, void* stream);
+/* TILES (additions to version 4; with no tiling, the default everywhere, every path issues the calls it always issued).  The tile-size
+ * switch of a super-resolution tool: a large frame runs as a batch of overlapping tiles of one shape.  The trunk is linear in the frame
+ * and the non-local block quadratic (4 N^2 84 FLOPs per clip, N = (H/2)(W/2)); on tiles the block runs at patch scale, nearer its
+ * training scale (in_size 32) than a 4K frame is.  The reference has no such switch; like the self-ensemble the loop sits around
+ * pfnl_forward.  The rule is stated once on the host, pfnl_amd/tiles.py, and once in C++, pfnl_amd/csrc/tile_geom.h.  Per axis of
+ * length n (even), tile extent t and margin p = pad:
+ *     t == 0 or t >= n: one tile [0, n) that owns all of it.  Otherwise t is even, p >= 0, 2p < t, and
+ *     step = t - 2p;  count = ceil((n - 2p) / step);  origin o_i = min(i step, n - t)   (the last tile moves inward)
+ *     tile i owns [a_i, b_i):  a_0 = 0,  a_i = o_i + p,  b_i = a_(i+1),  b_last = n
+ * so every tile has extent t and an even origin, the owned ranges partition [0, n), and every owned sample lies at least p from each
+ * tile edge that is not a frame edge.  One pad serves both axes.  The tiles of a call are numbered (b ny + iy) nx + ix and run in runs
+ * of `batch` consecutive tiles (the last run may be shorter; 0: all in one run), each run one forward at [run,T,th,tw,3]; the output is
+ * the owned rectangle of each tile's result, scaled by `scale`, at its place - every output element is written exactly once, nothing is
+ * blended.  With pad >= 4 + 2 num_block (the halo pfnl_forward_strip recomputes) the result differs from the full-frame forward only
+ * through the non-local block seeing its own tile.
+ *   pfnl_tile_axis: the axis rule; needs no device.  *count receives the number of tiles; the arrays, each NULL or of *count entries
+ *     (call once with NULL arrays for the count), the origins and the owned ranges.  A bad n, tile or pad is PFNL_ERR_INVALID.
+ *   pfnl_forward_tiled: arguments, checks, stream rule and host-pointer staging of pfnl_forward_ensemble, plus the tiling's own check
+ *     (odd or negative extents, 2 pad >= tile where the axis is split, negative pad or batch, a tile count beyond int), all before any
+ *     device call.  t == NULL, or one tile per clip in one run, IS pfnl_forward_ensemble(..., ensemble_n, ...): the same launches.  Else
+ *     each run is gather -> the forward (the ensemble for ensemble_n > 1) -> scatter on the caller's stream (pfnl_amd/csrc/tiles.hip: two
+ *     bandwidth-bound kernels).  Two grow-only handle buffers - the run's tile stack and the run's result - and the workspace of both run
+ *     sizes (the full run and the short last one; for ensemble_n == 8 of the transposed tile as well) are sized before the first run is
+ *     enqueued: nothing moves while runs are in flight.
+ *   Range: every run's tail kernel writes the call's flag.  A host-pointer call reads it once, behind the last run, and redoes the WHOLE
+ *     tiled call on the f32-MFMA kernels (one count in pfnl_range_reruns; PFNL_ERR_RANGE under precision=bf16); device-pointer calls stay
+ *     asynchronous and leave the flag to pfnl_sync / pfnl_range_flag.
+ *   The option "graph" does not apply: runs always execute eagerly.  The kernels of tiles.hip run under no profile class.
+ *   pfnl_stream_tile (below): a session's batches go through this call.
+ * Out of scope: blending in the overlap; per-axis pads; tiles for pfnl_forward_strip and the multi-GPU paths; gathering tiles straight
+ * from the session's uint8 ring. */
+typedef struct pfnl_tiling { int32_t tile_h, tile_w, pad, batch; } pfnl_tiling;
+int pfnl_tile_axis(int n, int tile, int pad, int* count, int32_t* origin, int32_t* own_first, int32_t* own_count);
+int pfnl_forward_tiled(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device, int B, int H, int W,
+                       const pfnl_tiling* t, int ensemble_n, void* stream);
 /* Every buffer a pfnl_forward with these arguments can touch.  pfnl_forward_ensemble with n > 1 adds two grow-only buffers that are not
  * counted here: the transformed input, B*T*H*W*3 floats, and one member's output, B*sH*sW*3 floats; with n = 8 also whatever the plan of
- * (B, W, H) needs beyond that of (B, H, W) (pfnl_workspace_bytes(h, B, W, H) states it). */
+ * (B, W, H) needs beyond that of (B, H, W) (pfnl_workspace_bytes(h, B, W, H) states it).  pfnl_forward_tiled touches what a forward of
+ * its full run touches, pfnl_workspace_bytes(h, run, th, tw), plus two grow-only buffers of its own: the run's tile stack,
+ * run*T*th*tw*3 floats, and the run's result, run*s*th*s*tw*3 floats. */
 int pfnl_workspace_bytes(pfnl_handle* h, int B, int H, int W, size_t* bytes);
 /* THE LAUNCH PLAN of the progressive-fusion trunk (reference model/pfnl.py:65-71) for a [B,T,H,W,3] forward under the handle's current
  * options, as text: "<structure> launches_per_block=<n> c1x1=<launches of class conv1x1 among them> precision=<..> conv3x3=<..> conv1x1=<..>
@@ -417,6 +454,12 @@ int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_devi
  * off; any other n is PFNL_ERR_INVALID.  Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); the
  * setting survives pfnl_stream_reset. */
 int pfnl_stream_ensemble(pfnl_stream* s, int n);
+/* TILES in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With a tiling
+ * set the one forward of every batch is pfnl_forward_tiled(..., t, the session's ensemble, ...) (TILES above); gather, quantisation, the
+ * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  t == NULL
+ * is off; a tiling that does not fit the session's H x W is PFNL_ERR_INVALID.  Accepted only while no frame of the current sequence has
+ * been pushed (else PFNL_ERR_STATE); the setting survives pfnl_stream_reset. */
+int pfnl_stream_tile(pfnl_stream* s, const pfnl_tiling* t);
 
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
@@ -757,6 +800,16 @@ int pfnl_op_blur_decimate(const float* hr, float* lr, int F, int H, int W, int s
  * 16-byte aligned; any alignment of whole floats otherwise. */
 int pfnl_op_dihedral(const float* in, float* out, int n_img, int H, int W, int k, float scale, void* stream);
 int pfnl_op_dihedral_accum(float* acc, const float* y, int n_img, int H, int W, int k, float scale, void* stream);
+/* The two launches of a tiled forward's run (TILES above; pfnl_amd/csrc/tiles.hip; the rule: pfnl_amd/tiles.py), device pointers,
+ * asynchronous on `stream`; NULL, a shape or tiling pfnl_forward_tiled would refuse, and tiles first .. first+count-1 that are not
+ * tiles of the call are PFNL_ERR_INVALID before any HIP call.
+ *   pfnl_op_tile_gather: in [B,T,H,W,3] -> tiles [count,T,th,tw,3], tiles first .. first+count-1 of the call.
+ *   pfnl_op_tile_scatter: y [count,scale th,scale tw,3], the results of those tiles -> their owned rectangles inside out [B,scale H,
+ *     scale W,3]; every element of them is stored once by one thread, nothing else in `out` is touched.  No atomics, no memset.
+ * Both copy bits.  Rows are contiguous runs of floats and, origins and widths being even, 8-byte aligned relative to their base: 16-byte
+ * accesses where the origins, the row lengths and both base pointers allow, else 8-byte, else 4-byte - chosen from the addresses. */
+int pfnl_op_tile_gather(const float* in, float* tiles, int B, int T, int H, int W, const pfnl_tiling* t, int first, int count, void* stream);
+int pfnl_op_tile_scatter(const float* y, float* out, int B, int H, int W, int scale, const pfnl_tiling* t, int first, int count, void* stream);
 /* MFMA operand/accumulator layout self-test (asymmetric operands); returns 0 if the f32
  * 32x32x2 fragment maps this library assumes hold on the device. */
 int pfnl_selftest_mfma(int device_id);

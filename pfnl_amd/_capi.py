@@ -41,8 +41,14 @@ class pfnl_rect(C.Structure):
     _fields_ = [("y", C.c_int32), ("x", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
 
+class pfnl_tiling(C.Structure):
+    """Tile extents, the margin and the tiles per run of a tiled forward (include/pfnl_hip.h TILES; pfnl_amd/tiles.py)."""
+    _fields_ = [("tile_h", C.c_int32), ("tile_w", C.c_int32), ("pad", C.c_int32), ("batch", C.c_int32)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/pfnl_hip.h declares
 _vp, _i, _fp = C.c_void_p, C.c_int, C.POINTER(C.c_float)
+_i32p, _tp = C.POINTER(C.c_int32), C.POINTER(pfnl_tiling)
 SIGNATURES = {
     "pfnl_last_error": (C.c_char_p, []),
     "pfnl_version": (_i, []),
@@ -58,6 +64,11 @@ SIGNATURES = {
     "pfnl_stream_ensemble": (_i, [_vp, _i]),
     "pfnl_op_dihedral": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, _vp]),
     "pfnl_op_dihedral_accum": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, _vp]),
+    "pfnl_tile_axis": (_i, [_i, _i, _i, C.POINTER(_i), _i32p, _i32p, _i32p]),
+    "pfnl_forward_tiled": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _tp, _i, _vp]),
+    "pfnl_op_tile_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _tp, _i, _i, _vp]),
+    "pfnl_op_tile_scatter": (_i, [_vp, _vp, _i, _i, _i, _i, _tp, _i, _i, _vp]),
+    "pfnl_stream_tile": (_i, [_vp, _tp]),
     "pfnl_forward_strip": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "pfnl_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "pfnl_plan": (_i, [_vp, _i, _i, _i, C.c_char_p, C.c_size_t]),

@@ -23,6 +23,7 @@
 #include "conv_split16.h"
 #include "conv_small.h"
 #include "launch_plan.h"
+#include "tile_geom.h"
 
 namespace {
 
@@ -235,6 +236,7 @@ struct pfnl_handle {
     DevBuf nl16;                                              // bf16 non-local: split K / V^T operands
     DevBuf X, Xo, nlp, inp0, inp1, base, pb, merge, stage_in, stage_out, scratch;
     DevBuf ens_in, ens_y;                                     // pfnl_forward_ensemble: g_k(in) [B][T][H][W][3] and one member's output [B][sH][sW][3]
+    DevBuf tile_in, tile_y;                                   // pfnl_forward_tiled: a run's tile stack [run][T][th][tw][3] and its result [run][s th][s tw][3]
     int lastB = 0, lastH = 0, lastW = 0;
 
     // profiling: boundary events.  One event after every kernel launch (plus one at the start of a
@@ -937,7 +939,7 @@ int pfnl_destroy(pfnl_handle* h) {
     h->pin_out.release();
     if (h->rflag_host) hipHostFree(h->rflag_host);
     for (DevBuf* b : {&h->p10, &h->Xs, &h->Q, &h->wdev16s, &h->wdev, &h->wdev16, &h->nl16, &h->X, &h->Xo, &h->nlp, &h->inp0, &h->inp0sf, &h->c10part, &h->inp1, &h->base, &h->pb, &h->merge,
-                      &h->stage_in, &h->stage_out, &h->scratch, &h->ens_in, &h->ens_y})
+                      &h->stage_in, &h->stage_out, &h->scratch, &h->ens_in, &h->ens_y, &h->tile_in, &h->tile_y})
         b->release();
     delete h;
     return 0;
@@ -1571,6 +1573,114 @@ int pfnl_forward_ensemble(pfnl_handle* h, const void* in, int in_is_device, void
         if (flagged && can_rerun) {
             h->strict_once = true;
             const int e = ensemble_device(h, din, dout, B, H, W, n, s, 0);
+            h->strict_once = false;
+            if (e) return e;
+            ++h->range_reruns;
+            if (!out_is_device) {
+                if (int e2 = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e2;
+            } else {
+                HIPCHK(hipStreamSynchronize(s));
+            }
+        } else if (flagged && h->opt.bf16) {
+            return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
+        }
+    }
+    return 0;
+}
+
+// ---- tiles (include/pfnl_hip.h TILES; the rule: pfnl_amd/tiles.py; the geometry: tile_geom.h): the loop of runs around the forward
+
+int pfnl_tile_axis(int n, int tile, int pad, int* count, int32_t* origin, int32_t* own_first, int32_t* own_count) {
+    if (!count) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (const char* why = pfnl::tile_axis_refused(n, tile, pad)) return fail(PFNL_ERR_INVALID, why);
+    const pfnl::TileAxis a = pfnl::tile_axis(n, tile, pad);
+    *count = a.count;
+    for (int i = 0; i < a.count; ++i) {
+        if (origin) origin[i] = pfnl::tile_origin(a, i);
+        if (own_first) own_first[i] = pfnl::tile_own_first(a, i);
+        if (own_count) own_count[i] = pfnl::tile_own_end(a, i) - pfnl::tile_own_first(a, i);
+    }
+    return 0;
+}
+
+// Everything the runs of one tiled call touch, sized before the first of them is enqueued: the two tile buffers at the full run, and for
+// both run sizes - the full run and the short last one, whose plans may differ - what the forward of a run needs (ensure_workspace only
+// grows; an ensemble adds its own buffers and, for n == 8, the workspace of the transposed tile)
+static int tiled_presize(pfnl_handle* h, const pfnl::TileGrid& g, int total, int run, int n) {
+    const int T = h->cfg.num_frames, sc = h->cfg.scale, th = g.y.extent, tw = g.x.extent;
+    if (h->tile_in.ensure((size_t)run * T * th * tw * 3) || h->tile_y.ensure((size_t)run * th * tw * sc * sc * 3))
+        return fail(PFNL_ERR_NOMEM, "tile buffer allocation failed");
+    for (const int r : {run, total % run}) {
+        if (!r) continue;
+        if (int e = n > 1 ? ensemble_presize(h, r, th, tw, n) : ensure_workspace(h, trunk_plan(h, r, th, tw, th), r, th, tw, (th / 2) * (tw / 2)))
+            return e;
+    }
+    return 0;
+}
+
+// all runs on `s`: din [B][T][H][W][3] -> dout [B][sH][sW][3] (device pointers); under the handle's current strict_once
+static int tiled_device(pfnl_handle* h, const float* din, float* dout, const pfnl::TileGrid& g, int total, int run, int n, hipStream_t s,
+                        int slot) {
+    const int T = h->cfg.num_frames, sc = h->cfg.scale, th = g.y.extent, tw = g.x.extent;
+    if (int e = tiled_presize(h, g, total, run, n)) return e;
+    for (int first = 0; first < total; first += run) {
+        const int count = total - first < run ? total - first : run;
+        HIPCHK(launch_tile_gather(din, h->tile_in.p, g, T, first, count, s));
+        if (int e = n > 1 ? ensemble_device(h, h->tile_in.p, h->tile_y.p, count, th, tw, n, s, slot)
+                          : forward_device(h, h->tile_in.p, h->tile_y.p, count, th, tw, s, nullptr, 0, -1, slot))
+            return e;
+        HIPCHK(launch_tile_scatter(h->tile_y.p, dout, g, sc, first, count, s));
+    }
+    return 0;
+}
+
+int pfnl_forward_tiled(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device, int B, int H, int W,
+                       const pfnl_tiling* t, int n, void* stream) {
+    if (n != 1 && n != 2 && n != 4 && n != 8) return fail(PFNL_ERR_INVALID, "ensemble: n must be 1, 2, 4 or 8");
+    if (!t) return pfnl_forward_ensemble(h, in, in_is_device, out, out_is_device, B, H, W, n, stream);
+    if (!h || !in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(PFNL_ERR_INVALID, "B, H, W must be positive");
+    if ((H & 1) || (W & 1))
+        return fail(PFNL_ERR_INVALID, "H and W must be even (space_to_depth(2), reference model/pfnl.py:57)");
+    if (const char* why = pfnl::tiling_refused(H, W, *t)) return fail(PFNL_ERR_INVALID, why);
+    const pfnl::TileGrid g = pfnl::tile_grid(H, W, *t);
+    const int total = pfnl::tile_total(g, B);
+    if (!total) return fail(PFNL_ERR_INVALID, "tile: the tile count overflows a 32-bit integer");
+    const int run = pfnl::tile_run(total, t->batch);
+    if (g.y.count == 1 && g.x.count == 1 && run == total)       // one tile per clip, one run: the forward itself
+        return pfnl_forward_ensemble(h, in, in_is_device, out, out_is_device, B, H, W, n, stream);
+    if (!h->finalized) return fail(PFNL_ERR_STATE, "pfnl_finalize_weights has not been called");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    const int T = h->cfg.num_frames, sc = h->cfg.scale;
+    const size_t n_in = (size_t)B * T * H * W * 3, n_out = (size_t)B * H * W * sc * sc * 3;
+    const float* din = (const float*)in;
+    float* dout = (float*)out;
+    const bool sync_call = !in_is_device || !out_is_device;     // as pfnl_forward: whose range flag, which stream
+    const int slot = sync_call ? 0 : 1;
+    const bool can_rerun = !h->opt.bf16 && !(h->opt.strict || !h->weights_f16_ok);
+    hipStream_t s = stream ? (hipStream_t)stream : ((in_is_device && out_is_device) ? (hipStream_t) nullptr : h->stream);
+    if (!in_is_device) {
+        if (h->stage_in.ensure(n_in)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
+        if (int e = stage_h2d(h, h->stage_in.p, in, n_in * sizeof(float), s)) return e;
+        din = h->stage_in.p;
+    }
+    if (!out_is_device) {
+        if (h->stage_out.ensure(n_out)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
+        dout = h->stage_out.p;
+    }
+    if (int e = tiled_device(h, din, dout, g, total, run, n, s, slot)) return e;
+    if (!out_is_device) {
+        if (int e = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e;
+    } else if (!in_is_device) {
+        HIPCHK(hipStreamSynchronize(s));   // the caller may reuse its host buffer on return
+    }
+    if (sync_call) {
+        // the flag of all runs, read once behind the last of them; set: the whole tiled call once more on the f32-MFMA kernels
+        int flagged = 0;
+        if (int e = range_flag_take(h, 0, &flagged)) return e;
+        if (flagged && can_rerun) {
+            h->strict_once = true;
+            const int e = tiled_device(h, din, dout, g, total, run, n, s, 0);
             h->strict_once = false;
             if (e) return e;
             ++h->range_reruns;

@@ -11,6 +11,7 @@
 #include "conv_small.h"
 #include "conv_split16.h"
 #include "surface_geom.h"
+#include "tile_geom.h"
 
 namespace {
 
@@ -1136,6 +1137,34 @@ int pfnl_op_dihedral(const float* in, float* out, int n_img, int H, int W, int k
 int pfnl_op_dihedral_accum(float* acc, const float* y, int n_img, int H, int W, int k, float scale, void* stream) {
     if (int r = dihedral_op_refused(acc, y, n_img, H, W, k)) return r;
     HIPCHK(pfnl::launch_dihedral_accum(acc, y, n_img, H, W, k, scale, (hipStream_t)stream));
+    return 0;
+}
+
+// as above: refused before any HIP call; the grid of a call that passed
+static int tile_op_refused(const void* a, const void* b, int B, int H, int W, const pfnl_tiling* t, int first, int count, pfnl::TileGrid* g) {
+    if (!a || !b || !t) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (B < 1) return fail(PFNL_ERR_INVALID, "tile: B must be positive");
+    if (const char* why = pfnl::tiling_refused(H, W, *t)) return fail(PFNL_ERR_INVALID, why);
+    *g = pfnl::tile_grid(H, W, *t);
+    const int total = pfnl::tile_total(*g, B);
+    if (!total) return fail(PFNL_ERR_INVALID, "tile: the tile count overflows a 32-bit integer");
+    if (first < 0 || count < 1 || count > total - first) return fail(PFNL_ERR_INVALID, "tile: first .. first + count - 1 must be tiles of the call");
+    return 0;
+}
+
+int pfnl_op_tile_gather(const float* in, float* tiles, int B, int T, int H, int W, const pfnl_tiling* t, int first, int count, void* stream) {
+    pfnl::TileGrid g;
+    if (int r = tile_op_refused(in, tiles, B, H, W, t, first, count, &g)) return r;
+    if (T < 1) return fail(PFNL_ERR_INVALID, "tile: T must be positive");
+    HIPCHK(pfnl::launch_tile_gather(in, tiles, g, T, first, count, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_tile_scatter(const float* y, float* out, int B, int H, int W, int scale, const pfnl_tiling* t, int first, int count, void* stream) {
+    pfnl::TileGrid g;
+    if (int r = tile_op_refused(y, out, B, H, W, t, first, count, &g)) return r;
+    if (scale < 1 || scale > 8) return fail(PFNL_ERR_INVALID, "tile: scale must lie in 1 .. 8");
+    HIPCHK(pfnl::launch_tile_scatter(y, out, g, scale, first, count, (hipStream_t)stream));
     return 0;
 }
 

@@ -14,6 +14,7 @@
 #include "capi_internal.h"
 #include "common.h"
 #include "stream_route.h"
+#include "tile_geom.h"
 
 namespace {
 
@@ -50,6 +51,8 @@ struct pfnl_stream {
     bool strict = false;                              // a batch was flagged: the rest of the sequence runs on the strict kernels
     std::string prior_strict, prior_precision;        // what the library held before go_strict changed it ("" = unchanged)
     int ensemble = 1;                                 // pfnl_stream_ensemble: the members of every batch's forward (1: the plain forward)
+    bool tiled = false;                               // pfnl_stream_tile: every batch's forward runs as tiles of `tiling`
+    pfnl_tiling tiling{};
     // scenes (pfnl_stream_scenes): allocated by the first call that turns them on; they have the ring's lifetime and its slots
     int scene_mode = 0;                               // 0 off | 1 marks | 2 marks + detector
     unsigned long long thr_sum = 0;                   // ceil(threshold H W): the detector compares sums
@@ -113,7 +116,8 @@ int enqueue(pfnl_stream* s, const Batch& b) {
     } else {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
-    if (int e = pfnl_forward_ensemble(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->ensemble, s->s)) return e;   // (1: pfnl_forward itself)
+    // (no tiling: pfnl_forward_ensemble itself, and with 1 member pfnl_forward itself)
+    if (int e = pfnl_forward_tiled(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->tiled ? &s->tiling : nullptr, s->ensemble, s->s)) return e;
     if (int e = s->route.sample_bytes == 2 ? run_route<uint16_t>(s, b) : run_route<uint8_t>(s, b)) return e;
     HIPCHK(hipEventRecord(s->ev[b.slot], s->s));
     return 0;
@@ -541,6 +545,16 @@ int pfnl_stream_ensemble(pfnl_stream* s, int n) {
     if (n != 1 && n != 2 && n != 4 && n != 8) return fail(PFNL_ERR_INVALID, "ensemble: n must be 1, 2, 4 or 8");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the ensemble is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     s->ensemble = n;
+    return 0;
+}
+
+int pfnl_stream_tile(pfnl_stream* s, const pfnl_tiling* t) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (t)
+        if (const char* why = pfnl::tiling_refused(s->H, s->W, *t)) return fail(PFNL_ERR_INVALID, why);
+    if (s->pushed) return fail(PFNL_ERR_STATE, "the tiling is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    s->tiled = t != nullptr;
+    s->tiling = t ? *t : pfnl_tiling{};
     return 0;
 }
 

@@ -253,6 +253,15 @@ hipError_t launch_dihedral(const float* in, float* out, int n, int H, int W, int
 // acc = (acc + g_k^-1(y)) * scale: acc [n][H][W][3]; y [n][H][W][3], or [n][W][H][3] for k >= 4; one thread per element of acc, no atomics
 hipError_t launch_dihedral_accum(float* acc, const float* y, int n, int H, int W, int k, float scale, hipStream_t s);
 
+// ---- the two launches of a tiled forward's run (tiles.hip; the geometry: tile_geom.h; the rule: pfnl_amd/tiles.py) ----
+// tiles first .. first + count - 1 of the call's grid `g` (inside its total: the callers check).  Both copy bits, in 16-, 8- or 4-byte words
+// as the addresses allow.
+struct TileGrid;
+// in [B][T][H][W][3] -> tiles [count][T][th][tw][3]
+hipError_t launch_tile_gather(const float* in, float* tiles, const TileGrid& g, int T, int first, int count, hipStream_t s);
+// y [count][scale th][scale tw][3] -> the owned rectangles of those tiles inside out [B][scale H][scale W][3], each element stored once
+hipError_t launch_tile_scatter(const float* y, float* out, const TileGrid& g, int scale, int first, int count, hipStream_t s);
+
 // ---- Y-channel PSNR / SSIM sums of uint8 RGB frame pairs (score.hip) ---------------------------
 // pred, truth [F][H][W][3]; out [F][4] = sum_d2_full, sum_d2_crop (border sp_border), ssim_sum_full, ssim_sum_valid;
 // partial: score_scratch_bytes(F, H, W) of device memory (one slot per workgroup: the sums are repeatable bit for bit)

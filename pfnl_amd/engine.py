@@ -12,7 +12,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import _capi
+from . import _capi, tiles as _tiles
 from .ensemble import members as _members
 from .spec import PFNLGeometry, check_weights
 
@@ -81,6 +81,17 @@ def ensemble_members(n) -> int:
     return int(n)
 
 
+def tile_argument(tile, shape):
+    """``tile`` ((th, tw), (th, tw, pad), (th, tw, pad, batch) or None) for an input of ``shape`` [B,T,H,W,3] as the C-ABI takes it: a
+    ``_capi.pfnl_tiling``, or None for None.  ValueError for what pfnl_amd/tiles.py ``check`` refuses; needs no device."""
+    if tile is None:
+        return None
+    t = _tiles.tiling(tile)
+    if len(shape) == 5:
+        t = _tiles.check(int(shape[2]), int(shape[3]), t)
+    return _capi.pfnl_tiling(*t)
+
+
 class PFNLEngine:
     def __init__(self, geom: PFNLGeometry = PFNLGeometry(), device: int = 0):
         self.geom = geom
@@ -94,6 +105,7 @@ class PFNLEngine:
         self._ready = False
         self._options: Dict[str, str] = {}       # what set_option was called with (the library's own view: get_option)
         self.ensemble = 1                        # members of forward()'s self-ensemble when the call names none (pfnl_amd/ensemble.py)
+        self.tile = None                         # forward()'s tiling when the call names none (pfnl_amd/tiles.py); None: the whole frame
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -136,6 +148,7 @@ class PFNLEngine:
             other.set_option(k, self.get_option(k))
         other.copy_weights_from(self)
         other.ensemble = self.ensemble
+        other.tile = self.tile
         return other
 
     def set_option(self, key: str, value: str) -> None:
@@ -173,13 +186,16 @@ class PFNLEngine:
         s = self.geom.scale
         return (B, 1, s * H, s * W, 3)
 
-    def forward(self, x, ensemble=None):
+    def forward(self, x, ensemble=None, tile=None):
         """x: [B,T,H,W,3] float32 (numpy array, torch CPU tensor or torch tensor on this engine's
         GPU) -> [B,1,sH,sW,3] float32 in the same kind of container (reference model/pfnl.py:39-80).
         Host containers: synchronous (H2D + kernels + D2H inside pfnl_forward).  Device tensors:
         enqueued on torch's current stream.  ``ensemble``: 1, 2, 4 or 8 members of the geometric self-ensemble
-        (pfnl_forward_ensemble; the rule: pfnl_amd/ensemble.py); None: ``self.ensemble``, 1 unless set - the plain forward."""
+        (pfnl_forward_ensemble; the rule: pfnl_amd/ensemble.py); None: ``self.ensemble``, 1 unless set - the plain forward.
+        ``tile``: (th, tw), (th, tw, pad) or (th, tw, pad, batch) - the frame as runs of ``batch`` overlapping tiles of th x tw with margin
+        ``pad`` (pfnl_forward_tiled; the rule: pfnl_amd/tiles.py); None: ``self.tile``, None unless set - the whole frame."""
         n = ensemble_members(self.ensemble if ensemble is None else ensemble)
+        t = tile_argument(self.tile if tile is None else tile, np.shape(x))
         if _is_torch(x):
             import torch
             if x.is_cuda:
@@ -189,18 +205,20 @@ class PFNLEngine:
                 x = x.contiguous()
                 out = torch.empty(self.out_shape(B, H, W), dtype=torch.float32, device=x.device)
                 stream = torch.cuda.current_stream(x.device).cuda_stream
-                _capi.check(self._forward(n, C.c_void_p(x.data_ptr()), 1, C.c_void_p(out.data_ptr()), 1, B, H, W, C.c_void_p(stream)))
+                _capi.check(self._forward(n, C.c_void_p(x.data_ptr()), 1, C.c_void_p(out.data_ptr()), 1, B, H, W, C.c_void_p(stream), t))
                 return out
-            return torch.from_numpy(self.forward(x.detach().numpy(), ensemble=n))
+            return torch.from_numpy(self.forward(x.detach().numpy(), ensemble=n, tile=None if t is None else (t.tile_h, t.tile_w, t.pad, t.batch)))
         x = np.asarray(x)
         B, T, H, W = self._check_input(x.shape, x.dtype == np.float32)
         x = np.ascontiguousarray(x)
         out = self._host_output(self.out_shape(B, H, W))
-        _capi.check(self._forward(n, x.ctypes.data_as(C.c_void_p), 0, out.ctypes.data_as(C.c_void_p), 0, B, H, W, None))
+        _capi.check(self._forward(n, x.ctypes.data_as(C.c_void_p), 0, out.ctypes.data_as(C.c_void_p), 0, B, H, W, None, t))
         return out
 
-    def _forward(self, n: int, inp, in_is_device: int, out, out_is_device: int, B: int, H: int, W: int, stream) -> int:
-        """pfnl_forward on this handle, or pfnl_forward_ensemble with n > 1 members; the status."""
+    def _forward(self, n: int, inp, in_is_device: int, out, out_is_device: int, B: int, H: int, W: int, stream, t=None) -> int:
+        """pfnl_forward on this handle, pfnl_forward_ensemble with n > 1 members, or pfnl_forward_tiled with a tiling ``t``; the status."""
+        if t is not None:
+            return self._lib.pfnl_forward_tiled(self._h, inp, in_is_device, out, out_is_device, B, H, W, C.byref(t), n, stream)
         if n == 1:
             return self._lib.pfnl_forward(self._h, inp, in_is_device, out, out_is_device, B, H, W, stream)
         return self._lib.pfnl_forward_ensemble(self._h, inp, in_is_device, out, out_is_device, B, H, W, n, stream)
@@ -224,13 +242,15 @@ class PFNLEngine:
         """"pinned" (pool of pfnl_host_alloc blocks) or "pageable": what bench.py records next to its host-pointer line."""
         return "pageable" if os.environ.get("PFNL_HOST_OUTPUT", "pinned") == "pageable" else "pinned (pfnl_host_alloc pool)"
 
-    def forward_device(self, in_ptr: int, out_ptr: int, B: int, H: int, W: int, stream: int = 0, ensemble: int = 1) -> None:
+    def forward_device(self, in_ptr: int, out_ptr: int, B: int, H: int, W: int, stream: int = 0, ensemble: int = 1, tile=None) -> None:
         """Raw device-pointer form (asynchronous on ``stream``; 0 = the legacy null stream, i.e. torch's default stream).
         Asynchronous calls cannot re-run on the f32 kernels when the f16-pipe range flag fires: check ``sync()``.
-        ``ensemble``: as for ``forward``; the default is the plain forward whatever ``self.ensemble`` holds."""
+        ``ensemble``, ``tile``: as for ``forward``; the defaults are the plain forward of the whole frame whatever ``self.ensemble`` and
+        ``self.tile`` hold."""
+        t = tile_argument(tile, (B, 0, H, W, 3))
         self._check_input((B, self.geom.num_frames, H, W, 3), True)
         _capi.check(self._forward(ensemble_members(ensemble), C.c_void_p(in_ptr), 1, C.c_void_p(out_ptr), 1, B, H, W,
-                                  C.c_void_p(stream) if stream else None))
+                                  C.c_void_p(stream) if stream else None, t))
 
     def forward_strip(self, x, out, row0: int, nrows: int) -> None:
         """Single-clip sharding: x [B,T,H,W,3] float32 cuda tensor (the whole clip), out [B,1,sH,sW,3] float32 cuda tensor

@@ -107,6 +107,7 @@ class VSR(object):
     device = 0
     num_block = 20
     self_ensemble = 1              # 1, 2, 4 or 8: geometric self-ensemble of every forward (pfnl_amd/ensemble.py); 1 = the reference's plain forward
+    tile = None                    # (th, tw[, pad[, batch]]): every forward as runs of overlapping tiles (pfnl_amd/tiles.py); None = the whole frame
 
     def geometry(self) -> PFNLGeometry:
         return PFNLGeometry(num_frames=self.num_frames, scale=self.scale, num_block=self.num_block)
@@ -144,10 +145,10 @@ class VSR(object):
             if prec != "fp32":
                 eng.set_option("precision", prec)
             self._engine = eng
-        # build-side knob (the reference has none): the members of every forward the harness issues (pfnl_amd/ensemble.py)
-        self._engine.ensemble = self.self_ensemble
+        # build-side knob (the reference has none): the members and the tiling of every forward the harness issues (pfnl_amd/ensemble.py, pfnl_amd/tiles.py)
+        self._engine.ensemble, self._engine.tile = self.self_ensemble, self.tile
         if getattr(self, "_engine2", None) is not None:
-            self._engine2.ensemble = self.self_ensemble
+            self._engine2.ensemble, self._engine2.tile = self.self_ensemble, self.tile
         return self._engine
 
     def save(self, sess, checkpoint_dir, step):

@@ -324,6 +324,57 @@ def dihedral_accum(acc, y, k: int, scale: float = 1.0):
     return acc
 
 
+def _tile_run(B, H, W, tile, first, count):
+    """(the tiling as the C-ABI takes it, th, tw, first, count) for tiles first .. first+count-1 (count None: all from ``first`` on) of a
+    call [B,.,H,W,3]; ValueError as pfnl_amd/tiles.py ``check``."""
+    from . import tiles
+    t = tiles.check(H, W, tile)
+    th, tw, rows, cols = tiles.grid(H, W, t)
+    total = B * len(rows) * len(cols)
+    first = int(first)
+    count = total - first if count is None else int(count)
+    if first < 0 or count < 1 or first + count > total:
+        raise ValueError(f"tiles {first} .. {first + count - 1} are not tiles of the call (it has {total})")
+    return _capi.pfnl_tiling(*t), th, tw, first, count
+
+
+def tile_gather(x, tile, first: int = 0, count=None, out=None):
+    """Tiles first .. first+count-1 of x [B,T,H,W,3] (cuda) as a stack [count,T,th,tw,3] (pfnl_amd/tiles.py split; ``count`` None: all
+    from ``first`` on).  ``out``: a contiguous tensor of that shape to fill."""
+    import torch
+    lib = _capi.load_library()
+    if x.dim() != 5 or x.shape[-1] != 3 or x.numel() == 0:
+        raise ValueError(f"x: expected [B,T,H,W,3], got {tuple(x.shape)}")
+    B, T, H, W = (int(v) for v in x.shape[:4])
+    t, th, tw, first, count = _tile_run(B, H, W, tile, first, count)
+    shape = (count, T, th, tw, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out must have shape {shape}, got {tuple(out.shape)}")
+    _capi.check(lib.pfnl_op_tile_gather(_req(x, "x"), _req(out, "out"), B, T, H, W, C.byref(t), first, count, _stream(x)))
+    return out
+
+
+def tile_scatter(y, out, tile, scale: int, first: int = 0):
+    """The owned rectangles of the tile results y [count,(1,)s*th,s*tw,3] (cuda), tiles first .. first+count-1 of the call, into ``out``
+    [B,(1,)s*H,s*W,3] in place (pfnl_amd/tiles.py assemble); every element of the rectangles is stored once, nothing else of ``out`` is
+    touched.  Returns ``out``."""
+    lib = _capi.load_library()
+    s = int(scale)
+    if s < 1 or out.dim() < 4 or out.shape[-1] != 3 or out.shape[-3] % s or out.shape[-2] % s or out.numel() == 0:
+        raise ValueError(f"out: expected [B,(1,){s}*H,{s}*W,3], got {tuple(out.shape)}")
+    H, W = int(out.shape[-3]) // s, int(out.shape[-2]) // s
+    B = out.numel() // (s * H * s * W * 3)
+    if y.dim() < 4 or y.numel() == 0:
+        raise ValueError(f"y: expected [count,(1,)s*th,s*tw,3], got {tuple(y.shape)}")
+    t, th, tw, first, count = _tile_run(B, H, W, tile, first, int(y.shape[0]))
+    if tuple(y.shape[-3:]) != (s * th, s * tw, 3) or y.numel() != count * s * th * s * tw * 3:
+        raise ValueError(f"y must be {count} tile results of ({s * th}, {s * tw}, 3), got {tuple(y.shape)}")
+    _capi.check(lib.pfnl_op_tile_scatter(_req(y, "y"), _req(out, "out"), B, H, W, s, C.byref(t), first, count, _stream(out)))
+    return out
+
+
 def blur_decimate(hr, scale: int = 4):
     """reference utils.py:169-192 (DownSample_4D with BLUR): hr [F,H,W,3] (cuda) -> [F,ceil(H/s),ceil(W/s),3]."""
     import torch

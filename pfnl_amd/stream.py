@@ -47,7 +47,7 @@ from typing import List, Tuple
 
 import numpy as np
 
-from . import _capi, ensemble as _ensemble, fit as _fit, resize as _resize, surface as _surface
+from . import _capi, ensemble as _ensemble, fit as _fit, resize as _resize, surface as _surface, tiles as _tiles
 
 
 def next_batch(num_frames: int, batch: int, pushed: int, ended: bool, launched: int) -> Tuple[int, int]:
@@ -141,6 +141,12 @@ def ensemble_argument(ensemble=1) -> int:
     return int(ensemble)
 
 
+def tiling_argument(H: int, W: int, tile_h, tile_w, pad=0, batch=0) -> Tuple[int, int, int, int]:
+    """The tiling of ``set_tiling`` for a session of H x W as ``(tile_h, tile_w, pad, batch)``; ValueError for anything the library would
+    refuse (pfnl_amd/tiles.py ``check``).  Needs no device."""
+    return _tiles.check(int(H), int(W), (tile_h, tile_w, pad, batch))
+
+
 def frame_shapes(pixel_format: str, H: int, W: int) -> Tuple[tuple, ...]:
     """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24 and rgb10; ``(H*3//2, W)`` or flat for the 4:2:0 formats
     (in samples: uint8, or uint16 for the 10-bit formats - ``frame_dtype``)."""
@@ -179,7 +185,10 @@ class VideoStream:
     out, or ``place`` itself - and the 8-bit colour ``fill`` elsewhere.  ``crop`` alone delivers the crop at its own size.  With any of the
     three set, ``vs.crop`` and ``vs.place`` are the resolved rectangles and ``vs.out_size`` the canvas; else they are None.
 
-    ``ensemble`` (1 | 2 | 4 | 8): every batch's forward as a geometric self-ensemble of that many members (pfnl_amd/ensemble.py); 1 is off."""
+    ``ensemble`` (1 | 2 | 4 | 8): every batch's forward as a geometric self-ensemble of that many members (pfnl_amd/ensemble.py); 1 is off.
+
+    ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
+    (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0), ensemble=1):
@@ -307,6 +316,23 @@ class VideoStream:
         _capi.check(self._lib.pfnl_stream_reset(self._handle()))
         self.cuts = []
         self.last_info = None
+
+    @property
+    def tiling(self):
+        """``(tile_h, tile_w, pad, batch)`` as ``set_tiling`` stored it, or None: whole frames."""
+        return getattr(self, "_tiling", None)
+
+    def set_tiling(self, tile_h, tile_w, pad=0, batch=0) -> None:
+        """Every batch's forward as runs of ``batch`` overlapping tiles of tile_h x tile_w with margin ``pad`` (pfnl_stream_tile; the rule:
+        pfnl_amd/tiles.py; batch 0: all tiles of a batch of windows in one run).  ``set_tiling(None, None)`` turns it off.  Accepted only
+        before the first frame of a sequence; the setting survives ``reset``."""
+        if tile_h is None and tile_w is None:
+            _capi.check(self._lib.pfnl_stream_tile(self._handle(), None))
+            self._tiling = None
+            return
+        t = tiling_argument(self.H, self.W, tile_h, tile_w, pad, batch)          # (before anything touches the session)
+        _capi.check(self._lib.pfnl_stream_tile(self._handle(), C.byref(_capi.pfnl_tiling(*t))))
+        self._tiling = t
 
     def mark_cut(self) -> None:
         """The next pushed frame starts a scene (needs ``scene_cut``; before the first frame of a sequence it changes nothing)."""
