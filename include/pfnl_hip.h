@@ -353,7 +353,7 @@ int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long l
  *   frames are tightly packed, H * W * 3 / 2 bytes: NV12 = Y [H][W], CbCr [H/2][W/2][2]; I420 = Y [H][W], Cb [H/2][W/2], Cr [H/2][W/2];
  *   coefficients of BT.601 or BT.709, limited (16..235 / 16..240) or full range, with 14 fractional bits, each rounded once
  *     (pfnl_yuv_coefficients: y0, then yr yg yb cbr cbg cbb crr crg crb, then dy drv dgu dgv dbu);
- *   chroma sited left (H.264 / HEVC type 0): in: 3 : 1 between the near and the far chroma row, 1 : 1 between two samples on odd columns,
+ *   chroma sited left (H.264 / HEVC type 0; SITING below names the others): in: 3 : 1 between the near and the far chroma row, 1 : 1 between two samples on odd columns,
  *     indices clamped; out: 1-2-1 over the two luma rows of the unrounded numerators, columns clamped, one rounding.
  *   pfnl_stream_format: in_fmt for push (H*W*3/2 bytes, converted into the frame's ring slot: a device pointer on the session's stream, a
  *     host pointer through a staging buffer on the copy's, before push returns), out_fmt for pop (sH*sW*3/2 bytes = the conversion of the
@@ -371,7 +371,7 @@ int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long l
  *   the input side (RGB24, NV12, I420), scenes, the push bound, reset and the replay behind the range fence are what they are at 8 bits.
  *   As in_fmt the three are PFNL_ERR_INVALID (10-bit input is not built: it needs a 16-bit ring), and so is RGB10 out of a YUV in_fmt.
  *   The 16-bit output slots are allocated by the call that sets the format (PFNL_ERR_NOMEM) and freed by pfnl_stream_close.
- * Out of scope: 10-bit input, 12 and 16 bits, 4:2:2 and 4:4:4, other sitings, transfer functions, BT.2020. */
+ * Out of scope: 10-bit input, 12 and 16 bits, 4:2:2 and 4:4:4, sitings beyond SITING's three, transfer functions, BT.2020. */
 enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2, PFNL_PIX_RGB10 = 3, PFNL_PIX_P010 = 4, PFNL_PIX_I010 = 5 };
 enum { PFNL_MATRIX_BT601 = 0, PFNL_MATRIX_BT709 = 1 };
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range);
@@ -448,6 +448,26 @@ typedef struct pfnl_surface {
 } pfnl_surface;
 int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_device);
 int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_device, long long* index, int* got);
+/* SITING (additions to version 4; a session that does not call pfnl_stream_chroma_siting issues the launches it always issued and
+ * delivers the same bytes).  4:2:0 streams differ in where a chroma sample sits among its four luma pixels, and converting with the
+ * wrong assumption shifts the colour by half a luma pixel - two pixels after a 4 x upscale.  Chroma sample (j, i) sits at the luma
+ * coordinates (row, column):
+ *   PFNL_SITING_LEFT    (2j + 1/2, 2i)        H.264 / HEVC type 0, MPEG-2, Y4M C420mpeg2: the default, and the rule stated above;
+ *   PFNL_SITING_CENTER  (2j + 1/2, 2i + 1/2)  JPEG, MPEG-1, Y4M C420jpeg;
+ *   PFNL_SITING_TOPLEFT (2j, 2i)              HEVC type 2 (UHD), Y4M C420paldv.
+ * Per axis a siting is midway (the vertical axis of LEFT, both of CENTER) or co-sited.  The rule is stated once on the host,
+ * pfnl_amd/yuv.py upsample / encode_filter (10 bits: pfnl_amd/depth10.py):
+ *   in: per axis two taps in quarters, chroma indices clamped - midway: near = j, far = j + 1 on odd and j - 1 on even luma indices,
+ *     3 : 1; co-sited: near = j, far = j + 1, 4 : 0 on even and 2 : 2 on odd indices; the sample is (sum wy wx C + 8) >> 4;
+ *   out: the unrounded numerators filtered per axis, indices clamped - midway: a box over 2j, 2j + 1 (k = 1); co-sited: 1-2-1 over
+ *     2j - 1, 2j, 2j + 1 (k = 2) - and one rounding by 14 + k bits, k summed over both axes: 3 for LEFT, 2 for CENTER, 4 for TOPLEFT.
+ *   pfnl_stream_chroma_siting: in_siting for what push takes, out_siting for what pop delivers, each used where that edge is 4:2:0 and
+ *     ignored by an RGB edge; the surface calls follow them.  NULL and a value outside the enum: PFNL_ERR_INVALID, before any HIP call.
+ *     Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); the setting survives pfnl_stream_reset
+ *     and pfnl_stream_format.  It allocates nothing: the siting is an argument of the edge's one conversion launch.
+ * Out of scope: HEVC types 1, 3, 4 and 5, sitings that differ between Cb and Cr, 4:2:2 and 4:4:4. */
+enum { PFNL_SITING_LEFT = 0, PFNL_SITING_CENTER = 1, PFNL_SITING_TOPLEFT = 2 };
+int pfnl_stream_chroma_siting(pfnl_stream* s, int in_siting, int out_siting);
 /* SELF-ENSEMBLE in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With
  * n in {2, 4, 8} the one forward of every batch is pfnl_forward_ensemble(..., n, ...) (SELF-ENSEMBLE above); gather, quantisation, the
  * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  n = 1 is
@@ -762,6 +782,16 @@ int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, ui
 int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream);
 int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, void* stream);
 int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream);
+/* The four conversion hooks above with the chroma siting named (SITING: PFNL_SITING_*), ahead of stream; the plain hooks are these with
+ * PFNL_SITING_LEFT.  A siting outside the enum is PFNL_ERR_INVALID before any HIP call, like every other argument. */
+int pfnl_op_yuv420_to_rgb_u8_sited(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, int siting,
+                                   void* stream);
+int pfnl_op_yuv420_to_rgb_u8_surface_sited(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W,
+                                           uint8_t* rgb /*[H][W][3] packed*/, int siting, void* stream);
+int pfnl_op_rgb_to_yuv420_u8_sited(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, int siting,
+                                   void* stream);
+int pfnl_op_rgb_to_yuv420_u10_sited(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, int siting,
+                                    void* stream);
 /* The session's placement kernels (PLACEMENT, pfnl_stream_place; the rule: pfnl_amd/fit.py place, pfnl_amd/depth10.py place10).  in
  * [n][H][W][3] -> out [n][oH][oW][3]: fill everywhere, the resize of in[src] at dst; src NULL = the whole frame, dst NULL = the whole canvas,
  * fill NULL = zeros; at 10 bits fill is in sample values, <= 1023.  Device pointers; they synchronise as pfnl_op_resize_u8 does.  One launch,

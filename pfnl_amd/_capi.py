@@ -145,6 +145,11 @@ SIGNATURES = {
     "pfnl_stream_push_surface": (_i, [_vp, C.POINTER(pfnl_surface), _i]),
     "pfnl_stream_pop_surface": (_i, [_vp, C.POINTER(pfnl_surface), _i, C.POINTER(C.c_longlong), C.POINTER(_i)]),
     "pfnl_op_yuv420_to_rgb_u8_surface": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_stream_chroma_siting": (_i, [_vp, _i, _i]),
+    "pfnl_op_yuv420_to_rgb_u8_sited": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "pfnl_op_yuv420_to_rgb_u8_surface_sited": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "pfnl_op_rgb_to_yuv420_u8_sited": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "pfnl_op_rgb_to_yuv420_u10_sited": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "pfnl_resize_max_taps": (_i, [_i, _i, C.POINTER(_i)]),
     "pfnl_resize_taps": (_i, [_i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int16)]),
     "pfnl_op_resize_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
@@ -172,6 +177,7 @@ PIXEL_FORMATS = {"rgb24": 0, "nv12": 1, "i420": 2, "rgb10": 3, "p010": 4, "i010"
 TEN_BIT_FORMATS = ("rgb10", "p010", "i010")                # uint16 samples; out_format only
 FORMATS_420 = ("nv12", "i420", "p010", "i010")             # H * W * 3 / 2 samples, even sizes
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                    # PFNL_MATRIX_*
+CHROMA_SITINGS = {"left": 0, "center": 1, "topleft": 2}    # PFNL_SITING_* (pfnl_amd/yuv.py SITINGS, in its order)
 COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX = 0, 1
 

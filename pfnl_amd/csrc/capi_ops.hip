@@ -963,27 +963,51 @@ static int yuv_op_refused(const void* a, const void* b, int fmt, int matrix, int
     return 0;
 }
 
-int pfnl_op_yuv420_to_rgb_u8(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, void* stream) {
+static int siting_refused(int siting) {
+    if (siting < PFNL_SITING_LEFT || siting > PFNL_SITING_TOPLEFT)
+        return fail(PFNL_ERR_INVALID, "yuv: siting must be PFNL_SITING_LEFT, PFNL_SITING_CENTER or PFNL_SITING_TOPLEFT");
+    return 0;
+}
+
+int pfnl_op_yuv420_to_rgb_u8_sited(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, int siting,
+                                   void* stream) {
     pfnl::YuvCoef c;
     if (int r = yuv_op_refused(yuv, rgb, fmt, matrix, full_range, n, H, W, &c)) return r;
-    HIPCHK(pfnl::launch_yuv420_to_rgb_u8(yuv, rgb, fmt == PFNL_PIX_NV12, c, n, H, W, (hipStream_t)stream));
+    if (int r = siting_refused(siting)) return r;
+    HIPCHK(pfnl::launch_yuv420_to_rgb_u8(yuv, rgb, fmt == PFNL_PIX_NV12, c, n, H, W, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_yuv420_to_rgb_u8(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, void* stream) {
+    return pfnl_op_yuv420_to_rgb_u8_sited(yuv, fmt, matrix, full_range, n, H, W, rgb, PFNL_SITING_LEFT, stream);
+}
+
+int pfnl_op_yuv420_to_rgb_u8_surface_sited(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint8_t* rgb, int siting,
+                                           void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = yuv_op_refused(yuv, rgb, fmt, matrix, full_range, 1, H, W, &c)) return r;
+    if (int r = siting_refused(siting)) return r;
+    if (const char* why = pfnl::surface_refused(yuv, fmt, H, W)) return fail(PFNL_ERR_INVALID, why);
+    HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*yuv, fmt == PFNL_PIX_NV12), rgb, fmt == PFNL_PIX_NV12, c, 1, H, W,
+                                                siting, (hipStream_t)stream));
     return 0;
 }
 
 int pfnl_op_yuv420_to_rgb_u8_surface(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint8_t* rgb, void* stream) {
+    return pfnl_op_yuv420_to_rgb_u8_surface_sited(yuv, fmt, matrix, full_range, H, W, rgb, PFNL_SITING_LEFT, stream);
+}
+
+int pfnl_op_rgb_to_yuv420_u8_sited(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, int siting,
+                                   void* stream) {
     pfnl::YuvCoef c;
-    if (int r = yuv_op_refused(yuv, rgb, fmt, matrix, full_range, 1, H, W, &c)) return r;
-    if (const char* why = pfnl::surface_refused(yuv, fmt, H, W)) return fail(PFNL_ERR_INVALID, why);
-    HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*yuv, fmt == PFNL_PIX_NV12), rgb, fmt == PFNL_PIX_NV12, c, 1, H, W,
-                                                (hipStream_t)stream));
+    if (int r = yuv_op_refused(rgb, yuv, fmt, matrix, full_range, n, H, W, &c)) return r;
+    if (int r = siting_refused(siting)) return r;
+    HIPCHK(pfnl::launch_rgb_to_yuv420(rgb, yuv, fmt == PFNL_PIX_NV12, c, n, H, W, siting, (hipStream_t)stream));
     return 0;
 }
 
 int pfnl_op_rgb_to_yuv420_u8(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, void* stream) {
-    pfnl::YuvCoef c;
-    if (int r = yuv_op_refused(rgb, yuv, fmt, matrix, full_range, n, H, W, &c)) return r;
-    HIPCHK(pfnl::launch_rgb_to_yuv420(rgb, yuv, fmt == PFNL_PIX_NV12, c, n, H, W, (hipStream_t)stream));
-    return 0;
+    return pfnl_op_rgb_to_yuv420_u8_sited(rgb, fmt, matrix, full_range, n, H, W, yuv, PFNL_SITING_LEFT, stream);
 }
 
 int pfnl_yuv10_coefficients(int matrix, int full_range, int32_t out[10]) {
@@ -1005,13 +1029,19 @@ int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream)
 }
 
 int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, void* stream) {
+    return pfnl_op_rgb_to_yuv420_u10_sited(rgb, fmt, matrix, full_range, n, H, W, yuv, PFNL_SITING_LEFT, stream);
+}
+
+int pfnl_op_rgb_to_yuv420_u10_sited(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, int siting,
+                                    void* stream) {
     if (!rgb || !yuv) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (fmt != PFNL_PIX_P010 && fmt != PFNL_PIX_I010) return fail(PFNL_ERR_INVALID, "yuv10: fmt must be PFNL_PIX_P010 or PFNL_PIX_I010");
     pfnl::YuvCoef c;
     if (!pfnl::yuv_coefficients(10, matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (n < 1 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "yuv10: n >= 1, H and W positive and even (4:2:0)");
     if ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(yuv)) % 2) return fail(PFNL_ERR_INVALID, "yuv10: uint16 samples are 2-byte aligned");
-    HIPCHK(pfnl::launch_rgb_to_yuv420(rgb, yuv, fmt == PFNL_PIX_P010, c, n, H, W, (hipStream_t)stream));
+    if (int r = siting_refused(siting)) return r;
+    HIPCHK(pfnl::launch_rgb_to_yuv420(rgb, yuv, fmt == PFNL_PIX_P010, c, n, H, W, siting, (hipStream_t)stream));
     return 0;
 }
 

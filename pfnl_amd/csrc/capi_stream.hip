@@ -69,6 +69,7 @@ struct pfnl_stream {
     // on its way into its ring slot.  Every stage `route` runs has a slot with room for a batch - 8- and 10-bit samples share it, as a
     // sequence has one route - and no other stage holds memory; stage 0 is allocated at open.
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
+    int in_siting = PFNL_SITING_LEFT, out_siting = PFNL_SITING_LEFT;   // pfnl_stream_chroma_siting: where a 4:2:0 edge's chroma sits
     pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
     pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010
     uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel; from the first YUV in_fmt on
@@ -102,7 +103,7 @@ int run_route(pfnl_stream* s, const Batch& b) {
     }
     if (r.runs[2])                                    // reads the resampled frames where stage 1 runs
         HIPCHK(pfnl::launch_rgb_to_yuv420(slot(r.runs[1] ? 1 : 0), slot(2), s->out_fmt == PFNL_PIX_NV12 || s->out_fmt == PFNL_PIX_P010,
-                                          ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w, s->s));
+                                          ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w, s->out_siting, s->s));
     return 0;
 }
 
@@ -460,7 +461,7 @@ int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
         s, is_device,
         [&](uint8_t* dst) {
             if (yuv_in)
-                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(frame, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->s));
+                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(frame, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->in_siting, s->s));
             else
                 HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
             return 0;
@@ -468,7 +469,7 @@ int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
         [&](uint8_t* dst) {
             if (yuv_in) {                             // (the staging frame is free again: every push ends with the copy stream idle)
                 HIPCHK(hipMemcpyAsync(s->yin, frame, s->lr_bytes / 2, hipMemcpyHostToDevice, s->cs));
-                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->cs));
+                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->in_siting, s->cs));
             } else {
                 HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
             }
@@ -485,7 +486,8 @@ int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_d
         s, is_device,
         [&](uint8_t* dst) {                           // YUV: the kernel reads the surface where it lies
             if (yuv_in)
-                HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*frame, nv12), dst, nv12, s->coef, 1, s->H, s->W, s->s));
+                HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*frame, nv12), dst, nv12, s->coef, 1, s->H, s->W,
+                                                            s->in_siting, s->s));
             else
                 HIPCHK(hipMemcpy2DAsync(dst, g.plane[0].row_bytes, frame->plane[0], frame->pitch[0], g.plane[0].row_bytes, g.plane[0].rows,
                                         hipMemcpyDeviceToDevice, s->s));
@@ -498,7 +500,7 @@ int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_d
                                         hipMemcpyHostToDevice, s->cs));
                 to += g.plane[k].rows * g.plane[k].row_bytes;
             }
-            if (yuv_in) HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, nv12, s->coef, 1, s->H, s->W, s->cs));
+            if (yuv_in) HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, nv12, s->coef, 1, s->H, s->W, s->in_siting, s->cs));
             return 0;
         });
 }
@@ -605,6 +607,18 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, "format staging allocation failed");
+}
+
+// no memory and no route depend on the sitings: they are arguments of the two conversion launches
+int pfnl_stream_chroma_siting(pfnl_stream* s, int in_siting, int out_siting) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    for (int v : {in_siting, out_siting})
+        if (v < PFNL_SITING_LEFT || v > PFNL_SITING_TOPLEFT)
+            return fail(PFNL_ERR_INVALID, "chroma siting: PFNL_SITING_LEFT, PFNL_SITING_CENTER or PFNL_SITING_TOPLEFT on either side");
+    if (s->pushed) return fail(PFNL_ERR_STATE, "the chroma siting is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    s->in_siting = in_siting;
+    s->out_siting = out_siting;
+    return 0;
 }
 
 // pfnl_stream_resize is the placement of the whole raster on the whole canvas: one body, and place_plan keeps resize_plan's words for it

@@ -190,8 +190,9 @@ struct YuvCoef {
 // bits 8: samples 0 .. 255, limited range 16 .. 235 / 16 .. 240; bits 10: samples 0 .. 1023, 64 .. 940 / 64 .. 960, y0 and the encode
 // side alone (the decode side stays zero); matrix 0 BT.601 | 1 BT.709; false: unknown depth, matrix or range (no device needed)
 bool yuv_coefficients(int bits, int matrix, int full_range, YuvCoef* c);
-// yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow)
-hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+// yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow);
+// siting: PFNL_SITING_* (0 left | 1 centre | 2 top left; anything else is hipErrorInvalidValue), in all four launchers
+hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);
 // The decode's source as planes: H rows of W bytes at y; NV12: H/2 rows of W bytes (Cb, Cr interleaved) at cb, cr unused; I420: H/2 rows of
 // W/2 bytes at cb and at cr.  pitch_*: bytes from one row to the next (>= the row); frame: bytes from one frame's planes to the next's.
 struct YuvPlanes {
@@ -199,11 +200,12 @@ struct YuvPlanes {
     size_t pitch_y, pitch_cb, pitch_cr, frame;
 };
 // the same kernel on planes (the packed launcher calls this with pitch W, W/2): words where W, every plane, every pitch and rgb allow
-hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting,
+                                          hipStream_t s);
 // the encode, one kernel over the sample type: uint8 -> NV12 (semiplanar) or I420 with the 8-bit table; uint16 with values 0 .. 1023 ->
 // P010 (semiplanar, samples << 6) or I010 with the 10-bit table; H, W even; any alignment a sample can have
-hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, hipStream_t s);
-hipError_t launch_rgb_to_yuv420(const uint16_t* rgb, uint16_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, hipStream_t s);
+hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);
+hipError_t launch_rgb_to_yuv420(const uint16_t* rgb, uint16_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);
 
 // ---- RGB frames at a chosen raster: the tap tables (resize.hip; the rule: pfnl_amd/resize.py) ----
 constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in

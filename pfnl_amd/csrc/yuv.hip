@@ -1,7 +1,8 @@
 // YUV 4:2:0 <-> packed RGB: the two edges of the streaming session (include/pfnl_hip.h, pfnl_stream_format) - the decode of NV12 / I420
 // input, and the encode to NV12 / I420 or, with uint16 samples 0 .. 1023, to P010 / I010.  The arithmetic is integer and stated once on the
 // host, pfnl_amd/yuv.py (10 bits: pfnl_amd/depth10.py): 14 fractional bits, coefficients rounded once, chroma sited left (on the even luma
-// columns, midway between two luma rows); the kernels give its samples.
+// columns, midway between two luma rows) unless the caller names another siting - centre or top left (include/pfnl_hip.h SITING), a template
+// parameter of both kernels; the kernels give its samples.
 // Both kernels move bytes - 1.5 samples per pixel on one side, 3 on the other.  A lane owns a strip of two luma rows by P pixels, so that the
 // chroma samples it reads (or forms) serve both rows.  8 bits: P = 16 reads and writes 16-byte words (8-byte ones for I420's half-width
 // planes), P = 4 4-byte words (2-byte ones), P = 2 single bytes; 10 bits: P = 8 reads three 16-byte words per row and writes one per luma
@@ -45,11 +46,15 @@ bool yuv_coefficients(int bits, int matrix, int full_range, YuvCoef* c) {
 // Strip k of 0 .. H/2 is the luma rows 2k - 1 and 2k: exactly the two rows that lie between the
 // chroma rows k - 1 and k, each three quarters its near row and one quarter the other (yuv.py upsample); row -1 and row H do not exist,
 // and there the missing chroma row clamps onto the present one.  Per row and plane a lane reads P/2 samples and the one to their right.
-template <int P, bool NV12>
+// S is the chroma siting (include/pfnl_hip.h SITING; yuv.py AXES).  S = 0, left, is the body above.  S = 1, centre: the same strips, and
+// horizontally the 3 : 1 rule as well - an even pixel's far sample is the one to its LEFT, so a lane also reads the sample left of its
+// strip (clamped at 0): P/2 + 2 per row and plane.  S = 2, top left: chroma row k lies ON luma row 2k, so strip k of 0 .. H/2 - 1 is the
+// rows 2k (row k alone) and 2k + 1 (half row k, half row min(k + 1, H/2 - 1)); horizontally as left.
+template <int P, bool NV12, int S>
 __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, uint8_t* __restrict__ rgb, int n, int H, int W, YuvCoef c) {
     constexpr bool WORDS = P > 2;
-    constexpr int HP = P / 2;
-    const int gw = W / P, strips = H / 2 + 1, hh = H >> 1, hw = W >> 1;
+    constexpr int HP = P / 2, L = S == 1 ? 1 : 0;                      // L: samples read left of the strip
+    const int gw = W / P, strips = S == 2 ? H / 2 : H / 2 + 1, hh = H >> 1, hw = W >> 1;
     const size_t total = (size_t)n * strips * gw;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
         const int g = (int)(t % gw);
@@ -60,8 +65,9 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
         const uint8_t* __restrict__ const fb = src.cb + f * src.frame;   // (NV12: Cb and Cr interleaved)
         const int x0 = g * P, i0 = x0 >> 1;
         const int ie = i0 + HP < hw ? i0 + HP : hw - 1;
-        const int jrow[2] = {k > 0 ? k - 1 : 0, k < hh ? k : hh - 1};
-        int cb[2][HP + 1], cr[2][HP + 1];
+        const int il = i0 > 0 ? i0 - 1 : 0;                            // (S = 1 alone reads it)
+        const int jrow[2] = {S == 2 ? k : (k > 0 ? k - 1 : 0), S == 2 ? (k + 1 < hh ? k + 1 : hh - 1) : (k < hh ? k : hh - 1)};
+        int cb[2][HP + 1 + L], cr[2][HP + 1 + L];                      // [L + q]: sample i0 + q; [0] of S = 1: sample il
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             if constexpr (NV12) {
@@ -70,19 +76,24 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
                 load_samples<uint8_t, P, WORDS>(p + x0, pair);
                 load_samples<uint8_t, 2, WORDS>(p + 2 * ie, e);
 #pragma unroll
-                for (int q = 0; q < HP; ++q) cb[a][q] = pair[2 * q], cr[a][q] = pair[2 * q + 1];
-                cb[a][HP] = e[0], cr[a][HP] = e[1];
+                for (int q = 0; q < HP; ++q) cb[a][L + q] = pair[2 * q], cr[a][L + q] = pair[2 * q + 1];
+                cb[a][L + HP] = e[0], cr[a][L + HP] = e[1];
+                if constexpr (L) {
+                    load_samples<uint8_t, 2, WORDS>(p + 2 * il, e);
+                    cb[a][0] = e[0], cr[a][0] = e[1];
+                }
             } else {
                 const uint8_t* const pb = fb + (size_t)jrow[a] * src.pitch_cb;
                 const uint8_t* const pr = src.cr + f * src.frame + (size_t)jrow[a] * src.pitch_cr;
-                load_samples<uint8_t, HP, WORDS>(pb + i0, cb[a]);
-                load_samples<uint8_t, HP, WORDS>(pr + i0, cr[a]);
-                cb[a][HP] = pb[ie], cr[a][HP] = pr[ie];
+                load_samples<uint8_t, HP, WORDS>(pb + i0, cb[a] + L);
+                load_samples<uint8_t, HP, WORDS>(pr + i0, cr[a] + L);
+                cb[a][L + HP] = pb[ie], cr[a][L + HP] = pr[ie];
+                if constexpr (L) cb[a][0] = pb[il], cr[a][0] = pr[il];
             }
         }
 #pragma unroll
         for (int a = 0; a < 2; ++a) {                                  // a = 0: row 2k - 1, near chroma row k - 1; a = 1: row 2k, near row k
-            const int y = 2 * k - 1 + a;
+            const int y = S == 2 ? 2 * k + a : 2 * k - 1 + a;          // (S = 2: row 2k + a, on chroma row k | between rows k and k + 1)
             if (y < 0 || y >= H) continue;
             int luma[P], out[3 * P];
             load_samples<uint8_t, P, WORDS>(fy + (size_t)y * src.pitch_y + x0, luma);
@@ -90,12 +101,27 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
             for (int px = 0; px < P; ++px) {
                 const int q = px >> 1;
                 int u, v;
-                if (px & 1) {
-                    u = (3 * cb[a][q] + cb[1 - a][q] + 3 * cb[a][q + 1] + cb[1 - a][q + 1] + 4) >> 3;
-                    v = (3 * cr[a][q] + cr[1 - a][q] + 3 * cr[a][q + 1] + cr[1 - a][q + 1] + 4) >> 3;
-                } else {
-                    u = (6 * cb[a][q] + 2 * cb[1 - a][q] + 4) >> 3;
-                    v = (6 * cr[a][q] + 2 * cr[1 - a][q] + 4) >> 3;
+                if constexpr (S == 0) {
+                    if (px & 1) {
+                        u = (3 * cb[a][q] + cb[1 - a][q] + 3 * cb[a][q + 1] + cb[1 - a][q + 1] + 4) >> 3;
+                        v = (3 * cr[a][q] + cr[1 - a][q] + 3 * cr[a][q + 1] + cr[1 - a][q + 1] + 4) >> 3;
+                    } else {
+                        u = (6 * cb[a][q] + 2 * cb[1 - a][q] + 4) >> 3;
+                        v = (6 * cr[a][q] + 2 * cr[1 - a][q] + 4) >> 3;
+                    }
+                } else if constexpr (S == 1) {                         // 3 : 1 on both axes: near sample [q + 1], far [q + 2] | [q]
+                    const int far = px & 1 ? q + 2 : q;
+                    u = (3 * (3 * cb[a][q + 1] + cb[a][far]) + 3 * cb[1 - a][q + 1] + cb[1 - a][far] + 8) >> 4;
+                    v = (3 * (3 * cr[a][q + 1] + cr[a][far]) + 3 * cr[1 - a][q + 1] + cr[1 - a][far] + 8) >> 4;
+                } else {                                               // both axes: the sample itself | the mean of it and the next
+                    const int e = px & 1 ? q + 1 : q;
+                    if (a) {
+                        u = (cb[0][q] + cb[1][q] + cb[0][e] + cb[1][e] + 2) >> 2;
+                        v = (cr[0][q] + cr[1][q] + cr[0][e] + cr[1][e] + 2) >> 2;
+                    } else {
+                        u = (cb[0][q] + cb[0][e] + 1) >> 1;
+                        v = (cr[0][q] + cr[0][e] + 1) >> 1;
+                    }
                 }
                 u -= 128, v -= 128;
                 const int yy = c.dy * (luma[px] - c.y0) + (1 << 13);
@@ -112,10 +138,15 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
 // rows 2j, 2j + 1 by P pixels: 2 P luma samples and P/2 samples of each chroma plane - the unrounded numerators of both rows added per
 // column, then 1-2-1 across columns 2i - 1, 2i, 2i + 1 (yuv.py downsample, depth10.py downsample10).  Only the column left of the strip is
 // not its own (2i + 1 <= W - 1 always); at x = 0 it clamps onto column 0.
-template <typename T, int P, bool SEMIPLANAR>
+// S is the chroma siting (yuv.py encode_filter).  S = 0, left, is the body above: weights that sum to 8, 17 bits of shift.  S = 1, centre:
+// the box over the strip's own 2 x 2 pixels, no neighbour column, 16 bits.  S = 2, top left: 1-2-1 over the rows 2j - 1, 2j, 2j + 1 as well -
+// the lane reads row 2j - 1 (row 0 where j = 0) for its chroma numerators only, the luma of that row belongs to the strip above - 18 bits.
+template <typename T, int P, bool SEMIPLANAR, int S>
 __global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const T* __restrict__ rgb, T* __restrict__ yuv, int n, int H, int W, YuvCoef c) {
     constexpr bool WORDS = P > 2;
     constexpr int HP = P / 2, LEVELS = Depth<T>::LEVELS, SH = sizeof(T) == 2 && SEMIPLANAR ? 6 : 0;
+    constexpr int A0 = S == 2 ? -1 : 0, P0 = S == 1 ? 1 : 0;           // the first row read, relative to 2j; the first column used of [0 .. P]
+    constexpr int CS = S == 0 ? 17 : (S == 1 ? 16 : 18);               // 14 + k (yuv.py downsample)
     const int gw = W / P, hh = H >> 1, hw = W >> 1;
     const size_t plane = (size_t)H * W, total = (size_t)n * hh * gw;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
@@ -127,27 +158,34 @@ __global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const T* __restrict_
         const int x0 = g * P, xl = x0 > 0 ? x0 - 1 : 0;
         int nb[P + 1], nr[P + 1];                                      // per column, both rows: [0] the column left of the strip
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            const int y = 2 * j + a;
+        for (int a = A0; a < 2; ++a) {
+            const int y = S == 2 && 2 * j + a < 0 ? 0 : 2 * j + a;
             const T* const row = rgb + (f * H + y) * (size_t)W * 3;
             int px[3 * P + 3], luma[P];
-            px[0] = row[3 * (size_t)xl], px[1] = row[3 * (size_t)xl + 1], px[2] = row[3 * (size_t)xl + 2];
+            if constexpr (S != 1) px[0] = row[3 * (size_t)xl], px[1] = row[3 * (size_t)xl + 1], px[2] = row[3 * (size_t)xl + 2];
             load_samples<T, 3 * P, WORDS>(row + (size_t)x0 * 3, px + 3);
 #pragma unroll
-            for (int p = 0; p <= P; ++p) {
+            for (int p = P0; p <= P; ++p) {
                 const int r = px[3 * p], gg = px[3 * p + 1], b = px[3 * p + 2];
-                const int vb = c.cbr * r + c.cbg * gg + c.cbb * b, vr = c.crr * r + c.crg * gg + c.crb * b;
-                nb[p] = a ? nb[p] + vb : vb;
-                nr[p] = a ? nr[p] + vr : vr;
-                if (p) luma[p - 1] = shift_clip<14, LEVELS>(c.yr * r + c.yg * gg + c.yb * b + (c.y0 << 14) + (1 << 13));
+                int vb = c.cbr * r + c.cbg * gg + c.cbb * b, vr = c.crr * r + c.crg * gg + c.crb * b;
+                if constexpr (S == 2)
+                    if (a == 0) vb *= 2, vr *= 2;                      // (1-2-1 down the rows as well)
+                nb[p] = a > A0 ? nb[p] + vb : vb;
+                nr[p] = a > A0 ? nr[p] + vr : vr;
+                if (p && a >= 0) luma[p - 1] = shift_clip<14, LEVELS>(c.yr * r + c.yg * gg + c.yb * b + (c.y0 << 14) + (1 << 13));
             }
-            store_samples<T, P, WORDS, SH>(fr + (size_t)y * W + x0, luma);
+            if (a >= 0) store_samples<T, P, WORDS, SH>(fr + (size_t)y * W + x0, luma);
         }
         int ob[HP], orr[HP];
 #pragma unroll
-        for (int q = 0; q < HP; ++q) {                                 // the chroma offset + (S' >> 17)
-            ob[q] = shift_clip<17, LEVELS>(nb[2 * q] + 2 * nb[2 * q + 1] + nb[2 * q + 2] + (1 << 16) + (Depth<T>::CHROMA << 17));
-            orr[q] = shift_clip<17, LEVELS>(nr[2 * q] + 2 * nr[2 * q + 1] + nr[2 * q + 2] + (1 << 16) + (Depth<T>::CHROMA << 17));
+        for (int q = 0; q < HP; ++q) {                                 // the chroma offset + (S' >> 17 | 16 | 18)
+            if constexpr (S == 1) {
+                ob[q] = shift_clip<CS, LEVELS>(nb[2 * q + 1] + nb[2 * q + 2] + (1 << (CS - 1)) + (Depth<T>::CHROMA << CS));
+                orr[q] = shift_clip<CS, LEVELS>(nr[2 * q + 1] + nr[2 * q + 2] + (1 << (CS - 1)) + (Depth<T>::CHROMA << CS));
+            } else {
+                ob[q] = shift_clip<CS, LEVELS>(nb[2 * q] + 2 * nb[2 * q + 1] + nb[2 * q + 2] + (1 << (CS - 1)) + (Depth<T>::CHROMA << CS));
+                orr[q] = shift_clip<CS, LEVELS>(nr[2 * q] + 2 * nr[2 * q + 1] + nr[2 * q + 2] + (1 << (CS - 1)) + (Depth<T>::CHROMA << CS));
+            }
         }
         if constexpr (SEMIPLANAR) {
             int pair[P];
@@ -195,16 +233,25 @@ int decode_strip_width(const YuvPlanes& p, const void* rgb, bool nv12, int W) {
 
 }  // namespace
 
-hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
-    if (!yuv_geometry_ok(src.y, rgb, n, H, W) || !src.cb || (!nv12 && !src.cr)) return hipErrorInvalidValue;
+hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting,
+                                          hipStream_t s) {
+    if (!yuv_geometry_ok(src.y, rgb, n, H, W) || !src.cb || (!nv12 && !src.cr) || siting < 0 || siting > 2) return hipErrorInvalidValue;
     if (src.pitch_y < (size_t)W || src.pitch_cb < (size_t)(nv12 ? W : W / 2) || (!nv12 && src.pitch_cr < (size_t)(W / 2))) return hipErrorInvalidValue;
     const int P = decode_strip_width(src, rgb, nv12, W);
-    const dim3 grid(strip_blocks((size_t)n * (H / 2 + 1) * (W / P))), block(256);
-#define PFNL_YUV_LAUNCH(P_)                                                                                        \
+    const dim3 grid(strip_blocks((size_t)n * (siting == 2 ? H / 2 : H / 2 + 1) * (W / P))), block(256);
+#define PFNL_YUV_LAUNCH_S(P_, S_)                                                                                  \
     if (nv12)                                                                                                      \
-        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, true>), grid, block, 0, s, src, rgb, n, H, W, c);          \
+        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, true, S_>), grid, block, 0, s, src, rgb, n, H, W, c);      \
     else                                                                                                           \
-        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, false>), grid, block, 0, s, src, rgb, n, H, W, c)
+        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, false, S_>), grid, block, 0, s, src, rgb, n, H, W, c)
+#define PFNL_YUV_LAUNCH(P_)                                                                                        \
+    if (siting == 0) {                                                                                             \
+        PFNL_YUV_LAUNCH_S(P_, 0);                                                                                  \
+    } else if (siting == 1) {                                                                                      \
+        PFNL_YUV_LAUNCH_S(P_, 1);                                                                                  \
+    } else {                                                                                                       \
+        PFNL_YUV_LAUNCH_S(P_, 2);                                                                                  \
+    }
     if (P == 16) {
         PFNL_YUV_LAUNCH(16);
     } else if (P == 4) {
@@ -213,30 +260,39 @@ hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bo
         PFNL_YUV_LAUNCH(2);
     }
 #undef PFNL_YUV_LAUNCH
+#undef PFNL_YUV_LAUNCH_S
     return hipGetLastError();
 }
 
 // the packed frames as planes: the same kernel, the same strip width as ever
-hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
     if (!yuv_geometry_ok(yuv, rgb, n, H, W)) return hipErrorInvalidValue;
     const size_t plane = (size_t)H * W, hw = (size_t)W / 2;
     const YuvPlanes src{yuv, yuv + plane, nv12 ? nullptr : yuv + plane + plane / 4, (size_t)W, nv12 ? (size_t)W : hw, nv12 ? 0 : hw, plane + plane / 2};
-    return launch_yuv420_planes_to_rgb_u8(src, rgb, nv12, c, n, H, W, s);
+    return launch_yuv420_planes_to_rgb_u8(src, rgb, nv12, c, n, H, W, siting, s);
 }
 
 namespace {
 
 template <typename T>
-hipError_t launch_encode(const T* rgb, T* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
+hipError_t launch_encode(const T* rgb, T* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
     const uintptr_t align = reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(yuv);
-    if (!yuv_geometry_ok(rgb, yuv, n, H, W) || align % sizeof(T)) return hipErrorInvalidValue;
+    if (!yuv_geometry_ok(rgb, yuv, n, H, W) || align % sizeof(T) || siting < 0 || siting > 2) return hipErrorInvalidValue;
     const int P = strip_width<T>(align, W);
     const dim3 grid(strip_blocks((size_t)n * (H / 2) * (W / P))), block(256);
-#define PFNL_YUV_LAUNCH(P_)                                                                                        \
+#define PFNL_YUV_LAUNCH_S(P_, S_)                                                                                  \
     if (semiplanar)                                                                                                \
-        hipLaunchKernelGGL((rgb_to_yuv420_kernel<T, P_, true>), grid, block, 0, s, rgb, yuv, n, H, W, c);          \
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<T, P_, true, S_>), grid, block, 0, s, rgb, yuv, n, H, W, c);      \
     else                                                                                                           \
-        hipLaunchKernelGGL((rgb_to_yuv420_kernel<T, P_, false>), grid, block, 0, s, rgb, yuv, n, H, W, c)
+        hipLaunchKernelGGL((rgb_to_yuv420_kernel<T, P_, false, S_>), grid, block, 0, s, rgb, yuv, n, H, W, c)
+#define PFNL_YUV_LAUNCH(P_)                                                                                        \
+    if (siting == 0) {                                                                                             \
+        PFNL_YUV_LAUNCH_S(P_, 0);                                                                                  \
+    } else if (siting == 1) {                                                                                      \
+        PFNL_YUV_LAUNCH_S(P_, 1);                                                                                  \
+    } else {                                                                                                       \
+        PFNL_YUV_LAUNCH_S(P_, 2);                                                                                  \
+    }
     if constexpr (sizeof(T) == 1) {
         if (P == 16) {
             PFNL_YUV_LAUNCH(16);
@@ -253,17 +309,18 @@ hipError_t launch_encode(const T* rgb, T* yuv, bool semiplanar, const YuvCoef& c
         }
     }
 #undef PFNL_YUV_LAUNCH
+#undef PFNL_YUV_LAUNCH_S
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
-    return launch_encode<uint8_t>(rgb, yuv, nv12, c, n, H, W, s);
+hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
+    return launch_encode<uint8_t>(rgb, yuv, nv12, c, n, H, W, siting, s);
 }
 
-hipError_t launch_rgb_to_yuv420(const uint16_t* rgb, uint16_t* yuv, bool p010, const YuvCoef& c, int n, int H, int W, hipStream_t s) {
-    return launch_encode<uint16_t>(rgb, yuv, p010, c, n, H, W, s);
+hipError_t launch_rgb_to_yuv420(const uint16_t* rgb, uint16_t* yuv, bool p010, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
+    return launch_encode<uint16_t>(rgb, yuv, p010, c, n, H, W, siting, s);
 }
 
 }  // namespace pfnl

@@ -14,12 +14,14 @@ quantise, pfnl_amd/resize.py, pfnl_amd/yuv.py) with the wider sample:
 * ``from_rgb10``: the construction of yuv.coefficients with the 10-bit ranges - limited: 64 .. 940 luma (ys = 876 / 1023), 64 .. 960 chroma
   (cs = 896 / 1023); full: 0 .. 1023 - Y = clip((yr R + yg G + yb B + (y0 << 14) + 2^13) >> 14, 0, 1023); the chroma numerators stay
   unrounded until the 1-2-1 filter over columns 2i - 1, 2i, 2i + 1 (clamped) of both luma rows has summed them, then
-  clip(512 + ((S + 2^16) >> 17), 0, 1023): chroma sited left, as yuv.downsample.  |S| + (512 << 17) + 2^16 < 2^31.
+  clip(512 + ((S + 2^16) >> 17), 0, 1023): chroma sited left, as yuv.downsample.  |S| + (512 << 17) + 2^16 < 2^31.  With another
+  ``siting`` (yuv.SITINGS) the filter is yuv.encode_filter's and the rounding (S + 2^(13 + k)) >> (14 + k), k = 2 for "center" and 4 for
+  "topleft": |S| <= 1023 * 2^14 * 16 stays below 2^31 with the offset and the rounding term.
 
 Layouts (tightly packed, H * W * 3 / 2 samples, H and W even): ``p010`` = Y [H][W], CbCr [H/2][W/2][2], every sample value << 6 (the low six
 bits zero); ``i010`` (yuv420p10le) = Y, Cb [H/2][W/2], Cr [H/2][W/2], every sample the value itself; ``rgb10`` = [H][W][3], values 0 .. 1023.
 
-Out of scope: 10-bit input, BT.2020 and transfer functions, 12 and 16 bits, 4:2:2 / 4:4:4, pitched planes.
+Out of scope: 10-bit input, BT.2020 and transfer functions, 12 and 16 bits, 4:2:2 / 4:4:4, pitched planes, sitings other than yuv.SITINGS.
 """
 from __future__ import annotations
 
@@ -116,15 +118,12 @@ def pack10(Y, Cb, Cr, fmt: str):
     return (np.concatenate([Y.reshape(-1), c.reshape(-1)]) << SHIFT[fmt]).astype(np.uint16).reshape(H * 3 // 2, W)
 
 
-def downsample10(N):
-    """Chroma numerators [H,W] (14 fractional bits, unrounded) -> the plane [H/2, W/2] of values: 1-2-1 over two rows, one rounding."""
-    N = np.asarray(N, np.int64)
-    H, W = N.shape
-    v = N[0::2] + N[1::2]                                               # [H/2, W]
-    c = np.arange(0, W, 2)
-    s = v[:, np.clip(c - 1, 0, W - 1)] + 2 * v[:, c] + v[:, np.clip(c + 1, 0, W - 1)]
-    assert np.abs(s).max() + (512 << (F + 3)) + (1 << (F + 2)) < (1 << 31)
-    return np.clip(512 + ((s + (1 << (F + 2))) >> (F + 3)), 0, MAXV).astype(np.uint16)
+def downsample10(N, siting="left"):
+    """Chroma numerators [H,W] (14 fractional bits, unrounded) -> the plane [H/2, W/2] of values: the siting's filter (left: 1-2-1 over two
+    rows), one rounding."""
+    s, k = _yuv.encode_filter(np.asarray(N, np.int64), siting)
+    assert np.abs(s).max() + (512 << (F + k)) + (1 << (F + k - 1)) < (1 << 31)
+    return np.clip(512 + ((s + (1 << (F + k - 1))) >> (F + k)), 0, MAXV).astype(np.uint16)
 
 
 def _check_rgb10(rgb10):
@@ -136,7 +135,7 @@ def _check_rgb10(rgb10):
     return rgb10
 
 
-def from_rgb10(rgb10, fmt: str, matrix: str = "bt709", full_range=False):
+def from_rgb10(rgb10, fmt: str, matrix: str = "bt709", full_range=False, siting="left"):
     """[H,W,3] uint16 with values <= 1023 -> one packed frame [H*3/2, W] uint16 in ``fmt``."""
     rgb10 = _check_rgb10(rgb10)
     H, W = rgb10.shape[:2]
@@ -144,8 +143,8 @@ def from_rgb10(rgb10, fmt: str, matrix: str = "bt709", full_range=False):
     y0, (yr, yg, yb, cbr, cbg, cbb, crr, crg, crb) = coefficients10(matrix, full_range)
     r, g, b = (rgb10[..., k].astype(np.int64) for k in range(3))
     Y = np.clip((yr * r + yg * g + yb * b + (y0 << F) + HALF) >> F, 0, MAXV)
-    Cb = downsample10(cbr * r + cbg * g + cbb * b)
-    Cr = downsample10(crr * r + crg * g + crb * b)
+    Cb = downsample10(cbr * r + cbg * g + cbb * b, siting)
+    Cr = downsample10(crr * r + crg * g + crb * b, siting)
     return pack10(Y, Cb, Cr, fmt)
 
 

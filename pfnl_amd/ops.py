@@ -593,12 +593,20 @@ def _yuv_ids(fmt, matrix, full_range):
     return _capi.PIXEL_FORMATS[fmt], _capi.YUV_MATRICES[matrix], int(bool(full_range))
 
 
-def yuv420_to_rgb(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None):
+def _siting_id(siting):
+    if siting not in _capi.CHROMA_SITINGS:
+        raise ValueError(f"siting: one of {sorted(_capi.CHROMA_SITINGS)}, got {siting!r}")
+    return _capi.CHROMA_SITINGS[siting]
+
+
+def yuv420_to_rgb(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None, siting="left"):
     """n tightly packed NV12 / I420 frames, a uint8 tensor (cuda) of n * H*W*3/2 elements in any shape -> [n,H,W,3] uint8, byte for byte
-    pfnl_amd/yuv.py to_rgb (pfnl_op_yuv420_to_rgb_u8: the streaming session's input edge).  Any alignment; ``out``: write there."""
+    pfnl_amd/yuv.py to_rgb (pfnl_op_yuv420_to_rgb_u8_sited: the streaming session's input edge).  Any alignment; ``out``: write there;
+    ``siting``: "left" | "center" | "topleft"."""
     import torch
     lib = _capi.load_library()
     ids = _yuv_ids(fmt, matrix, full_range)
+    sid = _siting_id(siting)
     src = _req_u8(frames, "frames")
     if H < 2 or W < 2 or H % 2 or W % 2:
         raise ValueError(f"H and W must be even and at least 2, got {H} x {W}")
@@ -610,19 +618,20 @@ def yuv420_to_rgb(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_
         out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=frames.device)
     elif out.numel() != n * H * W * 3 or out.device != frames.device:
         raise ValueError("out must hold n * H * W * 3 bytes on the frames' device")
-    _capi.check(lib.pfnl_op_yuv420_to_rgb_u8(src, ids[0], ids[1], ids[2], n, H, W, _req_u8(out, "out"), _stream(frames)))
+    _capi.check(lib.pfnl_op_yuv420_to_rgb_u8_sited(src, ids[0], ids[1], ids[2], n, H, W, _req_u8(out, "out"), sid, _stream(frames)))
     return out.view(n, H, W, 3)
 
 
-def yuv420_to_rgb_surface(planes, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None):
+def yuv420_to_rgb_surface(planes, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None, siting="left"):
     """One NV12 / I420 frame given as its planes - uint8 tensors (cuda), each a strided view with a row pitch of its own, as
     pfnl_amd/surface.py describes them: typically ``surface[:H, :W]`` of a decoder's pitched allocation -> [H,W,3] uint8, byte for byte
     pfnl_amd/yuv.py to_rgb of the packed frame (pfnl_op_yuv420_to_rgb_u8_surface: the kernel a device push_planes runs).  Any pointer and
-    any pitch; ``out``: write there."""
+    any pitch; ``out``: write there; ``siting`` as for yuv420_to_rgb."""
     import torch
     from . import surface as _surface
     lib = _capi.load_library()
     ids = _yuv_ids(fmt, matrix, full_range)
+    sid = _siting_id(siting)
     planes = tuple(planes)
     for k, p in enumerate(planes):
         if not (isinstance(p, torch.Tensor) and p.is_cuda and p.device == planes[0].device):
@@ -634,16 +643,19 @@ def yuv420_to_rgb_surface(planes, fmt: str, H: int, W: int, matrix: str = "bt709
         out = torch.empty((H, W, 3), dtype=torch.uint8, device=planes[0].device)
     elif out.numel() != H * W * 3 or out.device != planes[0].device:
         raise ValueError("out must hold H * W * 3 bytes on the planes' device")
-    _capi.check(lib.pfnl_op_yuv420_to_rgb_u8_surface(C.byref(sf), ids[0], ids[1], ids[2], H, W, _req_u8(out, "out"), _stream(planes[0])))
+    _capi.check(lib.pfnl_op_yuv420_to_rgb_u8_surface_sited(C.byref(sf), ids[0], ids[1], ids[2], H, W, _req_u8(out, "out"), sid,
+                                                           _stream(planes[0])))
     return out.view(H, W, 3)
 
 
-def rgb_to_yuv420(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None):
+def rgb_to_yuv420(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None, siting="left"):
     """[n,H,W,3] (or [H,W,3]) uint8 (cuda) -> [n, H*3/2, W] uint8: tightly packed NV12 / I420 frames, byte for byte pfnl_amd/yuv.py from_rgb
-    (pfnl_op_rgb_to_yuv420_u8: the streaming session's output edge).  H, W even; any alignment; ``out``: write there."""
+    (pfnl_op_rgb_to_yuv420_u8_sited: the streaming session's output edge).  H, W even; any alignment; ``out``: write there; ``siting``:
+    "left" | "center" | "topleft"."""
     import torch
     lib = _capi.load_library()
     ids = _yuv_ids(fmt, matrix, full_range)
+    sid = _siting_id(siting)
     src = _req_u8(frames, "frames")
     if frames.dim() == 3:
         frames = frames[None]
@@ -656,7 +668,7 @@ def rgb_to_yuv420(frames, fmt: str, matrix: str = "bt709", full_range=False, out
         out = torch.empty((n, H * 3 // 2, W), dtype=torch.uint8, device=frames.device)
     elif out.numel() != n * H * W * 3 // 2 or out.device != frames.device:
         raise ValueError("out must hold n * H * W * 3 / 2 bytes on the frames' device")
-    _capi.check(lib.pfnl_op_rgb_to_yuv420_u8(src, ids[0], ids[1], ids[2], n, H, W, _req_u8(out, "out"), _stream(frames)))
+    _capi.check(lib.pfnl_op_rgb_to_yuv420_u8_sited(src, ids[0], ids[1], ids[2], n, H, W, _req_u8(out, "out"), sid, _stream(frames)))
     return out.view(n, H * 3 // 2, W)
 
 
@@ -712,12 +724,13 @@ def quantise_u10(sr):
     return out
 
 
-def rgb_to_yuv420_u10(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None):
+def rgb_to_yuv420_u10(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None, siting="left"):
     """[n,H,W,3] (or [H,W,3]) uint16 (cuda) with values 0 .. 1023 -> [n, H*3/2, W] uint16: tightly packed P010 / I010 frames, sample for
     sample pfnl_amd/depth10.py from_rgb10 (pfnl_op_rgb_to_yuv420_u10: the streaming session's 10-bit output edge).  H, W even; any
-    alignment; ``out``: write there."""
+    alignment; ``out``: write there; ``siting`` as for rgb_to_yuv420."""
     import torch
     lib = _capi.load_library()
+    sid = _siting_id(siting)
     if fmt not in ("p010", "i010"):
         raise ValueError(f'fmt: "p010" or "i010", got {fmt!r}')
     if matrix not in _capi.YUV_MATRICES:
@@ -734,8 +747,8 @@ def rgb_to_yuv420_u10(frames, fmt: str, matrix: str = "bt709", full_range=False,
         out = torch.empty((n, H * 3 // 2, W), dtype=torch.uint16, device=frames.device)
     elif out.numel() != n * H * W * 3 // 2 or out.device != frames.device:
         raise ValueError("out must hold n * H * W * 3 / 2 samples on the frames' device")
-    _capi.check(lib.pfnl_op_rgb_to_yuv420_u10(src, _capi.PIXEL_FORMATS[fmt], _capi.YUV_MATRICES[matrix], int(bool(full_range)), n, H, W,
-                                              _req_u16(out, "out"), _stream(frames)))
+    _capi.check(lib.pfnl_op_rgb_to_yuv420_u10_sited(src, _capi.PIXEL_FORMATS[fmt], _capi.YUV_MATRICES[matrix], int(bool(full_range)), n, H, W,
+                                                    _req_u16(out, "out"), sid, _stream(frames)))
     return out.view(n, H * 3 // 2, W)
 
 

@@ -18,7 +18,8 @@ then stay inside its scene, and ``vs.cuts`` lists the delivered frames that star
 YUV 4:2:0 (off by default): ``open_stream(H, W, batch, pixel_format="nv12")`` takes frames as a decoder delivers them - ``(H*3//2, W)``
 uint8, or flat - and returns SR frames ``(sH*3//2, sW)`` for an encoder; ``"i420"`` likewise; ``out_format`` sets the two sides apart
 (``"rgb24"`` among them).  The conversion runs on the device at the two edges of the session, by the integer rule of pfnl_amd/yuv.py
-(``matrix`` "bt601" | "bt709", ``full_range``; chroma sited left); the ring, the scenes and the windows go on seeing RGB.
+(``matrix`` "bt601" | "bt709", ``full_range``; chroma sited left, or where ``chroma_siting`` / ``out_chroma_siting`` say: "center" is what
+JPEG and a Y4M stream's default ``C420jpeg`` mean, "topleft" UHD HEVC and ``C420paldv``); the ring, the scenes and the windows go on seeing RGB.
 
 Output size (off by default): ``open_stream(H, W, batch, out_size=(1080, 1920))`` delivers every frame at that raster - ``(oH, oW, 3)``, or
 ``(oH*3//2, oW)`` in a 4:2:0 output format (then both even) - resampled on the device behind the quantisation and ahead of the YUV conversion by
@@ -76,6 +77,17 @@ def format_arguments(pixel_format="rgb24", out_format=None, matrix="bt709", full
     if full_range not in (False, True, 0, 1):
         raise ValueError(f"full_range: False or True, got {full_range!r}")
     return _capi.PIXEL_FORMATS[pixel_format], _capi.PIXEL_FORMATS[out_format], _capi.YUV_MATRICES[matrix], int(bool(full_range))
+
+
+def siting_arguments(chroma_siting="left", out_chroma_siting=None) -> Tuple[int, int]:
+    """The two arguments of pfnl_stream_chroma_siting for open_stream's keywords (``out_chroma_siting`` None = ``chroma_siting``);
+    ValueError for anything the library would refuse.  Needs no device."""
+    if out_chroma_siting is None:
+        out_chroma_siting = chroma_siting
+    for name, value in (("chroma_siting", chroma_siting), ("out_chroma_siting", out_chroma_siting)):
+        if not isinstance(value, str) or value not in _capi.CHROMA_SITINGS:
+            raise ValueError(f"{name}: one of {sorted(_capi.CHROMA_SITINGS)}, got {value!r}")
+    return _capi.CHROMA_SITINGS[chroma_siting], _capi.CHROMA_SITINGS[out_chroma_siting]
 
 
 def resize_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24") -> Tuple[int, int]:
@@ -187,13 +199,19 @@ class VideoStream:
 
     ``ensemble`` (1 | 2 | 4 | 8): every batch's forward as a geometric self-ensemble of that many members (pfnl_amd/ensemble.py); 1 is off.
 
+    ``chroma_siting`` / ``out_chroma_siting`` ("left" | "center" | "topleft"; ``out_chroma_siting`` None = the same): where the chroma
+    samples of a 4:2:0 ``pixel_format`` / ``out_format`` sit (pfnl_amd/yuv.py SITINGS); an RGB side ignores its siting.
+
     ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
     (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
-                 full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0), ensemble=1):
+                 full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
+                 chroma_siting="left", out_chroma_siting=None, ensemble=1):
         import torch
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
+        sit = siting_arguments(chroma_siting, out_chroma_siting)
+        self.chroma_siting, self.out_chroma_siting = chroma_siting, chroma_siting if out_chroma_siting is None else out_chroma_siting
         self.ensemble = ensemble_argument(ensemble)
         self.pixel_format, self.out_format = pixel_format, pixel_format if out_format is None else out_format
         oH, oW, self.crop, self.place, self.fill = placement_arguments(out_size, engine.geom.scale * int(H), engine.geom.scale * int(W),
@@ -230,6 +248,12 @@ class VideoStream:
         if fmt[0] or fmt[1]:                        # (all defaults: the session as it always was, and no call)
             try:
                 _capi.check(self._lib.pfnl_stream_format(s, *fmt))
+            except Exception:
+                self.close()
+                raise
+        if sit[0] or sit[1]:                        # (left on both sides: the session as it always was, and no call)
+            try:
+                _capi.check(self._lib.pfnl_stream_chroma_siting(s, *sit))
             except Exception:
                 self.close()
                 raise

@@ -1,0 +1,175 @@
+"""``python -m pfnl_amd.upscale IN OUT``: a Y4M stream through the streaming session, end to end.
+
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m pfnl_amd.upscale --checkpoint DIR - - | ffmpeg -f yuv4mpegpipe -i - out.mkv
+
+The stream's header (pfnl_amd/y4m.py) names the raster, the chroma siting, the range and the sample aspect ratio; the frames are the
+session's ``i420`` frames as they are, converted on the device with that siting (pfnl_amd/yuv.py), and what the session delivers is written
+as ``i420`` - or ``i010`` with ``--bits 10`` - under a header of the output's raster, siting and aspect.  Y4M carries no matrix: ``--matrix
+auto`` takes BT.601 up to 576 lines and BT.709 above.  ``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+
+from . import y4m as _y4m
+
+OUT_FORMATS = {8: "i420", 10: "i010"}
+
+
+def auto_matrix(height: int) -> str:
+    """What a stream without a matrix tag is taken to be: BT.601 up to 576 lines (SD), BT.709 above."""
+    return "bt601" if height <= 576 else "bt709"
+
+
+def session_keywords(header, **session_kw) -> dict:
+    """``open_stream``'s keywords for a stream with this header: the caller's (``batch``, ``scene_cut``, ``out_format`` "i420" | "i010",
+    ``out_size``, ``fit``, ``out_chroma_siting``, ``ensemble``, ``matrix`` with "auto", ``full_range`` True to override the header), and from the
+    header the input siting, the range, and - with ``fit`` alone - the sample aspect ratio.  ValueError for what a Y4M stream cannot hold."""
+    kw = dict(session_kw)
+    for fixed in ("pixel_format", "chroma_siting", "sar"):
+        if fixed in kw:
+            raise ValueError(f"{fixed} comes from the stream's header")
+    kw.setdefault("batch", 1)
+    if kw.get("out_format") is None:
+        kw["out_format"] = "i420"
+    if kw["out_format"] not in OUT_FORMATS.values():
+        raise ValueError(f"out_format: a Y4M stream holds {sorted(OUT_FORMATS.values())}, got {kw['out_format']!r}")
+    if kw.get("matrix", "auto") == "auto":
+        kw["matrix"] = auto_matrix(header.height)
+    kw["full_range"] = bool(kw.get("full_range")) or header.full_range
+    kw["pixel_format"] = "i420"
+    kw["chroma_siting"] = header.siting
+    if kw.get("fit") is not None:
+        kw["sar"] = header.sar
+    return kw
+
+
+def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> int:
+    """Every frame of ``reader`` (y4m.Y4MReader) through a session, into ``writer`` (y4m.Y4MWriter); returns the frame count.
+    ``open_stream`` is ``PFNLEngine.open_stream`` or anything with its keywords; ``session_kw`` as ``session_keywords`` takes them;
+    ``tile`` is ``set_tiling``'s arguments.  The output header is written once the session exists - its raster, siting and aspect are the
+    session's - and frames in index order as ``push`` and ``end`` return them.  One line with frames, seconds and fps goes to ``log``."""
+    header = reader.header
+    kw = session_keywords(header, **session_kw)
+    batch = kw.pop("batch")
+    t0 = time.perf_counter()
+    done = 0
+    with open_stream(header.height, header.width, batch, **kw) as vs:
+        if tile is not None:
+            vs.set_tiling(*tile)
+        out_h, out_w = vs.out_size if vs.out_size is not None else (vs.scale * header.height, vs.scale * header.width)
+        writer.write_header(header.for_output(out_w, out_h, siting=vs.out_chroma_siting, bits=10 if kw["out_format"] == "i010" else 8,
+                                              sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw["full_range"]))
+
+        def deliver(frames):
+            nonlocal done
+            for index, frame in frames:
+                if index != done:
+                    raise RuntimeError(f"frame {index} delivered where {done} was due")
+                writer.write_frame(frame)
+                done += 1
+
+        for frame in reader:
+            deliver(vs.push(frame))
+        deliver(vs.end())
+    if done != reader.frames:
+        raise RuntimeError(f"{reader.frames} frames read, {done} delivered")
+    seconds = time.perf_counter() - t0
+    print(f"pfnl_amd.upscale: {done} frames in {seconds:.2f} s ({done / seconds if seconds > 0 else 0.0:.2f} fps)",
+          file=sys.stderr if log is None else log)
+    return done
+
+
+def _size(text):
+    try:
+        h, w = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"HxW, got {text!r}") from None
+    return h, w
+
+
+def _tile(text):
+    try:
+        t = tuple(int(v) for v in text.split(","))
+    except ValueError:
+        t = ()
+    if not 2 <= len(t) <= 4:
+        raise argparse.ArgumentTypeError(f"TH,TW[,PAD[,BATCH]], got {text!r}")
+    return t
+
+
+def _scene_cut(text):
+    if text == "manual":
+        raise argparse.ArgumentTypeError("a Y4M stream carries no cut marks: give the detector's threshold")
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a threshold in (0, 255], got {text!r}") from None
+
+
+def parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m pfnl_amd.upscale", description="Upscale a Y4M stream 4x with PFNL on the GPU.")
+    ap.add_argument("input", metavar="IN", help="a Y4M file, or - for stdin")
+    ap.add_argument("output", metavar="OUT", help="the Y4M file to write, or - for stdout")
+    w = ap.add_mutually_exclusive_group(required=True)
+    w.add_argument("--checkpoint", metavar="DIR", help="the directory of a trained checkpoint")
+    w.add_argument("--synthetic-weights", metavar="SEED", type=int, help="seeded random weights (for trying the pipeline)")
+    ap.add_argument("--num-block", type=int, default=20)
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto", help="auto: bt601 up to 576 lines, else bt709")
+    ap.add_argument("--full-range", action="store_true", help="full-range samples whatever the header says")
+    ap.add_argument("--batch", type=int, default=1, help="windows per forward")
+    ap.add_argument("--scene-cut", type=_scene_cut, default=None, metavar="THRESHOLD", help="keep windows inside a scene: the cut detector's threshold")
+    ap.add_argument("--bits", type=int, choices=(8, 10), default=8, help="10: yuv420p10le out")
+    ap.add_argument("--out-size", type=_size, default=None, metavar="HxW")
+    ap.add_argument("--fit", choices=("contain", "cover"), default=None, help="keep the aspect ratio on the --out-size canvas")
+    ap.add_argument("--out-siting", choices=("left", "center", "topleft"), default=None, help="the output's chroma siting (default: the input's)")
+    ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1)
+    ap.add_argument("--tile", type=_tile, default=None, metavar="TH,TW[,PAD[,BATCH]]")
+    return ap
+
+
+def main(argv=None) -> int:
+    a = parser().parse_args(argv)
+    from ._capi import PFNLHipError
+    fin = sys.stdin.buffer if a.input == "-" else open(a.input, "rb")
+    fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
+    eng = None
+    try:
+        reader = _y4m.Y4MReader(fin)
+        from . import checkpoint, synth
+        from .engine import PFNLEngine
+        from .spec import PFNLGeometry
+        geom = PFNLGeometry(num_block=a.num_block)
+        if a.checkpoint is not None:
+            found = checkpoint.load_checkpoint(a.checkpoint, geom)
+            if found is None:
+                raise ValueError(f"no checkpoint in {a.checkpoint!r}")
+            weights = found[1]
+        else:
+            weights = synth.synthetic_weights(geom, seed=a.synthetic_weights)
+        eng = PFNLEngine(geom, device=0)
+        eng.load_weights(weights)
+        if a.precision != "fp32":
+            eng.set_option("precision", a.precision)
+        upscale(reader, _y4m.Y4MWriter(fout), eng.open_stream, tile=a.tile, batch=a.batch, scene_cut=a.scene_cut, matrix=a.matrix,
+                full_range=a.full_range, out_format=OUT_FORMATS[a.bits], out_size=a.out_size, fit=a.fit, out_chroma_siting=a.out_siting,
+                ensemble=a.ensemble)
+        fout.flush()
+    except (ValueError, PFNLHipError) as e:
+        print(f"pfnl_amd.upscale: {e}", file=sys.stderr)
+        return 1
+    finally:
+        if eng is not None:
+            eng.close()
+        if fin is not sys.stdin.buffer:
+            fin.close()
+        if fout is not sys.stdout.buffer:
+            fout.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,238 @@
+"""YUV4MPEG2 (Y4M) streams, 4:2:0 (numpy only; no device): what ``ffmpeg -f yuv4mpegpipe`` writes and reads.
+
+A stream is one header line and, per frame, a ``FRAME`` line followed by the planes Y [H][W], Cb [H/2][W/2], Cr [H/2][W/2] - exactly the
+streaming session's tightly packed ``i420`` frame (pfnl_amd/yuv.py), so ``Y4MReader`` yields ``(H*3//2, W)`` uint8 arrays that
+``VideoStream.push`` takes as they are, and ``Y4MWriter`` takes what ``pop`` returns (``i010`` at 10 bits: little-endian uint16 samples).
+
+The header is ``YUV4MPEG2`` and space-separated tokens up to the newline:
+
+* ``W``, ``H``: the raster, required, both even (4:2:0);
+* ``F n:d``: the frame rate, kept verbatim; ``X...``: extensions, kept verbatim, ``XCOLORRANGE=FULL|LIMITED`` setting the range;
+* ``I``: ``p`` (progressive) and ``?`` (unknown) are accepted; ``t``, ``b``, ``m`` are refused - the network is no deinterlacer;
+* ``A n:d``: the sample aspect ratio, ``0:0`` (unknown) or absent = (1, 1);
+* ``C``: absent, ``420jpeg`` and bare ``420`` = chroma sited "center"; ``420mpeg2`` = "left"; ``420paldv`` = "topleft" (pfnl_amd/yuv.py
+  SITINGS); any other tag (``422``, ``444``, ``mono``, ``420p10``, ...) is a ValueError that names it.
+
+Out of scope: 4:2:2 / 4:4:4 / mono, input above 8 bits, interlaced streams, per-frame parameters (they are read and dropped).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, replace
+from typing import Iterator, Optional, Tuple
+
+import numpy as np
+
+MAGIC = b"YUV4MPEG2"
+MAX_LINE = 4096                                                         # a header or frame line longer than this is not Y4M
+SITING_OF_TAG = {"420jpeg": "center", "420": "center", "420mpeg2": "left", "420paldv": "topleft"}
+TAG_OF_SITING = {"center": "420jpeg", "left": "420mpeg2", "topleft": "420paldv"}
+TAG_10BIT = "420p10"
+RANGE_KEY = "XCOLORRANGE="
+
+
+def _ratio(text: str, what: str) -> Tuple[int, int]:
+    try:
+        n, d = (int(v) for v in text.split(":"))
+    except ValueError:
+        raise ValueError(f"y4m: {what} is n:d, got {text!r}") from None
+    if n < 0 or d < 0:
+        raise ValueError(f"y4m: {what} is n:d, got {text!r}")
+    return n, d
+
+
+@dataclass(frozen=True)
+class Y4MHeader:
+    """One stream's parameters.  ``rate`` and ``interlace`` are the ``F`` and ``I`` tokens' values or None where the stream has none;
+    ``extensions`` are the ``X`` tokens verbatim, in order, ``XCOLORRANGE`` among them; ``bits`` is 8, or 10 for a stream the writer makes."""
+    width: int
+    height: int
+    rate: Optional[str] = None
+    interlace: Optional[str] = None
+    sar: Tuple[int, int] = (1, 1)
+    siting: str = "center"
+    extensions: Tuple[str, ...] = ()
+    bits: int = 8
+
+    def __post_init__(self):
+        if self.width < 2 or self.height < 2 or self.width % 2 or self.height % 2:
+            raise ValueError(f"y4m: W and H must be even and at least 2 (4:2:0), got W{self.width} H{self.height}")
+        if self.interlace not in (None, "p", "?"):
+            raise ValueError(f"y4m: interlaced streams are not supported (I{self.interlace}); deinterlace first")
+        if self.siting not in TAG_OF_SITING:
+            raise ValueError(f"y4m: siting: one of {sorted(TAG_OF_SITING)}, got {self.siting!r}")
+        if self.bits not in (8, 10):
+            raise ValueError(f"y4m: bits: 8 or 10, got {self.bits!r}")
+
+    @property
+    def full_range(self) -> bool:
+        """True where the last ``XCOLORRANGE`` token says FULL; limited range otherwise."""
+        full = False
+        for x in self.extensions:
+            if x.startswith(RANGE_KEY):
+                full = x[len(RANGE_KEY):] == "FULL"
+        return full
+
+    @property
+    def frame_bytes(self) -> int:
+        return self.width * self.height * 3 // 2 * (2 if self.bits == 10 else 1)
+
+    @classmethod
+    def parse(cls, line: bytes) -> "Y4MHeader":
+        """The header of its line (without or with the newline)."""
+        try:
+            tokens = line.rstrip(b"\n").decode("ascii").split(" ")
+        except UnicodeDecodeError:
+            raise ValueError("y4m: the header is not ASCII") from None
+        if tokens[0] != MAGIC.decode():
+            raise ValueError(f"y4m: the stream does not start with {MAGIC.decode()}")
+        width = height = None
+        rate = interlace = None
+        sar, siting, ext = (1, 1), "center", []
+        for t in tokens[1:]:
+            if not t:
+                continue
+            key, value = t[0], t[1:]
+            if key in "WH":
+                try:
+                    v = int(value)
+                except ValueError:
+                    raise ValueError(f"y4m: {key} is an integer, got {t!r}") from None
+                width, height = (v, height) if key == "W" else (width, v)
+            elif key == "F":
+                _ratio(value, "F")
+                rate = value
+            elif key == "I":
+                interlace = value
+            elif key == "A":
+                sar = _ratio(value, "A")
+                if sar[0] == 0 or sar[1] == 0:
+                    sar = (1, 1)
+            elif key == "C":
+                if value not in SITING_OF_TAG:
+                    raise ValueError(f"y4m: chroma format C{value} is not supported (8-bit 4:2:0: {', '.join('C' + k for k in SITING_OF_TAG)})")
+                siting = SITING_OF_TAG[value]
+            elif key == "X":
+                if t.startswith(RANGE_KEY) and t[len(RANGE_KEY):] not in ("FULL", "LIMITED"):
+                    raise ValueError(f"y4m: {RANGE_KEY}FULL or {RANGE_KEY}LIMITED, got {t!r}")
+                ext.append(t)
+            else:
+                raise ValueError(f"y4m: unknown header token {t!r}")
+        if width is None or height is None:
+            raise ValueError("y4m: the header needs W and H")
+        return cls(width, height, rate, interlace, sar, siting, tuple(ext), 8)
+
+    def to_bytes(self) -> bytes:
+        """The header line, newline included: W H F I A C, then the extensions."""
+        t = [MAGIC.decode(), f"W{self.width}", f"H{self.height}"]
+        if self.rate is not None:
+            t.append("F" + self.rate)
+        if self.interlace is not None:
+            t.append("I" + self.interlace)
+        t.append(f"A{self.sar[0]}:{self.sar[1]}")
+        t.append("C" + (TAG_10BIT if self.bits == 10 else TAG_OF_SITING[self.siting]))
+        t += list(self.extensions)
+        return (" ".join(t) + "\n").encode("ascii")
+
+    def for_output(self, width: int, height: int, siting: Optional[str] = None, bits: int = 8, sar: Optional[Tuple[int, int]] = None,
+                   full_range: Optional[bool] = None) -> "Y4MHeader":
+        """The header of the stream made from this one: the new raster, siting, depth and aspect; ``F``, ``I`` and the extensions pass
+        through - but ``XYSCSS``, which restates the chroma format and becomes ``XYSCSS=420P10`` at 10 bits, and the range token where
+        ``full_range`` says otherwise than the stream."""
+        ext = [x for x in self.extensions if not x.startswith("XYSCSS=")]
+        if full_range is not None and bool(full_range) != self.full_range:
+            ext = [x for x in ext if not x.startswith(RANGE_KEY)] + [RANGE_KEY + ("FULL" if full_range else "LIMITED")]
+        if bits == 10:
+            ext.insert(0, "XYSCSS=420P10")
+        return replace(self, width=int(width), height=int(height), siting=self.siting if siting is None else siting, bits=bits,
+                       sar=self.sar if sar is None else tuple(sar), extensions=tuple(ext))
+
+
+def _read_exact(f, n: int) -> bytes:
+    """Up to n bytes, fewer only at the end of the stream: a pipe returns what it has."""
+    parts, got = [], 0
+    while got < n:
+        b = f.read(n - got)
+        if not b:
+            break
+        parts.append(b)
+        got += len(b)
+    return b"".join(parts)
+
+
+def _read_line(f) -> bytes:
+    """One line without its newline; None at the end of the stream; ValueError where the stream ends inside a line."""
+    line = bytearray()
+    while True:
+        b = f.read(1)
+        if not b:
+            if line:
+                raise ValueError("y4m: the stream ends inside a line")
+            return None
+        if b == b"\n":
+            return bytes(line)
+        line += b
+        if len(line) > MAX_LINE:
+            raise ValueError("y4m: a line without an end: not a Y4M stream")
+
+
+class Y4MReader:
+    """``Y4MReader(fileobj)`` reads the header at once (``.header``); iterating yields every frame as a ``(H*3//2, W)`` uint8 array."""
+
+    def __init__(self, fileobj):
+        self._f = fileobj
+        line = _read_line(fileobj)
+        if line is None:
+            raise ValueError("y4m: empty stream")
+        self.header = Y4MHeader.parse(line)
+        self.frames = 0
+
+    def read_frame(self):
+        """The next frame, or None at the end of the stream; ValueError for a bad frame line or a truncated frame."""
+        line = _read_line(self._f)
+        if line is None:
+            return None
+        if line != b"FRAME" and not line.startswith(b"FRAME "):
+            raise ValueError(f"y4m: frame {self.frames}: expected a FRAME line, got {line[:16]!r}")
+        h = self.header
+        data = _read_exact(self._f, h.frame_bytes)
+        if len(data) != h.frame_bytes:
+            raise ValueError(f"y4m: frame {self.frames} is truncated: {len(data)} of {h.frame_bytes} bytes")
+        self.frames += 1
+        return np.frombuffer(data, np.uint8).reshape(h.height * 3 // 2, h.width)
+
+    def __iter__(self) -> Iterator[np.ndarray]:
+        while True:
+            frame = self.read_frame()
+            if frame is None:
+                return
+            yield frame
+
+
+class Y4MWriter:
+    """``Y4MWriter(fileobj, header=None)``: ``write_header`` once (at construction where ``header`` is given), then ``write_frame`` per frame:
+    ``(H*3//2, W)`` or flat, uint8 - uint16 values 0 .. 1023 (``i010``) for a 10-bit header, written little-endian."""
+
+    def __init__(self, fileobj, header: Optional[Y4MHeader] = None):
+        self._f = fileobj
+        self.header = None
+        self.frames = 0
+        if header is not None:
+            self.write_header(header)
+
+    def write_header(self, header: Y4MHeader) -> None:
+        if self.header is not None:
+            raise ValueError("y4m: the header has been written")
+        self._f.write(header.to_bytes())
+        self.header = header
+
+    def write_frame(self, frame) -> None:
+        h = self.header
+        if h is None:
+            raise ValueError("y4m: write_header first")
+        frame = np.asarray(frame)
+        dtype = np.uint16 if h.bits == 10 else np.uint8
+        if frame.dtype != dtype or frame.size != h.width * h.height * 3 // 2:
+            raise ValueError(f"y4m: expected {h.width * h.height * 3 // 2} {np.dtype(dtype).name} samples, got {frame.dtype} x {frame.size}")
+        self._f.write(b"FRAME\n")
+        self._f.write(np.ascontiguousarray(frame).astype("<u2" if h.bits == 10 else np.uint8, copy=False).tobytes())
+        self.frames += 1

@@ -6,11 +6,17 @@ the rule its kernels are tested against, byte for byte.  Everything after the co
 * F = 14 fractional bits, ONE = 1 << 14, rnd(x) = floor(x * ONE + 0.5); every coefficient is computed in double precision and rounded once,
   the third of each encode row is derived from the other two - greys have zero chroma and white is y0 + round(255 ys) exactly;
 * frames are tightly packed, H * W * 3 / 2 bytes, H and W even: ``nv12`` = Y [H][W], CbCr [H/2][W/2][2]; ``i420`` = Y, Cb [H/2][W/2], Cr;
-* chroma is sited left (H.264 / HEVC type 0): on the even luma columns, midway between the two luma rows.  YUV -> RGB interpolates it
-  with the weights 3 : 1 vertically (near row : far row) and 1 : 1 between two samples on odd columns, indices clamped to the plane; RGB ->
-  YUV filters the unrounded chroma numerators with 1-2-1 over the two luma rows, columns clamped, and rounds once.
+* chroma is sited left by default (H.264 / HEVC type 0): on the even luma columns, midway between the two luma rows.  YUV -> RGB
+  interpolates it with the weights 3 : 1 vertically (near row : far row) and 1 : 1 between two samples on odd columns, indices clamped to
+  the plane; RGB -> YUV filters the unrounded chroma numerators with 1-2-1 over the two luma rows, columns clamped, and rounds once;
+* ``siting`` names where chroma sample (j, i) sits in luma coordinates (row, column): "left" (2j + 1/2, 2i), "center" (2j + 1/2, 2i + 1/2;
+  JPEG / MPEG-1, Y4M's C420jpeg), "topleft" (2j, 2i; HEVC type 2, C420paldv).  Per axis a siting is midway or co-sited (AXES).  Decode: two
+  taps per axis in quarters, indices clamped - midway: near = j, far = j + 1 on odd and j - 1 on even luma indices, 3 : 1; co-sited: near =
+  j, far = j + 1, 4 : 0 on even and 2 : 2 on odd indices - and (sum wy wx C + 8) >> 4.  Encode: per axis a box over 2j, 2j + 1 (midway, k =
+  1) or 1-2-1 over 2j - 1, 2j, 2j + 1 (co-sited, k = 2), indices clamped, and one rounding by F + k bits, k summed over both axes.
 
-Out of scope: pitched planes, 10-bit input (10-bit output is pfnl_amd/depth10.py), 4:2:2 / 4:4:4, other sitings, transfer functions, BT.2020.
+Out of scope: pitched planes, 10-bit input (10-bit output is pfnl_amd/depth10.py), 4:2:2 / 4:4:4, sitings other than these three (HEVC types
+1, 3, 4, 5), transfer functions, BT.2020.
 """
 from __future__ import annotations
 
@@ -23,6 +29,8 @@ F = 14
 ONE = 1 << F
 HALF = ONE >> 1
 FORMATS = ("nv12", "i420")
+SITINGS = ("left", "center", "topleft")                               # PFNL_SITING_*: the index is the C-ABI's value
+AXES = {"left": (True, False), "center": (True, True), "topleft": (False, False)}   # (vertical, horizontal): midway? (else co-sited)
 MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}       # Kr, Kb
 
 
@@ -90,42 +98,71 @@ def pack(Y, Cb, Cr, fmt: str):
     return np.concatenate([Y.reshape(-1), c.reshape(-1)]).reshape(H * 3 // 2, W)
 
 
-def upsample(C, H: int, W: int):
+def siting_id(siting) -> int:
+    """The C-ABI's PFNL_SITING_* value of a siting's name; ValueError for anything else."""
+    if siting not in SITINGS:
+        raise ValueError(f"siting: one of {SITINGS}, got {siting!r}")
+    return SITINGS.index(siting)
+
+
+def _decode_taps(n: int, midway: bool):
+    """(near, far, w_near, w_far) per luma index 0 .. n - 1 of one axis: chroma indices clamped to n / 2, weights in quarters."""
+    y = np.arange(n)
+    j = y >> 1
+    if midway:
+        far, wn, wf = np.where(y & 1, j + 1, j - 1), np.full(n, 3), np.full(n, 1)
+    else:
+        far, wn, wf = j + 1, np.where(y & 1, 2, 4), np.where(y & 1, 2, 0)
+    return j, np.clip(far, 0, n // 2 - 1), wn, wf
+
+
+def upsample(C, H: int, W: int, siting="left"):
     """One chroma plane [H/2, W/2] at every luma pixel, [H,W] int32 in [0, 255]."""
+    vmid, hmid = AXES[SITINGS[siting_id(siting)]]
     C = np.asarray(C).astype(np.int32)
-    y, x = np.arange(H), np.arange(W)
-    j, i = y >> 1, x >> 1
-    jn = np.clip(np.where(y & 1, j + 1, j - 1), 0, H // 2 - 1)
-    ir = np.clip(i + 1, 0, W // 2 - 1)
-    near, far = C[j], C[jn]                                             # [H, W/2]
-    even = (6 * near[:, i] + 2 * far[:, i] + 4) >> 3
-    odd = (3 * near[:, i] + far[:, i] + 3 * near[:, ir] + far[:, ir] + 4) >> 3
-    return np.where((x & 1)[None, :], odd, even)
+    jn, jf, wyn, wyf = _decode_taps(H, vmid)
+    i_n, i_f, wxn, wxf = _decode_taps(W, hmid)
+    rows = wyn[:, None] * C[jn] + wyf[:, None] * C[jf]                  # [H, W/2], in quarters
+    return (wxn[None, :] * rows[:, i_n] + wxf[None, :] * rows[:, i_f] + 8) >> 4
 
 
-def to_rgb(frame, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False):
+def to_rgb(frame, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, siting="left"):
     """One packed frame -> [H,W,3] uint8."""
     y0, _, (dy, drv, dgu, dgv, dbu) = coefficients(matrix, full_range)
     Y, Cb, Cr = planes(frame, fmt, H, W)
     yy = dy * (Y.astype(np.int32) - y0)
-    u, v = upsample(Cb, H, W) - 128, upsample(Cr, H, W) - 128
+    u, v = upsample(Cb, H, W, siting) - 128, upsample(Cr, H, W, siting) - 128
     r = (yy + drv * v + HALF) >> F
     g = (yy + dgu * u + dgv * v + HALF) >> F
     b = (yy + dbu * u + HALF) >> F
     return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
 
 
-def downsample(N):
-    """Chroma numerators [H,W] int32 (14 fractional bits, unrounded) -> the plane [H/2, W/2] uint8: 1-2-1 over two rows, one rounding."""
-    N = np.asarray(N, np.int32)
-    H, W = N.shape
-    v = N[0::2] + N[1::2]                                               # [H/2, W]
-    c = np.arange(0, W, 2)
-    s = v[:, np.clip(c - 1, 0, W - 1)] + 2 * v[:, c] + v[:, np.clip(c + 1, 0, W - 1)]
-    return np.clip(128 + ((s + (1 << (F + 2))) >> (F + 3)), 0, 255).astype(np.uint8)
+def encode_filter(N, siting="left"):
+    """(s, k): the chroma numerators [H,W] filtered per axis onto [H/2, W/2] - a box over 2j, 2j + 1 on a midway axis, 1-2-1 over 2j - 1, 2j,
+    2j + 1 (clamped) on a co-sited one - unrounded, in N's integer type, and the bits k its weights add: the sum of the weights is 1 << k."""
+    vmid, hmid = AXES[SITINGS[siting_id(siting)]]
+    N = np.asarray(N)
+    k = 0
+    for axis, mid in ((0, vmid), (1, hmid)):
+        n = N.shape[axis]
+        c = np.arange(0, n, 2)
+        if mid:
+            N = np.take(N, c, axis) + np.take(N, c + 1, axis)
+        else:
+            N = np.take(N, np.clip(c - 1, 0, n - 1), axis) + 2 * np.take(N, c, axis) + np.take(N, c + 1, axis)
+        k += 1 if mid else 2
+    return N, k
 
 
-def from_rgb(rgb, fmt: str, matrix: str = "bt709", full_range=False):
+def downsample(N, siting="left"):
+    """Chroma numerators [H,W] int32 (14 fractional bits, unrounded) -> the plane [H/2, W/2] uint8: the siting's filter (left: 1-2-1 over
+    two rows), one rounding."""
+    s, k = encode_filter(np.asarray(N, np.int32), siting)
+    return np.clip(128 + ((s + (1 << (F + k - 1))) >> (F + k)), 0, 255).astype(np.uint8)
+
+
+def from_rgb(rgb, fmt: str, matrix: str = "bt709", full_range=False, siting="left"):
     """[H,W,3] uint8 -> one packed frame [H*3/2, W] uint8."""
     rgb = np.asarray(rgb)
     if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
@@ -135,6 +172,6 @@ def from_rgb(rgb, fmt: str, matrix: str = "bt709", full_range=False):
     y0, (yr, yg, yb, cbr, cbg, cbb, crr, crg, crb), _ = coefficients(matrix, full_range)
     r, g, b = (rgb[..., k].astype(np.int32) for k in range(3))
     Y = np.clip((yr * r + yg * g + yb * b + (y0 << F) + HALF) >> F, 0, 255)
-    Cb = downsample(cbr * r + cbg * g + cbb * b)
-    Cr = downsample(crr * r + crg * g + crb * b)
+    Cb = downsample(cbr * r + cbg * g + cbb * b, siting)
+    Cr = downsample(crr * r + crg * g + crb * b, siting)
     return pack(Y, Cb, Cr, fmt)
