@@ -369,14 +369,38 @@ int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long l
  *     every sample the value itself; limited range is 64 .. 940 / 64 .. 960 (pfnl_yuv10_coefficients: y0, then the nine encode integers);
  *   the output size uses pfnl_resize_taps' tables with h = (sum c p + 2^9) >> 10 and clip((sum c h + 2^17) >> 18, 0, 1023);
  *   the input side (RGB24, NV12, I420), scenes, the push bound, reset and the replay behind the range fence are what they are at 8 bits.
- *   As in_fmt the three are PFNL_ERR_INVALID (10-bit input is not built: it needs a 16-bit ring), and so is RGB10 out of a YUV in_fmt.
+ *   As in_fmt the three are PFNL_ERR_INVALID (10-bit input is a setting of its own, 10 BITS IN below: in_fmt names the layout), and so is
+ *   RGB10 out of a YUV in_fmt.
  *   The 16-bit output slots are allocated by the call that sets the format (PFNL_ERR_NOMEM) and freed by pfnl_stream_close.
- * Out of scope: 10-bit input, 12 and 16 bits, 4:2:2 and 4:4:4, sitings beyond SITING's three, transfer functions, BT.2020. */
+ * Out of scope: 12 and 16 bits, 4:2:2 and 4:4:4, sitings beyond SITING's three, transfer functions, BT.2020. */
 enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2, PFNL_PIX_RGB10 = 3, PFNL_PIX_P010 = 4, PFNL_PIX_I010 = 5 };
 enum { PFNL_MATRIX_BT601 = 0, PFNL_MATRIX_BT709 = 1 };
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range);
 int pfnl_yuv_coefficients(int matrix, int full_range, int32_t out[15]);    /* y0, 9 encode, 5 decode; no device needed */
 int pfnl_yuv10_coefficients(int matrix, int full_range, int32_t out[10]);  /* y0, 9 encode, for 10-bit samples; no device needed */
+/* 10 BITS IN (additions to version 4; 8 by default, and a session that never calls pfnl_stream_input_depth, or sets 8, issues the launches
+ * it always issued).  HEVC Main10, AV1 and UHD sources are 10-bit; cut to 8 bits ahead of the network, a 10-bit out_fmt only widens what
+ * was already truncated.  The depth of the input is a setting of its own: in_fmt keeps naming the LAYOUT, and pfnl_stream_input_depth(s, 10)
+ * says that its samples are little-endian uint16 in the conventions of the three 10-bit output formats:
+ *   in_fmt RGB24 = the RGB10 layout, [H][W][3] values 0 .. 1023; NV12 = P010, the value in the upper ten bits; I420 = I010, the value itself.
+ *   The session is lenient where a decoder's memory is not: P010's low six bits are ignored, an I010 / RGB10 sample above 1023 counts as
+ *   1023 (pfnl_amd/depth10.py values10) - no kernel multiplies or indexes with an unclamped sample.
+ *   push and push_surface take such frames (push keeps its const uint8_t*, 2-byte aligned, as pop does for 16-bit output; surfaces are
+ *     checked with the 16-bit layout's geometry).  The ring becomes [cap][H][W][3] uint16 and the YUV staging frame doubles; they are
+ *     allocated by whichever of pfnl_stream_input_depth and pfnl_stream_format comes second (PFNL_ERR_NOMEM: nothing half-made stays and
+ *     the setting is unchanged); pfnl_stream_close frees everything.
+ *   P010 / I010 are decoded straight into the ring slot by the one conversion kernel on uint16 samples (pfnl_amd/depth10.py to_rgb10:
+ *     pfnl_yuv10_decode_coefficients' integers, chroma offset 512, clip at 1023; sitings as at 8 bits): a device pointer on the session's
+ *     stream, a host pointer through the staging frame on the copy stream.  The windows are u10 / 1023. - the division in double,
+ *     rounded once to fp32 (depth10.py dequantise10) - gathered from the 16-bit ring, recomputed batches included.  The scene sums use
+ *     (66 R + 129 G + 25 B + 512) >> 10, luma on the 8-bit scale (pfnl_amd/scene.py luma_u10): thresholds and pfnl_stream_pop_info's sad
+ *     keep their meaning and magnitude.  Everything behind the windows - forward, ensemble, tiles, quantisation, the output route - is
+ *     untouched, and any out_fmt is allowed under pfnl_stream_format's rule (RGB10 out still goes with the RGB layout in).
+ *   Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); any value but 8 or 10 is PFNL_ERR_INVALID
+ *     before any HIP call; the setting survives pfnl_stream_reset and pfnl_stream_format.
+ * Out of scope: 12 and 16 bits, 4:2:2 / 4:4:4, BT.2020 and transfer functions, the 10-bit names as in_fmt. */
+int pfnl_stream_input_depth(pfnl_stream* s, int bits);   /* 8 (default) | 10 */
+int pfnl_yuv10_decode_coefficients(int matrix, int full_range, int32_t out[6]);  /* y0, dy, drv, dgu, dgv, dbu; no device needed */
 /* OUTPUT SIZE (off by default; then the session is what it always was).  The network's factor is fixed and display and encode rasters are
  * not (480p -> 1080p is 2.25 x, 720p -> 2160p is 3 x): with a size set the session resamples each batch's uint8 RGB frames on the device,
  * behind the quantisation and ahead of the YUV conversion, so a delivered frame is a pure function of the bytes the plain session
@@ -441,7 +465,7 @@ int pfnl_stream_place(pfnl_stream* s, int out_H, int out_W, const pfnl_rect* src
  *   a window of a larger surface needs no argument of its own: point plane[] at the first displayed sample (x and y even, so that the
  *     chroma pointers are whole samples) and keep the surface's pitch - the frame is then that window, and chroma clamps at its edges.
  * Out of scope: conversion kernels that write into the caller's surface (the conversion runs per batch, before a destination is known),
- * 10-bit input, odd sizes (crop and letterbox: PLACEMENT above puts the frame on a canvas before it is delivered). */
+ * odd sizes (crop and letterbox: PLACEMENT above puts the frame on a canvas before it is delivered). */
 typedef struct pfnl_surface {
     void*  plane[3];   /* RGB24 / RGB10: [0].  NV12 / P010: Y, CbCr.  I420 / I010: Y, Cb, Cr.  Unused entries are ignored. */
     size_t pitch[3];   /* bytes from one row of that plane to the next */
@@ -802,6 +826,24 @@ int pfnl_op_resize_place_u8(const uint8_t* in, int n, int H, int W, int oH, int 
                             const uint8_t fill[3], uint8_t* out, void* stream);
 int pfnl_op_resize_place_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, const pfnl_rect* src, const pfnl_rect* dst,
                              const uint16_t fill[3], uint16_t* out, void* stream);
+/* 10 BITS IN, the op hooks (10 BITS IN above; the rules: pfnl_amd/depth10.py to_rgb10 / values10 / dequantise10, pfnl_amd/scene.py luma_u10).
+ * Device pointers to uint16 samples, 2-byte aligned (the rings 4-byte); NULL, a bad fmt / matrix / range / siting and odd sizes are
+ * PFNL_ERR_INVALID before any HIP call.  They are the 8-bit hooks' kernel bodies on uint16 samples and synchronise as those do.
+ *   pfnl_op_yuv420_to_rgb_u10_sited: yuv [n][H*W*3/2] in P010 (low six bits ignored) or I010 (above 1023 = 1023) -> rgb [n][H][W][3], values
+ *     0 .. 1023.  16-byte words (8 pixels a lane) where W % 8 == 0 and both pointers are 16-byte aligned; single samples otherwise.
+ *   pfnl_op_yuv420_to_rgb_u10_surface_sited: one frame as planes with a pitch (SURFACES), read in place.
+ *   pfnl_op_gather_windows_u10 / _scenes: pfnl_op_gather_windows_u8 / _scenes on a ring [cap][H][W][3] uint16: win = min(sample, 1023) / 1023.
+ *     through a 1024-entry table; H*W*3 even.
+ *   pfnl_op_scene_sad_u10: pfnl_op_scene_sad_u8 on two [H][W][3] uint16 frames with luma_u10. */
+int pfnl_op_yuv420_to_rgb_u10_sited(const uint16_t* yuv, int fmt /*P010|I010*/, int matrix, int full_range, int n, int H, int W, uint16_t* rgb,
+                                    int siting, void* stream);
+int pfnl_op_yuv420_to_rgb_u10_surface_sited(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint16_t* rgb, int siting,
+                                            void* stream);
+int pfnl_op_gather_windows_u10(const uint16_t* ring, float* win, int cap, long long last, long long first, int count, int T, int H, int W,
+                               void* stream);
+int pfnl_op_gather_windows_u10_scenes(const uint16_t* ring, const long long* scene_first_dev, float* win, int cap, long long last, long long first,
+                                      int count, int T, int H, int W, void* stream);
+int pfnl_op_scene_sad_u10(const uint16_t* a, const uint16_t* b, int H, int W, unsigned long long* out_dev, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

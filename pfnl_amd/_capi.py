@@ -159,6 +159,13 @@ SIGNATURES = {
     "pfnl_op_resize_place_u10": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(pfnl_rect), C.POINTER(pfnl_rect), C.POINTER(C.c_uint16), _vp, _vp]),
     "pfnl_op_scene_sad_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pfnl_op_gather_windows_u8_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
+    "pfnl_stream_input_depth": (_i, [_vp, _i]),
+    "pfnl_yuv10_decode_coefficients": (_i, [_i, _i, C.POINTER(C.c_int32)]),
+    "pfnl_op_yuv420_to_rgb_u10_sited": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "pfnl_op_yuv420_to_rgb_u10_surface_sited": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "pfnl_op_gather_windows_u10": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
+    "pfnl_op_gather_windows_u10_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
+    "pfnl_op_scene_sad_u10": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
     "pfnl_op_score_y": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pfnl_comm_get_unique_id": (_i, [_vp]),
@@ -174,7 +181,7 @@ SIGNATURES = {
     "pfnl_comm_allgather": (_i, [_vp, _vp, _vp, C.c_size_t, _vp]),
 }
 PIXEL_FORMATS = {"rgb24": 0, "nv12": 1, "i420": 2, "rgb10": 3, "p010": 4, "i010": 5}   # PFNL_PIX_*
-TEN_BIT_FORMATS = ("rgb10", "p010", "i010")                # uint16 samples; out_format only
+TEN_BIT_FORMATS = ("rgb10", "p010", "i010")                # uint16 samples; names of out_format (10-bit input: in_depth)
 FORMATS_420 = ("nv12", "i420", "p010", "i010")             # H * W * 3 / 2 samples, even sizes
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                    # PFNL_MATRIX_*
 CHROMA_SITINGS = {"left": 0, "center": 1, "topleft": 2}    # PFNL_SITING_* (pfnl_amd/yuv.py SITINGS, in its order)

@@ -1045,6 +1045,87 @@ int pfnl_op_rgb_to_yuv420_u10_sited(const uint16_t* rgb, int fmt, int matrix, in
     return 0;
 }
 
+// ---- 10 bits in: the op hooks of the 16-bit input edge -----------------------------------------------------------------------------------
+
+int pfnl_yuv10_decode_coefficients(int matrix, int full_range, int32_t out[6]) {
+    if (!out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    pfnl::YuvCoef c;
+    if (!pfnl::yuv_coefficients(10, matrix, full_range, &c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    const int v[6] = {c.y0, c.dy, c.drv, c.dgu, c.dgv, c.dbu};
+    for (int k = 0; k < 6; ++k) out[k] = v[k];
+    return 0;
+}
+
+// as yuv_op_refused, for the two 16-bit 4:2:0 layouts
+static int yuv10_op_refused(const void* a, const void* b, int fmt, int matrix, int full_range, int n, int H, int W, int siting, pfnl::YuvCoef* c) {
+    if (!a || !b) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (fmt != PFNL_PIX_P010 && fmt != PFNL_PIX_I010) return fail(PFNL_ERR_INVALID, "yuv10: fmt must be PFNL_PIX_P010 or PFNL_PIX_I010");
+    if (!pfnl::yuv_coefficients(10, matrix, full_range, c)) return fail(PFNL_ERR_INVALID, "yuv10: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (n < 1 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return fail(PFNL_ERR_INVALID, "yuv10: n >= 1, H and W positive and even (4:2:0)");
+    return siting_refused(siting);
+}
+
+int pfnl_op_yuv420_to_rgb_u10_sited(const uint16_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* rgb, int siting,
+                                    void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = yuv10_op_refused(yuv, rgb, fmt, matrix, full_range, n, H, W, siting, &c)) return r;
+    if ((reinterpret_cast<uintptr_t>(rgb) | reinterpret_cast<uintptr_t>(yuv)) % 2) return fail(PFNL_ERR_INVALID, "yuv10: uint16 samples are 2-byte aligned");
+    HIPCHK(pfnl::launch_yuv420_to_rgb(yuv, rgb, fmt == PFNL_PIX_P010, c, n, H, W, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_yuv420_to_rgb_u10_surface_sited(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint16_t* rgb, int siting,
+                                            void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = yuv10_op_refused(yuv, rgb, fmt, matrix, full_range, 1, H, W, siting, &c)) return r;
+    if (reinterpret_cast<uintptr_t>(rgb) % 2) return fail(PFNL_ERR_INVALID, "yuv10: uint16 samples are 2-byte aligned");
+    if (const char* why = pfnl::surface_refused(yuv, fmt, H, W)) return fail(PFNL_ERR_INVALID, why);
+    HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u10(pfnl_internal_yuv_planes(*yuv, fmt == PFNL_PIX_P010), rgb, fmt == PFNL_PIX_P010, c, 1, H, W,
+                                                 siting, (hipStream_t)stream));
+    return 0;
+}
+
+// as pfnl_op_gather_windows_u8: what both gathers refuse before any HIP call (scene_first: null for the plain one)
+static int gather_u10_refused(const uint16_t* ring, const long long* scene_first, const float* win, int cap, long long last, long long first,
+                              int count, int T, int H, int W) {
+    if (cap < 1 || last < 0 || first < 0 || count < 1 || T < 1 || !(T & 1) || H < 1 || W < 1 || ((size_t)H * W * 3) % 2)
+        return fail(PFNL_ERR_INVALID, "bad window geometry (H*W*3 must be even, T odd, cap >= 1, first, last >= 0)");
+    if (first + count - 1 > last) return fail(PFNL_ERR_INVALID, "a window's centre frame lies beyond `last`");
+    if (reinterpret_cast<uintptr_t>(ring) % 4 || reinterpret_cast<uintptr_t>(win) % 16 || reinterpret_cast<uintptr_t>(scene_first) % 8)
+        return fail(PFNL_ERR_INVALID, "ring must be 4-byte aligned, scene_first 8-byte and win 16-byte aligned");
+    const long long lo = first - T / 2 < 0 ? 0 : first - T / 2, hi = first + count - 1 + T / 2 > last ? last : first + count - 1 + T / 2;
+    if (hi - lo + 1 > cap) return fail(PFNL_ERR_INVALID, "the windows span more frames than the ring holds");
+    return 0;
+}
+
+int pfnl_op_gather_windows_u10(const uint16_t* ring, float* win, int cap, long long last, long long first, int count, int T, int H, int W,
+                               void* stream) {
+    if (!ring || !win) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (int r = gather_u10_refused(ring, nullptr, win, cap, last, first, count, T, H, W)) return r;
+    HIPCHK(pfnl::launch_gather_windows_u10(ring, win, cap, last, first, count, T, (size_t)H * W * 6, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_gather_windows_u10_scenes(const uint16_t* ring, const long long* scene_first_dev, float* win, int cap, long long last, long long first,
+                                      int count, int T, int H, int W, void* stream) {
+    if (!ring || !scene_first_dev || !win) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (int r = gather_u10_refused(ring, scene_first_dev, win, cap, last, first, count, T, H, W)) return r;
+    HIPCHK(pfnl::launch_gather_windows_u10_scenes(ring, scene_first_dev, win, cap, last, first, count, T, (size_t)H * W * 6, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_scene_sad_u10(const uint16_t* a, const uint16_t* b, int H, int W, unsigned long long* out_dev, void* stream) {
+    if (!a || !b || !out_dev) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "H and W must be positive");
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 2) return fail(PFNL_ERR_INVALID, "scene sad: uint16 samples are 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out_dev) % 8) return fail(PFNL_ERR_INVALID, "out_dev must be 8-byte aligned");
+    OpStage st(stream);
+    unsigned long long* scratch = st.alloc<unsigned long long>(2);
+    st.run([&] { return hipMemsetAsync(scratch, 0, 2 * sizeof(unsigned long long), st.s); });
+    st.run([&] { return pfnl::launch_scene_sad_u10(a, b, (size_t)H * W, scratch, pfnl::SceneDecision{out_dev, nullptr, 0, 0, 0, 0, 0, 0}, st.s); });
+    return st.finish("scene sad op: ");
+}
+
 int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream) {
     if (!in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (n < 1) return fail(PFNL_ERR_INVALID, "resize: n >= 1");

@@ -1,5 +1,6 @@
 // The streaming session of the C-ABI (include/pfnl_hip.h, pfnl_stream_*): uint8 LR frames are pushed one at a time, uint8 SR frames are
-// popped in order.  What the harness's loop does around the forward (reference model/pfnl.py:236-262; pfnl_amd/model.py
+// popped in order (uint16 samples at 10 bits on either side: pfnl_stream_input_depth, the 10-bit out_fmts).
+// What the harness's loop does around the forward (reference model/pfnl.py:236-262; pfnl_amd/model.py
 // _run_sequence_on_device) - clamped windows, batching, quantisation, the range flag and the recomputation on the strict kernels - lives
 // here, behind pfnl_forward's own interface: the session calls pfnl_forward / pfnl_get_option / pfnl_set_option / pfnl_range_flag like
 // any other caller and knows nothing of the handle's layout (capi_internal.h, pfnl_handle_view).
@@ -38,9 +39,11 @@ struct pfnl_stream {
     pfnl_handle* h = nullptr;
     int H = 0, W = 0, batch = 0, T = 0, scale = 0, device = 0, cap = 0;
     size_t lr_bytes = 0, sr_bytes = 0;                // one LR / SR frame, uint8
+    int in_depth = 8;                                 // pfnl_stream_input_depth: 8, or 10 - pushed samples, ring and staging frame are uint16
+    size_t in_bytes = 0;                              // one LR frame as the ring holds it: lr_bytes samples of 1 or 2 bytes
     hipStream_t s = nullptr;                          // everything the session computes runs here
     hipStream_t cs = nullptr;                         // host-pointer frames in and out: copies that never wait for a later batch
-    uint8_t* ring = nullptr;                          // [cap][H][W][3], frame f in slot f % cap
+    uint8_t* ring = nullptr;                          // [cap][H][W][3] samples of the input depth, frame f in slot f % cap
     float* win = nullptr;                             // [batch][T][H][W][3]
     float* sr = nullptr;                              // [batch][sH][sW][3]
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -65,14 +68,15 @@ struct pfnl_stream {
     bool has_info = false;                            // what pfnl_stream_pop_info returns
     long long info_first = 0;
     unsigned long long info_sad = 0;
-    // the setting (pfnl_stream_format, pfnl_stream_resize, pfnl_stream_place; stored by apply_setting alone).  The ring stays RGB24: a YUV frame is converted
+    // the setting (pfnl_stream_format, pfnl_stream_input_depth, pfnl_stream_resize, pfnl_stream_place; stored by apply_setting alone).  The ring stays RGB: a YUV frame is converted
     // on its way into its ring slot.  Every stage `route` runs has a slot with room for a batch - 8- and 10-bit samples share it, as a
     // sequence has one route - and no other stage holds memory; stage 0 is allocated at open.
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
     int in_siting = PFNL_SITING_LEFT, out_siting = PFNL_SITING_LEFT;   // pfnl_stream_chroma_siting: where a 4:2:0 edge's chroma sits
     pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
-    pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010
-    uint8_t* yin = nullptr;                           // [H*W*3/2]: a host-pointer frame on its way to the kernel; from the first YUV in_fmt on
+    pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010, the input side at an input depth of 10
+    uint8_t* yin = nullptr;                           // [H*W*3/2] samples: a host-pointer frame on its way to the kernel; from the first YUV in_fmt on
+    size_t yin_cap = 0;                               // its bytes
     pfnl::PlacePlan rplan;                            // stage 1: a rectangle of the raster on a canvas, the whole onto the whole for a plain size; cH = 0: off
     int32_t* rtab = nullptr;                          // rplan.r.blob on the device
     pfnl::OutRoute route{};
@@ -109,11 +113,17 @@ int run_route(pfnl_stream* s, const Batch& b) {
 
 // gather -> forward -> quantise (-> resize -> 4:2:0) into the batch's slots, then its event; asynchronous on the session's stream
 int enqueue(pfnl_stream* s, const Batch& b) {
+    const uint16_t* const ring10 = reinterpret_cast<const uint16_t*>(s->ring);   // (read at an input depth of 10 alone)
     if (s->scene_mode) {
         // every frame up to b.last has been decided: on this stream, or on the copy stream before its push returned.  A replay
         // (check_batch) reads the same entries: the push bound keeps a batch's slots until it has been delivered.
-        HIPCHK(pfnl::launch_gather_windows_u8_scenes(s->ring, s->scene_first, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
+        if (s->in_depth == 10)
+            HIPCHK(pfnl::launch_gather_windows_u10_scenes(ring10, s->scene_first, s->win, s->cap, b.last, b.first, b.count, s->T, s->in_bytes, s->s));
+        else
+            HIPCHK(pfnl::launch_gather_windows_u8_scenes(s->ring, s->scene_first, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
         HIPCHK(hipMemcpyAsync(s->info[b.slot], s->scene_first, 2 * (size_t)s->cap * sizeof(long long), hipMemcpyDeviceToHost, s->s));
+    } else if (s->in_depth == 10) {
+        HIPCHK(pfnl::launch_gather_windows_u10(ring10, s->win, s->cap, b.last, b.first, b.count, s->T, s->in_bytes, s->s));
     } else {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
@@ -204,8 +214,13 @@ int decide_scene(pfnl_stream* s, hipStream_t on) {
     }
     const int prev = (int)((f - 1) % s->cap);
     const pfnl::SceneDecision d{s->sad, s->scene_first, slot, prev, f, s->mark ? 1 : 0, s->scene_mode == 2 ? 1 : 0, s->thr_sum};
-    HIPCHK(pfnl::launch_scene_sad_u8(s->ring + (size_t)slot * s->lr_bytes, s->ring + (size_t)prev * s->lr_bytes, (size_t)s->H * s->W,
-                                     s->sad + s->cap, d, on));
+    const uint8_t* const a = s->ring + (size_t)slot * s->in_bytes;
+    const uint8_t* const b = s->ring + (size_t)prev * s->in_bytes;
+    if (s->in_depth == 10)
+        HIPCHK(pfnl::launch_scene_sad_u10(reinterpret_cast<const uint16_t*>(a), reinterpret_cast<const uint16_t*>(b), (size_t)s->H * s->W,
+                                          s->sad + s->cap, d, on));
+    else
+        HIPCHK(pfnl::launch_scene_sad_u8(a, b, (size_t)s->H * s->W, s->sad + s->cap, d, on));
     return 0;
 }
 
@@ -243,7 +258,7 @@ int push_frame(pfnl_stream* s, int is_device, OnDevice&& on_device, OnHost&& on_
     if ((count && s->launched - s->delivered + count > 2LL * s->batch) || s->pushed - lo + 1 > s->cap)
         return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
     HIPCHK(hipSetDevice(s->device));
-    uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->lr_bytes;
+    uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->in_bytes;
     if (is_device) {
         if (int e = on_device(dst)) return e;
         if (s->scene_mode) {                          // behind the copy, ahead of any gather that can name the frame
@@ -313,6 +328,23 @@ int pop_frame(pfnl_stream* s, int is_device, long long* index, int* got, Deliver
     return 0;
 }
 
+// the format of a pushed frame as surface_geom.h knows it: in_fmt names the layout, the input depth the sample
+int pushed_format(const pfnl_stream* s) {
+    if (s->in_depth != 10) return s->in_fmt;
+    return s->in_fmt == PFNL_PIX_NV12 ? PFNL_PIX_P010 : (s->in_fmt == PFNL_PIX_I420 ? PFNL_PIX_I010 : PFNL_PIX_RGB10);
+}
+
+// a packed 4:2:0 frame on the device -> its ring slot as RGB, at the session's input depth
+int decode_packed(pfnl_stream* s, const uint8_t* yuv, uint8_t* dst, hipStream_t on) {
+    const bool nv12 = s->in_fmt == PFNL_PIX_NV12;
+    if (s->in_depth == 10)
+        HIPCHK(pfnl::launch_yuv420_to_rgb(reinterpret_cast<const uint16_t*>(yuv), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, s->H, s->W,
+                                          s->in_siting, on));
+    else
+        HIPCHK(pfnl::launch_yuv420_to_rgb_u8(yuv, dst, nv12, s->coef, 1, s->H, s->W, s->in_siting, on));
+    return 0;
+}
+
 void drop_slot(StageSlot& t) {
     for (uint8_t* p : t.buf)
         if (p) (void)hipFree(p);
@@ -338,17 +370,20 @@ void release(pfnl_stream* s) {
 
 // The one place where a setting becomes the session's: every setter ends here, with a candidate they have validated and no frame pushed
 // (`plan` NULL: the output size stays).  1. the route and a batch's bytes per stage; 2. everything new first - a stage slot whose capacity
-// is below the need, the tap table of a new plan, the staging frame of the first YUV in_fmt - and where one fails, what was just made is
+// is below the need, the tap table of a new plan, the ring of another input depth, the staging frame of the first YUV in_fmt or of one at
+// a wider depth (so whichever of pfnl_stream_format and pfnl_stream_input_depth comes second makes it) - and where one fails, what was just made is
 // freed, the session is what it was and the answer is PFNL_ERR_NOMEM with `nomem`; 3. the new buffers go in, the ones they replace and the
 // slots of stages the route does not run are freed, the setting is stored.  A call that replaces or releases device memory first waits
 // for the session's stream - a dropped sequence's device-pointer pops may still be reading it - and only such a call: pfnl_stream_format
 // waits where a 10-bit format meets 8-bit slots or a 4:2:0 slot is no longer needed, and not where it only adds memory or changes none.
 int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& coef, const pfnl::YuvCoef& coef10, pfnl::PlacePlan* plan,
-                  const char* nomem) {
+                  int in_depth, const char* nomem) {
     const pfnl::PlacePlan& rp = plan ? *plan : s->rplan;
     const pfnl::OutRoute route = pfnl::out_route(out_fmt, s->scale * s->H, s->scale * s->W, rp.cH, rp.cW);   // (the delivered frame is the canvas)
     StageSlot fresh[pfnl::ROUTE_STAGES];              // cap != 0: the stage's slot is too small and this one takes its place
-    bool frees = plan && s->rtab;
+    const size_t in_bytes = s->lr_bytes * (in_depth == 10 ? 2 : 1);
+    const size_t yin_need = in_fmt != PFNL_PIX_RGB24 ? in_bytes / 2 : 0;
+    bool frees = (plan && s->rtab) || in_depth != s->in_depth || (yin_need > s->yin_cap && s->yin);
     for (int k = 0; k < pfnl::ROUTE_STAGES; ++k) {
         const size_t need = (size_t)s->batch * route.stage_bytes[k];   // (0 for a stage that does not run)
         if (need > s->slot[k].cap) fresh[k].cap = need;
@@ -357,20 +392,22 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
     HIPCHK(hipSetDevice(s->device));
     if (frees) HIPCHK(hipStreamSynchronize(s->s));
     int32_t* tab = nullptr;
-    uint8_t* yin = nullptr;
+    uint8_t *yin = nullptr, *ring = nullptr;
     bool ok = true;
     if (plan && plan->cH) {
         const std::vector<int32_t>& blob = plan->r.blob;
         ok = hipMalloc(reinterpret_cast<void**>(&tab), blob.size() * sizeof(int32_t)) == hipSuccess;
         ok = ok && hipMemcpy(tab, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (in_fmt != PFNL_PIX_RGB24 && !s->yin) ok = ok && hipMalloc(reinterpret_cast<void**>(&yin), s->lr_bytes / 2) == hipSuccess;
+    if (in_depth != s->in_depth) ok = ok && hipMalloc(reinterpret_cast<void**>(&ring), (size_t)s->cap * in_bytes) == hipSuccess;
+    if (yin_need > s->yin_cap) ok = ok && hipMalloc(reinterpret_cast<void**>(&yin), yin_need) == hipSuccess;
     for (StageSlot& t : fresh)
         for (int i = 0; i < 2 && t.cap; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&t.buf[i]), t.cap) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
         if (tab) (void)hipFree(tab);
         if (yin) (void)hipFree(yin);
+        if (ring) (void)hipFree(ring);
         for (StageSlot& t : fresh) drop_slot(t);
         return fail(PFNL_ERR_NOMEM, nomem);
     }
@@ -379,7 +416,17 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
         s->rtab = tab;
         s->rplan = std::move(*plan);
     }
-    if (yin) s->yin = yin;
+    if (yin) {
+        if (s->yin) (void)hipFree(s->yin);
+        s->yin = yin;
+        s->yin_cap = yin_need;
+    }
+    if (ring) {
+        (void)hipFree(s->ring);
+        s->ring = ring;
+    }
+    s->in_depth = in_depth;
+    s->in_bytes = in_bytes;
     for (int k = 0; k < pfnl::ROUTE_STAGES; ++k)
         if (fresh[k].cap || !route.runs[k]) {
             drop_slot(s->slot[k]);
@@ -428,7 +475,7 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
     s->scale = v.scale;
     s->device = v.device_id;
     s->s = hip_stream ? (hipStream_t)hip_stream : v.stream;
-    s->lr_bytes = (size_t)H * W * 3;
+    s->lr_bytes = s->in_bytes = (size_t)H * W * 3;
     s->sr_bytes = s->lr_bytes * v.scale * v.scale;
     // The ring keeps a batch's frames until the batch has been checked (it may have to be computed again): with two batches undelivered,
     // the oldest needed frame is launched - 2 batch - T/2, and pushes go on up to launched + batch + T/2 - 2 before the one that would
@@ -456,36 +503,39 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
 
 int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
     if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24;  // the frame is H*W*3/2 bytes and reaches its slot through the kernel, as RGB
+    if (s->in_depth == 10 && reinterpret_cast<uintptr_t>(frame) % 2) return fail(PFNL_ERR_INVALID, "push: uint16 samples are 2-byte aligned");
+    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24;  // the frame is H*W*3/2 samples and reaches its slot through the kernel, as RGB
     return push_frame(
         s, is_device,
         [&](uint8_t* dst) {
             if (yuv_in)
-                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(frame, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->in_siting, s->s));
-            else
-                HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyDeviceToDevice, s->s));
+                return decode_packed(s, frame, dst, s->s);
+            HIPCHK(hipMemcpyAsync(dst, frame, s->in_bytes, hipMemcpyDeviceToDevice, s->s));
             return 0;
         },
         [&](uint8_t* dst) {
             if (yuv_in) {                             // (the staging frame is free again: every push ends with the copy stream idle)
-                HIPCHK(hipMemcpyAsync(s->yin, frame, s->lr_bytes / 2, hipMemcpyHostToDevice, s->cs));
-                HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, s->in_fmt == PFNL_PIX_NV12, s->coef, 1, s->H, s->W, s->in_siting, s->cs));
-            } else {
-                HIPCHK(hipMemcpyAsync(dst, frame, s->lr_bytes, hipMemcpyHostToDevice, s->cs));
+                HIPCHK(hipMemcpyAsync(s->yin, frame, s->in_bytes / 2, hipMemcpyHostToDevice, s->cs));
+                return decode_packed(s, s->yin, dst, s->cs);
             }
+            HIPCHK(hipMemcpyAsync(dst, frame, s->in_bytes, hipMemcpyHostToDevice, s->cs));
             return 0;
         });
 }
 
 int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_device) {
     if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (const char* why = pfnl::surface_refused(frame, s->in_fmt, s->H, s->W)) return fail(PFNL_ERR_INVALID, why);
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->in_fmt, s->H, s->W);
+    const int fmt = pushed_format(s);                 // (2-byte samples at an input depth of 10)
+    if (const char* why = pfnl::surface_refused(frame, fmt, s->H, s->W)) return fail(PFNL_ERR_INVALID, why);
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(fmt, s->H, s->W);
     const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24, nv12 = s->in_fmt == PFNL_PIX_NV12;
     return push_frame(
         s, is_device,
         [&](uint8_t* dst) {                           // YUV: the kernel reads the surface where it lies
-            if (yuv_in)
+            if (yuv_in && s->in_depth == 10)
+                HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u10(pfnl_internal_yuv_planes(*frame, nv12), reinterpret_cast<uint16_t*>(dst), nv12,
+                                                             s->coef10, 1, s->H, s->W, s->in_siting, s->s));
+            else if (yuv_in)
                 HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*frame, nv12), dst, nv12, s->coef, 1, s->H, s->W,
                                                             s->in_siting, s->s));
             else
@@ -500,7 +550,7 @@ int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_d
                                         hipMemcpyHostToDevice, s->cs));
                 to += g.plane[k].rows * g.plane[k].row_bytes;
             }
-            if (yuv_in) HIPCHK(pfnl::launch_yuv420_to_rgb_u8(s->yin, dst, nv12, s->coef, 1, s->H, s->W, s->in_siting, s->cs));
+            if (yuv_in) return decode_packed(s, s->yin, dst, s->cs);
             return 0;
         });
 }
@@ -606,7 +656,16 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
     if (!pfnl::yuv_coefficients(8, matrix, full_range, &coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, "format staging allocation failed");
+    return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, s->in_depth, "format staging allocation failed");
+}
+
+// The depth of the pushed samples: in_fmt keeps naming the layout.  At 10 the ring and the staging frame hold uint16 samples; decode, scene
+// sums and both gathers run their uint16 bodies; everything behind the windows is what it was.
+int pfnl_stream_input_depth(pfnl_stream* s, int bits) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (bits != 8 && bits != 10) return fail(PFNL_ERR_INVALID, "input depth: 8 or 10 bits");
+    if (s->pushed) return fail(PFNL_ERR_STATE, "the input depth is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, bits, "input ring allocation failed");
 }
 
 // no memory and no route depend on the sitings: they are arguments of the two conversion launches
@@ -632,7 +691,7 @@ int pfnl_stream_place(pfnl_stream* s, int out_H, int out_W, const pfnl_rect* src
     if (const char* no = pfnl::route_refused(s->in_fmt, s->out_fmt, plan.cH ? plan.cH : sH, plan.cW ? plan.cW : sW)) return fail(PFNL_ERR_INVALID, no);
     if (s->pushed) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     for (int k = 0; k < 3 && fill_rgb; ++k) plan.fill[k] = fill_rgb[k];
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, "resize allocation failed");
+    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, s->in_depth, "resize allocation failed");
 }
 
 int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) { return pfnl_stream_place(s, out_H, out_W, nullptr, nullptr, nullptr); }

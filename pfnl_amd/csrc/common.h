@@ -179,6 +179,14 @@ hipError_t launch_scene_sad_u8(const uint8_t* a, const uint8_t* b, size_t npix, 
 hipError_t launch_scene_first_frame(unsigned long long* sad, long long* scene_first, int slot, hipStream_t s);
 hipError_t launch_gather_windows_u8_scenes(const uint8_t* ring, const long long* scene_first, float* win, int cap, long long last,
                                            long long first, int count, int T, size_t frame_bytes, hipStream_t s);
+// the same three kernel bodies on a ring of uint16 samples at 10 bits (a sample above 1023 counts as 1023): win = u10 / 1023. (depth10.py
+// dequantise10), the luma of the sums on the 8-bit scale (scene.py luma_u10); frame_bytes = 2 bytes per sample
+hipError_t launch_gather_windows_u10(const uint16_t* ring, float* win, int cap, long long last, long long first, int count, int T,
+                                     size_t frame_bytes, hipStream_t s);
+hipError_t launch_gather_windows_u10_scenes(const uint16_t* ring, const long long* scene_first, float* win, int cap, long long last,
+                                            long long first, int count, int T, size_t frame_bytes, hipStream_t s);
+hipError_t launch_scene_sad_u10(const uint16_t* a, const uint16_t* b, size_t npix, unsigned long long* scratch, const SceneDecision& d,
+                                hipStream_t s);
 
 // ---- YUV 4:2:0 <-> RGB (yuv.hip; the rule: pfnl_amd/yuv.py, 10 bits: pfnl_amd/depth10.py) ----
 // The fifteen integers of yuv.py coefficients(), 14 fractional bits: the one table, computed on the host and passed to the kernels by value.
@@ -187,14 +195,15 @@ struct YuvCoef {
     int yr, yg, yb, cbr, cbg, cbb, crr, crg, crb;   // RGB -> YUV
     int dy, drv, dgu, dgv, dbu;                     // YUV -> RGB
 };
-// bits 8: samples 0 .. 255, limited range 16 .. 235 / 16 .. 240; bits 10: samples 0 .. 1023, 64 .. 940 / 64 .. 960, y0 and the encode
-// side alone (the decode side stays zero); matrix 0 BT.601 | 1 BT.709; false: unknown depth, matrix or range (no device needed)
+// bits 8: samples 0 .. 255, limited range 16 .. 235 / 16 .. 240; bits 10: samples 0 .. 1023, 64 .. 940 / 64 .. 960; matrix 0 BT.601 |
+// 1 BT.709; false: unknown depth, matrix or range (no device needed)
 bool yuv_coefficients(int bits, int matrix, int full_range, YuvCoef* c);
 // yuv [n][H*W*3/2] (NV12 or I420, tightly packed) <-> rgb [n][H][W][3]; H, W even; any alignment (words where W and the pointers allow);
 // siting: PFNL_SITING_* (0 left | 1 centre | 2 top left; anything else is hipErrorInvalidValue), in all four launchers
 hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);
-// The decode's source as planes: H rows of W bytes at y; NV12: H/2 rows of W bytes (Cb, Cr interleaved) at cb, cr unused; I420: H/2 rows of
-// W/2 bytes at cb and at cr.  pitch_*: bytes from one row to the next (>= the row); frame: bytes from one frame's planes to the next's.
+// The decode's source as planes: H rows of W samples at y; NV12 / P010: H/2 rows of W samples (Cb, Cr interleaved) at cb, cr unused; I420 /
+// I010: H/2 rows of W/2 samples at cb and at cr.  pitch_*: BYTES from one row to the next (>= the row); frame: bytes from one frame's planes
+// to the next's.  16-bit samples: every pointer and pitch even.
 struct YuvPlanes {
     const uint8_t *y, *cb, *cr;
     size_t pitch_y, pitch_cb, pitch_cr, frame;
@@ -202,6 +211,11 @@ struct YuvPlanes {
 // the same kernel on planes (the packed launcher calls this with pitch W, W/2): words where W, every plane, every pitch and rgb allow
 hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting,
                                           hipStream_t s);
+// the decode at 10 bits, the same kernel body on uint16 samples with the 10-bit table: P010 (semiplanar, the value in the upper ten bits,
+// the low six ignored) or I010 (a sample above 1023 is 1023) -> rgb uint16 0 .. 1023; 16-byte words where W % 8 == 0 and the pointers allow
+hipError_t launch_yuv420_to_rgb(const uint16_t* yuv, uint16_t* rgb, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);
+hipError_t launch_yuv420_planes_to_rgb_u10(const YuvPlanes& src, uint16_t* rgb, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting,
+                                           hipStream_t s);
 // the encode, one kernel over the sample type: uint8 -> NV12 (semiplanar) or I420 with the 8-bit table; uint16 with values 0 .. 1023 ->
 // P010 (semiplanar, samples << 6) or I010 with the 10-bit table; H, W even; any alignment a sample can have
 hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);

@@ -1,5 +1,5 @@
-// The sample depth of the streaming session's output edge, and the device primitives every stage of it shares (misc_kernels.hip quantise,
-// place.hip resample, yuv.hip 4:2:0): 8 bits in uint8_t samples, 10 bits (0 .. 1023) in uint16_t samples.  A stage is one body over the
+// The sample depth of the streaming session's two edges, and the device primitives their stages share (misc_kernels.hip quantise,
+// place.hip resample, yuv.hip 4:2:0 both ways, stream.hip ring): 8 bits in uint8_t samples, 10 bits (0 .. 1023) in uint16_t samples.  A stage is one body over the
 // sample type T; what differs between the depths is in Depth<T> and in the width of a sample.
 #pragma once
 #include "common.h"
@@ -43,14 +43,16 @@ constexpr int word_of() {
     return B % 16 == 0 ? 16 : (B % 8 == 0 ? 8 : (B % 4 == 0 ? 4 : (B % 2 == 0 ? 2 : 1)));
 }
 
-// N samples at p -> v[0 .. N), in words (WORDS) or sample by sample
-template <typename T, int N, bool WORDS>
+// N samples at p -> v[0 .. N), each sample >> SH (P010 keeps its values in the upper ten bits: the shift is part of the load, and the low
+// six bits are ignored), in words (WORDS) or sample by sample
+template <typename T, int N, bool WORDS, int SH = 0>
 __device__ __forceinline__ void load_samples(const T* __restrict__ p, int* v) {
     constexpr int SZ = (int)sizeof(T), BITS = 8 * SZ, SPW = 4 / SZ, WB = WORDS ? word_of<T, N>() : SZ;   // SPW: samples per 32 bits
     constexpr unsigned MASK = (1u << BITS) - 1;
+    static_assert(SH == 0 || SZ == 2, "only 16-bit samples are loaded shifted");
     if constexpr (WB == SZ) {
 #pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = p[k];
+        for (int k = 0; k < N; ++k) v[k] = p[k] >> SH;
     } else if constexpr (WB == 2) {                                    // (two bytes)
 #pragma unroll
         for (int k = 0; k < N; k += 2) {
@@ -72,7 +74,19 @@ __device__ __forceinline__ void load_samples(const T* __restrict__ p, int* v) {
             }
         }
 #pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = (int)((w[k / SPW] >> (BITS * (k % SPW))) & MASK);
+        for (int k = 0; k < N; ++k) v[k] = (int)(((w[k / SPW] >> (BITS * (k % SPW))) & MASK) >> SH);
+    }
+}
+
+// load_samples as an input edge takes a caller's samples: values of at most LEVELS - 1 whatever the memory holds.  8 bits: every byte is a
+// value.  16 bits: >> 6 leaves ten bits (P010); unshifted samples (I010, RGB10) clamp onto 1023 - no multiply and no table index ever
+// sees more (pfnl_amd/depth10.py values10).
+template <typename T, int N, bool WORDS, int SH = 0>
+__device__ __forceinline__ void load_values(const T* __restrict__ p, int* v) {
+    load_samples<T, N, WORDS, SH>(p, v);
+    if constexpr (sizeof(T) == 2 && SH == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) v[k] = v[k] > Depth<T>::LEVELS - 1 ? Depth<T>::LEVELS - 1 : v[k];
     }
 }
 

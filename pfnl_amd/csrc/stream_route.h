@@ -49,7 +49,8 @@ inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW) {
 // nullptr: a session may take in_fmt -> out_fmt and deliver out_h x out_w; else why not.  Both setters ask this before they look at
 // the session's state, each with the other's current setting.
 inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w) {
-    if (is_10bit(in_fmt)) return "format: 10-bit input is not built (in_fmt: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420)";
+    if (is_10bit(in_fmt))
+        return "format: 10-bit input is set with pfnl_stream_input_depth; in_fmt names the layout: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420";
     if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || out_fmt < PFNL_PIX_RGB24 || out_fmt > PFNL_PIX_I010)
         return "format: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420, and as out_fmt PFNL_PIX_RGB10, PFNL_PIX_P010 or PFNL_PIX_I010";
     if (in_fmt != PFNL_PIX_RGB24 && out_fmt == PFNL_PIX_RGB10)

@@ -1,5 +1,6 @@
-// YUV 4:2:0 <-> packed RGB: the two edges of the streaming session (include/pfnl_hip.h, pfnl_stream_format) - the decode of NV12 / I420
-// input, and the encode to NV12 / I420 or, with uint16 samples 0 .. 1023, to P010 / I010.  The arithmetic is integer and stated once on the
+// YUV 4:2:0 <-> packed RGB: the two edges of the streaming session (include/pfnl_hip.h, pfnl_stream_format, pfnl_stream_input_depth) - the
+// decode of NV12 / I420 or, with uint16 samples, P010 / I010 input, and the encode to NV12 / I420 or, with uint16 samples 0 .. 1023, to
+// P010 / I010.  The arithmetic is integer and stated once on the
 // host, pfnl_amd/yuv.py (10 bits: pfnl_amd/depth10.py): 14 fractional bits, coefficients rounded once, chroma sited left (on the even luma
 // columns, midway between two luma rows) unless the caller names another siting - centre or top left (include/pfnl_hip.h SITING), a template
 // parameter of both kernels; the kernels give its samples.
@@ -7,7 +8,9 @@
 // chroma samples it reads (or forms) serve both rows.  8 bits: P = 16 reads and writes 16-byte words (8-byte ones for I420's half-width
 // planes), P = 4 4-byte words (2-byte ones), P = 2 single bytes; 10 bits: P = 8 reads three 16-byte words per row and writes one per luma
 // row and one of interleaved chroma (I010's half-width planes take 8 bytes each), P = 2 single samples.  So any even H, W and any pointer
-// a sample can sit at.  Edges are index clamps inside the one kernel.  The encode is one body over the sample type (sample_depth.h).
+// a sample can sit at (the decode mirrors it: one 16-byte word of luma per row and one of interleaved chroma in, three of RGB per row out).
+// Edges are index clamps inside the one kernel.  Each kernel is one body over the sample type (sample_depth.h); the decode takes a caller's
+// 16-bit samples as values10 does (depth10.py): P010 >> 6, anything else clamped onto 1023.
 // The decode reads its planes by pointer and row pitch, so a decoder's surface (include/pfnl_hip.h SURFACES) and a packed frame are one kernel.
 #include <cmath>
 
@@ -32,7 +35,6 @@ bool yuv_coefficients(int bits, int matrix, int full_range, YuvCoef* c) {
     c->crr = rnd(cs / 2.0);
     c->crb = rnd(-cs * kb / (2.0 * (1.0 - kr)));
     c->crg = -c->crr - c->crb;
-    if (bits != 8) return true;                                        // (no decode side: 10-bit input is not built)
     c->dy = rnd(1.0 / ys);
     c->drv = rnd(2.0 * (1.0 - kr) / cs);
     c->dbu = rnd(2.0 * (1.0 - kb) / cs);
@@ -50,9 +52,11 @@ bool yuv_coefficients(int bits, int matrix, int full_range, YuvCoef* c) {
 // horizontally the 3 : 1 rule as well - an even pixel's far sample is the one to its LEFT, so a lane also reads the sample left of its
 // strip (clamped at 0): P/2 + 2 per row and plane.  S = 2, top left: chroma row k lies ON luma row 2k, so strip k of 0 .. H/2 - 1 is the
 // rows 2k (row k alone) and 2k + 1 (half row k, half row min(k + 1, H/2 - 1)); horizontally as left.
-template <int P, bool NV12, int S>
-__global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, uint8_t* __restrict__ rgb, int n, int H, int W, YuvCoef c) {
+template <typename T, int P, bool NV12, int S>
+__global__ __launch_bounds__(256) void yuv420_to_rgb_kernel(YuvPlanes src, T* __restrict__ rgb, int n, int H, int W, YuvCoef c) {
     constexpr bool WORDS = P > 2;
+    constexpr int LEVELS = Depth<T>::LEVELS, SH = sizeof(T) == 2 && NV12 ? 6 : 0;   // (P010: the value sits in the upper ten bits)
+    const auto row_of = [](const uint8_t* plane, size_t row, size_t pitch) { return reinterpret_cast<const T*>(plane + row * pitch); };
     constexpr int HP = P / 2, L = S == 1 ? 1 : 0;                      // L: samples read left of the strip
     const int gw = W / P, strips = S == 2 ? H / 2 : H / 2 + 1, hh = H >> 1, hw = W >> 1;
     const size_t total = (size_t)n * strips * gw;
@@ -71,24 +75,28 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             if constexpr (NV12) {
-                const uint8_t* const p = fb + (size_t)jrow[a] * src.pitch_cb;
+                const T* const p = row_of(fb, jrow[a], src.pitch_cb);
                 int pair[P], e[2];
-                load_samples<uint8_t, P, WORDS>(p + x0, pair);
-                load_samples<uint8_t, 2, WORDS>(p + 2 * ie, e);
+                load_values<T, P, WORDS, SH>(p + x0, pair);
+                load_values<T, 2, WORDS, SH>(p + 2 * ie, e);
 #pragma unroll
                 for (int q = 0; q < HP; ++q) cb[a][L + q] = pair[2 * q], cr[a][L + q] = pair[2 * q + 1];
                 cb[a][L + HP] = e[0], cr[a][L + HP] = e[1];
                 if constexpr (L) {
-                    load_samples<uint8_t, 2, WORDS>(p + 2 * il, e);
+                    load_values<T, 2, WORDS, SH>(p + 2 * il, e);
                     cb[a][0] = e[0], cr[a][0] = e[1];
                 }
             } else {
-                const uint8_t* const pb = fb + (size_t)jrow[a] * src.pitch_cb;
-                const uint8_t* const pr = src.cr + f * src.frame + (size_t)jrow[a] * src.pitch_cr;
-                load_samples<uint8_t, HP, WORDS>(pb + i0, cb[a] + L);
-                load_samples<uint8_t, HP, WORDS>(pr + i0, cr[a] + L);
-                cb[a][L + HP] = pb[ie], cr[a][L + HP] = pr[ie];
-                if constexpr (L) cb[a][0] = pb[il], cr[a][0] = pr[il];
+                const T* const pb = row_of(fb, jrow[a], src.pitch_cb);
+                const T* const pr = row_of(src.cr + f * src.frame, jrow[a], src.pitch_cr);
+                load_values<T, HP, WORDS>(pb + i0, cb[a] + L);
+                load_values<T, HP, WORDS>(pr + i0, cr[a] + L);
+                load_values<T, 1, false>(pb + ie, &cb[a][L + HP]);
+                load_values<T, 1, false>(pr + ie, &cr[a][L + HP]);
+                if constexpr (L) {
+                    load_values<T, 1, false>(pb + il, &cb[a][0]);
+                    load_values<T, 1, false>(pr + il, &cr[a][0]);
+                }
             }
         }
 #pragma unroll
@@ -96,7 +104,7 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
             const int y = S == 2 ? 2 * k + a : 2 * k - 1 + a;          // (S = 2: row 2k + a, on chroma row k | between rows k and k + 1)
             if (y < 0 || y >= H) continue;
             int luma[P], out[3 * P];
-            load_samples<uint8_t, P, WORDS>(fy + (size_t)y * src.pitch_y + x0, luma);
+            load_values<T, P, WORDS, SH>(row_of(fy, y, src.pitch_y) + x0, luma);
 #pragma unroll
             for (int px = 0; px < P; ++px) {
                 const int q = px >> 1;
@@ -123,13 +131,13 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_u8_kernel(YuvPlanes src, ui
                         v = (cr[0][q] + cr[0][e] + 1) >> 1;
                     }
                 }
-                u -= 128, v -= 128;
+                u -= Depth<T>::CHROMA, v -= Depth<T>::CHROMA;
                 const int yy = c.dy * (luma[px] - c.y0) + (1 << 13);
-                out[3 * px] = shift_clip<14, 256>(yy + c.drv * v);
-                out[3 * px + 1] = shift_clip<14, 256>(yy + c.dgu * u + c.dgv * v);
-                out[3 * px + 2] = shift_clip<14, 256>(yy + c.dbu * u);
+                out[3 * px] = shift_clip<14, LEVELS>(yy + c.drv * v);
+                out[3 * px + 1] = shift_clip<14, LEVELS>(yy + c.dgu * u + c.dgv * v);
+                out[3 * px + 2] = shift_clip<14, LEVELS>(yy + c.dbu * u);
             }
-            store_samples<uint8_t, 3 * P, WORDS>(rgb + ((f * H + y) * W + x0) * 3, out);
+            store_samples<T, 3 * P, WORDS>(rgb + ((f * H + y) * W + x0) * 3, out);
         }
     }
 }
@@ -220,30 +228,37 @@ int strip_blocks(size_t items) {
 bool yuv_geometry_ok(const void* a, const void* b, int n, int H, int W) { return a && b && n >= 1 && H >= 2 && W >= 2 && !(H & 1) && !(W & 1); }
 
 // The strip width the decode runs with.  Every word is read or written at plane + row * pitch (+ f * frame) + a multiple of its size, so
-// the planes, their pitches, the frame stride and rgb (rows of 3 W bytes) all have to be multiples of it: 16 | 4 for the full-width planes
-// and rgb, half of that for I420's chroma planes, whose words are half as wide.  A tightly packed frame gives what strip_width gives.
+// the planes, their pitches, the frame stride and rgb (rows of 3 W samples) all have to be multiples of it: 16 | 4 for the full-width planes
+// and rgb, half of that for I420's / I010's chroma planes, whose words are half as wide.  A tightly packed frame gives what strip_width
+// gives.  16-bit samples: 8 pixels in 16-byte words, or single samples; 0: a plane or a pitch that no 16-bit sample can sit at.
+template <typename T>
 int decode_strip_width(const YuvPlanes& p, const void* rgb, bool nv12, int W) {
     const auto bits = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
     const uintptr_t full = bits(p.y) | p.pitch_y | p.frame | bits(rgb) | (nv12 ? bits(p.cb) | p.pitch_cb : 0);
     const uintptr_t half = nv12 ? 0 : bits(p.cb) | bits(p.cr) | p.pitch_cb | p.pitch_cr;
-    if (W % 16 == 0 && full % 16 == 0 && half % 8 == 0) return 16;
-    if (W % 4 == 0 && full % 4 == 0 && half % 2 == 0) return 4;
-    return 2;
+    if constexpr (sizeof(T) == 1) {
+        if (W % 16 == 0 && full % 16 == 0 && half % 8 == 0) return 16;
+        if (W % 4 == 0 && full % 4 == 0 && half % 2 == 0) return 4;
+        return 2;
+    } else {
+        if ((full | half) % 2) return 0;
+        return W % 8 == 0 && full % 16 == 0 && half % 8 == 0 ? 8 : 2;
+    }
 }
 
-}  // namespace
-
-hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting,
-                                          hipStream_t s) {
+template <typename T>
+hipError_t launch_decode(const YuvPlanes& src, T* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
     if (!yuv_geometry_ok(src.y, rgb, n, H, W) || !src.cb || (!nv12 && !src.cr) || siting < 0 || siting > 2) return hipErrorInvalidValue;
-    if (src.pitch_y < (size_t)W || src.pitch_cb < (size_t)(nv12 ? W : W / 2) || (!nv12 && src.pitch_cr < (size_t)(W / 2))) return hipErrorInvalidValue;
-    const int P = decode_strip_width(src, rgb, nv12, W);
+    const size_t row = (size_t)W * sizeof(T);                          // bytes of a luma row
+    if (src.pitch_y < row || src.pitch_cb < (nv12 ? row : row / 2) || (!nv12 && src.pitch_cr < row / 2)) return hipErrorInvalidValue;
+    const int P = decode_strip_width<T>(src, rgb, nv12, W);
+    if (!P) return hipErrorInvalidValue;
     const dim3 grid(strip_blocks((size_t)n * (siting == 2 ? H / 2 : H / 2 + 1) * (W / P))), block(256);
 #define PFNL_YUV_LAUNCH_S(P_, S_)                                                                                  \
     if (nv12)                                                                                                      \
-        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, true, S_>), grid, block, 0, s, src, rgb, n, H, W, c);      \
+        hipLaunchKernelGGL((yuv420_to_rgb_kernel<T, P_, true, S_>), grid, block, 0, s, src, rgb, n, H, W, c);      \
     else                                                                                                           \
-        hipLaunchKernelGGL((yuv420_to_rgb_u8_kernel<P_, false, S_>), grid, block, 0, s, src, rgb, n, H, W, c)
+        hipLaunchKernelGGL((yuv420_to_rgb_kernel<T, P_, false, S_>), grid, block, 0, s, src, rgb, n, H, W, c)
 #define PFNL_YUV_LAUNCH(P_)                                                                                        \
     if (siting == 0) {                                                                                             \
         PFNL_YUV_LAUNCH_S(P_, 0);                                                                                  \
@@ -252,12 +267,20 @@ hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bo
     } else {                                                                                                       \
         PFNL_YUV_LAUNCH_S(P_, 2);                                                                                  \
     }
-    if (P == 16) {
-        PFNL_YUV_LAUNCH(16);
-    } else if (P == 4) {
-        PFNL_YUV_LAUNCH(4);
+    if constexpr (sizeof(T) == 1) {
+        if (P == 16) {
+            PFNL_YUV_LAUNCH(16);
+        } else if (P == 4) {
+            PFNL_YUV_LAUNCH(4);
+        } else {
+            PFNL_YUV_LAUNCH(2);
+        }
     } else {
-        PFNL_YUV_LAUNCH(2);
+        if (P == 8) {
+            PFNL_YUV_LAUNCH(8);
+        } else {
+            PFNL_YUV_LAUNCH(2);
+        }
     }
 #undef PFNL_YUV_LAUNCH
 #undef PFNL_YUV_LAUNCH_S
@@ -265,11 +288,33 @@ hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bo
 }
 
 // the packed frames as planes: the same kernel, the same strip width as ever
-hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
+template <typename T>
+hipError_t launch_decode_packed(const T* yuv, T* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
     if (!yuv_geometry_ok(yuv, rgb, n, H, W)) return hipErrorInvalidValue;
-    const size_t plane = (size_t)H * W, hw = (size_t)W / 2;
-    const YuvPlanes src{yuv, yuv + plane, nv12 ? nullptr : yuv + plane + plane / 4, (size_t)W, nv12 ? (size_t)W : hw, nv12 ? 0 : hw, plane + plane / 2};
-    return launch_yuv420_planes_to_rgb_u8(src, rgb, nv12, c, n, H, W, siting, s);
+    const size_t plane = (size_t)H * W * sizeof(T), row = (size_t)W * sizeof(T);
+    const uint8_t* const at = reinterpret_cast<const uint8_t*>(yuv);
+    const YuvPlanes src{at, at + plane, nv12 ? nullptr : at + plane + plane / 4, row, nv12 ? row : row / 2, nv12 ? 0 : row / 2, plane + plane / 2};
+    return launch_decode<T>(src, rgb, nv12, c, n, H, W, siting, s);
+}
+
+}  // namespace
+
+hipError_t launch_yuv420_planes_to_rgb_u8(const YuvPlanes& src, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting,
+                                          hipStream_t s) {
+    return launch_decode<uint8_t>(src, rgb, nv12, c, n, H, W, siting, s);
+}
+
+hipError_t launch_yuv420_planes_to_rgb_u10(const YuvPlanes& src, uint16_t* rgb, bool p010, const YuvCoef& c, int n, int H, int W, int siting,
+                                           hipStream_t s) {
+    return launch_decode<uint16_t>(src, rgb, p010, c, n, H, W, siting, s);
+}
+
+hipError_t launch_yuv420_to_rgb_u8(const uint8_t* yuv, uint8_t* rgb, bool nv12, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
+    return launch_decode_packed<uint8_t>(yuv, rgb, nv12, c, n, H, W, siting, s);
+}
+
+hipError_t launch_yuv420_to_rgb(const uint16_t* yuv, uint16_t* rgb, bool p010, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s) {
+    return launch_decode_packed<uint16_t>(yuv, rgb, p010, c, n, H, W, siting, s);
 }
 
 namespace {

@@ -1,4 +1,5 @@
-"""SR frames at 10 bits: quantisation, resampling and YUV 4:2:0, stated once in integers (numpy and Python integers only; no device).
+"""Frames at 10 bits, out and in: quantisation, resampling and YUV 4:2:0 both ways, stated once in integers (numpy and Python integers
+only; no device).
 
 The network's result is fp32; the streaming session can deliver it at 10 bits instead of 8 (include/pfnl_hip.h, pfnl_stream_format with
 PFNL_PIX_RGB10 / PFNL_PIX_P010 / PFNL_PIX_I010; pfnl_amd/csrc/depth10.hip), and this module is the rule its kernels are tested against,
@@ -21,7 +22,16 @@ quantise, pfnl_amd/resize.py, pfnl_amd/yuv.py) with the wider sample:
 Layouts (tightly packed, H * W * 3 / 2 samples, H and W even): ``p010`` = Y [H][W], CbCr [H/2][W/2][2], every sample value << 6 (the low six
 bits zero); ``i010`` (yuv420p10le) = Y, Cb [H/2][W/2], Cr [H/2][W/2], every sample the value itself; ``rgb10`` = [H][W][3], values 0 .. 1023.
 
-Out of scope: 10-bit input, BT.2020 and transfer functions, 12 and 16 bits, 4:2:2 / 4:4:4, pitched planes, sitings other than yuv.SITINGS.
+The input side (pfnl_stream_input_depth; pfnl_amd/csrc/yuv.hip decode, stream.hip 16-bit ring) has three more functions, lenient where
+``planes10`` is strict - a decoder's surface is taken as it comes:
+
+* ``values10``: the sample values as the device takes them - p010: sample >> 6, the low six bits ignored; i010 / rgb10: min(sample, 1023).
+  The clamp is part of the rule: no kernel indexes a table or multiplies with an unclamped sample;
+* ``to_rgb10``: yuv.to_rgb with ``decode_coefficients10`` (the same construction, ys = 876 / 1023, cs = 896 / 1023, y0 = 64), the chroma
+  offset 512 and the clip at 1023; chroma at every luma pixel by yuv.upsample, whose arithmetic does not depend on the depth;
+* ``dequantise10``: v / 1023 in double, rounded once to float32 - what the network sees of a 10-bit sample.
+
+Out of scope: BT.2020 and transfer functions, 12 and 16 bits, 4:2:2 / 4:4:4, pitched planes, sitings other than yuv.SITINGS.
 """
 from __future__ import annotations
 
@@ -66,6 +76,23 @@ def coefficients10(matrix: str, full_range) -> Tuple[int, Tuple[int, ...]]:
     crr, crb = rnd(cs / 2.0), rnd(-cs * kb / (2.0 * (1.0 - kr)))
     crg = -crr - crb
     return y0, (yr, yg, yb, cbr, cbg, cbb, crr, crg, crb)
+
+
+def decode_coefficients10(matrix: str, full_range) -> Tuple[int, Tuple[int, ...]]:
+    """(y0, decode): decode = (dy, drv, dgu, dgv, dbu) - the six integers of pfnl_yuv10_decode_coefficients, in its order."""
+    if matrix not in MATRICES:
+        raise ValueError(f"matrix: one of {sorted(MATRICES)}, got {matrix!r}")
+    kr, kb = MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    if full_range:
+        y0, ys, cs = 0, 1.0, 1.0
+    else:
+        y0, ys, cs = 64, 876.0 / 1023.0, 896.0 / 1023.0
+    rnd = _yuv._rnd
+    dy = rnd(1.0 / ys)
+    drv, dbu = rnd(2.0 * (1.0 - kr) / cs), rnd(2.0 * (1.0 - kb) / cs)
+    dgu, dgv = rnd(-2.0 * kb * (1.0 - kb) / (kg * cs)), rnd(-2.0 * kr * (1.0 - kr) / (kg * cs))
+    return y0, (dy, drv, dgu, dgv, dbu)
 
 
 def _geometry(fmt: str, H: int, W: int) -> None:
@@ -116,6 +143,45 @@ def pack10(Y, Cb, Cr, fmt: str):
     Y, Cb, Cr = (p.astype(np.uint16) for p in (Y, Cb, Cr))
     c = np.stack([Cb, Cr], axis=-1) if fmt == "p010" else np.stack([Cb, Cr], axis=0)
     return (np.concatenate([Y.reshape(-1), c.reshape(-1)]) << SHIFT[fmt]).astype(np.uint16).reshape(H * 3 // 2, W)
+
+
+IN_FORMATS = FORMATS + ("rgb10",)                                       # what values10 takes
+
+
+def values10(frame, fmt: str):
+    """The sample values of a packed 10-bit frame as the device takes them, uint16 in [0, 1023], in the frame's shape: ``p010`` sample >> 6
+    (the low six bits are ignored), ``i010`` / ``rgb10`` min(sample, 1023).  Lenient where planes10 refuses."""
+    if fmt not in IN_FORMATS:
+        raise ValueError(f"fmt: one of {IN_FORMATS}, got {fmt!r}")
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint16:
+        raise ValueError(f"expected uint16 samples, got {frame.dtype}")
+    return frame >> SHIFT["p010"] if fmt == "p010" else np.minimum(frame, np.uint16(MAXV))
+
+
+def to_rgb10(frame, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, siting="left"):
+    """One packed ``p010`` / ``i010`` frame (any shape with H*W*3/2 uint16 samples, taken by values10) -> [H,W,3] uint16 in [0, 1023]."""
+    _geometry(fmt, H, W)
+    y0, (dy, drv, dgu, dgv, dbu) = decode_coefficients10(matrix, full_range)
+    flat = np.asarray(frame).reshape(-1)
+    if flat.dtype != np.uint16 or flat.size != frame_samples(H, W):
+        raise ValueError(f"expected {frame_samples(H, W)} uint16 samples, got {flat.dtype} x {flat.size}")
+    Y, Cb, Cr = planes10(values10(flat, fmt) << SHIFT[fmt], fmt, H, W)
+    yy = dy * (Y.astype(np.int64) - y0)
+    u = _yuv.upsample(Cb, H, W, siting).astype(np.int64) - 512
+    v = _yuv.upsample(Cr, H, W, siting).astype(np.int64) - 512
+    nums = np.stack([yy + drv * v, yy + dgu * u + dgv * v, yy + dbu * u], axis=-1) + HALF
+    assert np.abs(nums).max() < (1 << 31)                               # (over the whole sample cube: at most 36 085 868 + 2^13)
+    return np.clip(nums >> F, 0, MAXV).astype(np.uint16)
+
+
+def dequantise10(v):
+    """uint16 in any shape -> float32 in [0, 1]: min(v, 1023) / 1023, the division in double and rounded once - the 10-bit twin of the
+    harness's (u8 / 255.).astype(np.float32)."""
+    v = np.asarray(v)
+    if v.dtype != np.uint16:
+        raise ValueError(f"expected uint16 samples, got {v.dtype}")
+    return (np.minimum(v, np.uint16(MAXV)).astype(np.float64) / float(MAXV)).astype(np.float32)
 
 
 def downsample10(N, siting="left"):

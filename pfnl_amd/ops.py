@@ -752,6 +752,111 @@ def rgb_to_yuv420_u10(frames, fmt: str, matrix: str = "bt709", full_range=False,
     return out.view(n, H * 3 // 2, W)
 
 
+def _yuv10_ids(fmt, matrix, full_range):
+    if fmt not in ("p010", "i010"):
+        raise ValueError(f'fmt: "p010" or "i010", got {fmt!r}')
+    if matrix not in _capi.YUV_MATRICES:
+        raise ValueError(f"matrix: one of {sorted(_capi.YUV_MATRICES)}, got {matrix!r}")
+    return _capi.PIXEL_FORMATS[fmt], _capi.YUV_MATRICES[matrix], int(bool(full_range))
+
+
+def yuv420_to_rgb10(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None, siting="left"):
+    """n tightly packed P010 / I010 frames, a uint16 tensor (cuda) of n * H*W*3/2 samples in any shape -> [n,H,W,3] uint16 with values
+    0 .. 1023, sample for sample pfnl_amd/depth10.py to_rgb10 (pfnl_op_yuv420_to_rgb_u10_sited: the streaming session's input edge at an
+    input depth of 10).  P010's low six bits are ignored, an I010 sample above 1023 counts as 1023.  Any alignment of whole samples;
+    ``out``: write there; ``siting``: "left" | "center" | "topleft"."""
+    import torch
+    lib = _capi.load_library()
+    ids = _yuv10_ids(fmt, matrix, full_range)
+    sid = _siting_id(siting)
+    src = _req_u16(frames, "frames")
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"H and W must be even and at least 2, got {H} x {W}")
+    fs = H * W * 3 // 2
+    n = frames.numel() // fs
+    if n < 1 or n * fs != frames.numel():
+        raise ValueError(f"frames must hold a whole number of frames of {fs} samples, got {frames.numel()} samples")
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=torch.uint16, device=frames.device)
+    elif out.numel() != n * H * W * 3 or out.device != frames.device:
+        raise ValueError("out must hold n * H * W * 3 samples on the frames' device")
+    _capi.check(lib.pfnl_op_yuv420_to_rgb_u10_sited(src, ids[0], ids[1], ids[2], n, H, W, _req_u16(out, "out"), sid, _stream(frames)))
+    return out.view(n, H, W, 3)
+
+
+def yuv420_to_rgb10_surface(planes, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, out=None, siting="left"):
+    """One P010 / I010 frame given as its planes - uint16 tensors (cuda), each a strided view with a row pitch of its own
+    (pfnl_amd/surface.py) -> [H,W,3] uint16, sample for sample pfnl_amd/depth10.py to_rgb10 of the packed frame
+    (pfnl_op_yuv420_to_rgb_u10_surface_sited: the kernel a device push_planes runs at an input depth of 10).  Even pointers and pitches."""
+    import torch
+    from . import surface as _surface
+    lib = _capi.load_library()
+    ids = _yuv10_ids(fmt, matrix, full_range)
+    sid = _siting_id(siting)
+    planes = tuple(planes)
+    for k, p in enumerate(planes):
+        if not (isinstance(p, torch.Tensor) and p.is_cuda and p.device == planes[0].device):
+            raise TypeError(f"plane {k} must be a tensor on the GPU, all on one device")
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise ValueError(f"H and W must be even and at least 2, got {H} x {W}")
+    sf = _surface.as_struct(planes, fmt, H, W)
+    if out is None:
+        out = torch.empty((H, W, 3), dtype=torch.uint16, device=planes[0].device)
+    elif out.numel() != H * W * 3 or out.device != planes[0].device:
+        raise ValueError("out must hold H * W * 3 samples on the planes' device")
+    _capi.check(lib.pfnl_op_yuv420_to_rgb_u10_surface_sited(C.byref(sf), ids[0], ids[1], ids[2], H, W, _req_u16(out, "out"), sid,
+                                                            _stream(planes[0])))
+    return out.view(H, W, 3)
+
+
+def _ring_u10(ring, name):
+    _req_u16(ring, "ring")
+    if ring.dim() != 4 or ring.shape[3] != 3:
+        raise ValueError(f"{name} expects [cap,H,W,3]")
+    return ring.shape[:3]
+
+
+def gather_windows_u10(ring, last: int, first: int, count: int, num_frames: int):
+    """gather_windows_u8 on a ring [cap,H,W,3] uint16 (cuda) at 10 bits: the windows dequantised as pfnl_amd/depth10.py dequantise10 does,
+    (min(u10, 1023) / 1023.).astype(np.float32) (pfnl_op_gather_windows_u10)."""
+    import torch
+    lib = _capi.load_library()
+    cap, H, W = _ring_u10(ring, "gather_windows_u10")
+    out = torch.empty((count, num_frames, H, W, 3), dtype=torch.float32, device=ring.device)
+    _capi.check(lib.pfnl_op_gather_windows_u10(C.c_void_p(ring.data_ptr()), _req(out, "out"), cap, int(last), int(first), count, num_frames,
+                                               H, W, _stream(ring)))
+    return out
+
+
+def gather_windows_u10_scenes(ring, scene_first, last: int, first: int, count: int, num_frames: int):
+    """gather_windows_u8_scenes on a ring [cap,H,W,3] uint16 (cuda) at 10 bits (pfnl_op_gather_windows_u10_scenes)."""
+    import torch
+    lib = _capi.load_library()
+    cap, H, W = _ring_u10(ring, "gather_windows_u10_scenes")
+    if not (isinstance(scene_first, torch.Tensor) and scene_first.device == ring.device and scene_first.dtype == torch.int64
+            and scene_first.is_contiguous() and tuple(scene_first.shape) == (cap,)):
+        raise TypeError("scene_first must be a contiguous int64 tensor [cap] on the ring's device")
+    out = torch.empty((count, num_frames, H, W, 3), dtype=torch.float32, device=ring.device)
+    _capi.check(lib.pfnl_op_gather_windows_u10_scenes(C.c_void_p(ring.data_ptr()), C.c_void_p(scene_first.data_ptr()), _req(out, "out"), cap,
+                                                      int(last), int(first), count, num_frames, H, W, _stream(ring)))
+    return out
+
+
+def scene_sad_u10(a, b) -> int:
+    """sum |Y(a) - Y(b)| of two [H,W,3] uint16 frames (cuda) at 10 bits, Y = (66 R + 129 G + 25 B + 512) >> 10 on min(sample, 1023), as a
+    Python int (pfnl_op_scene_sad_u10; exact: pfnl_amd/scene.py frame_sad10).  Synchronises."""
+    import torch
+    lib = _capi.load_library()
+    _req_u16(a, "a")
+    _req_u16(b, "b")
+    if a.dim() != 3 or a.shape[2] != 3 or b.shape != a.shape or b.device != a.device:
+        raise ValueError("scene_sad_u10 expects two [H,W,3] frames on one device")
+    out = torch.zeros((1,), dtype=torch.int64, device=a.device)
+    _capi.check(lib.pfnl_op_scene_sad_u10(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), a.shape[0], a.shape[1],
+                                          C.c_void_p(out.data_ptr()), _stream(a)))
+    return int(out.item())
+
+
 def resize_u10(frames, out_size, out=None):
     """[n,H,W,3] (or [H,W,3]) uint16 (cuda) with values 0 .. 1023 -> [n,oH,oW,3] uint16, ``out_size`` = (oH, oW): sample for sample
     pfnl_amd/depth10.py resize10 (pfnl_op_resize_u10: the streaming session's resampler at 10 bits).  Each axis between a quarter and

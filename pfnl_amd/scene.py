@@ -46,15 +46,38 @@ def frame_sads(frames_u8) -> list:
     return [0] + [frame_sad(frames_u8[f], frames_u8[f - 1]) for f in range(1, len(frames_u8))]
 
 
-def scene_first(frames_u8, threshold: Optional[float] = None, marks: Iterable[int] = ()) -> np.ndarray:
+def luma_u10(frame) -> np.ndarray:
+    """[H,W,3] uint16 RGB at 10 bits (a sample above 1023 counts as 1023, depth10.values10) -> [H,W] int32:
+    (66 R + 129 G + 25 B + 512) >> 10 - luma on the 8-BIT scale, one rounding, so that thresholds and sums mean what they mean at 8 bits."""
+    f = np.asarray(frame)
+    if f.dtype != np.uint16 or f.ndim != 3 or f.shape[2] != 3:
+        raise ValueError(f"expected a [H,W,3] uint16 frame, got {f.dtype} {f.shape}")
+    f = np.minimum(f, np.uint16(1023)).astype(np.int32)
+    return (66 * f[..., 0] + 129 * f[..., 1] + 25 * f[..., 2] + 512) >> 10
+
+
+def frame_sad10(a, b) -> int:
+    """sum |luma_u10(a) - luma_u10(b)| as a Python int: exact."""
+    return int(np.abs(luma_u10(a) - luma_u10(b)).sum(dtype=np.int64))
+
+
+def frame_sads10(frames_u10) -> list:
+    """frame_sads of 10-bit frames."""
+    return [0] + [frame_sad10(frames_u10[f], frames_u10[f - 1]) for f in range(1, len(frames_u10))]
+
+
+def scene_first(frames_u8, threshold: Optional[float] = None, marks: Iterable[int] = (), depth: int = 8) -> np.ndarray:
     """int64 [F]: the index of the first frame of each frame's scene.  Frame 0 starts scene 0 and is never a cut; frame f >= 1 starts a
-    scene if it is in ``marks`` or, with a threshold, if cut_rule(sad[f], sad[f-1], threshold_sum) holds."""
+    scene if it is in ``marks`` or, with a threshold, if cut_rule(sad[f], sad[f-1], threshold_sum) holds.  ``depth`` = 10: the frames are
+    uint16 at 10 bits and the sums are frame_sads10's."""
+    if depth not in (8, 10):
+        raise ValueError(f"depth: 8 or 10, got {depth!r}")
     F = len(frames_u8)
     marks = set(int(m) for m in marks)
     out = np.zeros((F,), np.int64)
     if F == 0:
         return out
-    sad = frame_sads(frames_u8) if threshold is not None else [0] * F
+    sad = (frame_sads10 if depth == 10 else frame_sads)(frames_u8) if threshold is not None else [0] * F
     thr = threshold_sum(threshold, frames_u8[0].shape[0], frames_u8[0].shape[1]) if threshold is not None else 0
     for f in range(1, F):
         cut = f in marks or (threshold is not None and cut_rule(sad[f], sad[f - 1], thr))

@@ -29,7 +29,13 @@ network's own size.
 10 bits out (off by default): ``open_stream(H, W, batch, out_format="p010")`` delivers uint16 frames for an HEVC Main10 / AV1 encoder -
 ``(oH*3//2, oW)``, every sample value << 6; ``"i010"`` (yuv420p10le) the values themselves, ``"rgb10"`` ``(oH, oW, 3)`` with values 0 .. 1023:
 the fp32 result quantised to 1023 levels instead of 255, then the same resampling and conversion by the rule of pfnl_amd/depth10.py.
-These are output formats only (``pixel_format`` stays "rgb24" | "nv12" | "i420"), and "rgb10" goes with RGB input.
+These are names of output formats (``pixel_format`` stays "rgb24" | "nv12" | "i420"), and "rgb10" goes with RGB input.
+
+10 bits in (off by default): ``open_stream(H, W, batch, pixel_format="i420", in_depth=10)`` takes uint16 frames in ``pixel_format``'s layout
+at 10 bits - "i420" is then yuv420p10le (the values themselves), "nv12" P010 (the value in the upper ten bits), "rgb24" ``(H, W, 3)`` values
+0 .. 1023: the conventions of the three 10-bit output formats.  The ring on the device holds uint16 samples, the network sees
+value / 1023, scenes score luma on the 8-bit scale (pfnl_amd/depth10.py, pfnl_amd/scene.py luma_u10); everything behind the windows is
+what it was, and with ``out_format="p010"`` the session is 10-bit end to end.
 
 Placement (off by default): ``open_stream(H, W, batch, out_size=(1080, 1920), fit="contain")`` keeps the picture's aspect ratio - a 4:3
 source lands 1080 x 1440 in the middle of a 16:9 canvas, bars of ``fill`` left and right; ``fit="cover"`` fills the canvas and loses two
@@ -69,7 +75,8 @@ def format_arguments(pixel_format="rgb24", out_format=None, matrix="bt709", full
         if value not in _capi.PIXEL_FORMATS:
             raise ValueError(f"{name}: one of {sorted(_capi.PIXEL_FORMATS)}, got {value!r}")
     if pixel_format in _capi.TEN_BIT_FORMATS:
-        raise ValueError(f"pixel_format: 10-bit input is not built ({pixel_format!r} is an out_format), one of 'rgb24', 'nv12', 'i420'")
+        raise ValueError(f"pixel_format: 10-bit input is in_depth=10 ({pixel_format!r} names an out_format; pixel_format names the layout), "
+                         f"one of 'rgb24', 'nv12', 'i420'")
     if out_format == "rgb10" and pixel_format != "rgb24":
         raise ValueError(f"out_format 'rgb10' goes with pixel_format 'rgb24', got {pixel_format!r}")
     if matrix not in _capi.YUV_MATRICES:
@@ -77,6 +84,38 @@ def format_arguments(pixel_format="rgb24", out_format=None, matrix="bt709", full
     if full_range not in (False, True, 0, 1):
         raise ValueError(f"full_range: False or True, got {full_range!r}")
     return _capi.PIXEL_FORMATS[pixel_format], _capi.PIXEL_FORMATS[out_format], _capi.YUV_MATRICES[matrix], int(bool(full_range))
+
+
+IN_LAYOUTS = {"rgb24": "rgb10", "nv12": "p010", "i420": "i010"}         # what pixel_format's layout is called at an input depth of 10
+
+
+def depth_argument(in_depth=8) -> int:
+    """The argument of pfnl_stream_input_depth for open_stream's ``in_depth``: 8 (off: no call) or 10; ValueError for anything else.
+    Needs no device."""
+    if isinstance(in_depth, bool) or in_depth not in (8, 10):
+        raise ValueError(f"in_depth: 8 or 10, got {in_depth!r}")
+    return int(in_depth)
+
+
+def pushed_format(pixel_format: str, in_depth: int = 8) -> str:
+    """The format name whose layout and sample type a pushed frame has: ``pixel_format`` itself at 8 bits, its 10-bit twin at 10."""
+    return IN_LAYOUTS[pixel_format] if depth_argument(in_depth) == 10 else pixel_format
+
+
+def frame_argument(frame, pixel_format: str, H: int, W: int, in_depth: int = 8):
+    """``frame`` as ``push`` hands it on - a contiguous numpy array, or a contiguous tensor where it was one - after the checks that need
+    no session: uint8 samples, uint16 at an input depth of 10, in one of ``frame_shapes``; ValueError otherwise."""
+    layout = pushed_format(pixel_format, in_depth)
+    shapes = frame_shapes(layout, H, W)
+    name = np.dtype(frame_dtype(layout)).name
+    if type(frame).__module__.startswith("torch"):
+        if str(frame.dtype) != "torch." + name or tuple(frame.shape) not in shapes:
+            raise ValueError(f"expected a {name} frame of shape {' or '.join(map(str, shapes))}, got {frame.dtype} {tuple(frame.shape)}")
+        return frame.contiguous()
+    frame = np.asarray(frame)
+    if frame.dtype != np.dtype(name) or frame.shape not in shapes:
+        raise ValueError(f"expected a {name} frame of shape {' or '.join(map(str, shapes))}, got {frame.dtype} {frame.shape}")
+    return np.ascontiguousarray(frame)
 
 
 def siting_arguments(chroma_siting="left", out_chroma_siting=None) -> Tuple[int, int]:
@@ -189,6 +228,10 @@ class VideoStream:
     ``out_format`` "rgb10" | "p010" | "i010": ``pop`` returns uint16 frames (``torch.uint16`` on the device), 10-bit values by the rule of
     pfnl_amd/depth10.py - p010 in the upper ten bits of each sample; ``pixel_format`` takes none of them.
 
+    ``in_depth`` (8 | 10): at 10, ``push`` and ``push_planes`` take uint16 frames (numpy, or ``torch.uint16`` on the device) in
+    ``pixel_format``'s layout - "rgb24" values 0 .. 1023, "nv12" as P010, "i420" as I010 (pfnl_amd/depth10.py values10 / to_rgb10); ``cuts`` and
+    ``last_info`` keep their meaning (pfnl_amd/scene.py luma_u10).
+
     ``out_size`` (None | ``(oH, oW)``): the raster ``pop`` delivers, ``(oH, oW, 3)`` or ``(oH*3//2, oW)``, by the rule of pfnl_amd/resize.py;
     each axis between a quarter and twice the network's output, even in a 4:2:0 output format.
 
@@ -207,8 +250,9 @@ class VideoStream:
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
-                 chroma_siting="left", out_chroma_siting=None, ensemble=1):
+                 chroma_siting="left", out_chroma_siting=None, in_depth=8, ensemble=1):
         import torch
+        self.in_depth = depth_argument(in_depth)    # (before the engine is touched, as every check of an argument)
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
         sit = siting_arguments(chroma_siting, out_chroma_siting)
         self.chroma_siting, self.out_chroma_siting = chroma_siting, chroma_siting if out_chroma_siting is None else out_chroma_siting
@@ -242,6 +286,12 @@ class VideoStream:
                     _capi.check(self._lib.pfnl_stream_scenes(s, 1, 0.0))
                 else:
                     _capi.check(self._lib.pfnl_stream_scenes(s, 2, float(scene_cut)))
+            except Exception:
+                self.close()
+                raise
+        if self.in_depth != 8:                      # (8: the session as it always was, and no call)
+            try:
+                _capi.check(self._lib.pfnl_stream_input_depth(s, self.in_depth))
             except Exception:
                 self.close()
                 raise
@@ -309,22 +359,14 @@ class VideoStream:
         fetches the next frame (``pop`` is there for a caller that wants them at once)."""
         s = self._handle()
         due = self.ready()
-        shapes = frame_shapes(self.pixel_format, self.H, self.W)
-        shape = " or ".join(map(str, shapes))
         if type(frame).__module__.startswith("torch"):
-            import torch
-            if frame.dtype != torch.uint8 or tuple(frame.shape) not in shapes:
-                raise ValueError(f"expected a uint8 frame of shape {shape}, got {frame.dtype} {tuple(frame.shape)}")
+            frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth)
             if not frame.is_cuda or frame.device.index != self.device.index:
                 raise ValueError(f"tensor on {frame.device}, stream on {self.device} (host frames: numpy arrays)")
-            frame = frame.contiguous()
             self._device_frames = True
             _capi.check(self._lib.pfnl_stream_push(s, C.c_void_p(frame.data_ptr()), 1))
         else:
-            frame = np.asarray(frame)
-            if frame.dtype != np.uint8 or frame.shape not in shapes:
-                raise ValueError(f"expected a uint8 frame of shape {shape}, got {frame.dtype} {frame.shape}")
-            frame = np.ascontiguousarray(frame)
+            frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth)
             self._device_frames = False
             _capi.check(self._lib.pfnl_stream_push(s, frame.ctypes.data_as(C.c_void_p), 0))
         return self.pop_ready(due)
@@ -412,11 +454,11 @@ class VideoStream:
 
     def push_planes(self, *planes) -> List[tuple]:
         """``push`` of a frame given as its planes in ``pixel_format`` - (Y, CbCr) for nv12, (Y, Cb, Cr) for i420, one (H, W, 3) or (H, 3 W)
-        plane for rgb24 - each a numpy array or each a device tensor, with whatever row pitch its strides say (pfnl_amd/surface.py):
+        plane for rgb24; uint16 samples at an input depth of 10 - each a numpy array or each a device tensor, with whatever row pitch its strides say (pfnl_amd/surface.py):
         typically views ``surface[:H, :W]`` of a decoder's pitched surface, which is read where it lies.  Returns what ``push`` returns;
         the two may alternate within a sequence."""
         s = self._handle()
-        sf, on_device = self._planes_struct(planes, self.pixel_format, self.H, self.W)
+        sf, on_device = self._planes_struct(planes, pushed_format(self.pixel_format, self.in_depth), self.H, self.W)
         due = self.ready()
         _capi.check(self._lib.pfnl_stream_push_surface(s, C.byref(sf), 1 if on_device else 0))
         self._device_frames = on_device

@@ -4,7 +4,9 @@
 
 The stream's header (pfnl_amd/y4m.py) names the raster, the chroma siting, the range and the sample aspect ratio; the frames are the
 session's ``i420`` frames as they are, converted on the device with that siting (pfnl_amd/yuv.py), and what the session delivers is written
-as ``i420`` - or ``i010`` with ``--bits 10`` - under a header of the output's raster, siting and aspect.  Y4M carries no matrix: ``--matrix
+as ``i420`` - or ``i010`` with ``--bits 10`` - under a header of the output's raster, siting and aspect.  A ``C420p10`` stream (``ffmpeg
+-pix_fmt yuv420p10le -f yuv4mpegpipe``) is taken at its own depth - uint16 frames into a session opened with ``in_depth=10`` - and wants
+``--bits 10``: at the default of 8 the ten bits are kept on the way in and cut on the way out.  Y4M carries no matrix: ``--matrix
 auto`` takes BT.601 up to 576 lines and BT.709 above.  ``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
 """
 from __future__ import annotations
@@ -26,9 +28,10 @@ def auto_matrix(height: int) -> str:
 def session_keywords(header, **session_kw) -> dict:
     """``open_stream``'s keywords for a stream with this header: the caller's (``batch``, ``scene_cut``, ``out_format`` "i420" | "i010",
     ``out_size``, ``fit``, ``out_chroma_siting``, ``ensemble``, ``matrix`` with "auto", ``full_range`` True to override the header), and from the
-    header the input siting, the range, and - with ``fit`` alone - the sample aspect ratio.  ValueError for what a Y4M stream cannot hold."""
+    header the input siting, the range, ``in_depth=10`` for a 10-bit stream (and no such key for an 8-bit one) and - with ``fit`` alone -
+    the sample aspect ratio.  ValueError for what a Y4M stream cannot hold."""
     kw = dict(session_kw)
-    for fixed in ("pixel_format", "chroma_siting", "sar"):
+    for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth"):
         if fixed in kw:
             raise ValueError(f"{fixed} comes from the stream's header")
     kw.setdefault("batch", 1)
@@ -41,6 +44,8 @@ def session_keywords(header, **session_kw) -> dict:
     kw["full_range"] = bool(kw.get("full_range")) or header.full_range
     kw["pixel_format"] = "i420"
     kw["chroma_siting"] = header.siting
+    if header.bits == 10:
+        kw["in_depth"] = 10
     if kw.get("fit") is not None:
         kw["sar"] = header.sar
     return kw
@@ -122,7 +127,7 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--full-range", action="store_true", help="full-range samples whatever the header says")
     ap.add_argument("--batch", type=int, default=1, help="windows per forward")
     ap.add_argument("--scene-cut", type=_scene_cut, default=None, metavar="THRESHOLD", help="keep windows inside a scene: the cut detector's threshold")
-    ap.add_argument("--bits", type=int, choices=(8, 10), default=8, help="10: yuv420p10le out")
+    ap.add_argument("--bits", type=int, choices=(8, 10), default=8, help="10: yuv420p10le out (what a 10-bit source wants)")
     ap.add_argument("--out-size", type=_size, default=None, metavar="HxW")
     ap.add_argument("--fit", choices=("contain", "cover"), default=None, help="keep the aspect ratio on the --out-size canvas")
     ap.add_argument("--out-siting", choices=("left", "center", "topleft"), default=None, help="the output's chroma siting (default: the input's)")
@@ -138,7 +143,7 @@ def main(argv=None) -> int:
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     eng = None
     try:
-        reader = _y4m.Y4MReader(fin)
+        reader = _y4m.Y4MReader(fin, depths=(8, 10))
         from . import checkpoint, synth
         from .engine import PFNLEngine
         from .spec import PFNLGeometry

@@ -11,9 +11,12 @@ The header is ``YUV4MPEG2`` and space-separated tokens up to the newline:
 * ``I``: ``p`` (progressive) and ``?`` (unknown) are accepted; ``t``, ``b``, ``m`` are refused - the network is no deinterlacer;
 * ``A n:d``: the sample aspect ratio, ``0:0`` (unknown) or absent = (1, 1);
 * ``C``: absent, ``420jpeg`` and bare ``420`` = chroma sited "center"; ``420mpeg2`` = "left"; ``420paldv`` = "topleft" (pfnl_amd/yuv.py
-  SITINGS); any other tag (``422``, ``444``, ``mono``, ``420p10``, ...) is a ValueError that names it.
+  SITINGS); any other tag (``422``, ``444``, ``mono``, ...) is a ValueError that names it;
+* ``C420p10`` (yuv420p10le) is read where the caller asks for it - ``Y4MReader(f, depths=(8, 10))``; by default it is refused like any
+  other tag - and gives ``bits=10``, frames as ``(H*3//2, W)`` little-endian uint16 arrays (the session's ``i010``, taken with
+  ``in_depth=10``) and ``siting="left"``: Y4M's 10-bit tag carries no siting, and left is what HEVC / AV1 encoders mean unless told otherwise.
 
-Out of scope: 4:2:2 / 4:4:4 / mono, input above 8 bits, interlaced streams, per-frame parameters (they are read and dropped).
+Out of scope: 4:2:2 / 4:4:4 / mono, 12 and 16 bits, interlaced streams, per-frame parameters (they are read and dropped).
 """
 from __future__ import annotations
 
@@ -77,8 +80,9 @@ class Y4MHeader:
         return self.width * self.height * 3 // 2 * (2 if self.bits == 10 else 1)
 
     @classmethod
-    def parse(cls, line: bytes) -> "Y4MHeader":
-        """The header of its line (without or with the newline)."""
+    def parse(cls, line: bytes, depths: Tuple[int, ...] = (8,)) -> "Y4MHeader":
+        """The header of its line (without or with the newline).  ``depths``: the sample depths the caller takes; with 10 among them
+        ``C420p10`` parses to ``bits=10``, ``siting="left"``."""
         try:
             tokens = line.rstrip(b"\n").decode("ascii").split(" ")
         except UnicodeDecodeError:
@@ -87,7 +91,7 @@ class Y4MHeader:
             raise ValueError(f"y4m: the stream does not start with {MAGIC.decode()}")
         width = height = None
         rate = interlace = None
-        sar, siting, ext = (1, 1), "center", []
+        sar, siting, ext, bits = (1, 1), "center", [], 8
         for t in tokens[1:]:
             if not t:
                 continue
@@ -107,6 +111,8 @@ class Y4MHeader:
                 sar = _ratio(value, "A")
                 if sar[0] == 0 or sar[1] == 0:
                     sar = (1, 1)
+            elif key == "C" and value == TAG_10BIT and 10 in depths:
+                siting, bits = "left", 10
             elif key == "C":
                 if value not in SITING_OF_TAG:
                     raise ValueError(f"y4m: chroma format C{value} is not supported (8-bit 4:2:0: {', '.join('C' + k for k in SITING_OF_TAG)})")
@@ -119,7 +125,7 @@ class Y4MHeader:
                 raise ValueError(f"y4m: unknown header token {t!r}")
         if width is None or height is None:
             raise ValueError("y4m: the header needs W and H")
-        return cls(width, height, rate, interlace, sar, siting, tuple(ext), 8)
+        return cls(width, height, rate, interlace, sar, siting, tuple(ext), bits)
 
     def to_bytes(self) -> bytes:
         """The header line, newline included: W H F I A C, then the extensions."""
@@ -176,14 +182,15 @@ def _read_line(f) -> bytes:
 
 
 class Y4MReader:
-    """``Y4MReader(fileobj)`` reads the header at once (``.header``); iterating yields every frame as a ``(H*3//2, W)`` uint8 array."""
+    """``Y4MReader(fileobj)`` reads the header at once (``.header``); iterating yields every frame as a ``(H*3//2, W)`` uint8 array -
+    little-endian uint16 for a ``C420p10`` stream, which ``depths=(8, 10)`` lets through."""
 
-    def __init__(self, fileobj):
+    def __init__(self, fileobj, depths: Tuple[int, ...] = (8,)):
         self._f = fileobj
         line = _read_line(fileobj)
         if line is None:
             raise ValueError("y4m: empty stream")
-        self.header = Y4MHeader.parse(line)
+        self.header = Y4MHeader.parse(line, depths)
         self.frames = 0
 
     def read_frame(self):
@@ -198,7 +205,7 @@ class Y4MReader:
         if len(data) != h.frame_bytes:
             raise ValueError(f"y4m: frame {self.frames} is truncated: {len(data)} of {h.frame_bytes} bytes")
         self.frames += 1
-        return np.frombuffer(data, np.uint8).reshape(h.height * 3 // 2, h.width)
+        return np.frombuffer(data, "<u2" if h.bits == 10 else np.uint8).reshape(h.height * 3 // 2, h.width)
 
     def __iter__(self) -> Iterator[np.ndarray]:
         while True:

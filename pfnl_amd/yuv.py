@@ -15,7 +15,7 @@ the rule its kernels are tested against, byte for byte.  Everything after the co
   j, far = j + 1, 4 : 0 on even and 2 : 2 on odd indices - and (sum wy wx C + 8) >> 4.  Encode: per axis a box over 2j, 2j + 1 (midway, k =
   1) or 1-2-1 over 2j - 1, 2j, 2j + 1 (co-sited, k = 2), indices clamped, and one rounding by F + k bits, k summed over both axes.
 
-Out of scope: pitched planes, 10-bit input (10-bit output is pfnl_amd/depth10.py), 4:2:2 / 4:4:4, sitings other than these three (HEVC types
+Out of scope: pitched planes (pfnl_amd/surface.py), 10 bits (input and output: pfnl_amd/depth10.py), 4:2:2 / 4:4:4, sitings other than these three (HEVC types
 1, 3, 4, 5), transfer functions, BT.2020.
 """
 from __future__ import annotations
@@ -117,7 +117,8 @@ def _decode_taps(n: int, midway: bool):
 
 
 def upsample(C, H: int, W: int, siting="left"):
-    """One chroma plane [H/2, W/2] at every luma pixel, [H,W] int32 in [0, 255]."""
+    """One chroma plane [H/2, W/2] at every luma pixel, [H,W] int32 in the plane's range ([0, 255]; the arithmetic does not depend on the
+    depth: depth10.to_rgb10 calls it with values up to 1023)."""
     vmid, hmid = AXES[SITINGS[siting_id(siting)]]
     C = np.asarray(C).astype(np.int32)
     jn, jf, wyn, wyf = _decode_taps(H, vmid)
