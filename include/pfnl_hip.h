@@ -372,7 +372,7 @@ int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long l
  *   As in_fmt the three are PFNL_ERR_INVALID (10-bit input is a setting of its own, 10 BITS IN below: in_fmt names the layout), and so is
  *   RGB10 out of a YUV in_fmt.
  *   The 16-bit output slots are allocated by the call that sets the format (PFNL_ERR_NOMEM) and freed by pfnl_stream_close.
- * Out of scope: 12 and 16 bits, 4:2:2 and 4:4:4, sitings beyond SITING's three, transfer functions, BT.2020. */
+ * Out of scope: 12 and 16 bits, sitings beyond SITING's three, transfer functions, BT.2020 (4:2:2 and 4:4:4: CHROMA FORMAT below). */
 enum { PFNL_PIX_RGB24 = 0, PFNL_PIX_NV12 = 1, PFNL_PIX_I420 = 2, PFNL_PIX_RGB10 = 3, PFNL_PIX_P010 = 4, PFNL_PIX_I010 = 5 };
 enum { PFNL_MATRIX_BT601 = 0, PFNL_MATRIX_BT709 = 1 };
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range);
@@ -489,9 +489,36 @@ int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_devi
  *     ignored by an RGB edge; the surface calls follow them.  NULL and a value outside the enum: PFNL_ERR_INVALID, before any HIP call.
  *     Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); the setting survives pfnl_stream_reset
  *     and pfnl_stream_format.  It allocates nothing: the siting is an argument of the edge's one conversion launch.
- * Out of scope: HEVC types 1, 3, 4 and 5, sitings that differ between Cb and Cr, 4:2:2 and 4:4:4. */
+ * Out of scope: HEVC types 1, 3, 4 and 5, sitings that differ between Cb and Cr. */
 enum { PFNL_SITING_LEFT = 0, PFNL_SITING_CENTER = 1, PFNL_SITING_TOPLEFT = 2 };
 int pfnl_stream_chroma_siting(pfnl_stream* s, int in_siting, int out_siting);
+/* CHROMA FORMAT (additions to version 4).  The pixel formats name a LAYOUT - semi-planar (NV12 / P010) or planar (I420 / I010) - and a
+ * sample depth; how the chroma planes are subsampled is a value of its own, and 4:2:0 is what every entry without that value means:
+ *   PFNL_CHROMA_420  chroma planes of H/2 rows of W/2 samples: everything stated above;
+ *   PFNL_CHROMA_422  H rows of W/2 samples.  NV12 -> NV16 = Y [H][W], CbCr [H][W/2][2]; I420 -> I422 = Y, Cb [H][W/2], Cr; P010 -> P210
+ *                    (every value << 6); I010 -> yuv422p10le.  2 H W samples a frame; W even and >= 2, H >= 1;
+ *   PFNL_CHROMA_444  H rows of W samples.  NV24 = Y [H][W], CbCr [H][W][2]; I444 = three planes [H][W]; P410; yuv444p10le.  3 H W samples;
+ *                    any H, W >= 1.
+ * The rule is SITING's, applied per axis, and an axis that is not subsampled takes no filter at all (pfnl_amd/yuv.py, pfnl_amd/depth10.py
+ * with chroma = "422" | "444"): in, 4:2:2: (w_near C[near] + w_far C[far] + 2) >> 2 with the horizontal taps of the siting, 4:4:4: the
+ * sample itself; out, 4:2:2: the box (k = 1) or 1-2-1 (k = 2) across and one rounding by 14 + k bits, 4:4:4: (N + 2^13) >> 14.  Of a siting
+ * only the horizontal axis is read at 4:2:2 - LEFT and TOPLEFT are one rule there, CENTER the midway one - and nothing at 4:4:4.  Matrix
+ * and range coefficients are untouched.  A lane converts one luma row by 16, 4 or single pixels (10 bits: 8 or single), in 16-byte words
+ * where the width and every pointer, pitch and frame stride allow (pfnl_amd/csrc/yuv_chroma.hip).
+ *   pfnl_stream_chroma_format: in_chroma for what push takes, out_chroma for what pop delivers, each used where that edge's format is a
+ *     YUV layout and ignored by an RGB edge, as the siting is; push / pop and the surface calls follow it (frame sizes and planes as
+ *     above), and so does every combination a session allows with a YUV edge - 10 bits in and out, scenes, resize, place, ensemble,
+ *     tiling.  It follows pfnl_stream_input_depth's rules of order: whichever of it and pfnl_stream_format / pfnl_stream_resize /
+ *     pfnl_stream_place comes later checks against the other's setting and allocates the staging whose size depends on both; accepted
+ *     only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); it survives pfnl_stream_reset and
+ *     pfnl_stream_format; a failed call leaves the session as it was; NULL and a value outside the enum: PFNL_ERR_INVALID before any
+ *     HIP call.  A session that never calls it, or sets 420 / 420, issues exactly the launches it always issued.
+ *     The output size (and a canvas) is even along the axes the output subsampling halves: both at 4:2:0, the width at 4:2:2, none at
+ *     4:4:4.  Nothing behind the ring or ahead of the quantisation changes.
+ * The op hooks pfnl_op_*_chroma below are the two kernels on their own.
+ * Out of scope: monochrome, 4:1:1, alpha planes, 12 and 16 bits, BT.2020. */
+enum { PFNL_CHROMA_420 = 0, PFNL_CHROMA_422 = 1, PFNL_CHROMA_444 = 2 };
+int pfnl_stream_chroma_format(pfnl_stream* s, int in_chroma, int out_chroma);
 /* SELF-ENSEMBLE in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With
  * n in {2, 4, 8} the one forward of every batch is pfnl_forward_ensemble(..., n, ...) (SELF-ENSEMBLE above); gather, quantisation, the
  * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  n = 1 is
@@ -844,6 +871,23 @@ int pfnl_op_gather_windows_u10(const uint16_t* ring, float* win, int cap, long l
 int pfnl_op_gather_windows_u10_scenes(const uint16_t* ring, const long long* scene_first_dev, float* win, int cap, long long last, long long first,
                                       int count, int T, int H, int W, void* stream);
 int pfnl_op_scene_sad_u10(const uint16_t* a, const uint16_t* b, int H, int W, unsigned long long* out_dev, void* stream);
+/* The six _sited conversion hooks with the subsampling named (CHROMA FORMAT: PFNL_CHROMA_*), ahead of siting; with PFNL_CHROMA_420 each is
+ * its _sited twin, refusals included.  fmt names the layout: PFNL_PIX_NV12 / PFNL_PIX_I420 for the u8 hooks, PFNL_PIX_P010 / PFNL_PIX_I010
+ * for the u10 ones.  yuv holds n frames of 2 H W (4:2:2) or 3 H W (4:4:4) samples, a surface chroma planes of H rows.  Odd W at 4:2:2, an RGB
+ * fmt, chroma / siting / matrix / full_range outside their enums, n < 1, H or W < 1, NULL, a short pitch and an odd pointer or pitch for
+ * 16-bit samples: PFNL_ERR_INVALID before any HIP call, and pfnl_last_error names the argument. */
+int pfnl_op_yuv_to_rgb_u8_chroma(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, int chroma, int siting,
+                                 void* stream);
+int pfnl_op_yuv_to_rgb_u10_chroma(const uint16_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* rgb, int chroma,
+                                  int siting, void* stream);
+int pfnl_op_yuv_to_rgb_u8_surface_chroma(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint8_t* rgb, int chroma,
+                                         int siting, void* stream);
+int pfnl_op_yuv_to_rgb_u10_surface_chroma(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint16_t* rgb, int chroma,
+                                          int siting, void* stream);
+int pfnl_op_rgb_to_yuv_u8_chroma(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, int chroma, int siting,
+                                 void* stream);
+int pfnl_op_rgb_to_yuv_u10_chroma(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, int chroma,
+                                  int siting, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

@@ -163,6 +163,13 @@ SIGNATURES = {
     "pfnl_yuv10_decode_coefficients": (_i, [_i, _i, C.POINTER(C.c_int32)]),
     "pfnl_op_yuv420_to_rgb_u10_sited": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "pfnl_op_yuv420_to_rgb_u10_surface_sited": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "pfnl_stream_chroma_format": (_i, [_vp, _i, _i]),
+    "pfnl_op_yuv_to_rgb_u8_chroma": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "pfnl_op_yuv_to_rgb_u10_chroma": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "pfnl_op_yuv_to_rgb_u8_surface_chroma": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "pfnl_op_yuv_to_rgb_u10_surface_chroma": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "pfnl_op_rgb_to_yuv_u8_chroma": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "pfnl_op_rgb_to_yuv_u10_chroma": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "pfnl_op_gather_windows_u10": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows_u10_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_scene_sad_u10": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
@@ -184,6 +191,7 @@ PIXEL_FORMATS = {"rgb24": 0, "nv12": 1, "i420": 2, "rgb10": 3, "p010": 4, "i010"
 TEN_BIT_FORMATS = ("rgb10", "p010", "i010")                # uint16 samples; names of out_format (10-bit input: in_depth)
 FORMATS_420 = ("nv12", "i420", "p010", "i010")             # H * W * 3 / 2 samples, even sizes
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                    # PFNL_MATRIX_*
+CHROMA_FORMATS = {"420": 0, "422": 1, "444": 2}            # PFNL_CHROMA_* (pfnl_amd/yuv.py CHROMAS, in its order)
 CHROMA_SITINGS = {"left": 0, "center": 1, "topleft": 2}    # PFNL_SITING_* (pfnl_amd/yuv.py SITINGS, in its order)
 COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX = 0, 1

@@ -1085,6 +1085,99 @@ int pfnl_op_yuv420_to_rgb_u10_surface_sited(const pfnl_surface* yuv, int fmt, in
     return 0;
 }
 
+// ---- 4:2:2 and 4:4:4: the _sited hooks with the subsampling named (include/pfnl_hip.h CHROMA FORMAT) ------------------------------------
+
+// what the six hooks refuse before any HIP call at PFNL_CHROMA_422 / _444 (at _420 each is its _sited twin); *c = the table of `bits`
+static int chroma_op_refused(const void* a, const void* b, int bits, int fmt, int matrix, int full_range, int n, int H, int W, int chroma,
+                             int siting, pfnl::YuvCoef* c) {
+    if (!a || !b) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (bits == 8 && fmt != PFNL_PIX_NV12 && fmt != PFNL_PIX_I420) return fail(PFNL_ERR_INVALID, "yuv: fmt must be PFNL_PIX_NV12 or PFNL_PIX_I420");
+    if (bits == 10 && fmt != PFNL_PIX_P010 && fmt != PFNL_PIX_I010)
+        return fail(PFNL_ERR_INVALID, "yuv10: fmt must be PFNL_PIX_P010 or PFNL_PIX_I010");
+    if (!pfnl::yuv_coefficients(bits, matrix, full_range, c)) return fail(PFNL_ERR_INVALID, "yuv: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (n < 1 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "yuv: n >= 1, H and W positive");
+    if (chroma == PFNL_CHROMA_422 && (W & 1)) return fail(PFNL_ERR_INVALID, "yuv: W must be even (4:2:2)");
+    return siting_refused(siting);
+}
+
+static int chroma_refused(int chroma) {
+    if (chroma < PFNL_CHROMA_420 || chroma > PFNL_CHROMA_444)
+        return fail(PFNL_ERR_INVALID, "yuv: chroma must be PFNL_CHROMA_420, PFNL_CHROMA_422 or PFNL_CHROMA_444");
+    return 0;
+}
+
+static int aligned16_refused(const void* a, const void* b) {
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 2) return fail(PFNL_ERR_INVALID, "yuv10: uint16 samples are 2-byte aligned");
+    return 0;
+}
+
+int pfnl_op_yuv_to_rgb_u8_chroma(const uint8_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* rgb, int chroma, int siting,
+                                 void* stream) {
+    if (int r = chroma_refused(chroma)) return r;
+    if (chroma == PFNL_CHROMA_420) return pfnl_op_yuv420_to_rgb_u8_sited(yuv, fmt, matrix, full_range, n, H, W, rgb, siting, stream);
+    pfnl::YuvCoef c;
+    if (int r = chroma_op_refused(yuv, rgb, 8, fmt, matrix, full_range, n, H, W, chroma, siting, &c)) return r;
+    HIPCHK(pfnl::launch_yuv_to_rgb_chroma(yuv, rgb, fmt == PFNL_PIX_NV12, c, n, H, W, chroma, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_yuv_to_rgb_u10_chroma(const uint16_t* yuv, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* rgb, int chroma,
+                                  int siting, void* stream) {
+    if (int r = chroma_refused(chroma)) return r;
+    if (chroma == PFNL_CHROMA_420) return pfnl_op_yuv420_to_rgb_u10_sited(yuv, fmt, matrix, full_range, n, H, W, rgb, siting, stream);
+    pfnl::YuvCoef c;
+    if (int r = chroma_op_refused(yuv, rgb, 10, fmt, matrix, full_range, n, H, W, chroma, siting, &c)) return r;
+    if (int r = aligned16_refused(yuv, rgb)) return r;
+    HIPCHK(pfnl::launch_yuv_to_rgb_chroma(yuv, rgb, fmt == PFNL_PIX_P010, c, n, H, W, chroma, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_yuv_to_rgb_u8_surface_chroma(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint8_t* rgb, int chroma,
+                                         int siting, void* stream) {
+    if (int r = chroma_refused(chroma)) return r;
+    if (chroma == PFNL_CHROMA_420) return pfnl_op_yuv420_to_rgb_u8_surface_sited(yuv, fmt, matrix, full_range, H, W, rgb, siting, stream);
+    pfnl::YuvCoef c;
+    if (int r = chroma_op_refused(yuv, rgb, 8, fmt, matrix, full_range, 1, H, W, chroma, siting, &c)) return r;
+    if (const char* why = pfnl::surface_refused(yuv, fmt, H, W, chroma)) return fail(PFNL_ERR_INVALID, why);
+    HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(*yuv, fmt == PFNL_PIX_NV12), rgb, fmt == PFNL_PIX_NV12, c, 1, H, W, chroma,
+                                                 siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_yuv_to_rgb_u10_surface_chroma(const pfnl_surface* yuv, int fmt, int matrix, int full_range, int H, int W, uint16_t* rgb, int chroma,
+                                          int siting, void* stream) {
+    if (int r = chroma_refused(chroma)) return r;
+    if (chroma == PFNL_CHROMA_420) return pfnl_op_yuv420_to_rgb_u10_surface_sited(yuv, fmt, matrix, full_range, H, W, rgb, siting, stream);
+    pfnl::YuvCoef c;
+    if (int r = chroma_op_refused(yuv, rgb, 10, fmt, matrix, full_range, 1, H, W, chroma, siting, &c)) return r;
+    if (int r = aligned16_refused(rgb, nullptr)) return r;
+    if (const char* why = pfnl::surface_refused(yuv, fmt, H, W, chroma)) return fail(PFNL_ERR_INVALID, why);
+    HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(*yuv, fmt == PFNL_PIX_P010), rgb, fmt == PFNL_PIX_P010, c, 1, H, W, chroma,
+                                                 siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_rgb_to_yuv_u8_chroma(const uint8_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint8_t* yuv, int chroma, int siting,
+                                 void* stream) {
+    if (int r = chroma_refused(chroma)) return r;
+    if (chroma == PFNL_CHROMA_420) return pfnl_op_rgb_to_yuv420_u8_sited(rgb, fmt, matrix, full_range, n, H, W, yuv, siting, stream);
+    pfnl::YuvCoef c;
+    if (int r = chroma_op_refused(rgb, yuv, 8, fmt, matrix, full_range, n, H, W, chroma, siting, &c)) return r;
+    HIPCHK(pfnl::launch_rgb_to_yuv_chroma(rgb, yuv, fmt == PFNL_PIX_NV12, c, n, H, W, chroma, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_rgb_to_yuv_u10_chroma(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, int chroma,
+                                  int siting, void* stream) {
+    if (int r = chroma_refused(chroma)) return r;
+    if (chroma == PFNL_CHROMA_420) return pfnl_op_rgb_to_yuv420_u10_sited(rgb, fmt, matrix, full_range, n, H, W, yuv, siting, stream);
+    pfnl::YuvCoef c;
+    if (int r = chroma_op_refused(rgb, yuv, 10, fmt, matrix, full_range, n, H, W, chroma, siting, &c)) return r;
+    if (int r = aligned16_refused(rgb, yuv)) return r;
+    HIPCHK(pfnl::launch_rgb_to_yuv_chroma(rgb, yuv, fmt == PFNL_PIX_P010, c, n, H, W, chroma, siting, (hipStream_t)stream));
+    return 0;
+}
+
 // as pfnl_op_gather_windows_u8: what both gathers refuse before any HIP call (scene_first: null for the plain one)
 static int gather_u10_refused(const uint16_t* ring, const long long* scene_first, const float* win, int cap, long long last, long long first,
                               int count, int T, int H, int W) {

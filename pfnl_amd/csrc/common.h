@@ -221,6 +221,24 @@ hipError_t launch_yuv420_planes_to_rgb_u10(const YuvPlanes& src, uint16_t* rgb, 
 hipError_t launch_rgb_to_yuv420(const uint8_t* rgb, uint8_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);
 hipError_t launch_rgb_to_yuv420(const uint16_t* rgb, uint16_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int siting, hipStream_t s);
 
+// ---- YUV 4:2:2 / 4:4:4 <-> RGB (yuv_chroma.hip; the same rule with chroma = "422" | "444", the same tables) ----
+// chroma: PFNL_CHROMA_422 | PFNL_CHROMA_444 (4:2:0 is the launchers above; anything else is hipErrorInvalidValue); semiplanar: NV16 / NV24
+// (16-bit samples: P210 / P410, the value in the upper ten bits), else I422 / I444.  The chroma planes of YuvPlanes then have H rows of
+// W / 2 | W samples (interleaved: W | 2 W), a packed frame 2 H W | 3 H W samples.  4:2:2: W even; 4:4:4: any H, W >= 1.  Of the siting only
+// the horizontal axis is read, and at 4:2:2 alone.  Words where W and every pointer, pitch and frame stride allow, as above.
+hipError_t launch_yuv_planes_to_rgb_chroma(const YuvPlanes& src, uint8_t* rgb, bool semiplanar, const YuvCoef& c, int n, int H, int W, int chroma,
+                                           int siting, hipStream_t s);
+hipError_t launch_yuv_planes_to_rgb_chroma(const YuvPlanes& src, uint16_t* rgb, bool semiplanar, const YuvCoef& c, int n, int H, int W, int chroma,
+                                           int siting, hipStream_t s);
+hipError_t launch_yuv_to_rgb_chroma(const uint8_t* yuv, uint8_t* rgb, bool semiplanar, const YuvCoef& c, int n, int H, int W, int chroma, int siting,
+                                    hipStream_t s);
+hipError_t launch_yuv_to_rgb_chroma(const uint16_t* yuv, uint16_t* rgb, bool semiplanar, const YuvCoef& c, int n, int H, int W, int chroma, int siting,
+                                    hipStream_t s);
+hipError_t launch_rgb_to_yuv_chroma(const uint8_t* rgb, uint8_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int chroma, int siting,
+                                    hipStream_t s);
+hipError_t launch_rgb_to_yuv_chroma(const uint16_t* rgb, uint16_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int chroma, int siting,
+                                    hipStream_t s);
+
 // ---- RGB frames at a chosen raster: the tap tables (resize.hip; the rule: pfnl_amd/resize.py) ----
 constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in
 constexpr int RESIZE_TW = 64;            // output pixels of one workgroup: across,

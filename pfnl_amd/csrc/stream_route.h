@@ -1,6 +1,6 @@
 // THE OUTPUT ROUTE OF A STREAMING SESSION (include/pfnl_hip.h pfnl_stream_format / pfnl_stream_resize): what a batch goes through between
-// the fp32 result and pop - stage 0 quantise -> stage 1 resize (or a placement on a canvas: pfnl_stream_place) -> stage 2 RGB -> 4:2:0, at 1
-// or 2 bytes per sample -, the bytes of a frame behind each stage, which stage pop reads, the one check of a (formats, size) setting that
+// the fp32 result and pop - stage 0 quantise -> stage 1 resize (or a placement on a canvas: pfnl_stream_place) -> stage 2 RGB -> YUV at the
+// session's output subsampling (pfnl_stream_chroma_format; 4:2:0 unless it says otherwise), at 1 or 2 bytes per sample -, the bytes of a frame behind each stage, which stage pop reads, the one check of a (formats, size) setting that
 // needs no session, and the one check of a placement's rectangles.  No HIP types and no HIP runtime calls: a plain C++ program can include
 // this file and walk the rule (tests/test_route_host.py and tests/test_place_host.py do).
 #pragma once
@@ -10,8 +10,10 @@ namespace pfnl {
 
 inline bool is_10bit(int fmt) { return fmt == PFNL_PIX_RGB10 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
 inline bool is_420(int fmt) { return fmt == PFNL_PIX_NV12 || fmt == PFNL_PIX_I420 || fmt == PFNL_PIX_P010 || fmt == PFNL_PIX_I010; }
+inline bool is_yuv(int fmt) { return is_420(fmt); }   // the YUV layouts: 4:2:0 by name, at any subsampling with PFNL_CHROMA_*
+inline bool is_chroma(int chroma) { return chroma >= PFNL_CHROMA_420 && chroma <= PFNL_CHROMA_444; }
 
-constexpr int ROUTE_STAGES = 3;   // 0 quantise (always) | 1 resize (a size is set) | 2 RGB -> 4:2:0 (a 4:2:0 out_fmt)
+constexpr int ROUTE_STAGES = 3;   // 0 quantise (always) | 1 resize (a size is set) | 2 RGB -> YUV (a YUV out_fmt)
 
 struct OutRoute {
     bool runs[ROUTE_STAGES];
@@ -29,17 +31,18 @@ inline size_t packed_bytes(const SurfaceGeom& g) {
     return n;
 }
 
-// sH x sW: the network's raster; oH = oW = 0: no resampling.  Sizes are what route_refused has let through.
-inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW) {
+// sH x sW: the network's raster; oH = oW = 0: no resampling; chroma: the subsampling of a YUV out_fmt.  Sizes are what route_refused has
+// let through.
+inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW, int chroma = PFNL_CHROMA_420) {
     OutRoute r{};
     r.out_h = oH ? oH : sH;
     r.out_w = oW ? oW : sW;
-    const SurfaceGeom g = surface_geom(out_fmt, r.out_h, r.out_w);
+    const SurfaceGeom g = surface_geom(out_fmt, r.out_h, r.out_w, chroma);
     if (!g.planes) return r;
     const int rgb = is_10bit(out_fmt) ? PFNL_PIX_RGB10 : PFNL_PIX_RGB24;
     const SurfaceGeom writes[ROUTE_STAGES] = {surface_geom(rgb, sH, sW), surface_geom(rgb, r.out_h, r.out_w), g};
     r.sample_bytes = g.sample_bytes;
-    r.runs[0] = true, r.runs[1] = oH != 0, r.runs[2] = is_420(out_fmt);
+    r.runs[0] = true, r.runs[1] = oH != 0, r.runs[2] = is_yuv(out_fmt);
     for (int k = 0; k < ROUTE_STAGES; ++k)
         if (r.runs[k]) r.last = k, r.stage_bytes[k] = packed_bytes(writes[k]);
     r.frame_bytes = r.stage_bytes[r.last];
@@ -47,16 +50,20 @@ inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW) {
 }
 
 // nullptr: a session may take in_fmt -> out_fmt and deliver out_h x out_w; else why not.  Both setters ask this before they look at
-// the session's state, each with the other's current setting.
-inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w) {
+// the session's state, each with the other's current setting.  chroma: the subsampling of a YUV out_fmt - the size is even along the axes
+// it halves: both at 4:2:0, the width at 4:2:2, none at 4:4:4.
+inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w, int chroma = PFNL_CHROMA_420) {
+    if (!is_chroma(chroma)) return "chroma format: PFNL_CHROMA_420, PFNL_CHROMA_422 or PFNL_CHROMA_444";
     if (is_10bit(in_fmt))
         return "format: 10-bit input is set with pfnl_stream_input_depth; in_fmt names the layout: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420";
     if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || out_fmt < PFNL_PIX_RGB24 || out_fmt > PFNL_PIX_I010)
         return "format: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420, and as out_fmt PFNL_PIX_RGB10, PFNL_PIX_P010 or PFNL_PIX_I010";
     if (in_fmt != PFNL_PIX_RGB24 && out_fmt == PFNL_PIX_RGB10)
         return "format: PFNL_PIX_RGB10 is delivered for RGB24 input only (a YUV in_fmt pairs with a YUV out_fmt or RGB24)";
-    if (is_420(out_fmt) && ((out_h | out_w) & 1))
+    if (is_yuv(out_fmt) && chroma == PFNL_CHROMA_420 && ((out_h | out_w) & 1))
         return "a YUV output format needs an even output size (pfnl_stream_format, pfnl_stream_resize)";
+    if (is_yuv(out_fmt) && chroma == PFNL_CHROMA_422 && (out_w & 1))
+        return "a 4:2:2 output needs an even output width (pfnl_stream_chroma_format, pfnl_stream_resize)";
     return nullptr;
 }
 

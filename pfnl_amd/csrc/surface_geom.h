@@ -20,10 +20,13 @@ struct SurfaceGeom {
     SurfacePlane plane[3];
 };
 
-// H and W are the frame's (even for the 4:2:0 formats: the entries check that with their own geometry)
-inline SurfaceGeom surface_geom(int fmt, int H, int W) {
+// H and W are the frame's (even for the 4:2:0 formats: the entries check that with their own geometry).  chroma: PFNL_CHROMA_*, the
+// subsampling of a YUV format's chroma planes - H rows at 4:2:2, H rows of twice the samples at 4:4:4; an RGB format ignores it.
+inline SurfaceGeom surface_geom(int fmt, int H, int W, int chroma = PFNL_CHROMA_420) {
     SurfaceGeom g{};
-    if (fmt < PFNL_PIX_RGB24 || fmt > PFNL_PIX_I010 || H < 1 || W < 1) return g;
+    if (fmt < PFNL_PIX_RGB24 || fmt > PFNL_PIX_I010 || H < 1 || W < 1 || chroma < PFNL_CHROMA_420 || chroma > PFNL_CHROMA_444) return g;
+    const int ch = chroma == PFNL_CHROMA_420 ? H / 2 : H;               // rows of a chroma plane,
+    const size_t cw = chroma == PFNL_CHROMA_444 ? (size_t)W : (size_t)W / 2;   // and samples in a row of one
     const size_t b = fmt >= PFNL_PIX_RGB10 ? 2 : 1, w = (size_t)W;
     g.sample_bytes = (int)b;
     if (fmt == PFNL_PIX_RGB24 || fmt == PFNL_PIX_RGB10) {
@@ -32,20 +35,20 @@ inline SurfaceGeom surface_geom(int fmt, int H, int W) {
     } else if (fmt == PFNL_PIX_NV12 || fmt == PFNL_PIX_P010) {
         g.planes = 2;
         g.plane[0] = {H, w * b};
-        g.plane[1] = {H / 2, w * b};                 // Cb and Cr interleaved: W / 2 pairs
+        g.plane[1] = {ch, 2 * cw * b};               // Cb and Cr interleaved: W / 2 pairs (4:4:4: W)
     } else {
         g.planes = 3;
         g.plane[0] = {H, w * b};
-        g.plane[1] = g.plane[2] = {H / 2, w / 2 * b};
+        g.plane[1] = g.plane[2] = {ch, cw * b};
     }
     return g;
 }
 
 // nullptr: `sf` describes a frame of H x W in `fmt`; else what is wrong with it, in words that name the plane or the pitch.  Entries past
 // the format's planes are not looked at.
-inline const char* surface_refused(const pfnl_surface* sf, int fmt, int H, int W) {
+inline const char* surface_refused(const pfnl_surface* sf, int fmt, int H, int W, int chroma = PFNL_CHROMA_420) {
     if (!sf) return "NULL argument";
-    const SurfaceGeom g = surface_geom(fmt, H, W);
+    const SurfaceGeom g = surface_geom(fmt, H, W, chroma);
     if (!g.planes) return "surface: no plane layout for this format and size";
     for (int k = 0; k < g.planes; ++k) {
         if (!sf->plane[k]) return "surface: a plane the format needs is NULL";

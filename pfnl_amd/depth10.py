@@ -1,4 +1,4 @@
-"""Frames at 10 bits, out and in: quantisation, resampling and YUV 4:2:0 both ways, stated once in integers (numpy and Python integers
+"""Frames at 10 bits, out and in: quantisation, resampling and YUV 4:2:0 / 4:2:2 / 4:4:4 both ways, stated once in integers (numpy and Python integers
 only; no device).
 
 The network's result is fp32; the streaming session can deliver it at 10 bits instead of 8 (include/pfnl_hip.h, pfnl_stream_format with
@@ -31,7 +31,10 @@ The input side (pfnl_stream_input_depth; pfnl_amd/csrc/yuv.hip decode, stream.hi
   offset 512 and the clip at 1023; chroma at every luma pixel by yuv.upsample, whose arithmetic does not depend on the depth;
 * ``dequantise10``: v / 1023 in double, rounded once to float32 - what the network sees of a 10-bit sample.
 
-Out of scope: BT.2020 and transfer functions, 12 and 16 bits, 4:2:2 / 4:4:4, pitched planes, sitings other than yuv.SITINGS.
+With ``chroma`` "422" / "444" (yuv.CHROMAS) the same two layouts hold chroma planes of [H][W/2] / [H][W] - ``p010`` is then P210 / P410,
+``i010`` yuv422p10le / yuv444p10le; 2 H W / 3 H W samples - and the rule is yuv.py's: no filter along an axis that is not subsampled.
+
+Out of scope: BT.2020 and transfer functions, 12 and 16 bits, monochrome, 4:1:1 and alpha, pitched planes, sitings other than yuv.SITINGS.
 """
 from __future__ import annotations
 
@@ -95,24 +98,25 @@ def decode_coefficients10(matrix: str, full_range) -> Tuple[int, Tuple[int, ...]
     return y0, (dy, drv, dgu, dgv, dbu)
 
 
-def _geometry(fmt: str, H: int, W: int) -> None:
+def _geometry(fmt: str, H: int, W: int, chroma="420") -> None:
     if fmt not in FORMATS:
         raise ValueError(f"fmt: one of {FORMATS}, got {fmt!r}")
-    if H < 2 or W < 2 or H % 2 or W % 2:
-        raise ValueError(f"H and W must be even and at least 2, got {H} x {W}")
+    _yuv.check_size(H, W, chroma)
 
 
-def frame_samples(H: int, W: int) -> int:
-    return H * W * 3 // 2
+def frame_samples(H: int, W: int, chroma="420") -> int:
+    return _yuv.frame_bytes(H, W, chroma)
 
 
-def planes10(frame, fmt: str, H: int, W: int):
-    """(Y [H,W], Cb [H/2,W/2], Cr [H/2,W/2]) uint16 VALUES in [0, 1023] of one packed frame (any shape with H*W*3/2 samples).  ValueError
+def planes10(frame, fmt: str, H: int, W: int, chroma="420"):
+    """(Y [H,W], Cb [H/2,W/2], Cr [H/2,W/2]) uint16 VALUES in [0, 1023] of one packed frame (any shape with H*W*3/2 samples; Cb and Cr
+    [H,W/2] of 2 H W samples at 4:2:2, [H,W] of 3 H W at 4:4:4).  ValueError
     for a sample that is no 10-bit value in its place: above 1023 (i010), or with one of the low six bits set (p010)."""
-    _geometry(fmt, H, W)
+    _geometry(fmt, H, W, chroma)
+    ch, cw = _yuv.chroma_shape(H, W, chroma)
     flat = np.asarray(frame).reshape(-1)
-    if flat.dtype != np.uint16 or flat.size != frame_samples(H, W):
-        raise ValueError(f"expected {frame_samples(H, W)} uint16 samples, got {flat.dtype} x {flat.size}")
+    if flat.dtype != np.uint16 or flat.size != frame_samples(H, W, chroma):
+        raise ValueError(f"expected {frame_samples(H, W, chroma)} uint16 samples, got {flat.dtype} x {flat.size}")
     sh = SHIFT[fmt]
     if sh and (flat & ((1 << sh) - 1)).any():
         raise ValueError(f"{fmt}: the low {sh} bits of every sample are zero")
@@ -122,35 +126,37 @@ def planes10(frame, fmt: str, H: int, W: int):
     y = flat[:H * W].reshape(H, W)
     c = flat[H * W:]
     if fmt == "p010":
-        c = c.reshape(H // 2, W // 2, 2)
+        c = c.reshape(ch, cw, 2)
         return y, c[..., 0], c[..., 1]
-    c = c.reshape(2, H // 2, W // 2)
+    c = c.reshape(2, ch, cw)
     return y, c[0], c[1]
 
 
-def pack10(Y, Cb, Cr, fmt: str):
-    """[H*3/2, W] uint16: the planes (values in [0, 1023]) as one packed frame."""
+def pack10(Y, Cb, Cr, fmt: str, chroma="420"):
+    """[H*3/2, W] uint16 ([2H, W] at 4:2:2, [3H, W] at 4:4:4): the planes (values in [0, 1023]) as one packed frame."""
     Y, Cb, Cr = (np.asarray(p) for p in (Y, Cb, Cr))
     if Y.ndim != 2:
         raise ValueError("Y must be [H, W]")
     H, W = Y.shape
-    _geometry(fmt, H, W)
-    if Cb.shape != (H // 2, W // 2) or Cr.shape != Cb.shape:
-        raise ValueError("Cb and Cr must be [H/2, W/2]")
+    _geometry(fmt, H, W, chroma)
+    if Cb.shape != _yuv.chroma_shape(H, W, chroma) or Cr.shape != Cb.shape:
+        raise ValueError("Cb and Cr must be [H/2, W/2]" if chroma == "420" else f"Cb and Cr must be {list(_yuv.chroma_shape(H, W, chroma))}")
     for p in (Y, Cb, Cr):
         if p.size and (int(p.min()) < 0 or int(p.max()) > MAXV):
             raise ValueError(f"values must lie in 0 .. {MAXV}")
     Y, Cb, Cr = (p.astype(np.uint16) for p in (Y, Cb, Cr))
     c = np.stack([Cb, Cr], axis=-1) if fmt == "p010" else np.stack([Cb, Cr], axis=0)
-    return (np.concatenate([Y.reshape(-1), c.reshape(-1)]) << SHIFT[fmt]).astype(np.uint16).reshape(H * 3 // 2, W)
+    return (np.concatenate([Y.reshape(-1), c.reshape(-1)]) << SHIFT[fmt]).astype(np.uint16).reshape(frame_samples(H, W, chroma) // W, W)
 
 
 IN_FORMATS = FORMATS + ("rgb10",)                                       # what values10 takes
 
 
-def values10(frame, fmt: str):
+def values10(frame, fmt: str, chroma="420"):
     """The sample values of a packed 10-bit frame as the device takes them, uint16 in [0, 1023], in the frame's shape: ``p010`` sample >> 6
-    (the low six bits are ignored), ``i010`` / ``rgb10`` min(sample, 1023).  Lenient where planes10 refuses."""
+    (the low six bits are ignored), ``i010`` / ``rgb10`` min(sample, 1023).  Lenient where planes10 refuses.  The rule is per sample, so
+    ``chroma`` (checked against yuv.CHROMAS) changes nothing: P210 / P410 are taken as P010 is."""
+    _yuv.chroma_id(chroma)
     if fmt not in IN_FORMATS:
         raise ValueError(f"fmt: one of {IN_FORMATS}, got {fmt!r}")
     frame = np.asarray(frame)
@@ -159,17 +165,18 @@ def values10(frame, fmt: str):
     return frame >> SHIFT["p010"] if fmt == "p010" else np.minimum(frame, np.uint16(MAXV))
 
 
-def to_rgb10(frame, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, siting="left"):
-    """One packed ``p010`` / ``i010`` frame (any shape with H*W*3/2 uint16 samples, taken by values10) -> [H,W,3] uint16 in [0, 1023]."""
-    _geometry(fmt, H, W)
+def to_rgb10(frame, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, siting="left", chroma="420"):
+    """One packed ``p010`` / ``i010`` frame (any shape with H*W*3/2 uint16 samples - 2 H W | 3 H W at 4:2:2 | 4:4:4 - taken by values10) ->
+    [H,W,3] uint16 in [0, 1023]."""
+    _geometry(fmt, H, W, chroma)
     y0, (dy, drv, dgu, dgv, dbu) = decode_coefficients10(matrix, full_range)
     flat = np.asarray(frame).reshape(-1)
-    if flat.dtype != np.uint16 or flat.size != frame_samples(H, W):
-        raise ValueError(f"expected {frame_samples(H, W)} uint16 samples, got {flat.dtype} x {flat.size}")
-    Y, Cb, Cr = planes10(values10(flat, fmt) << SHIFT[fmt], fmt, H, W)
+    if flat.dtype != np.uint16 or flat.size != frame_samples(H, W, chroma):
+        raise ValueError(f"expected {frame_samples(H, W, chroma)} uint16 samples, got {flat.dtype} x {flat.size}")
+    Y, Cb, Cr = planes10(values10(flat, fmt) << SHIFT[fmt], fmt, H, W, chroma)
     yy = dy * (Y.astype(np.int64) - y0)
-    u = _yuv.upsample(Cb, H, W, siting).astype(np.int64) - 512
-    v = _yuv.upsample(Cr, H, W, siting).astype(np.int64) - 512
+    u = _yuv.upsample(Cb, H, W, siting, chroma).astype(np.int64) - 512
+    v = _yuv.upsample(Cr, H, W, siting, chroma).astype(np.int64) - 512
     nums = np.stack([yy + drv * v, yy + dgu * u + dgv * v, yy + dbu * u], axis=-1) + HALF
     assert np.abs(nums).max() < (1 << 31)                               # (over the whole sample cube: at most 36 085 868 + 2^13)
     return np.clip(nums >> F, 0, MAXV).astype(np.uint16)
@@ -184,10 +191,10 @@ def dequantise10(v):
     return (np.minimum(v, np.uint16(MAXV)).astype(np.float64) / float(MAXV)).astype(np.float32)
 
 
-def downsample10(N, siting="left"):
-    """Chroma numerators [H,W] (14 fractional bits, unrounded) -> the plane [H/2, W/2] of values: the siting's filter (left: 1-2-1 over two
-    rows), one rounding."""
-    s, k = _yuv.encode_filter(np.asarray(N, np.int64), siting)
+def downsample10(N, siting="left", chroma="420"):
+    """Chroma numerators [H,W] (14 fractional bits, unrounded) -> the plane [H/2, W/2] ([H, W/2] | [H, W]) of values: the siting's filter
+    (left: 1-2-1 over two rows), one rounding."""
+    s, k = _yuv.encode_filter(np.asarray(N, np.int64), siting, chroma)
     assert np.abs(s).max() + (512 << (F + k)) + (1 << (F + k - 1)) < (1 << 31)
     return np.clip(512 + ((s + (1 << (F + k - 1))) >> (F + k)), 0, MAXV).astype(np.uint16)
 
@@ -201,17 +208,17 @@ def _check_rgb10(rgb10):
     return rgb10
 
 
-def from_rgb10(rgb10, fmt: str, matrix: str = "bt709", full_range=False, siting="left"):
-    """[H,W,3] uint16 with values <= 1023 -> one packed frame [H*3/2, W] uint16 in ``fmt``."""
+def from_rgb10(rgb10, fmt: str, matrix: str = "bt709", full_range=False, siting="left", chroma="420"):
+    """[H,W,3] uint16 with values <= 1023 -> one packed frame [H*3/2, W] uint16 in ``fmt`` ([2H, W] at 4:2:2, [3H, W] at 4:4:4)."""
     rgb10 = _check_rgb10(rgb10)
     H, W = rgb10.shape[:2]
-    _geometry(fmt, H, W)
+    _geometry(fmt, H, W, chroma)
     y0, (yr, yg, yb, cbr, cbg, cbb, crr, crg, crb) = coefficients10(matrix, full_range)
     r, g, b = (rgb10[..., k].astype(np.int64) for k in range(3))
     Y = np.clip((yr * r + yg * g + yb * b + (y0 << F) + HALF) >> F, 0, MAXV)
-    Cb = downsample10(cbr * r + cbg * g + cbb * b, siting)
-    Cr = downsample10(crr * r + crg * g + crb * b, siting)
-    return pack10(Y, Cb, Cr, fmt)
+    Cb = downsample10(cbr * r + cbg * g + cbb * b, siting, chroma)
+    Cr = downsample10(crr * r + crg * g + crb * b, siting, chroma)
+    return pack10(Y, Cb, Cr, fmt, chroma)
 
 
 # ---- resampling --------------------------------------------------------------------------------------------------------------------------

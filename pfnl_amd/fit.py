@@ -11,7 +11,8 @@ for byte, and the rule that turns "contain" / "cover" and a sample aspect ratio 
 * per axis the limits are resize.check_limits between the rectangles' sizes, ceil(n_in / 4) <= n_out <= 2 n_in; frame and canvas are at
   most 16384 a side; a rectangle has h, w >= 1 and lies inside its raster (``check_rects``: pfnl_amd/csrc/stream_route.h place_refused).
 * ``rects(sH, sW, oH, oW, crop, fit, sar, g)`` -> (src, dst), with round(p / q) = (2 p + q) // (2 q), (cy, cx, ch, cw) = ``crop`` or the
-  whole raster, A = cw sar[0], B = ch sar[1] (the picture is A : B on a display of square pixels), g = 2 for a 4:2:0 output, else 1:
+  whole raster, A = cw sar[0], B = ch sar[1] (the picture is A : B on a display of square pixels), g = 2 for a 4:2:0 output, else 1 - or the grid per
+  axis as (gy, gx): (1, 2) for a 4:2:2 output, (1, 1) for 4:4:4 and RGB; below, g is the grid of the axis it stands with:
 
   - fit None: src = crop, dst the whole canvas - the stretch of pfnl_stream_resize;
   - "contain", A oH >= B oW: w = oW, h = min(oH, g max(1, round(oW B / (g A)))); else h = oH, w = min(oW, g max(1, round(oH A / (g B))));
@@ -96,10 +97,14 @@ def _round_div(p: int, q: int) -> int:
 def rects(sH: int, sW: int, oH: int, oW: int, crop: Optional[Rect] = None, fit: Optional[str] = None, sar=(1, 1), g: int = 1) -> Tuple[Rect, Rect]:
     """(src, dst) of a picture ``crop`` (None: the whole sH x sW raster) with sample aspect ratio ``sar`` on a canvas of oH x oW; see the
     module's text.  ValueError for an unknown ``fit``, a crop outside the raster and a pair outside the resampler's limits."""
-    sH, sW, oH, oW, g = int(sH), int(sW), int(oH), int(oW), int(g)
+    sH, sW, oH, oW = int(sH), int(sW), int(oH), int(oW)
     if fit not in (None, "contain", "cover"):
         raise ValueError(f'fit: None, "contain" or "cover", got {fit!r}')
-    if g not in (1, 2):
+    try:
+        gy, gx = (int(v) for v in g) if isinstance(g, (tuple, list)) else (int(g), int(g))
+    except (TypeError, ValueError):
+        raise ValueError(f"g: 1, or 2 for a 4:2:0 output, or (gy, gx), got {g!r}") from None
+    if gy not in (1, 2) or gx not in (1, 2):
         raise ValueError(f"g: 1, or 2 for a 4:2:0 output, got {g!r}")
     try:
         s0, s1 = (int(v) for v in sar)
@@ -116,10 +121,10 @@ def rects(sH: int, sW: int, oH: int, oW: int, crop: Optional[Rect] = None, fit: 
     dst = (0, 0, oH, oW)
     if fit == "contain":
         if A * oH >= B * oW:
-            w, h = oW, min(oH, g * max(1, _round_div(oW * B, g * A)))
+            w, h = oW, min(oH, gy * max(1, _round_div(oW * B, gy * A)))
         else:
-            h, w = oH, min(oW, g * max(1, _round_div(oH * A, g * B)))
-        dst = (((oH - h) // (2 * g)) * g, ((oW - w) // (2 * g)) * g, h, w)
+            h, w = oH, min(oW, gx * max(1, _round_div(oH * A, gx * B)))
+        dst = (((oH - h) // (2 * gy)) * gy, ((oW - w) // (2 * gx)) * gx, h, w)
     elif fit == "cover":
         if A * oH >= B * oW:
             cw2 = min(max(_round_div(ch * s1 * oW, oH * s0), 1), cw)

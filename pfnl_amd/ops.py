@@ -809,6 +809,124 @@ def yuv420_to_rgb10_surface(planes, fmt: str, H: int, W: int, matrix: str = "bt7
     return out.view(H, W, 3)
 
 
+# ---- 4:2:2 and 4:4:4 (include/pfnl_hip.h CHROMA FORMAT): the conversions with the subsampling named ------------------------------------------
+def _chroma_id(chroma):
+    if chroma not in _capi.CHROMA_FORMATS:
+        raise ValueError(f"chroma: one of {sorted(_capi.CHROMA_FORMATS)}, got {chroma!r}")
+    return _capi.CHROMA_FORMATS[chroma]
+
+
+def _yuv_to_rgb(frames, ids, H, W, chroma, siting, out, req, dtype, hook):
+    import torch
+    from . import yuv as _yuv
+    cid, sid = _chroma_id(chroma), _siting_id(siting)
+    src = req(frames, "frames")
+    _yuv.check_size(H, W, chroma)
+    fs = _yuv.frame_bytes(H, W, chroma)
+    n = frames.numel() // fs
+    if n < 1 or n * fs != frames.numel():
+        raise ValueError(f"frames must hold a whole number of frames of {fs} samples, got {frames.numel()} samples")
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=dtype, device=frames.device)
+    elif out.numel() != n * H * W * 3 or out.device != frames.device:
+        raise ValueError("out must hold n * H * W * 3 samples on the frames' device")
+    _capi.check(hook(src, ids[0], ids[1], ids[2], n, H, W, req(out, "out"), cid, sid, _stream(frames)))
+    return out.view(n, H, W, 3)
+
+
+def yuv_to_rgb(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, chroma="420", siting="left", out=None):
+    """yuv420_to_rgb with the subsampling named: n tightly packed frames in the layout ``fmt`` ("nv12" | "i420") at ``chroma`` "420" |
+    "422" (NV16 / I422, 2 H W bytes a frame, W even) | "444" (NV24 / I444, 3 H W bytes, any H and W) -> [n,H,W,3] uint8, byte for byte
+    pfnl_amd/yuv.py to_rgb(..., chroma=) (pfnl_op_yuv_to_rgb_u8_chroma).  Any alignment; ``out``: write there."""
+    import torch
+    lib = _capi.load_library()
+    return _yuv_to_rgb(frames, _yuv_ids(fmt, matrix, full_range), H, W, chroma, siting, out, _req_u8, torch.uint8, lib.pfnl_op_yuv_to_rgb_u8_chroma)
+
+
+def yuv_to_rgb_u10(frames, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, chroma="420", siting="left", out=None):
+    """yuv_to_rgb on uint16 samples: ``fmt`` "p010" (P210 / P410 at 4:2:2 / 4:4:4; the low six bits ignored) | "i010" (yuv422p10le /
+    yuv444p10le; above 1023 = 1023) -> [n,H,W,3] uint16 in 0 .. 1023, sample for sample pfnl_amd/depth10.py to_rgb10(..., chroma=)
+    (pfnl_op_yuv_to_rgb_u10_chroma)."""
+    import torch
+    lib = _capi.load_library()
+    return _yuv_to_rgb(frames, _yuv10_ids(fmt, matrix, full_range), H, W, chroma, siting, out, _req_u16, torch.uint16,
+                       lib.pfnl_op_yuv_to_rgb_u10_chroma)
+
+
+def _yuv_to_rgb_surface(planes, fmt, ids, H, W, chroma, siting, out, req, dtype, hook):
+    import torch
+    from . import surface as _surface
+    cid, sid = _chroma_id(chroma), _siting_id(siting)
+    planes = tuple(planes)
+    for k, p in enumerate(planes):
+        if not (isinstance(p, torch.Tensor) and p.is_cuda and p.device == planes[0].device):
+            raise TypeError(f"plane {k} must be a tensor on the GPU, all on one device")
+    sf = _surface.as_struct(planes, fmt, H, W, chroma)
+    if out is None:
+        out = torch.empty((H, W, 3), dtype=dtype, device=planes[0].device)
+    elif out.numel() != H * W * 3 or out.device != planes[0].device:
+        raise ValueError("out must hold H * W * 3 samples on the planes' device")
+    _capi.check(hook(C.byref(sf), ids[0], ids[1], ids[2], H, W, req(out, "out"), cid, sid, _stream(planes[0])))
+    return out.view(H, W, 3)
+
+
+def yuv_to_rgb_surface(planes, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, chroma="420", siting="left", out=None):
+    """yuv420_to_rgb_surface with the subsampling named: one frame as its planes (pfnl_amd/surface.py plane_shapes(..., chroma)), each a
+    strided uint8 view with a pitch of its own -> [H,W,3] uint8, byte for byte yuv_to_rgb of the packed frame
+    (pfnl_op_yuv_to_rgb_u8_surface_chroma)."""
+    import torch
+    lib = _capi.load_library()
+    return _yuv_to_rgb_surface(planes, fmt, _yuv_ids(fmt, matrix, full_range), H, W, chroma, siting, out, _req_u8, torch.uint8,
+                               lib.pfnl_op_yuv_to_rgb_u8_surface_chroma)
+
+
+def yuv_to_rgb_surface_u10(planes, fmt: str, H: int, W: int, matrix: str = "bt709", full_range=False, chroma="420", siting="left", out=None):
+    """yuv_to_rgb_surface on uint16 planes ("p010" | "i010"; even pointers and pitches) -> [H,W,3] uint16
+    (pfnl_op_yuv_to_rgb_u10_surface_chroma)."""
+    import torch
+    lib = _capi.load_library()
+    return _yuv_to_rgb_surface(planes, fmt, _yuv10_ids(fmt, matrix, full_range), H, W, chroma, siting, out, _req_u16, torch.uint16,
+                               lib.pfnl_op_yuv_to_rgb_u10_surface_chroma)
+
+
+def _rgb_to_yuv(frames, ids, chroma, siting, out, req, dtype, hook):
+    import torch
+    from . import yuv as _yuv
+    cid, sid = _chroma_id(chroma), _siting_id(siting)
+    src = req(frames, "frames")
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("expected [n,H,W,3]")
+    n, H, W, _ = frames.shape
+    _yuv.check_size(H, W, chroma)
+    rows = _yuv.frame_bytes(H, W, chroma) // W
+    if out is None:
+        out = torch.empty((n, rows, W), dtype=dtype, device=frames.device)
+    elif out.numel() != n * rows * W or out.device != frames.device:
+        raise ValueError(f"out must hold n * {rows} * W samples on the frames' device")
+    _capi.check(hook(src, ids[0], ids[1], ids[2], n, H, W, req(out, "out"), cid, sid, _stream(frames)))
+    return out.view(n, rows, W)
+
+
+def rgb_to_yuv(frames, fmt: str, matrix: str = "bt709", full_range=False, chroma="420", siting="left", out=None):
+    """rgb_to_yuv420 with the subsampling named: [n,H,W,3] (or [H,W,3]) uint8 -> [n, H*3/2 | 2H | 3H, W] uint8, tightly packed frames in
+    the layout ``fmt`` at ``chroma``, byte for byte pfnl_amd/yuv.py from_rgb(..., chroma=) (pfnl_op_rgb_to_yuv_u8_chroma).  Any
+    alignment; ``out``: write there."""
+    import torch
+    lib = _capi.load_library()
+    return _rgb_to_yuv(frames, _yuv_ids(fmt, matrix, full_range), chroma, siting, out, _req_u8, torch.uint8, lib.pfnl_op_rgb_to_yuv_u8_chroma)
+
+
+def rgb_to_yuv_u10(frames, fmt: str, matrix: str = "bt709", full_range=False, chroma="420", siting="left", out=None):
+    """rgb_to_yuv on uint16 samples with values 0 .. 1023 -> "p010" (every value << 6) | "i010" at ``chroma``, sample for sample
+    pfnl_amd/depth10.py from_rgb10(..., chroma=) (pfnl_op_rgb_to_yuv_u10_chroma)."""
+    import torch
+    lib = _capi.load_library()
+    return _rgb_to_yuv(frames, _yuv10_ids(fmt, matrix, full_range), chroma, siting, out, _req_u16, torch.uint16,
+                       lib.pfnl_op_rgb_to_yuv_u10_chroma)
+
+
 def _ring_u10(ring, name):
     _req_u16(ring, "ring")
     if ring.dim() != 4 or ring.shape[3] != 3:

@@ -21,6 +21,11 @@ uint8, or flat - and returns SR frames ``(sH*3//2, sW)`` for an encoder; ``"i420
 (``matrix`` "bt601" | "bt709", ``full_range``; chroma sited left, or where ``chroma_siting`` / ``out_chroma_siting`` say: "center" is what
 JPEG and a Y4M stream's default ``C420jpeg`` mean, "topleft" UHD HEVC and ``C420paldv``); the ring, the scenes and the windows go on seeing RGB.
 
+4:2:2 and 4:4:4 (off by default): ``open_stream(H, W, batch, pixel_format="i420", chroma="422")`` takes and delivers the layout at that
+subsampling (pfnl_amd/yuv.py CHROMAS) - "i420" is then I422 / I444, "nv12" NV16 / NV24, and with ``in_depth=10`` / a 10-bit ``out_format``
+yuv422p10le / yuv444p10le, P210 / P410: frames of ``(2*H, W)`` / ``(3*H, W)`` samples, or flat.  ``out_chroma`` sets the output side apart
+(None = the input's).  An axis that is not subsampled takes no filter; the output size is even along the axes that are.
+
 Output size (off by default): ``open_stream(H, W, batch, out_size=(1080, 1920))`` delivers every frame at that raster - ``(oH, oW, 3)``, or
 ``(oH*3//2, oW)`` in a 4:2:0 output format (then both even) - resampled on the device behind the quantisation and ahead of the YUV conversion by
 the integer rule of pfnl_amd/resize.py (a Keys cubic that widens when the raster shrinks): each axis between a quarter and twice the
@@ -102,11 +107,11 @@ def pushed_format(pixel_format: str, in_depth: int = 8) -> str:
     return IN_LAYOUTS[pixel_format] if depth_argument(in_depth) == 10 else pixel_format
 
 
-def frame_argument(frame, pixel_format: str, H: int, W: int, in_depth: int = 8):
+def frame_argument(frame, pixel_format: str, H: int, W: int, in_depth: int = 8, chroma: str = "420"):
     """``frame`` as ``push`` hands it on - a contiguous numpy array, or a contiguous tensor where it was one - after the checks that need
     no session: uint8 samples, uint16 at an input depth of 10, in one of ``frame_shapes``; ValueError otherwise."""
     layout = pushed_format(pixel_format, in_depth)
-    shapes = frame_shapes(layout, H, W)
+    shapes = frame_shapes(layout, H, W, chroma)
     name = np.dtype(frame_dtype(layout)).name
     if type(frame).__module__.startswith("torch"):
         if str(frame.dtype) != "torch." + name or tuple(frame.shape) not in shapes:
@@ -129,7 +134,26 @@ def siting_arguments(chroma_siting="left", out_chroma_siting=None) -> Tuple[int,
     return _capi.CHROMA_SITINGS[chroma_siting], _capi.CHROMA_SITINGS[out_chroma_siting]
 
 
-def resize_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24") -> Tuple[int, int]:
+def chroma_arguments(chroma="420", out_chroma=None) -> Tuple[int, int]:
+    """The two arguments of pfnl_stream_chroma_format for open_stream's keywords (``out_chroma`` None = ``chroma``); ValueError for
+    anything the library would refuse.  Needs no device."""
+    if out_chroma is None:
+        out_chroma = chroma
+    for name, value in (("chroma", chroma), ("out_chroma", out_chroma)):
+        if not isinstance(value, str) or value not in _capi.CHROMA_FORMATS:
+            raise ValueError(f"{name}: one of {sorted(_capi.CHROMA_FORMATS)}, got {value!r}")
+    return _capi.CHROMA_FORMATS[chroma], _capi.CHROMA_FORMATS[out_chroma]
+
+
+def output_grid(out_format: str, out_chroma: str = "420") -> Tuple[int, int]:
+    """(gy, gx): what the delivered size is a multiple of per axis - 2 along the axes a YUV ``out_format`` subsamples, else 1."""
+    chroma_arguments(out_chroma)
+    if out_format not in _capi.FORMATS_420:
+        return 1, 1
+    return {"420": (2, 2), "422": (1, 2), "444": (1, 1)}[out_chroma]
+
+
+def resize_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24", out_chroma: str = "420") -> Tuple[int, int]:
     """The two arguments of pfnl_stream_resize for open_stream's ``out_size`` (None = off = (0, 0)) behind a network output of sH x sW;
     ValueError for anything the library would refuse.  Needs no device."""
     if out_size is None:
@@ -140,12 +164,15 @@ def resize_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24") -> T
         raise ValueError(f"out_size: None or (oH, oW), got {out_size!r}") from None
     _resize.check_limits(sH, oH)
     _resize.check_limits(sW, oW)
-    if out_format in _capi.FORMATS_420 and (oH % 2 or oW % 2):
-        raise ValueError(f"out_size: a {out_format} output needs even sizes, got {oH} x {oW}")
+    gy, gx = output_grid(out_format, out_chroma)
+    if oH % gy or oW % gx:
+        raise ValueError(f"out_size: a {out_format} output needs even sizes, got {oH} x {oW}" if (gy, gx) == (2, 2) else
+                         f"out_size: a 4:2:2 {out_format} output needs an even width, got {oH} x {oW}")
     return oH, oW
 
 
-def placement_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24", crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0)):
+def placement_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24", crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
+                        out_chroma: str = "420"):
     """``(oH, oW, src, dst, fill)`` for open_stream's ``out_size``, ``crop``, ``fit``, ``place``, ``sar`` and ``fill`` behind a network output
     of sH x sW: the arguments of pfnl_stream_place, rectangles as (y, x, h, w).  With ``crop``, ``fit`` and ``place`` at their defaults src and
     dst are None and (oH, oW) is resize_arguments' answer - pfnl_stream_resize, or no call at all for (0, 0).  The canvas is ``out_size``, else
@@ -163,7 +190,7 @@ def placement_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24", c
         raise ValueError(f"sar: two positive integers, got {sar!r}")
     if sar[0] != sar[1] and fit is None:
         raise ValueError('sar goes with fit="contain" or "cover"')
-    oH, oW = resize_arguments(out_size, sH, sW, out_format) if crop is None and fit is None and place is None else (0, 0)
+    oH, oW = resize_arguments(out_size, sH, sW, out_format, out_chroma) if crop is None and fit is None and place is None else (0, 0)
     if crop is None and fit is None and place is None:
         return oH, oW, None, None, fill
     src = _fit.as_rect(crop, "crop", sH, sW)
@@ -174,9 +201,11 @@ def placement_arguments(out_size, sH: int, sW: int, out_format: str = "rgb24", c
             oH, oW = (int(v) for v in out_size)
         except (TypeError, ValueError):
             raise ValueError(f"out_size: None or (oH, oW), got {out_size!r}") from None
-    g = 2 if out_format in _capi.FORMATS_420 else 1
-    if g == 2 and (oH % 2 or oW % 2):
-        raise ValueError(f"a {out_format} output needs an even canvas, got {oH} x {oW}")
+    g = output_grid(out_format, out_chroma)
+    if oH % g[0] or oW % g[1]:
+        raise ValueError(f"a {out_format} output needs an even canvas, got {oH} x {oW}" if g == (2, 2) else
+                         f"a 4:2:2 {out_format} output needs a canvas of even width, got {oH} x {oW}")
+    g = g[0] if g[0] == g[1] else g
     if place is not None:
         dst = _fit.as_rect(place, "place", oH, oW)
         _fit.check_rects(sH, sW, oH, oW, src, dst)
@@ -198,12 +227,15 @@ def tiling_argument(H: int, W: int, tile_h, tile_w, pad=0, batch=0) -> Tuple[int
     return _tiles.check(int(H), int(W), (tile_h, tile_w, pad, batch))
 
 
-def frame_shapes(pixel_format: str, H: int, W: int) -> Tuple[tuple, ...]:
+def frame_shapes(pixel_format: str, H: int, W: int, chroma: str = "420") -> Tuple[tuple, ...]:
     """The shapes a frame of H x W pixels may have: ``(H, W, 3)`` for rgb24 and rgb10; ``(H*3//2, W)`` or flat for the 4:2:0 formats
-    (in samples: uint8, or uint16 for the 10-bit formats - ``frame_dtype``)."""
+    (in samples: uint8, or uint16 for the 10-bit formats - ``frame_dtype``); ``(2*H, W)`` / ``(3*H, W)`` or flat with ``chroma`` "422" /
+    "444"."""
+    chroma_arguments(chroma)
     if pixel_format in ("rgb24", "rgb10"):
         return ((H, W, 3),)
-    return ((H * 3 // 2, W), (H * W * 3 // 2,))
+    rows = {"420": H * 3 // 2, "422": 2 * H, "444": 3 * H}[chroma]
+    return ((rows, W), (rows * W,))
 
 
 def frame_dtype(pixel_format: str):
@@ -245,21 +277,27 @@ class VideoStream:
     ``chroma_siting`` / ``out_chroma_siting`` ("left" | "center" | "topleft"; ``out_chroma_siting`` None = the same): where the chroma
     samples of a 4:2:0 ``pixel_format`` / ``out_format`` sit (pfnl_amd/yuv.py SITINGS); an RGB side ignores its siting.
 
+    ``chroma`` / ``out_chroma`` ("420" | "422" | "444"; ``out_chroma`` None = the same): how the chroma planes of a YUV ``pixel_format`` /
+    ``out_format`` are subsampled (pfnl_amd/yuv.py CHROMAS) - frames of ``(2*H, W)`` / ``(3*H, W)`` samples at "422" / "444"; an RGB side
+    ignores it.  ``vs.chroma`` / ``vs.out_chroma`` are the resolved names.
+
     ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
     (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
-                 chroma_siting="left", out_chroma_siting=None, in_depth=8, ensemble=1):
+                 chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, ensemble=1):
         import torch
         self.in_depth = depth_argument(in_depth)    # (before the engine is touched, as every check of an argument)
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
+        sub = chroma_arguments(chroma, out_chroma)
+        self.chroma, self.out_chroma = chroma, chroma if out_chroma is None else out_chroma
         sit = siting_arguments(chroma_siting, out_chroma_siting)
         self.chroma_siting, self.out_chroma_siting = chroma_siting, chroma_siting if out_chroma_siting is None else out_chroma_siting
         self.ensemble = ensemble_argument(ensemble)
         self.pixel_format, self.out_format = pixel_format, pixel_format if out_format is None else out_format
         oH, oW, self.crop, self.place, self.fill = placement_arguments(out_size, engine.geom.scale * int(H), engine.geom.scale * int(W),
-                                                                       self.out_format, crop, fit, place, sar, fill)
+                                                                       self.out_format, crop, fit, place, sar, fill, self.out_chroma)
         self.out_size = (oH, oW) if oH else None
         self.fit, self.sar = fit, tuple(sar)
         self.matrix, self.full_range = matrix, bool(full_range)
@@ -304,6 +342,12 @@ class VideoStream:
         if sit[0] or sit[1]:                        # (left on both sides: the session as it always was, and no call)
             try:
                 _capi.check(self._lib.pfnl_stream_chroma_siting(s, *sit))
+            except Exception:
+                self.close()
+                raise
+        if sub[0] or sub[1]:                        # (4:2:0 on both sides: the session as it always was, and no call)
+            try:
+                _capi.check(self._lib.pfnl_stream_chroma_format(s, *sub))
             except Exception:
                 self.close()
                 raise
@@ -360,13 +404,13 @@ class VideoStream:
         s = self._handle()
         due = self.ready()
         if type(frame).__module__.startswith("torch"):
-            frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth)
+            frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth, self.chroma)
             if not frame.is_cuda or frame.device.index != self.device.index:
                 raise ValueError(f"tensor on {frame.device}, stream on {self.device} (host frames: numpy arrays)")
             self._device_frames = True
             _capi.check(self._lib.pfnl_stream_push(s, C.c_void_p(frame.data_ptr()), 1))
         else:
-            frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth)
+            frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth, self.chroma)
             self._device_frames = False
             _capi.check(self._lib.pfnl_stream_push(s, frame.ctypes.data_as(C.c_void_p), 0))
         return self.pop_ready(due)
@@ -414,7 +458,7 @@ class VideoStream:
         """The next SR frame as ``(index, frame)``, or None when none is deliverable; waits only for the batch that holds it."""
         s = self._handle()
         oH, oW = self.out_size if self.out_size is not None else (self.scale * self.H, self.scale * self.W)
-        shape = frame_shapes(self.out_format, oH, oW)[0]
+        shape = frame_shapes(self.out_format, oH, oW, self.out_chroma)[0]
         index, got = C.c_longlong(0), C.c_int(0)
         ten = self.out_format in _capi.TEN_BIT_FORMATS
         if self._device_frames:
@@ -441,7 +485,7 @@ class VideoStream:
             self.last_info = (0, 0)
 
     # ---- surfaces: planes with a row pitch (pfnl_amd/surface.py) -------------------------------
-    def _planes_struct(self, planes, fmt, H, W):
+    def _planes_struct(self, planes, fmt, H, W, chroma="420"):
         """(pfnl_surface, on the device?) of a tuple of planes, all numpy arrays or all tensors on the stream's device."""
         on_device = [type(p).__module__.startswith("torch") for p in planes]
         if any(on_device) != all(on_device):
@@ -450,7 +494,7 @@ class VideoStream:
             for p in planes:
                 if not p.is_cuda or p.device.index != self.device.index:
                     raise ValueError(f"tensor on {p.device}, stream on {self.device} (host planes: numpy arrays)")
-        return _surface.as_struct(planes, fmt, H, W), bool(planes) and on_device[0]
+        return _surface.as_struct(planes, fmt, H, W, chroma), bool(planes) and on_device[0]
 
     def push_planes(self, *planes) -> List[tuple]:
         """``push`` of a frame given as its planes in ``pixel_format`` - (Y, CbCr) for nv12, (Y, Cb, Cr) for i420, one (H, W, 3) or (H, 3 W)
@@ -458,7 +502,7 @@ class VideoStream:
         typically views ``surface[:H, :W]`` of a decoder's pitched surface, which is read where it lies.  Returns what ``push`` returns;
         the two may alternate within a sequence."""
         s = self._handle()
-        sf, on_device = self._planes_struct(planes, pushed_format(self.pixel_format, self.in_depth), self.H, self.W)
+        sf, on_device = self._planes_struct(planes, pushed_format(self.pixel_format, self.in_depth), self.H, self.W, self.chroma)
         due = self.ready()
         _capi.check(self._lib.pfnl_stream_push_surface(s, C.byref(sf), 1 if on_device else 0))
         self._device_frames = on_device
@@ -470,7 +514,7 @@ class VideoStream:
         frame's index, or None when no frame is deliverable (then nothing was written)."""
         s = self._handle()
         oH, oW = self.out_size if self.out_size is not None else (self.scale * self.H, self.scale * self.W)
-        sf, on_device = self._planes_struct(planes, self.out_format, oH, oW)
+        sf, on_device = self._planes_struct(planes, self.out_format, oH, oW, self.out_chroma)
         for p in planes:
             if not on_device and not p.flags.writeable:
                 raise ValueError("pop_planes writes into its planes: a read-only array")

@@ -9,7 +9,8 @@ them back, which is what the tests do with them.
 
 Planes of a frame of H x W (``plane_shapes``): rgb24 / rgb10 one plane of H rows of 3 W samples; nv12 / p010 Y with H rows of W and CbCr
 with H/2 rows of W (W/2 interleaved pairs); i420 / i010 Y, then Cb and Cr with H/2 rows of W/2 each.  uint8 samples, uint16 for the 10-bit
-formats.  A plane may be given with its row split into further axes - ``(H, W, 3)``, ``(H/2, W/2, 2)`` - as long as a row is contiguous.
+formats.  With ``chroma`` "422" / "444" (pfnl_amd/yuv.py CHROMAS) the chroma planes of a YUV format have H rows - of W / 2 samples (CbCr: W)
+at 4:2:2, of W (CbCr: 2 W) at 4:4:4 - and W alone is even at 4:2:2, nothing at 4:4:4; an RGB format ignores it.  A plane may be given with its row split into further axes - ``(H, W, 3)``, ``(H/2, W/2, 2)`` - as long as a row is contiguous.
 
 A window of a larger surface is just a view that starts at the window's first sample (even x and y): the frame is then that window."""
 from __future__ import annotations
@@ -22,19 +23,24 @@ import numpy as np
 from . import _capi
 
 
-def plane_shapes(fmt: str, H: int, W: int) -> Tuple[tuple, ...]:
+def plane_shapes(fmt: str, H: int, W: int, chroma: str = "420") -> Tuple[tuple, ...]:
     """Per plane of a frame of H x W in ``fmt``: (rows, samples per row, numpy dtype of a sample)."""
+    from . import yuv as _yuv
     if fmt not in _capi.PIXEL_FORMATS:
         raise ValueError(f"fmt: one of {sorted(_capi.PIXEL_FORMATS)}, got {fmt!r}")
     H, W = int(H), int(W)
-    if H < 1 or W < 1 or (fmt in _capi.FORMATS_420 and (H % 2 or W % 2)):
+    is_yuv = fmt in _capi.FORMATS_420                   # (the YUV layouts: 4:2:0 unless ``chroma`` says otherwise)
+    if H < 1 or W < 1 or (is_yuv and chroma == "420" and (H % 2 or W % 2)):
         raise ValueError(f"H and W must be positive, and even for a 4:2:0 format, got {H} x {W}")
     dt = np.dtype(np.uint16 if fmt in _capi.TEN_BIT_FORMATS else np.uint8)
     if fmt in ("rgb24", "rgb10"):
+        _yuv.chroma_id(chroma)
         return ((H, 3 * W, dt),)
+    _yuv.check_size(H, W, chroma)
+    ch, cw = _yuv.chroma_shape(H, W, chroma)
     if fmt in ("nv12", "p010"):
-        return ((H, W, dt), (H // 2, W, dt))
-    return ((H, W, dt), (H // 2, W // 2, dt), (H // 2, W // 2, dt))
+        return ((H, W, dt), (ch, 2 * cw, dt))
+    return ((H, W, dt), (ch, cw, dt), (ch, cw, dt))
 
 
 def _layout(a):
@@ -47,11 +53,11 @@ def _layout(a):
     return int(a.ctypes.data), a.shape, a.strides, a.dtype.itemsize, a.dtype.name
 
 
-def describe(arrays: Sequence, fmt: str, H: int, W: int) -> Tuple[List[int], List[int]]:
+def describe(arrays: Sequence, fmt: str, H: int, W: int, chroma: str = "420") -> Tuple[List[int], List[int]]:
     """(pointers, pitches in bytes) of the planes ``arrays`` hold for a frame of H x W in ``fmt``.  ValueError for a wrong plane count, a
     wrong dtype or shape, a row that is not contiguous (last-axis stride other than one sample), a negative stride, a row stride below
     the bytes of a row."""
-    shapes = plane_shapes(fmt, H, W)
+    shapes = plane_shapes(fmt, H, W, chroma)
     arrays = tuple(arrays)
     if len(arrays) != len(shapes):
         raise ValueError(f"{fmt} has {len(shapes)} plane(s), got {len(arrays)}")
@@ -77,17 +83,17 @@ def describe(arrays: Sequence, fmt: str, H: int, W: int) -> Tuple[List[int], Lis
     return pointers, pitches
 
 
-def as_struct(arrays: Sequence, fmt: str, H: int, W: int) -> "_capi.pfnl_surface":
+def as_struct(arrays: Sequence, fmt: str, H: int, W: int, chroma: str = "420") -> "_capi.pfnl_surface":
     """``describe`` as the ``pfnl_surface`` the library takes (the arrays must outlive the call it is passed to)."""
-    pointers, pitches = describe(arrays, fmt, H, W)
+    pointers, pitches = describe(arrays, fmt, H, W, chroma)
     pad = 3 - len(pointers)
     return _capi.pfnl_surface((C.c_void_p * 3)(*pointers, *([None] * pad)), (C.c_size_t * 3)(*pitches, *([0] * pad)))
 
 
-def split(frame, fmt: str, H: int, W: int) -> List[np.ndarray]:
+def split(frame, fmt: str, H: int, W: int, chroma: str = "420") -> List[np.ndarray]:
     """The planes of one tightly packed frame (what ``push`` takes and ``pop`` returns; any shape with the frame's samples) as
     (rows, samples) views: the packed frame is its planes one behind the other."""
-    shapes = plane_shapes(fmt, H, W)
+    shapes = plane_shapes(fmt, H, W, chroma)
     flat = np.asarray(frame).reshape(-1)
     if flat.dtype != shapes[0][2] or flat.size != sum(rows * n for rows, n, _ in shapes):
         raise ValueError(f"expected {sum(rows * n for rows, n, _ in shapes)} {shapes[0][2].name} samples, got {flat.size} {flat.dtype.name}")
@@ -118,10 +124,10 @@ def embed(planes: Sequence[np.ndarray], pitches: Sequence[int], fill: int = 0) -
     return out
 
 
-def views(buffers: Sequence, fmt: str, H: int, W: int) -> list:
+def views(buffers: Sequence, fmt: str, H: int, W: int, chroma: str = "420") -> list:
     """The planes inside pitched buffers (uint8 ``[rows, pitch]``, numpy or tensors): strided (rows, samples) views in the format's sample
     type, sharing the buffers' memory - what ``describe``, ``VideoStream.push_planes`` and ``pop_planes`` take."""
-    shapes = plane_shapes(fmt, H, W)
+    shapes = plane_shapes(fmt, H, W, chroma)
     buffers = list(buffers)
     if len(buffers) != len(shapes):
         raise ValueError(f"{fmt} has {len(shapes)} plane(s), got {len(buffers)} buffer(s)")
@@ -137,6 +143,6 @@ def views(buffers: Sequence, fmt: str, H: int, W: int) -> list:
     return out
 
 
-def extract(buffers: Sequence[np.ndarray], fmt: str, H: int, W: int) -> List[np.ndarray]:
+def extract(buffers: Sequence[np.ndarray], fmt: str, H: int, W: int, chroma: str = "420") -> List[np.ndarray]:
     """The planes of pitched numpy buffers as contiguous (rows, samples) arrays of their own."""
-    return [np.ascontiguousarray(v) for v in views(buffers, fmt, H, W)]
+    return [np.ascontiguousarray(v) for v in views(buffers, fmt, H, W, chroma)]

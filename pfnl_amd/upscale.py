@@ -7,7 +7,9 @@ session's ``i420`` frames as they are, converted on the device with that siting 
 as ``i420`` - or ``i010`` with ``--bits 10`` - under a header of the output's raster, siting and aspect.  A ``C420p10`` stream (``ffmpeg
 -pix_fmt yuv420p10le -f yuv4mpegpipe``) is taken at its own depth - uint16 frames into a session opened with ``in_depth=10`` - and wants
 ``--bits 10``: at the default of 8 the ten bits are kept on the way in and cut on the way out.  Y4M carries no matrix: ``--matrix
-auto`` takes BT.601 up to 576 lines and BT.709 above.  ``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
+auto`` takes BT.601 up to 576 lines and BT.709 above.  4:2:2 and 4:4:4 streams (``C422``, ``C444``, ``C422p10``, ``C444p10``) are taken
+where ``--chroma`` names them (or ``any``) - without it such a stream exits 1 naming its tag - and ``--out-chroma`` sets the subsampling of
+the output apart from the input's; a ``C422`` stream is horizontally co-sited, so a 4:2:2 output is written with the siting "left".  ``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
 """
 from __future__ import annotations
 
@@ -27,11 +29,13 @@ def auto_matrix(height: int) -> str:
 
 def session_keywords(header, **session_kw) -> dict:
     """``open_stream``'s keywords for a stream with this header: the caller's (``batch``, ``scene_cut``, ``out_format`` "i420" | "i010",
-    ``out_size``, ``fit``, ``out_chroma_siting``, ``ensemble``, ``matrix`` with "auto", ``full_range`` True to override the header), and from the
-    header the input siting, the range, ``in_depth=10`` for a 10-bit stream (and no such key for an 8-bit one) and - with ``fit`` alone -
-    the sample aspect ratio.  ValueError for what a Y4M stream cannot hold."""
+    ``out_size``, ``fit``, ``out_chroma_siting``, ``out_chroma``, ``ensemble``, ``matrix`` with "auto", ``full_range`` True to override the
+    header), and from the header the input siting, the range, ``in_depth=10`` for a 10-bit stream (and no such key for an 8-bit one),
+    ``chroma`` for a 4:2:2 / 4:4:4 stream (and no such key for a 4:2:0 one; ``out_chroma`` likewise only where the caller names one) and -
+    with ``fit`` alone - the sample aspect ratio.  A 4:2:2 output is co-sited across, as ``C422`` says: ``out_chroma_siting`` becomes "left"
+    where the caller names none.  ValueError for what a Y4M stream cannot hold."""
     kw = dict(session_kw)
-    for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth"):
+    for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth", "chroma"):
         if fixed in kw:
             raise ValueError(f"{fixed} comes from the stream's header")
     kw.setdefault("batch", 1)
@@ -46,6 +50,18 @@ def session_keywords(header, **session_kw) -> dict:
     kw["chroma_siting"] = header.siting
     if header.bits == 10:
         kw["in_depth"] = 10
+    in_chroma = header.chroma
+    if in_chroma != "420":
+        kw["chroma"] = in_chroma
+    if kw.get("out_chroma") is None:
+        kw.pop("out_chroma", None)
+    elif kw["out_chroma"] not in _y4m.CHROMAS:
+        raise ValueError(f"out_chroma: one of {_y4m.CHROMAS}, got {kw['out_chroma']!r}")
+    if kw.get("out_chroma", in_chroma) == "422":
+        if kw.get("out_chroma_siting") is None:
+            kw["out_chroma_siting"] = "left"
+        elif kw["out_chroma_siting"] == "center":
+            raise ValueError("out_chroma_siting: a Y4M C422 stream is horizontally co-sited (\"left\"), got 'center'")
     if kw.get("fit") is not None:
         kw["sar"] = header.sar
     return kw
@@ -65,8 +81,9 @@ def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> i
         if tile is not None:
             vs.set_tiling(*tile)
         out_h, out_w = vs.out_size if vs.out_size is not None else (vs.scale * header.height, vs.scale * header.width)
+        out_chroma = kw.get("out_chroma", kw.get("chroma", "420"))
         writer.write_header(header.for_output(out_w, out_h, siting=vs.out_chroma_siting, bits=10 if kw["out_format"] == "i010" else 8,
-                                              sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw["full_range"]))
+                                              sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw["full_range"], chroma=out_chroma))
 
         def deliver(frames):
             nonlocal done
@@ -131,6 +148,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--out-size", type=_size, default=None, metavar="HxW")
     ap.add_argument("--fit", choices=("contain", "cover"), default=None, help="keep the aspect ratio on the --out-size canvas")
     ap.add_argument("--out-siting", choices=("left", "center", "topleft"), default=None, help="the output's chroma siting (default: the input's)")
+    ap.add_argument("--chroma", choices=("420", "422", "444", "any"), default="420", help="the subsampling of the input stream that is taken")
+    ap.add_argument("--out-chroma", choices=("420", "422", "444"), default=None, help="the output's subsampling (default: the input's)")
     ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1)
     ap.add_argument("--tile", type=_tile, default=None, metavar="TH,TW[,PAD[,BATCH]]")
     return ap
@@ -143,7 +162,7 @@ def main(argv=None) -> int:
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     eng = None
     try:
-        reader = _y4m.Y4MReader(fin, depths=(8, 10))
+        reader = _y4m.Y4MReader(fin, depths=(8, 10), chromas=_y4m.CHROMAS if a.chroma == "any" else (a.chroma,))
         from . import checkpoint, synth
         from .engine import PFNLEngine
         from .spec import PFNLGeometry
@@ -161,7 +180,7 @@ def main(argv=None) -> int:
             eng.set_option("precision", a.precision)
         upscale(reader, _y4m.Y4MWriter(fout), eng.open_stream, tile=a.tile, batch=a.batch, scene_cut=a.scene_cut, matrix=a.matrix,
                 full_range=a.full_range, out_format=OUT_FORMATS[a.bits], out_size=a.out_size, fit=a.fit, out_chroma_siting=a.out_siting,
-                ensemble=a.ensemble)
+                ensemble=a.ensemble, out_chroma=a.out_chroma)
         fout.flush()
     except (ValueError, PFNLHipError) as e:
         print(f"pfnl_amd.upscale: {e}", file=sys.stderr)

@@ -1,4 +1,4 @@
-"""YUV4MPEG2 (Y4M) streams, 4:2:0 (numpy only; no device): what ``ffmpeg -f yuv4mpegpipe`` writes and reads.
+"""YUV4MPEG2 (Y4M) streams, 4:2:0 and - where the caller asks - 4:2:2 / 4:4:4 (numpy only; no device): what ``ffmpeg -f yuv4mpegpipe`` writes and reads.
 
 A stream is one header line and, per frame, a ``FRAME`` line followed by the planes Y [H][W], Cb [H/2][W/2], Cr [H/2][W/2] - exactly the
 streaming session's tightly packed ``i420`` frame (pfnl_amd/yuv.py), so ``Y4MReader`` yields ``(H*3//2, W)`` uint8 arrays that
@@ -14,9 +14,14 @@ The header is ``YUV4MPEG2`` and space-separated tokens up to the newline:
   SITINGS); any other tag (``422``, ``444``, ``mono``, ...) is a ValueError that names it;
 * ``C420p10`` (yuv420p10le) is read where the caller asks for it - ``Y4MReader(f, depths=(8, 10))``; by default it is refused like any
   other tag - and gives ``bits=10``, frames as ``(H*3//2, W)`` little-endian uint16 arrays (the session's ``i010``, taken with
-  ``in_depth=10``) and ``siting="left"``: Y4M's 10-bit tag carries no siting, and left is what HEVC / AV1 encoders mean unless told otherwise.
+  ``in_depth=10``) and ``siting="left"``: Y4M's 10-bit tag carries no siting, and left is what HEVC / AV1 encoders mean unless told otherwise;
+* ``C422``, ``C444``, ``C422p10``, ``C444p10`` are opt-in the same way - ``Y4MReader(f, depths=(8, 10), chromas=("420", "422", "444"))`` - and
+  give ``chroma`` "422" | "444" (pfnl_amd/yuv.py CHROMAS): the planes Y [H][W], Cb, Cr [H][W/2] or [H][W], the session's ``i420`` layout at
+  that subsampling, frames as ``(2*H, W)`` / ``(3*H, W)`` arrays.  ``C422`` is horizontally co-sited: ``siting="left"``; 4:4:4 has no
+  siting and says "left" too.  W is even at 4:2:2 and H anything; a ``C444`` stream may have odd W and H.  The writer adds the ``XYSCSS=``
+  token ffmpeg writes beside these tags (``422``, ``444``, ``422P10``, ``444P10``).
 
-Out of scope: 4:2:2 / 4:4:4 / mono, 12 and 16 bits, interlaced streams, per-frame parameters (they are read and dropped).
+Out of scope: mono, 4:1:1 and alpha, 12 and 16 bits, interlaced streams, per-frame parameters (they are read and dropped).
 """
 from __future__ import annotations
 
@@ -30,6 +35,8 @@ MAX_LINE = 4096                                                         # a head
 SITING_OF_TAG = {"420jpeg": "center", "420": "center", "420mpeg2": "left", "420paldv": "topleft"}
 TAG_OF_SITING = {"center": "420jpeg", "left": "420mpeg2", "topleft": "420paldv"}
 TAG_10BIT = "420p10"
+CHROMAS = ("420", "422", "444")                                         # pfnl_amd/yuv.py CHROMAS
+CHROMA_TAGS = {"422": ("422", 8), "444": ("444", 8), "422p10": ("422", 10), "444p10": ("444", 10)}   # tag -> (chroma, bits)
 RANGE_KEY = "XCOLORRANGE="
 
 
@@ -46,7 +53,8 @@ def _ratio(text: str, what: str) -> Tuple[int, int]:
 @dataclass(frozen=True)
 class Y4MHeader:
     """One stream's parameters.  ``rate`` and ``interlace`` are the ``F`` and ``I`` tokens' values or None where the stream has none;
-    ``extensions`` are the ``X`` tokens verbatim, in order, ``XCOLORRANGE`` among them; ``bits`` is 8, or 10 for a stream the writer makes."""
+    ``extensions`` are the ``X`` tokens verbatim, in order, ``XCOLORRANGE`` among them; ``bits`` is 8, or 10 for a stream the writer makes;
+    ``chroma`` is "420", or "422" | "444" for a stream read with ``chromas`` or made by the writer."""
     width: int
     height: int
     rate: Optional[str] = None
@@ -55,10 +63,17 @@ class Y4MHeader:
     siting: str = "center"
     extensions: Tuple[str, ...] = ()
     bits: int = 8
+    chroma: str = "420"
 
     def __post_init__(self):
-        if self.width < 2 or self.height < 2 or self.width % 2 or self.height % 2:
+        if self.chroma not in CHROMAS:
+            raise ValueError(f"y4m: chroma: one of {CHROMAS}, got {self.chroma!r}")
+        if self.chroma == "420" and (self.width < 2 or self.height < 2 or self.width % 2 or self.height % 2):
             raise ValueError(f"y4m: W and H must be even and at least 2 (4:2:0), got W{self.width} H{self.height}")
+        if self.chroma == "422" and (self.width < 2 or self.height < 1 or self.width % 2):
+            raise ValueError(f"y4m: W must be even and at least 2 and H at least 1 (4:2:2), got W{self.width} H{self.height}")
+        if self.chroma == "444" and (self.width < 1 or self.height < 1):
+            raise ValueError(f"y4m: W and H must be at least 1, got W{self.width} H{self.height}")
         if self.interlace not in (None, "p", "?"):
             raise ValueError(f"y4m: interlaced streams are not supported (I{self.interlace}); deinterlace first")
         if self.siting not in TAG_OF_SITING:
@@ -76,13 +91,18 @@ class Y4MHeader:
         return full
 
     @property
+    def frame_samples(self) -> int:
+        return self.width * self.height * {"420": 3, "422": 4, "444": 6}[self.chroma] // 2
+
+    @property
     def frame_bytes(self) -> int:
-        return self.width * self.height * 3 // 2 * (2 if self.bits == 10 else 1)
+        return self.frame_samples * (2 if self.bits == 10 else 1)
 
     @classmethod
-    def parse(cls, line: bytes, depths: Tuple[int, ...] = (8,)) -> "Y4MHeader":
+    def parse(cls, line: bytes, depths: Tuple[int, ...] = (8,), chromas: Tuple[str, ...] = ("420",)) -> "Y4MHeader":
         """The header of its line (without or with the newline).  ``depths``: the sample depths the caller takes; with 10 among them
-        ``C420p10`` parses to ``bits=10``, ``siting="left"``."""
+        ``C420p10`` parses to ``bits=10``, ``siting="left"``.  ``chromas``: the subsamplings the caller takes; with "422" / "444" among
+        them ``C422`` / ``C444`` (and, with 10 among ``depths``, ``C422p10`` / ``C444p10``) parse to that ``chroma``, ``siting="left"``."""
         try:
             tokens = line.rstrip(b"\n").decode("ascii").split(" ")
         except UnicodeDecodeError:
@@ -91,7 +111,7 @@ class Y4MHeader:
             raise ValueError(f"y4m: the stream does not start with {MAGIC.decode()}")
         width = height = None
         rate = interlace = None
-        sar, siting, ext, bits = (1, 1), "center", [], 8
+        sar, siting, ext, bits, chroma = (1, 1), "center", [], 8, "420"
         for t in tokens[1:]:
             if not t:
                 continue
@@ -111,12 +131,14 @@ class Y4MHeader:
                 sar = _ratio(value, "A")
                 if sar[0] == 0 or sar[1] == 0:
                     sar = (1, 1)
-            elif key == "C" and value == TAG_10BIT and 10 in depths:
-                siting, bits = "left", 10
+            elif key == "C" and value == TAG_10BIT and 10 in depths and "420" in chromas:
+                siting, bits, chroma = "left", 10, "420"
+            elif key == "C" and value in CHROMA_TAGS and CHROMA_TAGS[value][0] in chromas and CHROMA_TAGS[value][1] in depths:
+                siting, (chroma, bits) = "left", CHROMA_TAGS[value]
             elif key == "C":
-                if value not in SITING_OF_TAG:
+                if value not in SITING_OF_TAG or "420" not in chromas:
                     raise ValueError(f"y4m: chroma format C{value} is not supported (8-bit 4:2:0: {', '.join('C' + k for k in SITING_OF_TAG)})")
-                siting = SITING_OF_TAG[value]
+                siting, bits, chroma = SITING_OF_TAG[value], 8, "420"
             elif key == "X":
                 if t.startswith(RANGE_KEY) and t[len(RANGE_KEY):] not in ("FULL", "LIMITED"):
                     raise ValueError(f"y4m: {RANGE_KEY}FULL or {RANGE_KEY}LIMITED, got {t!r}")
@@ -125,7 +147,7 @@ class Y4MHeader:
                 raise ValueError(f"y4m: unknown header token {t!r}")
         if width is None or height is None:
             raise ValueError("y4m: the header needs W and H")
-        return cls(width, height, rate, interlace, sar, siting, tuple(ext), bits)
+        return cls(width, height, rate, interlace, sar, siting, tuple(ext), bits, chroma)
 
     def to_bytes(self) -> bytes:
         """The header line, newline included: W H F I A C, then the extensions."""
@@ -135,21 +157,26 @@ class Y4MHeader:
         if self.interlace is not None:
             t.append("I" + self.interlace)
         t.append(f"A{self.sar[0]}:{self.sar[1]}")
-        t.append("C" + (TAG_10BIT if self.bits == 10 else TAG_OF_SITING[self.siting]))
+        if self.chroma == "420":
+            t.append("C" + (TAG_10BIT if self.bits == 10 else TAG_OF_SITING[self.siting]))
+        else:
+            t.append("C" + self.chroma + ("p10" if self.bits == 10 else ""))
         t += list(self.extensions)
         return (" ".join(t) + "\n").encode("ascii")
 
     def for_output(self, width: int, height: int, siting: Optional[str] = None, bits: int = 8, sar: Optional[Tuple[int, int]] = None,
-                   full_range: Optional[bool] = None) -> "Y4MHeader":
+                   full_range: Optional[bool] = None, chroma: Optional[str] = None) -> "Y4MHeader":
         """The header of the stream made from this one: the new raster, siting, depth and aspect; ``F``, ``I`` and the extensions pass
-        through - but ``XYSCSS``, which restates the chroma format and becomes ``XYSCSS=420P10`` at 10 bits, and the range token where
-        ``full_range`` says otherwise than the stream."""
+        through - but ``XYSCSS``, which restates the chroma format and becomes ``XYSCSS=420P10`` at 10 bits (``422`` / ``444`` /
+        ``422P10`` / ``444P10`` for those tags), and the range token where ``full_range`` says otherwise than the stream.  ``chroma`` None:
+        this stream's."""
+        chroma = self.chroma if chroma is None else chroma
         ext = [x for x in self.extensions if not x.startswith("XYSCSS=")]
         if full_range is not None and bool(full_range) != self.full_range:
             ext = [x for x in ext if not x.startswith(RANGE_KEY)] + [RANGE_KEY + ("FULL" if full_range else "LIMITED")]
-        if bits == 10:
-            ext.insert(0, "XYSCSS=420P10")
-        return replace(self, width=int(width), height=int(height), siting=self.siting if siting is None else siting, bits=bits,
+        if bits == 10 or chroma != "420":
+            ext.insert(0, f"XYSCSS={chroma}" + ("P10" if bits == 10 else ""))
+        return replace(self, width=int(width), height=int(height), siting=self.siting if siting is None else siting, bits=bits, chroma=chroma,
                        sar=self.sar if sar is None else tuple(sar), extensions=tuple(ext))
 
 
@@ -183,14 +210,15 @@ def _read_line(f) -> bytes:
 
 class Y4MReader:
     """``Y4MReader(fileobj)`` reads the header at once (``.header``); iterating yields every frame as a ``(H*3//2, W)`` uint8 array -
-    little-endian uint16 for a ``C420p10`` stream, which ``depths=(8, 10)`` lets through."""
+    little-endian uint16 for a ``C420p10`` stream, which ``depths=(8, 10)`` lets through; ``(2*H, W)`` / ``(3*H, W)`` for a ``C422`` /
+    ``C444`` stream, which ``chromas=("420", "422", "444")`` lets through."""
 
-    def __init__(self, fileobj, depths: Tuple[int, ...] = (8,)):
+    def __init__(self, fileobj, depths: Tuple[int, ...] = (8,), chromas: Tuple[str, ...] = ("420",)):
         self._f = fileobj
         line = _read_line(fileobj)
         if line is None:
             raise ValueError("y4m: empty stream")
-        self.header = Y4MHeader.parse(line, depths)
+        self.header = Y4MHeader.parse(line, depths, chromas)
         self.frames = 0
 
     def read_frame(self):
@@ -205,7 +233,7 @@ class Y4MReader:
         if len(data) != h.frame_bytes:
             raise ValueError(f"y4m: frame {self.frames} is truncated: {len(data)} of {h.frame_bytes} bytes")
         self.frames += 1
-        return np.frombuffer(data, "<u2" if h.bits == 10 else np.uint8).reshape(h.height * 3 // 2, h.width)
+        return np.frombuffer(data, "<u2" if h.bits == 10 else np.uint8).reshape(h.frame_samples // h.width, h.width)
 
     def __iter__(self) -> Iterator[np.ndarray]:
         while True:
@@ -217,7 +245,8 @@ class Y4MReader:
 
 class Y4MWriter:
     """``Y4MWriter(fileobj, header=None)``: ``write_header`` once (at construction where ``header`` is given), then ``write_frame`` per frame:
-    ``(H*3//2, W)`` or flat, uint8 - uint16 values 0 .. 1023 (``i010``) for a 10-bit header, written little-endian."""
+    ``(H*3//2, W)`` or flat (2 H W / 3 H W samples under a 4:2:2 / 4:4:4 header), uint8 - uint16 values 0 .. 1023 (``i010``) for a 10-bit
+    header, written little-endian."""
 
     def __init__(self, fileobj, header: Optional[Y4MHeader] = None):
         self._f = fileobj
@@ -238,8 +267,8 @@ class Y4MWriter:
             raise ValueError("y4m: write_header first")
         frame = np.asarray(frame)
         dtype = np.uint16 if h.bits == 10 else np.uint8
-        if frame.dtype != dtype or frame.size != h.width * h.height * 3 // 2:
-            raise ValueError(f"y4m: expected {h.width * h.height * 3 // 2} {np.dtype(dtype).name} samples, got {frame.dtype} x {frame.size}")
+        if frame.dtype != dtype or frame.size != h.frame_samples:
+            raise ValueError(f"y4m: expected {h.frame_samples} {np.dtype(dtype).name} samples, got {frame.dtype} x {frame.size}")
         self._f.write(b"FRAME\n")
         self._f.write(np.ascontiguousarray(frame).astype("<u2" if h.bits == 10 else np.uint8, copy=False).tobytes())
         self.frames += 1
