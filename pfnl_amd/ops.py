@@ -31,12 +31,22 @@ def _host(a, name) -> Optional[np.ndarray]:
     return np.ascontiguousarray(np.asarray(a), dtype=np.float32)
 
 
+def _out(out, shape, dtype, device, name="out"):
+    """``out`` where the caller gave one (a tensor of exactly that shape and type, written in place), else a fresh tensor."""
+    import torch
+    if out is None:
+        return torch.empty(tuple(shape), dtype=dtype, device=device)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device:
+        raise ValueError(f"{name} must be a {dtype} tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
 def _stream(t):
     import torch
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def conv2d(x, kernel, bias=None, act=True, frames_per_item=1, addend=None, add_div=1, resid=None):
+def conv2d(x, kernel, bias=None, act=True, frames_per_item=1, addend=None, add_div=1, resid=None, out=None):
     """tf.layers.Conv2D(k in {1,3}, 'same') [+ bias] [+ addend] [lrelu] [+ resid] via the MFMA kernel.
 
     x: [items*frames_per_item, H, W, 64] (cuda) viewed as [items, H, W, 64*fpi]; kernel: HWIO host
@@ -50,7 +60,7 @@ def conv2d(x, kernel, bias=None, act=True, frames_per_item=1, addend=None, add_d
     if c != 64 or cin != 64 * frames_per_item or F % frames_per_item:
         raise ValueError("conv2d: channel / frame grouping mismatch")
     items = F // frames_per_item
-    out = torch.empty((items, H, W, cout), dtype=torch.float32, device=x.device)
+    out = _out(out, (items, H, W, cout), torch.float32, x.device)
     _capi.check(lib.pfnl_op_conv2d(
         _req(x, "x"), k.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p) if b is not None else None,
         _req(addend, "addend") if addend is not None else None, int(add_div),
@@ -59,7 +69,7 @@ def conv2d(x, kernel, bias=None, act=True, frames_per_item=1, addend=None, add_d
     return out
 
 
-def conv2_grouped(x, base, kernel, bias, resid, frames_per_clip, act=True):
+def conv2_grouped(x, base, kernel, bias, resid, frames_per_clip, act=True, out=None):
     """conv2_i of the reference in one launch: resid + act(conv3x3(concat([base[clip], x[frame]])) + bias).
     x/resid [clips*T, H, W, 64], base [clips, H, W, 64] (cuda); kernel HWIO [3,3,128,64].
     Reference: model/pfnl.py:51, :69-71."""
@@ -70,7 +80,7 @@ def conv2_grouped(x, base, kernel, bias, resid, frames_per_clip, act=True):
     F, H, W, c = x.shape
     if k.shape != (3, 3, 128, 64) or c != 64 or F % frames_per_clip or base.shape != (F // frames_per_clip, H, W, 64):
         raise ValueError("conv2_grouped: geometry mismatch")
-    out = torch.empty_like(x)
+    out = _out(out, x.shape, torch.float32, x.device)
     _capi.check(lib.pfnl_op_conv2_grouped(
         _req(x, "x"), _req(base, "base"), k.ctypes.data_as(C.c_void_p),
         b.ctypes.data_as(C.c_void_p) if b is not None else None, _req(resid, "resid"), _req(out, "out"),
@@ -78,7 +88,7 @@ def conv2_grouped(x, base, kernel, bias, resid, frames_per_clip, act=True):
     return out
 
 
-def conv3x3_accum(x, kernel, bias=None, act=True, frames_per_clip=1, variant="winograd"):
+def conv3x3_accum(x, kernel, bias=None, act=True, frames_per_clip=1, variant="winograd", out=None):
     """convmerge1: 3x3 over the concat of `frames_per_clip` frames, (64*fpc) -> cout <= 64, one accumulating
     launch of the persistent Winograd kernel (variant "winograd": even H, W) or of the split-f16 kernel ("split16").
     x [clips*fpc, H, W, 64] (cuda); kernel HWIO [3,3,64*fpc,cout]; returns [clips, H, W, cout].
@@ -91,7 +101,7 @@ def conv3x3_accum(x, kernel, bias=None, act=True, frames_per_clip=1, variant="wi
     cout = k.shape[3]
     if k.shape[:3] != (3, 3, 64 * frames_per_clip) or c != 64 or F % frames_per_clip or cout > 64:
         raise ValueError("conv3x3_accum: geometry mismatch")
-    out = torch.empty((F // frames_per_clip, H, W, 64), dtype=torch.float32, device=x.device)
+    out = _out(out, (F // frames_per_clip, H, W, 64), torch.float32, x.device)    # (all 64 channels; the result is its first cout)
     fn = lib.pfnl_op_conv3x3_accum_split16 if variant == "split16" else lib.pfnl_op_conv3x3_accum
     _capi.check(fn(
         _req(x, "x"), k.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p) if b is not None else None,
@@ -99,7 +109,7 @@ def conv3x3_accum(x, kernel, bias=None, act=True, frames_per_clip=1, variant="wi
     return out[..., :cout]
 
 
-def conv3x3_bf16(x, kernel, bias=None, act=True, addend=None, add_div=1, resid=None):
+def conv3x3_bf16(x, kernel, bias=None, act=True, addend=None, add_div=1, resid=None, out=None):
     """bf16 trunk: 3x3 64->64 'same' convolution on bf16 MFMA, fp32 accumulation; out = act(conv + bias + addend) + resid.
     x / addend / resid / result: bfloat16 [items, H, W, 64] (cuda); kernel fp32 HWIO [3,3,64,64] (rounded inside).
     Reference: model/pfnl.py:49,51 applied at :66,69-71."""
@@ -109,7 +119,7 @@ def conv3x3_bf16(x, kernel, bias=None, act=True, addend=None, add_div=1, resid=N
     F, H, W, c = x.shape
     if k.shape != (3, 3, 64, 64) or c != 64 or (addend is None) != (resid is None):
         raise ValueError("conv3x3_bf16: geometry mismatch")
-    out = torch.empty_like(x)
+    out = _out(out, x.shape, torch.bfloat16, x.device)
     _capi.check(lib.pfnl_op_conv3x3_bf16(
         _req16(x, "x"), k.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p) if b is not None else None,
         _req16(addend, "addend") if addend is not None else None, add_div,
@@ -117,7 +127,7 @@ def conv3x3_bf16(x, kernel, bias=None, act=True, addend=None, add_div=1, resid=N
     return out
 
 
-def conv1_conv10_bf16(x, k1, b1, k10, b10, frames_per_clip):
+def conv1_conv10_bf16(x, k1, b1, k10, b10, frames_per_clip, out1=None, base=None):
     """bf16 trunk: conv1_i + conv10_i in one launch.  x bfloat16 [clips*T, H, W, 64] -> (lrelu(conv3x3(x)+b1) bfloat16,
     lrelu(conv1x1 over the T outputs + b10) bfloat16 [clips, H, W, 64]).  Reference: model/pfnl.py:66-68."""
     import torch
@@ -127,8 +137,8 @@ def conv1_conv10_bf16(x, k1, b1, k10, b10, frames_per_clip):
     T = frames_per_clip
     if k1h.shape != (3, 3, 64, 64) or k10h.shape != (1, 1, 64 * T, 64) or c != 64 or F % T:
         raise ValueError("conv1_conv10_bf16: geometry mismatch")
-    out1 = torch.empty_like(x)
-    base = torch.empty((F // T, H, W, 64), dtype=torch.bfloat16, device=x.device)
+    out1 = _out(out1, x.shape, torch.bfloat16, x.device, "out1")
+    base = _out(base, (F // T, H, W, 64), torch.bfloat16, x.device, "base")
     _capi.check(lib.pfnl_op_conv1_conv10_bf16(
         _req16(x, "x"), k1h.ctypes.data_as(C.c_void_p), b1h.ctypes.data_as(C.c_void_p) if b1h is not None else None,
         k10h.ctypes.data_as(C.c_void_p), b10h.ctypes.data_as(C.c_void_p) if b10h is not None else None,
@@ -136,7 +146,7 @@ def conv1_conv10_bf16(x, k1, b1, k10, b10, frames_per_clip):
     return out1, base
 
 
-def conv3x3_accum_bf16(x, kernel, bias=None, act=True, frames_per_clip=7):
+def conv3x3_accum_bf16(x, kernel, bias=None, act=True, frames_per_clip=7, out=None):
     """bf16 trunk -> convmerge1: 3x3 over the concat of `frames_per_clip` frames, (64*fpc) -> cout <= 64, fp32 out
     [clips, H, W, 64] (channels >= cout hold act(0)).  x bfloat16 [clips*fpc, H, W, 64]; kernel fp32 HWIO [3,3,64*fpc,cout].
     Reference: model/pfnl.py:52, :73-74."""
@@ -147,14 +157,14 @@ def conv3x3_accum_bf16(x, kernel, bias=None, act=True, frames_per_clip=7):
     T = frames_per_clip
     if k.shape[:3] != (3, 3, 64 * T) or k.shape[3] > 64 or c != 64 or F % T:
         raise ValueError("conv3x3_accum_bf16: geometry mismatch")
-    out = torch.empty((F // T, H, W, 64), dtype=torch.float32, device=x.device)
+    out = _out(out, (F // T, H, W, 64), torch.float32, x.device)
     _capi.check(lib.pfnl_op_conv3x3_accum_bf16(
         _req16(x, "x"), k.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p) if b is not None else None,
         _req(out, "out"), F // T, T, H, W, int(k.shape[3]), 1 if act else 0, _stream(x)))
     return out
 
 
-def conv1x1_bf16(x, kernel, bias=None, act=True, frames_per_item=7):
+def conv1x1_bf16(x, kernel, bias=None, act=True, frames_per_item=7, out=None):
     """bf16 trunk: conv10_i, 1x1 over the concat of `frames_per_item` frames.  x bfloat16 [items*fpi, H, W, 64];
     kernel fp32 HWIO [1,1,64*fpi,64].  Reference: model/pfnl.py:50, :67-68."""
     import torch
@@ -164,14 +174,14 @@ def conv1x1_bf16(x, kernel, bias=None, act=True, frames_per_item=7):
     if k.shape != (1, 1, 64 * frames_per_item, 64) or c != 64 or F % frames_per_item:
         raise ValueError("conv1x1_bf16: geometry mismatch")
     items = F // frames_per_item
-    out = torch.empty((items, H, W, 64), dtype=torch.bfloat16, device=x.device)
+    out = _out(out, (items, H, W, 64), torch.bfloat16, x.device)
     _capi.check(lib.pfnl_op_conv1x1_bf16(
         _req16(x, "x"), k.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p) if b is not None else None,
         _req16(out, "out"), items, frames_per_item, H * W, 1 if act else 0, _stream(x)))
     return out
 
 
-def conv1x1_stream(x, kernel, bias=None, act=True, frames_per_item=1, variant="stream"):
+def conv1x1_stream(x, kernel, bias=None, act=True, frames_per_item=1, variant="stream", out=None):
     """conv10_i: 1x1 over the concat of `frames_per_item` frames, (64*fpi) -> 64, streaming kernel.
     x: [items*fpi, H, W, 64] (cuda); kernel HWIO [1,1,64*fpi,64].  Reference: model/pfnl.py:50, :67-68."""
     import torch
@@ -182,7 +192,7 @@ def conv1x1_stream(x, kernel, bias=None, act=True, frames_per_item=1, variant="s
     if k.shape != (1, 1, 64 * frames_per_item, 64) or c != 64 or F % frames_per_item:
         raise ValueError("conv1x1_stream: geometry mismatch")
     items = F // frames_per_item
-    out = torch.empty((items, H, W, 64), dtype=torch.float32, device=x.device)
+    out = _out(out, (items, H, W, 64), torch.float32, x.device)
     if variant.startswith("split16_sf"):                  # "split16_sf:io" - i, o in {0, 1}: input / output in the split format
         i_sf, o_sf = int(variant[-2]), int(variant[-1])
         _capi.check(lib.pfnl_op_conv1x1_split16_sf(
@@ -196,7 +206,7 @@ def conv1x1_stream(x, kernel, bias=None, act=True, frames_per_item=1, variant="s
     return out
 
 
-def conv_small(b, kernel, bias=None, a=None, a_div=1, b_mul=1, resid=None, items=None, act=True):
+def conv_small(b, kernel, bias=None, a=None, a_div=1, b_mul=1, resid=None, items=None, act=True, out=None):
     """The small-shape trunk kernel (conv_small.hip): out[i] = act(sum_s conv(src(i, s)) + bias) (+ resid[i]) with
     src(i, s) = a[i // a_div] for s < nA (nA = 1 if `a` is given) else b[i * b_mul + s - nA]; kernel HWIO [ks, ks, 64 * nsrc, cout]."""
     import torch
@@ -209,7 +219,10 @@ def conv_small(b, kernel, bias=None, a=None, a_div=1, b_mul=1, resid=None, items
     Fb, H, W, c = b.shape
     if items is None:
         items = Fb // b_mul
-    out = torch.zeros((items, H, W, 64), dtype=torch.float32, device=b.device)
+    if out is None:
+        out = torch.zeros((items, H, W, 64), dtype=torch.float32, device=b.device)
+    else:
+        _out(out, (items, H, W, 64), torch.float32, b.device)
     _capi.check(lib.pfnl_op_conv_small(
         _req(a, "a") if a is not None else None, _req(b, "b"), nA, int(a_div), int(b_mul), nsrc, k.ctypes.data_as(C.c_void_p),
         bs.ctypes.data_as(C.c_void_p) if bs is not None else None, _req(resid, "resid") if resid is not None else None,
@@ -217,21 +230,21 @@ def conv_small(b, kernel, bias=None, a=None, a_div=1, b_mul=1, resid=None, items
     return out
 
 
-def conv_small_pf_block(x, k1, b1, k10, b10, k2, b2, T):
+def conv_small_pf_block(x, k1, b1, k10, b10, k2, b2, T, inp1=None, out=None):
     """One progressive-fusion block on the small-shape kernels, two launches (pfnl_op_conv_small_pf_block; reference
     model/pfnl.py:66-71): x [clips*T,H,W,64] (cuda) -> (inp1, x + inp2)."""
     import torch
     lib = _capi.load_library()
     F, H, W, c = x.shape
     hs = [_host(a, n) for a, n in ((k1, "k1"), (b1, "b1"), (k10, "k10"), (b10, "b10"), (k2, "k2"), (b2, "b2"))]
-    inp1 = torch.empty_like(x)
-    out = torch.empty_like(x)
+    inp1 = _out(inp1, x.shape, torch.float32, x.device, "inp1")
+    out = _out(out, x.shape, torch.float32, x.device)
     _capi.check(lib.pfnl_op_conv_small_pf_block(_req(x, "x"), *[a.ctypes.data_as(C.c_void_p) for a in hs], _req(inp1, "inp1"), _req(out, "out"),
                                                 F // T, int(T), H, W, _stream(x)))
     return inp1, out
 
 
-def conv3x3_winograd(x, kernel, bias=None, act=True, addend=None, add_div=1, resid=None, variant="winograd"):
+def conv3x3_winograd(x, kernel, bias=None, act=True, addend=None, add_div=1, resid=None, variant="winograd", out=None):
     """The 3x3 64->64 'same' convolution through the fused Winograd F(2x2,3x3) kernel (even H, W)."""
     import torch
     lib = _capi.load_library()
@@ -240,7 +253,7 @@ def conv3x3_winograd(x, kernel, bias=None, act=True, addend=None, add_div=1, res
     if k.shape != (3, 3, 64, 64) and variant != "split16_sf_chain":
         raise ValueError("winograd path is 3x3, 64 -> 64 only")
     F, H, W, c = x.shape
-    out = torch.empty((F, H, W, 64), dtype=torch.float32, device=x.device)
+    out = _out(out, (F, H, W, 64), torch.float32, x.device)
     if variant in ("split16_sf_in", "split16_sf_out", "split16_sf_chain"):   # the split-format kernels (conv_sf.hip / conv1_i writing SF), fp32 at this interface
         if variant != "split16_sf_chain" and k.shape != (3, 3, 64, 64):
             raise ValueError("3x3, 64 -> 64 only")
@@ -259,7 +272,7 @@ def conv3x3_winograd(x, kernel, bias=None, act=True, addend=None, add_div=1, res
     return out
 
 
-def nonlocal_residual(x, wg, bg, ww, bw, precision="fp32"):
+def nonlocal_residual(x, wg, bg, ww, bw, precision="fp32", out=None):
     """x [B,T,H,W,3] (cuda) -> [B,H,W,3T] = stack + depth_to_space(NonLocalBlock(space_to_depth(stack)))
     (reference utils.py:18-71 with nltype=1, model/pfnl.py:55-60)."""
     import torch
@@ -269,21 +282,21 @@ def nonlocal_residual(x, wg, bg, ww, bw, precision="fp32"):
     arrs = [_host(a, n) for a, n in ((wg, "wg"), (bg, "bg"), (ww, "ww"), (bw, "bw"))]
     if arrs[0].size != C_ * C_ or arrs[2].size != C_ * C_ or arrs[1].size != C_ or arrs[3].size != C_:
         raise ValueError("nonlocal: weight shapes do not match 12*T channels")
-    out = torch.empty((B, H, W, 3 * T), dtype=torch.float32, device=x.device)
+    out = _out(out, (B, H, W, 3 * T), torch.float32, x.device)
     fn = {"split16": lib.pfnl_op_nonlocal_split16, "f16": lib.pfnl_op_nonlocal_f16}.get(precision, lib.pfnl_op_nonlocal)
     _capi.check(fn(_req(x, "x"), *[a.ctypes.data_as(C.c_void_p) for a in arrs],
                                      _req(out, "out"), B, T, H, W, _stream(x)))
     return out
 
 
-def bicubic(x, scale: int):
+def bicubic(x, scale: int, out=None):
     """TF1.12 legacy ResizeBicubic (reference model/pfnl.py:63): x [B,H,W,3] (cuda) -> [B,sH,sW,3]."""
     import torch
     lib = _capi.load_library()
     B, H, W, c = x.shape
     if c != 3:
         raise ValueError("bicubic expects 3 channels")
-    out = torch.empty((B, scale * H, scale * W, 3), dtype=torch.float32, device=x.device)
+    out = _out(out, (B, scale * H, scale * W, 3), torch.float32, x.device)
     _capi.check(lib.pfnl_op_bicubic(_req(x, "x"), _req(out, "out"), B, H, W, scale, _stream(x)))
     return out
 
@@ -375,14 +388,14 @@ def tile_scatter(y, out, tile, scale: int, first: int = 0):
     return out
 
 
-def blur_decimate(hr, scale: int = 4):
+def blur_decimate(hr, scale: int = 4, out=None):
     """reference utils.py:169-192 (DownSample_4D with BLUR): hr [F,H,W,3] (cuda) -> [F,ceil(H/s),ceil(W/s),3]."""
     import torch
     lib = _capi.load_library()
     F, H, W, c = hr.shape
     if c != 3:
         raise ValueError("blur_decimate expects 3 channels")
-    out = torch.empty((F, -(-H // scale), -(-W // scale), 3), dtype=torch.float32, device=hr.device)
+    out = _out(out, (F, -(-H // scale), -(-W // scale), 3), torch.float32, hr.device)
     _capi.check(lib.pfnl_op_blur_decimate(_req(hr, "hr"), _req(out, "out"), F, H, W, scale, _stream(hr)))
     return out
 
@@ -411,7 +424,7 @@ def nonlocal_embedded(x, wg, bg, ww, bw, wt, bt, wp, bp):
     return out
 
 
-def conv1_conv10_split16(x, k1, b1, k10, b10, frames_per_clip: int, sf0: bool = False):
+def conv1_conv10_split16(x, k1, b1, k10, b10, frames_per_clip: int, sf0: bool = False, out1=None, base=None):
     """conv1_i + conv10_i of a progressive-fusion block as one launch (reference model/pfnl.py:66-68): x [clips*T,H,W,64] (cuda) ->
     (inp1 [clips*T,H,W,64], base [clips,H,W,64]), both activated; k1 HWIO [3,3,64,64], k10 HWIO [1,1,64T,64].  sf0: the input is
     converted to the split format first and the kernel takes its halo from there by LDS-DMA (bit-identical results)."""
@@ -422,8 +435,8 @@ def conv1_conv10_split16(x, k1, b1, k10, b10, frames_per_clip: int, sf0: bool = 
     k1h, k10h = _host(k1, "k1"), _host(k10, "k10")
     if c != 64 or F % T or k1h.size != 9 * 64 * 64 or k10h.size != 64 * T * 64:
         raise ValueError("conv1_conv10_split16: geometry mismatch")
-    out1 = torch.empty((F, H, W, 64), dtype=torch.float32, device=x.device)
-    base = torch.empty((F // T, H, W, 64), dtype=torch.float32, device=x.device)
+    out1 = _out(out1, (F, H, W, 64), torch.float32, x.device, "out1")
+    base = _out(base, (F // T, H, W, 64), torch.float32, x.device, "base")
     fn = lib.pfnl_op_conv1_conv10_split16_sf0 if sf0 else lib.pfnl_op_conv1_conv10_split16
     _capi.check(fn(_req(x, "x"), _hp(k1h), _hp(_host(b1, "b1")), _hp(k10h), _hp(_host(b10, "b10")),
                                                  _req(out1, "out1"), _req(base, "base"), F // T, T, H, W, _stream(x)))
@@ -447,7 +460,7 @@ def conv2_chain_sf0(x, kernel, bias, base, resid, add_div: int, act: bool = True
     return out, out_sf
 
 
-def nonlocal_block(x, wg, bg, ww, bw, theta=None, phi=None, nltype: int = 1, sub_sample: int = 1):
+def nonlocal_block(x, wg, bg, ww, bw, theta=None, phi=None, nltype: int = 1, sub_sample: int = 1, out=None):
     """utils.NonLocalBlock(input_x, out_channels, sub_sample, nltype) in its general form (reference utils.py:18-71) inside the
     wrapper of model/pfnl.py:55-60: x [B,T,H,W,3] (cuda) -> [B,H,W,3T] = stack + depth_to_space(NonLocalBlock(space_to_depth(stack))).
     ``theta`` / ``phi`` = (kernel [C,C] or [1,1,C,C], bias [C]) of the two projections (nltype 0 and 2)."""
@@ -466,13 +479,13 @@ def nonlocal_block(x, wg, bg, ww, bw, theta=None, phi=None, nltype: int = 1, sub
     for a, n in zip(arrs + [p for p in proj if p is not None], (C_ * C_, C_) * 4):
         if a.size != n:
             raise ValueError("nonlocal_block: weight shapes do not match 12*T channels")
-    out = torch.empty((B, H, W, 3 * T), dtype=torch.float32, device=x.device)
+    out = _out(out, (B, H, W, 3 * T), torch.float32, x.device)
     _capi.check(lib.pfnl_op_nonlocal_block(_req(x, "x"), *[_hp(a) for a in arrs], *[_hp(a) for a in proj], int(nltype),
                                            int(sub_sample), _req(out, "out"), B, T, H, W, _stream(x)))
     return out
 
 
-def conv0(x, kernel, bias=None, f32=False):
+def conv0(x, kernel, bias=None, f32=False, out=None):
     """conv0 (reference model/pfnl.py:48,61-62): x [B,T,H,W,3] (cuda) -> lrelu(conv5x5(frame) + b) [B*T,H,W,64].
     f32: the fp32 VALU kernel of strict_fp32=on instead of the default split-f16 MFMA kernel."""
     import torch
@@ -481,12 +494,12 @@ def conv0(x, kernel, bias=None, f32=False):
     k, b = _host(kernel, "kernel"), _host(bias, "bias")
     if k.shape != (5, 5, 3, 64) or c != 3:
         raise ValueError("conv0: geometry mismatch")
-    out = torch.empty((B * T, H, W, 64), dtype=torch.float32, device=x.device)
+    out = _out(out, (B * T, H, W, 64), torch.float32, x.device)
     _capi.check(lib.pfnl_op_conv0_ex(_req(x, "x"), _hp(k), _hp(b), _req(out, "out"), B, T, H, W, 1 if f32 else 0, _stream(x)))
     return out
 
 
-def conv0_bf16(x, kernel, bias=None):
+def conv0_bf16(x, kernel, bias=None, out=None):
     """conv0 as precision=bf16 runs it (pfnl_op_conv0_bf16): the default kernel of `conv0`, its result rounded once to bf16 at the
     store.  x [B,T,H,W,3] float32 (cuda) -> [B*T,H,W,64] bfloat16."""
     import torch
@@ -495,12 +508,12 @@ def conv0_bf16(x, kernel, bias=None):
     k, b = _host(kernel, "kernel"), _host(bias, "bias")
     if k.shape != (5, 5, 3, 64) or c != 3:
         raise ValueError("conv0_bf16: geometry mismatch")
-    out = torch.empty((B * T, H, W, 64), dtype=torch.bfloat16, device=x.device)
+    out = _out(out, (B * T, H, W, 64), torch.bfloat16, x.device)
     _capi.check(lib.pfnl_op_conv0_bf16(_req(x, "x"), _hp(k), _hp(b), _req16(out, "out"), B, T, H, W, _stream(x)))
     return out
 
 
-def tail(merge, x, kernel, bias, scale: int):
+def tail(merge, x, kernel, bias, scale: int, out=None):
     """The tail (reference model/pfnl.py:53,63,76-80): merge [B,H,W,48] (cuda), x [B,T,H,W,3] (cuda) -> [B,1,sH,sW,3]."""
     import torch
     lib = _capi.load_library()
@@ -508,12 +521,12 @@ def tail(merge, x, kernel, bias, scale: int):
     k, b = _host(kernel, "kernel"), _host(bias, "bias")
     if merge.shape != (B, H, W, 48) or k.shape != (3, 3, 12, 12 if scale == 4 else 3):
         raise ValueError("tail: geometry mismatch")
-    out = torch.empty((B, 1, scale * H, scale * W, 3), dtype=torch.float32, device=x.device)
+    out = _out(out, (B, 1, scale * H, scale * W, 3), torch.float32, x.device)
     _capi.check(lib.pfnl_op_tail(_req(merge, "merge"), _req(x, "x"), _hp(k), _hp(b), _req(out, "out"), B, T, H, W, scale, _stream(x)))
     return out
 
 
-def gather_windows(frames, first: int, count: int, num_frames: int):
+def gather_windows(frames, first: int, count: int, num_frames: int, out=None):
     """frames [F,H,W,3] (cuda) -> [count,T,H,W,3]: the clamped sliding windows of frames first..first+count-1
     (reference model/pfnl.py:238-242)."""
     import torch
@@ -521,12 +534,12 @@ def gather_windows(frames, first: int, count: int, num_frames: int):
     F, H, W, c = frames.shape
     if c != 3:
         raise ValueError("gather_windows expects [F,H,W,3]")
-    out = torch.empty((count, num_frames, H, W, 3), dtype=torch.float32, device=frames.device)
+    out = _out(out, (count, num_frames, H, W, 3), torch.float32, frames.device)
     _capi.check(lib.pfnl_op_gather_windows(_req(frames, "frames"), _req(out, "out"), F, first, count, num_frames, H, W, _stream(frames)))
     return out
 
 
-def gather_windows_u8(ring, last: int, first: int, count: int, num_frames: int):
+def gather_windows_u8(ring, last: int, first: int, count: int, num_frames: int, out=None):
     """ring [cap,H,W,3] uint8 (cuda), frame f in slot f % cap -> [count,T,H,W,3] float32: the clamped sliding windows of frames
     first..first+count-1 of a sequence whose newest frame is ``last``, dequantised as the harness does, (u8 / 255.).astype(np.float32)
     (pfnl_op_gather_windows_u8: the streaming session's input side; reference model/pfnl.py:238-242, :287)."""
@@ -537,7 +550,7 @@ def gather_windows_u8(ring, last: int, first: int, count: int, num_frames: int):
     cap, H, W, c = ring.shape
     if c != 3:
         raise ValueError("gather_windows_u8 expects [cap,H,W,3]")
-    out = torch.empty((count, num_frames, H, W, 3), dtype=torch.float32, device=ring.device)
+    out = _out(out, (count, num_frames, H, W, 3), torch.float32, ring.device)
     _capi.check(lib.pfnl_op_gather_windows_u8(C.c_void_p(ring.data_ptr()), _req(out, "out"), cap, int(last), int(first), count, num_frames,
                                               H, W, _stream(ring)))
     return out
@@ -696,12 +709,12 @@ def resize_u8(frames, out_size, out=None):
     return out.view(n, oH, oW, 3)
 
 
-def quantise_u8(sr):
+def quantise_u8(sr, out=None):
     """uint8(np.round(np.clip(sr * 255, 0, 255))) on the device (reference model/pfnl.py:254-257)."""
     import torch
     lib = _capi.load_library()
     _req(sr, "sr")
-    out = torch.empty(sr.shape, dtype=torch.uint8, device=sr.device)
+    out = _out(out, sr.shape, torch.uint8, sr.device)
     _capi.check(lib.pfnl_op_quantise_u8(C.c_void_p(sr.data_ptr()), C.c_void_p(out.data_ptr()), sr.numel(), _stream(sr)))
     return out
 
@@ -713,13 +726,13 @@ def _req_u16(t, name):
     return C.c_void_p(t.data_ptr())
 
 
-def quantise_u10(sr):
+def quantise_u10(sr, out=None):
     """uint16(np.round(np.clip(sr * 1023, 0, 1023))) on the device, the product in float32 (pfnl_op_quantise_u10; sample for sample
     pfnl_amd/depth10.py quantise10; NaN gives 0).  sr.numel() a multiple of 4."""
     import torch
     lib = _capi.load_library()
     _req(sr, "sr")
-    out = torch.empty(sr.shape, dtype=torch.uint16, device=sr.device)
+    out = _out(out, sr.shape, torch.uint16, sr.device)
     _capi.check(lib.pfnl_op_quantise_u10(C.c_void_p(sr.data_ptr()), C.c_void_p(out.data_ptr()), sr.numel(), _stream(sr)))
     return out
 
@@ -934,13 +947,13 @@ def _ring_u10(ring, name):
     return ring.shape[:3]
 
 
-def gather_windows_u10(ring, last: int, first: int, count: int, num_frames: int):
+def gather_windows_u10(ring, last: int, first: int, count: int, num_frames: int, out=None):
     """gather_windows_u8 on a ring [cap,H,W,3] uint16 (cuda) at 10 bits: the windows dequantised as pfnl_amd/depth10.py dequantise10 does,
     (min(u10, 1023) / 1023.).astype(np.float32) (pfnl_op_gather_windows_u10)."""
     import torch
     lib = _capi.load_library()
     cap, H, W = _ring_u10(ring, "gather_windows_u10")
-    out = torch.empty((count, num_frames, H, W, 3), dtype=torch.float32, device=ring.device)
+    out = _out(out, (count, num_frames, H, W, 3), torch.float32, ring.device)
     _capi.check(lib.pfnl_op_gather_windows_u10(C.c_void_p(ring.data_ptr()), _req(out, "out"), cap, int(last), int(first), count, num_frames,
                                                H, W, _stream(ring)))
     return out
@@ -1039,7 +1052,7 @@ def resize_place_u10(frames, canvas, src=None, dst=None, fill=(0, 0, 0), out=Non
                          _capi.load_library().pfnl_op_resize_place_u10)
 
 
-def score_y(pred_u8, truth_u8, sp_border: int = 8):
+def score_y(pred_u8, truth_u8, sp_border: int = 8, out=None):
     """Y-channel quality sums of uint8 RGB frame pairs on the device (pfnl_op_score_y): pred_u8, truth_u8 [F,H,W,3] uint8 (cuda)
     -> [F,4] float64 (cuda): sum_d2_full, sum_d2_crop (spatial border sp_border), ssim_sum_full, ssim_sum_valid.
     metrics.sequence_scores turns them into PSNR_Y / SSIM / AVG_PSNR (matlab/compute_psnr.m, modules/SSIM_Index.py:23-89,
@@ -1055,7 +1068,7 @@ def score_y(pred_u8, truth_u8, sp_border: int = 8):
     nbytes = C.c_size_t(0)
     _capi.check(lib.pfnl_op_score_scratch_bytes(F, H, W, C.byref(nbytes)))
     scratch = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=pred_u8.device)
-    out = torch.empty((F, 4), dtype=torch.float64, device=pred_u8.device)
+    out = _out(out, (F, 4), torch.float64, pred_u8.device)
     _capi.check(lib.pfnl_op_score_y(C.c_void_p(pred_u8.data_ptr()), C.c_void_p(truth_u8.data_ptr()), F, H, W, int(sp_border),
                                     C.c_void_p(out.data_ptr()), C.c_void_p(scratch.data_ptr()), _stream(pred_u8)))
     return out

@@ -17,6 +17,16 @@ from pfnl_amd import ops  # noqa: E402
 
 
 SPLIT16_OP_REL_TOL = 4e-6    # a split-f16 op against its fp64 spec, relative to max(1, max|spec|) (tests/test_gpu_history.py imports it)
+# the other hooks' bounds against the fp64 spec, named so that tests/test_gpu_big.py holds the same hooks to the same numbers
+F32_MFMA_REL_TOL = 5e-6      # conv_mfma.hip, conv1x1.hip: an fp32 FMA chain, relative to max(1, max|spec|)
+WINOGRAD_REL_TOL = 2e-5      # the Winograd kernels (per-tile, persistent, grouped, accumulating): a few ulp more than direct
+NONLOCAL_ABS_TOL = 2e-5      # the non-local block on fp32 / split-f16 operands, absolute (|x| < 1)
+NONLOCAL_F16_ABS_TOL = 2e-3  # ... on binary16 operands (the non-local block of precision=bf16)
+CONV0_REL_TOL = 2e-6         # conv0, both kernels
+TAIL_ABS_TOL = 5e-6          # the tail
+RESAMPLE_ABS_TOL = 2e-6      # bicubic, blur_decimate
+SMALL_BLOCK_OUT_REL_TOL = 6e-6   # the second output of the two-launch small-shape block
+SF_OUT_REL_STEP = 2.0 ** -21     # conv1_i writing the split format against the fp32-output kernel, relative per element
 
 
 def dev(a):
@@ -35,7 +45,7 @@ def test_bicubic(B, H, W, scale):
     got = ops.bicubic(dev(x), scale).cpu().numpy()
     ref = pfnl_spec.resize_bicubic_tf1(x.astype(np.float64), scale)
     assert got.shape == ref.shape
-    assert np.abs(got - ref).max() < 2e-6
+    assert np.abs(got - ref).max() < RESAMPLE_ABS_TOL
     assert np.array_equal(got[:, ::scale, ::scale], x)          # t = 0 taps are exactly [0,1,0,0]
 
 
@@ -78,7 +88,7 @@ def test_conv_mfma(items, fpi, H, W, ks, cout, act, fused, mt, monkeypatch):
     got, ref = _conv_case(rng, items, fpi, H, W, ks, cout, act, fused)
     assert got.shape == ref.shape
     err = np.abs(got - ref).max()
-    assert err < 5e-6 * max(1.0, np.abs(ref).max()), err
+    assert err < F32_MFMA_REL_TOL * max(1.0, np.abs(ref).max()), err
 
 
 @pytest.mark.parametrize("clips,T,H,W", [
@@ -100,7 +110,7 @@ def test_conv2_grouped(clips, T, H, W):
     ref = res + pfnl_spec.lrelu(pfnl_spec.conv2d_same(cat.astype(np.float64), k.astype(np.float64), b.astype(np.float64)))
     got = ops.conv2_grouped(dev(x), dev(base), k, b, dev(res), T).cpu().numpy()
     assert got.shape == ref.shape
-    assert np.abs(got - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
+    assert np.abs(got - ref).max() < WINOGRAD_REL_TOL * max(1.0, np.abs(ref).max())
 
 
 @pytest.mark.parametrize("clips,T,H,W,cout", [
@@ -121,7 +131,7 @@ def test_conv3x3_accum(clips, T, H, W, cout, variant):
     ref = pfnl_spec.lrelu(pfnl_spec.conv2d_same(xin.astype(np.float64), k.astype(np.float64), b.astype(np.float64)))
     got = ops.conv3x3_accum(dev(x), k, b, act=True, frames_per_clip=T, variant=variant).cpu().numpy()
     assert got.shape == ref.shape
-    assert np.abs(got - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
+    assert np.abs(got - ref).max() < WINOGRAD_REL_TOL * max(1.0, np.abs(ref).max())
     if variant == "split16" and (H * W) % 2:
         return
     if variant == "split16":                                          # odd sizes too: the split-f16 kernel has no parity restriction
@@ -151,7 +161,7 @@ def test_conv1x1_stream(items, fpi, H, W, act, variant):
         ref = pfnl_spec.lrelu(ref)
     got = ops.conv1x1_stream(dev(x), k, b, act=act, frames_per_item=fpi, variant=variant).cpu().numpy()
     assert got.shape == ref.shape
-    assert np.abs(got - ref).max() < 5e-6 * max(1.0, np.abs(ref).max())
+    assert np.abs(got - ref).max() < F32_MFMA_REL_TOL * max(1.0, np.abs(ref).max())
 
 
 @pytest.mark.parametrize("items,H,W,act,fused", [
@@ -183,7 +193,7 @@ def test_conv3x3_winograd(items, H, W, act, fused, variant):
     got = ops.conv3x3_winograd(dev(x), k, b, act=act, variant=variant, **kw).cpu().numpy()
     direct = ops.conv2d(dev(x), k, b, act=act, **kw).cpu().numpy()
     err = np.abs(got - ref).max()
-    assert err < 2e-5 * max(1.0, np.abs(ref).max()), err          # Winograd: a few ulp more than direct
+    assert err < WINOGRAD_REL_TOL * max(1.0, np.abs(ref).max()), err          # Winograd: a few ulp more than direct
     assert np.abs(got - direct).max() < 2e-5 * max(1.0, np.abs(ref).max())
 
 
@@ -216,7 +226,7 @@ def test_nonlocal_residual(B, T, H, W, kernel):
                                  ww.astype(np.float64), bw.astype(np.float64))
     ref = stack + pfnl_spec.depth_to_space2(z)
     assert got.shape == ref.shape
-    assert np.abs(got - ref).max() < 2e-5, np.abs(got - ref).max()
+    assert np.abs(got - ref).max() < NONLOCAL_ABS_TOL, np.abs(got - ref).max()
 
 
 @pytest.mark.parametrize("N", [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 191, 193, 321])
@@ -239,7 +249,7 @@ def test_nonlocal_key_counts_around_tile_edges(N, kernel):
     z = pfnl_spec.nonlocal_block(pfnl_spec.space_to_depth2(stack), wg.astype(np.float64), bg.astype(np.float64),
                                  ww.astype(np.float64), bw.astype(np.float64))
     ref = stack + pfnl_spec.depth_to_space2(z)
-    tol = 2e-5 if kernel == "split16" else 2e-3                     # (f16: binary16 operands, the non-local block of precision=bf16)
+    tol = NONLOCAL_ABS_TOL if kernel == "split16" else NONLOCAL_F16_ABS_TOL                     # (f16: binary16 operands, the non-local block of precision=bf16)
     assert np.abs(got - ref).max() < tol, np.abs(got - ref).max()
 
 
@@ -310,7 +320,7 @@ def test_blur_decimate(F, H, W, scale):
     got = ops.blur_decimate(dev(hr), scale).cpu().numpy()
     ref = synth.blur_decimate(hr.astype(np.float64), scale)        # numpy restatement of utils.py:169-192
     assert got.shape == ref.shape == (F, -(-H // scale), -(-W // scale), 3)
-    assert np.abs(got - ref).max() < 2e-6
+    assert np.abs(got - ref).max() < RESAMPLE_ABS_TOL
 
 
 def test_ws_modes_random_geometries():
@@ -336,7 +346,7 @@ def test_conv0_op(B, T, H, W):
     got = ops.conv0(dev(x), k, b).cpu().numpy()
     ref = pfnl_spec.lrelu(pfnl_spec.conv2d_same(x.reshape(B * T, H, W, 3).astype(np.float64), k.astype(np.float64), b.astype(np.float64)))
     assert got.shape == ref.shape
-    assert np.abs(got - ref).max() < 2e-6 * max(1.0, np.abs(ref).max())
+    assert np.abs(got - ref).max() < CONV0_REL_TOL * max(1.0, np.abs(ref).max())
     delta = np.zeros((5, 5, 3, 64), np.float32)                       # pure data movement: a shifted delta kernel
     delta[1, 3, 2, 7] = 1.0
     got = ops.conv0(dev(x), delta, None).cpu().numpy()
@@ -363,7 +373,7 @@ def test_tail_op(B, T, H, W, scale):
         o = pfnl_spec.depth_to_space2(o)
     ref = (o + pfnl_spec.resize_bicubic_tf1(x[:, T // 2].astype(np.float64), scale))[:, None]
     assert got.shape == ref.shape
-    assert np.abs(got - ref).max() < 5e-6
+    assert np.abs(got - ref).max() < TAIL_ABS_TOL
 
 
 @pytest.mark.parametrize("B,T,H,W", [(1, 7, 16, 16), (2, 3, 6, 10), (1, 5, 12, 22)])
@@ -414,7 +424,7 @@ def test_nonlocal_block_general(B, T, H, W, nltype, sub):
     ref = stack + pfnl_spec.depth_to_space2(z)
     ok = np.isfinite(ref)                                                        # (nltype 2: a query without a positive affinity is 0 / 0 in
     assert got.shape == ref.shape and np.array_equal(np.isfinite(got), ok)       #  the reference: NaN on both sides, utils.py:61-63)
-    assert ok.mean() > 0.5 and np.abs(got[ok] - ref[ok]).max() < 2e-5, np.abs(got[ok] - ref[ok]).max()
+    assert ok.mean() > 0.5 and np.abs(got[ok] - ref[ok]).max() < NONLOCAL_ABS_TOL, np.abs(got[ok] - ref[ok]).max()
     if nltype == 1 and sub == 1:
         return
     plain = ops.nonlocal_residual(dev(x), wg, bg, ww, bw, precision="f32").cpu().numpy()
@@ -552,7 +562,7 @@ def test_conv3x3_split16_sf_output(items, H, W, act):
     old = ops.conv3x3_winograd(dev(x), k, b, act=act, variant="split16").cpu().numpy()
     rel = np.abs(got - old) / np.maximum(np.abs(old), 2.0 ** -14)
     print(f"sf_out {items}x{H}x{W}: max rel {rel.max():.3g}")
-    assert rel.max() <= 2.0 ** -21, rel.max()
+    assert rel.max() <= SF_OUT_REL_STEP, rel.max()
 
 
 @pytest.mark.parametrize("T,items,H,W", [(7, 2, 16, 32), (5, 1, 6, 10), (3, 3, 9, 7), (7, 4, 64, 64)])
@@ -714,7 +724,7 @@ def test_conv_small_pf_block_two_launches(T, clips, H, W):
     g1, g2 = ops.conv_small_pf_block(dev(x), k1, b1, k10, b10, k2, b2, T)
     e1, e2 = np.abs(g1.cpu().numpy() - r1).max(), np.abs(g2.cpu().numpy() - r2).max()
     print(f"conv_small block T{T} {clips}x{H}x{W}: inp1 err {e1:.3g}, out err {e2:.3g} (|ref| <= {np.abs(r2).max():.3g})")
-    assert e1 < SPLIT16_OP_REL_TOL * max(1.0, np.abs(r1).max()) and e2 < 6e-6 * max(1.0, np.abs(r2).max())
+    assert e1 < SPLIT16_OP_REL_TOL * max(1.0, np.abs(r1).max()) and e2 < SMALL_BLOCK_OUT_REL_TOL * max(1.0, np.abs(r2).max())
     h1, h2 = ops.conv_small_pf_block(dev(x), k1, b1, k10, b10, k2, b2, T)
     assert torch.equal(g1, h1) and torch.equal(g2, h2)
 
