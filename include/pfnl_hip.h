@@ -519,6 +519,46 @@ int pfnl_stream_chroma_siting(pfnl_stream* s, int in_siting, int out_siting);
  * Out of scope: monochrome, 4:1:1, alpha planes, 12 and 16 bits, BT.2020. */
 enum { PFNL_CHROMA_420 = 0, PFNL_CHROMA_422 = 1, PFNL_CHROMA_444 = 2 };
 int pfnl_stream_chroma_format(pfnl_stream* s, int in_chroma, int out_chroma);
+/* PACKED FORMATS (additions to version 4).  What a capture card, an SDI card or a swap chain hands over is ONE plane whose samples are
+ * interleaved within a pixel or a pixel group.  A packing is a setting per side of its own, beside layout, depth, chroma format and siting;
+ * PFNL_PACK_NONE is the planes of the layout, and the PFNL_PIX_* enum does not grow.  Each other value names one complete single-plane
+ * layout and is valid only on a side whose family, depth and chroma format agree with it:
+ *   value               side must be            unit                                                         bytes of a row
+ *   PFNL_PACK_BGR24     RGB, 8 bits             3 bytes B, G, R                                              3 W
+ *   PFNL_PACK_RGBA      RGB, 8 bits             4 bytes R, G, B, A                                           4 W
+ *   PFNL_PACK_BGRA      RGB, 8 bits             4 bytes B, G, R, A                                           4 W
+ *   PFNL_PACK_YUYV      YUV, 8 bits, 4:2:2      4 bytes Y0 Cb Y1 Cr per pixel pair (YUY2)                    2 W
+ *   PFNL_PACK_UYVY      YUV, 8 bits, 4:2:2      4 bytes Cb Y0 Cr Y1                                          2 W
+ *   PFNL_PACK_X2RGB10   RGB, 10 bits            one little-endian uint32: bits 29..20 R, 19..10 G, 9..0 B    4 W
+ *   PFNL_PACK_X2BGR10   RGB, 10 bits            uint32: bits 29..20 B, 19..10 G, 9..0 R (DXGI R10G10B10A2)   4 W
+ *   PFNL_PACK_Y210      YUV, 10 bits, 4:2:2     four uint16 Y0 Cb Y1 Cr, the value in the upper ten bits     4 W
+ *   PFNL_PACK_V210      YUV, 10 bits, 4:2:2,    16 bytes per 6 pixels: four little-endian uint32 of three    16 W / 6
+ *                       W a multiple of 6       10-bit samples at bits 9..0, 19..10, 29..20 - word 0: Cb0 Y0 Cr0; 1: Y1 Cb1 Y2;
+ *                                               2: Cr1 Y3 Cb2; 3: Y4 Cr2 Y5
+ * A tightly packed frame is H rows of the row bytes, except v210, whose rows are ((W + 47) / 48) * 128 bytes (the format's own rule).
+ * "Side must be" is read from what is set: the input side's in_fmt family and pfnl_stream_input_depth, the output side's out_fmt (which
+ * carries its depth), and PFNL_CHROMA_*.  A YUV layout name on a packed side only says the side is YUV.
+ * Alpha and the spare bits of an X2 word are ignored on input and written opaque (255; 3 in the two bits); bits 31..30 of a v210 word and
+ * the padding of a tight v210 row are written 0 and ignored on input; bytes between a row's end and the pitch of a caller's surface are
+ * never written.  Sample values pass as they come, 0 .. 1023 at 10 bits, with no clamp to a legal range.  A 4:2:2 packing reads the
+ * horizontal half of the side's siting exactly as planar 4:2:2 does; matrix and range are the session's.  The arithmetic is CHROMA FORMAT's
+ * at PFNL_CHROMA_422 and nothing else: a packed frame equals pack(planar result) byte for byte (pfnl_amd/packed.py).  A lane converts one
+ * row by the pixels of one 16-byte word of the packed side, or by one unit where the addresses do not allow that (pfnl_amd/csrc/packed.hip).
+ *   pfnl_stream_packing: in_pack for what push takes, out_pack for what pop delivers.  A value outside the enum, or a packing that
+ *     disagrees with its side as it is set at the call (the words name family, depth, chroma format or the width): PFNL_ERR_INVALID
+ *     before any HIP call.  Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); it survives
+ *     pfnl_stream_reset.  With a packing in force pfnl_stream_format, pfnl_stream_input_depth, pfnl_stream_chroma_format and the size
+ *     setters refuse a change that contradicts it (PFNL_ERR_INVALID: set PFNL_PACK_NONE first).  push / pop move tightly packed frames;
+ *     the surface calls use plane[0] / pitch[0], pointer and pitch multiples of 2 (y210) or 4 (x2rgb10, x2bgr10, v210).  On input every
+ *     packed side goes through the kernel, on output the packing is stage 2 of the route, for the RGB packings too.  A session that
+ *     never calls it issues exactly the launches it always issued.
+ * The op hooks pfnl_op_packed_to_rgb_* / pfnl_op_rgb_to_packed_* below are the two kernels on their own.
+ * Out of scope: big-endian variants, 12 and 16 bits, packed 4:4:4, alpha carried through, BT.2020, v210 widths not a multiple of 6. */
+enum {
+    PFNL_PACK_NONE = 0, PFNL_PACK_BGR24 = 1, PFNL_PACK_RGBA = 2, PFNL_PACK_BGRA = 3, PFNL_PACK_YUYV = 4, PFNL_PACK_UYVY = 5,
+    PFNL_PACK_X2RGB10 = 6, PFNL_PACK_X2BGR10 = 7, PFNL_PACK_Y210 = 8, PFNL_PACK_V210 = 9
+};
+int pfnl_stream_packing(pfnl_stream* s, int in_pack, int out_pack);
 /* SELF-ENSEMBLE in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With
  * n in {2, 4, 8} the one forward of every batch is pfnl_forward_ensemble(..., n, ...) (SELF-ENSEMBLE above); gather, quantisation, the
  * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  n = 1 is
@@ -888,6 +928,21 @@ int pfnl_op_rgb_to_yuv_u8_chroma(const uint8_t* rgb, int fmt, int matrix, int fu
                                  void* stream);
 int pfnl_op_rgb_to_yuv_u10_chroma(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, int chroma,
                                   int siting, void* stream);
+/* The two kernels of PACKED FORMATS on their own: n frames in ONE packed plane - frame f starts at plane + f * frame_stride, its rows lie
+ * `pitch` bytes apart - <-> rgb [n][H][W][3], uint8 for the 8-bit packings (the _u8 hooks), uint16 values 0 .. 1023 for the 10-bit ones
+ * (_u10).  Device pointers, asynchronous on `stream`.  An RGB packing ignores matrix, full_range and siting's value (all must still lie
+ * in their enums).  NULL, a packing outside the enum or of the other depth, a width its unit does not divide, n / H / W < 1, a pitch below
+ * the bytes of a row, a frame stride (n > 1) below H rows, a pointer, pitch or frame stride that is no multiple of 2 (y210) or 4
+ * (x2rgb10, x2bgr10, v210), an odd rgb pointer at 10 bits: PFNL_ERR_INVALID before any HIP call.  Bytes between a row's end and the
+ * pitch are never written. */
+int pfnl_op_packed_to_rgb_u8(const void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H,
+                             int W, uint8_t* rgb, void* stream);
+int pfnl_op_packed_to_rgb_u10(const void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H,
+                              int W, uint16_t* rgb, void* stream);
+int pfnl_op_rgb_to_packed_u8(void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H, int W,
+                             const uint8_t* rgb, void* stream);
+int pfnl_op_rgb_to_packed_u10(void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H, int W,
+                              const uint16_t* rgb, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

@@ -170,6 +170,11 @@ SIGNATURES = {
     "pfnl_op_yuv_to_rgb_u10_surface_chroma": (_i, [C.POINTER(pfnl_surface), _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "pfnl_op_rgb_to_yuv_u8_chroma": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "pfnl_op_rgb_to_yuv_u10_chroma": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "pfnl_stream_packing": (_i, [_vp, _i, _i]),
+    "pfnl_op_packed_to_rgb_u8": (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, C.c_size_t, _i, _i, _vp, _vp]),
+    "pfnl_op_packed_to_rgb_u10": (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, C.c_size_t, _i, _i, _vp, _vp]),
+    "pfnl_op_rgb_to_packed_u8": (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, C.c_size_t, _i, _i, _vp, _vp]),
+    "pfnl_op_rgb_to_packed_u10": (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, C.c_size_t, _i, _i, _vp, _vp]),
     "pfnl_op_gather_windows_u10": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows_u10_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_scene_sad_u10": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
@@ -193,6 +198,8 @@ FORMATS_420 = ("nv12", "i420", "p010", "i010")             # H * W * 3 / 2 sampl
 YUV_MATRICES = {"bt601": 0, "bt709": 1}                    # PFNL_MATRIX_*
 CHROMA_FORMATS = {"420": 0, "422": 1, "444": 2}            # PFNL_CHROMA_* (pfnl_amd/yuv.py CHROMAS, in its order)
 CHROMA_SITINGS = {"left": 0, "center": 1, "topleft": 2}    # PFNL_SITING_* (pfnl_amd/yuv.py SITINGS, in its order)
+PACKINGS = {"none": 0, "bgr24": 1, "rgba": 2, "bgra": 3, "yuyv422": 4, "uyvy422": 5, "x2rgb10": 6, "x2bgr10": 7, "y210": 8,
+            "v210": 9}                                     # PFNL_PACK_* (pfnl_amd/packed.py PACKINGS, in its order)
 COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX = 0, 1
 

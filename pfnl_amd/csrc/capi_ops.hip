@@ -1178,6 +1178,59 @@ int pfnl_op_rgb_to_yuv_u10_chroma(const uint16_t* rgb, int fmt, int matrix, int 
     return 0;
 }
 
+// ---- packed formats: the two kernels on one plane with a pitch (include/pfnl_hip.h PACKED FORMATS; pack_geom.h states the table) -------
+
+// what the four hooks refuse before any HIP call; *c = the table of `bits`
+static int packed_op_refused(const void* plane, size_t pitch, int pack, int bits, int matrix, int full_range, int siting, int n, size_t frame_stride,
+                             int H, int W, const void* rgb, pfnl::YuvCoef* c) {
+    if (!plane || !rgb) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!pfnl::is_packing(pack)) return fail(PFNL_ERR_INVALID, "packed: pack must be PFNL_PACK_BGR24 .. PFNL_PACK_V210");
+    if (n < 1 || H < 1 || W < 1) return fail(PFNL_ERR_INVALID, "packed: n >= 1, H and W positive");
+    const pfnl::PackInfo& p = pfnl::PACK_TABLE[pack];
+    if (const char* why = pfnl::pack_refused(pack, p.yuv, bits, PFNL_CHROMA_422, W)) return fail(PFNL_ERR_INVALID, why);
+    if (!pfnl::yuv_coefficients(bits, matrix, full_range, c)) return fail(PFNL_ERR_INVALID, "packed: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    if (int r = siting_refused(siting)) return r;
+    const size_t row = pfnl::pack_row_bytes(pack, W);
+    if (pitch < row) return fail(PFNL_ERR_INVALID, "packed: the pitch is smaller than the bytes of a row");
+    if (n > 1 && frame_stride < (size_t)(H - 1) * pitch + row) return fail(PFNL_ERR_INVALID, "packed: the frame stride is smaller than the rows of a frame");
+    if ((reinterpret_cast<uintptr_t>(plane) | pitch | (n > 1 ? frame_stride : 0)) % p.align)
+        return fail(PFNL_ERR_INVALID, "packed: plane pointer, pitch and frame stride must be multiples of 2 (y210) or 4 (x2rgb10, x2bgr10, v210)");
+    if (bits == 10 && reinterpret_cast<uintptr_t>(rgb) % 2) return fail(PFNL_ERR_INVALID, "packed: uint16 samples are 2-byte aligned");
+    return 0;
+}
+
+int pfnl_op_packed_to_rgb_u8(const void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H,
+                             int W, uint8_t* rgb, void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = packed_op_refused(plane, pitch, pack, 8, matrix, full_range, siting, n, frame_stride, H, W, rgb, &c)) return r;
+    HIPCHK(pfnl::launch_packed_to_rgb(plane, pitch, frame_stride, pack, rgb, c, n, H, W, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_packed_to_rgb_u10(const void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H,
+                              int W, uint16_t* rgb, void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = packed_op_refused(plane, pitch, pack, 10, matrix, full_range, siting, n, frame_stride, H, W, rgb, &c)) return r;
+    HIPCHK(pfnl::launch_packed_to_rgb(plane, pitch, frame_stride, pack, rgb, c, n, H, W, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_rgb_to_packed_u8(void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H, int W,
+                             const uint8_t* rgb, void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = packed_op_refused(plane, pitch, pack, 8, matrix, full_range, siting, n, frame_stride, H, W, rgb, &c)) return r;
+    HIPCHK(pfnl::launch_rgb_to_packed(rgb, plane, pitch, frame_stride, pack, c, n, H, W, siting, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_rgb_to_packed_u10(void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H, int W,
+                              const uint16_t* rgb, void* stream) {
+    pfnl::YuvCoef c;
+    if (int r = packed_op_refused(plane, pitch, pack, 10, matrix, full_range, siting, n, frame_stride, H, W, rgb, &c)) return r;
+    HIPCHK(pfnl::launch_rgb_to_packed(rgb, plane, pitch, frame_stride, pack, c, n, H, W, siting, (hipStream_t)stream));
+    return 0;
+}
+
 // as pfnl_op_gather_windows_u8: what both gathers refuse before any HIP call (scene_first: null for the plain one)
 static int gather_u10_refused(const uint16_t* ring, const long long* scene_first, const float* win, int cap, long long last, long long first,
                               int count, int T, int H, int W) {

@@ -74,9 +74,10 @@ struct pfnl_stream {
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
     int in_siting = PFNL_SITING_LEFT, out_siting = PFNL_SITING_LEFT;   // pfnl_stream_chroma_siting: where a 4:2:0 edge's chroma sits
     int in_chroma = PFNL_CHROMA_420, out_chroma = PFNL_CHROMA_420;     // pfnl_stream_chroma_format: how a YUV edge's chroma is subsampled
+    int in_pack = PFNL_PACK_NONE, out_pack = PFNL_PACK_NONE;           // pfnl_stream_packing: an edge as one plane of interleaved samples
     pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
     pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010, the input side at an input depth of 10
-    uint8_t* yin = nullptr;                           // [H*W*3/2] samples (4:2:2: 2 H W, 4:4:4: 3 H W): a host-pointer frame on its way to the kernel; from the first YUV in_fmt on
+    uint8_t* yin = nullptr;                           // [H*W*3/2] samples (4:2:2: 2 H W, 4:4:4: 3 H W; a packing: its tight frame): a host-pointer frame on its way to the kernel; from the first YUV in_fmt or input packing on
     size_t yin_cap = 0;                               // its bytes
     pfnl::PlacePlan rplan;                            // stage 1: a rectangle of the raster on a canvas, the whole onto the whole for a plain size; cH = 0: off
     int32_t* rtab = nullptr;                          // rplan.r.blob on the device
@@ -107,7 +108,10 @@ int run_route(pfnl_stream* s, const Batch& b) {
         HIPCHK(pfnl::launch_resize_place(slot(0), slot(1), s->rplan, s->rtab, fill, b.count, s->s));
     }
     const bool semiplanar = s->out_fmt == PFNL_PIX_NV12 || s->out_fmt == PFNL_PIX_P010;
-    if (r.runs[2] && s->out_chroma == PFNL_CHROMA_420)   // reads the resampled frames where stage 1 runs
+    if (r.runs[2] && s->out_pack != PFNL_PACK_NONE)      // the tight packed frame: rows of pack_tight_pitch, frames of stage_bytes[2]
+        HIPCHK(pfnl::launch_rgb_to_packed(slot(r.runs[1] ? 1 : 0), slot(2), pfnl::pack_tight_pitch(s->out_pack, r.out_w), r.stage_bytes[2], s->out_pack,
+                                          ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w, s->out_siting, s->s));
+    else if (r.runs[2] && s->out_chroma == PFNL_CHROMA_420)   // reads the resampled frames where stage 1 runs
         HIPCHK(pfnl::launch_rgb_to_yuv420(slot(r.runs[1] ? 1 : 0), slot(2), semiplanar, ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w,
                                           s->out_siting, s->s));
     else if (r.runs[2])
@@ -339,8 +343,9 @@ int pushed_format(const pfnl_stream* s) {
     return s->in_fmt == PFNL_PIX_NV12 ? PFNL_PIX_P010 : (s->in_fmt == PFNL_PIX_I420 ? PFNL_PIX_I010 : PFNL_PIX_RGB10);
 }
 
-// the bytes of a pushed frame in `in_fmt`'s layout at a depth and a subsampling; 0 for RGB24, which needs no staging
-size_t yuv_frame_bytes(const pfnl_stream* s, int in_fmt, int in_depth, int chroma) {
+// the bytes of a pushed frame in `in_fmt`'s layout at a depth and a subsampling, or in a packing; 0 for RGB24 in planes, which needs no staging
+size_t yuv_frame_bytes(const pfnl_stream* s, int in_fmt, int in_depth, int chroma, int pack = PFNL_PACK_NONE) {
+    if (pack != PFNL_PACK_NONE) return pfnl::pack_frame_bytes(pack, s->H, s->W);
     if (in_fmt == PFNL_PIX_RGB24) return 0;
     const int fmt = in_depth != 10 ? in_fmt : (in_fmt == PFNL_PIX_NV12 ? PFNL_PIX_P010 : PFNL_PIX_I010);
     return pfnl::packed_bytes(pfnl::surface_geom(fmt, s->H, s->W, chroma));
@@ -349,7 +354,10 @@ size_t yuv_frame_bytes(const pfnl_stream* s, int in_fmt, int in_depth, int chrom
 // a packed YUV frame on the device -> its ring slot as RGB, at the session's input depth and subsampling
 int decode_packed(pfnl_stream* s, const uint8_t* yuv, uint8_t* dst, hipStream_t on) {
     const bool nv12 = s->in_fmt == PFNL_PIX_NV12;
-    if (s->in_chroma != PFNL_CHROMA_420 && s->in_depth == 10)
+    if (s->in_pack != PFNL_PACK_NONE)                 // (a tight frame of an input packing: one plane at its own pitch)
+        HIPCHK(pfnl::launch_packed_to_rgb(yuv, pfnl::pack_tight_pitch(s->in_pack, s->W), 0, s->in_pack, dst, s->in_depth == 10 ? s->coef10 : s->coef, 1,
+                                          s->H, s->W, s->in_siting, on));
+    else if (s->in_chroma != PFNL_CHROMA_420 && s->in_depth == 10)
         HIPCHK(pfnl::launch_yuv_to_rgb_chroma(reinterpret_cast<const uint16_t*>(yuv), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, s->H,
                                               s->W, s->in_chroma, s->in_siting, on));
     else if (s->in_chroma != PFNL_CHROMA_420)
@@ -387,19 +395,19 @@ void release(pfnl_stream* s) {
 
 // The one place where a setting becomes the session's: every setter ends here, with a candidate they have validated and no frame pushed
 // (`plan` NULL: the output size stays).  1. the route and a batch's bytes per stage; 2. everything new first - a stage slot whose capacity
-// is below the need, the tap table of a new plan, the ring of another input depth, the staging frame of the first YUV in_fmt or of one at
+// is below the need (stage 2's follows the output packing's row bytes, the staging frame the input packing's), the tap table of a new plan, the ring of another input depth, the staging frame of the first YUV in_fmt or of one at
 // a wider depth or subsampling (so whichever of pfnl_stream_format, pfnl_stream_input_depth and pfnl_stream_chroma_format comes later makes it) - and where one fails, what was just made is
 // freed, the session is what it was and the answer is PFNL_ERR_NOMEM with `nomem`; 3. the new buffers go in, the ones they replace and the
 // slots of stages the route does not run are freed, the setting is stored.  A call that replaces or releases device memory first waits
 // for the session's stream - a dropped sequence's device-pointer pops may still be reading it - and only such a call: pfnl_stream_format
 // waits where a 10-bit format meets 8-bit slots or a 4:2:0 slot is no longer needed, and not where it only adds memory or changes none.
 int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& coef, const pfnl::YuvCoef& coef10, pfnl::PlacePlan* plan,
-                  int in_depth, int in_chroma, int out_chroma, const char* nomem) {
+                  int in_depth, int in_chroma, int out_chroma, int in_pack, int out_pack, const char* nomem) {
     const pfnl::PlacePlan& rp = plan ? *plan : s->rplan;
-    const pfnl::OutRoute route = pfnl::out_route(out_fmt, s->scale * s->H, s->scale * s->W, rp.cH, rp.cW, out_chroma);   // (the delivered frame is the canvas)
+    const pfnl::OutRoute route = pfnl::out_route(out_fmt, s->scale * s->H, s->scale * s->W, rp.cH, rp.cW, out_chroma, out_pack);   // (the delivered frame is the canvas)
     StageSlot fresh[pfnl::ROUTE_STAGES];              // cap != 0: the stage's slot is too small and this one takes its place
     const size_t in_bytes = s->lr_bytes * (in_depth == 10 ? 2 : 1);
-    const size_t yin_need = yuv_frame_bytes(s, in_fmt, in_depth, in_chroma);
+    const size_t yin_need = yuv_frame_bytes(s, in_fmt, in_depth, in_chroma, in_pack);
     bool frees = (plan && s->rtab) || in_depth != s->in_depth || (yin_need > s->yin_cap && s->yin);
     for (int k = 0; k < pfnl::ROUTE_STAGES; ++k) {
         const size_t need = (size_t)s->batch * route.stage_bytes[k];   // (0 for a stage that does not run)
@@ -453,9 +461,13 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
     s->out_fmt = out_fmt;
     s->in_chroma = in_chroma;
     s->out_chroma = out_chroma;
+    s->in_pack = in_pack;
+    s->out_pack = out_pack;
     s->coef = coef;
     s->coef10 = coef10;
     s->route = route;
+    // a tight v210 frame has zero bytes behind the samples of a row, and the kernel writes samples alone: the slot is cleared once, here
+    for (int i = 0; i < 2 && out_pack == PFNL_PACK_V210; ++i) HIPCHK(hipMemsetAsync(s->slot[2].buf[i], 0, s->slot[2].cap, s->s));
     return 0;
 }
 
@@ -523,8 +535,11 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
 int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
     if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (s->in_depth == 10 && reinterpret_cast<uintptr_t>(frame) % 2) return fail(PFNL_ERR_INVALID, "push: uint16 samples are 2-byte aligned");
-    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24;  // the frame is H*W*3/2 samples (2 H W | 3 H W) and reaches its slot through the kernel, as RGB
-    const size_t yuv_bytes = yuv_frame_bytes(s, s->in_fmt, s->in_depth, s->in_chroma);
+    if (is_device && s->in_pack != PFNL_PACK_NONE && reinterpret_cast<uintptr_t>(frame) % pfnl::PACK_TABLE[s->in_pack].align)
+        return fail(PFNL_ERR_INVALID, "push: a packed frame of 32-bit words (x2rgb10, x2bgr10, v210) is 4-byte aligned");
+    // the frame is H*W*3/2 samples (2 H W | 3 H W), or the tight frame of a packing, and reaches its slot through the kernel, as RGB
+    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || s->in_pack != PFNL_PACK_NONE;
+    const size_t yuv_bytes = yuv_frame_bytes(s, s->in_fmt, s->in_depth, s->in_chroma, s->in_pack);
     return push_frame(
         s, is_device,
         [&](uint8_t* dst) {
@@ -546,13 +561,17 @@ int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
 int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_device) {
     if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
     const int fmt = pushed_format(s);                 // (2-byte samples at an input depth of 10)
-    if (const char* why = pfnl::surface_refused(frame, fmt, s->H, s->W, s->in_chroma)) return fail(PFNL_ERR_INVALID, why);
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(fmt, s->H, s->W, s->in_chroma);
-    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24, nv12 = s->in_fmt == PFNL_PIX_NV12, sub420 = s->in_chroma == PFNL_CHROMA_420;
+    if (const char* why = pfnl::surface_refused(frame, fmt, s->H, s->W, s->in_chroma, s->in_pack)) return fail(PFNL_ERR_INVALID, why);
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(fmt, s->H, s->W, s->in_chroma, s->in_pack);
+    const bool packed = s->in_pack != PFNL_PACK_NONE;
+    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || packed, nv12 = s->in_fmt == PFNL_PIX_NV12, sub420 = s->in_chroma == PFNL_CHROMA_420;
     return push_frame(
         s, is_device,
-        [&](uint8_t* dst) {                           // YUV: the kernel reads the surface where it lies
-            if (yuv_in && !sub420 && s->in_depth == 10)
+        [&](uint8_t* dst) {                           // YUV and every packing: the kernel reads the surface where it lies
+            if (packed)
+                HIPCHK(pfnl::launch_packed_to_rgb(frame->plane[0], frame->pitch[0], 0, s->in_pack, dst, s->in_depth == 10 ? s->coef10 : s->coef, 1,
+                                                  s->H, s->W, s->in_siting, s->s));
+            else if (yuv_in && !sub420 && s->in_depth == 10)
                 HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(*frame, nv12), reinterpret_cast<uint16_t*>(dst), nv12,
                                                              s->coef10, 1, s->H, s->W, s->in_chroma, s->in_siting, s->s));
             else if (yuv_in && !sub420)
@@ -571,6 +590,11 @@ int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_d
         },
         [&](uint8_t* dst) {                           // YUV: the planes packed into the staging frame, then the packed push's kernel
             uint8_t* to = yuv_in ? s->yin : dst;
+            if (packed) {                             // (the rows at the tight frame's pitch: v210's is above its row bytes)
+                HIPCHK(hipMemcpy2DAsync(to, pfnl::pack_tight_pitch(s->in_pack, s->W), frame->plane[0], frame->pitch[0], g.plane[0].row_bytes,
+                                        g.plane[0].rows, hipMemcpyHostToDevice, s->cs));
+                return decode_packed(s, s->yin, dst, s->cs);
+            }
             for (int k = 0; k < g.planes; ++k) {
                 HIPCHK(hipMemcpy2DAsync(to, g.plane[k].row_bytes, frame->plane[k], frame->pitch[k], g.plane[k].row_bytes, g.plane[k].rows,
                                         hipMemcpyHostToDevice, s->cs));
@@ -606,9 +630,15 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
 
 int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_device, long long* index, int* got) {
     if (!s || !out || !index || !got) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (const char* why = pfnl::surface_refused(out, s->out_fmt, s->route.out_h, s->route.out_w, s->out_chroma)) return fail(PFNL_ERR_INVALID, why);
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->out_fmt, s->route.out_h, s->route.out_w, s->out_chroma);
+    if (const char* why = pfnl::surface_refused(out, s->out_fmt, s->route.out_h, s->route.out_w, s->out_chroma, s->out_pack))
+        return fail(PFNL_ERR_INVALID, why);
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->out_fmt, s->route.out_h, s->route.out_w, s->out_chroma, s->out_pack);
     return pop_frame(s, is_device, index, got, [&](const uint8_t* src, size_t, hipStream_t on) {
+        if (s->out_pack != PFNL_PACK_NONE) {          // one plane; the slot's rows lie at the tight frame's pitch, and only a row's samples move
+            HIPCHK(hipMemcpy2DAsync(out->plane[0], out->pitch[0], src, pfnl::pack_tight_pitch(s->out_pack, s->route.out_w), g.plane[0].row_bytes,
+                                    g.plane[0].rows, is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, on));
+            return 0;
+        }
         for (int k = 0; k < g.planes; ++k) {          // the packed frame is its planes one behind the other: rows of row_bytes, nothing between
             HIPCHK(hipMemcpy2DAsync(out->plane[k], out->pitch[k], src, g.plane[k].row_bytes, g.plane[k].row_bytes, g.plane[k].rows,
                                     is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, on));
@@ -674,15 +704,41 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
     return 0;
 }
 
+// A packing in force holds its side to the family, depth, chroma format and width it was accepted with: 0 where the candidate the other
+// setters are about to apply agrees with both packings, else PFNL_ERR_INVALID with the table's words and the way out.
+static int packing_contradicted(const pfnl_stream* s, int in_fmt, int out_fmt, int in_depth, int in_chroma, int out_chroma, int out_w) {
+    const char* why = pfnl::pack_refused(s->in_pack, pfnl::is_yuv(in_fmt), in_depth, in_chroma, s->W);
+    if (!why) why = pfnl::pack_refused(s->out_pack, pfnl::is_yuv(out_fmt), pfnl::is_10bit(out_fmt) ? 10 : 8, out_chroma, out_w);
+    if (!why) return 0;
+    return fail(PFNL_ERR_INVALID, std::string(why) + " - the change contradicts a packing in force: set PFNL_PACK_NONE first (pfnl_stream_packing)");
+}
+
+// The packing of the two edges.  The staging frame and stage 2's slot follow the row bytes, so it goes through apply_setting; each side is
+// checked against what is set at the call, and from then on the other setters hold that side to it (packing_contradicted).
+int pfnl_stream_packing(pfnl_stream* s, int in_pack, int out_pack) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    for (int v : {in_pack, out_pack})
+        if (v != PFNL_PACK_NONE && !pfnl::is_packing(v)) return fail(PFNL_ERR_INVALID, "packing: PFNL_PACK_NONE .. PFNL_PACK_V210 on either side");
+    if (const char* why = pfnl::pack_refused(in_pack, pfnl::is_yuv(s->in_fmt), s->in_depth, s->in_chroma, s->W))
+        return fail(PFNL_ERR_INVALID, std::string("input ") + why);
+    if (const char* why = pfnl::pack_refused(out_pack, pfnl::is_yuv(s->out_fmt), pfnl::is_10bit(s->out_fmt) ? 10 : 8, s->out_chroma, s->route.out_w))
+        return fail(PFNL_ERR_INVALID, std::string("output ") + why);
+    if (s->pushed) return fail(PFNL_ERR_STATE, "the packing is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, s->in_depth, s->in_chroma, s->out_chroma, in_pack, out_pack,
+                         "packing staging allocation failed");
+}
+
 // The setters: bad arguments first (stream_route.h: PFNL_ERR_INVALID at any time), then "before the first frame", then apply_setting.
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (const char* why = pfnl::route_refused(in_fmt, out_fmt, s->route.out_h, s->route.out_w, s->out_chroma)) return fail(PFNL_ERR_INVALID, why);
+    if (int e = packing_contradicted(s, in_fmt, out_fmt, s->in_depth, s->in_chroma, s->out_chroma, s->route.out_w)) return e;
     pfnl::YuvCoef coef, coef10;
     if (!pfnl::yuv_coefficients(8, matrix, full_range, &coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, s->in_depth, s->in_chroma, s->out_chroma, "format staging allocation failed");
+    return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, s->in_depth, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
+                         "format staging allocation failed");
 }
 
 // The depth of the pushed samples: in_fmt keeps naming the layout.  At 10 the ring and the staging frame hold uint16 samples; decode, scene
@@ -690,8 +746,10 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
 int pfnl_stream_input_depth(pfnl_stream* s, int bits) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (bits != 8 && bits != 10) return fail(PFNL_ERR_INVALID, "input depth: 8 or 10 bits");
+    if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, bits, s->in_chroma, s->out_chroma, s->route.out_w)) return e;
     if (s->pushed) return fail(PFNL_ERR_STATE, "the input depth is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, bits, s->in_chroma, s->out_chroma, "input ring allocation failed");
+    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, bits, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
+                         "input ring allocation failed");
 }
 
 // The subsampling of the two YUV edges: in_fmt / out_fmt keep naming the layout.  The staging frame and stage 2's slot follow it, so it goes
@@ -701,8 +759,9 @@ int pfnl_stream_chroma_format(pfnl_stream* s, int in_chroma, int out_chroma) {
     if (!pfnl::is_chroma(in_chroma) || !pfnl::is_chroma(out_chroma))
         return fail(PFNL_ERR_INVALID, "chroma format: PFNL_CHROMA_420, PFNL_CHROMA_422 or PFNL_CHROMA_444 on either side");
     if (const char* why = pfnl::route_refused(s->in_fmt, s->out_fmt, s->route.out_h, s->route.out_w, out_chroma)) return fail(PFNL_ERR_INVALID, why);
+    if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, s->in_depth, in_chroma, out_chroma, s->route.out_w)) return e;
     if (s->pushed) return fail(PFNL_ERR_STATE, "the chroma format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, s->in_depth, in_chroma, out_chroma,
+    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, s->in_depth, in_chroma, out_chroma, s->in_pack, s->out_pack,
                          "chroma format staging allocation failed");
 }
 
@@ -728,9 +787,11 @@ int pfnl_stream_place(pfnl_stream* s, int out_H, int out_W, const pfnl_rect* src
     if ((out_H || out_W) && !pfnl::place_plan(sH, sW, out_H, out_W, src, dst, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
     if (const char* no = pfnl::route_refused(s->in_fmt, s->out_fmt, plan.cH ? plan.cH : sH, plan.cW ? plan.cW : sW, s->out_chroma))
         return fail(PFNL_ERR_INVALID, no);
+    if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, s->in_depth, s->in_chroma, s->out_chroma, plan.cW ? plan.cW : sW)) return e;
     if (s->pushed) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     for (int k = 0; k < 3 && fill_rgb; ++k) plan.fill[k] = fill_rgb[k];
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, s->in_depth, s->in_chroma, s->out_chroma, "resize allocation failed");
+    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, s->in_depth, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
+                         "resize allocation failed");
 }
 
 int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) { return pfnl_stream_place(s, out_H, out_W, nullptr, nullptr, nullptr); }

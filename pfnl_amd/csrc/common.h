@@ -239,6 +239,17 @@ hipError_t launch_rgb_to_yuv_chroma(const uint8_t* rgb, uint8_t* yuv, bool semip
 hipError_t launch_rgb_to_yuv_chroma(const uint16_t* rgb, uint16_t* yuv, bool semiplanar, const YuvCoef& c, int n, int H, int W, int chroma, int siting,
                                     hipStream_t s);
 
+// ---- packed formats <-> RGB (packed.hip; the rule: pfnl_amd/packed.py; the table: pack_geom.h) ----
+// pack: PFNL_PACK_BGR24 .. PFNL_PACK_V210.  n frames in one plane: frame f at plane + f * frame_stride, rows `pitch` bytes apart (a tight
+// frame and a caller's surface are one kernel); rgb [n][H][W][3] of uint8 samples for the 8-bit packings and of uint16 values 0 .. 1023
+// for the 10-bit ones.  The table is the one of the packing's depth; an RGB packing does not read it.  hipErrorInvalidValue for what
+// pack_geom.h refuses, a short pitch or frame stride and a pointer, pitch or stride that is no multiple of the packing's alignment.
+// Bytes between a row's end and the pitch are neither read nor written.
+hipError_t launch_packed_to_rgb(const void* plane, size_t pitch, size_t frame_stride, int pack, void* rgb, const YuvCoef& c, int n, int H, int W,
+                                int siting, hipStream_t s);
+hipError_t launch_rgb_to_packed(const void* rgb, void* plane, size_t pitch, size_t frame_stride, int pack, const YuvCoef& c, int n, int H, int W,
+                                int siting, hipStream_t s);
+
 // ---- RGB frames at a chosen raster: the tap tables (resize.hip; the rule: pfnl_amd/resize.py) ----
 constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in
 constexpr int RESIZE_TW = 64;            // output pixels of one workgroup: across,

@@ -13,7 +13,7 @@ inline bool is_420(int fmt) { return fmt == PFNL_PIX_NV12 || fmt == PFNL_PIX_I42
 inline bool is_yuv(int fmt) { return is_420(fmt); }   // the YUV layouts: 4:2:0 by name, at any subsampling with PFNL_CHROMA_*
 inline bool is_chroma(int chroma) { return chroma >= PFNL_CHROMA_420 && chroma <= PFNL_CHROMA_444; }
 
-constexpr int ROUTE_STAGES = 3;   // 0 quantise (always) | 1 resize (a size is set) | 2 RGB -> YUV (a YUV out_fmt)
+constexpr int ROUTE_STAGES = 3;   // 0 quantise (always) | 1 resize (a size is set) | 2 RGB -> YUV (a YUV out_fmt) or -> a packing (pack_geom.h)
 
 struct OutRoute {
     bool runs[ROUTE_STAGES];
@@ -31,28 +31,31 @@ inline size_t packed_bytes(const SurfaceGeom& g) {
     return n;
 }
 
-// sH x sW: the network's raster; oH = oW = 0: no resampling; chroma: the subsampling of a YUV out_fmt.  Sizes are what route_refused has
-// let through.
-inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW, int chroma = PFNL_CHROMA_420) {
+// sH x sW: the network's raster; oH = oW = 0: no resampling; chroma: the subsampling of a YUV out_fmt; pack: the output side's packing,
+// which is stage 2 for an RGB out_fmt too and delivers the tightly packed frame (pack_frame_bytes).  Sizes are what route_refused has let
+// through.
+inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW, int chroma = PFNL_CHROMA_420, int pack = PFNL_PACK_NONE) {
     OutRoute r{};
     r.out_h = oH ? oH : sH;
     r.out_w = oW ? oW : sW;
-    const SurfaceGeom g = surface_geom(out_fmt, r.out_h, r.out_w, chroma);
+    const SurfaceGeom g = surface_geom(out_fmt, r.out_h, r.out_w, chroma, pack);
     if (!g.planes) return r;
     const int rgb = is_10bit(out_fmt) ? PFNL_PIX_RGB10 : PFNL_PIX_RGB24;
     const SurfaceGeom writes[ROUTE_STAGES] = {surface_geom(rgb, sH, sW), surface_geom(rgb, r.out_h, r.out_w), g};
     r.sample_bytes = g.sample_bytes;
-    r.runs[0] = true, r.runs[1] = oH != 0, r.runs[2] = is_yuv(out_fmt);
+    r.runs[0] = true, r.runs[1] = oH != 0, r.runs[2] = is_yuv(out_fmt) || pack != PFNL_PACK_NONE;
     for (int k = 0; k < ROUTE_STAGES; ++k)
         if (r.runs[k]) r.last = k, r.stage_bytes[k] = packed_bytes(writes[k]);
+    if (pack != PFNL_PACK_NONE) r.stage_bytes[2] = pack_frame_bytes(pack, r.out_h, r.out_w);
     r.frame_bytes = r.stage_bytes[r.last];
     return r;
 }
 
 // nullptr: a session may take in_fmt -> out_fmt and deliver out_h x out_w; else why not.  Both setters ask this before they look at
 // the session's state, each with the other's current setting.  chroma: the subsampling of a YUV out_fmt - the size is even along the axes
-// it halves: both at 4:2:0, the width at 4:2:2, none at 4:4:4.
-inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w, int chroma = PFNL_CHROMA_420) {
+// it halves: both at 4:2:0, the width at 4:2:2, none at 4:4:4.  pack: the output side's packing, which must agree with out_fmt's family and
+// depth, the chroma format and the output width (pack_refused).
+inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w, int chroma = PFNL_CHROMA_420, int pack = PFNL_PACK_NONE) {
     if (!is_chroma(chroma)) return "chroma format: PFNL_CHROMA_420, PFNL_CHROMA_422 or PFNL_CHROMA_444";
     if (is_10bit(in_fmt))
         return "format: 10-bit input is set with pfnl_stream_input_depth; in_fmt names the layout: PFNL_PIX_RGB24, PFNL_PIX_NV12 or PFNL_PIX_I420";
@@ -64,6 +67,7 @@ inline const char* route_refused(int in_fmt, int out_fmt, int out_h, int out_w, 
         return "a YUV output format needs an even output size (pfnl_stream_format, pfnl_stream_resize)";
     if (is_yuv(out_fmt) && chroma == PFNL_CHROMA_422 && (out_w & 1))
         return "a 4:2:2 output needs an even output width (pfnl_stream_chroma_format, pfnl_stream_resize)";
+    if (pack != PFNL_PACK_NONE) return pack_refused(pack, is_yuv(out_fmt), is_10bit(out_fmt) ? 10 : 8, chroma, out_w);
     return nullptr;
 }
 

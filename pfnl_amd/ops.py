@@ -940,6 +940,64 @@ def rgb_to_yuv_u10(frames, fmt: str, matrix: str = "bt709", full_range=False, ch
                        lib.pfnl_op_rgb_to_yuv_u10_chroma)
 
 
+# ---- packed formats (include/pfnl_hip.h PACKED FORMATS; the rule: pfnl_amd/packed.py) ------------------------------------------------------
+def _packed_args(name, matrix, full_range, siting, H, W, pitch):
+    from . import packed as _packed
+    _packed.check(name, H, W)
+    if matrix not in _capi.YUV_MATRICES:
+        raise ValueError(f"matrix: one of {sorted(_capi.YUV_MATRICES)}, got {matrix!r}")
+    pitch = _packed.tight_row_bytes(name, W) if pitch is None else int(pitch)
+    if pitch < _packed.row_bytes(name, W):
+        raise ValueError(f"pitch {pitch} is below the {_packed.row_bytes(name, W)} bytes of a row")
+    ten = _packed.bits(name) == 10
+    return _capi.PACKINGS[name], _capi.YUV_MATRICES[matrix], 1 if full_range else 0, _siting_id(siting), pitch, ten
+
+
+def packed_to_rgb(frames, name: str, H: int, W: int, matrix: str = "bt709", full_range=False, siting="left", pitch=None, out=None):
+    """n frames in the packing ``name`` (pfnl_amd/packed.py PACKINGS) -> [n,H,W,3], uint8 for an 8-bit packing and uint16 in 0 .. 1023 for a
+    10-bit one: the depth follows the packing, byte for byte packed.to_rgb (pfnl_op_packed_to_rgb_u8 / _u10).  ``frames``: a contiguous
+    uint8 tensor on the GPU of n * H * pitch bytes, rows ``pitch`` bytes apart (default: the tight frame's, packed.tight_row_bytes); its
+    address may be any the packing allows (y210: even, x2rgb10 / x2bgr10 / v210: a multiple of 4).  ``out``: write there."""
+    import torch
+    lib = _capi.load_library()
+    pid, mid, fr, sid, pitch, ten = _packed_args(name, matrix, full_range, siting, H, W, pitch)
+    src = _req_u8(frames, "frames")
+    n = frames.numel() // (H * pitch)
+    if n < 1 or n * H * pitch != frames.numel():
+        raise ValueError(f"frames must hold a whole number of frames of {H} rows of {pitch} bytes, got {frames.numel()} bytes")
+    dtype = torch.uint16 if ten else torch.uint8
+    if out is None:
+        out = torch.empty((n, H, W, 3), dtype=dtype, device=frames.device)
+    elif out.numel() != n * H * W * 3 or out.device != frames.device:
+        raise ValueError("out must hold n * H * W * 3 samples on the frames' device")
+    hook = lib.pfnl_op_packed_to_rgb_u10 if ten else lib.pfnl_op_packed_to_rgb_u8
+    _capi.check(hook(src, pitch, pid, mid, fr, sid, n, H * pitch, H, W, (_req_u16 if ten else _req_u8)(out, "out"), _stream(frames)))
+    return out.view(n, H, W, 3)
+
+
+def rgb_to_packed(frames, name: str, matrix: str = "bt709", full_range=False, siting="left", pitch=None, out=None):
+    """[n,H,W,3] (or [H,W,3]) - uint8 for an 8-bit packing, uint16 with values 0 .. 1023 for a 10-bit one - -> [n, H, pitch] uint8: n frames
+    in the packing ``name``, rows ``pitch`` bytes apart (default: the tight frame's), byte for byte packed.from_rgb (pfnl_op_rgb_to_packed_u8
+    / _u10).  Bytes between a row's end and the pitch are never written: a fresh result holds 0 there (a tight v210 frame's padding), ``out``
+    keeps what it held."""
+    import torch
+    lib = _capi.load_library()
+    if frames.dim() == 3:
+        frames = frames[None]
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("expected [n,H,W,3]")
+    n, H, W, _ = frames.shape
+    pid, mid, fr, sid, pitch, ten = _packed_args(name, matrix, full_range, siting, H, W, pitch)
+    src = (_req_u16 if ten else _req_u8)(frames, "frames")
+    if out is None:
+        out = torch.zeros((n, H, pitch), dtype=torch.uint8, device=frames.device)
+    elif out.numel() != n * H * pitch or out.device != frames.device:
+        raise ValueError(f"out must hold n * H * {pitch} bytes on the frames' device")
+    hook = lib.pfnl_op_rgb_to_packed_u10 if ten else lib.pfnl_op_rgb_to_packed_u8
+    _capi.check(hook(_req_u8(out, "out"), pitch, pid, mid, fr, sid, n, H * pitch, H, W, src, _stream(frames)))
+    return out.view(n, H, pitch)
+
+
 def _ring_u10(ring, name):
     _req_u16(ring, "ring")
     if ring.dim() != 4 or ring.shape[3] != 3:

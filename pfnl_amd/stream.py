@@ -48,6 +48,12 @@ edges; ``sar=(16, 15)`` honours non-square pixels; ``crop=(y, x, h, w)`` (SR-ras
 ``place=(y, x, h, w)`` names the destination outright (``out_size=(1088, 1920), place=(0, 0, 1080, 1920)``: coded height, no resampling).
 One launch on the device writes the canvas, by the integer rule of pfnl_amd/fit.py.
 
+Packed formats (off by default): ``open_stream(H, W, batch, pixel_format="nv12", chroma="422", packing="yuyv422", out_format="rgb24",
+out_packing="bgra")`` takes a capture card's frames and delivers a swap chain's: one plane of interleaved samples per frame
+(pfnl_amd/packed.py PACKINGS - bgr24, rgba, bgra, yuyv422, uyvy422, x2rgb10, x2bgr10, y210, v210).  The two sides are independent and None
+means planes; a packing goes with the family, depth and chroma format its side is set to (a YUV ``pixel_format`` only says the side is
+YUV).  Frames are uint8 arrays of ``packed.frame_shape`` - bytes, whatever the unit - or flat.
+
 Surfaces: ``vs.push_planes(y, cbcr)`` / ``vs.pop_planes(y, cbcr)`` take and fill a frame as a decoder or encoder holds it - one array per
 plane, each with the row pitch its strides say (pfnl_amd/surface.py), e.g. ``surface[:H, :W]`` of a pitched device allocation - in the
 session's formats; a device NV12 / I420 surface is converted where it lies, and only the samples of a destination are written.
@@ -123,6 +129,21 @@ def frame_argument(frame, pixel_format: str, H: int, W: int, in_depth: int = 8, 
     return np.ascontiguousarray(frame)
 
 
+def packed_frame_argument(frame, packing: str, H: int, W: int):
+    """``frame`` as ``push`` hands it on with an input packing: a contiguous uint8 numpy array or tensor of ``packed.frame_shape``, or flat
+    with the frame's bytes; ValueError otherwise."""
+    from . import packed as _packed
+    shapes = (_packed.frame_shape(packing, H, W), (_packed.frame_bytes(packing, H, W),))
+    if type(frame).__module__.startswith("torch"):
+        if str(frame.dtype) != "torch.uint8" or tuple(frame.shape) not in shapes:
+            raise ValueError(f"expected a uint8 {packing} frame of shape {' or '.join(map(str, shapes))}, got {frame.dtype} {tuple(frame.shape)}")
+        return frame.contiguous()
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint8 or frame.shape not in shapes:
+        raise ValueError(f"expected a uint8 {packing} frame of shape {' or '.join(map(str, shapes))}, got {frame.dtype} {frame.shape}")
+    return np.ascontiguousarray(frame)
+
+
 def siting_arguments(chroma_siting="left", out_chroma_siting=None) -> Tuple[int, int]:
     """The two arguments of pfnl_stream_chroma_siting for open_stream's keywords (``out_chroma_siting`` None = ``chroma_siting``);
     ValueError for anything the library would refuse.  Needs no device."""
@@ -143,6 +164,26 @@ def chroma_arguments(chroma="420", out_chroma=None) -> Tuple[int, int]:
         if not isinstance(value, str) or value not in _capi.CHROMA_FORMATS:
             raise ValueError(f"{name}: one of {sorted(_capi.CHROMA_FORMATS)}, got {value!r}")
     return _capi.CHROMA_FORMATS[chroma], _capi.CHROMA_FORMATS[out_chroma]
+
+
+def packing_arguments(packing=None, out_packing=None, pixel_format="rgb24", out_format=None, in_depth=8, chroma="420", out_chroma=None,
+                      W: int = 2, out_W: int = 2) -> Tuple[int, int]:
+    """The two arguments of pfnl_stream_packing for open_stream's ``packing`` / ``out_packing`` (None = planes; the sides are independent)
+    on sides set by the other keywords, W pixels wide in and out_W out; ValueError with the table's words (pfnl_amd/packed.py
+    side_refused) for a side that disagrees.  Needs no device."""
+    from . import packed as _packed
+    out_format = pixel_format if out_format is None else out_format
+    out_chroma = chroma if out_chroma is None else out_chroma
+    ids = []
+    for key, name, fmt, depth, sub, w in (("packing", packing, pixel_format, depth_argument(in_depth), chroma, W),
+                                          ("out_packing", out_packing, out_format, 10 if out_format in _capi.TEN_BIT_FORMATS else 8, out_chroma, out_W)):
+        if name is not None and not isinstance(name, str):
+            raise ValueError(f"{key}: None or one of {_packed.PACKINGS[1:]}, got {name!r}")
+        ids.append(_packed.packing_id(name))
+        why = _packed.side_refused(name, fmt in _capi.FORMATS_420, depth, sub, int(w))
+        if why:
+            raise ValueError(f"{key}: {why}")
+    return ids[0], ids[1]
 
 
 def output_grid(out_format: str, out_chroma: str = "420") -> Tuple[int, int]:
@@ -281,12 +322,17 @@ class VideoStream:
     ``out_format`` are subsampled (pfnl_amd/yuv.py CHROMAS) - frames of ``(2*H, W)`` / ``(3*H, W)`` samples at "422" / "444"; an RGB side
     ignores it.  ``vs.chroma`` / ``vs.out_chroma`` are the resolved names.
 
+    ``packing`` / ``out_packing`` (None | a name of pfnl_amd/packed.py PACKINGS; independent): ``push`` takes and ``pop`` returns one plane
+    of interleaved samples - uint8 ``packed.frame_shape`` or flat - and ``push_planes`` / ``pop_planes`` the one plane ``(H, row bytes)`` with
+    a pitch of its own.  A packing goes with the family, depth and chroma format of its side (packing_arguments).
+
     ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
     (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
-                 chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, ensemble=1):
+                 chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
+                 out_packing=None, ensemble=1):
         import torch
         self.in_depth = depth_argument(in_depth)    # (before the engine is touched, as every check of an argument)
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
@@ -299,6 +345,9 @@ class VideoStream:
         oH, oW, self.crop, self.place, self.fill = placement_arguments(out_size, engine.geom.scale * int(H), engine.geom.scale * int(W),
                                                                        self.out_format, crop, fit, place, sar, fill, self.out_chroma)
         self.out_size = (oH, oW) if oH else None
+        pk = packing_arguments(packing, out_packing, pixel_format, self.out_format, self.in_depth, self.chroma, self.out_chroma, int(W),
+                               oW if oH else engine.geom.scale * int(W))
+        self.packing, self.out_packing = (None if packing == "none" else packing), (None if out_packing == "none" else out_packing)
         self.fit, self.sar = fit, tuple(sar)
         self.matrix, self.full_range = matrix, bool(full_range)
         if not engine._ready:
@@ -361,6 +410,12 @@ class VideoStream:
             except Exception:
                 self.close()
                 raise
+        if pk[0] or pk[1]:                          # (planes on both sides: the session as it always was, and no call; behind every setting
+            try:                                    # a packing is checked against)
+                _capi.check(self._lib.pfnl_stream_packing(s, *pk))
+            except Exception:
+                self.close()
+                raise
         if self.ensemble != 1:                      # (1: the session as it always was, and no call)
             try:
                 _capi.check(self._lib.pfnl_stream_ensemble(s, self.ensemble))
@@ -403,14 +458,16 @@ class VideoStream:
         fetches the next frame (``pop`` is there for a caller that wants them at once)."""
         s = self._handle()
         due = self.ready()
-        if type(frame).__module__.startswith("torch"):
+        if self.packing is not None:
+            frame = packed_frame_argument(frame, self.packing, self.H, self.W)
+        else:
             frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth, self.chroma)
+        if type(frame).__module__.startswith("torch"):
             if not frame.is_cuda or frame.device.index != self.device.index:
                 raise ValueError(f"tensor on {frame.device}, stream on {self.device} (host frames: numpy arrays)")
             self._device_frames = True
             _capi.check(self._lib.pfnl_stream_push(s, C.c_void_p(frame.data_ptr()), 1))
         else:
-            frame = frame_argument(frame, self.pixel_format, self.H, self.W, self.in_depth, self.chroma)
             self._device_frames = False
             _capi.check(self._lib.pfnl_stream_push(s, frame.ctypes.data_as(C.c_void_p), 0))
         return self.pop_ready(due)
@@ -461,12 +518,15 @@ class VideoStream:
         shape = frame_shapes(self.out_format, oH, oW, self.out_chroma)[0]
         index, got = C.c_longlong(0), C.c_int(0)
         ten = self.out_format in _capi.TEN_BIT_FORMATS
+        if self.out_packing is not None:            # (bytes, whatever the unit)
+            from . import packed as _packed
+            shape, ten = _packed.frame_shape(self.out_packing, oH, oW), False
         if self._device_frames:
             import torch
             out = torch.empty(shape, dtype=torch.uint16 if ten else torch.uint8, device=self.device)
             _capi.check(self._lib.pfnl_stream_pop(s, C.c_void_p(out.data_ptr()), 1, C.byref(index), C.byref(got)))
         else:
-            out = np.empty(shape, frame_dtype(self.out_format))
+            out = np.empty(shape, np.uint8 if self.out_packing is not None else frame_dtype(self.out_format))
             _capi.check(self._lib.pfnl_stream_pop(s, out.ctypes.data_as(C.c_void_p), 0, C.byref(index), C.byref(got)))
         if not got.value:
             return None
@@ -485,7 +545,7 @@ class VideoStream:
             self.last_info = (0, 0)
 
     # ---- surfaces: planes with a row pitch (pfnl_amd/surface.py) -------------------------------
-    def _planes_struct(self, planes, fmt, H, W, chroma="420"):
+    def _planes_struct(self, planes, fmt, H, W, chroma="420", packing=None):
         """(pfnl_surface, on the device?) of a tuple of planes, all numpy arrays or all tensors on the stream's device."""
         on_device = [type(p).__module__.startswith("torch") for p in planes]
         if any(on_device) != all(on_device):
@@ -494,7 +554,7 @@ class VideoStream:
             for p in planes:
                 if not p.is_cuda or p.device.index != self.device.index:
                     raise ValueError(f"tensor on {p.device}, stream on {self.device} (host planes: numpy arrays)")
-        return _surface.as_struct(planes, fmt, H, W, chroma), bool(planes) and on_device[0]
+        return _surface.as_struct(planes, fmt, H, W, chroma, packing), bool(planes) and on_device[0]
 
     def push_planes(self, *planes) -> List[tuple]:
         """``push`` of a frame given as its planes in ``pixel_format`` - (Y, CbCr) for nv12, (Y, Cb, Cr) for i420, one (H, W, 3) or (H, 3 W)
@@ -502,7 +562,8 @@ class VideoStream:
         typically views ``surface[:H, :W]`` of a decoder's pitched surface, which is read where it lies.  Returns what ``push`` returns;
         the two may alternate within a sequence."""
         s = self._handle()
-        sf, on_device = self._planes_struct(planes, pushed_format(self.pixel_format, self.in_depth), self.H, self.W, self.chroma)
+        sf, on_device = self._planes_struct(planes, pushed_format(self.pixel_format, self.in_depth), self.H, self.W, self.chroma,
+                                            self.packing)
         due = self.ready()
         _capi.check(self._lib.pfnl_stream_push_surface(s, C.byref(sf), 1 if on_device else 0))
         self._device_frames = on_device
@@ -514,7 +575,7 @@ class VideoStream:
         frame's index, or None when no frame is deliverable (then nothing was written)."""
         s = self._handle()
         oH, oW = self.out_size if self.out_size is not None else (self.scale * self.H, self.scale * self.W)
-        sf, on_device = self._planes_struct(planes, self.out_format, oH, oW, self.out_chroma)
+        sf, on_device = self._planes_struct(planes, self.out_format, oH, oW, self.out_chroma, self.out_packing)
         for p in planes:
             if not on_device and not p.flags.writeable:
                 raise ValueError("pop_planes writes into its planes: a read-only array")

@@ -12,6 +12,9 @@ with H/2 rows of W (W/2 interleaved pairs); i420 / i010 Y, then Cb and Cr with H
 formats.  With ``chroma`` "422" / "444" (pfnl_amd/yuv.py CHROMAS) the chroma planes of a YUV format have H rows - of W / 2 samples (CbCr: W)
 at 4:2:2, of W (CbCr: 2 W) at 4:4:4 - and W alone is even at 4:2:2, nothing at 4:4:4; an RGB format ignores it.  A plane may be given with its row split into further axes - ``(H, W, 3)``, ``(H/2, W/2, 2)`` - as long as a row is contiguous.
 
+With ``packing`` (pfnl_amd/packed.py PACKINGS) the frame is ONE plane of H rows of ``packed.row_bytes`` bytes, uint8 whatever the unit, and
+``fmt`` says no more than the side's family and depth, which must agree with the packing.
+
 A window of a larger surface is just a view that starts at the window's first sample (even x and y): the frame is then that window."""
 from __future__ import annotations
 
@@ -23,12 +26,20 @@ import numpy as np
 from . import _capi
 
 
-def plane_shapes(fmt: str, H: int, W: int, chroma: str = "420") -> Tuple[tuple, ...]:
-    """Per plane of a frame of H x W in ``fmt``: (rows, samples per row, numpy dtype of a sample)."""
+def plane_shapes(fmt: str, H: int, W: int, chroma: str = "420", packing=None) -> Tuple[tuple, ...]:
+    """Per plane of a frame of H x W in ``fmt``: (rows, samples per row, numpy dtype of a sample).  ``packing``: the one plane of a packed
+    format, in bytes."""
     from . import yuv as _yuv
     if fmt not in _capi.PIXEL_FORMATS:
         raise ValueError(f"fmt: one of {sorted(_capi.PIXEL_FORMATS)}, got {fmt!r}")
     H, W = int(H), int(W)
+    if packing not in (None, "none"):
+        from . import packed as _packed
+        _packed.check(packing, H, W)
+        why = _packed.side_refused(packing, fmt in _capi.FORMATS_420, 10 if fmt in _capi.TEN_BIT_FORMATS else 8, chroma, W)
+        if why:
+            raise ValueError(why)
+        return ((H, _packed.row_bytes(packing, W), np.dtype(np.uint8)),)
     is_yuv = fmt in _capi.FORMATS_420                   # (the YUV layouts: 4:2:0 unless ``chroma`` says otherwise)
     if H < 1 or W < 1 or (is_yuv and chroma == "420" and (H % 2 or W % 2)):
         raise ValueError(f"H and W must be positive, and even for a 4:2:0 format, got {H} x {W}")
@@ -53,11 +64,11 @@ def _layout(a):
     return int(a.ctypes.data), a.shape, a.strides, a.dtype.itemsize, a.dtype.name
 
 
-def describe(arrays: Sequence, fmt: str, H: int, W: int, chroma: str = "420") -> Tuple[List[int], List[int]]:
+def describe(arrays: Sequence, fmt: str, H: int, W: int, chroma: str = "420", packing=None) -> Tuple[List[int], List[int]]:
     """(pointers, pitches in bytes) of the planes ``arrays`` hold for a frame of H x W in ``fmt``.  ValueError for a wrong plane count, a
     wrong dtype or shape, a row that is not contiguous (last-axis stride other than one sample), a negative stride, a row stride below
     the bytes of a row."""
-    shapes = plane_shapes(fmt, H, W, chroma)
+    shapes = plane_shapes(fmt, H, W, chroma, packing)
     arrays = tuple(arrays)
     if len(arrays) != len(shapes):
         raise ValueError(f"{fmt} has {len(shapes)} plane(s), got {len(arrays)}")
@@ -83,9 +94,9 @@ def describe(arrays: Sequence, fmt: str, H: int, W: int, chroma: str = "420") ->
     return pointers, pitches
 
 
-def as_struct(arrays: Sequence, fmt: str, H: int, W: int, chroma: str = "420") -> "_capi.pfnl_surface":
+def as_struct(arrays: Sequence, fmt: str, H: int, W: int, chroma: str = "420", packing=None) -> "_capi.pfnl_surface":
     """``describe`` as the ``pfnl_surface`` the library takes (the arrays must outlive the call it is passed to)."""
-    pointers, pitches = describe(arrays, fmt, H, W, chroma)
+    pointers, pitches = describe(arrays, fmt, H, W, chroma, packing)
     pad = 3 - len(pointers)
     return _capi.pfnl_surface((C.c_void_p * 3)(*pointers, *([None] * pad)), (C.c_size_t * 3)(*pitches, *([0] * pad)))
 
@@ -124,10 +135,10 @@ def embed(planes: Sequence[np.ndarray], pitches: Sequence[int], fill: int = 0) -
     return out
 
 
-def views(buffers: Sequence, fmt: str, H: int, W: int, chroma: str = "420") -> list:
+def views(buffers: Sequence, fmt: str, H: int, W: int, chroma: str = "420", packing=None) -> list:
     """The planes inside pitched buffers (uint8 ``[rows, pitch]``, numpy or tensors): strided (rows, samples) views in the format's sample
     type, sharing the buffers' memory - what ``describe``, ``VideoStream.push_planes`` and ``pop_planes`` take."""
-    shapes = plane_shapes(fmt, H, W, chroma)
+    shapes = plane_shapes(fmt, H, W, chroma, packing)
     buffers = list(buffers)
     if len(buffers) != len(shapes):
         raise ValueError(f"{fmt} has {len(shapes)} plane(s), got {len(buffers)} buffer(s)")
