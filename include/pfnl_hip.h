@@ -559,6 +559,49 @@ enum {
     PFNL_PACK_X2RGB10 = 6, PFNL_PACK_X2BGR10 = 7, PFNL_PACK_Y210 = 8, PFNL_PACK_V210 = 9
 };
 int pfnl_stream_packing(pfnl_stream* s, int in_pack, int out_pack);
+/* INTERLACED (additions to version 4; a session that does not call pfnl_stream_interlace, or sets PFNL_INTERLACE_OFF, issues the launches
+ * it always issued).  What an SDI card, a DVD or a broadcast archive delivers is woven: a frame of H rows (H even) is two fields of H / 2
+ * rows taken at two instants - the top field (parity 0) rows 0, 2, ..., the bottom field (parity 1) rows 1, 3, ...  With the setting on
+ * pushed frames are woven frames in the pushed layout, and progressive frames reach the ring; from the ring on nothing knows the frames
+ * were interlaced.  The rule is stated once on the host, pfnl_amd/deinterlace.py; its index rules once in pfnl_amd/csrc/field_geom.h:
+ *   fields: N frames are the fields k = 0 .. 2 N - 1 in time order; PFNL_FIELD_TFF: field 2 n is frame n's top field, 2 n + 1 its bottom
+ *     field; PFNL_FIELD_BFF the other way round.  An index q outside [0, 2 N - 1] is replaced by q + 2 (q < 0) or q - 2: same parity.
+ *   the progressive frame at the time of field k (parity p, samples A; P1, N1 = fields k -+ 1, P2, N2 = k -+ 2): row 2 i + p is A[i]; row
+ *     2 j + (1 - p), with u = j - p and field rows clamped to [0, H / 2 - 1], per sample (no horizontal term; MAX = 255 | 1023):
+ *       c = A[u], e = A[u + 1], s = clip((9 (c + e) - (A[u - 1] + A[u + 2]) + 8) >> 4, 0, MAX),  x = P1[j], y = N1[j], d = (x + y + 1) >> 1,
+ *       diff = max((|x - y| + 1) >> 1, (|P2[u] - c| + |P2[u + 1] - e| + 1) >> 1, (|N2[u] - c| + |N2[u + 1] - e| + 1) >> 1),
+ *       out = min(max(s, d - diff), d + diff): an exact weave where nothing moves, the field's own cubic within diff of d where it does.
+ *   decoding: a field is a picture of H / 2 rows - rows p, p + 2, ... of every plane of the pushed frame - decoded by the launch that
+ *     decodes a progressive frame of this setting, as a surface of H / 2 rows with every pitch doubled and the plane pointers advanced by
+ *     p rows: no conversion kernel is added.  Only 4:2:0 filters vertically; there a field's chroma rows belong to that field, H is a
+ *     multiple of 4, and a field's chroma is sited like a progressive picture's (the quarter-row offset of interlaced 4:2:0 is not modelled).
+ *   pfnl_stream_interlace: mode PFNL_INTERLACE_FRAME - one ring frame per pushed frame, at the time of its first field - or
+ *     PFNL_INTERLACE_FIELD - one per field, two per pushed frame -, PFNL_INTERLACE_OFF the session as it always was; field_order
+ *     PFNL_FIELD_TFF | PFNL_FIELD_BFF.  A setting beside layout, depth, chroma format, siting and packing: accepted only while no frame of
+ *     the current sequence has been pushed (else PFNL_ERR_STATE), it survives pfnl_stream_reset.  Unknown values, and 4:2:0 planes with
+ *     H % 4 != 0, are PFNL_ERR_INVALID; whichever of this call, pfnl_stream_format and pfnl_stream_chroma_format comes second makes that
+ *     check against the other's setting.  The first call that turns it on allocates the field store - three frames' decoded fields,
+ *     [3][2][H/2][W][3] samples of the input depth, ahead of the ring; PFNL_ERR_NOMEM leaves nothing half-made and the setting unchanged;
+ *     pfnl_stream_close frees it.
+ *   latency: frame n becomes deinterlaceable when frame n + 1 has been pushed, or at pfnl_stream_end - ONE FRAME of latency.  Then one
+ *     launch (pfnl_amd/csrc/deinterlace.hip) writes one ring frame or two straight into their ring slots, and each is admitted exactly as
+ *     a progressive push admits a frame: the scene sum and decision behind it, the batches it completes.  Pop indices count progressive
+ *     frames: N in frame mode, 2 N in field mode; pfnl_stream_ready, the batches, the range replay, ensemble, tiles and the output route
+ *     are what they are.  Every push path is taken: push and push_surface, host and device pointers (they may alternate), 8 and 10 bits,
+ *     RGB, NV12 / I420 at the three chroma formats, every packing.  A device-pointer push decodes and deinterlaces on the session's stream;
+ *     a host-pointer push does both on the copy stream before it returns.
+ *   the bound: a push that cannot admit every ring frame it completes returns PFNL_ERR_STATE ("pop first") and changes nothing - the
+ *     pushed frame is not stored, no counter moves; pfnl_stream_end first admits the held frame under the same bound, and a refusal
+ *     leaves the session un-ended.
+ *   cuts: pfnl_stream_mark_cut marks the next pushed frame; the mark travels with that frame and lands on the first ring frame made from
+ *     it.  pfnl_stream_reset forgets the field store's contents and a pending mark.  The deinterlacer itself reads no marks: across a cut
+ *     the rule's own clamp widens (t0 and t1 are large) and the made rows are the field's own cubic.
+ * The op hooks pfnl_op_deinterlace_u8 / _u10 below are the kernel on its own.
+ * Out of scope: edge-directed interpolation, inverse telecine and mixed streams, interlaced output, the interlaced 4:2:0 siting offset,
+ * marks read by the deinterlacer, 12 and 16 bits. */
+enum { PFNL_INTERLACE_OFF = 0, PFNL_INTERLACE_FRAME = 1, PFNL_INTERLACE_FIELD = 2 };
+enum { PFNL_FIELD_TFF = 0, PFNL_FIELD_BFF = 1 };
+int pfnl_stream_interlace(pfnl_stream* s, int mode, int field_order);
 /* SELF-ENSEMBLE in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With
  * n in {2, 4, 8} the one forward of every batch is pfnl_forward_ensemble(..., n, ...) (SELF-ENSEMBLE above); gather, quantisation, the
  * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  n = 1 is
@@ -943,6 +986,19 @@ int pfnl_op_rgb_to_packed_u8(void* plane, size_t pitch, int pack, int matrix, in
                              const uint8_t* rgb, void* stream);
 int pfnl_op_rgb_to_packed_u10(void* plane, size_t pitch, int pack, int matrix, int full_range, int siting, int n, size_t frame_stride, int H, int W,
                               const uint16_t* rgb, void* stream);
+/* The kernel of INTERLACED on its own: five decoded fields, tight [H/2][W][3] samples each (read-only; they may be one another, as at a
+ * sequence's ends), `cur` of parity `parity` -> the progressive frame out [H][W][3] at cur's time; uint8, or uint16 whose samples are
+ * taken as min(v, 1023) (_u10).  Device pointers, asynchronous on `stream`, any alignment a sample can have.  A NULL pointer, H < 2 or
+ * odd, W < 1, a parity other than 0 or 1: PFNL_ERR_INVALID before any HIP call, with a message that names the argument. */
+int pfnl_op_deinterlace_u8(const uint8_t* p2, const uint8_t* p1, const uint8_t* cur, const uint8_t* n1, const uint8_t* n2, int H, int W, int parity,
+                           uint8_t* out, void* stream);
+int pfnl_op_deinterlace_u10(const uint16_t* p2, const uint16_t* p1, const uint16_t* cur, const uint16_t* n1, const uint16_t* n2, int H, int W,
+                            int parity, uint16_t* out, void* stream);
+/* ... and the launch a field-rate session issues per push: fields[0 .. 5] are six consecutive fields k - 2 .. k + 3 (field k = fields[2]
+ * of parity `parity`, field k + 1 of the other), out [2][H][W][3] the progressive frames at the times of fields k and k + 1, both made by
+ * ONE launch.  The same refusals (the message names fields[i]). */
+int pfnl_op_deinterlace_pair_u8(const uint8_t* const fields[6], int H, int W, int parity, uint8_t* out, void* stream);
+int pfnl_op_deinterlace_pair_u10(const uint16_t* const fields[6], int H, int W, int parity, uint16_t* out, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

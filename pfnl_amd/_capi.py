@@ -175,6 +175,11 @@ SIGNATURES = {
     "pfnl_op_packed_to_rgb_u10": (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, C.c_size_t, _i, _i, _vp, _vp]),
     "pfnl_op_rgb_to_packed_u8": (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, C.c_size_t, _i, _i, _vp, _vp]),
     "pfnl_op_rgb_to_packed_u10": (_i, [_vp, C.c_size_t, _i, _i, _i, _i, _i, C.c_size_t, _i, _i, _vp, _vp]),
+    "pfnl_stream_interlace": (_i, [_vp, _i, _i]),
+    "pfnl_op_deinterlace_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pfnl_op_deinterlace_u10": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pfnl_op_deinterlace_pair_u8": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
+    "pfnl_op_deinterlace_pair_u10": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
     "pfnl_op_gather_windows_u10": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows_u10_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_scene_sad_u10": (_i, [_vp, _vp, _i, _i, _vp, _vp]),

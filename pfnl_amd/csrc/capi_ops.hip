@@ -1231,6 +1231,57 @@ int pfnl_op_rgb_to_packed_u10(void* plane, size_t pitch, int pack, int matrix, i
     return 0;
 }
 
+// ---- interlaced input: the deinterlacer on five decoded fields (include/pfnl_hip.h INTERLACED; deinterlace.hip) -------
+static int deinterlace_op_refused(const void* p2, const void* p1, const void* cur, const void* n1, const void* n2, int H, int W, int parity,
+                                  const void* out, int sample_bytes) {
+    const void* const ptr[6] = {p2, p1, cur, n1, n2, out};
+    const char* const name[6] = {"p2", "p1", "cur", "n1", "n2", "out"};
+    for (int k = 0; k < 6; ++k) {
+        if (!ptr[k]) return fail(PFNL_ERR_INVALID, std::string("deinterlace: ") + name[k] + " is NULL");
+        if (reinterpret_cast<uintptr_t>(ptr[k]) % sample_bytes) return fail(PFNL_ERR_INVALID, std::string("deinterlace: ") + name[k] + ": uint16 samples are 2-byte aligned");
+    }
+    if (H < 2 || (H & 1)) return fail(PFNL_ERR_INVALID, "deinterlace: H must be even and at least 2");
+    if (W < 1) return fail(PFNL_ERR_INVALID, "deinterlace: W must be at least 1");
+    if (parity != 0 && parity != 1) return fail(PFNL_ERR_INVALID, "deinterlace: parity is 0 (cur is the top field) or 1");
+    return 0;
+}
+
+int pfnl_op_deinterlace_u8(const uint8_t* p2, const uint8_t* p1, const uint8_t* cur, const uint8_t* n1, const uint8_t* n2, int H, int W, int parity,
+                           uint8_t* out, void* stream) {
+    if (int r = deinterlace_op_refused(p2, p1, cur, n1, n2, H, W, parity, out, 1)) return r;
+    HIPCHK(pfnl::launch_deinterlace(p2, p1, cur, n1, n2, H, W, parity, out, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_deinterlace_u10(const uint16_t* p2, const uint16_t* p1, const uint16_t* cur, const uint16_t* n1, const uint16_t* n2, int H, int W,
+                            int parity, uint16_t* out, void* stream) {
+    if (int r = deinterlace_op_refused(p2, p1, cur, n1, n2, H, W, parity, out, 2)) return r;
+    HIPCHK(pfnl::launch_deinterlace(p2, p1, cur, n1, n2, H, W, parity, out, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C++" template <typename T>
+static int op_deinterlace_pair(const T* const fields[6], int H, int W, int parity, T* out, void* stream) {
+    if (!fields) return fail(PFNL_ERR_INVALID, "deinterlace: fields is NULL");
+    for (int k = 0; k < 6; ++k) {
+        if (!fields[k]) return fail(PFNL_ERR_INVALID, "deinterlace: fields[" + std::to_string(k) + "] is NULL");
+        if (reinterpret_cast<uintptr_t>(fields[k]) % sizeof(T)) return fail(PFNL_ERR_INVALID, "deinterlace: fields[" + std::to_string(k) + "]: uint16 samples are 2-byte aligned");
+    }
+    if (int r = deinterlace_op_refused(fields[0], fields[1], fields[2], fields[3], fields[4], H, W, parity, out, (int)sizeof(T))) return r;
+    const pfnl::DeinterlaceJob<T> jobs[2] = {{fields[0], fields[1], fields[2], fields[3], fields[4], out, parity},
+                                             {fields[1], fields[2], fields[3], fields[4], fields[5], out + (size_t)H * W * 3, 1 - parity}};
+    HIPCHK(pfnl::launch_deinterlace(jobs, 2, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_deinterlace_pair_u8(const uint8_t* const fields[6], int H, int W, int parity, uint8_t* out, void* stream) {
+    return op_deinterlace_pair(fields, H, W, parity, out, stream);
+}
+
+int pfnl_op_deinterlace_pair_u10(const uint16_t* const fields[6], int H, int W, int parity, uint16_t* out, void* stream) {
+    return op_deinterlace_pair(fields, H, W, parity, out, stream);
+}
+
 // as pfnl_op_gather_windows_u8: what both gathers refuse before any HIP call (scene_first: null for the plain one)
 static int gather_u10_refused(const uint16_t* ring, const long long* scene_first, const float* win, int cap, long long last, long long first,
                               int count, int T, int H, int W) {

@@ -14,6 +14,7 @@
 #include "../../include/pfnl_hip.h"
 #include "capi_internal.h"
 #include "common.h"
+#include "field_geom.h"
 #include "stream_route.h"
 #include "tile_geom.h"
 
@@ -83,9 +84,19 @@ struct pfnl_stream {
     int32_t* rtab = nullptr;                          // rplan.r.blob on the device
     pfnl::OutRoute route{};
     StageSlot slot[pfnl::ROUTE_STAGES];
+    // interlaced input (pfnl_stream_interlace; field_geom.h): the decoded fields of the three newest woven frames, ahead of the ring
+    int il_mode = PFNL_INTERLACE_OFF, il_order = PFNL_FIELD_TFF;
+    uint8_t* fstore = nullptr;                        // [3][2][H/2][W][3] samples of the input depth: woven frame m in slot m % 3, its field of parity p at [p]
+    long long woven = 0, woven_done = 0;              // woven frames pushed; of those, the ones that have become ring frames
+    bool woven_mark[3] = {false, false, false};       // pfnl_stream_mark_cut's mark, travelling with the woven frame in the slot
+    hipEvent_t il_ev = nullptr;                       // the newest use of the field store on the session's stream (device-pointer pushes, end)
+    bool il_on_s = false;                             // ... that the copy stream has not yet been ordered behind
 };
 
 namespace {
+
+// a frame of the current sequence has been pushed: the settings are fixed until pfnl_stream_reset
+bool started(const pfnl_stream* s) { return s->pushed || s->woven; }
 
 int get_option(pfnl_stream* s, const char* key, std::string* v) {
     char buf[64];
@@ -249,6 +260,8 @@ int drop_sequence(pfnl_stream* s) {
     s->pushed = s->launched = s->delivered = 0;
     s->ended = false;
     s->mark = s->decided_on_s = s->has_info = false;
+    s->woven = s->woven_done = 0;                     // (both streams are idle: nothing reads the field store)
+    s->woven_mark[0] = s->woven_mark[1] = s->woven_mark[2] = s->il_on_s = false;
     if (int e = restore_options(s)) r = e;
     return r;
 }
@@ -370,6 +383,130 @@ int decode_packed(pfnl_stream* s, const uint8_t* yuv, uint8_t* dst, hipStream_t 
     return 0;
 }
 
+// ---- interlaced input (include/pfnl_hip.h INTERLACED): woven frames -> decoded fields in the field store -> progressive ring frames ----
+
+// a tightly packed pushed frame at `base` as the surface it is: its planes one behind the other, rows of their own bytes (a packing: of
+// the tight frame's pitch)
+pfnl_surface tight_surface(const pfnl_stream* s, const uint8_t* base) {
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(pushed_format(s), s->H, s->W, s->in_chroma, s->in_pack);
+    pfnl_surface sf{};
+    for (int k = 0; k < g.planes; ++k) {
+        sf.plane[k] = const_cast<uint8_t*>(base);
+        sf.pitch[k] = s->in_pack != PFNL_PACK_NONE ? pfnl::pack_tight_pitch(s->in_pack, s->W) : g.plane[k].row_bytes;
+        base += g.plane[k].rows * sf.pitch[k];
+    }
+    return sf;
+}
+
+uint8_t* field_at(const pfnl_stream* s, long long k) {    // field k of the sequence, in the slot of its frame
+    return s->fstore + ((size_t)(pfnl::field_frame(k) % 3) * 2 + pfnl::field_parity(k, s->il_order)) * (s->in_bytes / 2);
+}
+
+// The field of parity p of the woven frame `frame` (device planes; an RGB frame's may be host memory: from_host) -> its place in the slot
+// of woven frame s->woven, as RGB, by the launch that decodes a progressive frame of this setting - on a surface of H / 2 rows.
+int decode_field(pfnl_stream* s, const pfnl_surface& frame, int p, bool from_host, hipStream_t on) {
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(pushed_format(s), s->H, s->W, s->in_chroma, s->in_pack);
+    const pfnl_surface f = pfnl::field_surface(frame, g.planes, p);
+    uint8_t* const dst = s->fstore + ((size_t)(s->woven % 3) * 2 + p) * (s->in_bytes / 2);
+    const int h = s->H / 2;
+    const bool nv12 = s->in_fmt == PFNL_PIX_NV12, sub420 = s->in_chroma == PFNL_CHROMA_420;
+    if (s->in_pack != PFNL_PACK_NONE)
+        HIPCHK(pfnl::launch_packed_to_rgb(f.plane[0], f.pitch[0], 0, s->in_pack, dst, s->in_depth == 10 ? s->coef10 : s->coef, 1, h, s->W,
+                                          s->in_siting, on));
+    else if (s->in_fmt == PFNL_PIX_RGB24)
+        HIPCHK(hipMemcpy2DAsync(dst, g.plane[0].row_bytes, f.plane[0], f.pitch[0], g.plane[0].row_bytes, h,
+                                from_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, on));
+    else if (!sub420 && s->in_depth == 10)
+        HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(f, nv12), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, h, s->W,
+                                                     s->in_chroma, s->in_siting, on));
+    else if (!sub420)
+        HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(f, nv12), dst, nv12, s->coef, 1, h, s->W, s->in_chroma, s->in_siting, on));
+    else if (s->in_depth == 10)
+        HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u10(pfnl_internal_yuv_planes(f, nv12), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, h, s->W,
+                                                     s->in_siting, on));
+    else
+        HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(f, nv12), dst, nv12, s->coef, 1, h, s->W, s->in_siting, on));
+    return 0;
+}
+
+pfnl::RingCounters ring_counters(const pfnl_stream* s) {
+    return pfnl::RingCounters{s->pushed, s->launched, s->delivered, (int)s->q.size(), s->q.empty() ? 0 : s->q.front().first};
+}
+
+// the ring frames of woven frame s->woven_done, one launch, into the slots of ring frames s->pushed ..
+template <typename T>
+int launch_woven(pfnl_stream* s, int yield, hipStream_t on) {
+    const long long n = s->woven_done, fields = 2 * s->woven;
+    pfnl::DeinterlaceJob<T> job[2];
+    for (int i = 0; i < yield; ++i) {
+        const long long k = 2 * n + i;
+        const auto at = [&](long long q) { return reinterpret_cast<const T*>(field_at(s, pfnl::field_replace(q, fields))); };
+        job[i] = pfnl::DeinterlaceJob<T>{at(k - 2), at(k - 1), at(k), at(k + 1), at(k + 2),
+                                         reinterpret_cast<T*>(s->ring + (size_t)((s->pushed + i) % s->cap) * s->in_bytes), pfnl::field_parity(k, s->il_order)};
+    }
+    HIPCHK(pfnl::launch_deinterlace(job, yield, s->H, s->W, on));
+    return 0;
+}
+
+// Woven frame s->woven_done becomes its ring frames: the kernel writes them into their slots in one launch, and each is admitted as a
+// progressive push admits a frame (push_frame: the scene decision behind it, `pushed`, pump).  The caller has seen that the bound admits
+// them all.  The frame's mark lands on the first of them.
+int admit_woven(pfnl_stream* s, int is_device) {
+    const int yield = pfnl::interlace_yield(s->il_mode);
+    s->mark = s->woven_mark[s->woven_done % 3];
+    for (int i = 0; i < yield; ++i) {
+        const auto make = [&](hipStream_t on) {           // (the second frame's slot was written with the first's)
+            if (i) return 0;
+            return s->in_depth == 10 ? launch_woven<uint16_t>(s, yield, on) : launch_woven<uint8_t>(s, yield, on);
+        };
+        if (int e = push_frame(s, is_device, [&](uint8_t*) { return make(s->s); }, [&](uint8_t*) { return make(s->cs); })) return e;
+    }
+    ++s->woven_done;
+    return 0;
+}
+
+// What every push is with interlacing on: the bound for every ring frame the push completes, on copies of the counters (nothing has
+// changed where it refuses); the frame's two fields decoded into the slot of the field store - device pointers on the session's stream,
+// host pointers on the copy stream, YUV and packings through the staging frame -; then the woven frame before it, which now has both
+// neighbours, becomes its ring frames.  The field store is used on one stream at a time: the copy stream is idle when a push returns, and
+// falls in behind the session's stream's newest use of it first.
+int push_woven(pfnl_stream* s, int is_device, const pfnl_surface& frame) {
+    if (s->ended) return fail(PFNL_ERR_STATE, "push after pfnl_stream_end (pfnl_stream_reset starts the next sequence)");
+    const int yield = s->woven ? pfnl::interlace_yield(s->il_mode) : 0;
+    pfnl::RingCounters c = ring_counters(s);
+    if (!pfnl::ring_admit_all(s->T, s->batch, s->cap, yield, &c))
+        return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
+    HIPCHK(hipSetDevice(s->device));
+    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || s->in_pack != PFNL_PACK_NONE;
+    if (!is_device && s->il_on_s) {
+        HIPCHK(hipStreamWaitEvent(s->cs, s->il_ev, 0));
+        s->il_on_s = false;
+    }
+    pfnl_surface from = frame;
+    if (!is_device && yuv_in) {                       // (the staging frame is free again: every push ends with the copy stream idle)
+        const pfnl::SurfaceGeom g = pfnl::surface_geom(pushed_format(s), s->H, s->W, s->in_chroma, s->in_pack);
+        from = tight_surface(s, s->yin);
+        for (int k = 0; k < g.planes; ++k)
+            HIPCHK(hipMemcpy2DAsync(from.plane[k], from.pitch[k], frame.plane[k], frame.pitch[k], g.plane[k].row_bytes, g.plane[k].rows,
+                                    hipMemcpyHostToDevice, s->cs));
+    }
+    for (int p = 0; p < 2; ++p)
+        if (int e = decode_field(s, from, p, !is_device && !yuv_in, is_device ? s->s : s->cs)) return e;
+    s->woven_mark[s->woven % 3] = s->mark;
+    s->mark = false;
+    ++s->woven;
+    int r = 0;
+    if (yield)
+        r = admit_woven(s, is_device);
+    else if (!is_device)
+        HIPCHK(hipStreamSynchronize(s->cs));          // (the caller's memory is free on return)
+    if (is_device) {
+        HIPCHK(hipEventRecord(s->il_ev, s->s));
+        s->il_on_s = true;
+    }
+    return r;
+}
+
 void drop_slot(StageSlot& t) {
     for (uint8_t* p : t.buf)
         if (p) (void)hipFree(p);
@@ -385,6 +522,8 @@ void release(pfnl_stream* s) {
     if (s->scene_first) (void)hipFree(s->scene_first);
     if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
     if (s->yin) (void)hipFree(s->yin);
+    if (s->fstore) (void)hipFree(s->fstore);
+    if (s->il_ev) (void)hipEventDestroy(s->il_ev);
     if (s->rtab) (void)hipFree(s->rtab);
     if (s->ring) (void)hipFree(s->ring);
     if (s->win) (void)hipFree(s->win);
@@ -417,7 +556,7 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
     HIPCHK(hipSetDevice(s->device));
     if (frees) HIPCHK(hipStreamSynchronize(s->s));
     int32_t* tab = nullptr;
-    uint8_t *yin = nullptr, *ring = nullptr;
+    uint8_t *yin = nullptr, *ring = nullptr, *fstore = nullptr;   // (the field store follows the ring's depth)
     bool ok = true;
     if (plan && plan->cH) {
         const std::vector<int32_t>& blob = plan->r.blob;
@@ -425,6 +564,7 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
         ok = ok && hipMemcpy(tab, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (in_depth != s->in_depth) ok = ok && hipMalloc(reinterpret_cast<void**>(&ring), (size_t)s->cap * in_bytes) == hipSuccess;
+    if (in_depth != s->in_depth && s->fstore) ok = ok && hipMalloc(reinterpret_cast<void**>(&fstore), 3 * in_bytes) == hipSuccess;
     if (yin_need > s->yin_cap) ok = ok && hipMalloc(reinterpret_cast<void**>(&yin), yin_need) == hipSuccess;
     for (StageSlot& t : fresh)
         for (int i = 0; i < 2 && t.cap; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&t.buf[i]), t.cap) == hipSuccess;
@@ -433,6 +573,7 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
         if (tab) (void)hipFree(tab);
         if (yin) (void)hipFree(yin);
         if (ring) (void)hipFree(ring);
+        if (fstore) (void)hipFree(fstore);
         for (StageSlot& t : fresh) drop_slot(t);
         return fail(PFNL_ERR_NOMEM, nomem);
     }
@@ -449,6 +590,10 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
     if (ring) {
         (void)hipFree(s->ring);
         s->ring = ring;
+    }
+    if (fstore) {
+        (void)hipFree(s->fstore);
+        s->fstore = fstore;
     }
     s->in_depth = in_depth;
     s->in_bytes = in_bytes;
@@ -540,6 +685,7 @@ int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
     // the frame is H*W*3/2 samples (2 H W | 3 H W), or the tight frame of a packing, and reaches its slot through the kernel, as RGB
     const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || s->in_pack != PFNL_PACK_NONE;
     const size_t yuv_bytes = yuv_frame_bytes(s, s->in_fmt, s->in_depth, s->in_chroma, s->in_pack);
+    if (s->il_mode) return push_woven(s, is_device, tight_surface(s, frame));
     return push_frame(
         s, is_device,
         [&](uint8_t* dst) {
@@ -565,6 +711,7 @@ int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_d
     const pfnl::SurfaceGeom g = pfnl::surface_geom(fmt, s->H, s->W, s->in_chroma, s->in_pack);
     const bool packed = s->in_pack != PFNL_PACK_NONE;
     const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || packed, nv12 = s->in_fmt == PFNL_PIX_NV12, sub420 = s->in_chroma == PFNL_CHROMA_420;
+    if (s->il_mode) return push_woven(s, is_device, *frame);
     return push_frame(
         s, is_device,
         [&](uint8_t* dst) {                           // YUV and every packing: the kernel reads the surface where it lies
@@ -608,6 +755,15 @@ int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_d
 int pfnl_stream_end(pfnl_stream* s) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     HIPCHK(hipSetDevice(s->device));
+    if (s->il_mode && !s->ended && s->woven > s->woven_done) {   // the held frame first, under a push's bound: its fields past the end repeat
+        pfnl::RingCounters c = ring_counters(s);
+        if (!pfnl::ring_admit_all(s->T, s->batch, s->cap, pfnl::interlace_yield(s->il_mode), &c))
+            return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
+        const int r = admit_woven(s, 1);              // (on the session's stream: the copy stream is idle between calls)
+        HIPCHK(hipEventRecord(s->il_ev, s->s));
+        s->il_on_s = true;
+        if (r) return r;
+    }
     s->ended = true;
     if (int e = pump(s)) return e;
     if (s->delivered == s->pushed) return restore_options(s);   // (nothing left to pop: nothing in flight either)
@@ -651,7 +807,7 @@ int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_devi
 int pfnl_stream_ensemble(pfnl_stream* s, int n) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (n != 1 && n != 2 && n != 4 && n != 8) return fail(PFNL_ERR_INVALID, "ensemble: n must be 1, 2, 4 or 8");
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the ensemble is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "the ensemble is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     s->ensemble = n;
     return 0;
 }
@@ -660,7 +816,7 @@ int pfnl_stream_tile(pfnl_stream* s, const pfnl_tiling* t) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (t)
         if (const char* why = pfnl::tiling_refused(s->H, s->W, *t)) return fail(PFNL_ERR_INVALID, why);
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the tiling is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "the tiling is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     s->tiled = t != nullptr;
     s->tiling = t ? *t : pfnl_tiling{};
     return 0;
@@ -671,7 +827,7 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
     if (mode < 0 || mode > 2) return fail(PFNL_ERR_INVALID, "scenes: mode 0 (off), 1 (marks) or 2 (marks and the detector)");
     if (mode == 2 && !(threshold > 0.0 && threshold <= 255.0))
         return fail(PFNL_ERR_INVALID, "scenes: the threshold is a mean luma difference in (0, 255]");
-    if (s->pushed) return fail(PFNL_ERR_STATE, "scenes are set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "scenes are set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     if (mode && !s->scene_first) {
         HIPCHK(hipSetDevice(s->device));
         const size_t words = 2 * (size_t)s->cap + 2;  // scene_first | sad | the sum's scratch (zero between launches)
@@ -723,7 +879,7 @@ int pfnl_stream_packing(pfnl_stream* s, int in_pack, int out_pack) {
         return fail(PFNL_ERR_INVALID, std::string("input ") + why);
     if (const char* why = pfnl::pack_refused(out_pack, pfnl::is_yuv(s->out_fmt), pfnl::is_10bit(s->out_fmt) ? 10 : 8, s->out_chroma, s->route.out_w))
         return fail(PFNL_ERR_INVALID, std::string("output ") + why);
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the packing is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "the packing is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, s->in_depth, s->in_chroma, s->out_chroma, in_pack, out_pack,
                          "packing staging allocation failed");
 }
@@ -733,10 +889,12 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (const char* why = pfnl::route_refused(in_fmt, out_fmt, s->route.out_h, s->route.out_w, s->out_chroma)) return fail(PFNL_ERR_INVALID, why);
     if (int e = packing_contradicted(s, in_fmt, out_fmt, s->in_depth, s->in_chroma, s->out_chroma, s->route.out_w)) return e;
+    if (const char* why = pfnl::interlace_refused(s->il_mode, s->il_order, s->H, pfnl::is_yuv(in_fmt), s->in_chroma, s->in_pack))
+        return fail(PFNL_ERR_INVALID, why);
     pfnl::YuvCoef coef, coef10;
     if (!pfnl::yuv_coefficients(8, matrix, full_range, &coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, s->in_depth, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
                          "format staging allocation failed");
 }
@@ -747,7 +905,7 @@ int pfnl_stream_input_depth(pfnl_stream* s, int bits) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (bits != 8 && bits != 10) return fail(PFNL_ERR_INVALID, "input depth: 8 or 10 bits");
     if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, bits, s->in_chroma, s->out_chroma, s->route.out_w)) return e;
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the input depth is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "the input depth is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, bits, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
                          "input ring allocation failed");
 }
@@ -760,9 +918,37 @@ int pfnl_stream_chroma_format(pfnl_stream* s, int in_chroma, int out_chroma) {
         return fail(PFNL_ERR_INVALID, "chroma format: PFNL_CHROMA_420, PFNL_CHROMA_422 or PFNL_CHROMA_444 on either side");
     if (const char* why = pfnl::route_refused(s->in_fmt, s->out_fmt, s->route.out_h, s->route.out_w, out_chroma)) return fail(PFNL_ERR_INVALID, why);
     if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, s->in_depth, in_chroma, out_chroma, s->route.out_w)) return e;
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the chroma format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (const char* why = pfnl::interlace_refused(s->il_mode, s->il_order, s->H, pfnl::is_yuv(s->in_fmt), in_chroma, s->in_pack))
+        return fail(PFNL_ERR_INVALID, why);
+    if (started(s)) return fail(PFNL_ERR_STATE, "the chroma format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, s->in_depth, in_chroma, out_chroma, s->in_pack, s->out_pack,
                          "chroma format staging allocation failed");
+}
+
+// Interlaced input: pushed frames are woven, the ring receives progressive frames (field_geom.h; deinterlace.hip).  The field store is
+// allocated by the first call that turns it on, at the input depth (apply_setting makes it follow a later change of depth).
+int pfnl_stream_interlace(pfnl_stream* s, int mode, int field_order) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (const char* why = pfnl::interlace_refused(mode, field_order, s->H, pfnl::is_yuv(s->in_fmt), s->in_chroma, s->in_pack))
+        return fail(PFNL_ERR_INVALID, why);
+    if (started(s)) return fail(PFNL_ERR_STATE, "interlacing is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (mode && !s->fstore) {
+        HIPCHK(hipSetDevice(s->device));
+        uint8_t* store = nullptr;
+        hipEvent_t ev = nullptr;
+        bool ok = hipMalloc(reinterpret_cast<void**>(&store), 3 * s->in_bytes) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (store) (void)hipFree(store);
+            return fail(PFNL_ERR_NOMEM, "field store allocation failed");
+        }
+        s->fstore = store;
+        s->il_ev = ev;
+    }
+    s->il_mode = mode;
+    s->il_order = field_order;
+    return 0;
 }
 
 // no memory and no route depend on the sitings: they are arguments of the two conversion launches
@@ -771,7 +957,7 @@ int pfnl_stream_chroma_siting(pfnl_stream* s, int in_siting, int out_siting) {
     for (int v : {in_siting, out_siting})
         if (v < PFNL_SITING_LEFT || v > PFNL_SITING_TOPLEFT)
             return fail(PFNL_ERR_INVALID, "chroma siting: PFNL_SITING_LEFT, PFNL_SITING_CENTER or PFNL_SITING_TOPLEFT on either side");
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the chroma siting is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "the chroma siting is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     s->in_siting = in_siting;
     s->out_siting = out_siting;
     return 0;
@@ -788,7 +974,7 @@ int pfnl_stream_place(pfnl_stream* s, int out_H, int out_W, const pfnl_rect* src
     if (const char* no = pfnl::route_refused(s->in_fmt, s->out_fmt, plan.cH ? plan.cH : sH, plan.cW ? plan.cW : sW, s->out_chroma))
         return fail(PFNL_ERR_INVALID, no);
     if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, s->in_depth, s->in_chroma, s->out_chroma, plan.cW ? plan.cW : sW)) return e;
-    if (s->pushed) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     for (int k = 0; k < 3 && fill_rgb; ++k) plan.fill[k] = fill_rgb[k];
     return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, s->in_depth, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
                          "resize allocation failed");
@@ -799,7 +985,7 @@ int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) { return pfnl_strea
 int pfnl_stream_mark_cut(pfnl_stream* s) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (!s->scene_mode) return fail(PFNL_ERR_STATE, "mark_cut: scenes are off (pfnl_stream_scenes)");
-    if (s->pushed) s->mark = true;                    // (frame 0 starts scene 0 and is no cut)
+    if (started(s)) s->mark = true;                   // (frame 0 starts scene 0 and is no cut)
     return 0;
 }
 

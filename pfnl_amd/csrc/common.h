@@ -250,6 +250,24 @@ hipError_t launch_packed_to_rgb(const void* plane, size_t pitch, size_t frame_st
 hipError_t launch_rgb_to_packed(const void* rgb, void* plane, size_t pitch, size_t frame_stride, int pack, const YuvCoef& c, int n, int H, int W,
                                 int siting, hipStream_t s);
 
+// ---- interlaced input: five decoded fields -> one progressive frame (deinterlace.hip; the rule: pfnl_amd/deinterlace.py) ----
+// The fields are tight [H/2][W][3] samples of T (uint8_t, or uint16_t whose values are taken as min(v, 1023)), read-only, and may be one
+// another; cur has parity `parity` (0: it holds the frame's even rows); out is the tight frame [H][W][3] and overlaps none of them.  H even
+// and >= 2, W >= 1, any alignment a sample can have (16-byte words where 3 W samples and every pointer are multiples of 16 bytes, 4-byte
+// words for multiples of 4, else single samples).  n = 2 makes both frames of a pushed frame in ONE launch.  hipErrorInvalidValue otherwise.
+template <typename T>
+struct DeinterlaceJob {
+    const T *p2, *p1, *cur, *n1, *n2;
+    T* out;
+    int parity;
+};
+hipError_t launch_deinterlace(const DeinterlaceJob<uint8_t>* jobs, int n, int H, int W, hipStream_t s);
+hipError_t launch_deinterlace(const DeinterlaceJob<uint16_t>* jobs, int n, int H, int W, hipStream_t s);
+hipError_t launch_deinterlace(const uint8_t* p2, const uint8_t* p1, const uint8_t* cur, const uint8_t* n1, const uint8_t* n2, int H, int W, int parity,
+                              uint8_t* out, hipStream_t s);
+hipError_t launch_deinterlace(const uint16_t* p2, const uint16_t* p1, const uint16_t* cur, const uint16_t* n1, const uint16_t* n2, int H, int W,
+                              int parity, uint16_t* out, hipStream_t s);
+
 // ---- RGB frames at a chosen raster: the tap tables (resize.hip; the rule: pfnl_amd/resize.py) ----
 constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in
 constexpr int RESIZE_TW = 64;            // output pixels of one workgroup: across,

@@ -998,6 +998,61 @@ def rgb_to_packed(frames, name: str, matrix: str = "bt709", full_range=False, si
     return out.view(n, H, pitch)
 
 
+# ---- interlaced input (include/pfnl_hip.h INTERLACED; the rule: pfnl_amd/deinterlace.py) ---------------------------------------------------
+DEINTERLACE_STRIP_ROWS = 4                                  # csrc/field_geom.h DEINT_STRIP_ROWS: the rows of the progressive frame a lane walks down
+
+
+def _deinterlace(fields, parity, out, req, dtype, hook):
+    names = ("p2", "p1", "cur", "n1", "n2")
+    ptrs = [req(f, n) for f, n in zip(fields, names)]
+    cur = fields[2]
+    if cur.dim() != 3 or cur.shape[2] != 3 or any(tuple(f.shape) != tuple(cur.shape) or f.device != cur.device for f in fields):
+        raise ValueError("the five fields are [H/2, W, 3] tensors of one shape on one device")
+    if parity not in (0, 1):
+        raise ValueError(f"parity: 0 or 1, got {parity!r}")
+    h, W, _ = cur.shape
+    out = _out(out, (2 * h, W, 3), dtype, cur.device)
+    _capi.check(hook(*ptrs, 2 * h, W, int(parity), req(out, "out"), _stream(cur)))
+    return out
+
+
+def deinterlace(p2, p1, cur, n1, n2, parity, out=None):
+    """Five decoded fields, contiguous uint8 [H/2,W,3] tensors on the GPU (they may be one another, and start at any address), ``cur`` of
+    parity ``parity`` -> the progressive frame [H,W,3] at cur's time, byte for byte pfnl_amd/deinterlace.py interpolate
+    (pfnl_op_deinterlace_u8: the kernel ahead of the streaming session's ring).  ``out``: write there."""
+    import torch
+    return _deinterlace((p2, p1, cur, n1, n2), parity, out, _req_u8, torch.uint8, _capi.load_library().pfnl_op_deinterlace_u8)
+
+
+def deinterlace_pair(fields, parity, out=None):
+    """Six consecutive fields k - 2 .. k + 3, [H/2,W,3] uint8 (or all uint16: min(v, 1023)) tensors on the GPU, field k = ``fields[2]`` of
+    parity ``parity`` -> [2,H,W,3]: the progressive frames at the times of fields k and k + 1, made by ONE launch
+    (pfnl_op_deinterlace_pair_u8 / _u10: what a field-rate session issues per push)."""
+    import torch
+    fields = list(fields)
+    if len(fields) != 6:
+        raise ValueError("six consecutive fields")
+    ten = fields[2].dtype == torch.uint16
+    req = _req_u16 if ten else _req_u8
+    ptrs = (C.c_void_p * 6)(*(req(f, f"fields[{k}]") for k, f in enumerate(fields)))
+    cur = fields[2]
+    if cur.dim() != 3 or cur.shape[2] != 3 or any(tuple(f.shape) != tuple(cur.shape) or f.device != cur.device for f in fields):
+        raise ValueError("the six fields are [H/2, W, 3] tensors of one shape on one device")
+    if parity not in (0, 1):
+        raise ValueError(f"parity: 0 or 1, got {parity!r}")
+    h, W, _ = cur.shape
+    out = _out(out, (2, 2 * h, W, 3), cur.dtype, cur.device)
+    lib = _capi.load_library()
+    _capi.check((lib.pfnl_op_deinterlace_pair_u10 if ten else lib.pfnl_op_deinterlace_pair_u8)(ptrs, 2 * h, W, int(parity), req(out, "out"), _stream(cur)))
+    return out
+
+
+def deinterlace_u10(p2, p1, cur, n1, n2, parity, out=None):
+    """``deinterlace`` on uint16 fields, every sample taken as min(v, 1023) (pfnl_op_deinterlace_u10; interpolate with maxv = 1023)."""
+    import torch
+    return _deinterlace((p2, p1, cur, n1, n2), parity, out, _req_u16, torch.uint16, _capi.load_library().pfnl_op_deinterlace_u10)
+
+
 def _ring_u10(ring, name):
     _req_u16(ring, "ring")
     if ring.dim() != 4 or ring.shape[3] != 3:

@@ -95,7 +95,8 @@ def session_keywords(in_format: str, out_format=None, **session_kw) -> dict:
 def run(reader, writer, open_stream, out_format=None, log=None, **session_kw) -> int:
     """Every frame of ``reader`` (RawReader) through a session, into ``writer`` (RawWriter); returns the frame count.  ``open_stream`` is
     ``PFNLEngine.open_stream`` or anything with its keywords; ``session_kw`` as ``session_keywords`` takes them.  Frames are written in
-    index order as ``push`` and ``end`` return them.  One line with frames, seconds and fps goes to ``log``."""
+    index order as ``push`` and ``end`` return them - with ``interlaced="field"`` (and ``field_order``: a raw pipe has no header to say) two per
+    frame read.  One line with frames, seconds and fps goes to ``log``."""
     kw = session_keywords(reader.name, out_format, **session_kw)
     batch = kw.pop("batch")
     t0 = time.perf_counter()
@@ -113,8 +114,9 @@ def run(reader, writer, open_stream, out_format=None, log=None, **session_kw) ->
         for frame in reader:
             deliver(vs.push(frame))
         deliver(vs.end())
-    if done != reader.frames:
-        raise RuntimeError(f"{reader.frames} frames read, {done} delivered")
+    due = reader.frames * (2 if kw.get("interlaced") == "field" else 1)   # (at field rate a woven frame is two)
+    if done != due:
+        raise RuntimeError(f"{reader.frames} frames read, {done} delivered where {due} were due")
     seconds = time.perf_counter() - t0
     print(f"pfnl_amd.rawvideo: {done} frames in {seconds:.2f} s ({done / seconds if seconds > 0 else 0.0:.2f} fps)",
           file=sys.stderr if log is None else log)
@@ -146,6 +148,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--siting", choices=("left", "center", "topleft"), default="left", help="where the 4:2:2 chroma samples sit, in and out")
     ap.add_argument("--batch", type=int, default=1, help="windows per forward")
     ap.add_argument("--out-size", type=_size, default=None, metavar="HxW")
+    ap.add_argument("--interlaced", choices=("frame", "field"), default=None,
+                    help="the frames are woven fields: deinterlace on the device, one progressive frame per frame or per field")
+    ap.add_argument("--field-order", choices=("tff", "bff"), default="tff", help="which field of a woven frame comes first (a raw pipe has no header)")
     return ap
 
 
@@ -170,8 +175,9 @@ def main(argv=None) -> int:
             weights = synth.synthetic_weights(geom, seed=a.synthetic_weights)
         eng = PFNLEngine(geom, device=0)
         eng.load_weights(weights)
+        woven = {} if a.interlaced is None else {"interlaced": a.interlaced, "field_order": a.field_order}
         run(reader, RawWriter(fout), eng.open_stream, out_format=a.out_format, batch=a.batch, matrix=a.matrix, full_range=a.full_range,
-            chroma_siting=a.siting, out_size=a.out_size)
+            chroma_siting=a.siting, out_size=a.out_size, **woven)
         fout.flush()
     except (ValueError, PFNLHipError) as e:
         print(f"pfnl_amd.rawvideo: {e}", file=sys.stderr)

@@ -54,6 +54,11 @@ out_packing="bgra")`` takes a capture card's frames and delivers a swap chain's:
 means planes; a packing goes with the family, depth and chroma format its side is set to (a YUV ``pixel_format`` only says the side is
 YUV).  Frames are uint8 arrays of ``packed.frame_shape`` - bytes, whatever the unit - or flat.
 
+Interlaced input (off by default): ``open_stream(H, W, batch, pixel_format="i420", interlaced="field", field_order="tff")`` takes WOVEN
+frames - both fields in the pushed layout, whatever it is - and deinterlaces them on the device ahead of the ring by the integer rule of
+pfnl_amd/deinterlace.py: one progressive frame per pushed frame at "frame", two at "field", a frame later than the push that brought
+them.  Everything behind the ring is what it was.
+
 Surfaces: ``vs.push_planes(y, cbcr)`` / ``vs.pop_planes(y, cbcr)`` take and fill a frame as a decoder or encoder holds it - one array per
 plane, each with the row pitch its strides say (pfnl_amd/surface.py), e.g. ``surface[:H, :W]`` of a pitched device allocation - in the
 session's formats; a device NV12 / I420 surface is converted where it lies, and only the samples of a destination are written.
@@ -184,6 +189,17 @@ def packing_arguments(packing=None, out_packing=None, pixel_format="rgb24", out_
         if why:
             raise ValueError(f"{key}: {why}")
     return ids[0], ids[1]
+
+
+def interlace_arguments(interlaced=None, field_order="tff", H: int = 4, pixel_format="rgb24", chroma="420", packing=None) -> Tuple[int, int]:
+    """The two arguments of pfnl_stream_interlace for open_stream's ``interlaced`` (None = off: no call) and ``field_order``, for frames of H
+    rows in the input setting of the other keywords; ValueError for anything the library would refuse (pfnl_amd/deinterlace.py).  Needs no
+    device."""
+    from . import deinterlace as _deinterlace
+    mode, order = _deinterlace.mode_id(interlaced), _deinterlace.order_id(field_order)
+    if mode:
+        _deinterlace.check_height(int(H), pixel_format in _capi.FORMATS_420 and chroma == "420" and packing in (None, "none"))
+    return mode, order
 
 
 def output_grid(out_format: str, out_chroma: str = "420") -> Tuple[int, int]:
@@ -326,15 +342,22 @@ class VideoStream:
     of interleaved samples - uint8 ``packed.frame_shape`` or flat - and ``push_planes`` / ``pop_planes`` the one plane ``(H, row bytes)`` with
     a pitch of its own.  A packing goes with the family, depth and chroma format of its side (packing_arguments).
 
+    ``interlaced`` (None | "frame" | "field") with ``field_order`` ("tff" | "bff"): every pushed frame is woven - two fields in the pushed
+    layout, whatever it is - and is deinterlaced on the device ahead of the ring (pfnl_amd/deinterlace.py): indices then count progressive
+    frames, one per pushed frame at "frame" and two at "field".  A frame is made when the one after it has been pushed, or at ``end()``;
+    4:2:0 planes need H to be a multiple of 4.  ``mark_cut()`` marks the next pushed frame and lands on the first frame made from it.
+
     ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
     (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
                  chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
-                 out_packing=None, ensemble=1):
+                 out_packing=None, interlaced=None, field_order="tff", ensemble=1):
         import torch
         self.in_depth = depth_argument(in_depth)    # (before the engine is touched, as every check of an argument)
+        il = interlace_arguments(interlaced, field_order, H, pixel_format, chroma, packing)
+        self.interlaced, self.field_order = interlaced, field_order
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
         sub = chroma_arguments(chroma, out_chroma)
         self.chroma, self.out_chroma = chroma, chroma if out_chroma is None else out_chroma
@@ -422,6 +445,12 @@ class VideoStream:
             except Exception:
                 self.close()
                 raise
+        if il[0]:                                   # (None: the session as it always was, and no call; behind the input setting it is checked
+            try:                                    # against, and the depth its field store follows)
+                _capi.check(self._lib.pfnl_stream_interlace(s, *il))
+            except Exception:
+                self.close()
+                raise
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -466,15 +495,40 @@ class VideoStream:
             if not frame.is_cuda or frame.device.index != self.device.index:
                 raise ValueError(f"tensor on {frame.device}, stream on {self.device} (host frames: numpy arrays)")
             self._device_frames = True
-            _capi.check(self._lib.pfnl_stream_push(s, C.c_void_p(frame.data_ptr()), 1))
-        else:
-            self._device_frames = False
-            _capi.check(self._lib.pfnl_stream_push(s, frame.ctypes.data_as(C.c_void_p), 0))
+            return self._hand_over(lambda: self._lib.pfnl_stream_push(s, C.c_void_p(frame.data_ptr()), 1), due)
+        self._device_frames = False
+        return self._hand_over(lambda: self._lib.pfnl_stream_push(s, frame.ctypes.data_as(C.c_void_p), 0), due)
+
+    def _hand_over(self, call, due, container=None) -> List[tuple]:
+        """``call`` pushes the frame; then the ``due`` frames are popped.  An interlaced session admits up to two ring frames per push, so
+        the library may ask for the due frames first ("pop first": it has changed nothing): they are popped, the push is repeated, and
+        they are returned from this call all the same.  A progressive session's calls are what they always were.  ``container``: what
+        ``_device_frames`` becomes once the frame has been taken (None: the caller has set it)."""
+        try:
+            _capi.check(call())
+        except _capi.PFNLHipError as e:
+            if self.interlaced is None or "pop first" not in str(e):
+                raise
+            if container is not None:
+                self._device_frames = container
+            frames = self.pop_ready(due)
+            _capi.check(call())
+            return frames
+        if container is not None:
+            self._device_frames = container
         return self.pop_ready(due)
 
     def end(self) -> List[tuple]:
         """No more frames: the remaining windows clamp at the last one.  Returns the remaining SR frames."""
-        _capi.check(self._lib.pfnl_stream_end(self._handle()))
+        s = self._handle()
+        try:
+            _capi.check(self._lib.pfnl_stream_end(s))
+        except _capi.PFNLHipError as e:             # (an interlaced session's held frame did not fit: what is ready is popped, once)
+            if self.interlaced is None or "pop first" not in str(e):
+                raise
+            frames = self.pop_ready()
+            _capi.check(self._lib.pfnl_stream_end(s))
+            return frames + self.pop_ready()
         return self.pop_ready()
 
     def reset(self) -> None:
@@ -565,9 +619,7 @@ class VideoStream:
         sf, on_device = self._planes_struct(planes, pushed_format(self.pixel_format, self.in_depth), self.H, self.W, self.chroma,
                                             self.packing)
         due = self.ready()
-        _capi.check(self._lib.pfnl_stream_push_surface(s, C.byref(sf), 1 if on_device else 0))
-        self._device_frames = on_device
-        return self.pop_ready(due)
+        return self._hand_over(lambda: self._lib.pfnl_stream_push_surface(s, C.byref(sf), 1 if on_device else 0), due, on_device)
 
     def pop_planes(self, *planes):
         """``pop`` into planes the caller owns, in ``out_format`` at the output size - numpy arrays or device tensors with a row pitch of

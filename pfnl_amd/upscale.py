@@ -9,7 +9,10 @@ as ``i420`` - or ``i010`` with ``--bits 10`` - under a header of the output's ra
 ``--bits 10``: at the default of 8 the ten bits are kept on the way in and cut on the way out.  Y4M carries no matrix: ``--matrix
 auto`` takes BT.601 up to 576 lines and BT.709 above.  4:2:2 and 4:4:4 streams (``C422``, ``C444``, ``C422p10``, ``C444p10``) are taken
 where ``--chroma`` names them (or ``any``) - without it such a stream exits 1 naming its tag - and ``--out-chroma`` sets the subsampling of
-the output apart from the input's; a ``C422`` stream is horizontally co-sited, so a 4:2:2 output is written with the siting "left".  ``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
+the output apart from the input's; a ``C422`` stream is horizontally co-sited, so a 4:2:2 output is written with the siting "left".  Interlaced streams (``It`` / ``Ib``, what ``ffmpeg -f yuv4mpegpipe`` writes for DVD and broadcast material) are taken with
+``--deinterlace frame|field`` - without it such a stream exits 1 naming its tag -: the frames are woven, the field order is the header's, the
+session deinterlaces on the device (pfnl_amd/deinterlace.py) and the output is ``Ip``, at field rate with twice the frames and ``F`` doubled.
+``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
 """
 from __future__ import annotations
 
@@ -33,12 +36,21 @@ def session_keywords(header, **session_kw) -> dict:
     header), and from the header the input siting, the range, ``in_depth=10`` for a 10-bit stream (and no such key for an 8-bit one),
     ``chroma`` for a 4:2:2 / 4:4:4 stream (and no such key for a 4:2:0 one; ``out_chroma`` likewise only where the caller names one) and -
     with ``fit`` alone - the sample aspect ratio.  A 4:2:2 output is co-sited across, as ``C422`` says: ``out_chroma_siting`` becomes "left"
-    where the caller names none.  ValueError for what a Y4M stream cannot hold."""
+    where the caller names none.  ``deinterlace`` ("frame" | "field") becomes ``interlaced`` with the header's field order for an ``It`` / ``Ib``
+    stream (and no such key for a progressive one); without it such a stream is a ValueError that names its tag.  ValueError for what a Y4M
+    stream cannot hold."""
     kw = dict(session_kw)
-    for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth", "chroma"):
+    for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth", "chroma", "interlaced", "field_order"):
         if fixed in kw:
             raise ValueError(f"{fixed} comes from the stream's header")
     kw.setdefault("batch", 1)
+    rate = kw.pop("deinterlace", None)                # "frame" | "field": what an It / Ib stream needs; a progressive stream ignores it
+    if rate not in (None, "frame", "field"):
+        raise ValueError(f'deinterlace: None, "frame" or "field", got {rate!r}')
+    if header.interlace in ("t", "b"):
+        if rate is None:
+            raise ValueError(f"y4m: an interlaced stream (I{header.interlace}) needs --deinterlace frame or field")
+        kw["interlaced"], kw["field_order"] = rate, "tff" if header.interlace == "t" else "bff"
     if kw.get("out_format") is None:
         kw["out_format"] = "i420"
     if kw["out_format"] not in OUT_FORMATS.values():
@@ -83,7 +95,8 @@ def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> i
         out_h, out_w = vs.out_size if vs.out_size is not None else (vs.scale * header.height, vs.scale * header.width)
         out_chroma = kw.get("out_chroma", kw.get("chroma", "420"))
         writer.write_header(header.for_output(out_w, out_h, siting=vs.out_chroma_siting, bits=10 if kw["out_format"] == "i010" else 8,
-                                              sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw["full_range"], chroma=out_chroma))
+                                              sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw["full_range"], chroma=out_chroma,
+                                              progressive="interlaced" in kw, double_rate=kw.get("interlaced") == "field"))
 
         def deliver(frames):
             nonlocal done
@@ -96,8 +109,9 @@ def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> i
         for frame in reader:
             deliver(vs.push(frame))
         deliver(vs.end())
-    if done != reader.frames:
-        raise RuntimeError(f"{reader.frames} frames read, {done} delivered")
+    due = reader.frames * (2 if kw.get("interlaced") == "field" else 1)
+    if done != due:
+        raise RuntimeError(f"{reader.frames} frames read, {done} delivered where {due} were due")
     seconds = time.perf_counter() - t0
     print(f"pfnl_amd.upscale: {done} frames in {seconds:.2f} s ({done / seconds if seconds > 0 else 0.0:.2f} fps)",
           file=sys.stderr if log is None else log)
@@ -151,6 +165,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--chroma", choices=("420", "422", "444", "any"), default="420", help="the subsampling of the input stream that is taken")
     ap.add_argument("--out-chroma", choices=("420", "422", "444"), default=None, help="the output's subsampling (default: the input's)")
     ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1)
+    ap.add_argument("--deinterlace", choices=("frame", "field"), default=None,
+                    help="take an interlaced (It / Ib) stream: one progressive frame per frame, or per field (twice the frames and the rate)")
     ap.add_argument("--tile", type=_tile, default=None, metavar="TH,TW[,PAD[,BATCH]]")
     return ap
 
@@ -162,7 +178,8 @@ def main(argv=None) -> int:
     fout = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     eng = None
     try:
-        reader = _y4m.Y4MReader(fin, depths=(8, 10), chromas=_y4m.CHROMAS if a.chroma == "any" else (a.chroma,))
+        reader = _y4m.Y4MReader(fin, depths=(8, 10), chromas=_y4m.CHROMAS if a.chroma == "any" else (a.chroma,),
+                                   interlaced=a.deinterlace is not None)
         from . import checkpoint, synth
         from .engine import PFNLEngine
         from .spec import PFNLGeometry
@@ -180,7 +197,7 @@ def main(argv=None) -> int:
             eng.set_option("precision", a.precision)
         upscale(reader, _y4m.Y4MWriter(fout), eng.open_stream, tile=a.tile, batch=a.batch, scene_cut=a.scene_cut, matrix=a.matrix,
                 full_range=a.full_range, out_format=OUT_FORMATS[a.bits], out_size=a.out_size, fit=a.fit, out_chroma_siting=a.out_siting,
-                ensemble=a.ensemble, out_chroma=a.out_chroma)
+                ensemble=a.ensemble, out_chroma=a.out_chroma, deinterlace=a.deinterlace)
         fout.flush()
     except (ValueError, PFNLHipError) as e:
         print(f"pfnl_amd.upscale: {e}", file=sys.stderr)

@@ -25,7 +25,7 @@ Out of scope: mono, 4:1:1 and alpha, 12 and 16 bits, interlaced streams, per-fra
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, field, replace
 from typing import Iterator, Optional, Tuple
 
 import numpy as np
@@ -64,6 +64,7 @@ class Y4MHeader:
     extensions: Tuple[str, ...] = ()
     bits: int = 8
     chroma: str = "420"
+    interlaced_ok: bool = field(default=False, compare=False, repr=False)   # ``It`` / ``Ib`` pass: the caller deinterlaces (pfnl_amd/deinterlace.py)
 
     def __post_init__(self):
         if self.chroma not in CHROMAS:
@@ -74,7 +75,7 @@ class Y4MHeader:
             raise ValueError(f"y4m: W must be even and at least 2 and H at least 1 (4:2:2), got W{self.width} H{self.height}")
         if self.chroma == "444" and (self.width < 1 or self.height < 1):
             raise ValueError(f"y4m: W and H must be at least 1, got W{self.width} H{self.height}")
-        if self.interlace not in (None, "p", "?"):
+        if self.interlace not in (None, "p", "?") and not (self.interlaced_ok and self.interlace in ("t", "b")):
             raise ValueError(f"y4m: interlaced streams are not supported (I{self.interlace}); deinterlace first")
         if self.siting not in TAG_OF_SITING:
             raise ValueError(f"y4m: siting: one of {sorted(TAG_OF_SITING)}, got {self.siting!r}")
@@ -99,10 +100,11 @@ class Y4MHeader:
         return self.frame_samples * (2 if self.bits == 10 else 1)
 
     @classmethod
-    def parse(cls, line: bytes, depths: Tuple[int, ...] = (8,), chromas: Tuple[str, ...] = ("420",)) -> "Y4MHeader":
+    def parse(cls, line: bytes, depths: Tuple[int, ...] = (8,), chromas: Tuple[str, ...] = ("420",), interlaced: bool = False) -> "Y4MHeader":
         """The header of its line (without or with the newline).  ``depths``: the sample depths the caller takes; with 10 among them
         ``C420p10`` parses to ``bits=10``, ``siting="left"``.  ``chromas``: the subsamplings the caller takes; with "422" / "444" among
-        them ``C422`` / ``C444`` (and, with 10 among ``depths``, ``C422p10`` / ``C444p10``) parse to that ``chroma``, ``siting="left"``."""
+        them ``C422`` / ``C444`` (and, with 10 among ``depths``, ``C422p10`` / ``C444p10``) parse to that ``chroma``, ``siting="left"``.  ``interlaced``: ``It`` / ``Ib`` (top / bottom field first) pass, and ``.interlace`` says
+        which; ``Im`` (mixed) is refused either way."""
         try:
             tokens = line.rstrip(b"\n").decode("ascii").split(" ")
         except UnicodeDecodeError:
@@ -147,7 +149,7 @@ class Y4MHeader:
                 raise ValueError(f"y4m: unknown header token {t!r}")
         if width is None or height is None:
             raise ValueError("y4m: the header needs W and H")
-        return cls(width, height, rate, interlace, sar, siting, tuple(ext), bits, chroma)
+        return cls(width, height, rate, interlace, sar, siting, tuple(ext), bits, chroma, bool(interlaced))
 
     def to_bytes(self) -> bytes:
         """The header line, newline included: W H F I A C, then the extensions."""
@@ -165,18 +167,24 @@ class Y4MHeader:
         return (" ".join(t) + "\n").encode("ascii")
 
     def for_output(self, width: int, height: int, siting: Optional[str] = None, bits: int = 8, sar: Optional[Tuple[int, int]] = None,
-                   full_range: Optional[bool] = None, chroma: Optional[str] = None) -> "Y4MHeader":
+                   full_range: Optional[bool] = None, chroma: Optional[str] = None, progressive: bool = False,
+                   double_rate: bool = False) -> "Y4MHeader":
         """The header of the stream made from this one: the new raster, siting, depth and aspect; ``F``, ``I`` and the extensions pass
         through - but ``XYSCSS``, which restates the chroma format and becomes ``XYSCSS=420P10`` at 10 bits (``422`` / ``444`` /
         ``422P10`` / ``444P10`` for those tags), and the range token where ``full_range`` says otherwise than the stream.  ``chroma`` None:
-        this stream's."""
+        this stream's.  ``progressive``: the frames have been deinterlaced, ``I`` becomes ``Ip``; ``double_rate``: at field rate, ``F`` doubles
+        its numerator."""
         chroma = self.chroma if chroma is None else chroma
+        rate = self.rate
+        if double_rate and rate is not None:
+            num, den = _ratio(rate, "F")
+            rate = f"{2 * num}:{den}"
         ext = [x for x in self.extensions if not x.startswith("XYSCSS=")]
         if full_range is not None and bool(full_range) != self.full_range:
             ext = [x for x in ext if not x.startswith(RANGE_KEY)] + [RANGE_KEY + ("FULL" if full_range else "LIMITED")]
         if bits == 10 or chroma != "420":
             ext.insert(0, f"XYSCSS={chroma}" + ("P10" if bits == 10 else ""))
-        return replace(self, width=int(width), height=int(height), siting=self.siting if siting is None else siting, bits=bits, chroma=chroma,
+        return replace(self, rate=rate, interlace="p" if progressive else self.interlace, width=int(width), height=int(height), siting=self.siting if siting is None else siting, bits=bits, chroma=chroma,
                        sar=self.sar if sar is None else tuple(sar), extensions=tuple(ext))
 
 
@@ -211,14 +219,15 @@ def _read_line(f) -> bytes:
 class Y4MReader:
     """``Y4MReader(fileobj)`` reads the header at once (``.header``); iterating yields every frame as a ``(H*3//2, W)`` uint8 array -
     little-endian uint16 for a ``C420p10`` stream, which ``depths=(8, 10)`` lets through; ``(2*H, W)`` / ``(3*H, W)`` for a ``C422`` /
-    ``C444`` stream, which ``chromas=("420", "422", "444")`` lets through."""
+    ``C444`` stream, which ``chromas=("420", "422", "444")`` lets through.  ``interlaced=True`` lets ``It`` / ``Ib`` streams through - their frames are woven, and
+    ``header.interlace`` says which field comes first."""
 
-    def __init__(self, fileobj, depths: Tuple[int, ...] = (8,), chromas: Tuple[str, ...] = ("420",)):
+    def __init__(self, fileobj, depths: Tuple[int, ...] = (8,), chromas: Tuple[str, ...] = ("420",), interlaced: bool = False):
         self._f = fileobj
         line = _read_line(fileobj)
         if line is None:
             raise ValueError("y4m: empty stream")
-        self.header = Y4MHeader.parse(line, depths, chromas)
+        self.header = Y4MHeader.parse(line, depths, chromas, interlaced)
         self.frames = 0
 
     def read_frame(self):
