@@ -7,6 +7,10 @@
 // The output side is one route (stream_route.h: quantise -> resize / place -> YUV, at 1 or 2 bytes per sample) and one slot per stage: the
 // setters validate through that header and hand their candidate to apply_setting, the only place that allocates or frees a slot
 // after open; enqueue and pop_frame read the stored route.
+// The input side is one route as well (stream_route.h InRoute: the pushed surface, its tight frame, the staging frame, the decode kind),
+// stored by apply_setting next to the output route: every push - a tight frame is the surface with the tight pitches - is stage_host
+// (host pointers: the planes into the staging frame) and decode_surface (the one dispatch on decode kind and depth), on the whole frame
+// or, with interlacing on, on each of its fields.  A setter copies the stored Setting, changes its own fields and asks candidate_refused.
 #include <cmath>
 #include <deque>
 #include <string>
@@ -34,14 +38,23 @@ struct StageSlot {
     size_t cap = 0;                                   // bytes of each
 };
 
+// What the setters set and both routes follow (pfnl_stream_format, _input_depth, _chroma_format, _packing): in_fmt / out_fmt name the
+// layout, the depth the pushed sample, the chroma formats the subsampling of a YUV edge, a packing an edge as one plane of interleaved samples.
+struct Setting {
+    int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
+    int in_depth = 8;                                 // 8, or 10: pushed samples, ring and staging frame are uint16
+    int in_chroma = PFNL_CHROMA_420, out_chroma = PFNL_CHROMA_420;
+    int in_pack = PFNL_PACK_NONE, out_pack = PFNL_PACK_NONE;
+    pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
+    pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010, the input side at an input depth of 10
+};
+
 }  // namespace
 
 struct pfnl_stream {
     pfnl_handle* h = nullptr;
     int H = 0, W = 0, batch = 0, T = 0, scale = 0, device = 0, cap = 0;
     size_t lr_bytes = 0, sr_bytes = 0;                // one LR / SR frame, uint8
-    int in_depth = 8;                                 // pfnl_stream_input_depth: 8, or 10 - pushed samples, ring and staging frame are uint16
-    size_t in_bytes = 0;                              // one LR frame as the ring holds it: lr_bytes samples of 1 or 2 bytes
     hipStream_t s = nullptr;                          // everything the session computes runs here
     hipStream_t cs = nullptr;                         // host-pointer frames in and out: copies that never wait for a later batch
     uint8_t* ring = nullptr;                          // [cap][H][W][3] samples of the input depth, frame f in slot f % cap
@@ -69,20 +82,18 @@ struct pfnl_stream {
     bool has_info = false;                            // what pfnl_stream_pop_info returns
     long long info_first = 0;
     unsigned long long info_sad = 0;
-    // the setting (pfnl_stream_format, pfnl_stream_input_depth, pfnl_stream_resize, pfnl_stream_place; stored by apply_setting alone).  The ring stays RGB: a YUV frame is converted
+    // the setting (pfnl_stream_format, pfnl_stream_input_depth, pfnl_stream_chroma_format, pfnl_stream_packing, pfnl_stream_resize,
+    // pfnl_stream_place; stored by apply_setting alone, with the two routes it yields).  The ring stays RGB: a YUV frame is converted
     // on its way into its ring slot.  Every stage `route` runs has a slot with room for a batch - 8- and 10-bit samples share it, as a
     // sequence has one route - and no other stage holds memory; stage 0 is allocated at open.
-    int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
+    Setting set;
     int in_siting = PFNL_SITING_LEFT, out_siting = PFNL_SITING_LEFT;   // pfnl_stream_chroma_siting: where a 4:2:0 edge's chroma sits
-    int in_chroma = PFNL_CHROMA_420, out_chroma = PFNL_CHROMA_420;     // pfnl_stream_chroma_format: how a YUV edge's chroma is subsampled
-    int in_pack = PFNL_PACK_NONE, out_pack = PFNL_PACK_NONE;           // pfnl_stream_packing: an edge as one plane of interleaved samples
-    pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
-    pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010, the input side at an input depth of 10
-    uint8_t* yin = nullptr;                           // [H*W*3/2] samples (4:2:2: 2 H W, 4:4:4: 3 H W; a packing: its tight frame): a host-pointer frame on its way to the kernel; from the first YUV in_fmt or input packing on
+    uint8_t* yin = nullptr;                           // [in.staging_bytes] the staging frame: a host-pointer frame on its way to the kernel; from the first YUV in_fmt or input packing on
     size_t yin_cap = 0;                               // its bytes
     pfnl::PlacePlan rplan;                            // stage 1: a rectangle of the raster on a canvas, the whole onto the whole for a plain size; cH = 0: off
     int32_t* rtab = nullptr;                          // rplan.r.blob on the device
     pfnl::OutRoute route{};
+    pfnl::InRoute in{};                               // the pushed frame of `set` at H x W: in.ring_bytes is one LR frame as the ring holds it
     StageSlot slot[pfnl::ROUTE_STAGES];
     // interlaced input (pfnl_stream_interlace; field_geom.h): the decoded fields of the three newest woven frames, ahead of the ring
     int il_mode = PFNL_INTERLACE_OFF, il_order = PFNL_FIELD_TFF;
@@ -111,6 +122,8 @@ template <typename T>
 int run_route(pfnl_stream* s, const Batch& b) {
     constexpr bool ten = sizeof(T) == 2;
     const pfnl::OutRoute& r = s->route;
+    const Setting& c = s->set;
+    const pfnl::YuvCoef& coef = ten ? c.coef10 : c.coef;
     const auto slot = [&](int k) { return reinterpret_cast<T*>(s->slot[k].buf[b.slot]); };
     HIPCHK(pfnl::launch_quantise(s->sr, slot(0), (size_t)b.count * s->sr_bytes, s->s));
     if (r.runs[1]) {                                  // one launch writes the whole canvas, the fill colour included (a plain size has none)
@@ -118,16 +131,15 @@ int run_route(pfnl_stream* s, const Batch& b) {
         const T fill[3] = {sample(s->rplan.fill[0]), sample(s->rplan.fill[1]), sample(s->rplan.fill[2])};
         HIPCHK(pfnl::launch_resize_place(slot(0), slot(1), s->rplan, s->rtab, fill, b.count, s->s));
     }
-    const bool semiplanar = s->out_fmt == PFNL_PIX_NV12 || s->out_fmt == PFNL_PIX_P010;
-    if (r.runs[2] && s->out_pack != PFNL_PACK_NONE)      // the tight packed frame: rows of pack_tight_pitch, frames of stage_bytes[2]
-        HIPCHK(pfnl::launch_rgb_to_packed(slot(r.runs[1] ? 1 : 0), slot(2), pfnl::pack_tight_pitch(s->out_pack, r.out_w), r.stage_bytes[2], s->out_pack,
-                                          ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w, s->out_siting, s->s));
-    else if (r.runs[2] && s->out_chroma == PFNL_CHROMA_420)   // reads the resampled frames where stage 1 runs
-        HIPCHK(pfnl::launch_rgb_to_yuv420(slot(r.runs[1] ? 1 : 0), slot(2), semiplanar, ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w,
-                                          s->out_siting, s->s));
+    const bool semiplanar = c.out_fmt == PFNL_PIX_NV12 || c.out_fmt == PFNL_PIX_P010;
+    if (r.runs[2] && c.out_pack != PFNL_PACK_NONE)       // the tight packed frame: rows of pack_tight_pitch, frames of stage_bytes[2]
+        HIPCHK(pfnl::launch_rgb_to_packed(slot(r.runs[1] ? 1 : 0), slot(2), pfnl::pack_tight_pitch(c.out_pack, r.out_w), r.stage_bytes[2], c.out_pack,
+                                          coef, b.count, r.out_h, r.out_w, s->out_siting, s->s));
+    else if (r.runs[2] && c.out_chroma == PFNL_CHROMA_420)    // reads the resampled frames where stage 1 runs
+        HIPCHK(pfnl::launch_rgb_to_yuv420(slot(r.runs[1] ? 1 : 0), slot(2), semiplanar, coef, b.count, r.out_h, r.out_w, s->out_siting, s->s));
     else if (r.runs[2])
-        HIPCHK(pfnl::launch_rgb_to_yuv_chroma(slot(r.runs[1] ? 1 : 0), slot(2), semiplanar, ten ? s->coef10 : s->coef, b.count, r.out_h, r.out_w,
-                                              s->out_chroma, s->out_siting, s->s));
+        HIPCHK(pfnl::launch_rgb_to_yuv_chroma(slot(r.runs[1] ? 1 : 0), slot(2), semiplanar, coef, b.count, r.out_h, r.out_w, c.out_chroma,
+                                              s->out_siting, s->s));
     return 0;
 }
 
@@ -137,13 +149,13 @@ int enqueue(pfnl_stream* s, const Batch& b) {
     if (s->scene_mode) {
         // every frame up to b.last has been decided: on this stream, or on the copy stream before its push returned.  A replay
         // (check_batch) reads the same entries: the push bound keeps a batch's slots until it has been delivered.
-        if (s->in_depth == 10)
-            HIPCHK(pfnl::launch_gather_windows_u10_scenes(ring10, s->scene_first, s->win, s->cap, b.last, b.first, b.count, s->T, s->in_bytes, s->s));
+        if (s->set.in_depth == 10)
+            HIPCHK(pfnl::launch_gather_windows_u10_scenes(ring10, s->scene_first, s->win, s->cap, b.last, b.first, b.count, s->T, s->in.ring_bytes, s->s));
         else
             HIPCHK(pfnl::launch_gather_windows_u8_scenes(s->ring, s->scene_first, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
         HIPCHK(hipMemcpyAsync(s->info[b.slot], s->scene_first, 2 * (size_t)s->cap * sizeof(long long), hipMemcpyDeviceToHost, s->s));
-    } else if (s->in_depth == 10) {
-        HIPCHK(pfnl::launch_gather_windows_u10(ring10, s->win, s->cap, b.last, b.first, b.count, s->T, s->in_bytes, s->s));
+    } else if (s->set.in_depth == 10) {
+        HIPCHK(pfnl::launch_gather_windows_u10(ring10, s->win, s->cap, b.last, b.first, b.count, s->T, s->in.ring_bytes, s->s));
     } else {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
@@ -234,9 +246,9 @@ int decide_scene(pfnl_stream* s, hipStream_t on) {
     }
     const int prev = (int)((f - 1) % s->cap);
     const pfnl::SceneDecision d{s->sad, s->scene_first, slot, prev, f, s->mark ? 1 : 0, s->scene_mode == 2 ? 1 : 0, s->thr_sum};
-    const uint8_t* const a = s->ring + (size_t)slot * s->in_bytes;
-    const uint8_t* const b = s->ring + (size_t)prev * s->in_bytes;
-    if (s->in_depth == 10)
+    const uint8_t* const a = s->ring + (size_t)slot * s->in.ring_bytes;
+    const uint8_t* const b = s->ring + (size_t)prev * s->in.ring_bytes;
+    if (s->set.in_depth == 10)
         HIPCHK(pfnl::launch_scene_sad_u10(reinterpret_cast<const uint16_t*>(a), reinterpret_cast<const uint16_t*>(b), (size_t)s->H * s->W,
                                           s->sad + s->cap, d, on));
     else
@@ -280,7 +292,7 @@ int push_frame(pfnl_stream* s, int is_device, OnDevice&& on_device, OnHost&& on_
     if ((count && s->launched - s->delivered + count > 2LL * s->batch) || s->pushed - lo + 1 > s->cap)
         return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
     HIPCHK(hipSetDevice(s->device));
-    uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->in_bytes;
+    uint8_t* const dst = s->ring + (size_t)(s->pushed % s->cap) * s->in.ring_bytes;
     if (is_device) {
         if (int e = on_device(dst)) return e;
         if (s->scene_mode) {                          // behind the copy, ahead of any gather that can name the frame
@@ -350,84 +362,89 @@ int pop_frame(pfnl_stream* s, int is_device, long long* index, int* got, Deliver
     return 0;
 }
 
-// the format of a pushed frame as surface_geom.h knows it: in_fmt names the layout, the input depth the sample
-int pushed_format(const pfnl_stream* s) {
-    if (s->in_depth != 10) return s->in_fmt;
-    return s->in_fmt == PFNL_PIX_NV12 ? PFNL_PIX_P010 : (s->in_fmt == PFNL_PIX_I420 ? PFNL_PIX_I010 : PFNL_PIX_RGB10);
+// ---- the input route (stream_route.h InRoute, stored as s->in): a pushed surface -> RGB rows at `dst` ----
+
+// a tightly packed pushed frame at `base` as the surface it is: its planes one behind the other at the route's tight pitches
+pfnl_surface tight_surface(const pfnl_stream* s, const uint8_t* base) {
+    pfnl_surface sf{};
+    for (int k = 0; k < s->in.geom.planes; ++k) {
+        sf.plane[k] = const_cast<uint8_t*>(base);
+        sf.pitch[k] = s->in.pitch[k];
+        base += s->in.geom.plane[k].rows * sf.pitch[k];
+    }
+    return sf;
 }
 
-// the bytes of a pushed frame in `in_fmt`'s layout at a depth and a subsampling, or in a packing; 0 for RGB24 in planes, which needs no staging
-size_t yuv_frame_bytes(const pfnl_stream* s, int in_fmt, int in_depth, int chroma, int pack = PFNL_PACK_NONE) {
-    if (pack != PFNL_PACK_NONE) return pfnl::pack_frame_bytes(pack, s->H, s->W);
-    if (in_fmt == PFNL_PIX_RGB24) return 0;
-    const int fmt = in_depth != 10 ? in_fmt : (in_fmt == PFNL_PIX_NV12 ? PFNL_PIX_P010 : PFNL_PIX_I010);
-    return pfnl::packed_bytes(pfnl::surface_geom(fmt, s->H, s->W, chroma));
+// The one decode: `rows` rows of the surface `sf` of the session's input setting (the frame: H; one of its fields: H / 2) -> RGB at dst,
+// on `on`.  The only place that looks at the decode kind and the sample depth.  sf lies on the device; planar RGB is a copy and may lie
+// in host memory (from_host).
+// A tight frame comes here as tight_surface(), so the plane launchers see a frame stride of 0 where the tight launchers of yuv.hip /
+// yuv_chroma.hip pass the tight frame's bytes.  With n = 1 the stride enters the choice of the strip width alone (decode_strip_width,
+// strip_of), and never changes it: a strip of P samples needs W % P == 0, and the tight frame is H W 3/2 = (H / 2) 3 W samples at 4:2:0
+// (H even), 2 H W at 4:2:2, 3 H W at 4:4:4 - a multiple of W samples, so its bytes are a multiple of the P-sample word whenever W is.
+int decode_surface(pfnl_stream* s, const pfnl_surface& sf, int rows, uint8_t* dst, bool from_host, hipStream_t on) {
+    const Setting& c = s->set;
+    const bool ten = s->in.sample_bytes == 2, nv12 = c.in_fmt == PFNL_PIX_NV12;
+    const pfnl::YuvCoef& coef = ten ? c.coef10 : c.coef;
+    const pfnl::YuvPlanes yuv = pfnl_internal_yuv_planes(sf, nv12);   // (read by the two YUV kinds alone)
+    uint16_t* const dst10 = reinterpret_cast<uint16_t*>(dst);
+    const size_t row = s->in.geom.plane[0].row_bytes;
+    const hipMemcpyKind copy = from_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    switch (s->in.kind) {
+    case pfnl::IN_DECODE_PACK:
+        HIPCHK(pfnl::launch_packed_to_rgb(sf.plane[0], sf.pitch[0], 0, c.in_pack, dst, coef, 1, rows, s->W, s->in_siting, on));
+        return 0;
+    case pfnl::IN_DECODE_CHROMA:
+        HIPCHK(ten ? pfnl::launch_yuv_planes_to_rgb_chroma(yuv, dst10, nv12, coef, 1, rows, s->W, c.in_chroma, s->in_siting, on)
+                   : pfnl::launch_yuv_planes_to_rgb_chroma(yuv, dst, nv12, coef, 1, rows, s->W, c.in_chroma, s->in_siting, on));
+        return 0;
+    case pfnl::IN_DECODE_420:
+        HIPCHK(ten ? pfnl::launch_yuv420_planes_to_rgb_u10(yuv, dst10, nv12, coef, 1, rows, s->W, s->in_siting, on)
+                   : pfnl::launch_yuv420_planes_to_rgb_u8(yuv, dst, nv12, coef, 1, rows, s->W, s->in_siting, on));
+        return 0;
+    case pfnl::IN_DECODE_COPY:                        // rows that abut: one copy
+        HIPCHK(sf.pitch[0] == row ? hipMemcpyAsync(dst, sf.plane[0], rows * row, copy, on)
+                                  : hipMemcpy2DAsync(dst, row, sf.plane[0], sf.pitch[0], row, rows, copy, on));
+        return 0;
+    }
+    return fail(PFNL_ERR_STATE, "the session has no input route");   // (IN_DECODE_NONE: apply_setting stores no such setting)
 }
 
-// a packed YUV frame on the device -> its ring slot as RGB, at the session's input depth and subsampling
-int decode_packed(pfnl_stream* s, const uint8_t* yuv, uint8_t* dst, hipStream_t on) {
-    const bool nv12 = s->in_fmt == PFNL_PIX_NV12;
-    if (s->in_pack != PFNL_PACK_NONE)                 // (a tight frame of an input packing: one plane at its own pitch)
-        HIPCHK(pfnl::launch_packed_to_rgb(yuv, pfnl::pack_tight_pitch(s->in_pack, s->W), 0, s->in_pack, dst, s->in_depth == 10 ? s->coef10 : s->coef, 1,
-                                          s->H, s->W, s->in_siting, on));
-    else if (s->in_chroma != PFNL_CHROMA_420 && s->in_depth == 10)
-        HIPCHK(pfnl::launch_yuv_to_rgb_chroma(reinterpret_cast<const uint16_t*>(yuv), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, s->H,
-                                              s->W, s->in_chroma, s->in_siting, on));
-    else if (s->in_chroma != PFNL_CHROMA_420)
-        HIPCHK(pfnl::launch_yuv_to_rgb_chroma(yuv, dst, nv12, s->coef, 1, s->H, s->W, s->in_chroma, s->in_siting, on));
-    else if (s->in_depth == 10)
-        HIPCHK(pfnl::launch_yuv420_to_rgb(reinterpret_cast<const uint16_t*>(yuv), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, s->H, s->W,
-                                          s->in_siting, on));
-    else
-        HIPCHK(pfnl::launch_yuv420_to_rgb_u8(yuv, dst, nv12, s->coef, 1, s->H, s->W, s->in_siting, on));
+// The one staging step of a host push, on the copy stream: the caller's planes into the staging frame at the tight pitches (it is free
+// again: every push ends with the copy stream idle); *at = where the decode finds the frame.  Planar RGB has no staging frame: the decode
+// copies it from where it lies.  Planes that are tight and abut move in one copy - up to the last row's samples, as a surface promises
+// nothing behind them - else each plane in a 2-D copy of its rows' samples.
+int stage_host(pfnl_stream* s, const pfnl_surface& frame, pfnl_surface* at) {
+    *at = frame;
+    if (!s->in.staging_bytes) return 0;
+    *at = tight_surface(s, s->yin);
+    const pfnl::SurfaceGeom& g = s->in.geom;
+    const pfnl_surface tight = tight_surface(s, static_cast<const uint8_t*>(frame.plane[0]));
+    bool abut = true;
+    for (int k = 0; k < g.planes; ++k) abut = abut && frame.plane[k] == tight.plane[k] && frame.pitch[k] == tight.pitch[k];
+    const int last = g.planes - 1;
+    if (abut) {
+        HIPCHK(hipMemcpyAsync(s->yin, frame.plane[0], s->in.frame_bytes - (s->in.pitch[last] - g.plane[last].row_bytes), hipMemcpyHostToDevice, s->cs));
+        return 0;
+    }
+    for (int k = 0; k < g.planes; ++k)
+        HIPCHK(hipMemcpy2DAsync(at->plane[k], at->pitch[k], frame.plane[k], frame.pitch[k], g.plane[k].row_bytes, g.plane[k].rows, hipMemcpyHostToDevice, s->cs));
     return 0;
 }
 
 // ---- interlaced input (include/pfnl_hip.h INTERLACED): woven frames -> decoded fields in the field store -> progressive ring frames ----
 
-// a tightly packed pushed frame at `base` as the surface it is: its planes one behind the other, rows of their own bytes (a packing: of
-// the tight frame's pitch)
-pfnl_surface tight_surface(const pfnl_stream* s, const uint8_t* base) {
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(pushed_format(s), s->H, s->W, s->in_chroma, s->in_pack);
-    pfnl_surface sf{};
-    for (int k = 0; k < g.planes; ++k) {
-        sf.plane[k] = const_cast<uint8_t*>(base);
-        sf.pitch[k] = s->in_pack != PFNL_PACK_NONE ? pfnl::pack_tight_pitch(s->in_pack, s->W) : g.plane[k].row_bytes;
-        base += g.plane[k].rows * sf.pitch[k];
-    }
-    return sf;
-}
-
 uint8_t* field_at(const pfnl_stream* s, long long k) {    // field k of the sequence, in the slot of its frame
-    return s->fstore + ((size_t)(pfnl::field_frame(k) % 3) * 2 + pfnl::field_parity(k, s->il_order)) * (s->in_bytes / 2);
+    return s->fstore + ((size_t)(pfnl::field_frame(k) % 3) * 2 + pfnl::field_parity(k, s->il_order)) * (s->in.ring_bytes / 2);
 }
 
 // The field of parity p of the woven frame `frame` (device planes; an RGB frame's may be host memory: from_host) -> its place in the slot
 // of woven frame s->woven, as RGB, by the launch that decodes a progressive frame of this setting - on a surface of H / 2 rows.
 int decode_field(pfnl_stream* s, const pfnl_surface& frame, int p, bool from_host, hipStream_t on) {
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(pushed_format(s), s->H, s->W, s->in_chroma, s->in_pack);
-    const pfnl_surface f = pfnl::field_surface(frame, g.planes, p);
-    uint8_t* const dst = s->fstore + ((size_t)(s->woven % 3) * 2 + p) * (s->in_bytes / 2);
-    const int h = s->H / 2;
-    const bool nv12 = s->in_fmt == PFNL_PIX_NV12, sub420 = s->in_chroma == PFNL_CHROMA_420;
-    if (s->in_pack != PFNL_PACK_NONE)
-        HIPCHK(pfnl::launch_packed_to_rgb(f.plane[0], f.pitch[0], 0, s->in_pack, dst, s->in_depth == 10 ? s->coef10 : s->coef, 1, h, s->W,
-                                          s->in_siting, on));
-    else if (s->in_fmt == PFNL_PIX_RGB24)
-        HIPCHK(hipMemcpy2DAsync(dst, g.plane[0].row_bytes, f.plane[0], f.pitch[0], g.plane[0].row_bytes, h,
-                                from_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, on));
-    else if (!sub420 && s->in_depth == 10)
-        HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(f, nv12), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, h, s->W,
-                                                     s->in_chroma, s->in_siting, on));
-    else if (!sub420)
-        HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(f, nv12), dst, nv12, s->coef, 1, h, s->W, s->in_chroma, s->in_siting, on));
-    else if (s->in_depth == 10)
-        HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u10(pfnl_internal_yuv_planes(f, nv12), reinterpret_cast<uint16_t*>(dst), nv12, s->coef10, 1, h, s->W,
-                                                     s->in_siting, on));
-    else
-        HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(f, nv12), dst, nv12, s->coef, 1, h, s->W, s->in_siting, on));
-    return 0;
+    uint8_t* const dst = s->fstore + ((size_t)(s->woven % 3) * 2 + p) * (s->in.ring_bytes / 2);
+    return decode_surface(s, pfnl::field_surface(frame, s->in.geom.planes, p), s->H / 2, dst, from_host, on);
 }
+
 
 pfnl::RingCounters ring_counters(const pfnl_stream* s) {
     return pfnl::RingCounters{s->pushed, s->launched, s->delivered, (int)s->q.size(), s->q.empty() ? 0 : s->q.front().first};
@@ -442,7 +459,7 @@ int launch_woven(pfnl_stream* s, int yield, hipStream_t on) {
         const long long k = 2 * n + i;
         const auto at = [&](long long q) { return reinterpret_cast<const T*>(field_at(s, pfnl::field_replace(q, fields))); };
         job[i] = pfnl::DeinterlaceJob<T>{at(k - 2), at(k - 1), at(k), at(k + 1), at(k + 2),
-                                         reinterpret_cast<T*>(s->ring + (size_t)((s->pushed + i) % s->cap) * s->in_bytes), pfnl::field_parity(k, s->il_order)};
+                                         reinterpret_cast<T*>(s->ring + (size_t)((s->pushed + i) % s->cap) * s->in.ring_bytes), pfnl::field_parity(k, s->il_order)};
     }
     HIPCHK(pfnl::launch_deinterlace(job, yield, s->H, s->W, on));
     return 0;
@@ -457,7 +474,7 @@ int admit_woven(pfnl_stream* s, int is_device) {
     for (int i = 0; i < yield; ++i) {
         const auto make = [&](hipStream_t on) {           // (the second frame's slot was written with the first's)
             if (i) return 0;
-            return s->in_depth == 10 ? launch_woven<uint16_t>(s, yield, on) : launch_woven<uint8_t>(s, yield, on);
+            return s->set.in_depth == 10 ? launch_woven<uint16_t>(s, yield, on) : launch_woven<uint8_t>(s, yield, on);
         };
         if (int e = push_frame(s, is_device, [&](uint8_t*) { return make(s->s); }, [&](uint8_t*) { return make(s->cs); })) return e;
     }
@@ -477,21 +494,15 @@ int push_woven(pfnl_stream* s, int is_device, const pfnl_surface& frame) {
     if (!pfnl::ring_admit_all(s->T, s->batch, s->cap, yield, &c))
         return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
     HIPCHK(hipSetDevice(s->device));
-    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || s->in_pack != PFNL_PACK_NONE;
     if (!is_device && s->il_on_s) {
         HIPCHK(hipStreamWaitEvent(s->cs, s->il_ev, 0));
         s->il_on_s = false;
     }
     pfnl_surface from = frame;
-    if (!is_device && yuv_in) {                       // (the staging frame is free again: every push ends with the copy stream idle)
-        const pfnl::SurfaceGeom g = pfnl::surface_geom(pushed_format(s), s->H, s->W, s->in_chroma, s->in_pack);
-        from = tight_surface(s, s->yin);
-        for (int k = 0; k < g.planes; ++k)
-            HIPCHK(hipMemcpy2DAsync(from.plane[k], from.pitch[k], frame.plane[k], frame.pitch[k], g.plane[k].row_bytes, g.plane[k].rows,
-                                    hipMemcpyHostToDevice, s->cs));
-    }
+    if (!is_device)
+        if (int e = stage_host(s, frame, &from)) return e;
     for (int p = 0; p < 2; ++p)
-        if (int e = decode_field(s, from, p, !is_device && !yuv_in, is_device ? s->s : s->cs)) return e;
+        if (int e = decode_field(s, from, p, !is_device && !s->in.staging_bytes, is_device ? s->s : s->cs)) return e;
     s->woven_mark[s->woven % 3] = s->mark;
     s->mark = false;
     ++s->woven;
@@ -505,6 +516,18 @@ int push_woven(pfnl_stream* s, int is_device, const pfnl_surface& frame) {
         s->il_on_s = true;
     }
     return r;
+}
+
+// where both push entries end, each with its own argument checks behind it: the frame as a surface of the input route
+int push_surface(pfnl_stream* s, const pfnl_surface& frame, int is_device) {
+    if (s->il_mode) return push_woven(s, is_device, frame);
+    return push_frame(
+        s, is_device, [&](uint8_t* dst) { return decode_surface(s, frame, s->H, dst, false, s->s); },   // the kernel reads the surface where it lies
+        [&](uint8_t* dst) {
+            pfnl_surface from;
+            if (int e = stage_host(s, frame, &from)) return e;
+            return decode_surface(s, from, s->H, dst, !s->in.staging_bytes, s->cs);
+        });
 }
 
 void drop_slot(StageSlot& t) {
@@ -533,21 +556,21 @@ void release(pfnl_stream* s) {
 }
 
 // The one place where a setting becomes the session's: every setter ends here, with a candidate they have validated and no frame pushed
-// (`plan` NULL: the output size stays).  1. the route and a batch's bytes per stage; 2. everything new first - a stage slot whose capacity
+// (`plan` NULL: the output size stays).  1. the two routes: a batch's bytes per stage, the pushed frame's ring and staging bytes; 2. everything new first - a stage slot whose capacity
 // is below the need (stage 2's follows the output packing's row bytes, the staging frame the input packing's), the tap table of a new plan, the ring of another input depth, the staging frame of the first YUV in_fmt or of one at
 // a wider depth or subsampling (so whichever of pfnl_stream_format, pfnl_stream_input_depth and pfnl_stream_chroma_format comes later makes it) - and where one fails, what was just made is
 // freed, the session is what it was and the answer is PFNL_ERR_NOMEM with `nomem`; 3. the new buffers go in, the ones they replace and the
 // slots of stages the route does not run are freed, the setting is stored.  A call that replaces or releases device memory first waits
 // for the session's stream - a dropped sequence's device-pointer pops may still be reading it - and only such a call: pfnl_stream_format
 // waits where a 10-bit format meets 8-bit slots or a 4:2:0 slot is no longer needed, and not where it only adds memory or changes none.
-int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& coef, const pfnl::YuvCoef& coef10, pfnl::PlacePlan* plan,
-                  int in_depth, int in_chroma, int out_chroma, int in_pack, int out_pack, const char* nomem) {
+int apply_setting(pfnl_stream* s, const Setting& c, pfnl::PlacePlan* plan, const char* nomem) {
     const pfnl::PlacePlan& rp = plan ? *plan : s->rplan;
-    const pfnl::OutRoute route = pfnl::out_route(out_fmt, s->scale * s->H, s->scale * s->W, rp.cH, rp.cW, out_chroma, out_pack);   // (the delivered frame is the canvas)
+    const pfnl::OutRoute route = pfnl::out_route(c.out_fmt, s->scale * s->H, s->scale * s->W, rp.cH, rp.cW, c.out_chroma, c.out_pack);   // (the delivered frame is the canvas)
+    const pfnl::InRoute in = pfnl::in_route(c.in_fmt, c.in_depth, c.in_chroma, c.in_pack, s->H, s->W);
     StageSlot fresh[pfnl::ROUTE_STAGES];              // cap != 0: the stage's slot is too small and this one takes its place
-    const size_t in_bytes = s->lr_bytes * (in_depth == 10 ? 2 : 1);
-    const size_t yin_need = yuv_frame_bytes(s, in_fmt, in_depth, in_chroma, in_pack);
-    bool frees = (plan && s->rtab) || in_depth != s->in_depth || (yin_need > s->yin_cap && s->yin);
+    const size_t in_bytes = in.ring_bytes, yin_need = in.staging_bytes;
+    const bool regauged = c.in_depth != s->set.in_depth;   // the ring, and the field store with it, hold samples of another size
+    bool frees = (plan && s->rtab) || regauged || (yin_need > s->yin_cap && s->yin);
     for (int k = 0; k < pfnl::ROUTE_STAGES; ++k) {
         const size_t need = (size_t)s->batch * route.stage_bytes[k];   // (0 for a stage that does not run)
         if (need > s->slot[k].cap) fresh[k].cap = need;
@@ -563,8 +586,8 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
         ok = hipMalloc(reinterpret_cast<void**>(&tab), blob.size() * sizeof(int32_t)) == hipSuccess;
         ok = ok && hipMemcpy(tab, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (in_depth != s->in_depth) ok = ok && hipMalloc(reinterpret_cast<void**>(&ring), (size_t)s->cap * in_bytes) == hipSuccess;
-    if (in_depth != s->in_depth && s->fstore) ok = ok && hipMalloc(reinterpret_cast<void**>(&fstore), 3 * in_bytes) == hipSuccess;
+    if (regauged) ok = ok && hipMalloc(reinterpret_cast<void**>(&ring), (size_t)s->cap * in_bytes) == hipSuccess;
+    if (regauged && s->fstore) ok = ok && hipMalloc(reinterpret_cast<void**>(&fstore), 3 * in_bytes) == hipSuccess;
     if (yin_need > s->yin_cap) ok = ok && hipMalloc(reinterpret_cast<void**>(&yin), yin_need) == hipSuccess;
     for (StageSlot& t : fresh)
         for (int i = 0; i < 2 && t.cap; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&t.buf[i]), t.cap) == hipSuccess;
@@ -595,24 +618,16 @@ int apply_setting(pfnl_stream* s, int in_fmt, int out_fmt, const pfnl::YuvCoef& 
         (void)hipFree(s->fstore);
         s->fstore = fstore;
     }
-    s->in_depth = in_depth;
-    s->in_bytes = in_bytes;
     for (int k = 0; k < pfnl::ROUTE_STAGES; ++k)
         if (fresh[k].cap || !route.runs[k]) {
             drop_slot(s->slot[k]);
             s->slot[k] = fresh[k];
         }
-    s->in_fmt = in_fmt;
-    s->out_fmt = out_fmt;
-    s->in_chroma = in_chroma;
-    s->out_chroma = out_chroma;
-    s->in_pack = in_pack;
-    s->out_pack = out_pack;
-    s->coef = coef;
-    s->coef10 = coef10;
+    s->set = c;
     s->route = route;
+    s->in = in;
     // a tight v210 frame has zero bytes behind the samples of a row, and the kernel writes samples alone: the slot is cleared once, here
-    for (int i = 0; i < 2 && out_pack == PFNL_PACK_V210; ++i) HIPCHK(hipMemsetAsync(s->slot[2].buf[i], 0, s->slot[2].cap, s->s));
+    for (int i = 0; i < 2 && c.out_pack == PFNL_PACK_V210; ++i) HIPCHK(hipMemsetAsync(s->slot[2].buf[i], 0, s->slot[2].cap, s->s));
     return 0;
 }
 
@@ -651,7 +666,8 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
     s->scale = v.scale;
     s->device = v.device_id;
     s->s = hip_stream ? (hipStream_t)hip_stream : v.stream;
-    s->lr_bytes = s->in_bytes = (size_t)H * W * 3;
+    s->lr_bytes = (size_t)H * W * 3;
+    s->in = pfnl::in_route(s->set.in_fmt, s->set.in_depth, s->set.in_chroma, s->set.in_pack, H, W);   // planar RGB24: ring frames of lr_bytes
     s->sr_bytes = s->lr_bytes * v.scale * v.scale;
     // The ring keeps a batch's frames until the batch has been checked (it may have to be computed again): with two batches undelivered,
     // the oldest needed frame is launched - 2 batch - T/2, and pushes go on up to launched + batch + T/2 - 2 before the one that would
@@ -661,7 +677,7 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
     ok = ok && hipMalloc(reinterpret_cast<void**>(&s->ring), (size_t)s->cap * s->lr_bytes) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&s->win), (size_t)batch * s->T * s->lr_bytes * sizeof(float)) == hipSuccess;
     ok = ok && hipMalloc(reinterpret_cast<void**>(&s->sr), (size_t)batch * s->sr_bytes * sizeof(float)) == hipSuccess;
-    s->route = pfnl::out_route(s->out_fmt, v.scale * H, v.scale * W, 0, 0);   // RGB24 at the network's raster: stage 0 alone
+    s->route = pfnl::out_route(s->set.out_fmt, v.scale * H, v.scale * W, 0, 0);   // RGB24 at the network's raster: stage 0 alone
     s->slot[0].cap = (size_t)batch * s->route.stage_bytes[0];
     for (int i = 0; i < 2; ++i) {
         ok = ok && hipMalloc(reinterpret_cast<void**>(&s->slot[0].buf[i]), s->slot[0].cap) == hipSuccess;
@@ -679,77 +695,17 @@ int pfnl_stream_open(pfnl_handle* h, int H, int W, int batch, void* hip_stream, 
 
 int pfnl_stream_push(pfnl_stream* s, const uint8_t* frame, int is_device) {
     if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (s->in_depth == 10 && reinterpret_cast<uintptr_t>(frame) % 2) return fail(PFNL_ERR_INVALID, "push: uint16 samples are 2-byte aligned");
-    if (is_device && s->in_pack != PFNL_PACK_NONE && reinterpret_cast<uintptr_t>(frame) % pfnl::PACK_TABLE[s->in_pack].align)
+    if (s->set.in_depth == 10 && reinterpret_cast<uintptr_t>(frame) % 2) return fail(PFNL_ERR_INVALID, "push: uint16 samples are 2-byte aligned");
+    if (is_device && s->set.in_pack != PFNL_PACK_NONE && reinterpret_cast<uintptr_t>(frame) % pfnl::PACK_TABLE[s->set.in_pack].align)
         return fail(PFNL_ERR_INVALID, "push: a packed frame of 32-bit words (x2rgb10, x2bgr10, v210) is 4-byte aligned");
-    // the frame is H*W*3/2 samples (2 H W | 3 H W), or the tight frame of a packing, and reaches its slot through the kernel, as RGB
-    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || s->in_pack != PFNL_PACK_NONE;
-    const size_t yuv_bytes = yuv_frame_bytes(s, s->in_fmt, s->in_depth, s->in_chroma, s->in_pack);
-    if (s->il_mode) return push_woven(s, is_device, tight_surface(s, frame));
-    return push_frame(
-        s, is_device,
-        [&](uint8_t* dst) {
-            if (yuv_in)
-                return decode_packed(s, frame, dst, s->s);
-            HIPCHK(hipMemcpyAsync(dst, frame, s->in_bytes, hipMemcpyDeviceToDevice, s->s));
-            return 0;
-        },
-        [&](uint8_t* dst) {
-            if (yuv_in) {                             // (the staging frame is free again: every push ends with the copy stream idle)
-                HIPCHK(hipMemcpyAsync(s->yin, frame, yuv_bytes, hipMemcpyHostToDevice, s->cs));
-                return decode_packed(s, s->yin, dst, s->cs);
-            }
-            HIPCHK(hipMemcpyAsync(dst, frame, s->in_bytes, hipMemcpyHostToDevice, s->cs));
-            return 0;
-        });
+    // (no surface_refused: a host frame of an 8-bit packing may lie at any address, and the tight pitches are the route's own)
+    return push_surface(s, tight_surface(s, frame), is_device);
 }
 
 int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_device) {
     if (!s || !frame) return fail(PFNL_ERR_INVALID, "NULL argument");
-    const int fmt = pushed_format(s);                 // (2-byte samples at an input depth of 10)
-    if (const char* why = pfnl::surface_refused(frame, fmt, s->H, s->W, s->in_chroma, s->in_pack)) return fail(PFNL_ERR_INVALID, why);
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(fmt, s->H, s->W, s->in_chroma, s->in_pack);
-    const bool packed = s->in_pack != PFNL_PACK_NONE;
-    const bool yuv_in = s->in_fmt != PFNL_PIX_RGB24 || packed, nv12 = s->in_fmt == PFNL_PIX_NV12, sub420 = s->in_chroma == PFNL_CHROMA_420;
-    if (s->il_mode) return push_woven(s, is_device, *frame);
-    return push_frame(
-        s, is_device,
-        [&](uint8_t* dst) {                           // YUV and every packing: the kernel reads the surface where it lies
-            if (packed)
-                HIPCHK(pfnl::launch_packed_to_rgb(frame->plane[0], frame->pitch[0], 0, s->in_pack, dst, s->in_depth == 10 ? s->coef10 : s->coef, 1,
-                                                  s->H, s->W, s->in_siting, s->s));
-            else if (yuv_in && !sub420 && s->in_depth == 10)
-                HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(*frame, nv12), reinterpret_cast<uint16_t*>(dst), nv12,
-                                                             s->coef10, 1, s->H, s->W, s->in_chroma, s->in_siting, s->s));
-            else if (yuv_in && !sub420)
-                HIPCHK(pfnl::launch_yuv_planes_to_rgb_chroma(pfnl_internal_yuv_planes(*frame, nv12), dst, nv12, s->coef, 1, s->H, s->W,
-                                                             s->in_chroma, s->in_siting, s->s));
-            else if (yuv_in && s->in_depth == 10)
-                HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u10(pfnl_internal_yuv_planes(*frame, nv12), reinterpret_cast<uint16_t*>(dst), nv12,
-                                                             s->coef10, 1, s->H, s->W, s->in_siting, s->s));
-            else if (yuv_in)
-                HIPCHK(pfnl::launch_yuv420_planes_to_rgb_u8(pfnl_internal_yuv_planes(*frame, nv12), dst, nv12, s->coef, 1, s->H, s->W,
-                                                            s->in_siting, s->s));
-            else
-                HIPCHK(hipMemcpy2DAsync(dst, g.plane[0].row_bytes, frame->plane[0], frame->pitch[0], g.plane[0].row_bytes, g.plane[0].rows,
-                                        hipMemcpyDeviceToDevice, s->s));
-            return 0;
-        },
-        [&](uint8_t* dst) {                           // YUV: the planes packed into the staging frame, then the packed push's kernel
-            uint8_t* to = yuv_in ? s->yin : dst;
-            if (packed) {                             // (the rows at the tight frame's pitch: v210's is above its row bytes)
-                HIPCHK(hipMemcpy2DAsync(to, pfnl::pack_tight_pitch(s->in_pack, s->W), frame->plane[0], frame->pitch[0], g.plane[0].row_bytes,
-                                        g.plane[0].rows, hipMemcpyHostToDevice, s->cs));
-                return decode_packed(s, s->yin, dst, s->cs);
-            }
-            for (int k = 0; k < g.planes; ++k) {
-                HIPCHK(hipMemcpy2DAsync(to, g.plane[k].row_bytes, frame->plane[k], frame->pitch[k], g.plane[k].row_bytes, g.plane[k].rows,
-                                        hipMemcpyHostToDevice, s->cs));
-                to += g.plane[k].rows * g.plane[k].row_bytes;
-            }
-            if (yuv_in) return decode_packed(s, s->yin, dst, s->cs);
-            return 0;
-        });
+    if (const char* why = pfnl::surface_refused(frame, s->in.fmt, s->H, s->W, s->set.in_chroma, s->set.in_pack)) return fail(PFNL_ERR_INVALID, why);
+    return push_surface(s, *frame, is_device);
 }
 
 int pfnl_stream_end(pfnl_stream* s) {
@@ -786,12 +742,12 @@ int pfnl_stream_pop(pfnl_stream* s, uint8_t* out, int is_device, long long* inde
 
 int pfnl_stream_pop_surface(pfnl_stream* s, const pfnl_surface* out, int is_device, long long* index, int* got) {
     if (!s || !out || !index || !got) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (const char* why = pfnl::surface_refused(out, s->out_fmt, s->route.out_h, s->route.out_w, s->out_chroma, s->out_pack))
+    if (const char* why = pfnl::surface_refused(out, s->set.out_fmt, s->route.out_h, s->route.out_w, s->set.out_chroma, s->set.out_pack))
         return fail(PFNL_ERR_INVALID, why);
-    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->out_fmt, s->route.out_h, s->route.out_w, s->out_chroma, s->out_pack);
+    const pfnl::SurfaceGeom g = pfnl::surface_geom(s->set.out_fmt, s->route.out_h, s->route.out_w, s->set.out_chroma, s->set.out_pack);
     return pop_frame(s, is_device, index, got, [&](const uint8_t* src, size_t, hipStream_t on) {
-        if (s->out_pack != PFNL_PACK_NONE) {          // one plane; the slot's rows lie at the tight frame's pitch, and only a row's samples move
-            HIPCHK(hipMemcpy2DAsync(out->plane[0], out->pitch[0], src, pfnl::pack_tight_pitch(s->out_pack, s->route.out_w), g.plane[0].row_bytes,
+        if (s->set.out_pack != PFNL_PACK_NONE) {          // one plane; the slot's rows lie at the tight frame's pitch, and only a row's samples move
+            HIPCHK(hipMemcpy2DAsync(out->plane[0], out->pitch[0], src, pfnl::pack_tight_pitch(s->set.out_pack, s->route.out_w), g.plane[0].row_bytes,
                                     g.plane[0].rows, is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, on));
             return 0;
         }
@@ -860,43 +816,51 @@ int pfnl_stream_scenes(pfnl_stream* s, int mode, double threshold) {
     return 0;
 }
 
-// A packing in force holds its side to the family, depth, chroma format and width it was accepted with: 0 where the candidate the other
-// setters are about to apply agrees with both packings, else PFNL_ERR_INVALID with the table's words and the way out.
-static int packing_contradicted(const pfnl_stream* s, int in_fmt, int out_fmt, int in_depth, int in_chroma, int out_chroma, int out_w) {
-    const char* why = pfnl::pack_refused(s->in_pack, pfnl::is_yuv(in_fmt), in_depth, in_chroma, s->W);
-    if (!why) why = pfnl::pack_refused(s->out_pack, pfnl::is_yuv(out_fmt), pfnl::is_10bit(out_fmt) ? 10 : 8, out_chroma, out_w);
-    if (!why) return 0;
-    return fail(PFNL_ERR_INVALID, std::string(why) + " - the change contradicts a packing in force: set PFNL_PACK_NONE first (pfnl_stream_packing)");
+// The one check of a candidate against everything a setting must agree with, delivered at out_h x out_w: the route; both packings - a
+// packing in force holds its side to the family, depth, chroma format and width it was accepted with, and the answer names the way out -;
+// interlacing.  0, or PFNL_ERR_INVALID with the words of the first that refuses.  The stored setting has passed all of it, so a setter is
+// refused only for what it changes.
+static int candidate_refused(const pfnl_stream* s, const Setting& c, int out_h, int out_w) {
+    if (const char* why = pfnl::route_refused(c.in_fmt, c.out_fmt, out_h, out_w, c.out_chroma)) return fail(PFNL_ERR_INVALID, why);
+    const char* why = pfnl::pack_refused(c.in_pack, pfnl::is_yuv(c.in_fmt), c.in_depth, c.in_chroma, s->W);
+    if (!why) why = pfnl::pack_refused(c.out_pack, pfnl::is_yuv(c.out_fmt), pfnl::is_10bit(c.out_fmt) ? 10 : 8, c.out_chroma, out_w);
+    if (why) return fail(PFNL_ERR_INVALID, std::string(why) + " - the change contradicts a packing in force: set PFNL_PACK_NONE first (pfnl_stream_packing)");
+    if (const char* no = pfnl::interlace_refused(s->il_mode, s->il_order, s->H, pfnl::is_yuv(c.in_fmt), c.in_chroma, c.in_pack))
+        return fail(PFNL_ERR_INVALID, no);
+    return 0;
 }
 
+// The setters: bad arguments first (PFNL_ERR_INVALID at any time) - their own, then the stored setting with their fields changed before
+// candidate_refused -, then "before the first frame", then apply_setting.
+
 // The packing of the two edges.  The staging frame and stage 2's slot follow the row bytes, so it goes through apply_setting; each side is
-// checked against what is set at the call, and from then on the other setters hold that side to it (packing_contradicted).
+// checked against what is set at the call, in words that name the side, and from then on every setter holds that side to it.
 int pfnl_stream_packing(pfnl_stream* s, int in_pack, int out_pack) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     for (int v : {in_pack, out_pack})
         if (v != PFNL_PACK_NONE && !pfnl::is_packing(v)) return fail(PFNL_ERR_INVALID, "packing: PFNL_PACK_NONE .. PFNL_PACK_V210 on either side");
-    if (const char* why = pfnl::pack_refused(in_pack, pfnl::is_yuv(s->in_fmt), s->in_depth, s->in_chroma, s->W))
+    Setting c = s->set;
+    c.in_pack = in_pack;
+    c.out_pack = out_pack;
+    if (const char* why = pfnl::pack_refused(in_pack, pfnl::is_yuv(c.in_fmt), c.in_depth, c.in_chroma, s->W))
         return fail(PFNL_ERR_INVALID, std::string("input ") + why);
-    if (const char* why = pfnl::pack_refused(out_pack, pfnl::is_yuv(s->out_fmt), pfnl::is_10bit(s->out_fmt) ? 10 : 8, s->out_chroma, s->route.out_w))
+    if (const char* why = pfnl::pack_refused(out_pack, pfnl::is_yuv(c.out_fmt), pfnl::is_10bit(c.out_fmt) ? 10 : 8, c.out_chroma, s->route.out_w))
         return fail(PFNL_ERR_INVALID, std::string("output ") + why);
+    if (int e = candidate_refused(s, c, s->route.out_h, s->route.out_w)) return e;
     if (started(s)) return fail(PFNL_ERR_STATE, "the packing is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, s->in_depth, s->in_chroma, s->out_chroma, in_pack, out_pack,
-                         "packing staging allocation failed");
+    return apply_setting(s, c, nullptr, "packing staging allocation failed");
 }
 
-// The setters: bad arguments first (stream_route.h: PFNL_ERR_INVALID at any time), then "before the first frame", then apply_setting.
 int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int full_range) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (const char* why = pfnl::route_refused(in_fmt, out_fmt, s->route.out_h, s->route.out_w, s->out_chroma)) return fail(PFNL_ERR_INVALID, why);
-    if (int e = packing_contradicted(s, in_fmt, out_fmt, s->in_depth, s->in_chroma, s->out_chroma, s->route.out_w)) return e;
-    if (const char* why = pfnl::interlace_refused(s->il_mode, s->il_order, s->H, pfnl::is_yuv(in_fmt), s->in_chroma, s->in_pack))
-        return fail(PFNL_ERR_INVALID, why);
-    pfnl::YuvCoef coef, coef10;
-    if (!pfnl::yuv_coefficients(8, matrix, full_range, &coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &coef10))
+    Setting c = s->set;
+    c.in_fmt = in_fmt;
+    c.out_fmt = out_fmt;
+    if (int e = candidate_refused(s, c, s->route.out_h, s->route.out_w)) return e;
+    if (!pfnl::yuv_coefficients(8, matrix, full_range, &c.coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &c.coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
     if (started(s)) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, in_fmt, out_fmt, coef, coef10, nullptr, s->in_depth, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
-                         "format staging allocation failed");
+    return apply_setting(s, c, nullptr, "format staging allocation failed");
 }
 
 // The depth of the pushed samples: in_fmt keeps naming the layout.  At 10 the ring and the staging frame hold uint16 samples; decode, scene
@@ -904,10 +868,11 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
 int pfnl_stream_input_depth(pfnl_stream* s, int bits) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (bits != 8 && bits != 10) return fail(PFNL_ERR_INVALID, "input depth: 8 or 10 bits");
-    if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, bits, s->in_chroma, s->out_chroma, s->route.out_w)) return e;
+    Setting c = s->set;
+    c.in_depth = bits;
+    if (int e = candidate_refused(s, c, s->route.out_h, s->route.out_w)) return e;
     if (started(s)) return fail(PFNL_ERR_STATE, "the input depth is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, bits, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
-                         "input ring allocation failed");
+    return apply_setting(s, c, nullptr, "input ring allocation failed");
 }
 
 // The subsampling of the two YUV edges: in_fmt / out_fmt keep naming the layout.  The staging frame and stage 2's slot follow it, so it goes
@@ -916,27 +881,26 @@ int pfnl_stream_chroma_format(pfnl_stream* s, int in_chroma, int out_chroma) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (!pfnl::is_chroma(in_chroma) || !pfnl::is_chroma(out_chroma))
         return fail(PFNL_ERR_INVALID, "chroma format: PFNL_CHROMA_420, PFNL_CHROMA_422 or PFNL_CHROMA_444 on either side");
-    if (const char* why = pfnl::route_refused(s->in_fmt, s->out_fmt, s->route.out_h, s->route.out_w, out_chroma)) return fail(PFNL_ERR_INVALID, why);
-    if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, s->in_depth, in_chroma, out_chroma, s->route.out_w)) return e;
-    if (const char* why = pfnl::interlace_refused(s->il_mode, s->il_order, s->H, pfnl::is_yuv(s->in_fmt), in_chroma, s->in_pack))
-        return fail(PFNL_ERR_INVALID, why);
+    Setting c = s->set;
+    c.in_chroma = in_chroma;
+    c.out_chroma = out_chroma;
+    if (int e = candidate_refused(s, c, s->route.out_h, s->route.out_w)) return e;
     if (started(s)) return fail(PFNL_ERR_STATE, "the chroma format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, nullptr, s->in_depth, in_chroma, out_chroma, s->in_pack, s->out_pack,
-                         "chroma format staging allocation failed");
+    return apply_setting(s, c, nullptr, "chroma format staging allocation failed");
 }
 
 // Interlaced input: pushed frames are woven, the ring receives progressive frames (field_geom.h; deinterlace.hip).  The field store is
 // allocated by the first call that turns it on, at the input depth (apply_setting makes it follow a later change of depth).
 int pfnl_stream_interlace(pfnl_stream* s, int mode, int field_order) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (const char* why = pfnl::interlace_refused(mode, field_order, s->H, pfnl::is_yuv(s->in_fmt), s->in_chroma, s->in_pack))
+    if (const char* why = pfnl::interlace_refused(mode, field_order, s->H, pfnl::is_yuv(s->set.in_fmt), s->set.in_chroma, s->set.in_pack))
         return fail(PFNL_ERR_INVALID, why);
     if (started(s)) return fail(PFNL_ERR_STATE, "interlacing is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     if (mode && !s->fstore) {
         HIPCHK(hipSetDevice(s->device));
         uint8_t* store = nullptr;
         hipEvent_t ev = nullptr;
-        bool ok = hipMalloc(reinterpret_cast<void**>(&store), 3 * s->in_bytes) == hipSuccess;
+        bool ok = hipMalloc(reinterpret_cast<void**>(&store), 3 * s->in.ring_bytes) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
         if (!ok) {
             (void)hipGetLastError();
@@ -971,13 +935,10 @@ int pfnl_stream_place(pfnl_stream* s, int out_H, int out_W, const pfnl_rect* src
     std::string why;
     if (!out_H && !out_W && (src || dst || fill_rgb)) return fail(PFNL_ERR_INVALID, "place: src, dst and a fill colour need a canvas size (0, 0 is off)");
     if ((out_H || out_W) && !pfnl::place_plan(sH, sW, out_H, out_W, src, dst, &plan, &why)) return fail(PFNL_ERR_INVALID, why);
-    if (const char* no = pfnl::route_refused(s->in_fmt, s->out_fmt, plan.cH ? plan.cH : sH, plan.cW ? plan.cW : sW, s->out_chroma))
-        return fail(PFNL_ERR_INVALID, no);
-    if (int e = packing_contradicted(s, s->in_fmt, s->out_fmt, s->in_depth, s->in_chroma, s->out_chroma, plan.cW ? plan.cW : sW)) return e;
+    if (int e = candidate_refused(s, s->set, plan.cH ? plan.cH : sH, plan.cW ? plan.cW : sW)) return e;   // (the setting stays: the size changes)
     if (started(s)) return fail(PFNL_ERR_STATE, "the output size is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     for (int k = 0; k < 3 && fill_rgb; ++k) plan.fill[k] = fill_rgb[k];
-    return apply_setting(s, s->in_fmt, s->out_fmt, s->coef, s->coef10, &plan, s->in_depth, s->in_chroma, s->out_chroma, s->in_pack, s->out_pack,
-                         "resize allocation failed");
+    return apply_setting(s, s->set, &plan, "resize allocation failed");
 }
 
 int pfnl_stream_resize(pfnl_stream* s, int out_H, int out_W) { return pfnl_stream_place(s, out_H, out_W, nullptr, nullptr, nullptr); }

@@ -1,8 +1,11 @@
-// THE OUTPUT ROUTE OF A STREAMING SESSION (include/pfnl_hip.h pfnl_stream_format / pfnl_stream_resize): what a batch goes through between
-// the fp32 result and pop - stage 0 quantise -> stage 1 resize (or a placement on a canvas: pfnl_stream_place) -> stage 2 RGB -> YUV at the
-// session's output subsampling (pfnl_stream_chroma_format; 4:2:0 unless it says otherwise), at 1 or 2 bytes per sample -, the bytes of a frame behind each stage, which stage pop reads, the one check of a (formats, size) setting that
-// needs no session, and the one check of a placement's rectangles.  No HIP types and no HIP runtime calls: a plain C++ program can include
-// this file and walk the rule (tests/test_route_host.py and tests/test_place_host.py do).
+// THE TWO ROUTES OF A STREAMING SESSION.  The output route (include/pfnl_hip.h pfnl_stream_format / pfnl_stream_resize): what a batch goes
+// through between the fp32 result and pop - stage 0 quantise -> stage 1 resize (or a placement on a canvas: pfnl_stream_place) -> stage 2
+// RGB -> YUV at the session's output subsampling (pfnl_stream_chroma_format; 4:2:0 unless it says otherwise), at 1 or 2 bytes per sample -,
+// the bytes of a frame behind each stage, which stage pop reads, the one check of a (formats, size) setting that needs no session, and the
+// one check of a placement's rectangles.  The input route (pfnl_stream_format / _input_depth / _chroma_format / _packing): what a pushed
+// frame is - its surface format and geometry, the pitches and bytes of the tight frame, the staging frame a host push needs, the ring
+// frame - and which decode takes it into its ring slot.  No HIP types and no HIP runtime calls: a plain C++ program can include this file
+// and walk the rules (tests/test_route_host.py, tests/test_input_route_host.py and tests/test_place_host.py do).
 #pragma once
 #include "surface_geom.h"
 
@@ -48,6 +51,46 @@ inline OutRoute out_route(int out_fmt, int sH, int sW, int oH, int oW, int chrom
         if (r.runs[k]) r.last = k, r.stage_bytes[k] = packed_bytes(writes[k]);
     if (pack != PFNL_PACK_NONE) r.stage_bytes[2] = pack_frame_bytes(pack, r.out_h, r.out_w);
     r.frame_bytes = r.stage_bytes[r.last];
+    return r;
+}
+
+// THE INPUT ROUTE: a frame of H x W as it is pushed under (in_fmt, in_depth, in_chroma, in_pack) and the decode that makes it a ring frame.
+enum InDecode {
+    IN_DECODE_NONE = 0,   // no such setting: surface_geom or pack_refused refuses it, and every size is 0
+    IN_DECODE_COPY,       // planar RGB: the ring's own layout
+    IN_DECODE_420,        // NV12 / I420 (P010 / I010) at 4:2:0: yuv.hip
+    IN_DECODE_CHROMA,     // the same layouts at 4:2:2 / 4:4:4: yuv_chroma.hip
+    IN_DECODE_PACK,       // one plane of interleaved samples: packed.hip
+};
+
+struct InRoute {
+    int kind;             // InDecode
+    int fmt;              // the pushed surface's format: in_fmt names the layout, the depth the sample (RGB10 / P010 / I010 at 10 bits)
+    SurfaceGeom geom;     // ... and its planes (surface_geom)
+    size_t pitch[3];      // the pitch of each plane in a tight frame: its row bytes; a packing's pack_tight_pitch (v210's is above them)
+    size_t frame_bytes;   // the tight frame: its planes one behind the other at those pitches
+    size_t staging_bytes; // what a host push stages on the device ahead of the decode: the tight frame; 0 for planar RGB, copied as it is
+    size_t ring_bytes;    // the frame as the ring holds it: H W 3 samples
+    int sample_bytes;     // 1, or 2 at a depth of 10
+};
+
+inline InRoute in_route(int in_fmt, int in_depth, int in_chroma, int in_pack, int H, int W) {
+    InRoute r{};
+    if (in_fmt < PFNL_PIX_RGB24 || in_fmt > PFNL_PIX_I420 || (in_depth != 8 && in_depth != 10)) return r;
+    const int fmt = in_depth != 10 ? in_fmt : (in_fmt == PFNL_PIX_NV12 ? PFNL_PIX_P010 : (in_fmt == PFNL_PIX_I420 ? PFNL_PIX_I010 : PFNL_PIX_RGB10));
+    const SurfaceGeom g = surface_geom(fmt, H, W, in_chroma, in_pack);
+    if (!g.planes) return r;
+    const bool packed = in_pack != PFNL_PACK_NONE;
+    r.fmt = fmt;
+    r.geom = g;
+    r.sample_bytes = g.sample_bytes;
+    for (int k = 0; k < g.planes; ++k) {
+        r.pitch[k] = packed ? pack_tight_pitch(in_pack, W) : g.plane[k].row_bytes;
+        r.frame_bytes += g.plane[k].rows * r.pitch[k];
+    }
+    r.kind = packed ? IN_DECODE_PACK : (in_fmt == PFNL_PIX_RGB24 ? IN_DECODE_COPY : (in_chroma == PFNL_CHROMA_420 ? IN_DECODE_420 : IN_DECODE_CHROMA));
+    r.staging_bytes = r.kind == IN_DECODE_COPY ? 0 : r.frame_bytes;
+    r.ring_bytes = (size_t)H * W * 3 * g.sample_bytes;
     return r;
 }
 
