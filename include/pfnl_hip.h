@@ -16,7 +16,11 @@
  * Conventions: every entry point is extern "C", takes plain pointers and sizes, returns 0 on
  * success or a negative pfnl_status; the message of the last failure on the calling thread is
  * available from pfnl_last_error().  A handle is bound to one device and is not re-entrant;
- * distinct handles are independent.  "device pointer" = memory accessible from that device
+ * distinct handles are independent, from distinct host threads too (tests/test_gpu_threads.py), with one
+ * exception that is the HIP runtime's: while a handle captures a graph (option graph = on / auto, inside
+ * pfnl_forward), a BLOCKING copy made by the caller on another thread (hipMemcpy, hipMemcpyToSymbol) fails
+ * with hipErrorStreamCaptureImplicit and invalidates the capture: that pfnl_forward returns PFNL_ERR_HIP.
+ * The library's own blocking copies wait for a capture to end (one process-wide lock).  "device pointer" = memory accessible from that device
  * (e.g. a torch-ROCm tensor's data_ptr()); "stream" = a hipStream_t passed as void* (NULL: see
  * STREAMS below).  All tensors are float32 (the *_bf16 single-op hooks alone take bfloat16 bit patterns as
  * uint16_t), contiguous, NHWC-style as in the reference:

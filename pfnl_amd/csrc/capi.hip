@@ -39,14 +39,17 @@ int pfnl_internal_fail(int code, const std::string& msg) { return fail(code, msg
 
 namespace {
 
-static unsigned long long g_alloc_gen = 0;   // bumped whenever a device buffer moves: captured graphs hold raw pointers
+// bumped whenever a device buffer moves: captured graphs hold raw pointers.  Process-wide (DESIGN.md "What handles share"): every handle's
+// DevBuf::ensure bumps it and every handle's graph check reads it, from whatever host thread drives that handle - relaxed is enough, the
+// counter orders nothing: a handle only needs to see its OWN bumps, and those it made on its own thread
+static std::atomic<unsigned long long> g_alloc_gen{0};
 
 struct DevBuf {
     float* p = nullptr;
     size_t n = 0;   // floats
     int ensure(size_t count) {
         if (count <= n) return 0;
-        ++g_alloc_gen;
+        g_alloc_gen.fetch_add(1, std::memory_order_relaxed);
         if (p) hipFree(p);
         p = nullptr;
         n = 0;
@@ -1129,7 +1132,7 @@ int pfnl_finalize_weights(pfnl_handle* h) {
         b16.resize((b16.size() + 1) / 2 * 2 + 2, 0);
         h->wdev16_used = b16.size() / 2;
         if (h->wdev16.ensure(b16.size() / 2)) return fail(PFNL_ERR_NOMEM, "weight allocation failed");
-        HIPCHK(hipMemcpy(h->wdev16.p, b16.data(), b16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        { pfnl::BlockingCopyGuard guard; HIPCHK(hipMemcpy(h->wdev16.p, b16.data(), b16.size() * sizeof(uint16_t), hipMemcpyHostToDevice)); }
     }
     {   // split-f16 packs of the 3x3 64->64 kernels (conv3x3=split16)
         std::vector<uint16_t> b16;
@@ -1175,7 +1178,7 @@ int pfnl_finalize_weights(pfnl_handle* h) {
         }
         h->wdev16s_used = b16.size() / 2;
         if (h->wdev16s.ensure(b16.size() / 2)) return fail(PFNL_ERR_NOMEM, "weight allocation failed");
-        HIPCHK(hipMemcpy(h->wdev16s.p, b16.data(), b16.size() / 2 * 2 * sizeof(uint16_t), hipMemcpyHostToDevice));
+        { pfnl::BlockingCopyGuard guard; HIPCHK(hipMemcpy(h->wdev16s.p, b16.data(), b16.size() / 2 * 2 * sizeof(uint16_t), hipMemcpyHostToDevice)); }
     }
     {   // the f16-pipe kernels split the weights into binary16 pairs: a weight beyond that range sends the handle to the f32-MFMA kernels
         float wmax = 0.f;
@@ -1185,7 +1188,7 @@ int pfnl_finalize_weights(pfnl_handle* h) {
     }
     h->wdev_used = blob.size();
     if (h->wdev.ensure(blob.size())) return fail(PFNL_ERR_NOMEM, "weight allocation failed");
-    HIPCHK(hipMemcpy(h->wdev.p, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    { pfnl::BlockingCopyGuard guard; HIPCHK(hipMemcpy(h->wdev.p, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice)); }
     h->finalized = true;
     ++h->cfg_gen;
     return 0;
@@ -1384,7 +1387,7 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
             h->graphs.push_back({B, H, W, 0, nullptr, nullptr, 0, 0, h->cfg_gen, slot});
             ge = &h->graphs.back();
         }
-        if (ge->exec && (ge->alloc_gen != g_alloc_gen || ge->cfg_gen != h->cfg_gen)) {   // buffers moved / weights or options changed
+        if (ge->exec && (ge->alloc_gen != g_alloc_gen.load(std::memory_order_relaxed) || ge->cfg_gen != h->cfg_gen)) {   // buffers moved / weights or options changed
             // a replay of this graph may still be running on the stream (an asynchronous device-pointer call followed by pfnl_set_option):
             // whether the runtime defers the destruction of an executing graph depends on its version - wait for it
             HIPCHK(hipStreamSynchronize(s));
@@ -1400,10 +1403,16 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
         }
         if (!ge->exec && ge->seen >= 1) {
             // second call with this shape (the first one ran eagerly: workspaces allocated, kernel attributes set)
-            HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int fe = forward_device(h, h->stage_in.p, h->stage_out.p, B, H, W, s, nullptr, 0, -1, slot);
+            // (no other thread's blocking copy while the capture is open - it would fail and invalidate the capture: common.h CaptureGuard)
+            int fe = 0;
             hipGraph_t g = nullptr;
-            const hipError_t ce = hipStreamEndCapture(s, &g);
+            hipError_t ce = hipSuccess;
+            {
+                pfnl::CaptureGuard guard;
+                HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+                fe = forward_device(h, h->stage_in.p, h->stage_out.p, B, H, W, s, nullptr, 0, -1, slot);
+                ce = hipStreamEndCapture(s, &g);
+            }
             if (fe) return fe;
             if (ce != hipSuccess || !g) return fail(PFNL_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(ce));
             hipGraphExec_t ex = nullptr;
@@ -1414,7 +1423,7 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
             }
             ge->graph = g;
             ge->exec = ex;
-            ge->alloc_gen = g_alloc_gen;
+            ge->alloc_gen = g_alloc_gen.load(std::memory_order_relaxed);
             ge->cfg_gen = h->cfg_gen;
         }
         if (ge->exec) {
@@ -1783,6 +1792,7 @@ int pfnl_copy_weights(pfnl_handle* dst, pfnl_handle* src) {
     if (dst->wdev_used != src->wdev_used || dst->wdev16_used != src->wdev16_used || dst->wdev16s_used != src->wdev16s_used)
         return fail(PFNL_ERR_STATE, "the handles differ in geometry (weight blob sizes)");
     HIPCHK(hipSetDevice(dst->cfg.device_id));
+    pfnl::BlockingCopyGuard guard;
     HIPCHK(hipMemcpy(dst->wdev.p, src->wdev.p, src->wdev_used * sizeof(float), hipMemcpyDefault));
     HIPCHK(hipMemcpy(dst->wdev16.p, src->wdev16.p, src->wdev16_used * sizeof(float), hipMemcpyDefault));
     HIPCHK(hipMemcpy(dst->wdev16s.p, src->wdev16s.p, src->wdev16s_used * sizeof(float), hipMemcpyDefault));
@@ -1855,6 +1865,7 @@ int pfnl_debug_tap(pfnl_handle* h, const char* name, float* host_dst, size_t cou
     if (!h || !name || !host_dst) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (!h->lastB) return fail(PFNL_ERR_STATE, "no forward has run");
     HIPCHK(hipSetDevice(h->cfg.device_id));
+    pfnl::BlockingCopyGuard guard;                                 // (the device-wide wait and the blocking copies below)
     HIPCHK(hipDeviceSynchronize());
     const int B = h->lastB, H = h->lastH, W = h->lastW, T = h->cfg.num_frames;
     const std::string n(name);

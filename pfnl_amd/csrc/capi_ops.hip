@@ -46,7 +46,10 @@ class OpStage {
     template <class T>
     T* upload(const std::vector<T>& pack, size_t extra = 0) {
         T* d = alloc<T>(pack.size() + extra);
-        if (d) e = hipMemcpy(d, pack.data(), pack.size() * sizeof(T), hipMemcpyHostToDevice);
+        if (d) {
+            pfnl::BlockingCopyGuard guard;                                       // (never beside another handle's graph capture: common.h)
+            e = hipMemcpy(d, pack.data(), pack.size() * sizeof(T), hipMemcpyHostToDevice);
+        }
         return ok() ? d : nullptr;
     }
 

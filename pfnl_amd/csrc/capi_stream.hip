@@ -584,6 +584,7 @@ int apply_setting(pfnl_stream* s, const Setting& c, pfnl::PlacePlan* plan, const
     if (plan && plan->cH) {
         const std::vector<int32_t>& blob = plan->r.blob;
         ok = hipMalloc(reinterpret_cast<void**>(&tab), blob.size() * sizeof(int32_t)) == hipSuccess;
+        pfnl::BlockingCopyGuard guard;                                           // (never beside another handle's graph capture: common.h)
         ok = ok && hipMemcpy(tab, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
     }
     if (regauged) ok = ok && hipMalloc(reinterpret_cast<void**>(&ring), (size_t)s->cap * in_bytes) == hipSuccess;

@@ -5,6 +5,8 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <mutex>
+#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -53,6 +55,24 @@ inline int device_cu_count() {                                      // CUs of th
     }
     return n;
 }
+
+// Graph capture against blocking copies, process-wide (DESIGN.md "What handles share").  Measured on HIP 7.2: while ANY host thread
+// holds a stream capture open - hipStreamCaptureModeThreadLocal, on a blocking or on a non-blocking stream alike - another thread's
+// hipMemcpy / hipMemcpyToSymbol returns hipErrorStreamCaptureImplicit AND invalidates that capture (hipStreamEndCapture:
+// hipErrorStreamCaptureInvalidated).  Launches, asynchronous copies on a stream, hipMalloc / hipFree, hipHostMalloc and
+// hipStreamSynchronize(NULL) are accepted.  So pfnl_forward captures under CaptureGuard (exclusive) and every blocking copy of the
+// library is made under BlockingCopyGuard (shared): the two never overlap, whatever handles and threads they belong to.  Nothing on a
+// forward's path takes either lock unless it captures (graph=on / auto).  Not recursive: no blocking copy inside a capture.
+inline std::shared_mutex& capture_mutex() {
+    static std::shared_mutex m;
+    return m;
+}
+struct CaptureGuard {
+    std::unique_lock<std::shared_mutex> lk{capture_mutex()};
+};
+struct BlockingCopyGuard {
+    std::shared_lock<std::shared_mutex> lk{capture_mutex()};
+};
 
 __device__ __forceinline__ float lrelu(float v) { return fmaxf(v, 0.2f * v); }  // tf.nn.leaky_relu
 

@@ -562,7 +562,10 @@ hipError_t launch_blur_decimate(const float* hr, float* lr, int F, int H, int W,
         float w[169];
         for (int a = 0; a < 13; ++a)
             for (int b = 0; b < 13; ++b) w[a * 13 + b] = (float)((k[a] / sum) * (k[b] / sum));
-        e = hipMemcpyToSymbol(HIP_SYMBOL(c_blur), w, sizeof(w));
+        {
+            BlockingCopyGuard guard;                                // (never beside another handle's graph capture: common.h)
+            e = hipMemcpyToSymbol(HIP_SYMBOL(c_blur), w, sizeof(w));
+        }
         if (e != hipSuccess) return e;
         init[dev] = 1;
     }
@@ -598,6 +601,7 @@ hipError_t run_mfma_selftest(int* mismatches) {
     int* d = nullptr;
     hipError_t e = hipMalloc(&d, sizeof(int));
     if (e != hipSuccess) return e;
+    BlockingCopyGuard guard;                                        // (the blocking memset and copy: common.h)
     hipMemset(d, 0, sizeof(int));
     hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, 0, d);
     e = hipMemcpy(mismatches, d, sizeof(int), hipMemcpyDeviceToHost);

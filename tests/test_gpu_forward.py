@@ -1111,7 +1111,8 @@ def test_pinned_output_pool(monkeypatch):
     eng = PFNLEngine(geom, device=0)
     eng.load_weights(synth.synthetic_weights(geom, seed=0))
     x = synth.uniform_clips(2, 7, 64, 96, seed=8)                   # 2.4 MB out: above the 512 KB threshold
-    y1 = eng.forward(x)
+    gc.collect()                                                    # results of this size that earlier tests left in reference cycles go back
+    y1 = eng.forward(x)                                             # to the pool NOW, not on top of y1's block in the collection below
     want = y1.copy()
     p1 = y1.ctypes.data
     del y1
