@@ -601,11 +601,69 @@ int pfnl_stream_packing(pfnl_stream* s, int in_pack, int out_pack);
  *     it.  pfnl_stream_reset forgets the field store's contents and a pending mark.  The deinterlacer itself reads no marks: across a cut
  *     the rule's own clamp widens (t0 and t1 are large) and the made rows are the field's own cubic.
  * The op hooks pfnl_op_deinterlace_u8 / _u10 below are the kernel on its own.
- * Out of scope: edge-directed interpolation, inverse telecine and mixed streams, interlaced output, the interlaced 4:2:0 siting offset,
- * marks read by the deinterlacer, 12 and 16 bits. */
+ * Out of scope: edge-directed interpolation, interlaced output, the interlaced 4:2:0 siting offset, marks read by the deinterlacer, 12 and
+ * 16 bits.  (Film carried in fields - 3:2 pulldown - and streams that mix it with video: TELECINE below.) */
 enum { PFNL_INTERLACE_OFF = 0, PFNL_INTERLACE_FRAME = 1, PFNL_INTERLACE_FIELD = 2 };
 enum { PFNL_FIELD_TFF = 0, PFNL_FIELD_BFF = 1 };
 int pfnl_stream_interlace(pfnl_stream* s, int mode, int field_order);
+/* TELECINE (additions to version 4; a session that does not call pfnl_stream_telecine, or sets PFNL_TELECINE_OFF, issues the launches it
+ * always issued).  Film carried at 29.97 frames a second is not interlaced video: it is 24 progressive frames a second spread over fields
+ * by 3:2 pulldown, so two of every five pushed frames are woven from two different film frames and one picture in five is a repeat.  The
+ * deinterlacer would interpolate half the rows of those frames and keep the repeat; the film frames are all in the stream, intact as field
+ * pairs.  With this setting on, pushed frames are re-paired field by field ahead of the ring and, in mode DECIMATE, one frame in five is
+ * dropped.  The rule is stated once on the host, pfnl_amd/telecine.py, in INTERLACED's vocabulary (fields k = 0 .. 2 N - 1 in time order
+ * under field_order, the replacement at the ends, samples min(v, MAX), no horizontal term); its index rules once in
+ * pfnl_amd/csrc/telecine_geom.h:
+ *   matching: for pushed frame n the kept field is A = field 2 n, of parity p; its partner is field 2 n + 1 (candidate c: the frame as
+ *     pushed) or field 2 n - 1 (candidate p; replaced at n = 0, where it becomes field 1 and c = p).  A film frame covers two or three
+ *     consecutive fields, so one of the two always belongs to A's film frame, in every phase and either field order.
+ *   the comb count of a candidate X: over every missing row j = 0 .. h - 1 (h = H / 2), u = j - p, field rows clamped to [0, h - 1], and
+ *     every sample of the row: a = X[j] - A[u], b = X[j] - A[u + 1]; the sample is combed iff a b > T^2 - it lies on one side of both
+ *     vertical neighbours by more than T; T = threshold at 8 bits, 4 threshold at 10.  An exact integer, at most h 3 W.
+ *   the choice: the smaller count, c on a tie; the matched frame m_n is the weave of A and the chosen partner.  With post on, a frame whose
+ *     smaller count exceeds comb_limit is video: m_n is then INTERLACED's frame at the time of field 2 n, byte for byte.
+ *   pfnl_telecine_params: threshold (1 .. 255; default 10), post (0 | 1; default 1), comb_limit (default, and any negative value:
+ *     (h 3 W) >> 8).  Parameters of the rule - chosen, not measured.
+ *   decimation (PFNL_TELECINE_DECIMATE): D_n = sum |m_n - m_(n-1)| over all samples, D_0 the largest uint64.  Frames 5 q .. 5 q + 4, counted
+ *     from the start of the sequence or the last reset, are cycle q; of a complete cycle the frame with the smallest D is dropped (the
+ *     lowest index on a tie) and four are delivered in order; pfnl_stream_end delivers an incomplete last cycle whole.
+ *     PFNL_TELECINE_MATCH delivers every m_n.
+ *   pfnl_stream_telecine: a setting beside pfnl_stream_interlace and exclusive with it - whichever of the two is turned on while the other
+ *     is on returns PFNL_ERR_INVALID.  Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); it
+ *     survives pfnl_stream_reset.  Unknown values, odd H, 4:2:0 planes with H % 4 != 0 (checked by whichever of this call,
+ *     pfnl_stream_format and pfnl_stream_chroma_format comes second) and, in mode DECIMATE, a ring that can never hold the four frames a
+ *     cycle completes are PFNL_ERR_INVALID.  The first call that turns it on allocates INTERLACED's field store and, beside it, the five
+ *     matched frames of a cycle, the device words of the decision and a pinned host copy of a cycle's D; PFNL_ERR_NOMEM leaves nothing
+ *     half-made and the setting unchanged.
+ *   latency: m_n exists once frame n + 1 has been pushed, or at pfnl_stream_end - INTERLACED's one frame, which post needs.  Per matched
+ *     frame: the match launch, INTERLACED's launch into the frame's place (post on: the weave leaves it alone where the decision flags the
+ *     frame), the weave launch, which reads the decision from device memory and in mode DECIMATE sums D_n in the same pass
+ *     (pfnl_amd/csrc/telecine.hip).  No host round trip sits between the counts and the weave.  Mode MATCH writes m_n straight into its
+ *     ring slot.  Mode DECIMATE keeps a cycle's matched frames beside the ring and admits its four kept frames together when the
+ *     cycle's last matched frame exists: THE HOST WAITS ONCE PER CYCLE, and never per frame, for a pinned copy of the cycle's five D - on
+ *     the session's stream for a device-pointer push, on the copy stream for a host-pointer push -, as it must know the drop index to place
+ *     marks and to count pops.  A device-pointer push decodes the caller's frame on the session's stream, behind whatever is queued there,
+ *     and the D follow from that frame: this wait therefore also waits for the forwards in flight on that stream, once in five pushes,
+ *     where a host-pointer push waits for its own copy stream as every host-pointer push does.  Every push path INTERLACED takes is taken.
+ *   the bound: INTERLACED's, applied to everything a push completes - up to four ring frames at the end of a cycle.  A refused push or
+ *     pfnl_stream_end ("pop first", PFNL_ERR_STATE) changes nothing.
+ *   cuts: the mark of pfnl_stream_mark_cut travels with its pushed frame and lands on the first delivered frame made from it, or from a
+ *     later frame where its own is dropped.  Cycles do not restart at marks: the rate stays 4 / 5 throughout.
+ *   pfnl_stream_telecine_stats: out[5] = frames matched c, matched p, post-processed (counted there and under neither match), dropped,
+ *     and admitted to the ring, of the current sequence; it waits for the session's two streams.
+ *   pfnl_telecine_deliverable: the ring frames a session in `mode` has made of `pushed` pushed frames; needs no device.
+ * The op hooks pfnl_op_fieldmatch_* / pfnl_op_telecine_frame_* below are the kernels on their own.
+ * Out of scope: soft-telecine flags (RFF: a demuxer's matter), cadences other than 3:2 (they pass through MATCH; DECIMATE drops one frame
+ * in five whatever the cadence), interlaced output, the interlaced 4:2:0 siting offset. */
+enum { PFNL_TELECINE_OFF = 0, PFNL_TELECINE_MATCH = 1, PFNL_TELECINE_DECIMATE = 2 };
+typedef struct pfnl_telecine_params {
+    int threshold;
+    int post;
+    long long comb_limit;
+} pfnl_telecine_params;
+int pfnl_stream_telecine(pfnl_stream* s, int mode, int field_order, const pfnl_telecine_params* params /* NULL: the defaults */);
+int pfnl_stream_telecine_stats(pfnl_stream* s, long long out[5]);
+int pfnl_telecine_deliverable(int mode, long long pushed, int ended, long long* frames);
 /* SELF-ENSEMBLE in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With
  * n in {2, 4, 8} the one forward of every batch is pfnl_forward_ensemble(..., n, ...) (SELF-ENSEMBLE above); gather, quantisation, the
  * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  n = 1 is
@@ -1003,6 +1061,24 @@ int pfnl_op_deinterlace_u10(const uint16_t* p2, const uint16_t* p1, const uint16
  * ONE launch.  The same refusals (the message names fields[i]). */
 int pfnl_op_deinterlace_pair_u8(const uint8_t* const fields[6], int H, int W, int parity, uint8_t* out, void* stream);
 int pfnl_op_deinterlace_pair_u10(const uint16_t* const fields[6], int H, int W, int parity, uint16_t* out, void* stream);
+/* The kernels of TELECINE on their own.  A, Xc, Xp: the kept field of parity `parity` and its two candidate partners, tight [h][W][3]
+ * samples each (read-only; they may be one another); uint8, or uint16 whose samples are taken as min(v, 1023) (_u10).  Device pointers,
+ * any alignment a sample can have.  pfnl_op_fieldmatch_*: counts_dev[2] (8-byte aligned) = the comb counts of c and p; the hook owns its
+ * scratch words and is complete on return.  pfnl_op_telecine_frame_*: the two launches a session issues per matched frame, asynchronous
+ * on `stream` - counts, decision and weave: decision_dev[6] (8-byte aligned) = count of c, count of p, match (0: c, 1: p), post (0 | 1)
+ * and two scratch words the caller zeroes before the first call and every call leaves zero (calls that share them must not overlap), and
+ * out [2 h][W][3] the matched frame, which overlaps none of A, Xc, Xp (PFNL_ERR_INVALID).  With post != 0 the caller has put INTERLACED's
+ * frame into `out`, and a flagged frame leaves it as it is - every byte of `out` unwritten.  params == NULL IS THE DEFAULTS, post = 1
+ * among them: a caller who has no deinterlaced frame to offer passes params with post = 0, and the weave then always writes the frame.  comb_limit < 0: the default.  A NULL pointer, h < 1, W < 1, h 3 W >= 2^32, a parity other than 0 or 1,
+ * a threshold outside 1 .. 255: PFNL_ERR_INVALID before any HIP call, with a message that names the argument. */
+int pfnl_op_fieldmatch_u8(const uint8_t* A, const uint8_t* Xc, const uint8_t* Xp, int h, int W, int parity, int threshold,
+                          unsigned long long* counts_dev, void* stream);
+int pfnl_op_fieldmatch_u10(const uint16_t* A, const uint16_t* Xc, const uint16_t* Xp, int h, int W, int parity, int threshold,
+                           unsigned long long* counts_dev, void* stream);
+int pfnl_op_telecine_frame_u8(const uint8_t* A, const uint8_t* Xc, const uint8_t* Xp, int h, int W, int parity, const pfnl_telecine_params* params,
+                              uint8_t* out, unsigned long long* decision_dev, void* stream);
+int pfnl_op_telecine_frame_u10(const uint16_t* A, const uint16_t* Xc, const uint16_t* Xp, int h, int W, int parity,
+                               const pfnl_telecine_params* params, uint16_t* out, unsigned long long* decision_dev, void* stream);
 /* Quality scores of the harness' uint8 frames on the device (what the reference leaves to matlab/compute_psnr.m, matlab/SSIM.m and
  * utils.py:213-246 AVG_PSNR after the PNGs are written): pred, truth [F,H,W,3] uint8 (device), per frame in one pass over the bytes
  *   Y = 16 + 0.256788235294118 R + 0.504129411764706 G + 0.097905882352941 B            (utils.py:194-211 _rgb2ycbcr, fp64),

@@ -46,6 +46,11 @@ class pfnl_tiling(C.Structure):
     _fields_ = [("tile_h", C.c_int32), ("tile_w", C.c_int32), ("pad", C.c_int32), ("batch", C.c_int32)]
 
 
+class pfnl_telecine_params(C.Structure):
+    """The parameters of inverse telecine (include/pfnl_hip.h TELECINE; pfnl_amd/telecine.py); comb_limit < 0: the default."""
+    _fields_ = [("threshold", C.c_int), ("post", C.c_int), ("comb_limit", C.c_longlong)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/pfnl_hip.h declares
 _vp, _i, _fp = C.c_void_p, C.c_int, C.POINTER(C.c_float)
 _i32p, _tp = C.POINTER(C.c_int32), C.POINTER(pfnl_tiling)
@@ -180,6 +185,13 @@ SIGNATURES = {
     "pfnl_op_deinterlace_u10": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pfnl_op_deinterlace_pair_u8": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
     "pfnl_op_deinterlace_pair_u10": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _vp]),
+    "pfnl_stream_telecine": (_i, [_vp, _i, _i, C.POINTER(pfnl_telecine_params)]),
+    "pfnl_stream_telecine_stats": (_i, [_vp, C.POINTER(C.c_longlong)]),
+    "pfnl_telecine_deliverable": (_i, [_i, C.c_longlong, _i, C.POINTER(C.c_longlong)]),
+    "pfnl_op_fieldmatch_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_op_fieldmatch_u10": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "pfnl_op_telecine_frame_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(pfnl_telecine_params), _vp, _vp, _vp]),
+    "pfnl_op_telecine_frame_u10": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(pfnl_telecine_params), _vp, _vp, _vp]),
     "pfnl_op_gather_windows_u10": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows_u10_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_scene_sad_u10": (_i, [_vp, _vp, _i, _i, _vp, _vp]),

@@ -11,6 +11,7 @@
 #include "conv_small.h"
 #include "conv_split16.h"
 #include "surface_geom.h"
+#include "telecine_geom.h"
 #include "tile_geom.h"
 
 namespace {
@@ -1283,6 +1284,74 @@ int pfnl_op_deinterlace_pair_u8(const uint8_t* const fields[6], int H, int W, in
 
 int pfnl_op_deinterlace_pair_u10(const uint16_t* const fields[6], int H, int W, int parity, uint16_t* out, void* stream) {
     return op_deinterlace_pair(fields, H, W, parity, out, stream);
+}
+
+// ---- inverse telecine: the match and the weave on three decoded fields (include/pfnl_hip.h TELECINE; telecine.hip) -------
+// what both hooks refuse before any HIP call; *q: the parameters with the defaults filled in
+static int telecine_op_refused(const void* A, const void* Xc, const void* Xp, int h, int W, int parity, const pfnl_telecine_params* params,
+                               const void* out, const void* words_dev, int sample_bytes, pfnl_telecine_params* q) {
+    const void* const ptr[5] = {A, Xc, Xp, out, words_dev};
+    const char* const name[5] = {"A", "Xc", "Xp", "out", "the device words"};
+    for (int k = 0; k < 5; ++k) {
+        if (!ptr[k]) return fail(PFNL_ERR_INVALID, std::string("telecine: ") + name[k] + " is NULL");
+        if (k < 4 && reinterpret_cast<uintptr_t>(ptr[k]) % sample_bytes) return fail(PFNL_ERR_INVALID, std::string("telecine: ") + name[k] + ": uint16 samples are 2-byte aligned");
+    }
+    if (reinterpret_cast<uintptr_t>(words_dev) % 8) return fail(PFNL_ERR_INVALID, "telecine: the device words must be 8-byte aligned");
+    if (h < 1) return fail(PFNL_ERR_INVALID, "telecine: h must be at least 1");
+    if (W < 1) return fail(PFNL_ERR_INVALID, "telecine: W must be at least 1");
+    if ((unsigned long long)h * 3ull * (unsigned long long)W >= (1ull << 32)) return fail(PFNL_ERR_INVALID, "telecine: h 3 W must be below 2^32");
+    if (parity != 0 && parity != 1) return fail(PFNL_ERR_INVALID, "telecine: parity is 0 (A is the top field) or 1");
+    if (const char* why = pfnl::telecine_params_refused(params, h, W, q)) return fail(PFNL_ERR_INVALID, why);
+    return 0;
+}
+
+extern "C++" template <typename T>
+static int op_fieldmatch(const T* A, const T* Xc, const T* Xp, int h, int W, int parity, int threshold, unsigned long long* counts_dev, void* stream) {
+    const pfnl_telecine_params given{threshold, 0, 0};
+    pfnl_telecine_params q;
+    if (int r = telecine_op_refused(A, Xc, Xp, h, W, parity, &given, A, counts_dev, (int)sizeof(T), &q)) return r;
+    OpStage st(stream);
+    unsigned long long* words = st.alloc<unsigned long long>(6);      // scratch [2] | decision [4]
+    st.run([&] { return hipMemsetAsync(words, 0, 6 * sizeof(unsigned long long), st.s); });
+    st.run([&] { return pfnl::launch_telecine_match(A, Xc, Xp, h, W, parity, threshold, words, pfnl::TelecineDecide{words + 2, nullptr, 0, 0}, st.s); });
+    st.run([&] { return hipMemcpyAsync(counts_dev, words + 2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st.s); });
+    return st.finish("fieldmatch op: ");
+}
+
+extern "C++" template <typename T>
+static int op_telecine_frame(const T* A, const T* Xc, const T* Xp, int h, int W, int parity, const pfnl_telecine_params* params, T* out,
+                             unsigned long long* decision_dev, void* stream) {
+    pfnl_telecine_params q;
+    if (int r = telecine_op_refused(A, Xc, Xp, h, W, parity, params, out, decision_dev, (int)sizeof(T), &q)) return r;
+    const uintptr_t field = (uintptr_t)h * W * 3 * sizeof(T), o = reinterpret_cast<uintptr_t>(out);
+    for (const T* f : {A, Xc, Xp})
+        if (reinterpret_cast<uintptr_t>(f) < o + 2 * field && o < reinterpret_cast<uintptr_t>(f) + field)
+            return fail(PFNL_ERR_INVALID, "telecine: out overlaps one of the fields");
+    // the two launches a session issues per matched frame, and nothing else: the scratch is the caller's (words 4, 5; zero between launches)
+    HIPCHK(pfnl::launch_telecine_match(A, Xc, Xp, h, W, parity, q.threshold, decision_dev + 4,
+                                       pfnl::TelecineDecide{decision_dev, nullptr, q.post, (unsigned long long)q.comb_limit}, (hipStream_t)stream));
+    HIPCHK(pfnl::launch_telecine_weave(A, Xc, Xp, h, W, parity, decision_dev, out, nullptr, nullptr, nullptr, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_fieldmatch_u8(const uint8_t* A, const uint8_t* Xc, const uint8_t* Xp, int h, int W, int parity, int threshold,
+                          unsigned long long* counts_dev, void* stream) {
+    return op_fieldmatch(A, Xc, Xp, h, W, parity, threshold, counts_dev, stream);
+}
+
+int pfnl_op_fieldmatch_u10(const uint16_t* A, const uint16_t* Xc, const uint16_t* Xp, int h, int W, int parity, int threshold,
+                           unsigned long long* counts_dev, void* stream) {
+    return op_fieldmatch(A, Xc, Xp, h, W, parity, threshold, counts_dev, stream);
+}
+
+int pfnl_op_telecine_frame_u8(const uint8_t* A, const uint8_t* Xc, const uint8_t* Xp, int h, int W, int parity, const pfnl_telecine_params* params,
+                              uint8_t* out, unsigned long long* decision_dev, void* stream) {
+    return op_telecine_frame(A, Xc, Xp, h, W, parity, params, out, decision_dev, stream);
+}
+
+int pfnl_op_telecine_frame_u10(const uint16_t* A, const uint16_t* Xc, const uint16_t* Xp, int h, int W, int parity,
+                               const pfnl_telecine_params* params, uint16_t* out, unsigned long long* decision_dev, void* stream) {
+    return op_telecine_frame(A, Xc, Xp, h, W, parity, params, out, decision_dev, stream);
 }
 
 // as pfnl_op_gather_windows_u8: what both gathers refuse before any HIP call (scene_first: null for the plain one)

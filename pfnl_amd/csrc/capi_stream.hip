@@ -20,6 +20,7 @@
 #include "common.h"
 #include "field_geom.h"
 #include "stream_route.h"
+#include "telecine_geom.h"
 #include "tile_geom.h"
 
 namespace {
@@ -102,7 +103,19 @@ struct pfnl_stream {
     bool woven_mark[3] = {false, false, false};       // pfnl_stream_mark_cut's mark, travelling with the woven frame in the slot
     hipEvent_t il_ev = nullptr;                       // the newest use of the field store on the session's stream (device-pointer pushes, end)
     bool il_on_s = false;                             // ... that the copy stream has not yet been ordered behind
+    // inverse telecine (pfnl_stream_telecine; telecine_geom.h): exclusive with interlacing, and on its field store, `woven`, the marks and
+    // the event; woven_done counts the matched frames made
+    int tc_mode = PFNL_TELECINE_OFF, tc_order = PFNL_FIELD_TFF;
+    pfnl_telecine_params tc_par{};                    // with the defaults filled in
+    uint8_t* tc_frames = nullptr;                     // [5][H][W][3] samples of the input depth: the matched frames of the current cycle (mode DECIMATE reads them)
+    unsigned long long* tc_words = nullptr;           // device: the match's scratch [2] | the distance's scratch [2] | D [5] | stats [3] | decision [4]
+    unsigned long long* tc_host = nullptr;            // pinned: D [5] of a complete cycle | stats [3]
+    bool tc_mark[pfnl::TC_CYCLE] = {false, false, false, false, false};   // the marks of the cycle's pushed frames
+    bool tc_carry = false;                            // the mark of a dropped last frame, on its way to the next cycle's first
+    long long tc_dropped = 0, tc_admitted = 0;        // of the current sequence
 };
+
+constexpr int TC_WORDS = 16, TC_AT_SAD = 2, TC_AT_D = 4, TC_AT_STATS = 9, TC_AT_DECISION = 12;
 
 namespace {
 
@@ -274,6 +287,12 @@ int drop_sequence(pfnl_stream* s) {
     s->mark = s->decided_on_s = s->has_info = false;
     s->woven = s->woven_done = 0;                     // (both streams are idle: nothing reads the field store)
     s->woven_mark[0] = s->woven_mark[1] = s->woven_mark[2] = s->il_on_s = false;
+    for (bool& m : s->tc_mark) m = false;
+    s->tc_carry = false;
+    s->tc_dropped = s->tc_admitted = 0;
+    if (s->tc_words)                                  // the statistics are the sequence's (the scratch words are zero between launches)
+        if (hipMemsetAsync(s->tc_words, 0, TC_WORDS * sizeof(unsigned long long), s->cs) != hipSuccess || hipStreamSynchronize(s->cs) != hipSuccess)
+            r = fail(PFNL_ERR_HIP, "clearing the telecine statistics failed");
     if (int e = restore_options(s)) r = e;
     return r;
 }
@@ -435,7 +454,7 @@ int stage_host(pfnl_stream* s, const pfnl_surface& frame, pfnl_surface* at) {
 // ---- interlaced input (include/pfnl_hip.h INTERLACED): woven frames -> decoded fields in the field store -> progressive ring frames ----
 
 uint8_t* field_at(const pfnl_stream* s, long long k) {    // field k of the sequence, in the slot of its frame
-    return s->fstore + ((size_t)(pfnl::field_frame(k) % 3) * 2 + pfnl::field_parity(k, s->il_order)) * (s->in.ring_bytes / 2);
+    return s->fstore + ((size_t)(pfnl::field_frame(k) % 3) * 2 + pfnl::field_parity(k, s->tc_mode ? s->tc_order : s->il_order)) * (s->in.ring_bytes / 2);
 }
 
 // The field of parity p of the woven frame `frame` (device planes; an RGB frame's may be host memory: from_host) -> its place in the slot
@@ -482,14 +501,88 @@ int admit_woven(pfnl_stream* s, int is_device) {
     return 0;
 }
 
-// What every push is with interlacing on: the bound for every ring frame the push completes, on copies of the counters (nothing has
-// changed where it refuses); the frame's two fields decoded into the slot of the field store - device pointers on the session's stream,
-// host pointers on the copy stream, YUV and packings through the staging frame -; then the woven frame before it, which now has both
-// neighbours, becomes its ring frames.  The field store is used on one stream at a time: the copy stream is idle when a push returns, and
+// ---- inverse telecine (include/pfnl_hip.h TELECINE): the field store's fields -> matched frames -> the ring, all of them or four in five ----
+
+// Matched frame n into `out` on `on`: the match, which leaves its decision on the device; with post on the deinterlacer's frame at the time
+// of field 2 n, which a flagged frame keeps; the weave, which in mode DECIMATE also sums D_n against the matched frame before it.
+template <typename T>
+int make_matched(pfnl_stream* s, long long n, uint8_t* out, hipStream_t on) {
+    const long long fields = 2 * s->woven, k = 2 * n;
+    const pfnl::MatchFields mf = pfnl::telecine_match_fields(n, fields);
+    const auto at = [&](long long q) { return reinterpret_cast<const T*>(field_at(s, pfnl::field_replace(q, fields))); };
+    const int h = s->H / 2, parity = pfnl::field_parity(k, s->tc_order), slot = pfnl::telecine_cycle_slot(n);
+    const bool decimate = s->tc_mode == PFNL_TELECINE_DECIMATE;
+    unsigned long long* const w = s->tc_words;
+    HIPCHK(pfnl::launch_telecine_match(at(mf.a), at(mf.c), at(mf.p), h, s->W, parity, s->tc_par.threshold, w,
+                                       pfnl::TelecineDecide{w + TC_AT_DECISION, w + TC_AT_STATS, s->tc_par.post, (unsigned long long)s->tc_par.comb_limit}, on));
+    if (s->tc_par.post)
+        HIPCHK(pfnl::launch_deinterlace(at(k - 2), at(k - 1), at(k), at(k + 1), at(k + 2), s->H, s->W, parity, reinterpret_cast<T*>(out), on));
+    const uint8_t* const prev = decimate && n ? s->tc_frames + (size_t)pfnl::telecine_cycle_slot(n - 1) * s->in.ring_bytes : nullptr;
+    HIPCHK(pfnl::launch_telecine_weave(at(mf.a), at(mf.c), at(mf.p), h, s->W, parity, w + TC_AT_DECISION, reinterpret_cast<T*>(out),
+                                       reinterpret_cast<const T*>(prev), decimate ? w + TC_AT_SAD : nullptr, decimate ? w + TC_AT_D + slot : nullptr, on));
+    return 0;
+}
+
+// Pushed frame s->woven_done becomes its matched frame, and that whatever it completes.  Mode MATCH: written straight into its ring slot and
+// admitted as a progressive push admits a frame.  Mode DECIMATE: written into its place in the cycle; the cycle's last frame (at_end: the
+// sequence's) has the host wait - once per cycle - for the cycle's five D, and the kept frames are copied into their ring slots and
+// admitted in order, each with the mark that lands on it.  The caller has seen that the bound admits them all.
+int admit_matched(pfnl_stream* s, int is_device, bool at_end) {
+    const hipStream_t on = is_device ? s->s : s->cs;
+    const long long n = s->woven_done;
+    const bool ten = s->set.in_depth == 10;
+    const auto make = [&](uint8_t* dst, hipStream_t q) { return ten ? make_matched<uint16_t>(s, n, dst, q) : make_matched<uint8_t>(s, n, dst, q); };
+    if (s->tc_mode == PFNL_TELECINE_MATCH) {
+        s->mark = s->woven_mark[n % 3];
+        if (int e = push_frame(s, is_device, [&](uint8_t* dst) { return make(dst, s->s); }, [&](uint8_t* dst) { return make(dst, s->cs); })) return e;
+        ++s->woven_done;
+        ++s->tc_admitted;
+        return 0;
+    }
+    const int slot = pfnl::telecine_cycle_slot(n);
+    if (int e = make(s->tc_frames + (size_t)slot * s->in.ring_bytes, on)) return e;
+    s->tc_mark[slot] = s->woven_mark[n % 3];
+    ++s->woven_done;
+    const bool complete = slot == pfnl::TC_CYCLE - 1;
+    if (!complete && !at_end) {
+        if (!is_device) HIPCHK(hipStreamSynchronize(s->cs));          // (the caller's memory is free on return)
+        return 0;
+    }
+    int drop = -1;
+    if (complete) {
+        HIPCHK(hipMemcpyAsync(s->tc_host, s->tc_words + TC_AT_D, pfnl::TC_CYCLE * sizeof(unsigned long long), hipMemcpyDeviceToHost, on));
+        // The D depend on the frame this push decoded on `on`.  For a device-pointer push that is the session's stream - the caller's frame
+        // is read in the caller's order - so this also waits for the forwards queued there, once per cycle; an event behind the copy
+        // would complete no earlier on an in-order stream, and the copy stream cannot run ahead of a decode it must follow.
+        HIPCHK(hipStreamSynchronize(on));
+        drop = pfnl::telecine_drop_index(s->tc_host);
+        ++s->tc_dropped;
+    }
+    bool marks[pfnl::TC_CYCLE];
+    (void)pfnl::telecine_place_marks(s->tc_mark, slot + 1, drop, &s->tc_carry, marks);
+    for (int j = 0, i = 0; j <= slot; ++j) {
+        if (j == drop) continue;
+        const uint8_t* const src = s->tc_frames + (size_t)j * s->in.ring_bytes;
+        const auto copy = [&](uint8_t* dst, hipStream_t q) {
+            HIPCHK(hipMemcpyAsync(dst, src, s->in.ring_bytes, hipMemcpyDeviceToDevice, q));
+            return 0;
+        };
+        s->mark = marks[i++];
+        if (int e = push_frame(s, is_device, [&](uint8_t* dst) { return copy(dst, s->s); }, [&](uint8_t* dst) { return copy(dst, s->cs); })) return e;
+        ++s->tc_admitted;
+    }
+    return 0;
+}
+
+// What every push is with interlacing or inverse telecine on: the bound for every ring frame the push completes, on copies of the
+// counters (nothing has changed where it refuses); the frame's two fields decoded into the slot of the field store - device pointers on
+// the session's stream, host pointers on the copy stream, YUV and packings through the staging frame -; then the woven frame before it,
+// which now has both neighbours, becomes its ring frames (admit_woven), or its matched frame and whatever that completes (admit_matched).
+// The field store, and telecine's cycle and device words with it, is used on one stream at a time: the copy stream is idle when a push returns, and
 // falls in behind the session's stream's newest use of it first.
 int push_woven(pfnl_stream* s, int is_device, const pfnl_surface& frame) {
     if (s->ended) return fail(PFNL_ERR_STATE, "push after pfnl_stream_end (pfnl_stream_reset starts the next sequence)");
-    const int yield = s->woven ? pfnl::interlace_yield(s->il_mode) : 0;
+    const int yield = s->tc_mode ? pfnl::telecine_push_yield(s->tc_mode, s->woven) : (s->woven ? pfnl::interlace_yield(s->il_mode) : 0);
     pfnl::RingCounters c = ring_counters(s);
     if (!pfnl::ring_admit_all(s->T, s->batch, s->cap, yield, &c))
         return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
@@ -507,7 +600,9 @@ int push_woven(pfnl_stream* s, int is_device, const pfnl_surface& frame) {
     s->mark = false;
     ++s->woven;
     int r = 0;
-    if (yield)
+    if (s->tc_mode && s->woven > 1)                   // (a matched frame is made whether or not it completes a ring frame)
+        r = admit_matched(s, is_device, false);
+    else if (yield)
         r = admit_woven(s, is_device);
     else if (!is_device)
         HIPCHK(hipStreamSynchronize(s->cs));          // (the caller's memory is free on return)
@@ -520,7 +615,7 @@ int push_woven(pfnl_stream* s, int is_device, const pfnl_surface& frame) {
 
 // where both push entries end, each with its own argument checks behind it: the frame as a surface of the input route
 int push_surface(pfnl_stream* s, const pfnl_surface& frame, int is_device) {
-    if (s->il_mode) return push_woven(s, is_device, frame);
+    if (s->il_mode || s->tc_mode) return push_woven(s, is_device, frame);
     return push_frame(
         s, is_device, [&](uint8_t* dst) { return decode_surface(s, frame, s->H, dst, false, s->s); },   // the kernel reads the surface where it lies
         [&](uint8_t* dst) {
@@ -547,6 +642,9 @@ void release(pfnl_stream* s) {
     if (s->yin) (void)hipFree(s->yin);
     if (s->fstore) (void)hipFree(s->fstore);
     if (s->il_ev) (void)hipEventDestroy(s->il_ev);
+    if (s->tc_frames) (void)hipFree(s->tc_frames);
+    if (s->tc_words) (void)hipFree(s->tc_words);
+    if (s->tc_host) (void)hipHostFree(s->tc_host);
     if (s->rtab) (void)hipFree(s->rtab);
     if (s->ring) (void)hipFree(s->ring);
     if (s->win) (void)hipFree(s->win);
@@ -579,7 +677,7 @@ int apply_setting(pfnl_stream* s, const Setting& c, pfnl::PlacePlan* plan, const
     HIPCHK(hipSetDevice(s->device));
     if (frees) HIPCHK(hipStreamSynchronize(s->s));
     int32_t* tab = nullptr;
-    uint8_t *yin = nullptr, *ring = nullptr, *fstore = nullptr;   // (the field store follows the ring's depth)
+    uint8_t *yin = nullptr, *ring = nullptr, *fstore = nullptr, *cycle = nullptr;   // (the field store and telecine's cycle follow the ring's depth)
     bool ok = true;
     if (plan && plan->cH) {
         const std::vector<int32_t>& blob = plan->r.blob;
@@ -589,6 +687,7 @@ int apply_setting(pfnl_stream* s, const Setting& c, pfnl::PlacePlan* plan, const
     }
     if (regauged) ok = ok && hipMalloc(reinterpret_cast<void**>(&ring), (size_t)s->cap * in_bytes) == hipSuccess;
     if (regauged && s->fstore) ok = ok && hipMalloc(reinterpret_cast<void**>(&fstore), 3 * in_bytes) == hipSuccess;
+    if (regauged && s->tc_frames) ok = ok && hipMalloc(reinterpret_cast<void**>(&cycle), pfnl::TC_CYCLE * in_bytes) == hipSuccess;
     if (yin_need > s->yin_cap) ok = ok && hipMalloc(reinterpret_cast<void**>(&yin), yin_need) == hipSuccess;
     for (StageSlot& t : fresh)
         for (int i = 0; i < 2 && t.cap; ++i) ok = ok && hipMalloc(reinterpret_cast<void**>(&t.buf[i]), t.cap) == hipSuccess;
@@ -598,6 +697,7 @@ int apply_setting(pfnl_stream* s, const Setting& c, pfnl::PlacePlan* plan, const
         if (yin) (void)hipFree(yin);
         if (ring) (void)hipFree(ring);
         if (fstore) (void)hipFree(fstore);
+        if (cycle) (void)hipFree(cycle);
         for (StageSlot& t : fresh) drop_slot(t);
         return fail(PFNL_ERR_NOMEM, nomem);
     }
@@ -618,6 +718,10 @@ int apply_setting(pfnl_stream* s, const Setting& c, pfnl::PlacePlan* plan, const
     if (fstore) {
         (void)hipFree(s->fstore);
         s->fstore = fstore;
+    }
+    if (cycle) {
+        (void)hipFree(s->tc_frames);
+        s->tc_frames = cycle;
     }
     for (int k = 0; k < pfnl::ROUTE_STAGES; ++k)
         if (fresh[k].cap || !route.runs[k]) {
@@ -712,6 +816,15 @@ int pfnl_stream_push_surface(pfnl_stream* s, const pfnl_surface* frame, int is_d
 int pfnl_stream_end(pfnl_stream* s) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     HIPCHK(hipSetDevice(s->device));
+    if (s->tc_mode && !s->ended && s->woven > s->woven_done) {   // the held frame and what it completes, under a push's bound
+        pfnl::RingCounters c = ring_counters(s);
+        if (!pfnl::ring_admit_all(s->T, s->batch, s->cap, pfnl::telecine_end_yield(s->tc_mode, s->woven, s->woven_done), &c))
+            return fail(PFNL_ERR_STATE, "pop first: the session holds at most 2 * batch undelivered SR frames");
+        const int r = admit_matched(s, 1, true);      // (on the session's stream: the copy stream is idle between calls)
+        HIPCHK(hipEventRecord(s->il_ev, s->s));
+        s->il_on_s = true;
+        if (r) return r;
+    }
     if (s->il_mode && !s->ended && s->woven > s->woven_done) {   // the held frame first, under a push's bound: its fields past the end repeat
         pfnl::RingCounters c = ring_counters(s);
         if (!pfnl::ring_admit_all(s->T, s->batch, s->cap, pfnl::interlace_yield(s->il_mode), &c))
@@ -828,6 +941,8 @@ static int candidate_refused(const pfnl_stream* s, const Setting& c, int out_h, 
     if (why) return fail(PFNL_ERR_INVALID, std::string(why) + " - the change contradicts a packing in force: set PFNL_PACK_NONE first (pfnl_stream_packing)");
     if (const char* no = pfnl::interlace_refused(s->il_mode, s->il_order, s->H, pfnl::is_yuv(c.in_fmt), c.in_chroma, c.in_pack))
         return fail(PFNL_ERR_INVALID, no);
+    if (const char* no = pfnl::telecine_refused(s->tc_mode, s->tc_order, s->H, pfnl::is_yuv(c.in_fmt), c.in_chroma, c.in_pack, s->batch))
+        return fail(PFNL_ERR_INVALID, no);
     return 0;
 }
 
@@ -896,6 +1011,7 @@ int pfnl_stream_interlace(pfnl_stream* s, int mode, int field_order) {
     if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
     if (const char* why = pfnl::interlace_refused(mode, field_order, s->H, pfnl::is_yuv(s->set.in_fmt), s->set.in_chroma, s->set.in_pack))
         return fail(PFNL_ERR_INVALID, why);
+    if (mode && s->tc_mode) return fail(PFNL_ERR_INVALID, "interlace: inverse telecine is on (pfnl_stream_telecine): the two are exclusive");
     if (started(s)) return fail(PFNL_ERR_STATE, "interlacing is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     if (mode && !s->fstore) {
         HIPCHK(hipSetDevice(s->device));
@@ -913,6 +1029,71 @@ int pfnl_stream_interlace(pfnl_stream* s, int mode, int field_order) {
     }
     s->il_mode = mode;
     s->il_order = field_order;
+    return 0;
+}
+
+// Inverse telecine: pushed frames are fields of film, the ring receives the film's frames (telecine_geom.h; telecine.hip).  The first call
+// that turns it on allocates what it needs beside the field store, all of it or nothing.
+int pfnl_stream_telecine(pfnl_stream* s, int mode, int field_order, const pfnl_telecine_params* params) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (const char* why = pfnl::telecine_refused(mode, field_order, s->H, pfnl::is_yuv(s->set.in_fmt), s->set.in_chroma, s->set.in_pack, s->batch))
+        return fail(PFNL_ERR_INVALID, why);
+    pfnl_telecine_params q;
+    if (const char* why = pfnl::telecine_params_refused(params, s->H / 2, s->W, &q)) return fail(PFNL_ERR_INVALID, why);
+    if (mode && s->il_mode) return fail(PFNL_ERR_INVALID, "telecine: interlacing is on (pfnl_stream_interlace): the two are exclusive");
+    if (started(s)) return fail(PFNL_ERR_STATE, "inverse telecine is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (mode && !s->tc_frames) {
+        HIPCHK(hipSetDevice(s->device));
+        uint8_t *store = nullptr, *cycle = nullptr;
+        unsigned long long *words = nullptr, *host = nullptr;
+        hipEvent_t ev = nullptr;
+        bool ok = s->fstore || hipMalloc(reinterpret_cast<void**>(&store), 3 * s->in.ring_bytes) == hipSuccess;
+        ok = ok && (s->il_ev || hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess);
+        ok = ok && hipMalloc(reinterpret_cast<void**>(&cycle), pfnl::TC_CYCLE * s->in.ring_bytes) == hipSuccess;
+        ok = ok && hipMalloc(reinterpret_cast<void**>(&words), TC_WORDS * sizeof(unsigned long long)) == hipSuccess;
+        // (zeroed on the copy stream and waited for, as the scene table is)
+        ok = ok && hipMemsetAsync(words, 0, TC_WORDS * sizeof(unsigned long long), s->cs) == hipSuccess && hipStreamSynchronize(s->cs) == hipSuccess;
+        ok = ok && hipHostMalloc(reinterpret_cast<void**>(&host), 8 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (store) (void)hipFree(store);
+            if (ev) (void)hipEventDestroy(ev);
+            if (cycle) (void)hipFree(cycle);
+            if (words) (void)hipFree(words);
+            if (host) (void)hipHostFree(host);
+            return fail(PFNL_ERR_NOMEM, "telecine store allocation failed");
+        }
+        if (store) s->fstore = store;
+        if (ev) s->il_ev = ev;
+        s->tc_frames = cycle;
+        s->tc_words = words;
+        s->tc_host = host;
+    }
+    s->tc_mode = mode;
+    s->tc_order = field_order;
+    s->tc_par = q;
+    return 0;
+}
+
+int pfnl_stream_telecine_stats(pfnl_stream* s, long long out[5]) {
+    if (!s || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    for (int k = 0; k < 5; ++k) out[k] = 0;
+    if (!s->tc_words) return 0;
+    HIPCHK(hipSetDevice(s->device));
+    HIPCHK(hipStreamSynchronize(s->s));
+    HIPCHK(hipMemcpyAsync(s->tc_host + pfnl::TC_CYCLE, s->tc_words + TC_AT_STATS, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->cs));
+    HIPCHK(hipStreamSynchronize(s->cs));
+    for (int k = 0; k < 3; ++k) out[k] = (long long)s->tc_host[pfnl::TC_CYCLE + k];
+    out[3] = s->tc_dropped;
+    out[4] = s->tc_admitted;
+    return 0;
+}
+
+int pfnl_telecine_deliverable(int mode, long long pushed, int ended, long long* frames) {
+    if (!frames) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (mode != PFNL_TELECINE_MATCH && mode != PFNL_TELECINE_DECIMATE) return fail(PFNL_ERR_INVALID, "deliverable: mode PFNL_TELECINE_MATCH or PFNL_TELECINE_DECIMATE");
+    if (pushed < 0) return fail(PFNL_ERR_INVALID, "deliverable: pushed is not negative");
+    *frames = pfnl::telecine_deliverable(mode, pushed, ended != 0);
     return 0;
 }
 

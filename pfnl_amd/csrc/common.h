@@ -288,6 +288,30 @@ hipError_t launch_deinterlace(const uint8_t* p2, const uint8_t* p1, const uint8_
 hipError_t launch_deinterlace(const uint16_t* p2, const uint16_t* p1, const uint16_t* cur, const uint16_t* n1, const uint16_t* n2, int H, int W,
                               int parity, uint16_t* out, hipStream_t s);
 
+// ---- inverse telecine: field matching, the weave and the frame distance (telecine.hip; the rule: pfnl_amd/telecine.py) ----
+// A, Xc, Xp: the kept field of parity `parity` and its two candidate partners, tight [h][W][3] samples of T (uint16_t: min(v, 1023)),
+// read-only; they may be one another.  Any alignment a sample can have (16-byte words, 4-byte words or single samples, as deinterlace.hip).
+// The match leaves decision[4] = count of c, count of p, match (0: c, 1: p), post (0 | 1) in device memory and adds one to stats[0 | 1 | 2]
+// (matched c, matched p, post-processed; NULL: no statistics).  scratch: two zeroed 64-bit words that every launch leaves zeroed (launches
+// that share them must not overlap).  h 3 W < 2^32.
+struct TelecineDecide {
+    unsigned long long* decision;
+    unsigned long long* stats;
+    int post;                                // 1: a frame whose smaller count exceeds comb_limit is flagged
+    unsigned long long comb_limit;
+};
+hipError_t launch_telecine_match(const uint8_t* A, const uint8_t* Xc, const uint8_t* Xp, int h, int W, int parity, int threshold,
+                                 unsigned long long* scratch, const TelecineDecide& d, hipStream_t s);
+hipError_t launch_telecine_match(const uint16_t* A, const uint16_t* Xc, const uint16_t* Xp, int h, int W, int parity, int threshold,
+                                 unsigned long long* scratch, const TelecineDecide& d, hipStream_t s);
+// The matched frame out [2 h][W][3] from the decision on the device: the weave of A and the chosen partner, or, post-flagged, what `out`
+// already holds (the deinterlaced frame) untouched.  dist != NULL: *dist = sum |out - prev| over all samples, TC_D_FIRST where prev is NULL
+// (scratch as above; NULL with dist NULL).  out overlaps none of the inputs.
+hipError_t launch_telecine_weave(const uint8_t* A, const uint8_t* Xc, const uint8_t* Xp, int h, int W, int parity, const unsigned long long* decision,
+                                 uint8_t* out, const uint8_t* prev, unsigned long long* scratch, unsigned long long* dist, hipStream_t s);
+hipError_t launch_telecine_weave(const uint16_t* A, const uint16_t* Xc, const uint16_t* Xp, int h, int W, int parity, const unsigned long long* decision,
+                                 uint16_t* out, const uint16_t* prev, unsigned long long* scratch, unsigned long long* dist, hipStream_t s);
+
 // ---- RGB frames at a chosen raster: the tap tables (resize.hip; the rule: pfnl_amd/resize.py) ----
 constexpr int RESIZE_MAX_SIZE = 16384;   // per axis, in and out; ceil(n_in / 4) <= n_out <= 2 n_in
 constexpr int RESIZE_TW = 64;            // output pixels of one workgroup: across,

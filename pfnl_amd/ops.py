@@ -1053,6 +1053,53 @@ def deinterlace_u10(p2, p1, cur, n1, n2, parity, out=None):
     return _deinterlace((p2, p1, cur, n1, n2), parity, out, _req_u16, torch.uint16, _capi.load_library().pfnl_op_deinterlace_u10)
 
 
+# ---- inverse telecine (include/pfnl_hip.h TELECINE; the rule: pfnl_amd/telecine.py) --------------------------------------------------------
+def _telecine_fields(A, Xc, Xp, parity):
+    import torch
+    ten = A.dtype == torch.uint16
+    req = _req_u16 if ten else _req_u8
+    ptrs = [req(f, n) for f, n in zip((A, Xc, Xp), ("A", "Xc", "Xp"))]
+    if A.dim() != 3 or A.shape[2] != 3 or any(tuple(f.shape) != tuple(A.shape) or f.device != A.device for f in (Xc, Xp)):
+        raise ValueError("the three fields are [H/2, W, 3] tensors of one shape on one device")
+    if parity not in (0, 1):
+        raise ValueError(f"parity: 0 or 1, got {parity!r}")
+    return ten, req, ptrs
+
+
+def fieldmatch(A, Xc, Xp, parity, threshold=10):
+    """The kept field ``A`` of parity ``parity`` and its two candidate partners, contiguous [H/2,W,3] uint8 (or all uint16: min(v, 1023))
+    tensors on the GPU at any address -> (count of c, count of p): pfnl_amd/telecine.py comb_count of each, exactly
+    (pfnl_op_fieldmatch_u8 / _u10: the match launch of the streaming session's inverse telecine)."""
+    import torch
+    ten, _, ptrs = _telecine_fields(A, Xc, Xp, parity)
+    h, W, _ = A.shape
+    counts = torch.zeros(2, dtype=torch.int64, device=A.device)
+    lib = _capi.load_library()
+    _capi.check((lib.pfnl_op_fieldmatch_u10 if ten else lib.pfnl_op_fieldmatch_u8)(*ptrs, h, W, int(parity), int(threshold),
+                                                                                  C.c_void_p(counts.data_ptr()), _stream(A)))
+    return tuple(int(v) for v in counts.cpu())
+
+
+def telecine_frame(A, Xc, Xp, parity, threshold=None, post=False, comb_limit=None, out=None):
+    """Counts, decision and weave of one pushed frame (pfnl_op_telecine_frame_u8 / _u10) -> (the matched frame [H,W,3], {"count_c",
+    "count_p", "match": 0 (c) | 1 (p), "post": 0 | 1}).  With ``post`` the caller passes the deinterlaced frame as ``out``: a flagged frame
+    leaves it as it is.  ``threshold`` / ``comb_limit`` None: the defaults of pfnl_amd/telecine.py."""
+    import torch
+    ten, req, ptrs = _telecine_fields(A, Xc, Xp, parity)
+    h, W, _ = A.shape
+    if post and out is None:
+        raise ValueError("with post the deinterlaced frame is passed as out")
+    out = _out(out, (2 * h, W, 3), A.dtype, A.device)
+    par = _capi.pfnl_telecine_params(10 if threshold is None else int(threshold), int(bool(post)), -1 if comb_limit is None else int(comb_limit))
+    decision = torch.zeros(6, dtype=torch.int64, device=A.device)   # (the last two: the launches' scratch)
+    lib = _capi.load_library()
+    _capi.check((lib.pfnl_op_telecine_frame_u10 if ten else lib.pfnl_op_telecine_frame_u8)(*ptrs, h, W, int(parity), C.byref(par), req(out, "out"),
+                                                                                          C.c_void_p(decision.data_ptr()), _stream(A)))
+    d = [int(v) for v in decision.cpu()]
+    assert d[4] == d[5] == 0
+    return out, {"count_c": d[0], "count_p": d[1], "match": d[2], "post": d[3]}
+
+
 def _ring_u10(ring, name):
     _req_u16(ring, "ring")
     if ring.dim() != 4 or ring.shape[3] != 3:

@@ -18,7 +18,7 @@ import time
 
 import numpy as np
 
-from . import packed as _packed
+from . import packed as _packed, telecine as _telecine
 
 
 class RawReader:
@@ -115,6 +115,8 @@ def run(reader, writer, open_stream, out_format=None, log=None, **session_kw) ->
             deliver(vs.push(frame))
         deliver(vs.end())
     due = reader.frames * (2 if kw.get("interlaced") == "field" else 1)   # (at field rate a woven frame is two)
+    if kw.get("telecine") is not None:                                    # (film: every frame, or four in five)
+        due = _telecine.deliverable(kw["telecine"], reader.frames, True)
     if done != due:
         raise RuntimeError(f"{reader.frames} frames read, {done} delivered where {due} were due")
     seconds = time.perf_counter() - t0
@@ -150,6 +152,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--out-size", type=_size, default=None, metavar="HxW")
     ap.add_argument("--interlaced", choices=("frame", "field"), default=None,
                     help="the frames are woven fields: deinterlace on the device, one progressive frame per frame or per field")
+    ap.add_argument("--ivtc", choices=("match", "decimate"), default=None,
+                    help="the frames are film under 3:2 pulldown: match the fields on the device; decimate also drops the repeat (needs --batch 2 or more)")
     ap.add_argument("--field-order", choices=("tff", "bff"), default="tff", help="which field of a woven frame comes first (a raw pipe has no header)")
     return ap
 
@@ -176,6 +180,10 @@ def main(argv=None) -> int:
         eng = PFNLEngine(geom, device=0)
         eng.load_weights(weights)
         woven = {} if a.interlaced is None else {"interlaced": a.interlaced, "field_order": a.field_order}
+        if a.ivtc is not None:
+            if a.interlaced is not None:
+                raise ValueError("--ivtc and --interlaced are exclusive: film carried in fields is matched, video is deinterlaced")
+            woven = {"telecine": a.ivtc, "field_order": a.field_order}
         run(reader, RawWriter(fout), eng.open_stream, out_format=a.out_format, batch=a.batch, matrix=a.matrix, full_range=a.full_range,
             chroma_siting=a.siting, out_size=a.out_size, **woven)
         fout.flush()

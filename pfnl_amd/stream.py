@@ -59,6 +59,11 @@ frames - both fields in the pushed layout, whatever it is - and deinterlaces the
 pfnl_amd/deinterlace.py: one progressive frame per pushed frame at "frame", two at "field", a frame later than the push that brought
 them.  Everything behind the ring is what it was.
 
+Film under 3:2 pulldown (off by default): ``open_stream(H, W, batch, telecine="decimate", field_order="tff")`` takes the frames of film
+carried at 29.97 frames a second, re-pairs their fields on the device ahead of the ring by the integer rule of pfnl_amd/telecine.py and drops
+the one frame in five that repeats a picture: indices count film frames, and a cycle's four frames come together (``batch`` at least 2).
+``telecine="match"`` keeps every frame.  Exclusive with ``interlaced``.
+
 Surfaces: ``vs.push_planes(y, cbcr)`` / ``vs.pop_planes(y, cbcr)`` take and fill a frame as a decoder or encoder holds it - one array per
 plane, each with the row pitch its strides say (pfnl_amd/surface.py), e.g. ``surface[:H, :W]`` of a pitched device allocation - in the
 session's formats; a device NV12 / I420 surface is converted where it lies, and only the samples of a destination are written.
@@ -200,6 +205,23 @@ def interlace_arguments(interlaced=None, field_order="tff", H: int = 4, pixel_fo
     if mode:
         _deinterlace.check_height(int(H), pixel_format in _capi.FORMATS_420 and chroma == "420" and packing in (None, "none"))
     return mode, order
+
+
+def telecine_arguments(telecine=None, field_order="tff", telecine_params=None, H: int = 4, W: int = 2, pixel_format="rgb24", chroma="420",
+                       packing=None, interlaced=None):
+    """(mode, field order, (threshold, post, comb_limit)) of pfnl_stream_telecine for open_stream's ``telecine`` (None = off: no call),
+    ``field_order`` and ``telecine_params`` (None, or a dict with any of "threshold", "post", "comb_limit"), for frames of H x W in the input
+    setting of the other keywords; ValueError for anything the library would refuse (pfnl_amd/telecine.py).  Needs no device."""
+    from . import deinterlace as _deinterlace, telecine as _telecine
+    mode, order = _telecine.mode_id(telecine), _deinterlace.order_id(field_order)
+    par = dict(telecine_params or {})
+    if set(par) - {"threshold", "post", "comb_limit"}:
+        raise ValueError(f"telecine_params: threshold, post, comb_limit; got {sorted(par)}")
+    if mode:
+        if interlaced is not None:
+            raise ValueError("telecine and interlaced are exclusive: film carried in fields is matched, video is deinterlaced")
+        _deinterlace.check_height(int(H), pixel_format in _capi.FORMATS_420 and chroma == "420" and packing in (None, "none"))
+    return mode, order, _telecine.params(max(int(H) // 2, 1), int(W), par.get("threshold"), par.get("post"), par.get("comb_limit"))
 
 
 def output_grid(out_format: str, out_chroma: str = "420") -> Tuple[int, int]:
@@ -347,16 +369,23 @@ class VideoStream:
     frames, one per pushed frame at "frame" and two at "field".  A frame is made when the one after it has been pushed, or at ``end()``;
     4:2:0 planes need H to be a multiple of 4.  ``mark_cut()`` marks the next pushed frame and lands on the first frame made from it.
 
+    ``telecine`` (None | "match" | "decimate") with ``field_order`` and ``telecine_params`` (None | a dict with "threshold", "post",
+    "comb_limit"): every pushed frame is two fields of film under 3:2 pulldown; the fields are re-paired on the device ahead of the ring
+    (pfnl_amd/telecine.py) and, at "decimate", one frame in five - the repeat - is dropped, so indices count film frames and a cycle's four
+    frames come together; it needs a batch of at least 2.  Exclusive with ``interlaced``.  ``telecine_stats()`` counts the current sequence's frames.
+
     ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
     (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
                  chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
-                 out_packing=None, interlaced=None, field_order="tff", ensemble=1):
+                 out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, ensemble=1):
         import torch
         self.in_depth = depth_argument(in_depth)    # (before the engine is touched, as every check of an argument)
         il = interlace_arguments(interlaced, field_order, H, pixel_format, chroma, packing)
+        tc = telecine_arguments(telecine, field_order, telecine_params, H, W, pixel_format, chroma, packing, interlaced)
+        self.telecine = telecine
         self.interlaced, self.field_order = interlaced, field_order
         fmt = format_arguments(pixel_format, out_format, matrix, full_range)
         sub = chroma_arguments(chroma, out_chroma)
@@ -451,6 +480,12 @@ class VideoStream:
             except Exception:
                 self.close()
                 raise
+        if tc[0]:                                   # (None: the session as it always was, and no call; behind the input setting, as above)
+            try:
+                _capi.check(self._lib.pfnl_stream_telecine(s, tc[0], tc[1], C.byref(_capi.pfnl_telecine_params(*tc[2]))))
+            except Exception:
+                self.close()
+                raise
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -507,7 +542,7 @@ class VideoStream:
         try:
             _capi.check(call())
         except _capi.PFNLHipError as e:
-            if self.interlaced is None or "pop first" not in str(e):
+            if (self.interlaced is None and self.telecine is None) or "pop first" not in str(e):
                 raise
             if container is not None:
                 self._device_frames = container
@@ -524,7 +559,7 @@ class VideoStream:
         try:
             _capi.check(self._lib.pfnl_stream_end(s))
         except _capi.PFNLHipError as e:             # (an interlaced session's held frame did not fit: what is ready is popped, once)
-            if self.interlaced is None or "pop first" not in str(e):
+            if (self.interlaced is None and self.telecine is None) or "pop first" not in str(e):
                 raise
             frames = self.pop_ready()
             _capi.check(self._lib.pfnl_stream_end(s))
@@ -554,6 +589,13 @@ class VideoStream:
         t = tiling_argument(self.H, self.W, tile_h, tile_w, pad, batch)          # (before anything touches the session)
         _capi.check(self._lib.pfnl_stream_tile(self._handle(), C.byref(_capi.pfnl_tiling(*t))))
         self._tiling = t
+
+    def telecine_stats(self) -> dict:
+        """The current sequence's frames so far: matched as pushed ("c"), matched with the field before ("p"), post-processed as video,
+        dropped, and admitted to the ring (pfnl_stream_telecine_stats; all 0 without ``telecine``)."""
+        out = (C.c_longlong * 5)()
+        _capi.check(self._lib.pfnl_stream_telecine_stats(self._handle(), out))
+        return dict(zip(("matched_c", "matched_p", "post", "dropped", "delivered"), (int(v) for v in out)))
 
     def mark_cut(self) -> None:
         """The next pushed frame starts a scene (needs ``scene_cut``; before the first frame of a sequence it changes nothing)."""

@@ -20,7 +20,7 @@ import argparse
 import sys
 import time
 
-from . import y4m as _y4m
+from . import telecine as _telecine, y4m as _y4m
 
 OUT_FORMATS = {8: "i420", 10: "i010"}
 
@@ -37,20 +37,27 @@ def session_keywords(header, **session_kw) -> dict:
     ``chroma`` for a 4:2:2 / 4:4:4 stream (and no such key for a 4:2:0 one; ``out_chroma`` likewise only where the caller names one) and -
     with ``fit`` alone - the sample aspect ratio.  A 4:2:2 output is co-sited across, as ``C422`` says: ``out_chroma_siting`` becomes "left"
     where the caller names none.  ``deinterlace`` ("frame" | "field") becomes ``interlaced`` with the header's field order for an ``It`` / ``Ib``
-    stream (and no such key for a progressive one); without it such a stream is a ValueError that names its tag.  ValueError for what a Y4M
-    stream cannot hold."""
+    stream (and no such key for a progressive one); without it such a stream is a ValueError that names its tag.  ``ivtc`` ("match" |
+    "decimate") becomes ``telecine`` with the header's field order instead - the stream is film under 3:2 pulldown (pfnl_amd/telecine.py) -;
+    the two are exclusive.  ValueError for what a Y4M stream cannot hold."""
     kw = dict(session_kw)
-    for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth", "chroma", "interlaced", "field_order"):
+    for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth", "chroma", "interlaced", "field_order", "telecine"):
         if fixed in kw:
             raise ValueError(f"{fixed} comes from the stream's header")
     kw.setdefault("batch", 1)
     rate = kw.pop("deinterlace", None)                # "frame" | "field": what an It / Ib stream needs; a progressive stream ignores it
     if rate not in (None, "frame", "field"):
         raise ValueError(f'deinterlace: None, "frame" or "field", got {rate!r}')
+    ivtc = kw.pop("ivtc", None)                       # "match" | "decimate": an It / Ib stream that carries film
+    if ivtc not in (None, "match", "decimate"):
+        raise ValueError(f'ivtc: None, "match" or "decimate", got {ivtc!r}')
+    if ivtc is not None and rate is not None:
+        raise ValueError("--ivtc and --deinterlace are exclusive: film carried in fields is matched, video is deinterlaced")
     if header.interlace in ("t", "b"):
-        if rate is None:
-            raise ValueError(f"y4m: an interlaced stream (I{header.interlace}) needs --deinterlace frame or field")
-        kw["interlaced"], kw["field_order"] = rate, "tff" if header.interlace == "t" else "bff"
+        if rate is None and ivtc is None:
+            raise ValueError(f"y4m: an interlaced stream (I{header.interlace}) needs --deinterlace frame or field, or --ivtc")
+        kw["telecine" if rate is None else "interlaced"] = ivtc if rate is None else rate
+        kw["field_order"] = "tff" if header.interlace == "t" else "bff"
     if kw.get("out_format") is None:
         kw["out_format"] = "i420"
     if kw["out_format"] not in OUT_FORMATS.values():
@@ -96,7 +103,8 @@ def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> i
         out_chroma = kw.get("out_chroma", kw.get("chroma", "420"))
         writer.write_header(header.for_output(out_w, out_h, siting=vs.out_chroma_siting, bits=10 if kw["out_format"] == "i010" else 8,
                                               sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw["full_range"], chroma=out_chroma,
-                                              progressive="interlaced" in kw, double_rate=kw.get("interlaced") == "field"))
+                                              progressive="interlaced" in kw or "telecine" in kw, double_rate=kw.get("interlaced") == "field",
+                                              film_rate=kw.get("telecine") == "decimate"))
 
         def deliver(frames):
             nonlocal done
@@ -110,6 +118,8 @@ def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> i
             deliver(vs.push(frame))
         deliver(vs.end())
     due = reader.frames * (2 if kw.get("interlaced") == "field" else 1)
+    if kw.get("telecine") is not None:
+        due = _telecine.deliverable(kw["telecine"], reader.frames, True)
     if done != due:
         raise RuntimeError(f"{reader.frames} frames read, {done} delivered where {due} were due")
     seconds = time.perf_counter() - t0
@@ -167,6 +177,9 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--ensemble", type=int, choices=(1, 2, 4, 8), default=1)
     ap.add_argument("--deinterlace", choices=("frame", "field"), default=None,
                     help="take an interlaced (It / Ib) stream: one progressive frame per frame, or per field (twice the frames and the rate)")
+    ap.add_argument("--ivtc", action="store_true",
+                    help="take an It / Ib stream that carries film under 3:2 pulldown: match the fields and drop the repeat (4/5 of the frames and the rate; needs --batch 2 or more)")
+    ap.add_argument("--no-decimate", action="store_true", help="with --ivtc: match the fields and keep every frame")
     ap.add_argument("--tile", type=_tile, default=None, metavar="TH,TW[,PAD[,BATCH]]")
     return ap
 
@@ -179,7 +192,9 @@ def main(argv=None) -> int:
     eng = None
     try:
         reader = _y4m.Y4MReader(fin, depths=(8, 10), chromas=_y4m.CHROMAS if a.chroma == "any" else (a.chroma,),
-                                   interlaced=a.deinterlace is not None)
+                                   interlaced=a.deinterlace is not None or a.ivtc)
+        if a.no_decimate and not a.ivtc:
+            raise ValueError("--no-decimate goes with --ivtc")
         from . import checkpoint, synth
         from .engine import PFNLEngine
         from .spec import PFNLGeometry
@@ -197,7 +212,8 @@ def main(argv=None) -> int:
             eng.set_option("precision", a.precision)
         upscale(reader, _y4m.Y4MWriter(fout), eng.open_stream, tile=a.tile, batch=a.batch, scene_cut=a.scene_cut, matrix=a.matrix,
                 full_range=a.full_range, out_format=OUT_FORMATS[a.bits], out_size=a.out_size, fit=a.fit, out_chroma_siting=a.out_siting,
-                ensemble=a.ensemble, out_chroma=a.out_chroma, deinterlace=a.deinterlace)
+                ensemble=a.ensemble, out_chroma=a.out_chroma, deinterlace=a.deinterlace,
+                ivtc=("match" if a.no_decimate else "decimate") if a.ivtc else None)
         fout.flush()
     except (ValueError, PFNLHipError) as e:
         print(f"pfnl_amd.upscale: {e}", file=sys.stderr)

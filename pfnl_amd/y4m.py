@@ -25,6 +25,7 @@ Out of scope: mono, 4:1:1 and alpha, 12 and 16 bits, interlaced streams, per-fra
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field, replace
 from typing import Iterator, Optional, Tuple
 
@@ -168,14 +169,19 @@ class Y4MHeader:
 
     def for_output(self, width: int, height: int, siting: Optional[str] = None, bits: int = 8, sar: Optional[Tuple[int, int]] = None,
                    full_range: Optional[bool] = None, chroma: Optional[str] = None, progressive: bool = False,
-                   double_rate: bool = False) -> "Y4MHeader":
+                   double_rate: bool = False, film_rate: bool = False) -> "Y4MHeader":
         """The header of the stream made from this one: the new raster, siting, depth and aspect; ``F``, ``I`` and the extensions pass
         through - but ``XYSCSS``, which restates the chroma format and becomes ``XYSCSS=420P10`` at 10 bits (``422`` / ``444`` /
         ``422P10`` / ``444P10`` for those tags), and the range token where ``full_range`` says otherwise than the stream.  ``chroma`` None:
         this stream's.  ``progressive``: the frames have been deinterlaced, ``I`` becomes ``Ip``; ``double_rate``: at field rate, ``F`` doubles
-        its numerator."""
+        its numerator; ``film_rate``: one frame in five has been dropped, ``F`` becomes 4 / 5 of its rational in lowest terms (30000:1001 ->
+        24000:1001)."""
         chroma = self.chroma if chroma is None else chroma
         rate = self.rate
+        if film_rate and rate is not None:
+            num, den = _ratio(rate, "F")
+            g = math.gcd(4 * num, 5 * den)
+            rate = f"{4 * num // g}:{5 * den // g}"
         if double_rate and rate is not None:
             num, den = _ratio(rate, "F")
             rate = f"{2 * num}:{den}"
@@ -220,7 +226,7 @@ class Y4MReader:
     """``Y4MReader(fileobj)`` reads the header at once (``.header``); iterating yields every frame as a ``(H*3//2, W)`` uint8 array -
     little-endian uint16 for a ``C420p10`` stream, which ``depths=(8, 10)`` lets through; ``(2*H, W)`` / ``(3*H, W)`` for a ``C422`` /
     ``C444`` stream, which ``chromas=("420", "422", "444")`` lets through.  ``interlaced=True`` lets ``It`` / ``Ib`` streams through - their frames are woven, and
-    ``header.interlace`` says which field comes first."""
+    ``header.interlace`` says which field comes first; so are the frames of film under 3:2 pulldown (pfnl_amd/telecine.py)."""
 
     def __init__(self, fileobj, depths: Tuple[int, ...] = (8,), chromas: Tuple[str, ...] = ("420",), interlaced: bool = False):
         self._f = fileobj
