@@ -664,6 +664,43 @@ typedef struct pfnl_telecine_params {
 int pfnl_stream_telecine(pfnl_stream* s, int mode, int field_order, const pfnl_telecine_params* params /* NULL: the defaults */);
 int pfnl_stream_telecine_stats(pfnl_stream* s, long long out[5]);
 int pfnl_telecine_deliverable(int mode, long long pushed, int ended, long long* frames);
+/* COLOUR (additions to version 4; a session that does not call pfnl_stream_colour issues the launches it always issued).  SD material is
+ * BT.601 in matrix and SMPTE-C or EBU in primaries; an HD stream is read as BT.709 in both.  pfnl_stream_format gives the session one
+ * matrix and one range for both edges; with this setting each edge has its own colour description and the conversion between the two
+ * runs on the device.  The rule is stated once on the host, pfnl_amd/colour.py; its integers once in pfnl_amd/csrc/colour_geom.h:
+ *   matrix and range per side: the coefficients of YUV <-> RGB (pfnl_amd/yuv.py) are arguments of the two conversion launches; the decode
+ *     reads the input side's, the output route's last stage the output side's.  No kernel and no memory depend on them.  On an RGB side
+ *     they are accepted and ignored: RGB is full range.
+ *   primaries per side (PFNL_PRIM_*; white D65 for all three, no chromatic adaptation): where the two ids differ, stage 0 of the output
+ *     route - the launch that reads every fp32 result and writes every sample - is the colour kernel (pfnl_amd/csrc/colour.hip) in place
+ *     of the plain quantisation: the same levels, rintf(clip(x TOP, 0, TOP)) with NaN -> 0, then per pixel
+ *       out = E[clip((M . D[level] + 2^13) >> 14, 0, 65535)]
+ *     with D[v] = floor(65535 f^-1(v / TOP) + 0.5), E[l] = floor(TOP f(l / 65535) + 0.5), f the BT.709 OETF, which all three systems share,
+ *     and M = pfnl_colour_matrix(in, out): RGB -> XYZ of the input's primaries, XYZ -> RGB of the output's, in exact rationals, times
+ *     2^14, rounded half away from zero, the diagonal taking each row's residual.  Rows sum to 2^14 and E[D[v]] = v, so greys pass
+ *     untouched.  Everything behind stage 0 - resize, placement and its fill colour, YUV at every chroma format, siting and depth,
+ *     packing - is untouched and sees RGB in the output's colours; a batch recomputed behind the range fence takes the same launch.
+ *     The kernel keeps D and E in LDS (E as the code at the start of each 64-wide bucket of l and the thresholds: 3 KB at 8 bits, 6 KB
+ *     at 10); they are uploaded once per device and process, by the first setting whose ids differ (PFNL_ERR_NOMEM: the setting is
+ *     unchanged) or the first call of an op hook below, and are nobody's to free.
+ *   pfnl_stream_colour: in / out NULL: that side keeps what it has.  pfnl_stream_format keeps its meaning and its domain: it sets matrix
+ *     and range of both sides and leaves the primaries alone; each of the two calls replaces the matrix and range the other set.
+ *     Accepted only while no frame of the current sequence has been pushed (else PFNL_ERR_STATE); it survives pfnl_stream_reset; a
+ *     matrix other than 0 | 1, a full_range other than 0 | 1 and primaries outside the enum are PFNL_ERR_INVALID with the setting
+ *     unchanged.
+ *   pfnl_colour_matrix / pfnl_colour_tables (bits 8 | 10; decode [2^bits], encode [65536]): the integers themselves; they need no device
+ *     and refuse bad arguments with PFNL_ERR_INVALID before anything else.
+ * The op hooks pfnl_op_quantise_colour_* below are the kernel on its own.
+ * Out of scope: BT.2020, PQ / HLG and tone mapping, chromatic adaptation, per-frame colour changes. */
+enum { PFNL_PRIM_BT709 = 0, PFNL_PRIM_BT601_525 = 1, PFNL_PRIM_BT601_625 = 2 };
+typedef struct pfnl_colour {
+    int matrix;
+    int full_range;
+    int primaries;
+} pfnl_colour;
+int pfnl_stream_colour(pfnl_stream* s, const pfnl_colour* in, const pfnl_colour* out /* NULL: that side keeps what it has */);
+int pfnl_colour_matrix(int src, int dst, int32_t out[9]);
+int pfnl_colour_tables(int bits, uint16_t* decode, uint16_t* encode /* [65536] */);
 /* SELF-ENSEMBLE in a session (additions to version 4; a session that does not call this issues the launches it always issued).  With
  * n in {2, 4, 8} the one forward of every batch is pfnl_forward_ensemble(..., n, ...) (SELF-ENSEMBLE above); gather, quantisation, the
  * output route, scenes and the replay behind the range fence are untouched, and a recomputed batch goes through the same call.  n = 1 is
@@ -976,6 +1013,12 @@ int pfnl_op_resize_u8(const uint8_t* in, int n, int H, int W, int oH, int oW, ui
  * synchronises as that hook does.  NULL, odd or non-positive sizes, n < 1, an unknown fmt / matrix / full_range (fmt: the 8-bit formats
  * and PFNL_PIX_RGB10 among them) and sizes outside pfnl_resize_taps' limits: PFNL_ERR_INVALID before any HIP call. */
 int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream);
+/* Stage 0 with a change of primaries (COLOUR above; pfnl_amd/csrc/colour.hip): sr [pixels][3] fp32 -> out [pixels][3] samples, sample for
+ * sample pfnl_amd/colour.py convert(quantise(sr), src, dst); src == dst is pfnl_op_quantise_u8 / _u10 itself.  pixels a positive multiple
+ * of 4, sr 16-byte and out 8-byte aligned, src and dst PFNL_PRIM_*: PFNL_ERR_INVALID before any HIP call otherwise.  Asynchronous on
+ * `stream`, as pfnl_op_quantise_u10 is; the first call on a device uploads its tables (a blocking copy). */
+int pfnl_op_quantise_colour_u8(const float* sr, uint8_t* out, size_t pixels, int src, int dst, void* stream);
+int pfnl_op_quantise_colour_u10(const float* sr, uint16_t* out, size_t pixels, int src, int dst, void* stream);
 int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, void* stream);
 int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream);
 /* The four conversion hooks above with the chroma siting named (SITING: PFNL_SITING_*), ahead of stream; the plain hooks are these with

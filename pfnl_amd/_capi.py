@@ -51,6 +51,11 @@ class pfnl_telecine_params(C.Structure):
     _fields_ = [("threshold", C.c_int), ("post", C.c_int), ("comb_limit", C.c_longlong)]
 
 
+class pfnl_colour(C.Structure):
+    """The colour of one edge of a session (include/pfnl_hip.h COLOUR; pfnl_amd/colour.py): matrix 0 | 1, full_range 0 | 1, PFNL_PRIM_*."""
+    _fields_ = [("matrix", C.c_int), ("full_range", C.c_int), ("primaries", C.c_int)]
+
+
 # name -> (restype, argtypes); exactly the symbols include/pfnl_hip.h declares
 _vp, _i, _fp = C.c_void_p, C.c_int, C.POINTER(C.c_float)
 _i32p, _tp = C.POINTER(C.c_int32), C.POINTER(pfnl_tiling)
@@ -128,6 +133,11 @@ SIGNATURES = {
     "pfnl_op_gather_windows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "pfnl_op_quantise_u8": (_i, [_vp, _vp, C.c_size_t, _vp]),
     "pfnl_op_quantise_u10": (_i, [_vp, _vp, C.c_size_t, _vp]),
+    "pfnl_op_quantise_colour_u8": (_i, [_vp, _vp, C.c_size_t, _i, _i, _vp]),
+    "pfnl_op_quantise_colour_u10": (_i, [_vp, _vp, C.c_size_t, _i, _i, _vp]),
+    "pfnl_stream_colour": (_i, [_vp, C.POINTER(pfnl_colour), C.POINTER(pfnl_colour)]),
+    "pfnl_colour_matrix": (_i, [_i, _i, _i32p]),
+    "pfnl_colour_tables": (_i, [_i, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "pfnl_op_gather_windows_u8": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_stream_open": (_i, [_vp, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "pfnl_stream_push": (_i, [_vp, _vp, _i]),

@@ -6,6 +6,7 @@
 
 #include "../../include/pfnl_hip.h"
 #include "capi_internal.h"
+#include "colour_geom.h"
 #include "common.h"
 #include "conv_bf16.h"
 #include "conv_small.h"
@@ -1030,6 +1031,47 @@ int pfnl_op_quantise_u10(const float* sr, uint16_t* out, size_t n, void* stream)
         return fail(PFNL_ERR_INVALID, "quantise_u10: sr must be 16-byte aligned and out 8-byte aligned");
     HIPCHK(pfnl::launch_quantise(sr, out, n, (hipStream_t)stream));
     return 0;
+}
+
+int pfnl_colour_matrix(int src, int dst, int32_t out[9]) {
+    if (!out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    pfnl::ColourMatrix m;
+    if (!pfnl::colour_matrix(src, dst, &m)) return fail(PFNL_ERR_INVALID, "colour: primaries PFNL_PRIM_BT709, PFNL_PRIM_BT601_525 or PFNL_PRIM_BT601_625");
+    for (int k = 0; k < 9; ++k) out[k] = m.m[k];
+    return 0;
+}
+
+int pfnl_colour_tables(int bits, uint16_t* decode, uint16_t* encode) {
+    if (!decode || !encode) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!pfnl::colour_tables(bits, decode, encode)) return fail(PFNL_ERR_INVALID, "colour: bits 8 or 10");
+    return 0;
+}
+
+// both depths: refused before any HIP call; then the one launch, on the device's tables
+extern "C++" template <typename T>
+static int quantise_colour_op(const float* sr, T* out, size_t pixels, int src, int dst, void* stream) {
+    if (!sr || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!pixels || pixels % 4) return fail(PFNL_ERR_INVALID, "quantise_colour: the pixel count must be a positive multiple of 4");
+    if (reinterpret_cast<uintptr_t>(sr) % 16 || reinterpret_cast<uintptr_t>(out) % 8)
+        return fail(PFNL_ERR_INVALID, "quantise_colour: sr must be 16-byte aligned and out 8-byte aligned");
+    pfnl::ColourMatrix m;
+    if (!pfnl::colour_matrix(src, dst, &m)) return fail(PFNL_ERR_INVALID, "quantise_colour: primaries PFNL_PRIM_BT709, PFNL_PRIM_BT601_525 or PFNL_PRIM_BT601_625");
+    if (src == dst) {                                 // no conversion: the plain stage 0
+        HIPCHK(pfnl::launch_quantise(sr, out, 3 * pixels, (hipStream_t)stream));
+        return 0;
+    }
+    const uint16_t *tab8 = nullptr, *tab10 = nullptr;
+    HIPCHK(pfnl::colour_device_tables(&tab8, &tab10));
+    HIPCHK(pfnl::launch_quantise_colour(sr, out, pixels, sizeof(T) == 2 ? tab10 : tab8, m, (hipStream_t)stream));
+    return 0;
+}
+
+int pfnl_op_quantise_colour_u8(const float* sr, uint8_t* out, size_t pixels, int src, int dst, void* stream) {
+    return quantise_colour_op(sr, out, pixels, src, dst, stream);
+}
+
+int pfnl_op_quantise_colour_u10(const float* sr, uint16_t* out, size_t pixels, int src, int dst, void* stream) {
+    return quantise_colour_op(sr, out, pixels, src, dst, stream);
 }
 
 int pfnl_op_rgb_to_yuv420_u10(const uint16_t* rgb, int fmt, int matrix, int full_range, int n, int H, int W, uint16_t* yuv, void* stream) {

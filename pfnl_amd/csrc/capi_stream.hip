@@ -4,7 +4,8 @@
 // _run_sequence_on_device) - clamped windows, batching, quantisation, the range flag and the recomputation on the strict kernels - lives
 // here, behind pfnl_forward's own interface: the session calls pfnl_forward / pfnl_get_option / pfnl_set_option / pfnl_range_flag like
 // any other caller and knows nothing of the handle's layout (capi_internal.h, pfnl_handle_view).
-// The output side is one route (stream_route.h: quantise -> resize / place -> YUV, at 1 or 2 bytes per sample) and one slot per stage: the
+// The output side is one route (stream_route.h: quantise - with the change of primaries in it where the two edges' differ, colour.hip -
+// -> resize / place -> YUV, at 1 or 2 bytes per sample) and one slot per stage: the
 // setters validate through that header and hand their candidate to apply_setting, the only place that allocates or frees a slot
 // after open; enqueue and pop_frame read the stored route.
 // The input side is one route as well (stream_route.h InRoute: the pushed surface, its tight frame, the staging frame, the decode kind),
@@ -17,6 +18,7 @@
 
 #include "../../include/pfnl_hip.h"
 #include "capi_internal.h"
+#include "colour_geom.h"
 #include "common.h"
 #include "field_geom.h"
 #include "stream_route.h"
@@ -39,15 +41,23 @@ struct StageSlot {
     size_t cap = 0;                                   // bytes of each
 };
 
-// What the setters set and both routes follow (pfnl_stream_format, _input_depth, _chroma_format, _packing): in_fmt / out_fmt name the
+// The colour of one edge (pfnl_stream_colour; pfnl_stream_format sets matrix and range of both): the YUV coefficients of its matrix and
+// range at both depths - an RGB edge reads neither - and its primaries.
+struct SideColour {
+    pfnl::YuvCoef coef{};                             // 8 bits: an 8-bit input, NV12 / I420 out
+    pfnl::YuvCoef coef10{};                           // 10 bits: an input depth of 10, P010 / I010 out
+    int prim = PFNL_PRIM_BT709;
+};
+
+// What the setters set and both routes follow (pfnl_stream_format, _colour, _input_depth, _chroma_format, _packing): in_fmt / out_fmt name the
 // layout, the depth the pushed sample, the chroma formats the subsampling of a YUV edge, a packing an edge as one plane of interleaved samples.
 struct Setting {
     int in_fmt = PFNL_PIX_RGB24, out_fmt = PFNL_PIX_RGB24;
     int in_depth = 8;                                 // 8, or 10: pushed samples, ring and staging frame are uint16
     int in_chroma = PFNL_CHROMA_420, out_chroma = PFNL_CHROMA_420;
     int in_pack = PFNL_PACK_NONE, out_pack = PFNL_PACK_NONE;
-    pfnl::YuvCoef coef{};                             // 8 bits: the input side, and the output side of NV12 / I420
-    pfnl::YuvCoef coef10{};                           // 10 bits: the output side of P010 / I010, the input side at an input depth of 10
+    SideColour cin, cout;                             // the decode reads the input's coefficients, stage 2 the output's
+    pfnl::ColourMatrix gamut{};                       // cin.prim -> cout.prim: stage 0 converts exactly when the two differ
 };
 
 }  // namespace
@@ -93,6 +103,7 @@ struct pfnl_stream {
     size_t yin_cap = 0;                               // its bytes
     pfnl::PlacePlan rplan;                            // stage 1: a rectangle of the raster on a canvas, the whole onto the whole for a plain size; cH = 0: off
     int32_t* rtab = nullptr;                          // rplan.r.blob on the device
+    const uint16_t* ctab[2] = {nullptr, nullptr};     // the device's colour tables at 8 | 10 bits (colour_device_tables: not the session's to free)
     pfnl::OutRoute route{};
     pfnl::InRoute in{};                               // the pushed frame of `set` at H x W: in.ring_bytes is one LR frame as the ring holds it
     StageSlot slot[pfnl::ROUTE_STAGES];
@@ -136,9 +147,12 @@ int run_route(pfnl_stream* s, const Batch& b) {
     constexpr bool ten = sizeof(T) == 2;
     const pfnl::OutRoute& r = s->route;
     const Setting& c = s->set;
-    const pfnl::YuvCoef& coef = ten ? c.coef10 : c.coef;
+    const pfnl::YuvCoef& coef = ten ? c.cout.coef10 : c.cout.coef;
     const auto slot = [&](int k) { return reinterpret_cast<T*>(s->slot[k].buf[b.slot]); };
-    HIPCHK(pfnl::launch_quantise(s->sr, slot(0), (size_t)b.count * s->sr_bytes, s->s));
+    if (c.cin.prim != c.cout.prim)                    // the same levels, in the output's primaries: everything behind sees output-colour RGB
+        HIPCHK(pfnl::launch_quantise_colour(s->sr, slot(0), (size_t)b.count * (s->sr_bytes / 3), s->ctab[ten ? 1 : 0], c.gamut, s->s));
+    else
+        HIPCHK(pfnl::launch_quantise(s->sr, slot(0), (size_t)b.count * s->sr_bytes, s->s));
     if (r.runs[1]) {                                  // one launch writes the whole canvas, the fill colour included (a plain size has none)
         const auto sample = [](uint8_t v) { return (T)(ten ? pfnl::fill_u10(v) : v); };
         const T fill[3] = {sample(s->rplan.fill[0]), sample(s->rplan.fill[1]), sample(s->rplan.fill[2])};
@@ -404,7 +418,7 @@ pfnl_surface tight_surface(const pfnl_stream* s, const uint8_t* base) {
 int decode_surface(pfnl_stream* s, const pfnl_surface& sf, int rows, uint8_t* dst, bool from_host, hipStream_t on) {
     const Setting& c = s->set;
     const bool ten = s->in.sample_bytes == 2, nv12 = c.in_fmt == PFNL_PIX_NV12;
-    const pfnl::YuvCoef& coef = ten ? c.coef10 : c.coef;
+    const pfnl::YuvCoef& coef = ten ? c.cin.coef10 : c.cin.coef;
     const pfnl::YuvPlanes yuv = pfnl_internal_yuv_planes(sf, nv12);   // (read by the two YUV kinds alone)
     uint16_t* const dst10 = reinterpret_cast<uint16_t*>(dst);
     const size_t row = s->in.geom.plane[0].row_bytes;
@@ -973,10 +987,40 @@ int pfnl_stream_format(pfnl_stream* s, int in_fmt, int out_fmt, int matrix, int 
     c.in_fmt = in_fmt;
     c.out_fmt = out_fmt;
     if (int e = candidate_refused(s, c, s->route.out_h, s->route.out_w)) return e;
-    if (!pfnl::yuv_coefficients(8, matrix, full_range, &c.coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &c.coef10))
+    if (!pfnl::yuv_coefficients(8, matrix, full_range, &c.cin.coef) || !pfnl::yuv_coefficients(10, matrix, full_range, &c.cin.coef10))
         return fail(PFNL_ERR_INVALID, "format: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1");
+    c.cout.coef = c.cin.coef;                         // both sides' matrix and range, replacing what pfnl_stream_colour set; the primaries stay
+    c.cout.coef10 = c.cin.coef10;
     if (started(s)) return fail(PFNL_ERR_STATE, "the format is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
     return apply_setting(s, c, nullptr, "format staging allocation failed");
+}
+
+// The colour of each edge: matrix and range are the coefficients of that edge's YUV conversion and replace what pfnl_stream_format set for
+// it; where the primaries differ, stage 0 converts (colour.hip) on the device's tables, which the first such setting finds or uploads.  No
+// route and no slot depends on it.
+int pfnl_stream_colour(pfnl_stream* s, const pfnl_colour* in, const pfnl_colour* out) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    Setting c = s->set;
+    const pfnl_colour* const given[2] = {in, out};
+    SideColour* const side[2] = {&c.cin, &c.cout};
+    for (int k = 0; k < 2; ++k) {
+        if (!given[k]) continue;                      // that side keeps what it has
+        if (!pfnl::yuv_coefficients(8, given[k]->matrix, given[k]->full_range, &side[k]->coef) ||
+            !pfnl::yuv_coefficients(10, given[k]->matrix, given[k]->full_range, &side[k]->coef10) || !pfnl::is_primaries(given[k]->primaries))
+            return fail(PFNL_ERR_INVALID, "colour: matrix 0 (BT.601) or 1 (BT.709), full_range 0 or 1, primaries PFNL_PRIM_BT709, PFNL_PRIM_BT601_525 or PFNL_PRIM_BT601_625");
+        side[k]->prim = given[k]->primaries;
+    }
+    (void)pfnl::colour_matrix(c.cin.prim, c.cout.prim, &c.gamut);
+    if (started(s)) return fail(PFNL_ERR_STATE, "the colour is set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (c.cin.prim != c.cout.prim && !s->ctab[0]) {
+        HIPCHK(hipSetDevice(s->device));
+        if (pfnl::colour_device_tables(&s->ctab[0], &s->ctab[1]) != hipSuccess) {
+            (void)hipGetLastError();
+            s->ctab[0] = s->ctab[1] = nullptr;
+            return fail(PFNL_ERR_NOMEM, "colour table allocation failed");
+        }
+    }
+    return apply_setting(s, c, nullptr, "colour setting failed");
 }
 
 // The depth of the pushed samples: in_fmt keeps naming the layout.  At 10 the ring and the staging frame hold uint16 samples; decode, scene

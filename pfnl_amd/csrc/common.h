@@ -183,6 +183,12 @@ hipError_t launch_quantise(const float* sr, uint16_t* out, size_t n, hipStream_t
 // window w slot t = frame clamp(first + w + t - T/2, 0, last); frame_bytes % 4 == 0 (stream.hip)
 hipError_t launch_gather_windows_u8(const uint8_t* ring, float* win, int cap, long long last, long long first, int count, int T,
                                     size_t frame_bytes, hipStream_t s);
+// stage 0 with a change of primaries in it (colour.hip; the rule: pfnl_amd/colour.py): the same levels, then D -> m -> E per pixel; tab: the
+// device copy of colour_geom.h colour_blob of the depth (colour_device_tables); pixels % 4 == 0, sr 16-byte, out 8-byte aligned
+struct ColourMatrix;
+hipError_t colour_device_tables(const uint16_t** tab8, const uint16_t** tab10);   // of the current device: uploaded once per process, never freed
+hipError_t launch_quantise_colour(const float* sr, uint8_t* out, size_t pixels, const uint16_t* tab, const ColourMatrix& m, hipStream_t s);
+hipError_t launch_quantise_colour(const float* sr, uint16_t* out, size_t pixels, const uint16_t* tab, const ColourMatrix& m, hipStream_t s);
 // ---- scenes of the streaming session (stream.hip; the rule: pfnl_amd/scene.py) ----
 // What the block that completes a frame's sum of absolute luma differences does with it: sad[slot] = the sum and, where scene_first is
 // given, scene_first[slot] = (force || (detect && min(sum, |sum - sad[prev]|) >= thr_sum)) ? frame : scene_first[prev].

@@ -267,7 +267,8 @@ class PFNLEngine:
     def open_stream(self, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                     full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
                     chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
-                 out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, ensemble=1):
+                 out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, out_matrix=None,
+                    out_full_range=None, primaries="bt709", out_primaries=None, ensemble=1):
         """A streaming session on this engine (pfnl_stream_open; pfnl_amd/stream.py VideoStream): uint8 LR frames [H,W,3] pushed one at
         a time, uint8 SR frames popped in order, ``batch`` windows per forward.  One open session per engine.  ``scene_cut``: None,
         "manual" or a detector threshold - windows that stay inside a scene (VideoStream).  ``pixel_format`` / ``out_format`` "nv12" or "i420":
@@ -282,11 +283,13 @@ class PFNLEngine:
         ``out_chroma`` None: the input's.  ``packing`` / ``out_packing``: None, or a name of pfnl_amd/packed.py PACKINGS - that side as one plane
         of interleaved samples (yuyv422, v210, bgra, ...; VideoStream).  ``interlaced`` None | "frame" | "field", ``field_order`` "tff" | "bff": woven
         frames in, progressive frames into the ring at frame or field rate (pfnl_amd/deinterlace.py; VideoStream).  ``telecine`` None | "match" |
-        "decimate" with ``telecine_params``: film under 3:2 pulldown in, its frames into the ring (pfnl_amd/telecine.py; VideoStream)."""
+        "decimate" with ``telecine_params``: film under 3:2 pulldown in, its frames into the ring (pfnl_amd/telecine.py; VideoStream).
+        ``out_matrix`` / ``out_full_range`` / ``primaries`` / ``out_primaries`` (None: the input's): a colour description per side, the
+        primaries converted on the device where they differ (pfnl_amd/colour.py; VideoStream)."""
         from .stream import VideoStream
         return VideoStream(self, H, W, batch, scene_cut, pixel_format, out_format, matrix, full_range, out_size, crop, fit, place, sar, fill,
                            chroma_siting, out_chroma_siting, in_depth, chroma, out_chroma, packing, out_packing, interlaced, field_order,
-                           telecine, telecine_params, ensemble)
+                           telecine, telecine_params, out_matrix, out_full_range, primaries, out_primaries, ensemble)
 
     def sync(self) -> None:
         """Synchronise the engine's streams; raises if a device-pointer forward left the f16-pipe kernels' range

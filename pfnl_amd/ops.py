@@ -737,6 +737,25 @@ def quantise_u10(sr, out=None):
     return out
 
 
+def quantise_colour(x, src: str, dst: str, bits: int = 8, out=None):
+    """[..., 3] float32 (cuda) -> the levels of quantise_u8 / quantise_u10 taken from the primaries ``src`` to ``dst``, uint8 or uint16 of
+    the same shape: sample for sample pfnl_amd/colour.py ``convert(quantise(x), src, dst, bits)`` (pfnl_op_quantise_colour_u8 / _u10: stage
+    0 of a session whose two sides differ in primaries).  A pixel count that is a multiple of 4; ``src == dst`` is the plain quantise."""
+    import torch
+    from . import colour as _colour
+    lib = _capi.load_library()
+    ids = _colour.primaries_id(src), _colour.primaries_id(dst)
+    if isinstance(bits, bool) or bits not in (8, 10):
+        raise ValueError(f"bits: 8 or 10, got {bits!r}")
+    _req(x, "x")
+    if x.dim() < 1 or x.shape[-1] != 3:
+        raise ValueError("quantise_colour expects [..., 3]")
+    out = _out(out, x.shape, torch.uint8 if bits == 8 else torch.uint16, x.device)
+    hook = lib.pfnl_op_quantise_colour_u8 if bits == 8 else lib.pfnl_op_quantise_colour_u10
+    _capi.check(hook(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), x.numel() // 3, ids[0], ids[1], _stream(x)))
+    return out
+
+
 def rgb_to_yuv420_u10(frames, fmt: str, matrix: str = "bt709", full_range=False, out=None, siting="left"):
     """[n,H,W,3] (or [H,W,3]) uint16 (cuda) with values 0 .. 1023 -> [n, H*3/2, W] uint16: tightly packed P010 / I010 frames, sample for
     sample pfnl_amd/depth10.py from_rgb10 (pfnl_op_rgb_to_yuv420_u10: the streaming session's 10-bit output edge).  H, W even; any

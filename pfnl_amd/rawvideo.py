@@ -5,7 +5,9 @@
 
 A raw stream is frames of ``packed.frame_bytes`` one behind the other and nothing else (pfnl_amd/packed.py; what ``ffmpeg -f rawvideo
 -pix_fmt NAME -s WxH`` speaks - its names are this module's: bgr24, rgba, bgra, yuyv422, uyvy422, x2rgb10le = x2rgb10, x2bgr10le = x2bgr10,
-y210le = y210; v210 comes from ``-c:v v210``), so format, size, matrix, range and siting are the command line's.  ``RawReader`` /
+y210le = y210; v210 comes from ``-c:v v210``), so format, size, matrix, range and siting are the command line's.  A colour description per side (pfnl_amd/colour.py):
+``--primaries``, ``--out-matrix``, ``--out-range``, ``--out-primaries``, as pfnl_amd/upscale.py takes them - a DVD's capture to HD is
+``--matrix bt601 --primaries auto --out-matrix auto --out-primaries auto``.  ``RawReader`` /
 ``RawWriter`` move the frames, ``session_keywords`` turns two packing names into ``open_stream``'s keywords - each side's family, depth and
 chroma format follow from its packing -, ``run()`` is the loop (it mirrors pfnl_amd/upscale.py ``upscale``), ``main()`` the command line;
 nothing here computes.
@@ -18,7 +20,7 @@ import time
 
 import numpy as np
 
-from . import packed as _packed, telecine as _telecine
+from . import colour as _colour, packed as _packed, telecine as _telecine
 
 
 class RawReader:
@@ -96,8 +98,14 @@ def run(reader, writer, open_stream, out_format=None, log=None, **session_kw) ->
     """Every frame of ``reader`` (RawReader) through a session, into ``writer`` (RawWriter); returns the frame count.  ``open_stream`` is
     ``PFNLEngine.open_stream`` or anything with its keywords; ``session_kw`` as ``session_keywords`` takes them.  Frames are written in
     index order as ``push`` and ``end`` return them - with ``interlaced="field"`` (and ``field_order``: a raw pipe has no header to say) two per
-    frame read.  One line with frames, seconds and fps goes to ``log``."""
+    frame read.  ``out_matrix``, ``out_range``, ``primaries``, ``out_primaries`` (and ``scale``, 4 unless given) as pfnl_amd/upscale.py
+    ``session_keywords`` takes them: each reaches the session only where it is named.  One line with frames, seconds and fps goes to ``log``."""
+    session_kw = dict(session_kw)
+    named = {k: session_kw.pop(k, None) for k in ("out_matrix", "out_range", "primaries", "out_primaries")}
+    scale = session_kw.pop("scale", 4)
     kw = session_keywords(reader.name, out_format, **session_kw)
+    out_size = kw.get("out_size")
+    kw.update(_colour.side_keywords(reader.height, out_size[0] if out_size is not None else scale * reader.height, kw.get("matrix", "bt709"), **named))
     batch = kw.pop("batch")
     t0 = time.perf_counter()
     done = 0
@@ -147,6 +155,12 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--num-block", type=int, default=20)
     ap.add_argument("--matrix", choices=("bt601", "bt709"), default="bt709")
     ap.add_argument("--full-range", action="store_true")
+    ap.add_argument("--out-matrix", choices=("auto", "bt601", "bt709"), default=None, help="the output's matrix (default: the input's); auto: bt709 above 576 delivered lines")
+    ap.add_argument("--out-range", choices=("limited", "full"), default=None, help="the output's range (default: the input's)")
+    ap.add_argument("--primaries", choices=("auto",) + _colour.PRIMARIES, default=None,
+                    help="the input's primaries (default: bt709); auto: bt601-525 at 480 / 486 lines, bt601-625 at 576, else bt709")
+    ap.add_argument("--out-primaries", choices=("auto",) + _colour.PRIMARIES, default=None,
+                    help="the output's primaries (default: the input's), converted on the device; auto: bt709 above 576 delivered lines")
     ap.add_argument("--siting", choices=("left", "center", "topleft"), default="left", help="where the 4:2:2 chroma samples sit, in and out")
     ap.add_argument("--batch", type=int, default=1, help="windows per forward")
     ap.add_argument("--out-size", type=_size, default=None, metavar="HxW")
@@ -185,7 +199,9 @@ def main(argv=None) -> int:
                 raise ValueError("--ivtc and --interlaced are exclusive: film carried in fields is matched, video is deinterlaced")
             woven = {"telecine": a.ivtc, "field_order": a.field_order}
         run(reader, RawWriter(fout), eng.open_stream, out_format=a.out_format, batch=a.batch, matrix=a.matrix, full_range=a.full_range,
-            chroma_siting=a.siting, out_size=a.out_size, **woven)
+            chroma_siting=a.siting, out_size=a.out_size, scale=geom.scale, **woven,
+            **{k: v for k, v in (("out_matrix", a.out_matrix), ("out_range", a.out_range), ("primaries", a.primaries),
+                                 ("out_primaries", a.out_primaries)) if v is not None})
         fout.flush()
     except (ValueError, PFNLHipError) as e:
         print(f"pfnl_amd.rawvideo: {e}", file=sys.stderr)

@@ -64,6 +64,11 @@ carried at 29.97 frames a second, re-pairs their fields on the device ahead of t
 the one frame in five that repeats a picture: indices count film frames, and a cycle's four frames come together (``batch`` at least 2).
 ``telecine="match"`` keeps every frame.  Exclusive with ``interlaced``.
 
+Colour per side (off by default): ``open_stream(480, 720, batch, pixel_format="i420", matrix="bt601", primaries="bt601-525",
+out_size=(1080, 1440), out_matrix="bt709", out_primaries="bt709")`` takes a DVD's frames as they are and delivers what an HD stream is
+read as: the input's matrix on the way in, the output's on the way out, and the primaries converted on the device in linear light by the
+integer rule of pfnl_amd/colour.py, in the launch that quantises the SR frames.
+
 Surfaces: ``vs.push_planes(y, cbcr)`` / ``vs.pop_planes(y, cbcr)`` take and fill a frame as a decoder or encoder holds it - one array per
 plane, each with the row pitch its strides say (pfnl_amd/surface.py), e.g. ``surface[:H, :W]`` of a pitched device allocation - in the
 session's formats; a device NV12 / I420 surface is converted where it lies, and only the samples of a destination are written.
@@ -105,6 +110,27 @@ def format_arguments(pixel_format="rgb24", out_format=None, matrix="bt709", full
     if full_range not in (False, True, 0, 1):
         raise ValueError(f"full_range: False or True, got {full_range!r}")
     return _capi.PIXEL_FORMATS[pixel_format], _capi.PIXEL_FORMATS[out_format], _capi.YUV_MATRICES[matrix], int(bool(full_range))
+
+
+def colour_arguments(matrix="bt709", full_range=False, out_matrix=None, out_full_range=None, primaries="bt709", out_primaries=None):
+    """The two sides of pfnl_stream_colour for open_stream's keywords as ``((matrix, full_range, primaries), (...))`` of C-ABI values
+    (``out_matrix`` / ``out_full_range`` / ``out_primaries`` None = the input's), or None - no call, the session as it always was - with the
+    three ``out_`` keywords None and ``primaries`` "bt709"; ValueError for anything the library would refuse.  Needs no device."""
+    from . import colour as _colour
+    for name, value in (("matrix", matrix), ("out_matrix", out_matrix)):
+        if not (value is None and name == "out_matrix") and (not isinstance(value, str) or value not in _capi.YUV_MATRICES):
+            raise ValueError(f"{name}: one of {sorted(_capi.YUV_MATRICES)}, got {value!r}")
+    for name, value in (("full_range", full_range), ("out_full_range", out_full_range)):
+        if not (value is None and name == "out_full_range") and value not in (False, True, 0, 1):
+            raise ValueError(f"{name}: False or True, got {value!r}")
+    for name, value in (("primaries", primaries), ("out_primaries", out_primaries)):
+        if not (value is None and name == "out_primaries") and (not isinstance(value, str) or value not in _colour.PRIMARIES):
+            raise ValueError(f"{name}: one of {_colour.PRIMARIES}, got {value!r}")
+    if out_matrix is None and out_full_range is None and out_primaries is None and primaries == "bt709":
+        return None
+    side = (_capi.YUV_MATRICES[matrix], int(bool(full_range)), _colour.primaries_id(primaries))
+    return side, (side[0] if out_matrix is None else _capi.YUV_MATRICES[out_matrix], side[1] if out_full_range is None else int(bool(out_full_range)),
+                  side[2] if out_primaries is None else _colour.primaries_id(out_primaries))
 
 
 IN_LAYOUTS = {"rgb24": "rgb10", "nv12": "p010", "i420": "i010"}         # what pixel_format's layout is called at an input depth of 10
@@ -374,15 +400,26 @@ class VideoStream:
     (pfnl_amd/telecine.py) and, at "decimate", one frame in five - the repeat - is dropped, so indices count film frames and a cycle's four
     frames come together; it needs a batch of at least 2.  Exclusive with ``interlaced``.  ``telecine_stats()`` counts the current sequence's frames.
 
+    ``out_matrix`` / ``out_full_range`` / ``primaries`` / ``out_primaries`` (None = the input's; primaries "bt709" | "bt601-525" |
+    "bt601-625"): the colour of each side (pfnl_amd/colour.py).  ``matrix`` and ``full_range`` then describe the input, the ``out_`` pair
+    the delivered frames; where the primaries differ the SR frames are converted on the device in linear light, in the launch that
+    quantises them, and everything behind - size, placement, ``fill``, YUV, packing - is in the output's colours.  ``vs.out_matrix``,
+    ``vs.out_full_range``, ``vs.primaries`` and ``vs.out_primaries`` are the resolved values.
+
     ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
     (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
     def __init__(self, engine, H: int, W: int, batch: int = 1, scene_cut=None, pixel_format="rgb24", out_format=None, matrix="bt709",
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
                  chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
-                 out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, ensemble=1):
+                 out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, out_matrix=None,
+                 out_full_range=None, primaries="bt709", out_primaries=None, ensemble=1):
         import torch
         self.in_depth = depth_argument(in_depth)    # (before the engine is touched, as every check of an argument)
+        col = colour_arguments(matrix, full_range, out_matrix, out_full_range, primaries, out_primaries)
+        self.out_matrix = matrix if out_matrix is None else out_matrix
+        self.out_full_range = bool(full_range if out_full_range is None else out_full_range)
+        self.primaries, self.out_primaries = primaries, primaries if out_primaries is None else out_primaries
         il = interlace_arguments(interlaced, field_order, H, pixel_format, chroma, packing)
         tc = telecine_arguments(telecine, field_order, telecine_params, H, W, pixel_format, chroma, packing, interlaced)
         self.telecine = telecine
@@ -437,6 +474,12 @@ class VideoStream:
         if fmt[0] or fmt[1]:                        # (all defaults: the session as it always was, and no call)
             try:
                 _capi.check(self._lib.pfnl_stream_format(s, *fmt))
+            except Exception:
+                self.close()
+                raise
+        if col is not None:                         # (one colour for both sides, BT.709 primaries: the session as it always was, and no
+            try:                                    # call; behind the format, which sets matrix and range of both sides)
+                _capi.check(self._lib.pfnl_stream_colour(s, C.byref(_capi.pfnl_colour(*col[0])), C.byref(_capi.pfnl_colour(*col[1]))))
             except Exception:
                 self.close()
                 raise

@@ -12,6 +12,13 @@ where ``--chroma`` names them (or ``any``) - without it such a stream exits 1 na
 the output apart from the input's; a ``C422`` stream is horizontally co-sited, so a 4:2:2 output is written with the siting "left".  Interlaced streams (``It`` / ``Ib``, what ``ffmpeg -f yuv4mpegpipe`` writes for DVD and broadcast material) are taken with
 ``--deinterlace frame|field`` - without it such a stream exits 1 naming its tag -: the frames are woven, the field order is the header's, the
 session deinterlaces on the device (pfnl_amd/deinterlace.py) and the output is ``Ip``, at field rate with twice the frames and ``F`` doubled.
+A colour description per side (pfnl_amd/colour.py): ``--primaries``, ``--out-matrix``, ``--out-range`` and ``--out-primaries``; ``auto`` takes
+480 / 486 lines as bt601-525, 576 as bt601-625 and anything else as bt709 on the way in, and on the way out BT.709 above 576 delivered
+lines, else the input's.  A DVD to HD, in the colours an HD stream is read as:
+
+    ffmpeg -i dvd.vob -f yuv4mpegpipe - | python -m pfnl_amd.upscale --checkpoint DIR --deinterlace frame --out-size 1080x1440 \\
+        --primaries auto --out-matrix auto --out-primaries auto - - | ffmpeg -f yuv4mpegpipe -i - -colorspace bt709 -color_primaries bt709 hd.mkv
+
 ``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
 """
 from __future__ import annotations
@@ -20,7 +27,7 @@ import argparse
 import sys
 import time
 
-from . import telecine as _telecine, y4m as _y4m
+from . import colour as _colour, telecine as _telecine, y4m as _y4m
 
 OUT_FORMATS = {8: "i420", 10: "i010"}
 
@@ -39,12 +46,17 @@ def session_keywords(header, **session_kw) -> dict:
     where the caller names none.  ``deinterlace`` ("frame" | "field") becomes ``interlaced`` with the header's field order for an ``It`` / ``Ib``
     stream (and no such key for a progressive one); without it such a stream is a ValueError that names its tag.  ``ivtc`` ("match" |
     "decimate") becomes ``telecine`` with the header's field order instead - the stream is film under 3:2 pulldown (pfnl_amd/telecine.py) -;
-    the two are exclusive.  ValueError for what a Y4M stream cannot hold."""
+    the two are exclusive.  ``out_matrix`` ("auto" | "bt601" | "bt709"), ``out_range`` ("limited" | "full"), ``primaries`` and ``out_primaries``
+    ("auto" | a name of pfnl_amd/colour.py PRIMARIES) become ``open_stream``'s colour keywords, each only where the caller names it
+    (colour.side_keywords; ``scale``, 4 unless given, says how many lines a session without ``out_size`` delivers).  ValueError for what a
+    Y4M stream cannot hold."""
     kw = dict(session_kw)
     for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth", "chroma", "interlaced", "field_order", "telecine"):
         if fixed in kw:
             raise ValueError(f"{fixed} comes from the stream's header")
     kw.setdefault("batch", 1)
+    named = {k: kw.pop(k, None) for k in ("out_matrix", "out_range", "primaries", "out_primaries")}
+    scale = kw.pop("scale", 4)
     rate = kw.pop("deinterlace", None)                # "frame" | "field": what an It / Ib stream needs; a progressive stream ignores it
     if rate not in (None, "frame", "field"):
         raise ValueError(f'deinterlace: None, "frame" or "field", got {rate!r}')
@@ -65,6 +77,8 @@ def session_keywords(header, **session_kw) -> dict:
     if kw.get("matrix", "auto") == "auto":
         kw["matrix"] = auto_matrix(header.height)
     kw["full_range"] = bool(kw.get("full_range")) or header.full_range
+    out_size = kw.get("out_size")
+    kw.update(_colour.side_keywords(header.height, out_size[0] if out_size is not None else scale * header.height, kw["matrix"], **named))
     kw["pixel_format"] = "i420"
     kw["chroma_siting"] = header.siting
     if header.bits == 10:
@@ -102,7 +116,7 @@ def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> i
         out_h, out_w = vs.out_size if vs.out_size is not None else (vs.scale * header.height, vs.scale * header.width)
         out_chroma = kw.get("out_chroma", kw.get("chroma", "420"))
         writer.write_header(header.for_output(out_w, out_h, siting=vs.out_chroma_siting, bits=10 if kw["out_format"] == "i010" else 8,
-                                              sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw["full_range"], chroma=out_chroma,
+                                              sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw.get("out_full_range", kw["full_range"]), chroma=out_chroma,
                                               progressive="interlaced" in kw or "telecine" in kw, double_rate=kw.get("interlaced") == "field",
                                               film_rate=kw.get("telecine") == "decimate"))
 
@@ -166,6 +180,12 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--matrix", choices=("auto", "bt601", "bt709"), default="auto", help="auto: bt601 up to 576 lines, else bt709")
     ap.add_argument("--full-range", action="store_true", help="full-range samples whatever the header says")
+    ap.add_argument("--out-matrix", choices=("auto", "bt601", "bt709"), default=None, help="the output's matrix (default: the input's); auto: bt709 above 576 delivered lines")
+    ap.add_argument("--out-range", choices=("limited", "full"), default=None, help="the output's range (default: the input's)")
+    ap.add_argument("--primaries", choices=("auto",) + _colour.PRIMARIES, default=None,
+                    help="the input's primaries (default: bt709); auto: bt601-525 at 480 / 486 lines, bt601-625 at 576, else bt709")
+    ap.add_argument("--out-primaries", choices=("auto",) + _colour.PRIMARIES, default=None,
+                    help="the output's primaries (default: the input's), converted on the device; auto: bt709 above 576 delivered lines")
     ap.add_argument("--batch", type=int, default=1, help="windows per forward")
     ap.add_argument("--scene-cut", type=_scene_cut, default=None, metavar="THRESHOLD", help="keep windows inside a scene: the cut detector's threshold")
     ap.add_argument("--bits", type=int, choices=(8, 10), default=8, help="10: yuv420p10le out (what a 10-bit source wants)")
@@ -213,7 +233,9 @@ def main(argv=None) -> int:
         upscale(reader, _y4m.Y4MWriter(fout), eng.open_stream, tile=a.tile, batch=a.batch, scene_cut=a.scene_cut, matrix=a.matrix,
                 full_range=a.full_range, out_format=OUT_FORMATS[a.bits], out_size=a.out_size, fit=a.fit, out_chroma_siting=a.out_siting,
                 ensemble=a.ensemble, out_chroma=a.out_chroma, deinterlace=a.deinterlace,
-                ivtc=("match" if a.no_decimate else "decimate") if a.ivtc else None)
+                ivtc=("match" if a.no_decimate else "decimate") if a.ivtc else None, scale=geom.scale,
+                **{k: v for k, v in (("out_matrix", a.out_matrix), ("out_range", a.out_range), ("primaries", a.primaries),
+                                     ("out_primaries", a.out_primaries)) if v is not None})
         fout.flush()
     except (ValueError, PFNLHipError) as e:
         print(f"pfnl_amd.upscale: {e}", file=sys.stderr)
