@@ -768,11 +768,11 @@ int convmerge1(const Fwd& f) {
     }
 }
 
-// forward over device buffers
+// forward over device buffers on `s`; flag_slot: the range-flag word its tail kernel writes (0: synchronous call, 1: asynchronous)
 // `strip` != null: only LR rows [strip->yoff + core0, strip->yoff + core1) of the result are produced (single-clip sharding,
-// pfnl_forward_strip): the non-local block runs its queries [q0, q1) against ALL keys, the trunk runs on the strip + halo.
-int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull, int W, hipStream_t s,
-                   const StripGeom* strip = nullptr, int q0 = 0, int q1 = -1, int flag_slot = 1 /* 0: synchronous call, 1: asynchronous */) {
+// pfnl_forward_strip): the non-local block runs its queries [strip->q0, strip->q1) against ALL keys, the trunk runs on the strip + halo.
+int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull, int W, hipStream_t s, int flag_slot,
+                   const StripGeom* strip = nullptr) {
     const pfnl_config& c = h->cfg;
     const int T = c.num_frames;
     const int H = strip ? strip->Hs : Hfull;                       // rows the trunk buffers hold
@@ -782,7 +782,7 @@ int forward_device(pfnl_handle* h, const float* in, float* out, int B, int Hfull
     const Fwd f{h, pl, s, B, T, B * T, H, W, h->wdev.p, reinterpret_cast<const uint16_t*>(h->wdev16.p), reinterpret_cast<const uint16_t*>(h->wdev16s.p)};
     const float* const wd = h->wdev.p;
 
-    if (int e = nonlocal_block(f, in, Hfull, q0, q1)) return e;
+    if (int e = nonlocal_block(f, in, Hfull, strip ? strip->q0 : 0, strip ? strip->q1 : -1)) return e;
     {   // model/pfnl.py:61-62
         ProfScope ps(h, s, PFNL_K_CONV0);
         if (pl.bf16)
@@ -1358,124 +1358,51 @@ const char* const RANGE_MSG_BF16 =
     "this precision's non-local block and conv0 (inputs on a [0,1] scale, |x| < ~350). precision=fp32 covers the whole fp32 range";
 }  // namespace
 
-int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device, int B,
-                 int H, int W, void* stream) {
-    if (!h || !in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (!h->finalized) return fail(PFNL_ERR_STATE, "pfnl_finalize_weights has not been called");
+// ---- the call frame: what a call of pfnl_forward, pfnl_forward_ensemble or pfnl_forward_tiled does around its body
+
+static int refuse_shape(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return fail(PFNL_ERR_INVALID, "B, H, W must be positive");
     if ((H & 1) || (W & 1))
         return fail(PFNL_ERR_INVALID, "H and W must be even (space_to_depth(2), reference model/pfnl.py:57)");
+    return 0;
+}
+
+// what pfnl_forward and pfnl_forward_ensemble refuse, in the order they report it (pfnl_forward_tiled: the shape and the tiling before the handle)
+static int refuse_call(const pfnl_handle* h, const void* in, const void* out, int B, int H, int W) {
+    if (!h || !in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!h->finalized) return fail(PFNL_ERR_STATE, "pfnl_finalize_weights has not been called");
+    return refuse_shape(B, H, W);
+}
+
+namespace {
+// the forwards enqueued in this scope run on the f32-MFMA kernels (trunk_plan reads the handle's strict_once); cleared on every way out
+struct StrictOnce {
+    pfnl_handle* const h;
+    explicit StrictOnce(pfnl_handle* h_) : h(h_) { h->strict_once = true; }
+    ~StrictOnce() { h->strict_once = false; }
+};
+
+// One call.  body(din, dout, s, slot) enqueues its work on `s` over device pointers; its tail kernels write range-flag word `slot`.
+//  - the stream: the caller's if given.  Else a device-pointer call runs on the LEGACY NULL STREAM itself (what a caller that passes
+//    torch.cuda.current_stream().cuda_stream == 0 means: same-stream ordering with everything it has enqueued and will enqueue) and a call
+//    with a host pointer on the handle's stream.
+//  - a host pointer makes the call synchronous: the input goes through stage_in, the result through stage_out, and the call returns with
+//    `out` filled and the caller's host buffers free.  It owns flag word 0 and reads it once, behind everything the body enqueued
+//    (all members, all runs).  Set = the f16-pipe domain was left somewhere, or the input itself was non-finite: the whole body once more on
+//    the f32-MFMA kernels, whose range is the reference's (the fence is not armed there: still non-finite = so is the reference's result),
+//    one rerun counted; precision=bf16 has no such kernels and returns PFNL_ERR_RANGE.
+//  - a device-pointer call is asynchronous: its body gets the caller's pointers as they are, writes flag word 1 - which pfnl_sync and
+//    pfnl_range_flag read - and the frame neither reads a flag nor blocks.
+extern "C++" template <class Body>
+int run_call(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device, int B, int H, int W, void* stream, Body body) {
     HIPCHK(hipSetDevice(h->cfg.device_id));
     const int T = h->cfg.num_frames, sc = h->cfg.scale;
     const size_t n_in = (size_t)B * T * H * W * 3, n_out = (size_t)B * H * W * sc * sc * 3;
+    const bool sync_call = !in_is_device || !out_is_device;
+    const int slot = sync_call ? 0 : 1;
+    const hipStream_t s = stream ? (hipStream_t)stream : (sync_call ? h->stream : (hipStream_t) nullptr);
     const float* din = (const float*)in;
     float* dout = (float*)out;
-    const bool sync_call = !in_is_device || !out_is_device;     // a host pointer: the call returns with `out` filled
-    const int slot = sync_call ? 0 : 1;                         // whose range flag the tail kernel of this call writes
-    const bool can_rerun = !h->opt.bf16 && !(h->opt.strict || !h->weights_f16_ok);
-    const bool want_graph = !h->prof && (h->opt.graph_mode == 2 || (h->opt.graph_mode == 1 && (size_t)B * T * H * W <= 65536));
-    // stream == NULL: device-pointer calls are launched on the LEGACY NULL STREAM itself (what a caller that passes
-    // torch.cuda.current_stream().cuda_stream == 0 means: same-stream ordering with everything it has enqueued and will
-    // enqueue); host-pointer calls and graph replays (a capture cannot run on the null stream) use the handle's stream.
-    hipStream_t s = stream ? (hipStream_t)stream : ((in_is_device && out_is_device && !want_graph) ? (hipStream_t) nullptr : h->stream);
-    if (want_graph) {
-        if (h->stage_in.ensure(n_in) || h->stage_out.ensure(n_out)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
-        pfnl_handle::GraphEntry* ge = nullptr;
-        for (auto& g : h->graphs)
-            if (g.B == B && g.H == H && g.W == W && g.slot == slot) ge = &g;
-        if (!ge) {
-            h->graphs.push_back({B, H, W, 0, nullptr, nullptr, 0, 0, h->cfg_gen, slot});
-            ge = &h->graphs.back();
-        }
-        if (ge->exec && (ge->alloc_gen != g_alloc_gen.load(std::memory_order_relaxed) || ge->cfg_gen != h->cfg_gen)) {   // buffers moved / weights or options changed
-            // a replay of this graph may still be running on the stream (an asynchronous device-pointer call followed by pfnl_set_option):
-            // whether the runtime defers the destruction of an executing graph depends on its version - wait for it
-            HIPCHK(hipStreamSynchronize(s));
-            hipGraphExecDestroy(ge->exec);
-            hipGraphDestroy(ge->graph);
-            ge->exec = nullptr;
-            ge->graph = nullptr;
-            ge->seen = 0;
-        }
-        if (!ge->exec && ge->seen_cfg_gen != h->cfg_gen) {   // options / weights changed since the eager run: the path to be
-            ge->seen = 0;                                     // captured has not allocated its workspaces / set its attributes yet
-            ge->seen_cfg_gen = h->cfg_gen;
-        }
-        if (!ge->exec && ge->seen >= 1) {
-            // second call with this shape (the first one ran eagerly: workspaces allocated, kernel attributes set)
-            // (no other thread's blocking copy while the capture is open - it would fail and invalidate the capture: common.h CaptureGuard)
-            int fe = 0;
-            hipGraph_t g = nullptr;
-            hipError_t ce = hipSuccess;
-            {
-                pfnl::CaptureGuard guard;
-                HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                fe = forward_device(h, h->stage_in.p, h->stage_out.p, B, H, W, s, nullptr, 0, -1, slot);
-                ce = hipStreamEndCapture(s, &g);
-            }
-            if (fe) return fe;
-            if (ce != hipSuccess || !g) return fail(PFNL_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(ce));
-            hipGraphExec_t ex = nullptr;
-            const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-            if (ie != hipSuccess) {
-                hipGraphDestroy(g);
-                return fail(PFNL_ERR_HIP, std::string("graph instantiate: ") + hipGetErrorString(ie));
-            }
-            ge->graph = g;
-            ge->exec = ex;
-            ge->alloc_gen = g_alloc_gen.load(std::memory_order_relaxed);
-            ge->cfg_gen = h->cfg_gen;
-        }
-        if (ge->exec) {
-            // No stream given: the eager path relies on the legacy default stream's implicit ordering with the handle's
-            // (blocking) stream; a graph launch does not take part in it, so order explicitly in both directions.
-            if (!stream) {
-                if (!h->gev && hipEventCreateWithFlags(&h->gev, hipEventDisableTiming) != hipSuccess)
-                    return fail(PFNL_ERR_HIP, "event creation failed");
-                HIPCHK(hipEventRecord(h->gev, nullptr));
-                HIPCHK(hipStreamWaitEvent(s, h->gev, 0));
-            }
-            if (in_is_device)
-                HIPCHK(hipMemcpyAsync(h->stage_in.p, in, n_in * sizeof(float), hipMemcpyDeviceToDevice, s));
-            else if (int e = stage_h2d(h, h->stage_in.p, in, n_in * sizeof(float), s))
-                return e;
-            HIPCHK(hipGraphLaunch(ge->exec, s));
-            if (out_is_device)
-                HIPCHK(hipMemcpyAsync(out, h->stage_out.p, n_out * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (sync_call) {
-                if (!out_is_device) {
-                    if (int e = stage_d2h(h, out, h->stage_out.p, n_out * sizeof(float), s)) return e;
-                } else {
-                    HIPCHK(hipStreamSynchronize(s));
-                }
-                int flagged = 0;
-                if (int e = range_flag_take(h, 0, &flagged)) return e;
-                if (flagged && can_rerun) {   // once more, eagerly, on the f32-MFMA kernels
-                    h->strict_once = true;
-                    const int e = forward_device(h, h->stage_in.p, h->stage_out.p, B, H, W, s, nullptr, 0, -1, 0);
-                    h->strict_once = false;
-                    if (e) return e;
-                    ++h->range_reruns;
-                    if (out_is_device) {
-                        HIPCHK(hipMemcpyAsync(out, h->stage_out.p, n_out * sizeof(float), hipMemcpyDeviceToDevice, s));
-                        HIPCHK(hipStreamSynchronize(s));
-                    } else if (int e2 = stage_d2h(h, out, h->stage_out.p, n_out * sizeof(float), s)) {
-                        return e2;
-                    }
-                } else if (flagged && h->opt.bf16) {
-                    return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
-                }
-            } else if (!stream) {
-                HIPCHK(hipEventRecord(h->gev, s));
-                HIPCHK(hipStreamWaitEvent(nullptr, h->gev, 0));
-            }
-            h->lastB = B;
-            h->lastH = H;
-            h->lastW = W;
-            return 0;
-        }
-        ge->seen++;
-    }
     if (!in_is_device) {
         if (h->stage_in.ensure(n_in)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
         if (int e = stage_h2d(h, h->stage_in.p, in, n_in * sizeof(float), s)) return e;
@@ -1485,33 +1412,126 @@ int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, in
         if (h->stage_out.ensure(n_out)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
         dout = h->stage_out.p;
     }
-    if (int e = forward_device(h, din, dout, B, H, W, s, nullptr, 0, -1, slot)) return e;
-    if (!out_is_device) {
-        if (int e = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e;
-    } else if (!in_is_device) {
+    if (int e = body(din, dout, s, slot)) return e;
+    if (!sync_call) return 0;
+    const auto deliver = [&]() -> int {
+        if (!out_is_device) return stage_d2h(h, out, dout, n_out * sizeof(float), s);
         HIPCHK(hipStreamSynchronize(s));   // the caller may reuse its host buffer on return
+        return 0;
+    };
+    if (int e = deliver()) return e;
+    int flagged = 0;
+    if (int e = range_flag_take(h, 0, &flagged)) return e;
+    if (!flagged) return 0;
+    if (h->opt.bf16) return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
+    if (h->opt.strict || !h->weights_f16_ok) return 0;   // (these run the f32-MFMA kernels from the start, and arm no fence)
+    {
+        StrictOnce strict(h);
+        if (int e = body(din, dout, s, 0)) return e;
     }
-    if (sync_call) {
-        // a synchronous call: its range flag (slot 0, pinned) is read before it returns; set = the f16-pipe domain was left somewhere
-        // (or the input itself was non-finite): once more on the f32-MFMA kernels, whose range is the reference's
-        int flagged = 0;
-        if (int e = range_flag_take(h, 0, &flagged)) return e;
-        if (flagged && can_rerun) {
-            h->strict_once = true;
-            const int e = forward_device(h, din, dout, B, H, W, s, nullptr, 0, -1, 0);   // (strict: the fence is not armed; still
-            h->strict_once = false;                                                    //  non-finite = so is the reference's result)
-            if (e) return e;
-            ++h->range_reruns;
-            if (!out_is_device) {
-                if (int e2 = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e2;
-            } else {
-                HIPCHK(hipStreamSynchronize(s));
-            }
-        } else if (flagged && h->opt.bf16) {
-            return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
+    ++h->range_reruns;
+    return deliver();
+}
+}  // namespace
+
+// ---- graphs: launch-bound shapes replay the plain forward from a hipGraph captured between the staging buffers (pfnl_handle::GraphEntry)
+
+// *exec: the executable graph of the forward at (B, H, W) whose tail kernel writes flag word `slot`, or null - not yet, run eagerly: the
+// first call at a shape runs eagerly (workspaces allocated, kernel attributes set), the second captures on `s` and replays
+static int graph_for(pfnl_handle* h, int B, int H, int W, int slot, hipStream_t s, hipGraphExec_t* exec) {
+    const int T = h->cfg.num_frames, sc = h->cfg.scale;
+    if (h->stage_in.ensure((size_t)B * T * H * W * 3) || h->stage_out.ensure((size_t)B * H * W * sc * sc * 3))
+        return fail(PFNL_ERR_NOMEM, "staging allocation failed");
+    pfnl_handle::GraphEntry* ge = nullptr;
+    for (auto& g : h->graphs)
+        if (g.B == B && g.H == H && g.W == W && g.slot == slot) ge = &g;
+    if (!ge) {
+        h->graphs.push_back({B, H, W, 0, nullptr, nullptr, 0, 0, h->cfg_gen, slot});
+        ge = &h->graphs.back();
+    }
+    if (ge->exec && (ge->alloc_gen != g_alloc_gen.load(std::memory_order_relaxed) || ge->cfg_gen != h->cfg_gen)) {   // buffers moved / weights or options changed
+        // a replay of this graph may still be running on the stream (an asynchronous device-pointer call followed by pfnl_set_option):
+        // whether the runtime defers the destruction of an executing graph depends on its version - wait for it
+        HIPCHK(hipStreamSynchronize(s));
+        hipGraphExecDestroy(ge->exec);
+        hipGraphDestroy(ge->graph);
+        ge->exec = nullptr;
+        ge->graph = nullptr;
+        ge->seen = 0;
+    }
+    if (!ge->exec && ge->seen_cfg_gen != h->cfg_gen) {   // options / weights changed since the eager run: the path to be
+        ge->seen = 0;                                     // captured has not allocated its workspaces / set its attributes yet
+        ge->seen_cfg_gen = h->cfg_gen;
+    }
+    if (!ge->exec && ge->seen >= 1) {
+        // (no other thread's blocking copy while the capture is open - it would fail and invalidate the capture: common.h CaptureGuard)
+        int fe = 0;
+        hipGraph_t g = nullptr;
+        hipError_t ce = hipSuccess;
+        {
+            pfnl::CaptureGuard guard;
+            HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            fe = forward_device(h, h->stage_in.p, h->stage_out.p, B, H, W, s, slot);
+            ce = hipStreamEndCapture(s, &g);
         }
+        if (fe) return fe;
+        if (ce != hipSuccess || !g) return fail(PFNL_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(ce));
+        hipGraphExec_t ex = nullptr;
+        const hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+        if (ie != hipSuccess) {
+            hipGraphDestroy(g);
+            return fail(PFNL_ERR_HIP, std::string("graph instantiate: ") + hipGetErrorString(ie));
+        }
+        ge->graph = g;
+        ge->exec = ex;
+        ge->alloc_gen = g_alloc_gen.load(std::memory_order_relaxed);
+        ge->cfg_gen = h->cfg_gen;
     }
+    if (!ge->exec) ge->seen++;
+    *exec = ge->exec;
     return 0;
+}
+
+// a replay as a body of the frame: device pointers of the caller's are copied into and out of the staging buffers around the launch.
+// null_order: no stream was given.  The eager path relies on the legacy default stream's implicit ordering with the handle's (blocking)
+// stream; a graph launch does not take part in it, so order explicitly in both directions (a synchronous call waits for `s` itself).
+static int graph_replay(pfnl_handle* h, hipGraphExec_t exec, const float* din, float* dout, int B, int H, int W, hipStream_t s, int slot,
+                        bool null_order) {
+    const int T = h->cfg.num_frames, sc = h->cfg.scale;
+    if (null_order) {
+        if (!h->gev && hipEventCreateWithFlags(&h->gev, hipEventDisableTiming) != hipSuccess)
+            return fail(PFNL_ERR_HIP, "event creation failed");
+        HIPCHK(hipEventRecord(h->gev, nullptr));
+        HIPCHK(hipStreamWaitEvent(s, h->gev, 0));
+    }
+    if (din != h->stage_in.p)
+        HIPCHK(hipMemcpyAsync(h->stage_in.p, din, (size_t)B * T * H * W * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipGraphLaunch(exec, s));
+    if (dout != h->stage_out.p)
+        HIPCHK(hipMemcpyAsync(dout, h->stage_out.p, (size_t)B * H * W * sc * sc * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (null_order && slot == 1) {
+        HIPCHK(hipEventRecord(h->gev, s));
+        HIPCHK(hipStreamWaitEvent(nullptr, h->gev, 0));
+    }
+    h->lastB = B;                                             // (forward_device has not run: pfnl_debug_tap reads these)
+    h->lastH = H;
+    h->lastW = W;
+    return 0;
+}
+
+int pfnl_forward(pfnl_handle* h, const void* in, int in_is_device, void* out, int out_is_device, int B,
+                 int H, int W, void* stream) {
+    if (int e = refuse_call(h, in, out, B, H, W)) return e;
+    const bool want_graph = !h->prof && (h->opt.graph_mode == 2 || (h->opt.graph_mode == 1 && (size_t)B * h->cfg.num_frames * H * W <= 65536));
+    // (a capture cannot run on the null stream: a call that wants a graph and names no stream runs on the handle's, whatever its pointers)
+    return run_call(h, in, in_is_device, out, out_is_device, B, H, W, (stream || !want_graph) ? stream : (void*)h->stream,
+                    [&](const float* din, float* dout, hipStream_t s, int slot) -> int {
+                        hipGraphExec_t exec = nullptr;
+                        if (want_graph && !h->strict_once)   // (the rerun of a flagged call is eager and is not captured)
+                            if (int e = graph_for(h, B, H, W, slot, s, &exec)) return e;
+                        return exec ? graph_replay(h, exec, din, dout, B, H, W, s, slot, !stream)
+                                    : forward_device(h, din, dout, B, H, W, s, slot);
+                    });
 }
 
 // ---- self-ensemble (include/pfnl_hip.h SELF-ENSEMBLE; the rule: pfnl_amd/ensemble.py): the loop around forward_device
@@ -1532,11 +1552,11 @@ static int ensemble_presize(pfnl_handle* h, int B, int H, int W, int n) {
 static int ensemble_device(pfnl_handle* h, const float* din, float* dout, int B, int H, int W, int n, hipStream_t s, int slot) {
     const int T = h->cfg.num_frames, sc = h->cfg.scale;
     if (int e = ensemble_presize(h, B, H, W, n)) return e;
-    if (int e = forward_device(h, din, dout, B, H, W, s, nullptr, 0, -1, slot)) return e;   // member 0 writes acc
+    if (int e = forward_device(h, din, dout, B, H, W, s, slot)) return e;   // member 0 writes acc
     for (int k = 1; k < n; ++k) {
         const bool t = (k & 4) != 0;
         HIPCHK(launch_dihedral(din, h->ens_in.p, B * T, H, W, k, 1.0f, s));
-        if (int e = forward_device(h, h->ens_in.p, h->ens_y.p, B, t ? W : H, t ? H : W, s, nullptr, 0, -1, slot)) return e;
+        if (int e = forward_device(h, h->ens_in.p, h->ens_y.p, B, t ? W : H, t ? H : W, s, slot)) return e;
         HIPCHK(launch_dihedral_accum(dout, h->ens_y.p, B, sc * H, sc * W, k, k == n - 1 ? 1.0f / (float)n : 1.0f, s));
     }
     return 0;
@@ -1546,55 +1566,10 @@ int pfnl_forward_ensemble(pfnl_handle* h, const void* in, int in_is_device, void
                           void* stream) {
     if (n != 1 && n != 2 && n != 4 && n != 8) return fail(PFNL_ERR_INVALID, "ensemble: n must be 1, 2, 4 or 8");
     if (n == 1) return pfnl_forward(h, in, in_is_device, out, out_is_device, B, H, W, stream);
-    if (!h || !in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (!h->finalized) return fail(PFNL_ERR_STATE, "pfnl_finalize_weights has not been called");
-    if (B <= 0 || H <= 0 || W <= 0) return fail(PFNL_ERR_INVALID, "B, H, W must be positive");
-    if ((H & 1) || (W & 1))
-        return fail(PFNL_ERR_INVALID, "H and W must be even (space_to_depth(2), reference model/pfnl.py:57)");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    const int T = h->cfg.num_frames, sc = h->cfg.scale;
-    const size_t n_in = (size_t)B * T * H * W * 3, n_out = (size_t)B * H * W * sc * sc * 3;
-    const float* din = (const float*)in;
-    float* dout = (float*)out;
-    const bool sync_call = !in_is_device || !out_is_device;     // as pfnl_forward: whose range flag, which stream
-    const int slot = sync_call ? 0 : 1;
-    const bool can_rerun = !h->opt.bf16 && !(h->opt.strict || !h->weights_f16_ok);
-    hipStream_t s = stream ? (hipStream_t)stream : ((in_is_device && out_is_device) ? (hipStream_t) nullptr : h->stream);
-    if (!in_is_device) {
-        if (h->stage_in.ensure(n_in)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
-        if (int e = stage_h2d(h, h->stage_in.p, in, n_in * sizeof(float), s)) return e;
-        din = h->stage_in.p;
-    }
-    if (!out_is_device) {
-        if (h->stage_out.ensure(n_out)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
-        dout = h->stage_out.p;
-    }
-    if (int e = ensemble_device(h, din, dout, B, H, W, n, s, slot)) return e;
-    if (!out_is_device) {
-        if (int e = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e;
-    } else if (!in_is_device) {
-        HIPCHK(hipStreamSynchronize(s));   // the caller may reuse its host buffer on return
-    }
-    if (sync_call) {
-        // the flag of all n members, read once behind the last of them; set: the whole ensemble once more on the f32-MFMA kernels
-        int flagged = 0;
-        if (int e = range_flag_take(h, 0, &flagged)) return e;
-        if (flagged && can_rerun) {
-            h->strict_once = true;
-            const int e = ensemble_device(h, din, dout, B, H, W, n, s, 0);
-            h->strict_once = false;
-            if (e) return e;
-            ++h->range_reruns;
-            if (!out_is_device) {
-                if (int e2 = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e2;
-            } else {
-                HIPCHK(hipStreamSynchronize(s));
-            }
-        } else if (flagged && h->opt.bf16) {
-            return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
-        }
-    }
-    return 0;
+    if (int e = refuse_call(h, in, out, B, H, W)) return e;
+    return run_call(h, in, in_is_device, out, out_is_device, B, H, W, stream, [&](const float* din, float* dout, hipStream_t s, int slot) {
+        return ensemble_device(h, din, dout, B, H, W, n, s, slot);
+    });
 }
 
 // ---- tiles (include/pfnl_hip.h TILES; the rule: pfnl_amd/tiles.py; the geometry: tile_geom.h): the loop of runs around the forward
@@ -1636,7 +1611,7 @@ static int tiled_device(pfnl_handle* h, const float* din, float* dout, const pfn
         const int count = total - first < run ? total - first : run;
         HIPCHK(launch_tile_gather(din, h->tile_in.p, g, T, first, count, s));
         if (int e = n > 1 ? ensemble_device(h, h->tile_in.p, h->tile_y.p, count, th, tw, n, s, slot)
-                          : forward_device(h, h->tile_in.p, h->tile_y.p, count, th, tw, s, nullptr, 0, -1, slot))
+                          : forward_device(h, h->tile_in.p, h->tile_y.p, count, th, tw, s, slot))
             return e;
         HIPCHK(launch_tile_scatter(h->tile_y.p, dout, g, sc, first, count, s));
     }
@@ -1648,9 +1623,7 @@ int pfnl_forward_tiled(pfnl_handle* h, const void* in, int in_is_device, void* o
     if (n != 1 && n != 2 && n != 4 && n != 8) return fail(PFNL_ERR_INVALID, "ensemble: n must be 1, 2, 4 or 8");
     if (!t) return pfnl_forward_ensemble(h, in, in_is_device, out, out_is_device, B, H, W, n, stream);
     if (!h || !in || !out) return fail(PFNL_ERR_INVALID, "NULL argument");
-    if (B <= 0 || H <= 0 || W <= 0) return fail(PFNL_ERR_INVALID, "B, H, W must be positive");
-    if ((H & 1) || (W & 1))
-        return fail(PFNL_ERR_INVALID, "H and W must be even (space_to_depth(2), reference model/pfnl.py:57)");
+    if (int e = refuse_shape(B, H, W)) return e;
     if (const char* why = pfnl::tiling_refused(H, W, *t)) return fail(PFNL_ERR_INVALID, why);
     const pfnl::TileGrid g = pfnl::tile_grid(H, W, *t);
     const int total = pfnl::tile_total(g, B);
@@ -1659,50 +1632,9 @@ int pfnl_forward_tiled(pfnl_handle* h, const void* in, int in_is_device, void* o
     if (g.y.count == 1 && g.x.count == 1 && run == total)       // one tile per clip, one run: the forward itself
         return pfnl_forward_ensemble(h, in, in_is_device, out, out_is_device, B, H, W, n, stream);
     if (!h->finalized) return fail(PFNL_ERR_STATE, "pfnl_finalize_weights has not been called");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    const int T = h->cfg.num_frames, sc = h->cfg.scale;
-    const size_t n_in = (size_t)B * T * H * W * 3, n_out = (size_t)B * H * W * sc * sc * 3;
-    const float* din = (const float*)in;
-    float* dout = (float*)out;
-    const bool sync_call = !in_is_device || !out_is_device;     // as pfnl_forward: whose range flag, which stream
-    const int slot = sync_call ? 0 : 1;
-    const bool can_rerun = !h->opt.bf16 && !(h->opt.strict || !h->weights_f16_ok);
-    hipStream_t s = stream ? (hipStream_t)stream : ((in_is_device && out_is_device) ? (hipStream_t) nullptr : h->stream);
-    if (!in_is_device) {
-        if (h->stage_in.ensure(n_in)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
-        if (int e = stage_h2d(h, h->stage_in.p, in, n_in * sizeof(float), s)) return e;
-        din = h->stage_in.p;
-    }
-    if (!out_is_device) {
-        if (h->stage_out.ensure(n_out)) return fail(PFNL_ERR_NOMEM, "staging allocation failed");
-        dout = h->stage_out.p;
-    }
-    if (int e = tiled_device(h, din, dout, g, total, run, n, s, slot)) return e;
-    if (!out_is_device) {
-        if (int e = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e;
-    } else if (!in_is_device) {
-        HIPCHK(hipStreamSynchronize(s));   // the caller may reuse its host buffer on return
-    }
-    if (sync_call) {
-        // the flag of all runs, read once behind the last of them; set: the whole tiled call once more on the f32-MFMA kernels
-        int flagged = 0;
-        if (int e = range_flag_take(h, 0, &flagged)) return e;
-        if (flagged && can_rerun) {
-            h->strict_once = true;
-            const int e = tiled_device(h, din, dout, g, total, run, n, s, 0);
-            h->strict_once = false;
-            if (e) return e;
-            ++h->range_reruns;
-            if (!out_is_device) {
-                if (int e2 = stage_d2h(h, out, dout, n_out * sizeof(float), s)) return e2;
-            } else {
-                HIPCHK(hipStreamSynchronize(s));
-            }
-        } else if (flagged && h->opt.bf16) {
-            return fail(PFNL_ERR_RANGE, RANGE_MSG_BF16);
-        }
-    }
-    return 0;
+    return run_call(h, in, in_is_device, out, out_is_device, B, H, W, stream, [&](const float* din, float* dout, hipStream_t s, int slot) {
+        return tiled_device(h, din, dout, g, total, run, n, s, slot);
+    });
 }
 
 // Single-clip multi-GPU sharding: one rank's horizontal strip of the SR frame.
@@ -1717,14 +1649,13 @@ int pfnl_forward_strip(pfnl_handle* h, const void* in, void* out, int B, int H, 
     int a = row0 - halo, b = row0 + nrows + halo;
     a = a < 0 ? 0 : (a & ~1);                                    // even: space_to_depth(2) rows, Winograd tiles
     b = b > H ? H : ((b + 1) & ~1);
-    const StripGeom g{a, b - a, row0 - a, row0 - a + nrows};
     // non-local block: queries = the packed rows conv0 reads (2 LR rows of margin for its 5x5), keys = the whole frame
     const int W2 = W / 2, H2 = H / 2;
     int qa = (a - 2) >> 1, qb = (b + 2 + 1) >> 1;
     qa = qa < 0 ? 0 : qa;
     qb = qb > H2 ? H2 : qb;
-    hipStream_t s = stream ? (hipStream_t)stream : (hipStream_t) nullptr;
-    return forward_device(h, (const float*)in, (float*)out, B, H, W, s, &g, qa * W2, qb * W2);
+    const StripGeom g{a, b - a, row0 - a, row0 - a + nrows, qa * W2, qb * W2};
+    return forward_device(h, (const float*)in, (float*)out, B, H, W, (hipStream_t)stream, 1 /* asynchronous: the flag word pfnl_sync reads */, &g);
 }
 
 int pfnl_sync(pfnl_handle* h) {

@@ -162,9 +162,11 @@ hipError_t launch_nl_unpack(const float* Xo, float* out, int B, int T, int H, in
 
 // ---- head / tail (misc_kernels.hip) ----------------------------------------------------------
 // A strip of the frame (single-clip multi-GPU sharding): the trunk buffers hold LR rows [yoff, yoff + Hs)
-// of the H-row frame; only rows [core0, core1) (strip-local) of the result are written, at their place in the full output.
+// of the H-row frame; only rows [core0, core1) (strip-local) of the result are written, at their place in the full output.  The non-local
+// block runs the queries [q0, q1) of the packed frame (-1: all of them) against all keys.
 struct StripGeom {
     int yoff, Hs, core0, core1;
+    int q0 = 0, q1 = -1;
 };
 hipError_t launch_conv0(const float* Xo, const float* w75x64, const float* bias, float* out, int B,
                         int T, int H, int W, hipStream_t s, const StripGeom* strip = nullptr, bool force_f32 = false);   // force_f32: the VALU fp32 kernel
