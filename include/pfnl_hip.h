@@ -713,6 +713,32 @@ int pfnl_stream_ensemble(pfnl_stream* s, int n);
  * is off; a tiling that does not fit the session's H x W is PFNL_ERR_INVALID.  Accepted only while no frame of the current sequence has
  * been pushed (else PFNL_ERR_STATE); the setting survives pfnl_stream_reset. */
 int pfnl_stream_tile(pfnl_stream* s, const pfnl_tiling* t);
+/* BARS (additions to version 4; a session that does not call pfnl_stream_bars, or sets mode 0, issues the launches it always issued).  A
+ * letterboxed or pillarboxed frame carries its picture between black bars; this measures where the picture is, on the device, where the
+ * frames already are.  The rule is stated once on the host, pfnl_amd/bars.py; its integer steps once in pfnl_amd/csrc/bars_geom.h:
+ *   luma: the scene sums' - integer BT.601 on the 8-bit scale without its + 16 (black 0, white 219 | 220) at either depth.
+ *   rows[y] = the sum of luma along row y, cols[x] along column x: exact integers, below 2^32 for H, W <= 16384.
+ *   row y is picture iff rows[y] > limit W, column x iff cols[x] > limit H (limit 0 .. 219; 8 is ffmpeg cropdetect's 24 on a Y from 16).
+ *   box = (y0, x0, h, w) from the first to the last picture row and column, whatever lies between; (0, 0, 0, 0) with no picture row or column.
+ *   the kernel (pfnl_amd/csrc/bars.hip): one launch for all frames of a call; a workgroup sums a strip of whole rows, column sums leave it
+ *     as one 32-bit add per column and strip, and the workgroup that finishes a frame last scans both arrays and writes the box.  It
+ *     reads every sample once, in 16-byte words where the rows allow (W a multiple of 16, of 8 at 10 bits, and the pointer aligned), else
+ *     in 4-byte words or single samples, and leaves its scratch words zero for the next launch.
+ *   pfnl_stream_bars: mode 0 off (the default), mode 1: every ring frame is measured as it is admitted - behind the decode, the
+ *     deinterlacer or inverse telecine, on the stream that made it - with `limit` (ignored in mode 0).  Accepted only while no frame of the
+ *     current sequence has been pushed (else PFNL_ERR_STATE); it survives pfnl_stream_reset; a mode other than 0 | 1 or a limit outside
+ *     0 .. 219 is PFNL_ERR_INVALID.  The first call that turns it on allocates the boxes of the ring's slots, the kernel's scratch and
+ *     two pinned host copies; PFNL_ERR_NOMEM leaves nothing half-made and the setting unchanged.
+ *   pfnl_stream_pop_box: the box of the frame the last successful pop delivered.  The boxes travel with the batch as
+ *     pfnl_stream_pop_info's values do: the call waits for nothing.
+ *   pfnl_stream_content_box: the union of the boxes of the frames popped so far in the sequence, and their number.
+ *     Both: PFNL_ERR_STATE in mode 0 or before any frame of the sequence has been popped.
+ * The op hooks pfnl_op_content_box_u8 / _u10 below are the kernel on its own.
+ * Out of scope: acting on a box that changes inside a sequence, a crop decided inside the session (python -m pfnl_amd.upscale --crop
+ * opens the session at the cropped size), windowboxed material whose rows the pillars dilute below the limit. */
+int pfnl_stream_bars(pfnl_stream* s, int mode, int limit);
+int pfnl_stream_pop_box(pfnl_stream* s, int32_t box[4]);
+int pfnl_stream_content_box(pfnl_stream* s, int32_t box[4], long long* frames);
 
 /* Page-locked host buffers (hipHostMalloc / hipHostFree) for the tensors a caller hands to a host-pointer pfnl_forward - the call that
  * replaces sess.run(SR_test, feed_dict={L_test: ...}) (reference model/pfnl.py:252,309): the copy engine then moves them directly, with
@@ -1059,6 +1085,14 @@ int pfnl_op_gather_windows_u10(const uint16_t* ring, float* win, int cap, long l
 int pfnl_op_gather_windows_u10_scenes(const uint16_t* ring, const long long* scene_first_dev, float* win, int cap, long long last, long long first,
                                       int count, int T, int H, int W, void* stream);
 int pfnl_op_scene_sad_u10(const uint16_t* a, const uint16_t* b, int H, int W, unsigned long long* out_dev, void* stream);
+/* The kernel of BARS on its own.  frames [n][H][W][3] uint8 | uint16 at 10 bits (device; any alignment a sample can have) -> box_dev
+ * [n][4] int32 (y0, x0, h, w) and, where given, rows_dev [n][H] and cols_dev [n][W] uint32 (device, 4-byte aligned), exact against
+ * pfnl_amd/bars.py.  One launch for the n frames; it synchronises `stream` (it owns the scratch words).  NULL frames or box_dev, n < 1,
+ * H or W outside 1 .. 16384, a limit outside 0 .. 219 and a misaligned pointer: PFNL_ERR_INVALID before any HIP call. */
+int pfnl_op_content_box_u8(const uint8_t* frames, int n, int H, int W, int limit, int32_t* box_dev /*[n][4]*/,
+                           uint32_t* rows_dev /*[n][H] or NULL*/, uint32_t* cols_dev /*[n][W] or NULL*/, void* stream);
+int pfnl_op_content_box_u10(const uint16_t* frames, int n, int H, int W, int limit, int32_t* box_dev /*[n][4]*/,
+                            uint32_t* rows_dev /*[n][H] or NULL*/, uint32_t* cols_dev /*[n][W] or NULL*/, void* stream);
 /* The six _sited conversion hooks with the subsampling named (CHROMA FORMAT: PFNL_CHROMA_*), ahead of siting; with PFNL_CHROMA_420 each is
  * its _sited twin, refusals included.  fmt names the layout: PFNL_PIX_NV12 / PFNL_PIX_I420 for the u8 hooks, PFNL_PIX_P010 / PFNL_PIX_I010
  * for the u10 ones.  yuv holds n frames of 2 H W (4:2:2) or 3 H W (4:4:4) samples, a surface chroma planes of H rows.  Odd W at 4:2:2, an RGB

@@ -205,6 +205,11 @@ SIGNATURES = {
     "pfnl_op_gather_windows_u10": (_i, [_vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_gather_windows_u10_scenes": (_i, [_vp, _vp, _vp, _i, C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp]),
     "pfnl_op_scene_sad_u10": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "pfnl_op_content_box_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "pfnl_op_content_box_u10": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "pfnl_stream_bars": (_i, [_vp, _i, _i]),
+    "pfnl_stream_pop_box": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "pfnl_stream_content_box": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong)]),
     "pfnl_op_score_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
     "pfnl_op_score_y": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pfnl_comm_get_unique_id": (_i, [_vp]),

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/pfnl_hip.h"
+#include "bars_geom.h"
 #include "capi_internal.h"
 #include "colour_geom.h"
 #include "common.h"
@@ -353,6 +354,23 @@ static int op_nonlocal_block(const float* x, const float* wg, const float* bg, c
     });
     st.run([&] { return pfnl::launch_nl_unpack(dXo, out, B, T, H, W, st.s); });
     return st.finish("non-local block op: ");
+}
+
+// BARS: the kernel on its own, at either depth
+template <typename T>
+static int op_content_box(const T* frames, int n, int H, int W, int limit, int32_t* box_dev, uint32_t* rows_dev, uint32_t* cols_dev, void* stream) {
+    if (!frames || !box_dev) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (n < 1) return fail(PFNL_ERR_INVALID, "content box: n >= 1");
+    if (H < 1 || H > pfnl::BARS_MAX_SIDE || W < 1 || W > pfnl::BARS_MAX_SIDE) return fail(PFNL_ERR_INVALID, "content box: H and W in 1 .. 16384");
+    if (limit < 0 || limit > pfnl::BARS_LIMIT_MAX) return fail(PFNL_ERR_INVALID, "content box: limit in 0 .. 219");
+    if (reinterpret_cast<uintptr_t>(frames) % sizeof(T)) return fail(PFNL_ERR_INVALID, "content box: uint16 samples are 2-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(box_dev) | reinterpret_cast<uintptr_t>(rows_dev) | reinterpret_cast<uintptr_t>(cols_dev)) % 4)
+        return fail(PFNL_ERR_INVALID, "content box: box_dev, rows_dev and cols_dev must be 4-byte aligned");
+    OpStage st(stream);
+    uint32_t* const scratch = st.alloc<uint32_t>(pfnl::bars_scratch_words(n, H, W));
+    st.run([&] { return hipMemsetAsync(scratch, 0, (size_t)n * ((size_t)W + 1) * sizeof(uint32_t), st.s); });   // the column sums and the tickets
+    st.run([&] { return pfnl::launch_content_box(frames, n, H, W, limit, scratch, pfnl::BarsOut{box_dev, rows_dev, cols_dev}, st.s); });
+    return st.finish("content box op: ");
 }
 
 extern "C" {
@@ -1435,6 +1453,16 @@ int pfnl_op_scene_sad_u10(const uint16_t* a, const uint16_t* b, int H, int W, un
     st.run([&] { return hipMemsetAsync(scratch, 0, 2 * sizeof(unsigned long long), st.s); });
     st.run([&] { return pfnl::launch_scene_sad_u10(a, b, (size_t)H * W, scratch, pfnl::SceneDecision{out_dev, nullptr, 0, 0, 0, 0, 0, 0}, st.s); });
     return st.finish("scene sad op: ");
+}
+
+int pfnl_op_content_box_u8(const uint8_t* frames, int n, int H, int W, int limit, int32_t* box_dev, uint32_t* rows_dev, uint32_t* cols_dev,
+                           void* stream) {
+    return op_content_box<uint8_t>(frames, n, H, W, limit, box_dev, rows_dev, cols_dev, stream);
+}
+
+int pfnl_op_content_box_u10(const uint16_t* frames, int n, int H, int W, int limit, int32_t* box_dev, uint32_t* rows_dev, uint32_t* cols_dev,
+                            void* stream) {
+    return op_content_box<uint16_t>(frames, n, H, W, limit, box_dev, rows_dev, cols_dev, stream);
 }
 
 int pfnl_op_resize_u10(const uint16_t* in, int n, int H, int W, int oH, int oW, uint16_t* out, void* stream) {

@@ -17,6 +17,7 @@
 #include <string>
 
 #include "../../include/pfnl_hip.h"
+#include "bars_geom.h"
 #include "capi_internal.h"
 #include "colour_geom.h"
 #include "common.h"
@@ -124,6 +125,15 @@ struct pfnl_stream {
     bool tc_mark[pfnl::TC_CYCLE] = {false, false, false, false, false};   // the marks of the cycle's pushed frames
     bool tc_carry = false;                            // the mark of a dropped last frame, on its way to the next cycle's first
     long long tc_dropped = 0, tc_admitted = 0;        // of the current sequence
+    // the content box (pfnl_stream_bars; bars_geom.h): allocated by the first call that turns it on, with the ring's slots
+    int bars_mode = 0, bars_limit = 0;                // 0 off | 1 every ring frame is measured as it is admitted
+    int32_t* bars_box = nullptr;                      // device: box [cap][4], slot f % cap = frame f's | the kernel's scratch words (zero between launches)
+    int32_t* bars_info[2] = {nullptr, nullptr};       // pinned host copies of box [cap][4], one per output slot: they travel with the batch
+    hipEvent_t bars_ev = nullptr;                     // the newest measurement on the session's stream (device-pointer pushes)
+    bool bars_on_s = false;                           // ... that a measurement on the copy stream has not yet been ordered behind
+    bool has_box = false;                             // what pfnl_stream_pop_box and pfnl_stream_content_box return
+    int32_t pop_box[4] = {0, 0, 0, 0}, seq_box[4] = {0, 0, 0, 0};
+    long long box_frames = 0;
 };
 
 constexpr int TC_WORDS = 16, TC_AT_SAD = 2, TC_AT_D = 4, TC_AT_STATS = 9, TC_AT_DECISION = 12;
@@ -186,6 +196,8 @@ int enqueue(pfnl_stream* s, const Batch& b) {
     } else {
         HIPCHK(pfnl::launch_gather_windows_u8(s->ring, s->win, s->cap, b.last, b.first, b.count, s->T, s->lr_bytes, s->s));
     }
+    if (s->bars_mode)                                 // (every frame up to b.last has been measured, as it has been decided)
+        HIPCHK(hipMemcpyAsync(s->bars_info[b.slot], s->bars_box, 4 * (size_t)s->cap * sizeof(int32_t), hipMemcpyDeviceToHost, s->s));
     // (no tiling: pfnl_forward_ensemble itself, and with 1 member pfnl_forward itself)
     if (int e = pfnl_forward_tiled(s->h, s->win, 1, s->sr, 1, b.count, s->H, s->W, s->tiled ? &s->tiling : nullptr, s->ensemble, s->s)) return e;
     if (int e = s->route.sample_bytes == 2 ? run_route<uint16_t>(s, b) : run_route<uint8_t>(s, b)) return e;
@@ -283,6 +295,19 @@ int decide_scene(pfnl_stream* s, hipStream_t on) {
     return 0;
 }
 
+// frame s->pushed is in its slot on `on`: its content box into the slot's entry, behind whatever put the frame there
+int measure_bars(pfnl_stream* s, hipStream_t on) {
+    const int slot = (int)(s->pushed % s->cap);
+    const uint8_t* const a = s->ring + (size_t)slot * s->in.ring_bytes;
+    uint32_t* const scratch = reinterpret_cast<uint32_t*>(s->bars_box + 4 * (size_t)s->cap);
+    const pfnl::BarsOut out{s->bars_box + 4 * slot, nullptr, nullptr};
+    if (s->set.in_depth == 10)
+        HIPCHK(pfnl::launch_content_box(reinterpret_cast<const uint16_t*>(a), 1, s->H, s->W, s->bars_limit, scratch, out, on));
+    else
+        HIPCHK(pfnl::launch_content_box(a, 1, s->H, s->W, s->bars_limit, scratch, out, on));
+    return 0;
+}
+
 // forgets the sequence: nothing in flight afterwards, options as before the session changed them
 int drop_sequence(pfnl_stream* s) {
     int r = 0;
@@ -299,6 +324,9 @@ int drop_sequence(pfnl_stream* s) {
     s->pushed = s->launched = s->delivered = 0;
     s->ended = false;
     s->mark = s->decided_on_s = s->has_info = false;
+    s->bars_on_s = s->has_box = false;                // (the kernel's scratch words are zero between launches)
+    for (int k = 0; k < 4; ++k) s->pop_box[k] = s->seq_box[k] = 0;
+    s->box_frames = 0;
     s->woven = s->woven_done = 0;                     // (both streams are idle: nothing reads the field store)
     s->woven_mark[0] = s->woven_mark[1] = s->woven_mark[2] = s->il_on_s = false;
     for (bool& m : s->tc_mark) m = false;
@@ -333,6 +361,11 @@ int push_frame(pfnl_stream* s, int is_device, OnDevice&& on_device, OnHost&& on_
             HIPCHK(hipEventRecord(s->scene_ev, s->s));
             s->decided_on_s = true;
         }
+        if (s->bars_mode) {                           // likewise: the frame's box is in its slot's entry ahead of any batch that names it
+            if (int e = measure_bars(s, s->s)) return e;
+            HIPCHK(hipEventRecord(s->bars_ev, s->s));
+            s->bars_on_s = true;
+        }
     } else {
         // the slot's previous frame belongs to batches that have been delivered, so nothing on the session's stream reads it; the copy
         // runs beside the batches in flight and the caller's buffer is free on return
@@ -344,9 +377,15 @@ int push_frame(pfnl_stream* s, int is_device, OnDevice&& on_device, OnHost&& on_
             HIPCHK(hipStreamWaitEvent(s->cs, s->scene_ev, 0));
             s->decided_on_s = false;
         }
+        if (s->bars_mode && s->bars_on_s) {           // (the measurement shares its scratch words as the scene sum does)
+            HIPCHK(hipStreamWaitEvent(s->cs, s->bars_ev, 0));
+            s->bars_on_s = false;
+        }
         if (int e = on_host(dst)) return e;
         if (s->scene_mode)
             if (int e = decide_scene(s, s->cs)) return e;
+        if (s->bars_mode)
+            if (int e = measure_bars(s, s->cs)) return e;
         HIPCHK(hipStreamSynchronize(s->cs));
     }
     s->mark = false;
@@ -384,6 +423,13 @@ int pop_frame(pfnl_stream* s, int is_device, long long* index, int* got, Deliver
         s->info_sad = 0;
     }
     s->has_info = true;
+    if (s->bars_mode) {                               // (copied ahead of the batch's event as well)
+        const int32_t* const box = s->bars_info[b.slot] + 4 * (size_t)(s->delivered % s->cap);
+        for (int k = 0; k < 4; ++k) s->pop_box[k] = box[k];
+        pfnl::bars_union(s->seq_box, box);
+        ++s->box_frames;
+        s->has_box = true;
+    }
     *index = s->delivered++;
     *got = 1;
     if (s->delivered == b.first + b.count) {
@@ -653,6 +699,10 @@ void release(pfnl_stream* s) {
     }
     if (s->scene_first) (void)hipFree(s->scene_first);
     if (s->scene_ev) (void)hipEventDestroy(s->scene_ev);
+    for (int32_t* p : s->bars_info)
+        if (p) (void)hipHostFree(p);
+    if (s->bars_box) (void)hipFree(s->bars_box);
+    if (s->bars_ev) (void)hipEventDestroy(s->bars_ev);
     if (s->yin) (void)hipFree(s->yin);
     if (s->fstore) (void)hipFree(s->fstore);
     if (s->il_ev) (void)hipEventDestroy(s->il_ev);
@@ -1181,6 +1231,59 @@ int pfnl_stream_pop_info(pfnl_stream* s, long long* scene_first, unsigned long l
     if (!s->has_info) return fail(PFNL_ERR_STATE, "pop_info: no frame of this sequence has been popped");
     *scene_first = s->info_first;
     *sad = s->info_sad;
+    return 0;
+}
+
+// The content box of every ring frame.  The boxes have the ring's slots; the kernel's scratch words lie behind them and are zero between
+// launches, so they are zeroed once, here - on the copy stream and waited for, as the scene table is.
+int pfnl_stream_bars(pfnl_stream* s, int mode, int limit) {
+    if (!s) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (mode != 0 && mode != 1) return fail(PFNL_ERR_INVALID, "bars: mode 0 (off) or 1 (every ring frame is measured)");
+    if (mode && (limit < 0 || limit > pfnl::BARS_LIMIT_MAX)) return fail(PFNL_ERR_INVALID, "bars: the limit is a mean luma in 0 .. 219");
+    if (mode && !pfnl::bars_args_ok(s->H, s->W, limit)) return fail(PFNL_ERR_INVALID, "bars: H and W are at most 16384 (the sums are 32-bit)");
+    if (started(s)) return fail(PFNL_ERR_STATE, "bars are set before the first frame of a sequence (pfnl_stream_reset starts the next)");
+    if (mode && !s->bars_box) {
+        HIPCHK(hipSetDevice(s->device));
+        const size_t bytes = (4 * (size_t)s->cap + pfnl::bars_scratch_words(1, s->H, s->W)) * sizeof(int32_t);
+        int32_t *box = nullptr, *info[2] = {nullptr, nullptr};
+        hipEvent_t ev = nullptr;
+        bool ok = hipMalloc(reinterpret_cast<void**>(&box), bytes) == hipSuccess;
+        ok = ok && hipMemsetAsync(box, 0, bytes, s->cs) == hipSuccess && hipStreamSynchronize(s->cs) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+        for (int i = 0; i < 2; ++i)
+            ok = ok && hipHostMalloc(reinterpret_cast<void**>(&info[i]), 4 * (size_t)s->cap * sizeof(int32_t), hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            for (int32_t* p : info)
+                if (p) (void)hipHostFree(p);
+            if (ev) (void)hipEventDestroy(ev);
+            if (box) (void)hipFree(box);
+            return fail(PFNL_ERR_NOMEM, "content box allocation failed");
+        }
+        s->bars_box = box;
+        s->bars_info[0] = info[0];
+        s->bars_info[1] = info[1];
+        s->bars_ev = ev;
+    }
+    s->bars_mode = mode;
+    s->bars_limit = mode ? limit : 0;
+    return 0;
+}
+
+int pfnl_stream_pop_box(pfnl_stream* s, int32_t box[4]) {
+    if (!s || !box) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!s->bars_mode) return fail(PFNL_ERR_STATE, "pop_box: bars are off (pfnl_stream_bars)");
+    if (!s->has_box) return fail(PFNL_ERR_STATE, "pop_box: no frame of this sequence has been popped");
+    for (int k = 0; k < 4; ++k) box[k] = s->pop_box[k];
+    return 0;
+}
+
+int pfnl_stream_content_box(pfnl_stream* s, int32_t box[4], long long* frames) {
+    if (!s || !box || !frames) return fail(PFNL_ERR_INVALID, "NULL argument");
+    if (!s->bars_mode) return fail(PFNL_ERR_STATE, "content_box: bars are off (pfnl_stream_bars)");
+    if (!s->has_box) return fail(PFNL_ERR_STATE, "content_box: no frame of this sequence has been popped");
+    for (int k = 0; k < 4; ++k) box[k] = s->seq_box[k];
+    *frames = s->box_frames;
     return 0;
 }
 

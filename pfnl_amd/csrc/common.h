@@ -216,6 +216,20 @@ hipError_t launch_gather_windows_u10_scenes(const uint16_t* ring, const long lon
 hipError_t launch_scene_sad_u10(const uint16_t* a, const uint16_t* b, size_t npix, unsigned long long* scratch, const SceneDecision& d,
                                 hipStream_t s);
 
+// ---- the content box of RGB frames (bars.hip; the rule: pfnl_amd/bars.py, its integer steps: bars_geom.h) ----
+// frames [n][H][W][3] uint8, or uint16 at 10 bits (a sample above 1023 counts as 1023) -> what BarsOut names, one launch (per 32768
+// frames), any alignment a sample can have: 16-byte reads where the rows allow, else 4-byte ones or single samples.  H, W 1 .. 16384,
+// limit 0 .. 219, else hipErrorInvalidValue.  scratch: bars_scratch_words(n, H, W) 32-bit words, zero before the first launch; every
+// launch leaves the words it needs zero again (launches that share them must not overlap).
+struct BarsOut {
+    int32_t* box;                  // [n][4] y0, x0, h, w
+    uint32_t* rows;                // [n][H] the sums of luma along the rows, or null
+    uint32_t* cols;                // [n][W] ... along the columns, or null
+};
+size_t bars_scratch_words(int n, int H, int W);
+hipError_t launch_content_box(const uint8_t* frames, int n, int H, int W, int limit, uint32_t* scratch, const BarsOut& out, hipStream_t s);
+hipError_t launch_content_box(const uint16_t* frames, int n, int H, int W, int limit, uint32_t* scratch, const BarsOut& out, hipStream_t s);
+
 // ---- YUV 4:2:0 <-> RGB (yuv.hip; the rule: pfnl_amd/yuv.py, 10 bits: pfnl_amd/depth10.py) ----
 // The fifteen integers of yuv.py coefficients(), 14 fractional bits: the one table, computed on the host and passed to the kernels by value.
 struct YuvCoef {

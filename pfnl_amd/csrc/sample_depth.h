@@ -35,6 +35,18 @@ __device__ __forceinline__ int shift_clip(int v) {
     return v >> S;
 }
 
+// Integer BT.601 luma of one RGB pixel on the 8-BIT scale without its + 16 - black is 0, white 219 | 220 - at either depth: pfnl_amd/scene.py
+// luma_u8, and luma_u10 on values clamped onto 1023.  The scene sums (stream.hip) and the content box (bars.hip) read frames through it.
+template <typename T>
+__device__ __forceinline__ unsigned luma601(unsigned r, unsigned g, unsigned b) {
+    if constexpr (sizeof(T) == 1) {
+        return (66u * r + 129u * g + 25u * b + 128u) >> 8;
+    } else {
+        r = r > 1023u ? 1023u : r, g = g > 1023u ? 1023u : g, b = b > 1023u ? 1023u : b;
+        return (66u * r + 129u * g + 25u * b + 512u) >> 10;
+    }
+}
+
 // the widest word, in bytes, that divides N samples of T: the strips are laid out so that a run of N samples is aligned to it in the
 // forms that use words
 template <typename T, int N>

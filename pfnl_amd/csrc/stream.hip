@@ -168,10 +168,7 @@ namespace {
 // on the clamped values, (+ 512) >> 10: luma on the 8-bit scale, so a threshold and a sum mean the same at either depth
 template <typename T>
 __device__ __forceinline__ int luma_of(unsigned r, unsigned g, unsigned b) {
-    if constexpr (sizeof(T) == 1)
-        return (int)((66u * r + 129u * g + 25u * b + 128u) >> 8);
-    else
-        return (int)((66u * clamp10(r) + 129u * clamp10(g) + 25u * clamp10(b) + 512u) >> 10);
+    return (int)luma601<T>(r, g, b);
 }
 
 template <typename T, int NW>

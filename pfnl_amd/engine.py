@@ -268,7 +268,7 @@ class PFNLEngine:
                     full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
                     chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
                  out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, out_matrix=None,
-                    out_full_range=None, primaries="bt709", out_primaries=None, ensemble=1):
+                    out_full_range=None, primaries="bt709", out_primaries=None, bars=None, ensemble=1):
         """A streaming session on this engine (pfnl_stream_open; pfnl_amd/stream.py VideoStream): uint8 LR frames [H,W,3] pushed one at
         a time, uint8 SR frames popped in order, ``batch`` windows per forward.  One open session per engine.  ``scene_cut``: None,
         "manual" or a detector threshold - windows that stay inside a scene (VideoStream).  ``pixel_format`` / ``out_format`` "nv12" or "i420":
@@ -285,11 +285,12 @@ class PFNLEngine:
         frames in, progressive frames into the ring at frame or field rate (pfnl_amd/deinterlace.py; VideoStream).  ``telecine`` None | "match" |
         "decimate" with ``telecine_params``: film under 3:2 pulldown in, its frames into the ring (pfnl_amd/telecine.py; VideoStream).
         ``out_matrix`` / ``out_full_range`` / ``primaries`` / ``out_primaries`` (None: the input's): a colour description per side, the
-        primaries converted on the device where they differ (pfnl_amd/colour.py; VideoStream)."""
+        primaries converted on the device where they differ (pfnl_amd/colour.py; VideoStream).  ``bars``: None, or a limit in 0 .. 219 - every
+        ring frame is measured for letterbox and pillarbox bars on the device (pfnl_amd/bars.py; ``last_info["box"]``, ``content_box``)."""
         from .stream import VideoStream
         return VideoStream(self, H, W, batch, scene_cut, pixel_format, out_format, matrix, full_range, out_size, crop, fit, place, sar, fill,
                            chroma_siting, out_chroma_siting, in_depth, chroma, out_chroma, packing, out_packing, interlaced, field_order,
-                           telecine, telecine_params, out_matrix, out_full_range, primaries, out_primaries, ensemble)
+                           telecine, telecine_params, out_matrix, out_full_range, primaries, out_primaries, bars, ensemble)
 
     def sync(self) -> None:
         """Synchronise the engine's streams; raises if a device-pointer forward left the f16-pipe kernels' range

@@ -469,7 +469,7 @@ class PFNL(VSR):
                     out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0), chroma_siting="left",
                     out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
                  out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, out_matrix=None,
-                    out_full_range=None, primaries="bt709", out_primaries=None, ensemble=1):
+                    out_full_range=None, primaries="bt709", out_primaries=None, bars=None, ensemble=1):
         """A streaming session for frames that are not on disk (a decoder, a capture card, a socket): returns a
         pfnl_amd.stream.VideoStream - push [H,W,3] uint8 LR frames one at a time, get uint8 SR frames back in order, ``batch`` windows
         per forward (the batches of test_video_lr with num_once == batch, hence its bytes).  Restores the checkpoint as the harness
@@ -482,7 +482,7 @@ class PFNL(VSR):
         ``field_order`` ("tff" | "bff"): pushed frames are woven fields and are deinterlaced on the device ahead of the ring, see VideoStream.
         ``telecine`` (None | "match" | "decimate") with ``telecine_params``: film under 3:2 pulldown, matched field by field, see VideoStream.
         ``out_matrix`` / ``out_full_range`` / ``primaries`` ("bt709" | "bt601-525" | "bt601-625") / ``out_primaries``: a colour description per
-        side, see VideoStream.
+        side, see VideoStream.  ``bars`` (None | a limit in 0 .. 219): letterbox and pillarbox bars measured on the device, see VideoStream.
         (A method of its own: the reference has no counterpart.)"""
         import torch
         self._ensure_loaded(False)
@@ -490,7 +490,7 @@ class PFNL(VSR):
             return self._get_engine().open_stream(H, W, batch, scene_cut, pixel_format, out_format, matrix, full_range, out_size, crop, fit, place, sar, fill,
                                                   chroma_siting, out_chroma_siting, in_depth, chroma, out_chroma, packing, out_packing, interlaced,
                                                   field_order, telecine, telecine_params, out_matrix, out_full_range, primaries,
-                                                  out_primaries, ensemble)
+                                                  out_primaries, bars, ensemble)
 
     def test_video_truth(self, path, name='result', reuse=False, part=50):
         """HR pngs in <path>/truth -> blur + decimate (utils.py:169-192) -> SR pngs in <path>/<name>."""

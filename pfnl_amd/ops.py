@@ -1368,3 +1368,31 @@ def conv1_conv10_bf16_ex(x, k1, b1, k10, b10, frames_per_clip, mfma: int = 32, s
                                                  _req16(base, "base"), F // T, T, H, W, int(mfma), n_full, s, q, _stream(x)))
     return out1, base
 
+
+
+# ---- the content box (include/pfnl_hip.h BARS) ------------------------------------------------------------------------------------------------
+def content_box(frames, limit: int = 8, sums: bool = False):
+    """Where the picture of each frame lies inside letterbox or pillarbox bars: frames [n,H,W,3] (or one [H,W,3]) uint8, or uint16 at 10
+    bits, contiguous on the GPU at any alignment -> an int32 tensor [n,4] of boxes (y0, x0, h, w) on the frames' device, exact against
+    pfnl_amd/bars.py frame_box (pfnl_op_content_box_u8 / _u10; one launch for all frames).  ``sums``: also the uint32 sums of luma along
+    the rows [n,H] and the columns [n,W] (bars.line_sums), as ``(boxes, rows, cols)``.  Synchronises."""
+    import torch
+    from . import bars as _bars
+    lib = _capi.load_library()
+    limit = _bars.check_limit(limit)
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype in (torch.uint8, torch.uint16) and frames.is_contiguous()):
+        raise TypeError("frames must be a contiguous uint8 or uint16 tensor on the GPU")
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise ValueError("content_box expects frames [n,H,W,3]")
+    n, H, W = (int(v) for v in frames.shape[:3])
+    if not (1 <= H <= _bars.MAX_SIDE and 1 <= W <= _bars.MAX_SIDE):
+        raise ValueError(f"content_box: H and W in 1 .. {_bars.MAX_SIDE}")
+    box = torch.empty((n, 4), dtype=torch.int32, device=frames.device)
+    rows = torch.empty((n, H), dtype=torch.uint32, device=frames.device) if sums else None
+    cols = torch.empty((n, W), dtype=torch.uint32, device=frames.device) if sums else None
+    hook = lib.pfnl_op_content_box_u8 if frames.dtype == torch.uint8 else lib.pfnl_op_content_box_u10
+    _capi.check(hook(C.c_void_p(frames.data_ptr()), n, H, W, limit, C.c_void_p(box.data_ptr()),
+                     C.c_void_p(rows.data_ptr()) if sums else None, C.c_void_p(cols.data_ptr()) if sums else None, _stream(frames)))
+    return (box, rows, cols) if sums else box

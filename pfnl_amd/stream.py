@@ -250,6 +250,35 @@ def telecine_arguments(telecine=None, field_order="tff", telecine_params=None, H
     return mode, order, _telecine.params(max(int(H) // 2, 1), int(W), par.get("threshold"), par.get("post"), par.get("comb_limit"))
 
 
+def bars_argument(bars=None, H: int = 2, W: int = 2):
+    """The limit of pfnl_stream_bars for open_stream's ``bars`` (None = off: no call), for frames of H x W; ValueError for anything the
+    library would refuse (pfnl_amd/bars.py).  Needs no device."""
+    from . import bars as _bars
+    if bars is None:
+        return None
+    limit = _bars.check_limit(bars)
+    if int(H) > _bars.MAX_SIDE or int(W) > _bars.MAX_SIDE:
+        raise ValueError(f"bars: H and W are at most {_bars.MAX_SIDE}")
+    return limit
+
+
+class PopInfo(tuple):
+    """``last_info`` of a session with ``bars``: the tuple ``(scene_first, sad)`` it always was, and ``info["box"]`` - the content box
+    (y0, x0, h, w) of the frame - beside ``info["scene_first"]`` and ``info["sad"]``."""
+
+    def __new__(cls, scene_first, sad, box):
+        self = super().__new__(cls, (scene_first, sad))
+        self.box = tuple(box)
+        return self
+
+    def __getitem__(self, key):
+        if isinstance(key, str):
+            if key not in ("scene_first", "sad", "box"):
+                raise KeyError(key)
+            return self.box if key == "box" else tuple.__getitem__(self, ("scene_first", "sad").index(key))
+        return tuple.__getitem__(self, key)
+
+
 def output_grid(out_format: str, out_chroma: str = "420") -> Tuple[int, int]:
     """(gy, gx): what the delivered size is a multiple of per axis - 2 along the axes a YUV ``out_format`` subsamples, else 1."""
     chroma_arguments(out_chroma)
@@ -406,6 +435,11 @@ class VideoStream:
     quantises them, and everything behind - size, placement, ``fill``, YUV, packing - is in the output's colours.  ``vs.out_matrix``,
     ``vs.out_full_range``, ``vs.primaries`` and ``vs.out_primaries`` are the resolved values.
 
+    ``bars`` (None | a limit in 0 .. 219; 8 is the usual one): every ring frame - behind the decode, the deinterlacer or inverse telecine -
+    is measured on the device for letterbox and pillarbox bars (pfnl_amd/bars.py); ``vs.last_info["box"]`` is the box (y0, x0, h, w) of
+    the frame the last pop delivered and ``vs.content_box`` the union over the frames popped so far in the sequence (None before the
+    first).  The frames and the SR output are untouched: a crop ahead of the network is the caller's (python -m pfnl_amd.upscale --crop).
+
     ``set_tiling(tile_h, tile_w, pad=0, batch=0)``, before the first frame of a sequence: every batch's forward as runs of overlapping tiles
     (pfnl_amd/tiles.py); ``vs.tiling`` is the setting, None while off."""
 
@@ -413,9 +447,10 @@ class VideoStream:
                  full_range=False, out_size=None, crop=None, fit=None, place=None, sar=(1, 1), fill=(0, 0, 0),
                  chroma_siting="left", out_chroma_siting=None, in_depth=8, chroma="420", out_chroma=None, packing=None,
                  out_packing=None, interlaced=None, field_order="tff", telecine=None, telecine_params=None, out_matrix=None,
-                 out_full_range=None, primaries="bt709", out_primaries=None, ensemble=1):
+                 out_full_range=None, primaries="bt709", out_primaries=None, bars=None, ensemble=1):
         import torch
         self.in_depth = depth_argument(in_depth)    # (before the engine is touched, as every check of an argument)
+        self.bars = bars_argument(bars, H, W)
         col = colour_arguments(matrix, full_range, out_matrix, out_full_range, primaries, out_primaries)
         self.out_matrix = matrix if out_matrix is None else out_matrix
         self.out_full_range = bool(full_range if out_full_range is None else out_full_range)
@@ -529,6 +564,12 @@ class VideoStream:
             except Exception:
                 self.close()
                 raise
+        if self.bars is not None:                   # (None: the session as it always was, and no call)
+            try:
+                _capi.check(self._lib.pfnl_stream_bars(s, 1, self.bars))
+            except Exception:
+                self.close()
+                raise
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self) -> None:
@@ -617,6 +658,16 @@ class VideoStream:
         self.last_info = None
 
     @property
+    def content_box(self):
+        """With ``bars``: the union (y0, x0, h, w) of the content boxes of the frames popped so far in the sequence - (0, 0, 0, 0) while
+        all were black -, or None before the first pop and without ``bars``."""
+        if self.bars is None or self.last_info is None:
+            return None
+        box, n = (C.c_int32 * 4)(), C.c_longlong(0)
+        _capi.check(self._lib.pfnl_stream_content_box(self._handle(), box, C.byref(n)))
+        return tuple(int(v) for v in box)
+
+    @property
     def tiling(self):
         """``(tile_h, tile_w, pad, batch)`` as ``set_tiling`` stored it, or None: whole frames."""
         return getattr(self, "_tiling", None)
@@ -682,6 +733,10 @@ class VideoStream:
                 self.cuts.append(index)
         else:
             self.last_info = (0, 0)
+        if self.bars is not None:
+            box = (C.c_int32 * 4)()
+            _capi.check(self._lib.pfnl_stream_pop_box(s, box))
+            self.last_info = PopInfo(*self.last_info, (int(v) for v in box))
 
     # ---- surfaces: planes with a row pitch (pfnl_amd/surface.py) -------------------------------
     def _planes_struct(self, planes, fmt, H, W, chroma="420", packing=None):

@@ -19,6 +19,13 @@ lines, else the input's.  A DVD to HD, in the colours an HD stream is read as:
     ffmpeg -i dvd.vob -f yuv4mpegpipe - | python -m pfnl_amd.upscale --checkpoint DIR --deinterlace frame --out-size 1080x1440 \\
         --primaries auto --out-matrix auto --out-primaries auto - - | ffmpeg -f yuv4mpegpipe -i - -colorspace bt709 -color_primaries bt709 hd.mkv
 
+Letterbox and pillarbox bars (pfnl_amd/bars.py): ``--crop auto`` reads up to ``--crop-probe`` frames, measures on the device where their
+picture lies (``--crop-limit``: the mean luma a bar stays under), says ``crop Y,X,H,W (from K frames)`` on stderr and opens the session at
+that size; ``--crop Y,X,H,W`` names the rectangle, in input pixels on bars.align()'s grid.  Each frame is then pushed as a window of its
+planes, so the network never sees the bars, and ``--out-size`` / ``--fit`` work on the cropped picture.  A non-anamorphic widescreen DVD:
+
+    ffmpeg -i dvd.vob -f yuv4mpegpipe - | python -m pfnl_amd.upscale --checkpoint DIR --deinterlace frame --crop auto - - | ffmpeg -f yuv4mpegpipe -i - film.mkv
+
 ``upscale()`` is the loop, ``main()`` the command line; nothing here computes.
 """
 from __future__ import annotations
@@ -27,7 +34,7 @@ import argparse
 import sys
 import time
 
-from . import colour as _colour, telecine as _telecine, y4m as _y4m
+from . import bars as _bars, colour as _colour, telecine as _telecine, y4m as _y4m
 
 OUT_FORMATS = {8: "i420", 10: "i010"}
 
@@ -48,8 +55,8 @@ def session_keywords(header, **session_kw) -> dict:
     "decimate") becomes ``telecine`` with the header's field order instead - the stream is film under 3:2 pulldown (pfnl_amd/telecine.py) -;
     the two are exclusive.  ``out_matrix`` ("auto" | "bt601" | "bt709"), ``out_range`` ("limited" | "full"), ``primaries`` and ``out_primaries``
     ("auto" | a name of pfnl_amd/colour.py PRIMARIES) become ``open_stream``'s colour keywords, each only where the caller names it
-    (colour.side_keywords; ``scale``, 4 unless given, says how many lines a session without ``out_size`` delivers).  ValueError for what a
-    Y4M stream cannot hold."""
+    (colour.side_keywords; ``scale``, 4 unless given, says how many lines a session without ``out_size`` delivers - of ``crop_height``
+    lines where a crop ahead of the network leaves fewer than the header's).  ValueError for what a Y4M stream cannot hold."""
     kw = dict(session_kw)
     for fixed in ("pixel_format", "chroma_siting", "sar", "in_depth", "chroma", "interlaced", "field_order", "telecine"):
         if fixed in kw:
@@ -57,6 +64,7 @@ def session_keywords(header, **session_kw) -> dict:
     kw.setdefault("batch", 1)
     named = {k: kw.pop(k, None) for k in ("out_matrix", "out_range", "primaries", "out_primaries")}
     scale = kw.pop("scale", 4)
+    lines = kw.pop("crop_height", None) or header.height
     rate = kw.pop("deinterlace", None)                # "frame" | "field": what an It / Ib stream needs; a progressive stream ignores it
     if rate not in (None, "frame", "field"):
         raise ValueError(f'deinterlace: None, "frame" or "field", got {rate!r}')
@@ -78,7 +86,7 @@ def session_keywords(header, **session_kw) -> dict:
         kw["matrix"] = auto_matrix(header.height)
     kw["full_range"] = bool(kw.get("full_range")) or header.full_range
     out_size = kw.get("out_size")
-    kw.update(_colour.side_keywords(header.height, out_size[0] if out_size is not None else scale * header.height, kw["matrix"], **named))
+    kw.update(_colour.side_keywords(header.height, out_size[0] if out_size is not None else scale * lines, kw["matrix"], **named))
     kw["pixel_format"] = "i420"
     kw["chroma_siting"] = header.siting
     if header.bits == 10:
@@ -100,20 +108,88 @@ def session_keywords(header, **session_kw) -> dict:
     return kw
 
 
-def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> int:
+def frame_planes(frame, header) -> tuple:
+    """(Y, Cb, Cr) of a frame as y4m.Y4MReader yields it: views, nothing is copied."""
+    H, W = header.height, header.width
+    ch, cw = (H // 2 if header.chroma == "420" else H), (W if header.chroma == "444" else W // 2)
+    flat = frame.reshape(-1)
+    return flat[:H * W].reshape(H, W), flat[H * W:H * W + ch * cw].reshape(ch, cw), flat[H * W + ch * cw:].reshape(ch, cw)
+
+
+def window_planes(frame, header, box) -> tuple:
+    """The window ``box`` = (y0, x0, h, w), on bars.align()'s grid, of a frame's planes: strided views for ``push_planes``."""
+    y0, x0, h, w = box
+    sy, sx = (2 if header.chroma == "420" else 1), (1 if header.chroma == "444" else 2)
+    y, cb, cr = frame_planes(frame, header)
+    return (y[y0:y0 + h, x0:x0 + w], cb[y0 // sy:(y0 + h) // sy, x0 // sx:(x0 + w) // sx], cr[y0 // sy:(y0 + h) // sy, x0 // sx:(x0 + w) // sx])
+
+
+def measure_on_device(frames, header, limit, matrix="bt601", full_range=False, chunk=16) -> list:
+    """The content box of every frame of a Y4M stream (pfnl_amd/bars.py), measured on the GPU: decoded as they are - woven frames too:
+    bars are black in both fields - by ``ops.yuv_to_rgb`` / ``yuv_to_rgb_u10`` and boxed by ``ops.content_box``, ``chunk`` frames a launch."""
+    import numpy as np
+    import torch
+    from . import ops
+    decode, fmt = (ops.yuv_to_rgb_u10, "i010") if header.bits == 10 else (ops.yuv_to_rgb, "i420")
+    boxes = []
+    for k in range(0, len(frames), chunk):
+        host = np.stack([np.asarray(f).reshape(-1) for f in frames[k:k + chunk]])
+        packed = torch.from_numpy(host.view(np.int16)).cuda().view(torch.uint16) if header.bits == 10 else torch.from_numpy(host).cuda()
+        rgb = decode(packed.reshape(-1), fmt, header.height, header.width, matrix, full_range, header.chroma, header.siting)
+        boxes += [tuple(b) for b in ops.content_box(rgb, limit).cpu().tolist()]
+    return boxes
+
+
+def resolve_crop(reader, crop, limit=_bars.LIMIT, probe=120, measure=None, matrix="bt601", full_range=False, log=None):
+    """(box or None, the frames read ahead): ``crop`` "auto" reads up to ``probe`` frames, has ``measure(frames, header, limit)`` box them
+    (measure_on_device unless given), applies bars.decide on bars.align()'s grid and says so on ``log``; a rectangle is checked against
+    the frame and that grid (ValueError naming the reason).  None: the whole frame - no crop, the session as it always was."""
+    header = reader.header
+    H, W = header.height, header.width
+    ay, ax = _bars.align(header.chroma, header.interlace in ("t", "b"))
+    ahead = []
+    if crop == "auto":
+        limit = _bars.check_limit(limit)
+        if int(probe) < 1:
+            raise ValueError(f"crop-probe: at least 1 frame, got {probe!r}")
+        while len(ahead) < int(probe):
+            frame = reader.read_frame()
+            if frame is None:
+                break
+            ahead.append(frame)
+        if measure is None:
+            measure = lambda frames, head, lim: measure_on_device(frames, head, lim, matrix, full_range)   # noqa: E731
+        box = _bars.decide(measure(ahead, header, limit) if ahead else [], H, W, ay, ax)
+        print("crop %d,%d,%d,%d (from %d frames)" % (*box, len(ahead)), file=sys.stderr if log is None else log)
+    else:
+        box = _bars.check_crop(crop, H, W, ay, ax)
+    return (None if box == (0, 0, H, W) else box), ahead
+
+
+def upscale(reader, writer, open_stream, tile=None, log=None, crop=None, crop_limit=_bars.LIMIT, crop_probe=120, measure=None,
+            **session_kw) -> int:
     """Every frame of ``reader`` (y4m.Y4MReader) through a session, into ``writer`` (y4m.Y4MWriter); returns the frame count.
     ``open_stream`` is ``PFNLEngine.open_stream`` or anything with its keywords; ``session_kw`` as ``session_keywords`` takes them;
     ``tile`` is ``set_tiling``'s arguments.  The output header is written once the session exists - its raster, siting and aspect are the
-    session's - and frames in index order as ``push`` and ``end`` return them.  One line with frames, seconds and fps goes to ``log``."""
+    session's - and frames in index order as ``push`` and ``end`` return them.  One line with frames, seconds and fps goes to ``log``.
+    ``crop`` ("auto" | (y0, x0, h, w) in input pixels; ``resolve_crop`` with ``crop_limit``, ``crop_probe`` and ``measure``): the session is
+    opened at the cropped size and every frame goes in as a window of its planes (``push_planes``), the frames read ahead first; a crop
+    that is the whole frame, and no ``crop``, is the loop as it always was."""
     header = reader.header
     kw = session_keywords(header, **session_kw)
+    box, ahead = None, []
+    if crop is not None:
+        box, ahead = resolve_crop(reader, crop, crop_limit, crop_probe, measure, kw["matrix"], kw["full_range"], log)
+        if box is not None:
+            kw = session_keywords(header, crop_height=box[2], **session_kw)
+    in_h, in_w = (header.height, header.width) if box is None else box[2:]
     batch = kw.pop("batch")
     t0 = time.perf_counter()
     done = 0
-    with open_stream(header.height, header.width, batch, **kw) as vs:
+    with open_stream(in_h, in_w, batch, **kw) as vs:
         if tile is not None:
             vs.set_tiling(*tile)
-        out_h, out_w = vs.out_size if vs.out_size is not None else (vs.scale * header.height, vs.scale * header.width)
+        out_h, out_w = vs.out_size if vs.out_size is not None else (vs.scale * in_h, vs.scale * in_w)
         out_chroma = kw.get("out_chroma", kw.get("chroma", "420"))
         writer.write_header(header.for_output(out_w, out_h, siting=vs.out_chroma_siting, bits=10 if kw["out_format"] == "i010" else 8,
                                               sar=(1, 1) if kw.get("fit") is not None else header.sar, full_range=kw.get("out_full_range", kw["full_range"]), chroma=out_chroma,
@@ -128,8 +204,12 @@ def upscale(reader, writer, open_stream, tile=None, log=None, **session_kw) -> i
                 writer.write_frame(frame)
                 done += 1
 
-        for frame in reader:
-            deliver(vs.push(frame))
+        def frames():
+            yield from ahead
+            yield from reader
+
+        for frame in frames():
+            deliver(vs.push(frame) if box is None else vs.push_planes(*window_planes(frame, header, box)))
         deliver(vs.end())
     due = reader.frames * (2 if kw.get("interlaced") == "field" else 1)
     if kw.get("telecine") is not None:
@@ -158,6 +238,13 @@ def _tile(text):
     if not 2 <= len(t) <= 4:
         raise argparse.ArgumentTypeError(f"TH,TW[,PAD[,BATCH]], got {text!r}")
     return t
+
+
+def _crop(text):
+    try:
+        return _bars.parse_crop(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
 
 
 def _scene_cut(text):
@@ -201,6 +288,10 @@ def parser() -> argparse.ArgumentParser:
                     help="take an It / Ib stream that carries film under 3:2 pulldown: match the fields and drop the repeat (4/5 of the frames and the rate; needs --batch 2 or more)")
     ap.add_argument("--no-decimate", action="store_true", help="with --ivtc: match the fields and keep every frame")
     ap.add_argument("--tile", type=_tile, default=None, metavar="TH,TW[,PAD[,BATCH]]")
+    ap.add_argument("--crop", type=_crop, default=None, metavar="auto|Y,X,H,W",
+                    help="crop ahead of the network, in input pixels: auto measures the letterbox / pillarbox bars of the first frames on the device")
+    ap.add_argument("--crop-limit", type=int, default=_bars.LIMIT, metavar="L", help="with --crop auto: the mean luma (0 .. 219, black 0) a bar stays under")
+    ap.add_argument("--crop-probe", type=int, default=120, metavar="N", help="with --crop auto: the frames that are measured")
     return ap
 
 
@@ -215,6 +306,9 @@ def main(argv=None) -> int:
                                    interlaced=a.deinterlace is not None or a.ivtc)
         if a.no_decimate and not a.ivtc:
             raise ValueError("--no-decimate goes with --ivtc")
+        if a.crop is not None and a.crop != "auto":   # (ahead of the engine: a bad rectangle needs no device to be named)
+            head = reader.header
+            _bars.check_crop(a.crop, head.height, head.width, *_bars.align(head.chroma, head.interlace in ("t", "b")))
         from . import checkpoint, synth
         from .engine import PFNLEngine
         from .spec import PFNLGeometry
@@ -234,6 +328,7 @@ def main(argv=None) -> int:
                 full_range=a.full_range, out_format=OUT_FORMATS[a.bits], out_size=a.out_size, fit=a.fit, out_chroma_siting=a.out_siting,
                 ensemble=a.ensemble, out_chroma=a.out_chroma, deinterlace=a.deinterlace,
                 ivtc=("match" if a.no_decimate else "decimate") if a.ivtc else None, scale=geom.scale,
+                **({} if a.crop is None else {"crop": a.crop, "crop_limit": a.crop_limit, "crop_probe": a.crop_probe}),
                 **{k: v for k, v in (("out_matrix", a.out_matrix), ("out_range", a.out_range), ("primaries", a.primaries),
                                      ("out_primaries", a.out_primaries)) if v is not None})
         fout.flush()
